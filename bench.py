@@ -20,6 +20,12 @@ actually limits the kernel, priced against the ceiling tools/microbench.hip meas
 (profiles/r02_microbench.json) -- and the measured HBM traffic (`traffic`, `hbm_measured_GBps`).
 `cpu_baseline` times the CPU oracle (a port of the reference shaders; the reference itself
 cannot be built here) on evenly spaced planes of the same frame on the host cores.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what `value` / `ms_per_step` need: set up, warm
+up, time the N steps, print the line.  `--full` adds everything else the line can carry, each with
+runs of its own: the pair-count frame and `roofline`, the host-upload leg (`config.upload_inclusive`),
+the HBM copy probe and `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step computed
+(the frame a caller of the API pulls; a fixed seeded sample of it when the frame is large) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -56,6 +62,10 @@ def parse():
                     help="BASELINE.json configs index (1-based; 4 = the metric's workload), or harness:{tpw,tpw_swapped,vls,hercules,forces}[:yz] = "
                          "the frame the reference's own throughput harness beamforms (tests/throughput.c:443-491): then NOT the metric's workload")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink factor for rehearsal runs (metric is scale 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: pair-count frame + roofline, host-upload leg, HBM copy probe, CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write the last step's frame (a seeded sample of it when large) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU-baseline budget (DAS time summed over its three legs)")
     ap.add_argument("--das-path", type=int, default=0, help="0 auto, 1 general DAS kernel, 2 auto without the LDS-staged kernel (the gather kernel instead), 3 LDS-staged kernel wherever its window bound holds, 4 factored kernel wherever it applies, 6 HERCULES aligned-grid kernel also on narrow grids; flags to add: 16 no channel split, 256 / 512 the block-staged factored kernel (das_tile.hip) on / off")
@@ -75,6 +85,8 @@ def parse():
                     help="override the configuration's interpolation mode (config 5 with cubic = the reference harness's own setting)")
     ap.add_argument("--planes", type=int, default=0, help="profiling aid: beamform only this many centre z-planes (value is then NOT the metric)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.gpus_given = any(a == "--gpus" or a.startswith("--gpus=") for a in sys.argv[1:])
     return args
 
@@ -140,6 +152,8 @@ def main():
     args = parse()
     # torch.cuda.device_count() reads the driver's device list without creating a HIP context (what makes the child launch below legal)
     mode, n_gpus, ordinals = resolve_gpus(args, os.environ, torch.cuda.device_count())
+    if args.dump_outputs and mode in ("spawn", "rank"):
+        raise SystemExit("bench.py: --dump-outputs needs the frame in one process (--gpus 1, or --in-process)")
     if mode == "spawn":
         sys.exit(spawn_ranks(args, sys.argv[1:]))
     world = n_gpus if mode == "rank" else 1
@@ -288,18 +302,19 @@ def main():
                 "tile_window_samples": int(dd.tile_window_samples), "tile_spread_estimate": round(float(dd.tile_spread_estimate), 2),
                 "declined": {str(k): bytes(dd.declined[k]).split(b"\0")[0].decode() for k in range(8) if bytes(dd.declined[k]).split(b"\0")[0]}}
 
-    # one untimed frame with the geometry-only pair count: G of BASELINE.md section 4
-    L.beamformer_hip_enable_pair_counting(1)
-    step()
-    fence()
-    t = P.HipFrameTimings()
-    assert L.beamformer_hip_get_last_frame_timings(C.byref(t)), lib.last_error()
-    pairs_all_devices = int(t.das_pairs)           # in-process: summed over the library's devices
-    if in_process:
-        assert L.beamformer_hip_get_device_frame_timings(0, C.byref(t)), lib.last_error()
-    pairs_local = int(t.das_pairs)
-    taps, sample_bytes, das_path = int(t.das_taps), int(t.das_sample_bytes), int(t.das_path)
-    L.beamformer_hip_enable_pair_counting(0)
+    if args.full:
+        # one untimed frame with the geometry-only pair count: G of BASELINE.md section 4
+        L.beamformer_hip_enable_pair_counting(1)
+        step()
+        fence()
+        t = P.HipFrameTimings()
+        assert L.beamformer_hip_get_last_frame_timings(C.byref(t)), lib.last_error()
+        pairs_all_devices = int(t.das_pairs)           # in-process: summed over the library's devices
+        if in_process:
+            assert L.beamformer_hip_get_device_frame_timings(0, C.byref(t)), lib.last_error()
+        pairs_local = int(t.das_pairs)
+        taps, sample_bytes = int(t.das_taps), int(t.das_sample_bytes)
+        L.beamformer_hip_enable_pair_counting(0)
 
     for _ in range(args.warmup):
         step()
@@ -309,6 +324,10 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lib.get_last_frame(bp, shard_planes=z_count if args.planes else None),
+                     np.array(min_max, dtype=np.float32) if args.config == 5 else None)
 
     # Multi-GPU runs check what the schedule delivered, outside the timed region:
     #  (1) the slab of the last timed frame must be bit-identical to a recomputation from the same RF
@@ -342,6 +361,9 @@ def main():
     n_stage = int(stats.shader_count)
     ids = [int(stats.shader_ids[i]) for i in range(n_stage)]
     das_col = ids.index(int(P.ShaderKind.DAS))
+    t = P.HipFrameTimings()
+    assert L.beamformer_hip_get_last_frame_timings(C.byref(t)), lib.last_error()
+    das_path = int(t.das_path)
     info = P.HipFrameInfo()
     L.beamformer_hip_get_last_frame_info(C.byref(info))
     last_id = int(info.frame_id) - (1 if distributed else 0)      # skip the verification frame
@@ -369,7 +391,7 @@ def main():
     # are copied into one of three pinned slots, cross PCIe on the copy stream while the previous frame computes, and the frame follows.
     # Reported beside `value` (config.upload_inclusive), never as it.
     upload = None
-    if not distributed and n_gpus == 1 and not args.planes:
+    if args.full and not distributed and n_gpus == 1 and not args.planes:
         host_rf = np.ascontiguousarray(acq.rf)
         host_ptr, host_bytes = host_rf.ctypes.data_as(C.c_void_p), host_rf.nbytes
 
@@ -392,19 +414,19 @@ def main():
                           "-> frame, as tests/throughput.c:535-557 measures; `value` above starts from RF resident in HBM"}
 
     if distributed:
-        agg = torch.tensor([elapsed, das_s, float(pairs_local)], dtype=torch.float64, device="cpu" if rehearse else device)
+        agg = torch.tensor([elapsed, das_s, float(pairs_local if args.full else 0)], dtype=torch.float64, device="cpu" if rehearse else device)
         mx = agg.clone()
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         sm = agg.clone()
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
         elapsed, pairs_total = float(mx[0]), int(sm[2].item())
-    else:
+    elif args.full:
         pairs_total = pairs_all_devices
 
     # a measured copy figure next to the 8 TB/s nominal peak (1 GiB device-to-device
     # copies: bytes read + bytes written over the event-timed duration)
     hbm_copy = None
-    if rank == 0 and not args.planes:
+    if args.full and rank == 0 and not args.planes:
         a_buf = torch.empty(1 << 30, dtype=torch.uint8, device=device)
         b_buf = torch.empty_like(a_buf)
         b_buf.copy_(a_buf)
@@ -422,12 +444,6 @@ def main():
         value = voxels_total / (elapsed / args.steps)
         voxel_bytes = 8 if int(info.data_kind) == int(P.DataKind.Float32Complex) else 4
         cw = 4 if bp.coherency_weighting else 0
-        # per launch = rank 0's / device 0's slab; the others are symmetric
-        gather_bytes = pairs_local * taps * sample_bytes
-        bytes_alg = gather_bytes + (X * Y * planes_rank0) * (voxel_bytes + cw)
-        achieved = bytes_alg / das_s / 1e9
-        whole_metric_frame = args.scale == 1.0 and not args.planes and n_gpus == 1
-        traffic, traffic_source = measured_traffic(args.config, KERNEL_NAMES[das_path]) if whole_metric_frame else (None, "not the profiled launch (scale, planes or device count differ)")
         if distributed:
             how = (f"{world} z-slab(s), one process per GPU, RF broadcast via " + ("gloo through the host (one-GPU rehearsal)" if rehearse else "RCCL")
                    + (", broadcast of frame n+1 overlaps frame n" if pipelined else ", serial"))
@@ -461,7 +477,15 @@ def main():
                 "das_path": PATH_NAMES[das_path], "das_plan": das_plan, "slab_verified": verified, "rf_checksum_equal_on_all_ranks": rf_checksum_ok,
                 "stage_ms": stage_ms, **({"device_das_ms": device_das_ms, "devices": devices_info} if device_das_ms else {}),
             },
-            "roofline": {
+        }
+        if args.full:
+            # per launch = rank 0's / device 0's slab; the others are symmetric
+            gather_bytes = pairs_local * taps * sample_bytes
+            bytes_alg = gather_bytes + (X * Y * planes_rank0) * (voxel_bytes + cw)
+            achieved = bytes_alg / das_s / 1e9
+            whole_metric_frame = args.scale == 1.0 and not args.planes and n_gpus == 1
+            traffic, traffic_source = measured_traffic(args.config, KERNEL_NAMES[das_path]) if whole_metric_frame else (None, "not the profiled launch (scale, planes or device count differ)")
+            out["roofline"] = {
                 # what limits the dominant kernel (`binding` prices it): VALU issue for the LDS-staged kernel, the per-CU texture-address path for
                 # the gather kernels.  achieved / peak / frac keep the contract's HBM formula (see contract_note)
                 "bound": {"das_rca_staged_kernel": "valu-issue", "das_hercules_kernel": "valu-issue", "das_tile_kernel": "valu-issue"}.get(KERNEL_NAMES[das_path], "texture-address path (per-lane gathers served by L1)"),
@@ -479,9 +503,8 @@ def main():
                 "model": "G*taps*sizeof(sample) + V*(sizeof(voxel)+4 with CW); logical gather bytes, "
                          "compulsory HBM traffic is ~1e4x smaller (BASELINE.md section 4)",
                 "binding": binding_resource(args.config, KERNEL_NAMES[das_path], gather_bytes, taps * sample_bytes, das_s, pairs_local, das_plan, cw=bool(bp.coherency_weighting)),
-            },
-        }
-        if not args.no_cpu_baseline and n_gpus == 1:
+            }
+        if args.full and not args.no_cpu_baseline and n_gpus == 1:
             out["cpu_baseline"] = cpu_baseline(acq, args.cpu_seconds)
         assert out["n_gpus"] == (args.gpus if (args.gpus_given or not in_process) else len(ordinals)), (out["n_gpus"], args.gpus)
         print(json.dumps(out), flush=True)
@@ -489,6 +512,31 @@ def main():
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 21          # voxels of the seeded sample of a frame too large to write whole
+DUMP_WHOLE_BYTES = 48 << 20    # frames up to this size are written whole
+
+
+def dump_outputs(directory, frame, min_max=None):
+    """What the last timed step computed, as a caller of the API receives it (beamformer_get_last_frames), written as float32 .npy files
+    under `directory`: the whole frame when small, else the centre z-plane plus a fixed seeded sample of voxels (their flat C-order
+    indices in a float64 file beside it) -- at most ~34 MB.  Complex voxels get a trailing axis of 2 (real, imaginary)."""
+    os.makedirs(directory, exist_ok=True)
+
+    def as_real(a):
+        a = np.ascontiguousarray(a)
+        return a.view(np.float32).reshape(a.shape + (2,)) if np.iscomplexobj(a) else a.astype(np.float32, copy=False)
+
+    if frame.nbytes <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(directory, "frame.npy"), as_real(frame))
+    else:
+        index = np.unique(np.random.default_rng(20240607).integers(0, frame.size, DUMP_SAMPLE, dtype=np.int64))
+        np.save(os.path.join(directory, "frame_sample.npy"), as_real(frame.reshape(-1)[index]))
+        np.save(os.path.join(directory, "frame_sample_index.npy"), index.astype(np.float64))
+        np.save(os.path.join(directory, "frame_center_plane.npy"), as_real(frame[frame.shape[0] // 2]))
+    if min_max is not None:
+        np.save(os.path.join(directory, "min_max.npy"), min_max.astype(np.float32))
 
 
 def kernel_source_hash(kernel):

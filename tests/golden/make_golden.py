@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/host_math.npz from the reference's own host math.
+"""Generates tests/golden/host_math.npz (and ref_kaiser_draws.npz) from the reference's own host math.
 
 Runs only in the build container: it loads oracle/_ref/libref_math.so, which oracle/Makefile
 compiles (ROCm clang) from the reference sources in place under /root/reference
@@ -133,6 +133,25 @@ def main():
 
     np.savez_compressed(os.path.join(HERE, "host_math.npz"), **out)
     print("wrote", os.path.join(HERE, "host_math.npz"), os.path.getsize(os.path.join(HERE, "host_math.npz")), "bytes")
+    kaiser_draws(r)
+
+
+def kaiser_draws(r):
+    """the seeded random Kaiser designs of tests/test_host_math.py::test_against_live_reference_when_present, with the reference's taps"""
+    fp = C.POINTER(C.c_float)
+    r.ref_kaiser_low_pass.argtypes = [C.c_float] * 3 + [C.c_int, fp]
+    rng = np.random.default_rng(3)
+    args, taps = [], []
+    for _ in range(20):
+        fs = float(rng.uniform(5e6, 60e6)); fc = float(rng.uniform(0.02, 0.45) * fs)
+        beta = float(rng.uniform(0, 14)); n = int(rng.integers(3, 300))
+        b = np.zeros(n, np.float32)
+        r.ref_kaiser_low_pass(fc, fs, beta, n, b.ctypes.data_as(fp))
+        args.append((fc, fs, beta, n))
+        taps.append(b)
+    path = os.path.join(HERE, "ref_kaiser_draws.npz")
+    np.savez_compressed(path, args=np.array(args, np.float64), **{f"taps_{i}": t for i, t in enumerate(taps)})
+    print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":

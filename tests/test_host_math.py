@@ -144,18 +144,24 @@ def test_das_transforms_and_m4(oracle):
 
 
 def test_against_live_reference_when_present(oracle):
-    """in the build container the compiled reference itself is available: spot-check beyond
-    the committed fixture"""
+    """spot-check beyond the committed fixture: 20 seeded random Kaiser designs against the reference's taps for them
+    (tests/golden/ref_kaiser_draws.npz, recorded by tests/golden/make_golden.py), and against the compiled reference itself
+    where oracle/_ref/libref_math.so is built"""
     from oracle import binding
-    if not os.path.exists(binding.REF_LIBRARY_PATH):
-        pytest.skip("oracle/_ref/libref_math.so not built (no /root/reference here)")
-    r = C.CDLL(binding.REF_LIBRARY_PATH)
-    r.ref_kaiser_low_pass.argtypes = [C.c_float] * 3 + [C.c_int, fp]
+    D = np.load(os.path.join(ROOT, "tests", "golden", "ref_kaiser_draws.npz"))
+    r = None
+    if os.path.exists(binding.REF_LIBRARY_PATH):
+        r = C.CDLL(binding.REF_LIBRARY_PATH)
+        r.ref_kaiser_low_pass.argtypes = [C.c_float] * 3 + [C.c_int, fp]
     rng = np.random.default_rng(3)
-    for _ in range(20):
+    for i in range(20):
         fs = float(rng.uniform(5e6, 60e6)); fc = float(rng.uniform(0.02, 0.45) * fs)
         beta = float(rng.uniform(0, 14)); n = int(rng.integers(3, 300))
-        a, b = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        assert tuple(D["args"][i]) == (fc, fs, beta, n)
+        a = np.zeros(n, np.float32)
         oracle.library().oracle_kaiser_low_pass(fc, fs, beta, n, ptr(a))
-        r.ref_kaiser_low_pass(fc, fs, beta, n, ptr(b))
-        assert np.array_equal(a, b)
+        assert np.array_equal(a, D[f"taps_{i}"])
+        if r is not None:
+            b = np.zeros(n, np.float32)
+            r.ref_kaiser_low_pass(fc, fs, beta, n, ptr(b))
+            assert np.array_equal(a, b)

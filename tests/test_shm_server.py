@@ -6,6 +6,7 @@ lib/ogl_beamformer_lib.c compiled in place by oracle/Makefile (test infrastructu
 travels to the GPU box prebuilt).  The server is ogl_beamforming_amd/ogl_beamformer_server
 (csrc/shm_server.cpp)."""
 import ctypes as C
+import json
 import os
 import re
 import signal
@@ -21,6 +22,7 @@ from tests import cases
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SERVER = os.path.join(ROOT, "ogl_beamforming_amd", "ogl_beamformer_server")
 REF_CLIENT = os.path.join(ROOT, "oracle", "_ref", "libogl_beamformer_lib_ref.so")
+REF_CALLS = os.path.join(ROOT, "tests", "golden", "ref_client_calls.json")
 
 
 def layout():
@@ -114,7 +116,72 @@ def reference_client():
     lib.beamformer_push_data_with_compute.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.beamformer_maximum_rf_data_size.restype = C.c_uint64
     lib.beamformer_maximum_frames_for_simple_parameters.restype = C.c_uint64
+    lib.beamformer_push_focal_vectors.argtypes = [C.POINTER(C.c_float), C.c_uint32]
     return lib
+
+
+class ReplayedClient:
+    """The compiled reference client's answers to one differential test's calls, recorded in order with the server running
+    (tests/golden/ref_client_calls.json: [function, result, last error] per call): stands in for the client where it is not built."""
+
+    def __init__(self, calls):
+        self.calls, self.error = list(calls), 0
+
+    def beamformer_get_last_error(self):
+        return self.error
+
+    def __getattr__(self, name):
+        def call(*args):
+            want, result, self.error = self.calls.pop(0)
+            assert want == name, (want, name)
+            return result
+        return call
+
+
+class RecordingClient:
+    """the live reference client, each answer logged for ReplayedClient"""
+
+    def __init__(self, lib, log):
+        self.lib, self.log = lib, log
+
+    def beamformer_get_last_error(self):
+        return self.lib.beamformer_get_last_error()
+
+    def __getattr__(self, name):
+        fn = getattr(self.lib, name)
+
+        def call(*args):
+            result = fn(*args)
+            self.log.append([name, int(result), int(self.lib.beamformer_get_last_error())])
+            return result
+        return call
+
+
+@pytest.fixture
+def ref_client(request):
+    """the compiled reference client talking to the server where oracle/_ref holds it (REF_CLIENT_RECORD=1 then rewrites this test's
+    entry of tests/golden/ref_client_calls.json); elsewhere its recorded answers, replayed"""
+    name = request.node.name
+    if not os.path.exists(REF_CLIENT):
+        with open(REF_CALLS) as f:
+            client = ReplayedClient(json.load(f)[name])
+        yield client
+        assert not client.calls, f"{len(client.calls)} recorded calls were not made"
+        return
+    request.getfixturevalue("server")
+    if not os.environ.get("REF_CLIENT_RECORD"):
+        yield reference_client()
+        return
+    log = []
+    yield RecordingClient(reference_client(), log)
+    table = {}
+    if os.path.exists(REF_CALLS):
+        with open(REF_CALLS) as f:
+            table = json.load(f)
+    table[name] = log
+    with open(REF_CALLS, "w") as f:
+        json.dump(table, f, sort_keys=True)
+        f.write("\n")
 
 
 def test_protocol_handshake_without_a_device(server):
@@ -174,13 +241,13 @@ def test_reference_client_beamforms_through_the_server(name, server, oracle):
     assert int(P.ShaderKind.DAS) in ids
 
 
-def test_parameter_validation_agrees_with_the_compiled_reference_client(server, bflib):
+def test_parameter_validation_agrees_with_the_compiled_reference_client(ref_client, bflib):
     """Differential test of the drop-in's validation: 400 random parameter sets -- many invalid:
     counts past the limits, stage lists that start wrong, unknown stages and kinds, demodulation
     of complex data -- pushed through the compiled reference client (talking to the server) and
     through this library in process.  Same verdict and same error code every time
     (validate_parameters / validate_pipeline order, lib/ogl_beamformer_lib.c:252-311)."""
-    ref = reference_client()
+    ref = ref_client
     ours = bflib.library()
     rng = np.random.default_rng(41)
     base = cases.make("config1_small")
@@ -213,12 +280,11 @@ def test_parameter_validation_agrees_with_the_compiled_reference_client(server, 
     assert verdicts[True] >= 40 and verdicts[False] >= 40, verdicts       # both outcomes were exercised
 
 
-def test_array_pushes_and_data_size_checks_agree_with_the_reference_client(server, bflib):
+def test_array_pushes_and_data_size_checks_agree_with_the_reference_client(ref_client, bflib):
     """the remaining client-side checks (lib .c:438-464 array pushes, :410-429 filters, :503-511 data
     sizes, :239-250 block reservation), same differential arrangement"""
-    ref = reference_client()
+    ref = ref_client
     ours = bflib.library()
-    ref.beamformer_push_focal_vectors.argtypes = [C.POINTER(C.c_float), C.c_uint32]
     rng = np.random.default_rng(43)
 
     def both(name, *args):

@@ -77,7 +77,7 @@ def main():
     args = ap.parse_args()
     out = os.path.abspath(args.out)
     os.makedirs(out, exist_ok=True)
-    bench = ["python3", os.path.join(ROOT, "bench.py"), "--config", str(args.config), "--steps", "1", "--warmup", "0",
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--full", "--config", str(args.config), "--steps", "1", "--warmup", "0",
              "--no-cpu-baseline", "--das-path", str(args.das_path)]
     if args.planes:
         bench += ["--planes", str(args.planes)]

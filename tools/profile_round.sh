@@ -29,19 +29,19 @@ cp profiles/das_traffic.json profiles/${R}_das_bound.json profiles/${R}_pmc_tile
 exit 0
 fi
 # ---- part "bench" (expects profiles/${R}_microbench.json, das_traffic.json, ${R}_das_bound.json and ${R}_pmc_tile_cfg2.json of part "pmc" in the tree)
-timeout -k 10 400 python bench.py > $OUT/profiles/${R}_bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full > $OUT/profiles/${R}_bench.json 2> $OUT/bench.err
 cut -c1-400 $OUT/profiles/${R}_bench.json
 for c in 1 2 3 5; do
-  timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err
+  timeout -k 10 300 python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err
 done
-timeout -k 10 300 python bench.py --config 5 --interpolation cubic --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_cubic.json 2> $OUT/bench_cfg5_cubic.err
-timeout -k 10 300 python bench.py --das-path 2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg4_gather.json 2> $OUT/bench_cfg4_gather.err
+timeout -k 10 300 python bench.py --full --config 5 --interpolation cubic --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_cubic.json 2> $OUT/bench_cfg5_cubic.err
+timeout -k 10 300 python bench.py --full --das-path 2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg4_gather.json 2> $OUT/bench_cfg4_gather.err
 for k in tpw tpw_swapped vls hercules forces; do
-  timeout -k 10 200 python bench.py --config harness:$k --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_harness_$k.json 2> $OUT/bench_harness_$k.err
-  timeout -k 10 200 python bench.py --config harness:$k --das-path 1 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_harness_${k}_general.json 2> $OUT/last_leg.err
+  timeout -k 10 200 python bench.py --full --config harness:$k --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_harness_$k.json 2> $OUT/bench_harness_$k.err
+  timeout -k 10 200 python bench.py --full --config harness:$k --das-path 1 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_harness_${k}_general.json 2> $OUT/last_leg.err
 done
 PYTHONPATH=. timeout -k 10 300 python tools/tile_threshold.py --json $OUT/profiles/${R}_tile_threshold.json > $OUT/tile_threshold.log 2>&1
-timeout -k 10 300 python bench.py --in-process --devices 0,0 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_inprocess_0_0.json 2> $OUT/bench_inprocess.err
+timeout -k 10 300 python bench.py --full --in-process --devices 0,0 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_inprocess_0_0.json 2> $OUT/bench_inprocess.err
 python3 - $R <<'PY'
 import json, sys
 R = sys.argv[1]
@@ -69,12 +69,12 @@ for k in ("tpw", "tpw_swapped", "vls", "hercules", "forces"):
 json.dump(h, open("gpurun_out/" + R + "/profiles/" + R + "_harness.json", "w"), indent=1)
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o fast -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/profiles/${R}_bench_under_rocprof.json 2> $OUT/rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o fast -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/profiles/${R}_bench_under_rocprof.json 2> $OUT/rocprof.err
 for k in tpw hercules forces; do
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$k -o harness_$k -- python3 $ROOT/bench.py --config harness:$k --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_harness_${k}_rocprof.json 2> $OUT/rocprof_$k.err
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$k -o harness_$k -- python3 $ROOT/bench.py --full --config harness:$k --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_harness_${k}_rocprof.json 2> $OUT/rocprof_$k.err
 done
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -o cfg2 -- python3 $ROOT/bench.py --config 2 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_cfg2_rocprof.json 2> $OUT/rocprof2.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats5 -o cfg5 -- python3 $ROOT/bench.py --config 5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_rocprof.json 2> $OUT/rocprof5.err
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -o cfg2 -- python3 $ROOT/bench.py --full --config 2 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_cfg2_rocprof.json 2> $OUT/rocprof2.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats5 -o cfg5 -- python3 $ROOT/bench.py --full --config 5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_rocprof.json 2> $OUT/rocprof5.err
 cd $ROOT
 for n in fast cfg2 cfg5 harness_tpw harness_hercules harness_forces; do f=$(find $OUT -name "${n}_kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/profiles/${R}_${n}_kernel_stats.csv; done
 python3 tools/kernel_resources.py --json $OUT/profiles/${R}_kernel_resources.json > $OUT/kernel_resources.log 2>&1 || true

@@ -56,7 +56,7 @@ cd $ROOT
 NAMES=${VARIANTS:-base one_block pair_u quad_u oct_u hex_u quad_v quad_uv plane}
 for name in $NAMES; do
   if [ $name = base ]; then unset OGL_BEAMFORMER_LIB; else export OGL_BEAMFORMER_LIB=$V/libogl_$name.so; fi
-  timeout -k 10 200 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+  timeout -k 10 200 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_$name.json 2> $OUT/bench_$name.err
   timeout -k 10 400 python3 tools/pmc_das.py --config 4 --groups 7,9 --timeout 150 --out $OUT/pmc_$name > $OUT/pmc_$name.log 2>&1
   echo "$name done"
 done
