@@ -165,6 +165,12 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_frame_min_max(float out_min_max[2]
  * implementation.  out_size >= the 64-byte-rounded frame size. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_sum_last_frames(uint32_t count, void *out, uint64_t out_size);
 
+/* Copy of the buffer the newest frame's DAS stage read -- the RF slot when no stage runs before DAS, else the last pre-DAS
+ * stage's output -- to host memory: [channel][transmit][sample], channel_count x acquisition_count x das_samples elements
+ * (BeamformerHipPlan), f32 or f32 complex as the plan says (iq_pipeline).  Valid until the next push.  Returns 0 when size
+ * differs from that, when there is no such frame, or with several devices (beamformer_hip_set_devices). */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_copy_das_input(void *out, uint64_t size);
+
 /* Display reduction of the newest frame, the step on the far side of the path: the per-voxel
  * intensity the reference's render shader computes (sample_value, shaders/render_3d.frag.glsl:
  * 50-73; defaults threshold 55 dB, gamma 1, dynamic range 50 dB, ui.c:880-883): |v| clamped to
@@ -223,7 +229,9 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_das_path(uint32_t mode);
  *                           (BeamformerHipFrameTimings::staged_window_violations)
  *   STAGED_NOUNIFORM        transmit tables in LDS also where the wave-uniform (global table) form applies
  *   STAGED_TABLE_CAP=bytes  largest global transmit table taken (default 2 GiB; 0: always the LDS-table fallback)
- *   DEBUG                   one line per staged plan on stderr */
+ *   DEBUG                   one line per staged plan on stderr
+ *   SCRATCH_POISON          both intermediate buffers and the frame's ring slot filled with 0xFF bytes (NaN in binary16 and f32)
+ *                           at the start of every frame: an element a stage reads without the frame having written it turns into NaN */
 
 /* ---- ZBP acquisition files (external/zemp_bp.h; loader tests/throughput.c:135-374) ----
  * Host only, no device needed.  The reference keeps this loader in its throughput harness;

@@ -107,7 +107,7 @@ def matched_chirp_filter(fs, duration, fmin, fmax, complex_taps=True):
 
 
 def _base_parameters(C, A, S, points, kind, data_kind, stages, fs, fd, pitch, interp, f_number, cw,
-                     voxel_transform, xdc_transform, time_offset=0.0, decode=0, raw_pad=0, contrast=0):
+                     voxel_transform, xdc_transform, time_offset=0.0, decode=0, raw_pad=0, contrast=0, decimation=1):
     bp = P.SimpleParameters()
     bp.das_voxel_transform[:] = [float(v) for v in voxel_transform]
     bp.xdc_transform[:] = [float(v) for v in xdc_transform]
@@ -125,7 +125,7 @@ def _base_parameters(C, A, S, points, kind, data_kind, stages, fs, fd, pitch, in
     bp.f_number = f_number
     bp.interpolation_mode = int(interp)
     bp.coherency_weighting = 1 if cw else 0
-    bp.decimation_rate = 1
+    bp.decimation_rate = decimation
     bp.contrast_mode = contrast
     bp.emission_parameters.kind = 0
     bp.emission_parameters.sine.cycles = 2
@@ -202,7 +202,7 @@ def _rca_delays(bp, point, angles_deg, depths, orient):
 def rca(name, C, A, S, points, lo, hi, *, seed, data_kind=P.DataKind.Int16, interp=P.InterpolationMode.Linear,
         cw=False, f_number=1.0, pitch=0.3e-3, fs=25e6, fd=6.25e6, orientation=0x22, angles=None,
         depths=None, single=False, demodulate=True, kind=P.AcquisitionKind.RCA_TPW, scatterers=None,
-        noise=True, channel_shuffle=False, raw_pad=0, contrast=False, stages=None, plane=None, plane_offset=0.0):
+        noise=True, channel_shuffle=False, raw_pad=0, contrast=False, stages=None, plane=None, plane_offset=0.0, decimation=1, decode=0):
     """Row-column / linear array, plane or diverging waves (configs 1, 2, 4)."""
     rng = np.random.default_rng(seed)
     vt = _voxel_transform(points, lo, hi, plane, plane_offset)
@@ -213,7 +213,7 @@ def rca(name, C, A, S, points, lo, hi, *, seed, data_kind=P.DataKind.Int16, inte
         stages = ([P.ShaderKind.Demodulate] if demodulate else [P.ShaderKind.Decode]) + [P.ShaderKind.DAS]
     demodulate = P.ShaderKind.Demodulate in stages
     bp = _base_parameters(C, A, S, points, kind, data_kind, list(stages), fs, fd, (pitch, pitch), interp, f_number, cw,
-                          vt, xt, raw_pad=raw_pad, contrast=1 if contrast else 0)
+                          vt, xt, raw_pad=raw_pad, contrast=1 if contrast else 0, decimation=decimation, decode=decode)
     if angles is None:
         angles = np.zeros(A) if A == 1 else np.linspace(-15.0, 15.0, A)
     if depths is None:
@@ -256,14 +256,14 @@ def rca(name, C, A, S, points, lo, hi, *, seed, data_kind=P.DataKind.Int16, inte
 def hercules(name, C, A, S, points, lo, hi, *, seed, data_kind=P.DataKind.Int16, interp=P.InterpolationMode.Linear,
              cw=False, f_number=1.0, pitch=0.3e-3, fs=25e6, fd=6.25e6, orientation=0x12, focal=(0.0, np.inf),
              stages=(P.ShaderKind.Decode, P.ShaderKind.DAS), decode=1, kind=P.AcquisitionKind.HERCULES,
-             sparse=None, filters=None, noise_sigma=None, plane=None, plane_offset=0.0):
+             sparse=None, filters=None, noise_sigma=None, plane=None, plane_offset=0.0, decimation=1):
     """2-D aperture: receive channel along one axis x decoded transmit element along the
     other (configs 3, 5; das.glsl:233-286)."""
     rng = np.random.default_rng(seed)
     vt = _voxel_transform(points, lo, hi, plane, plane_offset)
     xt = translation((C - 1) / 2 * pitch, (A - 1) / 2 * pitch, 0.0)
     bp = _base_parameters(C, A, S, points, kind, data_kind, list(stages), fs, fd, (pitch, pitch), interp, f_number, cw,
-                          vt, xt, decode=decode)
+                          vt, xt, decode=decode, decimation=decimation)
     bp.single_focus = 1
     bp.single_orientation = 1
     bp.transmit_receive_orientation = orientation
@@ -284,13 +284,13 @@ def hercules(name, C, A, S, points, lo, hi, *, seed, data_kind=P.DataKind.Int16,
 
 def forces(name, C, A, S, points, lo, hi, *, seed, data_kind=P.DataKind.Int16, interp=P.InterpolationMode.Linear,
            cw=False, f_number=1.0, pitch=0.3e-3, fs=25e6, fd=6.25e6, kind=P.AcquisitionKind.FORCES,
-           stages=(P.ShaderKind.Decode, P.ShaderKind.DAS), decode=1, sparse=None, readi_groups=0, readi_group=0):
+           stages=(P.ShaderKind.Decode, P.ShaderKind.DAS), decode=1, sparse=None, readi_groups=0, readi_group=0, decimation=1):
     """FORCES / UFORCES / READI (das.glsl:288-366): imaging plane x-z."""
     rng = np.random.default_rng(seed)
     vt = _voxel_transform(points, lo, hi)
     xt = translation((C - 1) / 2 * pitch, (C - 1) / 2 * pitch, 0.0)
     bp = _base_parameters(C, A, S, points, kind, data_kind, list(stages), fs, fd, (pitch, pitch), interp, f_number, cw,
-                          vt, xt, decode=decode)
+                          vt, xt, decode=decode, decimation=decimation)
     bp.single_focus = 1
     bp.single_orientation = 1
     bp.transmit_receive_orientation = 0x22

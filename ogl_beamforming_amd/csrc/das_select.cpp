@@ -35,7 +35,7 @@ const char *das_kernel_name(int path)
 /* ---------------------------------------------------------------- hooks */
 
 static Hooks g_hooks;
-static const char *const g_hook_names[] = {"STAGED_SHAPE", "STAGED_CHECKED", "STAGED_NOUNIFORM", "STAGED_TABLE_CAP", "DEBUG", nullptr};
+static const char *const g_hook_names[] = {"STAGED_SHAPE", "STAGED_CHECKED", "STAGED_NOUNIFORM", "STAGED_TABLE_CAP", "DEBUG", "SCRATCH_POISON", nullptr};
 const char *const *hook_names() { return g_hook_names; }
 
 static bool apply_hook(Hooks &h, const char *name, const char *value)
@@ -50,6 +50,7 @@ static bool apply_hook(Hooks &h, const char *name, const char *value)
 	else if (!std::strcmp(name, "STAGED_NOUNIFORM")) h.staged_nouniform = on;
 	else if (!std::strcmp(name, "STAGED_TABLE_CAP")) h.staged_table_cap = on ? std::strtoull(value, nullptr, 0) : (2ull << 30);
 	else if (!std::strcmp(name, "DEBUG"))            h.debug = on;
+	else if (!std::strcmp(name, "SCRATCH_POISON"))   h.scratch_poison = on;
 	else return false;
 	return true;
 }

@@ -1,6 +1,6 @@
 /* das_select.h -- which DAS kernel a frame runs, and why: ONE table of rules, host only (no HIP call), shared by the executor
  * (which launches what it says), beamformer_hip_describe_das (which reports it, also without a device) and the tests (which ask
- * instead of restating the rules).  Also the library's five diagnostic switches (beamformer_hip_set_hook). */
+ * instead of restating the rules).  Also the library's six diagnostic switches (beamformer_hip_set_hook). */
 #ifndef BF_DAS_SELECT_H
 #define BF_DAS_SELECT_H
 
@@ -37,6 +37,9 @@ struct Hooks {
 	bool        staged_nouniform = false;      /* STAGED_NOUNIFORM: transmit tables in LDS also where the wave-uniform form applies */
 	uint64_t    staged_table_cap = 2ull << 30; /* STAGED_TABLE_CAP=bytes: largest global transmit table taken (0 forces the fallback) */
 	bool        debug = false;                 /* DEBUG: one line per staged plan on stderr */
+	bool        scratch_poison = false;        /* SCRATCH_POISON: both intermediate buffers and the frame's ring slot filled with 0xFF bytes (a NaN
+	                                              in binary16 and in f32) at the start of every frame, so that whatever a stage reads without
+	                                              this frame having written it turns into NaN (executor.cpp) */
 };
 Hooks &hooks();
 bool   set_hook(const char *name, const char *value);       /* value null or "" = unset; false: unknown name */

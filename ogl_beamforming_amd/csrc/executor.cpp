@@ -193,6 +193,7 @@ static void release_one_device(Device &d)
 	d.ring_next_offset = 0; d.frame_counter = 0; d.rf_index = 0;
 	d.have_sample = false; d.last_sampled_frame = 0; d.last_sampled_block = 0; d.replan_frame = 0;
 	d.last_rf = nullptr; d.last_rf_bytes = 0; d.last_rf_slot = 0; d.peer_access = 2;
+	d.das_input = nullptr; d.das_input_bytes = 0;
 	d.device = -1;
 }
 
@@ -426,6 +427,15 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 	int toggle = 0;
 	bool ok = true, das_segment_done = false;
 	uint32_t das_path = 0;
+	d.das_input = nullptr; d.das_input_bytes = 0;
+
+	/* hook SCRATCH_POISON: both intermediate buffers, and below the frame's ring slot once next_frame has placed it (nothing writes
+	 * it before the DAS stage), are filled with 0xFF bytes -- NaN in binary16 and in f32 -- so that an element a stage reads without
+	 * this frame having written it shows up as NaN.  Unset: no memset, no launch. */
+	const bool poison = hooks().scratch_poison;
+	if (poison)
+		for (DeviceBuffer &b : d.scratch)
+			if (b.ptr) ok &= HIP_OK(hipMemsetAsync(b.ptr, 0xFF, b.size, s));
 
 	for (size_t i = 0; i < plan.stages.size() && ok; i++) {
 		const Stage &st = plan.stages[i];
@@ -500,6 +510,8 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 			FrameRecord *f = next_frame(points, plan.iq_pipeline, block);
 			if (!f) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 			f->timing_slot = (int)(f->id % kTimingSlots);
+			if (poison && f->bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + f->offset, 0xFF, f->bytes, s));
+			d.das_input = cur; d.das_input_bytes = (uint64_t)Sd * A * C * (plan.iq_pipeline ? 8u : 4u);   /* [channel][transmit][sample] */
 			if (zcount == 0) {           /* more devices than planes: this device holds an empty slab of the frame */
 				t.das_voxels = 0; t.das_taps = 0; t.das_sample_bytes = 0; t.das_path = 0; t.frame_id = f->id;
 				break;
@@ -1184,6 +1196,24 @@ static bool newest_layout(Context &c, uint64_t offsets[kMaxDevices], uint64_t pe
 		total += (uint64_t)f.points[0] * f.points[1] * f.points[2] * per_voxel;
 	}
 	return true;
+}
+
+/* beamformer_hip_copy_das_input: the buffer the newest frame's DAS stage read, [channel][transmit][sample]; one device only */
+bool copy_das_input(void *out, uint64_t out_size)
+{
+	Context &c = g_context;
+	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	Device &d = c.devices[0];
+	if (!newest_record(d) || !d.das_input || out_size != d.das_input_bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	/* a parameter push since that frame may have regrown (reallocated) the buffer: then there is nothing to copy */
+	bool live = false;
+	for (const DeviceBuffer &b : d.scratch) live |= b.ptr == d.das_input && b.size >= out_size;
+	for (const DeviceBuffer &b : d.rf)      live |= b.ptr == d.das_input && b.size >= out_size;
+	if (!live) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && HIP_OK(hipMemcpyAsync(out, d.das_input, out_size, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
+	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
 }
 
 bool frame_min_max(float out[2])

@@ -506,6 +506,12 @@ uint32_t beamformer_hip_frame_min_max(float out_min_max[2])
 	return frame_min_max(out_min_max);
 }
 
+uint32_t beamformer_hip_copy_das_input(void *out, uint64_t size)
+{
+	if (!out) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	return copy_das_input(out, size);
+}
+
 uint32_t beamformer_hip_sum_last_frames(uint32_t count, void *out, uint64_t out_size)
 {
 	if (!out) return set_error(BeamformerLibErrorKind_InvalidAccess);

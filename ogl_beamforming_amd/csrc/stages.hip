@@ -412,28 +412,33 @@ __global__ __launch_bounds__(TRANSPOSE ? 1024 : 256) void filter_kernel(const Bf
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
+	/* filter.glsl:115 computes out_sample < S / D of the S samples Decode and DAS then read; the reference's buffers are cleared, so
+	 * with D > 1 samples [S / D, S) of every row are stored as zeros (the grid has a thread for each) -- never what an earlier frame
+	 * left in the buffer */
 	const uint32_t out_sample = wg * 64 + lane;
 	[[maybe_unused]] f32x2 *tile = reinterpret_cast<f32x2 *>(filter_lds + (size_t)kFilterTransposeWaves * window * 2);   /* TRANSPOSE: [64][16] */
-	if (out_sample < a.sample_count / D) {                            /* filter.glsl:115 */
+	if (out_sample < a.sample_count) {
 		f32x2 result = {0.f, 0.f};
-		const float *x = w + 2 * (size_t)(D * lane);
-		/* (unrolled: the taps' LDS reads and coefficient loads of eight turns are issued together and waited for once -- scalar loads and LDS
-		 * reads share one counter, so a turn of its own waits out both latencies 36 times per output; the sums keep their order) */
-		if (a.complex_filter && complex_sample) {
-			#pragma unroll 8
-			for (uint32_t j = 0; j < L; j++) {
-				float hr = a.coefficients[2 * j], hi = a.coefficients[2 * j + 1];
-				float xr = x[2 * j], xi = x[2 * j + 1];
-				result.x += hr * xr - hi * xi;
-				result.y += hi * xr + hr * xi;
-			}
-		} else {
-			const uint32_t hs = a.complex_filter ? 2 : 1;
-			#pragma unroll 8
-			for (uint32_t j = 0; j < L; j++) {
-				float h = a.coefficients[hs * j];
-				result.x += x[2 * j]     * h;
-				result.y += x[2 * j + 1] * h;
+		if (out_sample < a.sample_count / D) {
+			const float *x = w + 2 * (size_t)(D * lane);
+			/* (unrolled: the taps' LDS reads and coefficient loads of eight turns are issued together and waited for once -- scalar loads and LDS
+			 * reads share one counter, so a turn of its own waits out both latencies 36 times per output; the sums keep their order) */
+			if (a.complex_filter && complex_sample) {
+				#pragma unroll 8
+				for (uint32_t j = 0; j < L; j++) {
+					float hr = a.coefficients[2 * j], hi = a.coefficients[2 * j + 1];
+					float xr = x[2 * j], xi = x[2 * j + 1];
+					result.x += hr * xr - hi * xi;
+					result.y += hi * xr + hr * xi;
+				}
+			} else {
+				const uint32_t hs = a.complex_filter ? 2 : 1;
+				#pragma unroll 8
+				for (uint32_t j = 0; j < L; j++) {
+					float h = a.coefficients[hs * j];
+					result.x += x[2 * j]     * h;
+					result.y += x[2 * j + 1] * h;
+				}
 			}
 		}
 		if constexpr (TRANSPOSE) {
@@ -457,7 +462,7 @@ __global__ __launch_bounds__(TRANSPOSE ? 1024 : 256) void filter_kernel(const Bf
 		/* thread t stores sample t / 16 of transmit t % 16: 16 consecutive elements of the output per sample */
 		const uint32_t ts = threadIdx.x / kFilterTransposeWaves, tt = threadIdx.x % kFilterTransposeWaves;
 		const uint32_t sample = wg * 64 + ts, tx = blockIdx.z * kFilterTransposeWaves + tt;
-		if (sample < a.sample_count / D && tx < a.transmits) {
+		if (sample < a.sample_count && tx < a.transmits) {
 			const f32x2 v = tile[ts * kFilterTransposeWaves + tt];
 			const int64_t off = a.out_stride[1] * channel + a.out_stride[2] * tx + a.out_stride[0] * sample;
 			if (a.out_kind == 3) reinterpret_cast<f32x2 *>(a.out)[off] = v;

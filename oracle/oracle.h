@@ -238,6 +238,8 @@ int  oracle_beamform(const OracleParameterBlock *pb, const void *raw, float *out
 void oracle_set_nearest_ambiguity_buffer(float *budget);
 /* the double-precision twin of every DAS stage of later oracle_beamform* calls into `frame` (voxels x 1 or 2 doubles), or NULL: off */
 void oracle_set_f64_frame(double *frame);
+/* every chunk's DAS input of the next oracle_beamform* call, assembled as [channel][transmit][sample] (oracle_plan.c); NULL: off */
+void oracle_set_das_input_capture(void *buffer);
 /* Sampling strides of the sub-grid for later oracle_beamform_subgrid calls (1, 1 = contiguous): plane
  * z_first + k z_stride, row y_first + k y_stride.  bench.py's CPU baseline times evenly spaced planes. */
 void oracle_set_subgrid_stride(uint32_t z_stride, uint32_t y_stride);

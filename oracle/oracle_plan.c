@@ -237,6 +237,12 @@ void oracle_set_rows_outermost(int enable) { rows_outermost = enable != 0; }
 static double *f64_frame;
 void oracle_set_f64_frame(double *frame) { f64_frame = frame; }
 
+/* DAS-input capture (test infrastructure): when set, the next oracle_beamform* call also assembles every chunk's DAS input into this
+ * buffer -- the whole frame's [channel][transmit][sample] layout, channel_count x acquisition_count x input_sample_count elements of
+ * the DAS kind (f32 or f32 complex), chunk k's Cn channels at channel k * 16: what the library's beamformer_hip_copy_das_input returns. */
+static uint8_t *das_input_capture;
+void oracle_set_das_input_capture(void *buffer) { das_input_capture = (uint8_t *)buffer; }
+
 static uint32_t subgrid_z_stride = 1, subgrid_y_stride = 1;   /* oracle_set_subgrid_stride */
 
 static void run_stage(Exec *e, int slot, int channel_offset, const uint8_t *rf_pointer, int64_t rf_elements_left)
@@ -346,6 +352,10 @@ static void run_stage(Exec *e, int slot, int channel_offset, const uint8_t *rf_p
 		d.threads = e->threads;
 		d.z_first = e->z_first; d.z_count = e->z_count; d.y_first = e->y_first; d.y_count = e->y_count;
 		d.z_stride = subgrid_z_stride; d.y_stride = subgrid_y_stride;
+		if (das_input_capture) {
+			size_t row_bytes = (size_t)plan->input_sample_count * (size_t)A * (d.complex_data ? 8u : 4u);
+			memcpy(das_input_capture + (size_t)channel_offset * row_bytes, pp_das, (size_t)Cn * row_bytes);
+		}
 		if (e->defer_das) {
 			memcpy(e->deferred_inputs + (size_t)e->deferred_count * e->slot_bytes, pp_das, e->slot_bytes);
 			e->deferred[e->deferred_count++] = d;

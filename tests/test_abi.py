@@ -82,9 +82,10 @@ def test_header_compiles_as_c_and_cxx(tmp_path):
         assert subprocess.run([str(exe)]).returncode == 0
 
 
-def test_every_environment_variable_and_switch_is_documented_and_hooks_read_no_environment():
+def test_every_environment_variable_and_the_six_hook_switches_are_documented_and_read_no_environment():
     """include/ogl_beamformer_hip.h lists what the library reads from the environment (every getenv in csrc/) and every diagnostic
-    switch of the hook table (csrc/das_select.cpp); the switches are reachable through beamformer_hip_set_hook ONLY"""
+    switch of the hook table (csrc/das_select.cpp) -- exactly six since SCRATCH_POISON joined the five staged-kernel / debug
+    switches; the switches are reachable through beamformer_hip_set_hook ONLY"""
     import glob
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,7 +99,7 @@ def test_every_environment_variable_and_switch_is_documented_and_hooks_read_no_e
     assert "getenv" not in select
     table = re.search(r"g_hook_names\[\] = \{(.*?)nullptr\}", select, flags=re.S)
     hooks = re.findall(r'"([A-Z0-9_]+)"', table.group(1))
-    assert sorted(hooks) == ["DEBUG", "STAGED_CHECKED", "STAGED_NOUNIFORM", "STAGED_SHAPE", "STAGED_TABLE_CAP"]
+    assert sorted(hooks) == ["DEBUG", "SCRATCH_POISON", "STAGED_CHECKED", "STAGED_NOUNIFORM", "STAGED_SHAPE", "STAGED_TABLE_CAP"]
     missing = sorted(v for v in (read | set(hooks)) if v not in header)
     assert not missing, missing
 

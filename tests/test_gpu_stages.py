@@ -1,0 +1,425 @@
+"""Element-wise parity of the stages in front of DAS (ingest, channel map, A1S2, Reshape, Decode, Filter / Demodulate): every
+case pushes through the C ABI with the SCRATCH_POISON hook set (both intermediate buffers and the ring slot are 0xFF bytes --
+NaN -- when the frame starts), reads back what the DAS stage read (beamformer_hip_copy_das_input) and compares it element by
+element with the oracle's capture of the same buffer; then the frame with test_gpu_parity.compare.  A frame-level bar dilutes
+a wrong sample by C x A before it sees it; these bars are per element.
+
+Bars:
+  * bit-identical (uint32 view) wherever the arithmetic is exact: ingest, channel map, A1S2, Reshape, int/f16 -> f32
+    conversion, and Int16 RF decoded before any filter (integer partial sums below 2^24, one identical division);
+  * elsewhere |gpu - oracle| <= bar, a forward-error bound propagated stage by stage in float64 from the stage's input
+    magnitudes (stage_bounds below).  Each case prints its largest err / bar."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from ogl_beamforming_amd import configs as cfg
+from ogl_beamforming_amd import params as P
+from tests import cases
+from tests.test_gpu_parity import compare
+
+pytestmark = pytest.mark.gpu
+
+S = P.ShaderKind
+DK = P.DataKind
+U32 = 2.0 ** -24          # unit roundoff of binary32
+U16 = 2.0 ** -11          # ... of binary16
+# An input sample that the shader rounds to binary16 after the demodulation rotation may land one binary16 ulp (2 u) apart in
+# the two builds (the GPU contracts c*x - s*y to an FMA, the oracle does not), and the scale multiply that follows may round
+# the other way once more (2 u): 4 u per sample, taken as 6 u for the ulp at a binade edge.
+K_SAMPLE = 6
+# Binary16 store of a stage output: one rounding of values already within the propagated bound of each other.
+K_STORE = 2
+
+
+def k_sum(n):
+    """Two recursive sums of n products, each within gamma_{n+1} = (n+1) u of the exact sum (Higham 3.1): 2 (n + 1)."""
+    return 2 * (n + 1)
+
+
+# ------------------------------------------------------------------------------------------------ running a case
+
+def filter_taps(oracle, fp):
+    """(magnitude per tap |hr| + |hi| or |h|, length, complex_filter) exactly as both builds read the taps (Q7: complex taps only
+    for a matched chirp)"""
+    from oracle.binding import library
+    buf = np.zeros(8192, np.float32)
+    delay = C.c_float(0)
+    L = library().oracle_filter_create(C.byref(fp), buf.ctypes.data_as(C.POINTER(C.c_float)), 8192, C.byref(delay))
+    assert L > 0
+    complex_filter = bool(fp.complex) and fp.kind == int(P.FilterKind.MatchedChirp)
+    if complex_filter:
+        h = np.abs(buf[0:2 * L:2].astype(np.float64)) + np.abs(buf[1:2 * L:2].astype(np.float64))
+    else:
+        h = np.abs(buf[:L].astype(np.float64))
+    return h, L, complex_filter
+
+
+def plan_of(bflib, acq):
+    L = bflib.library()
+    for slot, fp in enumerate(acq.filters):
+        assert L.beamformer_create_filter(C.byref(fp), slot, 0)
+    assert L.beamformer_push_simple_parameters(C.byref(acq.bp))
+    plan = P.HipPlan()
+    assert L.beamformer_hip_describe_plan(0, C.byref(plan))
+    return plan
+
+
+def mapped_rf_magnitudes(acq):
+    """|scalar| of the RF slot after ingest (channel map, A1S2 contrast, raw padding dropped), flat, float64"""
+    bp = acq.bp
+    Cn, A, Sn = int(bp.channel_count), int(bp.acquisition_count), int(bp.sample_count)
+    n_scalar = 2 if P.DATA_KIND_COMPLEX[int(bp.data_kind)] else 1
+    raw = np.abs(np.asarray(acq.rf).reshape(int(bp.raw_data_dimensions[1]), -1).astype(np.float64))
+    rows = raw[[int(bp.channel_mapping[c]) for c in range(Cn)]]
+    row = A * Sn * n_scalar
+    if bp.contrast_mode:
+        n = Sn * n_scalar
+        out = np.zeros((Cn, row))
+        out[:, :n] = rows[:, :n] + rows[:, n:2 * n] + rows[:, 2 * n:3 * n]
+        return out.reshape(-1)
+    return rows[:, :row].reshape(-1)
+
+
+def stage_bounds(bflib, oracle, acq, plan):
+    """Walks the library's plan over scalar buffers and returns (exact, magnitude, bar) of the DAS input, both (C, A, Sd)
+    arrays: `magnitude` bounds |value| (|re| + |im| for complex), `bar` the distance two faithful evaluations can have.
+    exact: every stage on the way is exact arithmetic (then the comparison is bit-identical)."""
+    bp = acq.bp
+    Cn, A = int(bp.channel_count), int(bp.acquisition_count)
+    Sd = int(plan.das_samples)
+    mag = mapped_rf_magnitudes(acq)
+    err = np.zeros_like(mag)
+    exact, integer = True, P.DATA_KIND_NUMPY[int(bp.data_kind)] == "int16"
+    n_ch = np.arange(Cn)[:, None, None]
+    n_tx = np.arange(A)[None, :, None]
+    n_s = np.arange(Sd)[None, None, :]
+
+    def elements(buf, kind):
+        return buf[0::2] + buf[1::2] if kind & 1 else buf
+
+    def scatter(size_elements, kind, index, values_mag, values_err):
+        n = 2 if kind & 1 else 1
+        m = np.zeros(size_elements * n)
+        e = np.zeros(size_elements * n)
+        for k in range(n):
+            m[n * index + k] = values_mag
+            e[n * index + k] = values_err
+        return m, e
+
+    das_index = [int(plan.stages[i].kind) for i in range(plan.stage_count)].index(int(S.DAS))
+    for i in range(das_index):
+        st = plan.stages[i]
+        kind = int(st.kind)
+        ist, ost = [int(v) for v in st.in_stride], [int(v) for v in st.out_stride]
+        in_m, in_e = elements(mag, st.in_kind), elements(err, st.in_kind)
+        out_f16 = (st.out_kind >> 1) == 2
+        if kind == int(S.Reshape):
+            assert not (not (st.in_kind & 1) and (st.out_kind & 1)), "interleaving Reshape: not modelled"
+            src = ist[0] * n_s + ist[1] * n_ch + ist[2] * n_tx
+            dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
+            if out_f16 and not integer:
+                exact = False
+            mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, in_m[src], in_e[src] + (K_STORE * U16 * in_m[src] if out_f16 else 0))
+        elif kind == int(S.Decode):
+            T = A
+            src = ((n_s * Cn + n_ch) * T)[:, 0, :]                          # (C, Sd): element j at + j (decode kernel layout)
+            M = sum(in_m[src + j] for j in range(T)) / T
+            E = sum(in_e[src + j] for j in range(T)) / T
+            if not integer:                                                 # integer partial sums: exact, one identical division
+                exact = False
+                E = E + k_sum(T) * (U16 if out_f16 else U32) * M
+            integer = False
+            dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
+            mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, np.broadcast_to(M[:, None, :], dst.shape),
+                               np.broadcast_to(E[:, None, :], dst.shape))
+        elif kind in (int(S.Filter), int(S.Demodulate)):
+            demod = kind == int(S.Demodulate)
+            assert len(acq.filters) == 1
+            h, L, complex_filter = filter_taps(oracle, acq.filters[0])
+            D = max(1, int(bp.decimation_rate)) if demod else 1
+            f16 = (st.in_kind >> 1) != 1
+            scale = 1.0
+            if demod:
+                # the rotation keeps |s| but may grow |re| + |im| by sqrt(2); times the shader's scale (filter.glsl:98)
+                scale = math.sqrt(2.0) * (1.0 + 2 * U16)
+                if not complex_filter:
+                    scale *= float(np.float16(math.sqrt(2.0))) if f16 else float(np.float32(math.sqrt(2.0)))
+            terms = 2 * L if complex_filter and (demod or st.in_kind & 1) else L
+            keep = Sd // D
+            M = np.zeros((Cn, A, Sd))
+            E = np.zeros((Cn, A, Sd))
+            n_el = len(in_m)
+            for c in range(Cn):
+                for t in range(A):
+                    row_start = ist[1] * c + ist[2] * t
+                    if demod:
+                        row_start //= 2                                     # filter.glsl:81-87 (non-negative: floor = truncation)
+                    lo = row_start - (L - 1)
+                    hi = row_start + D * (keep - 1) + 1
+                    idx = np.arange(lo, hi)
+                    ok = (idx >= 0) & (idx < n_el)
+                    seg_m = np.where(ok, in_m[np.clip(idx, 0, n_el - 1)], 0.0)
+                    seg_e = np.where(ok, in_e[np.clip(idx, 0, n_el - 1)], 0.0)
+                    M[c, t, :keep] = scale * np.correlate(seg_m, h, "valid")[::D][:keep]
+                    E[c, t, :keep] = scale * np.correlate(seg_e, h, "valid")[::D][:keep]
+            u_in = U16 if f16 else U32
+            E = E + ((K_SAMPLE * u_in if demod else 0.0) + k_sum(terms) * U32) * M
+            if out_f16:
+                E = E + K_STORE * U16 * M
+            exact = integer = False
+            dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
+            if st.in_kind & 1 and not (st.out_kind & 1):                    # deinterleaving store: re, then im a batch later
+                batch = Cn * Sd * A
+                mag = np.zeros(2 * batch)
+                err = np.zeros(2 * batch)
+                for part in (0, batch):
+                    mag[dst + part] = M
+                    err[dst + part] = E
+            else:
+                mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, M, E)
+        else:
+            raise AssertionError(f"stage kind {kind} not modelled")
+    das = plan.stages[das_index]
+    ist = [int(v) for v in das.in_stride]
+    src = ist[0] * n_s + ist[1] * n_ch + ist[2] * n_tx
+    per_scalar = (lambda b: np.maximum(b[0::2], b[1::2])) if das.in_kind & 1 else (lambda b: b)
+    return exact, elements(mag, das.in_kind)[src], per_scalar(err)[src]
+
+
+def oracle_run(oracle, acq):
+    captured = {}
+    flags = {} if acq.bp.interpolation_mode == int(P.InterpolationMode.Nearest) else None
+    ref, _ = oracle.beamform(acq.bp, acq.rf, acq.filters, flags=flags, das_input=captured)
+    return ref, flags, captured["data"]
+
+
+def push(bflib, acq, hooks=None, poison=True, mode=0):
+    L = bflib.library()
+    if hooks is not None:
+        if poison:
+            hooks.set("SCRATCH_POISON")
+        else:
+            hooks.clear("SCRATCH_POISON")
+    L.beamformer_hip_set_das_path(mode)
+    try:
+        frame = bflib.beamform(acq.bp, acq.rf, acq.filters)
+        das_input = bflib.das_input(acq.bp)
+    finally:
+        L.beamformer_hip_set_das_path(0)
+    return frame, das_input
+
+
+def as_bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32)
+
+
+def check_das_input(bflib, oracle, acq, gpu_in, ref_in, label=""):
+    """the element-wise bar; returns ('bit-identical', 0) or ('bound', max err/bar)"""
+    plan = plan_of(bflib, acq)
+    assert gpu_in.shape == ref_in.shape, (gpu_in.shape, ref_in.shape)
+    assert not np.isnan(ref_in).any(), "the oracle's DAS input holds NaN"
+    nan = np.isnan(gpu_in)
+    if nan.any():
+        c, t, s = np.argwhere(nan)[0]
+        raise AssertionError(f"{label}: {int(nan.sum())} DAS-input elements are NaN (read without having been written this frame), "
+                             f"first at channel {c} transmit {t} sample {s} of {gpu_in.shape[2]} "
+                             f"(decimation {acq.bp.decimation_rate}: samples [{gpu_in.shape[2] // max(1, acq.bp.decimation_rate)}, "
+                             f"{gpu_in.shape[2]}) are the filter's tail)")
+    exact, mag, bar = stage_bounds(bflib, oracle, acq, plan)
+    if exact:
+        diff = as_bits(gpu_in) != as_bits(ref_in)
+        assert not diff.any(), (f"{label}: exact stages but {int(diff.sum())} DAS-input scalars differ in their bits, "
+                                f"first at {np.argwhere(diff.reshape(gpu_in.shape + (-1,)) if np.iscomplexobj(gpu_in) else diff)[0]}")
+        print(f"{label}: DAS input bit-identical")
+        return "bit-identical", 0.0
+    if np.iscomplexobj(gpu_in):
+        err = np.maximum(np.abs(gpu_in.real.astype(np.float64) - ref_in.real), np.abs(gpu_in.imag.astype(np.float64) - ref_in.imag))
+    else:
+        err = np.abs(gpu_in.astype(np.float64) - ref_in)
+    over = err > bar
+    if over.any():
+        c, t, s = np.argwhere(over)[0]
+        raise AssertionError(f"{label}: {int(over.sum())} DAS-input elements outside the forward-error bound; first at channel {c} "
+                             f"transmit {t} sample {s}: gpu {gpu_in[c, t, s]} oracle {ref_in[c, t, s]} bar {bar[c, t, s]:.3e}")
+    live = bar > 0
+    ratio = float((err[live] / bar[live]).max()) if live.any() else 0.0
+    print(f"{label}: DAS input within the bound, max err/bar {ratio:.3e}")
+    return "bound", ratio
+
+
+def run_case(bflib, oracle, hooks, acq, modes=(0,)):
+    ref, flags, ref_in = oracle_run(oracle, acq)
+    results = []
+    for mode in modes:
+        gpu, gpu_in = push(bflib, acq, hooks, poison=True, mode=mode)
+        results.append((gpu, gpu_in, check_das_input(bflib, oracle, acq, gpu_in, ref_in, f"{acq.name} mode {mode:#x}")))
+        compare(gpu, ref, acq, flags)
+    return ref, ref_in, results
+
+
+# ------------------------------------------------------------------------------------------------ geometry
+
+FS, FD, PITCH = 25e6, 6.25e6, 0.3e-3
+
+
+def deepest_sample(acq, plan):
+    """the sample index of one in-aperture term at the deepest voxel on the image axis (x = 0): the transmit that reaches
+    deepest, received on the element nearest the axis (das.glsl's plane-wave RCA geometry, as the oracle computes it)"""
+    bp = acq.bp
+    m = np.array(bp.das_voxel_transform[:], np.float64).reshape(4, 4).T
+    z1 = (m @ np.array([0.5, 1.0, 0.0, 1.0]))[2] if bp.output_points[2] <= 1 else (m @ np.array([0.5, 0.5, 1.0, 1.0]))[2]
+    half = (bp.channel_count - 1) / 2 * PITCH
+    rx = min(math.hypot(c * PITCH - half, z1) for c in range(bp.channel_count))
+    tx = max(z1 * math.cos(math.radians(bp.steering_angles[a])) for a in range(bp.acquisition_count))
+    return ((tx + rx) / cfg.SPEED_OF_SOUND + plan.das_time_offset) * plan.das_sampling_frequency
+
+
+def decimation_case(D, data_kind, L, A, decode, seed, C_=8, S_=2048, chirp=False):
+    """{Demodulate, DAS} or {Demodulate, Decode, DAS} at decimation D, whose deepest voxels take terms from samples around
+    1.4 Sd / D -- past the end of what the filter computes (Sd / D of the Sd samples of a DAS row)"""
+    t_deep = 1.4 * (S_ / (2 * D * D)) / (FS / (2 * D))           # seconds: 1.4 x the first tail sample
+    z1 = cfg.SPEED_OF_SOUND * t_deep / 2
+    stages = (S.Demodulate, S.Decode, S.DAS) if decode else (S.Demodulate, S.DAS)
+    name = f"dec{D}_{P.DataKind(data_kind).name}_L{L}_A{A}{'_decode' if decode else ''}{'_chirp' if chirp else ''}"
+    acq = cfg.rca(name, C_, A, S_, (16, 1, 24), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1), seed=seed, data_kind=data_kind,
+                  demodulate=True, stages=stages, decimation=D, decode=1 if decode else 0, fs=FS, fd=FD, pitch=PITCH,
+                  single=False, orientation=0x22, angles=np.linspace(-10, 10, A), scatterers=[(0.0, 0.0, 0.7 * z1)])
+    if chirp:
+        acq.filters = [cfg.matched_chirp_filter(FS / 2, L / (FS / 2), 2e6, 8e6)]
+    else:
+        acq.filters = [cfg.kaiser_filter(FS / 2, FD / 2, length=L)]
+    return acq
+
+
+KINDS = (DK.Int16, DK.Float16, DK.Float32)
+DECIMATION_CASES = {}
+for _i, (_D, _kind) in enumerate((d, k) for d in (2, 3, 4, 8) for k in KINDS):
+    _L = (7, 36, 101)[_i % 3]
+    _decode = _i % 2 == 1
+    _A = (12, 16, 20)[(_i // 2) % 3]
+    DECIMATION_CASES[f"D{_D}_{_kind.name}_L{_L}_A{_A}_{'decode' if _decode else 'das'}"] = (_D, _kind, _L, _A, _decode, False)
+# D = 8 with 101 taps: lds_t = 16 x (8*64 + 100) x 8 B + 8 KiB > 64 KiB -- the 256-thread form in front of Decode
+DECIMATION_CASES["D8_Int16_L101_A16_decode_untransposed"] = (8, DK.Int16, 101, 16, True, False)
+DECIMATION_CASES["D2_Int16_chirp_A12_decode"] = (2, DK.Int16, 48, 12, True, True)
+DECIMATION_CASES["D2_Float32_chirp_A20_das"] = (2, DK.Float32, 48, 20, False, True)
+
+
+def test_decimation_matrix_covers_the_issue():
+    covered = {(v[1], v[0]) for v in DECIMATION_CASES.values()}
+    assert covered >= {(k, d) for k in KINDS for d in (2, 3, 4, 8)}
+    assert {v[2] for v in DECIMATION_CASES.values()} >= {7, 36, 101}
+    assert {v[3] for v in DECIMATION_CASES.values() if v[4]} >= {12, 16, 20}
+
+
+@pytest.mark.parametrize("name", sorted(DECIMATION_CASES))
+def test_decimation(name, bflib, oracle, hooks):
+    D, kind, L, A, decode, chirp = DECIMATION_CASES[name]
+    acq = decimation_case(D, kind, L, A, decode, seed=300 + sorted(DECIMATION_CASES).index(name), chirp=chirp)
+    plan = plan_of(bflib, acq)
+    Sd = int(plan.das_samples)
+    assert Sd == acq.bp.sample_count // (2 * D)
+    reach = deepest_sample(acq, plan)
+    assert Sd // D <= reach < Sd - 2, f"the image reaches sample {reach:.1f}: not in the filter's tail [{Sd // D}, {Sd})"
+    _, ref_in, _ = run_case(bflib, oracle, hooks, acq)
+    assert not ref_in[:, :, Sd // D:].any(), "the oracle's tail is not zero"
+
+
+# ------------------------------------------------------------------------------------------------ ragged rows
+
+def ragged_case(S_, demod, seed):
+    stages = (S.Demodulate, S.DAS) if demod else (S.Decode, S.DAS)
+    fs_das = FS / 2 if demod else FS
+    z1 = 0.8 * cfg.SPEED_OF_SOUND * (S_ / (2 if demod else 1) / fs_das) / 2
+    return cfg.rca(f"ragged_{S_}_{'demod' if demod else 'decode'}", 8, 4, S_, (12, 1, 16), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1),
+                   seed=seed, stages=stages, decode=0 if demod else 1, fs=FS, fd=FD, pitch=PITCH,
+                   angles=np.linspace(-5, 5, 4), scatterers=[(0.0, 0.0, 0.6 * z1)])
+
+
+@pytest.mark.parametrize("demod", [True, False], ids=["demodulate", "decode"])
+@pytest.mark.parametrize("S_", [130, 200, 1000, 1001])
+def test_ragged_rows(S_, demod, bflib, oracle, hooks):
+    """sample counts that are not a multiple of 128 (64 after demodulation): a ragged last 64-sample group in Filter and
+    Decode, and with 1001 an odd row, whose half-element row start truncates (filter.glsl:81-87)"""
+    acq = ragged_case(S_, demod, seed=400 + S_ + demod)
+    run_case(bflib, oracle, hooks, acq, modes=(0,) if demod else (0, 0x20))
+
+
+# ------------------------------------------------------------------------------------------------ decode orders
+
+DECODE_KINDS = (DK.Int16, DK.Float16, DK.Float32Complex)
+
+
+@pytest.mark.parametrize("kind", DECODE_KINDS, ids=[k.name for k in DECODE_KINDS])
+@pytest.mark.parametrize("A", [2, 20, 24, 40, 128])
+def test_decode_orders(A, kind, bflib, oracle, hooks):
+    """FWHT base 20 (A = 20, 40), base 12 x 2 (24), the dense kernel's i0 + k < T guard (A = 2), 66 KiB of dynamic LDS (128
+    complex) -- against the oracle, and the Walsh-Hadamard form against the forced-dense one (0x20)"""
+    S_ = 200 if A >= 40 else 1000
+    Cn = 4
+    z1 = 0.8 * cfg.SPEED_OF_SOUND * (S_ / FS) / 2
+    acq = cfg.rca(f"decode_A{A}_{kind.name}", Cn, A, S_, (8, 1, 12), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1), seed=500 + A,
+                  data_kind=kind, stages=(S.Decode, S.DAS), decode=1, fs=FS, fd=FD, pitch=PITCH, angles=np.linspace(-5, 5, A))
+    _, ref_in, results = run_case(bflib, oracle, hooks, acq, modes=(0, 0x20))
+    (fast_frame, fast_in, (bar_fast, _)), (dense_frame, dense_in, (bar_dense, _)) = results
+    if kind == DK.Int16:
+        assert bar_fast == bar_dense == "bit-identical"
+        assert np.array_equal(as_bits(fast_in), as_bits(dense_in))
+        assert np.array_equal(as_bits(fast_frame), as_bits(dense_frame))
+
+
+# ------------------------------------------------------------------------------------------------ raw Float16Complex
+
+# (a pipeline must start with Decode or Demodulate, lib .c:305-309, and Demodulate takes real RF only: {DAS} and {Filter, DAS}
+# are written with a Decode that decode_mode None drops)
+F16C_STAGES = {"das": (S.Decode, S.DAS), "decode": (S.Decode, S.DAS), "filter": (S.Decode, S.Filter, S.DAS)}
+
+
+@pytest.mark.parametrize("pipeline", sorted(F16C_STAGES))
+def test_float16_complex_rf(pipeline, bflib, oracle, hooks):
+    """raw Float16Complex RF: converted by a Reshape, decoded, or through a complex matched-chirp filter"""
+    S_ = 512
+    z1 = 0.8 * cfg.SPEED_OF_SOUND * (S_ / FS) / 2
+    acq = cfg.rca(f"f16c_{pipeline}", 8, 4, S_, (12, 1, 16), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1), seed=600 + len(pipeline),
+                  data_kind=DK.Float16Complex, stages=F16C_STAGES[pipeline], decode=1 if pipeline == "decode" else 0,
+                  fs=FS, fd=FD, pitch=PITCH, angles=np.linspace(-5, 5, 4))
+    if pipeline == "filter":
+        acq.filters = [cfg.matched_chirp_filter(FS, 2e-6, 2e6, 8e6)]
+    run_case(bflib, oracle, hooks, acq)
+
+
+# ------------------------------------------------------------------------------------------------ every named case
+
+@pytest.mark.parametrize("name", sorted(cases.CASES))
+def test_named_case_das_input_and_write_coverage(name, bflib, oracle, hooks):
+    """the DAS input against the oracle (ingest with channel shuffle, raw padding and A1S2 included), and the poisoned frame
+    bit-identical to an unpoisoned push: every voxel of the frame is written by some kernel"""
+    acq = cases.make(name)
+    poisoned = run_case(bflib, oracle, hooks, acq)[2][0][0]
+    clean, _ = push(bflib, acq, hooks, poison=False)
+    diff = as_bits(poisoned) != as_bits(clean)
+    assert not diff.any(), f"{int(diff.sum())} frame scalars differ from the unpoisoned push (unwritten voxels keep 0xFFFFFFFF)"
+
+
+# ------------------------------------------------------------------------------------------------ order independence
+
+def test_decimation_tail_does_not_depend_on_earlier_frames(bflib, oracle, hooks):
+    """without the hook: a D = 2 frame after a large-amplitude D = 1 frame of a bigger plan (both scratch buffers dirty) equals
+    the same D = 2 frame pushed first after a fresh start, and the oracle"""
+    hooks.clear("SCRATCH_POISON")
+    acq = decimation_case(2, DK.Int16, 36, 16, True, seed=700)
+    ref, flags, ref_in = oracle_run(oracle, acq)
+    bflib.library().beamformer_hip_shutdown()
+    first, first_in = push(bflib, acq)
+    dirty = cfg.rca("dirty", 32, 16, 4096, (16, 1, 24), (-2e-3, 0, 5e-3), (2e-3, 0, 40e-3), seed=701, data_kind=DK.Float32,
+                    stages=(S.Demodulate, S.Decode, S.DAS), decode=1, fs=FS, fd=FD, pitch=PITCH, angles=np.linspace(-5, 5, 16))
+    dirty.rf = (dirty.rf * np.float32(1e6)).astype(np.float32)
+    push(bflib, dirty)
+    again, again_in = push(bflib, acq)
+    check_das_input(bflib, oracle, acq, again_in, ref_in, "after a dirty frame")
+    compare(again, ref, acq, flags)
+    assert np.array_equal(as_bits(first_in), as_bits(again_in)), "the DAS input depends on what ran before it"
+    assert np.array_equal(as_bits(first), as_bits(again)), "the frame depends on what ran before it"

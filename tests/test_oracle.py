@@ -252,3 +252,48 @@ def test_rows_outermost_schedule_is_bit_identical_to_the_chunk_by_chunk_one(name
     assert pa == pb and pa2 == pb2
     assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
     assert np.array_equal(a2.view(np.uint32), b2.view(np.uint32))
+
+
+def test_das_input_capture_is_the_filter_output_with_a_zero_tail(oracle):
+    """oracle.beamform(das_input=...) with Demodulate at decimation 2: the captured DAS input is oracle_filter run directly on the
+    channel-mapped RF (the stage's own parameters), and its samples [Sd/2, Sd) -- which filter.glsl:115 never computes -- are zero"""
+    from oracle.binding import library
+    L = library()
+
+    class OracleFilter(C.Structure):
+        _fields_ = [("filter_length", C.c_int), ("complex_filter", C.c_int), ("demodulate", C.c_int),
+                    ("sampling_frequency", C.c_float), ("demodulation_frequency", C.c_float),
+                    ("decimation_rate", C.c_int), ("sample_count", C.c_int), ("batch_sample_count", C.c_int),
+                    ("in_stride", C.c_int * 3), ("out_stride", C.c_int * 3), ("in_kind", C.c_int), ("out_kind", C.c_int),
+                    ("channels", C.c_int), ("transmits", C.c_int), ("in_elements", C.c_int64), ("workgroup", C.c_int),
+                    ("coefficients", fp)]
+    Cn, A, S_, D_ = 20, 3, 1000, 2                     # 20 channels: two oracle chunks (16 + 4) assembled into one capture
+    acq = cfg.rca("capture_d2", Cn, A, S_, (8, 1, 12), (-2e-3, 0, 5e-3), (2e-3, 0, 15e-3), seed=91, channel_shuffle=True,
+                  stages=(S.Demodulate, S.DAS), decimation=D_, angles=np.linspace(-5, 5, A))
+    captured = {}
+    oracle.beamform(acq.bp, acq.rf, acq.filters, das_input=captured)
+    got = captured["data"]
+    Sd = S_ // (2 * D_)
+    assert got.shape == (Cn, A, Sd) and got.dtype == np.complex64
+
+    mapped = np.ascontiguousarray(np.stack([acq.rf[acq.bp.channel_mapping[c]] for c in range(Cn)]))
+    taps = np.zeros(8192, np.float32)
+    delay = C.c_float(0)
+    f = OracleFilter()
+    f.filter_length = L.oracle_filter_create(C.byref(acq.filters[0]), taps.ctypes.data_as(fp), 8192, C.byref(delay))
+    f.complex_filter, f.demodulate = 0, 1
+    f.sampling_frequency, f.demodulation_frequency = acq.bp.sampling_frequency / 2, acq.bp.demodulation_frequency
+    f.decimation_rate, f.sample_count = D_, Sd
+    f.in_stride[:] = [1, S_ * A, S_]                    # raw layout in real samples (halved by the shader)
+    f.out_stride[:] = [1, Sd * A, Sd]
+    f.in_kind, f.out_kind = int(D.Int16Complex), int(D.Float32Complex)
+    f.channels, f.transmits = Cn, A
+    f.in_elements, f.workgroup = mapped.size // 2, 64
+    f.coefficients = taps.ctypes.data_as(fp)
+    want = np.zeros(Cn * A * Sd, np.complex64)
+    L.oracle_filter.argtypes = [C.POINTER(OracleFilter), C.c_void_p, C.c_void_p, C.c_uint32]
+    L.oracle_filter(C.byref(f), mapped.ctypes.data_as(C.c_void_p), want.ctypes.data_as(C.c_void_p), 0)
+    want = want.reshape(Cn, A, Sd)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.abs(got[:, :, : Sd // D_]).max() > 0
+    assert not got[:, :, Sd // D_:].view(np.uint32).any()
