@@ -71,6 +71,11 @@ typedef struct {
 	                                     have an instantiation without any row-end code for launches where it is 0 */
 } BfDasArgs;
 
+/* channel-paired staged kernel (uniform = 2): the LDS holds the 64-element blocks (two channels' 32-sample windows) of at most this
+ * many transmits at a time -- a multiple of 4 whose block indices, plus the two elements in front, stay below 4096 (the tap address
+ * is a 16-bit shift of the element index) */
+#define BF_STAGED_PAIRED_GROUP_MAX 60u
+
 /* tile geometry of the separable-delay fast path (das_separable.hip) */
 typedef struct {
 	uint32_t u_axis;          /* output axis (0 = x, 1 = y) the receive aperture runs along */
@@ -85,10 +90,13 @@ typedef struct {
 	uint32_t zero_offset;     /* byte offset (from BfDasArgs.rf) of >= 32 zero bytes the host keeps behind
 	                             the DAS input: where out-of-range lanes gather from */
 	/* staged kernel (complex, linear), 64 x 16 tiles with x along the receive axis: the transmit delays and phasors of a wave are
-	 * uniform and come from a global table (bf_launch_das_staged_tables writes it per frame) through scalar loads */
-	uint32_t uniform;         /* 1: use `tables` */
+	 * uniform and come from a global table (bf_launch_das_staged_tables writes it per frame) through scalar loads.
+	 * 32 x 32 tiles, 32-sample windows (uniform = 2, the channel-paired form): a lane beamforms rows w and w + 16 of the tile for
+	 * one channel of a pair, so a wave again shares its transmit rows (two of them) and reads them from a global table */
+	uint32_t uniform;         /* 1: use `tables` (64 x 16 tiles); 2: the channel-paired form, `tables` in its row-pair layout */
 	uint32_t window_samples;  /* 32 or 64 (= 1 << window_shift) */
-	uint32_t table_stride;    /* bytes per (lateral tile row, plane) slice: 4 A4 + 16 + 16 (A4 / 4) 48, A4 = transmits rounded up to 4 */
+	uint32_t table_stride;    /* bytes per (lateral tile row, plane) slice: 4 A4 + 16 + 16 (A4 / 4) 48 (uniform = 1) or
+	                             4 A4 + 16 + 16 (A4 / 2) 48 (uniform = 2), A4 = transmits rounded up to 4 */
 	void    *tables;          /* tiles[1] * tiles[2] slices */
 	uint32_t *violations;     /* staged kernels, range-checked loop: incremented once per wave and channel in which some term's window
 	                             position fell outside the staged window -- a violated host bound (plan_staged) made loud; may be null */

@@ -402,8 +402,26 @@ static bool plan_staged(const BfDasArgs &a, const std::vector<BfTransmit> &tx, c
 			}
 		}
 	}
+	/* The plan is 32 x 32 tiles of 1024 threads with 32-sample windows (config 4: its spread does not fit a 64-wide tile's window):
+	 * the channel-paired form of das_staged.hip, two voxels per lane (rows w, w + 16) and a wave's transmit rows shared, its transmit
+	 * tables global as for the form above.  Same tiles, windows and chunk; the LDS holds two channels' windows of up to
+	 * BF_STAGED_PAIRED_GROUP_MAX transmits at a time (in at most two groups here) instead of one channel's windows of all transmits
+	 * and the transmit tables.  Decided by the shape alone: a slab takes the form the whole frame takes. */
+	if (best_waves && allow_uniform && cplx && !cubic && !hk.staged_nouniform && best.threads == 1024 && best.u_shift == 5 && best.v_shift == 5 &&
+	    best.window_samples == 32) {
+		const uint32_t ngroups = (A4 + BF_STAGED_PAIRED_GROUP_MAX - 1u) / BF_STAGED_PAIRED_GROUP_MAX;
+		const uint64_t group = ((A4 + ngroups - 1u) / ngroups + 3u) & ~3u;
+		const uint32_t cc = best.channel_chunk;
+		uint64_t lds = 16ull * (group * 64 + 3) + 16ull * ((uint64_t)((cc + 1) & ~1u) << 5) + 4ull * (A4 + cc + 1) + 128;
+		lds = (lds + 15) & ~15ull;
+		if (ngroups <= 2 && lds <= lds_cu / 2 && ((cc & 1u) == 0 || cc == C)) {          /* (two blocks per CU, as before) */
+			best.uniform = 2u;
+			best.lds_bytes = (uint32_t)lds;
+			best.table_stride = 4u * A4 + 16u + 16u * (A4 / 2u) * 48u;
+		}
+	}
 	if (hk.staged_checked) best.depth_major |= 2u;       /* test hook: the range-checked loop for every wave */
-	/* uniform variant: the two blocks of a CU are neighbours along u in one plane (shared rows of the global transmit table) */
+	/* global-table variants: the two blocks of a CU are neighbours along u in one plane (shared rows of the global transmit table) */
 	if (best.uniform && (best.depth_major & 1u)) best.depth_major |= 4u;
 	if (hk.debug)
 		std::fprintf(stderr, "[beamformer] staged plan: step_u %.3f step_v %.3f waves %u u %u v %u w %u chunk %u lds %u uniform %u\n",

@@ -62,6 +62,35 @@ __device__ __forceinline__ float staged_phase_turns(float k, float index)
 	return hw_fract(p) + e;
 }
 
+/* The block's tile.  depth_major bit 2 (global transmit tables): planes in chunks of 32, so that blocks j and j + 32 of an XCD's
+ * sequence -- the two a CU holds (dispatch is breadth first over an XCD's 32 CUs) -- are NEIGHBOURS ALONG u in one plane: they read
+ * the same rows of the global transmit table (14.6 KB at 76 transmits: the scalar cache holds 16 KB) and adjacent RF windows.
+ * False: no tile (the grid's rounding, the last chunk's padding) -- a whole block. */
+__device__ __forceinline__ bool staged_tile_of(const BfSeparableArgs &q, bool global_tables, uint32_t &tu, uint32_t &tv, uint32_t &zl)
+{
+	const bool paired = global_tables && (q.depth_major & 4u);
+	const uint32_t zchunks = (q.tiles[2] + 31u) >> 5;
+	const uint32_t total = paired ? q.tiles[0] * q.tiles[1] * zchunks * 32u : q.tiles[0] * q.tiles[1] * q.tiles[2];
+	const uint32_t per   = (total + 7u) / 8u;
+	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+	if (tile >= total) return false;
+	if (paired) {                                            /* walk order: das_separable.hip */
+		uint32_t r = tile >> 5;
+		tu = r % q.tiles[0]; r /= q.tiles[0];
+		zl = (r % zchunks) * 32u + (tile & 31u);
+		tv = r / zchunks;
+		return zl < q.tiles[2];
+	}
+	if (q.depth_major & 1u) {
+		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
+	} else {
+		tu = tile % q.tiles[0];
+		tv = (tile / q.tiles[0]) % q.tiles[1];
+		zl = tile / (q.tiles[0] * q.tiles[1]);
+	}
+	return true;
+}
+
 /* LDS (A4 = transmits rounded up to a multiple of 4; transmits are kept in PAIRS so that one read serves two terms):
  *   stage[a*W + j]   = { c_j, d_j }: the line through samples j and j + 1 of window (c, a) in window coordinates
  *                      (d_j = s' - s, c_j = s + (1/2 - j) d_j; s = sample floor(rmin_c) + floor(tmin_a) + j of row (c, a),
@@ -79,7 +108,7 @@ __device__ __forceinline__ float staged_phase_turns(float k, float index)
  *      loop_probe_uniform: 40.2 clk per term against 43.7, at a higher sustained clock). */
 typedef __attribute__((address_space(4))) const f32x4 const_f32x4;
 template <bool CW, int VS, int WS, int NL, bool UNI>
-__global__ __launch_bounds__(1024, 8) void das_rca_staged_kernel(const BfDasArgs p, const BfSeparableArgs q)
+__device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparableArgs &q)
 {
 	extern __shared__ __attribute__((aligned(16))) f32x4 staged_lds[];
 	/* WS: log2 of the window length (5, 6) */
@@ -100,29 +129,8 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_kernel(const BfDasArgs
 	f32x2 *wave_range = reinterpret_cast<f32x2 *>(rfloor + ((chunk + 1) & ~1));      /* 16 entries, 8-byte aligned */
 	const uint32_t stage_elements = (uint32_t)A4 * W;
 
-	/* depth_major bit 2 (UNI): planes in chunks of 32, so that blocks j and j + 32 of an XCD's sequence -- the two a CU holds
-	 * (dispatch is breadth first over an XCD's 32 CUs) -- are NEIGHBOURS ALONG u in one plane: they read the same 16 rows of the
-	 * global transmit table (14.6 KB at 76 transmits: the scalar cache holds 16 KB) and adjacent RF windows */
-	const bool paired = UNI && (q.depth_major & 4u);
-	const uint32_t zchunks = (q.tiles[2] + 31u) >> 5;
-	const uint32_t total = paired ? q.tiles[0] * q.tiles[1] * zchunks * 32u : q.tiles[0] * q.tiles[1] * q.tiles[2];
-	const uint32_t per   = (total + 7u) / 8u;
-	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-	if (tile >= total) return;                               /* whole block */
-	uint32_t tu, tv, zl;                                     /* walk order: das_separable.hip */
-	if (paired) {
-		uint32_t r = tile >> 5;
-		tu = r % q.tiles[0]; r /= q.tiles[0];
-		zl = (r % zchunks) * 32u + (tile & 31u);
-		tv = r / zchunks;
-		if (zl >= q.tiles[2]) return;                        /* whole block: the last chunk's padding */
-	} else if (q.depth_major & 1u) {
-		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
-	} else {
-		tu = tile % q.tiles[0];
-		tv = (tile / q.tiles[0]) % q.tiles[1];
-		zl = tile / (q.tiles[0] * q.tiles[1]);
-	}
+	uint32_t tu, tv, zl;
+	if (!staged_tile_of(q, UNI, tu, tv, zl)) return;        /* whole block */
 	const uint32_t z  = p.z_first + zl;
 
 	const uint32_t u_axis = q.u_axis, v_axis = 1u - q.u_axis;
@@ -478,13 +486,291 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_kernel(const BfDasArgs
 	reinterpret_cast<f32x2 *>(p.out)[out_index] = coherent;
 }
 
+/* ---- the channel-paired form (q.uniform = 2): 32 x 32 tiles, 32-sample windows, 1024 threads -- the shape of config 4, whose delay
+ * spread does not fit a 64-wide tile's window.  Lane l of wave w beamforms rows w and w + 16 of the tile at u = l & 31, for the
+ * channel of parity h = l >> 5 of each channel pair: all 64 lanes of a wave share ONE PAIR of transmit-axis rows, so the transmit
+ * delays and phasors are wave uniform again and come from a global table (staged_tables_kernel, row-pair layout) through scalar
+ * loads as in UNI; and the two rows share the lane's receive position, so one packed add with the table's {T_A, T_B} forms both
+ * voxels' positions.  Per round (channel pair, group of transmits) the LDS holds for every transmit of the group a 64-element block:
+ * channel 2k's window, then channel 2k + 1's; the half offset h * W rides in the lane's receive entry and the lines are kept in the
+ * coordinate 1/2 - (e mod 64), so the tap address is still one 16-bit shift of y = p + M (group * 64 + 2 < 4096:
+ * BF_STAGED_PAIRED_GROUP_MAX).  After each channel pair lanes l and l + 32 hold the even- and the odd-channel terms of the same two
+ * voxels: one exchange (v_permlane32_swap) per value and each half accumulates one of the voxels.
+ * LDS: stage[a*64 + h*32 + j] (a < group), a zero element behind the largest group, R[cl*32 + u] for the chunk's channels (an odd
+ * last channel gets a zero partner), tfl[A4], rfloor[chunk]. */
+template <bool CW, int NL>
+__device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfSeparableArgs &q)
+{
+	extern __shared__ __attribute__((aligned(16))) f32x4 staged_lds[];
+	constexpr uint32_t U = 32, W = 32, B = 2 * W;
+	const int C = p.channel_count, A = p.acquisition_count, S = p.sample_count;
+	const uint32_t A4 = ((uint32_t)A + 3u) & ~3u;
+	const uint32_t ngroups = (A4 + BF_STAGED_PAIRED_GROUP_MAX - 1u) / BF_STAGED_PAIRED_GROUP_MAX;
+	const uint32_t G0 = ((A4 + ngroups - 1u) / ngroups + 3u) & ~3u;       /* transmits of every group but the last (76: 40 + 36) */
+	const int chunk = (int)q.channel_chunk;
+	f32x4 *stage  = staged_lds + 2;                          /* (two unused elements in front, as staged_body) */
+	f32x4 *R      = stage + (size_t)G0 * B + 1;
+	int   *tfl    = reinterpret_cast<int *>(R + (size_t)((chunk + 1) & ~1) * U);
+	int   *rfloor = tfl + A4;
+
+	uint32_t tu, tv, zl;
+	if (!staged_tile_of(q, true, tu, tv, zl)) return;        /* whole block */
+	const uint32_t z = p.z_first + zl;
+	const uint32_t u_axis = q.u_axis, v_axis = 1u - q.u_axis;
+	const bool rx_rows = (p.transmits[0].flags & BF_RX_ROWS) != 0;
+	const uint32_t tid = threadIdx.x;
+	if (q.depth_major & 2u) staged_violation_clear(tid);
+	/* the thread index through an opaque copy: values derived from it per chunk, pair or round are rebuilt there rather than held
+	 * across the channel loop (register budget: 64 at 8 waves per SIMD) */
+	auto opaque_tid = [&]() -> uint32_t { uint32_t t = tid; asm volatile("" : "+v"(t)); return t; };
+
+	/* the tile's slice of the global table: [A4] floors, {lo, hi} of the absolute delays, then per row pair w < 16 and batch of 2
+	 * transmits 48 bytes: {T''_A, T''_B of a, of a + 1}, {cos, sin}_A, {cos, sin}_B of a, the same of a + 1 */
+	const unsigned char *tile_tab = reinterpret_cast<const unsigned char *>(q.tables) + (size_t)(zl * q.tiles[1] + tv) * q.table_stride;
+	typedef __attribute__((address_space(4))) const int const_int;
+	const_int *tab_floor = (const_int *)(uintptr_t)tile_tab;
+	for (uint32_t a = tid; a < A4; a += 1024u) tfl[a] = reinterpret_cast<const int *>(tile_tab)[a];
+	if (tid == 0) stage[(size_t)G0 * B] = f32x4{0.f, 0.f, 0.f, 0.f};
+	f32x2 range = *reinterpret_cast<const f32x2 *>(tile_tab + 4u * A4);
+	{
+		const float lo = range.x, hi = range.y;              /* (scalar temporaries: see staged_body) */
+		range.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lo)));
+		range.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, hi)));
+	}
+
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+	const uint32_t h = (tid >> 5) & 1u, lu = tid & 31u;
+	/* a lane's voxels: rows w and w + 16 at u; row w + 16 is inside only if row w is.  A wave with no voxel inside skips the arithmetic
+	 * (wave uniform: the pair's exchange below needs all 64 lanes); lanes outside the grid of a partly inside wave compute voxels of
+	 * the tile that are never stored -- inside the tile, so inside the host's window bound */
+	bool inside;
+	{
+		const uint32_t gu = tu * U + lu, gv = tv * 32u + wave;
+		inside = gu < p.size[u_axis] && gv < p.size[v_axis];
+	}
+	const bool wave_inside = __builtin_amdgcn_ballot_w64(inside) != 0ull;
+
+	/* Staging: per round thread tid copies element e = tid + n * 1024 (n < NL) of the group's blocks: transmit a0 + e / 64 -- wave
+	 * uniform: its floor comes through a scalar load -- channel 2k + h, sample rfloor + floor(tmin_a) + (tid & 31).  lane_at: the
+	 * lane's part of the byte offset, per channel pair; a missing odd channel and the padding transmits point out of the buffer
+	 * (zeros: the padding transmits need zero windows, their |s| is summed with no phasor). */
+	const __amdgpu_buffer_rsrc_t rf_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+		const_cast<void *>(p.rf), 0, (int)((uint32_t)C * (uint32_t)A * (uint32_t)S * 8u), 0x00020000);
+	auto lane_at_of = [&](int c0, int cl) -> uint32_t {
+		return c0 + cl < C ? ((uint32_t)(c0 + cl) * (uint32_t)A * (uint32_t)S + (uint32_t)(rfloor[cl] + (int)(opaque_tid() & 31u))) * 8u : 0x80000000u;
+	};
+	auto stage_load = [&](uint32_t lane_at, uint32_t g, f32x2 (&regs)[NL]) {
+		const uint32_t a0 = g * G0, gn = A4 - a0 < G0 ? A4 - a0 : G0;
+		#pragma unroll
+		for (int n = 0; n < NL; n++) {
+			const uint32_t al = wave + (uint32_t)n * 16u, a = a0 + al;
+			const bool real = al < gn && a < (uint32_t)A;                        /* wave uniform */
+			const uint32_t off = real ? lane_at + ((a * (uint32_t)S + (uint32_t)tab_floor[real ? a : 0]) * 8u) : 0x80000000u;
+			i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rf_rsrc, (int)off, 0, 0);
+			regs[n] = __builtin_bit_cast(f32x2, v);
+		}
+	};
+	auto stage_store = [&](uint32_t g, const f32x2 (&regs)[NL]) {
+		const uint32_t a0 = g * G0, gn = A4 - a0 < G0 ? A4 - a0 : G0;
+		const uint32_t tid = opaque_tid();
+		const float half_minus_j = 0.5f - (float)(tid & 63u);  /* the line of element e in the coordinate 1/2 - (e mod 64) */
+		#pragma unroll
+		for (int n = 0; n < NL; n++) {
+			const float sx = regs[n].x, sy = regs[n].y;
+			const float nx = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sx), 0x130, 0xf, 0xf, true));
+			const float ny = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sy), 0x130, 0xf, 0xf, true));
+			const float dx = nx - sx, dy = ny - sy;
+			const uint32_t e = tid + (uint32_t)n * 1024u;
+			if (e < gn * B) stage[e] = f32x4{__builtin_fmaf(half_minus_j, dx, sx), __builtin_fmaf(half_minus_j, dy, sy), dx, dy};
+		}
+	};
+
+	f32x2 coherent   = {0.f, 0.f};                         /* the lane's voxel after the exchanges: row w (l < 32), row w + 16 (l >= 32) */
+	float incoherent = 0.f;
+	/* lanes l and l + 32 hold the even and the odd channel's sums of the same two voxels {x of voxel A, y of voxel B}: after one
+	 * exchange (v_permlane32_swap) lane l holds A's two, lane l + 32 B's two */
+	auto exchange = [](float x, float y) -> float {
+		const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, x), __builtin_bit_cast(uint32_t, y), false, false);
+		return __builtin_bit_cast(float, (uint32_t)r[0]) + __builtin_bit_cast(float, (uint32_t)r[1]);
+	};
+	const f32x4 *Rl = R + (size_t)h * U + lu;               /* the lane's entry of pair k: Rl[2k * U] */
+	const uint32_t ulast = (uint32_t)(S - 1);
+	const const_f32x4 *rows = (const_f32x4 *)(uintptr_t)(tile_tab + 4u * A4 + 16u) + (size_t)wave * (A4 / 2u) * 3u;
+
+	typedef __attribute__((address_space(4))) const BfDasArgs const_args;
+	const_args *kernel_args = (const_args *)__builtin_amdgcn_kernarg_segment_ptr();
+	for (int c0 = 0; c0 < C; c0 += chunk) {
+		const int cn = (C - c0) < chunk ? (C - c0) : chunk;
+		const int cn2 = (cn + 1) & ~1;                       /* rows of the receive table: an odd last channel gets a zero partner */
+		__syncthreads();        /* readers of the previous chunk's R / stage are done; tfl is complete */
+		{
+		const_args *ka = kernel_args;                        /* (through the kernel-argument segment: see staged_body) */
+		asm volatile("" : "+s"(ka));
+		const uint32_t k_size[3] = {ka->size[0], ka->size[1], ka->size[2]};
+		const float k_denom_u = fmaxf(1.0f, (float)k_size[u_axis] - 1.0f);
+		const float k_pz = (float)z / fmaxf(1.0f, (float)k_size[2] - 1.0f);
+		const float k_fs = ka->sampling_frequency, k_inv_c = ka->inv_speed_of_sound, k_c = ka->speed_of_sound, k_fnum = ka->f_number;
+		const float k_phase = ka->demodulation_frequency * ka->inv_sampling_frequency;
+		const float k_pitch = rx_rows ? ka->pitch[1] : ka->pitch[0];
+		for (uint32_t e = opaque_tid(); e < (uint32_t)cn2 * U; e += 1024u) {
+			uint32_t cl = e >> 5, iu = e & (U - 1);
+			f32x4 entry = {0.f, 0.f, 0.f, 0.f};
+			if ((int)cl < cn) {
+				uint32_t c = (uint32_t)c0 + cl;
+				float coord[3] = {0.f, 0.f, k_pz};
+				coord[u_axis] = (float)(tu * U + iu) / k_denom_u;
+				float wx, wy, wz, xx, xy, xz;
+				m4_point(ka->voxel_transform, coord[0], coord[1], coord[2], wx, wy, wz);
+				m4_point(ka->xdc_transform, wx, wy, wz, xx, xy, xz);
+				float lateral = rx_rows ? xy : xx;
+				float dx      = lateral - (float)c * k_pitch;
+				float a_arg   = __builtin_fabsf(dx * (k_fnum * hw_rcp(__builtin_fabsf(xz))));
+				float r_idx = div_speed_of_sound(hw_sqrt(dx * dx + xz * xz), k_inv_c, k_c) * k_fs;
+				entry.x = r_idx;
+				if (a_arg < 0.5f) {
+					float cs    = hw_cos_turns(0.5f * a_arg);
+					float apod  = cs * cs;
+					float turns = staged_phase_turns(k_phase, r_idx);
+					entry.y = apod * hw_cos_turns(turns);
+					entry.z = apod * hw_sin_turns(turns);
+					entry.w = apod;
+				}
+			}
+			R[e] = entry;
+		}
+		}
+		__syncthreads();
+		for (uint32_t cl = opaque_tid(); cl < (uint32_t)cn2; cl += 1024u) {
+			const float *row = reinterpret_cast<const float *>(R + (size_t)cl * U);
+			float m = row[0];
+			#pragma unroll 4
+			for (uint32_t iu = 1; iu < U; iu++) m = fminf(m, row[4 * iu]);
+			rfloor[cl] = (int)__builtin_floorf(m);
+		}
+		__syncthreads();
+		/* window-relative delay plus the half offset h * W of the lane's window in the block; the sign of the weight: the lane may leave
+		 * the RF row for some transmit of the tile (the zero partner of an odd channel never does) */
+		for (uint32_t e = opaque_tid(); e < (uint32_t)cn2 * U; e += 1024u) {
+			f32x4 entry = R[e];
+			const uint32_t cl = e >> 5;
+			const bool lane_safe = (int)cl >= cn || ((entry.x + range.x >= 0.f) && (entry.x + range.y < (float)(S - 1)));
+			entry.x = (entry.x - (float)rfloor[cl]) + (float)((cl & 1u) * W);     /* both steps exact */
+			if (!lane_safe) entry.w = -entry.w;
+			R[e] = entry;
+		}
+		__syncthreads();
+
+		f32x2 regs[NL];
+		stage_load(lane_at_of(c0, (int)h), 0, regs);
+		for (int k = 0; k < cn2 / 2; k++) {
+			f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f};
+			f32x2 mag2 = {0.f, 0.f};                         /* {voxel A, voxel B} */
+			for (uint32_t g = 0; g < ngroups; g++) {
+				__syncthreads();               /* everyone is done with the previous round's windows */
+				stage_store(g, regs);
+				__syncthreads();
+				if (g + 1 < ngroups)     stage_load(lane_at_of(c0, 2 * k + (int)h), g + 1, regs);     /* in flight during the arithmetic */
+				else if (2 * k + 2 < cn2) stage_load(lane_at_of(c0, 2 * k + 2 + (int)h), 0, regs);
+				if (!wave_inside) continue;
+
+				float r_rel, r_w;
+				{
+					const f32x4 r = Rl[(size_t)(2 * k) * U];
+					r_rel = r.x; r_w = r.w;
+				}
+				if (__builtin_amdgcn_ballot_w64(r_w != 0.f) == 0) continue;    /* F# culling per wave (both channels of the pair) */
+				const bool wave_safe = !(q.depth_major & 2u) && __builtin_amdgcn_ballot_w64(__builtin_signbitf(r_w)) == 0;
+				auto term = [&](f32x2 cs, float pos, f32x4 tap, f32x2 &acc1, f32x2 &acc2) -> float {
+					f32x2 sv = f32x2{tap.x, tap.y} + pos * f32x2{tap.z, tap.w};
+					acc1 += sv.x * cs;
+					acc2 += sv.y * cs;
+					if constexpr (CW) return hw_sqrt(__builtin_fmaf(sv.y, sv.y, sv.x * sv.x));
+					else return 0.f;
+				};
+				const uint32_t a0 = g * G0, gn = A4 - a0 < G0 ? A4 - a0 : G0;
+				auto batches = [&](auto checked) {
+					constexpr bool CHECK = decltype(checked)::value;
+					/* position -> tap as staged_body; M = 2^23 + 2 + (the batch's first block) * 64, the lane's window starts h * W
+					 * further (its receive entry carries that offset) */
+					uint32_t m_bits = 0x4B000002u;
+					[[maybe_unused]] bool window_left = false;
+					[[maybe_unused]] int rfl_h = 0;                          /* checked loop: rfloor of the lane's channel - h * W */
+					if constexpr (CHECK) rfl_h = rfloor[2 * k + (int)h] - (int)(h * W);
+					const f32x2 rr = {r_rel, r_rel};
+					const_f32x4 *row = rows + (size_t)(a0 / 2u) * 3u;
+					for (uint32_t a = 0; a < gn; a += 2, m_bits += 2u * B) {
+						uint32_t at[4]; f32x4 tap[4];
+						const float M = __builtin_bit_cast(float, m_bits);
+						const f32x2 M2 = {M, M};
+						const f32x4 tz = row[0], cs0 = row[1], cs1 = row[2];
+						row += 3;
+						const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};   /* {A, B} of transmit a, of a + 1 */
+						const f32x2 y0 = p0 + M2, y1 = p1 + M2;
+						const float ys[4] = {y0.x, y0.y, y1.x, y1.y};
+						#pragma unroll
+						for (int t = 0; t < 4; t++) {
+							const uint32_t yb = __builtin_bit_cast(uint32_t, ys[t]);
+							asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[t]) : "v"(yb));
+							if constexpr (CHECK) {
+								uint32_t lane_id = tid;
+								asm volatile("" : "+v"(lane_id));                            /* h * W = tid & 32, not held across the loop */
+								const uint32_t rel = yb - m_bits;                             /* round(p) in the transmit's block */
+								const uint32_t k_abs = (uint32_t)((int)rel + rfl_h + tfl[a0 + a + (uint32_t)(t >> 1)]);
+								at[t] = k_abs < ulast ? at[t] + (uint32_t)(t >> 1) * B * 16u : (G0 * B + 2u) * 16u;
+								window_left |= __builtin_amdgcn_ballot_w64(inside && rel - (lane_id & 32u) > W - 2u) != 0ull;   /* (voxels in the grid) */
+							}
+						}
+						#pragma unroll
+						for (int t = 0; t < 4; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
+						const float qa0 = term(f32x2{cs0.x, cs0.y}, p0.x, tap[0], acc1a, acc2a);
+						const float qb0 = term(f32x2{cs0.z, cs0.w}, p0.y, tap[1], acc1b, acc2b);
+						const float qa1 = term(f32x2{cs1.x, cs1.y}, p1.x, tap[2], acc1a, acc2a);
+						const float qb1 = term(f32x2{cs1.z, cs1.w}, p1.y, tap[3], acc1b, acc2b);
+						if constexpr (CW) { mag2 += f32x2{qa0, qb0}; mag2 += f32x2{qa1, qb1}; }
+					}
+					if constexpr (CHECK) { if (window_left) staged_violation_raise(); }
+				};
+				if (wave_safe) batches(std::false_type{});
+				else           batches(std::true_type{});
+				if (g + 1 < ngroups) continue;
+				/* the pair's fold: the lane's channel's term of both voxels, then the two channels of the pair summed per voxel */
+				float sa_x = acc1a.x - acc2a.y, sa_y = acc1a.y + acc2a.x;
+				float sb_x = acc1b.x - acc2b.y, sb_y = acc1b.y + acc2b.x;
+				asm volatile("" : "+v"(sa_x), "+v"(sa_y), "+v"(sb_x), "+v"(sb_y));
+				const f32x4 r = *(volatile lds_f32x4 *)(uintptr_t)((uint32_t)(uintptr_t)(lds_f32x4 *)Rl + (uint32_t)(2 * k) * U * 16u);
+				const float ca_x = __builtin_fmaf(sa_x, r.y, -sa_y * r.z), ca_y = __builtin_fmaf(sa_x, r.z, sa_y * r.y);
+				const float cb_x = __builtin_fmaf(sb_x, r.y, -sb_y * r.z), cb_y = __builtin_fmaf(sb_x, r.z, sb_y * r.y);
+				coherent.x += exchange(ca_x, cb_x);
+				coherent.y += exchange(ca_y, cb_y);
+				if constexpr (CW) incoherent += exchange(__builtin_fabsf(r.w) * mag2.x, __builtin_fabsf(r.w) * mag2.y);
+			}
+		}
+	}
+	if (q.depth_major & 2u) staged_violation_report(tid);      /* (block uniform: every thread reaches it) */
+	uint32_t thread = tid;
+	asm volatile("" : "+v"(thread));                      /* not the values computed before the loop */
+	const uint32_t gu = tu * U + (thread & 31u), gv = tv * 32u + (thread >> 6) + ((thread >> 5) & 1u) * 16u;
+	if (!(gu < p.size[u_axis] && gv < p.size[v_axis])) return;
+	const uint32_t x = u_axis == 0 ? gu : gv, y = u_axis == 0 ? gv : gu;
+	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
+	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
+	reinterpret_cast<f32x2 *>(p.out)[out_index] = coherent;
+}
+
+template <bool CW, int VS, int WS, int NL, bool UNI, bool PAIRED>
+__global__ __launch_bounds__(1024, 8) void das_rca_staged_kernel(const BfDasArgs p, const BfSeparableArgs q)
+{
+	if constexpr (PAIRED) staged_paired_body<CW, NL>(p, q);
+	else                  staged_body<CW, VS, WS, NL, UNI>(p, q);
+}
+
 template <bool CW, int VS, int WS, int NL, bool UNI>
 static hipError_t launch_staged(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
 	uint32_t total = q->tiles[0] * q->tiles[1] * q->tiles[2];
 	if (UNI && (q->depth_major & 4u)) total = q->tiles[0] * q->tiles[1] * ((q->tiles[2] + 31u) >> 5) * 32u;   /* the paired walk pads the planes to chunks of 32 */
 	uint32_t grid  = ((total + 7u) / 8u) * 8u;
-	auto kernel = das_rca_staged_kernel<CW, VS, WS, NL, UNI>;
+	auto kernel = das_rca_staged_kernel<CW, VS, WS, NL, UNI, false>;
 	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(kernel, dim3(grid), dim3(q->threads), q->lds_bytes, s, *a, *q);
@@ -506,9 +792,37 @@ static hipError_t launch_staged_loads(const BfDasArgs *a, const BfSeparableArgs 
 	return hipErrorInvalidValue;
 }
 
+template <bool CW, int NL>
+static hipError_t launch_staged_paired(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
+{
+	const uint32_t total = q->tiles[0] * q->tiles[1] * ((q->depth_major & 4u) ? ((q->tiles[2] + 31u) >> 5) * 32u : q->tiles[2]);
+	const uint32_t grid  = ((total + 7u) / 8u) * 8u;
+	auto kernel = das_rca_staged_kernel<CW, 5, 5, NL, true, true>;
+	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), q->lds_bytes, s, *a, *q);
+	return hipGetLastError();
+}
+
 template <bool CW>
 static hipError_t launch_staged_shape(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
+	if (q->uniform == 2) {
+		/* the channel-paired form: 32 x 32 tiles, 32-sample windows, 1024 threads, an even chunk of channels (or all of them) */
+		if (q->u_shift != 5 || q->v_shift != 5 || q->window_samples != 32 || q->threads != 1024 || !q->tables ||
+		    ((q->channel_chunk & 1u) && (int)q->channel_chunk < a->channel_count)) return hipErrorInvalidValue;
+		const uint32_t A4 = ((uint32_t)a->acquisition_count + 3u) & ~3u;
+		const uint32_t ngroups = (A4 + BF_STAGED_PAIRED_GROUP_MAX - 1u) / BF_STAGED_PAIRED_GROUP_MAX;
+		const uint32_t G0 = ((A4 + ngroups - 1u) / ngroups + 3u) & ~3u;
+		switch ((G0 * 64u + 1023u) / 1024u) {                /* staging passes of the largest group (one pass: as two -- the
+		                                                      * one-pass instance of this form spills) */
+		case 1:
+		case 2: return launch_staged_paired<CW, 2>(a, q, s);
+		case 3: return launch_staged_paired<CW, 3>(a, q, s);
+		case 4: return launch_staged_paired<CW, 4>(a, q, s);
+		}
+		return hipErrorInvalidValue;
+	}
 	if (q->uniform) {
 		/* wave-uniform transmit tables: a 64 x 16 tile with x along the receive axis, 1024 threads, tables written by bf_launch_das_staged_tables */
 		if (q->u_axis != 0 || q->u_shift != 6 || q->v_shift != 4 || q->threads != 1024 || !q->tables) return hipErrorInvalidValue;
@@ -540,10 +854,11 @@ extern "C" hipError_t bf_launch_das_staged(const BfDasArgs *a, const BfSeparable
  * kernel's own table build (same functions, same order: the entries are bit-identical to what a block would compute in LDS).
  * Layout per tile slice of q.table_stride bytes: int floor(tmin_a)[A4] | {lo, hi} of the absolute delays + 8 bytes of padding |
  * per lateral row iv < 16 and batch b < A4 / 4: {T'' of transmits 4b .. 4b + 3}, {cos, sin} of 4b, 4b + 1, {cos, sin} of 4b + 2, 4b + 3. */
+template <int VS>
 __global__ __launch_bounds__(256) void staged_tables_kernel(const BfDasArgs p, const BfSeparableArgs q)
 {
 	extern __shared__ __attribute__((aligned(16))) f32x4 tables_lds[];
-	constexpr uint32_t VS = 4, V = 1u << VS;
+	constexpr uint32_t V = 1u << VS;
 	const int A = p.acquisition_count;
 	const int A4 = (A + 3) & ~3;
 	float *t  = reinterpret_cast<float *>(tables_lds);                 /* [A4][V] */
@@ -607,8 +922,22 @@ __global__ __launch_bounds__(256) void staged_tables_kernel(const BfDasArgs p, c
 		reinterpret_cast<int *>(tile_tab)[a] = (int)fl;
 	}
 	__syncthreads();
-	const uint32_t batches = (uint32_t)A4 / 4u;
 	f32x4 *rows = reinterpret_cast<f32x4 *>(tile_tab + 4u * (uint32_t)A4 + 16u);
+	if constexpr (VS == 5) {
+		/* the channel-paired form: per row pair w < 16 (rows w, w + 16) and batch of 2 transmits a = 2b, a + 1 */
+		const uint32_t batches = (uint32_t)A4 / 2u;
+		for (uint32_t e = tid; e < 16u * batches; e += nthreads) {
+			const uint32_t w = e / batches, b = e % batches;
+			const float *t2 = t + (size_t)(2u * b) * V + w;
+			const f32x2 *c2 = cs + (size_t)(2u * b) * V + w;
+			f32x4 *row = rows + (size_t)e * 3u;
+			row[0] = f32x4{t2[0], t2[16], t2[V], t2[V + 16]};
+			row[1] = f32x4{c2[0].x, c2[0].y, c2[16].x, c2[16].y};
+			row[2] = f32x4{c2[V].x, c2[V].y, c2[V + 16].x, c2[V + 16].y};
+		}
+		return;
+	}
+	const uint32_t batches = (uint32_t)A4 / 4u;
 	for (uint32_t e = tid; e < V * batches; e += nthreads) {
 		const uint32_t iv = e / batches, b = e % batches;
 		const float *t4 = t + (size_t)(4u * b) * V + iv;
@@ -623,10 +952,20 @@ __global__ __launch_bounds__(256) void staged_tables_kernel(const BfDasArgs p, c
 /* one launch per frame and shard, before bf_launch_das_staged with q->uniform set; q->tables holds q->tiles[1] * q->tiles[2] slices */
 extern "C" hipError_t bf_launch_das_staged_tables(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
-	if (!q->uniform || !q->tables || q->v_shift != 4) return hipErrorInvalidValue;
 	const uint32_t A4 = ((uint32_t)a->acquisition_count + 3u) & ~3u;
-	if (q->table_stride < 4u * A4 + 16u + 16u * (A4 / 4u) * 48u) return hipErrorInvalidValue;
-	const uint32_t lds = A4 * 16u * 12u + 64u;
-	hipLaunchKernelGGL(staged_tables_kernel, dim3(q->tiles[1] * q->tiles[2]), dim3(256), lds, s, *a, *q);
-	return hipGetLastError();
+	if (!q->tables) return hipErrorInvalidValue;
+	if (q->uniform == 1 && q->v_shift == 4) {
+		if (q->table_stride < 4u * A4 + 16u + 16u * (A4 / 4u) * 48u) return hipErrorInvalidValue;
+		hipLaunchKernelGGL(staged_tables_kernel<4>, dim3(q->tiles[1] * q->tiles[2]), dim3(256), A4 * 16u * 12u + 64u, s, *a, *q);
+		return hipGetLastError();
+	}
+	if (q->uniform == 2 && q->v_shift == 5) {
+		if (q->table_stride < 4u * A4 + 16u + 16u * (A4 / 2u) * 48u) return hipErrorInvalidValue;
+		const uint32_t lds = A4 * 32u * 12u + 64u;
+		hipError_t e = hipFuncSetAttribute((const void *)staged_tables_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL(staged_tables_kernel<5>, dim3(q->tiles[1] * q->tiles[2]), dim3(256), lds, s, *a, *q);
+		return hipGetLastError();
+	}
+	return hipErrorInvalidValue;
 }

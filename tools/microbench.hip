@@ -15,6 +15,7 @@
  *   lds       ds_read_b64, ds_read_b128 (16-B aligned), ds_read2_b64 (16 B at 8-B alignment) with
  *             the same three patterns: bytes per clock per CU
  * Nothing here is on the product path; it is the evidence behind roofline.binding in bench.py.
+ * `microbench --loops` runs only the staged kernel's inner-loop probes (loop_probe, loop_probe_uniform, loop_probe_paired), twice.
  */
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -455,6 +456,63 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_uniform(const f32x4 *table
 	}
 }
 
+/* The channel-paired form (das_staged.hip, PAIRED): config 4's 32 x 32 tile with lane l of wave w beamforming rows w and w + 16 at
+ * u = l & 31 for channel parity h = l >> 5, so all 64 lanes share one PAIR of transmit-axis rows.  The LDS holds per transmit a
+ * 64-element block (channel 2k's 32-sample window, then channel 2k + 1's; the lane's position carries h * 32), one group of
+ * transmits at a time (40 + 36 of the 76).  Per batch of 2 transmits: {T_A, T_B} x 2 and the four phasors from a global table
+ * through scalar loads (48 bytes), one packed add per transmit forms both voxels' positions, four taps from the LDS. */
+__global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table, Stamp *stamps, float *sink, int iters)
+{
+	extern __shared__ __attribute__((aligned(16))) f32x4 probe_lds[];
+	constexpr uint32_t G0 = 40, G1 = 36, B = 64;
+	for (uint32_t i = threadIdx.x; i < G0 * B + 3; i += blockDim.x) probe_lds[i] = f32x4{0.5f + 0.001f * i, 0.25f, 0.125f, -0.5f};
+	__syncthreads();
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t lane = threadIdx.x & 63u;
+	const float r_rel = 0.4f * (float)(lane & 31u) + 32.f * (float)(lane >> 5);
+	typedef __attribute__((address_space(4))) const f32x4 const_f32x4;
+	const_f32x4 *row = (const_f32x4 *)(uintptr_t)(table + (size_t)wave * ((G0 + G1) / 2) * 3);   /* per wave and batch: {TA0, TB0, TA1, TB1}, {csA0, csB0}, {csA1, csB1} */
+	f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f}, mag2 = {0.f, 0.f};
+	uint64_t t0 = memtime(), r0 = memrealtime();
+	for (int i = 0; i < iters; i++) {
+		const f32x2 rr = {r_rel, r_rel};
+		const_f32x4 *at_row = row;
+		for (uint32_t g = 0; g < 2; g++) {
+			const uint32_t n = g ? G1 : G0;
+			uint32_t m_bits = 0x4B000002u;
+			for (uint32_t a = 0; a < n; a += 2, at_row += 3, m_bits += 2u * B) {
+				const float M = __builtin_bit_cast(float, m_bits);
+				const f32x2 M2 = {M, M};
+				const f32x4 tz = at_row[0], cs0 = at_row[1], cs1 = at_row[2];
+				const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};
+				const f32x2 y0 = p0 + M2, y1 = p1 + M2;
+				const float ys[4] = {y0.x, y0.y, y1.x, y1.y}, ps[4] = {p0.x, p0.y, p1.x, p1.y};
+				uint32_t at[4]; f32x4 tap[4];
+				#pragma unroll
+				for (int k = 0; k < 4; k++) asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[k]) : "v"(__builtin_bit_cast(uint32_t, ys[k])));
+				#pragma unroll
+				for (int k = 0; k < 4; k++) tap[k] = *(mb_lds_f32x4 *)(uintptr_t)(at[k] + (uint32_t)(k >> 1) * B * 16u);
+				const f32x2 cs[4] = {{cs0.x, cs0.y}, {cs0.z, cs0.w}, {cs1.x, cs1.y}, {cs1.z, cs1.w}};
+				float q[4];
+				#pragma unroll
+				for (int k = 0; k < 4; k++) {
+					f32x2 sv = f32x2{tap[k].x, tap[k].y} + ps[k] * f32x2{tap[k].z, tap[k].w};
+					if (k & 1) { acc1b += sv.x * cs[k]; acc2b += sv.y * cs[k]; }
+					else       { acc1a += sv.x * cs[k]; acc2a += sv.y * cs[k]; }
+					q[k] = __builtin_amdgcn_sqrtf(__builtin_fmaf(sv.y, sv.y, sv.x * sv.x));
+				}
+				mag2 += f32x2{q[0], q[1]}; mag2 += f32x2{q[2], q[3]};
+			}
+		}
+	}
+	uint64_t t1 = memtime(), r1 = memrealtime();
+	if (mag2.x + mag2.y + acc1a.x + acc1a.y + acc2a.x + acc2a.y + acc1b.x + acc1b.y + acc2b.x + acc2b.y == 12345.678f) sink[0] = mag2.x;
+	if ((threadIdx.x & 63) == 0) {
+		uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+		stamps[w] = Stamp{t1 - t0, r1 - r0};
+	}
+}
+
 /* ------------------------------------------------------------------ per-lane gathers from global memory */
 enum { PAT_COALESCED, PAT_DAS, PAT_RANDOM, PAT_COUNT };
 static const char *pat_name[PAT_COUNT] = {"contiguous", "das_like", "random"};
@@ -715,6 +773,30 @@ static void loop_uniform_case(const char *what)
 	CHECK(hipFree(d_table));
 }
 
+static void loop_paired_case(const char *what)
+{
+	const int iters = 1000;                            /* 152k terms per wave: 76 transmits x 2 voxels per iteration */
+	const uint32_t lds = 16u * (40u * 64u + 3u) + 64u;
+	CHECK(hipFuncSetAttribute((const void *)loop_probe_paired, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	std::vector<float> h(16 * 38 * 12);
+	for (int w = 0; w < 16; w++) for (int b = 0; b < 38; b++) {
+		float *e = &h[(size_t)(w * 38 + b) * 12];
+		for (int k = 0; k < 4; k++) e[k] = 1.f + 0.3f * (w + 16 * (k & 1)) + 0.7f * (float)((2 * b + (k >> 1)) % 5);
+		for (int k = 0; k < 4; k++) { e[4 + 2 * k] = 0.6f; e[5 + 2 * k] = 0.8f; }
+	}
+	f32x4 *d_table;
+	CHECK(hipMalloc(&d_table, h.size() * 4));
+	CHECK(hipMemcpy(d_table, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+	int blocks = n_cu * 2, waves = blocks * 16;
+	Result r = run([&] { hipLaunchKernelGGL(loop_probe_paired, dim3(blocks), dim3(1024), lds, 0, d_table, d_stamps, d_sink, iters); }, waves);
+	double terms = 152.0 * iters;
+	double wall_cycles = r.wall_ms * 1e-3 * r.clock_ghz * 1e9;
+	emit(",\n  {\"stream\":\"%s\",\"waves_per_simd\":8,"
+	     "\"cycles_per_term_per_simd_wall\":%.3f,\"cycles_per_term_per_simd_stamps\":%.3f,\"clock_ghz\":%.3f,\"wall_ms\":%.3f}",
+	     what, wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
+	CHECK(hipFree(d_table));
+}
+
 static char *d_window;
 
 template <int WIDTH, int PAT> static void gather_case(const char *level, uint32_t window, bool per_block, bool &first)
@@ -769,6 +851,17 @@ int main(int argc, char **argv)
 	CHECK(hipMalloc(&d_window, 512u << 20));
 	CHECK(hipMemset(d_window, 0, 512u << 20));
 	bool quick = argc > 1 && !strcmp(argv[1], "--quick");
+	if (argc > 1 && !strcmp(argv[1], "--loops")) {          /* the inner-loop probes of the staged kernel only */
+		emit("{\"device\":\"%s\",\"loops\":[\n  {\"stream\":\"(start)\"}", prop.name);
+		for (int rep = 0; rep < 2; rep++) {
+			loop_case<1>("das_staged inner loop with its LDS reads: address by v_lshlrev_b16");
+			loop_uniform_case("das_staged inner loop, wave-uniform delays and phasors through scalar loads (a 64 x 16 tile), LDS serves the taps only");
+			loop_paired_case("das_staged inner loop, channel-paired (32 x 32 tile, two voxels per lane, transmit groups of 40 + 36): scalar delays and phasors, LDS serves the taps only");
+		}
+		emit("]}\n");
+		fputs(json.c_str(), stdout);
+		return 0;
+	}
 
 	emit("{\"device\":\"%s\",\"arch\":\"%s\",\"compute_units\":%d,\"clock_rate_khz\":%d,\n", prop.name, prop.gcnArchName, n_cu, prop.clockRate);
 	emit(" \"method\":\"loops of inline-asm instructions, every CU busy with the stated waves per SIMD; clock_ghz = in-kernel s_memtime / s_memrealtime "
