@@ -315,6 +315,8 @@ typedef struct {
 	uint32_t tile_estimate_shift[3];/* ... and the tile it was computed for */
 	uint32_t row_ends;              /* 1: some in-aperture term of the launch may come within reach of an end of its RF row (a host bound, per plane, in
 	                                   double precision): the kernel's instantiation WITH the exact row-end evaluation runs (csrc/das_exact.h); 0: the one without */
+	int32_t  row_end_path;          /* the kernel (path numbering as above) of the planes the row-end rule re-routed -- of the most of them where
+	                                   there is more than one such run --; -1 when row_end_planes is 0 */
 } BeamformerHipDasDescription;
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_das(uint32_t parameter_slot, BeamformerHipDasDescription *out);
 

@@ -946,8 +946,10 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 	}
 	if (all) { whole.a.row_ends = whole.general.row_ends = 0; return; }      /* no term of this launch comes near a row end */
 	if (whole.path != DasPath_Staged && whole.path != DasPath_Tile) return;    /* every other kernel evaluates such terms itself */
-	/* the kernel behind the staged one: "automatic, never staged" with block staging off */
-	const uint32_t fallback_mode = (mode & ~0xFu & ~0x100u) | 0x200u | ((mode & 0xFu) == 1u ? 1u : 2u);
+	/* the kernel behind the staged one, with block staging off: the one asked for where it evaluates row ends itself (1: general,
+	 * 4: factored), else "automatic, never staged" (a request for the LDS-staged kernel, 3, included) */
+	const uint32_t asked = mode & 0xFu;
+	const uint32_t fallback_mode = (mode & ~0xFu & ~0x100u) | 0x200u | (asked == 1u || asked == 4u ? asked : 2u);
 	std::vector<DasDecision> cut;
 	uint32_t runs = 1;
 	for (uint32_t k = 1; k < zcount; k++) runs += clear[k] != clear[k - 1];
@@ -957,8 +959,10 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 		cut.emplace_back();
 		DasDecision &d = cut.back();
 		decide_das(pb, plan, tx, zfirst + begin, k - begin, clear[begin] ? mode : fallback_mode, d);
-		if (!clear[begin] && (d.path == DasPath_Staged || d.path == DasPath_Tile))
-			decide_das(pb, plan, tx, zfirst + begin, k - begin, (mode & ~0xFu & ~0x100u) | 0x200u | 1u, d);     /* (cannot happen: the general kernel) */
+		if (!clear[begin] && (d.path == DasPath_Staged || d.path == DasPath_Tile)) {
+			d = DasDecision{};                                                        /* (cannot happen: the general kernel) */
+			decide_das(pb, plan, tx, zfirst + begin, k - begin, (mode & ~0xFu & ~0x100u) | 0x200u | 1u, d);
+		}
 		d.row_end_fallback = !clear[begin];
 		d.a.row_ends = d.general.row_ends = clear[begin] ? 0u : 1u;
 		begin = k;

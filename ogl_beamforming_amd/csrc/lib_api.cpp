@@ -618,6 +618,10 @@ uint32_t beamformer_hip_describe_das(uint32_t parameter_slot, BeamformerHipDasDe
 	out->tile_spread_estimate = d.tile_spread;
 	for (int k = 0; k < 3; k++) out->tile_estimate_shift[k] = d.tile_estimate_shift[k];
 	out->row_ends = d.a.row_ends;
+	out->row_end_path = -1;
+	uint32_t most = 0;
+	for (const DasDecision &p : parts)
+		if (p.row_end_fallback && p.z_count > most) { most = p.z_count; out->row_end_path = p.path == DasPath_Zero ? -2 : p.path; }
 	return 1;
 }
 

@@ -146,7 +146,9 @@ def beamform(bp, rf, filters=(), threads=0, z=(0, 0), y=(0, 0), timing=None, str
     between the computed planes / rows.  Returns (frame (Z, Y, X) float32|complex64, pairs);
     timing (a dict) receives das_seconds; flags (a dict) receives, for nearest interpolation, "budget": per
     voxel the sum of |other sample - chosen sample| over the taps whose index sat within 2^-10 of a rounding
-    boundary (what tap flips can move the coherent sum by), and "near_half" = budget > 0; truth (a dict) receives "frame": the
+    boundary (what tap flips can move the coherent sum by), and "near_half" = budget > 0 -- for linear and cubic interpolation
+    the sum of |sample at the row's end| over the taps whose index sat within 2^-16 * max(S, 1024) of an end of the valid range
+    of the row (the taps whose keeping or dropping float rounding decides), "near_half" then marking the voxels that have one; truth (a dict) receives "frame": the
     same frame with every DAS stage run in double precision on the same float32 DAS input (oracle_set_f64_frame) -- complex128 / float64;
     das_input (a dict) receives "data": every chunk's DAS input assembled as (channels, transmits, DAS samples), float32 / complex64
     (oracle_set_das_input_capture) -- what the library's beamformer_hip_copy_das_input returns."""

@@ -234,7 +234,9 @@ int  oracle_beamform(const OracleParameterBlock *pb, const void *raw, float *out
  * zeroed by the caller), oracle_das adds to each voxel the ambiguity budget of its sum: for every tap whose
  * sample index lies within 2^-10 of a rounding boundary (k + 1/2, or an end of the valid range), where an
  * implementation that differs by float rounding legitimately picks the other sample, |other - chosen|.
- * A voxel with a zero entry has no such tap.  NULL switches it off. */
+ * A voxel with a zero entry has no such tap.  Linear and cubic interpolation: the same for every tap within 2^-16 * max(S, 1024)
+ * samples of an end of the valid range of its row (a step: kept on one side, dropped on the other), |sample at the row's end|.
+ * NULL switches it off. */
 void oracle_set_nearest_ambiguity_buffer(float *budget);
 /* the double-precision twin of every DAS stage of later oracle_beamform* calls into `frame` (voxels x 1 or 2 doubles), or NULL: off */
 void oracle_set_f64_frame(double *frame);

@@ -25,6 +25,11 @@ static int oracle_thread_count(int requested)
  * the caller's buffer (when set), so a parity test can demand |gpu - oracle| <= tolerance + budget on
  * EVERY voxel instead of allowing a fraction of mismatches.  Test infrastructure, not the shader. */
 #define ORACLE_NEAR_HALF (1.0 / 1024.0)
+/* Linear and cubic interpolation: the same budget for taps within 2^-16 * max(S, 1024) samples (2^-5 for 2048-sample rows) of an
+ * end of the valid range of a row -- sample_rf's range test is a step there --, eight times the library's edge margin
+ * 2^-19 * S: the voxels where the float oracle and its double twin can keep or drop a row-end term differently (tests/parity.py: the
+ * flip set) */
+#define ORACLE_NEAR_ROW_END(S) ((double)((S) > 1024 ? (S) : 1024) / 65536.0)
 static _Thread_local float oracle_near_half_budget;
 static float *oracle_near_half_buffer;          /* one float per sub-grid voxel, or NULL */
 void oracle_set_nearest_ambiguity_buffer(float *budget) { oracle_near_half_buffer = budget; }

@@ -59,6 +59,21 @@ static inline FN(c2) FN(cubic)(const OracleDAS *p, const float *rf, int offset, 
 	return r;
 }
 
+/* test infrastructure, not part of the shader: linear and cubic interpolation keep a term while lo <= index < hi -- a step.  A tap
+ * within ORACLE_NEAR_ROW_END(S) of lo or hi may be kept by one evaluation of the index and dropped by another (this one's float and
+ * double builds among them); it adds |the sample at the row's end| (+ a tiny amount, so that the voxel is marked) to the voxel's
+ * ambiguity budget (oracle_das.c), which then marks the voxels where a row-end flip is possible */
+static inline void FN(row_end_ambiguity)(const OracleDAS *p, const float *rf, int rf_offset, REAL index, int lo, int hi)
+{
+	if (!oracle_near_half_buffer) return;
+	const REAL near = (REAL)ORACLE_NEAR_ROW_END(p->sample_count);
+	if (!(R_FABS(index - (REAL)lo) < near || R_FABS(index - (REAL)hi) < near)) return;
+	int k = R_FABS(index - (REAL)lo) < near ? lo : hi;
+	if (k > p->sample_count - 1) k = p->sample_count - 1;
+	FN(c2) a = FN(load)(p, rf, rf_offset + k);
+	oracle_near_half_budget += (float)R_SQRT(a.x * a.x + a.y * a.y) + 1e-30f;
+}
+
 /* das.glsl:99-124 */
 static inline FN(c2) FN(sample_rf)(const OracleDAS *p, const float *rf, int rf_offset, REAL index)
 {
@@ -86,6 +101,7 @@ static inline FN(c2) FN(sample_rf)(const OracleDAS *p, const float *rf, int rf_o
 		}
 	}break;
 	case BeamformerInterpolationMode_Linear:{
+		FN(row_end_ambiguity)(p, rf, rf_offset, index, 0, p->sample_count - 1);
 		if (index >= 0 && index < (REAL)(p->sample_count - 1)) {
 			REAL tk, t = R_MODF(index, &tk);
 			int  n = rf_offset + (int)tk;
@@ -96,6 +112,7 @@ static inline FN(c2) FN(sample_rf)(const OracleDAS *p, const float *rf, int rf_o
 		}
 	}break;
 	case BeamformerInterpolationMode_Cubic:{
+		FN(row_end_ambiguity)(p, rf, rf_offset, index, 1, p->sample_count - 2);
 		if (index >= 1 && index < (REAL)(p->sample_count - 2)) {
 			REAL tk, t = R_MODF(index, &tk);
 			result = FN(rotate_iq)(p, FN(cubic)(p, rf, rf_offset + (int)index, t), index / fs);

@@ -214,10 +214,10 @@ def test_full_size_configurations_stay_clear_of_row_ends_and_the_harness_planes_
 
 
 def test_random_view_planes_select_the_plane_kernels():
-    """the view-plane generator of tests/test_gpu_random.py (the reference harness's shape at test size) is aimed at the HERCULES aligned-grid
+    """the view-plane generator of tests/draws.py (the reference harness's shape at test size) is aimed at the HERCULES aligned-grid
     kernel and at the factored kernel: the selection rules say so without a device (small frames: with the channel split switched off,
     flag 0x10, as the GPU test and the fuzz ask for them)"""
-    from tests import test_gpu_random as R
+    from tests import draws as R
     L = lib.library()
     taken = {}
     L.beamformer_hip_set_das_path(0x10)
@@ -231,3 +231,63 @@ def test_random_view_planes_select_the_plane_kernels():
         L.beamformer_hip_set_das_path(0)
     assert taken[True] == {int(P.DasPath.Hercules)}, taken
     assert int(P.DasPath.Factored) in taken[False] and int(P.DasPath.Hercules) not in taken[False], taken
+
+
+def test_random_paired_draws_are_planned_in_the_channel_paired_form():
+    """tests/draws.py draw_paired, asked for the LDS-staged kernel in 32 x 32 tiles with 32-sample windows (path 3, STAGED_SHAPE 5,5,5, as
+    tests/test_gpu_staged_paired.py runs them): the channel-paired form (uniform_tables 2) is planned for nearly every draw, across one and
+    two transmit groups, padded transmit counts and odd channel counts; never for more than two groups; and the short-row draws hand
+    their deepest plane to the kernel behind the staged one"""
+    from tests import draws
+    L = lib.library()
+    paired, other, short = [], [], []
+    lib.set_hook("STAGED_SHAPE", "5,5,5")
+    L.beamformer_hip_set_das_path(3)
+    try:
+        for seed in range(24):
+            acq = draws.draw_paired(seed)
+            path, kernel, _, reasons, d = lib.describe_das(acq.bp, acq.filters)
+            C, A = int(acq.bp.channel_count), int(acq.bp.acquisition_count)
+            if d.uniform_tables == 2:
+                assert path == 2 and d.u_shift == 5 and d.v_shift == 5 and d.window_samples == 32 and d.threads == 1024, (seed, kernel)
+                paired.append((seed, C, A))
+            else:
+                other.append((seed, C, A, path, int(d.uniform_tables)))
+            if A > 120:
+                # the padded transmit table (A rounded up to 4) splits into groups of at most 60 transmits whose two channel windows fit the
+                # LDS (das_select.cpp plan_staged, BF_STAGED_PAIRED_GROUP_MAX); the paired form takes at most two such groups
+                assert d.uniform_tables != 2, f"seed {seed}: {A} transmits need {-(-((A + 3) // 4 * 4) // 60)} groups of 60, the paired form was planned"
+            if acq.notes == "short rows":
+                assert d.row_end_planes > 0 and d.row_end_path == 1, (seed, int(d.row_end_planes), int(d.row_end_path))
+                short.append(seed)
+            else:
+                assert d.row_end_planes == 0 and d.row_end_path == -1, seed
+    finally:
+        lib.set_hook("STAGED_SHAPE", None)
+        L.beamformer_hip_set_das_path(0)
+    assert len(paired) >= 20, (paired, other)
+    assert any(A <= 60 for _, _, A in paired) and any(A > 60 for _, _, A in paired), paired           # one group and two groups
+    assert any(A % 4 for _, _, A in paired) and any(C % 2 for _, C, _ in paired), paired               # padded tables, a zero partner
+    assert any(A > 120 for _, _, A, _, _ in other) and short, (other, short)
+
+
+@pytest.mark.parametrize("seed", [120, 160, 385, 439])
+def test_planes_rerouted_from_the_block_staged_kernel_keep_the_factored_kernel_asked_for(seed):
+    """mode 0x114 asks for the factored kernel with block staging (das_tile.hip) and no channel split; on these short-row volumes of the
+    separable generator (tests/test_gpu_random.py ROW_END_SEPARABLE) the row-end rule takes planes away from the block-staged kernel, and
+    those run the factored kernel asked for (nibble 4 with block staging off), not "automatic, never staged".  Mode 3 on a linear draw
+    of the same generator (107) sends its re-routed plane to the gather kernel"""
+    from tests import draws
+    L = lib.library()
+    acq = draws.draw_separable(seed)
+    try:
+        L.beamformer_hip_set_das_path(0x114)
+        path, _, _, _, d = lib.describe_das(acq.bp, acq.filters)
+        assert d.row_end_planes > 0 and d.row_end_path == int(P.DasPath.Factored), (path, int(d.row_end_planes), int(d.row_end_path))
+        linear = draws.draw_separable(107)
+        assert linear.bp.interpolation_mode == int(P.InterpolationMode.Linear)
+        L.beamformer_hip_set_das_path(3)
+        path, _, _, _, d = lib.describe_das(linear.bp, linear.filters)
+        assert path == int(P.DasPath.Staged) and d.row_end_planes == 1 and d.row_end_path == int(P.DasPath.Gather)
+    finally:
+        L.beamformer_hip_set_das_path(0)

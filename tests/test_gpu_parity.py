@@ -6,79 +6,20 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import params as P
-from tests import cases
+from tests import cases, parity
+# the comparison lives in tests/parity.py (a plain module: its CPU tests, tests/test_compare.py, and the tools use it); reference and
+# truth_frame are re-exported from there, and compare with the DAS path of the library's newest frame in its log entry
+from tests.parity import reference, truth_frame  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-def reference(oracle, acq):
-    """(frame, pairs, flags) of the oracle; for nearest interpolation flags carries the per-voxel
-    ambiguity budget of taps that sit within 2^-10 of a rounding boundary (oracle/oracle.h)"""
-    flags = {} if acq.bp.interpolation_mode == int(P.InterpolationMode.Nearest) else None
-    ref, pairs = oracle.beamform(acq.bp, acq.rf, acq.filters, flags=flags)
-    return ref, pairs, flags
-
-
-def compare(gpu, ref, acq, flags=None):
-    assert gpu.shape == ref.shape and gpu.dtype == ref.dtype
-    nan_gpu, nan_ref = np.isnan(gpu), np.isnan(ref)
-    assert np.array_equal(nan_gpu, nan_ref), "NaN positions (coherency weighting with zero incoherent sum) differ"
-    ok = ~nan_ref
-    scale = np.max(np.abs(ref[ok])) if ok.any() else 1.0
-    assert scale > 0, "oracle image is empty: the case does not exercise the path"
-    tol = cases.tolerance(acq)
-    if acq.bp.interpolation_mode == int(P.InterpolationMode.Nearest):
-        # A sample index within float rounding of k + 1/2 may pick the other tap.  The oracle reports, per
-        # voxel, how far such flips can move the coherent sum (flags["budget"], zero where no tap is near a
-        # boundary): without coherency weighting EVERY voxel must agree within tolerance + budget; with it
-        # (a quotient of two sums the flips both touch) the voxels that hold no such tap must meet SURVEY
-        # 8c's bar: fewer than 1e-3 of them off by more than 1e-3.
-        assert flags is not None, "nearest interpolation is compared against the oracle's ambiguity budget"
-        err = np.abs(gpu - ref)
-        if not acq.bp.coherency_weighting:
-            slack = tol * scale + 1.01 * flags["budget"]
-            assert (err[ok] <= slack[ok]).all(), f"nearest: max excess {np.max(err[ok] - slack[ok]):.3e} over tolerance + tap ambiguity"
-        clean = ok & ~flags["near_half"]
-        if clean.any():
-            bad = float(np.mean(err[clean] > max(tol, 1e-3) * scale))
-            assert bad < 1e-3, f"nearest: mismatch fraction {bad:.2e} on the {int(clean.sum())} voxels without boundary taps"
-        # no systematic offset hiding under the budget: the median voxel agrees ten times better than the bar -- or, where float rounding
-        # of the phase alone is that large (round 4's fuzz draw general/1001: 12 terms at 96 turns, the float oracle itself 1.1e-5 from
-        # its double twin at the median voxel), the GPU's median distance to that truth is the oracle's own plus the same allowance
-        median_bar = 1e-5 if tol <= 1e-4 else tol
-        if not np.median(err[ok]) / scale < median_bar:
-            exact = truth_frame(acq, ref.shape)
-            assert exact is not None, f"nearest: median error {np.median(err[ok]) / scale:.3e} >= {median_bar:.0e}"
-            gpu_off, oracle_off = np.median(np.abs(gpu[ok] - exact[ok])) / scale, np.median(np.abs(ref[ok] - exact[ok])) / scale
-            assert gpu_off <= oracle_off + median_bar, (f"nearest: median error {np.median(err[ok]) / scale:.3e} >= {median_bar:.0e} and the GPU's median distance to the "
-                                                        f"double-precision truth {gpu_off:.3e} exceeds the float oracle's {oracle_off:.3e} by more than that")
-        return float(np.median(err[ok]) / scale)
-    err = np.abs(gpu[ok] - ref[ok]) / scale
-    if err.max() > tol:
-        # Second bar, for the voxels over the first: two float32 evaluations of one sum of white-noise taps differ by the rounding of a
-        # 2000-sample index on every tap (DESIGN.md 4), and neither is the truth.  The oracle's double-precision twin is (the same
-        # loops in double on the same float32 DAS input).  A voxel over the bar passes only if the GPU is no further from that truth than
-        # the float ORACLE gets from it on this frame, plus the bar -- never because another kernel of the library lands on the same
-        # value.  (Per voxel the two float errors are independent draws of one distribution -- asking the GPU to stay within the bar of
-        # the oracle's error AT THE SAME VOXEL fails whenever the oracle was lucky there: 2 of round 4's 33 regression draws by 8 %.
-        # The frame-wide maximum of the oracle's own error is the size of that distribution.)
-        exact = truth_frame(acq, ref.shape)
-        assert exact is not None, f"max relative error {err.max():.3e} > {tol:.0e}"
-        over = ok & (np.abs(gpu - ref) > tol * scale)
-        oracle_off = float(np.abs(ref[ok] - exact[ok]).max())
-        excess = (np.abs(gpu[over] - exact[over]) - oracle_off) / scale
-        assert (excess <= tol).all(), (f"max relative error {err.max():.3e} > {tol:.0e}, and on {int((excess > tol).sum())} of {int(over.sum())} such voxels the GPU is "
-                                      f"further from the double-precision truth than the float oracle ever is on this frame ({oracle_off / scale:.3e}) by {excess.max():.3e} > {tol:.0e}")
-    return float(err.max())
-
-
-def truth_frame(acq, shape):
-    """the oracle's frame with every DAS stage in double precision (oracle.beamform(truth=...)); None when the compared frame is a
-    sub-grid of it (those comparisons keep the first bar only)"""
-    from oracle import binding
-    truth = {}
-    binding.beamform(acq.bp, acq.rf, acq.filters, truth=truth)
-    return truth["frame"] if truth["frame"].shape == tuple(shape) else None
+def compare(gpu, ref, acq, flags=None, *, path=None, label=None):
+    """tests/parity.py compare(); the log entry names the DAS path of the library's newest frame unless `path` is given"""
+    if path is None:
+        from ogl_beamforming_amd import lib
+        path = last_das_path(lib)
+    return parity.compare(gpu, ref, acq, flags, path=path, label=label)
 
 
 def last_timings(bflib):

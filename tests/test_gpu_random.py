@@ -6,69 +6,14 @@ combinations here are not hand-picked."""
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import configs as cfg, params as P
-from tests import cases
+from ogl_beamforming_amd import params as P
+from tests.draws import K, draw, draw_plane, draw_separable, draw_tile  # noqa: F401  (the generators live in tests/draws.py)
 from tests.test_gpu_parity import compare, last_das_path, last_timings, reference
 
 pytestmark = pytest.mark.gpu
-S, D, I, K = P.ShaderKind, P.DataKind, P.InterpolationMode, P.AcquisitionKind
 
 
-def draw(seed):
-    rng = np.random.default_rng(1000 + seed)
-    pick = lambda *v: v[int(rng.integers(0, len(v)))]
-    interp = pick(I.Nearest, I.Linear, I.Linear, I.Cubic)
-    cw = bool(rng.integers(0, 2))
-    f_number = pick(0.0, 0.5, 1.0, 2.0)
-    C = int(pick(8, 12, 16, 24, 40))
-    samples = int(pick(256, 384, 512))
-    family = pick("rca2d", "rca3d", "rca3d", "vls", "hercules", "forces", "uforces")
-    common = dict(seed=seed, interp=interp, cw=cw, f_number=f_number)
-    path = 0.40 * samples / 25e6 * 1540.0
-    z0, z1 = 0.15 * path, 0.40 * path
-    if family in ("rca2d", "rca3d", "vls"):
-        A = int(pick(1, 2, 3, 5, 9))
-        kind = pick(D.Int16, D.Float16, D.Float32, D.Int16Complex, D.Float32Complex)
-        demod = kind in (D.Int16, D.Float16, D.Float32) and bool(rng.integers(0, 2))
-        if family == "rca2d":
-            points, lo, hi, orientation = (int(pick(12, 20, 33)), int(pick(12, 17)), 1), (-2e-3, 0, z0), (2e-3, 0, z1), 0x22
-        else:
-            points = (int(pick(6, 9, 16)), int(pick(6, 10)), int(pick(3, 5)))
-            lo, hi, orientation = (-2e-3, -2e-3, z0), (2e-3, 2e-3, z1), pick(0x12, 0x21)
-        depths = None
-        if family == "vls":
-            depths = rng.uniform(1.5 * z1, 4.0 * z1, A) * rng.choice([-1.0, 1.0], A)
-        acq = cfg.rca(f"random{seed}", C, A, samples, points, lo, hi, data_kind=kind, orientation=orientation,
-                      demodulate=demod, depths=depths, angles=rng.uniform(-12, 12, A) if A > 1 else None,
-                      kind=K.RCA_VLS if family == "vls" else K.RCA_TPW, **common)
-        bp = acq.bp
-        if family == "rca3d" and A > 1 and rng.integers(0, 3) == 0:
-            # per-transmit TRANSMIT orientation varies (receive fixed): still factorises
-            for a in range(A):
-                tx = int(pick(1, 2, 0))
-                bp.transmit_receive_orientations[a] = (tx << 4) | (orientation & 0xF)
-        elif family == "rca3d" and A > 1 and rng.integers(0, 4) == 0:
-            # receive orientation varies too: general kernel only
-            for a in range(A):
-                bp.transmit_receive_orientations[a] = int(pick(0x12, 0x21))
-        return acq
-    A = int(pick(4, 8, 12, 16))
-    kind = pick(D.Int16, D.Float16, D.Float32)
-    stages = pick((S.Decode, S.DAS), (S.Demodulate, S.Decode, S.DAS))
-    if family == "hercules":
-        return cfg.hercules(f"random{seed}", C, A, samples, (int(pick(6, 9)), int(pick(6, 8)), int(pick(4, 6))),
-                            (-1.5e-3, -1.5e-3, z0), (1.5e-3, 1.5e-3, z1), data_kind=kind, stages=stages,
-                            orientation=pick(0x12, 0x21), focal=pick((0.0, np.inf), (0.0, -4.0 * z1), (4.0, np.inf)), **common)
-    sparse = None
-    akind = K.FORCES
-    if family == "uforces":
-        akind = K.UFORCES
-        sparse = np.sort(rng.choice(max(C, A), A - 1, replace=False))
-    return cfg.forces(f"random{seed}", C, A, samples, (int(pick(12, 20, 31)), 1, int(pick(10, 16))), (-2e-3, 0, z0), (2e-3, 0, z1),
-                      data_kind=kind, stages=stages, kind=akind, sparse=sparse, **common)
-
-
-STAGED_DRAWS = []          # seeds whose forced-staged pass ran the LDS-staged kernel (reported by the last test of this module)
+STAGED_DRAWS = []          # (seed, form: uniform_tables 0 / 1 / 2) of the draws whose staged pass ran the LDS-staged kernel (reported below)
 
 
 # 1001: round 4's out-of-sample fuzz draw whose median error on the gather kernel (1.4e-5: the phase of 96 turns rounded once more than the
@@ -98,12 +43,13 @@ def test_random_acquisition(seed, bflib, oracle, hooks):
         bflib.library().beamformer_hip_set_das_path(3)
         hooks.set("STAGED_CHECKED")          # every term range-checked: a position outside its staged window is counted
         try:
+            form = int(bflib.describe_das(acq.bp, acq.filters)[4].uniform_tables)
             gpu = bflib.beamform(acq.bp, acq.rf, acq.filters)
             t = last_timings(bflib)
             assert int(t.das_path) in (1, 2)
             assert int(t.staged_window_violations) == 0, "a term left its staged window: plan_staged's bound is wrong"
             if int(t.das_path) == 2:
-                STAGED_DRAWS.append(seed)
+                STAGED_DRAWS.append((seed, form))
         finally:
             hooks.clear("STAGED_CHECKED")
             bflib.library().beamformer_hip_set_das_path(0)
@@ -120,29 +66,6 @@ def test_random_acquisition(seed, bflib, oracle, hooks):
         compare(gpu, ref, acq, flags)
 
 
-
-def draw_separable(seed):
-    """a row-column acquisition the LDS-staged kernels can take: receive and transmit on different axes, 6-20 transmits, plane or
-    focused / diverging waves, ragged grids, linear / cubic interpolation, IQ or real samples (the generator of the CPU property
-    test tests/test_das_select.py, with RF)"""
-    rng = np.random.default_rng(2000 + seed)
-    C = int(rng.choice([16, 32, 48]))
-    A = int(rng.integers(6, 20))
-    focused = bool(rng.integers(0, 2))
-    mode = int(rng.integers(0, 4))                       # 0, 1: IQ linear; 2: IQ cubic; 3: real linear
-    pitch = float(rng.choice([0.15e-3, 0.2e-3, 0.3e-3]))
-    half = (C - 1) / 2 * pitch * float(rng.uniform(0.6, 2.0))
-    z0 = float(rng.uniform(3e-3, 10e-3))
-    z1 = z0 + float(rng.uniform(2e-3, 8e-3))
-    points = (int(rng.integers(20, 110)), int(rng.integers(20, 70)), int(rng.integers(1, 3)) + 1)
-    depths = rng.choice([-30e-3, -12e-3, 25e-3, 60e-3, np.inf], A) if focused else None
-    return cfg.rca(f"staged{seed}", C, A, int(rng.choice([512, 1024, 2048])), points, (-half, -half * float(rng.uniform(0.5, 1.2)), z0), (half, half, z1),
-                   seed=seed, orientation=int(rng.choice([0x12, 0x21])), cw=bool(rng.integers(0, 2)), f_number=float(rng.uniform(0.3, 1.5)),
-                   pitch=pitch, angles=np.linspace(-float(rng.uniform(2, 20)), float(rng.uniform(2, 20)), A), depths=depths,
-                   kind=K.RCA_VLS if focused else K.RCA_TPW, interp=I.Cubic if mode == 2 else I.Linear,
-                   demodulate=mode != 3, data_kind=P.DataKind.Int16)
-
-
 @pytest.mark.parametrize("seed", range(32))
 def test_random_separable_acquisition_on_the_staged_kernels(seed, bflib, oracle, hooks):
     """32 draws aimed at the LDS-staged kernels (the 72 general draws above reach them once): automatic path, every term
@@ -153,7 +76,7 @@ def test_random_separable_acquisition_on_the_staged_kernels(seed, bflib, oracle,
     if not ok.any() or np.max(np.abs(ref[ok])) == 0:
         pytest.skip("empty image")
     bflib.library().beamformer_hip_set_das_path(0)
-    path = bflib.describe_das(acq.bp, acq.filters)[0]
+    path, _, _, _, d = bflib.describe_das(acq.bp, acq.filters)
     gpu = bflib.beamform(acq.bp, acq.rf, acq.filters)
     assert last_das_path(bflib) == path
     compare(gpu, ref, acq, flags)
@@ -163,52 +86,18 @@ def test_random_separable_acquisition_on_the_staged_kernels(seed, bflib, oracle,
         t = last_timings(bflib)
         assert int(t.das_path) == 2 and int(t.staged_window_violations) == 0, "a term left its staged window: plan_staged's bound is wrong"
         compare(checked, ref, acq, flags)
-        STAGED_DRAWS.append(100 + seed)
+        STAGED_DRAWS.append((100 + seed, int(d.uniform_tables)))
 
 
 def test_random_draws_reach_the_staged_kernel():
-    """how many draws exercised the LDS-staged kernels with the window-violation count on (none may be zero by luck)"""
-    print(f"staged draws: {len(STAGED_DRAWS)}: {STAGED_DRAWS}")
+    """how many draws exercised the LDS-staged kernels with the window-violation count on (none may be zero by luck), and in which form:
+    transmit tables in LDS (0), global wave-uniform tables (1), channel-paired (2; aimed at by tests/test_gpu_staged_paired.py's draws)"""
+    forms = {f: sum(1 for _, g in STAGED_DRAWS if g == f) for f in (0, 1, 2)}
+    print(f"staged draws: {len(STAGED_DRAWS)}, by form (uniform_tables) {forms}: {STAGED_DRAWS}")
     assert len(STAGED_DRAWS) >= 12, STAGED_DRAWS
 
 
 TILE_DRAWS = []            # (seed, staged chunks, gathered chunks) of the draws below that ran das_tile.hip
-
-
-def draw_tile(seed):
-    """a cubic IQ acquisition the block-staged factored kernel (das_tile.hip) can take: 2-D compounding or a view plane with tx and rx
-    on one axis, a thin volume, or FORCES / UFORCES; fine to moderately coarse grids (so that blocks meet chunks that fit their window and
-    chunks that do not), 4-24 plane, focused or diverging transmits, ragged tiles, short rows (terms off the end of a row: the checked
-    loop), f-numbers from near field to narrow apertures, with and without coherency weighting"""
-    rng = np.random.default_rng(3000 + seed)
-    family = str(rng.choice(["tpw", "tpw", "vls", "volume", "forces", "uforces"]))
-    C = int(rng.choice([12, 16, 24, 32]))
-    pitch = float(rng.choice([0.15e-3, 0.2e-3, 0.3e-3]))
-    # lateral half width: voxels of 25 um ... 250 um, and in a third of the draws around 1 mm (chunks that do not fit a window)
-    coarse = rng.integers(0, 3) == 0
-    half = (C - 1) / 2 * pitch * (float(rng.uniform(3.0, 6.0)) if coarse else float(rng.uniform(0.15, 1.3)))
-    z0 = float(rng.uniform(2e-3, 9e-3))
-    z1 = z0 + float(rng.uniform(0.4e-3, 6e-3))
-    samples = int(rng.choice([384, 512, 768, 1024]))
-    cw = bool(rng.integers(0, 2))
-    f_number = float(rng.uniform(0.3, 1.6))
-    nx, ny = int(rng.integers(40, 90 if coarse else 200)), int(rng.integers(18, 70))
-    if family in ("forces", "uforces"):
-        if family == "uforces":
-            sparse = sorted(int(v) for v in rng.choice(np.arange(C), size=int(rng.integers(5, 9)), replace=False))
-            return cfg.forces(f"tile{seed}", C, len(sparse) + 1, samples, (nx, 1, ny), (-half, 0, z0), (half, 0, z1), seed=seed, kind=K.UFORCES, sparse=sparse,
-                              decode=0, interp=I.Cubic, cw=cw, f_number=f_number, pitch=pitch, stages=(S.Demodulate, S.DAS))
-        return cfg.forces(f"tile{seed}", C, C, samples, (nx, 1, ny), (-half, 0, z0), (half, 0, z1), seed=seed, interp=I.Cubic, cw=cw, f_number=f_number,
-                          pitch=pitch, stages=(S.Demodulate, S.Decode, S.DAS))
-    A = int(rng.integers(4, 25))
-    depths = rng.choice([-30e-3, -12e-3, 25e-3, 60e-3, np.inf], A) if family == "vls" else None
-    if family == "volume":
-        points, lo, hi = (nx, ny, int(rng.integers(2, 5))), (-half, -half * 0.3, z0), (half, half * 0.3, z1)
-    else:
-        points, lo, hi = (nx, ny, 1), (-half, 0, z0), (half, 0, z1)
-    return cfg.rca(f"tile{seed}", C, A, samples, points, lo, hi, seed=seed, orientation=int(rng.choice([0x22, 0x22, 0x11])) if family != "volume" else 0x22,
-                   cw=cw, f_number=f_number, pitch=pitch, angles=np.linspace(-float(rng.uniform(2, 18)), float(rng.uniform(2, 18)), A), depths=depths,
-                   kind=K.RCA_VLS if family == "vls" else K.RCA_TPW, interp=I.Cubic, data_kind=P.DataKind.Int16)
 
 
 @pytest.mark.parametrize("seed", range(32))
@@ -243,42 +132,6 @@ def test_random_draws_reach_the_block_staged_kernel():
 
 
 PLANE_DRAWS = []           # (seed, das path, row-end planes) of the draws below
-
-
-def draw_plane(seed):
-    """a VIEW PLANE through row-column / HERCULES / FORCES data, as the reference's harness beamforms one out of every dataset
-    (tests/throughput.c:443-446; math.c:844-885): one voxel along z, depth on voxel y, 56-160 voxels wide so that the aligned-grid HERCULES
-    kernel and the factored kernel's band walk take it; a record that ends inside the image in about half the draws (terms at the ends
-    of the RF rows: the kernels' row-end instantiations), all three interpolations, with and without coherency weighting"""
-    rng = np.random.default_rng(4000 + seed)
-    kind = str(rng.choice(["tpw", "tpw_swapped", "vls", "hercules", "hercules", "forces"]))
-    plane = "xz" if kind == "forces" else str(rng.choice(["xz", "xz", "yz"]))
-    C = int(rng.choice([16, 32]))
-    A = int(rng.choice([8, 16]))
-    samples = int(rng.choice([512, 768, 1024]))
-    k = samples / 4096.0
-    nx, ny = int(rng.choice([56, 64, 96, 128, 160])), int(rng.integers(20, 72))
-    reach = float(rng.uniform(0.75, 1.15))                      # > ~0.95: the deepest rows lie beyond the record
-    width = float(rng.uniform(0.5, 1.1))
-    lo = (-60e-3 * k * width, -60e-3 * k * width, 10e-3 * k)
-    hi = (60e-3 * k * width, 60e-3 * k * width, 165e-3 * k * reach)
-    fs, fd = 20e6, 5e6
-    pitch = 0.25e-3 * max(k, 64.0 / C * k)
-    interp = [I.Linear, I.Cubic, I.Cubic, I.Nearest][int(rng.integers(0, 4))]
-    cw = bool(rng.integers(0, 2))
-    f_number = float(rng.choice([0.5, 0.5, 1.0, 1.5]))
-    canonical = (S.Demodulate, S.Decode, S.DAS)
-    points = (nx, ny, 1)
-    if kind in ("tpw", "tpw_swapped", "vls"):
-        depths = np.full(A, -40e-3 * k * float(rng.uniform(0.5, 2.0))) if kind == "vls" else None
-        return cfg.rca(f"plane{seed}", C, A, samples, points, lo, hi, seed=seed, interp=interp, cw=cw, f_number=f_number, pitch=pitch, fs=fs, fd=fd,
-                       orientation=0x21 if kind == "tpw_swapped" else 0x12, angles=np.linspace(-float(rng.uniform(4, 18)), float(rng.uniform(4, 18)), A),
-                       depths=depths, stages=canonical, plane=plane, kind=K.RCA_VLS if kind == "vls" else K.RCA_TPW)
-    if kind == "hercules":
-        return cfg.hercules(f"plane{seed}", C, A, samples, points, lo, hi, seed=seed, interp=interp, cw=cw, f_number=f_number, pitch=pitch, fs=fs, fd=fd,
-                            stages=canonical, plane=plane)
-    return cfg.forces(f"plane{seed}", C, A, samples, points, lo, hi, seed=seed, interp=interp, cw=cw, f_number=f_number, pitch=pitch, fs=fs, fd=fd,
-                      stages=canonical)
 
 
 @pytest.mark.parametrize("seed", range(40))
@@ -342,6 +195,10 @@ def test_row_end_draws_of_the_separable_generator(seed, bflib, oracle, hooks):
             t = last_timings(bflib)
             ran[mode] = (int(t.das_path), int(t.das_row_end_planes))
             assert int(t.staged_window_violations) == 0
+            if mode in (0x14, 0x114) and int(t.das_row_end_planes):
+                # the planes the row-end rule takes from the block-staged kernel run the factored kernel asked for
+                d = bflib.describe_das(acq.bp, acq.filters)[4]
+                assert int(d.row_end_planes) == int(t.das_row_end_planes) and int(d.row_end_path) == int(P.DasPath.Factored), (mode, int(d.row_end_path))
         finally:
             lib.beamformer_hip_set_das_path(0)
             if mode == 3:

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import configs as cfg
-from tests import cases
+from tests import cases, draws
 from tests.test_gpu_multi_device import same_bits, use_devices
 from tests.test_gpu_parity import compare, last_das_path, last_timings, reference
 
@@ -66,7 +66,57 @@ def test_paired_staged_kernel(name, bflib, oracle, hooks):
     scale = np.max(np.abs(in_lds[ok]))
     assert np.max(np.abs(paired[ok] - in_lds[ok])) <= 1e-4 * scale
     ref, _, flags = reference(oracle, acq)
-    compare(paired, ref, acq, flags)
+    compare(paired, ref, acq, flags, path=path)
+
+
+PAIRED_DRAWS = []          # (seed, uniform_tables the plan chose, DAS path of the frame, planes re-routed by the row-end rule)
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_draws_on_the_paired_staged_kernel(seed, bflib, oracle, hooks):
+    """tests/draws.py draw_paired: everything test_paired_staged_kernel asks of its fixed cases, on random draws -- one or two transmit
+    groups, padded transmit counts, odd channel counts, ragged tiles, short rows (the deepest plane on the gather kernel) -- and the
+    oracle's frame from draws the paired form does not take (more than two groups)"""
+    acq = draws.draw_paired(seed)
+    lib = bflib.library()
+    hooks.set("STAGED_SHAPE", "5,5,5")
+    lib.beamformer_hip_set_das_path(3)
+    try:
+        _, _, _, _, d = bflib.describe_das(acq.bp, acq.filters)
+        form = int(d.uniform_tables)
+        paired, path, violations = run(bflib, acq)
+        PAIRED_DRAWS.append((seed, form, path, int(d.row_end_planes)))
+        if form == 2:
+            assert path == 2 and d.u_shift == 5 and d.v_shift == 5 and d.window_samples == 32
+            again, _, _ = run(bflib, acq)
+            assert same_bits(paired, again)                      # repeat frames
+            hooks.set("STAGED_CHECKED")
+            checked, path_checked, violations = run(bflib, acq)
+            assert path_checked == 2 and violations == 0
+            assert same_bits(paired, checked)                    # every term range-checked: the same arithmetic
+            hooks.clear("STAGED_CHECKED")
+            hooks.set("STAGED_NOUNIFORM")
+            assert bflib.describe_das(acq.bp, acq.filters)[4].uniform_tables == 0
+            in_lds, path_lds, _ = run(bflib, acq)
+            assert path_lds == 2
+    finally:
+        lib.beamformer_hip_set_das_path(0)
+    ref, _, flags = reference(oracle, acq)
+    compare(paired, ref, acq, flags, path=path)
+    if form == 2:
+        ok = ~np.isnan(in_lds)
+        assert np.array_equal(np.isnan(paired), ~ok)
+        scale = np.max(np.abs(in_lds[ok]))
+        assert np.max(np.abs(paired[ok] - in_lds[ok])) <= 1e-4 * scale
+
+
+def test_random_draws_reach_the_paired_form():
+    """the draws above are worth their name only if most of them ran the channel-paired form"""
+    ran = [seed for seed, form, path, _ in PAIRED_DRAWS if form == 2 and path == 2]
+    print(f"paired-form draws: {len(ran)} of {len(PAIRED_DRAWS)}; with planes re-routed by the row-end rule: "
+          f"{sorted(seed for seed, form, _, planes in PAIRED_DRAWS if form == 2 and planes)}; other forms (seed, uniform_tables, path): "
+          f"{[(seed, form, path) for seed, form, path, _ in PAIRED_DRAWS if form != 2]}")
+    assert len(ran) >= 18, PAIRED_DRAWS
 
 
 @pytest.mark.parametrize("name, count", [("paired_two_groups", 2), ("config4_small", 3)])

@@ -1,4 +1,4 @@
-"""Named seeds of tests/test_gpu_random.py's generators under chosen das-path modes, against the oracle with the suite's comparison:
+"""Named seeds of tests/draws.py's generators under chosen das-path modes, against the oracle with the suite's comparison (tests/parity.py):
 PYTHONPATH=. python tools/fuzz_seeds.py separable 96,107,112 --modes 0,1,2,3,4   (modes: beamformer_hip_set_das_path)"""
 import argparse
 import sys
@@ -7,15 +7,16 @@ import numpy as np
 
 from ogl_beamforming_amd import lib as bflib
 from oracle import binding as oracle
-from tests import test_gpu_random as R
-from tests.test_gpu_parity import compare, last_timings, reference
+from tests import draws as R
+from tests.parity import compare, reference
+from tests.test_gpu_parity import last_timings
 
 ap = argparse.ArgumentParser()
-ap.add_argument("generator", choices=["general", "separable", "tile"])
+ap.add_argument("generator", choices=["general", "separable", "tile", "plane", "paired"])
 ap.add_argument("seeds")
 ap.add_argument("--modes", default="0")
 args = ap.parse_args()
-gen = {"general": R.draw, "separable": R.draw_separable, "tile": R.draw_tile}[args.generator]
+gen = {"general": R.draw, "separable": R.draw_separable, "tile": R.draw_tile, "plane": R.draw_plane, "paired": R.draw_paired}[args.generator]
 if "-" in args.seeds:
     a, b = args.seeds.split("-")
     seeds = list(range(int(a), int(b)))
@@ -40,8 +41,9 @@ for seed in seeds:
             gpu = bflib.beamform(acq.bp, acq.rf, acq.filters)
             path = int(last_timings(bflib).das_path)
             ran += 1
-            err = compare(gpu, ref, acq, flags)
-            print(args.generator, seed, "mode", hex(mode), "path", path, "ok", f"{err:.2e}")
+            v = compare(gpu, ref, acq, flags, path=path, label=f"{args.generator}/{seed}/{mode:#x}")
+            print(args.generator, seed, "mode", hex(mode), "path", path, "ok", f"{v.max_rel_err:.2e}", "bar", v.bar,
+                  "flip voxels", v.flip_voxels, "second-bar voxels", v.second_bar_voxels)
         except AssertionError as e:
             failed += 1
             print(args.generator, seed, "mode", hex(mode), "path", path, "FAIL:", str(e)[:120])
