@@ -75,6 +75,49 @@ typedef struct {
  * many transmits at a time -- a multiple of 4 whose block indices, plus the two elements in front, stay below 4096 (the tap address
  * is a 16-bit shift of the element index) */
 #define BF_STAGED_PAIRED_GROUP_MAX 60u
+/* ... and the block's LDS must leave room for a second block on the CU (160 KB) */
+#define BF_STAGED_PAIRED_LDS_BUDGET (80u * 1024u)
+
+#ifdef __HIPCC__
+#define BF_HOST_DEVICE __host__ __device__
+#else
+#define BF_HOST_DEVICE
+#endif
+/* dynamic LDS of the channel-paired form: the windows of the largest group (+ two elements in front, a zero element behind), the
+ * receive table of a chunk of channels (an odd chunk gets a zero partner), the transmits' floors, the channels' floors and row offsets */
+static inline BF_HOST_DEVICE uint32_t bf_staged_paired_lds_bytes(uint32_t group, uint32_t channel_chunk, uint32_t a4)
+{
+	const uint32_t lds = 16u * (group * 64u + 3u) + 16u * (((channel_chunk + 1u) & ~1u) << 5) + 4u * (a4 + 2u * (channel_chunk + 2u)) + 128u;
+	return (lds + 15u) & ~15u;
+}
+/* staging passes of a group: 1024 threads copy 1024 window elements = 16 transmits' blocks per pass (a group of one pass runs as two:
+ * the one-pass instance of the kernel spills) */
+static inline BF_HOST_DEVICE uint32_t bf_staged_paired_passes(uint32_t group)
+{
+	const uint32_t passes = (group + 15u) / 16u;
+	return passes < 2u ? 2u : passes;
+}
+/* THE split of a4 padded transmits (a multiple of 4) into the groups the channel-paired form stages one after the other -- the plan
+ * (das_select.cpp), the launcher and the kernel (das_staged.hip) all ask here.  At most two groups, g0 >= g1 (g1 = 0: one group), both
+ * multiples of 4, neither above BF_STAGED_PAIRED_GROUP_MAX nor above what the LDS budget leaves beside the receive table of
+ * `channel_chunk` channels.  Of the splits that fit, the one with the fewest staging passes (every wave of the block waits at the round's
+ * barrier for the slowest pass, kept or not: 76 transmits are 48 + 28 = 3 + 2 passes where halves of 40 + 36 are 3 + 3); among those a
+ * first group of whole passes, then the smaller first group (less LDS).  The transmits of group 0 are 0 .. g0 - 1, group 1 the rest: they
+ * are accumulated in index order whatever the split, so it changes no bit of a frame.  False: no such split (the form is not taken). */
+static inline BF_HOST_DEVICE bool bf_staged_paired_split(uint32_t a4, uint32_t channel_chunk, uint32_t *g0, uint32_t *g1)
+{
+	uint32_t gmax = BF_STAGED_PAIRED_GROUP_MAX;
+	while (gmax >= 4u && bf_staged_paired_lds_bytes(gmax, channel_chunk, a4) > BF_STAGED_PAIRED_LDS_BUDGET) gmax -= 4u;
+	*g0 = *g1 = 0u;
+	if (a4 < 4u || (a4 & 3u) || gmax < 4u || a4 > 2u * gmax) return false;
+	if (a4 <= gmax) { *g0 = a4; return true; }
+	uint32_t best_key = ~0u;
+	for (uint32_t first = gmax; 2u * first >= a4; first -= 4u) {
+		const uint32_t key = (bf_staged_paired_passes(first) + bf_staged_paired_passes(a4 - first)) * 256u + ((first & 15u) ? 128u : 0u) + first;
+		if (key < best_key) { best_key = key; *g0 = first; *g1 = a4 - first; }
+	}
+	return true;
+}
 
 /* tile geometry of the separable-delay fast path (das_separable.hip) */
 typedef struct {

@@ -409,12 +409,11 @@ static bool plan_staged(const BfDasArgs &a, const std::vector<BfTransmit> &tx, c
 	 * and the transmit tables.  Decided by the shape alone: a slab takes the form the whole frame takes. */
 	if (best_waves && allow_uniform && cplx && !cubic && !hk.staged_nouniform && best.threads == 1024 && best.u_shift == 5 && best.v_shift == 5 &&
 	    best.window_samples == 32) {
-		const uint32_t ngroups = (A4 + BF_STAGED_PAIRED_GROUP_MAX - 1u) / BF_STAGED_PAIRED_GROUP_MAX;
-		const uint64_t group = ((A4 + ngroups - 1u) / ngroups + 3u) & ~3u;
 		const uint32_t cc = best.channel_chunk;
-		uint64_t lds = 16ull * (group * 64 + 3) + 16ull * ((uint64_t)((cc + 1) & ~1u) << 5) + 4ull * (A4 + cc + 1) + 128;
-		lds = (lds + 15) & ~15ull;
-		if (ngroups <= 2 && lds <= lds_cu / 2 && ((cc & 1u) == 0 || cc == C)) {          /* (two blocks per CU, as before) */
+		uint32_t g0, g1;
+		/* the split (bf_kernels.h) fits the larger group beside the chunk's receive table in half a CU's LDS: two blocks per CU, as before */
+		if (bf_staged_paired_split(A4, cc, &g0, &g1) && ((cc & 1u) == 0 || cc == C)) {
+			const uint64_t lds = bf_staged_paired_lds_bytes(g0, cc, A4);
 			best.uniform = 2u;
 			best.lds_bytes = (uint32_t)lds;
 			best.table_stride = 4u * A4 + 16u + 16u * (A4 / 2u) * 48u;

@@ -497,7 +497,7 @@ __device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparabl
  * BF_STAGED_PAIRED_GROUP_MAX).  After each channel pair lanes l and l + 32 hold the even- and the odd-channel terms of the same two
  * voxels: one exchange (v_permlane32_swap) per value and each half accumulates one of the voxels.
  * LDS: stage[a*64 + h*32 + j] (a < group), a zero element behind the largest group, R[cl*32 + u] for the chunk's channels (an odd
- * last channel gets a zero partner), tfl[A4], rfloor[chunk]. */
+ * last channel gets a zero partner), tfl[A4], rfloor[chunk], rbase[chunk] (bf_staged_paired_lds_bytes, bf_kernels.h). */
 template <bool CW, int NL>
 __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfSeparableArgs &q)
 {
@@ -505,13 +505,16 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 	constexpr uint32_t U = 32, W = 32, B = 2 * W;
 	const int C = p.channel_count, A = p.acquisition_count, S = p.sample_count;
 	const uint32_t A4 = ((uint32_t)A + 3u) & ~3u;
-	const uint32_t ngroups = (A4 + BF_STAGED_PAIRED_GROUP_MAX - 1u) / BF_STAGED_PAIRED_GROUP_MAX;
-	const uint32_t G0 = ((A4 + ngroups - 1u) / ngroups + 3u) & ~3u;       /* transmits of every group but the last (76: 40 + 36) */
 	const int chunk = (int)q.channel_chunk;
+	/* the groups of transmits staged one after the other: G0 then G1 (0: one group).  NL: staging passes of G0, the larger */
+	uint32_t G0, G1;
+	if (!bf_staged_paired_split(A4, q.channel_chunk, &G0, &G1)) return;     /* (the launcher refused such a launch) */
+	const uint32_t ngroups = G1 ? 2u : 1u;
 	f32x4 *stage  = staged_lds + 2;                          /* (two unused elements in front, as staged_body) */
 	f32x4 *R      = stage + (size_t)G0 * B + 1;
 	int   *tfl    = reinterpret_cast<int *>(R + (size_t)((chunk + 1) & ~1) * U);
 	int   *rfloor = tfl + A4;
+	uint32_t *rbase = reinterpret_cast<uint32_t *>(rfloor + ((chunk + 2) & ~1));   /* per channel of the chunk: byte offset of its window's first sample in transmit 0's row */
 
 	uint32_t tu, tv, zl;
 	if (!staged_tile_of(q, true, tu, tv, zl)) return;        /* whole block */
@@ -556,32 +559,40 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 	 * (zeros: the padding transmits need zero windows, their |s| is summed with no phasor). */
 	const __amdgpu_buffer_rsrc_t rf_rsrc = __builtin_amdgcn_make_buffer_rsrc(
 		const_cast<void *>(p.rf), 0, (int)((uint32_t)C * (uint32_t)A * (uint32_t)S * 8u), 0x00020000);
-	auto lane_at_of = [&](int c0, int cl) -> uint32_t {
-		return c0 + cl < C ? ((uint32_t)(c0 + cl) * (uint32_t)A * (uint32_t)S + (uint32_t)(rfloor[cl] + (int)(opaque_tid() & 31u))) * 8u : 0x80000000u;
-	};
+	auto lane_at_of = [&](int cl) -> uint32_t { return rbase[cl] + ((opaque_tid() & 31u) << 3); };
+	/* The floors of a round's NL transmits are read first and together (one wait for the scalar loads, not one per pass) at an index
+	 * that always lies in the table, the out-of-range offset is selected afterwards: no branch around a load. */
 	auto stage_load = [&](uint32_t lane_at, uint32_t g, f32x2 (&regs)[NL]) {
-		const uint32_t a0 = g * G0, gn = A4 - a0 < G0 ? A4 - a0 : G0;
+		const uint32_t a0 = g ? G0 : 0u, gn = g ? G1 : G0;
+		int fl[NL];
+		#pragma unroll
+		for (int n = 0; n < NL; n++) {
+			const uint32_t a = a0 + wave + (uint32_t)n * 16u;
+			fl[n] = tab_floor[a < A4 ? a : A4 - 1u];
+		}
 		#pragma unroll
 		for (int n = 0; n < NL; n++) {
 			const uint32_t al = wave + (uint32_t)n * 16u, a = a0 + al;
 			const bool real = al < gn && a < (uint32_t)A;                        /* wave uniform */
-			const uint32_t off = real ? lane_at + ((a * (uint32_t)S + (uint32_t)tab_floor[real ? a : 0]) * 8u) : 0x80000000u;
+			const uint32_t off = real ? lane_at + ((a * (uint32_t)S + (uint32_t)fl[n]) * 8u) : 0x80000000u;
 			i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rf_rsrc, (int)off, 0, 0);
 			regs[n] = __builtin_bit_cast(f32x2, v);
 		}
 	};
+	/* A pass is 16 transmits' blocks, one per wave: wave w converts and stores in pass n only if transmit w + 16 n belongs to the group
+	 * (a scalar branch), so a group of 28 costs its slowest wave two passes and no wave a pass whose elements nobody keeps. */
 	auto stage_store = [&](uint32_t g, const f32x2 (&regs)[NL]) {
-		const uint32_t a0 = g * G0, gn = A4 - a0 < G0 ? A4 - a0 : G0;
+		const uint32_t gn = g ? G1 : G0;
 		const uint32_t tid = opaque_tid();
 		const float half_minus_j = 0.5f - (float)(tid & 63u);  /* the line of element e in the coordinate 1/2 - (e mod 64) */
 		#pragma unroll
 		for (int n = 0; n < NL; n++) {
+			if (wave + (uint32_t)n * 16u >= gn) break;
 			const float sx = regs[n].x, sy = regs[n].y;
 			const float nx = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sx), 0x130, 0xf, 0xf, true));
 			const float ny = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sy), 0x130, 0xf, 0xf, true));
 			const float dx = nx - sx, dy = ny - sy;
-			const uint32_t e = tid + (uint32_t)n * 1024u;
-			if (e < gn * B) stage[e] = f32x4{__builtin_fmaf(half_minus_j, dx, sx), __builtin_fmaf(half_minus_j, dy, sy), dx, dy};
+			stage[tid + (uint32_t)n * 1024u] = f32x4{__builtin_fmaf(half_minus_j, dx, sx), __builtin_fmaf(half_minus_j, dy, sy), dx, dy};
 		}
 	};
 
@@ -645,7 +656,11 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 			float m = row[0];
 			#pragma unroll 4
 			for (uint32_t iu = 1; iu < U; iu++) m = fminf(m, row[4 * iu]);
-			rfloor[cl] = (int)__builtin_floorf(m);
+			const int fl = (int)__builtin_floorf(m);
+			rfloor[cl] = fl;
+			/* (a missing odd channel points out of the buffer and stays there with a lane's and a transmit's offset added: the host
+			 * refuses inputs of 2 GiB and more) */
+			rbase[cl] = c0 + (int)cl < C ? ((uint32_t)(c0 + (int)cl) * (uint32_t)A * (uint32_t)S + (uint32_t)fl) * 8u : 0x80000000u;
 		}
 		__syncthreads();
 		/* window-relative delay plus the half offset h * W of the lane's window in the block; the sign of the weight: the lane may leave
@@ -661,25 +676,25 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 		__syncthreads();
 
 		f32x2 regs[NL];
-		stage_load(lane_at_of(c0, (int)h), 0, regs);
+		stage_load(lane_at_of((int)h), 0, regs);
 		for (int k = 0; k < cn2 / 2; k++) {
-			f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f};
-			f32x2 mag2 = {0.f, 0.f};                         /* {voxel A, voxel B} */
-			for (uint32_t g = 0; g < ngroups; g++) {
-				__syncthreads();               /* everyone is done with the previous round's windows */
-				stage_store(g, regs);
-				__syncthreads();
-				if (g + 1 < ngroups)     stage_load(lane_at_of(c0, 2 * k + (int)h), g + 1, regs);     /* in flight during the arithmetic */
-				else if (2 * k + 2 < cn2) stage_load(lane_at_of(c0, 2 * k + 2 + (int)h), 0, regs);
-				if (!wave_inside) continue;
-
-				float r_rel, r_w;
-				{
-					const f32x4 r = Rl[(size_t)(2 * k) * U];
-					r_rel = r.x; r_w = r.w;
-				}
-				if (__builtin_amdgcn_ballot_w64(r_w != 0.f) == 0) continue;    /* F# culling per wave (both channels of the pair) */
-				const bool wave_safe = !(q.depth_major & 2u) && __builtin_amdgcn_ballot_w64(__builtin_signbitf(r_w)) == 0;
+			/* the lane's receive entry and what the wave does with this channel pair, once per pair: nothing (no voxel inside, or the
+			 * f-number culls both channels for every lane), the plain loop, or the range-checked one.  The pair's rounds are written
+			 * once per case (`rounds` below), so that the accumulators live in one loop nest each and are not copied where the cases
+			 * would meet after every round. */
+			float r_rel = 0.f;
+			int mode = 0;
+			if (wave_inside) {
+				const f32x4 r = Rl[(size_t)(2 * k) * U];
+				r_rel = r.x;
+				if (__builtin_amdgcn_ballot_w64(r.w != 0.f) != 0)        /* F# culling per wave (both channels of the pair) */
+					mode = (!(q.depth_major & 2u) && __builtin_amdgcn_ballot_w64(__builtin_signbitf(r.w)) == 0) ? 1 : 2;
+			}
+			auto rounds = [&](auto mode_c) {
+				constexpr int MODE = decltype(mode_c)::value;
+				constexpr bool CHECK = MODE == 2;
+				f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f};
+				f32x2 mag2 = {0.f, 0.f};                         /* {voxel A, voxel B} */
 				auto term = [&](f32x2 cs, float pos, f32x4 tap, f32x2 &acc1, f32x2 &acc2) -> float {
 					f32x2 sv = f32x2{tap.x, tap.y} + pos * f32x2{tap.z, tap.w};
 					acc1 += sv.x * cs;
@@ -687,63 +702,71 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 					if constexpr (CW) return hw_sqrt(__builtin_fmaf(sv.y, sv.y, sv.x * sv.x));
 					else return 0.f;
 				};
-				const uint32_t a0 = g * G0, gn = A4 - a0 < G0 ? A4 - a0 : G0;
-				auto batches = [&](auto checked) {
-					constexpr bool CHECK = decltype(checked)::value;
-					/* position -> tap as staged_body; M = 2^23 + 2 + (the batch's first block) * 64, the lane's window starts h * W
-					 * further (its receive entry carries that offset) */
-					uint32_t m_bits = 0x4B000002u;
-					[[maybe_unused]] bool window_left = false;
-					[[maybe_unused]] int rfl_h = 0;                          /* checked loop: rfloor of the lane's channel - h * W */
-					if constexpr (CHECK) rfl_h = rfloor[2 * k + (int)h] - (int)(h * W);
-					const f32x2 rr = {r_rel, r_rel};
-					const_f32x4 *row = rows + (size_t)(a0 / 2u) * 3u;
-					for (uint32_t a = 0; a < gn; a += 2, m_bits += 2u * B) {
-						uint32_t at[4]; f32x4 tap[4];
-						const float M = __builtin_bit_cast(float, m_bits);
-						const f32x2 M2 = {M, M};
-						const f32x4 tz = row[0], cs0 = row[1], cs1 = row[2];
-						row += 3;
-						const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};   /* {A, B} of transmit a, of a + 1 */
-						const f32x2 y0 = p0 + M2, y1 = p1 + M2;
-						const float ys[4] = {y0.x, y0.y, y1.x, y1.y};
-						#pragma unroll
-						for (int t = 0; t < 4; t++) {
-							const uint32_t yb = __builtin_bit_cast(uint32_t, ys[t]);
-							asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[t]) : "v"(yb));
-							if constexpr (CHECK) {
-								uint32_t lane_id = tid;
-								asm volatile("" : "+v"(lane_id));                            /* h * W = tid & 32, not held across the loop */
-								const uint32_t rel = yb - m_bits;                             /* round(p) in the transmit's block */
-								const uint32_t k_abs = (uint32_t)((int)rel + rfl_h + tfl[a0 + a + (uint32_t)(t >> 1)]);
-								at[t] = k_abs < ulast ? at[t] + (uint32_t)(t >> 1) * B * 16u : (G0 * B + 2u) * 16u;
-								window_left |= __builtin_amdgcn_ballot_w64(inside && rel - (lane_id & 32u) > W - 2u) != 0ull;   /* (voxels in the grid) */
+				for (uint32_t g = 0; g < ngroups; g++) {
+					__syncthreads();               /* everyone is done with the previous round's windows */
+					stage_store(g, regs);
+					__syncthreads();
+					if (g + 1 < ngroups)     stage_load(lane_at_of(2 * k + (int)h), g + 1, regs);     /* in flight during the arithmetic */
+					else if (2 * k + 2 < cn2) stage_load(lane_at_of(2 * k + 2 + (int)h), 0, regs);
+					if constexpr (MODE != 0) {
+						const uint32_t a0 = g ? G0 : 0u, gn = g ? G1 : G0;
+						/* position -> tap as staged_body; M = 2^23 + 2 + (the batch's first block) * 64, the lane's window starts h * W
+						 * further (its receive entry carries that offset) */
+						uint32_t m_bits = 0x4B000002u;
+						[[maybe_unused]] bool window_left = false;
+						[[maybe_unused]] int rfl_h = 0;                          /* checked loop: rfloor of the lane's channel - h * W */
+						if constexpr (CHECK) rfl_h = rfloor[2 * k + (int)h] - (int)(h * W);
+						const f32x2 rr = {r_rel, r_rel};
+						const_f32x4 *row = rows + (size_t)(a0 / 2u) * 3u;
+						for (uint32_t a = 0; a < gn; a += 2, m_bits += 2u * B) {
+							uint32_t at[4]; f32x4 tap[4];
+							const float M = __builtin_bit_cast(float, m_bits);
+							const f32x2 M2 = {M, M};
+							const f32x4 tz = row[0], cs0 = row[1], cs1 = row[2];
+							row += 3;
+							const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};   /* {A, B} of transmit a, of a + 1 */
+							const f32x2 y0 = p0 + M2, y1 = p1 + M2;
+							const float ys[4] = {y0.x, y0.y, y1.x, y1.y};
+							#pragma unroll
+							for (int t = 0; t < 4; t++) {
+								const uint32_t yb = __builtin_bit_cast(uint32_t, ys[t]);
+								asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[t]) : "v"(yb));
+								if constexpr (CHECK) {
+									uint32_t lane_id = tid;
+									asm volatile("" : "+v"(lane_id));                            /* h * W = tid & 32, not held across the loop */
+									const uint32_t rel = yb - m_bits;                             /* round(p) in the transmit's block */
+									const uint32_t k_abs = (uint32_t)((int)rel + rfl_h + tfl[a0 + a + (uint32_t)(t >> 1)]);
+									at[t] = k_abs < ulast ? at[t] + (uint32_t)(t >> 1) * B * 16u : (G0 * B + 2u) * 16u;
+									window_left |= __builtin_amdgcn_ballot_w64(inside && rel - (lane_id & 32u) > W - 2u) != 0ull;   /* (voxels in the grid) */
+								}
 							}
+							#pragma unroll
+							for (int t = 0; t < 4; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
+							const float qa0 = term(f32x2{cs0.x, cs0.y}, p0.x, tap[0], acc1a, acc2a);
+							const float qb0 = term(f32x2{cs0.z, cs0.w}, p0.y, tap[1], acc1b, acc2b);
+							const float qa1 = term(f32x2{cs1.x, cs1.y}, p1.x, tap[2], acc1a, acc2a);
+							const float qb1 = term(f32x2{cs1.z, cs1.w}, p1.y, tap[3], acc1b, acc2b);
+							if constexpr (CW) { mag2 += f32x2{qa0, qb0}; mag2 += f32x2{qa1, qb1}; }
 						}
-						#pragma unroll
-						for (int t = 0; t < 4; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
-						const float qa0 = term(f32x2{cs0.x, cs0.y}, p0.x, tap[0], acc1a, acc2a);
-						const float qb0 = term(f32x2{cs0.z, cs0.w}, p0.y, tap[1], acc1b, acc2b);
-						const float qa1 = term(f32x2{cs1.x, cs1.y}, p1.x, tap[2], acc1a, acc2a);
-						const float qb1 = term(f32x2{cs1.z, cs1.w}, p1.y, tap[3], acc1b, acc2b);
-						if constexpr (CW) { mag2 += f32x2{qa0, qb0}; mag2 += f32x2{qa1, qb1}; }
+						if constexpr (CHECK) { if (window_left) staged_violation_raise(); }
 					}
-					if constexpr (CHECK) { if (window_left) staged_violation_raise(); }
-				};
-				if (wave_safe) batches(std::false_type{});
-				else           batches(std::true_type{});
-				if (g + 1 < ngroups) continue;
-				/* the pair's fold: the lane's channel's term of both voxels, then the two channels of the pair summed per voxel */
-				float sa_x = acc1a.x - acc2a.y, sa_y = acc1a.y + acc2a.x;
-				float sb_x = acc1b.x - acc2b.y, sb_y = acc1b.y + acc2b.x;
-				asm volatile("" : "+v"(sa_x), "+v"(sa_y), "+v"(sb_x), "+v"(sb_y));
-				const f32x4 r = *(volatile lds_f32x4 *)(uintptr_t)((uint32_t)(uintptr_t)(lds_f32x4 *)Rl + (uint32_t)(2 * k) * U * 16u);
-				const float ca_x = __builtin_fmaf(sa_x, r.y, -sa_y * r.z), ca_y = __builtin_fmaf(sa_x, r.z, sa_y * r.y);
-				const float cb_x = __builtin_fmaf(sb_x, r.y, -sb_y * r.z), cb_y = __builtin_fmaf(sb_x, r.z, sb_y * r.y);
-				coherent.x += exchange(ca_x, cb_x);
-				coherent.y += exchange(ca_y, cb_y);
-				if constexpr (CW) incoherent += exchange(__builtin_fabsf(r.w) * mag2.x, __builtin_fabsf(r.w) * mag2.y);
-			}
+				}
+				if constexpr (MODE != 0) {
+					/* the pair's fold: the lane's channel's term of both voxels, then the two channels of the pair summed per voxel */
+					float sa_x = acc1a.x - acc2a.y, sa_y = acc1a.y + acc2a.x;
+					float sb_x = acc1b.x - acc2b.y, sb_y = acc1b.y + acc2b.x;
+					asm volatile("" : "+v"(sa_x), "+v"(sa_y), "+v"(sb_x), "+v"(sb_y));
+					const f32x4 r = *(volatile lds_f32x4 *)(uintptr_t)((uint32_t)(uintptr_t)(lds_f32x4 *)Rl + (uint32_t)(2 * k) * U * 16u);
+					const float ca_x = __builtin_fmaf(sa_x, r.y, -sa_y * r.z), ca_y = __builtin_fmaf(sa_x, r.z, sa_y * r.y);
+					const float cb_x = __builtin_fmaf(sb_x, r.y, -sb_y * r.z), cb_y = __builtin_fmaf(sb_x, r.z, sb_y * r.y);
+					coherent.x += exchange(ca_x, cb_x);
+					coherent.y += exchange(ca_y, cb_y);
+					if constexpr (CW) incoherent += exchange(__builtin_fabsf(r.w) * mag2.x, __builtin_fabsf(r.w) * mag2.y);
+				}
+			};
+			if (mode == 1)      rounds(std::integral_constant<int, 1>{});
+			else if (mode == 2) rounds(std::integral_constant<int, 2>{});
+			else                rounds(std::integral_constant<int, 0>{});
 		}
 	}
 	if (q.depth_major & 2u) staged_violation_report(tid);      /* (block uniform: every thread reaches it) */
@@ -812,11 +835,9 @@ static hipError_t launch_staged_shape(const BfDasArgs *a, const BfSeparableArgs 
 		if (q->u_shift != 5 || q->v_shift != 5 || q->window_samples != 32 || q->threads != 1024 || !q->tables ||
 		    ((q->channel_chunk & 1u) && (int)q->channel_chunk < a->channel_count)) return hipErrorInvalidValue;
 		const uint32_t A4 = ((uint32_t)a->acquisition_count + 3u) & ~3u;
-		const uint32_t ngroups = (A4 + BF_STAGED_PAIRED_GROUP_MAX - 1u) / BF_STAGED_PAIRED_GROUP_MAX;
-		const uint32_t G0 = ((A4 + ngroups - 1u) / ngroups + 3u) & ~3u;
-		switch ((G0 * 64u + 1023u) / 1024u) {                /* staging passes of the largest group (one pass: as two -- the
-		                                                      * one-pass instance of this form spills) */
-		case 1:
+		uint32_t G0, G1;
+		if (!bf_staged_paired_split(A4, q->channel_chunk, &G0, &G1) || q->lds_bytes < bf_staged_paired_lds_bytes(G0, q->channel_chunk, A4)) return hipErrorInvalidValue;
+		switch (bf_staged_paired_passes(G0)) {               /* staging passes of the larger group; the other one's are bounded in the kernel */
 		case 2: return launch_staged_paired<CW, 2>(a, q, s);
 		case 3: return launch_staged_paired<CW, 3>(a, q, s);
 		case 4: return launch_staged_paired<CW, 4>(a, q, s);

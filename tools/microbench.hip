@@ -461,24 +461,63 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_uniform(const f32x4 *table
  * 64-element block (channel 2k's 32-sample window, then channel 2k + 1's; the lane's position carries h * 32), one group of
  * transmits at a time (40 + 36 of the 76).  Per batch of 2 transmits: {T_A, T_B} x 2 and the four phasors from a global table
  * through scalar loads (48 bytes), one packed add per transmit forms both voxels' positions, four taps from the LDS. */
-__global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table, Stamp *stamps, float *sink, int iters)
+/* ROUNDS: the same loop WITH THE ROUNDS AROUND IT, as staged_paired_body runs them per channel pair and group of transmits: the
+ * previous load's registers converted to lines and stored (a wave only in the passes whose transmit belongs to the group), both
+ * barriers, the next round's buffer loads (from a private 1 MiB of `rf` per block) issued before the arithmetic, and the pair's fold
+ * with its three exchanges -- "loop", "loop + rounds" and the kernel on one scale.  table_stride (in f32x4; 0: one table for the chip):
+ * every block reads rows of its own, as the kernel's CUs do out of the frame's table. */
+template <bool ROUNDS, uint32_t G0, uint32_t G1>
+__global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table, uint32_t table_stride, const void *rf, Stamp *stamps, float *sink, int iters)
 {
 	extern __shared__ __attribute__((aligned(16))) f32x4 probe_lds[];
-	constexpr uint32_t G0 = 40, G1 = 36, B = 64;
-	for (uint32_t i = threadIdx.x; i < G0 * B + 3; i += blockDim.x) probe_lds[i] = f32x4{0.5f + 0.001f * i, 0.25f, 0.125f, -0.5f};
+	constexpr uint32_t B = 64, g0 = G0, g1 = G1;
+	for (uint32_t i = threadIdx.x; i < g0 * B + 3; i += blockDim.x) probe_lds[i] = f32x4{0.5f + 0.001f * i, 0.25f, 0.125f, -0.5f};
 	__syncthreads();
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t lane = threadIdx.x & 63u;
 	const float r_rel = 0.4f * (float)(lane & 31u) + 32.f * (float)(lane >> 5);
 	typedef __attribute__((address_space(4))) const f32x4 const_f32x4;
-	const_f32x4 *row = (const_f32x4 *)(uintptr_t)(table + (size_t)wave * ((G0 + G1) / 2) * 3);   /* per wave and batch: {TA0, TB0, TA1, TB1}, {csA0, csB0}, {csA1, csB1} */
+	const_f32x4 *row = (const_f32x4 *)(uintptr_t)(table + (size_t)blockIdx.x * table_stride + (size_t)wave * ((g0 + g1) / 2) * 3);   /* per wave and batch: {TA0, TB0, TA1, TB1}, {csA0, csB0}, {csA1, csB1} */
 	f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f}, mag2 = {0.f, 0.f};
+	[[maybe_unused]] f32x2 coherent = {0.f, 0.f};
+	[[maybe_unused]] float incoherent = 0.f;
+	[[maybe_unused]] f32x2 regs[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+	[[maybe_unused]] const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(rf), 0, (int)(512u << 20), 0x00020000);
+	[[maybe_unused]] const uint32_t lane_at = (blockIdx.x & 511u) * (1u << 20) + wave * 512u + lane * 8u;
+	auto exchange = [](float x, float y) -> float {
+		const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, x), __builtin_bit_cast(uint32_t, y), false, false);
+		return __builtin_bit_cast(float, (uint32_t)r[0]) + __builtin_bit_cast(float, (uint32_t)r[1]);
+	};
 	uint64_t t0 = memtime(), r0 = memrealtime();
 	for (int i = 0; i < iters; i++) {
 		const f32x2 rr = {r_rel, r_rel};
 		const_f32x4 *at_row = row;
+		if constexpr (ROUNDS) { acc1a = acc2a = acc1b = acc2b = mag2 = f32x2{0.f, 0.f}; }
 		for (uint32_t g = 0; g < 2; g++) {
-			const uint32_t n = g ? G1 : G0;
+			const uint32_t n = g ? g1 : g0;
+			if constexpr (ROUNDS) {
+				uint32_t tid = threadIdx.x;
+				asm volatile("" : "+v"(tid));
+				const float half_minus_j = 0.5f - (float)(tid & 63u);
+				__syncthreads();
+				#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					if (wave + (uint32_t)k * 16u >= n) break;
+					const float sx = regs[k].x, sy = regs[k].y;
+					const float nx = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sx), 0x130, 0xf, 0xf, true));
+					const float ny = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sy), 0x130, 0xf, 0xf, true));
+					const float dx = nx - sx, dy = ny - sy;
+					/* (element tid + k * 1024 < n * 64 <= g0 * 64; the buffer holds zeros, so the windows become zero lines: the taps' addresses
+					 * come from the positions, not from the window contents) */
+					probe_lds[2u + tid + (uint32_t)k * 1024u] = f32x4{__builtin_fmaf(half_minus_j, dx, sx), __builtin_fmaf(half_minus_j, dy, sy), dx, dy};
+				}
+				__syncthreads();
+				#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					const uint32_t off = lane_at + ((((uint32_t)i & 15u) * 2u + g) * 3u + (uint32_t)k) * 8192u;
+					regs[k] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off, 0, 0));
+				}
+			}
 			uint32_t m_bits = 0x4B000002u;
 			for (uint32_t a = 0; a < n; a += 2, at_row += 3, m_bits += 2u * B) {
 				const float M = __builtin_bit_cast(float, m_bits);
@@ -504,9 +543,19 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table,
 				mag2 += f32x2{q[0], q[1]}; mag2 += f32x2{q[2], q[3]};
 			}
 		}
+		if constexpr (ROUNDS) {
+			float sa_x = acc1a.x - acc2a.y, sa_y = acc1a.y + acc2a.x, sb_x = acc1b.x - acc2b.y, sb_y = acc1b.y + acc2b.x;
+			asm volatile("" : "+v"(sa_x), "+v"(sa_y), "+v"(sb_x), "+v"(sb_y));
+			const f32x4 r = *(volatile mb_lds_f32x4 *)(uintptr_t)((1u + (lane & 31u)) * 16u);
+			const float ca_x = __builtin_fmaf(sa_x, r.y, -sa_y * r.z), ca_y = __builtin_fmaf(sa_x, r.z, sa_y * r.y);
+			const float cb_x = __builtin_fmaf(sb_x, r.y, -sb_y * r.z), cb_y = __builtin_fmaf(sb_x, r.z, sb_y * r.y);
+			coherent.x += exchange(ca_x, cb_x);
+			coherent.y += exchange(ca_y, cb_y);
+			incoherent += exchange(__builtin_fabsf(r.w) * mag2.x, __builtin_fabsf(r.w) * mag2.y);
+		}
 	}
 	uint64_t t1 = memtime(), r1 = memrealtime();
-	if (mag2.x + mag2.y + acc1a.x + acc1a.y + acc2a.x + acc2a.y + acc1b.x + acc1b.y + acc2b.x + acc2b.y == 12345.678f) sink[0] = mag2.x;
+	if (mag2.x + mag2.y + acc1a.x + acc1a.y + acc2a.x + acc2a.y + acc1b.x + acc1b.y + acc2b.x + acc2b.y + coherent.x + coherent.y + incoherent == 12345.678f) sink[0] = mag2.x;
 	if ((threadIdx.x & 63) == 0) {
 		uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 		stamps[w] = Stamp{t1 - t0, r1 - r0};
@@ -773,31 +822,37 @@ static void loop_uniform_case(const char *what)
 	CHECK(hipFree(d_table));
 }
 
-static void loop_paired_case(const char *what)
+static char *d_window;
+
+/* rounds: the loop with staging, barriers and fold around it; per_block: a table slice per block (29 KB each) instead of one for the chip */
+template <bool ROUNDS, uint32_t g0, uint32_t g1> static void loop_paired_case(const char *what, bool per_block)
 {
 	const int iters = 1000;                            /* 152k terms per wave: 76 transmits x 2 voxels per iteration */
-	const uint32_t lds = 16u * (40u * 64u + 3u) + 64u;
-	CHECK(hipFuncSetAttribute((const void *)loop_probe_paired, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	std::vector<float> h(16 * 38 * 12);
-	for (int w = 0; w < 16; w++) for (int b = 0; b < 38; b++) {
-		float *e = &h[(size_t)(w * 38 + b) * 12];
+	const uint32_t lds = 16u * (g0 * 64u + 3u) + 64u;
+	auto kernel = loop_probe_paired<ROUNDS, g0, g1>;
+	CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	const int batches = (int)(g0 + g1) / 2;
+	int blocks = n_cu * 2, waves = blocks * 16;
+	const int slices = per_block ? blocks : 1;
+	std::vector<float> h((size_t)slices * 16 * batches * 12);
+	for (int sl = 0; sl < slices; sl++) for (int w = 0; w < 16; w++) for (int b = 0; b < batches; b++) {
+		float *e = &h[((size_t)(sl * 16 + w) * batches + b) * 12];
 		for (int k = 0; k < 4; k++) e[k] = 1.f + 0.3f * (w + 16 * (k & 1)) + 0.7f * (float)((2 * b + (k >> 1)) % 5);
 		for (int k = 0; k < 4; k++) { e[4 + 2 * k] = 0.6f; e[5 + 2 * k] = 0.8f; }
 	}
 	f32x4 *d_table;
 	CHECK(hipMalloc(&d_table, h.size() * 4));
 	CHECK(hipMemcpy(d_table, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-	int blocks = n_cu * 2, waves = blocks * 16;
-	Result r = run([&] { hipLaunchKernelGGL(loop_probe_paired, dim3(blocks), dim3(1024), lds, 0, d_table, d_stamps, d_sink, iters); }, waves);
-	double terms = 152.0 * iters;
+	const uint32_t stride = per_block ? 16u * (uint32_t)batches * 3u : 0u;
+	Result r = run([&] { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(1024), lds, 0, d_table, stride, d_window, d_stamps, d_sink, iters); }, waves);
+	double terms = 2.0 * (g0 + g1) * iters;
 	double wall_cycles = r.wall_ms * 1e-3 * r.clock_ghz * 1e9;
-	emit(",\n  {\"stream\":\"%s\",\"waves_per_simd\":8,"
+	emit(",\n  {\"stream\":\"%s\",\"groups\":[%u,%u],\"rounds\":%s,\"table_slice_per_block\":%s,\"waves_per_simd\":8,"
 	     "\"cycles_per_term_per_simd_wall\":%.3f,\"cycles_per_term_per_simd_stamps\":%.3f,\"clock_ghz\":%.3f,\"wall_ms\":%.3f}",
-	     what, wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
+	     what, g0, g1, ROUNDS ? "true" : "false", per_block ? "true" : "false", wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
 	CHECK(hipFree(d_table));
 }
 
-static char *d_window;
 
 template <int WIDTH, int PAT> static void gather_case(const char *level, uint32_t window, bool per_block, bool &first)
 {
@@ -856,7 +911,10 @@ int main(int argc, char **argv)
 		for (int rep = 0; rep < 2; rep++) {
 			loop_case<1>("das_staged inner loop with its LDS reads: address by v_lshlrev_b16");
 			loop_uniform_case("das_staged inner loop, wave-uniform delays and phasors through scalar loads (a 64 x 16 tile), LDS serves the taps only");
-			loop_paired_case("das_staged inner loop, channel-paired (32 x 32 tile, two voxels per lane, transmit groups of 40 + 36): scalar delays and phasors, LDS serves the taps only");
+			loop_paired_case<false, 40, 36>("das_staged inner loop, channel-paired (32 x 32 tile, two voxels per lane, transmit groups of 40 + 36): scalar delays and phasors, LDS serves the taps only", false);
+			loop_paired_case<false, 40, 36>("the same, every block reading table rows of its own", true);
+			loop_paired_case<false, 48, 28>("the same in groups of 48 + 28", true);
+			loop_paired_case<true, 48, 28>("the same with the rounds around the loop (staging passes, two barriers, next round's loads, the pair's fold), groups of 48 + 28", true);
 		}
 		emit("]}\n");
 		fputs(json.c_str(), stdout);
