@@ -619,7 +619,9 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 		asm volatile("" : "+s"(ka));
 		const uint32_t k_size[3] = {ka->size[0], ka->size[1], ka->size[2]};
 		const float k_denom_u = fmaxf(1.0f, (float)k_size[u_axis] - 1.0f);
-		const float k_pz = (float)z / fmaxf(1.0f, (float)k_size[2] - 1.0f);
+		uint32_t k_z = z;                                    /* (opaque: (float)z is formed here, not held in a vector register across the chunks) */
+		asm volatile("" : "+s"(k_z));
+		const float k_pz = (float)k_z / fmaxf(1.0f, (float)k_size[2] - 1.0f);
 		const float k_fs = ka->sampling_frequency, k_inv_c = ka->inv_speed_of_sound, k_c = ka->speed_of_sound, k_fnum = ka->f_number;
 		const float k_phase = ka->demodulation_frequency * ka->inv_sampling_frequency;
 		const float k_pitch = rx_rows ? ka->pitch[1] : ka->pitch[0];
@@ -693,15 +695,11 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 			auto rounds = [&](auto mode_c) {
 				constexpr int MODE = decltype(mode_c)::value;
 				constexpr bool CHECK = MODE == 2;
+				/* the plain loop fetches the next batch's table row ahead (below); the range-checked loop and the four-pass instance have
+				 * no register for that order and read a batch's row at its top */
+				constexpr bool AHEAD = MODE == 1 && NL <= 3;
 				f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f};
 				f32x2 mag2 = {0.f, 0.f};                         /* {voxel A, voxel B} */
-				auto term = [&](f32x2 cs, float pos, f32x4 tap, f32x2 &acc1, f32x2 &acc2) -> float {
-					f32x2 sv = f32x2{tap.x, tap.y} + pos * f32x2{tap.z, tap.w};
-					acc1 += sv.x * cs;
-					acc2 += sv.y * cs;
-					if constexpr (CW) return hw_sqrt(__builtin_fmaf(sv.y, sv.y, sv.x * sv.x));
-					else return 0.f;
-				};
 				for (uint32_t g = 0; g < ngroups; g++) {
 					__syncthreads();               /* everyone is done with the previous round's windows */
 					stage_store(g, regs);
@@ -717,18 +715,21 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 						[[maybe_unused]] int rfl_h = 0;                          /* checked loop: rfloor of the lane's channel - h * W */
 						if constexpr (CHECK) rfl_h = rfloor[2 * k + (int)h] - (int)(h * W);
 						const f32x2 rr = {r_rel, r_rel};
-						const_f32x4 *row = rows + (size_t)(a0 / 2u) * 3u;
-						for (uint32_t a = 0; a < gn; a += 2, m_bits += 2u * B) {
-							uint32_t at[4]; f32x4 tap[4];
+						/* One batch: two transmits, four terms a lane ({A, B} of transmit a, of a + 1), from one table row: positions, tap
+						 * addresses, the LDS reads, then per term interpolation, rotate-accumulate and magnitude.  AHEAD: all rotate-accumulates
+						 * first -- behind them the row is dead --, `behind_rotates`, then the four magnitudes.  (Each accumulator sees its
+						 * terms in the same order either way: the same bits.) */
+						auto batch = [&](uint32_t a, const f32x4 tz, const f32x4 cs0, const f32x4 cs1, auto &&behind_rotates) {
+							constexpr int T = 4;
+							uint32_t at[T]; f32x4 tap[T]; f32x2 sv[T];
 							const float M = __builtin_bit_cast(float, m_bits);
 							const f32x2 M2 = {M, M};
-							const f32x4 tz = row[0], cs0 = row[1], cs1 = row[2];
-							row += 3;
-							const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};   /* {A, B} of transmit a, of a + 1 */
+							const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};
 							const f32x2 y0 = p0 + M2, y1 = p1 + M2;
-							const float ys[4] = {y0.x, y0.y, y1.x, y1.y};
+							const float ys[4] = {y0.x, y0.y, y1.x, y1.y}, ps[4] = {p0.x, p0.y, p1.x, p1.y};
+							const f32x2 cs[4] = {{cs0.x, cs0.y}, {cs0.z, cs0.w}, {cs1.x, cs1.y}, {cs1.z, cs1.w}};
 							#pragma unroll
-							for (int t = 0; t < 4; t++) {
+							for (int t = 0; t < T; t++) {
 								const uint32_t yb = __builtin_bit_cast(uint32_t, ys[t]);
 								asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[t]) : "v"(yb));
 								if constexpr (CHECK) {
@@ -741,12 +742,40 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 								}
 							}
 							#pragma unroll
-							for (int t = 0; t < 4; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
-							const float qa0 = term(f32x2{cs0.x, cs0.y}, p0.x, tap[0], acc1a, acc2a);
-							const float qb0 = term(f32x2{cs0.z, cs0.w}, p0.y, tap[1], acc1b, acc2b);
-							const float qa1 = term(f32x2{cs1.x, cs1.y}, p1.x, tap[2], acc1a, acc2a);
-							const float qb1 = term(f32x2{cs1.z, cs1.w}, p1.y, tap[3], acc1b, acc2b);
-							if constexpr (CW) { mag2 += f32x2{qa0, qb0}; mag2 += f32x2{qa1, qb1}; }
+							for (int t = 0; t < T; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
+							[[maybe_unused]] float q[T];
+							#pragma unroll
+							for (int t = 0; t < T; t++) {
+								sv[t] = f32x2{tap[t].x, tap[t].y} + ps[t] * f32x2{tap[t].z, tap[t].w};
+								if (t & 1) { acc1b += sv[t].x * cs[t]; acc2b += sv[t].y * cs[t]; }
+								else       { acc1a += sv[t].x * cs[t]; acc2a += sv[t].y * cs[t]; }
+								if constexpr (CW && !AHEAD) q[t] = hw_sqrt(__builtin_fmaf(sv[t].y, sv[t].y, sv[t].x * sv[t].x));
+							}
+							behind_rotates();
+							if constexpr (CW) {
+								#pragma unroll
+								for (int t = 0; AHEAD && t < T; t++) q[t] = hw_sqrt(__builtin_fmaf(sv[t].y, sv[t].y, sv[t].x * sv[t].x));
+								mag2 += f32x2{q[0], q[1]}; mag2 += f32x2{q[2], q[3]};
+							}
+						};
+						const_f32x4 *row = rows + (size_t)(a0 / 2u) * 3u;
+						if constexpr (!AHEAD) {
+							for (uint32_t a = 0; a < gn; a += 2, m_bits += 2u * B, row += 3) batch(a, row[0], row[1], row[2], [] {});
+						} else {
+							/* The plain loop asks for the NEXT batch's row where this batch's row dies, behind the last rotate-accumulate: the
+							 * twelve scalars are reloaded in place and the magnitudes cover the scalar loads' latency, so the wait at the top
+							 * of a batch finds them there.  The group's last batch stands behind the loop and asks for nothing: every row
+							 * requested is a row of the group. */
+							f32x4 tz = row[0], cs0 = row[1], cs1 = row[2];
+							uint32_t a = 0;
+							for (; a + 2u < gn; a += 2, m_bits += 2u * B)
+								batch(a, tz, cs0, cs1, [&] {
+									__builtin_amdgcn_sched_barrier(0);
+									row += 3;
+									tz = row[0]; cs0 = row[1]; cs1 = row[2];
+									__builtin_amdgcn_sched_barrier(0);
+								});
+							batch(a, tz, cs0, cs1, [] {});
 						}
 						if constexpr (CHECK) { if (window_left) staged_violation_raise(); }
 					}

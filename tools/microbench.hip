@@ -466,7 +466,10 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_uniform(const f32x4 *table
  * barriers, the next round's buffer loads (from a private 1 MiB of `rf` per block) issued before the arithmetic, and the pair's fold
  * with its three exchanges -- "loop", "loop + rounds" and the kernel on one scale.  table_stride (in f32x4; 0: one table for the chip):
  * every block reads rows of its own, as the kernel's CUs do out of the frame's table. */
-template <bool ROUNDS, uint32_t G0, uint32_t G1>
+/* AHEAD: the row of batch n + 1 is requested behind batch n's last rotate-accumulate, into the scalars that just died, with the
+ * magnitudes as the scalar loads' cover; the group's last batch stands behind the loop and requests nothing (staged_paired_body's
+ * plain loop).  Otherwise a batch starts with its own row's loads and the wait for them. */
+template <bool ROUNDS, uint32_t G0, uint32_t G1, bool AHEAD = false>
 __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table, uint32_t table_stride, const void *rf, Stamp *stamps, float *sink, int iters)
 {
 	extern __shared__ __attribute__((aligned(16))) f32x4 probe_lds[];
@@ -519,28 +522,44 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table,
 				}
 			}
 			uint32_t m_bits = 0x4B000002u;
-			for (uint32_t a = 0; a < n; a += 2, at_row += 3, m_bits += 2u * B) {
+			auto batch = [&](const f32x4 tz, const f32x4 cs0, const f32x4 cs1, auto &&behind_rotates) {
 				const float M = __builtin_bit_cast(float, m_bits);
 				const f32x2 M2 = {M, M};
-				const f32x4 tz = at_row[0], cs0 = at_row[1], cs1 = at_row[2];
 				const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};
 				const f32x2 y0 = p0 + M2, y1 = p1 + M2;
 				const float ys[4] = {y0.x, y0.y, y1.x, y1.y}, ps[4] = {p0.x, p0.y, p1.x, p1.y};
-				uint32_t at[4]; f32x4 tap[4];
+				uint32_t at[4]; f32x4 tap[4]; f32x2 sv[4];
 				#pragma unroll
 				for (int k = 0; k < 4; k++) asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[k]) : "v"(__builtin_bit_cast(uint32_t, ys[k])));
 				#pragma unroll
 				for (int k = 0; k < 4; k++) tap[k] = *(mb_lds_f32x4 *)(uintptr_t)(at[k] + (uint32_t)(k >> 1) * B * 16u);
 				const f32x2 cs[4] = {{cs0.x, cs0.y}, {cs0.z, cs0.w}, {cs1.x, cs1.y}, {cs1.z, cs1.w}};
-				float q[4];
+				#pragma unroll
+				for (int k = 0; k < 4; k++) sv[k] = f32x2{tap[k].x, tap[k].y} + ps[k] * f32x2{tap[k].z, tap[k].w};
 				#pragma unroll
 				for (int k = 0; k < 4; k++) {
-					f32x2 sv = f32x2{tap[k].x, tap[k].y} + ps[k] * f32x2{tap[k].z, tap[k].w};
-					if (k & 1) { acc1b += sv.x * cs[k]; acc2b += sv.y * cs[k]; }
-					else       { acc1a += sv.x * cs[k]; acc2a += sv.y * cs[k]; }
-					q[k] = __builtin_amdgcn_sqrtf(__builtin_fmaf(sv.y, sv.y, sv.x * sv.x));
+					if (k & 1) { acc1b += sv[k].x * cs[k]; acc2b += sv[k].y * cs[k]; }
+					else       { acc1a += sv[k].x * cs[k]; acc2a += sv[k].y * cs[k]; }
 				}
+				behind_rotates();
+				float q[4];
+				#pragma unroll
+				for (int k = 0; k < 4; k++) q[k] = __builtin_amdgcn_sqrtf(__builtin_fmaf(sv[k].y, sv[k].y, sv[k].x * sv[k].x));
 				mag2 += f32x2{q[0], q[1]}; mag2 += f32x2{q[2], q[3]};
+			};
+			if constexpr (AHEAD) {
+				f32x4 tz = at_row[0], cs0 = at_row[1], cs1 = at_row[2];
+				for (uint32_t a = 0; a + 2 < n; a += 2, m_bits += 2u * B)
+					batch(tz, cs0, cs1, [&] {
+						__builtin_amdgcn_sched_barrier(0);
+						at_row += 3;
+						tz = at_row[0]; cs0 = at_row[1]; cs1 = at_row[2];
+						__builtin_amdgcn_sched_barrier(0);
+					});
+				batch(tz, cs0, cs1, [] {});
+				at_row += 3;
+			} else {
+				for (uint32_t a = 0; a < n; a += 2, at_row += 3, m_bits += 2u * B) batch(at_row[0], at_row[1], at_row[2], [] {});
 			}
 		}
 		if constexpr (ROUNDS) {
@@ -825,11 +844,11 @@ static void loop_uniform_case(const char *what)
 static char *d_window;
 
 /* rounds: the loop with staging, barriers and fold around it; per_block: a table slice per block (29 KB each) instead of one for the chip */
-template <bool ROUNDS, uint32_t g0, uint32_t g1> static void loop_paired_case(const char *what, bool per_block)
+template <bool ROUNDS, uint32_t g0, uint32_t g1, bool AHEAD = false> static void loop_paired_case(const char *what, bool per_block)
 {
 	const int iters = 1000;                            /* 152k terms per wave: 76 transmits x 2 voxels per iteration */
 	const uint32_t lds = 16u * (g0 * 64u + 3u) + 64u;
-	auto kernel = loop_probe_paired<ROUNDS, g0, g1>;
+	auto kernel = loop_probe_paired<ROUNDS, g0, g1, AHEAD>;
 	CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	const int batches = (int)(g0 + g1) / 2;
 	int blocks = n_cu * 2, waves = blocks * 16;
@@ -847,9 +866,9 @@ template <bool ROUNDS, uint32_t g0, uint32_t g1> static void loop_paired_case(co
 	Result r = run([&] { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(1024), lds, 0, d_table, stride, d_window, d_stamps, d_sink, iters); }, waves);
 	double terms = 2.0 * (g0 + g1) * iters;
 	double wall_cycles = r.wall_ms * 1e-3 * r.clock_ghz * 1e9;
-	emit(",\n  {\"stream\":\"%s\",\"groups\":[%u,%u],\"rounds\":%s,\"table_slice_per_block\":%s,\"waves_per_simd\":8,"
+	emit(",\n  {\"stream\":\"%s\",\"groups\":[%u,%u],\"rounds\":%s,\"table_slice_per_block\":%s,\"rows_fetched_ahead\":%s,\"waves_per_simd\":8,"
 	     "\"cycles_per_term_per_simd_wall\":%.3f,\"cycles_per_term_per_simd_stamps\":%.3f,\"clock_ghz\":%.3f,\"wall_ms\":%.3f}",
-	     what, g0, g1, ROUNDS ? "true" : "false", per_block ? "true" : "false", wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
+	     what, g0, g1, ROUNDS ? "true" : "false", per_block ? "true" : "false", AHEAD ? "true" : "false", wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
 	CHECK(hipFree(d_table));
 }
 
@@ -914,7 +933,9 @@ int main(int argc, char **argv)
 			loop_paired_case<false, 40, 36>("das_staged inner loop, channel-paired (32 x 32 tile, two voxels per lane, transmit groups of 40 + 36): scalar delays and phasors, LDS serves the taps only", false);
 			loop_paired_case<false, 40, 36>("the same, every block reading table rows of its own", true);
 			loop_paired_case<false, 48, 28>("the same in groups of 48 + 28", true);
+			loop_paired_case<false, 48, 28, true>("groups of 48 + 28, table rows of its own per block, the next batch's row requested behind the rotate-accumulates", true);
 			loop_paired_case<true, 48, 28>("the same with the rounds around the loop (staging passes, two barriers, next round's loads, the pair's fold), groups of 48 + 28", true);
+			loop_paired_case<true, 48, 28, true>("rounds around the loop, groups of 48 + 28, the next batch's row requested behind the rotate-accumulates", true);
 		}
 		emit("]}\n");
 		fputs(json.c_str(), stdout);
