@@ -554,40 +554,54 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 	const bool wave_inside = __builtin_amdgcn_ballot_w64(inside) != 0ull;
 
 	/* Staging: per round thread tid copies element e = tid + n * 1024 (n < NL) of the group's blocks: transmit a0 + e / 64 -- wave
-	 * uniform: its floor comes through a scalar load -- channel 2k + h, sample rfloor + floor(tmin_a) + (tid & 31).  lane_at: the
-	 * lane's part of the byte offset, per channel pair; a missing odd channel and the padding transmits point out of the buffer
-	 * (zeros: the padding transmits need zero windows, their |s| is summed with no phasor). */
+	 * uniform -- channel 2k + h, sample rfloor + floor(tmin_a) + (tid & 31).  lane_at: the lane's part of the byte offset, per
+	 * channel pair; a missing odd channel points out of the buffer (zeros). */
 	const __amdgpu_buffer_rsrc_t rf_rsrc = __builtin_amdgcn_make_buffer_rsrc(
 		const_cast<void *>(p.rf), 0, (int)((uint32_t)C * (uint32_t)A * (uint32_t)S * 8u), 0x00020000);
 	auto lane_at_of = [&](int cl) -> uint32_t { return rbase[cl] + ((opaque_tid() & 31u) << 3); };
-	/* The floors of a round's NL transmits are read first and together (one wait for the scalar loads, not one per pass) at an index
-	 * that always lies in the table, the out-of-range offset is selected afterwards: no branch around a load. */
-	auto stage_load = [&](uint32_t lane_at, uint32_t g, f32x2 (&regs)[NL]) {
+	/* The wave's part of the offset is the same in every round of the tile: (a S + floor(tmin_a)) 8 for the transmit a = a0 + wave + 16 n
+	 * of pass n of group g.  It is formed ONCE per tile and kept in scalars (NL per group), so a round's pass costs one add to the
+	 * lane's offset -- added, not handed to the buffer load as its scalar offset: transmit 0's floor can be negative, and a scalar
+	 * operand that wraps past 4 GiB is not covered by anything this kernel relies on.  A pass the wave does not own -- its transmit
+	 * lies outside the group, or is one of the padding (the loop below stops at the last real transmit, so nobody
+	 * reads such a block) -- is marked by bit 2 (the offsets are multiples of 8): its conversion and store are left by a scalar
+	 * branch, so a group of 28 costs its slowest wave two passes and no wave a pass whose elements nobody keeps; its load is issued
+	 * all the same, 2 GiB further (the host refuses inputs of 2 GiB and more here: such an offset lies outside the buffer and returns
+	 * zeros without a memory access, or, where a missing odd channel's 2 GiB wrap it around, inside it: nothing is kept either way).
+	 * A branch around the load would make the staging registers meet behind it: moves in every round. */
+	constexpr uint32_t STAGE_SKIP = 0x80000004u;
+	uint32_t stage_off[2][NL];
+	#pragma unroll
+	for (int g = 0; g < 2; g++) {
 		const uint32_t a0 = g ? G0 : 0u, gn = g ? G1 : G0;
-		int fl[NL];
-		#pragma unroll
-		for (int n = 0; n < NL; n++) {
-			const uint32_t a = a0 + wave + (uint32_t)n * 16u;
-			fl[n] = tab_floor[a < A4 ? a : A4 - 1u];
-		}
 		#pragma unroll
 		for (int n = 0; n < NL; n++) {
 			const uint32_t al = wave + (uint32_t)n * 16u, a = a0 + al;
-			const bool real = al < gn && a < (uint32_t)A;                        /* wave uniform */
-			const uint32_t off = real ? lane_at + ((a * (uint32_t)S + (uint32_t)fl[n]) * 8u) : 0x80000000u;
-			i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rf_rsrc, (int)off, 0, 0);
+			const int fl = tab_floor[a < A4 ? a : A4 - 1u];                        /* (an index that always lies in the table) */
+			uint32_t off = (a * (uint32_t)S + (uint32_t)fl) * 8u;
+			if (a >= (uint32_t)A) off = STAGE_SKIP;                               /* padding: not staged */
+			if (al >= gn) off = STAGE_SKIP;
+			off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+			asm volatile("" : "+s"(off));                                         /* formed here, not again in every round */
+			stage_off[g][n] = off;
+		}
+	}
+	auto stage_load = [&](uint32_t lane_at, uint32_t g, f32x2 (&regs)[NL]) {
+		#pragma unroll
+		for (int n = 0; n < NL; n++) {
+			const uint32_t off = g ? stage_off[1][n] : stage_off[0][n];
+			i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rf_rsrc, (int)(lane_at + off), 0, 0);
 			regs[n] = __builtin_bit_cast(f32x2, v);
 		}
 	};
-	/* A pass is 16 transmits' blocks, one per wave: wave w converts and stores in pass n only if transmit w + 16 n belongs to the group
-	 * (a scalar branch), so a group of 28 costs its slowest wave two passes and no wave a pass whose elements nobody keeps. */
 	auto stage_store = [&](uint32_t g, const f32x2 (&regs)[NL]) {
-		const uint32_t gn = g ? G1 : G0;
 		const uint32_t tid = opaque_tid();
 		const float half_minus_j = 0.5f - (float)(tid & 63u);  /* the line of element e in the coordinate 1/2 - (e mod 64) */
 		#pragma unroll
 		for (int n = 0; n < NL; n++) {
-			if (wave + (uint32_t)n * 16u >= gn) break;
+			uint32_t off = g ? stage_off[1][n] : stage_off[0][n];
+			asm volatile("" : "+s"(off));                                         /* tested here: not six branch conditions held across the rounds */
+			if (off & 4u) break;                                                  /* (wave uniform; the passes a wave owns come first) */
 			const float sx = regs[n].x, sy = regs[n].y;
 			const float nx = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sx), 0x130, 0xf, 0xf, true));
 			const float ny = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sy), 0x130, 0xf, 0xf, true));
@@ -604,7 +618,11 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 		const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, x), __builtin_bit_cast(uint32_t, y), false, false);
 		return __builtin_bit_cast(float, (uint32_t)r[0]) + __builtin_bit_cast(float, (uint32_t)r[1]);
 	};
-	const f32x4 *Rl = R + (size_t)h * U + lu;               /* the lane's entry of pair k: Rl[2k * U] */
+	/* the lane's receive entry of pair k, R[2k * U + (tid & 63)], as an LDS byte address: rebuilt where it is read (once for the pair's
+	 * mode and delay, once for its fold) rather than held in a vector register across the rounds */
+	uint32_t r_base = (uint32_t)(uintptr_t)(lds_f32x4 *)R;
+	asm("" : "+s"(r_base));
+	auto entry_of = [&](int k) -> uint32_t { return r_base + (uint32_t)k * (2u * U * 16u) + ((opaque_tid() & 63u) << 4); };
 	const uint32_t ulast = (uint32_t)(S - 1);
 	const const_f32x4 *rows = (const_f32x4 *)(uintptr_t)(tile_tab + 4u * A4 + 16u) + (size_t)wave * (A4 / 2u) * 3u;
 
@@ -667,47 +685,63 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 		__syncthreads();
 		/* window-relative delay plus the half offset h * W of the lane's window in the block; the sign of the weight: the lane may leave
 		 * the RF row for some transmit of the tile (the zero partner of an odd channel never does) */
+		int k_last = S - 1;                                  /* (opaque, as k_z above: the float is formed per chunk, not held across them) */
+		asm volatile("" : "+s"(k_last));
 		for (uint32_t e = opaque_tid(); e < (uint32_t)cn2 * U; e += 1024u) {
 			f32x4 entry = R[e];
 			const uint32_t cl = e >> 5;
-			const bool lane_safe = (int)cl >= cn || ((entry.x + range.x >= 0.f) && (entry.x + range.y < (float)(S - 1)));
+			const bool lane_safe = (int)cl >= cn || ((entry.x + range.x >= 0.f) && (entry.x + range.y < (float)k_last));
 			entry.x = (entry.x - (float)rfloor[cl]) + (float)((cl & 1u) * W);     /* both steps exact */
 			if (!lane_safe) entry.w = -entry.w;
 			R[e] = entry;
 		}
 		__syncthreads();
 
-		f32x2 regs[NL];
-		stage_load(lane_at_of((int)h), 0, regs);
-		for (int k = 0; k < cn2 / 2; k++) {
-			/* the lane's receive entry and what the wave does with this channel pair, once per pair: nothing (no voxel inside, or the
-			 * f-number culls both channels for every lane), the plain loop, or the range-checked one.  The pair's rounds are written
-			 * once per case (`rounds` below), so that the accumulators live in one loop nest each and are not copied where the cases
-			 * would meet after every round. */
-			float r_rel = 0.f;
-			int mode = 0;
-			if (wave_inside) {
-				const f32x4 r = Rl[(size_t)(2 * k) * U];
-				r_rel = r.x;
-				if (__builtin_amdgcn_ballot_w64(r.w != 0.f) != 0)        /* F# culling per wave (both channels of the pair) */
-					mode = (!(q.depth_major & 2u) && __builtin_amdgcn_ballot_w64(__builtin_signbitf(r.w)) == 0) ? 1 : 2;
-			}
-			auto rounds = [&](auto mode_c) {
-				constexpr int MODE = decltype(mode_c)::value;
-				constexpr bool CHECK = MODE == 2;
-				/* the plain loop fetches the next batch's table row ahead (below); the range-checked loop and the four-pass instance have
-				 * no register for that order and read a batch's row at its top */
-				constexpr bool AHEAD = MODE == 1 && NL <= 3;
+		/* What a wave does with a channel pair: nothing (no voxel inside, or the f-number culls both channels for every lane), the plain
+		 * loop, or the range-checked one -- decided once per pair from the lane's receive entry, whose delay the pair's rounds use. */
+		const int pairs = cn2 / 2;
+		auto mode_of = [&](int k, float &r_rel) -> int {
+			if (!wave_inside) return 0;
+			const __attribute__((address_space(3))) float *r = (const __attribute__((address_space(3))) float *)(uintptr_t)entry_of(k);
+			const float r_w = r[3];                                            /* (two words of the entry, not the four) */
+			r_rel = r[0];
+			if (__builtin_amdgcn_ballot_w64(r_w != 0.f) == 0) return 0;        /* F# culling per wave (both channels of the pair) */
+			return (!(q.depth_major & 2u) && __builtin_amdgcn_ballot_w64(__builtin_signbitf(r_w)) == 0) ? 1 : 2;
+		};
+		float r_rel = 0.f;
+		int k = 0, mode = mode_of(0, r_rel);
+		/* A RUN of pairs: the pairs from k on for as long as the wave's mode stays MODE, at most to the end of the chunk.  The aperture
+		 * is a contiguous range of channels, so a wave's mode changes a handful of times over a frame's pairs; with the pair loop inside
+		 * the case the staging registers and the voxel's sums stay where they are from pair to pair, and the three cases meet once per
+		 * run instead of once per pair.  Every wave executes the same sequence of rounds whatever its mode: the barriers are block
+		 * uniform.  The staging registers belong to the run: it requests its first pair's windows itself, and its last pair requests
+		 * nothing -- the next pair's case is looked up at the top of a pair, before the round where the request would stand --, so no
+		 * load is in flight where two cases meet (a few times per tile, against a chunk's own first request once per chunk). */
+		auto run = [&](auto mode_c) {
+			constexpr int MODE = decltype(mode_c)::value;
+			constexpr bool CHECK = MODE == 2;
+			/* the plain loop fetches the next batch's table row ahead (below); the range-checked loop and the four-pass instance have
+			 * no register for that order and read a batch's row at its top */
+			constexpr bool AHEAD = MODE == 1 && NL <= 3;
+			f32x2 regs[NL] = {};
+			stage_load(lane_at_of(2 * k + (int)h), 0, regs);
+			do {
+				float next_rel = 0.f;
+				int next_mode = -1;                              /* (behind the chunk's last pair: no case) */
+				if (k + 1 < pairs) next_mode = mode_of(k + 1, next_rel);
 				f32x2 acc1a = {0.f, 0.f}, acc2a = {0.f, 0.f}, acc1b = {0.f, 0.f}, acc2b = {0.f, 0.f};
 				f32x2 mag2 = {0.f, 0.f};                         /* {voxel A, voxel B} */
 				for (uint32_t g = 0; g < ngroups; g++) {
 					__syncthreads();               /* everyone is done with the previous round's windows */
 					stage_store(g, regs);
 					__syncthreads();
-					if (g + 1 < ngroups)     stage_load(lane_at_of(2 * k + (int)h), g + 1, regs);     /* in flight during the arithmetic */
-					else if (2 * k + 2 < cn2) stage_load(lane_at_of(2 * k + 2 + (int)h), 0, regs);
+					if (g + 1 < ngroups) stage_load(lane_at_of(2 * k + (int)h), 1, regs);         /* in flight during the arithmetic */
+					else if (next_mode == MODE) stage_load(lane_at_of(2 * k + 2 + (int)h), 0, regs);
 					if constexpr (MODE != 0) {
 						const uint32_t a0 = g ? G0 : 0u, gn = g ? G1 : G0;
+						/* the transmits the round runs: the group's, or only its real ones (the padding of the count to a multiple of 4
+						 * sits at the end of the last group: zero phasors over zero windows, 1/76 of config 4's terms) */
+						const uint32_t left = (uint32_t)A - a0, gr = left < gn ? left : gn;
 						/* position -> tap as staged_body; M = 2^23 + 2 + (the batch's first block) * 64, the lane's window starts h * W
 						 * further (its receive entry carries that offset) */
 						uint32_t m_bits = 0x4B000002u;
@@ -718,10 +752,12 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 						/* One batch: two transmits, four terms a lane ({A, B} of transmit a, of a + 1), from one table row: positions, tap
 						 * addresses, the LDS reads, then per term interpolation, rotate-accumulate and magnitude.  AHEAD: all rotate-accumulates
 						 * first -- behind them the row is dead --, `behind_rotates`, then the four magnitudes.  (Each accumulator sees its
-						 * terms in the same order either way: the same bits.) */
-						auto batch = [&](uint32_t a, const f32x4 tz, const f32x4 cs0, const f32x4 cs1, auto &&behind_rotates) {
-							constexpr int T = 4;
-							uint32_t at[T]; f32x4 tap[T]; f32x2 sv[T];
+						 * terms in the same order either way: the same bits.)  PART: both transmits of the row, or only its first or its second
+						 * -- the same body, so that a group of an odd number of real transmits ends in the pair path's own registers. */
+						auto batch = [&](auto part_c, uint32_t a, const f32x4 tz, const f32x4 cs0, const f32x4 cs1, auto &&behind_rotates) {
+							constexpr int PART = decltype(part_c)::value;
+							constexpr int T0 = PART == 2 ? 2 : 0, T = PART == 1 ? 2 : 4;      /* terms T0 .. T - 1 */
+							uint32_t at[4]; f32x4 tap[4]; f32x2 sv[4];
 							const float M = __builtin_bit_cast(float, m_bits);
 							const f32x2 M2 = {M, M};
 							const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};
@@ -729,7 +765,7 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 							const float ys[4] = {y0.x, y0.y, y1.x, y1.y}, ps[4] = {p0.x, p0.y, p1.x, p1.y};
 							const f32x2 cs[4] = {{cs0.x, cs0.y}, {cs0.z, cs0.w}, {cs1.x, cs1.y}, {cs1.z, cs1.w}};
 							#pragma unroll
-							for (int t = 0; t < T; t++) {
+							for (int t = T0; t < T; t++) {
 								const uint32_t yb = __builtin_bit_cast(uint32_t, ys[t]);
 								asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[t]) : "v"(yb));
 								if constexpr (CHECK) {
@@ -742,10 +778,10 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 								}
 							}
 							#pragma unroll
-							for (int t = 0; t < T; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
-							[[maybe_unused]] float q[T];
+							for (int t = T0; t < T; t++) tap[t] = *(lds_f32x4 *)(uintptr_t)(at[t] + (CHECK ? 0u : (uint32_t)(t >> 1) * B * 16u));
+							[[maybe_unused]] float q[4] = {0.f, 0.f, 0.f, 0.f};
 							#pragma unroll
-							for (int t = 0; t < T; t++) {
+							for (int t = T0; t < T; t++) {
 								sv[t] = f32x2{tap[t].x, tap[t].y} + ps[t] * f32x2{tap[t].z, tap[t].w};
 								if (t & 1) { acc1b += sv[t].x * cs[t]; acc2b += sv[t].y * cs[t]; }
 								else       { acc1a += sv[t].x * cs[t]; acc2a += sv[t].y * cs[t]; }
@@ -754,28 +790,35 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 							behind_rotates();
 							if constexpr (CW) {
 								#pragma unroll
-								for (int t = 0; AHEAD && t < T; t++) q[t] = hw_sqrt(__builtin_fmaf(sv[t].y, sv[t].y, sv[t].x * sv[t].x));
-								mag2 += f32x2{q[0], q[1]}; mag2 += f32x2{q[2], q[3]};
+								for (int t = T0; AHEAD && t < T; t++) q[t] = hw_sqrt(__builtin_fmaf(sv[t].y, sv[t].y, sv[t].x * sv[t].x));
+								if constexpr (T0 == 0) mag2 += f32x2{q[0], q[1]};
+								if constexpr (T == 4)  mag2 += f32x2{q[2], q[3]};
 							}
 						};
+						constexpr std::integral_constant<int, 0> both{};
+						constexpr std::integral_constant<int, 1> first{};
+						constexpr std::integral_constant<int, 2> second{};
 						const_f32x4 *row = rows + (size_t)(a0 / 2u) * 3u;
+						uint32_t a = 0;
 						if constexpr (!AHEAD) {
-							for (uint32_t a = 0; a < gn; a += 2, m_bits += 2u * B, row += 3) batch(a, row[0], row[1], row[2], [] {});
+							for (; a + 1u < gr; a += 2, m_bits += 2u * B, row += 3) batch(both, a, row[0], row[1], row[2], [] {});
+							if (a < gr) batch(first, a, row[0], row[1], row[1], [] {});
 						} else {
 							/* The plain loop asks for the NEXT batch's row where this batch's row dies, behind the last rotate-accumulate: the
 							 * twelve scalars are reloaded in place and the magnitudes cover the scalar loads' latency, so the wait at the top
-							 * of a batch finds them there.  The group's last batch stands behind the loop and asks for nothing: every row
-							 * requested is a row of the group. */
+							 * of a batch finds them there.  The group's last row stands behind the loop and asks for nothing: every row requested
+							 * is a row of the group.  It is written as its first transmit and, if that is a real one, its second: written as
+							 * "a pair or one transmit" hipcc computes the common half once into new registers and copies four sums back. */
 							f32x4 tz = row[0], cs0 = row[1], cs1 = row[2];
-							uint32_t a = 0;
-							for (; a + 2u < gn; a += 2, m_bits += 2u * B)
-								batch(a, tz, cs0, cs1, [&] {
+							for (; a + 2u < gr; a += 2, m_bits += 2u * B)
+								batch(both, a, tz, cs0, cs1, [&] {
 									__builtin_amdgcn_sched_barrier(0);
 									row += 3;
 									tz = row[0]; cs0 = row[1]; cs1 = row[2];
 									__builtin_amdgcn_sched_barrier(0);
 								});
-							batch(a, tz, cs0, cs1, [] {});
+							batch(first, a, tz, cs0, cs1, [] {});
+							if (a + 1u < gr) batch(second, a, tz, cs0, cs1, [] {});
 						}
 						if constexpr (CHECK) { if (window_left) staged_violation_raise(); }
 					}
@@ -785,17 +828,24 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 					float sa_x = acc1a.x - acc2a.y, sa_y = acc1a.y + acc2a.x;
 					float sb_x = acc1b.x - acc2b.y, sb_y = acc1b.y + acc2b.x;
 					asm volatile("" : "+v"(sa_x), "+v"(sa_y), "+v"(sb_x), "+v"(sb_y));
-					const f32x4 r = *(volatile lds_f32x4 *)(uintptr_t)((uint32_t)(uintptr_t)(lds_f32x4 *)Rl + (uint32_t)(2 * k) * U * 16u);
+					const f32x4 r = *(volatile lds_f32x4 *)(uintptr_t)entry_of(k);
 					const float ca_x = __builtin_fmaf(sa_x, r.y, -sa_y * r.z), ca_y = __builtin_fmaf(sa_x, r.z, sa_y * r.y);
 					const float cb_x = __builtin_fmaf(sb_x, r.y, -sb_y * r.z), cb_y = __builtin_fmaf(sb_x, r.z, sb_y * r.y);
 					coherent.x += exchange(ca_x, cb_x);
 					coherent.y += exchange(ca_y, cb_y);
 					if constexpr (CW) incoherent += exchange(__builtin_fabsf(r.w) * mag2.x, __builtin_fabsf(r.w) * mag2.y);
 				}
-			};
-			if (mode == 1)      rounds(std::integral_constant<int, 1>{});
-			else if (mode == 2) rounds(std::integral_constant<int, 2>{});
-			else                rounds(std::integral_constant<int, 0>{});
+				k++;
+				mode = next_mode;
+				/* (the four-pass instance has no register to carry the next pair's delay through the round: it reads it again) */
+				if constexpr (NL >= 4) next_rel = mode > 0 ? *(volatile __attribute__((address_space(3))) float *)(uintptr_t)entry_of(k) : 0.f;
+				r_rel = next_rel;
+			} while (mode == MODE);
+		};
+		while (k < pairs) {
+			if (mode == 1)      run(std::integral_constant<int, 1>{});
+			else if (mode == 2) run(std::integral_constant<int, 2>{});
+			else                run(std::integral_constant<int, 0>{});
 		}
 	}
 	if (q.depth_major & 2u) staged_violation_report(tid);      /* (block uniform: every thread reaches it) */

@@ -469,7 +469,10 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_uniform(const f32x4 *table
 /* AHEAD: the row of batch n + 1 is requested behind batch n's last rotate-accumulate, into the scalars that just died, with the
  * magnitudes as the scalar loads' cover; the group's last batch stands behind the loop and requests nothing (staged_paired_body's
  * plain loop).  Otherwise a batch starts with its own row's loads and the wait for them. */
-template <bool ROUNDS, uint32_t G0, uint32_t G1, bool AHEAD = false>
+/* PAD: the last PAD transmits of the second group are the padding of the count to a multiple of 4 (config 4: 75 real ones, PAD = 1):
+ * the rounds neither stage nor run them, and a group's last row is run as its first transmit and, if that is a real one, its second
+ * (staged_paired_body since round 8).  Cycles per term are still quoted per PADDED term, so that the figures stay on one scale. */
+template <bool ROUNDS, uint32_t G0, uint32_t G1, bool AHEAD = false, uint32_t PAD = 0>
 __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table, uint32_t table_stride, const void *rf, Stamp *stamps, float *sink, int iters)
 {
 	extern __shared__ __attribute__((aligned(16))) f32x4 probe_lds[];
@@ -497,7 +500,7 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table,
 		const_f32x4 *at_row = row;
 		if constexpr (ROUNDS) { acc1a = acc2a = acc1b = acc2b = mag2 = f32x2{0.f, 0.f}; }
 		for (uint32_t g = 0; g < 2; g++) {
-			const uint32_t n = g ? g1 : g0;
+			const uint32_t n = g ? g1 - PAD : g0;            /* the real transmits of the group */
 			if constexpr (ROUNDS) {
 				uint32_t tid = threadIdx.x;
 				asm volatile("" : "+v"(tid));
@@ -522,7 +525,9 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table,
 				}
 			}
 			uint32_t m_bits = 0x4B000002u;
-			auto batch = [&](const f32x4 tz, const f32x4 cs0, const f32x4 cs1, auto &&behind_rotates) {
+			/* part_c: 0 both transmits of the row, 1 its first only, 2 its second only */
+			auto batch = [&](auto part_c, const f32x4 tz, const f32x4 cs0, const f32x4 cs1, auto &&behind_rotates) {
+				constexpr int PART = decltype(part_c)::value, K0 = PART == 2 ? 2 : 0, K1 = PART == 1 ? 2 : 4;
 				const float M = __builtin_bit_cast(float, m_bits);
 				const f32x2 M2 = {M, M};
 				const f32x2 p0 = rr + f32x2{tz.x, tz.y}, p1 = rr + f32x2{tz.z, tz.w};
@@ -530,36 +535,43 @@ __global__ __launch_bounds__(1024, 8) void loop_probe_paired(const f32x4 *table,
 				const float ys[4] = {y0.x, y0.y, y1.x, y1.y}, ps[4] = {p0.x, p0.y, p1.x, p1.y};
 				uint32_t at[4]; f32x4 tap[4]; f32x2 sv[4];
 				#pragma unroll
-				for (int k = 0; k < 4; k++) asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[k]) : "v"(__builtin_bit_cast(uint32_t, ys[k])));
+				for (int k = K0; k < K1; k++) asm("v_lshlrev_b16 %0, 4, %1" : "=v"(at[k]) : "v"(__builtin_bit_cast(uint32_t, ys[k])));
 				#pragma unroll
-				for (int k = 0; k < 4; k++) tap[k] = *(mb_lds_f32x4 *)(uintptr_t)(at[k] + (uint32_t)(k >> 1) * B * 16u);
+				for (int k = K0; k < K1; k++) tap[k] = *(mb_lds_f32x4 *)(uintptr_t)(at[k] + (uint32_t)(k >> 1) * B * 16u);
 				const f32x2 cs[4] = {{cs0.x, cs0.y}, {cs0.z, cs0.w}, {cs1.x, cs1.y}, {cs1.z, cs1.w}};
 				#pragma unroll
-				for (int k = 0; k < 4; k++) sv[k] = f32x2{tap[k].x, tap[k].y} + ps[k] * f32x2{tap[k].z, tap[k].w};
+				for (int k = K0; k < K1; k++) sv[k] = f32x2{tap[k].x, tap[k].y} + ps[k] * f32x2{tap[k].z, tap[k].w};
 				#pragma unroll
-				for (int k = 0; k < 4; k++) {
+				for (int k = K0; k < K1; k++) {
 					if (k & 1) { acc1b += sv[k].x * cs[k]; acc2b += sv[k].y * cs[k]; }
 					else       { acc1a += sv[k].x * cs[k]; acc2a += sv[k].y * cs[k]; }
 				}
 				behind_rotates();
-				float q[4];
+				float q[4] = {0.f, 0.f, 0.f, 0.f};
 				#pragma unroll
-				for (int k = 0; k < 4; k++) q[k] = __builtin_amdgcn_sqrtf(__builtin_fmaf(sv[k].y, sv[k].y, sv[k].x * sv[k].x));
-				mag2 += f32x2{q[0], q[1]}; mag2 += f32x2{q[2], q[3]};
+				for (int k = K0; k < K1; k++) q[k] = __builtin_amdgcn_sqrtf(__builtin_fmaf(sv[k].y, sv[k].y, sv[k].x * sv[k].x));
+				if constexpr (K0 == 0) mag2 += f32x2{q[0], q[1]};
+				if constexpr (K1 == 4) mag2 += f32x2{q[2], q[3]};
 			};
 			if constexpr (AHEAD) {
 				f32x4 tz = at_row[0], cs0 = at_row[1], cs1 = at_row[2];
-				for (uint32_t a = 0; a + 2 < n; a += 2, m_bits += 2u * B)
-					batch(tz, cs0, cs1, [&] {
+				uint32_t a = 0;
+				for (; a + 2 < n; a += 2, m_bits += 2u * B)
+					batch(std::integral_constant<int, 0>{}, tz, cs0, cs1, [&] {
 						__builtin_amdgcn_sched_barrier(0);
 						at_row += 3;
 						tz = at_row[0]; cs0 = at_row[1]; cs1 = at_row[2];
 						__builtin_amdgcn_sched_barrier(0);
 					});
-				batch(tz, cs0, cs1, [] {});
+				if constexpr (PAD == 0) batch(std::integral_constant<int, 0>{}, tz, cs0, cs1, [] {});
+				else {
+					batch(std::integral_constant<int, 1>{}, tz, cs0, cs1, [] {});
+					if (a + 1 < n) batch(std::integral_constant<int, 2>{}, tz, cs0, cs1, [] {});
+				}
 				at_row += 3;
 			} else {
-				for (uint32_t a = 0; a < n; a += 2, at_row += 3, m_bits += 2u * B) batch(at_row[0], at_row[1], at_row[2], [] {});
+				static_assert(AHEAD || PAD == 0, "the padding is only left out of the loop that fetches its rows ahead");
+				for (uint32_t a = 0; a < n; a += 2, at_row += 3, m_bits += 2u * B) batch(std::integral_constant<int, 0>{}, at_row[0], at_row[1], at_row[2], [] {});
 			}
 		}
 		if constexpr (ROUNDS) {
@@ -844,11 +856,11 @@ static void loop_uniform_case(const char *what)
 static char *d_window;
 
 /* rounds: the loop with staging, barriers and fold around it; per_block: a table slice per block (29 KB each) instead of one for the chip */
-template <bool ROUNDS, uint32_t g0, uint32_t g1, bool AHEAD = false> static void loop_paired_case(const char *what, bool per_block)
+template <bool ROUNDS, uint32_t g0, uint32_t g1, bool AHEAD = false, uint32_t PAD = 0> static void loop_paired_case(const char *what, bool per_block)
 {
 	const int iters = 1000;                            /* 152k terms per wave: 76 transmits x 2 voxels per iteration */
 	const uint32_t lds = 16u * (g0 * 64u + 3u) + 64u;
-	auto kernel = loop_probe_paired<ROUNDS, g0, g1, AHEAD>;
+	auto kernel = loop_probe_paired<ROUNDS, g0, g1, AHEAD, PAD>;
 	CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	const int batches = (int)(g0 + g1) / 2;
 	int blocks = n_cu * 2, waves = blocks * 16;
@@ -866,9 +878,9 @@ template <bool ROUNDS, uint32_t g0, uint32_t g1, bool AHEAD = false> static void
 	Result r = run([&] { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(1024), lds, 0, d_table, stride, d_window, d_stamps, d_sink, iters); }, waves);
 	double terms = 2.0 * (g0 + g1) * iters;
 	double wall_cycles = r.wall_ms * 1e-3 * r.clock_ghz * 1e9;
-	emit(",\n  {\"stream\":\"%s\",\"groups\":[%u,%u],\"rounds\":%s,\"table_slice_per_block\":%s,\"rows_fetched_ahead\":%s,\"waves_per_simd\":8,"
+	emit(",\n  {\"stream\":\"%s\",\"groups\":[%u,%u],\"rounds\":%s,\"table_slice_per_block\":%s,\"rows_fetched_ahead\":%s,\"padding_transmits_left_out\":%u,\"waves_per_simd\":8,"
 	     "\"cycles_per_term_per_simd_wall\":%.3f,\"cycles_per_term_per_simd_stamps\":%.3f,\"clock_ghz\":%.3f,\"wall_ms\":%.3f}",
-	     what, g0, g1, ROUNDS ? "true" : "false", per_block ? "true" : "false", AHEAD ? "true" : "false", wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
+	     what, g0, g1, ROUNDS ? "true" : "false", per_block ? "true" : "false", AHEAD ? "true" : "false", PAD, wall_cycles / (terms * 8), r.cycles_per_wave / (terms * 8), r.clock_ghz, r.wall_ms);
 	CHECK(hipFree(d_table));
 }
 
@@ -936,6 +948,7 @@ int main(int argc, char **argv)
 			loop_paired_case<false, 48, 28, true>("groups of 48 + 28, table rows of its own per block, the next batch's row requested behind the rotate-accumulates", true);
 			loop_paired_case<true, 48, 28>("the same with the rounds around the loop (staging passes, two barriers, next round's loads, the pair's fold), groups of 48 + 28", true);
 			loop_paired_case<true, 48, 28, true>("rounds around the loop, groups of 48 + 28, the next batch's row requested behind the rotate-accumulates", true);
+			loop_paired_case<true, 48, 28, true, 1>("the same over the 75 real transmits only: the padding transmit neither staged nor run, a group's last row as single transmits", true);
 		}
 		emit("]}\n");
 		fputs(json.c_str(), stdout);
