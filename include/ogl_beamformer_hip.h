@@ -115,6 +115,60 @@ typedef struct {
 /* Timings of the newest frame; waits for it to finish. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_frame_timings(BeamformerHipFrameTimings *out);
 
+/* ---- bursts: N RF frames of one geometry per call (Flash / ULM ensembles: hundreds of frames from one parameter block) ----
+ * frame_count RF frames back to back in `data`, each `frame_size` bytes under exactly the layout and size rules of
+ * beamformer_push_data_with_compute; all beamformed with parameter block `parameter_slot`.  Queues frame_count frames: they
+ * take consecutive frame ids, oldest = first in `data`, and beamformer_get_last_frames(out, size, frame_count) returns them.
+ *   - one upload, one RF-ring slot (grown to hold the burst), one API call; the frames lie contiguously in the frame ring (a burst
+ *     that would straddle its end starts again at offset 0);
+ *   - RCA-family blocks (Flash, RCA_TPW, RCA_VLS) whose single frames run the general kernel take ONE DAS launch for the whole
+ *     burst (csrc/das_burst.hip: a thread computes the geometry of each (channel, transmit) term once and applies it to
+ *     BEAMFORMER_HIP_BURST_FRAMES_PER_THREAD frames); every other block runs its single-frame DAS kernel once per frame on that
+ *     frame's slice of the batched DAS input.  beamformer_hip_describe_burst says which, and why;
+ *   - the ingest and every pre-DAS stage run ONCE for the burst (the filters in chunks of 65535 / channel_count frames: the grid limit);
+ *   - validation is the single push's, per frame, with the same error kinds; frame_count == 0 and frame_count >
+ *     BEAMFORMER_HIP_MAX_BURST_FRAMES are BufferOverflow; frame_count == 1 IS the single push.  The burst must fit as a whole:
+ *     frame_count x the 64-byte-rounded frame must not exceed the frame ring (FrameSizeOverflow) and the RF must fit device memory
+ *     (RFDataSizeOverflow).  A burst that is refused queues nothing: no frame id is consumed.  A burst that fails after that leaves
+ *     a tombstone under every one of its ids, as a failed single push does under its one;
+ *   - every frame of a burst appears in beamformer_compute_timings and beamformer_hip_get_last_frame_timings with the burst's
+ *     stage times divided by frame_count (one event set per burst);
+ *   - several devices (beamformer_hip_set_devices, count > 1): refused with InvalidAccess -- a burst is not sharded; frame graphs:
+ *     a burst runs as direct launches; pair counting: the geometry-only count runs once and every frame of the burst reports it; an
+ *     output shard on the block is honoured. */
+#define BEAMFORMER_HIP_MAX_BURST_FRAMES        1024u
+#define BEAMFORMER_HIP_BURST_FRAMES_PER_THREAD 4u
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_data_burst_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                                           uint32_t image_plane_tag, uint32_t parameter_slot);
+/* ... for RF that already resides on the library's device (beamformer_hip_push_device_data_with_compute's rules; a burst is always
+ * copied or ingested into the RF ring, never read in place) */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_device_data_burst_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                                  uint32_t image_plane_tag, uint32_t parameter_slot);
+
+typedef struct {
+	uint32_t burst_kernel;          /* 1: das_burst.hip takes the burst in das_launches launches; 0: the single-frame kernel(s), once per frame */
+	int32_t  single_path;           /* the single-frame decision this was derived from (BeamformerHipFrameTimings::das_path numbering; -1 / -2 as
+	                                   BeamformerHipDasDescription::path) */
+	uint32_t frames_per_thread;     /* burst kernel: BEAMFORMER_HIP_BURST_FRAMES_PER_THREAD; else 1 */
+	uint32_t das_launches;          /* DAS launches of the whole burst */
+	uint32_t stage_launches;        /* launches the whole burst takes of a pre-DAS filter stage (1 up to 65535 / channel_count frames); the ingest, Decode, Reshape: 1 */
+	uint32_t min_frames;            /* the smallest burst the burst kernel takes (csrc/das_select.h: kBurstMinFrames) */
+	char     reason[160];           /* why this route */
+} BeamformerHipBurstDescription;
+/* What a burst of frame_count frames of a parameter block would run, under the current das path mode.  Needs no device. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_burst(uint32_t parameter_slot, uint32_t frame_count, BeamformerHipBurstDescription *out);
+
+typedef struct {
+	BeamformerHipBurstDescription route;   /* of the burst that ran */
+	uint32_t first_frame_id, frame_count;
+	uint32_t stage_count;
+	uint32_t stage_kind[BEAMFORMER_HIP_MAX_TIMED_STAGES];  /* BeamformerShaderKind; ingest = 0xFFFF */
+	float    stage_ms[BEAMFORMER_HIP_MAX_TIMED_STAGES];    /* hipEvent pairs around each stage of the WHOLE burst */
+	float    burst_ms;                                     /* first event to last event */
+} BeamformerHipBurstInfo;
+/* The newest burst (frame_count >= 2); waits for it to finish.  Fails when the newest push was not a burst or did not complete. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_burst_info(BeamformerHipBurstInfo *out);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */
@@ -218,6 +272,7 @@ typedef enum {
 	BeamformerHipDasPath_TileStaging      = 0x100,/* flag: das_tile.hip (factored kernel, block-wide LDS staging of cubic polynomials) wherever it is supported --
 	                                                 automatic on fine grids only */
 	BeamformerHipDasPath_NoTileStaging    = 0x200,/* flag: never */
+	BeamformerHipDasPath_NoBurstKernel    = 0x400,/* flag: a burst (below) runs the single-frame DAS kernel once per frame also where das_burst.hip would take it */
 } BeamformerHipDasPath;
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_das_path(uint32_t mode);
 /* Environment variables the library reads (none is needed in production):

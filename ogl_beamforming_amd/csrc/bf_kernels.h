@@ -71,6 +71,14 @@ typedef struct {
 	                                     have an instantiation without any row-end code for launches where it is 0 */
 } BfDasArgs;
 
+/* ensemble form of the general kernel (das_burst.hip): frames a thread carries through one walk of its (channel, transmit) terms */
+#define BF_BURST_FRAMES_PER_THREAD 4u
+typedef struct {
+	uint32_t frame_count;             /* frames of the launch: frame f reads BfDasArgs.rf + f * rf_stride and writes BfDasArgs.out + f * out_stride */
+	uint32_t pad;
+	uint64_t rf_stride, out_stride;   /* bytes */
+} BfBurstArgs;
+
 /* channel-paired staged kernel (uniform = 2): the LDS holds the 64-element blocks (two channels' 32-sample windows) of at most this
  * many transmits at a time -- a multiple of 4 whose block indices, plus the two elements in front, stay below 4096 (the tap address
  * is a 16-bit shift of the element index) */
@@ -179,6 +187,8 @@ typedef struct {
 	uint32_t channels;
 	int32_t  a1s2, base;              /* A1S2 contrast reduction on BF_BASE_* scalars */
 	uint32_t a1s2_scalars;            /* sample_count * element_count */
+	uint32_t frames;                  /* a burst (executor.cpp push_burst): frames of the launch, 0 or 1 = one; frame f reads and writes f * the strides below further on */
+	uint64_t in_frame_bytes, out_frame_bytes;
 } BfIngestArgs;
 
 typedef struct {
@@ -186,6 +196,8 @@ typedef struct {
 	uint32_t size[3];
 	int64_t  in_stride[3], out_stride[3];
 	int32_t  in_kind, out_kind, interleave;
+	uint32_t frames;                  /* a burst (executor.cpp push_burst): frames of the launch, 0 or 1 = one; frame f reads and writes f * the strides below further on */
+	uint64_t in_frame_bytes, out_frame_bytes;
 } BfReshapeArgs;
 
 typedef struct {
@@ -196,6 +208,8 @@ typedef struct {
 	uint32_t transmit_count, channel_count, sample_count;
 	int64_t  out_stride[3];           /* sample, channel, transmit */
 	int32_t  in_kind, out_kind;
+	uint32_t frames;                  /* a burst (executor.cpp push_burst): frames of the launch, 0 or 1 = one; frame f reads and writes f * the strides below further on */
+	uint64_t in_frame_bytes, out_frame_bytes;
 } BfDecodeArgs;
 
 typedef struct {
@@ -209,6 +223,8 @@ typedef struct {
 	int64_t  in_elements;
 	uint32_t channels, transmits;
 	int32_t  in_kind, out_kind;
+	uint32_t frames;                  /* a burst (executor.cpp push_burst): frames of the launch, 0 or 1 = one; frame f reads and writes f * the strides below further on */
+	uint64_t in_frame_bytes, out_frame_bytes;
 } BfFilterArgs;
 
 /* Depth-major tile walk of VOLUMES (separable gather and LDS-staged kernels).  An XCD has ~64 consecutive tiles of its run in flight (two
@@ -265,6 +281,9 @@ static __device__ __forceinline__ bool bf_plane_walk(uint32_t block_id, uint32_t
 }
 #endif
 
+/* frames of a burst one Filter / Demodulate / Hilbert launch takes: they share grid y (at most 65535 blocks) with the channels */
+static inline uint32_t bf_stage_frame_chunk(uint32_t channels) { return channels && channels < 65535u ? 65535u / channels : 1u; }
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -276,6 +295,7 @@ hipError_t bf_launch_filter(const BfFilterArgs *a, hipStream_t s);
 hipError_t bf_launch_hilbert(const BfFilterArgs *a, hipStream_t s);
 hipError_t bf_launch_das(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_count(const BfDasArgs *a, hipStream_t s);
+hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s);   /* das_burst.hip: RCA family, `a` without a channel split */
 hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged_tables(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);

@@ -54,6 +54,7 @@ struct TimingSlot {
 	bool       created = false;
 	bool       sampled = true;       /* false: this frame recorded no events; events_slot names the slot whose events stand in */
 	uint32_t   events_slot = 0;
+	uint32_t   share = 1;            /* frames the events of events_slot cover: a frame of a burst reports 1 / share of each time (push_burst) */
 	uint64_t   das_voxels = 0;
 	uint32_t   das_taps = 0, das_sample_bytes = 0, das_path = 0;
 	bool       counted = false;
@@ -61,6 +62,14 @@ struct TimingSlot {
 	uint64_t   violations_slot = ~0ull;   /* staged kernels: index of this frame's window-violation counter, or ~0 */
 	uint32_t   das_row_end_planes = 0;    /* planes the row-end rule sent to the kernel behind the staged one */
 	bool       failed = false;            /* the push that owns this slot did not complete */
+};
+
+/* the newest burst (executor.cpp push_burst): what beamformer_hip_get_last_burst_info reports */
+struct BurstRecord {
+	bool          valid = false;
+	uint64_t      first_id = 0;
+	uint32_t      count = 0, events_slot = 0;
+	BurstDecision route;
 };
 
 struct PlanState {
@@ -106,6 +115,8 @@ struct Device {
 	bool         have_sample = false;
 	uint64_t     replan_frame = 0;                             /* first frame of the current plan */
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
+	DeviceBuffer burst_stage[2];                               /* push_burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
+	BurstRecord  burst;
 	DeviceBuffer hercules_pairs;                               /* das_hercules.hip: {sample, difference} copy of the DAS input (IQ, linear) */
 	DeviceBuffer staged_tables;        /* das_staged.hip, wave-uniform transmit tables (bf_launch_das_staged_tables) */
 	DeviceBuffer staged_violations;    /* das_staged*.hip: one counter per timing slot of window positions outside the staged window */
@@ -168,6 +179,8 @@ bool     set_error(BeamformerLibErrorKind kind);   /* records and returns false 
 bool ensure_device();                               /* SharedMemory error when no HIP device */
 uint64_t default_frame_ring_bytes();
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device);
+bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device);
+bool last_burst_info(BeamformerHipBurstInfo *out);
 bool wait_for_frames(int32_t timeout_ms);
 const FrameRecord *newest_record(const Device &d);     /* null: the newest push did not complete */
 bool export_last_frames(void *out, uint64_t out_size, uint32_t count, int32_t timeout_ms);

@@ -1,0 +1,234 @@
+/* das_burst.hip -- the general kernel (das.hip) for an ENSEMBLE: several RF frames of one geometry beamformed by one launch
+ * (beamformer_hip_push_data_burst_with_compute; the Flash / ULM use: hundreds of frames from one parameter block).
+ *
+ * das.hip spends most of its VALU slots per (voxel, channel, transmit) term on work that does not depend on the RF: the lateral
+ * distance, the f-number test, the square root, the sample index, its row-end settlement (settle_index, das_exact.h), the cos^2
+ * apodization, the tap address, the interpolation weights and the demodulation phasor.  Across an ensemble that work is the same
+ * for every frame.  Here a thread owns one voxel of BF_BURST_FRAMES_PER_THREAD frames: it walks das_rca's loops (transmit outer,
+ * channel inner -- the single kernel's summation order without its channel split) ONCE, computes the above once per term, and per
+ * frame only gathers, interpolates, rotates, weights and accumulates.  The gathers of all frames of a term are issued back to back
+ * before the first is consumed (one wait per term, not one per frame): frame f's DAS input lies at rf + f * rf_stride, so they are
+ * the same vector offset on FB wave-uniform bases.
+ *
+ * Grid: x = the general kernel's tiles (DasDecision::general: 256 voxels a block, no channel split -- the frames fill the chip
+ * instead), y = groups of FB frames; the last group may hold fewer (a wave-uniform count): its spare frames read the group's last
+ * frame again and store nothing, so the loops carry no per-frame branch.
+ *
+ * The per-frame arithmetic is sample_rf's (das_common.h) and Accumulator's (das_general.h), expression for expression, with the
+ * multiply-adds fused by hand and the same way in every frame slot (burst_term).  The ROUNDINGS therefore differ from das.hip's by
+ * design: there hipcc contracts as it sees fit, here the fusions are fixed, so a frame of a burst is within float rounding of its
+ * single push and not bit-identical to it (measured: none is) -- what is guaranteed instead is that its bits do not depend on its
+ * slot.  RCA family
+ * only (RCA_TPW, RCA_VLS, Flash): 3 interpolation modes x real / IQ x with / without coherency weighting = 12 instantiations.
+ * No LDS, no barrier, no MFMA: gather / VALU bound as das.hip is.
+ */
+#include "das_general.h"
+
+constexpr int FB = (int)BF_BURST_FRAMES_PER_THREAD;
+
+/* One in-aperture term of FB frames: sample_rf (das_common.h, das.glsl:99-124 + cubic :67-97) with everything that depends on the
+ * index alone -- range test, tap, weights, phasor -- taken once.  A term outside the valid range adds nothing (sample_rf gives +0). */
+template <int INTERP, bool CPLX, bool CW>
+__device__ __forceinline__ void burst_term(const char *const (&rf)[FB], int rf_offset, float index, float apodization, const BfDasArgs &p,
+                                           Accumulator<CPLX, CW, false> (&acc)[FB])
+{
+	/* The four frame slots must be the SAME arithmetic, so that a frame's bits do not depend on its place in the burst: left to itself
+	 * hipcc fuses the multiply-adds of the unrolled slots independently (it did: one ulp between slots, real samples with coherency
+	 * weighting).  Contraction is therefore off in here and every fused multiply-add is written out. */
+	#pragma clang fp contract(off)
+	constexpr uint32_t ES = CPLX ? 8 : 4;
+	const float S = (float)p.sample_count;
+	float c = 1.f, s = 0.f;
+	auto phasor = [&]() {                                   /* rotate_iq's, das.glsl:54-61 */
+		if constexpr (CPLX) {
+			float turns = hw_fract(index * p.turns_per_sample);
+			c = hw_cos_turns(turns); s = hw_sin_turns(turns);
+		}
+	};
+	/* rotate, weight, RESULT_STORE (das.glsl:28-32) */
+	auto add = [&](int f, sample_t<CPLX> v) {
+		#pragma clang fp contract(off)
+		if constexpr (CPLX) {
+			v = f32x2{__builtin_fmaf(c, v.x, -(s * v.y)), __builtin_fmaf(s, v.x, c * v.y)};
+			if constexpr (CW) {
+				const f32x2 w = apodization * v;
+				acc[f].coherent += w;
+				acc[f].incoherent += hw_sqrt(__builtin_fmaf(w.x, w.x, w.y * w.y));
+			} else {
+				acc[f].coherent = f32x2{__builtin_fmaf(apodization, v.x, acc[f].coherent.x), __builtin_fmaf(apodization, v.y, acc[f].coherent.y)};
+			}
+		} else {
+			if constexpr (CW) {
+				const float w = apodization * v;
+				acc[f].coherent += w;
+				acc[f].incoherent += __builtin_fabsf(w);
+			} else {
+				acc[f].coherent = __builtin_fmaf(apodization, v, acc[f].coherent);
+			}
+		}
+	};
+	auto fma2 = [](float a, f32x2 b, f32x2 c2) { return f32x2{__builtin_fmaf(a, b.x, c2.x), __builtin_fmaf(a, b.y, c2.y)}; };
+	if constexpr (INTERP == BF_INTERP_NEAREST) {
+		if (index >= 0.f && index < S - 0.5f) {
+			int k = (int)__builtin_roundf(index);
+			const uint32_t off = (uint32_t)(rf_offset + k) * ES;
+			phasor();
+			sample_t<CPLX> v[FB];
+			for (int f = 0; f < FB; f++) v[f] = gather<sample_t<CPLX>>(rf[f], off);
+			for (int f = 0; f < FB; f++) add(f, v[f]);
+		}
+	} else if constexpr (INTERP == BF_INTERP_LINEAR) {
+		uint32_t k = (uint32_t)cvt_floor_i32(index);
+		if (k < (uint32_t)(p.sample_count - 1)) {
+			float t = hw_fract(index);
+			const uint32_t off = ((uint32_t)rf_offset + k) * ES;
+			phasor();
+			if constexpr (CPLX) {
+				f32x4 v[FB];
+				for (int f = 0; f < FB; f++) v[f] = gather<f32x4_a8>(rf[f], off);
+				for (int f = 0; f < FB; f++) {
+					f32x2 a = {v[f].x, v[f].y}, b = {v[f].z, v[f].w};
+					add(f, fma2(t, b - a, a));
+				}
+			} else {
+				f32x2 v[FB];
+				for (int f = 0; f < FB; f++) v[f] = gather<f32x2_a4>(rf[f], off);
+				for (int f = 0; f < FB; f++) add(f, __builtin_fmaf(t, v[f].y - v[f].x, v[f].x));
+			}
+		}
+	} else {
+		uint32_t k = (uint32_t)(cvt_floor_i32(index) - 1);
+		if (k < (uint32_t)(p.sample_count - 3)) {
+			float t = hw_fract(index);
+			const uint32_t off = ((uint32_t)rf_offset + k) * ES;
+			float t2 = t * t, t3 = t2 * t;
+			/* Hermite basis with tangents 0.5 (P2 - P0), 0.5 (P3 - P1) */
+			float b0 =  2.f * t3 - 3.f * t2 + 1.f;
+			float b1 = -2.f * t3 + 3.f * t2;
+			float b2 =        t3 - 2.f * t2 + t;
+			float b3 =        t3 -       t2;
+			phasor();
+			if constexpr (CPLX) {
+				f32x4 lo[FB], hi[FB];
+				for (int f = 0; f < FB; f++) { lo[f] = gather<f32x4_a8>(rf[f], off); hi[f] = gather<f32x4_a8>(rf[f], off + 16); }
+				for (int f = 0; f < FB; f++) {
+					f32x2 s0 = {lo[f].x, lo[f].y}, s1 = {lo[f].z, lo[f].w}, s2 = {hi[f].x, hi[f].y}, s3 = {hi[f].z, hi[f].w};
+					f32x2 T1 = 0.5f * (s2 - s0), T2 = 0.5f * (s3 - s1);
+					add(f, fma2(b3, T2, fma2(b2, T1, fma2(b1, s2, b0 * s1))));
+				}
+			} else {
+				f32x4 v[FB];
+				for (int f = 0; f < FB; f++) v[f] = gather<f32x4_a4>(rf[f], off);
+				for (int f = 0; f < FB; f++) {
+					float T1 = 0.5f * (v[f].z - v[f].x), T2 = 0.5f * (v[f].w - v[f].y);
+					add(f, __builtin_fmaf(b3, T2, __builtin_fmaf(b2, T1, __builtin_fmaf(b1, v[f].z, b0 * v[f].y))));
+				}
+			}
+		}
+	}
+}
+
+/* das.glsl:368-407 + :204-231 (das_rca) over FB frames. */
+template <int INTERP, bool CPLX, bool CW>
+__global__ __launch_bounds__(256) void das_burst_kernel(const BfDasArgs p, const BfBurstArgs q)
+{
+	const GeneralTile tile = general_tile(p, blockIdx.x);
+	if (!tile.valid) return;
+	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
+
+	uint32_t tid = threadIdx.x;
+	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
+	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
+	uint32_t lz  = (tid >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u);
+	uint32_t x = (bx << p.tile_shift[0]) + lx;
+	uint32_t y = (by << p.tile_shift[1]) + ly;
+	uint32_t zl = (bz << p.tile_shift[2]) + lz;       /* z inside the shard */
+	if (!(x < p.size[0] && y < p.size[1] && zl < p.z_count)) return;
+
+	/* this block's frames: first .. first + count - 1; the spare slots of a short last group alias its last frame */
+	const uint32_t first = blockIdx.y * (uint32_t)FB;
+	const uint32_t count = q.frame_count - first < (uint32_t)FB ? q.frame_count - first : (uint32_t)FB;
+	const char *rf[FB];
+	for (int f = 0; f < FB; f++) {
+		const uint32_t frame = first + ((uint32_t)f < count ? (uint32_t)f : count - 1u);
+		rf[f] = (const char *)p.rf + (uint64_t)frame * q.rf_stride;
+	}
+	Accumulator<CPLX, CW, false> acc[FB];
+	for (int f = 0; f < FB; f++) acc[f].init();
+
+	uint32_t z = p.z_first + zl;
+	/* das.glsl:374-376 */
+	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
+	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
+	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
+	float wx, wy, wz;
+	m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+
+	/* das.glsl:204-231 */
+	float xx, xy, xz;
+	m4_point(p.xdc_transform, wx, wy, wz, xx, xy, xz);
+	const int S = p.sample_count, A = p.acquisition_count, C = p.channel_count;
+	const float inv_abs_z = hw_rcp(__builtin_fabsf(xz));
+	const float zz = xz * xz;
+
+	for (int acquisition = 0; acquisition < A; acquisition++) {
+		const BfTransmit t = p.transmits[acquisition];
+		const bool  rx_rows = (t.flags & BF_RX_ROWS) != 0;
+		const float lateral = rx_rows ? xy : xx;
+		const float pitch   = rx_rows ? p.pitch[1] : p.pitch[0];
+		const float tx_dist = transmit_distance(t, wx, wy, wz);
+		const float f_over_z = p.f_number * inv_abs_z;
+
+		int rf_offset = acquisition * S;
+		for (int channel = 0; channel < C; channel++) {
+			float dx    = lateral - (float)channel * pitch;
+			float a_arg = __builtin_fabsf(dx * f_over_z);
+			if (a_arg < 0.5f) {
+				float sidx = sample_index(tx_dist + hw_sqrt(dx * dx + zz), p);
+				sidx = settle_index<BF_DAS_RCA, INTERP>(sidx, p, x, y, z, channel, acquisition);
+				burst_term<INTERP, CPLX, CW>(rf, rf_offset, sidx, apodize(a_arg), p, acc);
+			}
+			rf_offset += S * A;
+		}
+	}
+
+	const uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
+	for (int f = 0; f < FB; f++) {
+		if ((uint32_t)f < count) {
+			sample_t<CPLX> v = acc[f].coherent;
+			/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949), as das.hip's epilogue */
+			if constexpr (CW) v = v * (v / acc[f].incoherent);
+			reinterpret_cast<sample_t<CPLX> *>((char *)p.out + (uint64_t)(first + (uint32_t)f) * q.out_stride)[out_index] = v;
+		}
+	}
+}
+
+template <int INTERP, bool CPLX, bool CW>
+static hipError_t launch_one(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s)
+{
+	uint32_t total = a->blocks[0] * a->blocks[1] * a->blocks[2];
+	uint32_t grid  = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
+	uint32_t groups = (b->frame_count + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
+	hipLaunchKernelGGL((das_burst_kernel<INTERP, CPLX, CW>), dim3(grid, groups), dim3(256), 0, s, *a, *b);
+	return hipGetLastError();
+}
+
+template <int INTERP>
+static hipError_t launch_kind(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s)
+{
+	if (a->complex_data) return a->coherency_weighting ? launch_one<INTERP, true,  true>(a, b, s) : launch_one<INTERP, true,  false>(a, b, s);
+	else                 return a->coherency_weighting ? launch_one<INTERP, false, true>(a, b, s) : launch_one<INTERP, false, false>(a, b, s);
+}
+
+/* `a`: the general kernel's arguments without a channel split (DasDecision::general), rf / out those of the burst's first frame. */
+extern "C" hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s)
+{
+	const uint32_t groups = (b->frame_count + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
+	if (a->family != BF_DAS_RCA || a->split_shift || b->frame_count == 0 || groups > 65535u) return hipErrorInvalidValue;
+	switch (a->interpolation) {
+	case BF_INTERP_NEAREST: return launch_kind<BF_INTERP_NEAREST>(a, b, s);
+	case BF_INTERP_LINEAR:  return launch_kind<BF_INTERP_LINEAR>(a, b, s);
+	case BF_INTERP_CUBIC:   return launch_kind<BF_INTERP_CUBIC>(a, b, s);
+	}
+	return hipErrorInvalidValue;
+}

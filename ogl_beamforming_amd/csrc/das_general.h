@@ -1,0 +1,101 @@
+/* das_general.h -- what the general kernel (das.hip) and its ensemble form (das_burst.hip) share: the transmit distance, the sample
+ * index, the row-end settlement of an index and the walk from a block id to a voxel tile.  One text, so that a frame of a burst is
+ * the same arithmetic as a single frame. */
+#ifndef BF_DAS_GENERAL_H
+#define BF_DAS_GENERAL_H
+
+#include "das_exact.h"
+
+template <bool CPLX, bool CW, bool COUNT>
+struct Accumulator {
+	sample_t<CPLX> coherent;
+	float          incoherent;
+	unsigned long long pairs;
+	__device__ __forceinline__ void init() { coherent = zero_sample<CPLX>(); incoherent = 0.f; pairs = 0; }
+	/* RESULT_STORE (das.glsl:28-32) */
+	__device__ __forceinline__ void add(sample_t<CPLX> v)
+	{
+		coherent += v;
+		if constexpr (CW) {
+			if constexpr (CPLX) incoherent += hw_sqrt(v.x * v.x + v.y * v.y);
+			else                incoherent += __builtin_fabsf(v);
+		}
+	}
+};
+
+/* das.glsl:187-202 with the per-transmit constants precomputed */
+__device__ __forceinline__ float transmit_distance(const BfTransmit &t, float wx, float wy, float wz)
+{
+	float result = 0.f;
+	if (!(t.flags & BF_TX_NONE)) {
+		float px = (t.flags & BF_TX_ROWS) ? wy : wx;
+		if (t.flags & BF_TX_PLANE) {
+			result = px * t.sin_a + wz * t.cos_a;
+		} else {
+			float dx = px - t.focus_x, dz = wz - t.focus_z;
+			result = hw_sqrt(dx * dx + dz * dz);
+		}
+	}
+	return result;
+}
+
+/* das.glsl:126-130 */
+__device__ __forceinline__ float sample_index(float distance, const BfDasArgs &p)
+{
+	return (div_speed_of_sound(distance, p) + p.time_offset) * p.sampling_frequency;
+}
+
+/* A term at an end of its RF row (das_exact.h): this kernel's index -- hardware square root, fused multiply-adds -- may differ
+ * from the shader's by an ulp, and sample_rf's range test is a step.  Within p.edge_margin of either end the index is therefore
+ * formed again, exactly as the shader's text forms it; everything else about the term stays as it is.  (Nearest interpolation:
+ * the index decides the tap at every half-integer, not only at the row ends -- the parity tests budget those flips per voxel.) */
+template <int FAMILY, int INTERP>
+__device__ __forceinline__ float settle_index(float index, const BfDasArgs &p, uint32_t x, uint32_t y, uint32_t z, int channel, int transmit)
+{
+	if constexpr (INTERP != BF_INTERP_NEAREST) {
+		if (bfx::edge_near<INTERP>(index, p.sample_count, p.edge_margin))
+			index = bfx::exact_index<FAMILY>(p, bfx::exact_voxel<FAMILY>(p, x, y, z), channel, transmit);
+	}
+	return index;
+}
+
+/* Block id -> tile (bx, by, bz) of the general kernel's grid; valid false: a block of the ragged tail, which has no tile. */
+struct GeneralTile { uint32_t bx, by, bz; bool valid; };
+__device__ __forceinline__ GeneralTile general_tile(const BfDasArgs &p, uint32_t bid)
+{
+	uint32_t bx = 0, by = 0, bz = 0;
+	/* blockIdx -> tile: consecutive block ids go round-robin over the 8 XCDs, so ids that
+	 * share (id % 8) share an L2.  Deal the tile list out so that each XCD walks a
+	 * contiguous run of tiles (neighbouring tiles read neighbouring RF windows). */
+	uint32_t total  = p.blocks[0] * p.blocks[1] * p.blocks[2];
+	uint32_t per    = (total + 7u) / 8u;
+	uint32_t tile   = (bid & 7u) * per + (bid >> 3);
+	if (p.depth_major != 3u && tile >= total) {
+		/* ragged tail: ids whose run is shorter map onto the unassigned remainder */
+		return GeneralTile{0, 0, 0, false};
+	}
+	/* depth-major walk: consecutive tiles (in flight together on an XCD) are one lateral column at
+	 * consecutive depths, whose RF windows overlap almost entirely (das_separable.hip) */
+	if (p.depth_major == 3u) {
+		bz = 0;
+		if (!bf_plane_walk(bid, p.blocks[0], p.blocks[1], p.band_rows, bx, by)) return GeneralTile{0, 0, 0, false};     /* whole block */
+	} else if (p.depth_major == 2u) {
+		/* view planes (depth on voxel y, one voxel along z): y fastest, so that each XCD's run of tiles is a lateral COLUMN
+		 * at every depth -- the work per tile grows with depth (f-number culling), a run of depth ROWS would leave the XCDs
+		 * that hold the shallow rows idle for a fifth of the launch */
+		by = tile % p.blocks[1];
+		bx = (tile / p.blocks[1]) % p.blocks[0];
+		bz = tile / (p.blocks[1] * p.blocks[0]);
+	} else if (p.depth_major) {
+		bz = tile % p.blocks[2];
+		bx = (tile / p.blocks[2]) % p.blocks[0];
+		by = tile / (p.blocks[2] * p.blocks[0]);
+	} else {
+		bx = tile % p.blocks[0];
+		by = (tile / p.blocks[0]) % p.blocks[1];
+		bz = tile / (p.blocks[0] * p.blocks[1]);
+	}
+	return GeneralTile{bx, by, bz, true};
+}
+
+#endif

@@ -969,6 +969,50 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 	parts.swap(cut);
 }
 
+void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const std::vector<DasDecision> &parts,
+                  uint32_t zfirst, uint32_t zcount, uint32_t mode, uint32_t frame_count, BurstDecision &out)
+{
+	out = BurstDecision{};
+	const DasDecision &head = main_part(parts);
+	out.single_path = head.path;
+	/* the ingest and every pre-DAS stage take the burst in one launch; the filters share a grid axis with the channels and take it in
+	 * chunks of bf_stage_frame_chunk frames (stages.hip) */
+	const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
+	out.stage_launches = (frame_count + chunk - 1) / chunk;
+	uint32_t launches = 0;
+	for (const DasDecision &d : parts) launches += d.path != DasPath_Zero;
+	out.das_launches = launches * frame_count;
+	char text[160];
+	if (plan.das_index < 0 || zcount == 0) {
+		out.reason = "no DAS stage runs: the frames are cleared";
+	} else if (head.path == DasPath_Zero) {
+		out.reason = "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared";
+	} else if (mode & 0x400u) {
+		out.reason = "das path flag 0x400: the single-frame kernel once per frame was asked for";
+	} else if (head.a.family != BF_DAS_RCA) {
+		out.reason = "the burst kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per frame";
+	} else if (parts.size() != 1) {
+		out.reason = "the row-end rule cuts the frame into parts run by different kernels: the single-frame launches once per frame";
+	} else if (head.path != DasPath_General) {
+		std::snprintf(text, sizeof(text), "single frames run the %s, which already shares the geometry across its loops: it runs once per frame", das_path_name(head.path));
+		out.reason = text;
+	} else if (frame_count < kBurstMinFrames) {
+		std::snprintf(text, sizeof(text), "fewer than %u frames: the single-frame general kernel", kBurstMinFrames);
+		out.reason = text;
+	} else {
+		/* the general kernel's tiles at one thread per voxel: the frames fill the chip, not a channel split */
+		DasDecision whole;
+		decide_das(pb, plan, tx, zfirst, zcount, mode | 0x10u, whole);
+		out.a = whole.general;
+		out.a.row_ends = head.general.row_ends;
+		out.burst_kernel = true;
+		out.frames_per_thread = BF_BURST_FRAMES_PER_THREAD;
+		out.das_launches = 1;
+		std::snprintf(text, sizeof(text), "RCA family on the general kernel: one launch, each thread applies a term's geometry to %u frames", BF_BURST_FRAMES_PER_THREAD);
+		out.reason = text;
+	}
+}
+
 uint32_t row_end_planes(const std::vector<DasDecision> &parts)
 {
 	uint32_t n = 0;

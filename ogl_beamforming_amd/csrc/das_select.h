@@ -25,6 +25,14 @@ constexpr uint32_t kStagedMinTransmits = 6;      /* das_staged.hip by default fr
                                                     profiles/r03_staged_threshold.json: 1.29 of the gather kernel's time at 4 transmits, 1.01 at 6,
                                                     1.0 at 8, 0.88 at 12, 0.75 at 16, 0.69-0.71 at 32-75; round 2's pass: 1.15, -, 0.91, 0.84, 0.75) */
 
+constexpr uint32_t kBurstMinFrames = 5;          /* das_burst.hip takes bursts of this many frames and more.  Wall time per frame of one burst on the
+                                                    burst kernel over N single pushes, upload included (tools/burst_rate.py, profiles/burst_rate.json),
+                                                    by N -- config 1 (64 ch, 1 tx, 256 x 256): 2: 1.16, 4: 0.88, 8: 0.71, 16: 0.53, 64: 0.51, 256: 0.33;
+                                                    the same plane with 2 transmits: 2: 1.37, 4: 1.02, 8: 0.78, 16: 0.60, 64: 0.75, 256: 0.54.  Two
+                                                    frames are one group of four slots, half of them aliased, on a quarter of the waves the single
+                                                    kernel's channel split launches: slower; four are level; from five on the burst is taken (the
+                                                    per-frame DAS route under the same batching: 1.04 / 1.24 at 2, 1.00 / 1.08 at 4, 0.95 / 1.00 at 8) */
+
 /* Diagnostic switches (none is needed in production, all default off): set through beamformer_hip_set_hook ONLY -- the library
  * reads no environment variable.  They select among code paths that ship anyway (the range-checked loop every boundary wave takes,
  * the LDS-table form every non-64 x 16 tile takes, ...) so that the tests can aim at each of them.  `version` counts changes:
@@ -84,6 +92,20 @@ void decide_das(const ParameterBlock &pb, const Plan &plan, const std::vector<Bf
  * row-end terms exactly).  Parts are contiguous, in z order, and cover [z_first, z_first + z_count). */
 void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits,
                       uint32_t z_first, uint32_t z_count, uint32_t mode, std::vector<DasDecision> &parts);
+/* How a burst of frame_count frames runs (beamformer_hip_describe_burst): das_burst.hip in one launch when the single-frame decision
+ * `parts` is ONE part on the general kernel, the family is RCA, frame_count >= kBurstMinFrames and mode does not carry
+ * BeamformerHipDasPath_NoBurstKernel; else the single-frame launch(es) once per frame.  `a`: the burst kernel's arguments (the general
+ * kernel's tiles without the channel split). */
+struct BurstDecision {
+	bool        burst_kernel = false;
+	int         single_path = DasPath_General;
+	uint32_t    frames_per_thread = 1, das_launches = 0, stage_launches = 0;
+	std::string reason;
+	BfDasArgs   a{};
+};
+void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const std::vector<DasDecision> &parts,
+                  uint32_t z_first, uint32_t z_count, uint32_t mode, uint32_t frame_count, BurstDecision &out);
+
 /* planes of `parts` that took the fallback */
 uint32_t row_end_planes(const std::vector<DasDecision> &parts);
 /* the part with the most planes (what a frame "ran on" in one word) */

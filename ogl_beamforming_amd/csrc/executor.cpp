@@ -179,7 +179,7 @@ static void release_one_device(Device &d)
 	for (auto &b : d.rf) b.release();
 	for (auto &b : d.scratch) b.release();
 	d.ring.release(); d.pair_counter.release(); d.minmax_scratch.release(); d.sum_scratch.release();
-	d.hercules_table.release(); d.hercules_pairs.release(); d.staged_tables.release(); d.staged_violations.release();
+	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.burst = BurstRecord{}; d.staged_tables.release(); d.staged_violations.release();
 	for (auto &g : d.frame_exec) { if (g) (void)hipGraphExecDestroy(g); g = nullptr; }
 	for (auto &g : d.graph_generation) g = 0;
 	for (auto &t : d.timing) {
@@ -316,6 +316,24 @@ static FrameRecord *next_frame(const uint32_t points[3], bool complex_frame, uin
 	return f;
 }
 
+/* `count` frames of one size, contiguous in the ring: a run that would straddle the end starts again at offset 0; the records it
+ * overwrites stop being exportable, as in next_frame.  Returns the first, or null when the run does not fit the ring. */
+static FrameRecord *next_burst_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count)
+{
+	Device &d = *g_context.cur;
+	const uint64_t bytes = round_up((uint64_t)points[0] * points[1] * points[2] * (complex_frame ? 8u : 4u), 64);
+	if (count == 0 || bytes > d.ring.size / count) return nullptr;
+	if (d.ring_next_offset > d.ring.size - bytes * count) d.ring_next_offset = 0;
+	FrameRecord *first = nullptr;
+	for (uint32_t k = 0; k < count; k++) {
+		FrameRecord *f = next_frame(points, complex_frame, block);
+		if (!f) return nullptr;
+		f->timing_slot = (int)(f->id % kTimingSlots);
+		if (k == 0) first = f;
+	}
+	return first;
+}
+
 /* A timed HIP event costs ~4 us of stream time on this runtime (measured: a 0.26 MB / 256 x 256
  * frame takes 36.5 us with its five records and 15.7 us without), nothing next to a 3-D volume
  * and more than the kernels of a real-time 2-D frame.  Small frames therefore record their
@@ -331,6 +349,184 @@ static bool record(TimingSlot &t, uint32_t index, hipStream_t s)
 }
 
 static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, bool ingest_timed);
+
+/* One pre-DAS stage: stage i of the plan reads `cur` (cur_elements_bytes: what may be read there, per frame) and writes `out`.  A burst
+ * passes its frame count and the byte strides from frame to frame of input and output: one launch (the filters: one per chunk of frames
+ * that fits the grid, stages.hip), each frame addressed and bounded as a single frame is. */
+static bool launch_stage(PlanState *ps, const BeamformerParameters &bp, size_t i, const void *cur, int64_t cur_elements_bytes, void *out, hipStream_t s,
+                         uint32_t frames = 1, uint64_t in_frame_bytes = 0, uint64_t out_frame_bytes = 0)
+{
+	Context &c = g_context;
+	const Plan &plan = ps->plan;
+	const Stage &st = plan.stages[i];
+	const uint32_t C = plan.channels, A = plan.acquisitions, Sd = plan.das_samples;
+	bool ok = true;
+	switch (st.kind) {
+	case BeamformerShaderKind_Reshape:{
+		BfReshapeArgs a{};
+		a.size[0] = Sd; a.size[1] = C; a.size[2] = A;                          /* beamformer_core.c:975-977 */
+		for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
+		a.in_kind = st.in_kind; a.out_kind = st.out_kind;
+		a.interleave = !bf_kind_complex[st.in_kind] && bf_kind_complex[st.out_kind];
+		a.left  = cur;
+		a.right = (const char *)cur + (size_t)Sd * C * A * (size_t)bf_kind_byte_size[st.in_kind];   /* :1384-1385 */
+		a.out = out;
+		a.frames = frames; a.in_frame_bytes = in_frame_bytes; a.out_frame_bytes = out_frame_bytes;
+		ok = HIP_OK(bf_launch_reshape(&a, s));
+	}break;
+	case BeamformerShaderKind_Decode:{
+		BfDecodeArgs a{};
+		a.in = cur; a.out = out;
+		a.hadamard_t = (const float *)ps->hadamard_t.ptr;
+		a.hadamard_base_order = (c.das_path_mode & 0x20) ? 0 : plan.hadamard_base_order;
+		a.hadamard_base = a.hadamard_base_order ? (const float *)ps->hadamard_base.ptr : nullptr;
+		a.transmit_count = A; a.channel_count = C; a.sample_count = Sd;
+		for (int k = 0; k < 3; k++) a.out_stride[k] = st.out_stride[k];
+		a.in_kind = st.in_kind; a.out_kind = st.out_kind;
+		a.frames = frames; a.in_frame_bytes = in_frame_bytes; a.out_frame_bytes = out_frame_bytes;
+		ok = HIP_OK(bf_launch_decode(&a, s));
+	}break;
+	case BeamformerShaderKind_Hilbert:{
+		BfFilterArgs a{};
+		a.in = cur; a.out = out;
+		a.coefficients  = (const float *)ps->taps[i].ptr;
+		a.filter_length = (uint32_t)st.filter.length;
+		a.sample_count  = Sd;
+		for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
+		a.in_elements = cur_elements_bytes / bf_kind_byte_size[st.in_kind];
+		a.channels = C; a.transmits = A;
+		a.in_kind = st.in_kind; a.out_kind = st.out_kind;
+		a.frames = frames; a.in_frame_bytes = in_frame_bytes; a.out_frame_bytes = out_frame_bytes;
+		ok = HIP_OK(bf_launch_hilbert(&a, s));
+	}break;
+	case BeamformerShaderKind_Filter:
+	case BeamformerShaderKind_Demodulate:{
+		bool demod = st.kind == BeamformerShaderKind_Demodulate;
+		BfFilterArgs a{};
+		a.in = cur; a.out = out;
+		a.coefficients   = (const float *)ps->taps[i].ptr;
+		a.phasors        = demod ? a.coefficients + st.filter.taps.size() : nullptr;
+		a.filter_length  = (uint32_t)st.filter.length;
+		a.complex_filter = st.filter.complex_taps;
+		a.demodulate     = demod;
+		a.decimation     = demod ? plan.decimation : 1;                          /* :846 */
+		a.sample_count   = Sd;                                                  /* :845 */
+		bool deinterleave = bf_kind_complex[st.in_kind] && !bf_kind_complex[st.out_kind];
+		a.batch_sample_count = deinterleave ? C * Sd * A : 0;                   /* :848-851 */
+		if (demod) {                                                            /* :870-873 */
+			a.demodulation_frequency = bp.demodulation_frequency;
+			a.sampling_frequency     = bp.sampling_frequency / 2;
+		}
+		for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
+		a.in_elements = cur_elements_bytes / bf_kind_byte_size[st.in_kind];
+		a.channels = C; a.transmits = A;
+		a.in_kind = st.in_kind; a.out_kind = st.out_kind;
+		a.frames = frames; a.in_frame_bytes = in_frame_bytes; a.out_frame_bytes = out_frame_bytes;
+		ok = HIP_OK(bf_launch_filter(&a, s));
+	}break;
+	default: break;
+	}
+	return ok;
+}
+
+
+/* The DAS decision(s) of a plan's frames over planes [zfirst, zfirst + zcount): computed once per plan / shard / path mode / hook change
+ * (das_select.cpp) and reused by every frame after it. */
+static std::vector<DasDecision> &frame_das_parts(PlanState *ps, const ParameterBlock &pb, uint32_t zfirst, uint32_t zcount)
+{
+	Context &c = g_context;
+	std::vector<DasDecision> &parts = ps->das_parts;
+	if (parts.empty() || !parts[0].valid || parts[0].generation != ps->generation || ps->das_z_first != zfirst || ps->das_z_count != zcount ||
+	    parts[0].mode_asked != c.das_path_mode || parts[0].hooks_version != hooks().version) {
+		decide_das_parts(pb, ps->plan, ps->transmit_table, zfirst, zcount, c.das_path_mode, parts);
+		for (DasDecision &dd : parts) { dd.generation = ps->generation; dd.mode_asked = c.das_path_mode; }
+		ps->das_z_first = zfirst; ps->das_z_count = zcount;
+	}
+	return parts;
+}
+
+/* One part of one frame's DAS stage (das_select.h: a frame is one part unless the row-end rule cut it): the kernel `dd` names on the DAS
+ * input `cur`, writing the part's planes at `out`.  part_path: the kernel that ran where a missing buffer sent the part to another one. */
+static bool launch_das_part(PlanState *ps, const DasDecision &dd, const void *cur, void *out, uint64_t out_bytes, uint32_t *frame_counters,
+                            hipStream_t s, uint32_t &part_path)
+{
+	Device &d = *g_context.cur;
+	bool ok = true;
+	BfDasArgs a = dd.a;
+	a.rf  = cur;
+	a.out = out;
+	a.transmits       = (const BfTransmit *)ps->transmits.ptr;
+	a.sparse_elements = (const int16_t *)ps->sparse.ptr;
+	a.readi_hadamard  = (const uint16_t *)ps->readi_hadamard.ptr;
+
+	if (dd.path == DasPath_Zero) {
+		ok &= HIP_OK(hipMemsetAsync(a.out, 0, out_bytes, s));
+	} else {
+		/* 64 zero bytes right behind the DAS input (every buffer it can live in is allocated with that much slack): the
+		 * gather target of out-of-range lanes */
+		const uint64_t used = dd.das_input_bytes;
+		if (dd.path != DasPath_General) ok &= HIP_OK(hipMemsetAsync((char *)const_cast<void *>(cur) + used, 0, 64, s));
+		switch (dd.path) {
+		case DasPath_Staged:
+		case DasPath_Gather:{
+			BfSeparableArgs sep = dd.sep;
+			bool staged = dd.path == DasPath_Staged;
+			if (staged && sep.uniform) {
+				/* the wave-uniform transmit tables live in global memory: one slice per (lateral tile row, plane), written per frame;
+				 * no memory: the shape with the tables in LDS, else the gather kernel with its own geometry */
+				const uint64_t table_bytes = (uint64_t)sep.table_stride * sep.tiles[1] * sep.tiles[2];
+				if (d.staged_tables.ensure(table_bytes)) {
+					sep.tables = d.staged_tables.ptr;
+					ok &= HIP_OK(bf_launch_das_staged_tables(&a, &sep, s));
+				} else if (dd.has_lds_tables) {
+					sep = dd.sep_lds_tables;
+				} else {
+					sep = dd.sep_gather; staged = false;
+				}
+			}
+			if (staged) {
+				/* window positions outside the staged window are counted (range-checked loop only: STAGED_CHECKED) */
+				sep.violations = frame_counters;
+				ok &= HIP_OK(!ps->plan.iq_pipeline ? bf_launch_das_staged_real(&a, &sep, s) :
+				             a.interpolation == 2 ? bf_launch_das_staged_cubic(&a, &sep, s) : bf_launch_das_staged(&a, &sep, s));
+				part_path = DasPath_Staged;
+			} else {
+				ok &= HIP_OK(bf_launch_das_separable(&a, &sep, s));
+				part_path = DasPath_Gather;
+			}
+		}break;
+		case DasPath_Hercules:{
+			BfHerculesArgs hq = dd.herc;
+			if (d.hercules_table.ensure(((size_t)hq.table_pitch + 2) * a.size[1] * sizeof(float))) {
+				hq.pairs = nullptr;
+				const uint64_t prepared = used * (a.interpolation == 2 ? 4u : 2u);      /* cubic: four coefficients per sample, 32 bytes */
+				if (dd.hercules_prepared && d.hercules_pairs.ensure(prepared + 64)) {
+					hq.pairs = d.hercules_pairs.ptr;
+					hq.zero_offset = (uint32_t)prepared;
+				}
+				hq.table    = (float *)d.hercules_table.ptr;
+				hq.extremes = hq.table + (size_t)hq.table_pitch * a.size[1];
+				ok &= HIP_OK(bf_launch_das_hercules(&a, &hq, s));
+			} else {
+				ok &= HIP_OK(bf_launch_das(&a, s));                                     /* no memory for the row table: the general kernel */
+				part_path = DasPath_General;
+			}
+		}break;
+		case DasPath_Factored:
+			ok &= HIP_OK(bf_launch_das_factored(&a, s));
+			break;
+		case DasPath_Tile:
+			/* (block, channel chunk) pairs served from staged windows, and those the kernel sent through its gather loop: words 1, 2 */
+			a.tile_counters = frame_counters ? frame_counters + 1 : nullptr;
+			ok &= HIP_OK(bf_launch_das_tile(&a, s));
+			break;
+		default:
+			ok &= HIP_OK(bf_launch_das(&a, s));
+			break;
+		}
+	}
+	return ok;
+}
 
 /* One frame.  With frame graphs on (beamformer_hip_enable_frame_graphs; BASELINE.json configs[4]: "hipGraph-
  * captured frame"; the reference's analogue is the one command list it records per frame,
@@ -404,7 +600,7 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 	hipStream_t s = d.stream;
 
 	TimingSlot &t = d.timing[d.frame_counter % kTimingSlots];
-	t.failed = false;
+	t.failed = false; t.share = 1;
 	if (!t.created) {
 		for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
 		t.created = true;
@@ -440,68 +636,14 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 	for (size_t i = 0; i < plan.stages.size() && ok; i++) {
 		const Stage &st = plan.stages[i];
 		switch (st.kind) {
-		case BeamformerShaderKind_Reshape:{
-			BfReshapeArgs a{};
-			a.size[0] = Sd; a.size[1] = C; a.size[2] = A;                          /* beamformer_core.c:975-977 */
-			for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
-			a.in_kind = st.in_kind; a.out_kind = st.out_kind;
-			a.interleave = !bf_kind_complex[st.in_kind] && bf_kind_complex[st.out_kind];
-			a.left  = cur;
-			a.right = (const char *)cur + (size_t)Sd * C * A * (size_t)bf_kind_byte_size[st.in_kind];   /* :1384-1385 */
-			a.out = d.scratch[toggle].ptr;
-			ok &= HIP_OK(bf_launch_reshape(&a, s));
-			cur = a.out; cur_elements_bytes = (int64_t)d.scratch[toggle].size; toggle ^= 1;
-		}break;
-		case BeamformerShaderKind_Decode:{
-			BfDecodeArgs a{};
-			a.in = cur; a.out = d.scratch[toggle].ptr;
-			a.hadamard_t = (const float *)ps->hadamard_t.ptr;
-			a.hadamard_base_order = (c.das_path_mode & 0x20) ? 0 : plan.hadamard_base_order;
-			a.hadamard_base = a.hadamard_base_order ? (const float *)ps->hadamard_base.ptr : nullptr;
-			a.transmit_count = A; a.channel_count = C; a.sample_count = Sd;
-			for (int k = 0; k < 3; k++) a.out_stride[k] = st.out_stride[k];
-			a.in_kind = st.in_kind; a.out_kind = st.out_kind;
-			ok &= HIP_OK(bf_launch_decode(&a, s));
-			cur = a.out; cur_elements_bytes = (int64_t)d.scratch[toggle].size; toggle ^= 1;
-		}break;
-		case BeamformerShaderKind_Hilbert:{
-			BfFilterArgs a{};
-			a.in = cur; a.out = d.scratch[toggle].ptr;
-			a.coefficients  = (const float *)ps->taps[i].ptr;
-			a.filter_length = (uint32_t)st.filter.length;
-			a.sample_count  = Sd;
-			for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
-			a.in_elements = cur_elements_bytes / bf_kind_byte_size[st.in_kind];
-			a.channels = C; a.transmits = A;
-			a.in_kind = st.in_kind; a.out_kind = st.out_kind;
-			ok &= HIP_OK(bf_launch_hilbert(&a, s));
-			cur = a.out; cur_elements_bytes = (int64_t)d.scratch[toggle].size; toggle ^= 1;
-		}break;
+		case BeamformerShaderKind_Reshape:
+		case BeamformerShaderKind_Decode:
+		case BeamformerShaderKind_Hilbert:
 		case BeamformerShaderKind_Filter:
-		case BeamformerShaderKind_Demodulate:{
-			bool demod = st.kind == BeamformerShaderKind_Demodulate;
-			BfFilterArgs a{};
-			a.in = cur; a.out = d.scratch[toggle].ptr;
-			a.coefficients   = (const float *)ps->taps[i].ptr;
-			a.phasors        = demod ? a.coefficients + st.filter.taps.size() : nullptr;
-			a.filter_length  = (uint32_t)st.filter.length;
-			a.complex_filter = st.filter.complex_taps;
-			a.demodulate     = demod;
-			a.decimation     = demod ? plan.decimation : 1;                          /* :846 */
-			a.sample_count   = Sd;                                                  /* :845 */
-			bool deinterleave = bf_kind_complex[st.in_kind] && !bf_kind_complex[st.out_kind];
-			a.batch_sample_count = deinterleave ? C * Sd * A : 0;                   /* :848-851 */
-			if (demod) {                                                            /* :870-873 */
-				a.demodulation_frequency = bp.demodulation_frequency;
-				a.sampling_frequency     = bp.sampling_frequency / 2;
-			}
-			for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
-			a.in_elements = cur_elements_bytes / bf_kind_byte_size[st.in_kind];
-			a.channels = C; a.transmits = A;
-			a.in_kind = st.in_kind; a.out_kind = st.out_kind;
-			ok &= HIP_OK(bf_launch_filter(&a, s));
-			cur = a.out; cur_elements_bytes = (int64_t)d.scratch[toggle].size; toggle ^= 1;
-		}break;
+		case BeamformerShaderKind_Demodulate:
+			ok &= launch_stage(ps, bp, i, cur, cur_elements_bytes, d.scratch[toggle].ptr, s);
+			cur = d.scratch[toggle].ptr; cur_elements_bytes = (int64_t)d.scratch[toggle].size; toggle ^= 1;
+			break;
 		case BeamformerShaderKind_DAS:{
 			uint32_t zfirst = 0, zcount = plan.output_points[2];
 			if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
@@ -520,13 +662,7 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 			/* which kernel, with which geometry: one table of rules (das_select.cpp), computed once per plan / shard / path mode / hook
 			 * change and reused by every frame after it.  Usually ONE launch; where a term of the frame can reach an end of its RF row
 			 * the z range is cut and the planes concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
-			std::vector<DasDecision> &parts = ps->das_parts;
-			if (parts.empty() || !parts[0].valid || parts[0].generation != ps->generation || ps->das_z_first != zfirst || ps->das_z_count != zcount ||
-			    parts[0].mode_asked != c.das_path_mode || parts[0].hooks_version != hooks().version) {
-				decide_das_parts(pb, plan, ps->transmit_table, zfirst, zcount, c.das_path_mode, parts);
-				for (DasDecision &dd : parts) { dd.generation = ps->generation; dd.mode_asked = c.das_path_mode; }
-				ps->das_z_first = zfirst; ps->das_z_count = zcount;
-			}
+			std::vector<DasDecision> &parts = frame_das_parts(ps, pb, zfirst, zcount);
 			const DasDecision &head = main_part(parts);
 			const uint32_t ext[3] = {head.a.size[0], head.a.size[1], zcount};
 			das_path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
@@ -548,80 +684,9 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 			const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * (plan.iq_pipeline ? 8u : 4u);
 
 			for (const DasDecision &dd : parts) {
-			BfDasArgs a = dd.a;
-			a.rf  = cur;
-			a.out = (char *)d.ring.ptr + f->offset + (uint64_t)(dd.z_first - zfirst) * plane_bytes;
-			a.transmits       = (const BfTransmit *)ps->transmits.ptr;
-			a.sparse_elements = (const int16_t *)ps->sparse.ptr;
-			a.readi_hadamard  = (const uint16_t *)ps->readi_hadamard.ptr;
 			uint32_t part_path = (uint32_t)dd.path;
-
-			if (dd.path == DasPath_Zero) {
-				ok &= HIP_OK(hipMemsetAsync(a.out, 0, dd.z_count * plane_bytes, s));
-			} else {
-				/* 64 zero bytes right behind the DAS input (every buffer it can live in is allocated with that much slack): the
-				 * gather target of out-of-range lanes */
-				const uint64_t used = dd.das_input_bytes;
-				if (dd.path != DasPath_General) ok &= HIP_OK(hipMemsetAsync((char *)const_cast<void *>(cur) + used, 0, 64, s));
-				switch (dd.path) {
-				case DasPath_Staged:
-				case DasPath_Gather:{
-					BfSeparableArgs sep = dd.sep;
-					bool staged = dd.path == DasPath_Staged;
-					if (staged && sep.uniform) {
-						/* the wave-uniform transmit tables live in global memory: one slice per (lateral tile row, plane), written per frame;
-						 * no memory: the shape with the tables in LDS, else the gather kernel with its own geometry */
-						const uint64_t table_bytes = (uint64_t)sep.table_stride * sep.tiles[1] * sep.tiles[2];
-						if (d.staged_tables.ensure(table_bytes)) {
-							sep.tables = d.staged_tables.ptr;
-							ok &= HIP_OK(bf_launch_das_staged_tables(&a, &sep, s));
-						} else if (dd.has_lds_tables) {
-							sep = dd.sep_lds_tables;
-						} else {
-							sep = dd.sep_gather; staged = false;
-						}
-					}
-					if (staged) {
-						/* window positions outside the staged window are counted (range-checked loop only: STAGED_CHECKED) */
-						sep.violations = frame_counters;
-						ok &= HIP_OK(!plan.iq_pipeline ? bf_launch_das_staged_real(&a, &sep, s) :
-						             a.interpolation == 2 ? bf_launch_das_staged_cubic(&a, &sep, s) : bf_launch_das_staged(&a, &sep, s));
-						part_path = DasPath_Staged;
-					} else {
-						ok &= HIP_OK(bf_launch_das_separable(&a, &sep, s));
-						part_path = DasPath_Gather;
-					}
-				}break;
-				case DasPath_Hercules:{
-					BfHerculesArgs hq = dd.herc;
-					if (d.hercules_table.ensure(((size_t)hq.table_pitch + 2) * a.size[1] * sizeof(float))) {
-						hq.pairs = nullptr;
-						const uint64_t prepared = used * (a.interpolation == 2 ? 4u : 2u);      /* cubic: four coefficients per sample, 32 bytes */
-						if (dd.hercules_prepared && d.hercules_pairs.ensure(prepared + 64)) {
-							hq.pairs = d.hercules_pairs.ptr;
-							hq.zero_offset = (uint32_t)prepared;
-						}
-						hq.table    = (float *)d.hercules_table.ptr;
-						hq.extremes = hq.table + (size_t)hq.table_pitch * a.size[1];
-						ok &= HIP_OK(bf_launch_das_hercules(&a, &hq, s));
-					} else {
-						ok &= HIP_OK(bf_launch_das(&a, s));                                     /* no memory for the row table: the general kernel */
-						part_path = DasPath_General;
-					}
-				}break;
-				case DasPath_Factored:
-					ok &= HIP_OK(bf_launch_das_factored(&a, s));
-					break;
-				case DasPath_Tile:
-					/* (block, channel chunk) pairs served from staged windows, and those the kernel sent through its gather loop: words 1, 2 */
-					a.tile_counters = frame_counters ? frame_counters + 1 : nullptr;
-					ok &= HIP_OK(bf_launch_das_tile(&a, s));
-					break;
-				default:
-					ok &= HIP_OK(bf_launch_das(&a, s));
-					break;
-				}
-			}
+			ok &= launch_das_part(ps, dd, cur, (char *)d.ring.ptr + f->offset + (uint64_t)(dd.z_first - zfirst) * plane_bytes, dd.z_count * plane_bytes,
+			                      frame_counters, s, part_path);
 			if (&dd == &head && dd.path != DasPath_Zero) das_path = part_path;
 			}
 			if (c.count_pairs && head.path != DasPath_Zero) {
@@ -721,6 +786,38 @@ static bool run_peers(uint32_t block, const void *src, uint64_t rf_size, uint32_
 	}
 	if (!select_device(0)) ok = false;
 	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
+}
+
+/* The pinned slot of an upload, free again (the copy or kernel that last read it has finished) and at least `size` bytes. */
+static bool claim_pinned(UploadSlot &u, uint64_t size)
+{
+	if (u.copy_pending) { (void)hipEventSynchronize(u.copied); u.copy_pending = false; }
+	if (u.pinned_size >= size) return true;
+	if (u.pinned) (void)hipHostFree(u.pinned);
+	u.pinned = nullptr; u.pinned_size = 0;
+	if (!HIP_OK(hipHostMalloc(&u.pinned, round_up(size, 4096), hipHostMallocDefault))) {
+		u.pinned = nullptr; (void)hipGetLastError();
+		return false;
+	}
+	u.pinned_size = round_up(size, 4096);
+	return true;
+}
+
+/* The caller's bytes into a pinned slot.  One core copies ~37 GB/s into pinned memory here; copies of 64 MiB and more are split over a few
+ * short-lived threads (the copy of a 512 MiB decode-benchmark frame drops from 14 ms to what the memory system gives). */
+static void copy_to_pinned(void *pinned, const void *data, size_t size)
+{
+	constexpr size_t kParallelCopyBytes = 64u << 20;
+	if (size < kParallelCopyBytes) { std::memcpy(pinned, data, size); return; }
+	const unsigned parts = 4;
+	const size_t   piece = ((size + parts - 1) / parts + 4095) & ~(size_t)4095;
+	std::thread workers[parts - 1];
+	for (unsigned i = 1; i < parts; i++) {
+		size_t begin = piece * i, end = begin + piece < size ? begin + piece : size;
+		workers[i - 1] = std::thread([=] { if (begin < end) std::memcpy((char *)pinned + begin, (const char *)data + begin, end - begin); });
+	}
+	std::memcpy(pinned, data, piece < size ? piece : size);
+	for (auto &w : workers) w.join();
 }
 
 /* lib .c:491-570 (client copy) + beamformer_core.c:1756-1805 (upload worker) */
@@ -829,33 +926,8 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 		 * stream. */
 		constexpr uint32_t kOverlapBytes = 8u << 20;
 		overlap = size >= kOverlapBytes;
-		if (u.copy_pending) { (void)hipEventSynchronize(u.copied); u.copy_pending = false; }
-		if (u.pinned_size < size) {
-			if (u.pinned) (void)hipHostFree(u.pinned);
-			u.pinned = nullptr; u.pinned_size = 0;
-			if (!HIP_OK(hipHostMalloc(&u.pinned, round_up(size, 4096), hipHostMallocDefault))) {
-				u.pinned = nullptr;
-				return set_error(BeamformerLibErrorKind_BufferOverflow);
-			}
-			u.pinned_size = round_up(size, 4096);
-		}
-		/* one core copies ~37 GB/s into pinned memory here; frames of 64 MiB and more are split
-		 * over a few short-lived threads (the copy of a 512 MiB decode-benchmark frame drops from
-		 * 14 ms to what the memory system gives) */
-		constexpr uint32_t kParallelCopyBytes = 64u << 20;
-		if (size >= kParallelCopyBytes) {
-			const unsigned parts = 4;
-			const size_t   piece = (((size_t)size + parts - 1) / parts + 4095) & ~(size_t)4095;
-			std::thread workers[parts - 1];
-			for (unsigned i = 1; i < parts; i++) {
-				size_t begin = piece * i, end = begin + piece < size ? begin + piece : size;
-				workers[i - 1] = std::thread([=] { if (begin < end) std::memcpy((char *)u.pinned + begin, (const char *)data + begin, end - begin); });
-			}
-			std::memcpy(u.pinned, data, piece < size ? piece : size);
-			for (auto &w : workers) w.join();
-		} else {
-			std::memcpy(u.pinned, data, size);
-		}
+		if (!claim_pinned(u, size)) return set_error(BeamformerLibErrorKind_BufferOverflow);
+		copy_to_pinned(u.pinned, data, size);
 		if (overlap) {
 			void *dst = d.rf[slot].ptr;
 			if (!direct) {
@@ -933,6 +1005,316 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 		for (uint32_t i = 1; i < c.device_count; i++) (void)hipStreamWaitEvent(s, c.devices[i].rf_landed[slot], 0);
 	lockstep.complete = done;
 	return done;
+}
+
+/* beamformer_hip_push_data_burst_with_compute: frame_count RF frames of one parameter block in one call (one device).
+ *   RF        the whole burst is one upload into one pinned slot -- over the copy engine into device staging when it is large, read in
+ *             place over PCIe when small, by push_rf_and_compute's rule applied to the burst -- and lands in ONE slot of the RF ring,
+ *             frame k at k * rf_stride with 64 spare bytes behind every frame;
+ *   stages    ingest, then every pre-DAS stage, ONE launch each for the whole burst: the stage kernels carry a frame dimension (grid z,
+ *             or grid y beside the channels for the filters, which then take the burst in chunks of 65535 / channels frames) and address
+ *             and bound every frame as a single frame is; frame k of a stage's output lies at k * stage_stride of burst_stage[];
+ *   DAS       the burst kernel in one launch where decide_burst says so, else the frame's own launch(es) on its slice of the input;
+ *   frames    contiguous in the frame ring (a burst that would straddle the end starts again at 0), consecutive ids;
+ *   timings   one event set for the burst, in the timing slot of its last frame; every frame's slot points there with share = N.
+ * Everything that can be refused is checked, and every buffer grown, BEFORE the ids are taken: a refused burst queues nothing.  After
+ * that a failure leaves tombstones under all of its ids (Lockstep's idea in push_rf_and_compute). */
+bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ParameterBlock &pb = c.blocks[block];
+	const BeamformerParameters &bp = pb.parameters;
+	hipStream_t s = d.stream;
+	const uint32_t N = frame_count;
+
+	const uint64_t bytes   = (uint64_t)bf_kind_byte_size[pb.data_kind];
+	const uint64_t out_row = bytes * bp.sample_count * bp.acquisition_count;
+	const uint64_t in_row  = bytes * bp.raw_data_dimensions[0];
+	const uint64_t rf_size = out_row * bp.channel_count;
+	for (uint32_t ch = 0; ch < bp.channel_count; ch++)
+		if ((uint16_t)pb.channel_mapping[ch] >= bp.raw_data_dimensions[1]) return set_error(BeamformerLibErrorKind_DataSizeMismatch);
+	const bool a1s2 = bp.contrast_mode == BeamformerContrastMode_A1S2;
+
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const Plan &plan = ps->plan;
+
+	/* the frames: all of one size, contiguous in the ring */
+	uint32_t zfirst = 0, zcount = plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
+	const uint64_t voxel_bytes = plan.iq_pipeline ? 8u : 4u;
+	const uint64_t frame_bytes = round_up((uint64_t)points[0] * points[1] * points[2] * voxel_bytes, 64);
+	if (frame_bytes > d.ring.size / N) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+
+	const bool has_das = plan.das_index >= 0;
+	std::vector<DasDecision> no_parts;
+	std::vector<DasDecision> &parts = has_das && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
+	BurstDecision route;
+	if (!parts.empty()) decide_burst(pb, plan, ps->transmit_table, parts, zfirst, zcount, c.das_path_mode, N, route);
+	else { route.stage_launches = (N + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels); route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared"; }
+
+	/* device and pinned memory, grown before anything is queued */
+	const uint64_t rf_stride    = round_up(rf_size, 64) + 64;
+	const uint64_t stage_stride = round_up(plan.intermediate_bytes, 64) + 64;
+	const uint64_t total        = (uint64_t)frame_size * N;
+	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
+	size_t pre_das_stages = 0;
+	for (size_t i = 0; i < plan.stages.size(); i++) {
+		const int kind = plan.stages[i].kind;
+		if (kind == BeamformerShaderKind_DAS) break;
+		pre_das_stages += kind != BeamformerShaderKind_CoherencyWeighting;
+	}
+	constexpr uint64_t kOverlapBytes = 8u << 20;                /* push_rf_and_compute's threshold, applied to the burst */
+	const bool overlap = !data_on_device && total >= kOverlapBytes;
+	bool fits = d.rf[slot].ensure(rf_stride * N);
+	if (pre_das_stages)     fits = fits && d.burst_stage[0].ensure(stage_stride * N);
+	if (pre_das_stages > 1) fits = fits && d.burst_stage[1].ensure(stage_stride * N);
+	if (overlap)            fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
+	if (!fits) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
+	UploadSlot &u = d.upload[slot];
+	if (!u.copied && (!HIP_OK(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming)) ||
+	                  !HIP_OK(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming))))
+		return set_error(BeamformerLibErrorKind_SharedMemory);
+	if (!data_on_device) {
+		if (!claim_pinned(u, total)) return set_error(BeamformerLibErrorKind_BufferOverflow);
+	}
+	const uint32_t owner = (uint32_t)((c.push_sequence + N - 1) % kTimingSlots);     /* the burst's events: its LAST frame's slot */
+	TimingSlot &t = d.timing[owner];
+	if (!t.created) {
+		for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
+		t.created = true;
+	}
+	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	bool wants_counters = false;
+	for (const DasDecision &dd : parts) wants_counters |= dd.path == DasPath_Staged || dd.path == DasPath_Tile;
+	if (wants_counters && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+
+	/* ---- from here on the burst owns ids first .. first + N - 1 ---- */
+	d.rf_index++;
+	const uint64_t first = c.push_sequence;
+	c.push_sequence += N;
+	d.frame_counter = first;
+	d.burst.valid = false;
+	struct BurstLockstep {
+		Device &d; uint64_t first; uint32_t count; bool complete;
+		~BurstLockstep() {
+			d.frame_counter = first + count;
+			if (complete) return;
+			for (uint64_t id = first; id < first + count; id++) {
+				FrameRecord &f = d.frames[id % d.frames.size()];
+				f = FrameRecord{}; f.points[0] = f.points[1] = f.points[2] = 0; f.id = (uint32_t)id; f.failed = true;
+				TimingSlot &t = d.timing[id % kTimingSlots];
+				t.count = 0; t.counted = false; t.violations_slot = ~0ull; t.das_voxels = 0; t.frame_id = id; t.failed = true;
+			}
+		}
+	} lockstep{d, first, N, false};
+
+	t.failed = false; t.sampled = true; t.events_slot = owner; t.share = N; t.count = 0; t.counted = false;
+	d.have_sample = false;          /* the burst's events cover N frames: a single frame that follows records its own */
+	auto segment = [&](uint32_t kind) {
+		if (t.count < BEAMFORMER_HIP_MAX_TIMED_STAGES) {
+			t.kinds[t.count++] = kind;
+			record(t, t.count, s);
+		}
+	};
+	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
+
+	/* ---- upload and ingest ---- */
+	const void *raw = data;
+	if (!data_on_device) {
+		copy_to_pinned(u.pinned, data, total);
+		if (overlap) {
+			if (u.unfenced_reader) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
+			if (u.consume_pending) ok &= HIP_OK(hipStreamWaitEvent(d.copy_stream, u.consumed, 0));
+			ok &= HIP_OK(hipMemcpyAsync(d.raw_staging[slot].ptr, u.pinned, total, hipMemcpyHostToDevice, d.copy_stream));
+			ok &= HIP_OK(hipEventRecord(u.copied, d.copy_stream));
+			u.copy_pending = true;
+			ok &= HIP_OK(hipStreamWaitEvent(s, u.copied, 0));
+			raw = d.raw_staging[slot].ptr;
+		} else {
+			void *mapped = nullptr;
+			if (!HIP_OK(hipHostGetDevicePointer(&mapped, u.pinned, 0))) return set_error(BeamformerLibErrorKind_InvalidAccess);
+			raw = mapped;
+		}
+	}
+	{
+		BfIngestArgs a{};
+		a.raw = raw; a.out = d.rf[slot].ptr;
+		a.channel_mapping = (const int16_t *)ps->mapping.ptr;
+		a.in_row_bytes = in_row; a.out_row_bytes = out_row; a.channels = bp.channel_count;
+		a.a1s2 = a1s2; a.base = bf_kind_base[pb.data_kind];
+		a.a1s2_scalars = bp.sample_count * (uint32_t)bf_kind_element_count[pb.data_kind];
+		a.frames = N; a.in_frame_bytes = frame_size; a.out_frame_bytes = rf_stride;
+		ok &= HIP_OK(bf_launch_ingest(&a, s));
+	}
+	if (!data_on_device && !overlap) {                /* the pinned slot is free again once the ingest kernel has run */
+		ok &= HIP_OK(hipEventRecord(u.copied, s));
+		u.copy_pending = true;
+	}
+	segment(kStageIngest);
+	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+	if (c.last_push_time > 0) {
+		if (c.rf_time_deltas.size() >= 32) c.rf_time_deltas.erase(c.rf_time_deltas.begin());
+		c.rf_time_deltas.push_back((float)(now - c.last_push_time));
+	}
+	c.last_push_time = now;
+	d.last_rf = (char *)d.rf[slot].ptr + (N - 1) * rf_stride; d.last_rf_bytes = rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
+	d.das_input = nullptr; d.das_input_bytes = 0;       /* (beamformer_hip_copy_das_input serves single frames) */
+
+	/* hook SCRATCH_POISON (run_frame_stages): the stage buffers of the whole burst, and below the burst's ring slots */
+	const bool poison = hooks().scratch_poison;
+	if (poison)
+		for (DeviceBuffer &b : d.burst_stage)
+			if (b.ptr) ok &= HIP_OK(hipMemsetAsync(b.ptr, 0xFF, b.size, s));
+
+	/* ---- stages, one after the other over all frames ---- */
+	const char *cur = (const char *)d.rf[slot].ptr;     /* frame k of the current stage's input: cur + k * cur_stride */
+	uint64_t cur_stride = rf_stride;
+	int64_t  cur_bound = (int64_t)rf_size;              /* what a stage may read of a frame: the RF itself, then a stage buffer's frame with its slack */
+	int toggle = 0;
+	FrameRecord *frame0 = nullptr;
+	uint32_t das_path = 0;
+	bool das_segment_done = false;
+	for (size_t i = 0; i < plan.stages.size() && ok; i++) {
+		const Stage &st = plan.stages[i];
+		das_segment_done = false;
+		switch (st.kind) {
+		case BeamformerShaderKind_Reshape:
+		case BeamformerShaderKind_Decode:
+		case BeamformerShaderKind_Hilbert:
+		case BeamformerShaderKind_Filter:
+		case BeamformerShaderKind_Demodulate:{
+			char *out = (char *)d.burst_stage[toggle].ptr;
+			ok &= launch_stage(ps, bp, i, cur, cur_bound, out, s, N, cur_stride, stage_stride);
+			cur = out; cur_stride = stage_stride; cur_bound = (int64_t)stage_stride; toggle ^= 1;
+		}break;
+		case BeamformerShaderKind_DAS:{
+			frame0 = next_burst_frames(points, plan.iq_pipeline, block, N);
+			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+			char *out0 = (char *)d.ring.ptr + frame0->offset;
+			if (poison && frame_bytes) ok &= HIP_OK(hipMemsetAsync(out0, 0xFF, frame_bytes * N, s));
+			if (zcount == 0) break;
+			const DasDecision &head = main_part(parts);
+			das_path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
+			const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes;
+			if (route.burst_kernel) {
+				BfDasArgs a = route.a;
+				a.rf = cur; a.out = out0;
+				a.transmits = (const BfTransmit *)ps->transmits.ptr; a.sparse_elements = (const int16_t *)ps->sparse.ptr;
+				a.readi_hadamard = (const uint16_t *)ps->readi_hadamard.ptr;
+				BfBurstArgs b{};
+				b.frame_count = N; b.rf_stride = cur_stride; b.out_stride = frame_bytes;
+				ok &= HIP_OK(bf_launch_das_burst(&a, &b, s));
+			} else {
+				for (uint32_t k = 0; k < N && ok; k++) {
+					uint32_t *frame_counters = nullptr;
+					if (wants_counters && N - k <= kTimingSlots) {       /* the table keeps the newest 32 frames: older ones of a long burst count nothing */
+						frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
+						ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
+					}
+					for (const DasDecision &dd : parts) {
+						uint32_t part_path = (uint32_t)dd.path;
+						ok &= launch_das_part(ps, dd, cur + k * cur_stride, out0 + k * frame_bytes + (uint64_t)(dd.z_first - zfirst) * plane_bytes,
+						                      dd.z_count * plane_bytes, frame_counters, s, part_path);
+						if (&dd == &head && dd.path != DasPath_Zero) das_path = part_path;
+					}
+				}
+			}
+			if (c.count_pairs && head.path != DasPath_Zero) {
+				/* the geometry-only count is the same for every frame: it runs once, into the last frame's counter, and the other
+				 * frames' counters are copies */
+				segment((uint32_t)st.kind);
+				unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
+				unsigned long long *mine = counters + owner;
+				ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
+				for (const DasDecision &dd : parts) {
+					BfDasArgs count = dd.general;
+					count.rf = cur; count.out = out0;
+					count.transmits = (const BfTransmit *)ps->transmits.ptr; count.sparse_elements = (const int16_t *)ps->sparse.ptr;
+					count.readi_hadamard = (const uint16_t *)ps->readi_hadamard.ptr;
+					count.pair_counter = mine;
+					ok &= HIP_OK(bf_launch_das_count(&count, s));
+				}
+				for (uint32_t k = 0; k + 1 < N && k + 1 < kTimingSlots; k++)
+					ok &= HIP_OK(hipMemcpyAsync(counters + (first + N - 2 - k) % kTimingSlots, mine, sizeof(*mine), hipMemcpyDeviceToDevice, s));
+				segment(kStagePairCount);
+				t.counted = true;
+				das_segment_done = true;
+			}
+		}break;
+		default: break;      /* CoherencyWeighting: the DAS epilogue */
+		}
+		if (!das_segment_done) segment((uint32_t)st.kind);
+	}
+	if (!has_das && ok) {
+		/* no DAS in the pipeline: the frames exist and stay zero */
+		frame0 = next_burst_frames(points, plan.iq_pipeline, block, N);
+		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+		if (frame_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, frame_bytes * N, s));
+	}
+	if (overlap) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
+	else         { u.consume_pending = false; u.unfenced_reader = true; }
+	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	/* every frame's row of the timing table: the burst's events, shared */
+	const bool das_ran = has_das && zcount && !parts.empty();
+	const BfDasArgs *da = das_ran ? &main_part(parts).a : nullptr;
+	const TimingSlot burst = t;
+	for (uint32_t k = 0; k < N; k++) {
+		const uint64_t id = first + k;
+		TimingSlot &ft = d.timing[id % kTimingSlots];
+		ft.count = burst.count; ft.counted = burst.counted;
+		std::memcpy(ft.kinds, burst.kinds, sizeof(ft.kinds));
+		ft.sampled = id % kTimingSlots == owner; ft.events_slot = owner; ft.share = N; ft.failed = false;
+		ft.frame_id = id;
+		ft.das_voxels = das_ran ? (uint64_t)points[0] * points[1] * points[2] : 0;
+		ft.das_taps = !das_ran ? 0 : da->interpolation == 0 ? 1 : da->interpolation == 1 ? 2 : 4;
+		ft.das_sample_bytes = das_ran ? (uint32_t)voxel_bytes : 0;
+		ft.das_path = das_ran ? das_path : 0;
+		ft.das_row_end_planes = das_ran ? row_end_planes(parts) : 0;
+		ft.violations_slot = wants_counters && !route.burst_kernel && N - k <= kTimingSlots ? id % kTimingSlots : ~0ull;
+	}
+	/* older unsampled frames whose row borrowed the events of the slot the burst has taken over: their row goes blank rather than show
+	 * the burst's times as one frame's */
+	for (uint32_t k = 0; k < kTimingSlots; k++) {
+		TimingSlot &old = d.timing[k];
+		if (old.frame_id < first && !old.sampled && old.events_slot == owner) old.count = 0;
+	}
+	d.burst.valid = true; d.burst.first_id = first; d.burst.count = N; d.burst.events_slot = owner; d.burst.route = route;
+	lockstep.complete = true;
+	return true;
+}
+
+/* beamformer_hip_get_last_burst_info */
+bool last_burst_info(BeamformerHipBurstInfo *out)
+{
+	Context &c = g_context;
+	std::memset(out, 0, sizeof(*out));
+	if (!c.device_ready) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	Device &d = c.devices[0];
+	const BurstRecord &b = d.burst;
+	/* the newest push must be that burst, complete */
+	if (!b.valid || d.frame_counter != b.first_id + b.count || !newest_record(d)) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!HIP_OK(hipSetDevice(d.device)) || !HIP_OK(hipStreamSynchronize(d.stream))) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	out->route.burst_kernel = b.route.burst_kernel; out->route.single_path = b.route.single_path == DasPath_Zero ? -2 : b.route.single_path;
+	out->route.frames_per_thread = b.route.frames_per_thread; out->route.das_launches = b.route.das_launches;
+	out->route.stage_launches = b.route.stage_launches; out->route.min_frames = kBurstMinFrames;
+	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.route.reason.c_str());
+	out->first_frame_id = (uint32_t)b.first_id; out->frame_count = b.count;
+	const TimingSlot &t = d.timing[b.events_slot];
+	out->stage_count = t.count;
+	for (uint32_t i = 0; i < t.count; i++) {
+		out->stage_kind[i] = t.kinds[i];
+		float ms = 0;
+		if (HIP_OK(hipEventElapsedTime(&ms, t.events[i], t.events[i + 1]))) out->stage_ms[i] = ms;
+	}
+	float total = 0;
+	if (t.count && HIP_OK(hipEventElapsedTime(&total, t.events[0], t.events[t.count]))) out->burst_ms = total;
+	return true;
 }
 
 /* the reference waits on futex locks with a timeout (lib .c:192-198, :679);
@@ -1051,10 +1433,10 @@ static bool timings_of(Device &d, BeamformerHipFrameTimings *out)
 	for (uint32_t i = 0; i < t.count; i++) {
 		out->stage_kind[i] = t.kinds[i];
 		float ms = 0;
-		if (HIP_OK(hipEventElapsedTime(&ms, e.events[i], e.events[i + 1]))) out->stage_ms[i] = ms;
+		if (HIP_OK(hipEventElapsedTime(&ms, e.events[i], e.events[i + 1]))) out->stage_ms[i] = ms / (float)t.share;
 	}
 	float total = 0;
-	if (t.count && HIP_OK(hipEventElapsedTime(&total, e.events[0], e.events[t.count]))) out->frame_ms = total;
+	if (t.count && HIP_OK(hipEventElapsedTime(&total, e.events[0], e.events[t.count]))) out->frame_ms = total / (float)t.share;
 	out->das_voxels = t.das_voxels; out->das_taps = t.das_taps;
 	out->das_sample_bytes = t.das_sample_bytes; out->das_path = t.das_path;
 	out->das_row_end_planes = t.das_row_end_planes;
@@ -1170,6 +1552,7 @@ bool fill_stats_table(BeamformerComputeStatsTable *out)
 				if (col >= BeamformerMaxComputeShaderStages) break;
 				float ms = 0;
 				(void)hipEventElapsedTime(&ms, e.events[i], e.events[i + 1]);
+				ms /= (float)t.share;                  /* a frame of a burst: its share of the burst's stage time */
 				float &cell = out->times[id % 32][col];
 				if (ms * 1e-3f > cell) cell = ms * 1e-3f;
 				if (dev == 0 && n == frames - 1) out->shader_ids[col] = t.kinds[i];

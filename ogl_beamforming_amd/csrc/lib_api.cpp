@@ -119,6 +119,44 @@ bool push_data_common(const void *data, uint32_t data_size, uint32_t image_plane
 	return push_rf_and_compute(slot, data, data_size, on_device);
 }
 
+/* A burst: the single push's checks per frame (one geometry: once), then what must hold for the burst as a whole.  Everything that needs
+ * no device is judged before the device is touched, so that a malformed burst is refused the same way on a machine without one. */
+bool push_burst_common(const void *data, uint32_t frame_size, uint32_t frame_count, uint32_t image_plane_tag, uint32_t slot, bool on_device)
+{
+	Context &c = ctx();
+	if (frame_count == 1) return push_data_common(data, frame_size, image_plane_tag, slot, on_device);
+	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES && frame_count <= BeamformerMaxBacklogFrames,
+	           BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
+	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
+	if (c.requested_count > 1 || (c.device_ready && c.device_count > 1)) {
+		std::fprintf(stderr, "[beamformer] a burst runs on one device: refused with the %u devices of beamformer_hip_set_devices\n",
+		             c.device_ready ? c.device_count : c.requested_count);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	const ParameterBlock &pb = c.blocks[slot];
+	const BeamformerParameters &bp = pb.parameters;
+	const uint64_t max_rf_size = frame_ring_bytes() / 3;
+	const uint64_t bytes    = (uint64_t)bf_kind_byte_size[pb.data_kind];
+	const uint64_t rf_size  = (uint64_t)bp.acquisition_count * bp.sample_count * bp.channel_count * bytes;
+	const uint64_t raw_size = (uint64_t)bp.raw_data_dimensions[0] * bp.raw_data_dimensions[1] * bytes;
+	if (!check(data != nullptr, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(rf_size <= max_rf_size && rf_size <= UINT32_MAX, BeamformerLibErrorKind_RFDataSizeOverflow)) return false;
+	if (!check(rf_size <= frame_size && (uint64_t)frame_size == raw_size, BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	if (!check(rf_size > 0, BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	if (!check(bp.channel_count <= BeamformerMaxChannelCount && bp.acquisition_count <= BeamformerMaxEmissionsCount,
+	           BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	/* the whole burst in the frame ring, and its DAS input below the 4 GiB the kernels' 32-bit byte offsets reach per frame */
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const uint64_t planes = pb.shard_z_count ? pb.shard_z_count : plan.output_points[2];
+	const uint64_t frame_bytes = ((uint64_t)plan.output_points[0] * plan.output_points[1] * planes * (plan.iq_pipeline ? 8u : 4u) + 63) / 64 * 64;
+	if (!check(frame_bytes <= frame_ring_bytes() / frame_count, BeamformerLibErrorKind_FrameSizeOverflow)) return false;
+	if (!ensure_device()) return false;
+	return push_burst(slot, data, frame_size, frame_count, on_device);
+}
+
 template <typename T>
 uint32_t push_array(T *dst, size_t dst_count, const T *src, uint32_t count, uint32_t elements, uint32_t block, uint32_t dirty)
 {
@@ -460,6 +498,53 @@ uint32_t beamformer_hip_push_device_data_with_compute(const void *device_data, u
                                                       uint32_t image_plane_tag, uint32_t parameter_slot)
 {
 	return push_data_common(device_data, size, image_plane_tag, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_push_data_burst_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                     uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_burst_common(data, frame_size, frame_count, image_plane_tag, parameter_slot, false);
+}
+
+uint32_t beamformer_hip_push_device_data_burst_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                            uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_burst_common(device_data, frame_size, frame_count, image_plane_tag, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_describe_burst(uint32_t parameter_slot, uint32_t frame_count, BeamformerHipBurstDescription *out)
+{
+	if (!valid_parameter_block(parameter_slot) || !check(out != nullptr && frame_count != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	Context &c = ctx();
+	const ParameterBlock &pb = c.blocks[parameter_slot];
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	std::memset(out, 0, sizeof(*out));
+	out->min_frames = kBurstMinFrames;
+	out->frames_per_thread = 1; out->stage_launches = (frame_count + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels);
+	if (plan.das_index < 0) {
+		out->single_path = -1;
+		std::snprintf(out->reason, sizeof(out->reason), "no DAS stage runs: the frames are cleared");
+		return 1;
+	}
+	uint32_t zfirst = 0, zcount = plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	const std::vector<BfTransmit> transmits = build_transmit_table(pb);
+	std::vector<DasDecision> parts;
+	decide_das_parts(pb, plan, transmits, zfirst, zcount, c.das_path_mode, parts);
+	BurstDecision b;
+	decide_burst(pb, plan, transmits, parts, zfirst, zcount, c.das_path_mode, frame_count, b);
+	out->burst_kernel = b.burst_kernel; out->single_path = b.single_path == DasPath_Zero ? -2 : b.single_path;
+	out->frames_per_thread = b.frames_per_thread; out->das_launches = b.das_launches; out->stage_launches = b.stage_launches;
+	std::snprintf(out->reason, sizeof(out->reason), "%s", b.reason.c_str());
+	return 1;
+}
+
+uint32_t beamformer_hip_get_last_burst_info(BeamformerHipBurstInfo *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
+	return last_burst_info(out);
 }
 
 uint32_t beamformer_hip_synchronize(void)

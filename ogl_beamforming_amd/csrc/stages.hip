@@ -57,8 +57,8 @@ __global__ __launch_bounds__(256) void ingest_copy_kernel(const BfIngestArgs a)
 {
 	uint32_t channel = blockIdx.y;
 	uint16_t row     = (uint16_t)a.channel_mapping[channel];
-	const V *in  = (const V *)((const char *)a.raw + a.in_row_bytes * row);
-	V       *out = (V *)((char *)a.out + a.out_row_bytes * channel);
+	const V *in  = (const V *)((const char *)a.raw + a.in_row_bytes * row + a.in_frame_bytes * blockIdx.z);
+	V       *out = (V *)((char *)a.out + a.out_row_bytes * channel + a.out_frame_bytes * blockIdx.z);
 	uint64_t n   = a.out_row_bytes / sizeof(V);
 	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
 		out[i] = in[i];
@@ -72,8 +72,8 @@ __global__ __launch_bounds__(256) void ingest_a1s2_kernel(const BfIngestArgs a)
 {
 	uint32_t channel = blockIdx.y;
 	uint16_t row     = (uint16_t)a.channel_mapping[channel];
-	const T *in  = (const T *)((const char *)a.raw + a.in_row_bytes * row);
-	T       *out = (T *)((char *)a.out + a.out_row_bytes * channel);
+	const T *in  = (const T *)((const char *)a.raw + a.in_row_bytes * row + a.in_frame_bytes * blockIdx.z);
+	T       *out = (T *)((char *)a.out + a.out_row_bytes * channel + a.out_frame_bytes * blockIdx.z);
 	uint64_t total = a.out_row_bytes / sizeof(T);
 	uint32_t n     = a.a1s2_scalars;
 	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
@@ -89,7 +89,7 @@ extern "C" hipError_t bf_launch_ingest(const BfIngestArgs *a, hipStream_t s)
 	typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 	if (a->a1s2) {
 		uint64_t n = a->out_row_bytes / (a->base == BF_BASE_F32 ? 4 : 2);
-		dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256), a->channels);
+		dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256), a->channels, a->frames ? a->frames : 1u);
 		switch (a->base) {
 		case BF_BASE_I16: hipLaunchKernelGGL(ingest_a1s2_kernel<int16_t>,  grid, dim3(256), 0, s, *a); break;
 		case BF_BASE_F32: hipLaunchKernelGGL(ingest_a1s2_kernel<float>,    grid, dim3(256), 0, s, *a); break;
@@ -97,10 +97,10 @@ extern "C" hipError_t bf_launch_ingest(const BfIngestArgs *a, hipStream_t s)
 		}
 		return hipGetLastError();
 	}
-	uint64_t align = a->in_row_bytes | a->out_row_bytes | (uint64_t)(uintptr_t)a->raw | (uint64_t)(uintptr_t)a->out;
+	uint64_t align = a->in_row_bytes | a->out_row_bytes | (uint64_t)(uintptr_t)a->raw | (uint64_t)(uintptr_t)a->out | a->in_frame_bytes | a->out_frame_bytes;
 	uint32_t v = (align % 16 == 0) ? 16 : (align % 4 == 0) ? 4 : 2;
 	uint64_t n = a->out_row_bytes / v;
-	dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256), a->channels);
+	dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256), a->channels, a->frames ? a->frames : 1u);
 	switch (v) {
 	case 16: hipLaunchKernelGGL(ingest_copy_kernel<u32x4>,    grid, dim3(256), 0, s, *a); break;
 	case 4:  hipLaunchKernelGGL(ingest_copy_kernel<uint32_t>, grid, dim3(256), 0, s, *a); break;
@@ -118,6 +118,10 @@ struct ReshapeOrder { uint32_t axis[3]; };
 
 __global__ __launch_bounds__(256) void reshape_kernel(const BfReshapeArgs a, const ReshapeOrder order)
 {
+	/* this block's frame (blockIdx.y) */
+	const void *left  = (const char *)a.left  + a.in_frame_bytes  * blockIdx.y;
+	const void *right = (const char *)a.right + a.in_frame_bytes  * blockIdx.y;
+	void       *out   = (char *)a.out         + a.out_frame_bytes * blockIdx.y;
 	uint64_t total = (uint64_t)a.size[0] * a.size[1] * a.size[2];
 	uint32_t n0 = a.size[order.axis[0]], n1 = a.size[order.axis[1]];
 	for (uint64_t id = (uint64_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (uint64_t)gridDim.x * 256) {
@@ -129,12 +133,12 @@ __global__ __launch_bounds__(256) void reshape_kernel(const BfReshapeArgs a, con
 		int64_t out_index = a.out_stride[0] * c[0] + a.out_stride[1] * c[1] + a.out_stride[2] * c[2];
 		f32x2 v;
 		if (a.interleave) {
-			v.x = load_element(a.in_kind, a.left,  in_index).x;
-			v.y = load_element(a.in_kind, a.right, in_index).x;
+			v.x = load_element(a.in_kind, left,  in_index).x;
+			v.y = load_element(a.in_kind, right, in_index).x;
 		} else {
-			v = load_element(a.in_kind, a.left, in_index);
+			v = load_element(a.in_kind, left, in_index);
 		}
-		store_element(a.out_kind, a.out, out_index, v);
+		store_element(a.out_kind, out, out_index, v);
 	}
 }
 
@@ -150,7 +154,7 @@ extern "C" hipError_t bf_launch_reshape(const BfReshapeArgs *a, hipStream_t s)
 	order.axis[2] = (uint32_t)((fast + 2) % 3);
 	uint64_t blocks = (total + 255) / 256;
 	if (blocks > 65536) blocks = 65536;
-	hipLaunchKernelGGL(reshape_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *a, order);
+	hipLaunchKernelGGL(reshape_kernel, dim3((unsigned)blocks, a->frames ? a->frames : 1u), dim3(256), 0, s, *a, order);
 	return hipGetLastError();
 }
 
@@ -166,8 +170,11 @@ extern "C" hipError_t bf_launch_reshape(const BfReshapeArgs *a, hipStream_t s)
  * OUTPUT element type, as in the shader (OutputDataType result[]): f32, or f16 rounded
  * after every operation when the planner leaves the output in half precision. */
 template <bool CPLX, bool ACC16>
-__global__ __launch_bounds__(256) void decode_kernel(const BfDecodeArgs a)
+__global__ __launch_bounds__(256) void decode_kernel(const BfDecodeArgs a0)
 {
+	BfDecodeArgs a = a0;                  /* this block's frame (blockIdx.z) */
+	a.in  = (const char *)a0.in + a0.in_frame_bytes  * blockIdx.z;
+	a.out = (char *)a0.out      + a0.out_frame_bytes * blockIdx.z;
 	const float *__restrict__ hadamard_t = a.hadamard_t;
 	extern __shared__ __attribute__((aligned(16))) float decode_lds[];
 	const uint32_t T = a.transmit_count, C = a.channel_count;
@@ -237,8 +244,11 @@ __global__ __launch_bounds__(256) void decode_kernel(const BfDecodeArgs a)
  * decode_kernel).  Lanes are samples (row pitch T+1: conflict free); the butterflies of a
  * stage are dealt to the four waves. */
 template <bool CPLX, uint32_t B>
-__global__ __launch_bounds__(256) void decode_fwht_kernel(const BfDecodeArgs a)
+__global__ __launch_bounds__(256) void decode_fwht_kernel(const BfDecodeArgs a0)
 {
+	BfDecodeArgs a = a0;                  /* this block's frame (blockIdx.z) */
+	a.in  = (const char *)a0.in + a0.in_frame_bytes  * blockIdx.z;
+	a.out = (char *)a0.out      + a0.out_frame_bytes * blockIdx.z;
 	typedef typename std::conditional<CPLX, f32x2, float>::type V;
 	extern __shared__ __attribute__((aligned(16))) float decode_lds[];
 	V *tile = reinterpret_cast<V *>(decode_lds);
@@ -308,7 +318,7 @@ extern "C" hipError_t bf_launch_decode(const BfDecodeArgs *a, hipStream_t s)
 	if (!a->sample_count || !a->channel_count || !a->transmit_count) return hipSuccess;
 	bool cplx  = (a->in_kind & 1) != 0;
 	bool acc16 = (a->out_kind >> 1) == 2;
-	dim3 grid((a->sample_count + 63) / 64, a->channel_count);
+	dim3 grid((a->sample_count + 63) / 64, a->channel_count, a->frames ? a->frames : 1u);
 	size_t lds = (size_t)64 * (a->transmit_count + 1) * (cplx ? 8 : 4);
 	if (lds > 160 * 1024) return hipErrorInvalidValue;
 	if (!acc16 && a->hadamard_base_order && a->hadamard_base && a->transmit_count >= 4) {
@@ -352,8 +362,12 @@ extern "C" hipError_t bf_launch_decode(const BfDecodeArgs *a, hipStream_t s)
  * stores it with 16 transmits contiguous per sample -- 64- / 128-byte pieces.  Same arithmetic, same values. */
 constexpr uint32_t kFilterTransposeWaves = 16;
 template <int IN_KIND, bool DEMOD, bool TRANSPOSE = false>
-__global__ __launch_bounds__(TRANSPOSE ? 1024 : 256) void filter_kernel(const BfFilterArgs a)
+__global__ __launch_bounds__(TRANSPOSE ? 1024 : 256) void filter_kernel(const BfFilterArgs a0)
 {
+	BfFilterArgs a = a0;                  /* this block's frame: blockIdx.y = frame * channels + channel */
+	const uint32_t frame = blockIdx.y / a0.channels;
+	a.in  = (const char *)a0.in + a0.in_frame_bytes  * frame;
+	a.out = (char *)a0.out      + a0.out_frame_bytes * frame;
 	constexpr bool F16 = (IN_KIND >> 1) != 1;                       /* every 16-bit kind stages through binary16 */
 	extern __shared__ __attribute__((aligned(16))) float filter_lds[];
 	const uint32_t L = a.filter_length, D = a.decimation;
@@ -361,7 +375,7 @@ __global__ __launch_bounds__(TRANSPOSE ? 1024 : 256) void filter_kernel(const Bf
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t wg   = TRANSPOSE ? blockIdx.x : blockIdx.x * 4 + wave;          /* the shader's gl_WorkGroupID.x */
-	const uint32_t channel = blockIdx.y;
+	const uint32_t channel = blockIdx.y - frame * a0.channels;
 	const uint32_t transmit_wanted = TRANSPOSE ? blockIdx.z * kFilterTransposeWaves + wave : blockIdx.z;
 	const uint32_t transmit = transmit_wanted < a.transmits ? transmit_wanted : a.transmits - 1;     /* (TRANSPOSE: a ragged last block computes a copy, stores nothing) */
 	float *w = filter_lds + (size_t)wave * window * 2;
@@ -471,11 +485,11 @@ __global__ __launch_bounds__(TRANSPOSE ? 1024 : 256) void filter_kernel(const Bf
 	}
 }
 
-extern "C" hipError_t bf_launch_filter(const BfFilterArgs *a, hipStream_t s)
+static hipError_t launch_filter_chunk(const BfFilterArgs *a, uint32_t frames, hipStream_t s)
 {
 	if (!a->sample_count || !a->channels || !a->transmits) return hipSuccess;
 	uint32_t groups = (a->sample_count + 63) / 64;
-	dim3 grid((groups + 3) / 4, a->channels, a->transmits);
+	dim3 grid((groups + 3) / 4, a->channels * frames, a->transmits);
 	size_t lds = (size_t)4 * (a->decimation * 64 + a->filter_length - 1) * 2 * sizeof(float);
 	if (lds > 160 * 1024) return hipErrorInvalidValue;
 	/* output with the transmits contiguous and the samples far apart (Decode's input layout), complex elements, several transmits:
@@ -484,7 +498,7 @@ extern "C" hipError_t bf_launch_filter(const BfFilterArgs *a, hipStream_t s)
 	const bool transpose = a->out_stride[2] == 1 && a->out_stride[0] >= (int64_t)a->transmits && a->transmits >= 4 && a->batch_sample_count == 0 &&
 	                       (a->out_kind & 1) && lds_t <= 64 * 1024;
 	if (transpose) {
-		dim3 grid_t(groups, a->channels, (a->transmits + kFilterTransposeWaves - 1) / kFilterTransposeWaves);
+		dim3 grid_t(groups, a->channels * frames, (a->transmits + kFilterTransposeWaves - 1) / kFilterTransposeWaves);
 		#define BF_FILTER_T(kind) \
 			case kind: if (a->demodulate) hipLaunchKernelGGL((filter_kernel<kind, true,  true>), grid_t, dim3(1024), lds_t, s, *a); \
 			           else               hipLaunchKernelGGL((filter_kernel<kind, false, true>), grid_t, dim3(1024), lds_t, s, *a); break;
@@ -513,14 +527,18 @@ extern "C" hipError_t bf_launch_filter(const BfFilterArgs *a, hipStream_t s)
  * transform).  The reference has no implementation to follow (include/ogl_beamformer_hip.h).
  * Same shape as the filter kernel: a wave owns 64 outputs and an LDS window of 64 + L - 1 real
  * samples; f32 products and sums; samples outside the row are zero. */
-__global__ __launch_bounds__(256) void hilbert_kernel(const BfFilterArgs a)
+__global__ __launch_bounds__(256) void hilbert_kernel(const BfFilterArgs a0)
 {
+	BfFilterArgs a = a0;                  /* this block's frame: blockIdx.y = frame * channels + channel */
+	const uint32_t frame = blockIdx.y / a0.channels;
+	a.in  = (const char *)a0.in + a0.in_frame_bytes  * frame;
+	a.out = (char *)a0.out      + a0.out_frame_bytes * frame;
 	extern __shared__ __attribute__((aligned(16))) float filter_lds[];
 	const uint32_t L = a.filter_length, window = 64 + L - 1;
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t wg   = blockIdx.x * 4 + wave;
-	const uint32_t channel = blockIdx.y, transmit = blockIdx.z;
+	const uint32_t channel = blockIdx.y - frame * a0.channels, transmit = blockIdx.z;
 	float *w = filter_lds + (size_t)wave * window;
 	const int64_t row = a.in_stride[1] * channel + a.in_stride[2] * transmit;
 	const int64_t first = (int64_t)wg * 64 - (int64_t)(L - 1);
@@ -549,15 +567,35 @@ __global__ __launch_bounds__(256) void hilbert_kernel(const BfFilterArgs a)
 	}
 }
 
-extern "C" hipError_t bf_launch_hilbert(const BfFilterArgs *a, hipStream_t s)
+static hipError_t launch_hilbert_chunk(const BfFilterArgs *a, uint32_t frames, hipStream_t s)
 {
 	if (!a->sample_count || !a->channels || !a->transmits) return hipSuccess;
 	uint32_t groups = (a->sample_count + 63) / 64;
-	dim3 grid((groups + 3) / 4, a->channels, a->transmits);
+	dim3 grid((groups + 3) / 4, a->channels * frames, a->transmits);
 	size_t lds = (size_t)4 * (64 + a->filter_length - 1) * sizeof(float);
 	hipLaunchKernelGGL(hilbert_kernel, dim3(grid), dim3(256), lds, s, *a);
 	return hipGetLastError();
 }
+
+/* The frames of a burst ride on grid y beside the channels (z carries the transmits): chunks of as many frames as the 16-bit grid limit
+ * leaves room for -- bf_stage_frame_chunk(channels), one launch for every burst of up to 255 frames of 256 channels. */
+template <typename Launch>
+static hipError_t launch_frame_chunks(const BfFilterArgs *a, hipStream_t s, Launch launch)
+{
+	const uint32_t frames = a->frames ? a->frames : 1u;
+	if (!a->channels) return hipSuccess;
+	const uint32_t chunk = bf_stage_frame_chunk(a->channels);
+	for (uint32_t first = 0; first < frames; first += chunk) {
+		BfFilterArgs part = *a;
+		part.in  = (const char *)a->in + a->in_frame_bytes  * first;
+		part.out = (char *)a->out      + a->out_frame_bytes * first;
+		hipError_t e = launch(&part, frames - first < chunk ? frames - first : chunk, s);
+		if (e != hipSuccess) return e;
+	}
+	return hipSuccess;
+}
+extern "C" hipError_t bf_launch_filter(const BfFilterArgs *a, hipStream_t s)  { return launch_frame_chunks(a, s, launch_filter_chunk); }
+extern "C" hipError_t bf_launch_hilbert(const BfFilterArgs *a, hipStream_t s) { return launch_frame_chunks(a, s, launch_hilbert_chunk); }
 
 /* ------------------------------------------------------------------ sum */
 

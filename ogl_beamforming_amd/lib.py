@@ -102,6 +102,10 @@ def _load():
         "beamformer_hip_set_stream": (u32, [vp]),
         "beamformer_hip_set_output_shard": (u32, [u32, u32, u32]),
         "beamformer_hip_push_device_data_with_compute": (u32, [vp, u32, u32, u32]),
+        "beamformer_hip_push_data_burst_with_compute": (u32, [vp, u32, u32, u32, u32]),
+        "beamformer_hip_push_device_data_burst_with_compute": (u32, [vp, u32, u32, u32, u32]),
+        "beamformer_hip_describe_burst": (u32, [u32, u32, C.POINTER(P.HipBurstDescription)]),
+        "beamformer_hip_get_last_burst_info": (u32, [C.POINTER(P.HipBurstInfo)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -186,6 +190,63 @@ def beamform(bp, rf, filters=(), timeout_ms=-1):
     rf = np.ascontiguousarray(rf)
     _check(lib.beamformer_push_data_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, 0, 0))
     return get_last_frame(bp)
+
+
+def get_last_frames(bp, count, shard_planes=None):
+    """The `count` newest frames, oldest first, as one array (count, Z, Y, X); all of this block's size and kind."""
+    lib = library()
+    shape = list(frame_shape(bp))
+    if shard_planes is not None:
+        shape[0] = shard_planes
+    info = P.HipFrameInfo()
+    _check(lib.beamformer_hip_get_last_frame_info(C.byref(info)))
+    complex_out = info.data_kind == int(P.DataKind.Float32Complex)
+    voxels = int(np.prod(shape))
+    each = (voxels * (8 if complex_out else 4) + 63) // 64 * 64          # frames are exported rounded up to 64 bytes
+    raw = np.zeros(count * each // 4, dtype=np.float32)
+    _check(lib.beamformer_get_last_frames(raw.ctypes.data_as(C.c_void_p), raw.nbytes, count))
+    frames = raw.reshape(count, each // 4)
+    if complex_out:
+        return np.ascontiguousarray(frames[:, : 2 * voxels]).view(np.complex64).reshape([count] + shape)
+    return np.ascontiguousarray(frames[:, :voxels]).reshape([count] + shape)
+
+
+def beamform_burst(bp, rf_frames, filters=(), timeout_ms=-1, on_device_pointer=None):
+    """N frames of one geometry in one call (beamformer_hip_push_data_burst_with_compute): `rf_frames` is a C-contiguous array
+    whose first axis runs over the frames, each frame laid out as beamform() takes it.  Returns (N, Z, Y, X), oldest first."""
+    lib = library()
+    for slot, fp in enumerate(filters):
+        if fp is not None:
+            _check(lib.beamformer_create_filter(C.byref(fp), slot, 0))
+    _check(lib.beamformer_push_simple_parameters(C.byref(bp)))
+    lib.beamformer_set_global_timeout(C.c_uint32(timeout_ms & 0xFFFFFFFF).value)
+    rf_frames = np.ascontiguousarray(rf_frames)
+    count = rf_frames.shape[0]
+    frame_size = rf_frames.nbytes // count
+    if on_device_pointer is not None:
+        _check(lib.beamformer_hip_push_device_data_burst_with_compute(C.c_void_p(on_device_pointer), frame_size, count, 0, 0))
+    else:
+        _check(lib.beamformer_hip_push_data_burst_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, count, 0, 0))
+    return get_last_frames(bp, count)
+
+
+def describe_burst(bp, n, filters=(), slot=0):
+    """What a burst of n frames of these parameters would run (beamformer_hip_describe_burst): the description struct; .reason
+    says why.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    d = P.HipBurstDescription()
+    _check(L.beamformer_hip_describe_burst(slot, n, C.byref(d)))
+    return d
+
+
+def last_burst_info():
+    """beamformer_hip_get_last_burst_info: the newest burst's route, ids and whole-burst stage times; waits for it."""
+    info = P.HipBurstInfo()
+    _check(library().beamformer_hip_get_last_burst_info(C.byref(info)))
+    return info
 
 
 def get_last_frame(bp, shard_planes=None):

@@ -216,6 +216,20 @@ class HipFrameTimings(C.Structure):
     ]
 
 
+class HipBurstDescription(C.Structure):
+    _fields_ = [("burst_kernel", C.c_uint32), ("single_path", C.c_int32), ("frames_per_thread", C.c_uint32),
+                ("das_launches", C.c_uint32), ("stage_launches", C.c_uint32), ("min_frames", C.c_uint32), ("reason", C.c_char * 160)]
+
+
+class HipBurstInfo(C.Structure):
+    _fields_ = [("route", HipBurstDescription), ("first_frame_id", C.c_uint32), ("frame_count", C.c_uint32), ("stage_count", C.c_uint32),
+                ("stage_kind", C.c_uint32 * HIP_MAX_TIMED_STAGES), ("stage_ms", C.c_float * HIP_MAX_TIMED_STAGES), ("burst_ms", C.c_float)]
+
+
+HIP_MAX_BURST_FRAMES = 1024
+HIP_DAS_PATH_NO_BURST_KERNEL = 0x400     # beamformer_hip_set_das_path flag: bursts run the single-frame DAS kernel once per frame
+
+
 class DasPath(enum.IntEnum):
     """BeamformerHipFrameTimings::das_path / BeamformerHipDasDescription::path (csrc/das_select.h)"""
     General = 0

@@ -1,0 +1,134 @@
+"""Bursts (beamformer_hip_push_data_burst_with_compute) on the CPU: the four entry points exist and are bound, the burst kernel is
+in the library with its twelve instantiations, beamformer_hip_describe_burst (no device needed) names the route the rules of
+csrc/das_select.cpp give, and a malformed burst is refused before any device is touched."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from ogl_beamforming_amd import lib
+from ogl_beamforming_amd import params as P
+from tests import cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E = P.LibError
+BURST_SYMBOLS = ("beamformer_hip_push_data_burst_with_compute", "beamformer_hip_push_device_data_burst_with_compute",
+                 "beamformer_hip_describe_burst", "beamformer_hip_get_last_burst_info")
+
+
+def test_the_four_burst_symbols_are_declared_exported_and_bound():
+    header = open(os.path.join(ROOT, "include", "ogl_beamformer_hip.h")).read()
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIBRARY_PATH], capture_output=True, text=True, check=True)
+    exported = {line.split()[-1] for line in nm.stdout.splitlines() if " T " in line}
+    for name in BURST_SYMBOLS:
+        assert f"{name}(" in header, name
+        assert name in exported, name
+        assert name in lib.exported_symbols(), name
+    assert "#define BEAMFORMER_HIP_MAX_BURST_FRAMES" in header and P.HIP_MAX_BURST_FRAMES >= 256
+    # the structs the binding mirrors: 6 words + the reason; the description + 3 words + 24 kinds + 24 times + the total
+    assert C.sizeof(P.HipBurstDescription) == 24 + 160
+    assert C.sizeof(P.HipBurstInfo) == 184 + 12 + 4 * 24 + 4 * 24 + 4
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
+def test_the_burst_kernel_has_twelve_instantiations_without_spills():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    kernels = [k for k in kernel_resources.kernels_of(lib.LIBRARY_PATH) if "das_burst_kernel" in k["demangled"]]
+    assert len({k["demangled"] for k in kernels}) == 12, sorted(k["demangled"] for k in kernels)
+    for k in kernels:
+        assert not k["vgpr_spill_count"] and not k["private_segment_fixed_size"], k["demangled"]
+        assert k["vgpr_count"] <= 128, (k["demangled"], k["vgpr_count"])        # 256-thread blocks: 4 waves per SIMD at least
+
+
+@pytest.mark.parametrize("name", ["config1_small", "rca_flash_none_tx", "rca_cubic_real"])
+@pytest.mark.parametrize("n", [5, 64])
+def test_general_kernel_rca_blocks_take_the_burst_kernel_in_one_launch(name, n):
+    acq = cases.make(name)
+    lib.library().beamformer_hip_set_das_path(0)
+    d = lib.describe_burst(acq.bp, n, acq.filters)
+    assert d.burst_kernel == 1 and d.das_launches == 1, d.reason
+    assert d.single_path == int(P.DasPath.General) and d.frames_per_thread == 4
+    assert d.stage_launches == 1 and d.reason          # ingest and every pre-DAS stage: one launch for the burst
+
+
+@pytest.mark.parametrize("name, word", [("forces", "family"), ("hercules_real", "family"), ("rca_staged_auto", "kernel")])
+def test_other_blocks_take_the_fallback_and_say_why(name, word):
+    acq = cases.make(name)
+    lib.library().beamformer_hip_set_das_path(0)
+    single = lib.describe_das(acq.bp, acq.filters)
+    d = lib.describe_burst(acq.bp, 5, acq.filters)
+    assert d.burst_kernel == 0 and d.frames_per_thread == 1
+    assert d.single_path == single[0]
+    assert word in d.reason.decode(), d.reason
+    # the single-frame launches, once per frame: rca_staged_auto's frames are cut in two by the row-end rule
+    parts = 2 if name == "rca_staged_auto" else 1
+    assert d.das_launches == 5 * parts and d.stage_launches == 1
+
+
+def test_fewer_frames_than_the_threshold_and_the_flag_take_the_fallback():
+    acq = cases.make("config1_small")
+    L = lib.library()
+    L.beamformer_hip_set_das_path(0)
+    d = lib.describe_burst(acq.bp, 2, acq.filters)
+    assert d.min_frames >= 2
+    below = lib.describe_burst(acq.bp, d.min_frames - 1, acq.filters)
+    assert below.burst_kernel == 0 and "fewer than" in below.reason.decode()
+    assert lib.describe_burst(acq.bp, d.min_frames, acq.filters).burst_kernel == 1
+    try:
+        L.beamformer_hip_set_das_path(P.HIP_DAS_PATH_NO_BURST_KERNEL)
+        forced = lib.describe_burst(acq.bp, 64, acq.filters)
+        assert forced.burst_kernel == 0 and forced.das_launches == 64 and "0x400" in forced.reason.decode()
+        # the flag changes nothing about single frames
+        assert lib.describe_das(acq.bp, acq.filters)[0] == int(P.DasPath.General)
+    finally:
+        L.beamformer_hip_set_das_path(0)
+    assert not L.beamformer_hip_describe_burst(0, 0, C.byref(P.HipBurstDescription())) and lib.last_error()[0] == E.InvalidAccess
+
+
+def test_long_bursts_of_many_channels_take_the_filters_in_chunks():
+    """the filters' grid carries frames x channels on one 16-bit axis: 65535 // 64 = 1023 frames of config 1's 64 channels a launch"""
+    acq = cases.make("config1_small")
+    acq.bp.channel_count = 64
+    acq.bp.raw_data_dimensions[1] = 64
+    lib.library().beamformer_hip_set_das_path(0)
+    assert lib.describe_burst(acq.bp, 1023, acq.filters).stage_launches == 1
+    assert lib.describe_burst(acq.bp, 1024, acq.filters).stage_launches == 2
+
+
+def push_parameters(acq):
+    L = lib.library()
+    for s, fp in enumerate(acq.filters):
+        assert L.beamformer_create_filter(C.byref(fp), s, 0)
+    assert L.beamformer_push_simple_parameters(C.byref(acq.bp)), lib.last_error()
+    return L
+
+
+def test_malformed_bursts_are_refused_before_a_device_is_touched():
+    acq = cases.make("config1_small")
+    L = push_parameters(acq)
+    rf = np.ascontiguousarray(np.stack([acq.rf] * 3))
+    ptr, size = rf.ctypes.data_as(C.c_void_p), acq.rf.nbytes
+    burst = L.beamformer_hip_push_data_burst_with_compute
+    assert not burst(ptr, size, 0, 0, 0) and lib.last_error()[0] == E.BufferOverflow
+    assert not burst(ptr, size, P.HIP_MAX_BURST_FRAMES + 1, 0, 0) and lib.last_error()[0] == E.BufferOverflow
+    # the single push's checks, with its error kinds (lib/ogl_beamformer_lib.c:503-511)
+    assert not burst(ptr, size - 2, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
+    assert not burst(ptr, size + 2, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
+    assert not burst(ptr, size, 3, 7, 0) and lib.last_error()[0] == E.InvalidImagePlane
+    assert not burst(ptr, size, 3, 0, 5) and lib.last_error()[0] == E.ParameterBlockUnallocated
+    assert not burst(None, size, 3, 0, 0) and lib.last_error()[0] == E.BufferOverflow
+    assert not L.beamformer_hip_push_device_data_burst_with_compute(ptr, size - 2, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
+
+
+def test_a_burst_larger_than_the_frame_ring_is_refused_whole():
+    """1024 x 1024 complex voxels are 8 MiB a frame: 1024 of them are twice the default 4 GiB ring (one of them fits)"""
+    acq = cases.make("config1_small")
+    acq.bp.output_points[:] = [1024, 1024, 1, 1]
+    L = push_parameters(acq)
+    rf = np.zeros((1024,) + acq.rf.shape, acq.rf.dtype)
+    assert not L.beamformer_hip_push_data_burst_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 1024, 0, 0)
+    assert lib.last_error()[0] == E.FrameSizeOverflow

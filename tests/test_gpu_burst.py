@@ -1,0 +1,352 @@
+"""Bursts through the C ABI (beamformer_hip_push_data_burst_with_compute) on the device.  Frame k of a burst is judged exactly as a
+single frame is: tests/parity.py compare() against the CPU oracle's frame of RF k, with cases.tolerance -- nothing is loosened.  The
+RF frames of a burst are independent seeded noise of the case's shape and dtype.
+
+The burst kernel (csrc/das_burst.hip) takes a burst when single frames of the block run the general kernel (csrc/das_select.cpp
+decide_burst).  rca_nearest_real has three transmits and its single frames run the factored kernel: it is run under das path 1 (the
+general kernel for every frame), where the burst kernel takes it -- the nearest x real instantiation -- and on the automatic path,
+where the per-frame route must meet the same checks."""
+import ctypes as C
+import dataclasses
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+
+from ogl_beamforming_amd import configs as cfg
+from ogl_beamforming_amd import params as P
+from tests import cases, draws
+from tests.test_gpu_parity import compare, reference
+
+pytestmark = pytest.mark.gpu
+E = P.LibError
+I = P.InterpolationMode
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+BURST_KERNEL_CASES = ["config1_small", "rca_flash_none_tx", "rca_nearest_real", "rca_cubic_real", "rca_f32_complex_in", "rca_i16_complex_in",
+                      "rca_f32_demod", "rca_shuffled_padded", "rca_a1s2"]
+GENERAL_PATH_FOR = {"rca_nearest_real"}            # see the module docstring
+FALLBACK_CASES = ["forces", "hercules_wide_cw", "rca_staged_auto", "config5_literal_order"]
+# tests/draws.py draw(): the first 30 seeds whose draw is of the RCA family with at most two transmits and a non-empty image
+# (checked again in the test)
+RCA_SEEDS = [0, 6, 8, 16, 27, 36, 39, 43, 44, 54, 56, 57, 58, 59, 61, 75, 80, 81, 82, 87, 90, 91, 96, 105, 107, 115, 124, 127, 129, 134]
+
+
+def row_end_case(interp):
+    """A two-transmit RCA plane of real f32 samples whose 256-sample rows end inside the image (the deepest voxels ask for sample
+    290): it takes the burst kernel, and -- found by a scan of the depth range on the CPU -- the float oracle and its double twin
+    keep or drop a row-end term differently at one or two of its voxels (parity.py's flip set)."""
+    j = {I.Linear: 29, I.Cubic: 68}[interp]
+    return cfg.rca(f"burst_row_ends_{interp.name.lower()}", 24, 2, 256, (96, 1, 96), (-3e-3, 0, 5e-3), (3e-3, 0, 9.0e-3 + j * 37e-6),
+                   seed=900 + j, interp=interp, demodulate=False, data_kind=P.DataKind.Float32, f_number=1.0, angles=np.array([-6.0, 6.0]))
+
+
+def noise_frames(acq, n, seed):
+    rng = np.random.default_rng(seed)
+    shape = (n,) + acq.rf.shape
+    if acq.rf.dtype.kind == "i":
+        return np.clip(np.rint(rng.normal(0, 1000.0, shape)), -32000, 32000).astype(acq.rf.dtype)
+    return rng.normal(0, 1.0, shape).astype(acq.rf.dtype)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def single_push(bflib, acq, rf):
+    rf = np.ascontiguousarray(rf)
+    assert bflib.library().beamformer_push_data_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, 0, 0), bflib.last_error()
+    return bflib.get_last_frame(acq.bp).copy()
+
+
+def check_burst(bflib, oracle, acq, n, seed, expect_kernel, against_single=True):
+    """one burst of n noise frames: parity of every frame, pairwise different frames, frame k belongs to RF k, the route the library
+    reports, and every frame against the single push of the same RF.  Returns (frames, RF)."""
+    L = bflib.library()
+    rf = noise_frames(acq, n, seed)
+    described = bflib.describe_burst(acq.bp, n, acq.filters)
+    assert bool(described.burst_kernel) == expect_kernel, described.reason
+    gpu = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
+    info = bflib.last_burst_info()
+    assert info.frame_count == n and bool(info.route.burst_kernel) == expect_kernel, info.route.reason
+    assert info.route.das_launches == described.das_launches and info.route.single_path == described.single_path
+    if expect_kernel:
+        assert info.route.das_launches == 1 and info.route.frames_per_thread == 4
+    frame_info = P.HipFrameInfo()
+    assert L.beamformer_hip_get_last_frame_info(C.byref(frame_info)) and frame_info.frame_id == info.first_frame_id + n - 1
+    assert gpu.shape[0] == n
+    worst = 0.0
+    for k in range(n):
+        acq_k = dataclasses.replace(acq, rf=rf[k])
+        ref, pairs, flags = reference(oracle, acq_k)
+        v = compare(gpu[k], ref, acq_k, flags, label=f"{acq.name}/burst{n}/{k}")
+        worst = max(worst, v.max_rel_err)
+    print(f"{acq.name}: burst of {n} on the {'burst kernel' if expect_kernel else 'per-frame route'}: worst max_rel_err {worst:.3e}")
+    for a in range(n):
+        for b in range(a + 1, n):
+            assert not np.array_equal(gpu[a], gpu[b], equal_nan=True), (a, b)
+    # the order: the same frames permuted come back permuted, bit for bit (a frame's bits do not depend on its slot in the burst)
+    perm = np.random.default_rng(seed + 1).permutation(n)
+    again = bflib.beamform_burst(acq.bp, rf[perm], acq.filters)
+    for i in range(n):
+        assert same_bits(again[i], gpu[perm[i]]), f"frame {i} of the permuted burst is not the frame of RF {perm[i]}"
+    if against_single:
+        identical = 0
+        tol = cases.tolerance(acq)
+        nearest = acq.bp.interpolation_mode == int(I.Nearest)
+        for k in range(n):
+            one = single_push(bflib, acq, rf[k])
+            assert np.array_equal(np.isnan(one), np.isnan(gpu[k]))
+            ok = ~np.isnan(one)
+            scale = np.abs(one[ok]).max()
+            slack = tol * scale
+            if nearest:
+                # a tap within float rounding of k + 1/2 may fall either way in either kernel: the oracle's per-voxel budget, once each
+                flags = {}
+                oracle.beamform(acq.bp, rf[k], acq.filters, flags=flags)
+                slack = slack + 2.02 * flags["budget"][ok]
+            err = np.abs(one[ok] - gpu[k][ok])
+            assert (err <= slack).all(), f"frame {k}: burst and single push differ by {err.max() / scale:.3e} of the frame maximum"
+            identical += same_bits(one, gpu[k])
+        if expect_kernel:
+            print(f"{acq.name}: {identical} of {n} frames of the burst equal their single push bit for bit")
+    return gpu, rf
+
+
+@pytest.fixture(autouse=True)
+def automatic_path(bflib):
+    L = bflib.library()
+    L.beamformer_set_global_timeout(0xFFFFFFFF)
+    L.beamformer_hip_set_das_path(0)
+    yield
+    L.beamformer_hip_set_das_path(0)
+
+
+@pytest.mark.parametrize("n", [5, 9])
+@pytest.mark.parametrize("name", BURST_KERNEL_CASES)
+def test_burst_kernel_parity(name, n, bflib, oracle):
+    acq = cases.make(name)
+    if name in GENERAL_PATH_FOR:
+        bflib.library().beamformer_hip_set_das_path(1)
+    check_burst(bflib, oracle, acq, n, seed=4000 + n, expect_kernel=True)
+
+
+def test_three_transmit_nearest_case_on_its_automatic_route(bflib, oracle):
+    """rca_nearest_real as the selection gives it: single frames on the factored kernel, so the burst runs that kernel once per frame"""
+    check_burst(bflib, oracle, cases.make("rca_nearest_real"), 5, seed=4100, expect_kernel=False)
+
+
+@pytest.mark.parametrize("interp", [I.Linear, I.Cubic], ids=["linear", "cubic"])
+def test_rows_that_end_inside_the_image(interp, bflib, oracle):
+    """settle_index survived the restructuring: on a plane whose oracle flip set is not empty (checked first, on the CPU) every frame
+    meets compare()'s rule, the flip-set rule included"""
+    acq = row_end_case(interp)
+    n = 5
+    rf = noise_frames(acq, n, 4200)
+    flips = []
+    for k in range(n):
+        acq_k = dataclasses.replace(acq, rf=rf[k])
+        ref, _, flags = reference(oracle, acq_k)
+        v = compare(ref.copy(), ref, acq_k, flags, path=-1, label=f"{acq.name}/oracle/{k}")     # the oracle against itself: counts its flip set
+        flips.append(v.flip_voxels)
+    assert min(flips) >= 1, f"the oracle's flip set is empty on some frame: {flips}"
+    d = bflib.describe_das(acq.bp, acq.filters)[4]
+    assert int(d.row_ends) == 1
+    check_burst(bflib, oracle, acq, n, seed=4200, expect_kernel=True)
+
+
+@pytest.mark.parametrize("n", [5, 9])
+@pytest.mark.parametrize("name", FALLBACK_CASES)
+def test_fallback_parity(name, n, bflib, oracle):
+    acq = cases.make(name)
+    check_burst(bflib, oracle, acq, n, seed=4300 + n, expect_kernel=False)
+
+
+def test_bursts_and_single_pushes_interleaved_come_back_oldest_first(bflib, oracle):
+    acq = cases.make("rca_cubic_real")
+    rf = noise_frames(acq, 6, 4400)
+    L = bflib.library()
+    burst = bflib.beamform_burst(acq.bp, rf[1:4], acq.filters).copy()
+    singles = [single_push(bflib, acq, rf[k]) for k in range(6)]
+    for k in range(3):
+        assert np.abs(burst[k] - singles[1 + k]).max() <= 1e-4 * np.abs(singles[1 + k]).max()
+    # single, burst of three, single, burst of two: the union, oldest first
+    info = P.HipFrameInfo()
+    single_push(bflib, acq, rf[0])
+    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
+    first_id = info.frame_id
+    ptr = rf[1:4].ctypes.data_as(C.c_void_p)
+    assert L.beamformer_hip_push_data_burst_with_compute(ptr, rf[0].nbytes, 3, 0, 0), bflib.last_error()
+    single_push(bflib, acq, rf[4])
+    assert L.beamformer_hip_push_data_burst_with_compute(rf[4:6].ctypes.data_as(C.c_void_p), rf[0].nbytes, 2, 0, 0), bflib.last_error()
+    assert L.beamformer_hip_get_last_frame_info(C.byref(info)) and info.frame_id == first_id + 6       # consecutive ids
+    got = bflib.get_last_frames(acq.bp, 7)
+    expected = [singles[0], burst[0], burst[1], burst[2], singles[4]]
+    for k, frame in enumerate(expected):
+        assert same_bits(got[k], frame), k
+    two = bflib.beamform_burst(acq.bp, rf[4:6], acq.filters)
+    assert same_bits(got[5], two[0]) and same_bits(got[6], two[1])
+    # a burst of one IS the single push
+    assert L.beamformer_hip_push_data_burst_with_compute(rf[2:3].ctypes.data_as(C.c_void_p), rf[0].nbytes, 1, 0, 0)
+    assert same_bits(bflib.get_last_frame(acq.bp), singles[2])
+    assert not L.beamformer_hip_get_last_burst_info(C.byref(P.HipBurstInfo())) and bflib.last_error()[0] == E.InvalidAccess
+
+
+@pytest.mark.parametrize("name", ["config1_small", "rca_shuffled_padded", "forces"])
+def test_device_resident_bursts_equal_host_bursts(name, bflib):
+    import torch
+    acq = cases.make(name)
+    rf = noise_frames(acq, 5, 4500)
+    host = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
+    dev = torch.from_numpy(rf.view(np.uint8).reshape(-1)).cuda()
+    torch.cuda.synchronize()
+    device = bflib.beamform_burst(acq.bp, rf, acq.filters, on_device_pointer=dev.data_ptr())
+    for k in range(5):
+        assert same_bits(host[k], device[k]), k
+
+
+def test_a_burst_that_wraps_the_ring_stays_exportable():
+    """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/burst_wrap_worker.py"""
+    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "burst_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "wrapped" in run.stdout, run.stdout
+
+
+def test_timings_of_a_burst_are_per_frame_shares(bflib):
+    L = bflib.library()
+    acq = cases.make("config1_small")
+    n = 8
+    bflib.beamform_burst(acq.bp, noise_frames(acq, n, 4600), acq.filters)
+    info = bflib.last_burst_info()
+    table = P.ComputeStatsTable()
+    assert L.beamformer_compute_timings(C.byref(table), -1)
+    stages = [(int(info.stage_kind[i]), float(info.stage_ms[i])) for i in range(info.stage_count)]
+    assert stages[0][0] == 0xFFFF and stages[-1][0] == int(P.ShaderKind.DAS)
+    planned = [s for s in stages if s[0] not in (0xFFFF, 0xFFFE)]
+    assert table.shader_count == len(planned)
+    for col, (kind, ms) in enumerate(planned):
+        assert table.shader_ids[col] == kind
+        total = sum(table.times[(info.first_frame_id + k) % 32][col] for k in range(n))
+        assert ms > 0 and abs(total - ms * 1e-3) <= 1e-5 * ms * 1e-3 + 1e-12, (kind, total, ms)
+    t = P.HipFrameTimings()
+    assert L.beamformer_hip_get_last_frame_timings(C.byref(t))
+    assert t.das_voxels == acq.voxels and t.das_path == 0 and t.das_taps == 2
+    assert abs(t.frame_ms * n - info.burst_ms) <= 1e-5 * info.burst_ms
+    # pair counting: the geometry-only count runs once; the newest frame reports what a single push reports
+    try:
+        L.beamformer_hip_enable_pair_counting(1)
+        rf = noise_frames(acq, 3, 4601)
+        bflib.beamform_burst(acq.bp, rf, acq.filters)
+        assert L.beamformer_hip_get_last_frame_timings(C.byref(t))
+        burst_pairs = int(t.das_pairs)
+        single_push(bflib, acq, rf[0])
+        assert L.beamformer_hip_get_last_frame_timings(C.byref(t))
+        assert burst_pairs == int(t.das_pairs) > 0
+    finally:
+        L.beamformer_hip_enable_pair_counting(0)
+
+
+def test_an_output_shard_is_honoured(bflib):
+    L = bflib.library()
+    acq = cases.make("rca_vls_cw")                       # 12 x 10 x 14
+    rf = noise_frames(acq, 3, 4650)
+    whole = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
+    try:
+        assert L.beamformer_hip_set_output_shard(0, 4, 6)
+        assert L.beamformer_hip_push_data_burst_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 3, 0, 0), bflib.last_error()
+        part = bflib.get_last_frames(acq.bp, 3, shard_planes=6)
+    finally:
+        assert L.beamformer_hip_set_output_shard(0, 0, 0)
+    for k in range(3):
+        assert same_bits(part[k], np.ascontiguousarray(whole[k][4:10])), k
+
+
+def test_several_devices_refuse_a_burst_and_frame_graphs_change_nothing(bflib, capfd):
+    L = bflib.library()
+    acq = cases.make("config1_small")
+    rf = noise_frames(acq, 5, 4700)
+    plain = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
+    try:
+        L.beamformer_hip_enable_frame_graphs(1)
+        for _ in range(2):            # (a plan's first frame never runs from a graph)
+            graphs = bflib.beamform_burst(acq.bp, rf, acq.filters)
+        for k in range(5):
+            assert same_bits(plain[k], graphs[k]), k
+    finally:
+        L.beamformer_hip_enable_frame_graphs(0)
+    try:
+        L.beamformer_hip_shutdown()
+        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
+        assert L.beamformer_push_simple_parameters(C.byref(acq.bp))
+        capfd.readouterr()
+        assert not L.beamformer_hip_push_data_burst_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 5, 0, 0)
+        assert bflib.last_error()[0] == E.InvalidAccess
+        assert "one device" in capfd.readouterr().err
+    finally:
+        L.beamformer_hip_shutdown()
+        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
+    again = bflib.beamform_burst(acq.bp, rf, acq.filters)
+    for k in range(5):
+        assert same_bits(plain[k], again[k]), k
+
+
+@pytest.mark.parametrize("seed", RCA_SEEDS)
+def test_random_rca_draws(seed, bflib, oracle, hooks):
+    """draws of the general generator with at most two transmits, N drawn from {2, 3, 5, 8, 9}: on the route the automatic selection
+    gives the draw, and on the burst kernel (das path 1: the general kernel for single frames) where that is another one.  Every third
+    draw runs with SCRATCH_POISON: a frame that read another frame's slice, or an element nobody wrote, shows as NaN."""
+    acq = draws.draw(seed)
+    K = P.AcquisitionKind
+    assert K(acq.bp.acquisition_kind) in (K.RCA_TPW, K.RCA_VLS, K.Flash) and acq.bp.acquisition_count <= 2
+    n = int(np.random.default_rng(7000 + seed).choice([2, 3, 5, 8, 9]))
+    if seed % 3 == 0:
+        hooks.set("SCRATCH_POISON")
+    automatic = bool(bflib.describe_burst(acq.bp, n, acq.filters).burst_kernel)
+    check_burst(bflib, oracle, acq, n, seed=7100 + seed, expect_kernel=automatic, against_single=False)
+    if not automatic:
+        bflib.library().beamformer_hip_set_das_path(1)
+        takes = bool(bflib.describe_burst(acq.bp, n, acq.filters).burst_kernel)        # (not below kBurstMinFrames)
+        assert takes == (n >= bflib.describe_burst(acq.bp, n, acq.filters).min_frames)
+        check_burst(bflib, oracle, acq, n, seed=7100 + seed, expect_kernel=takes, against_single=False)
+
+
+def test_a_burst_of_64_full_size_frames_is_not_slower_than_64_single_pushes(bflib):
+    """config 1 at full size, wall time fence to fence with the upload, median of 5 after a warm-up of each: the single path is
+    the parent commit's code, and the bar is "not slower" """
+    L = bflib.library()
+    acq = cfg.config(1)
+    n = 64
+    rf = noise_frames(acq, n, 4800)
+    ptr, size = rf.ctypes.data_as(C.c_void_p), rf[0].nbytes
+    frames = [rf[k].ctypes.data_as(C.c_void_p) for k in range(n)]
+    bflib.beamform_burst(acq.bp, rf[:2], acq.filters)                  # parameters, plan, buffers
+
+    def singles():
+        for p in frames:
+            assert L.beamformer_push_data_with_compute(p, size, 0, 0)
+        assert L.beamformer_hip_synchronize()
+
+    def burst():
+        assert L.beamformer_hip_push_data_burst_with_compute(ptr, size, n, 0, 0)
+        assert L.beamformer_hip_synchronize()
+
+    def median_seconds(run):
+        run(); run()
+        times = []
+        for _ in range(5):
+            assert L.beamformer_hip_synchronize()
+            t0 = time.perf_counter()
+            run()
+            times.append(time.perf_counter() - t0)
+        return statistics.median(times)
+
+    single_s, burst_s = median_seconds(singles), median_seconds(burst)
+    info = bflib.last_burst_info()
+    assert info.route.burst_kernel == 1
+    print(f"rate: 64 config-1 frames: singles {single_s / n * 1e6:.1f} us/frame, burst {burst_s / n * 1e6:.1f} us/frame, ratio {burst_s / single_s:.3f}")
+    assert burst_s <= single_s, f"one burst of 64 took {burst_s * 1e3:.3f} ms, 64 single pushes {single_s * 1e3:.3f} ms"
