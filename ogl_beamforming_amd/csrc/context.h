@@ -34,7 +34,7 @@ struct FrameRecord {
 	int      data_kind = BeamformerDataKind_Float32;
 	uint32_t id = 0, block = 0;
 	int      timing_slot = -1;
-	bool     failed = false;         /* tombstone of a push that did not complete (executor.cpp, Lockstep) */
+	bool     failed = false;         /* tombstone of a push that did not complete (executor.cpp, Tombstones) */
 };
 
 /* one RF frame in flight on the upload side (beamformer_rf_upload's slot, beamformer_core.c:1756-1805) */
@@ -121,7 +121,7 @@ struct Device {
 	DeviceBuffer staged_tables;        /* das_staged.hip, wave-uniform transmit tables (bf_launch_das_staged_tables) */
 	DeviceBuffer staged_violations;    /* das_staged*.hip: one counter per timing slot of window positions outside the staged window */
 	DeviceBuffer hercules_table;                               /* das_hercules.hip: per-row lateral table, rebuilt per launch */
-	/* multi-device frames (executor.cpp push_multi): the RF of slot k landed on this device / the frame
+	/* multi-device frames (executor.cpp run_peers): the RF of slot k landed on this device / the frame
 	 * that read slot k has finished */
 	hipStream_t  peer_stream = nullptr;                        /* carries the copies INTO this device */
 	hipEvent_t   rf_landed[BeamformerMaxRawDataFramesInFlight]{}, rf_consumed[BeamformerMaxRawDataFramesInFlight]{};

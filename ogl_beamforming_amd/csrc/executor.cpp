@@ -9,7 +9,7 @@
  *                                                                stream order, one pass over
  *                                                                all channels
  *   complete_queue / Export     (beamformer_core.c:1468-1509)  -> export_last_frames
- *   beamformer_frame_next       (beamformer_core.c:440-466)    -> next_frame
+ *   beamformer_frame_next       (beamformer_core.c:440-466)    -> next_frames
  *   gpu_command_timestamp + coalesce_timing_table
  *                               (beamformer_core.c:1611-1655, :1683-1747) -> HIP event pairs
  * There is no CPU fallback: without a HIP device every entry point fails with
@@ -225,7 +225,7 @@ static PlanState *commit_block(uint32_t block)
 	ParameterBlock &pb = c.blocks[block];
 	PlanState &ps = d.plans[block];
 	if (ps.valid && !pb.dirty) return &ps;
-	/* with several devices every one of them replans: the change reaches them through push_multi,
+	/* with several devices every one of them replans: the change reaches them through push_rf_and_compute,
 	 * which commits the ingest device LAST -- only that commit clears the dirty bits */
 	const bool clears_dirty = c.device_count == 1 || d.index == 0;
 
@@ -295,40 +295,28 @@ static PlanState *commit_block(uint32_t block)
 	return &ps;
 }
 
-/* beamformer_frame_next (beamformer_core.c:440-466) */
-static FrameRecord *next_frame(const uint32_t points[3], bool complex_frame, uint32_t block)
-{
-	Context &c = g_context;
-	Device  &d = *c.cur;
-	int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
-	uint64_t bytes = round_up((uint64_t)points[0] * points[1] * points[2] * (uint64_t)bf_kind_byte_size[kind], 64);
-	if (bytes > d.ring.size) return nullptr;
-	if (d.ring_next_offset > d.ring.size - bytes) d.ring_next_offset = 0;
-	uint64_t id = d.frame_counter++;
-	FrameRecord *f = &d.frames[id % d.frames.size()];
-	/* records whose storage this frame reuses stop being exportable */
-	for (FrameRecord &old : d.frames)
-		if (old.bytes && old.offset < d.ring_next_offset + bytes && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
-	f->offset = d.ring_next_offset; f->bytes = bytes;
-	f->points[0] = points[0]; f->points[1] = points[1]; f->points[2] = points[2];
-	f->data_kind = kind; f->id = (uint32_t)id; f->block = block; f->failed = false;
-	d.ring_next_offset += bytes;
-	return f;
-}
-
-/* `count` frames of one size, contiguous in the ring: a run that would straddle the end starts again at offset 0; the records it
- * overwrites stop being exportable, as in next_frame.  Returns the first, or null when the run does not fit the ring. */
-static FrameRecord *next_burst_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count)
+/* beamformer_frame_next (beamformer_core.c:440-466), for `count` frames of one size (a single push: one), contiguous in the ring: a run
+ * that would straddle the end starts again at offset 0; the records it overwrites stop being exportable.  Consecutive ids, each frame's
+ * timing slot named in its record.  Returns the first, or null when the run does not fit the ring. */
+static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count)
 {
 	Device &d = *g_context.cur;
-	const uint64_t bytes = round_up((uint64_t)points[0] * points[1] * points[2] * (complex_frame ? 8u : 4u), 64);
+	const int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
+	const uint64_t bytes = round_up((uint64_t)points[0] * points[1] * points[2] * (uint64_t)bf_kind_byte_size[kind], 64);
 	if (count == 0 || bytes > d.ring.size / count) return nullptr;
 	if (d.ring_next_offset > d.ring.size - bytes * count) d.ring_next_offset = 0;
 	FrameRecord *first = nullptr;
 	for (uint32_t k = 0; k < count; k++) {
-		FrameRecord *f = next_frame(points, complex_frame, block);
-		if (!f) return nullptr;
-		f->timing_slot = (int)(f->id % kTimingSlots);
+		uint64_t id = d.frame_counter++;
+		FrameRecord *f = &d.frames[id % d.frames.size()];
+		/* records whose storage this frame reuses stop being exportable */
+		for (FrameRecord &old : d.frames)
+			if (old.bytes && old.offset < d.ring_next_offset + bytes && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
+		f->offset = d.ring_next_offset; f->bytes = bytes;
+		f->points[0] = points[0]; f->points[1] = points[1]; f->points[2] = points[2];
+		f->data_kind = kind; f->id = (uint32_t)id; f->block = block; f->failed = false;
+		f->timing_slot = (int)(id % kTimingSlots);
+		d.ring_next_offset += bytes;
 		if (k == 0) first = f;
 	}
 	return first;
@@ -341,11 +329,32 @@ static FrameRecord *next_burst_frames(const uint32_t points[3], bool complex_fra
  * at all and report the newest sampled timings in the stats table. */
 constexpr uint64_t kTimingSamplePeriod = 8;
 constexpr uint64_t kSmallFrameBytes    = 8ull << 20;
+/* A copy-engine transfer and each cross-queue dependency cost 40-60 us of latency on this runtime (tools/h2d_probe.cpp: 0.26 MB pinned
+ * H2D + a kernel = 114 us per frame), more than a small frame's compute, so host uploads (a single frame's, a whole burst's) under
+ * kOverlapBytes skip the copy engine: the ingest kernel reads the pinned slot in place over PCIe, in order on the compute stream. */
+constexpr uint64_t kOverlapBytes       = 8ull << 20;
+
+static bool ensure_events(TimingSlot &t)
+{
+	if (t.created) return true;
+	for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
+	t.created = true;
+	return true;
+}
 
 static bool record(TimingSlot &t, uint32_t index, hipStream_t s)
 {
 	if (!t.sampled) return true;
 	return HIP_OK(hipEventRecord(t.events[index], s));
+}
+
+/* segment k of a slot's timings is bracketed by events[k] and events[k+1]: closes the one that ran since the last record as `kind` */
+static void segment(TimingSlot &t, uint32_t kind, hipStream_t s)
+{
+	if (t.count < BEAMFORMER_HIP_MAX_TIMED_STAGES) {
+		t.kinds[t.count++] = kind;
+		record(t, t.count, s);
+	}
 }
 
 static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, bool ingest_timed);
@@ -445,6 +454,14 @@ static std::vector<DasDecision> &frame_das_parts(PlanState *ps, const ParameterB
 	return parts;
 }
 
+/* the plan's device tables, which every DAS launch reads */
+static void bind_tables(const PlanState *ps, BfDasArgs &a)
+{
+	a.transmits       = (const BfTransmit *)ps->transmits.ptr;
+	a.sparse_elements = (const int16_t *)ps->sparse.ptr;
+	a.readi_hadamard  = (const uint16_t *)ps->readi_hadamard.ptr;
+}
+
 /* One part of one frame's DAS stage (das_select.h: a frame is one part unless the row-end rule cut it): the kernel `dd` names on the DAS
  * input `cur`, writing the part's planes at `out`.  part_path: the kernel that ran where a missing buffer sent the part to another one. */
 static bool launch_das_part(PlanState *ps, const DasDecision &dd, const void *cur, void *out, uint64_t out_bytes, uint32_t *frame_counters,
@@ -455,9 +472,7 @@ static bool launch_das_part(PlanState *ps, const DasDecision &dd, const void *cu
 	BfDasArgs a = dd.a;
 	a.rf  = cur;
 	a.out = out;
-	a.transmits       = (const BfTransmit *)ps->transmits.ptr;
-	a.sparse_elements = (const int16_t *)ps->sparse.ptr;
-	a.readi_hadamard  = (const uint16_t *)ps->readi_hadamard.ptr;
+	bind_tables(ps, a);
 
 	if (dd.path == DasPath_Zero) {
 		ok &= HIP_OK(hipMemsetAsync(a.out, 0, out_bytes, s));
@@ -551,10 +566,7 @@ static bool run_frame(uint32_t block, const void *rf, int64_t rf_bytes, bool ing
 	hipStream_t s = d.stream;
 	TimingSlot &t = d.timing[d.frame_counter % kTimingSlots];
 	t.failed = false;
-	if (!t.created) {
-		for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
-		t.created = true;
-	}
+	if (!ensure_events(t)) return false;
 	const bool sampled = t.sampled;
 	const uint32_t first = ingest_timed ? 1u : 0u;          /* events[0] -> events[1] is the caller's ingest segment */
 	if (sampled && !HIP_OK(hipEventRecord(t.events[first], s))) return set_error(BeamformerLibErrorKind_InvalidAccess);
@@ -588,152 +600,194 @@ static bool run_frame(uint32_t block, const void *rf, int64_t rf_bytes, bool ing
 	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
 }
 
-static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, bool ingest_timed)
+/* All parts of one frame's DAS stage: the frame's DAS input at `cur`, its ring slot at `out`.  head_path: the kernel that ran the main part. */
+static bool launch_frame_parts(PlanState *ps, const std::vector<DasDecision> &parts, uint32_t zfirst, uint64_t plane_bytes, const void *cur, char *out,
+                               uint32_t *frame_counters, hipStream_t s, uint32_t &head_path)
+{
+	const DasDecision &head = main_part(parts);
+	bool ok = true;
+	for (const DasDecision &dd : parts) {
+		uint32_t part_path = (uint32_t)dd.path;
+		ok &= launch_das_part(ps, dd, cur, out + (uint64_t)(dd.z_first - zfirst) * plane_bytes, dd.z_count * plane_bytes, frame_counters, s, part_path);
+		if (&dd == &head && dd.path != DasPath_Zero) head_path = part_path;
+	}
+	return ok;
+}
+
+/* The DAS fields of a frame's row of the timing table; parts == null: no DAS kernel ran for the frame (no DAS stage, an empty slab). */
+static void fill_das_fields(TimingSlot &t, uint64_t id, const std::vector<DasDecision> *parts, const uint32_t points[3], bool iq, uint32_t das_path,
+                            uint64_t violations_slot)
+{
+	const uint32_t interpolation = parts ? main_part(*parts).a.interpolation : 0;
+	t.frame_id = id;
+	t.das_voxels = parts ? (uint64_t)points[0] * points[1] * points[2] : 0;
+	t.das_taps = !parts ? 0 : interpolation == 0 ? 1 : interpolation == 1 ? 2 : 4;
+	t.das_sample_bytes = !parts ? 0 : iq ? 8 : 4;
+	t.das_path = parts ? das_path : 0;
+	t.das_row_end_planes = parts ? row_end_planes(*parts) : 0;
+	t.violations_slot = violations_slot;
+}
+
+/* What a walk over a plan runs on: `frames` frames, frame k of every buffer k * that buffer's stride further on (one frame: stride 0). */
+struct StageWalk {
+	uint32_t      frames;
+	const void   *in;               /* the first stage's input, and what it may read of a frame there */
+	uint64_t      in_stride;
+	int64_t       in_bound;
+	DeviceBuffer *stage;            /* the ping-pong pair the pre-DAS stages write */
+	uint64_t      stage_stride;     /* 0: a stage may read its predecessor's whole buffer; else its frame's stride */
+	TimingSlot   &t;                /* owns the events; its ingest segment (or events[0]) is already recorded */
+	const BurstDecision *route;     /* a burst's DAS route (das_select.h); null: a single push */
+};
+
+/* The stages of a plan over the frames of one push, in stream order: every pre-DAS stage ONE launch for all frames (launch_stage), then the
+ * frames placed in the ring and the DAS stage -- a burst's kernel in one launch where its route says so, else each frame's own launch(es)
+ * on its slice of the input -- with one timing segment per stage in w.t and the DAS fields of every frame's timing row. */
+static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
 	const Plan &plan = ps->plan;
 	const ParameterBlock &pb = c.blocks[block];
-	const BeamformerParameters &bp = pb.parameters;
 	hipStream_t s = d.stream;
+	TimingSlot &t = w.t;
+	const uint32_t N = w.frames;
 
-	TimingSlot &t = d.timing[d.frame_counter % kTimingSlots];
-	t.failed = false; t.share = 1;
-	if (!t.created) {
-		for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
-		t.created = true;
-	}
-	/* segment k of the frame is bracketed by events[k] and events[k+1]; events[0] was recorded
-	 * in front of the ingest by the caller when ingest_timed */
-	t.count = 0; t.counted = false;
-	auto segment = [&](uint32_t kind) {
-		if (t.count < BEAMFORMER_HIP_MAX_TIMED_STAGES) {
-			t.kinds[t.count++] = kind;
-			record(t, t.count, s);
-		}
-	};
-	if (ingest_timed) segment(kStageIngest);
-	else              record(t, 0, s);
-
-	const uint32_t C = plan.channels, A = plan.acquisitions, Sd = plan.das_samples;
-	const void *cur = rf;
-	int64_t cur_elements_bytes = rf_bytes;
+	const char *cur = (const char *)w.in;
+	uint64_t cur_stride = w.in_stride;
+	int64_t  cur_bound = w.in_bound;
 	int toggle = 0;
-	bool ok = true, das_segment_done = false;
-	uint32_t das_path = 0;
+	bool ok = true;
 	d.das_input = nullptr; d.das_input_bytes = 0;
 
-	/* hook SCRATCH_POISON: both intermediate buffers, and below the frame's ring slot once next_frame has placed it (nothing writes
-	 * it before the DAS stage), are filled with 0xFF bytes -- NaN in binary16 and in f32 -- so that an element a stage reads without
-	 * this frame having written it shows up as NaN.  Unset: no memset, no launch. */
+	uint32_t zfirst = 0, zcount = plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	if (c.device_count > 1) { zfirst = d.slab_first; zcount = d.slab_count; }   /* this device's z-slab (run_peers) */
+	uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
+	const uint64_t voxel_bytes = plan.iq_pipeline ? 8u : 4u;
+	const uint64_t first = d.frame_counter;                 /* the id of the walk's first frame */
+	const std::vector<DasDecision> *ran = nullptr;          /* the parts of the DAS stage, once it has run */
+	uint32_t das_path = 0;
+	bool counters_kept = false;
+
+	/* hook SCRATCH_POISON: both intermediate buffers, and below the frames' ring slots once next_frames has placed them (nothing writes
+	 * them before the DAS stage), are filled with 0xFF bytes -- NaN in binary16 and in f32 -- so that an element a stage reads without
+	 * this push having written it shows up as NaN.  Unset: no memset, no launch. */
 	const bool poison = hooks().scratch_poison;
 	if (poison)
-		for (DeviceBuffer &b : d.scratch)
-			if (b.ptr) ok &= HIP_OK(hipMemsetAsync(b.ptr, 0xFF, b.size, s));
+		for (int k = 0; k < 2; k++)
+			if (w.stage[k].ptr) ok &= HIP_OK(hipMemsetAsync(w.stage[k].ptr, 0xFF, w.stage[k].size, s));
 
 	for (size_t i = 0; i < plan.stages.size() && ok; i++) {
 		const Stage &st = plan.stages[i];
+		bool das_segment_done = false;
 		switch (st.kind) {
 		case BeamformerShaderKind_Reshape:
 		case BeamformerShaderKind_Decode:
 		case BeamformerShaderKind_Hilbert:
 		case BeamformerShaderKind_Filter:
-		case BeamformerShaderKind_Demodulate:
-			ok &= launch_stage(ps, bp, i, cur, cur_elements_bytes, d.scratch[toggle].ptr, s);
-			cur = d.scratch[toggle].ptr; cur_elements_bytes = (int64_t)d.scratch[toggle].size; toggle ^= 1;
-			break;
+		case BeamformerShaderKind_Demodulate:{
+			DeviceBuffer &out = w.stage[toggle];
+			ok &= launch_stage(ps, pb.parameters, i, cur, cur_bound, out.ptr, s, N, cur_stride, w.stage_stride);
+			cur = (const char *)out.ptr; cur_stride = w.stage_stride; cur_bound = (int64_t)(w.stage_stride ? w.stage_stride : out.size); toggle ^= 1;
+		}break;
 		case BeamformerShaderKind_DAS:{
-			uint32_t zfirst = 0, zcount = plan.output_points[2];
-			if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-			if (c.device_count > 1) { zfirst = d.slab_first; zcount = d.slab_count; }   /* this device's z-slab (push_multi) */
-			uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
-			FrameRecord *f = next_frame(points, plan.iq_pipeline, block);
-			if (!f) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-			f->timing_slot = (int)(f->id % kTimingSlots);
-			if (poison && f->bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + f->offset, 0xFF, f->bytes, s));
-			d.das_input = cur; d.das_input_bytes = (uint64_t)Sd * A * C * (plan.iq_pipeline ? 8u : 4u);   /* [channel][transmit][sample] */
-			if (zcount == 0) {           /* more devices than planes: this device holds an empty slab of the frame */
-				t.das_voxels = 0; t.das_taps = 0; t.das_sample_bytes = 0; t.das_path = 0; t.frame_id = f->id;
-				break;
+			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, N);
+			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+			char *out0 = (char *)d.ring.ptr + frame0->offset;
+			const uint64_t frame_bytes = frame0->bytes;
+			if (poison && frame_bytes) ok &= HIP_OK(hipMemsetAsync(out0, 0xFF, frame_bytes * N, s));
+			if (!w.route) {              /* (beamformer_hip_copy_das_input serves single frames) */
+				d.das_input = cur; d.das_input_bytes = (uint64_t)plan.das_samples * plan.acquisitions * plan.channels * voxel_bytes;   /* [channel][transmit][sample] */
 			}
+			if (zcount == 0) break;      /* more devices than planes: this device holds an empty slab of the frame */
 
 			/* which kernel, with which geometry: one table of rules (das_select.cpp), computed once per plan / shard / path mode / hook
 			 * change and reused by every frame after it.  Usually ONE launch; where a term of the frame can reach an end of its RF row
 			 * the z range is cut and the planes concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
-			std::vector<DasDecision> &parts = frame_das_parts(ps, pb, zfirst, zcount);
+			const std::vector<DasDecision> &parts = frame_das_parts(ps, pb, zfirst, zcount);
 			const DasDecision &head = main_part(parts);
-			const uint32_t ext[3] = {head.a.size[0], head.a.size[1], zcount};
+			ran = &parts;
 			das_path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
-			uint64_t violations_slot = ~0ull;
-			uint32_t *frame_counters = nullptr;        /* [0] staged window violations, [1] / [2] das_tile.hip's staged / gathered chunks */
-			for (const DasDecision &dd : parts)
-				if (dd.path == DasPath_Staged || dd.path == DasPath_Tile) {
-					if (d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) {
-						frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * (f->id % kTimingSlots);
+			const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes;
+			if (w.route && w.route->burst_kernel) {
+				BfDasArgs a = w.route->a;
+				a.rf = cur; a.out = out0;
+				bind_tables(ps, a);
+				BfBurstArgs b{};
+				b.frame_count = N; b.rf_stride = cur_stride; b.out_stride = frame_bytes;
+				ok &= HIP_OK(bf_launch_das_burst(&a, &b, s));
+			} else {
+				/* [0] staged window violations, [1] / [2] das_tile.hip's staged / gathered chunks: one set per timing slot */
+				for (const DasDecision &dd : parts) counters_kept |= dd.path == DasPath_Staged || dd.path == DasPath_Tile;
+				if (counters_kept && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) ok = false;
+				for (uint32_t k = 0; k < N && ok; k++) {
+					uint32_t *frame_counters = nullptr;
+					if (counters_kept && N - k <= kTimingSlots) {        /* the table keeps the newest 32 frames: older ones of a long burst count nothing */
+						frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
 						ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
-						violations_slot = f->id % kTimingSlots;
-					} else ok = false;
-					break;
+					}
+					ok &= launch_frame_parts(ps, parts, zfirst, plane_bytes, cur + k * cur_stride, out0 + k * frame_bytes, frame_counters, s, das_path);
 				}
-			if (c.count_pairs) {
-				ok &= d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2));
-				if (ok) ok &= HIP_OK(hipMemsetAsync((unsigned long long *)d.pair_counter.ptr + (f->id % kTimingSlots), 0, sizeof(unsigned long long), s));
-			}
-			const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * (plan.iq_pipeline ? 8u : 4u);
-
-			for (const DasDecision &dd : parts) {
-			uint32_t part_path = (uint32_t)dd.path;
-			ok &= launch_das_part(ps, dd, cur, (char *)d.ring.ptr + f->offset + (uint64_t)(dd.z_first - zfirst) * plane_bytes, dd.z_count * plane_bytes,
-			                      frame_counters, s, part_path);
-			if (&dd == &head && dd.path != DasPath_Zero) das_path = part_path;
 			}
 			if (c.count_pairs && head.path != DasPath_Zero) {
-				/* geometry-only recount of the apodization test; its own segment so that it
-				 * stays out of the DAS time */
-				segment((uint32_t)st.kind);
+				/* geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is the
+				 * same for every frame of the walk: it runs once, into the last frame's counter, and the other frames' counters are copies */
+				segment(t, (uint32_t)st.kind, s);
+				ok &= d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2));
+				unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
+				unsigned long long *mine = counters + (first + N - 1) % kTimingSlots;
+				if (ok) ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
 				for (const DasDecision &dd : parts) {
+					if (!ok) break;
 					BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
-					count.rf = cur; count.out = (char *)d.ring.ptr + f->offset + (uint64_t)(dd.z_first - zfirst) * plane_bytes;
-					count.transmits = (const BfTransmit *)ps->transmits.ptr; count.sparse_elements = (const int16_t *)ps->sparse.ptr;
-					count.readi_hadamard = (const uint16_t *)ps->readi_hadamard.ptr;
-					count.pair_counter = (unsigned long long *)d.pair_counter.ptr + (f->id % kTimingSlots);
+					count.rf = cur; count.out = out0 + (uint64_t)(dd.z_first - zfirst) * plane_bytes;
+					bind_tables(ps, count);
+					count.pair_counter = mine;
 					ok &= HIP_OK(bf_launch_das_count(&count, s));
 				}
-				segment(kStagePairCount);
+				for (uint32_t k = 0; k + 1 < N && k + 1 < kTimingSlots && ok; k++)
+					ok &= HIP_OK(hipMemcpyAsync(counters + (first + N - 2 - k) % kTimingSlots, mine, sizeof(*mine), hipMemcpyDeviceToDevice, s));
+				segment(t, kStagePairCount, s);
 				t.counted = true;
 				das_segment_done = true;
 			}
-			const BfDasArgs &a = head.a;
-			t.das_row_end_planes = row_end_planes(parts);
-			t.das_voxels = (uint64_t)ext[0] * ext[1] * ext[2];
-			t.das_taps = a.interpolation == 0 ? 1 : a.interpolation == 1 ? 2 : 4;
-			t.das_sample_bytes = plan.iq_pipeline ? 8 : 4;
-			t.das_path = das_path; t.frame_id = f->id;
-			t.violations_slot = violations_slot;
 		}break;
-		case BeamformerShaderKind_CoherencyWeighting:
-			/* fused into the DAS epilogue (das.hip); kept in the plan so that the stage list a
-			 * client sees through beamformer_compute_timings matches the reference's */
-			break;
-		default: break;
+		default: break;      /* CoherencyWeighting: fused into the DAS epilogue (das.hip); kept in the plan so that the stage list a client
+		                      * sees through beamformer_compute_timings matches the reference's */
 		}
-		if (!(st.kind == BeamformerShaderKind_DAS && das_segment_done)) segment((uint32_t)st.kind);
+		if (!das_segment_done) segment(t, (uint32_t)st.kind, s);
 	}
 	if (plan.das_index < 0 && ok) {
-		/* no DAS in the pipeline: the frame exists and stays zero (the reference clears it,
-		 * beamformer_core.c:1573-1585, and nothing writes it) */
-		/* (several devices: the ingest device holds the whole zero frame, the others an empty slab of it) */
-		uint32_t points[3] = {plan.output_points[0], plan.output_points[1], c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2]};
-		FrameRecord *f = next_frame(points, plan.iq_pipeline, block);
-		if (!f) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-		f->timing_slot = (int)(f->id % kTimingSlots);
-		if (f->bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + f->offset, 0, f->bytes, s));
-		t.das_voxels = 0; t.das_taps = 0; t.das_sample_bytes = 0; t.das_path = 0; t.frame_id = f->id;
+		/* no DAS in the pipeline: the frames exist and stay zero (the reference clears them, beamformer_core.c:1573-1585, and nothing
+		 * writes them).  A single push's frame is the block's whole grid whatever its shard -- with several devices on the ingest device,
+		 * the others holding an empty slab of it; a burst's frames are the shard's planes */
+		if (!w.route) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
+		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, N);
+		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+		if (frame0->bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, frame0->bytes * N, s));
 	}
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	for (uint32_t k = 0; k < N; k++)
+		fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, ran, points, plan.iq_pipeline, das_path,
+		                counters_kept && N - k <= kTimingSlots ? (first + k) % kTimingSlots : ~0ull);
 	return true;
+}
+
+/* One frame of a single push: the walk over d.scratch[], timed in the frame's own slot. */
+static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, bool ingest_timed)
+{
+	Device &d = *g_context.cur;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	TimingSlot &t = d.timing[d.frame_counter % kTimingSlots];
+	t.failed = false; t.share = 1;
+	if (!ensure_events(t)) return false;
+	/* events[0] was recorded in front of the ingest by the caller when ingest_timed */
+	t.count = 0; t.counted = false;
+	if (ingest_timed) segment(t, kStageIngest, d.stream);
+	else              record(t, 0, d.stream);
+	return walk_plan(block, ps, StageWalk{1, rf, 0, rf_bytes, d.scratch, 0, t, nullptr});
 }
 
 /* z-slab of device `i` of `n` over `planes` planes starting at `first`: contiguous, sizes differing by
@@ -820,6 +874,129 @@ static void copy_to_pinned(void *pinned, const void *data, size_t size)
 	for (auto &w : workers) w.join();
 }
 
+/* How a push's RF lies in the caller's buffer (rows of in_row bytes, one per raw channel) and in the RF ring (rows of out_row bytes, one
+ * per mapped channel; rf_size per frame). */
+struct RfLayout {
+	uint64_t in_row, out_row, rf_size;
+	bool     a1s2, identity;        /* identity: channel_mapping[ch] == ch for every channel */
+};
+
+static bool rf_layout(const ParameterBlock &pb, RfLayout &l)
+{
+	const BeamformerParameters &bp = pb.parameters;
+	const uint64_t bytes = (uint64_t)bf_kind_byte_size[pb.data_kind];
+	l.out_row = bytes * bp.sample_count * bp.acquisition_count;
+	l.in_row  = bytes * bp.raw_data_dimensions[0];
+	l.rf_size = l.out_row * bp.channel_count;
+	/* the reference copies whatever row the mapping names (lib .c:520-528); on a GPU an
+	 * out-of-range row would fault, so it is an error here */
+	l.identity = true;
+	for (uint32_t ch = 0; ch < bp.channel_count; ch++) {
+		uint16_t row = (uint16_t)pb.channel_mapping[ch];
+		if (row >= bp.raw_data_dimensions[1]) return set_error(BeamformerLibErrorKind_DataSizeMismatch);
+		l.identity &= row == ch;
+	}
+	l.a1s2 = bp.contrast_mode == BeamformerContrastMode_A1S2;
+	return true;
+}
+
+/* The ingest kernel: `frames` raw frames at `raw` into the mapped layout at `out`, frame k at k * the frame strides (one frame: 0). */
+static bool launch_ingest(PlanState *ps, const ParameterBlock &pb, const RfLayout &l, const void *raw, void *out, uint32_t frames,
+                          uint64_t in_frame_bytes, uint64_t out_frame_bytes, hipStream_t s)
+{
+	BfIngestArgs a{};
+	a.raw = raw; a.out = out;
+	a.channel_mapping = (const int16_t *)ps->mapping.ptr;
+	a.in_row_bytes = l.in_row; a.out_row_bytes = l.out_row; a.channels = pb.parameters.channel_count;
+	a.a1s2 = l.a1s2; a.base = bf_kind_base[pb.data_kind];
+	a.a1s2_scalars = pb.parameters.sample_count * (uint32_t)bf_kind_element_count[pb.data_kind];
+	a.frames = frames; a.in_frame_bytes = in_frame_bytes; a.out_frame_bytes = out_frame_bytes;
+	return HIP_OK(bf_launch_ingest(&a, s));
+}
+
+/* The upload of a push's host bytes, in the three steps a burst needs apart (it grows every buffer before it takes its ids):
+ *   claim_upload     the slot's events exist and -- host data -- its pinned memory is free and large enough;
+ *   enqueue_upload   the caller's bytes are copied into the pinned slot (after which the caller may reuse its buffer, as with the
+ *                    reference's copy into shared memory).  With a device destination the H2D runs on the copy stream and the compute
+ *                    stream waits for it -- so the upload of push n+1 overlaps the kernels of push n, which one stream and pageable
+ *                    memory cannot do; without one (uploads under kOverlapBytes) the first kernel reads the pinned slot in place.
+ *                    Returns what that kernel reads, or null;
+ *   pinned_read_by / finish_upload   the fences the next user of the slot waits on. */
+static bool claim_upload(UploadSlot &u, uint64_t size, bool host_data)
+{
+	if (!u.copied && (!HIP_OK(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming)) ||
+	                  !HIP_OK(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming))))
+		return set_error(BeamformerLibErrorKind_SharedMemory);
+	if (host_data && !claim_pinned(u, size)) return set_error(BeamformerLibErrorKind_BufferOverflow);
+	return true;
+}
+
+static const void *enqueue_upload(Device &d, UploadSlot &u, const void *data, uint64_t size, void *dst, uint64_t dst_bytes)
+{
+	hipStream_t s = d.stream;
+	copy_to_pinned(u.pinned, data, size);
+	void *mapped = nullptr;
+	if (!dst) return HIP_OK(hipHostGetDevicePointer(&mapped, u.pinned, 0)) ? mapped : nullptr;
+	bool ok = true;
+	/* the device buffers of this slot were last read by the push three pushes ago; if that
+	 * push recorded no `consumed` event (small or device-resident pushes do not), fence
+	 * against everything enqueued so far instead */
+	if (u.unfenced_reader) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
+	if (u.consume_pending) ok &= HIP_OK(hipStreamWaitEvent(d.copy_stream, u.consumed, 0));
+	ok &= HIP_OK(hipMemcpyAsync(dst, u.pinned, dst_bytes, hipMemcpyHostToDevice, d.copy_stream));
+	ok &= HIP_OK(hipEventRecord(u.copied, d.copy_stream));
+	u.copy_pending = true;
+	ok &= HIP_OK(hipStreamWaitEvent(s, u.copied, 0));
+	return ok ? dst : nullptr;
+}
+
+/* the kernel just enqueued on s read the pinned slot in place: the slot is free again once it has run */
+static bool pinned_read_by(UploadSlot &u, hipStream_t s)
+{
+	u.copy_pending = true;
+	return HIP_OK(hipEventRecord(u.copied, s));
+}
+
+/* after the push's last launch: a push that went over the copy engine records `consumed`, any other leaves an unfenced reader */
+static void finish_upload(UploadSlot &u, bool overlap, hipStream_t s)
+{
+	if (overlap) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
+	else         { u.consume_pending = false; u.unfenced_reader = true; }
+}
+
+static void note_push_time()
+{
+	Context &c = g_context;
+	double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+	if (c.last_push_time > 0) {
+		if (c.rf_time_deltas.size() >= 32) c.rf_time_deltas.erase(c.rf_time_deltas.begin());
+		c.rf_time_deltas.push_back((float)(now - c.last_push_time));
+	}
+	c.last_push_time = now;
+}
+
+/* A push owns ids [first, first + count) on the first device_count devices (a single push: one id on every device of the set; a burst:
+ * count ids on one device).  Whatever fails after the ids are taken -- a peer's replan, a peer copy, the stages -- the next push starts
+ * all devices on the same id again, and a push that does not complete leaves a TOMBSTONE under each of its ids (no bytes, no voxels, no
+ * stage timings): the readers below refuse it -- "the newest frame is missing" -- instead of serving whatever record sat in that ring
+ * slot BeamformerMaxBacklogFrames pushes ago. */
+struct Tombstones {
+	Context &c; uint64_t first; uint32_t count, device_count; bool complete;
+	~Tombstones() {
+		for (uint32_t i = 0; i < device_count; i++) {
+			Device &p = c.devices[i];
+			p.frame_counter = first + count;
+			if (complete) continue;
+			for (uint64_t id = first; id < first + count; id++) {
+				FrameRecord &f = p.frames[id % p.frames.size()];
+				f = FrameRecord{}; f.points[0] = f.points[1] = f.points[2] = 0; f.id = (uint32_t)id; f.failed = true;
+				TimingSlot &t = p.timing[id % kTimingSlots];
+				t.count = 0; t.counted = false; t.violations_slot = ~0ull; t.das_voxels = 0; t.frame_id = id; t.failed = true;
+			}
+		}
+	}
+};
+
 /* lib .c:491-570 (client copy) + beamformer_core.c:1756-1805 (upload worker) */
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device)
 {
@@ -829,46 +1006,17 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 	const BeamformerParameters &bp = pb.parameters;
 	hipStream_t s = d.stream;
 
-	const uint64_t bytes   = (uint64_t)bf_kind_byte_size[pb.data_kind];
-	const uint64_t out_row = bytes * bp.sample_count * bp.acquisition_count;
-	const uint64_t in_row  = bytes * bp.raw_data_dimensions[0];
-	const uint64_t rf_size = out_row * bp.channel_count;
-
-	/* the reference copies whatever row the mapping names (lib .c:520-528); on a GPU an
-	 * out-of-range row would fault, so it is an error here */
-	bool identity = true;
-	for (uint32_t ch = 0; ch < bp.channel_count; ch++) {
-		uint16_t row = (uint16_t)pb.channel_mapping[ch];
-		if (row >= bp.raw_data_dimensions[1]) return set_error(BeamformerLibErrorKind_DataSizeMismatch);
-		identity &= row == ch;
-	}
-	bool a1s2 = bp.contrast_mode == BeamformerContrastMode_A1S2;
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	const uint64_t rf_size = l.rf_size;
 
 	uint32_t slot = (uint32_t)(d.rf_index++ % BeamformerMaxRawDataFramesInFlight);
 	if (!d.rf[slot].ensure(round_up(rf_size, 64) + 64)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
 	const bool multi = c.device_count > 1;
-	/* ONE frame id for every device of the set, taken here: whatever fails below -- a peer's replan, a peer copy, the ingest
-	 * device's own stages -- the next push starts all devices on the same id again, and beamformer_get_last_frames refuses exactly
-	 * the frames that are incomplete instead of skipping every frame from then on */
+	/* ONE frame id for every device of the set, taken here -- before the plan is committed: a push refused from here on leaves a tombstone */
 	const uint64_t sequence = c.push_sequence++;
 	for (uint32_t i = 0; i < c.device_count; i++) c.devices[i].frame_counter = sequence;
-	/* ... and a push that does not complete leaves a TOMBSTONE under its id on every device (no bytes, no voxels, no stage timings): the readers
-	 * below refuse it -- "the newest frame is missing" -- instead of serving whatever record sat in that ring slot
-	 * BeamformerMaxBacklogFrames pushes ago */
-	struct Lockstep {
-		Context &c; uint64_t id; bool complete;
-		~Lockstep() {
-			for (uint32_t i = 0; i < c.device_count; i++) {
-				Device &p = c.devices[i];
-				p.frame_counter = id + 1;
-				if (complete) continue;
-				FrameRecord &f = p.frames[id % p.frames.size()];
-				f = FrameRecord{}; f.points[0] = f.points[1] = f.points[2] = 0; f.id = (uint32_t)id; f.failed = true;
-				TimingSlot &t = p.timing[id % kTimingSlots];
-				t.count = 0; t.counted = false; t.violations_slot = ~0ull; t.das_voxels = 0; t.frame_id = id; t.failed = true;
-			}
-		}
-	} lockstep{c, sequence, false};
+	Tombstones lockstep{c, sequence, 1, c.device_count, false};
 	if (multi) {
 		/* every peer replans before the ingest device does (its commit clears the dirty bits) */
 		for (uint32_t i = 1; i < c.device_count; i++) {
@@ -885,10 +1033,7 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 
 	TimingSlot &t = d.timing[d.frame_counter % kTimingSlots];
 	t.failed = false;
-	if (!t.created) {
-		for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
-		t.created = true;
-	}
+	if (!ensure_events(t)) return false;
 	/* sample this frame's per-stage timings?  always for frames that are not small, after a replan,
 	 * when pair counting rides along, and every kTimingSamplePeriod-th frame otherwise */
 	const bool small = rf_size < kSmallFrameBytes &&
@@ -906,52 +1051,27 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 		t.events_slot = (uint32_t)(d.last_sampled_frame % kTimingSlots);
 	}
 
+	/* the copy shortcuts of a single push.  direct: the mapped layout is the raw layout, so one copy (H2D or D2D) lands the RF in its slot
+	 * and no ingest kernel runs -- unless the upload is small, when the ingest kernel IS the copy out of the pinned slot */
 	UploadSlot &u = d.upload[slot];
-	if (!u.copied && (!HIP_OK(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming)) ||
-	                  !HIP_OK(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming))))
-		return set_error(BeamformerLibErrorKind_SharedMemory);
-
-	bool ok = true, overlap = false;
-	const bool direct = identity && !a1s2 && in_row == out_row;
+	if (!claim_upload(u, size, !data_on_device)) return false;
+	const bool direct  = l.identity && !l.a1s2 && l.in_row == l.out_row;
+	const bool overlap = !data_on_device && size >= kOverlapBytes;
 	const void *raw = data;
 	if (!data_on_device) {
-		/* Host data: the caller's bytes are copied into a pinned slot (after which the caller
-		 * may reuse its buffer, as with the reference's copy into shared memory), the H2D runs
-		 * on the copy stream and the compute stream waits for it -- so the upload of frame n+1
-		 * overlaps the kernels of frame n, which one stream and pageable memory cannot do.
-		 * A copy-engine transfer and each cross-queue dependency cost 40-60 us of latency on
-		 * this runtime (tools/h2d_probe.cpp: 0.26 MB pinned H2D + a kernel = 114 us per frame),
-		 * more than a small frame's compute, so frames under kOverlapBytes skip the copy engine:
-		 * the ingest kernel reads the pinned slot in place over PCIe, in order on the compute
-		 * stream. */
-		constexpr uint32_t kOverlapBytes = 8u << 20;
-		overlap = size >= kOverlapBytes;
-		if (!claim_pinned(u, size)) return set_error(BeamformerLibErrorKind_BufferOverflow);
-		copy_to_pinned(u.pinned, data, size);
+		void *dst = nullptr;
 		if (overlap) {
-			void *dst = d.rf[slot].ptr;
+			dst = d.rf[slot].ptr;
 			if (!direct) {
 				if (!d.raw_staging[slot].ensure(round_up(size, 64) + 64)) return set_error(BeamformerLibErrorKind_BufferOverflow);
 				dst = d.raw_staging[slot].ptr;
 			}
-			/* the device buffers of this slot were last read by the frame three pushes ago; if that
-			 * frame recorded no `consumed` event (small or device-resident pushes do not), fence
-			 * against everything enqueued so far instead */
-			if (u.unfenced_reader) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
-			if (u.consume_pending) ok &= HIP_OK(hipStreamWaitEvent(d.copy_stream, u.consumed, 0));
-			ok &= HIP_OK(hipMemcpyAsync(dst, u.pinned, direct ? rf_size : (uint64_t)size, hipMemcpyHostToDevice, d.copy_stream));
-			ok &= HIP_OK(hipEventRecord(u.copied, d.copy_stream));
-			u.copy_pending = true;
-			ok &= HIP_OK(hipStreamWaitEvent(s, u.copied, 0));
-			raw = dst;
-		} else {
-			void *mapped = nullptr;
-			if (!HIP_OK(hipHostGetDevicePointer(&mapped, u.pinned, 0))) return set_error(BeamformerLibErrorKind_InvalidAccess);
-			raw = mapped;
 		}
+		raw = enqueue_upload(d, u, data, size, dst, direct ? rf_size : (uint64_t)size);
+		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	}
 	const bool zero_copy = !data_on_device && !overlap;
-	/* Device-resident RF already in the mapped layout is read in place by the first stage (no
+	/* borrowed: device-resident RF already in the mapped layout is read in place by the first stage (no
 	 * copy into the RF ring): the caller keeps it unchanged until the frame has run, which stream
 	 * order gives for free when its producer is on the library's stream.  Plans that start with
 	 * DAS still copy: the DAS input needs the library's zero block behind it. */
@@ -961,32 +1081,17 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 		if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
 		borrowed = !ps->plan.stages.empty() && ps->plan.stages[0].kind != BeamformerShaderKind_DAS;
 	}
+	bool ok = true;
 	if (direct && !zero_copy) {
-		/* the mapped layout is the raw layout: one copy straight into the RF slot */
 		if (data_on_device && !borrowed) ok &= HIP_OK(hipMemcpyAsync(d.rf[slot].ptr, data, rf_size, hipMemcpyDeviceToDevice, s));
 	} else {
 		PlanState *ps = commit_block(block);
 		if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-		BfIngestArgs a{};
-		a.raw = raw; a.out = d.rf[slot].ptr;
-		a.channel_mapping = (const int16_t *)ps->mapping.ptr;
-		a.in_row_bytes = in_row; a.out_row_bytes = out_row; a.channels = bp.channel_count;
-		a.a1s2 = a1s2; a.base = bf_kind_base[pb.data_kind];
-		a.a1s2_scalars = bp.sample_count * (uint32_t)bf_kind_element_count[pb.data_kind];
-		ok &= HIP_OK(bf_launch_ingest(&a, s));
-		if (zero_copy) {                   /* the pinned slot is free again once this kernel has run */
-			ok &= HIP_OK(hipEventRecord(u.copied, s));
-			u.copy_pending = true;
-		}
+		ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, 1, 0, 0, s);
+		if (zero_copy) ok &= pinned_read_by(u, s);
 	}
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
-
-	double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-	if (c.last_push_time > 0) {
-		if (c.rf_time_deltas.size() >= 32) c.rf_time_deltas.erase(c.rf_time_deltas.begin());
-		c.rf_time_deltas.push_back((float)(now - c.last_push_time));
-	}
-	c.last_push_time = now;
+	note_push_time();
 
 	/* what beamformer_hip_get_device_info checksums later.  A caller's device buffer is only borrowed for the duration of the frame: its
 	 * pointer is NOT kept -- with several devices the checksum of what the ingest device read is taken here, on the stream, while the
@@ -995,10 +1100,10 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 	if (multi && borrowed && d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2)))
 		d.last_rf_sum_ready = HIP_OK(bf_launch_rf_checksum(data, rf_size, (unsigned long long *)d.pair_counter.ptr + kTimingSlots + 1, s));
 	if (multi && !run_peers(block, borrowed ? data : d.rf[slot].ptr, rf_size, slot)) return false;
+	/* what the first stage may read: a borrowed buffer's RF, else the whole RF slot */
 	bool done = borrowed ? run_frame(block, data, (int64_t)rf_size, true)
 	                     : run_frame(block, d.rf[slot].ptr, (int64_t)d.rf[slot].size, true);
-	if (overlap) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
-	else         { u.consume_pending = false; u.unfenced_reader = true; }
+	finish_upload(u, overlap, s);
 	/* a caller's device buffer read in place: the contract lets the caller overwrite it from work enqueued
 	 * later on the library's stream, so that stream also waits for the peer copies out of it */
 	if (multi && borrowed)
@@ -1009,7 +1114,7 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 
 /* beamformer_hip_push_data_burst_with_compute: frame_count RF frames of one parameter block in one call (one device).
  *   RF        the whole burst is one upload into one pinned slot -- over the copy engine into device staging when it is large, read in
- *             place over PCIe when small, by push_rf_and_compute's rule applied to the burst -- and lands in ONE slot of the RF ring,
+ *             place over PCIe when small, by kOverlapBytes applied to the burst -- and lands in ONE slot of the RF ring,
  *             frame k at k * rf_stride with 64 spare bytes behind every frame;
  *   stages    ingest, then every pre-DAS stage, ONE launch each for the whole burst: the stage kernels carry a frame dimension (grid z,
  *             or grid y beside the channels for the filters, which then take the burst in chunks of 65535 / channels frames) and address
@@ -1018,24 +1123,17 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
  *   frames    contiguous in the frame ring (a burst that would straddle the end starts again at 0), consecutive ids;
  *   timings   one event set for the burst, in the timing slot of its last frame; every frame's slot points there with share = N.
  * Everything that can be refused is checked, and every buffer grown, BEFORE the ids are taken: a refused burst queues nothing.  After
- * that a failure leaves tombstones under all of its ids (Lockstep's idea in push_rf_and_compute). */
+ * that a failure leaves tombstones under all of its ids. */
 bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
 	ParameterBlock &pb = c.blocks[block];
-	const BeamformerParameters &bp = pb.parameters;
 	hipStream_t s = d.stream;
 	const uint32_t N = frame_count;
 
-	const uint64_t bytes   = (uint64_t)bf_kind_byte_size[pb.data_kind];
-	const uint64_t out_row = bytes * bp.sample_count * bp.acquisition_count;
-	const uint64_t in_row  = bytes * bp.raw_data_dimensions[0];
-	const uint64_t rf_size = out_row * bp.channel_count;
-	for (uint32_t ch = 0; ch < bp.channel_count; ch++)
-		if ((uint16_t)pb.channel_mapping[ch] >= bp.raw_data_dimensions[1]) return set_error(BeamformerLibErrorKind_DataSizeMismatch);
-	const bool a1s2 = bp.contrast_mode == BeamformerContrastMode_A1S2;
-
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
 	PlanState *ps = commit_block(block);
 	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
 	const Plan &plan = ps->plan;
@@ -1043,20 +1141,17 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	/* the frames: all of one size, contiguous in the ring */
 	uint32_t zfirst = 0, zcount = plan.output_points[2];
 	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
-	const uint64_t voxel_bytes = plan.iq_pipeline ? 8u : 4u;
-	const uint64_t frame_bytes = round_up((uint64_t)points[0] * points[1] * points[2] * voxel_bytes, 64);
+	const uint64_t frame_bytes = round_up((uint64_t)plan.output_points[0] * plan.output_points[1] * zcount * (plan.iq_pipeline ? 8u : 4u), 64);
 	if (frame_bytes > d.ring.size / N) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 
-	const bool has_das = plan.das_index >= 0;
 	std::vector<DasDecision> no_parts;
-	std::vector<DasDecision> &parts = has_das && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
+	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
 	BurstDecision route;
 	if (!parts.empty()) decide_burst(pb, plan, ps->transmit_table, parts, zfirst, zcount, c.das_path_mode, N, route);
 	else { route.stage_launches = (N + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels); route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared"; }
 
 	/* device and pinned memory, grown before anything is queued */
-	const uint64_t rf_stride    = round_up(rf_size, 64) + 64;
+	const uint64_t rf_stride    = round_up(l.rf_size, 64) + 64;
 	const uint64_t stage_stride = round_up(plan.intermediate_bytes, 64) + 64;
 	const uint64_t total        = (uint64_t)frame_size * N;
 	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
@@ -1066,7 +1161,6 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 		if (kind == BeamformerShaderKind_DAS) break;
 		pre_das_stages += kind != BeamformerShaderKind_CoherencyWeighting;
 	}
-	constexpr uint64_t kOverlapBytes = 8u << 20;                /* push_rf_and_compute's threshold, applied to the burst */
 	const bool overlap = !data_on_device && total >= kOverlapBytes;
 	bool fits = d.rf[slot].ensure(rf_stride * N);
 	if (pre_das_stages)     fits = fits && d.burst_stage[0].ensure(stage_stride * N);
@@ -1074,18 +1168,10 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	if (overlap)            fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
 	if (!fits) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
 	UploadSlot &u = d.upload[slot];
-	if (!u.copied && (!HIP_OK(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming)) ||
-	                  !HIP_OK(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming))))
-		return set_error(BeamformerLibErrorKind_SharedMemory);
-	if (!data_on_device) {
-		if (!claim_pinned(u, total)) return set_error(BeamformerLibErrorKind_BufferOverflow);
-	}
+	if (!claim_upload(u, total, !data_on_device)) return false;
 	const uint32_t owner = (uint32_t)((c.push_sequence + N - 1) % kTimingSlots);     /* the burst's events: its LAST frame's slot */
 	TimingSlot &t = d.timing[owner];
-	if (!t.created) {
-		for (auto &e : t.events) if (!HIP_OK(hipEventCreate(&e))) return set_error(BeamformerLibErrorKind_SharedMemory);
-		t.created = true;
-	}
+	if (!ensure_events(t)) return false;
 	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
 	bool wants_counters = false;
 	for (const DasDecision &dd : parts) wants_counters |= dd.path == DasPath_Staged || dd.path == DasPath_Tile;
@@ -1097,172 +1183,32 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	c.push_sequence += N;
 	d.frame_counter = first;
 	d.burst.valid = false;
-	struct BurstLockstep {
-		Device &d; uint64_t first; uint32_t count; bool complete;
-		~BurstLockstep() {
-			d.frame_counter = first + count;
-			if (complete) return;
-			for (uint64_t id = first; id < first + count; id++) {
-				FrameRecord &f = d.frames[id % d.frames.size()];
-				f = FrameRecord{}; f.points[0] = f.points[1] = f.points[2] = 0; f.id = (uint32_t)id; f.failed = true;
-				TimingSlot &t = d.timing[id % kTimingSlots];
-				t.count = 0; t.counted = false; t.violations_slot = ~0ull; t.das_voxels = 0; t.frame_id = id; t.failed = true;
-			}
-		}
-	} lockstep{d, first, N, false};
+	Tombstones lockstep{c, first, N, 1, false};
 
 	t.failed = false; t.sampled = true; t.events_slot = owner; t.share = N; t.count = 0; t.counted = false;
 	d.have_sample = false;          /* the burst's events cover N frames: a single frame that follows records its own */
-	auto segment = [&](uint32_t kind) {
-		if (t.count < BEAMFORMER_HIP_MAX_TIMED_STAGES) {
-			t.kinds[t.count++] = kind;
-			record(t, t.count, s);
-		}
-	};
 	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
 
-	/* ---- upload and ingest ---- */
+	/* ---- upload and ingest: a burst always runs the ingest kernel ---- */
 	const void *raw = data;
 	if (!data_on_device) {
-		copy_to_pinned(u.pinned, data, total);
-		if (overlap) {
-			if (u.unfenced_reader) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
-			if (u.consume_pending) ok &= HIP_OK(hipStreamWaitEvent(d.copy_stream, u.consumed, 0));
-			ok &= HIP_OK(hipMemcpyAsync(d.raw_staging[slot].ptr, u.pinned, total, hipMemcpyHostToDevice, d.copy_stream));
-			ok &= HIP_OK(hipEventRecord(u.copied, d.copy_stream));
-			u.copy_pending = true;
-			ok &= HIP_OK(hipStreamWaitEvent(s, u.copied, 0));
-			raw = d.raw_staging[slot].ptr;
-		} else {
-			void *mapped = nullptr;
-			if (!HIP_OK(hipHostGetDevicePointer(&mapped, u.pinned, 0))) return set_error(BeamformerLibErrorKind_InvalidAccess);
-			raw = mapped;
-		}
+		raw = enqueue_upload(d, u, data, total, overlap ? d.raw_staging[slot].ptr : nullptr, total);
+		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	}
-	{
-		BfIngestArgs a{};
-		a.raw = raw; a.out = d.rf[slot].ptr;
-		a.channel_mapping = (const int16_t *)ps->mapping.ptr;
-		a.in_row_bytes = in_row; a.out_row_bytes = out_row; a.channels = bp.channel_count;
-		a.a1s2 = a1s2; a.base = bf_kind_base[pb.data_kind];
-		a.a1s2_scalars = bp.sample_count * (uint32_t)bf_kind_element_count[pb.data_kind];
-		a.frames = N; a.in_frame_bytes = frame_size; a.out_frame_bytes = rf_stride;
-		ok &= HIP_OK(bf_launch_ingest(&a, s));
-	}
-	if (!data_on_device && !overlap) {                /* the pinned slot is free again once the ingest kernel has run */
-		ok &= HIP_OK(hipEventRecord(u.copied, s));
-		u.copy_pending = true;
-	}
-	segment(kStageIngest);
+	ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, N, frame_size, rf_stride, s);
+	if (!data_on_device && !overlap) ok &= pinned_read_by(u, s);
+	segment(t, kStageIngest, s);
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	note_push_time();
+	d.last_rf = (char *)d.rf[slot].ptr + (N - 1) * rf_stride; d.last_rf_bytes = l.rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
 
-	double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-	if (c.last_push_time > 0) {
-		if (c.rf_time_deltas.size() >= 32) c.rf_time_deltas.erase(c.rf_time_deltas.begin());
-		c.rf_time_deltas.push_back((float)(now - c.last_push_time));
-	}
-	c.last_push_time = now;
-	d.last_rf = (char *)d.rf[slot].ptr + (N - 1) * rf_stride; d.last_rf_bytes = rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
-	d.das_input = nullptr; d.das_input_bytes = 0;       /* (beamformer_hip_copy_das_input serves single frames) */
-
-	/* hook SCRATCH_POISON (run_frame_stages): the stage buffers of the whole burst, and below the burst's ring slots */
-	const bool poison = hooks().scratch_poison;
-	if (poison)
-		for (DeviceBuffer &b : d.burst_stage)
-			if (b.ptr) ok &= HIP_OK(hipMemsetAsync(b.ptr, 0xFF, b.size, s));
-
-	/* ---- stages, one after the other over all frames ---- */
-	const char *cur = (const char *)d.rf[slot].ptr;     /* frame k of the current stage's input: cur + k * cur_stride */
-	uint64_t cur_stride = rf_stride;
-	int64_t  cur_bound = (int64_t)rf_size;              /* what a stage may read of a frame: the RF itself, then a stage buffer's frame with its slack */
-	int toggle = 0;
-	FrameRecord *frame0 = nullptr;
-	uint32_t das_path = 0;
-	bool das_segment_done = false;
-	for (size_t i = 0; i < plan.stages.size() && ok; i++) {
-		const Stage &st = plan.stages[i];
-		das_segment_done = false;
-		switch (st.kind) {
-		case BeamformerShaderKind_Reshape:
-		case BeamformerShaderKind_Decode:
-		case BeamformerShaderKind_Hilbert:
-		case BeamformerShaderKind_Filter:
-		case BeamformerShaderKind_Demodulate:{
-			char *out = (char *)d.burst_stage[toggle].ptr;
-			ok &= launch_stage(ps, bp, i, cur, cur_bound, out, s, N, cur_stride, stage_stride);
-			cur = out; cur_stride = stage_stride; cur_bound = (int64_t)stage_stride; toggle ^= 1;
-		}break;
-		case BeamformerShaderKind_DAS:{
-			frame0 = next_burst_frames(points, plan.iq_pipeline, block, N);
-			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-			char *out0 = (char *)d.ring.ptr + frame0->offset;
-			if (poison && frame_bytes) ok &= HIP_OK(hipMemsetAsync(out0, 0xFF, frame_bytes * N, s));
-			if (zcount == 0) break;
-			const DasDecision &head = main_part(parts);
-			das_path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
-			const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes;
-			if (route.burst_kernel) {
-				BfDasArgs a = route.a;
-				a.rf = cur; a.out = out0;
-				a.transmits = (const BfTransmit *)ps->transmits.ptr; a.sparse_elements = (const int16_t *)ps->sparse.ptr;
-				a.readi_hadamard = (const uint16_t *)ps->readi_hadamard.ptr;
-				BfBurstArgs b{};
-				b.frame_count = N; b.rf_stride = cur_stride; b.out_stride = frame_bytes;
-				ok &= HIP_OK(bf_launch_das_burst(&a, &b, s));
-			} else {
-				for (uint32_t k = 0; k < N && ok; k++) {
-					uint32_t *frame_counters = nullptr;
-					if (wants_counters && N - k <= kTimingSlots) {       /* the table keeps the newest 32 frames: older ones of a long burst count nothing */
-						frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
-						ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
-					}
-					for (const DasDecision &dd : parts) {
-						uint32_t part_path = (uint32_t)dd.path;
-						ok &= launch_das_part(ps, dd, cur + k * cur_stride, out0 + k * frame_bytes + (uint64_t)(dd.z_first - zfirst) * plane_bytes,
-						                      dd.z_count * plane_bytes, frame_counters, s, part_path);
-						if (&dd == &head && dd.path != DasPath_Zero) das_path = part_path;
-					}
-				}
-			}
-			if (c.count_pairs && head.path != DasPath_Zero) {
-				/* the geometry-only count is the same for every frame: it runs once, into the last frame's counter, and the other
-				 * frames' counters are copies */
-				segment((uint32_t)st.kind);
-				unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
-				unsigned long long *mine = counters + owner;
-				ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
-				for (const DasDecision &dd : parts) {
-					BfDasArgs count = dd.general;
-					count.rf = cur; count.out = out0;
-					count.transmits = (const BfTransmit *)ps->transmits.ptr; count.sparse_elements = (const int16_t *)ps->sparse.ptr;
-					count.readi_hadamard = (const uint16_t *)ps->readi_hadamard.ptr;
-					count.pair_counter = mine;
-					ok &= HIP_OK(bf_launch_das_count(&count, s));
-				}
-				for (uint32_t k = 0; k + 1 < N && k + 1 < kTimingSlots; k++)
-					ok &= HIP_OK(hipMemcpyAsync(counters + (first + N - 2 - k) % kTimingSlots, mine, sizeof(*mine), hipMemcpyDeviceToDevice, s));
-				segment(kStagePairCount);
-				t.counted = true;
-				das_segment_done = true;
-			}
-		}break;
-		default: break;      /* CoherencyWeighting: the DAS epilogue */
-		}
-		if (!das_segment_done) segment((uint32_t)st.kind);
-	}
-	if (!has_das && ok) {
-		/* no DAS in the pipeline: the frames exist and stay zero */
-		frame0 = next_burst_frames(points, plan.iq_pipeline, block, N);
-		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-		if (frame_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, frame_bytes * N, s));
-	}
-	if (overlap) { u.consume_pending = HIP_OK(hipEventRecord(u.consumed, s)); u.unfenced_reader = false; }
-	else         { u.consume_pending = false; u.unfenced_reader = true; }
-	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	/* ---- stages, one after the other over all frames: what a stage may read of a frame is the RF itself, then a stage buffer's frame
+	 * with its slack ---- */
+	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_stride, (int64_t)l.rf_size, d.burst_stage, stage_stride, t, &route});
+	finish_upload(u, overlap, s);
+	if (!done) return false;
 
 	/* every frame's row of the timing table: the burst's events, shared */
-	const bool das_ran = has_das && zcount && !parts.empty();
-	const BfDasArgs *da = das_ran ? &main_part(parts).a : nullptr;
 	const TimingSlot burst = t;
 	for (uint32_t k = 0; k < N; k++) {
 		const uint64_t id = first + k;
@@ -1270,13 +1216,6 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 		ft.count = burst.count; ft.counted = burst.counted;
 		std::memcpy(ft.kinds, burst.kinds, sizeof(ft.kinds));
 		ft.sampled = id % kTimingSlots == owner; ft.events_slot = owner; ft.share = N; ft.failed = false;
-		ft.frame_id = id;
-		ft.das_voxels = das_ran ? (uint64_t)points[0] * points[1] * points[2] : 0;
-		ft.das_taps = !das_ran ? 0 : da->interpolation == 0 ? 1 : da->interpolation == 1 ? 2 : 4;
-		ft.das_sample_bytes = das_ran ? (uint32_t)voxel_bytes : 0;
-		ft.das_path = das_ran ? das_path : 0;
-		ft.das_row_end_planes = das_ran ? row_end_planes(parts) : 0;
-		ft.violations_slot = wants_counters && !route.burst_kernel && N - k <= kTimingSlots ? id % kTimingSlots : ~0ull;
 	}
 	/* older unsampled frames whose row borrowed the events of the slot the burst has taken over: their row goes blank rather than show
 	 * the burst's times as one frame's */
