@@ -169,6 +169,68 @@ typedef struct {
 /* The newest burst (frame_count >= 2); waits for it to finish.  Fails when the newest push was not a burst or did not complete. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_burst_info(BeamformerHipBurstInfo *out);
 
+/* ---- views: ONE RF frame beamformed on K voxel grids per call (live X-plane / tri-plane imaging: the reference's 3DXPlane view;
+ * ULM patch refinement: tens to hundreds of small fine grids around detections, all from the RF of one push) ----
+ * `data` is one RF frame under exactly the layout and size rules of beamformer_push_data_with_compute.  Everything except the grid
+ * comes from parameter block `parameter_slot`: view k is the frame a single push of the same RF would give if the block's
+ * das_voxel_transform and output_points[0..2] were views[k]'s.  Queues view_count frames: they take consecutive frame ids in view
+ * order, and beamformer_get_last_frames(out, size, view_count) returns them oldest first, each at its own 64-byte-rounded size.
+ *   - one upload, one RF-ring slot, ONE launch of the ingest and of every pre-DAS stage; the views lie contiguously in the frame ring,
+ *     each rounded to 64 bytes (a run that would straddle the end of the ring starts again at offset 0);
+ *   - every view gets its own single-frame decision (beamformer_hip_describe_das's, on that grid).  Views of RCA-family blocks
+ *     (Flash, RCA_TPW, RCA_VLS) that the general kernel would run take ONE DAS launch together (csrc/das_views.hip: the tiles of all
+ *     such views side by side along the grid, each block the general kernel's own loop on its view's grid, no channel split) when
+ *     their 256-voxel tiles number at least BeamformerHipViewsDescription::min_tiles; every other view runs its single-frame kernel(s)
+ *     on the shared DAS input.  A view's bits do not depend on which other views the push holds, nor on their order.
+ *     beamformer_hip_describe_views says which route, and why;
+ *   - beamformer_hip_get_last_frame_info describes the LAST view (its points); every frame record carries its view's points and tag;
+ *   - validation is the single push's, with the same error kinds (DataSizeMismatch, InvalidImagePlane per view,
+ *     ParameterBlockUnallocated, ...).  view_count == 0 and view_count > BEAMFORMER_HIP_MAX_VIEWS are BufferOverflow; views == NULL or
+ *     a zero extent is InvalidAccess; all views together (each rounded to 64 bytes) exceeding the frame ring is FrameSizeOverflow;
+ *     several devices (beamformer_hip_set_devices, count > 1) or an output shard on the block is InvalidAccess -- a view is not
+ *     sharded.  Everything that can be refused is checked before a device is touched, and every buffer whose absence
+ *     would fail the push is grown before the ids are taken: a refused push queues nothing.  A push that fails after that leaves a tombstone under every one of its ids;
+ *   - view_count == 1 goes through the same code (it is not the single push: the grid comes from the view);
+ *   - one event set per push: every view appears in beamformer_compute_timings and beamformer_hip_get_last_frame_timings with the
+ *     push's stage times divided by view_count; frame graphs: a views push runs as direct launches; pair counting: the
+ *     geometry-only count runs per view. */
+#define BEAMFORMER_HIP_MAX_VIEWS 1024u
+typedef struct {
+	float    das_voxel_transform[16];   /* as BeamformerParameters::das_voxel_transform (column major) */
+	uint32_t output_points[3];          /* x, y, z voxels of this view, each >= 1 */
+	uint32_t image_plane_tag;           /* BeamformerViewPlaneTag */
+} BeamformerHipView;
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_data_views_with_compute(const void *data, uint32_t size, const BeamformerHipView *views,
+                                                                           uint32_t view_count, uint32_t parameter_slot);
+/* ... for RF that already resides on the library's device (beamformer_hip_push_device_data_with_compute's rules; the RF of a views
+ * push is always ingested into the RF ring, never read in place) */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_device_data_views_with_compute(const void *device_data, uint32_t size, const BeamformerHipView *views,
+                                                                                  uint32_t view_count, uint32_t parameter_slot);
+
+typedef struct {
+	uint32_t kernel_views;          /* views das_views.hip takes, all in one launch (0: none) */
+	uint32_t das_launches;          /* DAS launches of the whole push: that one, plus the single-frame launch(es) of every other view */
+	uint32_t min_tiles;             /* the fewest 256-voxel tiles of eligible views the views kernel takes (csrc/das_select.h: kViewsMinTiles) */
+	int8_t   path[BEAMFORMER_HIP_MAX_VIEWS];   /* per view: its OWN single-frame decision (BeamformerHipFrameTimings::das_path numbering; -1 / -2 as
+	                                              BeamformerHipDasDescription::path), whichever route the push takes */
+	char     reason[160];           /* why this route */
+} BeamformerHipViewsDescription;
+/* What a views push of these grids on a parameter block would run, under the current das path mode.  Needs no device. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_views(uint32_t parameter_slot, const BeamformerHipView *views, uint32_t view_count,
+                                                             BeamformerHipViewsDescription *out);
+
+typedef struct {
+	BeamformerHipViewsDescription route;   /* of the push that ran */
+	uint32_t first_frame_id, view_count;
+	uint32_t stage_count;
+	uint32_t stage_kind[BEAMFORMER_HIP_MAX_TIMED_STAGES];  /* BeamformerShaderKind; ingest = 0xFFFF */
+	float    stage_ms[BEAMFORMER_HIP_MAX_TIMED_STAGES];    /* hipEvent pairs around each stage of the WHOLE push */
+	float    views_ms;                                     /* first event to last event */
+	float    decide_us;                                    /* host time the push spent deciding its views' routes */
+} BeamformerHipViewsInfo;
+/* The newest views push; waits for it to finish.  Fails when the newest push was not a views push or did not complete. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_views_info(BeamformerHipViewsInfo *out);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */
@@ -272,7 +334,12 @@ typedef enum {
 	BeamformerHipDasPath_TileStaging      = 0x100,/* flag: das_tile.hip (factored kernel, block-wide LDS staging of cubic polynomials) wherever it is supported --
 	                                                 automatic on fine grids only */
 	BeamformerHipDasPath_NoTileStaging    = 0x200,/* flag: never */
-	BeamformerHipDasPath_NoBurstKernel    = 0x400,/* flag: a burst (below) runs the single-frame DAS kernel once per frame also where das_burst.hip would take it */
+	BeamformerHipDasPath_NoBurstKernel    = 0x400,/* flag: a burst (above) runs the single-frame DAS kernel once per frame also where das_burst.hip would take it */
+	BeamformerHipDasPath_NoViewsKernel    = 0x800,/* flag: a views push runs every view's single-frame DAS kernel also where das_views.hip would take it */
+	BeamformerHipDasPath_PreferViewsKernel = 0x1000,/* flag: das_views.hip takes the eligible views however few their tiles (for tests) */
+	BeamformerHipDasPath_FailViewsDas     = 0x2000,/* flag: a views push FAILS (InvalidAccess) at its DAS stage, after its ids are taken and its frames placed and
+	                                                  before anything is launched there -- what a failed launch leaves behind (a tombstone under every id of
+	                                                  the push), reachable without a device fault (for tests; no other push is affected) */
 } BeamformerHipDasPath;
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_das_path(uint32_t mode);
 /* Environment variables the library reads (none is needed in production):

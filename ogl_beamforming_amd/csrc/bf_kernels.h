@@ -5,6 +5,7 @@
 #ifndef BF_KERNELS_H
 #define BF_KERNELS_H
 
+#include <stddef.h>
 #include <stdint.h>
 #include <hip/hip_runtime_api.h>
 
@@ -78,6 +79,29 @@ typedef struct {
 	uint32_t pad;
 	uint64_t rf_stride, out_stride;   /* bytes */
 } BfBurstArgs;
+
+/* views form of the general kernel (das_views.hip): one DAS input beamformed on several grids by one launch.  A row holds what differs
+ * from view to view; everything else is the launch's BfDasArgs.  128 bytes, read through wave-uniform (scalar) loads. */
+typedef struct {
+	float    voxel_transform[16];
+	uint32_t size[3];                 /* the view's grid (z_first = 0, z_count = size[2]) */
+	uint32_t tile_shift[3];           /* 256-voxel tiles, no channel split */
+	uint32_t blocks[3];
+	uint32_t depth_major;             /* 0, 1 or 2: the view's own walk order (a view plane's balanced bands, 3, become 2: no XCD dealing here) */
+	uint32_t band_rows;
+	uint32_t pad0;
+	uint64_t out_offset;              /* bytes from BfDasArgs.out to the view's frame */
+	uint32_t pad1[2];
+} BfViewRow;
+#ifdef __cplusplus
+static_assert(sizeof(BfViewRow) == 128 && offsetof(BfViewRow, size) == 64 && offsetof(BfViewRow, out_offset) == 112 && offsetof(BfViewRow, out_offset) % 8 == 0,
+              "BfViewRow: 128 bytes, the same on the host that fills it and in the kernel that reads it");
+#endif
+typedef struct {
+	const BfViewRow *rows;            /* [view_count], device */
+	const uint32_t  *first_block;     /* [view_count + 1], device: view v owns block ids first_block[v] .. first_block[v + 1] - 1 */
+	uint32_t view_count, pad;
+} BfViewsArgs;
 
 /* channel-paired staged kernel (uniform = 2): the LDS holds the 64-element blocks (two channels' 32-sample windows) of at most this
  * many transmits at a time -- a multiple of 4 whose block indices, plus the two elements in front, stay below 4096 (the tap address
@@ -296,6 +320,8 @@ hipError_t bf_launch_hilbert(const BfFilterArgs *a, hipStream_t s);
 hipError_t bf_launch_das(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_count(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s);   /* das_burst.hip: RCA family, `a` without a channel split */
+hipError_t bf_launch_views_table(void *dst, const void *src, uint32_t bytes, hipStream_t s);   /* das_views.hip: bytes (a multiple of 4) from mapped pinned memory into the device table */
+hipError_t bf_launch_das_views(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s);   /* das_views.hip: RCA family, no channel split */
 hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged_tables(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);

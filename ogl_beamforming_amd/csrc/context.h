@@ -34,6 +34,8 @@ struct FrameRecord {
 	int      data_kind = BeamformerDataKind_Float32;
 	uint32_t id = 0, block = 0;
 	int      timing_slot = -1;
+	uint32_t tag = 0;                /* BeamformerViewPlaneTag of a views push's frame (0 for every other push, whose tag stops at validation as it always
+	                                    has).  Recorded for the consumer the tag exists for -- a display that routes frames to its planes; no call reports it yet */
 	bool     failed = false;         /* tombstone of a push that did not complete (executor.cpp, Tombstones) */
 };
 
@@ -70,6 +72,15 @@ struct BurstRecord {
 	uint64_t      first_id = 0;
 	uint32_t      count = 0, events_slot = 0;
 	BurstDecision route;
+};
+
+/* the newest views push (executor.cpp push_views): what beamformer_hip_get_last_views_info reports */
+struct ViewsRecord {
+	bool        valid = false;
+	uint64_t    first_id = 0;
+	uint32_t    count = 0, events_slot = 0;
+	BeamformerHipViewsDescription route{};
+	float       decide_us = 0;
 };
 
 struct PlanState {
@@ -117,6 +128,11 @@ struct Device {
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
 	DeviceBuffer burst_stage[2];                               /* push_burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
 	BurstRecord  burst;
+	ViewsRecord  views;
+	DeviceBuffer views_table;                                  /* push_views: the BfViewRows and the prefix table das_views.hip reads */
+	void        *views_pinned = nullptr;                       /* ... and the pinned memory they are sent from, free again once views_copied has passed */
+	hipEvent_t   views_copied = nullptr;
+	bool         views_copy_pending = false;
 	DeviceBuffer hercules_pairs;                               /* das_hercules.hip: {sample, difference} copy of the DAS input (IQ, linear) */
 	DeviceBuffer staged_tables;        /* das_staged.hip, wave-uniform transmit tables (bf_launch_das_staged_tables) */
 	DeviceBuffer staged_violations;    /* das_staged*.hip: one counter per timing slot of window positions outside the staged window */
@@ -181,6 +197,10 @@ uint64_t default_frame_ring_bytes();
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device);
 bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device);
 bool last_burst_info(BeamformerHipBurstInfo *out);
+bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device);
+bool last_views_info(BeamformerHipViewsInfo *out);
+std::vector<ViewGrid> view_grids(const BeamformerHipView *views, uint32_t view_count);     /* the grids decide_views takes */
+void describe_views_decision(const ViewsDecision &route, uint32_t view_count, BeamformerHipViewsDescription *out);
 bool wait_for_frames(int32_t timeout_ms);
 const FrameRecord *newest_record(const Device &d);     /* null: the newest push did not complete */
 bool export_last_frames(void *out, uint64_t out_size, uint32_t count, int32_t timeout_ms);

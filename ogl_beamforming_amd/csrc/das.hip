@@ -25,42 +25,6 @@
  */
 #include "das_general.h"
 
-/* das.glsl:204-231 */
-template <int INTERP, bool CPLX, bool CW, bool COUNT>
-__device__ __forceinline__ void das_rca(const BfDasArgs &p, const char *rf, float wx, float wy, float wz, uint32_t x, uint32_t y, uint32_t z,
-                                        int ch0, int ch1, Accumulator<CPLX, CW, COUNT> &acc)
-{
-	float xx, xy, xz;
-	m4_point(p.xdc_transform, wx, wy, wz, xx, xy, xz);
-	const int S = p.sample_count, A = p.acquisition_count;
-	const float inv_abs_z = hw_rcp(__builtin_fabsf(xz));
-	const float zz = xz * xz;
-
-	for (int acquisition = 0; acquisition < A; acquisition++) {
-		const BfTransmit t = p.transmits[acquisition];
-		const bool  rx_rows = (t.flags & BF_RX_ROWS) != 0;
-		const float lateral = rx_rows ? xy : xx;
-		const float pitch   = rx_rows ? p.pitch[1] : p.pitch[0];
-		const float tx_dist = transmit_distance(t, wx, wy, wz);
-		const float f_over_z = p.f_number * inv_abs_z;
-
-		int rf_offset = acquisition * S + ch0 * S * A;
-		for (int channel = ch0; channel < ch1; channel++) {
-			float dx    = lateral - (float)channel * pitch;
-			float a_arg = __builtin_fabsf(dx * f_over_z);
-			bool  pass  = a_arg < 0.5f;
-			if constexpr (COUNT) {
-				acc.pairs += pass;
-			} else if (pass) {
-				float sidx = sample_index(tx_dist + hw_sqrt(dx * dx + zz), p);
-				sidx = settle_index<BF_DAS_RCA, INTERP>(sidx, p, x, y, z, channel, acquisition);
-				acc.add(apodize(a_arg) * sample_rf<INTERP, CPLX>(rf, rf_offset, sidx, p));
-			}
-			rf_offset += S * A;
-		}
-	}
-}
-
 /* das.glsl:233-286 */
 template <int INTERP, bool CPLX, bool CW, bool COUNT>
 __device__ __forceinline__ void das_hercules(const BfDasArgs &p, const char *rf, float wx, float wy, float wz, uint32_t x, uint32_t y, uint32_t z,

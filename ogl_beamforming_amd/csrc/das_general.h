@@ -1,6 +1,6 @@
-/* das_general.h -- what the general kernel (das.hip) and its ensemble form (das_burst.hip) share: the transmit distance, the sample
- * index, the row-end settlement of an index and the walk from a block id to a voxel tile.  One text, so that a frame of a burst is
- * the same arithmetic as a single frame. */
+/* das_general.h -- what the general kernel (das.hip), its ensemble form (das_burst.hip) and its views form (das_views.hip) share: the
+ * transmit distance, the sample index, the row-end settlement of an index, the RCA family's loop (das_rca) and the walk from a block id
+ * to a voxel tile.  One text, so that a frame of a burst and a view of a views push are the same arithmetic as a single frame. */
 #ifndef BF_DAS_GENERAL_H
 #define BF_DAS_GENERAL_H
 
@@ -59,6 +59,42 @@ __device__ __forceinline__ float settle_index(float index, const BfDasArgs &p, u
 	return index;
 }
 
+/* das.glsl:204-231 */
+template <int INTERP, bool CPLX, bool CW, bool COUNT>
+__device__ __forceinline__ void das_rca(const BfDasArgs &p, const char *rf, float wx, float wy, float wz, uint32_t x, uint32_t y, uint32_t z,
+                                        int ch0, int ch1, Accumulator<CPLX, CW, COUNT> &acc)
+{
+	float xx, xy, xz;
+	m4_point(p.xdc_transform, wx, wy, wz, xx, xy, xz);
+	const int S = p.sample_count, A = p.acquisition_count;
+	const float inv_abs_z = hw_rcp(__builtin_fabsf(xz));
+	const float zz = xz * xz;
+
+	for (int acquisition = 0; acquisition < A; acquisition++) {
+		const BfTransmit t = p.transmits[acquisition];
+		const bool  rx_rows = (t.flags & BF_RX_ROWS) != 0;
+		const float lateral = rx_rows ? xy : xx;
+		const float pitch   = rx_rows ? p.pitch[1] : p.pitch[0];
+		const float tx_dist = transmit_distance(t, wx, wy, wz);
+		const float f_over_z = p.f_number * inv_abs_z;
+
+		int rf_offset = acquisition * S + ch0 * S * A;
+		for (int channel = ch0; channel < ch1; channel++) {
+			float dx    = lateral - (float)channel * pitch;
+			float a_arg = __builtin_fabsf(dx * f_over_z);
+			bool  pass  = a_arg < 0.5f;
+			if constexpr (COUNT) {
+				acc.pairs += pass;
+			} else if (pass) {
+				float sidx = sample_index(tx_dist + hw_sqrt(dx * dx + zz), p);
+				sidx = settle_index<BF_DAS_RCA, INTERP>(sidx, p, x, y, z, channel, acquisition);
+				acc.add(apodize(a_arg) * sample_rf<INTERP, CPLX>(rf, rf_offset, sidx, p));
+			}
+			rf_offset += S * A;
+		}
+	}
+}
+
 /* Block id -> tile (bx, by, bz) of the general kernel's grid; valid false: a block of the ragged tail, which has no tile. */
 struct GeneralTile { uint32_t bx, by, bz; bool valid; };
 __device__ __forceinline__ GeneralTile general_tile(const BfDasArgs &p, uint32_t bid)
@@ -83,6 +119,28 @@ __device__ __forceinline__ GeneralTile general_tile(const BfDasArgs &p, uint32_t
 		/* view planes (depth on voxel y, one voxel along z): y fastest, so that each XCD's run of tiles is a lateral COLUMN
 		 * at every depth -- the work per tile grows with depth (f-number culling), a run of depth ROWS would leave the XCDs
 		 * that hold the shallow rows idle for a fifth of the launch */
+		by = tile % p.blocks[1];
+		bx = (tile / p.blocks[1]) % p.blocks[0];
+		bz = tile / (p.blocks[1] * p.blocks[0]);
+	} else if (p.depth_major) {
+		bz = tile % p.blocks[2];
+		bx = (tile / p.blocks[2]) % p.blocks[0];
+		by = tile / (p.blocks[2] * p.blocks[0]);
+	} else {
+		bx = tile % p.blocks[0];
+		by = (tile / p.blocks[0]) % p.blocks[1];
+		bz = tile / (p.blocks[0] * p.blocks[1]);
+	}
+	return GeneralTile{bx, by, bz, true};
+}
+
+/* Tile NUMBER (below blocks[0] * blocks[1] * blocks[2]) -> tile, in the walk order depth_major 0, 1 or 2 names: general_tile's second
+ * half without its dealing of block ids to the XCDs.  das_views.hip, whose blocks take the tiles of several grids in turn, enters here.
+ * (general_tile keeps its own text: split in two it compiled to other code, and a single frame's kernels stay as they are.) */
+__device__ __forceinline__ GeneralTile general_tile_at(const BfDasArgs &p, uint32_t tile)
+{
+	uint32_t bx = 0, by = 0, bz = 0;
+	if (p.depth_major == 2u) {
 		by = tile % p.blocks[1];
 		bx = (tile / p.blocks[1]) % p.blocks[0];
 		bz = tile / (p.blocks[1] * p.blocks[0]);

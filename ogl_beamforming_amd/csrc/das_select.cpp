@@ -1013,6 +1013,93 @@ void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<
 	}
 }
 
+void plan_on_view(const ParameterBlock &pb, const ViewGrid &view, Plan &plan)
+{
+	const BeamformerParameters &bp = pb.parameters;
+	for (int k = 0; k < 3; k++) plan.output_points[k] = view.points[k] > 1 ? view.points[k] : 1u;
+	std::memcpy(plan.das_voxel_transform, view.transform, sizeof(plan.das_voxel_transform));
+	if (bp.acquisition_kind == BeamformerAcquisitionKind_UFORCES || bp.acquisition_kind == BeamformerAcquisitionKind_FORCES)
+		m4_mul(bp.xdc_transform, view.transform, plan.das_voxel_transform);
+}
+
+void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
+                  uint32_t mode, ViewsDecision &out)
+{
+	out = ViewsDecision{};
+	out.parts.resize(view_count);
+	out.taken.assign(view_count, 0);
+	if (plan.das_index < 0) { out.reason = "no DAS stage runs: the frames are cleared"; return; }
+	Plan on_view = plan;                         /* one copy; per view only the grid changes */
+	std::vector<BfViewRow> rows(view_count);
+	std::vector<uint8_t> eligible(view_count, 0);
+	uint32_t tiles = 0, candidates = 0, zero = 0, cut = 0, faster = 0;
+	int family = BF_DAS_RCA, faster_path = DasPath_General;
+	for (uint32_t v = 0; v < view_count; v++) {
+		plan_on_view(pb, views[v], on_view);
+		const uint32_t zcount = on_view.output_points[2];
+		std::vector<DasDecision> &parts = out.parts[v];
+		decide_das_parts(pb, on_view, tx, 0, zcount, mode, parts);
+		const DasDecision &head = main_part(parts);
+		family = head.a.family;
+		for (const DasDecision &d : parts) out.das_launches += d.path != DasPath_Zero;
+		if (head.path == DasPath_Zero) { zero++; continue; }
+		if (parts.size() != 1) { cut++; continue; }
+		if (head.path != DasPath_General) { faster++; faster_path = head.path; continue; }
+		if (head.a.family != BF_DAS_RCA || (mode & 0x800u)) continue;
+		/* the general kernel's tiles at one thread per voxel (decide_das under flag 0x10): the views fill the chip, not a channel split */
+		BfViewRow &r = rows[v];
+		r = BfViewRow{};
+		BfDasArgs g = head.general;
+		float to_xdc[16];
+		m4_mul(pb.parameters.xdc_transform, on_view.das_voxel_transform, to_xdc);
+		const int depth_axis = choose_tile(to_xdc, g.size, zcount, g.tile_shift, 8);
+		uint32_t view_tiles = 1;
+		for (int k = 0; k < 3; k++) {
+			r.size[k] = g.size[k]; r.tile_shift[k] = g.tile_shift[k];
+			r.blocks[k] = (g.size[k] + (1u << g.tile_shift[k]) - 1) >> g.tile_shift[k];
+			view_tiles *= r.blocks[k];
+		}
+		r.depth_major = tile_walk(depth_axis, zcount, r.blocks[1], r.band_rows);
+		if (r.depth_major == 3u) { r.depth_major = 2u; r.band_rows = 1; }      /* a view plane's balanced bands deal padded ids to the XCDs: here y fastest */
+		std::memcpy(r.voxel_transform, on_view.das_voxel_transform, sizeof(r.voxel_transform));
+		if ((uint64_t)tiles + view_tiles > 0x7FFFFFFFu) continue;               /* (grid x: such a view runs its own launch) */
+		eligible[v] = 1; candidates++; tiles += view_tiles;
+		out.a = head.general;                                                   /* (what is not the grid is the same in every view) */
+	}
+	char text[160];
+	const bool take = candidates && (tiles >= kViewsMinTiles || (mode & 0x1000u));
+	if (take) {
+		uint32_t row_ends = 0, next = 0;
+		for (uint32_t v = 0; v < view_count; v++) {
+			if (!eligible[v]) continue;
+			const DasDecision &head = out.parts[v][0];
+			row_ends |= head.general.row_ends;
+			out.taken[v] = 1;
+			out.first_block.push_back(next);
+			next += rows[v].blocks[0] * rows[v].blocks[1] * rows[v].blocks[2];
+			out.rows.push_back(rows[v]);
+			out.das_launches--;                                             /* its single-frame launch does not run */
+		}
+		out.first_block.push_back(next);
+		out.kernel_views = candidates; out.kernel_tiles = tiles; out.das_launches++;
+		out.a.split_shift = 0; out.a.row_ends = row_ends;
+		std::snprintf(text, sizeof(text), "RCA family on the general kernel: %u of %u views, %u tiles, in one launch of the views kernel", candidates, view_count, tiles);
+	} else if (zero == view_count) {
+		std::snprintf(text, sizeof(text), "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared");
+	} else if (mode & 0x800u) {
+		std::snprintf(text, sizeof(text), "das path flag 0x800: each view's single-frame kernel on the shared DAS input was asked for");
+	} else if (family != BF_DAS_RCA) {
+		std::snprintf(text, sizeof(text), "the views kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per view");
+	} else if (!candidates) {
+		if (faster) std::snprintf(text, sizeof(text), "single frames on these grids run the %s: it runs once per view on the shared DAS input", das_path_name(faster_path));
+		else if (cut) std::snprintf(text, sizeof(text), "the row-end rule cuts the views into parts run by different kernels: the single-frame launches once per view");
+		else          std::snprintf(text, sizeof(text), "no view the views kernel can take: each runs its own launch");
+	} else {
+		std::snprintf(text, sizeof(text), "fewer than %u tiles in the eligible views: the single-frame general kernel once per view", kViewsMinTiles);
+	}
+	out.reason = text;
+}
+
 uint32_t row_end_planes(const std::vector<DasDecision> &parts)
 {
 	uint32_t n = 0;

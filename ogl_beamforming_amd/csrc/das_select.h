@@ -106,6 +106,36 @@ struct BurstDecision {
 void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const std::vector<DasDecision> &parts,
                   uint32_t z_first, uint32_t z_count, uint32_t mode, uint32_t frame_count, BurstDecision &out);
 
+/* das_views.hip takes the eligible views of a push when their 256-voxel tiles number at least this.  PROVISIONAL: the smallest tile
+ * count at which the views kernel is not slower than the per-view route by more than three times that route's run-to-run spread, to be
+ * read off profiles/views_rate.json (tools/views_rate.py) -- see the note beside that file in profiles/README.md. */
+constexpr uint32_t kViewsMinTiles = 2;
+
+/* One grid of a views push: BeamformerHipView without its tag. */
+struct ViewGrid {
+	float    transform[16];            /* as BeamformerParameters::das_voxel_transform */
+	uint32_t points[3];                /* each >= 1 */
+};
+/* The block's plan on a view's grid: `plan` with the view's points and voxel transform (FORCES / UFORCES: pre-multiplied by the transducer
+ * transform as build_plan does, beamformer_core.c:913-915).  What decide_das_parts takes for that view. */
+void plan_on_view(const ParameterBlock &pb, const ViewGrid &view, Plan &plan);
+
+/* How a views push runs (beamformer_hip_describe_views): every view gets its own decide_das_parts -- its single-frame decision, parts[v].
+ * A view is ELIGIBLE for das_views.hip when that decision is one part on the general kernel, the family is RCA and mode does not carry
+ * BeamformerHipDasPath_NoViewsKernel; the eligible views run in ONE launch when their 256-voxel tiles (no channel split) number at least
+ * kViewsMinTiles, or mode carries BeamformerHipDasPath_PreferViewsKernel.  Every other view runs its single-frame launch(es). */
+struct ViewsDecision {
+	std::vector<std::vector<DasDecision>> parts;      /* per view */
+	std::vector<uint8_t>   taken;                     /* per view: 1 = in the views kernel's launch */
+	std::vector<BfViewRow> rows;                      /* the taken views, in view order (out_offset: filled by the executor) */
+	std::vector<uint32_t>  first_block;               /* rows.size() + 1 */
+	uint32_t    kernel_views = 0, kernel_tiles = 0, das_launches = 0;
+	BfDasArgs   a{};                                  /* the views kernel's arguments: the general kernel's without grid and channel split */
+	std::string reason;
+};
+void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const ViewGrid *views, uint32_t view_count,
+                  uint32_t mode, ViewsDecision &out);
+
 /* planes of `parts` that took the fallback */
 uint32_t row_end_planes(const std::vector<DasDecision> &parts);
 /* the part with the most planes (what a frame "ran on" in one word) */

@@ -179,7 +179,12 @@ static void release_one_device(Device &d)
 	for (auto &b : d.rf) b.release();
 	for (auto &b : d.scratch) b.release();
 	d.ring.release(); d.pair_counter.release(); d.minmax_scratch.release(); d.sum_scratch.release();
-	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.burst = BurstRecord{}; d.staged_tables.release(); d.staged_violations.release();
+	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.burst = BurstRecord{};
+	d.views = ViewsRecord{}; d.views_table.release();
+	if (d.views_pinned) (void)hipHostFree(d.views_pinned);
+	if (d.views_copied) (void)hipEventDestroy(d.views_copied);
+	d.views_pinned = nullptr; d.views_copied = nullptr; d.views_copy_pending = false;
+	d.staged_tables.release(); d.staged_violations.release();
 	for (auto &g : d.frame_exec) { if (g) (void)hipGraphExecDestroy(g); g = nullptr; }
 	for (auto &g : d.graph_generation) g = 0;
 	for (auto &t : d.timing) {
@@ -295,26 +300,46 @@ static PlanState *commit_block(uint32_t block)
 	return &ps;
 }
 
-/* beamformer_frame_next (beamformer_core.c:440-466), for `count` frames of one size (a single push: one), contiguous in the ring: a run
- * that would straddle the end starts again at offset 0; the records it overwrites stop being exportable.  Consecutive ids, each frame's
- * timing slot named in its record.  Returns the first, or null when the run does not fit the ring. */
-static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count)
+/* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: all of
+ * `points` (a single push: one; a burst), or -- `views` given -- frame k of views[k]'s points and tag.  A run that would straddle the end
+ * starts again at offset 0; the records it overwrites stop being exportable.  Consecutive ids, each frame's timing slot named in its
+ * record.  Returns the first, or null when the run does not fit the ring; run_bytes: the bytes of the whole run. */
+static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count, const BeamformerHipView *views = nullptr,
+                                uint64_t *run_bytes = nullptr)
 {
 	Device &d = *g_context.cur;
 	const int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
-	const uint64_t bytes = round_up((uint64_t)points[0] * points[1] * points[2] * (uint64_t)bf_kind_byte_size[kind], 64);
-	if (count == 0 || bytes > d.ring.size / count) return nullptr;
-	if (d.ring_next_offset > d.ring.size - bytes * count) d.ring_next_offset = 0;
+	auto frame_bytes = [&](uint32_t k) {
+		const uint32_t *n = views ? views[k].output_points : points;
+		return round_up((uint64_t)n[0] * n[1] * n[2] * (uint64_t)bf_kind_byte_size[kind], 64);
+	};
+	if (count == 0) return nullptr;
+	uint64_t total = 0;
+	if (!views) {
+		if (frame_bytes(0) > d.ring.size / count) return nullptr;
+		total = frame_bytes(0) * count;
+	} else {
+		for (uint32_t k = 0; k < count; k++) {
+			total += frame_bytes(k);
+			if (total > d.ring.size) return nullptr;
+		}
+	}
+	if (run_bytes) *run_bytes = total;
+	if (d.ring_next_offset > d.ring.size - total) d.ring_next_offset = 0;
+	/* records whose storage the run reuses stop being exportable: one pass for the run's whole byte range (the run's own records are
+	 * written below, after it) */
+	for (FrameRecord &old : d.frames)
+		if (old.bytes && old.offset < d.ring_next_offset + total && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
 	FrameRecord *first = nullptr;
 	for (uint32_t k = 0; k < count; k++) {
+		const uint64_t bytes = frame_bytes(k);
+		const uint32_t *n = views ? views[k].output_points : points;
 		uint64_t id = d.frame_counter++;
 		FrameRecord *f = &d.frames[id % d.frames.size()];
-		/* records whose storage this frame reuses stop being exportable */
-		for (FrameRecord &old : d.frames)
-			if (old.bytes && old.offset < d.ring_next_offset + bytes && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
 		f->offset = d.ring_next_offset; f->bytes = bytes;
-		f->points[0] = points[0]; f->points[1] = points[1]; f->points[2] = points[2];
+		f->points[0] = n[0]; f->points[1] = n[1]; f->points[2] = n[2];
 		f->data_kind = kind; f->id = (uint32_t)id; f->block = block; f->failed = false;
+		f->tag = views ? views[k].image_plane_tag : 0u;
 		f->timing_slot = (int)(id % kTimingSlots);
 		d.ring_next_offset += bytes;
 		if (k == 0) first = f;
@@ -628,6 +653,13 @@ static void fill_das_fields(TimingSlot &t, uint64_t id, const std::vector<DasDec
 	t.violations_slot = violations_slot;
 }
 
+/* A views push's DAS stage: K grids, their route (das_select.h: decide_views). */
+struct ViewsWalk {
+	const BeamformerHipView *views;
+	uint32_t count;
+	const ViewsDecision *route;
+};
+
 /* What a walk over a plan runs on: `frames` frames, frame k of every buffer k * that buffer's stride further on (one frame: stride 0). */
 struct StageWalk {
 	uint32_t      frames;
@@ -638,11 +670,93 @@ struct StageWalk {
 	uint64_t      stage_stride;     /* 0: a stage may read its predecessor's whole buffer; else its frame's stride */
 	TimingSlot   &t;                /* owns the events; its ingest segment (or events[0]) is already recorded */
 	const BurstDecision *route;     /* a burst's DAS route (das_select.h); null: a single push */
+	const ViewsWalk *views = nullptr;   /* a views push: `frames` is 1 and the DAS stage writes views->count frames from its one input */
 };
+
+/* The DAS stage of a views push: K frames (ids first .., contiguous from out0, each rounded to 64 bytes) from the ONE DAS input `cur`.
+ * The views das_views.hip takes run in one launch -- their rows and the prefix table go through pinned memory on the push's stream
+ * ahead of it, read in place by a small kernel (no copy engine: bf_launch_views_table) --, then every other view runs its own single-frame launch(es): the kernels of a single push, on the shared input.
+ * With pair counting the geometry-only count follows, per view, in a segment of its own.  paths[k]: the kernel that ran view k. */
+static bool launch_views(PlanState *ps, const ViewsWalk &vw, const char *cur, char *out0, uint64_t first, uint64_t voxel_bytes, uint32_t das_kind,
+                         TimingSlot &t, hipStream_t s, std::vector<uint32_t> &paths, bool &counters_kept, bool &das_segment_done)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	const ViewsDecision &route = *vw.route;
+	const uint32_t K = vw.count;
+	bool ok = true;
+	std::vector<uint64_t> offset(K);
+	for (uint32_t k = 0; k < K; k++) offset[k] = d.frames[(first + k) % d.frames.size()].offset - d.frames[first % d.frames.size()].offset;
+	paths.assign(K, (uint32_t)DasPath_General);
+
+	if (route.kernel_views) {
+		const uint32_t n = route.kernel_views;
+		const size_t rows_bytes = sizeof(BfViewRow) * n, table_bytes = rows_bytes + sizeof(uint32_t) * (n + 1);
+		if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
+		BfViewRow *rows = (BfViewRow *)d.views_pinned;
+		for (uint32_t k = 0, r = 0; k < K; k++) {
+			if (!route.taken[k]) continue;
+			rows[r] = route.rows[r];
+			rows[r].out_offset = offset[k];
+			r++;
+		}
+		std::memcpy((char *)d.views_pinned + rows_bytes, route.first_block.data(), sizeof(uint32_t) * (n + 1));
+		void *mapped = nullptr;
+		ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
+		if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)table_bytes, s));
+		d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
+		ok &= d.views_copy_pending;
+		BfDasArgs a = route.a;
+		a.rf = cur; a.out = out0;
+		bind_tables(ps, a);
+		BfViewsArgs v{};
+		v.rows = (const BfViewRow *)d.views_table.ptr;
+		v.first_block = (const uint32_t *)((const char *)d.views_table.ptr + rows_bytes);
+		v.view_count = n;
+		if (ok) ok &= HIP_OK(bf_launch_das_views(&a, &v, route.first_block[n], s));
+	}
+	for (uint32_t k = 0; k < K; k++)
+		for (const DasDecision &dd : route.parts[k]) counters_kept |= !route.taken[k] && (dd.path == DasPath_Staged || dd.path == DasPath_Tile);
+	for (uint32_t k = 0; k < K && ok; k++) {
+		if (route.taken[k]) continue;
+		const std::vector<DasDecision> &parts = route.parts[k];
+		const DasDecision &head = main_part(parts);
+		paths[k] = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
+		uint32_t *frame_counters = nullptr;
+		if (counters_kept && K - k <= kTimingSlots) {
+			frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
+			ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
+		}
+		const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes;
+		ok &= launch_frame_parts(ps, parts, 0, plane_bytes, cur, out0 + offset[k], frame_counters, s, paths[k]);
+	}
+	if (c.count_pairs && ok) {
+		/* geometry-only recount of the apodization test, per view (the grids differ); its own segment so that it stays out of the DAS time */
+		segment(t, das_kind, s);
+		unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
+		for (uint32_t k = K > kTimingSlots ? K - kTimingSlots : 0; k < K && ok; k++) {
+			unsigned long long *mine = counters + (first + k) % kTimingSlots;
+			ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
+			for (const DasDecision &dd : route.parts[k]) {
+				if (!ok || dd.path == DasPath_Zero) continue;
+				BfDasArgs count = dd.general;
+				count.rf = cur; count.out = out0 + offset[k];
+				bind_tables(ps, count);
+				count.pair_counter = mine;
+				ok &= HIP_OK(bf_launch_das_count(&count, s));
+			}
+		}
+		segment(t, kStagePairCount, s);
+		t.counted = true;
+		das_segment_done = true;
+	}
+	return ok;
+}
 
 /* The stages of a plan over the frames of one push, in stream order: every pre-DAS stage ONE launch for all frames (launch_stage), then the
  * frames placed in the ring and the DAS stage -- a burst's kernel in one launch where its route says so, else each frame's own launch(es)
- * on its slice of the input -- with one timing segment per stage in w.t and the DAS fields of every frame's timing row. */
+ * on its slice of the input; a views push: K frames from the ONE input (launch_views) -- with one timing segment per stage in w.t and the
+ * DAS fields of every frame's timing row. */
 static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 {
 	Context &c = g_context;
@@ -652,6 +766,9 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	hipStream_t s = d.stream;
 	TimingSlot &t = w.t;
 	const uint32_t N = w.frames;
+	const ViewsWalk *vw = w.views;
+	const uint32_t F = vw ? vw->count : N;                  /* frames the walk queues */
+	std::vector<uint32_t> view_path;                        /* a views push: the kernel that ran each view */
 
 	const char *cur = (const char *)w.in;
 	uint64_t cur_stride = w.in_stride;
@@ -692,13 +809,23 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			cur = (const char *)out.ptr; cur_stride = w.stage_stride; cur_bound = (int64_t)(w.stage_stride ? w.stage_stride : out.size); toggle ^= 1;
 		}break;
 		case BeamformerShaderKind_DAS:{
-			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, N);
+			uint64_t run_bytes = 0;
+			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, vw ? vw->views : nullptr, &run_bytes);
 			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 			char *out0 = (char *)d.ring.ptr + frame0->offset;
 			const uint64_t frame_bytes = frame0->bytes;
-			if (poison && frame_bytes) ok &= HIP_OK(hipMemsetAsync(out0, 0xFF, frame_bytes * N, s));
-			if (!w.route) {              /* (beamformer_hip_copy_das_input serves single frames) */
+			if (poison && run_bytes) ok &= HIP_OK(hipMemsetAsync(out0, 0xFF, run_bytes, s));
+			if (!w.route) {              /* (beamformer_hip_copy_das_input serves single frames and views pushes) */
 				d.das_input = cur; d.das_input_bytes = (uint64_t)plan.das_samples * plan.acquisitions * plan.channels * voxel_bytes;   /* [channel][transmit][sample] */
+			}
+			if (vw) {
+				/* the third mode of this step: K outputs from one DAS input.  (Flag 0x2000: the step fails here, as a refused launch would --
+				 * the only way to a views push's tombstones that needs no device fault: everything a caller can get wrong is refused
+				 * before the ids are taken) */
+				if (c.das_path_mode & 0x2000u) return set_error(BeamformerLibErrorKind_InvalidAccess);
+				ran = &vw->route->parts[F - 1];
+				ok &= launch_views(ps, *vw, cur, out0, first, voxel_bytes, (uint32_t)st.kind, t, s, view_path, counters_kept, das_segment_done);
+				break;
 			}
 			if (zcount == 0) break;      /* more devices than planes: this device holds an empty slab of the frame */
 
@@ -763,14 +890,19 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		 * writes them).  A single push's frame is the block's whole grid whatever its shard -- with several devices on the ingest device,
 		 * the others holding an empty slab of it; a burst's frames are the shard's planes */
 		if (!w.route) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
-		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, N);
+		uint64_t run_bytes = 0;
+		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, vw ? vw->views : nullptr, &run_bytes);
 		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-		if (frame0->bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, frame0->bytes * N, s));
+		if (run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, run_bytes, s));
 	}
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	for (uint32_t k = 0; k < N; k++)
-		fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, ran, points, plan.iq_pipeline, das_path,
-		                counters_kept && N - k <= kTimingSlots ? (first + k) % kTimingSlots : ~0ull);
+	for (uint32_t k = 0; k < F; k++) {
+		const bool own_counters = counters_kept && F - k <= kTimingSlots;
+		if (vw) fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, ran ? &vw->route->parts[k] : nullptr, vw->views[k].output_points,
+		                        plan.iq_pipeline, ran ? view_path[k] : 0, own_counters ? (first + k) % kTimingSlots : ~0ull);
+		else    fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, ran, points, plan.iq_pipeline, das_path,
+		                        own_counters ? (first + k) % kTimingSlots : ~0ull);
+	}
 	return true;
 }
 
@@ -1112,6 +1244,26 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 	return done;
 }
 
+/* Every frame's row of the timing table after a push of N frames with ONE event set (a burst, a views push), in slot `owner`: the
+ * push's events, shared -- each row reports 1 / N of every stage time. */
+static void share_timing_rows(Device &d, uint64_t first, uint32_t N, uint32_t owner)
+{
+	const TimingSlot push = d.timing[owner];
+	for (uint32_t k = 0; k < N; k++) {
+		const uint64_t id = first + k;
+		TimingSlot &ft = d.timing[id % kTimingSlots];
+		ft.count = push.count; ft.counted = push.counted;
+		std::memcpy(ft.kinds, push.kinds, sizeof(ft.kinds));
+		ft.sampled = id % kTimingSlots == owner; ft.events_slot = owner; ft.share = N; ft.failed = false;
+	}
+	/* older unsampled frames whose row borrowed the events of the slot the push has taken over: their row goes blank rather than show
+	 * the push's times as one frame's */
+	for (uint32_t k = 0; k < kTimingSlots; k++) {
+		TimingSlot &old = d.timing[k];
+		if (old.frame_id < first && !old.sampled && old.events_slot == owner) old.count = 0;
+	}
+}
+
 /* beamformer_hip_push_data_burst_with_compute: frame_count RF frames of one parameter block in one call (one device).
  *   RF        the whole burst is one upload into one pinned slot -- over the copy engine into device staging when it is large, read in
  *             place over PCIe when small, by kOverlapBytes applied to the burst -- and lands in ONE slot of the RF ring,
@@ -1208,21 +1360,8 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	finish_upload(u, overlap, s);
 	if (!done) return false;
 
-	/* every frame's row of the timing table: the burst's events, shared */
-	const TimingSlot burst = t;
-	for (uint32_t k = 0; k < N; k++) {
-		const uint64_t id = first + k;
-		TimingSlot &ft = d.timing[id % kTimingSlots];
-		ft.count = burst.count; ft.counted = burst.counted;
-		std::memcpy(ft.kinds, burst.kinds, sizeof(ft.kinds));
-		ft.sampled = id % kTimingSlots == owner; ft.events_slot = owner; ft.share = N; ft.failed = false;
-	}
-	/* older unsampled frames whose row borrowed the events of the slot the burst has taken over: their row goes blank rather than show
-	 * the burst's times as one frame's */
-	for (uint32_t k = 0; k < kTimingSlots; k++) {
-		TimingSlot &old = d.timing[k];
-		if (old.frame_id < first && !old.sampled && old.events_slot == owner) old.count = 0;
-	}
+	share_timing_rows(d, first, N, owner);
+	d.views.valid = false;
 	d.burst.valid = true; d.burst.first_id = first; d.burst.count = N; d.burst.events_slot = owner; d.burst.route = route;
 	lockstep.complete = true;
 	return true;
@@ -1253,6 +1392,155 @@ bool last_burst_info(BeamformerHipBurstInfo *out)
 	}
 	float total = 0;
 	if (t.count && HIP_OK(hipEventElapsedTime(&total, t.events[0], t.events[t.count]))) out->burst_ms = total;
+	return true;
+}
+
+std::vector<ViewGrid> view_grids(const BeamformerHipView *views, uint32_t view_count)
+{
+	std::vector<ViewGrid> grids(view_count);
+	for (uint32_t k = 0; k < view_count; k++) {
+		std::memcpy(grids[k].transform, views[k].das_voxel_transform, sizeof(grids[k].transform));
+		for (int i = 0; i < 3; i++) grids[k].points[i] = views[k].output_points[i];
+	}
+	return grids;
+}
+
+/* beamformer_hip_describe_views / _get_last_views_info: a decision in the words of the C ABI */
+void describe_views_decision(const ViewsDecision &route, uint32_t view_count, BeamformerHipViewsDescription *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	out->kernel_views = route.kernel_views; out->das_launches = route.das_launches; out->min_tiles = kViewsMinTiles;
+	for (uint32_t k = 0; k < view_count && k < BEAMFORMER_HIP_MAX_VIEWS; k++) {
+		if (route.parts[k].empty()) { out->path[k] = -1; continue; }
+		const int path = main_part(route.parts[k]).path;
+		out->path[k] = (int8_t)(path == DasPath_Zero ? -2 : path);
+	}
+	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
+}
+
+/* beamformer_hip_push_data_views_with_compute: ONE RF frame beamformed on view_count grids (one device, no output shard).
+ *   RF        one upload into one pinned slot -- over the copy engine into device staging when it is large, read in place over PCIe when
+ *             small (kOverlapBytes) --, the ingest kernel, ONE slot of the RF ring;
+ *   stages    every pre-DAS stage ONE launch, as in a single push, on d.scratch[];
+ *   DAS       K frames from the one DAS input (launch_views): the views kernel's launch, then the other views' own;
+ *   frames    contiguous in the frame ring, each at its own 64-byte-rounded size, consecutive ids in view order;
+ *   timings   one event set for the push, in the timing slot of its last view; every view's slot points there with share = K.
+ * Everything that can be refused is checked, and every buffer whose absence would fail the push is grown, BEFORE the ids are taken: a
+ * refused push queues nothing.  (The tables some single-frame kernels keep -- staged_tables, hercules_table, hercules_pairs -- are grown
+ * where a view's launch asks for them, launch_das_part, each with a kernel to fall back on: growing one mid-push drains the device and
+ * fails nothing.)  After that a failure leaves tombstones under all of its ids. */
+bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ParameterBlock &pb = c.blocks[block];
+	hipStream_t s = d.stream;
+	const uint32_t K = view_count;
+	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const Plan &plan = ps->plan;
+
+	/* each view's own single-frame decision, and which of them the views kernel takes */
+	const auto decide_begin = std::chrono::steady_clock::now();
+	ViewsDecision route;
+	decide_views(pb, plan, ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, route);
+	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
+
+	/* the frames: contiguous in the ring */
+	uint64_t run_bytes = 0;
+	for (uint32_t k = 0; k < K; k++) {
+		const uint32_t *n = views[k].output_points;
+		run_bytes += round_up((uint64_t)n[0] * n[1] * n[2] * (plan.iq_pipeline ? 8u : 4u), 64);
+		if (run_bytes > d.ring.size) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+	}
+
+	/* device and pinned memory, grown before anything is queued */
+	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
+	const bool overlap = !data_on_device && size >= kOverlapBytes;
+	bool fits = d.rf[slot].ensure(round_up(l.rf_size, 64) + 64);
+	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(size, 64) + 64);
+	if (route.kernel_views) {
+		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
+		fits = fits && d.views_table.ensure(table_bytes);
+		if (fits && !d.views_pinned && !HIP_OK(hipHostMalloc(&d.views_pinned, table_bytes, hipHostMallocDefault))) { d.views_pinned = nullptr; fits = false; }
+		if (fits && !d.views_copied && !HIP_OK(hipEventCreateWithFlags(&d.views_copied, hipEventDisableTiming))) { d.views_copied = nullptr; fits = false; }
+	}
+	if (!fits) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
+	UploadSlot &u = d.upload[slot];
+	if (!claim_upload(u, size, !data_on_device)) return false;
+	const uint32_t owner = (uint32_t)((c.push_sequence + K - 1) % kTimingSlots);     /* the push's events: its LAST view's slot */
+	TimingSlot &t = d.timing[owner];
+	if (!ensure_events(t)) return false;
+	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	bool wants_counters = false;
+	for (uint32_t k = 0; k < K; k++)
+		for (const DasDecision &dd : route.parts[k]) wants_counters |= !route.taken[k] && (dd.path == DasPath_Staged || dd.path == DasPath_Tile);
+	if (wants_counters && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+
+	/* ---- from here on the push owns ids first .. first + K - 1 ---- */
+	d.rf_index++;
+	const uint64_t first = c.push_sequence;
+	c.push_sequence += K;
+	d.frame_counter = first;
+	d.burst.valid = false; d.views.valid = false;
+	Tombstones lockstep{c, first, K, 1, false};
+
+	t.failed = false; t.sampled = true; t.events_slot = owner; t.share = K; t.count = 0; t.counted = false;
+	d.have_sample = false;          /* the push's events cover K frames: a single frame that follows records its own */
+	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
+
+	/* ---- upload and ingest: a views push always runs the ingest kernel ---- */
+	const void *raw = data;
+	if (!data_on_device) {
+		raw = enqueue_upload(d, u, data, size, overlap ? d.raw_staging[slot].ptr : nullptr, size);
+		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, 1, 0, 0, s);
+	if (!data_on_device && !overlap) ok &= pinned_read_by(u, s);
+	segment(t, kStageIngest, s);
+	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	note_push_time();
+	d.last_rf = d.rf[slot].ptr; d.last_rf_bytes = l.rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
+
+	/* ---- the stages of a single push, then K frames from the one DAS input ---- */
+	const ViewsWalk vw{views, K, &route};
+	const bool done = walk_plan(block, ps, StageWalk{1, d.rf[slot].ptr, 0, (int64_t)d.rf[slot].size, d.scratch, 0, t, nullptr, &vw});
+	finish_upload(u, overlap, s);
+	if (!done) return false;
+
+	share_timing_rows(d, first, K, owner);
+	d.views.valid = true; d.views.first_id = first; d.views.count = K; d.views.events_slot = owner; d.views.decide_us = decide_us;
+	describe_views_decision(route, K, &d.views.route);
+	lockstep.complete = true;
+	return true;
+}
+
+/* beamformer_hip_get_last_views_info */
+bool last_views_info(BeamformerHipViewsInfo *out)
+{
+	Context &c = g_context;
+	std::memset(out, 0, sizeof(*out));
+	if (!c.device_ready) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	Device &d = c.devices[0];
+	const ViewsRecord &v = d.views;
+	/* the newest push must be that views push, complete */
+	if (!v.valid || d.frame_counter != v.first_id + v.count || !newest_record(d)) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!HIP_OK(hipSetDevice(d.device)) || !HIP_OK(hipStreamSynchronize(d.stream))) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	out->route = v.route;
+	out->first_frame_id = (uint32_t)v.first_id; out->view_count = v.count; out->decide_us = v.decide_us;
+	const TimingSlot &t = d.timing[v.events_slot];
+	out->stage_count = t.count;
+	for (uint32_t i = 0; i < t.count; i++) {
+		out->stage_kind[i] = t.kinds[i];
+		float ms = 0;
+		if (HIP_OK(hipEventElapsedTime(&ms, t.events[i], t.events[i + 1]))) out->stage_ms[i] = ms;
+	}
+	float total = 0;
+	if (t.count && HIP_OK(hipEventElapsedTime(&total, t.events[0], t.events[t.count]))) out->views_ms = total;
 	return true;
 }
 

@@ -157,6 +157,73 @@ bool push_burst_common(const void *data, uint32_t frame_size, uint32_t frame_cou
 	return push_burst(slot, data, frame_size, frame_count, on_device);
 }
 
+/* What a views call must satisfy that needs neither the RF nor a device: the count, the list, the block, every view's tag and extents. */
+bool validate_views(const BeamformerHipView *views, uint32_t view_count, uint32_t slot)
+{
+	Context &c = ctx();
+	if (!check(view_count != 0 && view_count <= BEAMFORMER_HIP_MAX_VIEWS, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(views != nullptr, BeamformerLibErrorKind_InvalidAccess)) return false;
+	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
+	for (uint32_t k = 0; k < view_count; k++) {
+		if (!check(views[k].image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
+		const uint32_t *n = views[k].output_points;
+		if (!check(n[0] != 0 && n[1] != 0 && n[2] != 0, BeamformerLibErrorKind_InvalidAccess)) return false;
+	}
+	return true;
+}
+
+/* all views together, each rounded to 64 bytes, in the frame ring (three 32-bit extents can wrap 64 bits: saturating) */
+bool views_fit_the_ring(const BeamformerHipView *views, uint32_t view_count, uint64_t voxel_bytes)
+{
+	const uint64_t ring = frame_ring_bytes();
+	uint64_t total = 0;
+	for (uint32_t k = 0; k < view_count; k++) {
+		const uint32_t *n = views[k].output_points;
+		const uint64_t plane = (uint64_t)n[0] * n[1];
+		if (plane > ring || plane * n[2] > ring / voxel_bytes) return false;
+		total += (plane * n[2] * voxel_bytes + 63) / 64 * 64;
+		if (total > ring) return false;
+	}
+	return true;
+}
+
+static_assert(BEAMFORMER_HIP_MAX_VIEWS <= BeamformerMaxBacklogFrames, "every view of a push keeps its frame record");
+
+/* A views push: the single push's checks of the RF (once), then what must hold for the views.  Everything that needs no device is judged
+ * before the device is touched, so that a malformed push is refused the same way on a machine without one. */
+bool push_views_common(const void *data, uint32_t data_size, const BeamformerHipView *views, uint32_t view_count, uint32_t slot, bool on_device)
+{
+	Context &c = ctx();
+	if (!validate_views(views, view_count, slot)) return false;
+	const ParameterBlock &pb = c.blocks[slot];
+	if (c.requested_count > 1 || (c.device_ready && c.device_count > 1)) {
+		std::fprintf(stderr, "[beamformer] a views push runs on one device: refused with the %u devices of beamformer_hip_set_devices\n",
+		             c.device_ready ? c.device_count : c.requested_count);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	if (pb.shard_z_count) {
+		std::fprintf(stderr, "[beamformer] a view is not sharded: refused with the output shard set on parameter block %u\n", slot);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	const BeamformerParameters &bp = pb.parameters;
+	const uint64_t max_rf_size = frame_ring_bytes() / 3;
+	const uint64_t bytes    = (uint64_t)bf_kind_byte_size[pb.data_kind];
+	const uint64_t rf_size  = (uint64_t)bp.acquisition_count * bp.sample_count * bp.channel_count * bytes;
+	const uint64_t raw_size = (uint64_t)bp.raw_data_dimensions[0] * bp.raw_data_dimensions[1] * bytes;
+	if (!check(data != nullptr, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(rf_size <= max_rf_size && rf_size <= UINT32_MAX, BeamformerLibErrorKind_RFDataSizeOverflow)) return false;
+	if (!check(rf_size <= data_size && (uint64_t)data_size == raw_size, BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	if (!check(rf_size > 0, BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	if (!check(bp.channel_count <= BeamformerMaxChannelCount && bp.acquisition_count <= BeamformerMaxEmissionsCount,
+	           BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	if (!check(views_fit_the_ring(views, view_count, plan.iq_pipeline ? 8u : 4u), BeamformerLibErrorKind_FrameSizeOverflow)) return false;
+	if (!ensure_device()) return false;
+	return push_views(slot, data, data_size, views, view_count, on_device);
+}
+
 template <typename T>
 uint32_t push_array(T *dst, size_t dst_count, const T *src, uint32_t count, uint32_t elements, uint32_t block, uint32_t dirty)
 {
@@ -545,6 +612,38 @@ uint32_t beamformer_hip_get_last_burst_info(BeamformerHipBurstInfo *out)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
 	return last_burst_info(out);
+}
+
+uint32_t beamformer_hip_push_data_views_with_compute(const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count,
+                                                     uint32_t parameter_slot)
+{
+	return push_views_common(data, size, views, view_count, parameter_slot, false);
+}
+
+uint32_t beamformer_hip_push_device_data_views_with_compute(const void *device_data, uint32_t size, const BeamformerHipView *views, uint32_t view_count,
+                                                            uint32_t parameter_slot)
+{
+	return push_views_common(device_data, size, views, view_count, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_describe_views(uint32_t parameter_slot, const BeamformerHipView *views, uint32_t view_count, BeamformerHipViewsDescription *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !validate_views(views, view_count, parameter_slot)) return 0;
+	Context &c = ctx();
+	const ParameterBlock &pb = c.blocks[parameter_slot];
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	ViewsDecision route;
+	decide_views(pb, plan, build_transmit_table(pb), view_grids(views, view_count).data(), view_count, c.das_path_mode, route);
+	describe_views_decision(route, view_count, out);
+	return 1;
+}
+
+uint32_t beamformer_hip_get_last_views_info(BeamformerHipViewsInfo *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
+	return last_views_info(out);
 }
 
 uint32_t beamformer_hip_synchronize(void)

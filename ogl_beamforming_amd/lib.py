@@ -106,6 +106,10 @@ def _load():
         "beamformer_hip_push_device_data_burst_with_compute": (u32, [vp, u32, u32, u32, u32]),
         "beamformer_hip_describe_burst": (u32, [u32, u32, C.POINTER(P.HipBurstDescription)]),
         "beamformer_hip_get_last_burst_info": (u32, [C.POINTER(P.HipBurstInfo)]),
+        "beamformer_hip_push_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
+        "beamformer_hip_push_device_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
+        "beamformer_hip_describe_views": (u32, [u32, C.POINTER(P.HipView), u32, C.POINTER(P.HipViewsDescription)]),
+        "beamformer_hip_get_last_views_info": (u32, [C.POINTER(P.HipViewsInfo)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -246,6 +250,90 @@ def last_burst_info():
     """beamformer_hip_get_last_burst_info: the newest burst's route, ids and whole-burst stage times; waits for it."""
     info = P.HipBurstInfo()
     _check(library().beamformer_hip_get_last_burst_info(C.byref(info)))
+    return info
+
+
+def view(points, lo, hi, plane=None, plane_offset=0.0, tag=0):
+    """A HipView of `points` voxels spanning lo .. hi: the grid configs' acquisitions are built on (configs._voxel_transform: a volume
+    when it has z planes, else a view plane with depth on image y -- plane "yz" for the YZ plane)."""
+    from . import configs
+    v = P.HipView()
+    v.das_voxel_transform[:] = [float(x) for x in configs._voxel_transform(points, lo, hi, plane, plane_offset)]
+    v.output_points[:] = [max(1, int(n)) for n in points]
+    v.image_plane_tag = int(tag)
+    return v
+
+
+def view_of(bp, tag=0):
+    """The HipView of a parameter struct's own grid."""
+    v = P.HipView()
+    v.das_voxel_transform[:] = list(bp.das_voxel_transform)
+    v.output_points[:] = [max(1, int(n)) for n in bp.output_points[:3]]
+    v.image_plane_tag = int(tag)
+    return v
+
+
+def _view_array(views):
+    views = list(views)
+    return (P.HipView * len(views))(*views), len(views)
+
+
+def get_last_views(views):
+    """The frames of the newest views push of these views, oldest first: a list of arrays (Z, Y, X), each of its view's size."""
+    lib = library()
+    info = P.HipFrameInfo()
+    _check(lib.beamformer_hip_get_last_frame_info(C.byref(info)))
+    complex_out = info.data_kind == int(P.DataKind.Float32Complex)
+    shapes = [(int(v.output_points[2]), int(v.output_points[1]), int(v.output_points[0])) for v in views]
+    sizes = [(int(np.prod(sh)) * (8 if complex_out else 4) + 63) // 64 * 64 for sh in shapes]     # each exported rounded up to 64 bytes
+    raw = np.zeros(sum(sizes) // 4, dtype=np.float32)
+    _check(lib.beamformer_get_last_frames(raw.ctypes.data_as(C.c_void_p), raw.nbytes, len(shapes)))
+    out, at = [], 0
+    for sh, size in zip(shapes, sizes):
+        voxels = int(np.prod(sh))
+        if complex_out:
+            out.append(raw[at // 4: at // 4 + 2 * voxels].view(np.complex64).reshape(sh).copy())
+        else:
+            out.append(raw[at // 4: at // 4 + voxels].reshape(sh).copy())
+        at += size
+    return out
+
+
+def beamform_views(bp, rf, views, filters=(), timeout_ms=-1, on_device_pointer=None):
+    """ONE RF frame on K grids in one call (beamformer_hip_push_data_views_with_compute): everything but the grid from `bp`, view k on
+    views[k] (HipView: see view()).  `rf` as beamform() takes it.  Returns a list of K arrays (Z, Y, X), in view order."""
+    lib = library()
+    for slot, fp in enumerate(filters):
+        if fp is not None:
+            _check(lib.beamformer_create_filter(C.byref(fp), slot, 0))
+    _check(lib.beamformer_push_simple_parameters(C.byref(bp)))
+    lib.beamformer_set_global_timeout(C.c_uint32(timeout_ms & 0xFFFFFFFF).value)
+    rf = np.ascontiguousarray(rf)
+    array, count = _view_array(views)
+    if on_device_pointer is not None:
+        _check(lib.beamformer_hip_push_device_data_views_with_compute(C.c_void_p(on_device_pointer), rf.nbytes, array, count, 0))
+    else:
+        _check(lib.beamformer_hip_push_data_views_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, array, count, 0))
+    return get_last_views(views)
+
+
+def describe_views(bp, views, filters=(), slot=0):
+    """What a views push of these grids would run (beamformer_hip_describe_views): the description struct; .path[k] is view k's own
+    single-frame decision, .reason says why this route.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    array, count = _view_array(views)
+    d = P.HipViewsDescription()
+    _check(L.beamformer_hip_describe_views(slot, array, count, C.byref(d)))
+    return d
+
+
+def last_views_info():
+    """beamformer_hip_get_last_views_info: the newest views push's route, ids and whole-push stage times; waits for it."""
+    info = P.HipViewsInfo()
+    _check(library().beamformer_hip_get_last_views_info(C.byref(info)))
     return info
 
 

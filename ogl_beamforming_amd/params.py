@@ -230,6 +230,28 @@ HIP_MAX_BURST_FRAMES = 1024
 HIP_DAS_PATH_NO_BURST_KERNEL = 0x400     # beamformer_hip_set_das_path flag: bursts run the single-frame DAS kernel once per frame
 
 
+HIP_MAX_VIEWS = 1024
+HIP_DAS_PATH_NO_VIEWS_KERNEL = 0x800      # beamformer_hip_set_das_path flag: a views push runs every view's single-frame DAS kernel
+HIP_DAS_PATH_PREFER_VIEWS_KERNEL = 0x1000 # ... flag: the views kernel takes the eligible views however few their tiles
+HIP_DAS_PATH_FAIL_VIEWS_DAS = 0x2000      # ... flag: a views push fails at its DAS stage, after its ids are taken (tombstones, for tests)
+
+
+class HipView(C.Structure):
+    """BeamformerHipView: one grid of a views push"""
+    _fields_ = [("das_voxel_transform", C.c_float * 16), ("output_points", C.c_uint32 * 3), ("image_plane_tag", C.c_uint32)]
+
+
+class HipViewsDescription(C.Structure):
+    _fields_ = [("kernel_views", C.c_uint32), ("das_launches", C.c_uint32), ("min_tiles", C.c_uint32),
+                ("path", C.c_int8 * HIP_MAX_VIEWS), ("reason", C.c_char * 160)]
+
+
+class HipViewsInfo(C.Structure):
+    _fields_ = [("route", HipViewsDescription), ("first_frame_id", C.c_uint32), ("view_count", C.c_uint32), ("stage_count", C.c_uint32),
+                ("stage_kind", C.c_uint32 * HIP_MAX_TIMED_STAGES), ("stage_ms", C.c_float * HIP_MAX_TIMED_STAGES), ("views_ms", C.c_float),
+                ("decide_us", C.c_float)]
+
+
 class DasPath(enum.IntEnum):
     """BeamformerHipFrameTimings::das_path / BeamformerHipDasDescription::path (csrc/das_select.h)"""
     General = 0
