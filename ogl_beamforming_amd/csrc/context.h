@@ -56,7 +56,7 @@ struct TimingSlot {
 	bool       created = false;
 	bool       sampled = true;       /* false: this frame recorded no events; events_slot names the slot whose events stand in */
 	uint32_t   events_slot = 0;
-	uint32_t   share = 1;            /* frames the events of events_slot cover: a frame of a burst reports 1 / share of each time (push_burst) */
+	uint32_t   share = 1;            /* frames the events of events_slot cover: a frame of a burst reports 1 / share of each time (push_frames) */
 	uint64_t   das_voxels = 0;
 	uint32_t   das_taps = 0, das_sample_bytes = 0, das_path = 0;
 	bool       counted = false;
@@ -66,21 +66,14 @@ struct TimingSlot {
 	bool       failed = false;            /* the push that owns this slot did not complete */
 };
 
-/* the newest burst (executor.cpp push_burst): what beamformer_hip_get_last_burst_info reports */
-struct BurstRecord {
-	bool          valid = false;
+/* the newest multi-frame push (executor.cpp push_frames): what beamformer_hip_get_last_burst_info / _views_info report, each of its own kind */
+struct PushRecord {
+	enum Kind { None, Burst, Views } kind = None;
 	uint64_t      first_id = 0;
 	uint32_t      count = 0, events_slot = 0;
-	BurstDecision route;
-};
-
-/* the newest views push (executor.cpp push_views): what beamformer_hip_get_last_views_info reports */
-struct ViewsRecord {
-	bool        valid = false;
-	uint64_t    first_id = 0;
-	uint32_t    count = 0, events_slot = 0;
-	BeamformerHipViewsDescription route{};
-	float       decide_us = 0;
+	BurstDecision burst;                      /* Burst: its route */
+	BeamformerHipViewsDescription views{};    /* Views: its route, and the host time spent deciding it */
+	float         decide_us = 0;
 };
 
 struct PlanState {
@@ -104,6 +97,24 @@ constexpr uint32_t kStagePairCount = 0xFFFE;
 
 constexpr uint32_t kMaxDevices = 8;      /* one node of MI355X */
 
+/* The bytes of a run of `count` frames, contiguous in the frame ring, each rounded to 64 bytes: `count` frames of `points` voxels, or --
+ * `views` given -- frame k of views[k]'s.  Host arithmetic only, saturating (three 32-bit extents can wrap 64 bits).  False: the run
+ * does not fit `ring` bytes. */
+inline bool frame_run_bytes(const uint32_t points[3], const BeamformerHipView *views, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total)
+{
+	const uint32_t distinct = views ? count : 1u, each = views ? 1u : count;      /* equal frames: one size, `count` times */
+	total = 0;
+	for (uint32_t k = 0; k < distinct; k++) {
+		const uint32_t *n = views ? views[k].output_points : points;
+		const uint64_t plane = (uint64_t)n[0] * n[1];
+		if (plane > ring || plane * n[2] > ring / voxel_bytes) return false;
+		const uint64_t frame = (plane * n[2] * voxel_bytes + 63) / 64 * 64;
+		if (each && frame > (ring - total) / each) return false;
+		total += frame * each;
+	}
+	return true;
+}
+
 /* Everything that lives on one HIP device.  A process normally owns one (devices[0]); after
  * beamformer_hip_set_devices it owns several, each beamforming one z-slab of every frame. */
 struct Device {
@@ -126,10 +137,9 @@ struct Device {
 	bool         have_sample = false;
 	uint64_t     replan_frame = 0;                             /* first frame of the current plan */
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
-	DeviceBuffer burst_stage[2];                               /* push_burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
-	BurstRecord  burst;
-	ViewsRecord  views;
-	DeviceBuffer views_table;                                  /* push_views: the BfViewRows and the prefix table das_views.hip reads */
+	DeviceBuffer burst_stage[2];                               /* a burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
+	PushRecord   multi;
+	DeviceBuffer views_table;                                  /* a views push: the BfViewRows and the prefix table das_views.hip reads */
 	void        *views_pinned = nullptr;                       /* ... and the pinned memory they are sent from, free again once views_copied has passed */
 	hipEvent_t   views_copied = nullptr;
 	bool         views_copy_pending = false;

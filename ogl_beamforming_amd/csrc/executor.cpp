@@ -179,8 +179,8 @@ static void release_one_device(Device &d)
 	for (auto &b : d.rf) b.release();
 	for (auto &b : d.scratch) b.release();
 	d.ring.release(); d.pair_counter.release(); d.minmax_scratch.release(); d.sum_scratch.release();
-	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.burst = BurstRecord{};
-	d.views = ViewsRecord{}; d.views_table.release();
+	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.multi = PushRecord{};
+	d.views_table.release();
 	if (d.views_pinned) (void)hipHostFree(d.views_pinned);
 	if (d.views_copied) (void)hipEventDestroy(d.views_copied);
 	d.views_pinned = nullptr; d.views_copied = nullptr; d.views_copy_pending = false;
@@ -303,28 +303,12 @@ static PlanState *commit_block(uint32_t block)
 /* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: all of
  * `points` (a single push: one; a burst), or -- `views` given -- frame k of views[k]'s points and tag.  A run that would straddle the end
  * starts again at offset 0; the records it overwrites stop being exportable.  Consecutive ids, each frame's timing slot named in its
- * record.  Returns the first, or null when the run does not fit the ring; run_bytes: the bytes of the whole run. */
-static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count, const BeamformerHipView *views = nullptr,
-                                uint64_t *run_bytes = nullptr)
+ * record.  Returns the first, or null when the run does not fit the ring; total: the bytes of the whole run (frame_run_bytes). */
+static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count, const BeamformerHipView *views, uint64_t &total)
 {
 	Device &d = *g_context.cur;
 	const int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
-	auto frame_bytes = [&](uint32_t k) {
-		const uint32_t *n = views ? views[k].output_points : points;
-		return round_up((uint64_t)n[0] * n[1] * n[2] * (uint64_t)bf_kind_byte_size[kind], 64);
-	};
-	if (count == 0) return nullptr;
-	uint64_t total = 0;
-	if (!views) {
-		if (frame_bytes(0) > d.ring.size / count) return nullptr;
-		total = frame_bytes(0) * count;
-	} else {
-		for (uint32_t k = 0; k < count; k++) {
-			total += frame_bytes(k);
-			if (total > d.ring.size) return nullptr;
-		}
-	}
-	if (run_bytes) *run_bytes = total;
+	if (count == 0 || !frame_run_bytes(points, views, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total)) return nullptr;
 	if (d.ring_next_offset > d.ring.size - total) d.ring_next_offset = 0;
 	/* records whose storage the run reuses stop being exportable: one pass for the run's whole byte range (the run's own records are
 	 * written below, after it) */
@@ -332,8 +316,8 @@ static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, ui
 		if (old.bytes && old.offset < d.ring_next_offset + total && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
 	FrameRecord *first = nullptr;
 	for (uint32_t k = 0; k < count; k++) {
-		const uint64_t bytes = frame_bytes(k);
 		const uint32_t *n = views ? views[k].output_points : points;
+		const uint64_t bytes = round_up((uint64_t)n[0] * n[1] * n[2] * (uint64_t)bf_kind_byte_size[kind], 64);
 		uint64_t id = d.frame_counter++;
 		FrameRecord *f = &d.frames[id % d.frames.size()];
 		f->offset = d.ring_next_offset; f->bytes = bytes;
@@ -653,14 +637,7 @@ static void fill_das_fields(TimingSlot &t, uint64_t id, const std::vector<DasDec
 	t.violations_slot = violations_slot;
 }
 
-/* A views push's DAS stage: K grids, their route (das_select.h: decide_views). */
-struct ViewsWalk {
-	const BeamformerHipView *views;
-	uint32_t count;
-	const ViewsDecision *route;
-};
-
-/* What a walk over a plan runs on: `frames` frames, frame k of every buffer k * that buffer's stride further on (one frame: stride 0). */
+/* What a walk over a plan runs on: `frames` RF frames, frame k of every buffer k * that buffer's stride further on (one frame: stride 0). */
 struct StageWalk {
 	uint32_t      frames;
 	const void   *in;               /* the first stage's input, and what it may read of a frame there */
@@ -669,94 +646,80 @@ struct StageWalk {
 	DeviceBuffer *stage;            /* the ping-pong pair the pre-DAS stages write */
 	uint64_t      stage_stride;     /* 0: a stage may read its predecessor's whole buffer; else its frame's stride */
 	TimingSlot   &t;                /* owns the events; its ingest segment (or events[0]) is already recorded */
-	const BurstDecision *route;     /* a burst's DAS route (das_select.h); null: a single push */
-	const ViewsWalk *views = nullptr;   /* a views push: `frames` is 1 and the DAS stage writes views->count frames from its one input */
+	const BurstDecision *route;     /* a burst's DAS route (das_select.h); null: a single push, a views push */
+	const BeamformerHipView *views = nullptr;     /* a views push: `frames` is 1 and the DAS stage writes view_count frames from its one input, */
+	uint32_t             view_count = 0;
+	const ViewsDecision *views_route = nullptr;   /* by this route (das_select.h: decide_views) */
 };
 
-/* The DAS stage of a views push: K frames (ids first .., contiguous from out0, each rounded to 64 bytes) from the ONE DAS input `cur`.
- * The views das_views.hip takes run in one launch -- their rows and the prefix table go through pinned memory on the push's stream
- * ahead of it, read in place by a small kernel (no copy engine: bf_launch_views_table) --, then every other view runs its own single-frame launch(es): the kernels of a single push, on the shared input.
- * With pair counting the geometry-only count follows, per view, in a segment of its own.  paths[k]: the kernel that ran view k. */
-static bool launch_views(PlanState *ps, const ViewsWalk &vw, const char *cur, char *out0, uint64_t first, uint64_t voxel_bytes, uint32_t das_kind,
-                         TimingSlot &t, hipStream_t s, std::vector<uint32_t> &paths, bool &counters_kept, bool &das_segment_done)
-{
-	Context &c = g_context;
-	Device  &d = *c.cur;
-	const ViewsDecision &route = *vw.route;
-	const uint32_t K = vw.count;
-	bool ok = true;
-	std::vector<uint64_t> offset(K);
-	for (uint32_t k = 0; k < K; k++) offset[k] = d.frames[(first + k) % d.frames.size()].offset - d.frames[first % d.frames.size()].offset;
-	paths.assign(K, (uint32_t)DasPath_General);
+/* One frame the DAS stage writes: what it reads, where it writes, the parts that compute it (das_select.h) on which grid, whether the
+ * push's fused launch (a burst's kernel, the views kernel) covers it; path: the kernel that ran its main part. */
+struct DasJob {
+	const char     *in;
+	char           *out;
+	const std::vector<DasDecision> *parts;
+	uint32_t        z_first;
+	const uint32_t *points;
+	bool            fused;
+	uint32_t        path;
+};
 
-	if (route.kernel_views) {
-		const uint32_t n = route.kernel_views;
-		const size_t rows_bytes = sizeof(BfViewRow) * n, table_bytes = rows_bytes + sizeof(uint32_t) * (n + 1);
-		if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
-		BfViewRow *rows = (BfViewRow *)d.views_pinned;
-		for (uint32_t k = 0, r = 0; k < K; k++) {
-			if (!route.taken[k]) continue;
-			rows[r] = route.rows[r];
-			rows[r].out_offset = offset[k];
-			r++;
-		}
-		std::memcpy((char *)d.views_pinned + rows_bytes, route.first_block.data(), sizeof(uint32_t) * (n + 1));
-		void *mapped = nullptr;
-		ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
-		if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)table_bytes, s));
-		d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
-		ok &= d.views_copy_pending;
-		BfDasArgs a = route.a;
-		a.rf = cur; a.out = out0;
-		bind_tables(ps, a);
-		BfViewsArgs v{};
-		v.rows = (const BfViewRow *)d.views_table.ptr;
-		v.first_block = (const uint32_t *)((const char *)d.views_table.ptr + rows_bytes);
-		v.view_count = n;
-		if (ok) ok &= HIP_OK(bf_launch_das_views(&a, &v, route.first_block[n], s));
+/* The burst kernel (das_burst.hip): N frames, frame k at k * the strides of input and output, in one launch. */
+static bool launch_burst_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, uint32_t N, uint64_t in_stride, uint64_t out_stride, hipStream_t s)
+{
+	BfDasArgs a = route.a;
+	a.rf = first.in; a.out = first.out;
+	bind_tables(ps, a);
+	BfBurstArgs b{};
+	b.frame_count = N; b.rf_stride = in_stride; b.out_stride = out_stride;
+	return HIP_OK(bf_launch_das_burst(&a, &b, s));
+}
+
+/* The views kernel (das_views.hip): the views the route has it take, from the ONE DAS input, in one launch -- their rows and the prefix
+ * table go through pinned memory on the push's stream ahead of it, read in place by a small kernel (no copy engine: bf_launch_views_table). */
+static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const DasJob *jobs, uint32_t K, hipStream_t s)
+{
+	Device &d = *g_context.cur;
+	bool ok = true;
+	const uint32_t n = route.kernel_views;
+	const size_t rows_bytes = sizeof(BfViewRow) * n, table_bytes = rows_bytes + sizeof(uint32_t) * (n + 1);
+	if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
+	BfViewRow *rows = (BfViewRow *)d.views_pinned;
+	for (uint32_t k = 0, r = 0; k < K; k++) {
+		if (!route.taken[k]) continue;
+		rows[r] = route.rows[r];
+		rows[r].out_offset = (uint64_t)(jobs[k].out - jobs[0].out);
+		r++;
 	}
-	for (uint32_t k = 0; k < K; k++)
-		for (const DasDecision &dd : route.parts[k]) counters_kept |= !route.taken[k] && (dd.path == DasPath_Staged || dd.path == DasPath_Tile);
-	for (uint32_t k = 0; k < K && ok; k++) {
-		if (route.taken[k]) continue;
-		const std::vector<DasDecision> &parts = route.parts[k];
-		const DasDecision &head = main_part(parts);
-		paths[k] = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
-		uint32_t *frame_counters = nullptr;
-		if (counters_kept && K - k <= kTimingSlots) {
-			frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
-			ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
-		}
-		const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes;
-		ok &= launch_frame_parts(ps, parts, 0, plane_bytes, cur, out0 + offset[k], frame_counters, s, paths[k]);
-	}
-	if (c.count_pairs && ok) {
-		/* geometry-only recount of the apodization test, per view (the grids differ); its own segment so that it stays out of the DAS time */
-		segment(t, das_kind, s);
-		unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
-		for (uint32_t k = K > kTimingSlots ? K - kTimingSlots : 0; k < K && ok; k++) {
-			unsigned long long *mine = counters + (first + k) % kTimingSlots;
-			ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
-			for (const DasDecision &dd : route.parts[k]) {
-				if (!ok || dd.path == DasPath_Zero) continue;
-				BfDasArgs count = dd.general;
-				count.rf = cur; count.out = out0 + offset[k];
-				bind_tables(ps, count);
-				count.pair_counter = mine;
-				ok &= HIP_OK(bf_launch_das_count(&count, s));
-			}
-		}
-		segment(t, kStagePairCount, s);
-		t.counted = true;
-		das_segment_done = true;
-	}
+	std::memcpy((char *)d.views_pinned + rows_bytes, route.first_block.data(), sizeof(uint32_t) * (n + 1));
+	void *mapped = nullptr;
+	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
+	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)table_bytes, s));
+	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
+	ok &= d.views_copy_pending;
+	BfDasArgs a = route.a;
+	a.rf = jobs[0].in; a.out = jobs[0].out;
+	bind_tables(ps, a);
+	BfViewsArgs v{};
+	v.rows = (const BfViewRow *)d.views_table.ptr;
+	v.first_block = (const uint32_t *)((const char *)d.views_table.ptr + rows_bytes);
+	v.view_count = n;
+	if (ok) ok &= HIP_OK(bf_launch_das_views(&a, &v, route.first_block[n], s));
 	return ok;
 }
 
-/* The stages of a plan over the frames of one push, in stream order: every pre-DAS stage ONE launch for all frames (launch_stage), then the
- * frames placed in the ring and the DAS stage -- a burst's kernel in one launch where its route says so, else each frame's own launch(es)
- * on its slice of the input; a views push: K frames from the ONE input (launch_views) -- with one timing segment per stage in w.t and the
- * DAS fields of every frame's timing row. */
+/* a frame's parts keep the per-frame counters: [0] staged window violations, [1] / [2] das_tile.hip's staged / gathered chunks */
+static bool keeps_counters(const std::vector<DasDecision> &parts)
+{
+	for (const DasDecision &dd : parts) if (dd.path == DasPath_Staged || dd.path == DasPath_Tile) return true;
+	return false;
+}
+
+/* The stages of a plan over the frames of one push, in stream order: every pre-DAS stage ONE launch for all RF frames (launch_stage), then
+ * the frames placed in the ring and the DAS stage as a list of jobs, one per frame -- a single push: one; a burst: N, frame k on its slice
+ * of the input; a views push: K grids on the ONE input --: the push's fused launch for the jobs its route gives it, each other job's own
+ * launch(es), the pair count per run of jobs with the same parts -- with one timing segment per stage in w.t and the DAS fields of every
+ * frame's timing row. */
 static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 {
 	Context &c = g_context;
@@ -766,9 +729,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	hipStream_t s = d.stream;
 	TimingSlot &t = w.t;
 	const uint32_t N = w.frames;
-	const ViewsWalk *vw = w.views;
-	const uint32_t F = vw ? vw->count : N;                  /* frames the walk queues */
-	std::vector<uint32_t> view_path;                        /* a views push: the kernel that ran each view */
+	const uint32_t F = w.views ? w.view_count : N;          /* frames the walk queues */
 
 	const char *cur = (const char *)w.in;
 	uint64_t cur_stride = w.in_stride;
@@ -783,9 +744,9 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
 	const uint64_t voxel_bytes = plan.iq_pipeline ? 8u : 4u;
 	const uint64_t first = d.frame_counter;                 /* the id of the walk's first frame */
-	const std::vector<DasDecision> *ran = nullptr;          /* the parts of the DAS stage, once it has run */
-	uint32_t das_path = 0;
-	bool counters_kept = false;
+	DasJob one{}, *jobs = nullptr;                          /* the DAS stage's jobs, once it has run (a single push: no allocation) */
+	std::vector<DasJob> many;
+	bool counters_kept = false;                             /* some job that is not fused has a Staged or Tile part */
 
 	/* hook SCRATCH_POISON: both intermediate buffers, and below the frames' ring slots once next_frames has placed them (nothing writes
 	 * them before the DAS stage), are filled with 0xFF bytes -- NaN in binary16 and in f32 -- so that an element a stage reads without
@@ -810,71 +771,79 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		}break;
 		case BeamformerShaderKind_DAS:{
 			uint64_t run_bytes = 0;
-			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, vw ? vw->views : nullptr, &run_bytes);
+			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes);
 			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-			char *out0 = (char *)d.ring.ptr + frame0->offset;
-			const uint64_t frame_bytes = frame0->bytes;
-			if (poison && run_bytes) ok &= HIP_OK(hipMemsetAsync(out0, 0xFF, run_bytes, s));
-			if (!w.route) {              /* (beamformer_hip_copy_das_input serves single frames and views pushes) */
+			if (poison && run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0xFF, run_bytes, s));
+			if (N == 1) {                /* all jobs share one input (beamformer_hip_copy_das_input serves single frames and views pushes) */
 				d.das_input = cur; d.das_input_bytes = (uint64_t)plan.das_samples * plan.acquisitions * plan.channels * voxel_bytes;   /* [channel][transmit][sample] */
 			}
-			if (vw) {
-				/* the third mode of this step: K outputs from one DAS input.  (Flag 0x2000: the step fails here, as a refused launch would --
-				 * the only way to a views push's tombstones that needs no device fault: everything a caller can get wrong is refused
-				 * before the ids are taken) */
-				if (c.das_path_mode & 0x2000u) return set_error(BeamformerLibErrorKind_InvalidAccess);
-				ran = &vw->route->parts[F - 1];
-				ok &= launch_views(ps, *vw, cur, out0, first, voxel_bytes, (uint32_t)st.kind, t, s, view_path, counters_kept, das_segment_done);
-				break;
-			}
+			/* (Flag 0x2000: a views push's step fails here, as a refused launch would -- the only way to a views push's tombstones that
+			 * needs no device fault: everything a caller can get wrong is refused before the ids are taken) */
+			if (w.views && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
 			if (zcount == 0) break;      /* more devices than planes: this device holds an empty slab of the frame */
 
-			/* which kernel, with which geometry: one table of rules (das_select.cpp), computed once per plan / shard / path mode / hook
-			 * change and reused by every frame after it.  Usually ONE launch; where a term of the frame can reach an end of its RF row
-			 * the z range is cut and the planes concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
-			const std::vector<DasDecision> &parts = frame_das_parts(ps, pb, zfirst, zcount);
-			const DasDecision &head = main_part(parts);
-			ran = &parts;
-			das_path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
-			const uint64_t plane_bytes = (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes;
-			if (w.route && w.route->burst_kernel) {
-				BfDasArgs a = w.route->a;
-				a.rf = cur; a.out = out0;
-				bind_tables(ps, a);
-				BfBurstArgs b{};
-				b.frame_count = N; b.rf_stride = cur_stride; b.out_stride = frame_bytes;
-				ok &= HIP_OK(bf_launch_das_burst(&a, &b, s));
-			} else {
-				/* [0] staged window violations, [1] / [2] das_tile.hip's staged / gathered chunks: one set per timing slot */
-				for (const DasDecision &dd : parts) counters_kept |= dd.path == DasPath_Staged || dd.path == DasPath_Tile;
-				if (counters_kept && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) ok = false;
-				for (uint32_t k = 0; k < N && ok; k++) {
-					uint32_t *frame_counters = nullptr;
-					if (counters_kept && N - k <= kTimingSlots) {        /* the table keeps the newest 32 frames: older ones of a long burst count nothing */
-						frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
-						ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
-					}
-					ok &= launch_frame_parts(ps, parts, zfirst, plane_bytes, cur + k * cur_stride, out0 + k * frame_bytes, frame_counters, s, das_path);
-				}
+			/* ---- the jobs.  Which kernel, with which geometry: one table of rules (das_select.cpp), for a single push and a burst computed
+			 * once per plan / shard / path mode / hook change and reused by every frame after it, for a views push per view by its route.
+			 * Usually ONE launch per job; where a term of the frame can reach an end of its RF row the z range is cut and the planes
+			 * concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
+			if (F > 1) many.resize(F);
+			jobs = F > 1 ? many.data() : &one;
+			const std::vector<DasDecision> *cached = w.views ? nullptr : &frame_das_parts(ps, pb, zfirst, zcount);
+			bool any_fused = false, any_counted = false;
+			for (uint32_t k = 0; k < F; k++) {
+				DasJob &j = jobs[k];
+				j.in  = cur + k * cur_stride;
+				j.out = (char *)d.ring.ptr + d.frames[(first + k) % d.frames.size()].offset;
+				if (w.views) { j.parts = &w.views_route->parts[k]; j.z_first = 0; j.points = w.views[k].output_points; j.fused = w.views_route->taken[k] != 0; }
+				else         { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
+				const DasDecision &head = main_part(*j.parts);
+				j.path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
+				any_fused     |= j.fused;
+				any_counted   |= head.path != DasPath_Zero;
+				counters_kept |= !j.fused && keeps_counters(*j.parts);
 			}
-			if (c.count_pairs && head.path != DasPath_Zero) {
-				/* geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is the
-				 * same for every frame of the walk: it runs once, into the last frame's counter, and the other frames' counters are copies */
+
+			/* ---- 1. the push's fused launch */
+			if (any_fused) ok &= w.views ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
+			                             : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
+			/* ---- 2. every other job's own launch(es): the kernels of a single push.  One set of counters per timing slot */
+			if (counters_kept && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) ok = false;
+			for (uint32_t k = 0; k < F && ok; k++) {
+				DasJob &j = jobs[k];
+				if (j.fused) continue;
+				uint32_t *frame_counters = nullptr;
+				if (counters_kept && F - k <= kTimingSlots) {        /* the table keeps the newest 32 frames: older ones of a long push count nothing */
+					frame_counters = (uint32_t *)d.staged_violations.ptr + 4 * ((first + k) % kTimingSlots);
+					ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
+				}
+				const DasDecision &head = main_part(*j.parts);
+				ok &= launch_frame_parts(ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path);
+			}
+			/* ---- 3. geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is
+			 * the same for every job of a run of jobs with the same parts (a burst: one run; a views push: one per view): it runs once,
+			 * into the counter of the run's last frame, and the run's other frames' counters are copies -- the newest 32 frames only */
+			if (c.count_pairs && any_counted) {
 				segment(t, (uint32_t)st.kind, s);
 				ok &= d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2));
 				unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
-				unsigned long long *mine = counters + (first + N - 1) % kTimingSlots;
-				if (ok) ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
-				for (const DasDecision &dd : parts) {
-					if (!ok) break;
-					BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
-					count.rf = cur; count.out = out0 + (uint64_t)(dd.z_first - zfirst) * plane_bytes;
-					bind_tables(ps, count);
-					count.pair_counter = mine;
-					ok &= HIP_OK(bf_launch_das_count(&count, s));
+				for (uint32_t begin = 0, end; begin < F && ok; begin = end) {
+					for (end = begin + 1; end < F && jobs[end].parts == jobs[begin].parts; end++) {}
+					if (F - (end - 1) > kTimingSlots) continue;
+					const DasJob &j = jobs[begin];
+					unsigned long long *mine = counters + (first + end - 1) % kTimingSlots;
+					ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
+					const DasDecision &head = main_part(*j.parts);
+					for (const DasDecision &dd : *j.parts) {
+						if (!ok || dd.path == DasPath_Zero) continue;
+						BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
+						count.rf = j.in; count.out = j.out + (uint64_t)(dd.z_first - j.z_first) * head.a.size[0] * head.a.size[1] * voxel_bytes;
+						bind_tables(ps, count);
+						count.pair_counter = mine;
+						ok &= HIP_OK(bf_launch_das_count(&count, s));
+					}
+					for (uint32_t k = end - 1; k-- > begin && F - k <= kTimingSlots && ok;)
+						ok &= HIP_OK(hipMemcpyAsync(counters + (first + k) % kTimingSlots, mine, sizeof(*mine), hipMemcpyDeviceToDevice, s));
 				}
-				for (uint32_t k = 0; k + 1 < N && k + 1 < kTimingSlots && ok; k++)
-					ok &= HIP_OK(hipMemcpyAsync(counters + (first + N - 2 - k) % kTimingSlots, mine, sizeof(*mine), hipMemcpyDeviceToDevice, s));
 				segment(t, kStagePairCount, s);
 				t.counted = true;
 				das_segment_done = true;
@@ -891,17 +860,16 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		 * the others holding an empty slab of it; a burst's frames are the shard's planes */
 		if (!w.route) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
 		uint64_t run_bytes = 0;
-		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, vw ? vw->views : nullptr, &run_bytes);
+		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes);
 		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 		if (run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, run_bytes, s));
 	}
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	for (uint32_t k = 0; k < F; k++) {
 		const bool own_counters = counters_kept && F - k <= kTimingSlots;
-		if (vw) fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, ran ? &vw->route->parts[k] : nullptr, vw->views[k].output_points,
-		                        plan.iq_pipeline, ran ? view_path[k] : 0, own_counters ? (first + k) % kTimingSlots : ~0ull);
-		else    fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, ran, points, plan.iq_pipeline, das_path,
-		                        own_counters ? (first + k) % kTimingSlots : ~0ull);
+		const DasJob *j = jobs ? &jobs[k] : nullptr;         /* null: no DAS kernel ran for the frame */
+		fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, j ? j->parts : nullptr, j ? j->points : points, plan.iq_pipeline,
+		                j ? j->path : 0, own_counters ? (first + k) % kTimingSlots : ~0ull);
 	}
 	return true;
 }
@@ -1244,8 +1212,8 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 	return done;
 }
 
-/* Every frame's row of the timing table after a push of N frames with ONE event set (a burst, a views push), in slot `owner`: the
- * push's events, shared -- each row reports 1 / N of every stage time. */
+/* Every frame's row of the timing table after a push of N frames with ONE event set, in slot `owner`: the push's events, shared -- each
+ * row reports 1 / N of every stage time. */
 static void share_timing_rows(Device &d, uint64_t first, uint32_t N, uint32_t owner)
 {
 	const TimingSlot push = d.timing[owner];
@@ -1264,24 +1232,131 @@ static void share_timing_rows(Device &d, uint64_t first, uint32_t N, uint32_t ow
 	}
 }
 
-/* beamformer_hip_push_data_burst_with_compute: frame_count RF frames of one parameter block in one call (one device).
- *   RF        the whole burst is one upload into one pinned slot -- over the copy engine into device staging when it is large, read in
- *             place over PCIe when small, by kOverlapBytes applied to the burst -- and lands in ONE slot of the RF ring,
- *             frame k at k * rf_stride with 64 spare bytes behind every frame;
- *   stages    ingest, then every pre-DAS stage, ONE launch each for the whole burst: the stage kernels carry a frame dimension (grid z,
- *             or grid y beside the channels for the filters, which then take the burst in chunks of 65535 / channels frames) and address
- *             and bound every frame as a single frame is; frame k of a stage's output lies at k * stage_stride of burst_stage[];
- *   DAS       the burst kernel in one launch where decide_burst says so, else the frame's own launch(es) on its slice of the input;
- *   frames    contiguous in the frame ring (a burst that would straddle the end starts again at 0), consecutive ids;
- *   timings   one event set for the burst, in the timing slot of its last frame; every frame's slot points there with share = N.
- * Everything that can be refused is checked, and every buffer grown, BEFORE the ids are taken: a refused burst queues nothing.  After
- * that a failure leaves tombstones under all of its ids. */
+/* What is a multi-frame push's own (push_frames runs the rest): */
+struct FramesPush {
+	PushRecord::Kind kind;
+	uint32_t rf_frames, rf_frame_size;       /* the upload: this many RF frames back to back, each this many bytes of the caller's */
+	uint32_t frames;                         /* the frames it queues: all of `points`, or -- `views` given -- frame k of views[k]'s */
+	const uint32_t *points;
+	const BeamformerHipView *views;
+	const BurstDecision *burst;              /* its route (das_select.h), one of the two */
+	const ViewsDecision *views_route;
+	bool          wants_counters;            /* a frame's own launch keeps the staged / tile counters */
+	DeviceBuffer *stage;                     /* the pre-DAS stages' ping-pong pair and, where it holds every RF frame's output, the stride to grow it by */
+	uint64_t      stage_stride;
+	float         decide_us;
+};
+
+/* A push of several frames with ONE upload and ONE event set (one device) -- a burst: N RF frames, N frames; a views push: one RF frame
+ * on K grids.
+ *   RF        one upload into one pinned slot -- over the copy engine into device staging when it is large, read in place over PCIe when
+ *             small, by kOverlapBytes applied to the whole upload -- and ONE slot of the RF ring, frame k at k * rf_stride with 64 spare
+ *             bytes behind every frame;
+ *   stages    ingest, then every pre-DAS stage, ONE launch each for all RF frames: the stage kernels carry a frame dimension (grid z, or
+ *             grid y beside the channels for the filters, which then take a burst in chunks of 65535 / channels frames) and address and
+ *             bound every frame as a single frame is; several RF frames: frame k of a stage's output at k * stage_stride of burst_stage[],
+ *             one: the single push's d.scratch[];
+ *   DAS       the jobs of walk_plan: the push's fused launch (das_burst.hip where decide_burst says so; das_views.hip for the views
+ *             decide_views gives it), every other frame its own launch(es) -- a burst's on its slice of the input, a view's on the one input;
+ *   frames    contiguous in the frame ring, each rounded to 64 bytes (a run that would straddle the end starts again at 0), consecutive
+ *             ids -- a burst's oldest RF frame first, a views push's in view order;
+ *   timings   one event set for the push, in the timing slot of its last frame; every frame's slot points there with share = frames.
+ * Everything that can be refused is checked, and every buffer whose absence would fail the push is grown, BEFORE the ids are taken: a
+ * refused push queues nothing.  (The tables some single-frame kernels keep -- staged_tables, hercules_table, hercules_pairs -- are grown
+ * where a frame's launch asks for them, launch_das_part, each with a kernel to fall back on: growing one mid-push drains the device and
+ * fails nothing.)  After that a failure leaves tombstones under all of its ids. */
+static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const void *data, bool data_on_device, const FramesPush &m)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	const ParameterBlock &pb = c.blocks[block];
+	const Plan &plan = ps->plan;
+	hipStream_t s = d.stream;
+	const uint32_t N = m.rf_frames, F = m.frames;
+
+	uint64_t run_bytes = 0;
+	if (!frame_run_bytes(m.points, m.views, F, plan.iq_pipeline ? 8u : 4u, d.ring.size, run_bytes)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+
+	/* device and pinned memory, grown before anything is queued */
+	const uint64_t rf_stride = round_up(l.rf_size, 64) + 64;
+	const uint64_t total     = (uint64_t)m.rf_frame_size * N;
+	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
+	const bool overlap = !data_on_device && total >= kOverlapBytes;
+	bool fits = d.rf[slot].ensure(rf_stride * N);
+	if (m.stage_stride) {
+		size_t pre_das_stages = 0;
+		for (size_t i = 0; i < plan.stages.size(); i++) {
+			const int kind = plan.stages[i].kind;
+			if (kind == BeamformerShaderKind_DAS) break;
+			pre_das_stages += kind != BeamformerShaderKind_CoherencyWeighting;
+		}
+		for (size_t k = 0; k < 2 && k < pre_das_stages; k++) fits = fits && m.stage[k].ensure(m.stage_stride * N);
+	}
+	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
+	if (m.views_route && m.views_route->kernel_views) {
+		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
+		fits = fits && d.views_table.ensure(table_bytes);
+		if (fits && !d.views_pinned && !HIP_OK(hipHostMalloc(&d.views_pinned, table_bytes, hipHostMallocDefault))) { d.views_pinned = nullptr; fits = false; }
+		if (fits && !d.views_copied && !HIP_OK(hipEventCreateWithFlags(&d.views_copied, hipEventDisableTiming))) { d.views_copied = nullptr; fits = false; }
+	}
+	if (!fits) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
+	UploadSlot &u = d.upload[slot];
+	if (!claim_upload(u, total, !data_on_device)) return false;
+	const uint32_t owner = (uint32_t)((c.push_sequence + F - 1) % kTimingSlots);     /* the push's events: its LAST frame's slot */
+	TimingSlot &t = d.timing[owner];
+	if (!ensure_events(t)) return false;
+	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	if (m.wants_counters && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+
+	/* ---- from here on the push owns ids first .. first + F - 1 ---- */
+	d.rf_index++;
+	const uint64_t first = c.push_sequence;
+	c.push_sequence += F;
+	d.frame_counter = first;
+	d.multi.kind = PushRecord::None;
+	Tombstones lockstep{c, first, F, 1, false};
+
+	t.failed = false; t.sampled = true; t.events_slot = owner; t.share = F; t.count = 0; t.counted = false;
+	d.have_sample = false;          /* the push's events cover F frames: a single frame that follows records its own */
+	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
+
+	/* ---- upload and ingest: a multi-frame push always runs the ingest kernel.  One RF frame: strides 0, as in a single push ---- */
+	const uint64_t in_step = N > 1 ? m.rf_frame_size : 0, rf_step = N > 1 ? rf_stride : 0;
+	const void *raw = data;
+	if (!data_on_device) {
+		raw = enqueue_upload(d, u, data, total, overlap ? d.raw_staging[slot].ptr : nullptr, total);
+		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, N, in_step, rf_step, s);
+	if (!data_on_device && !overlap) ok &= pinned_read_by(u, s);
+	segment(t, kStageIngest, s);
+	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	note_push_time();
+	d.last_rf = (char *)d.rf[slot].ptr + (N - 1) * rf_stride; d.last_rf_bytes = l.rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
+
+	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
+	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
+	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_step, (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size), m.stage, m.stage_stride, t,
+	                                                 m.burst, m.views, m.views ? F : 0u, m.views_route});
+	finish_upload(u, overlap, s);
+	if (!done) return false;
+
+	share_timing_rows(d, first, F, owner);
+	PushRecord &r = d.multi;
+	r.kind = m.kind; r.first_id = first; r.count = F; r.events_slot = owner; r.decide_us = m.decide_us;
+	if (m.burst) r.burst = *m.burst;
+	else         describe_views_decision(*m.views_route, F, &r.views);
+	lockstep.complete = true;
+	return true;
+}
+
+/* beamformer_hip_push_data_burst_with_compute: frame_count RF frames of one parameter block in one call, frame_count frames of the
+ * block's grid (its shard's planes).  The route: decide_burst on the block's own single-frame decision. */
 bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
 	ParameterBlock &pb = c.blocks[block];
-	hipStream_t s = d.stream;
 	const uint32_t N = frame_count;
 
 	RfLayout l;
@@ -1290,108 +1365,57 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
 	const Plan &plan = ps->plan;
 
-	/* the frames: all of one size, contiguous in the ring */
 	uint32_t zfirst = 0, zcount = plan.output_points[2];
 	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-	const uint64_t frame_bytes = round_up((uint64_t)plan.output_points[0] * plan.output_points[1] * zcount * (plan.iq_pipeline ? 8u : 4u), 64);
-	if (frame_bytes > d.ring.size / N) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
 	std::vector<DasDecision> no_parts;
 	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
 	BurstDecision route;
 	if (!parts.empty()) decide_burst(pb, plan, ps->transmit_table, parts, zfirst, zcount, c.das_path_mode, N, route);
 	else { route.stage_launches = (N + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels); route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared"; }
 
-	/* device and pinned memory, grown before anything is queued */
-	const uint64_t rf_stride    = round_up(l.rf_size, 64) + 64;
-	const uint64_t stage_stride = round_up(plan.intermediate_bytes, 64) + 64;
-	const uint64_t total        = (uint64_t)frame_size * N;
-	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
-	size_t pre_das_stages = 0;
-	for (size_t i = 0; i < plan.stages.size(); i++) {
-		const int kind = plan.stages[i].kind;
-		if (kind == BeamformerShaderKind_DAS) break;
-		pre_das_stages += kind != BeamformerShaderKind_CoherencyWeighting;
+	return push_frames(block, ps, l, data, data_on_device,
+	                   FramesPush{PushRecord::Burst, N, frame_size, N, points, nullptr, &route, nullptr, keeps_counters(parts),
+	                              d.burst_stage, round_up(plan.intermediate_bytes, 64) + 64, 0.0f});
+}
+
+/* The record of the newest multi-frame push, when the newest push IS that push, of `kind` and complete: waited for, with its stage
+ * kinds and times (hipEvent pairs around each stage of the WHOLE push; total: first event to last).  Else null, InvalidAccess. */
+static const PushRecord *newest_push(PushRecord::Kind kind, uint32_t &first_id, uint32_t &count, uint32_t &stage_count, uint32_t *stage_kind,
+                                     float *stage_ms, float &total_ms)
+{
+	Context &c = g_context;
+	Device &d = c.devices[0];
+	const PushRecord &r = d.multi;
+	if (!c.device_ready || r.kind != kind || d.frame_counter != r.first_id + r.count || !newest_record(d) ||
+	    !HIP_OK(hipSetDevice(d.device)) || !HIP_OK(hipStreamSynchronize(d.stream))) {
+		set_error(BeamformerLibErrorKind_InvalidAccess);
+		return nullptr;
 	}
-	const bool overlap = !data_on_device && total >= kOverlapBytes;
-	bool fits = d.rf[slot].ensure(rf_stride * N);
-	if (pre_das_stages)     fits = fits && d.burst_stage[0].ensure(stage_stride * N);
-	if (pre_das_stages > 1) fits = fits && d.burst_stage[1].ensure(stage_stride * N);
-	if (overlap)            fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
-	if (!fits) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
-	UploadSlot &u = d.upload[slot];
-	if (!claim_upload(u, total, !data_on_device)) return false;
-	const uint32_t owner = (uint32_t)((c.push_sequence + N - 1) % kTimingSlots);     /* the burst's events: its LAST frame's slot */
-	TimingSlot &t = d.timing[owner];
-	if (!ensure_events(t)) return false;
-	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
-	bool wants_counters = false;
-	for (const DasDecision &dd : parts) wants_counters |= dd.path == DasPath_Staged || dd.path == DasPath_Tile;
-	if (wants_counters && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
-
-	/* ---- from here on the burst owns ids first .. first + N - 1 ---- */
-	d.rf_index++;
-	const uint64_t first = c.push_sequence;
-	c.push_sequence += N;
-	d.frame_counter = first;
-	d.burst.valid = false;
-	Tombstones lockstep{c, first, N, 1, false};
-
-	t.failed = false; t.sampled = true; t.events_slot = owner; t.share = N; t.count = 0; t.counted = false;
-	d.have_sample = false;          /* the burst's events cover N frames: a single frame that follows records its own */
-	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
-
-	/* ---- upload and ingest: a burst always runs the ingest kernel ---- */
-	const void *raw = data;
-	if (!data_on_device) {
-		raw = enqueue_upload(d, u, data, total, overlap ? d.raw_staging[slot].ptr : nullptr, total);
-		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	first_id = (uint32_t)r.first_id; count = r.count;
+	const TimingSlot &t = d.timing[r.events_slot];
+	stage_count = t.count;
+	for (uint32_t i = 0; i < t.count; i++) {
+		stage_kind[i] = t.kinds[i];
+		float ms = 0;
+		if (HIP_OK(hipEventElapsedTime(&ms, t.events[i], t.events[i + 1]))) stage_ms[i] = ms;
 	}
-	ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, N, frame_size, rf_stride, s);
-	if (!data_on_device && !overlap) ok &= pinned_read_by(u, s);
-	segment(t, kStageIngest, s);
-	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	note_push_time();
-	d.last_rf = (char *)d.rf[slot].ptr + (N - 1) * rf_stride; d.last_rf_bytes = l.rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
-
-	/* ---- stages, one after the other over all frames: what a stage may read of a frame is the RF itself, then a stage buffer's frame
-	 * with its slack ---- */
-	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_stride, (int64_t)l.rf_size, d.burst_stage, stage_stride, t, &route});
-	finish_upload(u, overlap, s);
-	if (!done) return false;
-
-	share_timing_rows(d, first, N, owner);
-	d.views.valid = false;
-	d.burst.valid = true; d.burst.first_id = first; d.burst.count = N; d.burst.events_slot = owner; d.burst.route = route;
-	lockstep.complete = true;
-	return true;
+	float total = 0;
+	if (t.count && HIP_OK(hipEventElapsedTime(&total, t.events[0], t.events[t.count]))) total_ms = total;
+	return &r;
 }
 
 /* beamformer_hip_get_last_burst_info */
 bool last_burst_info(BeamformerHipBurstInfo *out)
 {
-	Context &c = g_context;
 	std::memset(out, 0, sizeof(*out));
-	if (!c.device_ready) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	Device &d = c.devices[0];
-	const BurstRecord &b = d.burst;
-	/* the newest push must be that burst, complete */
-	if (!b.valid || d.frame_counter != b.first_id + b.count || !newest_record(d)) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	if (!HIP_OK(hipSetDevice(d.device)) || !HIP_OK(hipStreamSynchronize(d.stream))) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	out->route.burst_kernel = b.route.burst_kernel; out->route.single_path = b.route.single_path == DasPath_Zero ? -2 : b.route.single_path;
-	out->route.frames_per_thread = b.route.frames_per_thread; out->route.das_launches = b.route.das_launches;
-	out->route.stage_launches = b.route.stage_launches; out->route.min_frames = kBurstMinFrames;
-	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.route.reason.c_str());
-	out->first_frame_id = (uint32_t)b.first_id; out->frame_count = b.count;
-	const TimingSlot &t = d.timing[b.events_slot];
-	out->stage_count = t.count;
-	for (uint32_t i = 0; i < t.count; i++) {
-		out->stage_kind[i] = t.kinds[i];
-		float ms = 0;
-		if (HIP_OK(hipEventElapsedTime(&ms, t.events[i], t.events[i + 1]))) out->stage_ms[i] = ms;
-	}
-	float total = 0;
-	if (t.count && HIP_OK(hipEventElapsedTime(&total, t.events[0], t.events[t.count]))) out->burst_ms = total;
+	const PushRecord *r = newest_push(PushRecord::Burst, out->first_frame_id, out->frame_count, out->stage_count, out->stage_kind, out->stage_ms, out->burst_ms);
+	if (!r) return false;
+	const BurstDecision &b = r->burst;
+	out->route.burst_kernel = b.burst_kernel; out->route.single_path = b.single_path == DasPath_Zero ? -2 : b.single_path;
+	out->route.frames_per_thread = b.frames_per_thread; out->route.das_launches = b.das_launches;
+	out->route.stage_launches = b.stage_launches; out->route.min_frames = kBurstMinFrames;
+	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.reason.c_str());
 	return true;
 }
 
@@ -1418,23 +1442,13 @@ void describe_views_decision(const ViewsDecision &route, uint32_t view_count, Be
 	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
 }
 
-/* beamformer_hip_push_data_views_with_compute: ONE RF frame beamformed on view_count grids (one device, no output shard).
- *   RF        one upload into one pinned slot -- over the copy engine into device staging when it is large, read in place over PCIe when
- *             small (kOverlapBytes) --, the ingest kernel, ONE slot of the RF ring;
- *   stages    every pre-DAS stage ONE launch, as in a single push, on d.scratch[];
- *   DAS       K frames from the one DAS input (launch_views): the views kernel's launch, then the other views' own;
- *   frames    contiguous in the frame ring, each at its own 64-byte-rounded size, consecutive ids in view order;
- *   timings   one event set for the push, in the timing slot of its last view; every view's slot points there with share = K.
- * Everything that can be refused is checked, and every buffer whose absence would fail the push is grown, BEFORE the ids are taken: a
- * refused push queues nothing.  (The tables some single-frame kernels keep -- staged_tables, hercules_table, hercules_pairs -- are grown
- * where a view's launch asks for them, launch_das_part, each with a kernel to fall back on: growing one mid-push drains the device and
- * fails nothing.)  After that a failure leaves tombstones under all of its ids. */
+/* beamformer_hip_push_data_views_with_compute: ONE RF frame beamformed on view_count grids (no output shard), view k's frame at its own
+ * size.  The route: decide_views -- each view's own single-frame decision, and which of them the views kernel takes. */
 bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
 	ParameterBlock &pb = c.blocks[block];
-	hipStream_t s = d.stream;
 	const uint32_t K = view_count;
 	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
 
@@ -1442,105 +1456,25 @@ bool push_views(uint32_t block, const void *data, uint32_t size, const Beamforme
 	if (!rf_layout(pb, l)) return false;
 	PlanState *ps = commit_block(block);
 	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	const Plan &plan = ps->plan;
 
-	/* each view's own single-frame decision, and which of them the views kernel takes */
 	const auto decide_begin = std::chrono::steady_clock::now();
 	ViewsDecision route;
-	decide_views(pb, plan, ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, route);
+	decide_views(pb, ps->plan, ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, route);
 	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
-
-	/* the frames: contiguous in the ring */
-	uint64_t run_bytes = 0;
-	for (uint32_t k = 0; k < K; k++) {
-		const uint32_t *n = views[k].output_points;
-		run_bytes += round_up((uint64_t)n[0] * n[1] * n[2] * (plan.iq_pipeline ? 8u : 4u), 64);
-		if (run_bytes > d.ring.size) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-	}
-
-	/* device and pinned memory, grown before anything is queued */
-	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
-	const bool overlap = !data_on_device && size >= kOverlapBytes;
-	bool fits = d.rf[slot].ensure(round_up(l.rf_size, 64) + 64);
-	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(size, 64) + 64);
-	if (route.kernel_views) {
-		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
-		fits = fits && d.views_table.ensure(table_bytes);
-		if (fits && !d.views_pinned && !HIP_OK(hipHostMalloc(&d.views_pinned, table_bytes, hipHostMallocDefault))) { d.views_pinned = nullptr; fits = false; }
-		if (fits && !d.views_copied && !HIP_OK(hipEventCreateWithFlags(&d.views_copied, hipEventDisableTiming))) { d.views_copied = nullptr; fits = false; }
-	}
-	if (!fits) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
-	UploadSlot &u = d.upload[slot];
-	if (!claim_upload(u, size, !data_on_device)) return false;
-	const uint32_t owner = (uint32_t)((c.push_sequence + K - 1) % kTimingSlots);     /* the push's events: its LAST view's slot */
-	TimingSlot &t = d.timing[owner];
-	if (!ensure_events(t)) return false;
-	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
 	bool wants_counters = false;
-	for (uint32_t k = 0; k < K; k++)
-		for (const DasDecision &dd : route.parts[k]) wants_counters |= !route.taken[k] && (dd.path == DasPath_Staged || dd.path == DasPath_Tile);
-	if (wants_counters && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	for (uint32_t k = 0; k < K; k++) wants_counters |= !route.taken[k] && keeps_counters(route.parts[k]);
 
-	/* ---- from here on the push owns ids first .. first + K - 1 ---- */
-	d.rf_index++;
-	const uint64_t first = c.push_sequence;
-	c.push_sequence += K;
-	d.frame_counter = first;
-	d.burst.valid = false; d.views.valid = false;
-	Tombstones lockstep{c, first, K, 1, false};
-
-	t.failed = false; t.sampled = true; t.events_slot = owner; t.share = K; t.count = 0; t.counted = false;
-	d.have_sample = false;          /* the push's events cover K frames: a single frame that follows records its own */
-	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
-
-	/* ---- upload and ingest: a views push always runs the ingest kernel ---- */
-	const void *raw = data;
-	if (!data_on_device) {
-		raw = enqueue_upload(d, u, data, size, overlap ? d.raw_staging[slot].ptr : nullptr, size);
-		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
-	ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, 1, 0, 0, s);
-	if (!data_on_device && !overlap) ok &= pinned_read_by(u, s);
-	segment(t, kStageIngest, s);
-	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	note_push_time();
-	d.last_rf = d.rf[slot].ptr; d.last_rf_bytes = l.rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
-
-	/* ---- the stages of a single push, then K frames from the one DAS input ---- */
-	const ViewsWalk vw{views, K, &route};
-	const bool done = walk_plan(block, ps, StageWalk{1, d.rf[slot].ptr, 0, (int64_t)d.rf[slot].size, d.scratch, 0, t, nullptr, &vw});
-	finish_upload(u, overlap, s);
-	if (!done) return false;
-
-	share_timing_rows(d, first, K, owner);
-	d.views.valid = true; d.views.first_id = first; d.views.count = K; d.views.events_slot = owner; d.views.decide_us = decide_us;
-	describe_views_decision(route, K, &d.views.route);
-	lockstep.complete = true;
-	return true;
+	return push_frames(block, ps, l, data, data_on_device,
+	                   FramesPush{PushRecord::Views, 1, size, K, nullptr, views, nullptr, &route, wants_counters, d.scratch, 0, decide_us});
 }
 
 /* beamformer_hip_get_last_views_info */
 bool last_views_info(BeamformerHipViewsInfo *out)
 {
-	Context &c = g_context;
 	std::memset(out, 0, sizeof(*out));
-	if (!c.device_ready) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	Device &d = c.devices[0];
-	const ViewsRecord &v = d.views;
-	/* the newest push must be that views push, complete */
-	if (!v.valid || d.frame_counter != v.first_id + v.count || !newest_record(d)) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	if (!HIP_OK(hipSetDevice(d.device)) || !HIP_OK(hipStreamSynchronize(d.stream))) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	out->route = v.route;
-	out->first_frame_id = (uint32_t)v.first_id; out->view_count = v.count; out->decide_us = v.decide_us;
-	const TimingSlot &t = d.timing[v.events_slot];
-	out->stage_count = t.count;
-	for (uint32_t i = 0; i < t.count; i++) {
-		out->stage_kind[i] = t.kinds[i];
-		float ms = 0;
-		if (HIP_OK(hipEventElapsedTime(&ms, t.events[i], t.events[i + 1]))) out->stage_ms[i] = ms;
-	}
-	float total = 0;
-	if (t.count && HIP_OK(hipEventElapsedTime(&total, t.events[0], t.events[t.count]))) out->views_ms = total;
+	const PushRecord *r = newest_push(PushRecord::Views, out->first_frame_id, out->view_count, out->stage_count, out->stage_kind, out->stage_ms, out->views_ms);
+	if (!r) return false;
+	out->route = r->views; out->decide_us = r->decide_us;
 	return true;
 }
 

@@ -92,30 +92,53 @@ bool validate_pipeline(const int32_t *shaders, uint32_t shader_count, Beamformer
 	return check(start_ok, BeamformerLibErrorKind_InvalidStartShader);
 }
 
+/* One RF frame of `size` bytes at `data` against a parameter block (beamformer_push_data_base, lib .c:503-511).  The reference does this
+ * arithmetic in u32; a product that wraps there passes its check and then reads far outside the caller's buffer.  Same checks and
+ * error codes, in u64: sizes the reference accepts without wrapping are judged identically, wrapped ones are refused. */
+bool valid_rf_frame(const ParameterBlock &pb, const void *data, uint32_t size)
+{
+	const BeamformerParameters &bp = pb.parameters;
+	const uint64_t max_rf_size = frame_ring_bytes() / 3;             /* capabilities.max_rf_data_size */
+	const uint64_t bytes    = (uint64_t)bf_kind_byte_size[pb.data_kind];
+	const uint64_t rf_size  = (uint64_t)bp.acquisition_count * bp.sample_count * bp.channel_count * bytes;
+	const uint64_t raw_size = (uint64_t)bp.raw_data_dimensions[0] * bp.raw_data_dimensions[1] * bytes;
+	if (!check(data != nullptr, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(rf_size <= max_rf_size && rf_size <= UINT32_MAX, BeamformerLibErrorKind_RFDataSizeOverflow)) return false;
+	if (!check(rf_size <= size && (uint64_t)size == raw_size, BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	if (!check(rf_size > 0, BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	/* the ingest walks channel_mapping[0 .. channel_count): bound it before anything indexes with it */
+	return check(bp.channel_count <= BeamformerMaxChannelCount && bp.acquisition_count <= BeamformerMaxEmissionsCount,
+	             BeamformerLibErrorKind_DataSizeMismatch);
+}
+
+/* a multi-frame push (`what`) is not sharded over the devices of beamformer_hip_set_devices */
+bool on_one_device(const char *what)
+{
+	Context &c = ctx();
+	if (c.requested_count <= 1 && !(c.device_ready && c.device_count > 1)) return true;
+	std::fprintf(stderr, "[beamformer] a %s runs on one device: refused with the %u devices of beamformer_hip_set_devices\n", what,
+	             c.device_ready ? c.device_count : c.requested_count);
+	return set_error(BeamformerLibErrorKind_InvalidAccess);
+}
+
+/* a multi-frame push's whole run of frames in the frame ring (context.h: frame_run_bytes; needs the block's plan, no device) */
+bool run_fits_the_ring(const ParameterBlock &pb, const BeamformerHipView *views, uint32_t count)
+{
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, ctx().hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], pb.shard_z_count ? pb.shard_z_count : plan.output_points[2]};
+	uint64_t total;
+	return check(frame_run_bytes(points, views, count, plan.iq_pipeline ? 8u : 4u, frame_ring_bytes(), total), BeamformerLibErrorKind_FrameSizeOverflow);
+}
+
 bool push_data_common(const void *data, uint32_t data_size, uint32_t image_plane_tag, uint32_t slot, bool on_device)
 {
 	Context &c = ctx();
 	if (!ensure_device()) return false;
 	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
 	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
-
-	/* beamformer_push_data_base, lib .c:503-511 */
-	const ParameterBlock &pb = c.blocks[slot];
-	const BeamformerParameters &bp = pb.parameters;
-	uint64_t max_rf_size = frame_ring_bytes() / 3;                   /* capabilities.max_rf_data_size */
-	/* The reference does this arithmetic in u32 (lib .c:503-511); a product that wraps there passes
-	 * its check and then reads far outside the caller's buffer.  Same checks and error codes, in u64:
-	 * sizes the reference accepts without wrapping are judged identically, wrapped ones are refused. */
-	uint64_t bytes    = (uint64_t)bf_kind_byte_size[pb.data_kind];
-	uint64_t rf_size  = (uint64_t)bp.acquisition_count * bp.sample_count * bp.channel_count * bytes;
-	uint64_t raw_size = (uint64_t)bp.raw_data_dimensions[0] * bp.raw_data_dimensions[1] * bytes;
-	if (!check(data != nullptr, BeamformerLibErrorKind_BufferOverflow)) return false;
-	if (!check(rf_size <= max_rf_size && rf_size <= UINT32_MAX, BeamformerLibErrorKind_RFDataSizeOverflow)) return false;
-	if (!check(rf_size <= data_size && (uint64_t)data_size == raw_size, BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	if (!check(rf_size > 0, BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	/* the ingest walks channel_mapping[0 .. channel_count): bound it before anything indexes with it */
-	if (!check(bp.channel_count <= BeamformerMaxChannelCount && bp.acquisition_count <= BeamformerMaxEmissionsCount,
-	           BeamformerLibErrorKind_DataSizeMismatch)) return false;
+	if (!valid_rf_frame(c.blocks[slot], data, data_size)) return false;
 	return push_rf_and_compute(slot, data, data_size, on_device);
 }
 
@@ -129,30 +152,9 @@ bool push_burst_common(const void *data, uint32_t frame_size, uint32_t frame_cou
 	           BeamformerLibErrorKind_BufferOverflow)) return false;
 	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
 	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
-	if (c.requested_count > 1 || (c.device_ready && c.device_count > 1)) {
-		std::fprintf(stderr, "[beamformer] a burst runs on one device: refused with the %u devices of beamformer_hip_set_devices\n",
-		             c.device_ready ? c.device_count : c.requested_count);
-		return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
-	const ParameterBlock &pb = c.blocks[slot];
-	const BeamformerParameters &bp = pb.parameters;
-	const uint64_t max_rf_size = frame_ring_bytes() / 3;
-	const uint64_t bytes    = (uint64_t)bf_kind_byte_size[pb.data_kind];
-	const uint64_t rf_size  = (uint64_t)bp.acquisition_count * bp.sample_count * bp.channel_count * bytes;
-	const uint64_t raw_size = (uint64_t)bp.raw_data_dimensions[0] * bp.raw_data_dimensions[1] * bytes;
-	if (!check(data != nullptr, BeamformerLibErrorKind_BufferOverflow)) return false;
-	if (!check(rf_size <= max_rf_size && rf_size <= UINT32_MAX, BeamformerLibErrorKind_RFDataSizeOverflow)) return false;
-	if (!check(rf_size <= frame_size && (uint64_t)frame_size == raw_size, BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	if (!check(rf_size > 0, BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	if (!check(bp.channel_count <= BeamformerMaxChannelCount && bp.acquisition_count <= BeamformerMaxEmissionsCount,
-	           BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	/* the whole burst in the frame ring, and its DAS input below the 4 GiB the kernels' 32-bit byte offsets reach per frame */
-	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	const uint64_t planes = pb.shard_z_count ? pb.shard_z_count : plan.output_points[2];
-	const uint64_t frame_bytes = ((uint64_t)plan.output_points[0] * plan.output_points[1] * planes * (plan.iq_pipeline ? 8u : 4u) + 63) / 64 * 64;
-	if (!check(frame_bytes <= frame_ring_bytes() / frame_count, BeamformerLibErrorKind_FrameSizeOverflow)) return false;
+	if (!on_one_device("burst")) return false;
+	if (!valid_rf_frame(c.blocks[slot], data, frame_size)) return false;
+	if (!run_fits_the_ring(c.blocks[slot], nullptr, frame_count)) return false;
 	if (!ensure_device()) return false;
 	return push_burst(slot, data, frame_size, frame_count, on_device);
 }
@@ -172,21 +174,6 @@ bool validate_views(const BeamformerHipView *views, uint32_t view_count, uint32_
 	return true;
 }
 
-/* all views together, each rounded to 64 bytes, in the frame ring (three 32-bit extents can wrap 64 bits: saturating) */
-bool views_fit_the_ring(const BeamformerHipView *views, uint32_t view_count, uint64_t voxel_bytes)
-{
-	const uint64_t ring = frame_ring_bytes();
-	uint64_t total = 0;
-	for (uint32_t k = 0; k < view_count; k++) {
-		const uint32_t *n = views[k].output_points;
-		const uint64_t plane = (uint64_t)n[0] * n[1];
-		if (plane > ring || plane * n[2] > ring / voxel_bytes) return false;
-		total += (plane * n[2] * voxel_bytes + 63) / 64 * 64;
-		if (total > ring) return false;
-	}
-	return true;
-}
-
 static_assert(BEAMFORMER_HIP_MAX_VIEWS <= BeamformerMaxBacklogFrames, "every view of a push keeps its frame record");
 
 /* A views push: the single push's checks of the RF (once), then what must hold for the views.  Everything that needs no device is judged
@@ -196,30 +183,13 @@ bool push_views_common(const void *data, uint32_t data_size, const BeamformerHip
 	Context &c = ctx();
 	if (!validate_views(views, view_count, slot)) return false;
 	const ParameterBlock &pb = c.blocks[slot];
-	if (c.requested_count > 1 || (c.device_ready && c.device_count > 1)) {
-		std::fprintf(stderr, "[beamformer] a views push runs on one device: refused with the %u devices of beamformer_hip_set_devices\n",
-		             c.device_ready ? c.device_count : c.requested_count);
-		return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
+	if (!on_one_device("views push")) return false;
 	if (pb.shard_z_count) {
 		std::fprintf(stderr, "[beamformer] a view is not sharded: refused with the output shard set on parameter block %u\n", slot);
 		return set_error(BeamformerLibErrorKind_InvalidAccess);
 	}
-	const BeamformerParameters &bp = pb.parameters;
-	const uint64_t max_rf_size = frame_ring_bytes() / 3;
-	const uint64_t bytes    = (uint64_t)bf_kind_byte_size[pb.data_kind];
-	const uint64_t rf_size  = (uint64_t)bp.acquisition_count * bp.sample_count * bp.channel_count * bytes;
-	const uint64_t raw_size = (uint64_t)bp.raw_data_dimensions[0] * bp.raw_data_dimensions[1] * bytes;
-	if (!check(data != nullptr, BeamformerLibErrorKind_BufferOverflow)) return false;
-	if (!check(rf_size <= max_rf_size && rf_size <= UINT32_MAX, BeamformerLibErrorKind_RFDataSizeOverflow)) return false;
-	if (!check(rf_size <= data_size && (uint64_t)data_size == raw_size, BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	if (!check(rf_size > 0, BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	if (!check(bp.channel_count <= BeamformerMaxChannelCount && bp.acquisition_count <= BeamformerMaxEmissionsCount,
-	           BeamformerLibErrorKind_DataSizeMismatch)) return false;
-	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	if (!check(views_fit_the_ring(views, view_count, plan.iq_pipeline ? 8u : 4u), BeamformerLibErrorKind_FrameSizeOverflow)) return false;
+	if (!valid_rf_frame(pb, data, data_size)) return false;
+	if (!run_fits_the_ring(pb, views, view_count)) return false;
 	if (!ensure_device()) return false;
 	return push_views(slot, data, data_size, views, view_count, on_device);
 }

@@ -180,17 +180,23 @@ def output_is_complex(bp):
     return int(P.ShaderKind.Demodulate) in stages or P.DATA_KIND_COMPLEX[int(bp.data_kind)]
 
 
-def beamform(bp, rf, filters=(), timeout_ms=-1):
-    """One frame through the C ABI exactly as tests/throughput.c drives the reference:
-    create_filter* -> push_simple_parameters -> push_data_with_compute -> get_last_frames.
-    `rf` is a C-contiguous numpy array holding raw_data_dimensions[1] rows.  Returns the frame
-    as float32 or complex64 with shape (Z, Y, X)."""
+def _prepared(bp, filters, timeout_ms):
+    """The library with the filters, the parameters (block 0) and the timeout of a beamform*() call in place."""
     lib = library()
     for slot, fp in enumerate(filters):
         if fp is not None:
             _check(lib.beamformer_create_filter(C.byref(fp), slot, 0))
     _check(lib.beamformer_push_simple_parameters(C.byref(bp)))
     lib.beamformer_set_global_timeout(C.c_uint32(timeout_ms & 0xFFFFFFFF).value)
+    return lib
+
+
+def beamform(bp, rf, filters=(), timeout_ms=-1):
+    """One frame through the C ABI exactly as tests/throughput.c drives the reference:
+    create_filter* -> push_simple_parameters -> push_data_with_compute -> get_last_frames.
+    `rf` is a C-contiguous numpy array holding raw_data_dimensions[1] rows.  Returns the frame
+    as float32 or complex64 with shape (Z, Y, X)."""
+    lib = _prepared(bp, filters, timeout_ms)
     rf = np.ascontiguousarray(rf)
     _check(lib.beamformer_push_data_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, 0, 0))
     return get_last_frame(bp)
@@ -218,12 +224,7 @@ def get_last_frames(bp, count, shard_planes=None):
 def beamform_burst(bp, rf_frames, filters=(), timeout_ms=-1, on_device_pointer=None):
     """N frames of one geometry in one call (beamformer_hip_push_data_burst_with_compute): `rf_frames` is a C-contiguous array
     whose first axis runs over the frames, each frame laid out as beamform() takes it.  Returns (N, Z, Y, X), oldest first."""
-    lib = library()
-    for slot, fp in enumerate(filters):
-        if fp is not None:
-            _check(lib.beamformer_create_filter(C.byref(fp), slot, 0))
-    _check(lib.beamformer_push_simple_parameters(C.byref(bp)))
-    lib.beamformer_set_global_timeout(C.c_uint32(timeout_ms & 0xFFFFFFFF).value)
+    lib = _prepared(bp, filters, timeout_ms)
     rf_frames = np.ascontiguousarray(rf_frames)
     count = rf_frames.shape[0]
     frame_size = rf_frames.nbytes // count
@@ -302,12 +303,7 @@ def get_last_views(views):
 def beamform_views(bp, rf, views, filters=(), timeout_ms=-1, on_device_pointer=None):
     """ONE RF frame on K grids in one call (beamformer_hip_push_data_views_with_compute): everything but the grid from `bp`, view k on
     views[k] (HipView: see view()).  `rf` as beamform() takes it.  Returns a list of K arrays (Z, Y, X), in view order."""
-    lib = library()
-    for slot, fp in enumerate(filters):
-        if fp is not None:
-            _check(lib.beamformer_create_filter(C.byref(fp), slot, 0))
-    _check(lib.beamformer_push_simple_parameters(C.byref(bp)))
-    lib.beamformer_set_global_timeout(C.c_uint32(timeout_ms & 0xFFFFFFFF).value)
+    lib = _prepared(bp, filters, timeout_ms)
     rf = np.ascontiguousarray(rf)
     array, count = _view_array(views)
     if on_device_pointer is not None:

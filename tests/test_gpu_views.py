@@ -425,3 +425,33 @@ def test_a_push_that_fails_leaves_a_tombstone_under_every_one_of_its_ids(route, 
     assert info.route.kernel_views == (K if route == "views kernel" else 0)
     for k in range(K):
         assert same_bits(again[k], good[k]), k
+
+
+def test_only_the_newest_multi_frame_push_serves_its_info(bflib):
+    """beamformer_hip_get_last_views_info serves a views push and beamformer_hip_get_last_burst_info a burst only while that push is the
+    newest one, complete: the other call, both calls after a single push, and both after a views push that failed are InvalidAccess"""
+    L = bflib.library()
+    acq = cases.make("config1_small")
+    rf = noise_frames(acq, 5, 5400)
+    views = kernel_views(acq)[:3]          # 1 x 1 x 1, 5 x 1 x 7, 33 x 1 x 17
+    assert all(int(np.prod(list(v.output_points))) <= 33 * 17 for v in views)
+
+    def served():
+        out = []
+        for call, info in ((L.beamformer_hip_get_last_views_info, P.HipViewsInfo()), (L.beamformer_hip_get_last_burst_info, P.HipBurstInfo())):
+            out.append(True if call(C.byref(info)) else bflib.last_error()[0])
+        return out
+
+    bflib.beamform_views(acq.bp, rf[0], views, acq.filters)
+    assert served() == [True, E.InvalidAccess]
+    bflib.beamform_burst(acq.bp, rf, acq.filters)
+    assert served() == [E.InvalidAccess, True]
+    bflib.beamform(acq.bp, rf[0], acq.filters)
+    assert served() == [E.InvalidAccess, E.InvalidAccess]
+    bflib.beamform_views(acq.bp, rf[1], views, acq.filters)
+    assert served() == [True, E.InvalidAccess]
+    L.beamformer_hip_set_das_path(P.HIP_DAS_PATH_FAIL_VIEWS_DAS)
+    array = (P.HipView * len(views))(*views)
+    assert not L.beamformer_hip_push_data_views_with_compute(rf[2].ctypes.data_as(C.c_void_p), rf[2].nbytes, array, len(views), 0)
+    assert bflib.last_error()[0] == E.InvalidAccess
+    assert served() == [E.InvalidAccess, E.InvalidAccess]

@@ -1,8 +1,9 @@
 """What the push entry points produce, without a single time in it: for a fixed list of small cases (tests/cases.py) pushed as single
-frames, as device-resident frames and as bursts, the SHA-256 of every exported frame with its id, and beside them the bookkeeping a
-client can read back -- das_path, das_row_end_planes and the stage kinds of beamformer_hip_get_last_frame_timings, a burst's route and
-stage kinds from beamformer_hip_get_last_burst_info, das_pairs where pair counting is on, the graphs instantiated where frame graphs
-are.  The kernels are deterministic and the RF is seeded, so two builds of the library that enqueue the same work print the same
+frames, as device-resident frames, as bursts and as views pushes, the SHA-256 of every exported frame with its id, and beside them the
+bookkeeping a client can read back -- das_path, das_row_end_planes and the stage kinds of beamformer_hip_get_last_frame_timings, a
+burst's route and stage kinds from beamformer_hip_get_last_burst_info, a views push's from beamformer_hip_get_last_views_info, das_pairs
+where pair counting is on (of the newest frame's row: the C ABI reads no other row's), which of the two info calls is served after each
+push of a mixed sequence, what a views push that fails leaves behind, the graphs instantiated where frame graphs are.  The kernels are deterministic and the RF is seeded, so two builds of the library that enqueue the same work print the same
 object: run it on both (OGL_BEAMFORMER_LIB selects the library, tools/build_variant.sh builds the other one) and compare.
 Run from the repository root on a GPU box:  PYTHONPATH=. python tools/push_digest.py --json profiles/push_digest.json"""
 import argparse
@@ -16,6 +17,8 @@ import torch
 from ogl_beamforming_amd import lib, params as P
 from tests import cases
 from tests.test_gpu_burst import noise_frames, row_end_case
+from tests.test_gpu_views import kernel_views, per_view_views, prepared
+from tests.test_views_host import mixed_views
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--json", default="")
@@ -148,6 +151,143 @@ padded[:, : acq.rf.shape[1]] = noise_frames(acq, 1, 600)[0]
 assert padded.nbytes >= OVERLAP_BYTES > padded.nbytes - rows * acq.rf.itemsize
 fresh(acq)
 result["rca_shuffled_padded_8MiB"] = {"single": single(acq, padded), "rf_bytes": padded.nbytes}
+
+# ---- views pushes: one RF frame on K grids ----
+PREFER, NO_KERNEL, FAIL_DAS = P.HIP_DAS_PATH_PREFER_VIEWS_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL, P.HIP_DAS_PATH_FAIL_VIEWS_DAS
+
+
+def sha(frame):
+    return hashlib.sha256(np.ascontiguousarray(frame).tobytes()).hexdigest()
+
+
+def row(pairs=False):
+    """the newest frame's row of the timing table"""
+    t = P.HipFrameTimings()
+    assert L.beamformer_hip_get_last_frame_timings(C.byref(t)), lib.last_error()
+    out = {"das_path": int(t.das_path), "das_row_end_planes": int(t.das_row_end_planes), "das_voxels": int(t.das_voxels),
+           "stage_kinds": [int(t.stage_kind[i]) for i in range(int(t.stage_count))],
+           "staged_and_tile_counters": [int(t.staged_window_violations), int(t.tile_staged_chunks), int(t.tile_gather_chunks)]}
+    if pairs:
+        out["das_pairs"] = int(t.das_pairs)
+    return out
+
+
+def views_push(rf, views, on_device=False, pairs=False):
+    """one views push: per view its id, digest and the path of its own decision; the push's route and stage kinds; the last view's row"""
+    rf = np.ascontiguousarray(rf)
+    array = (P.HipView * len(views))(*views)
+    if on_device:
+        dev = torch.from_numpy(rf.view(np.uint8).reshape(-1)).cuda()
+        torch.cuda.synchronize()
+        assert L.beamformer_hip_push_device_data_views_with_compute(C.c_void_p(dev.data_ptr()), rf.nbytes, array, len(views), 0), lib.last_error()
+        assert L.beamformer_hip_synchronize()
+    else:
+        assert L.beamformer_hip_push_data_views_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, array, len(views), 0), lib.last_error()
+    frames = lib.get_last_views(views)
+    info = lib.last_views_info()
+    assert int(info.view_count) == len(views)
+    return {"views": [{"id": int(info.first_frame_id) + k, "sha256": sha(frames[k]), "das_path": int(info.route.path[k])} for k in range(len(views))],
+            "route": {"kernel_views": int(info.route.kernel_views), "das_launches": int(info.route.das_launches), "reason": info.route.reason.decode(),
+                      "stage_kinds": [int(info.stage_kind[i]) for i in range(int(info.stage_count))]},
+            "last_row": row(pairs)}
+
+
+def served():
+    """which of the two info calls the newest push serves, and the error of the one it refuses"""
+    out = {}
+    for name, fn, struct in (("burst_info", L.beamformer_hip_get_last_burst_info, P.HipBurstInfo), ("views_info", L.beamformer_hip_get_last_views_info, P.HipViewsInfo)):
+        info = struct()
+        out[name] = "served" if fn(C.byref(info)) else lib.last_error()[0].name
+    return out
+
+
+try:
+    # the views kernel's view set under the automatic path, preferred and switched off, from host and from device-resident RF
+    acq = cases.make("config1_small")
+    rf = noise_frames(acq, 6, 700)
+    views = kernel_views(acq)
+    result["views_config1_small"] = {}
+    for name, mode in (("auto", 0), ("prefer_kernel", PREFER), ("no_kernel", NO_KERNEL)):
+        fresh(acq)
+        L.beamformer_hip_set_das_path(mode)
+        result["views_config1_small"][name] = {"host": views_push(rf[0], views), "device": views_push(rf[1], views, on_device=True)}
+
+    # views the kernel takes and views it does not, in one push
+    mixed = cases.make("rca_flash_none_tx")
+    fresh(mixed)
+    L.beamformer_hip_set_das_path(PREFER)
+    result["views_mixed"] = views_push(noise_frames(mixed, 1, 710)[0], mixed_views(mixed))
+    L.beamformer_hip_set_das_path(0)
+
+    # every view its own single-frame launch(es): the staged counters and the hercules tables per view
+    for k, name in enumerate(["rca_staged_auto", "hercules_wide_cw"]):
+        other = cases.make(name)
+        fresh(other)
+        result["views_" + name] = views_push(noise_frames(other, 1, 720 + k)[0], per_view_views(other))
+
+    # several parts per view: the plane, the rows around the depth at which the RF rows end, the strip past them
+    ends, ends_rf, ends_views, _ = prepared("row_ends_linear")
+    fresh(ends)
+    L.beamformer_hip_set_das_path(PREFER)
+    result["views_row_ends_linear"] = {"prefer_kernel": views_push(ends_rf, ends_views)}
+    L.beamformer_hip_set_das_path(NO_KERNEL)
+    result["views_row_ends_linear"]["no_kernel"] = views_push(ends_rf, ends_views)
+
+    # pair counting runs per view: view k's count is the newest row's after a push that ends with view k
+    fresh(acq)
+    L.beamformer_hip_enable_pair_counting(1)
+    counted = {}
+    for name, mode in (("prefer_kernel", PREFER), ("no_kernel", NO_KERNEL)):
+        L.beamformer_hip_set_das_path(mode)
+        counted[name] = {"whole": views_push(rf[0], views, pairs=True),
+                         "das_pairs_of_view": [views_push(rf[0], views[: k + 1], pairs=True)["last_row"]["das_pairs"] for k in range(len(views))]}
+    result["views_config1_small_pair_counting"] = counted
+
+    # more frames than timing slots on the per-frame route, pair counting on: counters and pair-count copies for the newest 32 only
+    fresh(acq)
+    L.beamformer_hip_set_das_path(P.HIP_DAS_PATH_NO_BURST_KERNEL)
+    result["config1_small_pair_counting_burst40"] = burst(acq, noise_frames(acq, 40, 730), pairs=True)
+    L.beamformer_hip_enable_pair_counting(0)
+
+    # a views push that fails at its DAS stage (flag 0x2000), in both routes: failure, a tombstone under every id, the next single push
+    three = views[:3]
+    array = (P.HipView * 3)(*three)
+    result["views_failed"] = {}
+    for name, mode in (("prefer_kernel", PREFER), ("no_kernel", NO_KERNEL)):
+        fresh(acq)
+        L.beamformer_hip_set_das_path(mode)
+        before = single(acq, rf[2])
+        L.beamformer_hip_set_das_path(mode | FAIL_DAS)
+        pushed = bool(L.beamformer_hip_push_data_views_with_compute(rf[3].ctypes.data_as(C.c_void_p), rf[3].nbytes, array, 3, 0))
+        entry = {"before": before, "push": "served" if pushed else lib.last_error()[0].name, "info": served(), "last_frames": {}}
+        sentinel = np.full(1 << 16, -7.0, np.float32)
+        for count in (1, 2, 3):
+            ok = bool(L.beamformer_get_last_frames(sentinel.ctypes.data_as(C.c_void_p), sentinel.nbytes, count))
+            entry["last_frames"][str(count)] = {"served": ok, "error": lib.last_error()[0].name, "buffer_untouched": bool((sentinel == -7.0).all())}
+        entry["frame_info_served"] = bool(L.beamformer_hip_get_last_frame_info(C.byref(P.HipFrameInfo())))
+        entry["frame_timings_served"] = bool(L.beamformer_hip_get_last_frame_timings(C.byref(P.HipFrameTimings())))
+        L.beamformer_hip_set_das_path(mode)
+        entry["single_after"] = single(acq, rf[4])
+        entry["views_after"] = views_push(rf[5], three)
+        result["views_failed"][name] = entry
+
+    # single -> views -> burst -> views -> single: which info call each push leaves served
+    fresh(acq)
+    L.beamformer_hip_set_das_path(0)
+    sequence = []
+    for step in ("single", "views", "burst", "views", "single"):
+        if step == "single":
+            entry = single(acq, rf[0])
+        elif step == "views":
+            entry = views_push(rf[1], three)
+        else:
+            entry = burst(acq, rf[:5])
+        sequence.append({"push": step, "result": entry, "info": served()})
+    result["single_views_burst_views_single"] = sequence
+finally:
+    L.beamformer_hip_enable_pair_counting(0)
+    L.beamformer_hip_set_das_path(0)
+
 
 text = json.dumps(result, indent=1, sort_keys=True)
 print(text)
