@@ -138,6 +138,31 @@ def test_a_frame_closer_to_the_truth_passes_on_the_second_bar(seed):
         parity.compare(gpu, ref, acq, flags)
 
 
+def test_the_twin_bar_sees_what_the_pipeline_bar_cannot():
+    """rca_staged_auto (Int16 + Demodulate: 2e-3) and its DAS-only twin (tests/twins.py: 1e-4): the same error of 5e-4 of the frame
+    maximum, planted at one valid voxel with no row-end mark, passes on the original and is refused on the twin"""
+    from oracle import binding
+    from tests import twins
+    acq = cases.make("rca_staged_auto")
+    twin, ref, _, _ = twins.oracle_twin(binding, acq)
+    twin_ref, _, twin_flags = parity.reference(binding, twin)
+    assert np.array_equal(twins.bits(twin_ref), twins.bits(ref))
+    assert cases.tolerance(acq) == 2e-3 and cases.tolerance(twin) == 1e-4
+    ok = ~np.isnan(ref)
+    scale = float(np.abs(ref[ok]).max())
+    marks = parity.row_end_marks(twin, twin_ref.shape, twin_ref)
+    cands = np.argwhere(ok & ~marks)
+    at = tuple(cands[len(cands) // 2])
+    planted = ref.copy()
+    planted[at] += ref.dtype.type(5e-4 * scale)
+    v = parity.compare(planted, ref, acq, None)
+    assert v.bar == "first" and 4e-4 < v.max_rel_err < 6e-4
+    planted_twin = twin_ref.copy()
+    planted_twin[at] += twin_ref.dtype.type(5e-4 * scale)
+    with pytest.raises(AssertionError, match="further from the double-precision truth"):
+        parity.compare(planted_twin, twin_ref, twin, twin_flags)
+
+
 def test_the_flips_are_at_row_ends_and_rounding_alone_is_not_a_flip():
     """the oracle marks the voxels that hold a term within float rounding of an end of its RF row: every voxel of the row-end draws at
     which it is more than 1.5 tol from its twin is one of them.  On draw_paired 14 (Int16Complex with coherency weighting, 1e-4 bar, no row
