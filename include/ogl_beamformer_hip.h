@@ -287,6 +287,12 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_sum_last_frames(uint32_t count, vo
  * differs from that, when there is no such frame, or with several devices (beamformer_hip_set_devices). */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_copy_das_input(void *out, uint64_t size);
 
+/* The same for RF frame `frame` of the newest push: a burst's frame `frame` (0: its oldest), each frame of the layout and size above;
+ * a single push and a views push hold one RF frame, frame 0.  beamformer_hip_copy_das_input serves the newest frame: after a burst its
+ * last one.  Valid until the next push.  Returns 0 (InvalidAccess) when frame is not below the push's RF frame count, and where
+ * beamformer_hip_copy_das_input does. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_copy_das_input_frame(uint32_t frame, void *out, uint64_t size);
+
 /* Display reduction of the newest frame, the step on the far side of the path: the per-voxel
  * intensity the reference's render shader computes (sample_value, shaders/render_3d.frag.glsl:
  * 50-73; defaults threshold 55 dB, gamma 1, dynamic range 50 dB, ui.c:880-883): |v| clamped to

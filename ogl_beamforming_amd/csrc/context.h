@@ -161,9 +161,12 @@ struct Device {
 	uint64_t     last_rf_bytes = 0;
 	const void  *last_rf = nullptr;                            /* what the newest frame's first stage read: the library's own RF slot, never a caller's pointer */
 	bool         last_rf_sum_ready = false;                    /* a borrowed device buffer: its checksum was taken inside the push */
-	const void  *das_input = nullptr;                          /* what the newest frame's DAS stage read (the RF slot or a scratch buffer; null:
-	                                                              no DAS stage, or the frame did not reach it) and its size -- beamformer_hip_copy_das_input */
-	uint64_t     das_input_bytes = 0;
+	const void  *das_input = nullptr;                          /* what the newest push's DAS stage read (the RF slot, a scratch buffer or a burst's
+	                                                              stage buffer; null: no DAS stage, or the push did not reach it), a frame's size,
+	                                                              and -- a burst -- the frames it holds, das_input_stride bytes apart (one frame, or
+	                                                              a views push's one input: stride 0) -- beamformer_hip_copy_das_input_frame */
+	uint64_t     das_input_bytes = 0, das_input_stride = 0;
+	uint32_t     das_input_frames = 0;
 	/* frame graphs (beamformer_hip_enable_frame_graphs): one instantiated hipGraph per parameter block, updated
 	 * in place from each frame's capture; graph_generation = the plan generation it was warmed up for */
 	hipGraphExec_t frame_exec[BeamformerMaxParameterBlocks]{};
@@ -220,6 +223,7 @@ bool device_info(uint32_t device_index, BeamformerHipDeviceInfo *out);
 bool fill_stats_table(BeamformerComputeStatsTable *out);
 bool frame_min_max(float out[2]);
 bool copy_das_input(void *out, uint64_t out_size);
+bool copy_das_input_frame(uint32_t frame, void *out, uint64_t out_size);
 bool sum_last_frames(uint32_t count, void *out, uint64_t out_size);
 bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float *out, uint64_t out_floats);
 void shutdown_device();

@@ -198,7 +198,7 @@ static void release_one_device(Device &d)
 	d.ring_next_offset = 0; d.frame_counter = 0; d.rf_index = 0;
 	d.have_sample = false; d.last_sampled_frame = 0; d.last_sampled_block = 0; d.replan_frame = 0;
 	d.last_rf = nullptr; d.last_rf_bytes = 0; d.last_rf_slot = 0; d.peer_access = 2;
-	d.das_input = nullptr; d.das_input_bytes = 0;
+	d.das_input = nullptr; d.das_input_bytes = d.das_input_stride = 0; d.das_input_frames = 0;
 	d.device = -1;
 }
 
@@ -736,7 +736,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	int64_t  cur_bound = w.in_bound;
 	int toggle = 0;
 	bool ok = true;
-	d.das_input = nullptr; d.das_input_bytes = 0;
+	d.das_input = nullptr; d.das_input_bytes = d.das_input_stride = 0; d.das_input_frames = 0;
 
 	uint32_t zfirst = 0, zcount = plan.output_points[2];
 	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
@@ -774,9 +774,10 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes);
 			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 			if (poison && run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0xFF, run_bytes, s));
-			if (N == 1) {                /* all jobs share one input (beamformer_hip_copy_das_input serves single frames and views pushes) */
-				d.das_input = cur; d.das_input_bytes = (uint64_t)plan.das_samples * plan.acquisitions * plan.channels * voxel_bytes;   /* [channel][transmit][sample] */
-			}
+			/* what beamformer_hip_copy_das_input_frame serves: RF frame k's input at k * cur_stride (one RF frame -- a single push, a views
+			 * push -- : all jobs share the one input) */
+			d.das_input = cur; d.das_input_bytes = (uint64_t)plan.das_samples * plan.acquisitions * plan.channels * voxel_bytes;   /* [channel][transmit][sample] */
+			d.das_input_stride = N > 1 ? cur_stride : 0; d.das_input_frames = N;
 			/* (Flag 0x2000: a views push's step fails here, as a refused launch would -- the only way to a views push's tombstones that
 			 * needs no device fault: everything a caller can get wrong is refused before the ids are taken) */
 			if (w.views && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
@@ -1742,22 +1743,33 @@ static bool newest_layout(Context &c, uint64_t offsets[kMaxDevices], uint64_t pe
 	return true;
 }
 
-/* beamformer_hip_copy_das_input: the buffer the newest frame's DAS stage read, [channel][transmit][sample]; one device only */
-bool copy_das_input(void *out, uint64_t out_size)
+/* beamformer_hip_copy_das_input_frame: what the DAS stage read for RF frame `frame` of the newest push, [channel][transmit][sample]; one
+ * device only */
+bool copy_das_input_frame(uint32_t frame, void *out, uint64_t out_size)
 {
 	Context &c = g_context;
 	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	Device &d = c.devices[0];
-	if (!newest_record(d) || !d.das_input || out_size != d.das_input_bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	/* a parameter push since that frame may have regrown (reallocated) the buffer: then there is nothing to copy */
+	if (!newest_record(d) || !d.das_input || frame >= d.das_input_frames || out_size != d.das_input_bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	/* a parameter push since that push may have regrown (reallocated) the buffer: then there is nothing to copy */
+	const uint64_t offset = (uint64_t)frame * d.das_input_stride, end = offset + out_size;
 	bool live = false;
-	for (const DeviceBuffer &b : d.scratch) live |= b.ptr == d.das_input && b.size >= out_size;
-	for (const DeviceBuffer &b : d.rf)      live |= b.ptr == d.das_input && b.size >= out_size;
+	for (const DeviceBuffer &b : d.scratch)     live |= b.ptr == d.das_input && b.size >= end;
+	for (const DeviceBuffer &b : d.burst_stage) live |= b.ptr == d.das_input && b.size >= end;
+	for (const DeviceBuffer &b : d.rf)          live |= b.ptr == d.das_input && b.size >= end;      /* (a plan with no pre-DAS stage) */
 	if (!live) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && HIP_OK(hipMemcpyAsync(out, d.das_input, out_size, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipMemcpyAsync(out, (const char *)d.das_input + offset, out_size, hipMemcpyDeviceToHost, d.stream));
 	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
 	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
+}
+
+/* beamformer_hip_copy_das_input: the newest frame's -- a single push's, a views push's one input, a burst's last frame */
+bool copy_das_input(void *out, uint64_t out_size)
+{
+	const Context &c = g_context;
+	const uint32_t frames = c.devices[0].das_input_frames;
+	return copy_das_input_frame(frames ? frames - 1 : 0, out, out_size);
 }
 
 bool frame_min_max(float out[2])

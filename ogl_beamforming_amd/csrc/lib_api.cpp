@@ -666,6 +666,12 @@ uint32_t beamformer_hip_copy_das_input(void *out, uint64_t size)
 	return copy_das_input(out, size);
 }
 
+uint32_t beamformer_hip_copy_das_input_frame(uint32_t frame, void *out, uint64_t size)
+{
+	if (!out) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	return copy_das_input_frame(frame, out, size);
+}
+
 uint32_t beamformer_hip_sum_last_frames(uint32_t count, void *out, uint64_t out_size)
 {
 	if (!out) return set_error(BeamformerLibErrorKind_InvalidAccess);

@@ -119,6 +119,7 @@ def _load():
         "beamformer_hip_frame_min_max": (u32, [C.POINTER(C.c_float)]),
         "beamformer_hip_sum_last_frames": (u32, [u32, vp, u64]),
         "beamformer_hip_copy_das_input": (u32, [vp, u64]),
+        "beamformer_hip_copy_das_input_frame": (u32, [u32, vp, u64]),
         "beamformer_hip_display_last_frame": (u32, [C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), u64]),
         "beamformer_hip_enable_hilbert": (u32, [u32]),
         "beamformer_hip_set_das_path": (u32, [u32]),
@@ -351,15 +352,19 @@ def get_last_frame(bp, shard_planes=None):
     return raw[:voxels].reshape(shape)
 
 
-def das_input(bp):
+def das_input(bp, frame=None):
     """beamformer_hip_copy_das_input: what the newest frame's DAS stage read, as float32 or complex64 of shape
-    (channels, transmits, DAS samples).  Valid until the next push; one device only."""
+    (channels, transmits, DAS samples); frame = k: RF frame k of the newest push (beamformer_hip_copy_das_input_frame: a burst's
+    frame k).  Valid until the next push; one device only."""
     lib = library()
     plan = P.HipPlan()
     _check(lib.beamformer_hip_describe_plan(0, C.byref(plan)))
     shape = (int(bp.channel_count), int(bp.acquisition_count), int(plan.das_samples))
     out = np.empty(int(np.prod(shape)), np.complex64 if plan.iq_pipeline else np.float32)
-    _check(lib.beamformer_hip_copy_das_input(out.ctypes.data_as(C.c_void_p), out.nbytes))
+    if frame is None:
+        _check(lib.beamformer_hip_copy_das_input(out.ctypes.data_as(C.c_void_p), out.nbytes))
+    else:
+        _check(lib.beamformer_hip_copy_das_input_frame(frame, out.ctypes.data_as(C.c_void_p), out.nbytes))
     return out.reshape(shape)
 
 

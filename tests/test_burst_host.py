@@ -11,7 +11,7 @@ import pytest
 
 from ogl_beamforming_amd import lib
 from ogl_beamforming_amd import params as P
-from tests import cases
+from tests import burst_chunk_cases, cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E = P.LibError
@@ -97,6 +97,38 @@ def test_long_bursts_of_many_channels_take_the_filters_in_chunks():
     lib.library().beamformer_hip_set_das_path(0)
     assert lib.describe_burst(acq.bp, 1023, acq.filters).stage_launches == 1
     assert lib.describe_burst(acq.bp, 1024, acq.filters).stage_launches == 2
+
+
+@pytest.mark.parametrize("name", sorted(burst_chunk_cases.CASES))
+def test_the_chunk_boundary_cases_cross_a_chunk(name):
+    """tests/burst_chunk_cases.py, which tests/test_gpu_stages_burst.py runs on the device: 257 frames take two launches of the
+    filter-shaped stages and 255 take one, so that a change to a case or to the chunk rule cannot turn the device test into a one-launch
+    test unseen; and each case keeps the stage form it is there for"""
+    bc = burst_chunk_cases
+    L = lib.library()
+    L.beamformer_hip_set_das_path(0)
+    assert L.beamformer_hip_enable_hilbert(1 if name in bc.NEEDS_HILBERT else 0)
+    try:
+        acq = bc.CASES[name]()
+        assert (bc.FRAMES, bc.CHANNELS, bc.CHUNK) == (257, 256, 255) and acq.bp.channel_count == bc.CHANNELS
+        assert lib.describe_burst(acq.bp, bc.FRAMES, acq.filters).stage_launches == 2
+        assert lib.describe_burst(acq.bp, bc.CHUNK, acq.filters).stage_launches == 1
+        plan = P.HipPlan()
+        assert L.beamformer_hip_describe_plan(0, C.byref(plan))
+        kinds = [int(plan.stages[i].kind) for i in range(plan.stage_count)]
+        S = P.ShaderKind
+        assert kinds == {"demodulate_das": [S.Demodulate, S.DAS], "demodulate_decode_das": [S.Demodulate, S.Decode, S.DAS],
+                         "decode_hilbert_das": [S.Hilbert, S.DAS]}[name]
+        first = plan.stages[0]
+        if name == "demodulate_decode_das":      # the transposing 1024-thread filter form (csrc/stages.hip launch_filter_chunk)
+            assert acq.bp.acquisition_count == 4 and first.out_stride[2] == 1 and first.out_stride[0] >= 4 and first.out_kind & 1
+        if name == "demodulate_das":
+            assert acq.bp.decimation_rate == 2 and acq.bp.acquisition_count == 1 and acq.bp.data_kind == int(P.DataKind.Int16)
+    finally:
+        L.beamformer_hip_enable_hilbert(0)
+    a = bc.assignment(9400)
+    assert len(a) == bc.FRAMES and len({a[254], a[255], a[256]}) == 3 and a[255] != a[0] and a[256] != a[1]
+    assert np.array_equal(a, bc.assignment(9400)) and len(set(a)) == bc.SOURCES
 
 
 def push_parameters(acq):

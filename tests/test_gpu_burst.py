@@ -63,6 +63,22 @@ def single_push(bflib, acq, rf):
     return bflib.get_last_frame(acq.bp).copy()
 
 
+def close_to_single_push(oracle, acq, rf, one, frame, k):
+    """a burst's frame `frame` against the single push `one` of the same RF, where another DAS kernel computed it (the burst kernel):
+    within the case's tolerance of the frame maximum"""
+    assert np.array_equal(np.isnan(one), np.isnan(frame))
+    ok = ~np.isnan(one)
+    scale = np.abs(one[ok]).max()
+    slack = cases.tolerance(acq) * scale
+    if acq.bp.interpolation_mode == int(I.Nearest):
+        # a tap within float rounding of k + 1/2 may fall either way in either kernel: the oracle's per-voxel budget, once each
+        flags = {}
+        oracle.beamform(acq.bp, rf, acq.filters, flags=flags)
+        slack = slack + 2.02 * flags["budget"][ok]
+    err = np.abs(one[ok] - frame[ok])
+    assert (err <= slack).all(), f"frame {k}: burst and single push differ by {err.max() / scale:.3e} of the frame maximum"
+
+
 def check_burst(bflib, oracle, acq, n, seed, expect_kernel, against_single=True):
     """one burst of n noise frames: parity of every frame, pairwise different frames, frame k belongs to RF k, the route the library
     reports, and every frame against the single push of the same RF.  Returns (frames, RF)."""
@@ -96,21 +112,9 @@ def check_burst(bflib, oracle, acq, n, seed, expect_kernel, against_single=True)
         assert same_bits(again[i], gpu[perm[i]]), f"frame {i} of the permuted burst is not the frame of RF {perm[i]}"
     if against_single:
         identical = 0
-        tol = cases.tolerance(acq)
-        nearest = acq.bp.interpolation_mode == int(I.Nearest)
         for k in range(n):
             one = single_push(bflib, acq, rf[k])
-            assert np.array_equal(np.isnan(one), np.isnan(gpu[k]))
-            ok = ~np.isnan(one)
-            scale = np.abs(one[ok]).max()
-            slack = tol * scale
-            if nearest:
-                # a tap within float rounding of k + 1/2 may fall either way in either kernel: the oracle's per-voxel budget, once each
-                flags = {}
-                oracle.beamform(acq.bp, rf[k], acq.filters, flags=flags)
-                slack = slack + 2.02 * flags["budget"][ok]
-            err = np.abs(one[ok] - gpu[k][ok])
-            assert (err <= slack).all(), f"frame {k}: burst and single push differ by {err.max() / scale:.3e} of the frame maximum"
+            close_to_single_push(oracle, acq, rf[k], one, gpu[k], k)
             identical += same_bits(one, gpu[k])
         if expect_kernel:
             print(f"{acq.name}: {identical} of {n} frames of the burst equal their single push bit for bit")

@@ -1,4 +1,4 @@
-"""Element-wise parity of the stages in front of DAS (ingest, channel map, A1S2, Reshape, Decode, Filter / Demodulate): every
+"""Element-wise parity of the stages in front of DAS (ingest, channel map, A1S2, Reshape, Decode, Filter / Demodulate, Hilbert): every
 case pushes through the C ABI with the SCRATCH_POISON hook set (both intermediate buffers and the ring slot are 0xFF bytes --
 NaN -- when the frame starts), reads back what the DAS stage read (beamformer_hip_copy_das_input) and compares it element by
 element with the oracle's capture of the same buffer; then the frame with test_gpu_parity.compare.  A frame-level bar dilutes
@@ -55,6 +55,13 @@ def filter_taps(oracle, fp):
     else:
         h = np.abs(buf[:L].astype(np.float64))
     return h, L, complex_filter
+
+
+def hilbert_taps(oracle):
+    """(|hr| + |hi| per tap, length) of the build-defined Hilbert FIR, in the correlation order both builds apply it"""
+    taps = np.zeros(2 * 63, np.float32)
+    oracle.library().oracle_hilbert_fir(taps.ctypes.data_as(C.POINTER(C.c_float)))
+    return np.abs(taps[0::2].astype(np.float64)) + np.abs(taps[1::2].astype(np.float64)), 63
 
 
 def plan_of(bflib, acq):
@@ -180,6 +187,25 @@ def stage_bounds(bflib, oracle, acq, plan):
                     err[dst + part] = E
             else:
                 mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, M, E)
+        elif kind == int(S.Hilbert):
+            # a filter stage without demodulation: 63 complex taps on the real input samples of the row itself (outside it: zero),
+            # L terms per component, f32 products and sums; int / f16 -> f32 conversion of the input is exact
+            assert not st.in_kind & 1 and st.out_kind & 1, "the Hilbert stage takes real samples and stores complex ones"
+            h, L = hilbert_taps(oracle)
+            M = np.zeros((Cn, A, Sd))
+            E = np.zeros((Cn, A, Sd))
+            pad = np.zeros(L - 1)
+            for c in range(Cn):
+                for t in range(A):
+                    row = ist[0] * np.arange(Sd) + ist[1] * c + ist[2] * t
+                    M[c, t] = np.correlate(np.concatenate([pad, in_m[row]]), h, "valid")
+                    E[c, t] = np.correlate(np.concatenate([pad, in_e[row]]), h, "valid")
+            E = E + k_sum(L) * U32 * M
+            if out_f16:
+                E = E + K_STORE * U16 * M
+            exact = integer = False
+            dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
+            mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, M, E)
         else:
             raise AssertionError(f"stage kind {kind} not modelled")
     das = plan.stages[das_index]
@@ -353,16 +379,20 @@ def test_ragged_rows(S_, demod, bflib, oracle, hooks):
 DECODE_KINDS = (DK.Int16, DK.Float16, DK.Float32Complex)
 
 
+def decode_order_case(A, kind):
+    S_ = 200 if A >= 40 else 1000
+    Cn = 4
+    z1 = 0.8 * cfg.SPEED_OF_SOUND * (S_ / FS) / 2
+    return cfg.rca(f"decode_A{A}_{kind.name}", Cn, A, S_, (8, 1, 12), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1), seed=500 + A,
+                   data_kind=kind, stages=(S.Decode, S.DAS), decode=1, fs=FS, fd=FD, pitch=PITCH, angles=np.linspace(-5, 5, A))
+
+
 @pytest.mark.parametrize("kind", DECODE_KINDS, ids=[k.name for k in DECODE_KINDS])
 @pytest.mark.parametrize("A", [2, 20, 24, 40, 128])
 def test_decode_orders(A, kind, bflib, oracle, hooks):
     """FWHT base 20 (A = 20, 40), base 12 x 2 (24), the dense kernel's i0 + k < T guard (A = 2), 66 KiB of dynamic LDS (128
     complex) -- against the oracle, and the Walsh-Hadamard form against the forced-dense one (0x20)"""
-    S_ = 200 if A >= 40 else 1000
-    Cn = 4
-    z1 = 0.8 * cfg.SPEED_OF_SOUND * (S_ / FS) / 2
-    acq = cfg.rca(f"decode_A{A}_{kind.name}", Cn, A, S_, (8, 1, 12), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1), seed=500 + A,
-                  data_kind=kind, stages=(S.Decode, S.DAS), decode=1, fs=FS, fd=FD, pitch=PITCH, angles=np.linspace(-5, 5, A))
+    acq = decode_order_case(A, kind)
     _, ref_in, results = run_case(bflib, oracle, hooks, acq, modes=(0, 0x20))
     (fast_frame, fast_in, (bar_fast, _)), (dense_frame, dense_in, (bar_dense, _)) = results
     if kind == DK.Int16:
@@ -378,9 +408,7 @@ def test_decode_orders(A, kind, bflib, oracle, hooks):
 F16C_STAGES = {"das": (S.Decode, S.DAS), "decode": (S.Decode, S.DAS), "filter": (S.Decode, S.Filter, S.DAS)}
 
 
-@pytest.mark.parametrize("pipeline", sorted(F16C_STAGES))
-def test_float16_complex_rf(pipeline, bflib, oracle, hooks):
-    """raw Float16Complex RF: converted by a Reshape, decoded, or through a complex matched-chirp filter"""
+def float16_complex_case(pipeline):
     S_ = 512
     z1 = 0.8 * cfg.SPEED_OF_SOUND * (S_ / FS) / 2
     acq = cfg.rca(f"f16c_{pipeline}", 8, 4, S_, (12, 1, 16), (-2e-3, 0, 0.3 * z1), (2e-3, 0, z1), seed=600 + len(pipeline),
@@ -388,7 +416,13 @@ def test_float16_complex_rf(pipeline, bflib, oracle, hooks):
                   fs=FS, fd=FD, pitch=PITCH, angles=np.linspace(-5, 5, 4))
     if pipeline == "filter":
         acq.filters = [cfg.matched_chirp_filter(FS, 2e-6, 2e6, 8e6)]
-    run_case(bflib, oracle, hooks, acq)
+    return acq
+
+
+@pytest.mark.parametrize("pipeline", sorted(F16C_STAGES))
+def test_float16_complex_rf(pipeline, bflib, oracle, hooks):
+    """raw Float16Complex RF: converted by a Reshape, decoded, or through a complex matched-chirp filter"""
+    run_case(bflib, oracle, hooks, float16_complex_case(pipeline))
 
 
 # ------------------------------------------------------------------------------------------------ every named case

@@ -21,12 +21,30 @@ def acquisitions():
                                       data_kind=D.Float32, interp=I.Cubic, cw=True, orientation=0x12)
     out["hercules_decode"] = cfg.hercules("hercules_hilbert", 16, 8, 512, (8, 8, 6), LO3, HI3, seed=73, data_kind=D.Float16)
     out["forces_decode"] = cfg.forces("forces_hilbert", 16, 8, 512, (16, 1, 12), LO3, HI3, seed=74)
-    for acq in out.values():                                  # {Decode, DAS} -> {Decode, Hilbert, DAS}
-        bp = acq.bp
-        assert list(bp.compute_stages[:2]) == [int(S.Decode), int(S.DAS)]
-        bp.compute_stages[1], bp.compute_stages[2] = int(S.Hilbert), int(S.DAS)
-        bp.compute_stages_count = 3
+    for acq in out.values():
+        with_hilbert(acq)
     return out
+
+
+def with_hilbert(acq):
+    """{Decode, DAS} -> {Decode, Hilbert, DAS}"""
+    bp = acq.bp
+    assert list(bp.compute_stages[:2]) == [int(S.Decode), int(S.DAS)]
+    bp.compute_stages[1], bp.compute_stages[2] = int(S.Hilbert), int(S.DAS)
+    bp.compute_stages_count = 3
+    return acq
+
+
+RAGGED_SAMPLES = (130, 1001)
+
+
+def ragged_acquisition(samples):
+    """tests/test_gpu_stages.py's decoded ragged rows with the stage behind the Decode: a wave's window is 64 + 62 samples, so 130
+    leaves a last group of two outputs whose window ends 62 samples past the row, and 1001 an odd row"""
+    from tests.test_gpu_stages import ragged_case
+    acq = with_hilbert(ragged_case(samples, False, seed=800 + samples))
+    acq.name = f"ragged_{samples}_hilbert"
+    return acq
 
 
 @pytest.fixture
@@ -109,3 +127,14 @@ def test_frame_parity_with_the_stage(name, bflib, oracle, hilbert):
         finally:
             bflib.library().beamformer_hip_set_das_path(0)
         compare(gpu, ref, acq, flags)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(acquisitions()) + [f"ragged_{n}" for n in RAGGED_SAMPLES])
+def test_das_input_with_the_stage(name, bflib, oracle, hooks, hilbert):
+    """the element-wise bar of tests/test_gpu_stages.py in a single push with SCRATCH_POISON: what the DAS stage read against the
+    oracle's capture of it, inside the forward-error bound stage_bounds propagates through the 63 taps; then the frame"""
+    from tests.test_gpu_stages import run_case
+    acq = ragged_acquisition(int(name[7:])) if name.startswith("ragged_") else acquisitions()[name]
+    _, _, results = run_case(bflib, oracle, hooks, acq)
+    assert results[0][2][0] == "bound"
