@@ -58,6 +58,16 @@ __device__ __forceinline__ float div_speed_of_sound(float distance, float inv_sp
 	return __builtin_fmaf(e, inv_speed_of_sound, q);
 }
 
+/* demodulation phase of a partial sample index, in turns in [0,1): fract(k * index) with the
+ * rounding error of the product recovered by an fma, so that splitting the phase in two
+ * parts does not cost precision (Q3 of oracle/oracle.h: the phase is defined range-reduced) */
+__device__ __forceinline__ float phase_turns(float k, float index)
+{
+	float p = k * index;
+	float e = __builtin_fmaf(k, index, -p);
+	return hw_fract(p) + e;
+}
+
 /* The LDS-staged kernels (das_staged*.hip) trust the host's bound on the delay spread of a tile (plan_staged, das_select.cpp): a
  * position outside the staged window would read a neighbouring transmit's window -- wrong voxels, no fault.  Their range-checked loop
  * (every wave under the STAGED_CHECKED hook) therefore tests every term; an offending wave raises a flag in the first LDS word (the

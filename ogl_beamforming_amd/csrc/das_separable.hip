@@ -24,21 +24,12 @@
  * read neighbouring RF windows) share an L2.  Gather-accumulate, VALU/L1-bound: no MFMA.
  */
 #include "das_exact.h"
+#include "das_staged_shared.h"
 
 /* (voxel, channel, transmit) terms whose gathers are in flight together per lane */
 #ifndef BF_SEP_BATCH
 #define BF_SEP_BATCH 4
 #endif
-
-/* demodulation phase of a partial sample index, in turns in [0,1): fract(k * index) with the
- * rounding error of the product recovered by an fma, so that splitting the phase in two
- * parts does not cost precision (Q3 of oracle/oracle.h: the phase is defined range-reduced) */
-__device__ __forceinline__ float phase_turns(float k, float index)
-{
-	float p = k * index;
-	float e = __builtin_fmaf(k, index, -p);
-	return hw_fract(p) + e;
-}
 
 /* LDS tables, 16-byte entries so that every read is one ds_read_b128:
  *   R[(c - c0)*U + u] = { r_index, apod*cos(phi_r), apod*sin(phi_r), apod }   (apod == 0: fails the F# test)
@@ -61,23 +52,8 @@ __global__ __launch_bounds__(1024, 8) void das_rca_separable_kernel(const BfDasA
 	f32x4 *R = sep_lds;
 	f32x4 *T = sep_lds + (size_t)chunk * U;
 
-	/* blockIdx -> tile with each XCD walking a contiguous run of tiles (das.hip) */
-	const uint32_t total = q.tiles[0] * q.tiles[1] * q.tiles[2];
-	const uint32_t per   = (total + 7u) / 8u;
-	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-	if (tile >= total) return;                               /* whole block: no barrier is skipped */
-	/* walk order of the tile list.  Depth-major (default): consecutive tiles -- the ones an XCD has in
-	 * flight together -- are a few columns adjacent along u at consecutive depths, whose RF windows overlap
-	 * (the window moves ~1.5 samples per plane and ~14 per tile laterally at config 4), so the lines one tile
-	 * pulls into the XCD's L2 serve its neighbours (bf_column_walk, bf_kernels.h).  Plane-major: x, then y, then z. */
-	uint32_t tu, tv, zl;                                         /* along the receive axis, along the transmit axis, plane inside the shard */
-	if (q.depth_major) {
-		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
-	} else {
-		tu = tile % q.tiles[0];
-		tv = (tile / q.tiles[0]) % q.tiles[1];
-		zl = tile / (q.tiles[0] * q.tiles[1]);
-	}
+	uint32_t tu, tv, zl;
+	if (!staged_tile_of<~0u>(q, false, tu, tv, zl)) return;  /* whole block; depth-major on any bit of q.depth_major */
 	const uint32_t z  = p.z_first + zl;
 
 	const uint32_t u_axis = q.u_axis, v_axis = 1u - q.u_axis;
@@ -87,7 +63,9 @@ __global__ __launch_bounds__(1024, 8) void das_rca_separable_kernel(const BfDasA
 	const float phase_k = p.demodulation_frequency * p.inv_sampling_frequency;
 	const bool  rx_rows = (p.transmits[0].flags & BF_RX_ROWS) != 0;
 
-	/* ---- transmit table: A x V entries, built once */
+	/* ---- transmit table: A x V entries, built once.  The index is rca_transmit_index (das_staged_shared.h) written out: as a call
+	 * hipcc gave the cubic complex instances 64 VGPRs and 3 spills where this text gives 57 and 59.  A change to one is a change
+	 * to the other: the row-end rule (das_select.cpp) assumes every kernel of the family forms the same index. */
 	for (uint32_t e = threadIdx.x; e < (uint32_t)A * V; e += blockDim.x) {
 		uint32_t a = e >> v_shift, iv = e & (V - 1);
 		float coord[3] = {0.f, 0.f, pz};
@@ -111,49 +89,17 @@ __global__ __launch_bounds__(1024, 8) void das_rca_separable_kernel(const BfDasA
 		T[e] = entry;
 	}
 
-	/* tile-wide extremes of the transmit delay (for the range-test shortcut): every wave
-	 * reduces its share of the table, the block combines the per-wave results */
 	__shared__ f32x2 wave_range[16];
-	__syncthreads();
-	{
-		float lo = __builtin_inff(), hi = -__builtin_inff();
-		for (uint32_t e = threadIdx.x; e < (uint32_t)A * V; e += blockDim.x) {
-			float v = T[e].z;
-			lo = fminf(lo, v); hi = fmaxf(hi, v);
-		}
-		for (int off = 32; off > 0; off >>= 1) {
-			lo = fminf(lo, __shfl_xor(lo, off, 64));
-			hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-		}
-		if ((threadIdx.x & 63u) == 0) wave_range[threadIdx.x >> 6] = f32x2{lo, hi};
-	}
-	__syncthreads();
-	f32x2 range = wave_range[0];
-	for (uint32_t w = 1; w < (blockDim.x >> 6); w++) {
-		range.x = fminf(range.x, wave_range[w].x);
-		range.y = fmaxf(range.y, wave_range[w].y);
-	}
-	/* the same for every lane: kept in scalar registers (through scalar temporaries -- das_staged.hip says why) */
-	{
-		const float lo = range.x, hi = range.y;
-		range.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lo)));
-		range.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, hi)));
-	}
+	const f32x2 range = rca_tile_range((uint32_t)A * V, wave_range, [&](uint32_t e) { return T[e].z; });
 
 	/* thread -> voxel: lanes run along the output's x axis */
 	/* (the voxel is worked out again where it is needed -- the row-end fix-up, the store at the very end -- rather than held in
 	 * two vector registers across the channel loop: the cubic instances have none to spare) */
-	auto voxel_of = [&](uint32_t thread, uint32_t &vx, uint32_t &vy, uint32_t &lane_u, uint32_t &lane_v) {
-		if (u_axis == 0) { lane_u = thread & (U - 1); lane_v = thread >> q.u_shift; }
-		else             { lane_v = thread & (V - 1); lane_u = thread >> v_shift; }
-		const uint32_t gu = tu * U + lane_u, gv = tv * V + lane_v;
-		vx = u_axis == 0 ? gu : gv; vy = u_axis == 0 ? gv : gu;
-	};
 	uint32_t lu, lv;
 	bool inside;
 	{
 		uint32_t x0, y0;
-		voxel_of(threadIdx.x, x0, y0, lu, lv);
+		rca_voxel_of(threadIdx.x, u_axis, U, q.u_shift, V, v_shift, tu, tv, x0, y0, lu, lv);
 		inside = x0 < p.size[0] && y0 < p.size[1];
 	}
 
@@ -173,7 +119,7 @@ __global__ __launch_bounds__(1024, 8) void das_rca_separable_kernel(const BfDasA
 		if constexpr (INTERP != BF_INTERP_NEAREST) {
 			uint32_t x, y, unused_u, unused_v, thread = threadIdx.x;
 			asm volatile("" : "+v"(thread));                  /* not the values computed before the loop */
-			voxel_of(thread, x, y, unused_u, unused_v);
+			rca_voxel_of(thread, u_axis, U, q.u_shift, V, v_shift, tu, tv, x, y, unused_u, unused_v);
 			for (int a = 0; a < A; a++) {
 				const float index = r.x + Tl[(size_t)a * V].z;
 				if (bfx::edge_near<INTERP>(index, S, edge_margin) && r.w != 0.f)
@@ -187,7 +133,7 @@ __global__ __launch_bounds__(1024, 8) void das_rca_separable_kernel(const BfDasA
 		__syncthreads();            /* previous chunk's readers are done (and T is complete) */
 		/* ---- receive table for channels [c0, c0 + cn).  The ~50 scalars of the launch arguments it is built from (two 4 x 4 transforms,
 		 * pitch, f-number, speed of sound, ...) are read from the kernel-argument segment here, at the top of every chunk, instead of being
-		 * held in SGPRs across the channel loop (das_staged.hip: the same trick; at 8 waves per SIMD a wave has 80 SGPRs) */
+		 * held in SGPRs across the channel loop (staged_receive_table, das_staged_shared.h: the same trick; at 8 waves per SIMD a wave has 80 SGPRs) */
 		{
 		const bfx::KernelArgs &ka = bfx::kernel_args();
 		const float k_denom_u = fmaxf(1.0f, (float)ka.size[u_axis] - 1.0f);
@@ -360,22 +306,14 @@ __global__ __launch_bounds__(1024, 8) void das_rca_separable_kernel(const BfDasA
 
 	uint32_t x, y, unused_u, unused_v, thread = threadIdx.x;
 	asm volatile("" : "+v"(thread));
-	voxel_of(thread, x, y, unused_u, unused_v);
-	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<VT *>(p.out)[out_index] = coherent;
+	rca_voxel_of(thread, u_axis, U, q.u_shift, V, v_shift, tu, tv, x, y, unused_u, unused_v);
+	rca_store_voxel<CW>(p, zl, x, y, coherent, incoherent);
 }
 
 template <int INTERP, bool CPLX, bool CW, int VS>
 static hipError_t launch_sep(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
-	uint32_t total = q->tiles[0] * q->tiles[1] * q->tiles[2];
-	uint32_t grid  = ((total + 7u) / 8u) * 8u;
-	auto kernel = das_rca_separable_kernel<INTERP, CPLX, CW, VS>;
-	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(q->threads), q->lds_bytes, s, *a, *q);
-	return hipGetLastError();
+	return rca_launch_tiles(das_rca_separable_kernel<INTERP, CPLX, CW, VS>, q->tiles[0] * q->tiles[1] * q->tiles[2], q->threads, a, q, s);
 }
 
 template <int INTERP>

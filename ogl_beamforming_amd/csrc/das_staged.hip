@@ -47,49 +47,7 @@
  * MI355X): 785-850 ms per 512^3 frame against 1116-1191 ms for the gather kernel; VALU 94 % busy,
  * 0.83-0.86 of the rate of its own VALU stream run without memory instructions.
  */
-#include "das_common.h"
-
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef float f32x3 __attribute__((ext_vector_type(3)));
-typedef __attribute__((address_space(3))) f32x3 lds_f32x3;
-
-__device__ __forceinline__ float staged_phase_turns(float k, float index)
-{
-	float p = k * index;
-	float e = __builtin_fmaf(k, index, -p);
-	return hw_fract(p) + e;
-}
-
-/* The block's tile.  depth_major bit 2 (global transmit tables): planes in chunks of 32, so that blocks j and j + 32 of an XCD's
- * sequence -- the two a CU holds (dispatch is breadth first over an XCD's 32 CUs) -- are NEIGHBOURS ALONG u in one plane: they read
- * the same rows of the global transmit table (14.6 KB at 76 transmits: the scalar cache holds 16 KB) and adjacent RF windows.
- * False: no tile (the grid's rounding, the last chunk's padding) -- a whole block. */
-__device__ __forceinline__ bool staged_tile_of(const BfSeparableArgs &q, bool global_tables, uint32_t &tu, uint32_t &tv, uint32_t &zl)
-{
-	const bool paired = global_tables && (q.depth_major & 4u);
-	const uint32_t zchunks = (q.tiles[2] + 31u) >> 5;
-	const uint32_t total = paired ? q.tiles[0] * q.tiles[1] * zchunks * 32u : q.tiles[0] * q.tiles[1] * q.tiles[2];
-	const uint32_t per   = (total + 7u) / 8u;
-	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-	if (tile >= total) return false;
-	if (paired) {                                            /* walk order: das_separable.hip */
-		uint32_t r = tile >> 5;
-		tu = r % q.tiles[0]; r /= q.tiles[0];
-		zl = (r % zchunks) * 32u + (tile & 31u);
-		tv = r / zchunks;
-		return zl < q.tiles[2];
-	}
-	if (q.depth_major & 1u) {
-		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
-	} else {
-		tu = tile % q.tiles[0];
-		tv = (tile / q.tiles[0]) % q.tiles[1];
-		zl = tile / (q.tiles[0] * q.tiles[1]);
-	}
-	return true;
-}
+#include "das_staged_shared.h"
 
 /* LDS (A4 = transmits rounded up to a multiple of 4; transmits are kept in PAIRS so that one read serves two terms):
  *   stage[a*W + j]   = { c_j, d_j }: the line through samples j and j + 1 of window (c, a) in window coordinates
@@ -134,13 +92,7 @@ __device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparabl
 	const uint32_t z  = p.z_first + zl;
 
 	const uint32_t u_axis = q.u_axis, v_axis = 1u - q.u_axis;
-	const float denom[3] = {fmaxf(1.0f, (float)p.size[0] - 1.0f), fmaxf(1.0f, (float)p.size[1] - 1.0f),
-	                        fmaxf(1.0f, (float)p.size[2] - 1.0f)};
-	const float pz = (float)z / denom[2];
-	const float phase_k = p.demodulation_frequency * p.inv_sampling_frequency;
-	const BfTransmit t0 = p.transmits[0];
-	const bool  rx_rows = (t0.flags & BF_RX_ROWS) != 0;
-	[[maybe_unused]] const float rx_pitch = rx_rows ? p.pitch[1] : p.pitch[0];
+	const bool  rx_rows = (p.transmits[0].flags & BF_RX_ROWS) != 0;
 	const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
 	if (q.depth_major & 2u) staged_violation_clear(tid);       /* STAGED_CHECKED: das_common.h */
 
@@ -151,91 +103,30 @@ __device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparabl
 	if constexpr (UNI) {
 		for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads) tfl[a] = reinterpret_cast<const int *>(tile_tab)[a];
 		if (tid == 0) stage[stage_elements] = f32x4{0.f, 0.f, 0.f, 0.f};
-		range = *reinterpret_cast<const f32x2 *>(tile_tab + 4u * (uint32_t)A4);
+		range = staged_uniform_range(*reinterpret_cast<const f32x2 *>(tile_tab + 4u * (uint32_t)A4));
 	} else {
-		/* ---- transmit tables (absolute delays first) */
-		for (uint32_t e = tid; e < (uint32_t)A4 * V; e += nthreads) {
-			uint32_t a = e >> VS, iv = e & (V - 1);
-			float cs_c = 0.f, cs_s = 0.f, t_idx = 0.f;           /* padding transmits: zero phasor, window position 0 */
-			if (a < (uint32_t)A) {
-				float coord[3] = {0.f, 0.f, pz};
-				coord[v_axis] = (float)(tv * V + iv) / denom[v_axis];
-				float wx, wy, wz;
-				m4_point(p.voxel_transform, coord[0], coord[1], coord[2], wx, wy, wz);
-				const BfTransmit t = p.transmits[a];
-				float dist = 0.f;
-				if (!(t.flags & BF_TX_NONE)) {
-					float px = (t.flags & BF_TX_ROWS) ? wy : wx;
-					if (t.flags & BF_TX_PLANE) dist = px * t.sin_a + wz * t.cos_a;
-					else { float ddx = px - t.focus_x, ddz = wz - t.focus_z; dist = hw_sqrt(ddx * ddx + ddz * ddz); }
-				}
-				t_idx = (div_speed_of_sound(dist, p) + p.time_offset) * p.sampling_frequency;
-				float turns = staged_phase_turns(phase_k, t_idx);
-				cs_c = hw_cos_turns(turns); cs_s = hw_sin_turns(turns);
-			}
+		staged_transmit_entries<VS, true>(p, v_axis, tv, z, tid, nthreads, [&](uint32_t a, uint32_t iv, uint32_t, float t_idx, float cs_c, float cs_s) {
 			const uint32_t pair = (a >> 1) * V + iv, half = a & 1u;
 			reinterpret_cast<f32x2 *>(Tcs + pair)[half] = f32x2{cs_c, cs_s};
 			reinterpret_cast<float *>(Tz + pair)[half]  = t_idx;
-		}
+		});
 		if (tid == 0) stage[stage_elements] = f32x4{0.f, 0.f, 0.f, 0.f};
-		/* tile-wide extremes of the absolute transmit delay (range-test shortcut, as das_separable.hip) */
-		__syncthreads();
-		{
-			float lo = __builtin_inff(), hi = -__builtin_inff();
-			for (uint32_t e = tid; e < (uint32_t)A * V; e += nthreads) {
-				uint32_t a = e >> VS, iv = e & (V - 1);
-				float v = reinterpret_cast<const float *>(Tz + (a >> 1) * V + iv)[a & 1u];
-				lo = fminf(lo, v); hi = fmaxf(hi, v);
-			}
-			for (int off = 32; off > 0; off >>= 1) {
-				lo = fminf(lo, __shfl_xor(lo, off, 64));
-				hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-			}
-			if ((tid & 63u) == 0) wave_range[tid >> 6] = f32x2{lo, hi};
-		}
-		__syncthreads();
-		range = wave_range[0];
-		for (uint32_t w = 1; w < (nthreads >> 6); w++) {
-			range.x = fminf(range.x, wave_range[w].x);
-			range.y = fmaxf(range.y, wave_range[w].y);
-		}
-	}
-	/* the same for every lane: keep it in scalar registers.  (Through scalar temporaries: __builtin_bit_cast applied
-	 * directly to a vector component reads the vector's FIRST component with this hipcc -- range.y silently became
-	 * range.x, and waves whose lanes reach the end of the RF row for the tile's largest transmit delay only took the
-	 * unchecked loop; found by the focused-transmit parity case, whose delays differ by hundreds of samples.) */
-	{
-		const float lo = range.x, hi = range.y;
-		range.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lo)));
-		range.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, hi)));
-	}
-	/* per transmit: floor of the smallest delay of its table row; the row becomes window-relative */
-	for (uint32_t a = tid; !UNI && a < (uint32_t)A4; a += nthreads) {
-		float *row = reinterpret_cast<float *>(Tz + (size_t)(a >> 1) * V) + (a & 1u);
-		float  m   = row[0];
-		#pragma unroll 4
-		for (uint32_t iv = 1; iv < V; iv++) m = fminf(m, row[2 * iv]);
-		float fl = __builtin_floorf(m);
-		#pragma unroll 4
-		for (uint32_t iv = 0; iv < V; iv++) row[2 * iv] = (row[2 * iv] - fl) - 0.5f;      /* both steps exact */
-		tfl[a] = (int)fl;
+		range = rca_tile_range((uint32_t)A * V, wave_range, [&](uint32_t e) {
+			uint32_t a = e >> VS, iv = e & (V - 1);
+			return reinterpret_cast<const float *>(Tz + (a >> 1) * V + iv)[a & 1u];
+		});
+		for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads)
+			tfl[a] = staged_window_row<V, 2, 0>(reinterpret_cast<float *>(Tz + (size_t)(a >> 1) * V) + (a & 1u));
 	}
 	__syncthreads();                                         /* the floors are read below */
 
 	/* the lane's voxel: needed for `inside` here and for the store at the very end -- recomputed there rather than held in two
 	 * vector registers across the channel loop (the NL = 4 instances had none to spare) */
-	auto voxel_of = [&](uint32_t thread, uint32_t &vx, uint32_t &vy, uint32_t &lane_u) {
-		uint32_t lv_;
-		if (u_axis == 0) { lane_u = thread & (U - 1); lv_ = thread >> q.u_shift; }
-		else             { lv_ = thread & (V - 1); lane_u = thread >> VS; }
-		const uint32_t gu = tu * U + lane_u, gv = tv * V + lv_;
-		vx = u_axis == 0 ? gu : gv; vy = u_axis == 0 ? gv : gu;
-	};
 	uint32_t lu;
 	bool inside;
 	{
-		uint32_t x0, y0;
-		voxel_of(tid, x0, y0, lu);
+		uint32_t x0, y0, lv_unused;
+		rca_voxel_of(tid, u_axis, U, q.u_shift, V, VS, tu, tv, x0, y0, lu, lv_unused);
 		inside = x0 < p.size[0] && y0 < p.size[1];
 	}
 
@@ -250,33 +141,11 @@ __device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparabl
 	 * to every address of the inner loop instead of once here */
 	asm("" : "+s"(tcs_base), "+s"(tz_base));
 
-	/* Staging.  Thread tid copies element j = tid % W of windows a_n = tid / W + n * (threads / W), n < NL:
-	 * sample rfl + floor(tmin_a) + j of row (channel, a).  The loads are buffer loads over the whole DAS
-	 * input: an offset outside it (a window that starts before the first row or ends behind the last)
-	 * returns zero instead of faulting, and samples a window holds from a NEIGHBOURING row are never
-	 * consumed -- a term is only evaluated (unchecked loop) or only kept (checked loop) when both of
-	 * its taps lie inside its own row.  Per thread and n one loop-invariant byte offset; per channel one add. */
-	const __amdgpu_buffer_rsrc_t rf_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-		const_cast<void *>(p.rf), 0, (int)((uint32_t)C * (uint32_t)A * (uint32_t)S * 8u), 0x00020000);
+	/* staging (das_staged_shared.h): 8-byte samples, windows that start at the two floors */
+	const __amdgpu_buffer_rsrc_t rf_rsrc = staged_rf_resource<f32x2>(p);
 	uint32_t stage_inv[NL];
-	{
-		const uint32_t windows_per_pass = nthreads >> WS;
-		#pragma unroll
-		for (int n = 0; n < NL; n++) {
-			uint32_t a = (tid >> WS) + (uint32_t)n * windows_per_pass;
-			/* transmits of the padding (a >= A) point far outside the buffer: they stage zeros */
-			stage_inv[n] = a < (uint32_t)A ? (a * (uint32_t)S + (uint32_t)(tfl[a] + (int)(tid & (W - 1)))) * 8u : 0x80000000u;
-		}
-	}
-	auto stage_load = [&](int channel, int rfl, f32x2 (&regs)[NL]) {
-		const uint32_t at = ((uint32_t)channel * (uint32_t)A * (uint32_t)S + (uint32_t)rfl) * 8u;
-		#pragma unroll
-		for (int n = 0; n < NL; n++) {
-			/* (the padding's 0x80000000 + at stays out of range: the host refuses inputs of 2 GiB and more here) */
-			i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rf_rsrc, (int)(stage_inv[n] + at), 0, 0);
-			regs[n] = __builtin_bit_cast(f32x2, v);
-		}
-	};
+	staged_stage_offsets<f32x2, WS, 0>(stage_inv, tfl, A, S, tid, nthreads);
+	auto stage_load = [&](int channel, int rfl, f32x2 (&regs)[NL]) { staged_stage_load(rf_rsrc, stage_inv, channel, A, S, rfl, regs); };
 	/* Element j keeps the LINE through samples j and j + 1 in window coordinates, {c_j, d_j} with d_j = s_(j+1) - s_j and
 	 * c_j = s_j + (1/2 - j) d_j, so that the interpolated sample at position p (measured from half a sample into the window,
 	 * as the tables hold it) is c_j + p d_j for j = round(p): one packed fma of the position itself, no fraction needed.
@@ -297,71 +166,10 @@ __device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparabl
 		}
 	};
 
-	/* The receive table is rebuilt once per chunk of channels from ~50 scalars of the launch arguments (two 4 x 4 transforms, pitch,
-	 * f-number, speed of sound, ...).  Held in SGPRs across the channel loop they cost this kernel 140 scalar spills (v_writelane /
-	 * v_readlane into two of its 64 VGPRs, which in turn pushed 5 vector registers to scratch: 3.4 GiB written per 1 GiB frame).  They are
-	 * read from the kernel-argument segment instead, through a pointer the compiler cannot see through, at the top of every chunk: a
-	 * few s_load per 16 channels, dead again before the channel loop. */
-	typedef __attribute__((address_space(4))) const BfDasArgs const_args;
-	const_args *kernel_args = (const_args *)__builtin_amdgcn_kernarg_segment_ptr();
-	static_assert(__builtin_offsetof(BfDasArgs, xdc_transform) == 0, "BfDasArgs is the kernel's first argument: it sits at offset 0 of the segment");
 	for (int c0 = 0; c0 < C; c0 += chunk) {
 		const int cn = (C - c0) < chunk ? (C - c0) : chunk;
 		__syncthreads();        /* readers of the previous chunk's R / stage are done; the transmit tables are complete */
-		{
-		const_args *ka = kernel_args;
-		asm volatile("" : "+s"(ka));
-		const uint32_t k_size[3] = {ka->size[0], ka->size[1], ka->size[2]};
-		const float k_denom_u = fmaxf(1.0f, (float)k_size[u_axis] - 1.0f);
-		const float k_pz = (float)z / fmaxf(1.0f, (float)k_size[2] - 1.0f);
-		const float k_fs = ka->sampling_frequency, k_inv_c = ka->inv_speed_of_sound, k_c = ka->speed_of_sound, k_fnum = ka->f_number;
-		const float k_phase = ka->demodulation_frequency * ka->inv_sampling_frequency;
-		const float k_pitch = rx_rows ? ka->pitch[1] : ka->pitch[0];
-		for (uint32_t e = tid; e < (uint32_t)cn * U; e += nthreads) {
-			uint32_t c = (uint32_t)c0 + (e >> q.u_shift), iu = e & (U - 1);
-			float coord[3] = {0.f, 0.f, k_pz};
-			coord[u_axis] = (float)(tu * U + iu) / k_denom_u;
-			float wx, wy, wz, xx, xy, xz;
-			m4_point(ka->voxel_transform, coord[0], coord[1], coord[2], wx, wy, wz);
-			m4_point(ka->xdc_transform, wx, wy, wz, xx, xy, xz);
-			float lateral = rx_rows ? xy : xx;
-			float dx      = lateral - (float)c * k_pitch;
-			float a_arg   = __builtin_fabsf(dx * (k_fnum * hw_rcp(__builtin_fabsf(xz))));
-			/* the delay is kept for lanes outside the aperture too: it keeps their (discarded)
-			 * LDS reads inside the window */
-			float r_idx = div_speed_of_sound(hw_sqrt(dx * dx + xz * xz), k_inv_c, k_c) * k_fs;
-			f32x4 entry = {r_idx, 0.f, 0.f, 0.f};
-			if (a_arg < 0.5f) {
-				float cs    = hw_cos_turns(0.5f * a_arg);
-				float apod  = cs * cs;
-				float turns = staged_phase_turns(k_phase, r_idx);
-				entry.y = apod * hw_cos_turns(turns);
-				entry.z = apod * hw_sin_turns(turns);
-				entry.w = apod;
-			}
-			R[e] = entry;
-		}
-		}
-		__syncthreads();
-		for (uint32_t cl = tid; cl < (uint32_t)cn; cl += nthreads) {
-			const float *row = reinterpret_cast<const float *>(R + (size_t)cl * U);
-			float m = row[0];
-			#pragma unroll 4
-			for (uint32_t iu = 1; iu < U; iu++) m = fminf(m, row[4 * iu]);
-			rfloor[cl] = (int)__builtin_floorf(m);
-		}
-		__syncthreads();
-		/* the entries become what the channel loop consumes with no arithmetic: the delay relative to the channel's window
-		 * (exact) and, in the SIGN of the weight, whether the lane can leave the RF row for some transmit of the tile
-		 * (r + min T < 0 or r + max T >= S - 1: such a wave runs the checked loop) */
-		for (uint32_t e = tid; e < (uint32_t)cn * U; e += nthreads) {
-			f32x4 entry = R[e];
-			const bool lane_safe = (entry.x + range.x >= 0.f) && (entry.x + range.y < (float)(S - 1));
-			entry.x -= (float)rfloor[e >> q.u_shift];
-			if (!lane_safe) entry.w = -entry.w;          /* -0.0f for a lane outside the aperture: still "unsafe" to the sign test */
-			R[e] = entry;
-		}
-		__syncthreads();
+		staged_receive_table<f32x4, 0>(R, rfloor, c0, cn, tu, z, u_axis, q.u_shift, rx_rows, range, S, tid, nthreads);
 
 		f32x2 regs[NL];
 		stage_load(c0, rfloor[0], regs);
@@ -478,12 +286,10 @@ __device__ __forceinline__ void staged_body(const BfDasArgs &p, const BfSeparabl
 	if (q.depth_major & 2u) staged_violation_report(tid);      /* (block uniform: every thread reaches it) */
 	if (!inside) return;
 
-	uint32_t x, y, lane_u_unused, thread = tid;
+	uint32_t x, y, lu_unused, lv_unused, thread = tid;
 	asm volatile("" : "+v"(thread));                      /* not the values computed before the loop */
-	voxel_of(thread, x, y, lane_u_unused);
-	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<f32x2 *>(p.out)[out_index] = coherent;
+	rca_voxel_of(thread, u_axis, U, q.u_shift, V, VS, tu, tv, x, y, lu_unused, lv_unused);
+	rca_store_voxel<CW>(p, zl, x, y, coherent, incoherent);
 }
 
 /* ---- the channel-paired form (q.uniform = 2): 32 x 32 tiles, 32-sample windows, 1024 threads -- the shape of config 4, whose delay
@@ -536,7 +342,7 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 	if (tid == 0) stage[(size_t)G0 * B] = f32x4{0.f, 0.f, 0.f, 0.f};
 	f32x2 range = *reinterpret_cast<const f32x2 *>(tile_tab + 4u * A4);
 	{
-		const float lo = range.x, hi = range.y;              /* (scalar temporaries: see staged_body) */
+		const float lo = range.x, hi = range.y;              /* (scalar temporaries: see staged_uniform_range, das_staged_shared.h) */
 		range.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lo)));
 		range.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, hi)));
 	}
@@ -633,7 +439,7 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 		const int cn2 = (cn + 1) & ~1;                       /* rows of the receive table: an odd last channel gets a zero partner */
 		__syncthreads();        /* readers of the previous chunk's R / stage are done; tfl is complete */
 		{
-		const_args *ka = kernel_args;                        /* (through the kernel-argument segment: see staged_body) */
+		const_args *ka = kernel_args;                        /* (through the kernel-argument segment: see staged_receive_table, das_staged_shared.h) */
 		asm volatile("" : "+s"(ka));
 		const uint32_t k_size[3] = {ka->size[0], ka->size[1], ka->size[2]};
 		const float k_denom_u = fmaxf(1.0f, (float)k_size[u_axis] - 1.0f);
@@ -661,7 +467,7 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 				if (a_arg < 0.5f) {
 					float cs    = hw_cos_turns(0.5f * a_arg);
 					float apod  = cs * cs;
-					float turns = staged_phase_turns(k_phase, r_idx);
+					float turns = phase_turns(k_phase, r_idx);
 					entry.y = apod * hw_cos_turns(turns);
 					entry.z = apod * hw_sin_turns(turns);
 					entry.w = apod;
@@ -866,49 +672,12 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_kernel(const BfDasArgs
 	else                  staged_body<CW, VS, WS, NL, UNI>(p, q);
 }
 
-template <bool CW, int VS, int WS, int NL, bool UNI>
-static hipError_t launch_staged(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	uint32_t total = q->tiles[0] * q->tiles[1] * q->tiles[2];
-	if (UNI && (q->depth_major & 4u)) total = q->tiles[0] * q->tiles[1] * ((q->tiles[2] + 31u) >> 5) * 32u;   /* the paired walk pads the planes to chunks of 32 */
-	uint32_t grid  = ((total + 7u) / 8u) * 8u;
-	auto kernel = das_rca_staged_kernel<CW, VS, WS, NL, UNI, false>;
-	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(q->threads), q->lds_bytes, s, *a, *q);
-	return hipGetLastError();
-}
-
-template <bool CW, int VS, int WS, bool UNI>
-static hipError_t launch_staged_loads(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	const uint32_t A4 = ((uint32_t)a->acquisition_count + 3u) & ~3u;
-	/* passes a thread stages per channel: whole windows per wave */
-	const uint32_t passes = ((A4 << WS) + q->threads - 1) / q->threads;
-	switch (passes) {
-	case 1: return launch_staged<CW, VS, WS, 1, UNI>(a, q, s);
-	case 2: return launch_staged<CW, VS, WS, 2, UNI>(a, q, s);
-	case 3: return launch_staged<CW, VS, WS, 3, UNI>(a, q, s);
-	case 4: return launch_staged<CW, VS, WS, 4, UNI>(a, q, s);
-	}
-	return hipErrorInvalidValue;
-}
-
-template <bool CW, int NL>
-static hipError_t launch_staged_paired(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	const uint32_t total = q->tiles[0] * q->tiles[1] * ((q->depth_major & 4u) ? ((q->tiles[2] + 31u) >> 5) * 32u : q->tiles[2]);
-	const uint32_t grid  = ((total + 7u) / 8u) * 8u;
-	auto kernel = das_rca_staged_kernel<CW, 5, 5, NL, true, true>;
-	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), q->lds_bytes, s, *a, *q);
-	return hipGetLastError();
-}
-
 template <bool CW>
 static hipError_t launch_staged_shape(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
+	/* the paired walk (depth_major bit 2, global tables only) pads the planes to chunks of 32 */
+	const uint32_t tiles = q->tiles[0] * q->tiles[1] * q->tiles[2];
+	const uint32_t tiles_padded = (q->depth_major & 4u) ? q->tiles[0] * q->tiles[1] * ((q->tiles[2] + 31u) >> 5) * 32u : tiles;
 	if (q->uniform == 2) {
 		/* the channel-paired form: 32 x 32 tiles, 32-sample windows, 1024 threads, an even chunk of channels (or all of them) */
 		if (q->u_shift != 5 || q->v_shift != 5 || q->window_samples != 32 || q->threads != 1024 || !q->tables ||
@@ -917,28 +686,31 @@ static hipError_t launch_staged_shape(const BfDasArgs *a, const BfSeparableArgs 
 		uint32_t G0, G1;
 		if (!bf_staged_paired_split(A4, q->channel_chunk, &G0, &G1) || q->lds_bytes < bf_staged_paired_lds_bytes(G0, q->channel_chunk, A4)) return hipErrorInvalidValue;
 		switch (bf_staged_paired_passes(G0)) {               /* staging passes of the larger group; the other one's are bounded in the kernel */
-		case 2: return launch_staged_paired<CW, 2>(a, q, s);
-		case 3: return launch_staged_paired<CW, 3>(a, q, s);
-		case 4: return launch_staged_paired<CW, 4>(a, q, s);
+		case 2: return rca_launch_tiles(das_rca_staged_kernel<CW, 5, 5, 2, true, true>, tiles_padded, 1024u, a, q, s);
+		case 3: return rca_launch_tiles(das_rca_staged_kernel<CW, 5, 5, 3, true, true>, tiles_padded, 1024u, a, q, s);
+		case 4: return rca_launch_tiles(das_rca_staged_kernel<CW, 5, 5, 4, true, true>, tiles_padded, 1024u, a, q, s);
 		}
 		return hipErrorInvalidValue;
 	}
 	if (q->uniform) {
 		/* wave-uniform transmit tables: a 64 x 16 tile with x along the receive axis, 1024 threads, tables written by bf_launch_das_staged_tables */
 		if (q->u_axis != 0 || q->u_shift != 6 || q->v_shift != 4 || q->threads != 1024 || !q->tables) return hipErrorInvalidValue;
-		if (q->window_samples == 32) return launch_staged_loads<CW, 4, 5, true>(a, q, s);
-		if (q->window_samples == 64) return launch_staged_loads<CW, 4, 6, true>(a, q, s);
+		auto loads = [&](auto ws) {
+			constexpr int WS = decltype(ws)::value;
+			return staged_for_passes(staged_passes(a, q, WS), [&](auto nl) {
+				return rca_launch_tiles(das_rca_staged_kernel<CW, 4, WS, decltype(nl)::value, true, false>, tiles_padded, q->threads, a, q, s);
+			});
+		};
+		if (q->window_samples == 32) return loads(std::integral_constant<int, 5>{});
+		if (q->window_samples == 64) return loads(std::integral_constant<int, 6>{});
 		return hipErrorInvalidValue;
 	}
-	switch ((q->v_shift << 4) | q->window_shift) {
-	case (4 << 4) | 5: return launch_staged_loads<CW, 4, 5, false>(a, q, s);
-	case (5 << 4) | 5: return launch_staged_loads<CW, 5, 5, false>(a, q, s);
-	case (6 << 4) | 5: return launch_staged_loads<CW, 6, 5, false>(a, q, s);
-	case (4 << 4) | 6: return launch_staged_loads<CW, 4, 6, false>(a, q, s);
-	case (5 << 4) | 6: return launch_staged_loads<CW, 5, 6, false>(a, q, s);
-	case (6 << 4) | 6: return launch_staged_loads<CW, 6, 6, false>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	return staged_for_shape(q, [&](auto vs, auto ws) {
+		constexpr int VS = decltype(vs)::value, WS = decltype(ws)::value;
+		return staged_for_passes(staged_passes(a, q, WS), [&](auto nl) {
+			return rca_launch_tiles(das_rca_staged_kernel<CW, VS, WS, decltype(nl)::value, false, false>, tiles, q->threads, a, q, s);
+		});
+	});
 }
 
 /* complex samples, linear interpolation only; the caller checked q->window_shift */
@@ -950,7 +722,7 @@ extern "C" hipError_t bf_launch_das_staged(const BfDasArgs *a, const BfSeparable
 	return a->coherency_weighting ? launch_staged_shape<true>(a, q, s) : launch_staged_shape<false>(a, q, s);
 }
 
-/* ---- the transmit tables of the UNI variant, once per frame: one block per (lateral tile row tv, plane zl), the arithmetic of the
+/* ---- the transmit tables of the UNI variant, once per frame: one block per (lateral tile row tv, plane zl), the calls of the
  * kernel's own table build (same functions, same order: the entries are bit-identical to what a block would compute in LDS).
  * Layout per tile slice of q.table_stride bytes: int floor(tmin_a)[A4] | {lo, hi} of the absolute delays + 8 bytes of padding |
  * per lateral row iv < 16 and batch b < A4 / 4: {T'' of transmits 4b .. 4b + 3}, {cos, sin} of 4b, 4b + 1, {cos, sin} of 4b + 2, 4b + 3. */
@@ -965,62 +737,14 @@ __global__ __launch_bounds__(256) void staged_tables_kernel(const BfDasArgs p, c
 	f32x2 *cs = reinterpret_cast<f32x2 *>(t + (size_t)A4 * V);          /* [A4][V] */
 	f32x2 *wave_range = cs + (size_t)A4 * V;                            /* [4] */
 	const uint32_t tv = blockIdx.x % q.tiles[1], zl = blockIdx.x / q.tiles[1];
-	const uint32_t z  = p.z_first + zl;
-	const uint32_t v_axis = 1u - q.u_axis;
-	const float denom[3] = {fmaxf(1.0f, (float)p.size[0] - 1.0f), fmaxf(1.0f, (float)p.size[1] - 1.0f),
-	                        fmaxf(1.0f, (float)p.size[2] - 1.0f)};
-	const float pz = (float)z / denom[2];
-	const float phase_k = p.demodulation_frequency * p.inv_sampling_frequency;
 	const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
-	for (uint32_t e = tid; e < (uint32_t)A4 * V; e += nthreads) {
-		uint32_t a = e >> VS, iv = e & (V - 1);
-		float cs_c = 0.f, cs_s = 0.f, t_idx = 0.f;
-		if (a < (uint32_t)A) {
-			float coord[3] = {0.f, 0.f, pz};
-			coord[v_axis] = (float)(tv * V + iv) / denom[v_axis];
-			float wx, wy, wz;
-			m4_point(p.voxel_transform, coord[0], coord[1], coord[2], wx, wy, wz);
-			const BfTransmit t_a = p.transmits[a];
-			float dist = 0.f;
-			if (!(t_a.flags & BF_TX_NONE)) {
-				float px = (t_a.flags & BF_TX_ROWS) ? wy : wx;
-				if (t_a.flags & BF_TX_PLANE) dist = px * t_a.sin_a + wz * t_a.cos_a;
-				else { float ddx = px - t_a.focus_x, ddz = wz - t_a.focus_z; dist = hw_sqrt(ddx * ddx + ddz * ddz); }
-			}
-			t_idx = (div_speed_of_sound(dist, p) + p.time_offset) * p.sampling_frequency;
-			float turns = staged_phase_turns(phase_k, t_idx);
-			cs_c = hw_cos_turns(turns); cs_s = hw_sin_turns(turns);
-		}
+	staged_transmit_entries<VS, true>(p, 1u - q.u_axis, tv, p.z_first + zl, tid, nthreads, [&](uint32_t, uint32_t, uint32_t e, float t_idx, float cs_c, float cs_s) {
 		t[e] = t_idx; cs[e] = f32x2{cs_c, cs_s};
-	}
-	__syncthreads();
-	{
-		float lo = __builtin_inff(), hi = -__builtin_inff();
-		for (uint32_t e = tid; e < (uint32_t)A * V; e += nthreads) { lo = fminf(lo, t[e]); hi = fmaxf(hi, t[e]); }
-		for (int off = 32; off > 0; off >>= 1) {
-			lo = fminf(lo, __shfl_xor(lo, off, 64));
-			hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-		}
-		if ((tid & 63u) == 0) wave_range[tid >> 6] = f32x2{lo, hi};
-	}
-	__syncthreads();
+	});
+	const f32x2 range = rca_tile_range((uint32_t)A * V, wave_range, [&](uint32_t e) { return t[e]; });
 	unsigned char *tile_tab = reinterpret_cast<unsigned char *>(q.tables) + (size_t)blockIdx.x * q.table_stride;
-	if (tid == 0) {
-		f32x2 range = wave_range[0];
-		for (uint32_t w = 1; w < (nthreads >> 6); w++) {
-			range.x = fminf(range.x, wave_range[w].x);
-			range.y = fmaxf(range.y, wave_range[w].y);
-		}
-		*reinterpret_cast<f32x4 *>(tile_tab + 4u * (uint32_t)A4) = f32x4{range.x, range.y, 0.f, 0.f};
-	}
-	for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads) {
-		float *row = t + (size_t)a * V;
-		float  m   = row[0];
-		for (uint32_t iv = 1; iv < V; iv++) m = fminf(m, row[iv]);
-		float fl = __builtin_floorf(m);
-		for (uint32_t iv = 0; iv < V; iv++) row[iv] = (row[iv] - fl) - 0.5f;      /* both steps exact */
-		reinterpret_cast<int *>(tile_tab)[a] = (int)fl;
-	}
+	if (tid == 0) *reinterpret_cast<f32x4 *>(tile_tab + 4u * (uint32_t)A4) = f32x4{range.x, range.y, 0.f, 0.f};
+	for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads) reinterpret_cast<int *>(tile_tab)[a] = staged_window_row<V, 1, 0>(t + (size_t)a * V);
 	__syncthreads();
 	f32x4 *rows = reinterpret_cast<f32x4 *>(tile_tab + 4u * (uint32_t)A4 + 16u);
 	if constexpr (VS == 5) {

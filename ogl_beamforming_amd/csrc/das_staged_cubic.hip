@@ -16,20 +16,7 @@
  *     (samples j - 1, j + 1, j + 2) come from its neighbour lanes by one-lane wave shifts.
  * 78 KB of windows per block at 76 transmits: one 1024-thread block per CU, 128 VGPRs per lane.
  */
-#include "das_common.h"
-
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef float f32x3 __attribute__((ext_vector_type(3)));
-typedef __attribute__((address_space(3))) f32x3 lds_f32x3;
-
-__device__ __forceinline__ float cubic_phase_turns(float k, float index)
-{
-	float p = k * index;
-	float e = __builtin_fmaf(k, index, -p);
-	return hw_fract(p) + e;
-}
+#include "das_staged_shared.h"
 
 /* LDS (A4 = transmits rounded up to a multiple of 4; transmits in PAIRS):
  *   stage[a*W + j]   = { b0, b1, b2, b3 }: the Catmull-Rom segment between window samples j and j + 1 of window (c, a) as a
@@ -37,6 +24,11 @@ __device__ __forceinline__ float cubic_phase_turns(float k, float index)
  *                      valid for 1 <= j <= W - 3; two unused elements in front, one zero element behind      2 x f32x4
  *   Tcs, R, Tz, tfl, rfloor, wave_range: as das_staged.hip (Tz holds T'' = t_index - floor(tmin_a) + 1/2) */
 /* NL: window elements a thread stages per channel, ceil(A4 * W / threads) */
+/* The tile set-up below is das_staged_shared.h's, operation for operation (block id -> tile, rca_transmit_index with the phasor,
+ * rca_tile_range, staged_receive_table and the staging with LEAD = 1), written out: built from those calls the kernel computed the
+ * same frames bit for bit and its inner loops came out instruction for instruction the same, but config 4 with cubic interpolation
+ * ran 1299.1 against 1294.1 ms per frame (five alternating runs a side, spreads 0.5-0.6 ms) -- over the bar, so the text stays here
+ * and every instantiation disassembles to what it was.  A change to the shared arithmetic is a change to this text too. */
 template <bool CW, int VS, int WS, int NL>
 __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfDasArgs p, const BfSeparableArgs q)
 {
@@ -61,7 +53,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 	const uint32_t per   = (total + 7u) / 8u;
 	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
 	if (tile >= total) return;                               /* whole block */
-	uint32_t tu, tv, zl;                                     /* walk order: das_separable.hip */
+	uint32_t tu, tv, zl;                                     /* walk order: staged_tile_of */
 	if (q.depth_major & 1u) {
 		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
 	} else {
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 	/* ---- transmit tables (absolute delays first) */
 	for (uint32_t e = tid; e < (uint32_t)A4 * V; e += nthreads) {
 		uint32_t a = e >> VS, iv = e & (V - 1);
-		float cs_c = 0.f, cs_s = 0.f, t_idx = 0.f;           /* padding transmits: zero phasor, window position 0 */
+		float cs_c = 0.f, cs_s = 0.f, t_idx = 0.f;
 		if (a < (uint32_t)A) {
 			float coord[3] = {0.f, 0.f, pz};
 			coord[v_axis] = (float)(tv * V + iv) / denom[v_axis];
@@ -99,7 +91,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 				else { float ddx = px - t.focus_x, ddz = wz - t.focus_z; dist = hw_sqrt(ddx * ddx + ddz * ddz); }
 			}
 			t_idx = (div_speed_of_sound(dist, p) + p.time_offset) * p.sampling_frequency;
-			float turns = cubic_phase_turns(phase_k, t_idx);
+			float turns = phase_turns(phase_k, t_idx);
 			cs_c = hw_cos_turns(turns); cs_s = hw_sin_turns(turns);
 		}
 		const uint32_t pair = (a >> 1) * V + iv, half = a & 1u;
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 		reinterpret_cast<float *>(Tz + pair)[half]  = t_idx;
 	}
 	if (tid < 2) stage[2 * stage_elements + tid] = f32x4{0.f, 0.f, 0.f, 0.f};
-	/* tile-wide extremes of the absolute transmit delay (range-test shortcut, as das_separable.hip) */
+	/* tile-wide extremes of the absolute transmit delay: rca_tile_range */
 	__syncthreads();
 	{
 		float lo = __builtin_inff(), hi = -__builtin_inff();
@@ -128,26 +120,14 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 		range.x = fminf(range.x, wave_range[w].x);
 		range.y = fmaxf(range.y, wave_range[w].y);
 	}
-	/* the same for every lane: keep it in scalar registers.  (Through scalar temporaries: __builtin_bit_cast applied
-	 * directly to a vector component reads the vector's FIRST component with this hipcc -- range.y silently became
-	 * range.x, and waves whose lanes reach the end of the RF row for the tile's largest transmit delay only took the
-	 * unchecked loop; found by the focused-transmit parity case, whose delays differ by hundreds of samples.) */
+	/* the same for every lane: in scalar registers, through scalar temporaries (staged_uniform_range, das_staged_shared.h, says why) */
 	{
 		const float lo = range.x, hi = range.y;
 		range.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lo)));
 		range.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, hi)));
 	}
-	/* per transmit: floor of the smallest delay of its table row; the row becomes window-relative */
-	for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads) {
-		float *row = reinterpret_cast<float *>(Tz + (size_t)(a >> 1) * V) + (a & 1u);
-		float  m   = row[0];
-		#pragma unroll 4
-		for (uint32_t iv = 1; iv < V; iv++) m = fminf(m, row[2 * iv]);
-		float fl = __builtin_floorf(m);
-		#pragma unroll 4
-		for (uint32_t iv = 0; iv < V; iv++) row[2 * iv] = (row[2 * iv] - fl) + 0.5f;      /* both steps exact */
-		tfl[a] = (int)fl;
-	}
+	for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads)
+		tfl[a] = staged_window_row<V, 2, 1>(reinterpret_cast<float *>(Tz + (size_t)(a >> 1) * V) + (a & 1u));
 	__syncthreads();                                         /* the floors are read below */
 
 	uint32_t lu, lv;
@@ -167,12 +147,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 	 * to every address of the inner loop instead of once here */
 	asm("" : "+s"(tcs_base), "+s"(tz_base));
 
-	/* Staging.  Thread tid copies element j = tid % W of windows a_n = tid / W + n * (threads / W), n < NL:
-	 * sample rfl + floor(tmin_a) + j of row (channel, a).  The loads are buffer loads over the whole DAS
-	 * input: an offset outside it (a window that starts before the first row or ends behind the last)
-	 * returns zero instead of faulting, and samples a window holds from a NEIGHBOURING row are never
-	 * consumed -- a term is only evaluated (unchecked loop) or only kept (checked loop) when both of
-	 * its taps lie inside its own row.  Per thread and n one loop-invariant byte offset; per channel one add. */
+	/* staging as staged_stage_offsets / staged_stage_load (das_staged_shared.h) with LEAD = 1: the window starts one sample early */
 	const __amdgpu_buffer_rsrc_t rf_rsrc = __builtin_amdgcn_make_buffer_rsrc(
 		const_cast<void *>(p.rf), 0, (int)((uint32_t)C * (uint32_t)A * (uint32_t)S * 8u), 0x00020000);
 	const uint32_t windows_per_pass = nthreads >> WS;
@@ -180,14 +155,12 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 	#pragma unroll
 	for (int n = 0; n < NL; n++) {
 		uint32_t a = (tid >> WS) + (uint32_t)n * windows_per_pass;
-		/* transmits of the padding (a >= A) point far outside the buffer: they stage zeros */
 		stage_inv[n] = a < (uint32_t)A ? (a * (uint32_t)S + (uint32_t)(tfl[a] - 1 + (int)(tid & (W - 1)))) * 8u : 0x80000000u;
 	}
 	auto stage_load = [&](int channel, int rfl, f32x2 (&regs)[NL]) {
 		const uint32_t at = ((uint32_t)channel * (uint32_t)A * (uint32_t)S + (uint32_t)rfl) * 8u;
 		#pragma unroll
 		for (int n = 0; n < NL; n++) {
-			/* (the padding's 0x80000000 + at stays out of range: the host refuses inputs of 2 GiB and more here) */
 			i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rf_rsrc, (int)(stage_inv[n] + at), 0, 0);
 			regs[n] = __builtin_bit_cast(f32x2, v);
 		}
@@ -226,8 +199,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 		const int cn = (C - c0) < chunk ? (C - c0) : chunk;
 		__syncthreads();        /* readers of the previous chunk's R / stage are done; the transmit tables are complete */
 		{
-		/* the ~45 scalars of the receive-table build come from the kernel-argument segment at the top of every chunk instead of
-		 * living in SGPRs across the channel loop (das_staged.hip) */
+		/* the receive table of the chunk, through the kernel-argument segment: staged_receive_table (das_staged_shared.h) says why */
 		typedef __attribute__((address_space(4))) const BfDasArgs const_args;
 		const_args *ka = (const_args *)__builtin_amdgcn_kernarg_segment_ptr();
 		asm volatile("" : "+s"(ka));
@@ -246,14 +218,12 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 			float lateral = rx_rows ? xy : xx;
 			float dx      = lateral - (float)c * k_pitch;
 			float a_arg   = __builtin_fabsf(dx * (k_fnum * hw_rcp(__builtin_fabsf(xz))));
-			/* the delay is kept for lanes outside the aperture too: it keeps their (discarded)
-			 * LDS reads inside the window */
 			float r_idx = div_speed_of_sound(hw_sqrt(dx * dx + xz * xz), k_inv_c, k_c) * k_fs;
 			f32x4 entry = {r_idx, 0.f, 0.f, 0.f};
 			if (a_arg < 0.5f) {
 				float cs    = hw_cos_turns(0.5f * a_arg);
 				float apod  = cs * cs;
-				float turns = cubic_phase_turns(k_phase, r_idx);
+				float turns = phase_turns(k_phase, r_idx);
 				entry.y = apod * hw_cos_turns(turns);
 				entry.z = apod * hw_sin_turns(turns);
 				entry.w = apod;
@@ -270,14 +240,12 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 			rfloor[cl] = (int)__builtin_floorf(m);
 		}
 		__syncthreads();
-		/* the entries become what the channel loop consumes with no arithmetic: the delay relative to the channel's window
-		 * (exact) and, in the SIGN of the weight, whether the lane can leave the RF row for some transmit of the tile
-		 * (r + min T < 0 or r + max T >= S - 1: such a wave runs the checked loop) */
+		/* window-relative delay, the range flag in the sign of the weight: staged_receive_table with LEAD = 1 */
 		for (uint32_t e = tid; e < (uint32_t)cn * U; e += nthreads) {
 			f32x4 entry = R[e];
 			const bool lane_safe = (entry.x + range.x >= 1.f) && (entry.x + range.y < (float)(S - 2));      /* das.glsl: 1 <= index < S - 2 */
 			entry.x -= (float)rfloor[e >> q.u_shift];
-			if (!lane_safe) entry.w = -entry.w;          /* -0.0f for a lane outside the aperture: still "unsafe" to the sign test */
+			if (!lane_safe) entry.w = -entry.w;
 			R[e] = entry;
 		}
 		__syncthreads();
@@ -375,50 +343,19 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 	if (q.depth_major & 2u) staged_violation_report(tid);      /* (block uniform: every thread reaches it) */
 	if (!inside) return;
 
-	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<f32x2 *>(p.out)[out_index] = coherent;
-}
-
-template <bool CW, int VS, int WS, int NL>
-static hipError_t launch_cubic(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	uint32_t total = q->tiles[0] * q->tiles[1] * q->tiles[2];
-	uint32_t grid  = ((total + 7u) / 8u) * 8u;
-	auto kernel = das_rca_staged_cubic_kernel<CW, VS, WS, NL>;
-	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(q->threads), q->lds_bytes, s, *a, *q);
-	return hipGetLastError();
-}
-
-template <bool CW, int VS, int WS>
-static hipError_t launch_cubic_loads(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	const uint32_t A4 = ((uint32_t)a->acquisition_count + 3u) & ~3u;
-	switch (((A4 << WS) + q->threads - 1) / q->threads) {
-	case 1: return launch_cubic<CW, VS, WS, 1>(a, q, s);
-	case 2: return launch_cubic<CW, VS, WS, 2>(a, q, s);
-	case 3: return launch_cubic<CW, VS, WS, 3>(a, q, s);
-	case 4: return launch_cubic<CW, VS, WS, 4>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	rca_store_voxel<CW>(p, zl, x, y, coherent, incoherent);
 }
 
 template <bool CW>
 static hipError_t launch_cubic_shape(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
-	switch ((q->v_shift << 4) | q->window_shift) {
-	case (4 << 4) | 5: return launch_cubic_loads<CW, 4, 5>(a, q, s);
-	case (5 << 4) | 5: return launch_cubic_loads<CW, 5, 5>(a, q, s);
-	case (6 << 4) | 5: return launch_cubic_loads<CW, 6, 5>(a, q, s);
-	case (4 << 4) | 6: return launch_cubic_loads<CW, 4, 6>(a, q, s);
-	case (5 << 4) | 6: return launch_cubic_loads<CW, 5, 6>(a, q, s);
-	case (6 << 4) | 6: return launch_cubic_loads<CW, 6, 6>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	return staged_for_shape(q, [&](auto vs, auto ws) {
+		constexpr int VS = decltype(vs)::value, WS = decltype(ws)::value;
+		return staged_for_passes(staged_passes(a, q, WS), [&](auto nl) {
+			return rca_launch_tiles(das_rca_staged_cubic_kernel<CW, VS, WS, decltype(nl)::value>, q->tiles[0] * q->tiles[1] * q->tiles[2], q->threads, a, q, s);
+		});
+	});
 }
-
 /* complex samples, cubic interpolation; the caller checked q->window_shift */
 extern "C" hipError_t bf_launch_das_staged_cubic(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {

@@ -12,9 +12,7 @@
  * fma (interpolation), one add (sum), and with coherency weighting one add of |sample| (a free modifier).
  * The gather kernel (das_separable.hip) pays 16.3 clk per wave64 gather for the same term.
  */
-#include "das_common.h"
-
-typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
+#include "das_staged_shared.h"
 
 /* LDS (A4 = transmits rounded up to a multiple of 4):
  *   stage[a*W + j]   = { c_j, d_j }: the line through samples j and j + 1 of window (c, a) in window coordinates;
@@ -41,95 +39,30 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_real_kernel(const BfDa
 	f32x2 *wave_range = reinterpret_cast<f32x2 *>(rfloor + ((chunk + 1) & ~1));
 	const uint32_t stage_elements = (uint32_t)A4 * W;
 
-	const uint32_t total = q.tiles[0] * q.tiles[1] * q.tiles[2];
-	const uint32_t per   = (total + 7u) / 8u;
-	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-	if (tile >= total) return;                               /* whole block */
-	uint32_t tu, tv, zl;                                     /* walk order: das_separable.hip */
-	if (q.depth_major & 1u) {
-		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
-	} else {
-		tu = tile % q.tiles[0];
-		tv = (tile / q.tiles[0]) % q.tiles[1];
-		zl = tile / (q.tiles[0] * q.tiles[1]);
-	}
+	uint32_t tu, tv, zl;
+	if (!staged_tile_of(q, false, tu, tv, zl)) return;      /* whole block */
 	const uint32_t z  = p.z_first + zl;
 
 	const uint32_t u_axis = q.u_axis, v_axis = 1u - q.u_axis;
-	const float denom[3] = {fmaxf(1.0f, (float)p.size[0] - 1.0f), fmaxf(1.0f, (float)p.size[1] - 1.0f),
-	                        fmaxf(1.0f, (float)p.size[2] - 1.0f)};
-	const float pz = (float)z / denom[2];
-	const BfTransmit t0 = p.transmits[0];
-	const bool  rx_rows = (t0.flags & BF_RX_ROWS) != 0;
-	[[maybe_unused]] const float rx_pitch = rx_rows ? p.pitch[1] : p.pitch[0];
+	const bool  rx_rows = (p.transmits[0].flags & BF_RX_ROWS) != 0;
 	const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
 	if (q.depth_major & 2u) staged_violation_clear(tid);       /* STAGED_CHECKED: das_common.h */
 
-	/* ---- transmit delays (absolute first) */
-	for (uint32_t e = tid; e < (uint32_t)A4 * V; e += nthreads) {
-		uint32_t a = e >> VS, iv = e & (V - 1);
-		float t_idx = 0.f;                                   /* padding transmits: window position 0 over a zero row */
-		if (a < (uint32_t)A) {
-			float coord[3] = {0.f, 0.f, pz};
-			coord[v_axis] = (float)(tv * V + iv) / denom[v_axis];
-			float wx, wy, wz;
-			m4_point(p.voxel_transform, coord[0], coord[1], coord[2], wx, wy, wz);
-			const BfTransmit t = p.transmits[a];
-			float dist = 0.f;
-			if (!(t.flags & BF_TX_NONE)) {
-				float px = (t.flags & BF_TX_ROWS) ? wy : wx;
-				if (t.flags & BF_TX_PLANE) dist = px * t.sin_a + wz * t.cos_a;
-				else { float ddx = px - t.focus_x, ddz = wz - t.focus_z; dist = hw_sqrt(ddx * ddx + ddz * ddz); }
-			}
-			t_idx = (div_speed_of_sound(dist, p) + p.time_offset) * p.sampling_frequency;
-		}
+	/* ---- transmit delays: no phasors */
+	staged_transmit_entries<VS, false>(p, v_axis, tv, z, tid, nthreads, [&](uint32_t a, uint32_t iv, uint32_t, float t_idx, float, float) {
 		reinterpret_cast<float *>(Tz + (a >> 1) * V + iv)[a & 1u] = t_idx;
-	}
+	});
 	if (tid == 0) stage[stage_elements] = f32x2{0.f, 0.f};
-	__syncthreads();
-	{
-		float lo = __builtin_inff(), hi = -__builtin_inff();
-		for (uint32_t e = tid; e < (uint32_t)A * V; e += nthreads) {
-			uint32_t a = e >> VS, iv = e & (V - 1);
-			float v = reinterpret_cast<const float *>(Tz + (a >> 1) * V + iv)[a & 1u];
-			lo = fminf(lo, v); hi = fmaxf(hi, v);
-		}
-		for (int off = 32; off > 0; off >>= 1) {
-			lo = fminf(lo, __shfl_xor(lo, off, 64));
-			hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-		}
-		if ((tid & 63u) == 0) wave_range[tid >> 6] = f32x2{lo, hi};
-	}
-	__syncthreads();
-	float range_lo, range_hi;
-	{
-		/* (scalar temporaries throughout: __builtin_bit_cast on a vector component reads component 0 with this hipcc) */
-		float lo = __builtin_inff(), hi = -__builtin_inff();
-		for (uint32_t w = 0; w < (nthreads >> 6); w++) {
-			const f32x2 r = wave_range[w];
-			const float rl = r.x, rh = r.y;
-			lo = fminf(lo, rl); hi = fmaxf(hi, rh);
-		}
-		range_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lo)));
-		range_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, hi)));
-	}
-	for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads) {
-		float *row = reinterpret_cast<float *>(Tz + (size_t)(a >> 1) * V) + (a & 1u);
-		float  m   = row[0];
-		#pragma unroll 4
-		for (uint32_t iv = 1; iv < V; iv++) m = fminf(m, row[2 * iv]);
-		float fl = __builtin_floorf(m);
-		#pragma unroll 4
-		for (uint32_t iv = 0; iv < V; iv++) row[2 * iv] = (row[2 * iv] - fl) - 0.5f;      /* both steps exact */
-		tfl[a] = (int)fl;
-	}
+	const f32x2 range = rca_tile_range((uint32_t)A * V, wave_range, [&](uint32_t e) {
+		uint32_t a = e >> VS, iv = e & (V - 1);
+		return reinterpret_cast<const float *>(Tz + (a >> 1) * V + iv)[a & 1u];
+	});
+	for (uint32_t a = tid; a < (uint32_t)A4; a += nthreads)
+		tfl[a] = staged_window_row<V, 2, 0>(reinterpret_cast<float *>(Tz + (size_t)(a >> 1) * V) + (a & 1u));
 	__syncthreads();                                         /* the floors are read below */
 
-	uint32_t lu, lv;
-	if (u_axis == 0) { lu = tid & (U - 1); lv = tid >> q.u_shift; }
-	else             { lv = tid & (V - 1); lu = tid >> VS; }
-	const uint32_t gu = tu * U + lu, gv = tv * V + lv;
-	const uint32_t x = u_axis == 0 ? gu : gv, y = u_axis == 0 ? gv : gu;
+	uint32_t x, y, lu, lv_unused;
+	rca_voxel_of(tid, u_axis, U, q.u_shift, V, VS, tu, tv, x, y, lu, lv_unused);
 	const bool inside = x < p.size[0] && y < p.size[1];
 
 	float coherent = 0.f, incoherent = 0.f;
@@ -138,22 +71,11 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_real_kernel(const BfDa
 	uint32_t tz_base = (uint32_t)(uintptr_t)(lds_f32x2 *)Tz;
 	asm("" : "+s"(tz_base));
 
-	/* staging: as das_staged.hip, 4-byte samples */
-	const __amdgpu_buffer_rsrc_t rf_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-		const_cast<void *>(p.rf), 0, (int)((uint32_t)C * (uint32_t)A * (uint32_t)S * 4u), 0x00020000);
-	const uint32_t windows_per_pass = nthreads >> WS;
+	/* staging (das_staged_shared.h): 4-byte samples */
+	const __amdgpu_buffer_rsrc_t rf_rsrc = staged_rf_resource<float>(p);
 	uint32_t stage_inv[NL];
-	#pragma unroll
-	for (int n = 0; n < NL; n++) {
-		uint32_t a = (tid >> WS) + (uint32_t)n * windows_per_pass;
-		stage_inv[n] = a < (uint32_t)A ? (a * (uint32_t)S + (uint32_t)(tfl[a] + (int)(tid & (W - 1)))) * 4u : 0x80000000u;
-	}
-	auto stage_load = [&](int channel, int rfl, float (&regs)[NL]) {
-		const uint32_t at = ((uint32_t)channel * (uint32_t)A * (uint32_t)S + (uint32_t)rfl) * 4u;
-		#pragma unroll
-		for (int n = 0; n < NL; n++)
-			regs[n] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf_rsrc, (int)(stage_inv[n] + at), 0, 0));
-	};
+	staged_stage_offsets<float, WS, 0>(stage_inv, tfl, A, S, tid, nthreads);
+	auto stage_load = [&](int channel, int rfl, float (&regs)[NL]) { staged_stage_load(rf_rsrc, stage_inv, channel, A, S, rfl, regs); };
 	const float half_minus_j = 0.5f - (float)(tid & (W - 1));
 	auto stage_store = [&](const float (&regs)[NL]) {
 		#pragma unroll
@@ -169,50 +91,7 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_real_kernel(const BfDa
 	for (int c0 = 0; c0 < C; c0 += chunk) {
 		const int cn = (C - c0) < chunk ? (C - c0) : chunk;
 		__syncthreads();
-		{
-		/* the ~45 scalars of the receive-table build come from the kernel-argument segment at the top of every chunk instead of
-		 * living in SGPRs across the channel loop (das_staged.hip) */
-		typedef __attribute__((address_space(4))) const BfDasArgs const_args;
-		const_args *ka = (const_args *)__builtin_amdgcn_kernarg_segment_ptr();
-		asm volatile("" : "+s"(ka));
-		const float k_denom_u = fmaxf(1.0f, (float)ka->size[u_axis] - 1.0f);
-		const float k_pz = (float)z / fmaxf(1.0f, (float)ka->size[2] - 1.0f);
-		const float k_fs = ka->sampling_frequency, k_inv_c = ka->inv_speed_of_sound, k_c = ka->speed_of_sound, k_fnum = ka->f_number;
-		const float k_pitch = rx_rows ? ka->pitch[1] : ka->pitch[0];
-		for (uint32_t e = tid; e < (uint32_t)cn * U; e += nthreads) {
-			uint32_t c = (uint32_t)c0 + (e >> q.u_shift), iu = e & (U - 1);
-			float coord[3] = {0.f, 0.f, k_pz};
-			coord[u_axis] = (float)(tu * U + iu) / k_denom_u;
-			float wx, wy, wz, xx, xy, xz;
-			m4_point(ka->voxel_transform, coord[0], coord[1], coord[2], wx, wy, wz);
-			m4_point(ka->xdc_transform, wx, wy, wz, xx, xy, xz);
-			float lateral = rx_rows ? xy : xx;
-			float dx      = lateral - (float)c * k_pitch;
-			float a_arg   = __builtin_fabsf(dx * (k_fnum * hw_rcp(__builtin_fabsf(xz))));
-			float r_idx   = div_speed_of_sound(hw_sqrt(dx * dx + xz * xz), k_inv_c, k_c) * k_fs;
-			float apod    = 0.f;
-			if (a_arg < 0.5f) { float cs = hw_cos_turns(0.5f * a_arg); apod = cs * cs; }
-			R[e] = f32x2{r_idx, apod};
-		}
-		}
-		__syncthreads();
-		for (uint32_t cl = tid; cl < (uint32_t)cn; cl += nthreads) {
-			const float *row = reinterpret_cast<const float *>(R + (size_t)cl * U);
-			float m = row[0];
-			#pragma unroll 4
-			for (uint32_t iu = 1; iu < U; iu++) m = fminf(m, row[2 * iu]);
-			rfloor[cl] = (int)__builtin_floorf(m);
-		}
-		__syncthreads();
-		for (uint32_t e = tid; e < (uint32_t)cn * U; e += nthreads) {
-			const f32x2 entry = R[e];
-			float r_abs = entry.x, w = entry.y;
-			const bool lane_safe = (r_abs + range_lo >= 0.f) && (r_abs + range_hi < (float)(S - 1));
-			r_abs -= (float)rfloor[e >> q.u_shift];
-			if (!lane_safe) w = -w;                          /* -0.0f outside the aperture: still "unsafe" to the sign test */
-			R[e] = f32x2{r_abs, w};
-		}
-		__syncthreads();
+		staged_receive_table<f32x2, 0>(R, rfloor, c0, cn, tu, z, u_axis, q.u_shift, rx_rows, range, S, tid, nthreads);
 
 		float regs[NL];
 		stage_load(c0, rfloor[0], regs);
@@ -285,50 +164,24 @@ __global__ __launch_bounds__(1024, 8) void das_rca_staged_real_kernel(const BfDa
 	if (q.depth_major & 2u) staged_violation_report(tid);      /* (block uniform: every thread reaches it) */
 	if (!inside) return;
 
-	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<float *>(p.out)[out_index] = coherent;
-}
-
-template <bool CW, int VS, int WS, int NL>
-static hipError_t launch_staged_real(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	uint32_t total = q->tiles[0] * q->tiles[1] * q->tiles[2];
-	uint32_t grid  = ((total + 7u) / 8u) * 8u;
-	auto kernel = das_rca_staged_real_kernel<CW, VS, WS, NL>;
-	hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(q->threads), q->lds_bytes, s, *a, *q);
-	return hipGetLastError();
-}
-
-template <bool CW, int VS, int WS>
-static hipError_t launch_staged_real_loads(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	const uint32_t A4 = ((uint32_t)a->acquisition_count + 3u) & ~3u;
-	switch (((A4 << WS) + q->threads - 1) / q->threads) {
-	case 1: return launch_staged_real<CW, VS, WS, 1>(a, q, s);
-	case 2: return launch_staged_real<CW, VS, WS, 2>(a, q, s);
-	case 3: return launch_staged_real<CW, VS, WS, 3>(a, q, s);
-	case 4: return launch_staged_real<CW, VS, WS, 4>(a, q, s);
-	case 5: case 6: return launch_staged_real<CW, VS, WS, 6>(a, q, s);       /* (a staging width larger than needed only loads zeros) */
-	case 7: case 8: return launch_staged_real<CW, VS, WS, 8>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	rca_store_voxel<CW>(p, zl, x, y, coherent, incoherent);
 }
 
 template <bool CW>
 static hipError_t launch_staged_real_shape(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
-	switch ((q->v_shift << 4) | q->window_shift) {
-	case (4 << 4) | 5: return launch_staged_real_loads<CW, 4, 5>(a, q, s);
-	case (5 << 4) | 5: return launch_staged_real_loads<CW, 5, 5>(a, q, s);
-	case (6 << 4) | 5: return launch_staged_real_loads<CW, 6, 5>(a, q, s);
-	case (4 << 4) | 6: return launch_staged_real_loads<CW, 4, 6>(a, q, s);
-	case (5 << 4) | 6: return launch_staged_real_loads<CW, 5, 6>(a, q, s);
-	case (6 << 4) | 6: return launch_staged_real_loads<CW, 6, 6>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	return staged_for_shape(q, [&](auto vs, auto ws) {
+		constexpr int VS = decltype(vs)::value, WS = decltype(ws)::value;
+		auto launch = [&](auto nl) {
+			return rca_launch_tiles(das_rca_staged_real_kernel<CW, VS, WS, decltype(nl)::value>, q->tiles[0] * q->tiles[1] * q->tiles[2], q->threads, a, q, s);
+		};
+		const uint32_t passes = staged_passes(a, q, WS);
+		switch (passes) {
+		case 5: case 6: return launch(std::integral_constant<int, 6>{});       /* (a staging width larger than needed only loads zeros) */
+		case 7: case 8: return launch(std::integral_constant<int, 8>{});
+		}
+		return staged_for_passes(passes, launch);
+	});
 }
 
 /* real samples, linear interpolation; the caller (bf_launch_das_staged) checked the rest */

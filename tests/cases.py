@@ -66,6 +66,11 @@ def _cases():
     c["rca_staged_real_short_rows"] = lambda: cfg.rca("rca_staged_real_short_rows", 24, 7, 256, (45, 70, 2), LO3, HI3, seed=50,
                                                       orientation=0x21, cw=False, demodulate=False, data_kind=D.Float32, f_number=0.6,
                                                       angles=np.linspace(-12, 12, 7))
+    # ... and the same call over half the lateral extent with coherency weighting: the one real-sample case whose delay spread a
+    # 32-sample window holds (every tile and window shape of the real kernel under STAGED_SHAPE)
+    c["rca_staged_real_narrow_cw"] = lambda: cfg.rca("rca_staged_real_narrow_cw", 24, 7, 256, (45, 70, 2), (-1.5e-3, -1.5e-3, 6e-3),
+                                                     (1.5e-3, 1.5e-3, 18e-3), seed=56, orientation=0x21, cw=True, demodulate=False,
+                                                     data_kind=D.Float32, f_number=0.6, angles=np.linspace(-12, 12, 7))
     # cubic interpolation of IQ samples on the staged kernel's cubic twin (9 transmits: padded batch), and with rows short enough
     # that most waves run its checked loop
     c["rca_staged_cubic"] = lambda: cfg.rca("rca_staged_cubic", 32, 9, 1024, (40, 36, 3), LO3, HI3, seed=51, orientation=0x12, cw=True,
@@ -250,7 +255,7 @@ CASES.update(_plane_cases())
 EXPECTED_AUTOMATIC = {
     "config1_small": 0, "config2_small": 3, "config3_small": 0, "config4_small": 1, "config5_small": 0,
     "rca_staged_auto": 2, "rca_staged_w64": 1, "rca_staged_too_wide": 1, "rca_staged_ragged": 2, "rca_vls_staged": 2,
-    "rca_staged_real": 2, "rca_staged_cubic": 2, "rca_staged_fine": 2, "rca_sep_ragged_cubic": 3, "rca_sep_real_nearest": 3,
+    "rca_staged_real": 2, "rca_staged_real_narrow_cw": 2, "rca_staged_cubic": 2, "rca_staged_fine": 2, "rca_sep_ragged_cubic": 3, "rca_sep_real_nearest": 3,
     "hercules_wide_cw": 4, "hercules_wide_real_swapped": 4, "hercules_wide_cubic_cw": 4, "hercules_plane_xz": 4, "hercules_plane_yz": 4,
     "forces": 3, "uforces_sparse": 3, "readi": 0, "harness_tpw_small": 3, "harness_forces_small": 3, "harness_hercules_small": 0,
     "hercules_plane_xz_short_rows": 4, "hercules_plane_yz_short_rows": 4,
@@ -258,7 +263,14 @@ EXPECTED_AUTOMATIC = {
 # ... and how many z-planes of the case the row-end rule hands to the kernel BEHIND that choice (cases not listed: none)
 EXPECTED_ROW_END_PLANES = {
     "rca_staged_auto": 1, "rca_staged_fine": 1, "rca_staged_ragged": 1,
-    "rca_staged_cubic_short_rows": 1, "rca_staged_real_short_rows": 1, "rca_staged_fine_vls_short_rows": 2, "rca_vls_staged_short_rows": 3,
+    "rca_staged_cubic_short_rows": 1, "rca_staged_real_short_rows": 1, "rca_staged_real_narrow_cw": 1, "rca_staged_fine_vls_short_rows": 2, "rca_vls_staged_short_rows": 3,
 }
 # ... and the cases of which NO plane keeps the staged kernel (their das path is the fallback's)
 ROW_END_EVERY_PLANE = {"rca_staged_fine_vls_short_rows", "rca_vls_staged_short_rows"}
+# ... and, under das path 3, the BEAMFORMER_HIP_STAGED_SHAPE values ("log2 U, log2 V, log2 W") at which the planner takes the staged
+# kernel for the two cases that carry the real and the cubic kernel through every (V, W) instantiation
+# (tests/test_gpu_parity.py test_lds_staged_kernel_every_tile_and_window_shape tolerates a declined shape: this list keeps it honest)
+STAGED_SHAPES_TAKEN = {
+    "rca_staged_real_narrow_cw": ["5,4,5", "4,5,5", "4,6,5", "5,4,6", "4,5,6", "6,4,6", "5,5,6", "4,6,6"],
+    "rca_staged_cubic_short_rows": ["5,4,5", "4,5,5", "4,6,5", "5,4,6", "4,5,6", "6,4,6", "5,5,6", "4,6,6"],
+}

@@ -49,6 +49,26 @@ def test_forced_paths_and_reasons():
         L.beamformer_hip_set_das_path(0)
 
 
+@pytest.mark.parametrize("name", sorted(cases.STAGED_SHAPES_TAKEN))
+def test_staged_shapes_of_the_real_and_cubic_kernels_are_taken(name):
+    """das path 3 under BEAMFORMER_HIP_STAGED_SHAPE: the planner takes the staged kernel at every shape listed for the case -- each
+    (V, W) instantiation of the real-sample and of the cubic kernel -- so the GPU test over these shapes runs the kernel it names"""
+    acq = cases.make(name)
+    L = lib.library()
+    L.beamformer_hip_set_das_path(3)
+    try:
+        for shape in cases.STAGED_SHAPES_TAKEN[name]:
+            lib.set_hook("STAGED_SHAPE", shape)
+            path, kernel, _, reasons, d = lib.describe_das(acq.bp, acq.filters)
+            u, v, w = (int(x) for x in shape.split(","))
+            assert path == int(P.DasPath.Staged), (shape, kernel, reasons[2])
+            assert (int(d.u_shift), int(d.v_shift), int(d.window_samples)) == (u, v, 1 << w), shape
+        assert {(s.split(",")[1], s.split(",")[2]) for s in cases.STAGED_SHAPES_TAKEN[name]} == {(v, w) for v in "456" for w in "56"}
+    finally:
+        lib.set_hook("STAGED_SHAPE", None)
+        L.beamformer_hip_set_das_path(0)
+
+
 def test_block_staged_kernel_selection():
     """das_tile.hip (path 5): automatic for BASELINE config 2 at full size (fine grid, cubic IQ, tx and rx on one axis: 64 x 16 tiles,
     32-sample windows -- the derivative bound says 27.9 samples, the spread sampled on the image's extreme tiles 26 --, the banded plane walk), declined with its reason on small frames (channel split), under flag 0x200, for other

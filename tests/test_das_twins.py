@@ -15,7 +15,7 @@ MODES = (0, 1, 2, 3, 6, 0x04, 0x14, 0x14 | 0x100, 0x11, 0x10 | 0x100)
 
 
 def test_the_binary16_staged_cases_are_the_ones_counted():
-    assert len(cases.CASES) == 67 and len(F16_STAGED) == 50
+    assert len(cases.CASES) == 68 and len(F16_STAGED) == 50
     for name in ("config1_small", "config2_small", "config3_small", "config4_small", "config5_small", "rca_staged_auto", "tile_tpw",
                  "harness_tpw_small", "hercules_plane_yz", "hercules_real"):
         assert name in F16_STAGED

@@ -36,13 +36,13 @@ def last_das_path(bflib):
 # geometries whose receive and transmit axes differ: the separable-delay fast path must pick
 # them up on its own (das_separable.hip)
 SEPARABLE = {"config4_small", "rca_vls_cw", "rca_sep_ragged_cubic", "rca_sep_real_nearest",
-             "rca_staged_w64", "rca_staged_too_wide", "rca_staged_ragged", "rca_staged_auto", "rca_vls_staged", "rca_vls_staged_short_rows", "rca_staged_real", "rca_staged_real_short_rows", "rca_staged_cubic", "rca_staged_cubic_short_rows",
+             "rca_staged_w64", "rca_staged_too_wide", "rca_staged_ragged", "rca_staged_auto", "rca_vls_staged", "rca_vls_staged_short_rows", "rca_staged_real", "rca_staged_real_short_rows", "rca_staged_real_narrow_cw", "rca_staged_cubic", "rca_staged_cubic_short_rows",
              "rca_staged_fine", "rca_staged_fine_vls_short_rows"}
 # ... and of those, the ones with linear interpolation (complex or real samples) or cubic interpolation of complex samples whose
 # delay spread fits an LDS window
 # can run the LDS-staged kernel (das_staged.hip): automatically from STAGED_MIN_TRANSMITS transmits per
 # channel (executor.cpp kStagedMinTransmits), on request (path 3) below that
-STAGED = {"config4_small", "rca_staged_w64", "rca_staged_ragged", "rca_staged_auto", "rca_vls_staged", "rca_vls_staged_short_rows", "rca_staged_real", "rca_staged_real_short_rows", "rca_staged_cubic", "rca_staged_cubic_short_rows",
+STAGED = {"config4_small", "rca_staged_w64", "rca_staged_ragged", "rca_staged_auto", "rca_vls_staged", "rca_vls_staged_short_rows", "rca_staged_real", "rca_staged_real_short_rows", "rca_staged_real_narrow_cw", "rca_staged_cubic", "rca_staged_cubic_short_rows",
           "rca_sep_ragged_cubic", "rca_staged_fine", "rca_staged_fine_vls_short_rows"}
 STAGED_MIN_TRANSMITS = 6
 
@@ -132,7 +132,7 @@ def test_lds_staged_kernel(name, bflib, oracle):
 
 
 @pytest.mark.parametrize("shape", ["5,4,5", "4,5,5", "6,4,5", "5,5,5", "4,6,5", "5,4,6", "4,5,6", "6,4,6", "5,5,6", "4,6,6"])
-@pytest.mark.parametrize("name", ["rca_staged_auto", "rca_staged_ragged"])
+@pytest.mark.parametrize("name", ["rca_staged_auto", "rca_staged_ragged", "rca_staged_cubic_short_rows", "rca_staged_real_narrow_cw"])
 def test_lds_staged_kernel_every_tile_and_window_shape(name, shape, bflib, oracle, hooks):
     """BEAMFORMER_HIP_STAGED_SHAPE = "log2 U, log2 V, log2 W": each instantiation of the staged kernel (tile extents along
     the receive / transmit axes, 32- or 64-sample windows, 512- and 1024-thread blocks) instead of the shape the host would

@@ -1,0 +1,96 @@
+"""Same-box alternating A/B of two builds of the library over a list of measurement rows: every row is a command that prints JSON
+lines; it runs `--runs` times a side, the parent's library first in every pair (OGL_BEAMFORMER_LIB selects it), and one figure is read
+from each run.  Records per row both sides' runs, medians, spreads (max - min of a side) and the difference, and applies the project's
+bar (profiles/README.md): a row is slower when its median is worse than the parent's by more than three times the parent's spread.
+Run from the repository root on a GPU box:
+  PYTHONPATH=. python tools/ab_rows.py --parent build/variants/libogl_parent.so --rows headline,gather --json out.json"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+BENCH = [sys.executable, "bench.py", "--gpus", "1", "--config", "4", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+
+
+def last_json(text, want):
+    for line in reversed(text.strip().split("\n")):
+        line = line.strip()
+        if line.startswith("{") or line.startswith("["):
+            try:
+                v = json.loads(line)
+            except ValueError:
+                continue
+            if want(v):
+                return v
+    raise RuntimeError("no JSON result line in:\n" + text[-2000:])
+
+
+def bench_row(extra):
+    def run(env):
+        out = subprocess.run(BENCH + extra, env=env, capture_output=True, text=True, check=True, timeout=600).stdout
+        v = last_json(out, lambda v: isinstance(v, dict) and "ms_per_step" in v)
+        return {"figure": float(v["ms_per_step"]), "das_path": v["config"]["das_path"]}
+    return run
+
+
+def uniform_rows(env):
+    out = subprocess.run([sys.executable, "tools/staged_uniform.py", "--scales", "0.5"], env=env, capture_output=True, text=True, check=True, timeout=600).stdout
+    v = last_json(out, lambda v: isinstance(v, dict) and "uniform_ms" in v)
+    return {"figure": float(v["uniform_ms"]), "das_path": v["uniform_path"], "tables_in_lds_ms": float(v["tables_in_lds_ms"]), "tables_in_lds_path": v["tables_in_lds_path"]}
+
+
+def real_row(env):
+    out = subprocess.run([sys.executable, "tools/staged_real_rate.py"], env=env, capture_output=True, text=True, check=True, timeout=600).stdout
+    v = last_json(out, lambda v: isinstance(v, dict) and "das_ms_median" in v)
+    return {"figure": float(v["das_ms_median"]), "das_path": v["das_path"]}
+
+
+ROWS = {
+    "headline": ("bench.py config 4 (channel-paired staged kernel: identical code, the noise reference), ms per step", bench_row([])),
+    "gather": ("bench.py config 4 --das-path 2 (gather kernel), ms per step", bench_row(["--das-path", "2"])),
+    "cubic": ("bench.py config 4 --interpolation cubic (staged cubic kernel), ms per step", bench_row(["--interpolation", "cubic"])),
+    "uniform": ("tools/staged_uniform.py --scales 0.5, 32 planes: unpaired complex kernel, uniform tables, DAS ms (tables in LDS beside it)", uniform_rows),
+    "real": ("tools/staged_real_rate.py: real-sample staged kernel on config 4's geometry without Demodulate, median DAS ms of 5 pushes", real_row),
+}
+
+
+def side(runs, key="figure"):
+    vals = [r[key] for r in runs]
+    return {"runs": vals, "median": statistics.median(vals), "spread": max(vals) - min(vals)}
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", required=True)
+    ap.add_argument("--library", default=os.path.join("ogl_beamforming_amd", "libogl_beamformer_lib.so"))
+    ap.add_argument("--rows", default=",".join(ROWS))
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--json", default="")
+    args = ap.parse_args()
+    result = {"what": "same-box alternating A/B, parent first in every pair, lower is better; slower = median over the parent's by more than 3 x the parent's spread",
+              "runs_a_side": args.runs, "rows": {}}
+    for name in args.rows.split(","):
+        what, run = ROWS[name]
+        sides = {"parent": [], "this": []}
+        for _ in range(args.runs):
+            for label, library in (("parent", args.parent), ("this", args.library)):
+                env = dict(os.environ, OGL_BEAMFORMER_LIB=os.path.abspath(library), PYTHONPATH=os.getcwd())
+                sides[label].append(run(env))
+        row = {"what": what, "parent": side(sides["parent"]), "this": side(sides["this"]),
+               "das_path": sorted({str(r["das_path"]) for r in sides["parent"] + sides["this"]})}
+        if name == "uniform":
+            row["tables_in_lds"] = {"parent": side(sides["parent"], "tables_in_lds_ms"), "this": side(sides["this"], "tables_in_lds_ms")}
+            t = row["tables_in_lds"]
+            t["difference"] = t["this"]["median"] - t["parent"]["median"]
+            t["slower"] = t["difference"] > 3.0 * t["parent"]["spread"]
+        row["difference"] = row["this"]["median"] - row["parent"]["median"]
+        row["bar"] = 3.0 * row["parent"]["spread"]
+        row["slower"] = row["difference"] > row["bar"]
+        result["rows"][name] = row
+        print(json.dumps({name: row}), flush=True)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")

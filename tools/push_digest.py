@@ -3,7 +3,7 @@ frames, as device-resident frames, as bursts and as views pushes, the SHA-256 of
 bookkeeping a client can read back -- das_path, das_row_end_planes and the stage kinds of beamformer_hip_get_last_frame_timings, a
 burst's route and stage kinds from beamformer_hip_get_last_burst_info, a views push's from beamformer_hip_get_last_views_info, das_pairs
 where pair counting is on (of the newest frame's row: the C ABI reads no other row's), which of the two info calls is served after each
-push of a mixed sequence, what a views push that fails leaves behind, the graphs instantiated where frame graphs are.  The kernels are deterministic and the RF is seeded, so two builds of the library that enqueue the same work print the same
+push of a mixed sequence, what a views push that fails leaves behind, the graphs instantiated where frame graphs are; and for the row-column DAS family every named case under every das path mode and staged-kernel hook of its parity tests.  The kernels are deterministic and the RF is seeded, so two builds of the library that enqueue the same work print the same
 object: run it on both (OGL_BEAMFORMER_LIB selects the library, tools/build_variant.sh builds the other one) and compare.
 Run from the repository root on a GPU box:  PYTHONPATH=. python tools/push_digest.py --json profiles/push_digest.json"""
 import argparse
@@ -288,6 +288,38 @@ finally:
     L.beamformer_hip_enable_pair_counting(0)
     L.beamformer_hip_set_das_path(0)
 
+
+# ---- the row-column DAS family (das_staged*.hip, das_separable.hip): every named case the gather or a staged kernel takes, under
+# the das path modes and staged-kernel hooks of tests/test_gpu_parity.py -- the frame's digest and the path that produced it
+from tests.test_gpu_parity import SEPARABLE, STAGED                      # noqa: E402
+
+STAGED_SHAPES = ["5,4,5", "4,5,5", "6,4,5", "5,5,5", "4,6,5", "5,4,6", "4,5,6", "6,4,6", "5,5,6", "4,6,6"]
+FAMILY_MODES = [("path0", 0, ()), ("path2", 2, ()), ("path3", 3, ()), ("path3_checked", 3, (("STAGED_CHECKED", "1"),)),
+                ("path3_nouniform", 3, (("STAGED_NOUNIFORM", "1"),))] + \
+               [("path3_shape_" + shape, 3, (("STAGED_SHAPE", shape),)) for shape in STAGED_SHAPES]
+family = {}
+L.beamformer_hip_shutdown()
+assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
+try:
+    for name in sorted(STAGED | SEPARABLE):
+        acq = cases.make(name)
+        family[name] = {}
+        for label, mode, hooks in FAMILY_MODES:
+            for hook, value in hooks:
+                lib.set_hook(hook, value)
+            L.beamformer_hip_set_das_path(mode)
+            try:
+                frame = lib.beamform(acq.bp, acq.rf, acq.filters)
+                t = P.HipFrameTimings()
+                assert L.beamformer_hip_get_last_frame_timings(C.byref(t)), lib.last_error()
+                family[name][label] = {"sha256": sha(frame), "das_path": int(t.das_path), "das_row_end_planes": int(t.das_row_end_planes),
+                                       "staged_window_violations": int(t.staged_window_violations)}
+            finally:
+                for hook, _ in hooks:
+                    lib.set_hook(hook, None)
+finally:
+    L.beamformer_hip_set_das_path(0)
+result["rca_family"] = family
 
 text = json.dumps(result, indent=1, sort_keys=True)
 print(text)
