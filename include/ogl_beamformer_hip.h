@@ -169,6 +169,43 @@ typedef struct {
 /* The newest burst (frame_count >= 2); waits for it to finish.  Fails when the newest push was not a burst or did not complete. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_burst_info(BeamformerHipBurstInfo *out);
 
+/* ---- READI sweeps: the N group acquisitions of a READI sequence per call ----
+ * A READI image is the sum of readi_group_count partial frames; acquisition k is beamformed with readi_group = g_k, which selects row
+ * g_k of the Hadamard matrix as per-group signs (shaders/das.glsl:323-366).  A sweep is a burst with a group list: frame_count RF
+ * frames back to back in `data` under exactly the burst's layout and size rules, and frame k is the frame a single push of RF k would
+ * give if the block's readi_group were readi_groups[k].  readi_groups == NULL means (block.readi_group + k) % readi_group_count.
+ * Everything else is the burst's contract (above):
+ *   - consecutive frame ids, oldest = first in `data`; one upload and one RF-ring slot; the ingest and every pre-DAS stage ONCE; the
+ *     frames contiguous in the frame ring; one event set, every frame reporting its 1 / frame_count share; an output shard on the block
+ *     is honoured; several devices are refused (InvalidAccess); frame graphs: direct launches; pair counting: one count, reported by
+ *     every frame; frame_count == 0 and frame_count > BEAMFORMER_HIP_MAX_BURST_FRAMES are BufferOverflow.  frame_count == 1 goes through
+ *     the same code as any other count (it is NOT handed to the single push: its group comes from the list);
+ *   - blocks whose single frames run the general kernel (every READI block on the automatic path) take ONE DAS launch for sweeps of
+ *     min_frames frames and more (csrc/das_burst.hip: das_readi_burst_kernel -- a thread computes each (channel, transmit) term's
+ *     geometry once and applies it to BEAMFORMER_HIP_BURST_FRAMES_PER_THREAD frames, each under its own group's signs); a frame of it
+ *     is within float rounding of its single push and its bits do not depend on its place in the sweep.  Otherwise -- fewer frames,
+ *     BeamformerHipDasPath_NoBurstKernel -- every frame runs the single-frame launch(es) with its group, and IS the single push's frame
+ *     bit for bit.  beamformer_hip_describe_readi_sweep says which, and why;
+ *   - refusals, all before a device is touched and before ids are taken (a refused sweep queues nothing): a block that is not READI --
+ *     an acquisition kind other than FORCES / UFORCES, or readi_group_count <= 1 -- is InvalidAccess, with a line on stderr; a list
+ *     entry >= readi_group_count is InvalidComputeStage, the kind a single push of a block with that readi_group gets (the planner
+ *     refuses the block).  A sweep that fails later leaves tombstones under all its ids;
+ *   - beamformer_hip_get_last_burst_info serves a sweep as it serves a burst (route.min_frames: the sweep's threshold).
+ * The plain burst call keeps its behaviour for READI blocks: every frame under the block's one readi_group, on the per-frame route. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_data_readi_sweep_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                                                 const uint32_t *readi_groups, uint32_t image_plane_tag,
+                                                                                 uint32_t parameter_slot);
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_device_data_readi_sweep_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                                        const uint32_t *readi_groups, uint32_t image_plane_tag,
+                                                                                        uint32_t parameter_slot);
+/* What a sweep of frame_count frames would run, under the current das path mode (min_frames: csrc/das_select.h kReadiSweepMinFrames).
+ * The block and the list are judged as the push judges them.  Needs no device. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_readi_sweep(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count,
+                                                                   BeamformerHipBurstDescription *out);
+/* The group of every frame of such a sweep, as the push resolves the list (NULL included): out[frame_count].  Needs no device. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_resolve_readi_groups(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count,
+                                                                   uint32_t *out);
+
 /* ---- views: ONE RF frame beamformed on K voxel grids per call (live X-plane / tri-plane imaging: the reference's 3DXPlane view;
  * ULM patch refinement: tens to hundreds of small fine grids around detections, all from the RF of one push) ----
  * `data` is one RF frame under exactly the layout and size rules of beamformer_push_data_with_compute.  Everything except the grid

@@ -79,6 +79,12 @@ typedef struct {
 	uint32_t pad;
 	uint64_t rf_stride, out_stride;   /* bytes */
 } BfBurstArgs;
+/* READI sweep form (das_burst.hip: das_readi_burst_kernel): a burst whose frame f is beamformed with row groups[f] of the Hadamard
+ * matrix (BfDasArgs.readi_group is not read).  The ids are validated on the host (all below readi_group_count); the kernel trusts them. */
+typedef struct {
+	BfBurstArgs     burst;
+	const uint32_t *groups;           /* [burst.frame_count], device */
+} BfReadiSweepArgs;
 
 /* views form of the general kernel (das_views.hip): one DAS input beamformed on several grids by one launch.  A row holds what differs
  * from view to view; everything else is the launch's BfDasArgs.  128 bytes, read through wave-uniform (scalar) loads. */
@@ -320,6 +326,7 @@ hipError_t bf_launch_hilbert(const BfFilterArgs *a, hipStream_t s);
 hipError_t bf_launch_das(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_count(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s);   /* das_burst.hip: RCA family, `a` without a channel split */
+hipError_t bf_launch_das_readi_sweep(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s);   /* das_burst.hip: READI, `a` without a channel split */
 hipError_t bf_launch_views_table(void *dst, const void *src, uint32_t bytes, hipStream_t s);   /* das_views.hip: bytes (a multiple of 4) from mapped pinned memory into the device table */
 hipError_t bf_launch_das_views(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s);   /* das_views.hip: RCA family, no channel split */
 hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);

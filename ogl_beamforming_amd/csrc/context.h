@@ -139,7 +139,7 @@ struct Device {
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
 	DeviceBuffer burst_stage[2];                               /* a burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
 	PushRecord   multi;
-	DeviceBuffer views_table;                                  /* a views push: the BfViewRows and the prefix table das_views.hip reads */
+	DeviceBuffer views_table;                                  /* a views push: the BfViewRows and the prefix table das_views.hip reads; a READI sweep: its frames' group ids */
 	void        *views_pinned = nullptr;                       /* ... and the pinned memory they are sent from, free again once views_copied has passed */
 	hipEvent_t   views_copied = nullptr;
 	bool         views_copy_pending = false;
@@ -209,6 +209,7 @@ bool ensure_device();                               /* SharedMemory error when n
 uint64_t default_frame_ring_bytes();
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device);
 bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device);
+bool push_readi_sweep(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);
 bool last_burst_info(BeamformerHipBurstInfo *out);
 bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device);
 bool last_views_info(BeamformerHipViewsInfo *out);

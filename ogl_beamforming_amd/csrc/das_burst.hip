@@ -21,15 +21,25 @@
  * slot.  RCA family
  * only (RCA_TPW, RCA_VLS, Flash): 3 interpolation modes x real / IQ x with / without coherency weighting = 12 instantiations.
  * No LDS, no barrier, no MFMA: gather / VALU bound as das.hip is.
+ *
+ * das_readi_burst_kernel is the same for a READI SWEEP (beamformer_hip_push_data_readi_sweep_with_compute): the group acquisitions of a
+ * READI image, frame f beamformed under row groups[f] of the Hadamard matrix.  das_forces<READI>'s loops (das.hip) walked once, the
+ * same grid and frame slots, burst_term with one weight per slot -- the apodization times the slot's sign --: 12 more instantiations.
  */
 #include "das_general.h"
 
 constexpr int FB = (int)BF_BURST_FRAMES_PER_THREAD;
 
+/* a term's weight in frame slot f: one apodization for every slot (RCA: float), or one per slot (READI: SlotWeights) */
+struct SlotWeights { float w[FB]; };
+__device__ __forceinline__ float slot_weight(float w, int) { return w; }
+__device__ __forceinline__ float slot_weight(const SlotWeights &w, int f) { return w.w[f]; }
+
 /* One in-aperture term of FB frames: sample_rf (das_common.h, das.glsl:99-124 + cubic :67-97) with everything that depends on the
- * index alone -- range test, tap, weights, phasor -- taken once.  A term outside the valid range adds nothing (sample_rf gives +0). */
-template <int INTERP, bool CPLX, bool CW>
-__device__ __forceinline__ void burst_term(const char *const (&rf)[FB], int rf_offset, float index, float apodization, const BfDasArgs &p,
+ * index alone -- range test, tap, weights, phasor -- taken once.  A term outside the valid range adds nothing (sample_rf gives +0).
+ * W: float, or SlotWeights (slot_weight). */
+template <int INTERP, bool CPLX, bool CW, typename W>
+__device__ __forceinline__ void burst_term(const char *const (&rf)[FB], int rf_offset, float index, W weights, const BfDasArgs &p,
                                            Accumulator<CPLX, CW, false> (&acc)[FB])
 {
 	/* The four frame slots must be the SAME arithmetic, so that a frame's bits do not depend on its place in the burst: left to itself
@@ -48,6 +58,7 @@ __device__ __forceinline__ void burst_term(const char *const (&rf)[FB], int rf_o
 	/* rotate, weight, RESULT_STORE (das.glsl:28-32) */
 	auto add = [&](int f, sample_t<CPLX> v) {
 		#pragma clang fp contract(off)
+		const float apodization = slot_weight(weights, f);
 		if constexpr (CPLX) {
 			v = f32x2{__builtin_fmaf(c, v.x, -(s * v.y)), __builtin_fmaf(s, v.x, c * v.y)};
 			if constexpr (CW) {
@@ -203,6 +214,99 @@ __global__ __launch_bounds__(256) void das_burst_kernel(const BfDasArgs p, const
 	}
 }
 
+/* das.glsl:368-407 + :323-366 (READI_FORCES) over FB frames, frame f under row q.groups[f] of the Hadamard matrix: das_forces<READI>
+ * (das.hip) in its own loop order -- channel, transmit group, transmit event -- without the channel split, so a frame's sum runs in the
+ * single frame's order.  Once per channel: the receive term, the aperture test, the apodization.  Once per term: the transmit term, the
+ * row-end settlement and everything burst_term takes once.  Per frame: the gather and the weight apodization * h[f], where
+ * h[f] = H[groups[f] * G + tx_group] (binary16 +-1: the product is exact) is block-uniform and read through scalar loads -- the table
+ * holds G * G >= 4 halves, an even count, and is read as 32-bit words. */
+template <int INTERP, bool CPLX, bool CW>
+__global__ __launch_bounds__(256) void das_readi_burst_kernel(const BfDasArgs p, const BfReadiSweepArgs r)
+{
+	const BfBurstArgs &q = r.burst;
+	const GeneralTile tile = general_tile(p, blockIdx.x);
+	if (!tile.valid) return;
+	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
+
+	uint32_t tid = threadIdx.x;
+	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
+	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
+	uint32_t lz  = (tid >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u);
+	uint32_t x = (bx << p.tile_shift[0]) + lx;
+	uint32_t y = (by << p.tile_shift[1]) + ly;
+	uint32_t zl = (bz << p.tile_shift[2]) + lz;       /* z inside the shard */
+	if (!(x < p.size[0] && y < p.size[1] && zl < p.z_count)) return;
+
+	/* this block's frames, as in das_burst_kernel; row[f]: where frame f's signs begin in the Hadamard matrix */
+	const uint32_t first = blockIdx.y * (uint32_t)FB;
+	const uint32_t count = q.frame_count - first < (uint32_t)FB ? q.frame_count - first : (uint32_t)FB;
+	const uint32_t G = p.readi_group_count;
+	const char *rf[FB];
+	uint32_t row[FB];
+	for (int f = 0; f < FB; f++) {
+		const uint32_t frame = first + ((uint32_t)f < count ? (uint32_t)f : count - 1u);
+		rf[f]  = (const char *)p.rf + (uint64_t)frame * q.rf_stride;
+		row[f] = r.groups[frame] * G;
+	}
+	Accumulator<CPLX, CW, false> acc[FB];
+	for (int f = 0; f < FB; f++) acc[f].init();
+	const uint32_t *hadamard = reinterpret_cast<const uint32_t *>(p.readi_hadamard);
+
+	uint32_t z = p.z_first + zl;
+	/* das.glsl:374-376; the host pre-multiplied the voxel transform: (xx, xy, xz) is in transducer space (das.hip das_forces) */
+	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
+	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
+	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
+	float xx, xy, xz;
+	m4_point(p.voxel_transform, px, py, pz, xx, xy, xz);
+
+	/* das.glsl:323-366 */
+	const int S = p.sample_count, A = p.acquisition_count, C = p.channel_count;
+	const float z_delta_squared     = xz * xz;
+	const float transmit_y_delta    = xy - p.pitch[1] * (float)C * 0.5f;
+	const float transmit_yz_squared = transmit_y_delta * transmit_y_delta + z_delta_squared;
+	const float f_over_z            = p.f_number * hw_rcp(xz);
+
+	for (int channel = 0; channel < C; channel++) {
+		float receive_x_delta = xx - (float)channel * p.pitch[0];
+		float a_arg           = __builtin_fabsf(receive_x_delta * f_over_z);
+		if (!(a_arg < 0.5f)) continue;
+
+		float receive_index = sample_index(hw_sqrt(receive_x_delta * receive_x_delta + z_delta_squared), p);
+		float apodization   = apodize(a_arg);
+
+		const int channel_rf_offset = channel * S * A;
+		for (uint32_t tx_group = 0; tx_group < G; tx_group++) {
+			int rf_offset = channel_rf_offset;     /* every group's events read the channel's A rows: the groups differ in geometry and sign */
+			SlotWeights weights;
+			for (int f = 0; f < FB; f++) {
+				const uint32_t at   = row[f] + tx_group;
+				const uint32_t word = hadamard[at >> 1];
+				_Float16 h = __builtin_bit_cast(_Float16, (uint16_t)((at & 1u) ? word >> 16 : word));
+				weights.w[f] = apodization * (float)h;
+			}
+			for (int tx_event = 0; tx_event < A; tx_event++) {
+				float tx_element       = (float)tx_group * (float)A + (float)tx_event;
+				float transmit_x_delta = xx - p.pitch[0] * tx_element;
+				float transmit_index   = div_speed_of_sound(hw_sqrt(transmit_yz_squared + transmit_x_delta * transmit_x_delta) * p.sampling_frequency, p);
+				const float index = settle_index<BF_DAS_READI, INTERP>(receive_index + transmit_index, p, x, y, z, channel, (int)tx_group * A + tx_event);
+				burst_term<INTERP, CPLX, CW>(rf, rf_offset, index, weights, p, acc);
+				rf_offset += S;
+			}
+		}
+	}
+
+	const uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
+	for (int f = 0; f < FB; f++) {
+		if ((uint32_t)f < count) {
+			sample_t<CPLX> v = acc[f].coherent;
+			/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949), as das.hip's epilogue */
+			if constexpr (CW) v = v * (v / acc[f].incoherent);
+			reinterpret_cast<sample_t<CPLX> *>((char *)p.out + (uint64_t)(first + (uint32_t)f) * q.out_stride)[out_index] = v;
+		}
+	}
+}
+
 template <int INTERP, bool CPLX, bool CW>
 static hipError_t launch_one(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s)
 {
@@ -229,6 +333,38 @@ extern "C" hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs 
 	case BF_INTERP_NEAREST: return launch_kind<BF_INTERP_NEAREST>(a, b, s);
 	case BF_INTERP_LINEAR:  return launch_kind<BF_INTERP_LINEAR>(a, b, s);
 	case BF_INTERP_CUBIC:   return launch_kind<BF_INTERP_CUBIC>(a, b, s);
+	}
+	return hipErrorInvalidValue;
+}
+
+template <int INTERP, bool CPLX, bool CW>
+static hipError_t launch_sweep_one(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s)
+{
+	uint32_t total = a->blocks[0] * a->blocks[1] * a->blocks[2];
+	uint32_t grid  = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
+	uint32_t groups = (b->burst.frame_count + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
+	hipLaunchKernelGGL((das_readi_burst_kernel<INTERP, CPLX, CW>), dim3(grid, groups), dim3(256), 0, s, *a, *b);
+	return hipGetLastError();
+}
+
+template <int INTERP>
+static hipError_t launch_sweep_kind(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s)
+{
+	if (a->complex_data) return a->coherency_weighting ? launch_sweep_one<INTERP, true,  true>(a, b, s) : launch_sweep_one<INTERP, true,  false>(a, b, s);
+	else                 return a->coherency_weighting ? launch_sweep_one<INTERP, false, true>(a, b, s) : launch_sweep_one<INTERP, false, false>(a, b, s);
+}
+
+/* `a` as for bf_launch_das_burst, family READI; b->groups: frame_count validated group ids on the device. */
+extern "C" hipError_t bf_launch_das_readi_sweep(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s)
+{
+	const uint32_t frames = b->burst.frame_count;
+	const uint32_t groups = (frames + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
+	if (a->family != BF_DAS_READI || a->split_shift || a->readi_group_count < 2u || !a->readi_hadamard || !b->groups || frames == 0 || groups > 65535u)
+		return hipErrorInvalidValue;
+	switch (a->interpolation) {
+	case BF_INTERP_NEAREST: return launch_sweep_kind<BF_INTERP_NEAREST>(a, b, s);
+	case BF_INTERP_LINEAR:  return launch_sweep_kind<BF_INTERP_LINEAR>(a, b, s);
+	case BF_INTERP_CUBIC:   return launch_sweep_kind<BF_INTERP_CUBIC>(a, b, s);
 	}
 	return hipErrorInvalidValue;
 }

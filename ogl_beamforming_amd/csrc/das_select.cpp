@@ -970,9 +970,13 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 }
 
 void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const std::vector<DasDecision> &parts,
-                  uint32_t zfirst, uint32_t zcount, uint32_t mode, uint32_t frame_count, BurstDecision &out)
+                  uint32_t zfirst, uint32_t zcount, uint32_t mode, uint32_t frame_count, BurstDecision &out, bool readi_sweep)
 {
 	out = BurstDecision{};
+	out.readi_sweep = readi_sweep;
+	const bool sweep = readi_sweep && main_part(parts).a.family == BF_DAS_READI;      /* the family the sweep kernel exists for */
+	const uint32_t min_frames = sweep ? kReadiSweepMinFrames : kBurstMinFrames;
+	out.min_frames = min_frames;
 	const DasDecision &head = main_part(parts);
 	out.single_path = head.path;
 	/* the ingest and every pre-DAS stage take the burst in one launch; the filters share a grid axis with the channels and take it in
@@ -989,15 +993,15 @@ void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<
 		out.reason = "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared";
 	} else if (mode & 0x400u) {
 		out.reason = "das path flag 0x400: the single-frame kernel once per frame was asked for";
-	} else if (head.a.family != BF_DAS_RCA) {
+	} else if (head.a.family != BF_DAS_RCA && !sweep) {
 		out.reason = "the burst kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per frame";
 	} else if (parts.size() != 1) {
 		out.reason = "the row-end rule cuts the frame into parts run by different kernels: the single-frame launches once per frame";
 	} else if (head.path != DasPath_General) {
 		std::snprintf(text, sizeof(text), "single frames run the %s, which already shares the geometry across its loops: it runs once per frame", das_path_name(head.path));
 		out.reason = text;
-	} else if (frame_count < kBurstMinFrames) {
-		std::snprintf(text, sizeof(text), "fewer than %u frames: the single-frame general kernel", kBurstMinFrames);
+	} else if (frame_count < min_frames) {
+		std::snprintf(text, sizeof(text), "fewer than %u frames: the single-frame general kernel", min_frames);
 		out.reason = text;
 	} else {
 		/* the general kernel's tiles at one thread per voxel: the frames fill the chip, not a channel split */
@@ -1008,7 +1012,8 @@ void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<
 		out.burst_kernel = true;
 		out.frames_per_thread = BF_BURST_FRAMES_PER_THREAD;
 		out.das_launches = 1;
-		std::snprintf(text, sizeof(text), "RCA family on the general kernel: one launch, each thread applies a term's geometry to %u frames", BF_BURST_FRAMES_PER_THREAD);
+		std::snprintf(text, sizeof(text), sweep ? "READI sweep on the general kernel: one launch, each thread applies a term's geometry to %u frames, each with its group's signs"
+		                                        : "RCA family on the general kernel: one launch, each thread applies a term's geometry to %u frames", BF_BURST_FRAMES_PER_THREAD);
 		out.reason = text;
 	}
 }

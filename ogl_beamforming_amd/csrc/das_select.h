@@ -33,6 +33,15 @@ constexpr uint32_t kBurstMinFrames = 5;          /* das_burst.hip takes bursts o
                                                     kernel's channel split launches: slower; four are level; from five on the burst is taken (the
                                                     per-frame DAS route under the same batching: 1.04 / 1.24 at 2, 1.00 / 1.08 at 4, 0.95 / 1.00 at 8) */
 
+constexpr uint32_t kReadiSweepMinFrames = 5;     /* das_readi_burst_kernel (das_burst.hip) takes READI sweeps of this many frames and more: the smallest
+                                                    measured frame count from which the sweep on the kernel is not slower than the sweep on the
+                                                    per-frame route by more than three times that route's run-to-run spread (tools/readi_rate.py,
+                                                    profiles/readi_rate.json).  Wall time per frame of the kernel over the per-frame route, upload
+                                                    included, by N -- G = 4: 5: 0.66, 6: 0.58, 8: 0.46, 16: 0.37, 64: 0.34; G = 8: 5: 0.69, 8: 0.49,
+                                                    16: 0.35, 64: 0.37; G = 16: 5: 0.68, 16: 0.36, 64: 0.35; over N x (parameter push + single push):
+                                                    0.55-0.60 at 5, 0.28-0.32 at 64.  Fewer than 5 frames were not measured on the kernel (the value
+                                                    in force, the burst kernel's, sent them down the per-frame route) */
+
 /* Diagnostic switches (none is needed in production, all default off): set through beamformer_hip_set_hook ONLY -- the library
  * reads no environment variable.  They select among code paths that ship anyway (the range-checked loop every boundary wave takes,
  * the LDS-table form every non-64 x 16 tile takes, ...) so that the tests can aim at each of them.  `version` counts changes:
@@ -98,13 +107,19 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
  * kernel's tiles without the channel split). */
 struct BurstDecision {
 	bool        burst_kernel = false;
+	bool        readi_sweep = false;         /* the push is a READI sweep: burst_kernel names das_readi_burst_kernel */
 	int         single_path = DasPath_General;
 	uint32_t    frames_per_thread = 1, das_launches = 0, stage_launches = 0;
+	uint32_t    min_frames = kBurstMinFrames;   /* the threshold that was applied */
 	std::string reason;
 	BfDasArgs   a{};
 };
+/* readi_sweep: the push is a READI sweep (beamformer_hip_describe_readi_sweep) -- frame k under its own readi_group.  Its kernel,
+ * das_readi_burst_kernel, takes it when `parts` is ONE part on the general kernel, the family is READI, frame_count >=
+ * kReadiSweepMinFrames and mode does not carry BeamformerHipDasPath_NoBurstKernel; else the single-frame launch(es) once per frame,
+ * each with its frame's group.  A plain burst (readi_sweep false) of a READI block never takes a kernel of das_burst.hip. */
 void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const std::vector<DasDecision> &parts,
-                  uint32_t z_first, uint32_t z_count, uint32_t mode, uint32_t frame_count, BurstDecision &out);
+                  uint32_t z_first, uint32_t z_count, uint32_t mode, uint32_t frame_count, BurstDecision &out, bool readi_sweep = false);
 
 /* das_views.hip takes the eligible views of a push when their 256-voxel tiles number at least this.  PROVISIONAL: the smallest tile
  * count at which the views kernel is not slower than the per-view route by more than three times that route's run-to-run spread, to be

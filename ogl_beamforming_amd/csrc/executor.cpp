@@ -474,7 +474,7 @@ static void bind_tables(const PlanState *ps, BfDasArgs &a)
 /* One part of one frame's DAS stage (das_select.h: a frame is one part unless the row-end rule cut it): the kernel `dd` names on the DAS
  * input `cur`, writing the part's planes at `out`.  part_path: the kernel that ran where a missing buffer sent the part to another one. */
 static bool launch_das_part(PlanState *ps, const DasDecision &dd, const void *cur, void *out, uint64_t out_bytes, uint32_t *frame_counters,
-                            hipStream_t s, uint32_t &part_path)
+                            hipStream_t s, uint32_t &part_path, int32_t readi_group = -1)
 {
 	Device &d = *g_context.cur;
 	bool ok = true;
@@ -482,6 +482,7 @@ static bool launch_das_part(PlanState *ps, const DasDecision &dd, const void *cu
 	a.rf  = cur;
 	a.out = out;
 	bind_tables(ps, a);
+	if (readi_group >= 0) a.readi_group = (uint32_t)readi_group;       /* a READI sweep's frame: its only difference from a single push */
 
 	if (dd.path == DasPath_Zero) {
 		ok &= HIP_OK(hipMemsetAsync(a.out, 0, out_bytes, s));
@@ -611,13 +612,13 @@ static bool run_frame(uint32_t block, const void *rf, int64_t rf_bytes, bool ing
 
 /* All parts of one frame's DAS stage: the frame's DAS input at `cur`, its ring slot at `out`.  head_path: the kernel that ran the main part. */
 static bool launch_frame_parts(PlanState *ps, const std::vector<DasDecision> &parts, uint32_t zfirst, uint64_t plane_bytes, const void *cur, char *out,
-                               uint32_t *frame_counters, hipStream_t s, uint32_t &head_path)
+                               uint32_t *frame_counters, hipStream_t s, uint32_t &head_path, int32_t readi_group = -1)
 {
 	const DasDecision &head = main_part(parts);
 	bool ok = true;
 	for (const DasDecision &dd : parts) {
 		uint32_t part_path = (uint32_t)dd.path;
-		ok &= launch_das_part(ps, dd, cur, out + (uint64_t)(dd.z_first - zfirst) * plane_bytes, dd.z_count * plane_bytes, frame_counters, s, part_path);
+		ok &= launch_das_part(ps, dd, cur, out + (uint64_t)(dd.z_first - zfirst) * plane_bytes, dd.z_count * plane_bytes, frame_counters, s, part_path, readi_group);
 		if (&dd == &head && dd.path != DasPath_Zero) head_path = part_path;
 	}
 	return ok;
@@ -650,6 +651,7 @@ struct StageWalk {
 	const BeamformerHipView *views = nullptr;     /* a views push: `frames` is 1 and the DAS stage writes view_count frames from its one input, */
 	uint32_t             view_count = 0;
 	const ViewsDecision *views_route = nullptr;   /* by this route (das_select.h: decide_views) */
+	const uint32_t      *readi_groups = nullptr;  /* a READI sweep: frame k is beamformed with readi_group = readi_groups[k] (validated: lib_api.cpp) */
 };
 
 /* One frame the DAS stage writes: what it reads, where it writes, the parts that compute it (das_select.h) on which grid, whether the
@@ -662,6 +664,7 @@ struct DasJob {
 	const uint32_t *points;
 	bool            fused;
 	uint32_t        path;
+	int32_t         readi_group;    /* >= 0: the job's launches run with this BfDasArgs::readi_group (a READI sweep's frame); -1: the block's */
 };
 
 /* The burst kernel (das_burst.hip): N frames, frame k at k * the strides of input and output, in one launch. */
@@ -673,6 +676,30 @@ static bool launch_burst_kernel(PlanState *ps, const BurstDecision &route, const
 	BfBurstArgs b{};
 	b.frame_count = N; b.rf_stride = in_stride; b.out_stride = out_stride;
 	return HIP_OK(bf_launch_das_burst(&a, &b, s));
+}
+
+/* The READI sweep kernel (das_burst.hip: das_readi_burst_kernel): the burst kernel's launch with the frames' group ids, which go
+ * through pinned memory on the push's stream ahead of it as a views push's table does (the same buffers: push_frames grew them). */
+static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, const uint32_t *groups, uint32_t N,
+                                      uint64_t in_stride, uint64_t out_stride, hipStream_t s)
+{
+	Device &d = *g_context.cur;
+	bool ok = true;
+	if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
+	std::memcpy(d.views_pinned, groups, sizeof(uint32_t) * N);
+	void *mapped = nullptr;
+	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
+	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)(sizeof(uint32_t) * N), s));
+	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
+	ok &= d.views_copy_pending;
+	BfDasArgs a = route.a;
+	a.rf = first.in; a.out = first.out;
+	bind_tables(ps, a);
+	BfReadiSweepArgs b{};
+	b.burst.frame_count = N; b.burst.rf_stride = in_stride; b.burst.out_stride = out_stride;
+	b.groups = (const uint32_t *)d.views_table.ptr;
+	if (ok) ok &= HIP_OK(bf_launch_das_readi_sweep(&a, &b, s));
+	return ok;
 }
 
 /* The views kernel (das_views.hip): the views the route has it take, from the ONE DAS input, in one launch -- their rows and the prefix
@@ -795,6 +822,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 				DasJob &j = jobs[k];
 				j.in  = cur + k * cur_stride;
 				j.out = (char *)d.ring.ptr + d.frames[(first + k) % d.frames.size()].offset;
+				j.readi_group = w.readi_groups ? (int32_t)w.readi_groups[k] : -1;
 				if (w.views) { j.parts = &w.views_route->parts[k]; j.z_first = 0; j.points = w.views[k].output_points; j.fused = w.views_route->taken[k] != 0; }
 				else         { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
 				const DasDecision &head = main_part(*j.parts);
@@ -805,8 +833,9 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			}
 
 			/* ---- 1. the push's fused launch */
-			if (any_fused) ok &= w.views ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
-			                             : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
+			if (any_fused) ok &= w.views        ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
+			                  : w.readi_groups ? launch_readi_sweep_kernel(ps, *w.route, jobs[0], w.readi_groups, N, cur_stride, frame0->bytes, s)
+			                                   : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
 			/* ---- 2. every other job's own launch(es): the kernels of a single push.  One set of counters per timing slot */
 			if (counters_kept && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) ok = false;
 			for (uint32_t k = 0; k < F && ok; k++) {
@@ -818,7 +847,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 					ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
 				}
 				const DasDecision &head = main_part(*j.parts);
-				ok &= launch_frame_parts(ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path);
+				ok &= launch_frame_parts(ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.readi_group);
 			}
 			/* ---- 3. geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is
 			 * the same for every job of a run of jobs with the same parts (a burst: one run; a views push: one per view): it runs once,
@@ -828,6 +857,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 				ok &= d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2));
 				unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
 				for (uint32_t begin = 0, end; begin < F && ok; begin = end) {
+					/* (a READI sweep's jobs differ in their group alone, which only signs the terms: one run, one count) */
 					for (end = begin + 1; end < F && jobs[end].parts == jobs[begin].parts; end++) {}
 					if (F - (end - 1) > kTimingSlots) continue;
 					const DasJob &j = jobs[begin];
@@ -839,6 +869,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 						BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
 						count.rf = j.in; count.out = j.out + (uint64_t)(dd.z_first - j.z_first) * head.a.size[0] * head.a.size[1] * voxel_bytes;
 						bind_tables(ps, count);
+						if (j.readi_group >= 0) count.readi_group = (uint32_t)j.readi_group;
 						count.pair_counter = mine;
 						ok &= HIP_OK(bf_launch_das_count(&count, s));
 					}
@@ -1246,6 +1277,7 @@ struct FramesPush {
 	DeviceBuffer *stage;                     /* the pre-DAS stages' ping-pong pair and, where it holds every RF frame's output, the stride to grow it by */
 	uint64_t      stage_stride;
 	float         decide_us;
+	const uint32_t *readi_groups = nullptr;  /* a READI sweep: rf_frames validated group ids, frame k's readi_group */
 };
 
 /* A push of several frames with ONE upload and ONE event set (one device) -- a burst: N RF frames, N frames; a views push: one RF frame
@@ -1294,7 +1326,8 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 		for (size_t k = 0; k < 2 && k < pre_das_stages; k++) fits = fits && m.stage[k].ensure(m.stage_stride * N);
 	}
 	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
-	if (m.views_route && m.views_route->kernel_views) {
+	if ((m.views_route && m.views_route->kernel_views) || (m.readi_groups && m.burst && m.burst->burst_kernel)) {
+		/* (one size for both users: a sweep's BEAMFORMER_HIP_MAX_BURST_FRAMES group ids are 4 KiB of it) */
 		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
 		fits = fits && d.views_table.ensure(table_bytes);
 		if (fits && !d.views_pinned && !HIP_OK(hipHostMalloc(&d.views_pinned, table_bytes, hipHostMallocDefault))) { d.views_pinned = nullptr; fits = false; }
@@ -1338,7 +1371,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
 	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
 	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_step, (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size), m.stage, m.stage_stride, t,
-	                                                 m.burst, m.views, m.views ? F : 0u, m.views_route});
+	                                                 m.burst, m.views, m.views ? F : 0u, m.views_route, m.readi_groups});
 	finish_upload(u, overlap, s);
 	if (!done) return false;
 
@@ -1380,6 +1413,37 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	                              d.burst_stage, round_up(plan.intermediate_bytes, 64) + 64, 0.0f});
 }
 
+/* beamformer_hip_push_data_readi_sweep_with_compute: a burst of a READI block whose frame k is beamformed with readi_group = groups[k]
+ * (frame_count ids, every one below the block's readi_group_count: lib_api.cpp has checked both).  The route: decide_burst as a sweep.
+ * One RF frame: the single push's buffers, as a views push. */
+bool push_readi_sweep(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ParameterBlock &pb = c.blocks[block];
+	const uint32_t N = frame_count;
+
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const Plan &plan = ps->plan;
+
+	uint32_t zfirst = 0, zcount = plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
+	std::vector<DasDecision> no_parts;
+	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
+	const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
+	BurstDecision route;
+	if (!parts.empty()) decide_burst(pb, plan, ps->transmit_table, parts, zfirst, zcount, c.das_path_mode, N, route, true);
+	else { route.readi_sweep = true; route.min_frames = kReadiSweepMinFrames; route.stage_launches = (N + chunk - 1) / chunk; route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared"; }
+
+	return push_frames(block, ps, l, data, data_on_device,
+	                   FramesPush{PushRecord::Burst, N, frame_size, N, points, nullptr, &route, nullptr, keeps_counters(parts),
+	                              N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0, 0.0f, groups});
+}
+
 /* The record of the newest multi-frame push, when the newest push IS that push, of `kind` and complete: waited for, with its stage
  * kinds and times (hipEvent pairs around each stage of the WHOLE push; total: first event to last).  Else null, InvalidAccess. */
 static const PushRecord *newest_push(PushRecord::Kind kind, uint32_t &first_id, uint32_t &count, uint32_t &stage_count, uint32_t *stage_kind,
@@ -1415,7 +1479,7 @@ bool last_burst_info(BeamformerHipBurstInfo *out)
 	const BurstDecision &b = r->burst;
 	out->route.burst_kernel = b.burst_kernel; out->route.single_path = b.single_path == DasPath_Zero ? -2 : b.single_path;
 	out->route.frames_per_thread = b.frames_per_thread; out->route.das_launches = b.das_launches;
-	out->route.stage_launches = b.stage_launches; out->route.min_frames = kBurstMinFrames;
+	out->route.stage_launches = b.stage_launches; out->route.min_frames = b.min_frames;
 	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.reason.c_str());
 	return true;
 }

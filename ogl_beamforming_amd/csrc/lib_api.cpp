@@ -159,6 +159,49 @@ bool push_burst_common(const void *data, uint32_t frame_size, uint32_t frame_cou
 	return push_burst(slot, data, frame_size, frame_count, on_device);
 }
 
+/* A READI sweep's block and group list, no device needed: the block beamforms READI (FORCES / UFORCES with readi_group_count > 1), else
+ * InvalidAccess with a line on stderr; every group id is below readi_group_count, else InvalidComputeStage -- what a single push of a
+ * block with that readi_group gets (the planner refuses the block: planner.cpp).  `out`: the frame_count ids, groups == null:
+ * (block.readi_group + k) % readi_group_count. */
+bool resolve_readi_groups(uint32_t slot, const uint32_t *groups, uint32_t frame_count, std::vector<uint32_t> &out)
+{
+	Context &c = ctx();
+	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES && frame_count <= BeamformerMaxBacklogFrames,
+	           BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
+	const BeamformerParameters &bp = c.blocks[slot].parameters;
+	const bool forces = bp.acquisition_kind == BeamformerAcquisitionKind_FORCES || bp.acquisition_kind == BeamformerAcquisitionKind_UFORCES;
+	if (!forces || bp.readi_group_count <= 1) {
+		std::fprintf(stderr, "[beamformer] a READI sweep needs a FORCES / UFORCES block with readi_group_count > 1: refused (acquisition kind %d, readi_group_count %u)\n",
+		             (int)bp.acquisition_kind, bp.readi_group_count);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	const uint32_t G = bp.readi_group_count;
+	out.resize(frame_count);
+	for (uint32_t k = 0; k < frame_count; k++) {
+		out[k] = groups ? groups[k] : (uint32_t)(((uint64_t)bp.readi_group + k) % G);
+		if (!check(out[k] < G, BeamformerLibErrorKind_InvalidComputeStage)) return false;
+	}
+	return true;
+}
+
+/* A READI sweep: the burst's checks and the list's, all before the device is touched; frame_count == 1 goes the same way. */
+bool push_readi_sweep_common(const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, uint32_t image_plane_tag, uint32_t slot,
+                             bool on_device)
+{
+	Context &c = ctx();
+	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES && frame_count <= BeamformerMaxBacklogFrames,
+	           BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
+	std::vector<uint32_t> ids;
+	if (!resolve_readi_groups(slot, groups, frame_count, ids)) return false;
+	if (!on_one_device("READI sweep")) return false;
+	if (!valid_rf_frame(c.blocks[slot], data, frame_size)) return false;
+	if (!run_fits_the_ring(c.blocks[slot], nullptr, frame_count)) return false;
+	if (!ensure_device()) return false;
+	return push_readi_sweep(slot, data, frame_size, frame_count, ids.data(), on_device);
+}
+
 /* What a views call must satisfy that needs neither the RF nor a device: the count, the list, the block, every view's tag and extents. */
 bool validate_views(const BeamformerHipView *views, uint32_t view_count, uint32_t slot)
 {
@@ -549,16 +592,16 @@ uint32_t beamformer_hip_push_device_data_burst_with_compute(const void *device_d
 	return push_burst_common(device_data, frame_size, frame_count, image_plane_tag, parameter_slot, true);
 }
 
-uint32_t beamformer_hip_describe_burst(uint32_t parameter_slot, uint32_t frame_count, BeamformerHipBurstDescription *out)
+/* beamformer_hip_describe_burst, and -- readi_sweep -- beamformer_hip_describe_readi_sweep once the block and the list have passed */
+static uint32_t describe_burst_route(uint32_t parameter_slot, uint32_t frame_count, BeamformerHipBurstDescription *out, bool readi_sweep)
 {
-	if (!valid_parameter_block(parameter_slot) || !check(out != nullptr && frame_count != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
 	Context &c = ctx();
 	const ParameterBlock &pb = c.blocks[parameter_slot];
 	Plan plan;
 	std::string error;
 	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
 	std::memset(out, 0, sizeof(*out));
-	out->min_frames = kBurstMinFrames;
+	out->min_frames = readi_sweep ? kReadiSweepMinFrames : kBurstMinFrames;
 	out->frames_per_thread = 1; out->stage_launches = (frame_count + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels);
 	if (plan.das_index < 0) {
 		out->single_path = -1;
@@ -571,10 +614,47 @@ uint32_t beamformer_hip_describe_burst(uint32_t parameter_slot, uint32_t frame_c
 	std::vector<DasDecision> parts;
 	decide_das_parts(pb, plan, transmits, zfirst, zcount, c.das_path_mode, parts);
 	BurstDecision b;
-	decide_burst(pb, plan, transmits, parts, zfirst, zcount, c.das_path_mode, frame_count, b);
+	decide_burst(pb, plan, transmits, parts, zfirst, zcount, c.das_path_mode, frame_count, b, readi_sweep);
+	out->min_frames = b.min_frames;
 	out->burst_kernel = b.burst_kernel; out->single_path = b.single_path == DasPath_Zero ? -2 : b.single_path;
 	out->frames_per_thread = b.frames_per_thread; out->das_launches = b.das_launches; out->stage_launches = b.stage_launches;
 	std::snprintf(out->reason, sizeof(out->reason), "%s", b.reason.c_str());
+	return 1;
+}
+
+uint32_t beamformer_hip_describe_burst(uint32_t parameter_slot, uint32_t frame_count, BeamformerHipBurstDescription *out)
+{
+	if (!valid_parameter_block(parameter_slot) || !check(out != nullptr && frame_count != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return describe_burst_route(parameter_slot, frame_count, out, false);
+}
+
+uint32_t beamformer_hip_push_data_readi_sweep_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                           const uint32_t *readi_groups, uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_readi_sweep_common(data, frame_size, frame_count, readi_groups, image_plane_tag, parameter_slot, false);
+}
+
+uint32_t beamformer_hip_push_device_data_readi_sweep_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                  const uint32_t *readi_groups, uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_readi_sweep_common(device_data, frame_size, frame_count, readi_groups, image_plane_tag, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_describe_readi_sweep(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count,
+                                             BeamformerHipBurstDescription *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	std::vector<uint32_t> ids;
+	if (!resolve_readi_groups(parameter_slot, readi_groups, frame_count, ids)) return 0;
+	return describe_burst_route(parameter_slot, frame_count, out, true);
+}
+
+uint32_t beamformer_hip_resolve_readi_groups(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count, uint32_t *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	std::vector<uint32_t> ids;
+	if (!resolve_readi_groups(parameter_slot, readi_groups, frame_count, ids)) return 0;
+	std::memcpy(out, ids.data(), sizeof(uint32_t) * frame_count);
 	return 1;
 }
 

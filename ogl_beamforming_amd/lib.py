@@ -106,6 +106,10 @@ def _load():
         "beamformer_hip_push_device_data_burst_with_compute": (u32, [vp, u32, u32, u32, u32]),
         "beamformer_hip_describe_burst": (u32, [u32, u32, C.POINTER(P.HipBurstDescription)]),
         "beamformer_hip_get_last_burst_info": (u32, [C.POINTER(P.HipBurstInfo)]),
+        "beamformer_hip_push_data_readi_sweep_with_compute": (u32, [vp, u32, u32, C.POINTER(u32), u32, u32]),
+        "beamformer_hip_push_device_data_readi_sweep_with_compute": (u32, [vp, u32, u32, C.POINTER(u32), u32, u32]),
+        "beamformer_hip_describe_readi_sweep": (u32, [u32, C.POINTER(u32), u32, C.POINTER(P.HipBurstDescription)]),
+        "beamformer_hip_resolve_readi_groups": (u32, [u32, C.POINTER(u32), u32, C.POINTER(u32)]),
         "beamformer_hip_push_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
         "beamformer_hip_push_device_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
         "beamformer_hip_describe_views": (u32, [u32, C.POINTER(P.HipView), u32, C.POINTER(P.HipViewsDescription)]),
@@ -253,6 +257,51 @@ def last_burst_info():
     info = P.HipBurstInfo()
     _check(library().beamformer_hip_get_last_burst_info(C.byref(info)))
     return info
+
+
+def _group_array(groups):
+    """A READI sweep's group list as the C ABI takes it: None -> NULL."""
+    if groups is None:
+        return None
+    groups = [int(g) for g in groups]
+    return (C.c_uint32 * len(groups))(*groups)
+
+
+def beamform_readi_sweep(bp, rf_frames, groups=None, filters=(), timeout_ms=-1, on_device_pointer=None):
+    """The group acquisitions of a READI sequence in one call (beamformer_hip_push_data_readi_sweep_with_compute): `rf_frames` as
+    beamform_burst() takes it, frame k beamformed with readi_group = groups[k]; groups None: (bp.readi_group + k) % readi_group_count.
+    Returns (N, Z, Y, X), oldest first."""
+    lib = _prepared(bp, filters, timeout_ms)
+    rf_frames = np.ascontiguousarray(rf_frames)
+    count = rf_frames.shape[0]
+    assert groups is None or len(groups) == count
+    frame_size = rf_frames.nbytes // count
+    if on_device_pointer is not None:
+        _check(lib.beamformer_hip_push_device_data_readi_sweep_with_compute(C.c_void_p(on_device_pointer), frame_size, count, _group_array(groups), 0, 0))
+    else:
+        _check(lib.beamformer_hip_push_data_readi_sweep_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, count, _group_array(groups), 0, 0))
+    return get_last_frames(bp, count)
+
+
+def describe_readi_sweep(bp, n, groups=None, filters=(), slot=0):
+    """What a READI sweep of n frames of these parameters would run (beamformer_hip_describe_readi_sweep): the description struct;
+    .reason says why.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    d = P.HipBurstDescription()
+    _check(L.beamformer_hip_describe_readi_sweep(slot, _group_array(groups), n, C.byref(d)))
+    return d
+
+
+def resolve_readi_groups(bp, n, groups=None, slot=0):
+    """The group of every frame of such a sweep, as the push resolves the list (beamformer_hip_resolve_readi_groups).  Needs no device."""
+    L = library()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    out = (C.c_uint32 * n)()
+    _check(L.beamformer_hip_resolve_readi_groups(slot, _group_array(groups), n, out))
+    return list(out)
 
 
 def view(points, lo, hi, plane=None, plane_offset=0.0, tag=0):
