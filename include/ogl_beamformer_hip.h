@@ -206,6 +206,69 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_readi_sweep(uint32_t para
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_resolve_readi_groups(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count,
                                                                    uint32_t *out);
 
+/* ---- READI image: the N group acquisitions of a READI sequence compounded into ONE frame per call ----
+ * The input is a READI sweep's exactly (above): frame_count RF frames back to back under the single push's layout and size rules,
+ * readi_groups[k] the group of frame k, NULL meaning (block.readi_group + k) % readi_group_count.  The push queues ONE frame, with one
+ * frame id.  DEFINITION of that frame: READI_FORCES is FORCES with transmit element tx_group * acquisition_count + tx_event and every
+ * term multiplied by Hadamard[readi_group * G + tx_group] (shaders/das.glsl:288-366), and interpolation, IQ rotation, apodization and
+ * accumulation are linear in the samples.  The image is therefore the frame a single push would give for the DERIVED BLOCK on the
+ * DECODED ACQUISITION D:
+ *     derived block   the same block with acquisition_kind = FORCES, acquisition_count = readi_group_count x acquisition_count, READI
+ *                     off (UFORCES blocks with readi_group_count > 1 ignore sparse_elements in the shader: their derived block is the
+ *                     same non-sparse FORCES block);
+ *     D               D[channel][t * A + event][sample] = sum over k of H[g_k][t] * x_k[channel][event][sample], t < G, where x_k is
+ *                     the DAS INPUT of RF frame k -- the decode takes place after every pre-DAS stage -- and the sum is float32,
+ *                     k = 0, 1, ... frame_count - 1 in that order (csrc/readi_decode.hip).
+ * It does G times less DAS work than the sweep (C x G x A terms a voxel instead of N x C x G x A) and needs no DAS arithmetic of its
+ * own.  The list need not cover every group: an omitted group contributes nothing, a repeated one counts twice.  frame_count == 1 is
+ * valid.
+ *   - WITHOUT coherency weighting the image is the sum of the sweep's frame_count frames to within float rounding.
+ *   - WITH coherency_weighting set the weighting is taken over ALL terms of the image -- FORCES' epilogue on D: (sum of all terms)
+ *     x |sum of all terms| / (sum of every term's magnitude).  This is NOT the sum of separately weighted partial frames, which weights
+ *     each acquisition by its own coherence; a caller who wants that sums the sweep's frames.
+ *   - refusals, all before a device is touched and before an id is taken (a refused push queues nothing): a block that is not READI
+ *     (kind other than FORCES / UFORCES, or readi_group_count <= 1) InvalidAccess with a line on stderr; a list entry >=
+ *     readi_group_count InvalidComputeStage; frame_count == 0 or > BEAMFORMER_HIP_MAX_BURST_FRAMES BufferOverflow; readi_group_count x
+ *     acquisition_count > BeamformerMaxEmissionsCount InvalidAccess with a line on stderr; a decoded input of 4 GiB or more, or memory
+ *     that cannot be grown, RFDataSizeOverflow; a frame larger than the frame ring FrameSizeOverflow; several devices InvalidAccess.
+ *     A push that fails after its id is taken leaves a tombstone under it;
+ *   - one upload and one RF-ring slot; the ingest and every pre-DAS stage ONCE for all RF frames, as for a sweep; then the decode; then
+ *     the derived block's own single-frame DAS launch(es) -- its own decision (beamformer_hip_describe_das of the derived block), row-end
+ *     rule included.  An output shard is honoured; frame graphs: direct launches; pair counting counts on the derived block;
+ *   - the stage list of the push (beamformer_hip_get_last_readi_image_info, the frame's timing row) holds the across-acquisition
+ *     decode as one extra entry of kind BeamformerShaderKind_Decode directly before DAS;
+ *   - beamformer_hip_copy_das_input after an image push returns D, [channel][G x A][das_samples];
+ *     beamformer_hip_copy_das_input_frame(k) for k < frame_count returns x_k, what the decode read;
+ *   - beamformer_hip_get_last_burst_info and beamformer_hip_get_last_views_info refuse an image push. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_data_readi_image_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                                                 const uint32_t *readi_groups, uint32_t image_plane_tag,
+                                                                                 uint32_t parameter_slot);
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_device_data_readi_image_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                                        const uint32_t *readi_groups, uint32_t image_plane_tag,
+                                                                                        uint32_t parameter_slot);
+typedef struct {
+	uint32_t transmit_count;        /* the derived block's acquisition_count: readi_group_count x acquisition_count */
+	int32_t  das_path;              /* the derived block's own DAS decision (BeamformerHipDasDescription::path numbering, -1 / -2 included) */
+	uint32_t das_launches;          /* DAS launches of the push: the derived block's single-frame launches, once */
+	uint32_t stage_launches;        /* launches the push takes of a pre-DAS filter stage (BeamformerHipBurstDescription::stage_launches) */
+	uint32_t decode_launches;       /* launches of the across-acquisition decode: 1 (0: no DAS kernel runs) */
+	char     reason[160];
+} BeamformerHipReadiImageDescription;
+/* What an image push of frame_count RF frames would run, under the current das path mode; the block, the list and the count are judged
+ * as the push judges them.  Needs no device. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_readi_image(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count,
+                                                                   BeamformerHipReadiImageDescription *out);
+typedef struct {
+	BeamformerHipReadiImageDescription route;   /* of the push that ran */
+	uint32_t frame_id, rf_frame_count;
+	uint32_t stage_count;
+	uint32_t stage_kind[BEAMFORMER_HIP_MAX_TIMED_STAGES];  /* BeamformerShaderKind; ingest = 0xFFFF; the across-acquisition decode: Decode, directly before DAS */
+	float    stage_ms[BEAMFORMER_HIP_MAX_TIMED_STAGES];    /* hipEvent pairs around each stage of the WHOLE push */
+	float    image_ms;                                     /* first event to last event */
+} BeamformerHipReadiImageInfo;
+/* The newest image push; waits for it to finish.  Fails when the newest push was not an image push or did not complete. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_readi_image_info(BeamformerHipReadiImageInfo *out);
+
 /* ---- views: ONE RF frame beamformed on K voxel grids per call (live X-plane / tri-plane imaging: the reference's 3DXPlane view;
  * ULM patch refinement: tens to hundreds of small fine grids around detections, all from the RF of one push) ----
  * `data` is one RF frame under exactly the layout and size rules of beamformer_push_data_with_compute.  Everything except the grid
@@ -321,12 +384,14 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_sum_last_frames(uint32_t count, vo
 /* Copy of the buffer the newest frame's DAS stage read -- the RF slot when no stage runs before DAS, else the last pre-DAS
  * stage's output -- to host memory: [channel][transmit][sample], channel_count x acquisition_count x das_samples elements
  * (BeamformerHipPlan), f32 or f32 complex as the plan says (iq_pipeline).  Valid until the next push.  Returns 0 when size
- * differs from that, when there is no such frame, or with several devices (beamformer_hip_set_devices). */
+ * differs from that, when there is no such frame, or with several devices (beamformer_hip_set_devices).  After a READI image push
+ * the buffer its DAS stage read is the one decoded across the acquisitions: channel_count x (readi_group_count x acquisition_count) x
+ * das_samples elements, and `size` is judged against that. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_copy_das_input(void *out, uint64_t size);
 
 /* The same for RF frame `frame` of the newest push: a burst's frame `frame` (0: its oldest), each frame of the layout and size above;
  * a single push and a views push hold one RF frame, frame 0.  beamformer_hip_copy_das_input serves the newest frame: after a burst its
- * last one.  Valid until the next push.  Returns 0 (InvalidAccess) when frame is not below the push's RF frame count, and where
+ * last one; after a READI image push frame k is what the decode read for RF frame k.  Valid until the next push.  Returns 0 (InvalidAccess) when frame is not below the push's RF frame count, and where
  * beamformer_hip_copy_das_input does. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_copy_das_input_frame(uint32_t frame, void *out, uint64_t size);
 

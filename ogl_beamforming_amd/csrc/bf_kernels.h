@@ -86,6 +86,19 @@ typedef struct {
 	const uint32_t *groups;           /* [burst.frame_count], device */
 } BfReadiSweepArgs;
 
+/* READI image (readi_decode.hip: readi_image_decode_kernel): the DAS inputs of `frames` group acquisitions, frame k in_frame_bytes behind
+ * frame k - 1, each [channel][slab_floats] float32 (a slab: [acquisition][sample], complex samples as pairs of floats), decoded into
+ * out[channel][t][slab_floats], t < group_count: out[c][t] = sum over k, in that order, of H[groups[k]][t] * in_k[c].  The ids are
+ * validated on the host (all below group_count); the kernel trusts them. */
+typedef struct {
+	const void     *in;
+	void           *out;
+	const uint32_t *groups;           /* [frames], device */
+	const uint32_t *hadamard;         /* group_count^2 entries of +-1 as binary16 (row g entry t at g * group_count + t), read two to a word */
+	uint64_t        in_frame_bytes, slab_floats;
+	uint32_t        frames, group_count, channels, pad;
+} BfReadiDecodeArgs;
+
 /* views form of the general kernel (das_views.hip): one DAS input beamformed on several grids by one launch.  A row holds what differs
  * from view to view; everything else is the launch's BfDasArgs.  128 bytes, read through wave-uniform (scalar) loads. */
 typedef struct {
@@ -327,6 +340,7 @@ hipError_t bf_launch_das(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_count(const BfDasArgs *a, hipStream_t s);
 hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s);   /* das_burst.hip: RCA family, `a` without a channel split */
 hipError_t bf_launch_das_readi_sweep(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s);   /* das_burst.hip: READI, `a` without a channel split */
+hipError_t bf_launch_readi_image_decode(const BfReadiDecodeArgs *a, hipStream_t s);   /* readi_decode.hip */
 hipError_t bf_launch_views_table(void *dst, const void *src, uint32_t bytes, hipStream_t s);   /* das_views.hip: bytes (a multiple of 4) from mapped pinned memory into the device table */
 hipError_t bf_launch_das_views(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s);   /* das_views.hip: RCA family, no channel split */
 hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);

@@ -68,11 +68,13 @@ struct TimingSlot {
 
 /* the newest multi-frame push (executor.cpp push_frames): what beamformer_hip_get_last_burst_info / _views_info report, each of its own kind */
 struct PushRecord {
-	enum Kind { None, Burst, Views } kind = None;
+	enum Kind { None, Burst, Views, Image } kind = None;
 	uint64_t      first_id = 0;
 	uint32_t      count = 0, events_slot = 0;
 	BurstDecision burst;                      /* Burst: its route */
 	BeamformerHipViewsDescription views{};    /* Views: its route, and the host time spent deciding it */
+	ReadiImageDecision image;                 /* Image: its route, and the RF frames it compounded */
+	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
 };
 
@@ -89,6 +91,14 @@ struct PlanState {
 	std::vector<DasDecision> das_parts;   /* the DAS kernel(s) and geometry of this plan's frames (das_select.cpp: decide_das_parts), reused until
 	                                         the plan, the shard, the path mode or a hook changes */
 	uint32_t     das_z_first = 0, das_z_count = 0;
+};
+
+/* A READI image push's derived block (das_select.h: derive_readi_image) on one device: its plan state -- the transmit table of its
+ * G x A transmits, the DAS decision -- kept with the block's own plan state and rebuilt when that one is (source_generation). */
+struct ImagePlanState {
+	PlanState      ps;
+	ParameterBlock pb;
+	uint64_t       source_generation = 0;
 };
 
 constexpr uint32_t kTimingSlots = 32;    /* beamformer_compute_stats.c: 32-frame table */
@@ -122,6 +132,7 @@ struct Device {
 	uint32_t     index = 0;                                    /* position in Context::devices */
 	hipStream_t  own_stream = nullptr, stream = nullptr;
 	PlanState    plans[BeamformerMaxParameterBlocks];
+	ImagePlanState image_plans[BeamformerMaxParameterBlocks];  /* READI image pushes: the derived FORCES block of plans[k] */
 	DeviceBuffer raw_staging[BeamformerMaxRawDataFramesInFlight];
 	UploadSlot   upload[BeamformerMaxRawDataFramesInFlight];
 	hipStream_t  copy_stream = nullptr;                        /* H2D of frame n+1 overlaps compute of frame n */
@@ -139,7 +150,8 @@ struct Device {
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
 	DeviceBuffer burst_stage[2];                               /* a burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
 	PushRecord   multi;
-	DeviceBuffer views_table;                                  /* a views push: the BfViewRows and the prefix table das_views.hip reads; a READI sweep: its frames' group ids */
+	DeviceBuffer readi_decoded;                                /* a READI image push: the DAS input decoded across its acquisitions (readi_decode.hip), 64 spare bytes behind it */
+	DeviceBuffer views_table;                                  /* a views push: the BfViewRows and the prefix table das_views.hip reads; a READI sweep, a READI image push: the frames' group ids */
 	void        *views_pinned = nullptr;                       /* ... and the pinned memory they are sent from, free again once views_copied has passed */
 	hipEvent_t   views_copied = nullptr;
 	bool         views_copy_pending = false;
@@ -167,6 +179,8 @@ struct Device {
 	                                                              a views push's one input: stride 0) -- beamformer_hip_copy_das_input_frame */
 	uint64_t     das_input_bytes = 0, das_input_stride = 0;
 	uint32_t     das_input_frames = 0;
+	uint64_t     das_decoded_bytes = 0;                        /* a READI image push: readi_decoded holds this many bytes of decoded DAS input, what
+	                                                              beamformer_hip_copy_das_input serves (0: any other push) */
 	/* frame graphs (beamformer_hip_enable_frame_graphs): one instantiated hipGraph per parameter block, updated
 	 * in place from each frame's capture; graph_generation = the plan generation it was warmed up for */
 	hipGraphExec_t frame_exec[BeamformerMaxParameterBlocks]{};
@@ -210,6 +224,9 @@ uint64_t default_frame_ring_bytes();
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device);
 bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device);
 bool push_readi_sweep(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);
+bool push_readi_image(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);
+bool last_readi_image_info(BeamformerHipReadiImageInfo *out);
+void describe_readi_image_decision(const ReadiImageDecision &route, BeamformerHipReadiImageDescription *out);
 bool last_burst_info(BeamformerHipBurstInfo *out);
 bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device);
 bool last_views_info(BeamformerHipViewsInfo *out);

@@ -1018,6 +1018,40 @@ void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<
 	}
 }
 
+void derive_readi_image(const ParameterBlock &pb, const Plan &plan, ParameterBlock &derived_pb, Plan &derived_plan)
+{
+	derived_pb = pb;
+	BeamformerParameters &bp = derived_pb.parameters;
+	bp.acquisition_kind  = BeamformerAcquisitionKind_FORCES;
+	bp.acquisition_count = pb.parameters.readi_group_count * pb.parameters.acquisition_count;
+	bp.readi_group_count = 0; bp.readi_group = 0;
+	derived_plan = plan;
+	derived_plan.acquisitions = bp.acquisition_count;
+	derived_plan.das_sparse = false;
+	derived_plan.readi_hadamard.clear();
+}
+
+void decide_readi_image(const Plan &derived_plan, const std::vector<DasDecision> &parts, uint32_t group_count, uint32_t frame_count, ReadiImageDecision &out)
+{
+	out = ReadiImageDecision{};
+	out.transmit_count = derived_plan.acquisitions;
+	const uint32_t chunk = bf_stage_frame_chunk(derived_plan.channels);
+	out.stage_launches = (frame_count + chunk - 1) / chunk;
+	if (parts.empty()) { out.reason = "no DAS stage runs: the frame is cleared"; return; }
+	const DasDecision &head = main_part(parts);
+	out.path = head.path;
+	for (const DasDecision &d : parts) out.das_launches += d.path != DasPath_Zero;
+	char text[160];
+	if (head.path == DasPath_Zero) {
+		out.reason = "interpolation mode the shader leaves at zero: the frame is cleared";
+	} else {
+		out.decode_launches = 1;
+		std::snprintf(text, sizeof(text), "READI image: %u acquisitions decoded across %u groups into %u FORCES transmits, one pass of the %s",
+		              frame_count, group_count, out.transmit_count, das_path_name(head.path));
+		out.reason = text;
+	}
+}
+
 void plan_on_view(const ParameterBlock &pb, const ViewGrid &view, Plan &plan)
 {
 	const BeamformerParameters &bp = pb.parameters;

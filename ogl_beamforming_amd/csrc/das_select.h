@@ -151,6 +151,23 @@ struct ViewsDecision {
 void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const ViewGrid *views, uint32_t view_count,
                   uint32_t mode, ViewsDecision &out);
 
+/* READI image (beamformer_hip_push_data_readi_image_with_compute).  READI_FORCES is FORCES with transmit element
+ * tx_group * acquisition_count + tx_event and every term signed by Hadamard[readi_group * G + tx_group] (das.glsl:288-366), and everything
+ * behind the sign is linear in the samples: the sum of a sequence's partial frames is ONE frame of the DERIVED block -- the same block with
+ * acquisition_kind FORCES, acquisition_count G x A, READI off, not sparse (the shader's READI branch ignores sparse_elements) -- on the
+ * DAS input decoded across the acquisitions (readi_decode.hip).  derive_readi_image gives that block and its plan: the block's own
+ * resolved plan -- das_samples, sampling frequency, time offset, IQ pipeline, grid, voxel transform and stages as they are -- changed only
+ * in the acquisition count and the family.  `pb` is a READI block with G x A <= BeamformerMaxEmissionsCount (lib_api.cpp has checked). */
+void derive_readi_image(const ParameterBlock &pb, const Plan &plan, ParameterBlock &derived_pb, Plan &derived_plan);
+/* How an image push of frame_count RF frames runs, `parts` being decide_das_parts of the derived block: the decode in one launch, then
+ * the derived block's single-frame launch(es), once. */
+struct ReadiImageDecision {
+	uint32_t    transmit_count = 0, das_launches = 0, stage_launches = 0, decode_launches = 0;
+	int         path = -1;            /* the derived block's main part (DasPath); -1: no DAS stage */
+	std::string reason;
+};
+void decide_readi_image(const Plan &derived_plan, const std::vector<DasDecision> &parts, uint32_t group_count, uint32_t frame_count, ReadiImageDecision &out);
+
 /* planes of `parts` that took the fallback */
 uint32_t row_end_planes(const std::vector<DasDecision> &parts);
 /* the part with the most planes (what a frame "ran on" in one word) */

@@ -180,6 +180,8 @@ static void release_one_device(Device &d)
 	for (auto &b : d.scratch) b.release();
 	d.ring.release(); d.pair_counter.release(); d.minmax_scratch.release(); d.sum_scratch.release();
 	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.multi = PushRecord{};
+	for (auto &ip : d.image_plans) { ip.ps.transmits.release(); ip.ps.sparse.release(); ip.ps.valid = false; ip.ps.das_parts.clear(); }
+	d.readi_decoded.release(); d.das_decoded_bytes = 0;
 	d.views_table.release();
 	if (d.views_pinned) (void)hipHostFree(d.views_pinned);
 	if (d.views_copied) (void)hipEventDestroy(d.views_copied);
@@ -298,6 +300,28 @@ static PlanState *commit_block(uint32_t block)
 	ps.generation++;
 	ps.das_parts.clear();
 	return &ps;
+}
+
+/* The derived block of a READI image push (das_select.h: derive_readi_image) beside the block's own plan state `ps`: its plan, the
+ * transmit table of its G x A transmits on the device, and -- filled by frame_das_parts -- its own DAS decision.  Rebuilt when the block
+ * has been replanned since (a dirtied block drops it with its plan). */
+static ImagePlanState *commit_image_plan(uint32_t block, PlanState *ps)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ImagePlanState &ip = d.image_plans[block];
+	if (ip.ps.valid && ip.source_generation == ps->generation) return &ip;
+	hipStream_t s = d.stream;
+	(void)hipStreamSynchronize(s);          /* as commit_block: an earlier frame may still read the tables */
+	derive_readi_image(c.blocks[block], ps->plan, ip.pb, ip.ps.plan);
+	ip.ps.transmit_table = build_transmit_table(ip.pb);
+	bool ok = upload(ip.ps.transmits, ip.ps.transmit_table.data(), sizeof(BfTransmit) * ip.ps.transmit_table.size(), s);
+	ok &= upload(ip.ps.sparse, ip.pb.sparse_elements, sizeof(ip.pb.sparse_elements), s);
+	ok &= HIP_OK(hipStreamSynchronize(s));
+	ip.ps.das_parts.clear();
+	ip.ps.generation = ip.source_generation = ps->generation;
+	ip.ps.valid = ok;
+	return ok ? &ip : nullptr;
 }
 
 /* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: all of
@@ -652,6 +676,8 @@ struct StageWalk {
 	uint32_t             view_count = 0;
 	const ViewsDecision *views_route = nullptr;   /* by this route (das_select.h: decide_views) */
 	const uint32_t      *readi_groups = nullptr;  /* a READI sweep: frame k is beamformed with readi_group = readi_groups[k] (validated: lib_api.cpp) */
+	ImagePlanState      *image = nullptr;         /* a READI image push: the `frames` DAS inputs are decoded across the acquisitions by readi_groups
+	                                                 (readi_decode.hip) and the DAS stage writes ONE frame from that, under this derived block */
 };
 
 /* One frame the DAS stage writes: what it reads, where it writes, the parts that compute it (das_select.h) on which grid, whether the
@@ -678,10 +704,9 @@ static bool launch_burst_kernel(PlanState *ps, const BurstDecision &route, const
 	return HIP_OK(bf_launch_das_burst(&a, &b, s));
 }
 
-/* The READI sweep kernel (das_burst.hip: das_readi_burst_kernel): the burst kernel's launch with the frames' group ids, which go
- * through pinned memory on the push's stream ahead of it as a views push's table does (the same buffers: push_frames grew them). */
-static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, const uint32_t *groups, uint32_t N,
-                                      uint64_t in_stride, uint64_t out_stride, hipStream_t s)
+/* The group ids of a READI sweep's or a READI image push's frames into d.views_table: through pinned memory on the push's stream, as a
+ * views push's table goes (the same buffers: push_frames grew them). */
+static bool upload_group_ids(const uint32_t *groups, uint32_t N, hipStream_t s)
 {
 	Device &d = *g_context.cur;
 	bool ok = true;
@@ -691,7 +716,15 @@ static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route,
 	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
 	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)(sizeof(uint32_t) * N), s));
 	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
-	ok &= d.views_copy_pending;
+	return ok && d.views_copy_pending;
+}
+
+/* The READI sweep kernel (das_burst.hip: das_readi_burst_kernel): the burst kernel's launch with the frames' group ids ahead of it. */
+static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, const uint32_t *groups, uint32_t N,
+                                      uint64_t in_stride, uint64_t out_stride, hipStream_t s)
+{
+	Device &d = *g_context.cur;
+	bool ok = upload_group_ids(groups, N, s);
 	BfDasArgs a = route.a;
 	a.rf = first.in; a.out = first.out;
 	bind_tables(ps, a);
@@ -735,6 +768,24 @@ static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const
 	return ok;
 }
 
+/* The READI image's decode across acquisitions (readi_decode.hip): the N DAS inputs at `in`, in_stride bytes apart, each
+ * [channel][A][samples], into d.readi_decoded as [channel][G x A][samples] by the signs of the block's own READI matrix (ps: the
+ * block's plan state -- the table the block's READI kernels read). */
+static bool launch_image_decode(PlanState *ps, const BeamformerParameters &bp, const void *in, uint64_t in_stride, const uint32_t *groups, uint32_t N, hipStream_t s)
+{
+	Device &d = *g_context.cur;
+	const Plan &plan = ps->plan;
+	bool ok = upload_group_ids(groups, N, s);
+	BfReadiDecodeArgs a{};
+	a.in = in; a.out = d.readi_decoded.ptr;
+	a.groups   = (const uint32_t *)d.views_table.ptr;
+	a.hadamard = (const uint32_t *)ps->readi_hadamard.ptr;
+	a.in_frame_bytes = in_stride;
+	a.slab_floats = (uint64_t)plan.acquisitions * plan.das_samples * (plan.iq_pipeline ? 2u : 1u);
+	a.frames = N; a.group_count = bp.readi_group_count; a.channels = plan.channels;
+	return ok && HIP_OK(bf_launch_readi_image_decode(&a, s));
+}
+
 /* a frame's parts keep the per-frame counters: [0] staged window violations, [1] / [2] das_tile.hip's staged / gathered chunks */
 static bool keeps_counters(const std::vector<DasDecision> &parts)
 {
@@ -756,14 +807,15 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	hipStream_t s = d.stream;
 	TimingSlot &t = w.t;
 	const uint32_t N = w.frames;
-	const uint32_t F = w.views ? w.view_count : N;          /* frames the walk queues */
+	const uint32_t F = w.views ? w.view_count : w.image ? 1u : N;          /* frames the walk queues */
+	PlanState *das_ps = w.image ? &w.image->ps : ps;        /* whose tables and decision the DAS launches run with */
 
 	const char *cur = (const char *)w.in;
 	uint64_t cur_stride = w.in_stride;
 	int64_t  cur_bound = w.in_bound;
 	int toggle = 0;
 	bool ok = true;
-	d.das_input = nullptr; d.das_input_bytes = d.das_input_stride = 0; d.das_input_frames = 0;
+	d.das_input = nullptr; d.das_input_bytes = d.das_input_stride = 0; d.das_input_frames = 0; d.das_decoded_bytes = 0;
 
 	uint32_t zfirst = 0, zcount = plan.output_points[2];
 	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
@@ -816,13 +868,23 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			 * concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
 			if (F > 1) many.resize(F);
 			jobs = F > 1 ? many.data() : &one;
-			const std::vector<DasDecision> *cached = w.views ? nullptr : &frame_das_parts(ps, pb, zfirst, zcount);
+			const std::vector<DasDecision> *cached = w.views ? nullptr : w.image ? &frame_das_parts(das_ps, w.image->pb, zfirst, zcount)
+			                                                              : &frame_das_parts(ps, pb, zfirst, zcount);
+			if (w.image && main_part(*cached).path != DasPath_Zero) {
+				/* ---- 0. a READI image push: the N DAS inputs decoded across the acquisitions, its own segment directly before DAS; the
+				 * ONE job below reads the decoded buffer (push_frames grew it) */
+				if (poison) ok &= HIP_OK(hipMemsetAsync(d.readi_decoded.ptr, 0xFF, d.readi_decoded.size, s));
+				ok &= launch_image_decode(ps, pb.parameters, cur, N > 1 ? cur_stride : 0, w.readi_groups, N, s);
+				segment(t, (uint32_t)BeamformerShaderKind_Decode, s);
+				d.das_decoded_bytes = main_part(*cached).das_input_bytes;
+				cur = (const char *)d.readi_decoded.ptr; cur_stride = 0;
+			}
 			bool any_fused = false, any_counted = false;
 			for (uint32_t k = 0; k < F; k++) {
 				DasJob &j = jobs[k];
 				j.in  = cur + k * cur_stride;
 				j.out = (char *)d.ring.ptr + d.frames[(first + k) % d.frames.size()].offset;
-				j.readi_group = w.readi_groups ? (int32_t)w.readi_groups[k] : -1;
+				j.readi_group = w.readi_groups && !w.image ? (int32_t)w.readi_groups[k] : -1;
 				if (w.views) { j.parts = &w.views_route->parts[k]; j.z_first = 0; j.points = w.views[k].output_points; j.fused = w.views_route->taken[k] != 0; }
 				else         { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
 				const DasDecision &head = main_part(*j.parts);
@@ -847,7 +909,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 					ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
 				}
 				const DasDecision &head = main_part(*j.parts);
-				ok &= launch_frame_parts(ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.readi_group);
+				ok &= launch_frame_parts(das_ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.readi_group);
 			}
 			/* ---- 3. geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is
 			 * the same for every job of a run of jobs with the same parts (a burst: one run; a views push: one per view): it runs once,
@@ -868,7 +930,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 						if (!ok || dd.path == DasPath_Zero) continue;
 						BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
 						count.rf = j.in; count.out = j.out + (uint64_t)(dd.z_first - j.z_first) * head.a.size[0] * head.a.size[1] * voxel_bytes;
-						bind_tables(ps, count);
+						bind_tables(das_ps, count);
 						if (j.readi_group >= 0) count.readi_group = (uint32_t)j.readi_group;
 						count.pair_counter = mine;
 						ok &= HIP_OK(bf_launch_das_count(&count, s));
@@ -890,7 +952,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		/* no DAS in the pipeline: the frames exist and stay zero (the reference clears them, beamformer_core.c:1573-1585, and nothing
 		 * writes them).  A single push's frame is the block's whole grid whatever its shard -- with several devices on the ingest device,
 		 * the others holding an empty slab of it; a burst's frames are the shard's planes */
-		if (!w.route) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
+		if (!w.route && !w.image) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
 		uint64_t run_bytes = 0;
 		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes);
 		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
@@ -1277,7 +1339,10 @@ struct FramesPush {
 	DeviceBuffer *stage;                     /* the pre-DAS stages' ping-pong pair and, where it holds every RF frame's output, the stride to grow it by */
 	uint64_t      stage_stride;
 	float         decide_us;
-	const uint32_t *readi_groups = nullptr;  /* a READI sweep: rf_frames validated group ids, frame k's readi_group */
+	const uint32_t *readi_groups = nullptr;  /* a READI sweep, a READI image push: rf_frames validated group ids, frame k's readi_group */
+	ImagePlanState *image = nullptr;         /* a READI image push: its derived block, its route and the bytes of its decoded DAS input */
+	const ReadiImageDecision *image_route = nullptr;
+	uint64_t        decoded_bytes = 0;
 };
 
 /* A push of several frames with ONE upload and ONE event set (one device) -- a burst: N RF frames, N frames; a views push: one RF frame
@@ -1326,7 +1391,8 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 		for (size_t k = 0; k < 2 && k < pre_das_stages; k++) fits = fits && m.stage[k].ensure(m.stage_stride * N);
 	}
 	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
-	if ((m.views_route && m.views_route->kernel_views) || (m.readi_groups && m.burst && m.burst->burst_kernel)) {
+	if (m.image) fits = fits && d.readi_decoded.ensure(round_up(m.decoded_bytes, 64) + 64);
+	if ((m.views_route && m.views_route->kernel_views) || (m.readi_groups && m.burst && m.burst->burst_kernel) || m.image) {
 		/* (one size for both users: a sweep's BEAMFORMER_HIP_MAX_BURST_FRAMES group ids are 4 KiB of it) */
 		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
 		fits = fits && d.views_table.ensure(table_bytes);
@@ -1371,15 +1437,17 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
 	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
 	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_step, (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size), m.stage, m.stage_stride, t,
-	                                                 m.burst, m.views, m.views ? F : 0u, m.views_route, m.readi_groups});
+	                                                 m.burst, m.views, m.views ? F : 0u, m.views_route, m.readi_groups, m.image});
 	finish_upload(u, overlap, s);
 	if (!done) return false;
 
 	share_timing_rows(d, first, F, owner);
 	PushRecord &r = d.multi;
 	r.kind = m.kind; r.first_id = first; r.count = F; r.events_slot = owner; r.decide_us = m.decide_us;
-	if (m.burst) r.burst = *m.burst;
-	else         describe_views_decision(*m.views_route, F, &r.views);
+	r.rf_frames = N;
+	if (m.burst)            r.burst = *m.burst;
+	else if (m.image_route) r.image = *m.image_route;
+	else                    describe_views_decision(*m.views_route, F, &r.views);
 	lockstep.complete = true;
 	return true;
 }
@@ -1444,6 +1512,39 @@ bool push_readi_sweep(uint32_t block, const void *data, uint32_t frame_size, uin
 	                              N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0, 0.0f, groups});
 }
 
+/* beamformer_hip_push_data_readi_image_with_compute: the sweep's RF frames and group ids (lib_api.cpp has checked the block, the list
+ * and G x A), ONE frame: the derived block's single-frame DAS launch(es) on the DAS input decoded across the acquisitions.  One RF
+ * frame: the single push's buffers, as a sweep of one. */
+bool push_readi_image(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ParameterBlock &pb = c.blocks[block];
+	const uint32_t N = frame_count;
+
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	ImagePlanState *image = commit_image_plan(block, ps);
+	if (!image) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	const Plan &plan = ps->plan;
+
+	uint32_t zfirst = 0, zcount = plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
+	std::vector<DasDecision> no_parts;
+	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(&image->ps, image->pb, zfirst, zcount) : no_parts;
+	ReadiImageDecision route;
+	decide_readi_image(image->ps.plan, parts, pb.parameters.readi_group_count, N, route);
+	const uint64_t decoded = (uint64_t)plan.channels * image->ps.plan.acquisitions * plan.das_samples * (plan.iq_pipeline ? 8u : 4u);
+
+	return push_frames(block, ps, l, data, data_on_device,
+	                   FramesPush{PushRecord::Image, N, frame_size, 1, points, nullptr, nullptr, nullptr, keeps_counters(parts),
+	                              N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0, 0.0f, groups,
+	                              image, &route, decoded});
+}
+
 /* The record of the newest multi-frame push, when the newest push IS that push, of `kind` and complete: waited for, with its stage
  * kinds and times (hipEvent pairs around each stage of the WHOLE push; total: first event to last).  Else null, InvalidAccess. */
 static const PushRecord *newest_push(PushRecord::Kind kind, uint32_t &first_id, uint32_t &count, uint32_t &stage_count, uint32_t *stage_kind,
@@ -1481,6 +1582,28 @@ bool last_burst_info(BeamformerHipBurstInfo *out)
 	out->route.frames_per_thread = b.frames_per_thread; out->route.das_launches = b.das_launches;
 	out->route.stage_launches = b.stage_launches; out->route.min_frames = b.min_frames;
 	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.reason.c_str());
+	return true;
+}
+
+/* beamformer_hip_describe_readi_image / _get_last_readi_image_info: a decision in the words of the C ABI */
+void describe_readi_image_decision(const ReadiImageDecision &route, BeamformerHipReadiImageDescription *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	out->transmit_count = route.transmit_count;
+	out->das_path = route.path == DasPath_Zero ? -2 : route.path;
+	out->das_launches = route.das_launches; out->stage_launches = route.stage_launches; out->decode_launches = route.decode_launches;
+	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
+}
+
+/* beamformer_hip_get_last_readi_image_info */
+bool last_readi_image_info(BeamformerHipReadiImageInfo *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	uint32_t count = 0;
+	const PushRecord *r = newest_push(PushRecord::Image, out->frame_id, count, out->stage_count, out->stage_kind, out->stage_ms, out->image_ms);
+	if (!r) return false;
+	describe_readi_image_decision(r->image, &out->route);
+	out->rf_frame_count = r->rf_frames;
 	return true;
 }
 
@@ -1831,7 +1954,16 @@ bool copy_das_input_frame(uint32_t frame, void *out, uint64_t out_size)
 /* beamformer_hip_copy_das_input: the newest frame's -- a single push's, a views push's one input, a burst's last frame */
 bool copy_das_input(void *out, uint64_t out_size)
 {
-	const Context &c = g_context;
+	Context &c = g_context;
+	Device &d = c.devices[0];
+	if (c.device_ready && c.device_count == 1 && d.das_decoded_bytes) {
+		/* a READI image push: what its DAS stage read is the buffer decoded across the acquisitions, [channel][G x A][sample] */
+		if (!newest_record(d) || !d.das_input || out_size != d.das_decoded_bytes || d.readi_decoded.size < out_size) return set_error(BeamformerLibErrorKind_InvalidAccess);
+		bool ok = HIP_OK(hipSetDevice(d.device));
+		ok = ok && HIP_OK(hipMemcpyAsync(out, d.readi_decoded.ptr, out_size, hipMemcpyDeviceToHost, d.stream));
+		ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
+		return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
 	const uint32_t frames = c.devices[0].das_input_frames;
 	return copy_das_input_frame(frames ? frames - 1 : 0, out, out_size);
 }

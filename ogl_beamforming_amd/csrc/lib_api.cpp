@@ -202,6 +202,47 @@ bool push_readi_sweep_common(const void *data, uint32_t frame_size, uint32_t fra
 	return push_readi_sweep(slot, data, frame_size, frame_count, ids.data(), on_device);
 }
 
+/* A READI image push's block, list and count, no device needed: the sweep's checks (resolve_readi_groups), then what the derived block
+ * -- FORCES with readi_group_count x acquisition_count transmits -- must satisfy: the emission limit (InvalidAccess, with a line on
+ * stderr) and a decoded DAS input under 4 GiB (RFDataSizeOverflow).  `derived` / `derived_plan`: that block and its plan. */
+bool resolve_readi_image(uint32_t slot, const uint32_t *groups, uint32_t frame_count, std::vector<uint32_t> &ids, ParameterBlock &derived, Plan &derived_plan)
+{
+	Context &c = ctx();
+	if (!resolve_readi_groups(slot, groups, frame_count, ids)) return false;
+	const ParameterBlock &pb = c.blocks[slot];
+	const BeamformerParameters &bp = pb.parameters;
+	const uint64_t transmits = (uint64_t)bp.readi_group_count * bp.acquisition_count;
+	if (transmits > BeamformerMaxEmissionsCount) {
+		std::fprintf(stderr, "[beamformer] a READI image needs readi_group_count x acquisition_count <= %d transmits: refused (%u x %u)\n",
+		             (int)BeamformerMaxEmissionsCount, bp.readi_group_count, bp.acquisition_count);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	derive_readi_image(pb, plan, derived, derived_plan);
+	const uint64_t decoded = (uint64_t)plan.channels * transmits * plan.das_samples * (plan.iq_pipeline ? 8u : 4u);
+	return check(decoded < (1ull << 32), BeamformerLibErrorKind_RFDataSizeOverflow);
+}
+
+/* A READI image push: the sweep's checks and the derived block's, all before the device is touched; ONE frame must fit the ring. */
+bool push_readi_image_common(const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, uint32_t image_plane_tag, uint32_t slot,
+                             bool on_device)
+{
+	Context &c = ctx();
+	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
+	std::vector<uint32_t> ids;
+	ParameterBlock derived;
+	Plan derived_plan;
+	if (!resolve_readi_image(slot, groups, frame_count, ids, derived, derived_plan)) return false;
+	if (!on_one_device("READI image push")) return false;
+	if (!valid_rf_frame(c.blocks[slot], data, frame_size)) return false;
+	if (!run_fits_the_ring(c.blocks[slot], nullptr, 1)) return false;
+	if (!ensure_device()) return false;
+	return push_readi_image(slot, data, frame_size, frame_count, ids.data(), on_device);
+}
+
 /* What a views call must satisfy that needs neither the RF nor a device: the count, the list, the block, every view's tag and extents. */
 bool validate_views(const BeamformerHipView *views, uint32_t view_count, uint32_t slot)
 {
@@ -656,6 +697,44 @@ uint32_t beamformer_hip_resolve_readi_groups(uint32_t parameter_slot, const uint
 	if (!resolve_readi_groups(parameter_slot, readi_groups, frame_count, ids)) return 0;
 	std::memcpy(out, ids.data(), sizeof(uint32_t) * frame_count);
 	return 1;
+}
+
+uint32_t beamformer_hip_push_data_readi_image_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                           const uint32_t *readi_groups, uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_readi_image_common(data, frame_size, frame_count, readi_groups, image_plane_tag, parameter_slot, false);
+}
+
+uint32_t beamformer_hip_push_device_data_readi_image_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                  const uint32_t *readi_groups, uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_readi_image_common(device_data, frame_size, frame_count, readi_groups, image_plane_tag, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_describe_readi_image(uint32_t parameter_slot, const uint32_t *readi_groups, uint32_t frame_count,
+                                             BeamformerHipReadiImageDescription *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	Context &c = ctx();
+	std::vector<uint32_t> ids;
+	ParameterBlock derived;
+	Plan derived_plan;
+	if (!resolve_readi_image(parameter_slot, readi_groups, frame_count, ids, derived, derived_plan)) return 0;
+	const ParameterBlock &pb = c.blocks[parameter_slot];
+	uint32_t zfirst = 0, zcount = derived_plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	std::vector<DasDecision> parts;
+	if (derived_plan.das_index >= 0 && zcount) decide_das_parts(derived, derived_plan, build_transmit_table(derived), zfirst, zcount, c.das_path_mode, parts);
+	ReadiImageDecision route;
+	decide_readi_image(derived_plan, parts, pb.parameters.readi_group_count, frame_count, route);
+	describe_readi_image_decision(route, out);
+	return 1;
+}
+
+uint32_t beamformer_hip_get_last_readi_image_info(BeamformerHipReadiImageInfo *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
+	return last_readi_image_info(out);
 }
 
 uint32_t beamformer_hip_get_last_burst_info(BeamformerHipBurstInfo *out)

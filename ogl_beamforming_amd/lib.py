@@ -110,6 +110,10 @@ def _load():
         "beamformer_hip_push_device_data_readi_sweep_with_compute": (u32, [vp, u32, u32, C.POINTER(u32), u32, u32]),
         "beamformer_hip_describe_readi_sweep": (u32, [u32, C.POINTER(u32), u32, C.POINTER(P.HipBurstDescription)]),
         "beamformer_hip_resolve_readi_groups": (u32, [u32, C.POINTER(u32), u32, C.POINTER(u32)]),
+        "beamformer_hip_push_data_readi_image_with_compute": (u32, [vp, u32, u32, C.POINTER(u32), u32, u32]),
+        "beamformer_hip_push_device_data_readi_image_with_compute": (u32, [vp, u32, u32, C.POINTER(u32), u32, u32]),
+        "beamformer_hip_describe_readi_image": (u32, [u32, C.POINTER(u32), u32, C.POINTER(P.HipReadiImageDescription)]),
+        "beamformer_hip_get_last_readi_image_info": (u32, [C.POINTER(P.HipReadiImageInfo)]),
         "beamformer_hip_push_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
         "beamformer_hip_push_device_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
         "beamformer_hip_describe_views": (u32, [u32, C.POINTER(P.HipView), u32, C.POINTER(P.HipViewsDescription)]),
@@ -304,6 +308,41 @@ def resolve_readi_groups(bp, n, groups=None, slot=0):
     return list(out)
 
 
+def beamform_readi_image(bp, rf_frames, groups=None, filters=(), timeout_ms=-1, on_device_pointer=None):
+    """The group acquisitions of a READI sequence compounded into ONE frame (beamformer_hip_push_data_readi_image_with_compute):
+    `rf_frames` and `groups` as beamform_readi_sweep() takes them.  Returns the image, (Z, Y, X): the derived FORCES block's frame of
+    the DAS input decoded across the acquisitions -- without coherency weighting the sum of the sweep's frames."""
+    lib = _prepared(bp, filters, timeout_ms)
+    rf_frames = np.ascontiguousarray(rf_frames)
+    count = rf_frames.shape[0]
+    assert groups is None or len(groups) == count
+    frame_size = rf_frames.nbytes // count
+    if on_device_pointer is not None:
+        _check(lib.beamformer_hip_push_device_data_readi_image_with_compute(C.c_void_p(on_device_pointer), frame_size, count, _group_array(groups), 0, 0))
+    else:
+        _check(lib.beamformer_hip_push_data_readi_image_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, count, _group_array(groups), 0, 0))
+    return get_last_frame(bp)
+
+
+def describe_readi_image(bp, n, groups=None, filters=(), slot=0):
+    """What a READI image push of n RF frames of these parameters would run (beamformer_hip_describe_readi_image): the description
+    struct; .reason says what.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    d = P.HipReadiImageDescription()
+    _check(L.beamformer_hip_describe_readi_image(slot, _group_array(groups), n, C.byref(d)))
+    return d
+
+
+def last_readi_image_info():
+    """beamformer_hip_get_last_readi_image_info: the newest image push's route, id and whole-push stage times; waits for it."""
+    info = P.HipReadiImageInfo()
+    _check(library().beamformer_hip_get_last_readi_image_info(C.byref(info)))
+    return info
+
+
 def view(points, lo, hi, plane=None, plane_offset=0.0, tag=0):
     """A HipView of `points` voxels spanning lo .. hi: the grid configs' acquisitions are built on (configs._voxel_transform: a volume
     when it has z planes, else a view plane with depth on image y -- plane "yz" for the YZ plane)."""
@@ -401,14 +440,15 @@ def get_last_frame(bp, shard_planes=None):
     return raw[:voxels].reshape(shape)
 
 
-def das_input(bp, frame=None):
+def das_input(bp, frame=None, transmits=None):
     """beamformer_hip_copy_das_input: what the newest frame's DAS stage read, as float32 or complex64 of shape
     (channels, transmits, DAS samples); frame = k: RF frame k of the newest push (beamformer_hip_copy_das_input_frame: a burst's
-    frame k).  Valid until the next push; one device only."""
+    frame k).  transmits: the transmit count where it is not the block's (a READI image push's decoded input: G x A).  Valid until the
+    next push; one device only."""
     lib = library()
     plan = P.HipPlan()
     _check(lib.beamformer_hip_describe_plan(0, C.byref(plan)))
-    shape = (int(bp.channel_count), int(bp.acquisition_count), int(plan.das_samples))
+    shape = (int(bp.channel_count), int(bp.acquisition_count if transmits is None else transmits), int(plan.das_samples))
     out = np.empty(int(np.prod(shape)), np.complex64 if plan.iq_pipeline else np.float32)
     if frame is None:
         _check(lib.beamformer_hip_copy_das_input(out.ctypes.data_as(C.c_void_p), out.nbytes))

@@ -226,6 +226,16 @@ class HipBurstInfo(C.Structure):
                 ("stage_kind", C.c_uint32 * HIP_MAX_TIMED_STAGES), ("stage_ms", C.c_float * HIP_MAX_TIMED_STAGES), ("burst_ms", C.c_float)]
 
 
+class HipReadiImageDescription(C.Structure):
+    _fields_ = [("transmit_count", C.c_uint32), ("das_path", C.c_int32), ("das_launches", C.c_uint32), ("stage_launches", C.c_uint32),
+                ("decode_launches", C.c_uint32), ("reason", C.c_char * 160)]
+
+
+class HipReadiImageInfo(C.Structure):
+    _fields_ = [("route", HipReadiImageDescription), ("frame_id", C.c_uint32), ("rf_frame_count", C.c_uint32), ("stage_count", C.c_uint32),
+                ("stage_kind", C.c_uint32 * HIP_MAX_TIMED_STAGES), ("stage_ms", C.c_float * HIP_MAX_TIMED_STAGES), ("image_ms", C.c_float)]
+
+
 HIP_MAX_BURST_FRAMES = 1024
 HIP_DAS_PATH_NO_BURST_KERNEL = 0x400     # beamformer_hip_set_das_path flag: bursts run the single-frame DAS kernel once per frame
 
