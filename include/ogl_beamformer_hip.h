@@ -331,6 +331,72 @@ typedef struct {
 /* The newest views push; waits for it to finish.  Fails when the newest push was not a views push or did not complete. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_views_info(BeamformerHipViewsInfo *out);
 
+/* ---- burst views: N RF frames of one geometry beamformed on K voxel grids per call (bi-plane / tri-plane ultrafast imaging with a
+ * row-column array: the X-plane view over a Flash or few-angle ensemble; ULM: an ensemble refined on one set of patches) ----
+ * `data` is the burst's: frame_count RF frames back to back, each `frame_size` bytes under exactly the layout and size rules of
+ * beamformer_push_data_with_compute; `views` is the views push's.  Frame (view v, RF frame k) is the frame a single push of RF k would
+ * give if the block's das_voxel_transform and output_points[0..2] were views[v]'s.  Queues frame_count x view_count frames, VIEW-MAJOR:
+ * frame v * frame_count + k is (view v, RF frame k), so a view's ensemble is frame_count consecutive ids -- in the frame ring
+ * frame_count equal-sized frames at a fixed stride --, the views' runs follow one another, each frame rounded to 64 bytes (a run that
+ * would straddle the end of the ring starts again at offset 0), and beamformer_get_last_frames(out, size, frame_count x view_count)
+ * returns them oldest first, each at its own size.
+ *   - one upload, one RF-ring slot, the ingest and every pre-DAS stage ONCE for the push (the burst's frame chunks), one event set:
+ *     every frame's timing row shows a 1 / (frame_count x view_count) share; beamformer_hip_copy_das_input_frame(k) serves RF frame k;
+ *   - the DAS route is a ladder (csrc/das_select.h: decide_burst_views; beamformer_hip_describe_burst_views says which rung, and why):
+ *       1. frame_count >= BeamformerHipBurstViewsDescription::min_frames, neither NoBurstKernel (0x400) nor NoViewsKernel (0x800):
+ *          the views a views push's kernel is eligible for (RCA family, single frames on the general kernel) run in ONE launch whatever
+ *          their tile count (csrc/das_burst.hip: das_burst_views_kernel -- the burst kernel's frame slots on the views kernel's
+ *          concatenated tiles); every other view runs its single-frame kernel(s) per RF frame.  A frame of the fused launch is within
+ *          float rounding of its single push (the burst kernel's contract); its bits depend neither on its slot nor on the other views;
+ *       2. below the threshold, or under 0x400: per RF frame the views push's own DAS step -- frame (v, k) is the frame of a views
+ *          push of RF k alone, bit for bit;
+ *       3. under 0x800, and for every view rung 1 does not take: the view's single-frame launch(es) per RF frame -- frame (v, k) is
+ *          the single push of RF k on the block with that grid, bit for bit;
+ *   - validation is the single push's per frame and the views push's per view, with their error kinds.  frame_count == 0 or >
+ *     BEAMFORMER_HIP_MAX_BURST_FRAMES, view_count == 0 or > BEAMFORMER_HIP_MAX_VIEWS, and frame_count x view_count >
+ *     BeamformerMaxBacklogFrames (every frame keeps its record) are BufferOverflow; views == NULL or a zero extent is InvalidAccess;
+ *     the whole run exceeding the frame ring is FrameSizeOverflow; RF or stage memory that cannot be grown is RFDataSizeOverflow;
+ *     several devices or an output shard on the block is InvalidAccess.  All of that is judged before a device is touched and before
+ *     an id is taken: a refused push queues nothing.  A push that fails after that leaves a tombstone under every one of its ids;
+ *   - frame_count == 1 goes through the same code (rung 2 or 3);
+ *   - beamformer_hip_get_last_burst_info, _views_info and _readi_image_info refuse this push, and its own info call refuses theirs;
+ *     frame graphs: the push runs as direct launches; pair counting: one geometry-only count per view, reported by all of that view's
+ *     frames; das path flag FailViewsDas (0x2000) fails this push's DAS step as it fails a views push's. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_data_burst_views_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count,
+                                                                                 const BeamformerHipView *views, uint32_t view_count,
+                                                                                 uint32_t parameter_slot);
+/* ... for RF that already resides on the library's device (beamformer_hip_push_device_data_burst_with_compute's rules) */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_device_data_burst_views_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                                        const BeamformerHipView *views, uint32_t view_count,
+                                                                                        uint32_t parameter_slot);
+
+typedef struct {
+	uint32_t rung;                  /* 1, 2 or 3: the lowest-numbered rung some view of the push runs on (above) */
+	uint32_t kernel_views;          /* rung 1: views the fused kernel takes, all in one launch; else 0 */
+	uint32_t frame_kernel_views;    /* rung 2: views das_views.hip takes, once per RF frame; else 0 */
+	uint32_t das_launches;          /* DAS launches of the whole push */
+	uint32_t stage_launches;        /* launches the push takes of a pre-DAS filter stage (BeamformerHipBurstDescription::stage_launches) */
+	uint32_t frames_per_thread;     /* rung 1: BEAMFORMER_HIP_BURST_FRAMES_PER_THREAD; else 1 */
+	uint32_t min_frames;            /* the fewest RF frames the fused kernel takes (csrc/das_select.h: kBurstViewsMinFrames) */
+	int8_t   path[BEAMFORMER_HIP_MAX_VIEWS];   /* per view: its OWN single-frame decision, as BeamformerHipViewsDescription::path */
+	char     reason[160];           /* why this route */
+} BeamformerHipBurstViewsDescription;
+/* What a burst views push of frame_count RF frames on these grids would run, under the current das path mode.  Needs no device. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_burst_views(uint32_t parameter_slot, uint32_t frame_count, const BeamformerHipView *views,
+                                                                   uint32_t view_count, BeamformerHipBurstViewsDescription *out);
+
+typedef struct {
+	BeamformerHipBurstViewsDescription route;   /* of the push that ran */
+	uint32_t first_frame_id, frame_count, view_count;      /* frame_count: RF frames; the push queued frame_count x view_count frames */
+	uint32_t stage_count;
+	uint32_t stage_kind[BEAMFORMER_HIP_MAX_TIMED_STAGES];  /* BeamformerShaderKind; ingest = 0xFFFF */
+	float    stage_ms[BEAMFORMER_HIP_MAX_TIMED_STAGES];    /* hipEvent pairs around each stage of the WHOLE push */
+	float    push_ms;                                      /* first event to last event */
+	float    decide_us;                                    /* host time the push spent deciding its route (one decision per view, not per frame) */
+} BeamformerHipBurstViewsInfo;
+/* The newest burst views push; waits for it to finish.  Fails when the newest push was not one or did not complete. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_burst_views_info(BeamformerHipBurstViewsInfo *out);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

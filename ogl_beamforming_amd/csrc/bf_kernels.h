@@ -110,10 +110,12 @@ typedef struct {
 	uint32_t band_rows;
 	uint32_t pad0;
 	uint64_t out_offset;              /* bytes from BfDasArgs.out to the view's frame */
-	uint32_t pad1[2];
+	uint64_t out_stride;              /* das_burst_views_kernel: bytes from a view's frame of one RF frame to its frame of the next (das_views_kernel
+	                                     does not read it) */
 } BfViewRow;
 #ifdef __cplusplus
-static_assert(sizeof(BfViewRow) == 128 && offsetof(BfViewRow, size) == 64 && offsetof(BfViewRow, out_offset) == 112 && offsetof(BfViewRow, out_offset) % 8 == 0,
+static_assert(sizeof(BfViewRow) == 128 && offsetof(BfViewRow, size) == 64 && offsetof(BfViewRow, out_offset) == 112 && offsetof(BfViewRow, out_offset) % 8 == 0 &&
+              offsetof(BfViewRow, out_stride) == 120,
               "BfViewRow: 128 bytes, the same on the host that fills it and in the kernel that reads it");
 #endif
 typedef struct {
@@ -343,6 +345,9 @@ hipError_t bf_launch_das_readi_sweep(const BfDasArgs *a, const BfReadiSweepArgs 
 hipError_t bf_launch_readi_image_decode(const BfReadiDecodeArgs *a, hipStream_t s);   /* readi_decode.hip */
 hipError_t bf_launch_views_table(void *dst, const void *src, uint32_t bytes, hipStream_t s);   /* das_views.hip: bytes (a multiple of 4) from mapped pinned memory into the device table */
 hipError_t bf_launch_das_views(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s);   /* das_views.hip: RCA family, no channel split */
+/* das_burst.hip: the burst kernel's frame slots on the views kernel's tiles -- RCA family, no channel split; frame f of the view of row r
+ * reads a->rf + f * b->rf_stride and writes a->out + r.out_offset + f * r.out_stride (b->out_stride is not read) */
+hipError_t bf_launch_das_burst_views(const BfDasArgs *a, const BfBurstArgs *b, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s);
 hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged_tables(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);

@@ -68,12 +68,13 @@ struct TimingSlot {
 
 /* the newest multi-frame push (executor.cpp push_frames): what beamformer_hip_get_last_burst_info / _views_info report, each of its own kind */
 struct PushRecord {
-	enum Kind { None, Burst, Views, Image } kind = None;
+	enum Kind { None, Burst, Views, Image, BurstViews } kind = None;
 	uint64_t      first_id = 0;
 	uint32_t      count = 0, events_slot = 0;
 	BurstDecision burst;                      /* Burst: its route */
 	BeamformerHipViewsDescription views{};    /* Views: its route, and the host time spent deciding it */
 	ReadiImageDecision image;                 /* Image: its route, and the RF frames it compounded */
+	BeamformerHipBurstViewsDescription burst_views{};   /* BurstViews: its route; rf_frames RF frames on count / rf_frames views */
 	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
 };
@@ -110,9 +111,11 @@ constexpr uint32_t kMaxDevices = 8;      /* one node of MI355X */
 /* The bytes of a run of `count` frames, contiguous in the frame ring, each rounded to 64 bytes: `count` frames of `points` voxels, or --
  * `views` given -- frame k of views[k]'s.  Host arithmetic only, saturating (three 32-bit extents can wrap 64 bits).  False: the run
  * does not fit `ring` bytes. */
-inline bool frame_run_bytes(const uint32_t points[3], const BeamformerHipView *views, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total)
+inline bool frame_run_bytes(const uint32_t points[3], const BeamformerHipView *views, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total,
+                            uint32_t per_view = 1)
 {
-	const uint32_t distinct = views ? count : 1u, each = views ? 1u : count;      /* equal frames: one size, `count` times */
+	/* equal frames: one size, `count` times; views: frame j is of views[j / per_view] (a burst views push: per_view RF frames a view) */
+	const uint32_t distinct = views ? count / per_view : 1u, each = views ? per_view : count;
 	total = 0;
 	for (uint32_t k = 0; k < distinct; k++) {
 		const uint32_t *n = views ? views[k].output_points : points;
@@ -230,6 +233,10 @@ void describe_readi_image_decision(const ReadiImageDecision &route, BeamformerHi
 bool last_burst_info(BeamformerHipBurstInfo *out);
 bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device);
 bool last_views_info(BeamformerHipViewsInfo *out);
+bool push_burst_views(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count,
+                      bool data_on_device);
+bool last_burst_views_info(BeamformerHipBurstViewsInfo *out);
+void describe_burst_views_decision(const BurstViewsDecision &route, uint32_t view_count, BeamformerHipBurstViewsDescription *out);
 std::vector<ViewGrid> view_grids(const BeamformerHipView *views, uint32_t view_count);     /* the grids decide_views takes */
 void describe_views_decision(const ViewsDecision &route, uint32_t view_count, BeamformerHipViewsDescription *out);
 bool wait_for_frames(int32_t timeout_ms);

@@ -1061,8 +1061,10 @@ void plan_on_view(const ParameterBlock &pb, const ViewGrid &view, Plan &plan)
 		m4_mul(bp.xdc_transform, view.transform, plan.das_voxel_transform);
 }
 
-void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
-                  uint32_t mode, ViewsDecision &out)
+/* decide_views; any_tile_count: the eligible views are taken however few their tiles (what flag 0x1000 asks of a views push, and what a
+ * burst views push's fused kernel does: there the frames fill the chip) */
+static void decide_views_for(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
+                             uint32_t mode, bool any_tile_count, ViewsDecision &out)
 {
 	out = ViewsDecision{};
 	out.parts.resize(view_count);
@@ -1106,7 +1108,7 @@ void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<
 		out.a = head.general;                                                   /* (what is not the grid is the same in every view) */
 	}
 	char text[160];
-	const bool take = candidates && (tiles >= kViewsMinTiles || (mode & 0x1000u));
+	const bool take = candidates && (tiles >= kViewsMinTiles || any_tile_count);
 	if (take) {
 		uint32_t row_ends = 0, next = 0;
 		for (uint32_t v = 0; v < view_count; v++) {
@@ -1137,6 +1139,54 @@ void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<
 		std::snprintf(text, sizeof(text), "fewer than %u tiles in the eligible views: the single-frame general kernel once per view", kViewsMinTiles);
 	}
 	out.reason = text;
+}
+
+void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
+                  uint32_t mode, ViewsDecision &out)
+{
+	decide_views_for(pb, plan, tx, views, view_count, mode, (mode & 0x1000u) != 0, out);
+}
+
+void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
+                        uint32_t mode, uint32_t frame_count, BurstViewsDecision &out)
+{
+	out = BurstViewsDecision{};
+	const uint32_t N = frame_count;
+	const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
+	out.stage_launches = (N + chunk - 1) / chunk;
+	const bool fused_asked = N >= kBurstViewsMinFrames && !(mode & 0x400u) && !(mode & 0x800u);
+	/* rung 1: the views the views kernel is eligible for, whatever their tile count; rungs 2 and 3: decide_views' own rules (under 0x800 it
+	 * takes no view) */
+	if (fused_asked) decide_views_for(pb, plan, tx, views, view_count, mode, true, out.views);
+	else             decide_views(pb, plan, tx, views, view_count, mode, out.views);
+	const ViewsDecision &v = out.views;
+	uint32_t own = 0;                        /* single-frame launches of the views no kernel takes, for one RF frame */
+	for (uint32_t k = 0; k < view_count; k++)
+		if (!v.taken[k]) for (const DasDecision &d : v.parts[k]) own += d.path != DasPath_Zero;
+	char text[160];
+	if (fused_asked && v.kernel_views) {
+		out.rung = 1;
+		out.kernel_views = v.kernel_views; out.frames_per_thread = BF_BURST_FRAMES_PER_THREAD;
+		out.das_launches = 1 + N * own;
+		if (v.kernel_views == view_count)
+			std::snprintf(text, sizeof(text), "RCA family on the general kernel: %u views, %u tiles, %u frames in one launch, a term's geometry applied to %u frames",
+			              v.kernel_views, v.kernel_tiles, N, BF_BURST_FRAMES_PER_THREAD);
+		else
+			std::snprintf(text, sizeof(text), "%u of %u views (%u tiles) x %u frames in one fused launch; the other views' single-frame launches once per RF frame: %u",
+			              v.kernel_views, view_count, v.kernel_tiles, N, N * own);
+		out.reason = text;
+	} else if (v.kernel_views) {
+		out.rung = 2;
+		out.frame_kernel_views = v.kernel_views;
+		out.das_launches = N * v.das_launches;
+		if (mode & 0x400u) std::snprintf(text, sizeof(text), "das path flag 0x400: the views kernel once per RF frame (%u of %u views) was asked for", v.kernel_views, view_count);
+		else               std::snprintf(text, sizeof(text), "fewer than %u frames: the views kernel once per RF frame (%u of %u views)", kBurstViewsMinFrames, v.kernel_views, view_count);
+		out.reason = text;
+	} else {
+		out.rung = 3;
+		out.das_launches = N * v.das_launches;
+		out.reason = v.reason.empty() ? std::string("each view's single-frame launch(es) once per RF frame") : v.reason + ", per RF frame";
+	}
 }
 
 uint32_t row_end_planes(const std::vector<DasDecision> &parts)

@@ -151,6 +151,31 @@ struct ViewsDecision {
 void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const ViewGrid *views, uint32_t view_count,
                   uint32_t mode, ViewsDecision &out);
 
+/* das_burst_views_kernel (das_burst_views.hip) takes burst views pushes of this many RF frames and more: the smallest measured frame
+ * count from which the push on the fused kernel is not slower than the views kernel per RF frame (flag 0x400) by more than three times
+ * that route's run-to-run spread (tools/burst_views_rate.py, profiles/burst_views_rate.json: min_frames_from_this_table).  Wall time
+ * per queued frame of the fused kernel over that route, upload included, by N -- 2 planes of 256 x 1 x 256: 5: 0.57, 8: 0.49, 16: 0.37,
+ * 64: 0.44, 256: 0.31; 3 planes: 5: 0.69, 8: 0.51, 64: 0.40, 256: 0.31; 16 patches of 16 x 1 x 16: 5: 0.52, 16: 0.36, 256: 0.21; over
+ * K x (parameter push + burst push): 0.35-0.75 on the planes, 0.06-0.10 on the patches.  Fewer than 5 frames were not measured on the
+ * kernel (the value in force, the burst kernel's break-even, sent them down the per-frame route). */
+constexpr uint32_t kBurstViewsMinFrames = 5;
+
+/* How a burst views push of frame_count RF frames on view_count grids runs (beamformer_hip_describe_burst_views): a ladder.
+ *   rung 1  the fused kernel: the views das_views.hip is eligible for (decide_views: one part on the general kernel, RCA family), ALL in
+ *           one launch whatever their tile count, when frame_count >= kBurstViewsMinFrames and mode carries neither
+ *           BeamformerHipDasPath_NoBurstKernel (0x400) nor _NoViewsKernel (0x800); every other view its single-frame launch(es) per RF frame;
+ *   rung 2  below the threshold or under 0x400, 0x800 absent: per RF frame the views push's own DAS step under decide_views' unchanged rules;
+ *   rung 3  under 0x800, or where no view is eligible: every (view, RF frame) its view's single-frame launch(es).
+ * `views`: the per-view decisions, and for rungs 1 and 2 the taken views' rows and prefix table. */
+struct BurstViewsDecision {
+	ViewsDecision views;
+	uint32_t    rung = 3, kernel_views = 0, frame_kernel_views = 0, frames_per_thread = 1, das_launches = 0, stage_launches = 0;
+	uint32_t    min_frames = kBurstViewsMinFrames;
+	std::string reason;
+};
+void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const ViewGrid *views, uint32_t view_count,
+                        uint32_t mode, uint32_t frame_count, BurstViewsDecision &out);
+
 /* READI image (beamformer_hip_push_data_readi_image_with_compute).  READI_FORCES is FORCES with transmit element
  * tx_group * acquisition_count + tx_event and every term signed by Hadamard[readi_group * G + tx_group] (das.glsl:288-366), and everything
  * behind the sign is linear in the samples: the sum of a sequence's partial frames is ONE frame of the DERIVED block -- the same block with

@@ -325,14 +325,16 @@ static ImagePlanState *commit_image_plan(uint32_t block, PlanState *ps)
 }
 
 /* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: all of
- * `points` (a single push: one; a burst), or -- `views` given -- frame k of views[k]'s points and tag.  A run that would straddle the end
+ * `points` (a single push: one; a burst), or -- `views` given -- frame k of views[k / per_view]'s points and tag (a views push: one frame
+ * a view; a burst views push: its RF frames, view-major).  A run that would straddle the end
  * starts again at offset 0; the records it overwrites stop being exportable.  Consecutive ids, each frame's timing slot named in its
  * record.  Returns the first, or null when the run does not fit the ring; total: the bytes of the whole run (frame_run_bytes). */
-static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count, const BeamformerHipView *views, uint64_t &total)
+static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count, const BeamformerHipView *views, uint64_t &total,
+                                uint32_t per_view = 1)
 {
 	Device &d = *g_context.cur;
 	const int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
-	if (count == 0 || !frame_run_bytes(points, views, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total)) return nullptr;
+	if (count == 0 || !frame_run_bytes(points, views, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total, per_view)) return nullptr;
 	if (d.ring_next_offset > d.ring.size - total) d.ring_next_offset = 0;
 	/* records whose storage the run reuses stop being exportable: one pass for the run's whole byte range (the run's own records are
 	 * written below, after it) */
@@ -340,14 +342,14 @@ static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, ui
 		if (old.bytes && old.offset < d.ring_next_offset + total && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
 	FrameRecord *first = nullptr;
 	for (uint32_t k = 0; k < count; k++) {
-		const uint32_t *n = views ? views[k].output_points : points;
+		const uint32_t *n = views ? views[k / per_view].output_points : points;
 		const uint64_t bytes = round_up((uint64_t)n[0] * n[1] * n[2] * (uint64_t)bf_kind_byte_size[kind], 64);
 		uint64_t id = d.frame_counter++;
 		FrameRecord *f = &d.frames[id % d.frames.size()];
 		f->offset = d.ring_next_offset; f->bytes = bytes;
 		f->points[0] = n[0]; f->points[1] = n[1]; f->points[2] = n[2];
 		f->data_kind = kind; f->id = (uint32_t)id; f->block = block; f->failed = false;
-		f->tag = views ? views[k].image_plane_tag : 0u;
+		f->tag = views ? views[k / per_view].image_plane_tag : 0u;
 		f->timing_slot = (int)(id % kTimingSlots);
 		d.ring_next_offset += bytes;
 		if (k == 0) first = f;
@@ -675,6 +677,8 @@ struct StageWalk {
 	const BeamformerHipView *views = nullptr;     /* a views push: `frames` is 1 and the DAS stage writes view_count frames from its one input, */
 	uint32_t             view_count = 0;
 	const ViewsDecision *views_route = nullptr;   /* by this route (das_select.h: decide_views) */
+	const BurstViewsDecision *burst_views = nullptr;   /* a burst views push: `frames` RF frames on the view_count grids, frames x view_count frames
+	                                                      view-major, by this route (views_route: its per-view decisions and table) */
 	const uint32_t      *readi_groups = nullptr;  /* a READI sweep: frame k is beamformed with readi_group = readi_groups[k] (validated: lib_api.cpp) */
 	ImagePlanState      *image = nullptr;         /* a READI image push: the `frames` DAS inputs are decoded across the acquisitions by readi_groups
 	                                                 (readi_decode.hip) and the DAS stage writes ONE frame from that, under this derived block */
@@ -736,8 +740,11 @@ static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route,
 }
 
 /* The views kernel (das_views.hip): the views the route has it take, from the ONE DAS input, in one launch -- their rows and the prefix
- * table go through pinned memory on the push's stream ahead of it, read in place by a small kernel (no copy engine: bf_launch_views_table). */
-static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const DasJob *jobs, uint32_t K, hipStream_t s)
+ * table go through pinned memory on the push's stream ahead of it, read in place by a small kernel (no copy engine: bf_launch_views_table).
+ * View k's job is jobs[k * step] (a views push: step 1).  fused_frames: a burst views push's fused launch (das_burst.hip:
+ * das_burst_views_kernel) instead -- that many RF frames, in_stride apart, view k's frames jobs[k * step .. k * step + fused_frames - 1]. */
+static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const DasJob *jobs, uint32_t K, hipStream_t s, uint32_t step = 1,
+                                uint32_t fused_frames = 0, uint64_t in_stride = 0)
 {
 	Device &d = *g_context.cur;
 	bool ok = true;
@@ -748,7 +755,8 @@ static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const
 	for (uint32_t k = 0, r = 0; k < K; k++) {
 		if (!route.taken[k]) continue;
 		rows[r] = route.rows[r];
-		rows[r].out_offset = (uint64_t)(jobs[k].out - jobs[0].out);
+		rows[r].out_offset = (uint64_t)(jobs[k * step].out - jobs[0].out);
+		rows[r].out_stride = fused_frames > 1 ? (uint64_t)(jobs[k * step + 1].out - jobs[k * step].out) : 0;
 		r++;
 	}
 	std::memcpy((char *)d.views_pinned + rows_bytes, route.first_block.data(), sizeof(uint32_t) * (n + 1));
@@ -764,7 +772,9 @@ static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const
 	v.rows = (const BfViewRow *)d.views_table.ptr;
 	v.first_block = (const uint32_t *)((const char *)d.views_table.ptr + rows_bytes);
 	v.view_count = n;
-	if (ok) ok &= HIP_OK(bf_launch_das_views(&a, &v, route.first_block[n], s));
+	BfBurstArgs b{};
+	b.frame_count = fused_frames; b.rf_stride = in_stride;
+	if (ok) ok &= fused_frames ? HIP_OK(bf_launch_das_burst_views(&a, &b, &v, route.first_block[n], s)) : HIP_OK(bf_launch_das_views(&a, &v, route.first_block[n], s));
 	return ok;
 }
 
@@ -807,7 +817,8 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	hipStream_t s = d.stream;
 	TimingSlot &t = w.t;
 	const uint32_t N = w.frames;
-	const uint32_t F = w.views ? w.view_count : w.image ? 1u : N;          /* frames the walk queues */
+	const uint32_t F = w.burst_views ? w.view_count * N : w.views ? w.view_count : w.image ? 1u : N;          /* frames the walk queues */
+	const uint32_t per_view = w.burst_views ? N : 1u;      /* frames of a view: job v * per_view + k is (view v, RF frame k) */
 	PlanState *das_ps = w.image ? &w.image->ps : ps;        /* whose tables and decision the DAS launches run with */
 
 	const char *cur = (const char *)w.in;
@@ -850,7 +861,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		}break;
 		case BeamformerShaderKind_DAS:{
 			uint64_t run_bytes = 0;
-			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes);
+			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes, per_view);
 			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 			if (poison && run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0xFF, run_bytes, s));
 			/* what beamformer_hip_copy_das_input_frame serves: RF frame k's input at k * cur_stride (one RF frame -- a single push, a views
@@ -882,10 +893,12 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			bool any_fused = false, any_counted = false;
 			for (uint32_t k = 0; k < F; k++) {
 				DasJob &j = jobs[k];
-				j.in  = cur + k * cur_stride;
+				const uint32_t view = k / per_view, rf_frame = w.burst_views ? k % per_view : k;
+				j.in  = cur + rf_frame * cur_stride;
 				j.out = (char *)d.ring.ptr + d.frames[(first + k) % d.frames.size()].offset;
 				j.readi_group = w.readi_groups && !w.image ? (int32_t)w.readi_groups[k] : -1;
-				if (w.views) { j.parts = &w.views_route->parts[k]; j.z_first = 0; j.points = w.views[k].output_points; j.fused = w.views_route->taken[k] != 0; }
+				/* (a burst views push: `fused` also names the jobs the views kernel covers per RF frame, rung 2) */
+				if (w.views) { j.parts = &w.views_route->parts[view]; j.z_first = 0; j.points = w.views[view].output_points; j.fused = w.views_route->taken[view] != 0; }
 				else         { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
 				const DasDecision &head = main_part(*j.parts);
 				j.path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
@@ -894,10 +907,18 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 				counters_kept |= !j.fused && keeps_counters(*j.parts);
 			}
 
-			/* ---- 1. the push's fused launch */
-			if (any_fused) ok &= w.views        ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
-			                  : w.readi_groups ? launch_readi_sweep_kernel(ps, *w.route, jobs[0], w.readi_groups, N, cur_stride, frame0->bytes, s)
-			                                   : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
+			/* ---- 1. the push's fused launch; a burst views push: rung 1 its kernel once, rung 2 the views kernel once per RF frame, on
+			 * that frame's jobs (k, N + k, 2 N + k, ...) and its slice of the input */
+			if (!any_fused) {
+			} else if (w.burst_views && w.burst_views->rung == 1) {
+				ok &= launch_views_kernel(ps, *w.views_route, jobs, w.view_count, s, N, N, N > 1 ? cur_stride : 0);
+			} else if (w.burst_views) {
+				for (uint32_t k = 0; k < N && ok; k++) ok &= launch_views_kernel(ps, *w.views_route, jobs + k, w.view_count, s, N);
+			} else {
+				ok &= w.views        ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
+				    : w.readi_groups ? launch_readi_sweep_kernel(ps, *w.route, jobs[0], w.readi_groups, N, cur_stride, frame0->bytes, s)
+				                     : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
+			}
 			/* ---- 2. every other job's own launch(es): the kernels of a single push.  One set of counters per timing slot */
 			if (counters_kept && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) ok = false;
 			for (uint32_t k = 0; k < F && ok; k++) {
@@ -954,7 +975,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		 * the others holding an empty slab of it; a burst's frames are the shard's planes */
 		if (!w.route && !w.image) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
 		uint64_t run_bytes = 0;
-		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes);
+		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes, per_view);
 		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 		if (run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, run_bytes, s));
 	}
@@ -1343,10 +1364,12 @@ struct FramesPush {
 	ImagePlanState *image = nullptr;         /* a READI image push: its derived block, its route and the bytes of its decoded DAS input */
 	const ReadiImageDecision *image_route = nullptr;
 	uint64_t        decoded_bytes = 0;
+	const BurstViewsDecision *burst_views = nullptr;   /* a burst views push: `frames` = rf_frames x its views, view-major; views_route: its per-view part */
 };
 
 /* A push of several frames with ONE upload and ONE event set (one device) -- a burst: N RF frames, N frames; a views push: one RF frame
- * on K grids.
+ * on K grids; a burst views push: N RF frames on K grids, N x K frames view-major (frame v * N + k: view v, RF frame k), by the ladder of
+ * decide_burst_views -- its fused launch (das_burst_views.hip), or per RF frame the views push's DAS step, or every frame its own launch(es).
  *   RF        one upload into one pinned slot -- over the copy engine into device staging when it is large, read in place over PCIe when
  *             small, by kOverlapBytes applied to the whole upload -- and ONE slot of the RF ring, frame k at k * rf_stride with 64 spare
  *             bytes behind every frame;
@@ -1373,7 +1396,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	const uint32_t N = m.rf_frames, F = m.frames;
 
 	uint64_t run_bytes = 0;
-	if (!frame_run_bytes(m.points, m.views, F, plan.iq_pipeline ? 8u : 4u, d.ring.size, run_bytes)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+	if (!frame_run_bytes(m.points, m.views, F, plan.iq_pipeline ? 8u : 4u, d.ring.size, run_bytes, m.burst_views ? N : 1u)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 
 	/* device and pinned memory, grown before anything is queued */
 	const uint64_t rf_stride = round_up(l.rf_size, 64) + 64;
@@ -1437,7 +1460,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
 	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
 	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_step, (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size), m.stage, m.stage_stride, t,
-	                                                 m.burst, m.views, m.views ? F : 0u, m.views_route, m.readi_groups, m.image});
+	                                                 m.burst, m.views, m.views ? F / (m.burst_views ? N : 1u) : 0u, m.views_route, m.burst_views, m.readi_groups, m.image});
 	finish_upload(u, overlap, s);
 	if (!done) return false;
 
@@ -1447,6 +1470,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	r.rf_frames = N;
 	if (m.burst)            r.burst = *m.burst;
 	else if (m.image_route) r.image = *m.image_route;
+	else if (m.burst_views) describe_burst_views_decision(*m.burst_views, F / N, &r.burst_views);
 	else                    describe_views_decision(*m.views_route, F, &r.views);
 	lockstep.complete = true;
 	return true;
@@ -1663,6 +1687,63 @@ bool last_views_info(BeamformerHipViewsInfo *out)
 	const PushRecord *r = newest_push(PushRecord::Views, out->first_frame_id, out->view_count, out->stage_count, out->stage_kind, out->stage_ms, out->views_ms);
 	if (!r) return false;
 	out->route = r->views; out->decide_us = r->decide_us;
+	return true;
+}
+
+/* beamformer_hip_describe_burst_views / _get_last_burst_views_info: a decision in the words of the C ABI */
+void describe_burst_views_decision(const BurstViewsDecision &route, uint32_t view_count, BeamformerHipBurstViewsDescription *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	out->rung = route.rung; out->kernel_views = route.kernel_views; out->frame_kernel_views = route.frame_kernel_views;
+	out->das_launches = route.das_launches; out->stage_launches = route.stage_launches;
+	out->frames_per_thread = route.frames_per_thread; out->min_frames = route.min_frames;
+	for (uint32_t k = 0; k < view_count && k < BEAMFORMER_HIP_MAX_VIEWS; k++) {
+		if (route.views.parts[k].empty()) { out->path[k] = -1; continue; }
+		const int path = main_part(route.views.parts[k]).path;
+		out->path[k] = (int8_t)(path == DasPath_Zero ? -2 : path);
+	}
+	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
+}
+
+/* beamformer_hip_push_data_burst_views_with_compute: frame_count RF frames beamformed on view_count grids (no output shard),
+ * frame_count x view_count frames view-major, each at its view's size.  The route: decide_burst_views -- ONE decide_das_parts per view,
+ * not per frame.  One RF frame: the single push's buffers, as a views push. */
+bool push_burst_views(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count,
+                      bool data_on_device)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ParameterBlock &pb = c.blocks[block];
+	const uint32_t N = frame_count, K = view_count;
+	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+
+	const auto decide_begin = std::chrono::steady_clock::now();
+	BurstViewsDecision route;
+	decide_burst_views(pb, ps->plan, ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, N, route);
+	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
+	bool wants_counters = false;
+	for (uint32_t k = 0; k < K; k++) wants_counters |= !route.views.taken[k] && keeps_counters(route.views.parts[k]);
+
+	FramesPush m{PushRecord::BurstViews, N, frame_size, N * K, nullptr, views, nullptr, &route.views, wants_counters,
+	             N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(ps->plan.intermediate_bytes, 64) + 64 : 0, decide_us};
+	m.burst_views = &route;
+	return push_frames(block, ps, l, data, data_on_device, m);
+}
+
+/* beamformer_hip_get_last_burst_views_info */
+bool last_burst_views_info(BeamformerHipBurstViewsInfo *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	uint32_t frames = 0;
+	const PushRecord *r = newest_push(PushRecord::BurstViews, out->first_frame_id, frames, out->stage_count, out->stage_kind, out->stage_ms, out->push_ms);
+	if (!r) return false;
+	out->route = r->burst_views; out->decide_us = r->decide_us;
+	out->frame_count = r->rf_frames; out->view_count = r->rf_frames ? frames / r->rf_frames : 0;
 	return true;
 }
 

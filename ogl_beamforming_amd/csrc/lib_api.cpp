@@ -122,14 +122,14 @@ bool on_one_device(const char *what)
 }
 
 /* a multi-frame push's whole run of frames in the frame ring (context.h: frame_run_bytes; needs the block's plan, no device) */
-bool run_fits_the_ring(const ParameterBlock &pb, const BeamformerHipView *views, uint32_t count)
+bool run_fits_the_ring(const ParameterBlock &pb, const BeamformerHipView *views, uint32_t count, uint32_t per_view = 1)
 {
 	Plan plan;
 	std::string error;
 	if (!build_plan(pb, plan, error, ctx().hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
 	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], pb.shard_z_count ? pb.shard_z_count : plan.output_points[2]};
 	uint64_t total;
-	return check(frame_run_bytes(points, views, count, plan.iq_pipeline ? 8u : 4u, frame_ring_bytes(), total), BeamformerLibErrorKind_FrameSizeOverflow);
+	return check(frame_run_bytes(points, views, count, plan.iq_pipeline ? 8u : 4u, frame_ring_bytes(), total, per_view), BeamformerLibErrorKind_FrameSizeOverflow);
 }
 
 bool push_data_common(const void *data, uint32_t data_size, uint32_t image_plane_tag, uint32_t slot, bool on_device)
@@ -276,6 +276,35 @@ bool push_views_common(const void *data, uint32_t data_size, const BeamformerHip
 	if (!run_fits_the_ring(pb, views, view_count)) return false;
 	if (!ensure_device()) return false;
 	return push_views(slot, data, data_size, views, view_count, on_device);
+}
+
+/* What a burst views call must satisfy that needs neither the RF nor a device: both counts, their product (every frame keeps its record),
+ * then the views push's checks of the list. */
+bool validate_burst_views(uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count, uint32_t slot)
+{
+	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(view_count != 0 && view_count <= BEAMFORMER_HIP_MAX_VIEWS, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check((uint64_t)frame_count * view_count <= BeamformerMaxBacklogFrames, BeamformerLibErrorKind_BufferOverflow)) return false;
+	return validate_views(views, view_count, slot);
+}
+
+/* A burst views push: the burst's checks of the RF, the views push's of the views, then the whole run against the ring -- all before the
+ * device is touched; frame_count == 1 goes the same way. */
+bool push_burst_views_common(const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count, uint32_t slot,
+                             bool on_device)
+{
+	Context &c = ctx();
+	if (!validate_burst_views(frame_count, views, view_count, slot)) return false;
+	const ParameterBlock &pb = c.blocks[slot];
+	if (!on_one_device("burst views push")) return false;
+	if (pb.shard_z_count) {
+		std::fprintf(stderr, "[beamformer] a view is not sharded: refused with the output shard set on parameter block %u\n", slot);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	if (!valid_rf_frame(pb, data, frame_size)) return false;
+	if (!run_fits_the_ring(pb, views, frame_count * view_count, frame_count)) return false;
+	if (!ensure_device()) return false;
+	return push_burst_views(slot, data, frame_size, frame_count, views, view_count, on_device);
 }
 
 template <typename T>
@@ -773,6 +802,39 @@ uint32_t beamformer_hip_get_last_views_info(BeamformerHipViewsInfo *out)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
 	return last_views_info(out);
+}
+
+uint32_t beamformer_hip_push_data_burst_views_with_compute(const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views,
+                                                           uint32_t view_count, uint32_t parameter_slot)
+{
+	return push_burst_views_common(data, frame_size, frame_count, views, view_count, parameter_slot, false);
+}
+
+uint32_t beamformer_hip_push_device_data_burst_views_with_compute(const void *device_data, uint32_t frame_size, uint32_t frame_count,
+                                                                  const BeamformerHipView *views, uint32_t view_count, uint32_t parameter_slot)
+{
+	return push_burst_views_common(device_data, frame_size, frame_count, views, view_count, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_describe_burst_views(uint32_t parameter_slot, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count,
+                                             BeamformerHipBurstViewsDescription *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !validate_burst_views(frame_count, views, view_count, parameter_slot)) return 0;
+	Context &c = ctx();
+	const ParameterBlock &pb = c.blocks[parameter_slot];
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	BurstViewsDecision route;
+	decide_burst_views(pb, plan, build_transmit_table(pb), view_grids(views, view_count).data(), view_count, c.das_path_mode, frame_count, route);
+	describe_burst_views_decision(route, view_count, out);
+	return 1;
+}
+
+uint32_t beamformer_hip_get_last_burst_views_info(BeamformerHipBurstViewsInfo *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
+	return last_burst_views_info(out);
 }
 
 uint32_t beamformer_hip_synchronize(void)

@@ -118,6 +118,10 @@ def _load():
         "beamformer_hip_push_device_data_views_with_compute": (u32, [vp, u32, C.POINTER(P.HipView), u32, u32]),
         "beamformer_hip_describe_views": (u32, [u32, C.POINTER(P.HipView), u32, C.POINTER(P.HipViewsDescription)]),
         "beamformer_hip_get_last_views_info": (u32, [C.POINTER(P.HipViewsInfo)]),
+        "beamformer_hip_push_data_burst_views_with_compute": (u32, [vp, u32, u32, C.POINTER(P.HipView), u32, u32]),
+        "beamformer_hip_push_device_data_burst_views_with_compute": (u32, [vp, u32, u32, C.POINTER(P.HipView), u32, u32]),
+        "beamformer_hip_describe_burst_views": (u32, [u32, u32, C.POINTER(P.HipView), u32, C.POINTER(P.HipBurstViewsDescription)]),
+        "beamformer_hip_get_last_burst_views_info": (u32, [C.POINTER(P.HipBurstViewsInfo)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -419,6 +423,44 @@ def last_views_info():
     """beamformer_hip_get_last_views_info: the newest views push's route, ids and whole-push stage times; waits for it."""
     info = P.HipViewsInfo()
     _check(library().beamformer_hip_get_last_views_info(C.byref(info)))
+    return info
+
+
+def beamform_burst_views(bp, rf_frames, views, filters=(), timeout_ms=-1, on_device_pointer=None):
+    """N RF frames on K grids in one call (beamformer_hip_push_data_burst_views_with_compute): `rf_frames` as beamform_burst() takes it,
+    `views` as beamform_views() does.  Returns a list of K lists of N arrays (Z, Y, X): [v][k] is (view v, RF frame k) -- the order the
+    frames are queued in, view-major."""
+    lib = _prepared(bp, filters, timeout_ms)
+    rf_frames = np.ascontiguousarray(rf_frames)
+    n = rf_frames.shape[0]
+    frame_size = rf_frames.nbytes // n
+    views = list(views)
+    array, count = _view_array(views)
+    if on_device_pointer is not None:
+        _check(lib.beamformer_hip_push_device_data_burst_views_with_compute(C.c_void_p(on_device_pointer), frame_size, n, array, count, 0))
+    else:
+        _check(lib.beamformer_hip_push_data_burst_views_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, n, array, count, 0))
+    flat = get_last_views([v for v in views for _ in range(n)])
+    return [flat[v * n:(v + 1) * n] for v in range(count)]
+
+
+def describe_burst_views(bp, n, views, filters=(), slot=0):
+    """What a burst views push of n RF frames on these grids would run (beamformer_hip_describe_burst_views): the description struct;
+    .rung is the ladder's rung, .path[k] view k's own single-frame decision, .reason says why.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    array, count = _view_array(views)
+    d = P.HipBurstViewsDescription()
+    _check(L.beamformer_hip_describe_burst_views(slot, n, array, count, C.byref(d)))
+    return d
+
+
+def last_burst_views_info():
+    """beamformer_hip_get_last_burst_views_info: the newest burst views push's route, ids and whole-push stage times; waits for it."""
+    info = P.HipBurstViewsInfo()
+    _check(library().beamformer_hip_get_last_burst_views_info(C.byref(info)))
     return info
 
 

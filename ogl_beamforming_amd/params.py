@@ -262,6 +262,18 @@ class HipViewsInfo(C.Structure):
                 ("decide_us", C.c_float)]
 
 
+class HipBurstViewsDescription(C.Structure):
+    _fields_ = [("rung", C.c_uint32), ("kernel_views", C.c_uint32), ("frame_kernel_views", C.c_uint32), ("das_launches", C.c_uint32),
+                ("stage_launches", C.c_uint32), ("frames_per_thread", C.c_uint32), ("min_frames", C.c_uint32),
+                ("path", C.c_int8 * HIP_MAX_VIEWS), ("reason", C.c_char * 160)]
+
+
+class HipBurstViewsInfo(C.Structure):
+    _fields_ = [("route", HipBurstViewsDescription), ("first_frame_id", C.c_uint32), ("frame_count", C.c_uint32), ("view_count", C.c_uint32),
+                ("stage_count", C.c_uint32), ("stage_kind", C.c_uint32 * HIP_MAX_TIMED_STAGES), ("stage_ms", C.c_float * HIP_MAX_TIMED_STAGES),
+                ("push_ms", C.c_float), ("decide_us", C.c_float)]
+
+
 class DasPath(enum.IntEnum):
     """BeamformerHipFrameTimings::das_path / BeamformerHipDasDescription::path (csrc/das_select.h)"""
     General = 0
