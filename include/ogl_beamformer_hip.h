@@ -397,6 +397,82 @@ typedef struct {
 /* The newest burst views push; waits for it to finish.  Fails when the newest push was not one or did not complete. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_burst_views_info(BeamformerHipBurstViewsInfo *out);
 
+/* ---- variants: ONE RF frame beamformed under K sets of DAS scalars per call (sound-speed autofocus, system-delay calibration, f-number
+ * tuning: the same RF under K candidate values, the sharpest or most coherent result kept) ----
+ * `data` is one RF frame under exactly the layout and size rules of beamformer_push_data_with_compute.  Everything except the three
+ * values comes from parameter block `parameter_slot`: frame k is the frame a single push of the same RF would give if the block's
+ * speed_of_sound, time_offset and f_number were variants[k]'s (time_offset is the BLOCK field, BeamformerParameters::time_offset: the
+ * delays of the block's filters are added to it exactly as the planner adds them to the block's own).  Queues variant_count frames of
+ * the block's own grid: they take consecutive frame ids, variant 0 first, lie contiguously in the frame ring (a run that would straddle
+ * the end of the ring starts again at offset 0), and beamformer_get_last_frames(out, size, variant_count) returns them oldest first.
+ *   - one upload, one RF-ring slot, ONE launch of the ingest and of every pre-DAS stage: only the DAS stage depends on the candidate;
+ *   - the parameter block is left alone: no field is written, no dirty bit set, no replan -- a single push afterwards gives the block's
+ *     own frame;
+ *   - every variant gets its own single-frame decision (beamformer_hip_describe_das's, of the block carrying its values).  Variants of
+ *     RCA-family blocks (Flash, RCA_TPW, RCA_VLS) that the general kernel would run take ONE DAS launch together (csrc/das_variants.hip:
+ *     grid x the 256-voxel tiles of the grid, grid y the variant, each block the general kernel's own loop under its variant's values, no
+ *     channel split) when variants x tiles number at least BeamformerHipVariantsDescription::min_tiles or the variants at least
+ *     ::min_variants (the launch has a floor of about 36 us: it pays from 8 candidates, or 4 on a full 256 x 256 plane); such a frame is within float
+ *     rounding of its single push, and its bits depend neither on the other variants nor on their order.  Every other variant -- other
+ *     families, grids on which a faster kernel runs, planes the row-end rule cuts -- runs its single-frame kernel(s) on the shared DAS
+ *     input under its own derived plan state, and IS the single push's frame bit for bit.  beamformer_hip_describe_variants says which
+ *     route, and why;
+ *   - validation is the single push's, with the same error kinds.  variant_count == 0 and variant_count > BEAMFORMER_HIP_MAX_VARIANTS
+ *     are BufferOverflow; variants == NULL, a field that is not finite or speed_of_sound <= 0 is InvalidAccess (with a line on stderr);
+ *     several devices (beamformer_hip_set_devices, count > 1) or an output shard on the block is InvalidAccess, as for a views push; the
+ *     frames together exceeding the frame ring is FrameSizeOverflow; device memory that cannot be grown is RFDataSizeOverflow.  All of
+ *     that is judged before a device is touched and before an id is taken: a refused push queues nothing.  A push that fails after that
+ *     leaves a tombstone under every one of its ids (das path flag FailViewsDas, 0x2000, fails this push's DAS step as it fails a views
+ *     push's);
+ *   - variant_count == 1 goes through the same code;
+ *   - one event set per push: every variant appears in beamformer_compute_timings and beamformer_hip_get_last_frame_timings with the
+ *     push's stage times divided by variant_count; frame graphs: the push runs as direct launches; pair counting: the geometry-only
+ *     count runs per variant (f_number changes it);
+ *   - beamformer_hip_get_last_burst_info, _views_info, _burst_views_info and _readi_image_info refuse this push, and
+ *     beamformer_hip_get_last_variants_info refuses theirs. */
+#define BEAMFORMER_HIP_MAX_VARIANTS 64u
+typedef struct {
+	float speed_of_sound;               /* m/s, > 0 */
+	float time_offset;                  /* s, as BeamformerParameters::time_offset */
+	float f_number;
+} BeamformerHipDasVariant;
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_data_variants_with_compute(const void *data, uint32_t size, const BeamformerHipDasVariant *variants,
+                                                                              uint32_t variant_count, uint32_t image_plane_tag, uint32_t parameter_slot);
+/* ... for RF that already resides on the library's device (beamformer_hip_push_device_data_with_compute's rules; the RF of a variants
+ * push is always ingested into the RF ring, never read in place) */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_push_device_data_variants_with_compute(const void *device_data, uint32_t size,
+                                                                                     const BeamformerHipDasVariant *variants, uint32_t variant_count,
+                                                                                     uint32_t image_plane_tag, uint32_t parameter_slot);
+
+typedef struct {
+	uint32_t kernel_variants;       /* variants das_variants.hip takes, all in one launch (0: none) */
+	uint32_t fused_launches;        /* launches of das_variants.hip: 1 or 0 */
+	uint32_t das_launches;          /* DAS launches of the whole push: that one, plus the single-frame launch(es) of every other variant */
+	uint32_t kernel_tiles;          /* blocks of the fused launch: kernel_variants x the grid's 256-voxel tiles */
+	uint32_t min_tiles;             /* the variants kernel takes the eligible variants when variants x tiles reach this (csrc/das_select.h: kVariantsMinTiles) */
+	uint32_t min_variants;          /* ... or when they number at least this (kVariantsMinVariants) */
+	int8_t   path[BEAMFORMER_HIP_MAX_VARIANTS];    /* per variant: its OWN single-frame decision (BeamformerHipFrameTimings::das_path numbering; -1 / -2
+	                                                  as BeamformerHipDasDescription::path), whichever route the push takes */
+	uint8_t  taken[BEAMFORMER_HIP_MAX_VARIANTS];   /* per variant: 1 = in the fused launch */
+	char     reason[160];           /* why this route */
+} BeamformerHipVariantsDescription;
+/* What a variants push of these candidates on a parameter block would run, under the current das path mode.  Needs no device and leaves
+ * the block as it is. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_variants(uint32_t parameter_slot, const BeamformerHipDasVariant *variants, uint32_t variant_count,
+                                                                BeamformerHipVariantsDescription *out);
+
+typedef struct {
+	BeamformerHipVariantsDescription route;   /* of the push that ran */
+	uint32_t first_frame_id, variant_count;
+	uint32_t stage_count;
+	uint32_t stage_kind[BEAMFORMER_HIP_MAX_TIMED_STAGES];  /* BeamformerShaderKind; ingest = 0xFFFF */
+	float    stage_ms[BEAMFORMER_HIP_MAX_TIMED_STAGES];    /* hipEvent pairs around each stage of the WHOLE push */
+	float    variants_ms;                                  /* first event to last event */
+	float    decide_us;                                    /* host time the push spent deciding its variants' routes */
+} BeamformerHipVariantsInfo;
+/* The newest variants push; waits for it to finish.  Fails when the newest push was not a variants push or did not complete. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_variants_info(BeamformerHipVariantsInfo *out);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */
@@ -511,9 +587,12 @@ typedef enum {
 	BeamformerHipDasPath_NoBurstKernel    = 0x400,/* flag: a burst (above) runs the single-frame DAS kernel once per frame also where das_burst.hip would take it */
 	BeamformerHipDasPath_NoViewsKernel    = 0x800,/* flag: a views push runs every view's single-frame DAS kernel also where das_views.hip would take it */
 	BeamformerHipDasPath_PreferViewsKernel = 0x1000,/* flag: das_views.hip takes the eligible views however few their tiles (for tests) */
-	BeamformerHipDasPath_FailViewsDas     = 0x2000,/* flag: a views push FAILS (InvalidAccess) at its DAS stage, after its ids are taken and its frames placed and
-	                                                  before anything is launched there -- what a failed launch leaves behind (a tombstone under every id of
-	                                                  the push), reachable without a device fault (for tests; no other push is affected) */
+	BeamformerHipDasPath_FailViewsDas     = 0x2000,/* flag: a views push (a burst views push, a variants push) FAILS (InvalidAccess) at its DAS stage, after its
+	                                                  ids are taken and its frames placed and before anything is launched there -- what a failed launch leaves
+	                                                  behind (a tombstone under every id of the push), reachable without a device fault (for tests; no other
+	                                                  push is affected) */
+	BeamformerHipDasPath_NoVariantsKernel = 0x4000,/* flag: a variants push runs every variant's single-frame DAS kernel also where das_variants.hip would take it */
+	BeamformerHipDasPath_PreferVariantsKernel = 0x8000,/* flag: das_variants.hip takes the eligible variants however few their tiles (for tests) */
 } BeamformerHipDasPath;
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_das_path(uint32_t mode);
 /* Environment variables the library reads (none is needed in production):

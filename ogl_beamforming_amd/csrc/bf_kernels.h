@@ -124,6 +124,23 @@ typedef struct {
 	uint32_t view_count, pad;
 } BfViewsArgs;
 
+/* variants form of the general kernel (das_variants.hip): one DAS input beamformed on the launch's own grid under several sets of DAS
+ * scalars.  A row holds what differs from variant to variant -- the five fields of BfDasArgs that speed_of_sound, time_offset and
+ * f_number reach, as the host fills them for a block carrying those values (das_select.cpp: decide_das), and the variant's frame;
+ * everything else is the launch's BfDasArgs.  32 bytes, read through wave-uniform (scalar) loads. */
+typedef struct {
+	float    speed_of_sound, inv_speed_of_sound;
+	float    time_offset;             /* resolved: the block field plus the filters' delays */
+	float    f_number;
+	float    edge_margin;
+	uint32_t pad0;
+	uint64_t out_offset;              /* bytes from BfDasArgs.out to the variant's frame */
+} BfVariantRow;
+#ifdef __cplusplus
+static_assert(sizeof(BfVariantRow) == 32 && offsetof(BfVariantRow, out_offset) == 24,
+              "BfVariantRow: 32 bytes, the same on the host that fills it and in the kernel that reads it");
+#endif
+
 /* channel-paired staged kernel (uniform = 2): the LDS holds the 64-element blocks (two channels' 32-sample windows) of at most this
  * many transmits at a time -- a multiple of 4 whose block indices, plus the two elements in front, stay below 4096 (the tap address
  * is a 16-bit shift of the element index) */
@@ -348,6 +365,9 @@ hipError_t bf_launch_das_views(const BfDasArgs *a, const BfViewsArgs *v, uint32_
 /* das_burst.hip: the burst kernel's frame slots on the views kernel's tiles -- RCA family, no channel split; frame f of the view of row r
  * reads a->rf + f * b->rf_stride and writes a->out + r.out_offset + f * r.out_stride (b->out_stride is not read) */
 hipError_t bf_launch_das_burst_views(const BfDasArgs *a, const BfBurstArgs *b, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s);
+/* das_variants.hip: RCA family, 256-voxel tiles in a walk order general_tile_at knows (depth_major 0 - 2), no channel split, the whole
+ * grid; variant r of the launch runs under rows[r] (device) and writes a->out + rows[r].out_offset */
+hipError_t bf_launch_das_variants(const BfDasArgs *a, const BfVariantRow *rows, uint32_t variant_count, hipStream_t s);
 hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);
 hipError_t bf_launch_das_staged_tables(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s);

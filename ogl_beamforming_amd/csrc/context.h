@@ -66,15 +66,16 @@ struct TimingSlot {
 	bool       failed = false;            /* the push that owns this slot did not complete */
 };
 
-/* the newest multi-frame push (executor.cpp push_frames): what beamformer_hip_get_last_burst_info / _views_info report, each of its own kind */
+/* the newest multi-frame push (executor.cpp push_frames): what beamformer_hip_get_last_burst_info / _views_info / _variants_info report, each of its own kind */
 struct PushRecord {
-	enum Kind { None, Burst, Views, Image, BurstViews } kind = None;
+	enum Kind { None, Burst, Views, Image, BurstViews, Variants } kind = None;
 	uint64_t      first_id = 0;
 	uint32_t      count = 0, events_slot = 0;
 	BurstDecision burst;                      /* Burst: its route */
 	BeamformerHipViewsDescription views{};    /* Views: its route, and the host time spent deciding it */
 	ReadiImageDecision image;                 /* Image: its route, and the RF frames it compounded */
 	BeamformerHipBurstViewsDescription burst_views{};   /* BurstViews: its route; rf_frames RF frames on count / rf_frames views */
+	BeamformerHipVariantsDescription variants{};        /* Variants: its route */
 	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
 };
@@ -101,6 +102,20 @@ struct ImagePlanState {
 	ParameterBlock pb;
 	uint64_t       source_generation = 0;
 };
+
+/* A variants push's derived block (das_select.h: derive_variant) on one device: the DAS decision of the block with `variant`'s three
+ * values -- BfDasArgs, the part list, the staged / factored / HERCULES geometry planned with them -- kept with the block's own plan
+ * state and reused while the triple, the block's plan (source_generation), the path mode and the hooks are what it was decided for; a
+ * replan of the block drops them all.  The device tables a DAS launch reads besides (transmits, sparse elements, READI matrix) do not
+ * depend on the triple: the derived state runs on the block's own (executor.cpp: DasJob::ps), and the tables the staged and HERCULES
+ * kernels build per launch are built from the job's own BfDasArgs. */
+struct VariantPlanState {
+	DasVariant variant{};
+	std::vector<DasDecision> parts;
+	uint64_t   source_generation = 0, hooks_version = 0;
+	uint32_t   mode = 0;
+};
+constexpr size_t kMaxVariantPlans = 256;          /* per block: four pushes of BEAMFORMER_HIP_MAX_VARIANTS; a push that would exceed it starts the list afresh */
 
 constexpr uint32_t kTimingSlots = 32;    /* beamformer_compute_stats.c: 32-frame table */
 constexpr uint32_t kStageIngest    = 0xFFFF;
@@ -136,6 +151,7 @@ struct Device {
 	hipStream_t  own_stream = nullptr, stream = nullptr;
 	PlanState    plans[BeamformerMaxParameterBlocks];
 	ImagePlanState image_plans[BeamformerMaxParameterBlocks];  /* READI image pushes: the derived FORCES block of plans[k] */
+	std::list<VariantPlanState> variant_plans[BeamformerMaxParameterBlocks];   /* variants pushes: derived blocks of plans[k] */
 	DeviceBuffer raw_staging[BeamformerMaxRawDataFramesInFlight];
 	UploadSlot   upload[BeamformerMaxRawDataFramesInFlight];
 	hipStream_t  copy_stream = nullptr;                        /* H2D of frame n+1 overlaps compute of frame n */
@@ -236,6 +252,9 @@ bool last_views_info(BeamformerHipViewsInfo *out);
 bool push_burst_views(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count,
                       bool data_on_device);
 bool last_burst_views_info(BeamformerHipBurstViewsInfo *out);
+bool push_variants(uint32_t block, const void *data, uint32_t size, const DasVariant *variants, uint32_t variant_count, bool data_on_device);
+bool last_variants_info(BeamformerHipVariantsInfo *out);
+void describe_variants_decision(const VariantsDecision &route, uint32_t variant_count, BeamformerHipVariantsDescription *out);
 void describe_burst_views_decision(const BurstViewsDecision &route, uint32_t view_count, BeamformerHipBurstViewsDescription *out);
 std::vector<ViewGrid> view_grids(const BeamformerHipView *views, uint32_t view_count);     /* the grids decide_views takes */
 void describe_views_decision(const ViewsDecision &route, uint32_t view_count, BeamformerHipViewsDescription *out);

@@ -1189,6 +1189,113 @@ void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::v
 	}
 }
 
+void derive_variant(const ParameterBlock &pb, const Plan &plan, const DasVariant &variant, ParameterBlock &derived_pb, Plan &derived_plan)
+{
+	derived_pb = pb;
+	BeamformerParameters &bp = derived_pb.parameters;
+	bp.speed_of_sound = variant.speed_of_sound;
+	bp.time_offset    = variant.time_offset;
+	bp.f_number       = variant.f_number;
+	derived_plan = Plan{};
+	derived_plan.stages = plan.stages;
+	derived_plan.das_index = plan.das_index; derived_plan.iq_pipeline = plan.iq_pipeline; derived_plan.pipeline_data_kind = plan.pipeline_data_kind;
+	derived_plan.channels = plan.channels; derived_plan.acquisitions = plan.acquisitions; derived_plan.raw_samples = plan.raw_samples;
+	derived_plan.das_samples = plan.das_samples; derived_plan.das_sampling_frequency = plan.das_sampling_frequency;
+	derived_plan.decimation = plan.decimation; derived_plan.das_sparse = plan.das_sparse;
+	derived_plan.hadamard_base_order = plan.hadamard_base_order; derived_plan.intermediate_bytes = plan.intermediate_bytes;
+	std::memcpy(derived_plan.output_points, plan.output_points, sizeof(plan.output_points));
+	std::memcpy(derived_plan.das_voxel_transform, plan.das_voxel_transform, sizeof(plan.das_voxel_transform));
+	/* planner.cpp: time_offset = bp.time_offset, then += every Filter / Demodulate / Hilbert stage's delay on the way to DAS */
+	float time_offset = variant.time_offset;
+	for (int i = 0; i < plan.das_index && i < (int)plan.stages.size(); i++) {
+		const Stage &st = plan.stages[(size_t)i];
+		if (st.kind == BeamformerShaderKind_Filter || st.kind == BeamformerShaderKind_Demodulate || st.kind == BeamformerShaderKind_Hilbert)
+			time_offset += st.filter.time_delay;
+	}
+	derived_plan.das_time_offset = time_offset;
+}
+
+void decide_variants(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const DasVariant *variants, uint32_t variant_count,
+                     uint32_t mode, VariantsDecision &out, const std::vector<DasDecision> *const *known)
+{
+	out = VariantsDecision{};
+	out.parts.resize(variant_count);
+	out.taken.assign(variant_count, 0);
+	if (plan.das_index < 0) { out.reason = "no DAS stage runs: the frames are cleared"; return; }
+	const uint32_t zcount = plan.output_points[2];
+	std::vector<uint8_t> eligible(variant_count, 0);
+	uint32_t candidates = 0, zero = 0, cut = 0, faster = 0;
+	int family = BF_DAS_RCA, faster_path = DasPath_General;
+	ParameterBlock derived_pb;
+	Plan derived_plan;
+	for (uint32_t v = 0; v < variant_count; v++) {
+		std::vector<DasDecision> &parts = out.parts[v];
+		if (known && known[v]) {
+			parts = *known[v];
+		} else {
+			derive_variant(pb, plan, variants[v], derived_pb, derived_plan);
+			decide_das_parts(derived_pb, derived_plan, tx, 0, zcount, mode, parts);
+		}
+		const DasDecision &head = main_part(parts);
+		family = head.a.family;
+		for (const DasDecision &d : parts) out.das_launches += d.path != DasPath_Zero;
+		if (head.path == DasPath_Zero) { zero++; continue; }
+		if (parts.size() != 1) { cut++; continue; }
+		if (head.path != DasPath_General) { faster++; faster_path = head.path; continue; }
+		if (head.a.family != BF_DAS_RCA || (mode & 0x4000u)) continue;
+		eligible[v] = 1; candidates++;
+	}
+	/* the general kernel's tiles at one thread per voxel (decide_das under flag 0x10), the same for every variant: the grid is the block's */
+	uint64_t tiles = 0;
+	if (candidates) {
+		DasDecision whole;
+		decide_das(pb, plan, tx, 0, zcount, mode | 0x10u, whole);
+		out.a = whole.general;
+		if (out.a.depth_major == 3u) { out.a.depth_major = 2u; out.a.band_rows = 1; }      /* a view plane's balanced bands deal padded ids to the XCDs: here y fastest */
+		tiles = (uint64_t)out.a.blocks[0] * out.a.blocks[1] * out.a.blocks[2];
+		if (tiles == 0 || tiles > 0x7FFFFFFFu) candidates = 0;                            /* (grid x: such a grid runs its own launches) */
+	}
+	char text[160];
+	const bool take = candidates && (tiles * candidates >= kVariantsMinTiles || candidates >= kVariantsMinVariants || (mode & 0x8000u));
+	if (take) {
+		uint32_t row_ends = 0;
+		for (uint32_t v = 0; v < variant_count; v++) {
+			if (!eligible[v]) continue;
+			const BfDasArgs &g = out.parts[v][0].general;      /* the five fields as decide_das fills them for the derived block */
+			BfVariantRow r{};
+			r.speed_of_sound = g.speed_of_sound; r.inv_speed_of_sound = g.inv_speed_of_sound;
+			r.time_offset = g.time_offset; r.f_number = g.f_number; r.edge_margin = g.edge_margin;
+			if (out.rows.empty()) {
+				out.a.speed_of_sound = g.speed_of_sound; out.a.inv_speed_of_sound = g.inv_speed_of_sound;
+				out.a.time_offset = g.time_offset; out.a.f_number = g.f_number; out.a.edge_margin = g.edge_margin;
+			}
+			row_ends |= g.row_ends;
+			out.taken[v] = 1;
+			out.rows.push_back(r);
+			out.das_launches--;                                                 /* its single-frame launch does not run */
+		}
+		out.kernel_variants = candidates; out.kernel_tiles = (uint32_t)(tiles * candidates > 0xFFFFFFFFull ? 0xFFFFFFFFull : tiles * candidates);
+		out.das_launches++;
+		out.a.split_shift = 0; out.a.row_ends = row_ends;
+		out.a.z_first = 0; out.a.z_count = out.a.size[2];
+		std::snprintf(text, sizeof(text), "RCA family on the general kernel: %u of %u variants x %u tiles in one launch of the variants kernel", candidates, variant_count, (uint32_t)tiles);
+	} else if (zero == variant_count) {
+		std::snprintf(text, sizeof(text), "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared");
+	} else if (mode & 0x4000u) {
+		std::snprintf(text, sizeof(text), "das path flag 0x4000: each variant's single-frame kernel on the shared DAS input was asked for");
+	} else if (family != BF_DAS_RCA) {
+		std::snprintf(text, sizeof(text), "the variants kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per variant");
+	} else if (!candidates) {
+		if (faster) std::snprintf(text, sizeof(text), "single frames on this grid run the %s: it runs once per variant on the shared DAS input", das_path_name(faster_path));
+		else if (cut) std::snprintf(text, sizeof(text), "the row-end rule cuts the frames into parts run by different kernels: the single-frame launches once per variant");
+		else          std::snprintf(text, sizeof(text), "no variant the variants kernel can take: each runs its own launch");
+	} else {
+		std::snprintf(text, sizeof(text), "fewer than %u eligible variants and fewer than %u variants x tiles: the single-frame general kernel once per variant",
+		              kVariantsMinVariants, kVariantsMinTiles);
+	}
+	out.reason = text;
+}
+
 uint32_t row_end_planes(const std::vector<DasDecision> &parts)
 {
 	uint32_t n = 0;

@@ -176,6 +176,48 @@ struct BurstViewsDecision {
 void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const ViewGrid *views, uint32_t view_count,
                         uint32_t mode, uint32_t frame_count, BurstViewsDecision &out);
 
+/* das_variants.hip takes the eligible variants of a push when they number at least kVariantsMinVariants, or when variants x 256-voxel
+ * tiles of the block's grid number at least kVariantsMinTiles: each the smallest measured count from which the push on the kernel is not
+ * slower than the push on the per-variant route by more than three times that route's run-to-run spread, in every row at that count and
+ * above (tools/variants_rate.py, profiles/variants_rate.json: min_variants_from_this_table, min_tiles_from_this_table; the tool's runs on
+ * the MI355X gave 4 and 8 variants, 512 and 1024 tiles -- four variants on a patch, two on the plane are within a few us either way --
+ * and the larger figures are in force, with which the rule holds in every run).  The break-even was expected to follow variants x tiles
+ * alone, from about 2; measured, it follows the NUMBER OF VARIANTS: the fused launch's DAS segment has a floor of about 36 us whatever it
+ * computes (its table transfer, and one thread per voxel walking all channels where the single-frame general kernel splits them over up
+ * to 16 waves), a single-frame launch costs 9 - 14 us and each further one 6 - 11 us more.  DESIGN 3.1f has the table. */
+constexpr uint32_t kVariantsMinVariants = 8;
+constexpr uint32_t kVariantsMinTiles = 1024;
+
+/* One candidate of a variants push: BeamformerHipDasVariant. */
+struct DasVariant {
+	float speed_of_sound, time_offset, f_number;   /* as the BeamformerParameters fields of those names (time_offset: the block field, not the plan's sum) */
+};
+/* The block with the three fields replaced, and its plan: `plan` -- the block's own resolved plan -- with das_time_offset resolved anew,
+ * in the planner's own order of additions (planner.cpp: the block field, then every pre-DAS filter's delay in stage order), so that it is
+ * the float a block carrying that value plans to.  The three values reach nothing else of a plan, and of a frame only the DAS decision
+ * (decide_das: inv_speed_of_sound, speed_of_sound, time_offset, f_number, edge_margin, and the kernel choices and tables that follow from
+ * them).  The derived plan leaves out the Hadamard matrices, which no DAS decision reads. */
+void derive_variant(const ParameterBlock &pb, const Plan &plan, const DasVariant &variant, ParameterBlock &derived_pb, Plan &derived_plan);
+
+/* How a variants push runs (beamformer_hip_describe_variants): every variant gets decide_das_parts of its derived block -- its
+ * single-frame decision, parts[v] (known[v] given: that decision from an earlier call for the same block, plan, variant, mode and hooks,
+ * taken as it is).  A variant is ELIGIBLE for das_variants.hip when that decision is one part on the general kernel, the family is RCA
+ * and mode does not carry BeamformerHipDasPath_NoVariantsKernel; the eligible variants run in ONE launch when they, times the 256-voxel
+ * tiles of the grid (no channel split), number at least kVariantsMinTiles, when they number at least kVariantsMinVariants, or when mode
+ * carries BeamformerHipDasPath_PreferVariantsKernel.
+ * Every other variant runs its single-frame launch(es) on the shared DAS input. */
+struct VariantsDecision {
+	std::vector<std::vector<DasDecision>> parts;      /* per variant */
+	std::vector<uint8_t>      taken;                  /* per variant: 1 = in the variants kernel's launch */
+	std::vector<BfVariantRow> rows;                   /* the taken variants, in variant order (out_offset: filled by the executor) */
+	uint32_t    kernel_variants = 0, kernel_tiles = 0, das_launches = 0;      /* kernel_tiles: blocks of the fused launch */
+	BfDasArgs   a{};                                  /* the variants kernel's arguments: the general kernel's on 256-voxel tiles, no channel split;
+	                                                     row_ends the OR over the taken variants */
+	std::string reason;
+};
+void decide_variants(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &transmits, const DasVariant *variants, uint32_t variant_count,
+                     uint32_t mode, VariantsDecision &out, const std::vector<DasDecision> *const *known = nullptr);
+
 /* READI image (beamformer_hip_push_data_readi_image_with_compute).  READI_FORCES is FORCES with transmit element
  * tx_group * acquisition_count + tx_event and every term signed by Hadamard[readi_group * G + tx_group] (das.glsl:288-366), and everything
  * behind the sign is linear in the samples: the sum of a sequence's partial frames is ONE frame of the DERIVED block -- the same block with

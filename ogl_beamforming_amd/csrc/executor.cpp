@@ -180,6 +180,7 @@ static void release_one_device(Device &d)
 	for (auto &b : d.scratch) b.release();
 	d.ring.release(); d.pair_counter.release(); d.minmax_scratch.release(); d.sum_scratch.release();
 	d.hercules_table.release(); d.hercules_pairs.release(); for (auto &b : d.burst_stage) b.release(); d.multi = PushRecord{};
+	for (auto &vp : d.variant_plans) vp.clear();
 	for (auto &ip : d.image_plans) { ip.ps.transmits.release(); ip.ps.sparse.release(); ip.ps.valid = false; ip.ps.das_parts.clear(); }
 	d.readi_decoded.release(); d.das_decoded_bytes = 0;
 	d.views_table.release();
@@ -299,6 +300,7 @@ static PlanState *commit_block(uint32_t block)
 	ps.valid = true;
 	ps.generation++;
 	ps.das_parts.clear();
+	d.variant_plans[block].clear();            /* a variants push's derived decisions were made for the plan that has just gone */
 	return &ps;
 }
 
@@ -682,6 +684,9 @@ struct StageWalk {
 	const uint32_t      *readi_groups = nullptr;  /* a READI sweep: frame k is beamformed with readi_group = readi_groups[k] (validated: lib_api.cpp) */
 	ImagePlanState      *image = nullptr;         /* a READI image push: the `frames` DAS inputs are decoded across the acquisitions by readi_groups
 	                                                 (readi_decode.hip) and the DAS stage writes ONE frame from that, under this derived block */
+	const VariantsDecision   *variants = nullptr;      /* a variants push: `frames` is 1 and the DAS stage writes variant_count frames of the block's grid
+	                                                      from its one input, frame k under the derived decision variants->parts[k], by this route */
+	uint32_t                  variant_count = 0;
 };
 
 /* One frame the DAS stage writes: what it reads, where it writes, the parts that compute it (das_select.h) on which grid, whether the
@@ -695,6 +700,9 @@ struct DasJob {
 	bool            fused;
 	uint32_t        path;
 	int32_t         readi_group;    /* >= 0: the job's launches run with this BfDasArgs::readi_group (a READI sweep's frame); -1: the block's */
+	PlanState      *ps;             /* the plan state the job's launches run under -- whose device tables they bind: the block's own; a READI image's
+	                                   derived block's.  (A variant's derived decision is `parts`; the tables it binds do not depend on its values
+	                                   and are the block's: context.h, VariantPlanState) */
 };
 
 /* The burst kernel (das_burst.hip): N frames, frame k at k * the strides of input and output, in one launch. */
@@ -736,6 +744,33 @@ static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route,
 	b.burst.frame_count = N; b.burst.rf_stride = in_stride; b.burst.out_stride = out_stride;
 	b.groups = (const uint32_t *)d.views_table.ptr;
 	if (ok) ok &= HIP_OK(bf_launch_das_readi_sweep(&a, &b, s));
+	return ok;
+}
+
+/* The variants kernel (das_variants.hip): the variants the route has it take, from the ONE DAS input on the block's grid, in one launch --
+ * their rows go the way a views push's table goes (the same buffers: push_frames grew them).  Variant k's job is jobs[k]. */
+static bool launch_variants_kernel(PlanState *ps, const VariantsDecision &route, const DasJob *jobs, uint32_t K, hipStream_t s)
+{
+	Device &d = *g_context.cur;
+	bool ok = true;
+	const uint32_t n = route.kernel_variants;
+	if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
+	BfVariantRow *rows = (BfVariantRow *)d.views_pinned;
+	for (uint32_t k = 0, r = 0; k < K; k++) {
+		if (!route.taken[k]) continue;
+		rows[r] = route.rows[r];
+		rows[r].out_offset = (uint64_t)(jobs[k].out - jobs[0].out);
+		r++;
+	}
+	void *mapped = nullptr;
+	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
+	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)(sizeof(BfVariantRow) * n), s));
+	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
+	ok &= d.views_copy_pending;
+	BfDasArgs a = route.a;
+	a.rf = jobs[0].in; a.out = jobs[0].out;
+	bind_tables(ps, a);
+	if (ok) ok &= HIP_OK(bf_launch_das_variants(&a, (const BfVariantRow *)d.views_table.ptr, n, s));
 	return ok;
 }
 
@@ -817,7 +852,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	hipStream_t s = d.stream;
 	TimingSlot &t = w.t;
 	const uint32_t N = w.frames;
-	const uint32_t F = w.burst_views ? w.view_count * N : w.views ? w.view_count : w.image ? 1u : N;          /* frames the walk queues */
+	const uint32_t F = w.burst_views ? w.view_count * N : w.views ? w.view_count : w.variants ? w.variant_count : w.image ? 1u : N;   /* frames the walk queues */
 	const uint32_t per_view = w.burst_views ? N : 1u;      /* frames of a view: job v * per_view + k is (view v, RF frame k) */
 	PlanState *das_ps = w.image ? &w.image->ps : ps;        /* whose tables and decision the DAS launches run with */
 
@@ -870,7 +905,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			d.das_input_stride = N > 1 ? cur_stride : 0; d.das_input_frames = N;
 			/* (Flag 0x2000: a views push's step fails here, as a refused launch would -- the only way to a views push's tombstones that
 			 * needs no device fault: everything a caller can get wrong is refused before the ids are taken) */
-			if (w.views && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
+			if ((w.views || w.variants) && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
 			if (zcount == 0) break;      /* more devices than planes: this device holds an empty slab of the frame */
 
 			/* ---- the jobs.  Which kernel, with which geometry: one table of rules (das_select.cpp), for a single push and a burst computed
@@ -879,7 +914,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 			 * concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
 			if (F > 1) many.resize(F);
 			jobs = F > 1 ? many.data() : &one;
-			const std::vector<DasDecision> *cached = w.views ? nullptr : w.image ? &frame_das_parts(das_ps, w.image->pb, zfirst, zcount)
+			const std::vector<DasDecision> *cached = w.views || w.variants ? nullptr : w.image ? &frame_das_parts(das_ps, w.image->pb, zfirst, zcount)
 			                                                              : &frame_das_parts(ps, pb, zfirst, zcount);
 			if (w.image && main_part(*cached).path != DasPath_Zero) {
 				/* ---- 0. a READI image push: the N DAS inputs decoded across the acquisitions, its own segment directly before DAS; the
@@ -898,8 +933,10 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 				j.out = (char *)d.ring.ptr + d.frames[(first + k) % d.frames.size()].offset;
 				j.readi_group = w.readi_groups && !w.image ? (int32_t)w.readi_groups[k] : -1;
 				/* (a burst views push: `fused` also names the jobs the views kernel covers per RF frame, rung 2) */
-				if (w.views) { j.parts = &w.views_route->parts[view]; j.z_first = 0; j.points = w.views[view].output_points; j.fused = w.views_route->taken[view] != 0; }
-				else         { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
+				j.ps = das_ps;
+				if (w.views)         { j.parts = &w.views_route->parts[view]; j.z_first = 0; j.points = w.views[view].output_points; j.fused = w.views_route->taken[view] != 0; }
+				else if (w.variants) { j.parts = &w.variants->parts[k]; j.z_first = zfirst; j.points = points; j.fused = w.variants->taken[k] != 0; }
+				else                 { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
 				const DasDecision &head = main_part(*j.parts);
 				j.path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
 				any_fused     |= j.fused;
@@ -916,6 +953,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 				for (uint32_t k = 0; k < N && ok; k++) ok &= launch_views_kernel(ps, *w.views_route, jobs + k, w.view_count, s, N);
 			} else {
 				ok &= w.views        ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
+				    : w.variants     ? launch_variants_kernel(ps, *w.variants, jobs, F, s)
 				    : w.readi_groups ? launch_readi_sweep_kernel(ps, *w.route, jobs[0], w.readi_groups, N, cur_stride, frame0->bytes, s)
 				                     : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
 			}
@@ -930,10 +968,10 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 					ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
 				}
 				const DasDecision &head = main_part(*j.parts);
-				ok &= launch_frame_parts(das_ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.readi_group);
+				ok &= launch_frame_parts(j.ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.readi_group);
 			}
 			/* ---- 3. geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is
-			 * the same for every job of a run of jobs with the same parts (a burst: one run; a views push: one per view): it runs once,
+			 * the same for every job of a run of jobs with the same parts (a burst: one run; a views push: one per view; a variants push: one per variant -- f_number changes the count): it runs once,
 			 * into the counter of the run's last frame, and the run's other frames' counters are copies -- the newest 32 frames only */
 			if (c.count_pairs && any_counted) {
 				segment(t, (uint32_t)st.kind, s);
@@ -951,7 +989,7 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 						if (!ok || dd.path == DasPath_Zero) continue;
 						BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
 						count.rf = j.in; count.out = j.out + (uint64_t)(dd.z_first - j.z_first) * head.a.size[0] * head.a.size[1] * voxel_bytes;
-						bind_tables(das_ps, count);
+						bind_tables(j.ps, count);
 						if (j.readi_group >= 0) count.readi_group = (uint32_t)j.readi_group;
 						count.pair_counter = mine;
 						ok &= HIP_OK(bf_launch_das_count(&count, s));
@@ -1365,10 +1403,12 @@ struct FramesPush {
 	const ReadiImageDecision *image_route = nullptr;
 	uint64_t        decoded_bytes = 0;
 	const BurstViewsDecision *burst_views = nullptr;   /* a burst views push: `frames` = rf_frames x its views, view-major; views_route: its per-view part */
+	const VariantsDecision   *variants = nullptr;      /* a variants push: its route; `frames` variants of `points` */
 };
 
 /* A push of several frames with ONE upload and ONE event set (one device) -- a burst: N RF frames, N frames; a views push: one RF frame
- * on K grids; a burst views push: N RF frames on K grids, N x K frames view-major (frame v * N + k: view v, RF frame k), by the ladder of
+ * on K grids; a variants push: one RF frame on the block's grid under K sets of DAS scalars (das_variants.hip for the variants
+ * decide_variants gives it, every other variant its own launch(es) under its derived decision); a burst views push: N RF frames on K grids, N x K frames view-major (frame v * N + k: view v, RF frame k), by the ladder of
  * decide_burst_views -- its fused launch (das_burst_views.hip), or per RF frame the views push's DAS step, or every frame its own launch(es).
  *   RF        one upload into one pinned slot -- over the copy engine into device staging when it is large, read in place over PCIe when
  *             small, by kOverlapBytes applied to the whole upload -- and ONE slot of the RF ring, frame k at k * rf_stride with 64 spare
@@ -1415,7 +1455,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	}
 	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
 	if (m.image) fits = fits && d.readi_decoded.ensure(round_up(m.decoded_bytes, 64) + 64);
-	if ((m.views_route && m.views_route->kernel_views) || (m.readi_groups && m.burst && m.burst->burst_kernel) || m.image) {
+	if ((m.views_route && m.views_route->kernel_views) || (m.variants && m.variants->kernel_variants) || (m.readi_groups && m.burst && m.burst->burst_kernel) || m.image) {
 		/* (one size for both users: a sweep's BEAMFORMER_HIP_MAX_BURST_FRAMES group ids are 4 KiB of it) */
 		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
 		fits = fits && d.views_table.ensure(table_bytes);
@@ -1460,7 +1500,8 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
 	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
 	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_step, (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size), m.stage, m.stage_stride, t,
-	                                                 m.burst, m.views, m.views ? F / (m.burst_views ? N : 1u) : 0u, m.views_route, m.burst_views, m.readi_groups, m.image});
+	                                                 m.burst, m.views, m.views ? F / (m.burst_views ? N : 1u) : 0u, m.views_route, m.burst_views, m.readi_groups, m.image,
+	                                                 m.variants, m.variants ? F : 0u});
 	finish_upload(u, overlap, s);
 	if (!done) return false;
 
@@ -1471,6 +1512,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	if (m.burst)            r.burst = *m.burst;
 	else if (m.image_route) r.image = *m.image_route;
 	else if (m.burst_views) describe_burst_views_decision(*m.burst_views, F / N, &r.burst_views);
+	else if (m.variants)    describe_variants_decision(*m.variants, F, &r.variants);
 	else                    describe_views_decision(*m.views_route, F, &r.views);
 	lockstep.complete = true;
 	return true;
@@ -1744,6 +1786,80 @@ bool last_burst_views_info(BeamformerHipBurstViewsInfo *out)
 	if (!r) return false;
 	out->route = r->burst_views; out->decide_us = r->decide_us;
 	out->frame_count = r->rf_frames; out->view_count = r->rf_frames ? frames / r->rf_frames : 0;
+	return true;
+}
+
+/* beamformer_hip_describe_variants / _get_last_variants_info: a decision in the words of the C ABI */
+void describe_variants_decision(const VariantsDecision &route, uint32_t variant_count, BeamformerHipVariantsDescription *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	out->kernel_variants = route.kernel_variants; out->fused_launches = route.kernel_variants ? 1u : 0u;
+	out->das_launches = route.das_launches; out->kernel_tiles = route.kernel_tiles; out->min_tiles = kVariantsMinTiles;
+	out->min_variants = kVariantsMinVariants;
+	for (uint32_t k = 0; k < variant_count && k < BEAMFORMER_HIP_MAX_VARIANTS; k++) {
+		out->taken[k] = route.taken[k];
+		if (route.parts[k].empty()) { out->path[k] = -1; continue; }
+		const int path = main_part(route.parts[k]).path;
+		out->path[k] = (int8_t)(path == DasPath_Zero ? -2 : path);
+	}
+	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
+}
+
+static bool same_variant(const DasVariant &a, const DasVariant &b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
+
+/* beamformer_hip_push_data_variants_with_compute: ONE RF frame beamformed on the block's grid (no output shard) under variant_count
+ * triples of speed of sound, time offset and f-number.  The block is read, never written: no dirty bit, no replan.  The route:
+ * decide_variants -- each variant's own single-frame decision under its derived block, kept in the block's derived plan states
+ * (context.h: VariantPlanState) and reused by later pushes of the same triple, and which of them the variants kernel takes. */
+bool push_variants(uint32_t block, const void *data, uint32_t size, const DasVariant *variants, uint32_t variant_count, bool data_on_device)
+{
+	Context &c = g_context;
+	Device  &d = *c.cur;
+	ParameterBlock &pb = c.blocks[block];
+	const uint32_t K = variant_count;
+	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const Plan &plan = ps->plan;
+
+	const auto decide_begin = std::chrono::steady_clock::now();
+	std::list<VariantPlanState> &kept = d.variant_plans[block];
+	auto current = [&](const VariantPlanState &vp, const DasVariant &v) {
+		return same_variant(vp.variant, v) && vp.source_generation == ps->generation && vp.mode == c.das_path_mode && vp.hooks_version == hooks().version;
+	};
+	if (kept.size() + K > kMaxVariantPlans) kept.clear();
+	std::vector<const std::vector<DasDecision> *> known(K, nullptr);
+	for (uint32_t k = 0; k < K; k++)
+		for (const VariantPlanState &vp : kept)
+			if (current(vp, variants[k])) { known[k] = &vp.parts; break; }
+	VariantsDecision route;
+	decide_variants(pb, plan, ps->transmit_table, variants, K, c.das_path_mode, route, known.data());
+	for (uint32_t k = 0; k < K; k++) {
+		if (known[k] || route.parts[k].empty()) continue;
+		bool listed = false;                         /* (the same triple twice in one push) */
+		for (const VariantPlanState &vp : kept) listed |= current(vp, variants[k]);
+		if (!listed) kept.push_back(VariantPlanState{variants[k], route.parts[k], ps->generation, hooks().version, c.das_path_mode});
+	}
+	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
+	bool wants_counters = false;
+	for (uint32_t k = 0; k < K; k++) wants_counters |= !route.taken[k] && !route.parts[k].empty() && keeps_counters(route.parts[k]);
+
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], plan.output_points[2]};
+	FramesPush m{PushRecord::Variants, 1, size, K, points, nullptr, nullptr, nullptr, wants_counters, d.scratch, 0, decide_us};
+	m.variants = &route;
+	return push_frames(block, ps, l, data, data_on_device, m);
+}
+
+/* beamformer_hip_get_last_variants_info */
+bool last_variants_info(BeamformerHipVariantsInfo *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	const PushRecord *r = newest_push(PushRecord::Variants, out->first_frame_id, out->variant_count, out->stage_count, out->stage_kind, out->stage_ms, out->variants_ms);
+	if (!r) return false;
+	out->route = r->variants; out->decide_us = r->decide_us;
 	return true;
 }
 

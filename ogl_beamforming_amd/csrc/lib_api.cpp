@@ -12,6 +12,7 @@
  * (the reference's "server unreachable") when there is none.
  */
 #include "context.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -305,6 +306,53 @@ bool push_burst_views_common(const void *data, uint32_t frame_size, uint32_t fra
 	if (!run_fits_the_ring(pb, views, frame_count * view_count, frame_count)) return false;
 	if (!ensure_device()) return false;
 	return push_burst_views(slot, data, frame_size, frame_count, views, view_count, on_device);
+}
+
+static_assert(BEAMFORMER_HIP_MAX_VARIANTS <= BeamformerMaxBacklogFrames, "every variant of a push keeps its frame record");
+
+/* What a variants call must satisfy that needs neither the RF nor a device: the count, the list, the block, every variant's fields. */
+bool validate_variants(const BeamformerHipDasVariant *variants, uint32_t variant_count, uint32_t slot)
+{
+	Context &c = ctx();
+	if (!check(variant_count != 0 && variant_count <= BEAMFORMER_HIP_MAX_VARIANTS, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(variants != nullptr, BeamformerLibErrorKind_InvalidAccess)) return false;
+	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
+	for (uint32_t k = 0; k < variant_count; k++) {
+		const BeamformerHipDasVariant &v = variants[k];
+		if (std::isfinite(v.speed_of_sound) && std::isfinite(v.time_offset) && std::isfinite(v.f_number) && v.speed_of_sound > 0.0f) continue;
+		std::fprintf(stderr, "[beamformer] variant %u needs finite fields and a speed of sound above 0: refused (speed_of_sound %g, time_offset %g, f_number %g)\n",
+		             k, (double)v.speed_of_sound, (double)v.time_offset, (double)v.f_number);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	return true;
+}
+
+std::vector<DasVariant> das_variants(const BeamformerHipDasVariant *variants, uint32_t variant_count)
+{
+	std::vector<DasVariant> out(variant_count);
+	for (uint32_t k = 0; k < variant_count; k++) out[k] = DasVariant{variants[k].speed_of_sound, variants[k].time_offset, variants[k].f_number};
+	return out;
+}
+
+/* A variants push: the list's checks, the single push's checks of the RF (once), then what must hold for the run of frames.  Everything
+ * that needs no device is judged before the device is touched, so that a malformed push is refused the same way on a machine without one. */
+bool push_variants_common(const void *data, uint32_t data_size, const BeamformerHipDasVariant *variants, uint32_t variant_count, uint32_t image_plane_tag,
+                          uint32_t slot, bool on_device)
+{
+	Context &c = ctx();
+	if (!check(variant_count != 0 && variant_count <= BEAMFORMER_HIP_MAX_VARIANTS, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
+	if (!validate_variants(variants, variant_count, slot)) return false;
+	const ParameterBlock &pb = c.blocks[slot];
+	if (!on_one_device("variants push")) return false;
+	if (pb.shard_z_count) {
+		std::fprintf(stderr, "[beamformer] a variant is not sharded: refused with the output shard set on parameter block %u\n", slot);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	if (!valid_rf_frame(pb, data, data_size)) return false;
+	if (!run_fits_the_ring(pb, nullptr, variant_count)) return false;
+	if (!ensure_device()) return false;
+	return push_variants(slot, data, data_size, das_variants(variants, variant_count).data(), variant_count, on_device);
 }
 
 template <typename T>
@@ -835,6 +883,39 @@ uint32_t beamformer_hip_get_last_burst_views_info(BeamformerHipBurstViewsInfo *o
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
 	return last_burst_views_info(out);
+}
+
+uint32_t beamformer_hip_push_data_variants_with_compute(const void *data, uint32_t size, const BeamformerHipDasVariant *variants, uint32_t variant_count,
+                                                        uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_variants_common(data, size, variants, variant_count, image_plane_tag, parameter_slot, false);
+}
+
+uint32_t beamformer_hip_push_device_data_variants_with_compute(const void *device_data, uint32_t size, const BeamformerHipDasVariant *variants,
+                                                               uint32_t variant_count, uint32_t image_plane_tag, uint32_t parameter_slot)
+{
+	return push_variants_common(device_data, size, variants, variant_count, image_plane_tag, parameter_slot, true);
+}
+
+uint32_t beamformer_hip_describe_variants(uint32_t parameter_slot, const BeamformerHipDasVariant *variants, uint32_t variant_count,
+                                          BeamformerHipVariantsDescription *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !validate_variants(variants, variant_count, parameter_slot)) return 0;
+	Context &c = ctx();
+	const ParameterBlock &pb = c.blocks[parameter_slot];
+	Plan plan;
+	std::string error;
+	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	VariantsDecision route;
+	decide_variants(pb, plan, build_transmit_table(pb), das_variants(variants, variant_count).data(), variant_count, c.das_path_mode, route);
+	describe_variants_decision(route, variant_count, out);
+	return 1;
+}
+
+uint32_t beamformer_hip_get_last_variants_info(BeamformerHipVariantsInfo *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess) || !ensure_device()) return 0;
+	return last_variants_info(out);
 }
 
 uint32_t beamformer_hip_synchronize(void)

@@ -122,6 +122,10 @@ def _load():
         "beamformer_hip_push_device_data_burst_views_with_compute": (u32, [vp, u32, u32, C.POINTER(P.HipView), u32, u32]),
         "beamformer_hip_describe_burst_views": (u32, [u32, u32, C.POINTER(P.HipView), u32, C.POINTER(P.HipBurstViewsDescription)]),
         "beamformer_hip_get_last_burst_views_info": (u32, [C.POINTER(P.HipBurstViewsInfo)]),
+        "beamformer_hip_push_data_variants_with_compute": (u32, [vp, u32, C.POINTER(P.HipDasVariant), u32, u32, u32]),
+        "beamformer_hip_push_device_data_variants_with_compute": (u32, [vp, u32, C.POINTER(P.HipDasVariant), u32, u32, u32]),
+        "beamformer_hip_describe_variants": (u32, [u32, C.POINTER(P.HipDasVariant), u32, C.POINTER(P.HipVariantsDescription)]),
+        "beamformer_hip_get_last_variants_info": (u32, [C.POINTER(P.HipVariantsInfo)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -423,6 +427,64 @@ def last_views_info():
     """beamformer_hip_get_last_views_info: the newest views push's route, ids and whole-push stage times; waits for it."""
     info = P.HipViewsInfo()
     _check(library().beamformer_hip_get_last_views_info(C.byref(info)))
+    return info
+
+
+def variant(speed_of_sound, time_offset, f_number):
+    """A HipDasVariant: the three DAS scalars of one candidate of a variants push."""
+    return P.HipDasVariant(float(speed_of_sound), float(time_offset), float(f_number))
+
+
+def variant_of(bp, **changes):
+    """The HipDasVariant of a parameter struct's own values, with `changes` (speed_of_sound=, time_offset=, f_number=) applied."""
+    values = {"speed_of_sound": bp.speed_of_sound, "time_offset": bp.time_offset, "f_number": bp.f_number}
+    values.update(changes)
+    return variant(**values)
+
+
+def with_variant(bp, v):
+    """A copy of the parameter struct carrying the variant's three values: the block whose single push frame k of a variants push is."""
+    out = type(bp).from_buffer_copy(bp)
+    out.speed_of_sound, out.time_offset, out.f_number = v.speed_of_sound, v.time_offset, v.f_number
+    return out
+
+
+def _variant_array(variants):
+    variants = list(variants)
+    return (P.HipDasVariant * len(variants))(*variants), len(variants)
+
+
+def beamform_variants(bp, rf, variants, filters=(), timeout_ms=-1, on_device_pointer=None):
+    """ONE RF frame under K sets of DAS scalars in one call (beamformer_hip_push_data_variants_with_compute): everything but speed of
+    sound, time offset and f-number from `bp`, frame k under variants[k] (HipDasVariant: see variant()).  `rf` as beamform() takes it.
+    Returns (K, Z, Y, X), variant 0 first."""
+    lib = _prepared(bp, filters, timeout_ms)
+    rf = np.ascontiguousarray(rf)
+    array, count = _variant_array(variants)
+    if on_device_pointer is not None:
+        _check(lib.beamformer_hip_push_device_data_variants_with_compute(C.c_void_p(on_device_pointer), rf.nbytes, array, count, 0, 0))
+    else:
+        _check(lib.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, array, count, 0, 0))
+    return get_last_frames(bp, count)
+
+
+def describe_variants(bp, variants, filters=(), slot=0):
+    """What a variants push of these candidates would run (beamformer_hip_describe_variants): the description struct; .path[k] is
+    variant k's own single-frame decision, .taken[k] whether the fused launch takes it, .reason says why this route.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    array, count = _variant_array(variants)
+    d = P.HipVariantsDescription()
+    _check(L.beamformer_hip_describe_variants(slot, array, count, C.byref(d)))
+    return d
+
+
+def last_variants_info():
+    """beamformer_hip_get_last_variants_info: the newest variants push's route, ids and whole-push stage times; waits for it."""
+    info = P.HipVariantsInfo()
+    _check(library().beamformer_hip_get_last_variants_info(C.byref(info)))
     return info
 
 

@@ -274,6 +274,28 @@ class HipBurstViewsInfo(C.Structure):
                 ("push_ms", C.c_float), ("decide_us", C.c_float)]
 
 
+HIP_MAX_VARIANTS = 64
+HIP_DAS_PATH_NO_VARIANTS_KERNEL = 0x4000      # beamformer_hip_set_das_path flag: a variants push runs every variant's single-frame DAS kernel
+HIP_DAS_PATH_PREFER_VARIANTS_KERNEL = 0x8000  # ... flag: the variants kernel takes the eligible variants however few their tiles
+
+
+class HipDasVariant(C.Structure):
+    """BeamformerHipDasVariant: one candidate of a variants push"""
+    _fields_ = [("speed_of_sound", C.c_float), ("time_offset", C.c_float), ("f_number", C.c_float)]
+
+
+class HipVariantsDescription(C.Structure):
+    _fields_ = [("kernel_variants", C.c_uint32), ("fused_launches", C.c_uint32), ("das_launches", C.c_uint32), ("kernel_tiles", C.c_uint32),
+                ("min_tiles", C.c_uint32), ("min_variants", C.c_uint32), ("path", C.c_int8 * HIP_MAX_VARIANTS), ("taken", C.c_uint8 * HIP_MAX_VARIANTS),
+                ("reason", C.c_char * 160)]
+
+
+class HipVariantsInfo(C.Structure):
+    _fields_ = [("route", HipVariantsDescription), ("first_frame_id", C.c_uint32), ("variant_count", C.c_uint32), ("stage_count", C.c_uint32),
+                ("stage_kind", C.c_uint32 * HIP_MAX_TIMED_STAGES), ("stage_ms", C.c_float * HIP_MAX_TIMED_STAGES), ("variants_ms", C.c_float),
+                ("decide_us", C.c_float)]
+
+
 class DasPath(enum.IntEnum):
     """BeamformerHipFrameTimings::das_path / BeamformerHipDasDescription::path (csrc/das_select.h)"""
     General = 0
