@@ -473,6 +473,67 @@ typedef struct {
 /* The newest variants push; waits for it to finish.  Fails when the newest push was not a variants push or did not complete. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_last_variants_info(BeamformerHipVariantsInfo *out);
 
+/* ---- frame metrics: the `count` newest frames of the frame ring reduced ON THE DEVICE to one small row of focus metrics each (the K
+ * frames of a variants push scored so that the sharpest can be kept; the patches of a views push; per-frame energy and peak position
+ * of a burst) -- instead of downloading them all to obtain `count` numbers ----
+ * DEFINITION of a row (tests/frame_metrics_ref.py restates it in numpy).  The magnitude |v| of a voxel is ONE float32:
+ * sqrtf(re * re + im * im) for Float32Complex frames, every operation rounded to float32 on its own (no fused multiply-add), fabsf(v)
+ * for Float32 frames.  A voxel is finite when that float is.  Everything else is formed in double from that float: a = (double)|v|;
+ * the powers a, a * a and (a * a) * (a * a); the gradient term d = (double)|v[i + 1]| - (double)|v[i]|, then d * d.  A voxel that is not
+ * finite counts in non_finite and contributes to nothing else; a pair with such a voxel is not a pair; pairs never leave the box.
+ * The sums are double sums in an order the box alone fixes (no floating-point atomics): the bits of a frame's row depend on that frame
+ * and the region only -- not on count, not on the other frames of the call, not on the call being repeated. */
+#define BEAMFORMER_HIP_MAX_SCORED_FRAMES 1024u      /* = BEAMFORMER_HIP_MAX_VIEWS: a whole views push can be scored */
+typedef struct { uint32_t first[3], count[3]; } BeamformerHipFrameRegion;   /* a box of voxel indices, x, y, z; every count >= 1 */
+typedef struct {
+	uint32_t frame_id, parameter_block, data_kind, image_plane_tag;   /* from the frame's record */
+	uint32_t points[3];                       /* the frame's own grid */
+	uint32_t region_first[3], region_count[3];/* the box that was reduced (the whole frame when region == NULL) */
+	uint32_t max_index[3];                    /* x, y, z IN THE FRAME (not relative to the box) of max_abs; the lowest flat index (x fastest) among ties;
+	                                             0, 0, 0 when voxels == 0 */
+	uint64_t voxels;                          /* voxels of the box whose magnitude is finite: the ones every sum below runs over */
+	uint64_t non_finite;                      /* voxels of the box whose magnitude is NaN or infinite (coherency weighting leaves NaN where no term passed) */
+	uint64_t gradient_pairs[3];               /* per axis: neighbour pairs (i, i + 1 along that axis) with both voxels inside the box and both finite */
+	double   sum_abs, sum_abs2, sum_abs4;     /* sum of |v|, |v|^2, |v|^4 */
+	double   gradient2[3];                    /* per axis: sum over those pairs of (|v[i + 1]| - |v[i]|)^2 */
+	float    max_abs;                         /* largest finite |v|; 0 when voxels == 0 */
+	uint32_t reserved;                        /* 0 (the struct has no padding: rows compare byte for byte) */
+} BeamformerHipFrameMetrics;
+/* out[count], oldest first (the order of beamformer_get_last_frames).  The frames may differ in grid and in data kind (a views push:
+ * K sizes); every row carries its own points.  region == NULL: every frame whole; else the same box of every frame.  The reduction --
+ * one partial launch for all frames, one launch that folds them (csrc/frame_metrics.hip) -- is enqueued on the library's current stream
+ * behind the frames it reads (no host wait for them first); the rows come back through one device-to-host copy and one stream
+ * synchronise.  device_ms, when not NULL: the time between two events around the two launches.
+ * Refusals, all decided before anything is launched and leaving `out` unwritten: count == 0 or > BEAMFORMER_HIP_MAX_SCORED_FRAMES is
+ * BufferOverflow; InvalidAccess: out == NULL; no device in use yet; fewer than count frames ever queued; one of the count frames a
+ * tombstone (a push that did not complete), or its record overwritten, or its ring storage reused by a newer frame; a region with a
+ * zero count, or one that does not fit inside EVERY one of the frames; several devices (beamformer_hip_set_devices: a frame is a set
+ * of z-slabs there and the z gradient would cross them). */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                BeamformerHipFrameMetrics *out, float *device_ms);
+/* The frame with this id -- while its record and its ring storage are still its own -- copied to host memory at its 64-byte-rounded
+ * size, as beamformer_get_last_frames exports it: on the current stream, ending in a synchronise.  (beamformer_get_last_frames serves
+ * the newest `count` only: this is how candidate k of a variants push is kept without downloading the ones behind it.)  An unknown
+ * id, a tombstone, reused storage, out == NULL, no device yet, several devices: InvalidAccess; out_size below the rounded size:
+ * ExportSpaceOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
+/* beamformer_hip_get_last_frame_info for that id: in place, no copy, no synchronisation.  Refused as beamformer_hip_copy_frame. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_get_frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);
+
+typedef enum {
+	BeamformerHipFrameScore_Energy         = 0,   /* sum_abs2 */
+	BeamformerHipFrameScore_MeanMagnitude  = 1,   /* sum_abs / voxels                       (speckle brightness) */
+	BeamformerHipFrameScore_Sharpness      = 2,   /* voxels * sum_abs4 / sum_abs2^2         (normalised fourth moment) */
+	BeamformerHipFrameScore_GradientEnergy = 3,   /* (gradient2[0] + [1] + [2]) / sum_abs2 */
+	BeamformerHipFrameScore_Count
+} BeamformerHipFrameScore;
+/* Host only: touches no device and no library state but the last error.  scores[i] (scores may be NULL): the criterion of
+ * metrics[i] as written above, evaluated in double; a row with voxels == 0 or sum_abs2 == 0 scores -INFINITY.  *best_index: the
+ * highest score, the lowest index among ties.  Returns 0 (InvalidAccess) for count == 0, a NULL argument other than scores, an unknown criterion, or
+ * when every score is -INFINITY (scores, when given, is filled all the same). */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_rank_frames(const BeamformerHipFrameMetrics *metrics, uint32_t count, uint32_t criterion,
+                                                          double *scores, uint32_t *best_index);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

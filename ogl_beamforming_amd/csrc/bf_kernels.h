@@ -346,6 +346,38 @@ static __device__ __forceinline__ bool bf_plane_walk(uint32_t block_id, uint32_t
 /* frames of a burst one Filter / Demodulate / Hilbert launch takes: they share grid y (at most 65535 blocks) with the channels */
 static inline uint32_t bf_stage_frame_chunk(uint32_t channels) { return channels && channels < 65535u ? 65535u / channels : 1u; }
 
+/* ---- frame metrics (frame_metrics.hip: beamformer_hip_score_last_frames) ---- */
+#define BF_METRICS_MAX_BLOCKS       1024u
+#define BF_METRICS_VOXELS_PER_BLOCK 1024u     /* 256 threads, four voxels each, until BF_METRICS_MAX_BLOCKS blocks walk further */
+/* blocks that walk a box of `volume` voxels: a function of the box alone -- a frame's bits do not depend on its company in the launch */
+static inline uint32_t bf_metrics_blocks(uint64_t volume)
+{
+	const uint64_t blocks = (volume + BF_METRICS_VOXELS_PER_BLOCK - 1u) / BF_METRICS_VOXELS_PER_BLOCK;
+	return blocks > BF_METRICS_MAX_BLOCKS ? BF_METRICS_MAX_BLOCKS : blocks ? (uint32_t)blocks : 1u;
+}
+typedef struct {
+	uint64_t offset;             /* of the frame in the frame ring, bytes */
+	uint32_t points[3], cplx;    /* the frame's grid; 1: Float32Complex, 0: Float32 */
+	uint32_t first[3], count[3]; /* the box, inside the grid, every count >= 1 */
+	uint32_t blocks;             /* bf_metrics_blocks of the box */
+	uint32_t partial_first;      /* its first BfMetricsPartial */
+	uint32_t step[3];            /* blocks * 256 voxels of the box as steps in x, y, z: (n % cx, n / cx % cy, n / (cx * cy)) */
+	uint32_t reserved;
+} BfMetricsRow;
+typedef struct {                 /* one block's share of a box */
+	double   s1, s2, s4, g[3];
+	uint64_t max_index;          /* flat index in the FRAME of the largest finite magnitude; max_abs -1: the block saw none */
+	float    max_abs;
+	uint32_t n, bad, pairs[3];
+} BfMetricsPartial;
+typedef struct {                 /* a frame's box */
+	double   s1, s2, s4, g[3];
+	uint64_t voxels, bad, pairs[3];
+	uint64_t max_index;          /* 0 with max_abs 0 when no voxel of the box is finite */
+	float    max_abs;
+	uint32_t reserved;
+} BfMetricsResult;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -383,6 +415,11 @@ hipError_t bf_launch_display(const void *frame, uint64_t voxels, int complex_dat
                              float gamma, float db_cutoff, float *out, hipStream_t s);
 hipError_t bf_launch_min_max(const void *frame, uint64_t voxels, int complex_data,
                              float *scratch, float *out2, hipStream_t s);
+/* frame_metrics.hip: two launches, no atomics -- a partial pass (grid x max_blocks, the most blocks any row asks for; grid y the frame) and
+ * one wave a frame that folds its partials into results[frame].  `ring` and the three tables are device memory; every row's box lies
+ * inside its frame (the caller checks: the kernels index with what the rows say) */
+hipError_t bf_launch_frame_metrics(const void *ring, const BfMetricsRow *rows, uint32_t frame_count, uint32_t max_blocks,
+                                   BfMetricsPartial *partials, BfMetricsResult *results, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

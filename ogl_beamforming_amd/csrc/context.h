@@ -167,6 +167,10 @@ struct Device {
 	bool         have_sample = false;
 	uint64_t     replan_frame = 0;                             /* first frame of the current plan */
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
+	DeviceBuffer metrics_scratch;                              /* score_last_frames: the frames' BfMetricsRows, their results, the blocks' partials (frame_metrics.hip) */
+	void        *metrics_pinned = nullptr;                     /* ... the pinned memory the rows are sent from and the results land in (free again when the call returns: it ends in a synchronise) */
+	size_t       metrics_pinned_size = 0;
+	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
 	DeviceBuffer burst_stage[2];                               /* a burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
 	PushRecord   multi;
 	DeviceBuffer readi_decoded;                                /* a READI image push: the DAS input decoded across its acquisitions (readi_decode.hip), 64 spare bytes behind it */
@@ -270,6 +274,10 @@ bool copy_das_input(void *out, uint64_t out_size);
 bool copy_das_input_frame(uint32_t frame, void *out, uint64_t out_size);
 bool sum_last_frames(uint32_t count, void *out, uint64_t out_size);
 bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float *out, uint64_t out_floats);
+bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms);
+const FrameRecord *record_of(const Device &d, uint32_t frame_id);   /* null: no such frame, a tombstone, or storage that a newer frame reused */
+bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
+bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);
 void shutdown_device();
 
 } // namespace bf

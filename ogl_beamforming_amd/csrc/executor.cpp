@@ -183,6 +183,11 @@ static void release_one_device(Device &d)
 	for (auto &vp : d.variant_plans) vp.clear();
 	for (auto &ip : d.image_plans) { ip.ps.transmits.release(); ip.ps.sparse.release(); ip.ps.valid = false; ip.ps.das_parts.clear(); }
 	d.readi_decoded.release(); d.das_decoded_bytes = 0;
+	d.metrics_scratch.release();
+	if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
+	if (d.metrics_begin) (void)hipEventDestroy(d.metrics_begin);
+	if (d.metrics_end)   (void)hipEventDestroy(d.metrics_end);
+	d.metrics_pinned = nullptr; d.metrics_pinned_size = 0; d.metrics_begin = d.metrics_end = nullptr;
 	d.views_table.release();
 	if (d.views_pinned) (void)hipHostFree(d.views_pinned);
 	if (d.views_copied) (void)hipEventDestroy(d.views_copied);
@@ -2273,6 +2278,149 @@ bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float 
 	}
 	(void)hipSetDevice(c.devices[0].device);
 	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
+}
+
+/* beamformer_hip_score_last_frames: focus metrics of the `count` newest frames, reduced where they lie (frame_metrics.hip).  The records
+ * are judged the way export_last_frames and sum_last_frames judge theirs -- but ANY frame missing refuses the call: a row per frame is
+ * promised.  Everything that can refuse is decided before anything is enqueued. */
+bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms)
+{
+	Context &c = g_context;
+	/* several devices: a frame is a set of z-slabs there, and the z gradient would cross them */
+	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	Device &d = c.devices[0];
+	if (count > d.frame_counter || count > d.frames.size()) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (region) for (int k = 0; k < 3; k++) if (!region->count[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	const size_t rows_bytes = round_up(sizeof(BfMetricsRow) * count, 64), results_bytes = round_up(sizeof(BfMetricsResult) * count, 64);
+	std::vector<BfMetricsRow> rows(count);
+	uint32_t partials = 0, max_blocks = 0;
+	const uint64_t first_id = d.frame_counter - count;
+	for (uint32_t n = 0; n < count; n++) {
+		const FrameRecord &f = d.frames[(first_id + n) % d.frames.size()];
+		if (f.id != (uint32_t)(first_id + n) || f.failed || !f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
+		BfMetricsRow &r = rows[n];
+		r = BfMetricsRow{};
+		r.offset = f.offset;
+		r.cplx = f.data_kind == BeamformerDataKind_Float32Complex;
+		uint64_t volume = 1;
+		for (int k = 0; k < 3; k++) {
+			r.points[k] = f.points[k];
+			r.first[k] = region ? region->first[k] : 0u;
+			r.count[k] = region ? region->count[k] : f.points[k];
+			/* the box inside the frame (a frame of no voxels -- a pipeline without DAS on a peer -- holds no box) */
+			if (!r.count[k] || (uint64_t)r.first[k] + r.count[k] > f.points[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
+			volume *= r.count[k];       /* (at most the frame's voxels, which fit its record's 64-bit byte count) */
+		}
+		/* and the frame inside the ring: what the kernels index with is what the record says */
+		if (f.offset > d.ring.size || f.bytes > d.ring.size - f.offset ||
+		    (uint64_t)f.points[0] * f.points[1] * f.points[2] * (r.cplx ? 8u : 4u) > f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
+		r.blocks = bf_metrics_blocks(volume);
+		r.partial_first = partials;
+		const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
+		r.step[0] = (uint32_t)(stride % r.count[0]);
+		r.step[1] = (uint32_t)(stride / r.count[0] % r.count[1]);
+		r.step[2] = (uint32_t)(stride / plane);
+		partials += r.blocks;
+		if (r.blocks > max_blocks) max_blocks = r.blocks;
+	}
+
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	const size_t partials_bytes = sizeof(BfMetricsPartial) * partials, pinned_bytes = rows_bytes + results_bytes;
+	if (ok && d.metrics_pinned_size < pinned_bytes) {
+		if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
+		d.metrics_pinned = nullptr; d.metrics_pinned_size = 0;
+		ok = HIP_OK(hipHostMalloc(&d.metrics_pinned, pinned_bytes, hipHostMallocDefault));
+		if (ok) d.metrics_pinned_size = pinned_bytes; else d.metrics_pinned = nullptr;
+	}
+	ok = ok && d.metrics_scratch.ensure(rows_bytes + results_bytes + partials_bytes);
+	if (ok && !d.metrics_begin) ok = HIP_OK(hipEventCreate(&d.metrics_begin));
+	if (ok && !d.metrics_end)   ok = HIP_OK(hipEventCreate(&d.metrics_end));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
+	const BfMetricsRow *device_rows    = (const BfMetricsRow *)device;
+	BfMetricsResult    *device_results = (BfMetricsResult *)(device + rows_bytes);
+	BfMetricsPartial   *device_partials = (BfMetricsPartial *)(device + rows_bytes + results_bytes);
+	const BfMetricsResult *results = (const BfMetricsResult *)(pinned + rows_bytes);
+	std::memcpy(pinned, rows.data(), sizeof(BfMetricsRow) * count);
+	hipStream_t s = d.stream;
+	ok &= HIP_OK(hipMemcpyAsync(device, pinned, sizeof(BfMetricsRow) * count, hipMemcpyHostToDevice, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
+	if (ok) ok &= HIP_OK(bf_launch_frame_metrics(d.ring.ptr, device_rows, count, max_blocks, device_partials, device_results, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
+	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + rows_bytes, device_results, sizeof(BfMetricsResult) * count, hipMemcpyDeviceToHost, s));
+	/* the one synchronise: also what frees the pinned memory for the next call, so it runs whatever failed above */
+	ok &= HIP_OK(hipStreamSynchronize(s));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (device_ms) {
+		float ms = 0;
+		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
+	}
+
+	for (uint32_t n = 0; n < count; n++) {
+		const FrameRecord &f = d.frames[(first_id + n) % d.frames.size()];
+		const BfMetricsRow &r = rows[n];
+		const BfMetricsResult &v = results[n];
+		BeamformerHipFrameMetrics &m = out[n];
+		std::memset(&m, 0, sizeof(m));
+		m.frame_id = f.id; m.parameter_block = f.block; m.data_kind = (uint32_t)f.data_kind; m.image_plane_tag = f.tag;
+		const uint64_t plane = (uint64_t)f.points[0] * f.points[1];
+		for (int k = 0; k < 3; k++) {
+			m.points[k] = f.points[k]; m.region_first[k] = r.first[k]; m.region_count[k] = r.count[k];
+			m.gradient_pairs[k] = v.pairs[k]; m.gradient2[k] = v.g[k];
+		}
+		m.max_index[0] = (uint32_t)(v.max_index % f.points[0]);
+		m.max_index[1] = (uint32_t)(v.max_index / f.points[0] % f.points[1]);
+		m.max_index[2] = (uint32_t)(v.max_index / plane);
+		m.voxels = v.voxels; m.non_finite = v.bad;
+		m.sum_abs = v.s1; m.sum_abs2 = v.s2; m.sum_abs4 = v.s4;
+		m.max_abs = v.max_abs;
+	}
+	return true;
+}
+
+/* The record of the frame with this id, while the frame is still there: its record not yet overwritten (the newest frames.size() ids),
+ * no tombstone, its ring storage not reused by a newer frame (next_frames clears `bytes` then). */
+const FrameRecord *record_of(const Device &d, uint32_t frame_id)
+{
+	if (d.frame_counter == 0 || d.frames.empty()) return nullptr;
+	/* ids are the low 32 bits of the frame counter: the newest frame that carries this one */
+	const uint64_t newest = d.frame_counter - 1, id = newest - (uint32_t)((uint32_t)newest - frame_id);
+	if (id > newest || newest - id >= d.frames.size()) return nullptr;
+	const FrameRecord &f = d.frames[id % d.frames.size()];
+	return (f.id == frame_id && !f.failed && f.bytes) ? &f : nullptr;
+}
+
+/* beamformer_hip_copy_frame: one frame by its id, as export_last_frames copies the newest ones; one device only */
+bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
+{
+	Context &c = g_context;
+	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	Device &d = c.devices[0];
+	const FrameRecord *f = record_of(d, frame_id);
+	if (!f || f->offset > d.ring.size || f->bytes > d.ring.size - f->offset) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (out_size < f->bytes) return set_error(BeamformerLibErrorKind_ExportSpaceOverflow);
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && HIP_OK(hipMemcpyAsync(out, (const char *)d.ring.ptr + f->offset, f->bytes, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
+	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
+}
+
+/* beamformer_hip_get_frame_info: beamformer_hip_get_last_frame_info for that id */
+bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out)
+{
+	Context &c = g_context;
+	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	const Device &d = c.devices[0];
+	const FrameRecord *f = record_of(d, frame_id);
+	if (!f) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	out->device_pointer = (char *)d.ring.ptr + f->offset;
+	out->size_bytes = f->bytes;
+	out->points[0] = f->points[0]; out->points[1] = f->points[1]; out->points[2] = f->points[2];
+	out->data_kind = (uint32_t)f->data_kind;
+	out->frame_id = f->id; out->parameter_block = f->block;
+	return true;
 }
 
 } // namespace bf

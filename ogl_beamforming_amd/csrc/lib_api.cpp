@@ -981,6 +981,52 @@ uint32_t beamformer_hip_sum_last_frames(uint32_t count, void *out, uint64_t out_
 	return sum_last_frames(count, out, out_size);
 }
 
+/* the three below serve frames that exist: they start no device (no device yet: there is no frame, InvalidAccess) */
+uint32_t beamformer_hip_score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return score_last_frames(count, region, out, device_ms);
+}
+
+uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return copy_frame(frame_id, out, out_size);
+}
+
+uint32_t beamformer_hip_get_frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return frame_info(frame_id, out);
+}
+
+/* host only: the criterion of every row in double, the best one (include/ogl_beamformer_hip.h: BeamformerHipFrameScore) */
+uint32_t beamformer_hip_rank_frames(const BeamformerHipFrameMetrics *metrics, uint32_t count, uint32_t criterion, double *scores, uint32_t *best_index)
+{
+	if (!check(metrics != nullptr && best_index != nullptr && count >= 1 && criterion < (uint32_t)BeamformerHipFrameScore_Count,
+	           BeamformerLibErrorKind_InvalidAccess)) return 0;
+	double   best = -INFINITY;
+	uint32_t best_at = 0;
+	for (uint32_t i = 0; i < count; i++) {
+		const BeamformerHipFrameMetrics &m = metrics[i];
+		double score = -INFINITY;
+		if (m.voxels != 0 && m.sum_abs2 != 0) {
+			switch (criterion) {
+			case BeamformerHipFrameScore_Energy:         score = m.sum_abs2; break;
+			case BeamformerHipFrameScore_MeanMagnitude:  score = m.sum_abs / (double)m.voxels; break;
+			case BeamformerHipFrameScore_Sharpness:      score = (double)m.voxels * m.sum_abs4 / (m.sum_abs2 * m.sum_abs2); break;
+			case BeamformerHipFrameScore_GradientEnergy: score = (m.gradient2[0] + m.gradient2[1] + m.gradient2[2]) / m.sum_abs2; break;
+			}
+		}
+		if (scores) scores[i] = score;
+		if (score > best) { best = score; best_at = i; }
+	}
+	if (!check(best > -INFINITY, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	*best_index = best_at;
+	return 1;
+}
+
 uint32_t beamformer_hip_display_last_frame(float threshold_db, float gamma, float db_cutoff, float *out, uint64_t out_floats)
 {
 	if (!out) return set_error(BeamformerLibErrorKind_InvalidAccess);

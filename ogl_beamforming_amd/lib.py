@@ -126,6 +126,10 @@ def _load():
         "beamformer_hip_push_device_data_variants_with_compute": (u32, [vp, u32, C.POINTER(P.HipDasVariant), u32, u32, u32]),
         "beamformer_hip_describe_variants": (u32, [u32, C.POINTER(P.HipDasVariant), u32, C.POINTER(P.HipVariantsDescription)]),
         "beamformer_hip_get_last_variants_info": (u32, [C.POINTER(P.HipVariantsInfo)]),
+        "beamformer_hip_score_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(P.HipFrameMetrics), C.POINTER(C.c_float)]),
+        "beamformer_hip_copy_frame": (u32, [u32, vp, u64]),
+        "beamformer_hip_get_frame_info": (u32, [u32, C.POINTER(P.HipFrameInfo)]),
+        "beamformer_hip_rank_frames": (u32, [C.POINTER(P.HipFrameMetrics), u32, u32, C.POINTER(C.c_double), C.POINTER(u32)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -486,6 +490,51 @@ def last_variants_info():
     info = P.HipVariantsInfo()
     _check(library().beamformer_hip_get_last_variants_info(C.byref(info)))
     return info
+
+
+def frame_region(first, count):
+    """A HipFrameRegion: the box of voxels first .. first + count (x, y, z)."""
+    return P.HipFrameRegion((C.c_uint32 * 3)(*[int(v) for v in first]), (C.c_uint32 * 3)(*[int(v) for v in count]))
+
+
+def score_last_frames(count, region=None):
+    """beamformer_hip_score_last_frames: the `count` newest frames reduced on the device to one HipFrameMetrics row each, oldest first;
+    region (HipFrameRegion: see frame_region()) None: every frame whole.  Returns (rows, device_ms): a ctypes array of `count` rows and
+    the device time of the reduction."""
+    rows = (P.HipFrameMetrics * max(1, int(count)))()
+    ms = C.c_float(0)
+    _check(library().beamformer_hip_score_last_frames(count, None if region is None else C.byref(region), rows, C.byref(ms)))
+    return rows, float(ms.value)
+
+
+def rank_frames(rows, criterion):
+    """beamformer_hip_rank_frames (host only): (scores, best) -- the criterion (P.FrameScore) of every row as a float64 array, and the
+    index of the highest, the lowest index among ties.  Raises when no row has a score."""
+    rows = list(rows)
+    array = (P.HipFrameMetrics * max(1, len(rows)))(*rows)
+    scores = np.zeros(max(1, len(rows)), np.float64)
+    best = C.c_uint32(0)
+    _check(library().beamformer_hip_rank_frames(array, len(rows), int(criterion), scores.ctypes.data_as(C.POINTER(C.c_double)), C.byref(best)))
+    return scores[:len(rows)], int(best.value)
+
+
+def frame_info(frame_id):
+    """beamformer_hip_get_frame_info: the HipFrameInfo of the frame with this id, while it is still in the frame ring."""
+    info = P.HipFrameInfo()
+    _check(library().beamformer_hip_get_frame_info(int(frame_id), C.byref(info)))
+    return info
+
+
+def copy_frame(frame_id):
+    """beamformer_hip_copy_frame: the frame with this id, as float32 or complex64 of shape (Z, Y, X) -- its own points and kind."""
+    info = frame_info(frame_id)
+    raw = np.zeros(int(info.size_bytes) // 4, dtype=np.float32)
+    _check(library().beamformer_hip_copy_frame(int(frame_id), raw.ctypes.data_as(C.c_void_p), raw.nbytes))
+    shape = (int(info.points[2]), int(info.points[1]), int(info.points[0]))
+    voxels = int(np.prod(shape))
+    if info.data_kind == int(P.DataKind.Float32Complex):
+        return raw[: 2 * voxels].view(np.complex64).reshape(shape)
+    return raw[:voxels].reshape(shape)
 
 
 def beamform_burst_views(bp, rf_frames, views, filters=(), timeout_ms=-1, on_device_pointer=None):

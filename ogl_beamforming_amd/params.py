@@ -296,6 +296,31 @@ class HipVariantsInfo(C.Structure):
                 ("decide_us", C.c_float)]
 
 
+HIP_MAX_SCORED_FRAMES = 1024
+
+
+class HipFrameRegion(C.Structure):
+    """BeamformerHipFrameRegion: a box of voxel indices, x, y, z"""
+    _fields_ = [("first", C.c_uint32 * 3), ("count", C.c_uint32 * 3)]
+
+
+class HipFrameMetrics(C.Structure):
+    """BeamformerHipFrameMetrics: one frame's row of beamformer_hip_score_last_frames (no padding: rows compare byte for byte)"""
+    _fields_ = [("frame_id", C.c_uint32), ("parameter_block", C.c_uint32), ("data_kind", C.c_uint32), ("image_plane_tag", C.c_uint32),
+                ("points", C.c_uint32 * 3), ("region_first", C.c_uint32 * 3), ("region_count", C.c_uint32 * 3), ("max_index", C.c_uint32 * 3),
+                ("voxels", C.c_uint64), ("non_finite", C.c_uint64), ("gradient_pairs", C.c_uint64 * 3),
+                ("sum_abs", C.c_double), ("sum_abs2", C.c_double), ("sum_abs4", C.c_double), ("gradient2", C.c_double * 3),
+                ("max_abs", C.c_float), ("reserved", C.c_uint32)]
+
+
+class FrameScore(enum.IntEnum):
+    """BeamformerHipFrameScore: the criteria of beamformer_hip_rank_frames"""
+    Energy = 0
+    MeanMagnitude = 1
+    Sharpness = 2
+    GradientEnergy = 3
+
+
 class DasPath(enum.IntEnum):
     """BeamformerHipFrameTimings::das_path / BeamformerHipDasDescription::path (csrc/das_select.h)"""
     General = 0
