@@ -66,7 +66,7 @@ struct TimingSlot {
 	bool       failed = false;            /* the push that owns this slot did not complete */
 };
 
-/* the newest multi-frame push (executor.cpp push_frames): what beamformer_hip_get_last_burst_info / _views_info / _variants_info report, each of its own kind */
+/* the newest multi-frame push (executor.cpp push_frames, and the push_* function for its route): what the beamformer_hip_get_last_*_info calls report, each of its own kind */
 struct PushRecord {
 	enum Kind { None, Burst, Views, Image, BurstViews, Variants } kind = None;
 	uint64_t      first_id = 0;
@@ -107,7 +107,7 @@ struct ImagePlanState {
  * values -- BfDasArgs, the part list, the staged / factored / HERCULES geometry planned with them -- kept with the block's own plan
  * state and reused while the triple, the block's plan (source_generation), the path mode and the hooks are what it was decided for; a
  * replan of the block drops them all.  The device tables a DAS launch reads besides (transmits, sparse elements, READI matrix) do not
- * depend on the triple: the derived state runs on the block's own (executor.cpp: DasJob::ps), and the tables the staged and HERCULES
+ * depend on the triple: the derived state runs on the block's own (executor.cpp: Push::das_ps), and the tables the staged and HERCULES
  * kernels build per launch are built from the job's own BfDasArgs. */
 struct VariantPlanState {
 	DasVariant variant{};
@@ -245,8 +245,7 @@ bool     set_error(BeamformerLibErrorKind kind);   /* records and returns false 
 bool ensure_device();                               /* SharedMemory error when no HIP device */
 uint64_t default_frame_ring_bytes();
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device);
-bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device);
-bool push_readi_sweep(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);
+bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);   /* groups: a READI sweep */
 bool push_readi_image(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);
 bool last_readi_image_info(BeamformerHipReadiImageInfo *out);
 void describe_readi_image_decision(const ReadiImageDecision &route, BeamformerHipReadiImageDescription *out);

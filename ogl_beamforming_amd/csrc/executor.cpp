@@ -331,17 +331,44 @@ static ImagePlanState *commit_image_plan(uint32_t block, PlanState *ps)
 	return ok ? &ip : nullptr;
 }
 
-/* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: all of
- * `points` (a single push: one; a burst), or -- `views` given -- frame k of views[k / per_view]'s points and tag (a views push: one frame
- * a view; a burst views push: its RF frames, view-major).  A run that would straddle the end
- * starts again at offset 0; the records it overwrites stop being exportable.  Consecutive ids, each frame's timing slot named in its
- * record.  Returns the first, or null when the run does not fit the ring; total: the bytes of the whole run (frame_run_bytes). */
-static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, uint32_t block, uint32_t count, const BeamformerHipView *views, uint64_t &total,
-                                uint32_t per_view = 1)
+/* One frame a push queues.  The push describes it -- which RF frame's DAS input it reads, its grid, the parts that compute it
+ * (das_select.h) and whether the push's fused launch covers it --; walk_plan places it in the ring, resolves `in` and `out` and runs it. */
+struct DasJob {
+	uint32_t        rf_frame;       /* reads the DAS input of this RF frame of the push */
+	const uint32_t *points;         /* its grid, and the tag its record carries */
+	uint32_t        tag;
+	uint32_t        z_first;
+	const std::vector<DasDecision> *parts;   /* null: no DAS runs for the frame (no DAS stage, an empty slab) and it stays zero */
+	bool            fused;          /* the push's fused launch covers it; else it gets its own launch(es), the kernels of a single push */
+	int32_t         group;          /* >= 0: its launches run with this BfDasArgs::readi_group; -1: the block's */
+	/* the walk's: */
+	const char     *in;
+	char           *out;
+	uint32_t        path;           /* the kernel that ran its main part */
+};
+
+/* The bytes of a run of frames, contiguous in the frame ring, each rounded to 64 bytes (frame_run_bytes per frame: saturating).  False:
+ * the run does not fit `ring` bytes. */
+static bool job_run_bytes(const DasJob *jobs, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total)
+{
+	total = 0;
+	for (uint32_t k = 0; k < count; k++) {
+		uint64_t frame;
+		if (!frame_run_bytes(jobs[k].points, nullptr, 1, voxel_bytes, ring, frame) || frame > ring - total) return false;
+		total += frame;
+	}
+	return true;
+}
+
+/* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: frame
+ * k has jobs[k]'s points and tag.  A run that would straddle the end starts again at offset 0; the records it overwrites stop being
+ * exportable.  Consecutive ids, each frame's timing slot named in its record.  Returns the first, or null when the run does not fit the
+ * ring; total: the bytes of the whole run. */
+static FrameRecord *next_frames(const DasJob *jobs, uint32_t count, bool complex_frame, uint32_t block, uint64_t &total)
 {
 	Device &d = *g_context.cur;
 	const int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
-	if (count == 0 || !frame_run_bytes(points, views, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total, per_view)) return nullptr;
+	if (count == 0 || !job_run_bytes(jobs, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total)) return nullptr;
 	if (d.ring_next_offset > d.ring.size - total) d.ring_next_offset = 0;
 	/* records whose storage the run reuses stop being exportable: one pass for the run's whole byte range (the run's own records are
 	 * written below, after it) */
@@ -349,14 +376,14 @@ static FrameRecord *next_frames(const uint32_t points[3], bool complex_frame, ui
 		if (old.bytes && old.offset < d.ring_next_offset + total && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
 	FrameRecord *first = nullptr;
 	for (uint32_t k = 0; k < count; k++) {
-		const uint32_t *n = views ? views[k / per_view].output_points : points;
+		const uint32_t *n = jobs[k].points;
 		const uint64_t bytes = round_up((uint64_t)n[0] * n[1] * n[2] * (uint64_t)bf_kind_byte_size[kind], 64);
 		uint64_t id = d.frame_counter++;
 		FrameRecord *f = &d.frames[id % d.frames.size()];
 		f->offset = d.ring_next_offset; f->bytes = bytes;
 		f->points[0] = n[0]; f->points[1] = n[1]; f->points[2] = n[2];
 		f->data_kind = kind; f->id = (uint32_t)id; f->block = block; f->failed = false;
-		f->tag = views ? views[k / per_view].image_plane_tag : 0u;
+		f->tag = jobs[k].tag;
 		f->timing_slot = (int)(id % kTimingSlots);
 		d.ring_next_offset += bytes;
 		if (k == 0) first = f;
@@ -482,10 +509,11 @@ static bool launch_stage(PlanState *ps, const BeamformerParameters &bp, size_t i
 
 
 /* The DAS decision(s) of a plan's frames over planes [zfirst, zfirst + zcount): computed once per plan / shard / path mode / hook change
- * (das_select.cpp) and reused by every frame after it. */
-static std::vector<DasDecision> &frame_das_parts(PlanState *ps, const ParameterBlock &pb, uint32_t zfirst, uint32_t zcount)
+ * (das_select.cpp) and reused by every frame after it.  Null: no DAS runs -- the plan has no DAS stage, or there are no planes. */
+static const std::vector<DasDecision> *frame_das_parts(PlanState *ps, const ParameterBlock &pb, uint32_t zfirst, uint32_t zcount)
 {
 	Context &c = g_context;
+	if (ps->plan.das_index < 0 || !zcount) return nullptr;
 	std::vector<DasDecision> &parts = ps->das_parts;
 	if (parts.empty() || !parts[0].valid || parts[0].generation != ps->generation || ps->das_z_first != zfirst || ps->das_z_count != zcount ||
 	    parts[0].mode_asked != c.das_path_mode || parts[0].hooks_version != hooks().version) {
@@ -493,7 +521,7 @@ static std::vector<DasDecision> &frame_das_parts(PlanState *ps, const ParameterB
 		for (DasDecision &dd : parts) { dd.generation = ps->generation; dd.mode_asked = c.das_path_mode; }
 		ps->das_z_first = zfirst; ps->das_z_count = zcount;
 	}
-	return parts;
+	return &parts;
 }
 
 /* the plan's device tables, which every DAS launch reads */
@@ -671,107 +699,103 @@ static void fill_das_fields(TimingSlot &t, uint64_t id, const std::vector<DasDec
 	t.violations_slot = violations_slot;
 }
 
-/* What a walk over a plan runs on: `frames` RF frames, frame k of every buffer k * that buffer's stride further on (one frame: stride 0). */
-struct StageWalk {
-	uint32_t      frames;
-	const void   *in;               /* the first stage's input, and what it may read of a frame there */
-	uint64_t      in_stride;
-	int64_t       in_bound;
-	DeviceBuffer *stage;            /* the ping-pong pair the pre-DAS stages write */
-	uint64_t      stage_stride;     /* 0: a stage may read its predecessor's whole buffer; else its frame's stride */
-	TimingSlot   &t;                /* owns the events; its ingest segment (or events[0]) is already recorded */
-	const BurstDecision *route;     /* a burst's DAS route (das_select.h); null: a single push, a views push */
-	const BeamformerHipView *views = nullptr;     /* a views push: `frames` is 1 and the DAS stage writes view_count frames from its one input, */
-	uint32_t             view_count = 0;
-	const ViewsDecision *views_route = nullptr;   /* by this route (das_select.h: decide_views) */
-	const BurstViewsDecision *burst_views = nullptr;   /* a burst views push: `frames` RF frames on the view_count grids, frames x view_count frames
-	                                                      view-major, by this route (views_route: its per-view decisions and table) */
-	const uint32_t      *readi_groups = nullptr;  /* a READI sweep: frame k is beamformed with readi_group = readi_groups[k] (validated: lib_api.cpp) */
-	ImagePlanState      *image = nullptr;         /* a READI image push: the `frames` DAS inputs are decoded across the acquisitions by readi_groups
-	                                                 (readi_decode.hip) and the DAS stage writes ONE frame from that, under this derived block */
-	const VariantsDecision   *variants = nullptr;      /* a variants push: `frames` is 1 and the DAS stage writes variant_count frames of the block's grid
-	                                                      from its one input, frame k under the derived decision variants->parts[k], by this route */
-	uint32_t                  variant_count = 0;
+/* The fused launch of a push: one kernel launch (or one per RF frame) that computes every job marked `fused`.  ONE tagged description;
+ * walk_plan dispatches it through its one switch.  The pointers are the routes (das_select.h) of the kinds that name them. */
+struct FusedLaunch {
+	enum Kind {
+		None,               /* every frame gets its own launch(es) */
+		Burst,              /* das_burst.hip: every frame of a burst */
+		ReadiSweep,         /* das_burst.hip, das_readi_burst_kernel: every frame of a READI sweep, frame k under groups[k] */
+		Views,              /* das_views.hip: the views the route takes, from the one RF frame */
+		Variants,           /* das_variants.hip: the variants the route takes, from the one RF frame */
+		BurstViews,         /* das_burst_views.hip, once: the views the route takes, of every RF frame (a burst views push, rung 1) */
+		ViewsPerRfFrame,    /* das_views.hip once per RF frame, on that frame's jobs and its slice of the input (a burst views push, rung 2) */
+	} kind = None;
+	const BurstDecision    *burst = nullptr;
+	const ViewsDecision    *views = nullptr;
+	const VariantsDecision *variants = nullptr;
+	const uint32_t         *groups = nullptr;
 };
 
-/* One frame the DAS stage writes: what it reads, where it writes, the parts that compute it (das_select.h) on which grid, whether the
- * push's fused launch (a burst's kernel, the views kernel) covers it; path: the kernel that ran its main part. */
-struct DasJob {
-	const char     *in;
-	char           *out;
-	const std::vector<DasDecision> *parts;
-	uint32_t        z_first;
-	const uint32_t *points;
-	bool            fused;
-	uint32_t        path;
-	int32_t         readi_group;    /* >= 0: the job's launches run with this BfDasArgs::readi_group (a READI sweep's frame); -1: the block's */
-	PlanState      *ps;             /* the plan state the job's launches run under -- whose device tables they bind: the block's own; a READI image's
-	                                   derived block's.  (A variant's derived decision is `parts`; the tables it binds do not depend on its values
-	                                   and are the block's: context.h, VariantPlanState) */
+/* A push, as walk_plan and push_frames run it; every member is assigned by name.
+ * The RF frames and the buffers the pre-DAS stages run on: frame k of every buffer k * that buffer's stride further on (one frame:
+ * stride 0).  The single push fills them in run_frame_stages, push_frames for every other push.
+ * The frames: the jobs the push queues, in id order, the plan state their DAS launches bind, the fused launch that covers the jobs
+ * marked `fused`, the decode step ahead of DAS.  The push_* function fills them, and what of its upload and record is its own. */
+struct Push {
+	uint32_t      rf_frames = 1;
+	const void   *in = nullptr;         /* the first stage's input, and what it may read of a frame there */
+	uint64_t      in_stride = 0;
+	int64_t       in_bound = 0;
+	DeviceBuffer *stage = nullptr;      /* the ping-pong pair the pre-DAS stages write */
+	uint64_t      stage_stride = 0;     /* 0: a stage may read its predecessor's whole buffer; else its frame's stride */
+	TimingSlot   *t = nullptr;          /* owns the events; its ingest segment (or events[0]) is already recorded */
+	DasJob       *jobs = nullptr;
+	uint32_t      frames = 1;
+	PlanState    *das_ps = nullptr;     /* whose device tables the DAS launches bind: the block's own; a READI image's derived block's.  (A variant's
+	                                       derived decision is its job's `parts`; the tables it binds do not depend on its values and are the
+	                                       block's: context.h, VariantPlanState) */
+	FusedLaunch   fused;
+	const uint32_t *decode_groups = nullptr;   /* the decode step: the rf_frames DAS inputs are decoded across the acquisitions by these group ids
+	                                              (readi_decode.hip) and the ONE job reads the result */
+	bool          fails_on_flag = false;       /* path flag 0x2000 fails the DAS step once the ids are taken */
+	PushRecord::Kind kind = PushRecord::None;
+	uint32_t      rf_frame_size = 0;    /* rf_frames RF frames back to back, each this many bytes of the caller's */
+	uint64_t      decoded_bytes = 0;    /* the decode step's output */
+	float         decide_us = 0;
 };
 
-/* The burst kernel (das_burst.hip): N frames, frame k at k * the strides of input and output, in one launch. */
-static bool launch_burst_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, uint32_t N, uint64_t in_stride, uint64_t out_stride, hipStream_t s)
-{
-	BfDasArgs a = route.a;
-	a.rf = first.in; a.out = first.out;
-	bind_tables(ps, a);
-	BfBurstArgs b{};
-	b.frame_count = N; b.rf_stride = in_stride; b.out_stride = out_stride;
-	return HIP_OK(bf_launch_das_burst(&a, &b, s));
-}
-
-/* The group ids of a READI sweep's or a READI image push's frames into d.views_table: through pinned memory on the push's stream, as a
- * views push's table goes (the same buffers: push_frames grew them). */
-static bool upload_group_ids(const uint32_t *groups, uint32_t N, hipStream_t s)
+/* The small tables some launches read (a views push's rows and prefix table, a variants push's rows, the group ids of a READI sweep or
+ * image) go to d.views_table through pinned memory on the push's stream, read in place by a small kernel (no copy engine:
+ * bf_launch_views_table); push_frames grew both.  `fill` writes the `bytes` into the pinned memory once the copy that last read it has
+ * passed. */
+template <class Fill> static bool stage_table(size_t bytes, hipStream_t s, Fill fill)
 {
 	Device &d = *g_context.cur;
-	bool ok = true;
 	if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
-	std::memcpy(d.views_pinned, groups, sizeof(uint32_t) * N);
+	fill(d.views_pinned);
 	void *mapped = nullptr;
-	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
-	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)(sizeof(uint32_t) * N), s));
+	bool ok = HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
+	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)bytes, s));
 	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
 	return ok && d.views_copy_pending;
 }
 
-/* The READI sweep kernel (das_burst.hip: das_readi_burst_kernel): the burst kernel's launch with the frames' group ids ahead of it. */
-static bool launch_readi_sweep_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, const uint32_t *groups, uint32_t N,
-                                      uint64_t in_stride, uint64_t out_stride, hipStream_t s)
+static bool stage_group_ids(const uint32_t *groups, uint32_t N, hipStream_t s)
 {
-	Device &d = *g_context.cur;
-	bool ok = upload_group_ids(groups, N, s);
+	return stage_table(sizeof(uint32_t) * N, s, [&](void *pinned) { std::memcpy(pinned, groups, sizeof(uint32_t) * N); });
+}
+
+/* The burst kernel (das_burst.hip): N frames, frame k at k * the strides of input and output, in one launch.  `groups`: the READI sweep
+ * kernel (das_readi_burst_kernel) instead -- the same launch with the frames' group ids staged ahead of it. */
+static bool launch_burst_kernel(PlanState *ps, const BurstDecision &route, const DasJob &first, const uint32_t *groups, uint32_t N, uint64_t in_stride,
+                                uint64_t out_stride, hipStream_t s)
+{
 	BfDasArgs a = route.a;
 	a.rf = first.in; a.out = first.out;
 	bind_tables(ps, a);
 	BfReadiSweepArgs b{};
 	b.burst.frame_count = N; b.burst.rf_stride = in_stride; b.burst.out_stride = out_stride;
-	b.groups = (const uint32_t *)d.views_table.ptr;
-	if (ok) ok &= HIP_OK(bf_launch_das_readi_sweep(&a, &b, s));
-	return ok;
+	b.groups = (const uint32_t *)g_context.cur->views_table.ptr;
+	if (!groups) return HIP_OK(bf_launch_das_burst(&a, &b.burst, s));
+	return stage_group_ids(groups, N, s) && HIP_OK(bf_launch_das_readi_sweep(&a, &b, s));
 }
 
 /* The variants kernel (das_variants.hip): the variants the route has it take, from the ONE DAS input on the block's grid, in one launch --
- * their rows go the way a views push's table goes (the same buffers: push_frames grew them).  Variant k's job is jobs[k]. */
+ * their rows staged ahead of it.  Variant k's job is jobs[k]. */
 static bool launch_variants_kernel(PlanState *ps, const VariantsDecision &route, const DasJob *jobs, uint32_t K, hipStream_t s)
 {
 	Device &d = *g_context.cur;
-	bool ok = true;
 	const uint32_t n = route.kernel_variants;
-	if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
-	BfVariantRow *rows = (BfVariantRow *)d.views_pinned;
-	for (uint32_t k = 0, r = 0; k < K; k++) {
-		if (!route.taken[k]) continue;
-		rows[r] = route.rows[r];
-		rows[r].out_offset = (uint64_t)(jobs[k].out - jobs[0].out);
-		r++;
-	}
-	void *mapped = nullptr;
-	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
-	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)(sizeof(BfVariantRow) * n), s));
-	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
-	ok &= d.views_copy_pending;
+	bool ok = stage_table(sizeof(BfVariantRow) * n, s, [&](void *pinned) {
+		BfVariantRow *rows = (BfVariantRow *)pinned;
+		for (uint32_t k = 0, r = 0; k < K; k++) {
+			if (!route.taken[k]) continue;
+			rows[r] = route.rows[r];
+			rows[r].out_offset = (uint64_t)(jobs[k].out - jobs[0].out);
+			r++;
+		}
+	});
 	BfDasArgs a = route.a;
 	a.rf = jobs[0].in; a.out = jobs[0].out;
 	bind_tables(ps, a);
@@ -780,31 +804,26 @@ static bool launch_variants_kernel(PlanState *ps, const VariantsDecision &route,
 }
 
 /* The views kernel (das_views.hip): the views the route has it take, from the ONE DAS input, in one launch -- their rows and the prefix
- * table go through pinned memory on the push's stream ahead of it, read in place by a small kernel (no copy engine: bf_launch_views_table).
- * View k's job is jobs[k * step] (a views push: step 1).  fused_frames: a burst views push's fused launch (das_burst.hip:
- * das_burst_views_kernel) instead -- that many RF frames, in_stride apart, view k's frames jobs[k * step .. k * step + fused_frames - 1]. */
+ * table staged ahead of it.  View k's job is jobs[k * step] (a views push: step 1).  fused_frames: a burst views push's fused launch
+ * (das_burst.hip: das_burst_views_kernel) instead -- that many RF frames, in_stride apart, view k's frames
+ * jobs[k * step .. k * step + fused_frames - 1]. */
 static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const DasJob *jobs, uint32_t K, hipStream_t s, uint32_t step = 1,
                                 uint32_t fused_frames = 0, uint64_t in_stride = 0)
 {
 	Device &d = *g_context.cur;
-	bool ok = true;
 	const uint32_t n = route.kernel_views;
 	const size_t rows_bytes = sizeof(BfViewRow) * n, table_bytes = rows_bytes + sizeof(uint32_t) * (n + 1);
-	if (d.views_copy_pending) { (void)hipEventSynchronize(d.views_copied); d.views_copy_pending = false; }
-	BfViewRow *rows = (BfViewRow *)d.views_pinned;
-	for (uint32_t k = 0, r = 0; k < K; k++) {
-		if (!route.taken[k]) continue;
-		rows[r] = route.rows[r];
-		rows[r].out_offset = (uint64_t)(jobs[k * step].out - jobs[0].out);
-		rows[r].out_stride = fused_frames > 1 ? (uint64_t)(jobs[k * step + 1].out - jobs[k * step].out) : 0;
-		r++;
-	}
-	std::memcpy((char *)d.views_pinned + rows_bytes, route.first_block.data(), sizeof(uint32_t) * (n + 1));
-	void *mapped = nullptr;
-	ok &= HIP_OK(hipHostGetDevicePointer(&mapped, d.views_pinned, 0));
-	if (ok) ok &= HIP_OK(bf_launch_views_table(d.views_table.ptr, mapped, (uint32_t)table_bytes, s));
-	d.views_copy_pending = HIP_OK(hipEventRecord(d.views_copied, s));
-	ok &= d.views_copy_pending;
+	bool ok = stage_table(table_bytes, s, [&](void *pinned) {
+		BfViewRow *rows = (BfViewRow *)pinned;
+		for (uint32_t k = 0, r = 0; k < K; k++) {
+			if (!route.taken[k]) continue;
+			rows[r] = route.rows[r];
+			rows[r].out_offset = (uint64_t)(jobs[k * step].out - jobs[0].out);
+			rows[r].out_stride = fused_frames > 1 ? (uint64_t)(jobs[k * step + 1].out - jobs[k * step].out) : 0;
+			r++;
+		}
+		std::memcpy((char *)pinned + rows_bytes, route.first_block.data(), sizeof(uint32_t) * (n + 1));
+	});
 	BfDasArgs a = route.a;
 	a.rf = jobs[0].in; a.out = jobs[0].out;
 	bind_tables(ps, a);
@@ -818,48 +837,77 @@ static bool launch_views_kernel(PlanState *ps, const ViewsDecision &route, const
 	return ok;
 }
 
-/* The READI image's decode across acquisitions (readi_decode.hip): the N DAS inputs at `in`, in_stride bytes apart, each
- * [channel][A][samples], into d.readi_decoded as [channel][G x A][samples] by the signs of the block's own READI matrix (ps: the
- * block's plan state -- the table the block's READI kernels read). */
-static bool launch_image_decode(PlanState *ps, const BeamformerParameters &bp, const void *in, uint64_t in_stride, const uint32_t *groups, uint32_t N, hipStream_t s)
+/* A READI image push's decode across acquisitions (readi_decode.hip): the N DAS inputs at `cur`, cur_stride bytes apart, each
+ * [channel][A][samples], into d.readi_decoded (push_frames grew it) as [channel][G x A][samples] by the signs of the block's own READI
+ * matrix (ps: the block's plan state -- the table the block's READI kernels read).  `cur` becomes the decoded buffer, decoded_bytes of
+ * it what beamformer_hip_copy_das_input serves. */
+static bool launch_decode_step(PlanState *ps, const BeamformerParameters &bp, const char *&cur, uint64_t &cur_stride, const uint32_t *groups, uint32_t N,
+                                uint64_t decoded_bytes, hipStream_t s)
 {
 	Device &d = *g_context.cur;
 	const Plan &plan = ps->plan;
-	bool ok = upload_group_ids(groups, N, s);
+	bool ok = true;
+	if (hooks().scratch_poison) ok &= HIP_OK(hipMemsetAsync(d.readi_decoded.ptr, 0xFF, d.readi_decoded.size, s));
+	ok &= stage_group_ids(groups, N, s);
 	BfReadiDecodeArgs a{};
-	a.in = in; a.out = d.readi_decoded.ptr;
+	a.in = cur; a.out = d.readi_decoded.ptr;
 	a.groups   = (const uint32_t *)d.views_table.ptr;
 	a.hadamard = (const uint32_t *)ps->readi_hadamard.ptr;
-	a.in_frame_bytes = in_stride;
+	a.in_frame_bytes = N > 1 ? cur_stride : 0;
 	a.slab_floats = (uint64_t)plan.acquisitions * plan.das_samples * (plan.iq_pipeline ? 2u : 1u);
 	a.frames = N; a.group_count = bp.readi_group_count; a.channels = plan.channels;
-	return ok && HIP_OK(bf_launch_readi_image_decode(&a, s));
+	ok = ok && HIP_OK(bf_launch_readi_image_decode(&a, s));
+	d.das_decoded_bytes = decoded_bytes;
+	cur = (const char *)d.readi_decoded.ptr; cur_stride = 0;
+	return ok;
 }
 
-/* a frame's parts keep the per-frame counters: [0] staged window violations, [1] / [2] das_tile.hip's staged / gathered chunks */
-static bool keeps_counters(const std::vector<DasDecision> &parts)
+/* some job that is not fused has a Staged or Tile part: its own launch keeps the per-frame counters -- [0] staged window violations,
+ * [1] / [2] das_tile.hip's staged / gathered chunks */
+static bool wants_counters(const DasJob *jobs, uint32_t count)
 {
-	for (const DasDecision &dd : parts) if (dd.path == DasPath_Staged || dd.path == DasPath_Tile) return true;
+	for (uint32_t k = 0; k < count; k++) {
+		if (jobs[k].fused || !jobs[k].parts) continue;
+		for (const DasDecision &dd : *jobs[k].parts) if (dd.path == DasPath_Staged || dd.path == DasPath_Tile) return true;
+	}
 	return false;
 }
 
-/* The stages of a plan over the frames of one push, in stream order: every pre-DAS stage ONE launch for all RF frames (launch_stage), then
- * the frames placed in the ring and the DAS stage as a list of jobs, one per frame -- a single push: one; a burst: N, frame k on its slice
- * of the input; a views push: K grids on the ONE input --: the push's fused launch for the jobs its route gives it, each other job's own
- * launch(es), the pair count per run of jobs with the same parts -- with one timing segment per stage in w.t and the DAS fields of every
- * frame's timing row. */
-static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
+/* The geometry-only recount of job j's apodization test into `mine`: the general kernel's count over every part of the frame. */
+static bool launch_pair_count(PlanState *das_ps, const DasJob &j, unsigned long long *mine, uint64_t voxel_bytes, hipStream_t s)
+{
+	bool ok = HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
+	const DasDecision &head = main_part(*j.parts);
+	for (const DasDecision &dd : *j.parts) {
+		if (!ok || dd.path == DasPath_Zero) continue;
+		BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
+		count.rf = j.in; count.out = j.out + (uint64_t)(dd.z_first - j.z_first) * head.a.size[0] * head.a.size[1] * voxel_bytes;
+		bind_tables(das_ps, count);
+		if (j.group >= 0) count.readi_group = (uint32_t)j.group;
+		count.pair_counter = mine;
+		ok &= HIP_OK(bf_launch_das_count(&count, s));
+	}
+	return ok;
+}
+
+/* The stages of a plan over one push, in stream order, with one timing segment per stage in w.t.
+ * Pre-DAS: every stage ONE launch for all RF frames (launch_stage), ping-ponging between the push's stage buffers.
+ * DAS: the push's frames are placed in the ring (next_frames) and each job's `in` -- its RF frame's slice of the DAS input -- and `out`
+ * -- its ring slot -- resolved.  Then, in this order: the optional decode step, which replaces the DAS input; the push's fused launch
+ * for the jobs marked `fused`, dispatched by kind in the one switch below; every other job's own launch(es), the kernels of a single
+ * push; the pair count, once per run of jobs with the same parts.  Which push is running shows in that switch and nowhere else: all
+ * other steps read the job list.
+ * No DAS stage in the plan: the frames are placed and cleared.  Last, the DAS fields of every frame's timing row. */
+static bool walk_plan(uint32_t block, PlanState *ps, const Push &w)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
 	const Plan &plan = ps->plan;
 	const ParameterBlock &pb = c.blocks[block];
 	hipStream_t s = d.stream;
-	TimingSlot &t = w.t;
-	const uint32_t N = w.frames;
-	const uint32_t F = w.burst_views ? w.view_count * N : w.views ? w.view_count : w.variants ? w.variant_count : w.image ? 1u : N;   /* frames the walk queues */
-	const uint32_t per_view = w.burst_views ? N : 1u;      /* frames of a view: job v * per_view + k is (view v, RF frame k) */
-	PlanState *das_ps = w.image ? &w.image->ps : ps;        /* whose tables and decision the DAS launches run with */
+	TimingSlot &t = *w.t;
+	const uint32_t N = w.rf_frames, F = w.frames;
+	DasJob *jobs = w.jobs;
 
 	const char *cur = (const char *)w.in;
 	uint64_t cur_stride = w.in_stride;
@@ -868,15 +916,9 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	bool ok = true;
 	d.das_input = nullptr; d.das_input_bytes = d.das_input_stride = 0; d.das_input_frames = 0; d.das_decoded_bytes = 0;
 
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-	if (c.device_count > 1) { zfirst = d.slab_first; zcount = d.slab_count; }   /* this device's z-slab (run_peers) */
-	uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
 	const uint64_t voxel_bytes = plan.iq_pipeline ? 8u : 4u;
 	const uint64_t first = d.frame_counter;                 /* the id of the walk's first frame */
-	DasJob one{}, *jobs = nullptr;                          /* the DAS stage's jobs, once it has run (a single push: no allocation) */
-	std::vector<DasJob> many;
-	bool counters_kept = false;                             /* some job that is not fused has a Staged or Tile part */
+	const bool counters_kept = wants_counters(jobs, F);
 
 	/* hook SCRATCH_POISON: both intermediate buffers, and below the frames' ring slots once next_frames has placed them (nothing writes
 	 * them before the DAS stage), are filled with 0xFF bytes -- NaN in binary16 and in f32 -- so that an element a stage reads without
@@ -901,66 +943,48 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 		}break;
 		case BeamformerShaderKind_DAS:{
 			uint64_t run_bytes = 0;
-			FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes, per_view);
+			FrameRecord *frame0 = next_frames(jobs, F, plan.iq_pipeline, block, run_bytes);
 			if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 			if (poison && run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0xFF, run_bytes, s));
-			/* what beamformer_hip_copy_das_input_frame serves: RF frame k's input at k * cur_stride (one RF frame -- a single push, a views
-			 * push -- : all jobs share the one input) */
+			/* what beamformer_hip_copy_das_input_frame serves: RF frame k's input at k * cur_stride (one RF frame: all jobs share the one
+			 * input) */
 			d.das_input = cur; d.das_input_bytes = (uint64_t)plan.das_samples * plan.acquisitions * plan.channels * voxel_bytes;   /* [channel][transmit][sample] */
 			d.das_input_stride = N > 1 ? cur_stride : 0; d.das_input_frames = N;
-			/* (Flag 0x2000: a views push's step fails here, as a refused launch would -- the only way to a views push's tombstones that
-			 * needs no device fault: everything a caller can get wrong is refused before the ids are taken) */
-			if ((w.views || w.variants) && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
-			if (zcount == 0) break;      /* more devices than planes: this device holds an empty slab of the frame */
+			/* (Flag 0x2000: the step fails here, as a refused launch would -- the only way to such a push's tombstones that needs no
+			 * device fault: everything a caller can get wrong is refused before the ids are taken) */
+			if (w.fails_on_flag && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
+			if (!jobs[0].parts) break;   /* more devices than planes: this device holds an empty slab of the frame */
 
-			/* ---- the jobs.  Which kernel, with which geometry: one table of rules (das_select.cpp), for a single push and a burst computed
-			 * once per plan / shard / path mode / hook change and reused by every frame after it, for a views push per view by its route.
-			 * Usually ONE launch per job; where a term of the frame can reach an end of its RF row the z range is cut and the planes
-			 * concerned go to the kernel behind the staged one (decide_das_parts, das_exact.h). */
-			if (F > 1) many.resize(F);
-			jobs = F > 1 ? many.data() : &one;
-			const std::vector<DasDecision> *cached = w.views || w.variants ? nullptr : w.image ? &frame_das_parts(das_ps, w.image->pb, zfirst, zcount)
-			                                                              : &frame_das_parts(ps, pb, zfirst, zcount);
-			if (w.image && main_part(*cached).path != DasPath_Zero) {
-				/* ---- 0. a READI image push: the N DAS inputs decoded across the acquisitions, its own segment directly before DAS; the
-				 * ONE job below reads the decoded buffer (push_frames grew it) */
-				if (poison) ok &= HIP_OK(hipMemsetAsync(d.readi_decoded.ptr, 0xFF, d.readi_decoded.size, s));
-				ok &= launch_image_decode(ps, pb.parameters, cur, N > 1 ? cur_stride : 0, w.readi_groups, N, s);
+			/* ---- the jobs.  Which kernel, with which geometry: one table of rules (das_select.cpp), in each job's parts.  Usually ONE
+			 * launch per job; where a term of the frame can reach an end of its RF row the z range is cut and the planes concerned go to
+			 * the kernel behind the staged one (decide_das_parts, das_exact.h). */
+			if (w.decode_groups && main_part(*jobs[0].parts).path != DasPath_Zero) {
+				/* ---- 0. the decode step, its own segment directly before DAS */
+				ok &= launch_decode_step(ps, pb.parameters, cur, cur_stride, w.decode_groups, N, main_part(*jobs[0].parts).das_input_bytes, s);
 				segment(t, (uint32_t)BeamformerShaderKind_Decode, s);
-				d.das_decoded_bytes = main_part(*cached).das_input_bytes;
-				cur = (const char *)d.readi_decoded.ptr; cur_stride = 0;
 			}
 			bool any_fused = false, any_counted = false;
 			for (uint32_t k = 0; k < F; k++) {
 				DasJob &j = jobs[k];
-				const uint32_t view = k / per_view, rf_frame = w.burst_views ? k % per_view : k;
-				j.in  = cur + rf_frame * cur_stride;
+				j.in  = cur + j.rf_frame * cur_stride;
 				j.out = (char *)d.ring.ptr + d.frames[(first + k) % d.frames.size()].offset;
-				j.readi_group = w.readi_groups && !w.image ? (int32_t)w.readi_groups[k] : -1;
-				/* (a burst views push: `fused` also names the jobs the views kernel covers per RF frame, rung 2) */
-				j.ps = das_ps;
-				if (w.views)         { j.parts = &w.views_route->parts[view]; j.z_first = 0; j.points = w.views[view].output_points; j.fused = w.views_route->taken[view] != 0; }
-				else if (w.variants) { j.parts = &w.variants->parts[k]; j.z_first = zfirst; j.points = points; j.fused = w.variants->taken[k] != 0; }
-				else                 { j.parts = cached; j.z_first = zfirst; j.points = points; j.fused = w.route && w.route->burst_kernel; }
 				const DasDecision &head = main_part(*j.parts);
 				j.path = (uint32_t)(head.path == DasPath_Zero ? DasPath_General : head.path);
-				any_fused     |= j.fused;
-				any_counted   |= head.path != DasPath_Zero;
-				counters_kept |= !j.fused && keeps_counters(*j.parts);
+				any_fused   |= j.fused;
+				any_counted |= head.path != DasPath_Zero;
 			}
 
-			/* ---- 1. the push's fused launch; a burst views push: rung 1 its kernel once, rung 2 the views kernel once per RF frame, on
-			 * that frame's jobs (k, N + k, 2 N + k, ...) and its slice of the input */
-			if (!any_fused) {
-			} else if (w.burst_views && w.burst_views->rung == 1) {
-				ok &= launch_views_kernel(ps, *w.views_route, jobs, w.view_count, s, N, N, N > 1 ? cur_stride : 0);
-			} else if (w.burst_views) {
-				for (uint32_t k = 0; k < N && ok; k++) ok &= launch_views_kernel(ps, *w.views_route, jobs + k, w.view_count, s, N);
-			} else {
-				ok &= w.views        ? launch_views_kernel(ps, *w.views_route, jobs, F, s)
-				    : w.variants     ? launch_variants_kernel(ps, *w.variants, jobs, F, s)
-				    : w.readi_groups ? launch_readi_sweep_kernel(ps, *w.route, jobs[0], w.readi_groups, N, cur_stride, frame0->bytes, s)
-				                     : launch_burst_kernel(ps, *w.route, jobs[0], N, cur_stride, frame0->bytes, s);
+			/* ---- 1. the push's fused launch.  Jobs are view-major where there are views: view v's RF frame k is job v * N + k */
+			switch (any_fused ? w.fused.kind : FusedLaunch::None) {
+			case FusedLaunch::None:       break;
+			case FusedLaunch::Burst:      ok &= launch_burst_kernel(ps, *w.fused.burst, jobs[0], nullptr, N, cur_stride, frame0->bytes, s); break;
+			case FusedLaunch::ReadiSweep: ok &= launch_burst_kernel(ps, *w.fused.burst, jobs[0], w.fused.groups, N, cur_stride, frame0->bytes, s); break;
+			case FusedLaunch::Views:      ok &= launch_views_kernel(ps, *w.fused.views, jobs, F, s); break;
+			case FusedLaunch::Variants:   ok &= launch_variants_kernel(ps, *w.fused.variants, jobs, F, s); break;
+			case FusedLaunch::BurstViews: ok &= launch_views_kernel(ps, *w.fused.views, jobs, F / N, s, N, N, N > 1 ? cur_stride : 0); break;
+			case FusedLaunch::ViewsPerRfFrame:      /* RF frame k: jobs k, N + k, 2 N + k, ... */
+				for (uint32_t k = 0; k < N && ok; k++) ok &= launch_views_kernel(ps, *w.fused.views, jobs + k, F / N, s, N);
+				break;
 			}
 			/* ---- 2. every other job's own launch(es): the kernels of a single push.  One set of counters per timing slot */
 			if (counters_kept && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) ok = false;
@@ -973,32 +997,21 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 					ok &= HIP_OK(hipMemsetAsync(frame_counters, 0, 4 * sizeof(uint32_t), s));
 				}
 				const DasDecision &head = main_part(*j.parts);
-				ok &= launch_frame_parts(j.ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.readi_group);
+				ok &= launch_frame_parts(w.das_ps, *j.parts, j.z_first, (uint64_t)head.a.size[0] * head.a.size[1] * voxel_bytes, j.in, j.out, frame_counters, s, j.path, j.group);
 			}
 			/* ---- 3. geometry-only recount of the apodization test; its own segment so that it stays out of the DAS time.  The count is
-			 * the same for every job of a run of jobs with the same parts (a burst: one run; a views push: one per view; a variants push: one per variant -- f_number changes the count): it runs once,
-			 * into the counter of the run's last frame, and the run's other frames' counters are copies -- the newest 32 frames only */
+			 * the same for every job of a run of jobs with the same parts (jobs that differ in their group alone are one run: the group
+			 * only signs the terms; jobs under different f-numbers are not): it runs once, into the counter of the run's last frame, and
+			 * the run's other frames' counters are copies -- the newest 32 frames only */
 			if (c.count_pairs && any_counted) {
 				segment(t, (uint32_t)st.kind, s);
 				ok &= d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2));
 				unsigned long long *counters = (unsigned long long *)d.pair_counter.ptr;
 				for (uint32_t begin = 0, end; begin < F && ok; begin = end) {
-					/* (a READI sweep's jobs differ in their group alone, which only signs the terms: one run, one count) */
 					for (end = begin + 1; end < F && jobs[end].parts == jobs[begin].parts; end++) {}
 					if (F - (end - 1) > kTimingSlots) continue;
-					const DasJob &j = jobs[begin];
 					unsigned long long *mine = counters + (first + end - 1) % kTimingSlots;
-					ok &= HIP_OK(hipMemsetAsync(mine, 0, sizeof(*mine), s));
-					const DasDecision &head = main_part(*j.parts);
-					for (const DasDecision &dd : *j.parts) {
-						if (!ok || dd.path == DasPath_Zero) continue;
-						BfDasArgs count = dd.general;              /* the general kernel's own tiles: the specialised kernels reshape them */
-						count.rf = j.in; count.out = j.out + (uint64_t)(dd.z_first - j.z_first) * head.a.size[0] * head.a.size[1] * voxel_bytes;
-						bind_tables(j.ps, count);
-						if (j.readi_group >= 0) count.readi_group = (uint32_t)j.readi_group;
-						count.pair_counter = mine;
-						ok &= HIP_OK(bf_launch_das_count(&count, s));
-					}
+					ok &= launch_pair_count(w.das_ps, jobs[begin], mine, voxel_bytes, s);
 					for (uint32_t k = end - 1; k-- > begin && F - k <= kTimingSlots && ok;)
 						ok &= HIP_OK(hipMemcpyAsync(counters + (first + k) % kTimingSlots, mine, sizeof(*mine), hipMemcpyDeviceToDevice, s));
 				}
@@ -1014,30 +1027,30 @@ static bool walk_plan(uint32_t block, PlanState *ps, const StageWalk &w)
 	}
 	if (plan.das_index < 0 && ok) {
 		/* no DAS in the pipeline: the frames exist and stay zero (the reference clears them, beamformer_core.c:1573-1585, and nothing
-		 * writes them).  A single push's frame is the block's whole grid whatever its shard -- with several devices on the ingest device,
-		 * the others holding an empty slab of it; a burst's frames are the shard's planes */
-		if (!w.route && !w.image) points[2] = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
+		 * writes them) */
 		uint64_t run_bytes = 0;
-		FrameRecord *frame0 = next_frames(points, plan.iq_pipeline, block, F, w.views, run_bytes, per_view);
+		FrameRecord *frame0 = next_frames(jobs, F, plan.iq_pipeline, block, run_bytes);
 		if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 		if (run_bytes) ok &= HIP_OK(hipMemsetAsync((char *)d.ring.ptr + frame0->offset, 0, run_bytes, s));
 	}
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	for (uint32_t k = 0; k < F; k++) {
 		const bool own_counters = counters_kept && F - k <= kTimingSlots;
-		const DasJob *j = jobs ? &jobs[k] : nullptr;         /* null: no DAS kernel ran for the frame */
-		fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, j ? j->parts : nullptr, j ? j->points : points, plan.iq_pipeline,
-		                j ? j->path : 0, own_counters ? (first + k) % kTimingSlots : ~0ull);
+		const DasJob &j = jobs[k];                            /* parts null: no DAS kernel ran for the frame */
+		fill_das_fields(d.timing[(first + k) % kTimingSlots], first + k, j.parts, j.points, plan.iq_pipeline, j.path, own_counters ? (first + k) % kTimingSlots : ~0ull);
 	}
 	return true;
 }
 
-/* One frame of a single push: the walk over d.scratch[], timed in the frame's own slot. */
+/* One frame of a single push: the walk over d.scratch[], timed in the frame's own slot, with its one job on the stack. */
 static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, bool ingest_timed)
 {
-	Device &d = *g_context.cur;
+	Context &c = g_context;
+	Device &d = *c.cur;
 	PlanState *ps = commit_block(block);
 	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const Plan &plan = ps->plan;
+	const ParameterBlock &pb = c.blocks[block];
 	TimingSlot &t = d.timing[d.frame_counter % kTimingSlots];
 	t.failed = false; t.share = 1;
 	if (!ensure_events(t)) return false;
@@ -1045,7 +1058,21 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 	t.count = 0; t.counted = false;
 	if (ingest_timed) segment(t, kStageIngest, d.stream);
 	else              record(t, 0, d.stream);
-	return walk_plan(block, ps, StageWalk{1, rf, 0, rf_bytes, d.scratch, 0, t, nullptr});
+
+	uint32_t zfirst = 0, zcount = plan.output_points[2];
+	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	if (c.device_count > 1) { zfirst = d.slab_first; zcount = d.slab_count; }   /* this device's z-slab (run_peers) */
+	/* no DAS in the pipeline: a single push's frame is the block's whole grid whatever its shard -- with several devices on the ingest
+	 * device, the others holding an empty slab of it (a burst's frames are the shard's planes) */
+	if (plan.das_index < 0) zcount = c.device_count > 1 && d.index != 0 ? 0u : plan.output_points[2];
+	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
+	DasJob one{};
+	one.points = points; one.z_first = zfirst; one.group = -1;
+	one.parts = frame_das_parts(ps, pb, zfirst, zcount);
+	Push w;
+	w.in = rf; w.in_bound = rf_bytes; w.stage = d.scratch; w.t = &t;
+	w.jobs = &one; w.das_ps = ps;
+	return walk_plan(block, ps, w);
 }
 
 /* z-slab of device `i` of `n` over `planes` planes starting at `first`: contiguous, sizes differing by
@@ -1390,31 +1417,50 @@ static void share_timing_rows(Device &d, uint64_t first, uint32_t N, uint32_t ow
 	}
 }
 
-/* What is a multi-frame push's own (push_frames runs the rest): */
-struct FramesPush {
-	PushRecord::Kind kind;
-	uint32_t rf_frames, rf_frame_size;       /* the upload: this many RF frames back to back, each this many bytes of the caller's */
-	uint32_t frames;                         /* the frames it queues: all of `points`, or -- `views` given -- frame k of views[k]'s */
-	const uint32_t *points;
-	const BeamformerHipView *views;
-	const BurstDecision *burst;              /* its route (das_select.h), one of the two */
-	const ViewsDecision *views_route;
-	bool          wants_counters;            /* a frame's own launch keeps the staged / tile counters */
-	DeviceBuffer *stage;                     /* the pre-DAS stages' ping-pong pair and, where it holds every RF frame's output, the stride to grow it by */
-	uint64_t      stage_stride;
-	float         decide_us;
-	const uint32_t *readi_groups = nullptr;  /* a READI sweep, a READI image push: rf_frames validated group ids, frame k's readi_group */
-	ImagePlanState *image = nullptr;         /* a READI image push: its derived block, its route and the bytes of its decoded DAS input */
-	const ReadiImageDecision *image_route = nullptr;
-	uint64_t        decoded_bytes = 0;
-	const BurstViewsDecision *burst_views = nullptr;   /* a burst views push: `frames` = rf_frames x its views, view-major; views_route: its per-view part */
-	const VariantsDecision   *variants = nullptr;      /* a variants push: its route; `frames` variants of `points` */
+/* What every multi-frame push starts from: how the block's RF lies in memory, its committed plan, and the planes and grid of its frames
+ * (the block's output shard, where it has one).  whole_grid: the push takes one device and no output shard -- its frames are views of
+ * their own or cover the block's whole grid -- and is refused otherwise. */
+struct PushGround {
+	RfLayout   l;
+	PlanState *ps;
+	uint32_t   z_first, z_count, points[3];
 };
 
-/* A push of several frames with ONE upload and ONE event set (one device) -- a burst: N RF frames, N frames; a views push: one RF frame
- * on K grids; a variants push: one RF frame on the block's grid under K sets of DAS scalars (das_variants.hip for the variants
- * decide_variants gives it, every other variant its own launch(es) under its derived decision); a burst views push: N RF frames on K grids, N x K frames view-major (frame v * N + k: view v, RF frame k), by the ladder of
- * decide_burst_views -- its fused launch (das_burst_views.hip), or per RF frame the views push's DAS step, or every frame its own launch(es).
+static bool begin_push(uint32_t block, bool whole_grid, PushGround &g)
+{
+	Context &c = g_context;
+	const ParameterBlock &pb = c.blocks[block];
+	if (whole_grid && (c.device_count > 1 || pb.shard_z_count)) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!rf_layout(pb, g.l)) return false;
+	g.ps = commit_block(block);
+	if (!g.ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const Plan &plan = g.ps->plan;
+	g.z_first = 0; g.z_count = plan.output_points[2];
+	if (pb.shard_z_count) { g.z_first = pb.shard_z_first; g.z_count = pb.shard_z_count; }
+	g.points[0] = plan.output_points[0]; g.points[1] = plan.output_points[1]; g.points[2] = g.z_count;
+	return true;
+}
+
+/* A frame of the push's own grid, from RF frame rf_frame's DAS input */
+static DasJob grid_job(const PushGround &g, const std::vector<DasDecision> *parts, uint32_t rf_frame, bool fused)
+{
+	DasJob j{};
+	j.rf_frame = rf_frame; j.points = g.points; j.z_first = g.z_first;
+	j.parts = parts; j.fused = fused; j.group = -1;
+	return j;
+}
+
+/* A frame of a view's grid: its whole grid, whatever the block's */
+static DasJob view_job(const BeamformerHipView &view, const std::vector<DasDecision> &parts, uint32_t rf_frame, bool fused)
+{
+	DasJob j{};
+	j.rf_frame = rf_frame; j.points = view.output_points; j.tag = view.image_plane_tag;
+	j.parts = parts.empty() ? nullptr : &parts; j.fused = fused; j.group = -1;
+	return j;
+}
+
+/* A push of several frames with ONE upload and ONE event set, on one device.  The push_* function below describes the frames (Push: the
+ * job list, the fused launch, the decode step); this function runs them:
  *   RF        one upload into one pinned slot -- over the copy engine into device staging when it is large, read in place over PCIe when
  *             small, by kOverlapBytes applied to the whole upload -- and ONE slot of the RF ring, frame k at k * rf_stride with 64 spare
  *             bytes behind every frame;
@@ -1422,26 +1468,28 @@ struct FramesPush {
  *             grid y beside the channels for the filters, which then take a burst in chunks of 65535 / channels frames) and address and
  *             bound every frame as a single frame is; several RF frames: frame k of a stage's output at k * stage_stride of burst_stage[],
  *             one: the single push's d.scratch[];
- *   DAS       the jobs of walk_plan: the push's fused launch (das_burst.hip where decide_burst says so; das_views.hip for the views
- *             decide_views gives it), every other frame its own launch(es) -- a burst's on its slice of the input, a view's on the one input;
+ *   DAS       the jobs of walk_plan;
  *   frames    contiguous in the frame ring, each rounded to 64 bytes (a run that would straddle the end starts again at 0), consecutive
- *             ids -- a burst's oldest RF frame first, a views push's in view order;
+ *             ids in job order;
  *   timings   one event set for the push, in the timing slot of its last frame; every frame's slot points there with share = frames.
  * Everything that can be refused is checked, and every buffer whose absence would fail the push is grown, BEFORE the ids are taken: a
  * refused push queues nothing.  (The tables some single-frame kernels keep -- staged_tables, hercules_table, hercules_pairs -- are grown
  * where a frame's launch asks for them, launch_das_part, each with a kernel to fall back on: growing one mid-push drains the device and
- * fails nothing.)  After that a failure leaves tombstones under all of its ids. */
-static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const void *data, bool data_on_device, const FramesPush &m)
+ * fails nothing.)  After that a failure leaves tombstones under all of its ids.  True: d.multi records the push, but for its route,
+ * which the caller adds. */
+static bool push_frames(uint32_t block, const PushGround &g, const void *data, bool data_on_device, Push &m)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
 	const ParameterBlock &pb = c.blocks[block];
+	PlanState *ps = g.ps;
 	const Plan &plan = ps->plan;
+	const RfLayout &l = g.l;
 	hipStream_t s = d.stream;
 	const uint32_t N = m.rf_frames, F = m.frames;
 
 	uint64_t run_bytes = 0;
-	if (!frame_run_bytes(m.points, m.views, F, plan.iq_pipeline ? 8u : 4u, d.ring.size, run_bytes, m.burst_views ? N : 1u)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+	if (!job_run_bytes(m.jobs, F, plan.iq_pipeline ? 8u : 4u, d.ring.size, run_bytes)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 
 	/* device and pinned memory, grown before anything is queued */
 	const uint64_t rf_stride = round_up(l.rf_size, 64) + 64;
@@ -1449,6 +1497,8 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
 	const bool overlap = !data_on_device && total >= kOverlapBytes;
 	bool fits = d.rf[slot].ensure(rf_stride * N);
+	m.stage = N > 1 ? d.burst_stage : d.scratch;
+	m.stage_stride = N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0;
 	if (m.stage_stride) {
 		size_t pre_das_stages = 0;
 		for (size_t i = 0; i < plan.stages.size(); i++) {
@@ -1459,9 +1509,9 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 		for (size_t k = 0; k < 2 && k < pre_das_stages; k++) fits = fits && m.stage[k].ensure(m.stage_stride * N);
 	}
 	if (overlap) fits = fits && d.raw_staging[slot].ensure(round_up(total, 64) + 64);
-	if (m.image) fits = fits && d.readi_decoded.ensure(round_up(m.decoded_bytes, 64) + 64);
-	if ((m.views_route && m.views_route->kernel_views) || (m.variants && m.variants->kernel_variants) || (m.readi_groups && m.burst && m.burst->burst_kernel) || m.image) {
-		/* (one size for both users: a sweep's BEAMFORMER_HIP_MAX_BURST_FRAMES group ids are 4 KiB of it) */
+	if (m.decode_groups) fits = fits && d.readi_decoded.ensure(round_up(m.decoded_bytes, 64) + 64);
+	if (m.decode_groups || (m.fused.kind != FusedLaunch::None && m.fused.kind != FusedLaunch::Burst)) {
+		/* what stage_table goes through (one size for all users: a sweep's BEAMFORMER_HIP_MAX_BURST_FRAMES group ids are 4 KiB of it) */
 		const size_t table_bytes = (sizeof(BfViewRow) + sizeof(uint32_t)) * BEAMFORMER_HIP_MAX_VIEWS + sizeof(uint32_t);
 		fits = fits && d.views_table.ensure(table_bytes);
 		if (fits && !d.views_pinned && !HIP_OK(hipHostMalloc(&d.views_pinned, table_bytes, hipHostMallocDefault))) { d.views_pinned = nullptr; fits = false; }
@@ -1474,7 +1524,7 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	TimingSlot &t = d.timing[owner];
 	if (!ensure_events(t)) return false;
 	if (c.count_pairs && !d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2))) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
-	if (m.wants_counters && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	if (wants_counters(m.jobs, F) && !d.staged_violations.ensure(sizeof(uint32_t) * 4 * kTimingSlots)) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
 
 	/* ---- from here on the push owns ids first .. first + F - 1 ---- */
 	d.rf_index++;
@@ -1504,9 +1554,9 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 
 	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
 	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
-	const bool done = walk_plan(block, ps, StageWalk{N, d.rf[slot].ptr, rf_step, (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size), m.stage, m.stage_stride, t,
-	                                                 m.burst, m.views, m.views ? F / (m.burst_views ? N : 1u) : 0u, m.views_route, m.burst_views, m.readi_groups, m.image,
-	                                                 m.variants, m.variants ? F : 0u});
+	m.in = d.rf[slot].ptr; m.in_stride = rf_step; m.in_bound = (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size);
+	m.t = &t;
+	const bool done = walk_plan(block, ps, m);
 	finish_upload(u, overlap, s);
 	if (!done) return false;
 
@@ -1514,106 +1564,77 @@ static bool push_frames(uint32_t block, PlanState *ps, const RfLayout &l, const 
 	PushRecord &r = d.multi;
 	r.kind = m.kind; r.first_id = first; r.count = F; r.events_slot = owner; r.decide_us = m.decide_us;
 	r.rf_frames = N;
-	if (m.burst)            r.burst = *m.burst;
-	else if (m.image_route) r.image = *m.image_route;
-	else if (m.burst_views) describe_burst_views_decision(*m.burst_views, F / N, &r.burst_views);
-	else if (m.variants)    describe_variants_decision(*m.variants, F, &r.variants);
-	else                    describe_views_decision(*m.views_route, F, &r.views);
 	lockstep.complete = true;
 	return true;
 }
 
-/* beamformer_hip_push_data_burst_with_compute: frame_count RF frames of one parameter block in one call, frame_count frames of the
- * block's grid (its shard's planes).  The route: decide_burst on the block's own single-frame decision. */
-bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, bool data_on_device)
+/* beamformer_hip_push_data_burst_with_compute: frame_count (two or more: one goes to the single push) RF frames of one parameter block
+ * in one call, frame_count frames of the block's grid (its shard's planes).  The route: decide_burst on the block's own single-frame
+ * decision.
+ * beamformer_hip_push_data_readi_sweep_with_compute (groups given): a burst of a READI block whose frame k is beamformed with
+ * readi_group = groups[k] (frame_count ids, every one below the block's readi_group_count: lib_api.cpp has checked both).  The route:
+ * decide_burst as a sweep. */
+bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
-	ParameterBlock &pb = c.blocks[block];
+	const ParameterBlock &pb = c.blocks[block];
 	const uint32_t N = frame_count;
+	PushGround g;
+	if (!begin_push(block, false, g)) return false;
+	const Plan &plan = g.ps->plan;
 
-	RfLayout l;
-	if (!rf_layout(pb, l)) return false;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	const Plan &plan = ps->plan;
-
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
-	std::vector<DasDecision> no_parts;
-	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
+	const std::vector<DasDecision> *parts = frame_das_parts(g.ps, pb, g.z_first, g.z_count);
 	BurstDecision route;
-	if (!parts.empty()) decide_burst(pb, plan, ps->transmit_table, parts, zfirst, zcount, c.das_path_mode, N, route);
-	else { route.stage_launches = (N + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels); route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared"; }
+	if (parts) decide_burst(pb, plan, g.ps->transmit_table, *parts, g.z_first, g.z_count, c.das_path_mode, N, route, groups != nullptr);
+	else {
+		const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
+		route.readi_sweep = groups != nullptr;
+		if (groups) route.min_frames = kReadiSweepMinFrames;
+		route.stage_launches = (N + chunk - 1) / chunk; route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared";
+	}
 
-	return push_frames(block, ps, l, data, data_on_device,
-	                   FramesPush{PushRecord::Burst, N, frame_size, N, points, nullptr, &route, nullptr, keeps_counters(parts),
-	                              d.burst_stage, round_up(plan.intermediate_bytes, 64) + 64, 0.0f});
-}
-
-/* beamformer_hip_push_data_readi_sweep_with_compute: a burst of a READI block whose frame k is beamformed with readi_group = groups[k]
- * (frame_count ids, every one below the block's readi_group_count: lib_api.cpp has checked both).  The route: decide_burst as a sweep.
- * One RF frame: the single push's buffers, as a views push. */
-bool push_readi_sweep(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device)
-{
-	Context &c = g_context;
-	Device  &d = *c.cur;
-	ParameterBlock &pb = c.blocks[block];
-	const uint32_t N = frame_count;
-
-	RfLayout l;
-	if (!rf_layout(pb, l)) return false;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	const Plan &plan = ps->plan;
-
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
-	std::vector<DasDecision> no_parts;
-	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(ps, pb, zfirst, zcount) : no_parts;
-	const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
-	BurstDecision route;
-	if (!parts.empty()) decide_burst(pb, plan, ps->transmit_table, parts, zfirst, zcount, c.das_path_mode, N, route, true);
-	else { route.readi_sweep = true; route.min_frames = kReadiSweepMinFrames; route.stage_launches = (N + chunk - 1) / chunk; route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared"; }
-
-	return push_frames(block, ps, l, data, data_on_device,
-	                   FramesPush{PushRecord::Burst, N, frame_size, N, points, nullptr, &route, nullptr, keeps_counters(parts),
-	                              N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0, 0.0f, groups});
+	std::vector<DasJob> jobs(N);
+	for (uint32_t k = 0; k < N; k++) {
+		jobs[k] = grid_job(g, parts, k, route.burst_kernel);
+		if (groups) jobs[k].group = (int32_t)groups[k];
+	}
+	Push m;
+	m.kind = PushRecord::Burst; m.rf_frames = N; m.rf_frame_size = frame_size;
+	m.jobs = jobs.data(); m.frames = N; m.das_ps = g.ps;
+	if (route.burst_kernel) { m.fused.kind = groups ? FusedLaunch::ReadiSweep : FusedLaunch::Burst; m.fused.burst = &route; m.fused.groups = groups; }
+	if (!push_frames(block, g, data, data_on_device, m)) return false;
+	d.multi.burst = route;
+	return true;
 }
 
 /* beamformer_hip_push_data_readi_image_with_compute: the sweep's RF frames and group ids (lib_api.cpp has checked the block, the list
- * and G x A), ONE frame: the derived block's single-frame DAS launch(es) on the DAS input decoded across the acquisitions.  One RF
- * frame: the single push's buffers, as a sweep of one. */
+ * and G x A), ONE frame: the derived block's single-frame DAS launch(es) on the DAS input decoded across the acquisitions. */
 bool push_readi_image(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
-	ParameterBlock &pb = c.blocks[block];
+	const ParameterBlock &pb = c.blocks[block];
 	const uint32_t N = frame_count;
-
-	RfLayout l;
-	if (!rf_layout(pb, l)) return false;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	ImagePlanState *image = commit_image_plan(block, ps);
+	PushGround g;
+	if (!begin_push(block, false, g)) return false;
+	ImagePlanState *image = commit_image_plan(block, g.ps);
 	if (!image) return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
-	const Plan &plan = ps->plan;
+	const Plan &plan = g.ps->plan;
 
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
-	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], zcount};
-	std::vector<DasDecision> no_parts;
-	std::vector<DasDecision> &parts = plan.das_index >= 0 && zcount ? frame_das_parts(&image->ps, image->pb, zfirst, zcount) : no_parts;
+	const std::vector<DasDecision> no_parts, *parts = frame_das_parts(&image->ps, image->pb, g.z_first, g.z_count);
 	ReadiImageDecision route;
-	decide_readi_image(image->ps.plan, parts, pb.parameters.readi_group_count, N, route);
-	const uint64_t decoded = (uint64_t)plan.channels * image->ps.plan.acquisitions * plan.das_samples * (plan.iq_pipeline ? 8u : 4u);
+	decide_readi_image(image->ps.plan, parts ? *parts : no_parts, pb.parameters.readi_group_count, N, route);
 
-	return push_frames(block, ps, l, data, data_on_device,
-	                   FramesPush{PushRecord::Image, N, frame_size, 1, points, nullptr, nullptr, nullptr, keeps_counters(parts),
-	                              N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0, 0.0f, groups,
-	                              image, &route, decoded});
+	DasJob one = grid_job(g, parts, 0, false);
+	Push m;
+	m.kind = PushRecord::Image; m.rf_frames = N; m.rf_frame_size = frame_size;
+	m.jobs = &one; m.frames = 1; m.das_ps = &image->ps;
+	m.decode_groups = groups;
+	m.decoded_bytes = (uint64_t)plan.channels * image->ps.plan.acquisitions * plan.das_samples * (plan.iq_pipeline ? 8u : 4u);
+	if (!push_frames(block, g, data, data_on_device, m)) return false;
+	d.multi.image = route;
+	return true;
 }
 
 /* The record of the newest multi-frame push, when the newest push IS that push, of `kind` and complete: waited for, with its stage
@@ -1642,6 +1663,10 @@ static const PushRecord *newest_push(PushRecord::Kind kind, uint32_t &first_id, 
 	return &r;
 }
 
+/* A DAS path in the words of the C ABI: -2 the zero kernel, -1 none (no DAS stage runs: an empty part list), else the DasPath. */
+static int abi_path(int path) { return path == DasPath_Zero ? -2 : path; }
+static int abi_path(const std::vector<DasDecision> &parts) { return parts.empty() ? -1 : abi_path(main_part(parts).path); }
+
 /* beamformer_hip_get_last_burst_info */
 bool last_burst_info(BeamformerHipBurstInfo *out)
 {
@@ -1649,7 +1674,7 @@ bool last_burst_info(BeamformerHipBurstInfo *out)
 	const PushRecord *r = newest_push(PushRecord::Burst, out->first_frame_id, out->frame_count, out->stage_count, out->stage_kind, out->stage_ms, out->burst_ms);
 	if (!r) return false;
 	const BurstDecision &b = r->burst;
-	out->route.burst_kernel = b.burst_kernel; out->route.single_path = b.single_path == DasPath_Zero ? -2 : b.single_path;
+	out->route.burst_kernel = b.burst_kernel; out->route.single_path = abi_path(b.single_path);
 	out->route.frames_per_thread = b.frames_per_thread; out->route.das_launches = b.das_launches;
 	out->route.stage_launches = b.stage_launches; out->route.min_frames = b.min_frames;
 	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.reason.c_str());
@@ -1661,7 +1686,7 @@ void describe_readi_image_decision(const ReadiImageDecision &route, BeamformerHi
 {
 	std::memset(out, 0, sizeof(*out));
 	out->transmit_count = route.transmit_count;
-	out->das_path = route.path == DasPath_Zero ? -2 : route.path;
+	out->das_path = abi_path(route.path);
 	out->das_launches = route.das_launches; out->stage_launches = route.stage_launches; out->decode_launches = route.decode_launches;
 	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
 }
@@ -1693,11 +1718,7 @@ void describe_views_decision(const ViewsDecision &route, uint32_t view_count, Be
 {
 	std::memset(out, 0, sizeof(*out));
 	out->kernel_views = route.kernel_views; out->das_launches = route.das_launches; out->min_tiles = kViewsMinTiles;
-	for (uint32_t k = 0; k < view_count && k < BEAMFORMER_HIP_MAX_VIEWS; k++) {
-		if (route.parts[k].empty()) { out->path[k] = -1; continue; }
-		const int path = main_part(route.parts[k]).path;
-		out->path[k] = (int8_t)(path == DasPath_Zero ? -2 : path);
-	}
+	for (uint32_t k = 0; k < view_count && k < BEAMFORMER_HIP_MAX_VIEWS; k++) out->path[k] = (int8_t)abi_path(route.parts[k]);
 	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
 }
 
@@ -1707,24 +1728,25 @@ bool push_views(uint32_t block, const void *data, uint32_t size, const Beamforme
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
-	ParameterBlock &pb = c.blocks[block];
 	const uint32_t K = view_count;
-	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
-
-	RfLayout l;
-	if (!rf_layout(pb, l)) return false;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	PushGround g;
+	if (!begin_push(block, true, g)) return false;
 
 	const auto decide_begin = std::chrono::steady_clock::now();
 	ViewsDecision route;
-	decide_views(pb, ps->plan, ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, route);
+	decide_views(c.blocks[block], g.ps->plan, g.ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, route);
 	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
-	bool wants_counters = false;
-	for (uint32_t k = 0; k < K; k++) wants_counters |= !route.taken[k] && keeps_counters(route.parts[k]);
 
-	return push_frames(block, ps, l, data, data_on_device,
-	                   FramesPush{PushRecord::Views, 1, size, K, nullptr, views, nullptr, &route, wants_counters, d.scratch, 0, decide_us});
+	std::vector<DasJob> jobs(K);
+	for (uint32_t k = 0; k < K; k++) jobs[k] = view_job(views[k], route.parts[k], 0, route.taken[k] != 0);
+	Push m;
+	m.kind = PushRecord::Views; m.rf_frame_size = size; m.decide_us = decide_us;
+	m.jobs = jobs.data(); m.frames = K; m.das_ps = g.ps;
+	if (route.kernel_views) { m.fused.kind = FusedLaunch::Views; m.fused.views = &route; }
+	m.fails_on_flag = true;
+	if (!push_frames(block, g, data, data_on_device, m)) return false;
+	describe_views_decision(route, K, &d.multi.views);
+	return true;
 }
 
 /* beamformer_hip_get_last_views_info */
@@ -1744,42 +1766,40 @@ void describe_burst_views_decision(const BurstViewsDecision &route, uint32_t vie
 	out->rung = route.rung; out->kernel_views = route.kernel_views; out->frame_kernel_views = route.frame_kernel_views;
 	out->das_launches = route.das_launches; out->stage_launches = route.stage_launches;
 	out->frames_per_thread = route.frames_per_thread; out->min_frames = route.min_frames;
-	for (uint32_t k = 0; k < view_count && k < BEAMFORMER_HIP_MAX_VIEWS; k++) {
-		if (route.views.parts[k].empty()) { out->path[k] = -1; continue; }
-		const int path = main_part(route.views.parts[k]).path;
-		out->path[k] = (int8_t)(path == DasPath_Zero ? -2 : path);
-	}
+	for (uint32_t k = 0; k < view_count && k < BEAMFORMER_HIP_MAX_VIEWS; k++) out->path[k] = (int8_t)abi_path(route.views.parts[k]);
 	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
 }
 
 /* beamformer_hip_push_data_burst_views_with_compute: frame_count RF frames beamformed on view_count grids (no output shard),
- * frame_count x view_count frames view-major, each at its view's size.  The route: decide_burst_views -- ONE decide_das_parts per view,
- * not per frame.  One RF frame: the single push's buffers, as a views push. */
+ * frame_count x view_count frames view-major (frame v * N + k: view v, RF frame k), each at its view's size.  The route:
+ * decide_burst_views -- ONE decide_das_parts per view, not per frame --, a ladder: its fused launch (das_burst_views.hip), or per RF
+ * frame the views push's DAS step, or every frame its own launch(es). */
 bool push_burst_views(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count,
                       bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
-	ParameterBlock &pb = c.blocks[block];
 	const uint32_t N = frame_count, K = view_count;
-	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
-
-	RfLayout l;
-	if (!rf_layout(pb, l)) return false;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	PushGround g;
+	if (!begin_push(block, true, g)) return false;
 
 	const auto decide_begin = std::chrono::steady_clock::now();
 	BurstViewsDecision route;
-	decide_burst_views(pb, ps->plan, ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, N, route);
+	decide_burst_views(c.blocks[block], g.ps->plan, g.ps->transmit_table, view_grids(views, K).data(), K, c.das_path_mode, N, route);
 	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
-	bool wants_counters = false;
-	for (uint32_t k = 0; k < K; k++) wants_counters |= !route.views.taken[k] && keeps_counters(route.views.parts[k]);
 
-	FramesPush m{PushRecord::BurstViews, N, frame_size, N * K, nullptr, views, nullptr, &route.views, wants_counters,
-	             N > 1 ? d.burst_stage : d.scratch, N > 1 ? round_up(ps->plan.intermediate_bytes, 64) + 64 : 0, decide_us};
-	m.burst_views = &route;
-	return push_frames(block, ps, l, data, data_on_device, m);
+	/* (`fused` also names the jobs the views kernel covers per RF frame, rung 2) */
+	std::vector<DasJob> jobs((size_t)N * K);
+	for (uint32_t v = 0; v < K; v++)
+		for (uint32_t k = 0; k < N; k++) jobs[(size_t)v * N + k] = view_job(views[v], route.views.parts[v], k, route.views.taken[v] != 0);
+	Push m;
+	m.kind = PushRecord::BurstViews; m.rf_frames = N; m.rf_frame_size = frame_size; m.decide_us = decide_us;
+	m.jobs = jobs.data(); m.frames = N * K; m.das_ps = g.ps;
+	if (route.views.kernel_views) { m.fused.kind = route.rung == 1 ? FusedLaunch::BurstViews : FusedLaunch::ViewsPerRfFrame; m.fused.views = &route.views; }
+	m.fails_on_flag = true;
+	if (!push_frames(block, g, data, data_on_device, m)) return false;
+	describe_burst_views_decision(route, K, &d.multi.burst_views);
+	return true;
 }
 
 /* beamformer_hip_get_last_burst_views_info */
@@ -1803,9 +1823,7 @@ void describe_variants_decision(const VariantsDecision &route, uint32_t variant_
 	out->min_variants = kVariantsMinVariants;
 	for (uint32_t k = 0; k < variant_count && k < BEAMFORMER_HIP_MAX_VARIANTS; k++) {
 		out->taken[k] = route.taken[k];
-		if (route.parts[k].empty()) { out->path[k] = -1; continue; }
-		const int path = main_part(route.parts[k]).path;
-		out->path[k] = (int8_t)(path == DasPath_Zero ? -2 : path);
+		out->path[k] = (int8_t)abi_path(route.parts[k]);
 	}
 	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
 }
@@ -1813,22 +1831,19 @@ void describe_variants_decision(const VariantsDecision &route, uint32_t variant_
 static bool same_variant(const DasVariant &a, const DasVariant &b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
 
 /* beamformer_hip_push_data_variants_with_compute: ONE RF frame beamformed on the block's grid (no output shard) under variant_count
- * triples of speed of sound, time offset and f-number.  The block is read, never written: no dirty bit, no replan.  The route:
+ * triples of speed of sound, time offset and f-number: das_variants.hip for the variants decide_variants gives it, every other variant
+ * its own launch(es) under its derived decision.  The block is read, never written: no dirty bit, no replan.  The route:
  * decide_variants -- each variant's own single-frame decision under its derived block, kept in the block's derived plan states
  * (context.h: VariantPlanState) and reused by later pushes of the same triple, and which of them the variants kernel takes. */
 bool push_variants(uint32_t block, const void *data, uint32_t size, const DasVariant *variants, uint32_t variant_count, bool data_on_device)
 {
 	Context &c = g_context;
 	Device  &d = *c.cur;
-	ParameterBlock &pb = c.blocks[block];
+	const ParameterBlock &pb = c.blocks[block];
 	const uint32_t K = variant_count;
-	if (c.device_count > 1 || pb.shard_z_count) return set_error(BeamformerLibErrorKind_InvalidAccess);
-
-	RfLayout l;
-	if (!rf_layout(pb, l)) return false;
-	PlanState *ps = commit_block(block);
-	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-	const Plan &plan = ps->plan;
+	PushGround g;
+	if (!begin_push(block, true, g)) return false;
+	PlanState *ps = g.ps;
 
 	const auto decide_begin = std::chrono::steady_clock::now();
 	std::list<VariantPlanState> &kept = d.variant_plans[block];
@@ -1841,7 +1856,7 @@ bool push_variants(uint32_t block, const void *data, uint32_t size, const DasVar
 		for (const VariantPlanState &vp : kept)
 			if (current(vp, variants[k])) { known[k] = &vp.parts; break; }
 	VariantsDecision route;
-	decide_variants(pb, plan, ps->transmit_table, variants, K, c.das_path_mode, route, known.data());
+	decide_variants(pb, ps->plan, ps->transmit_table, variants, K, c.das_path_mode, route, known.data());
 	for (uint32_t k = 0; k < K; k++) {
 		if (known[k] || route.parts[k].empty()) continue;
 		bool listed = false;                         /* (the same triple twice in one push) */
@@ -1849,13 +1864,17 @@ bool push_variants(uint32_t block, const void *data, uint32_t size, const DasVar
 		if (!listed) kept.push_back(VariantPlanState{variants[k], route.parts[k], ps->generation, hooks().version, c.das_path_mode});
 	}
 	const float decide_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - decide_begin).count();
-	bool wants_counters = false;
-	for (uint32_t k = 0; k < K; k++) wants_counters |= !route.taken[k] && !route.parts[k].empty() && keeps_counters(route.parts[k]);
 
-	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], plan.output_points[2]};
-	FramesPush m{PushRecord::Variants, 1, size, K, points, nullptr, nullptr, nullptr, wants_counters, d.scratch, 0, decide_us};
-	m.variants = &route;
-	return push_frames(block, ps, l, data, data_on_device, m);
+	std::vector<DasJob> jobs(K);
+	for (uint32_t k = 0; k < K; k++) jobs[k] = grid_job(g, route.parts[k].empty() ? nullptr : &route.parts[k], 0, route.taken[k] != 0);
+	Push m;
+	m.kind = PushRecord::Variants; m.rf_frame_size = size; m.decide_us = decide_us;
+	m.jobs = jobs.data(); m.frames = K; m.das_ps = ps;
+	if (route.kernel_variants) { m.fused.kind = FusedLaunch::Variants; m.fused.variants = &route; }
+	m.fails_on_flag = true;
+	if (!push_frames(block, g, data, data_on_device, m)) return false;
+	describe_variants_decision(route, K, &d.multi.variants);
+	return true;
 }
 
 /* beamformer_hip_get_last_variants_info */

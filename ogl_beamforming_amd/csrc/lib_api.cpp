@@ -133,6 +133,29 @@ bool run_fits_the_ring(const ParameterBlock &pb, const BeamformerHipView *views,
 	return check(frame_run_bytes(points, views, count, plan.iq_pipeline ? 8u : 4u, frame_ring_bytes(), total, per_view), BeamformerLibErrorKind_FrameSizeOverflow);
 }
 
+/* the RF frames of a burst, a sweep, an image, a burst views push: a count the ABI's tables hold */
+static_assert(BEAMFORMER_HIP_MAX_BURST_FRAMES <= BeamformerMaxBacklogFrames, "every frame of a burst keeps its frame record");
+bool valid_burst_count(uint32_t frame_count)
+{
+	return check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES, BeamformerLibErrorKind_BufferOverflow);
+}
+
+/* The last checks of every multi-frame push (`what`), after those of its own arguments: one device; `whole_grid` (a push of views or
+ * variants; `item`: one of them) no output shard on the block; the RF frame; `count` frames in the ring, of the block's grid or --
+ * `views` given -- frame k of views[k / per_view]'s; a device.  Everything that needs no device is judged before the device is touched,
+ * so that a malformed push is refused the same way on a machine without one. */
+bool multi_push_ready(const char *what, const char *item, uint32_t slot, const void *data, uint32_t frame_size, const BeamformerHipView *views, uint32_t count,
+                      uint32_t per_view = 1)
+{
+	const ParameterBlock &pb = ctx().blocks[slot];
+	if (!on_one_device(what)) return false;
+	if (item && pb.shard_z_count) {
+		std::fprintf(stderr, "[beamformer] a %s is not sharded: refused with the output shard set on parameter block %u\n", item, slot);
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	return valid_rf_frame(pb, data, frame_size) && run_fits_the_ring(pb, views, count, per_view) && ensure_device();
+}
+
 bool push_data_common(const void *data, uint32_t data_size, uint32_t image_plane_tag, uint32_t slot, bool on_device)
 {
 	Context &c = ctx();
@@ -143,21 +166,16 @@ bool push_data_common(const void *data, uint32_t data_size, uint32_t image_plane
 	return push_rf_and_compute(slot, data, data_size, on_device);
 }
 
-/* A burst: the single push's checks per frame (one geometry: once), then what must hold for the burst as a whole.  Everything that needs
- * no device is judged before the device is touched, so that a malformed burst is refused the same way on a machine without one. */
+/* A burst: the single push's checks per frame (one geometry: once), then what must hold for the burst as a whole. */
 bool push_burst_common(const void *data, uint32_t frame_size, uint32_t frame_count, uint32_t image_plane_tag, uint32_t slot, bool on_device)
 {
 	Context &c = ctx();
 	if (frame_count == 1) return push_data_common(data, frame_size, image_plane_tag, slot, on_device);
-	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES && frame_count <= BeamformerMaxBacklogFrames,
-	           BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!valid_burst_count(frame_count)) return false;
 	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
 	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
-	if (!on_one_device("burst")) return false;
-	if (!valid_rf_frame(c.blocks[slot], data, frame_size)) return false;
-	if (!run_fits_the_ring(c.blocks[slot], nullptr, frame_count)) return false;
-	if (!ensure_device()) return false;
-	return push_burst(slot, data, frame_size, frame_count, on_device);
+	if (!multi_push_ready("burst", nullptr, slot, data, frame_size, nullptr, frame_count)) return false;
+	return push_burst(slot, data, frame_size, frame_count, nullptr, on_device);
 }
 
 /* A READI sweep's block and group list, no device needed: the block beamforms READI (FORCES / UFORCES with readi_group_count > 1), else
@@ -167,8 +185,7 @@ bool push_burst_common(const void *data, uint32_t frame_size, uint32_t frame_cou
 bool resolve_readi_groups(uint32_t slot, const uint32_t *groups, uint32_t frame_count, std::vector<uint32_t> &out)
 {
 	Context &c = ctx();
-	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES && frame_count <= BeamformerMaxBacklogFrames,
-	           BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!valid_burst_count(frame_count)) return false;
 	if (!check(slot < c.reserved_parameter_blocks, BeamformerLibErrorKind_ParameterBlockUnallocated)) return false;
 	const BeamformerParameters &bp = c.blocks[slot].parameters;
 	const bool forces = bp.acquisition_kind == BeamformerAcquisitionKind_FORCES || bp.acquisition_kind == BeamformerAcquisitionKind_UFORCES;
@@ -190,17 +207,12 @@ bool resolve_readi_groups(uint32_t slot, const uint32_t *groups, uint32_t frame_
 bool push_readi_sweep_common(const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, uint32_t image_plane_tag, uint32_t slot,
                              bool on_device)
 {
-	Context &c = ctx();
-	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES && frame_count <= BeamformerMaxBacklogFrames,
-	           BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!valid_burst_count(frame_count)) return false;
 	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
 	std::vector<uint32_t> ids;
 	if (!resolve_readi_groups(slot, groups, frame_count, ids)) return false;
-	if (!on_one_device("READI sweep")) return false;
-	if (!valid_rf_frame(c.blocks[slot], data, frame_size)) return false;
-	if (!run_fits_the_ring(c.blocks[slot], nullptr, frame_count)) return false;
-	if (!ensure_device()) return false;
-	return push_readi_sweep(slot, data, frame_size, frame_count, ids.data(), on_device);
+	if (!multi_push_ready("READI sweep", nullptr, slot, data, frame_size, nullptr, frame_count)) return false;
+	return push_burst(slot, data, frame_size, frame_count, ids.data(), on_device);
 }
 
 /* A READI image push's block, list and count, no device needed: the sweep's checks (resolve_readi_groups), then what the derived block
@@ -230,17 +242,13 @@ bool resolve_readi_image(uint32_t slot, const uint32_t *groups, uint32_t frame_c
 bool push_readi_image_common(const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, uint32_t image_plane_tag, uint32_t slot,
                              bool on_device)
 {
-	Context &c = ctx();
-	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!valid_burst_count(frame_count)) return false;
 	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
 	std::vector<uint32_t> ids;
 	ParameterBlock derived;
 	Plan derived_plan;
 	if (!resolve_readi_image(slot, groups, frame_count, ids, derived, derived_plan)) return false;
-	if (!on_one_device("READI image push")) return false;
-	if (!valid_rf_frame(c.blocks[slot], data, frame_size)) return false;
-	if (!run_fits_the_ring(c.blocks[slot], nullptr, 1)) return false;
-	if (!ensure_device()) return false;
+	if (!multi_push_ready("READI image push", nullptr, slot, data, frame_size, nullptr, 1)) return false;
 	return push_readi_image(slot, data, frame_size, frame_count, ids.data(), on_device);
 }
 
@@ -261,21 +269,11 @@ bool validate_views(const BeamformerHipView *views, uint32_t view_count, uint32_
 
 static_assert(BEAMFORMER_HIP_MAX_VIEWS <= BeamformerMaxBacklogFrames, "every view of a push keeps its frame record");
 
-/* A views push: the single push's checks of the RF (once), then what must hold for the views.  Everything that needs no device is judged
- * before the device is touched, so that a malformed push is refused the same way on a machine without one. */
+/* A views push: what must hold for the views, then the single push's checks of the RF (once). */
 bool push_views_common(const void *data, uint32_t data_size, const BeamformerHipView *views, uint32_t view_count, uint32_t slot, bool on_device)
 {
-	Context &c = ctx();
 	if (!validate_views(views, view_count, slot)) return false;
-	const ParameterBlock &pb = c.blocks[slot];
-	if (!on_one_device("views push")) return false;
-	if (pb.shard_z_count) {
-		std::fprintf(stderr, "[beamformer] a view is not sharded: refused with the output shard set on parameter block %u\n", slot);
-		return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
-	if (!valid_rf_frame(pb, data, data_size)) return false;
-	if (!run_fits_the_ring(pb, views, view_count)) return false;
-	if (!ensure_device()) return false;
+	if (!multi_push_ready("views push", "view", slot, data, data_size, views, view_count)) return false;
 	return push_views(slot, data, data_size, views, view_count, on_device);
 }
 
@@ -283,7 +281,7 @@ bool push_views_common(const void *data, uint32_t data_size, const BeamformerHip
  * then the views push's checks of the list. */
 bool validate_burst_views(uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count, uint32_t slot)
 {
-	if (!check(frame_count != 0 && frame_count <= BEAMFORMER_HIP_MAX_BURST_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!valid_burst_count(frame_count)) return false;
 	if (!check(view_count != 0 && view_count <= BEAMFORMER_HIP_MAX_VIEWS, BeamformerLibErrorKind_BufferOverflow)) return false;
 	if (!check((uint64_t)frame_count * view_count <= BeamformerMaxBacklogFrames, BeamformerLibErrorKind_BufferOverflow)) return false;
 	return validate_views(views, view_count, slot);
@@ -294,17 +292,8 @@ bool validate_burst_views(uint32_t frame_count, const BeamformerHipView *views, 
 bool push_burst_views_common(const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count, uint32_t slot,
                              bool on_device)
 {
-	Context &c = ctx();
 	if (!validate_burst_views(frame_count, views, view_count, slot)) return false;
-	const ParameterBlock &pb = c.blocks[slot];
-	if (!on_one_device("burst views push")) return false;
-	if (pb.shard_z_count) {
-		std::fprintf(stderr, "[beamformer] a view is not sharded: refused with the output shard set on parameter block %u\n", slot);
-		return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
-	if (!valid_rf_frame(pb, data, frame_size)) return false;
-	if (!run_fits_the_ring(pb, views, frame_count * view_count, frame_count)) return false;
-	if (!ensure_device()) return false;
+	if (!multi_push_ready("burst views push", "view", slot, data, frame_size, views, frame_count * view_count, frame_count)) return false;
 	return push_burst_views(slot, data, frame_size, frame_count, views, view_count, on_device);
 }
 
@@ -334,24 +323,14 @@ std::vector<DasVariant> das_variants(const BeamformerHipDasVariant *variants, ui
 	return out;
 }
 
-/* A variants push: the list's checks, the single push's checks of the RF (once), then what must hold for the run of frames.  Everything
- * that needs no device is judged before the device is touched, so that a malformed push is refused the same way on a machine without one. */
+/* A variants push: the list's checks, the single push's checks of the RF (once), then what must hold for the run of frames. */
 bool push_variants_common(const void *data, uint32_t data_size, const BeamformerHipDasVariant *variants, uint32_t variant_count, uint32_t image_plane_tag,
                           uint32_t slot, bool on_device)
 {
-	Context &c = ctx();
 	if (!check(variant_count != 0 && variant_count <= BEAMFORMER_HIP_MAX_VARIANTS, BeamformerLibErrorKind_BufferOverflow)) return false;
 	if (!check(image_plane_tag < BeamformerViewPlaneTag_Count, BeamformerLibErrorKind_InvalidImagePlane)) return false;
 	if (!validate_variants(variants, variant_count, slot)) return false;
-	const ParameterBlock &pb = c.blocks[slot];
-	if (!on_one_device("variants push")) return false;
-	if (pb.shard_z_count) {
-		std::fprintf(stderr, "[beamformer] a variant is not sharded: refused with the output shard set on parameter block %u\n", slot);
-		return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
-	if (!valid_rf_frame(pb, data, data_size)) return false;
-	if (!run_fits_the_ring(pb, nullptr, variant_count)) return false;
-	if (!ensure_device()) return false;
+	if (!multi_push_ready("variants push", "variant", slot, data, data_size, nullptr, variant_count)) return false;
 	return push_variants(slot, data, data_size, das_variants(variants, variant_count).data(), variant_count, on_device);
 }
 

@@ -7,6 +7,7 @@ Run from the repository root on a GPU box:
 import argparse
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -47,13 +48,62 @@ def real_row(env):
     return {"figure": float(v["das_ms_median"]), "das_path": v["das_path"]}
 
 
+FIGURE_KEYS = ("_us", "_us_per_frame", "_us_per_push", "_ms")
+
+
+def tool_rows(command):
+    """every row a rate tool prints (tools/*_rate.py: one JSON object a row), as one figure per timing of the row -- its keys that end
+    in _us, _us_per_frame, _us_per_push or _ms, spreads left out --, named by the row's first four plain fields (the case and its counts)"""
+    def run(env):
+        out = subprocess.run([sys.executable] + command, env=env, capture_output=True, text=True, check=True, timeout=900).stdout
+        figures = {}
+        for line in out.splitlines():
+            if not line.startswith("{"):
+                continue
+            row = json.loads(line)
+            timings = {k: float(v) for k, v in row.items() if k.endswith(FIGURE_KEYS) and "spread" not in k and isinstance(v, (int, float))}
+            plain = [f"{k}={v}" for k, v in row.items() if k not in timings and isinstance(v, (str, int)) and not isinstance(v, bool)][:4]
+            for k, v in timings.items():
+                figures[" ".join(plain + [k])] = v
+        assert figures, out[-2000:]
+        return {"figures": figures, "das_path": "-"}
+    return run
+
+
+def hostpush_rows(env):
+    """tools/hostpush.py: frame time and enqueue time of configs 1-4, device and host pushes"""
+    out = subprocess.run([sys.executable, "tools/hostpush.py"], env=env, capture_output=True, text=True, check=True, timeout=900).stdout
+    figures = {}
+    for cfg, mode, frame, enqueue in re.findall(r"cfg(\d) (\w+)\s+rf .*? frame\s+([\d.]+) us\s+enqueue\s+([\d.]+) us/frame", out):
+        figures[f"cfg{cfg} {mode} frame_us"] = float(frame)
+        figures[f"cfg{cfg} {mode} enqueue_us"] = float(enqueue)
+    assert len(figures) == 16, out[-2000:]
+    return {"figures": figures, "das_path": "-"}
+
+
 ROWS = {
     "headline": ("bench.py config 4 (channel-paired staged kernel: identical code, the noise reference), ms per step", bench_row([])),
     "gather": ("bench.py config 4 --das-path 2 (gather kernel), ms per step", bench_row(["--das-path", "2"])),
     "cubic": ("bench.py config 4 --interpolation cubic (staged cubic kernel), ms per step", bench_row(["--interpolation", "cubic"])),
     "uniform": ("tools/staged_uniform.py --scales 0.5, 32 planes: unpaired complex kernel, uniform tables, DAS ms (tables in LDS beside it)", uniform_rows),
     "real": ("tools/staged_real_rate.py: real-sample staged kernel on config 4's geometry without Demodulate, median DAS ms of 5 pushes", real_row),
+    # host time per push: the single push and every multi-frame push, each rate tool at the smallest and largest count of its profile
+    "hostpush": ("tools/hostpush.py, us", hostpush_rows),
+    "burst_rate": ("tools/burst_rate.py --frames 2,256", tool_rows(["tools/burst_rate.py", "--frames", "2,256"])),
+    "views_rate": ("tools/views_rate.py --views 1,256", tool_rows(["tools/views_rate.py", "--views", "1,256"])),
+    "readi_rate": ("tools/readi_rate.py --groups 4 --extra-frames 5 (4 to 64 frames)", tool_rows(["tools/readi_rate.py", "--groups", "4", "--extra-frames", "5"])),
+    "readi_image_rate": ("tools/readi_image_rate.py --groups 4,16", tool_rows(["tools/readi_image_rate.py", "--groups", "4,16"])),
+    "burst_views_rate": ("tools/burst_views_rate.py --frames 2,256", tool_rows(["tools/burst_views_rate.py", "--frames", "2,256"])),
+    "variants_rate": ("tools/variants_rate.py --counts 1,64", tool_rows(["tools/variants_rate.py", "--counts", "1,64"])),
 }
+
+
+def write_result(path, result):
+    """the result as JSON, one row a line (a rate tool's rows are some fifty figures each)"""
+    head = {k: v for k, v in result.items() if k != "rows"}
+    rows = ",\n".join(f" {json.dumps(name)}: {json.dumps(row)}" for name, row in result["rows"].items())
+    with open(path, "w") as f:
+        f.write(json.dumps(head, indent=1)[:-2] + ',\n "rows": {\n' + rows + "\n }\n}\n")
 
 
 def side(runs, key="figure"):
@@ -78,19 +128,23 @@ if __name__ == "__main__":
             for label, library in (("parent", args.parent), ("this", args.library)):
                 env = dict(os.environ, OGL_BEAMFORMER_LIB=os.path.abspath(library), PYTHONPATH=os.getcwd())
                 sides[label].append(run(env))
-        row = {"what": what, "parent": side(sides["parent"]), "this": side(sides["this"]),
-               "das_path": sorted({str(r["das_path"]) for r in sides["parent"] + sides["this"]})}
-        if name == "uniform":
-            row["tables_in_lds"] = {"parent": side(sides["parent"], "tables_in_lds_ms"), "this": side(sides["this"], "tables_in_lds_ms")}
-            t = row["tables_in_lds"]
-            t["difference"] = t["this"]["median"] - t["parent"]["median"]
-            t["slower"] = t["difference"] > 3.0 * t["parent"]["spread"]
-        row["difference"] = row["this"]["median"] - row["parent"]["median"]
-        row["bar"] = 3.0 * row["parent"]["spread"]
-        row["slower"] = row["difference"] > row["bar"]
-        result["rows"][name] = row
-        print(json.dumps({name: row}), flush=True)
+        # a row of several figures is one row per figure
+        figures = sorted(sides["parent"][0].get("figures", {}))
+        for label in sides:
+            sides[label] = [dict(r, **r.get("figures", {})) for r in sides[label]]
+        for figure in figures or ["figure"]:
+            key = name + ": " + figure if figures else name
+            row = {"what": what, "parent": side(sides["parent"], figure), "this": side(sides["this"], figure),
+                   "das_path": sorted({str(r["das_path"]) for r in sides["parent"] + sides["this"]})}
+            if name == "uniform":
+                row["tables_in_lds"] = {"parent": side(sides["parent"], "tables_in_lds_ms"), "this": side(sides["this"], "tables_in_lds_ms")}
+                t = row["tables_in_lds"]
+                t["difference"] = t["this"]["median"] - t["parent"]["median"]
+                t["slower"] = t["difference"] > 3.0 * t["parent"]["spread"]
+            row["difference"] = row["this"]["median"] - row["parent"]["median"]
+            row["bar"] = 3.0 * row["parent"]["spread"]
+            row["slower"] = row["difference"] > row["bar"]
+            result["rows"][key] = row
+            print(json.dumps({key: {k: row[k] for k in ("parent", "this", "difference", "bar", "slower")}}), flush=True)
         if args.json:
-            with open(args.json, "w") as f:
-                json.dump(result, f, indent=1)
-                f.write("\n")
+            write_result(args.json, result)

@@ -1,5 +1,6 @@
 """What the push entry points produce, without a single time in it: for a fixed list of small cases (tests/cases.py) pushed as single
-frames, as device-resident frames, as bursts and as views pushes, the SHA-256 of every exported frame with its id, and beside them the
+frames, as device-resident frames, as bursts, as views pushes and -- on every route each has -- as READI sweeps, READI images, burst
+views pushes and variants pushes, the SHA-256 of every exported frame with its id, and beside them the
 bookkeeping a client can read back -- das_path, das_row_end_planes and the stage kinds of beamformer_hip_get_last_frame_timings, a
 burst's route and stage kinds from beamformer_hip_get_last_burst_info, a views push's from beamformer_hip_get_last_views_info, das_pairs
 where pair counting is on (of the newest frame's row: the C ABI reads no other row's), which of the two info calls is served after each
@@ -287,6 +288,192 @@ try:
 finally:
     L.beamformer_hip_enable_pair_counting(0)
     L.beamformer_hip_set_das_path(0)
+
+
+# ---- the other multi-frame pushes: a READI sweep, a READI image, a burst views push, a variants push -- each on every route it has,
+# from host and from device-resident RF, with pair counting on and under the SCRATCH_POISON hook
+from tests import readi_image_cases as R                                  # noqa: E402
+from tests import variants_cases as vc                                    # noqa: E402
+from tests.test_gpu_burst_views import four_views                         # noqa: E402
+from tests.test_gpu_readi_sweep import GROUPS5, groups_for, sweep_case    # noqa: E402
+
+NO_BURST = P.HIP_DAS_PATH_NO_BURST_KERNEL
+
+
+def compact(value):
+    """the same record with every leaf collection on one line: a dict or list of plain values becomes one string (k=v pairs by key, or
+    the values in order), bottom-up -- a frame is "id=... sha256=...", a route one line; a list of records stays a list.  The sections
+    below record some hundred pushes: written out a value a line they would be most of the file."""
+    plain = lambda x: x is None or isinstance(x, (str, int, float, bool))
+    if isinstance(value, dict):
+        inner = {k: compact(v) for k, v in value.items()}
+        return " ".join(f"{k}={inner[k]}" for k in sorted(inner)) if all(plain(v) for v in inner.values()) else inner
+    if isinstance(value, list):
+        return " ".join(str(v) for v in value) if all(plain(v) for v in value) else [compact(v) for v in value]
+    return value
+
+
+def route_of(route, names, counted=()):
+    """the named fields of an info call's route; `counted`: (array field, entries) pairs"""
+    out = {name: int(getattr(route, name)) for name in names}
+    out.update({name: [int(v) for v in getattr(route, name)[:n]] for name, n in counted})
+    out["reason"] = route.reason.decode()
+    return out
+
+
+def pushed(frames, first_id, info, route, pairs):
+    """what every push records: its frames' ids and digests, its route and stage kinds as its info call reports them, the newest row"""
+    return {"frames": [{"id": int(first_id) + k, "sha256": sha(f)} for k, f in enumerate(frames)], "route": route,
+            "stage_kinds": [int(info.stage_kind[i]) for i in range(int(info.stage_count))], "last_row": row(pairs)}
+
+
+def on_device(rf):
+    """(the tensor that keeps the copy alive, its pointer)"""
+    dev = torch.from_numpy(np.ascontiguousarray(rf).view(np.uint8).reshape(-1)).cuda()
+    torch.cuda.synchronize()
+    return dev, dev.data_ptr()
+
+
+def sweep_push(acq, rf, groups, device=False, pairs=False):
+    dev, pointer = on_device(rf) if device else (None, None)
+    frames = lib.beamform_readi_sweep(acq.bp, rf, groups, acq.filters, on_device_pointer=pointer)
+    info = lib.last_burst_info()
+    assert int(info.frame_count) == len(rf)
+    return pushed(frames, info.first_frame_id, info, route_of(info.route, ["burst_kernel", "single_path", "frames_per_thread", "das_launches", "stage_launches", "min_frames"]), pairs)
+
+
+def image_push(acq, rf, groups, device=False, pairs=False):
+    dev, pointer = on_device(rf) if device else (None, None)
+    frame = lib.beamform_readi_image(acq.bp, rf, groups, acq.filters, on_device_pointer=pointer)
+    info = lib.last_readi_image_info()
+    assert int(info.rf_frame_count) == len(rf)
+    return pushed([frame], info.frame_id, info, route_of(info.route, ["transmit_count", "das_path", "das_launches", "stage_launches", "decode_launches"]), pairs)
+
+
+def burst_views_push(acq, rf, views, device=False, pairs=False):
+    dev, pointer = on_device(rf) if device else (None, None)
+    frames = lib.beamform_burst_views(acq.bp, rf, views, acq.filters, on_device_pointer=pointer)
+    info = lib.last_burst_views_info()
+    assert (int(info.frame_count), int(info.view_count)) == (len(rf), len(views))
+    route = route_of(info.route, ["rung", "kernel_views", "frame_kernel_views", "das_launches", "stage_launches", "frames_per_thread", "min_frames"], [("path", len(views))])
+    return pushed([f for view in frames for f in view], info.first_frame_id, info, route, pairs)
+
+
+def variants_push(acq, rf, variants, device=False, pairs=False):
+    dev, pointer = on_device(rf) if device else (None, None)
+    frames = lib.beamform_variants(acq.bp, rf, variants, acq.filters, on_device_pointer=pointer)
+    info = lib.last_variants_info()
+    K = len(variants)
+    assert int(info.variant_count) == K
+    route = route_of(info.route, ["kernel_variants", "fused_launches", "das_launches", "kernel_tiles", "min_tiles", "min_variants"], [("taken", K), ("path", K)])
+    return pushed(list(frames), info.first_frame_id, info, route, pairs)
+
+
+def every_way(acq, mode, push):
+    """push(device=, pairs=) on a fresh library under das path `mode`: from host, from device-resident RF, with pair counting on and
+    under SCRATCH_POISON"""
+    fresh(acq)
+    L.beamformer_hip_set_das_path(mode)
+    out = {"host": push(), "device": push(device=True)}
+    L.beamformer_hip_enable_pair_counting(1)
+    try:
+        out["pair_counting"] = push(pairs=True)
+    finally:
+        L.beamformer_hip_enable_pair_counting(0)
+    lib.set_hook("SCRATCH_POISON", "1")
+    try:
+        out["scratch_poison"] = push()
+    finally:
+        lib.set_hook("SCRATCH_POISON", None)
+        L.beamformer_hip_set_das_path(0)
+    return out
+
+
+def served_all():
+    """which of the five info calls the newest push serves, and the error of those it refuses"""
+    out = {}
+    for name, fn, struct in (("burst_info", L.beamformer_hip_get_last_burst_info, P.HipBurstInfo), ("views_info", L.beamformer_hip_get_last_views_info, P.HipViewsInfo),
+                             ("readi_image_info", L.beamformer_hip_get_last_readi_image_info, P.HipReadiImageInfo),
+                             ("burst_views_info", L.beamformer_hip_get_last_burst_views_info, P.HipBurstViewsInfo),
+                             ("variants_info", L.beamformer_hip_get_last_variants_info, P.HipVariantsInfo)):
+        info = struct()
+        out[name] = "served" if fn(C.byref(info)) else lib.last_error()[0].name
+    return out
+
+
+try:
+    # a READI sweep: on its kernel (5 frames and more), on the per-frame route (flag 0x400), and of one frame
+    sweep_acq = sweep_case("g4a4", P.InterpolationMode.Linear, True, False)
+    sweep_rf = noise_frames(sweep_acq, 5, 800)
+    groups5 = groups_for(sweep_acq, GROUPS5)
+    result["readi_sweep"] = {"kernel": every_way(sweep_acq, 0, lambda **how: sweep_push(sweep_acq, sweep_rf, groups5, **how)),
+                             "per_frame": every_way(sweep_acq, NO_BURST, lambda **how: sweep_push(sweep_acq, sweep_rf, groups5, **how)),
+                             "one_frame": every_way(sweep_acq, 0, lambda **how: sweep_push(sweep_acq, sweep_rf[:1], groups5[:1], **how))}
+
+    # a READI image: every group once (a permutation), and one RF frame
+    image_acq = R.image_case("g4a4", P.InterpolationMode.Linear, "iq")
+    image_rf = noise_frames(image_acq, 4, 810)
+    permutation = R.PERMUTATIONS["g4a4"]
+    result["readi_image"] = {"four_frames": every_way(image_acq, 0, lambda **how: image_push(image_acq, image_rf, permutation, **how)),
+                             "one_frame": every_way(image_acq, 0, lambda **how: image_push(image_acq, image_rf[:1], permutation[:1], **how))}
+
+    # a burst views push: the ladder's three rungs (automatic at 5 RF frames, 0x400, 0x800) and one RF frame
+    bv_acq = cases.make("config1_small")
+    bv_rf = noise_frames(bv_acq, 5, 820)
+    bv_views = four_views(bv_acq)
+    result["burst_views"] = {name: every_way(bv_acq, mode, lambda **how: burst_views_push(bv_acq, bv_rf, bv_views, **how))
+                             for name, mode in (("rung1", 0), ("rung2_0x400", NO_BURST), ("rung3_0x800", NO_KERNEL))}
+    result["burst_views"]["one_frame"] = every_way(bv_acq, 0, lambda **how: burst_views_push(bv_acq, bv_rf[:1], bv_views, **how))
+
+    # a variants push: every variant fused (flag 0x8000, and eight candidates on the automatic route), none fused (flag 0x4000, and
+    # three candidates below both thresholds), and a block whose variants run different single-frame kernels, each its own launch(es).
+    # (No block of the test suites gives a route with some variants fused and others not: beamformer_hip_describe_variants, scanned.)
+    v_acq = vc.block("linear", True, True)
+    three_variants = vc.candidates(v_acq.bp)
+    eight_variants = three_variants + [lib.variant_of(v_acq.bp, speed_of_sound=1400.0 + 40.0 * k) for k in range(5)]
+    result["variants"] = {name: every_way(v_acq, mode, lambda **how: variants_push(v_acq, v_acq.rf, chosen, **how))
+                          for name, mode, chosen in (("prefer_kernel", vc.PREFER, three_variants), ("no_kernel", vc.NO_KERNEL, three_variants),
+                                                     ("automatic_eight", 0, eight_variants), ("automatic_three", 0, three_variants))}
+    staged_acq = cases.make("rca_staged_auto")
+    staged_variants = vc.candidates(staged_acq.bp) + [lib.variant_of(staged_acq.bp, speed_of_sound=3000.0)]
+    result["variants"]["own_kernels"] = every_way(staged_acq, 0, lambda **how: variants_push(staged_acq, staged_acq.rf, staged_variants, **how))
+
+    # a variants push that fails at its DAS stage (flag 0x2000), in both routes: failure, a tombstone under every id, the next pushes
+    array = (P.HipDasVariant * 3)(*three_variants)
+    v_rf = np.ascontiguousarray(v_acq.rf)
+    result["variants_failed"] = {}
+    for name, mode in (("prefer_kernel", vc.PREFER), ("no_kernel", vc.NO_KERNEL)):
+        fresh(v_acq)
+        L.beamformer_hip_set_das_path(mode)
+        before = single(v_acq, v_rf)
+        L.beamformer_hip_set_das_path(mode | FAIL_DAS)
+        ok = bool(L.beamformer_hip_push_data_variants_with_compute(v_rf.ctypes.data_as(C.c_void_p), v_rf.nbytes, array, 3, 0, 0))
+        entry = {"before": before, "push": "served" if ok else lib.last_error()[0].name, "info": served_all(), "last_frames": {}}
+        sentinel = np.full(1 << 16, -7.0, np.float32)
+        for count in (1, 2, 3):
+            ok = bool(L.beamformer_get_last_frames(sentinel.ctypes.data_as(C.c_void_p), sentinel.nbytes, count))
+            entry["last_frames"][str(count)] = {"served": ok, "error": lib.last_error()[0].name, "buffer_untouched": bool((sentinel == -7.0).all())}
+        entry["frame_info_served"] = bool(L.beamformer_hip_get_last_frame_info(C.byref(P.HipFrameInfo())))
+        entry["frame_timings_served"] = bool(L.beamformer_hip_get_last_frame_timings(C.byref(P.HipFrameTimings())))
+        L.beamformer_hip_set_das_path(mode)
+        entry["single_after"] = single(v_acq, v_rf)
+        entry["variants_after"] = variants_push(v_acq, v_rf, three_variants)
+        result["variants_failed"][name] = entry
+
+    # one sequence over all push kinds: which of the five info calls each push leaves served
+    L.beamformer_hip_set_das_path(0)
+    steps = [("single", lambda: (fresh(bv_acq), single(bv_acq, bv_rf[0]))[1]), ("views", lambda: views_push(bv_rf[1], bv_views[:3])),
+             ("burst", lambda: burst(bv_acq, bv_rf)), ("burst_views", lambda: burst_views_push(bv_acq, bv_rf, bv_views)),
+             ("variants", lambda: variants_push(v_acq, v_acq.rf, eight_variants)), ("readi_sweep", lambda: sweep_push(sweep_acq, sweep_rf, groups5)),
+             ("readi_image", lambda: image_push(image_acq, image_rf, permutation)), ("single", lambda: single(image_acq, image_rf[0])),
+             ("variants", lambda: variants_push(v_acq, v_acq.rf, three_variants)), ("views", lambda: (fresh(bv_acq), views_push(bv_rf[1], bv_views[:3]))[1])]
+    result["all_push_kinds"] = [{"push": name, "result": step(), "info": served_all()} for name, step in steps]
+finally:
+    L.beamformer_hip_enable_pair_counting(0)
+    lib.set_hook("SCRATCH_POISON", None)
+    L.beamformer_hip_set_das_path(0)
+for section in ("readi_sweep", "readi_image", "burst_views", "variants", "variants_failed", "all_push_kinds"):
+    result[section] = compact(result[section])
 
 
 # ---- the row-column DAS family (das_staged*.hip, das_separable.hip): every named case the gather or a staged kernel takes, under
