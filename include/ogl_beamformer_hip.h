@@ -534,6 +534,74 @@ typedef enum {
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_rank_frames(const BeamformerHipFrameMetrics *metrics, uint32_t count, uint32_t criterion,
                                                           double *scores, uint32_t *best_index);
 
+/* ---- frame peaks: the local maxima of the `count` newest frames, found ON THE DEVICE (ULM: a burst push beamforms an ensemble on a
+ * coarse grid; its peaks say where the 16 x 16-voxel patches of the burst views push that refines it go -- coarse ensemble -> peaks ->
+ * patches -> refined ensemble without a frame leaving the device) ----
+ * DEFINITION (tests/frame_peaks_ref.py restates it in numpy).  Every decision is taken on ONE float32 a voxel, the decision value q:
+ * re * re + im * im for Float32Complex frames, every operation rounded to float32 on its own (no fused multiply-add), fabsf(v) for
+ * Float32 frames.  No square root takes part in a decision, so numpy reproduces every one by basic IEEE operations.  A voxel is finite
+ * when q is.  It is ELIGIBLE when it is finite and q >= t: t is `threshold` for real frames and the float32 product
+ * threshold * threshold for complex ones -- the threshold is on the magnitude, in the frame's own units.  A voxel at flat frame index
+ * i (x fastest) is a PEAK when it is eligible, lies inside the box, and for every voxel n of its 3 x 3 x 3 neighbourhood whose q_n is
+ * finite: q > q_n when n's flat index is below i, q >= q_n when it is above.  The neighbourhood is clipped to the FRAME, not to the box:
+ * a voxel on a face of the box is judged by its real neighbours, so tiling a frame into boxes neither invents nor doubles a peak.
+ * Neighbours outside the frame and non-finite ones (the NaN coherency weighting leaves) do not count.  Under the tie rule no two
+ * adjacent voxels are both peaks; of a plateau, the voxel of the lowest flat index is one (an all-zero frame at threshold 0: one peak,
+ * at 0, 0, 0).
+ * A record's magnitude is the frame metrics' magnitude of the voxel (sqrtf(q) for complex frames, q for real ones).  Axis a is FITTED
+ * when both neighbours at -1 and +1 along it lie in the frame and are finite and den = (m_minus + m_plus) - (m0 + m0) is negative; then
+ * offset[a] = 0.5f * (m_minus - m_plus) / den clamped to [-0.5, 0.5] -- the vertex of the parabola through the three magnitudes, in
+ * voxels, float32 arithmetic in this operation order without contraction.  Axes that are not fitted carry 0.
+ * A frame's list is in ascending flat frame index and depends on that frame, the box and the threshold only: not on count, not on the
+ * other frames of the call, not on the call being repeated (the device uses no atomics: a peak's place is a function of its index). */
+#define BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME 65536u
+typedef struct {
+	uint32_t index[3];                        /* x, y, z IN THE FRAME */
+	float    magnitude;
+	float    offset[3];                       /* sub-voxel offset per axis, in voxels, within [-0.5, 0.5]; 0 where not fitted */
+	uint32_t fitted;                          /* bit a: axis a was fitted */
+} BeamformerHipFramePeak;                     /* 32 bytes, no padding */
+typedef struct {
+	uint32_t frame_id, parameter_block, data_kind, image_plane_tag;   /* from the frame's record */
+	uint32_t points[3];                       /* the frame's own grid */
+	uint32_t region_first[3], region_count[3];/* the box that was searched (the whole frame when region == NULL) */
+	float    threshold;                       /* the threshold used for this frame */
+	uint32_t first;                           /* index into `peaks` of this frame's first record */
+	uint32_t stored;                          /* min(found, max_per_frame) */
+	uint64_t found;                           /* every peak of the box, stored or not */
+	uint64_t above_threshold;                 /* eligible voxels of the box */
+} BeamformerHipFramePeaks;                    /* 80 bytes, no padding */
+/* frames[count], oldest first; the frames may differ in grid and in data kind.  thresholds: threshold_count == 1: one for all frames;
+ * else threshold_count == count, oldest first; each finite and >= 0.  `peaks` has room for count * max_per_frame records and comes back
+ * PACKED: frame n's `stored` records start at frames[n].first, the frames follow one another, *peak_count is their total.  When
+ * found > stored the records kept are the first in flat order: raise the threshold or the cap.  The call runs on the library's current
+ * stream behind the frames it reads: the rows go up, a mark pass and a scan run (csrc/frame_peaks.hip), the per-frame counts come back
+ * (first synchronise), the list buffer is grown to the total stored, the emit pass runs (skipped when the total is 0) and exactly the
+ * stored records come back (second synchronise).  device_ms, when not NULL: the time between events around the launches, both parts
+ * added.
+ * Refusals, all decided before anything is launched and leaving every output unwritten: count == 0 or > BEAMFORMER_HIP_MAX_SCORED_FRAMES,
+ * max_per_frame == 0 or > BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME: BufferOverflow; InvalidAccess: a NULL pointer other than region and
+ * device_ms; threshold_count neither 1 nor count; a threshold that is negative or not finite; and everything
+ * beamformer_hip_score_last_frames refuses -- no device in use yet, fewer than count frames queued, a tombstone, an overwritten record,
+ * reused storage, a region that does not fit inside every frame, several devices. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                     const float *thresholds, uint32_t threshold_count, uint32_t max_per_frame,
+                                                                     BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks,
+                                                                     uint32_t *peak_count, float *device_ms);
+/* Host only: touches no device and no library state but the last error.  out[peak_count]: for every peak, the view of a views or
+ * burst views push that is a patch of patch_points voxels spanning patch_extent_voxels SOURCE voxels around it.  source_voxel_transform
+ * and source_points are those of the grid the peaks were found on.  The kernels map voxel i of an axis to i / max(1, points - 1) and
+ * then through the transform M; per axis a, with P = source_points[a]: the normalised centre is c = (index + offset) / max(1, P - 1)
+ * (offset dropped when use_offsets == 0) and the span s = extent / max(1, P - 1).  The patch's transform has the translation
+ * M (c - s/2, 1) and column a of M times s where patch_points[a] > 1; where patch_points[a] == 1 -- its only index is 0 -- column a
+ * of M unchanged (the matrix stays regular) and c in the place of c - s/2: patch voxel j of axis a lands on the source's fractional voxel
+ * index + offset - extent/2 + j * extent / (patch_points[a] - 1).  InvalidAccess: a NULL argument, a zero patch_points entry, an extent
+ * that is negative or not finite.  peak_count == 0 writes nothing and succeeds. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_peaks_to_views(const float source_voxel_transform[16], const uint32_t source_points[3],
+                                                             const BeamformerHipFramePeak *peaks, uint32_t peak_count,
+                                                             const uint32_t patch_points[3], const float patch_extent_voxels[3],
+                                                             uint32_t use_offsets, uint32_t image_plane_tag, BeamformerHipView *out);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

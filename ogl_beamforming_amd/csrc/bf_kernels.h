@@ -378,6 +378,22 @@ typedef struct {                 /* a frame's box */
 	uint32_t reserved;
 } BfMetricsResult;
 
+/* ---- frame peaks (frame_peaks.hip: beamformer_hip_find_peaks_last_frames) ---- */
+#define BF_PEAKS_MAX_BLOCKS 0x7FFFFFFFu      /* grid x: a frame's blocks are ceil(waves / 4), uncapped (512^3: about 5 x 10^5) */
+typedef struct {
+	uint64_t offset;             /* of the frame in the frame ring, bytes */
+	uint64_t wave_first;         /* its first 64-bit peak mask: one a wave */
+	uint64_t block_first;        /* its first block count and block offset */
+	uint32_t points[3], cplx;    /* the frame's grid; 1: Float32Complex, 0: Float32 */
+	uint32_t first[3], count[3]; /* the box, inside the grid, every count >= 1 */
+	uint32_t waves_per_row;      /* ceil(count[0] / 64): a wave owns 64 consecutive x of one box row */
+	uint32_t waves, blocks;      /* waves_per_row * count[1] * count[2], in flat box order; ceil(waves / 4) */
+	float    threshold;          /* on the decision value: the caller's threshold (real frames), its float32 square (complex ones) */
+	uint32_t cap;                /* records kept: the first `cap` in flat order */
+	uint32_t reserved;
+} BfPeaksRow;
+typedef struct { uint64_t found, above_threshold; } BfPeaksResult;   /* a frame's box */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -420,6 +436,15 @@ hipError_t bf_launch_min_max(const void *frame, uint64_t voxels, int complex_dat
  * inside its frame (the caller checks: the kernels index with what the rows say) */
 hipError_t bf_launch_frame_metrics(const void *ring, const BfMetricsRow *rows, uint32_t frame_count, uint32_t max_blocks,
                                    BfMetricsPartial *partials, BfMetricsResult *results, hipStream_t s);
+/* frame_peaks.hip: three launches, no atomics.  _mark: the mark pass (grid x max_blocks, the most blocks any row asks for; grid y the
+ * frame) and the scan, one block a frame; _emit: the mark pass's grid again, storing 32-byte records (BeamformerHipFramePeak's layout) at
+ * list[firsts[frame] + rank].  The host reads `results` between the two to size `list` and to fill `firsts`.  All tables are device
+ * memory; every row's box lies inside its frame (the caller checks: the kernels index with what the rows say) */
+hipError_t bf_launch_frame_peaks_mark(const void *ring, const BfPeaksRow *rows, uint32_t frame_count, uint32_t max_blocks,
+                                      uint64_t *masks, uint32_t *counts, uint32_t *offsets, BfPeaksResult *results, hipStream_t s);
+hipError_t bf_launch_frame_peaks_emit(const void *ring, const BfPeaksRow *rows, uint32_t frame_count, uint32_t max_blocks,
+                                      const uint64_t *masks, const uint32_t *counts, const uint32_t *offsets, const uint32_t *firsts,
+                                      void *list, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

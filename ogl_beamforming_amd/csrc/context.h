@@ -171,6 +171,8 @@ struct Device {
 	void        *metrics_pinned = nullptr;                     /* ... the pinned memory the rows are sent from and the results land in (free again when the call returns: it ends in a synchronise) */
 	size_t       metrics_pinned_size = 0;
 	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
+	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
+	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
 	DeviceBuffer burst_stage[2];                               /* a burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
 	PushRecord   multi;
 	DeviceBuffer readi_decoded;                                /* a READI image push: the DAS input decoded across its acquisitions (readi_decode.hip), 64 spare bytes behind it */
@@ -274,6 +276,9 @@ bool copy_das_input_frame(uint32_t frame, void *out, uint64_t out_size);
 bool sum_last_frames(uint32_t count, void *out, uint64_t out_size);
 bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float *out, uint64_t out_floats);
 bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms);
+bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                            uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
+                            float *device_ms);                     /* arguments checked by the caller (lib_api.cpp) */
 const FrameRecord *record_of(const Device &d, uint32_t frame_id);   /* null: no such frame, a tombstone, or storage that a newer frame reused */
 bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
 bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);

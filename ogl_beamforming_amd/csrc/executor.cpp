@@ -184,6 +184,10 @@ static void release_one_device(Device &d)
 	for (auto &ip : d.image_plans) { ip.ps.transmits.release(); ip.ps.sparse.release(); ip.ps.valid = false; ip.ps.das_parts.clear(); }
 	d.readi_decoded.release(); d.das_decoded_bytes = 0;
 	d.metrics_scratch.release();
+	d.peaks_list.release();
+	if (d.peaks_begin) (void)hipEventDestroy(d.peaks_begin);
+	if (d.peaks_end)   (void)hipEventDestroy(d.peaks_end);
+	d.peaks_begin = d.peaks_end = nullptr;
 	if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
 	if (d.metrics_begin) (void)hipEventDestroy(d.metrics_begin);
 	if (d.metrics_end)   (void)hipEventDestroy(d.metrics_end);
@@ -2299,42 +2303,88 @@ bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float 
 	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
 }
 
-/* beamformer_hip_score_last_frames: focus metrics of the `count` newest frames, reduced where they lie (frame_metrics.hip).  The records
- * are judged the way export_last_frames and sum_last_frames judge theirs -- but ANY frame missing refuses the call: a row per frame is
- * promised.  Everything that can refuse is decided before anything is enqueued. */
-bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms)
+namespace {
+
+/* one of the `count` newest frames as score_last_frames and find_peaks_last_frames take it: its record, and the box inside it */
+struct BoxedFrame {
+	const FrameRecord *record;
+	uint32_t first[3], count[3], cplx;
+	uint64_t volume;                 /* voxels of the box */
+};
+
+/* The `count` newest frames of the one device, oldest first, each with the box of `region` (NULL: the frame whole).  The records are
+ * judged the way export_last_frames and sum_last_frames judge theirs -- but ANY frame missing refuses: something per frame is promised.
+ * False, with InvalidAccess set: no device or several, fewer frames queued, a tombstone, an overwritten record, reused storage, a box
+ * that does not fit inside every frame, a frame that does not lie inside the ring. */
+bool newest_boxed_frames(uint32_t count, const BeamformerHipFrameRegion *region, std::vector<BoxedFrame> &out)
 {
 	Context &c = g_context;
-	/* several devices: a frame is a set of z-slabs there, and the z gradient would cross them */
+	/* several devices: a frame is a set of z-slabs there, and a z neighbour would lie across them */
 	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	Device &d = c.devices[0];
 	if (count > d.frame_counter || count > d.frames.size()) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	if (region) for (int k = 0; k < 3; k++) if (!region->count[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-
-	const size_t rows_bytes = round_up(sizeof(BfMetricsRow) * count, 64), results_bytes = round_up(sizeof(BfMetricsResult) * count, 64);
-	std::vector<BfMetricsRow> rows(count);
-	uint32_t partials = 0, max_blocks = 0;
+	out.resize(count);
 	const uint64_t first_id = d.frame_counter - count;
 	for (uint32_t n = 0; n < count; n++) {
 		const FrameRecord &f = d.frames[(first_id + n) % d.frames.size()];
 		if (f.id != (uint32_t)(first_id + n) || f.failed || !f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
-		BfMetricsRow &r = rows[n];
-		r = BfMetricsRow{};
-		r.offset = f.offset;
-		r.cplx = f.data_kind == BeamformerDataKind_Float32Complex;
-		uint64_t volume = 1;
+		BoxedFrame &b = out[n];
+		b.record = &f;
+		b.cplx = f.data_kind == BeamformerDataKind_Float32Complex;
+		b.volume = 1;
 		for (int k = 0; k < 3; k++) {
-			r.points[k] = f.points[k];
-			r.first[k] = region ? region->first[k] : 0u;
-			r.count[k] = region ? region->count[k] : f.points[k];
+			b.first[k] = region ? region->first[k] : 0u;
+			b.count[k] = region ? region->count[k] : f.points[k];
 			/* the box inside the frame (a frame of no voxels -- a pipeline without DAS on a peer -- holds no box) */
-			if (!r.count[k] || (uint64_t)r.first[k] + r.count[k] > f.points[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-			volume *= r.count[k];       /* (at most the frame's voxels, which fit its record's 64-bit byte count) */
+			if (!b.count[k] || (uint64_t)b.first[k] + b.count[k] > f.points[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
+			b.volume *= b.count[k];     /* (at most the frame's voxels, which fit its record's 64-bit byte count) */
 		}
 		/* and the frame inside the ring: what the kernels index with is what the record says */
 		if (f.offset > d.ring.size || f.bytes > d.ring.size - f.offset ||
-		    (uint64_t)f.points[0] * f.points[1] * f.points[2] * (r.cplx ? 8u : 4u) > f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
-		r.blocks = bf_metrics_blocks(volume);
+		    (uint64_t)f.points[0] * f.points[1] * f.points[2] * (b.cplx ? 8u : 4u) > f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	}
+	return true;
+}
+
+/* the pinned memory, the device scratch and the first event pair that score_last_frames and find_peaks_last_frames share: both calls
+ * end in a synchronise, so all of it is free again when either returns */
+bool ensure_metrics_memory(Device &d, size_t pinned_bytes, size_t device_bytes)
+{
+	bool ok = true;
+	if (d.metrics_pinned_size < pinned_bytes) {
+		if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
+		d.metrics_pinned = nullptr; d.metrics_pinned_size = 0;
+		ok = HIP_OK(hipHostMalloc(&d.metrics_pinned, pinned_bytes, hipHostMallocDefault));
+		if (ok) d.metrics_pinned_size = pinned_bytes; else d.metrics_pinned = nullptr;
+	}
+	ok = ok && d.metrics_scratch.ensure(device_bytes);
+	if (ok && !d.metrics_begin) ok = HIP_OK(hipEventCreate(&d.metrics_begin));
+	if (ok && !d.metrics_end)   ok = HIP_OK(hipEventCreate(&d.metrics_end));
+	return ok;
+}
+
+} // namespace
+
+/* beamformer_hip_score_last_frames: focus metrics of the `count` newest frames, reduced where they lie (frame_metrics.hip).  Everything
+ * that can refuse is decided before anything is enqueued. */
+bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms)
+{
+	std::vector<BoxedFrame> boxed;
+	if (!newest_boxed_frames(count, region, boxed)) return false;
+	Device &d = g_context.devices[0];
+
+	const size_t rows_bytes = round_up(sizeof(BfMetricsRow) * count, 64), results_bytes = round_up(sizeof(BfMetricsResult) * count, 64);
+	std::vector<BfMetricsRow> rows(count);
+	uint32_t partials = 0, max_blocks = 0;
+	for (uint32_t n = 0; n < count; n++) {
+		const BoxedFrame &b = boxed[n];
+		BfMetricsRow &r = rows[n];
+		r = BfMetricsRow{};
+		r.offset = b.record->offset;
+		r.cplx = b.cplx;
+		for (int k = 0; k < 3; k++) { r.points[k] = b.record->points[k]; r.first[k] = b.first[k]; r.count[k] = b.count[k]; }
+		r.blocks = bf_metrics_blocks(b.volume);
 		r.partial_first = partials;
 		const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
 		r.step[0] = (uint32_t)(stride % r.count[0]);
@@ -2346,15 +2396,7 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 
 	bool ok = HIP_OK(hipSetDevice(d.device));
 	const size_t partials_bytes = sizeof(BfMetricsPartial) * partials, pinned_bytes = rows_bytes + results_bytes;
-	if (ok && d.metrics_pinned_size < pinned_bytes) {
-		if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
-		d.metrics_pinned = nullptr; d.metrics_pinned_size = 0;
-		ok = HIP_OK(hipHostMalloc(&d.metrics_pinned, pinned_bytes, hipHostMallocDefault));
-		if (ok) d.metrics_pinned_size = pinned_bytes; else d.metrics_pinned = nullptr;
-	}
-	ok = ok && d.metrics_scratch.ensure(rows_bytes + results_bytes + partials_bytes);
-	if (ok && !d.metrics_begin) ok = HIP_OK(hipEventCreate(&d.metrics_begin));
-	if (ok && !d.metrics_end)   ok = HIP_OK(hipEventCreate(&d.metrics_end));
+	ok = ok && ensure_metrics_memory(d, pinned_bytes, rows_bytes + results_bytes + partials_bytes);
 	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
 
 	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
@@ -2378,7 +2420,7 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 	}
 
 	for (uint32_t n = 0; n < count; n++) {
-		const FrameRecord &f = d.frames[(first_id + n) % d.frames.size()];
+		const FrameRecord &f = *boxed[n].record;
 		const BfMetricsRow &r = rows[n];
 		const BfMetricsResult &v = results[n];
 		BeamformerHipFrameMetrics &m = out[n];
@@ -2396,6 +2438,111 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 		m.sum_abs = v.s1; m.sum_abs2 = v.s2; m.sum_abs4 = v.s4;
 		m.max_abs = v.max_abs;
 	}
+	return true;
+}
+
+/* beamformer_hip_find_peaks_last_frames: the local maxima of the `count` newest frames, found where they lie (frame_peaks.hip).  The
+ * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Two synchronises:
+ * the list buffer is sized by what the scan found. */
+bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                            uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
+                            float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipFramePeak) == 32 && sizeof(BeamformerHipFramePeaks) == 80, "records without padding");
+	std::vector<BoxedFrame> boxed;
+	if (!newest_boxed_frames(count, region, boxed)) return false;
+	Device &d = g_context.devices[0];
+
+	std::vector<BfPeaksRow> rows(count);
+	uint64_t waves = 0, blocks = 0;
+	uint32_t max_blocks = 0;
+	for (uint32_t n = 0; n < count; n++) {
+		const BoxedFrame &b = boxed[n];
+		BfPeaksRow &r = rows[n];
+		r = BfPeaksRow{};
+		r.offset = b.record->offset;
+		r.cplx = b.cplx;
+		for (int k = 0; k < 3; k++) { r.points[k] = b.record->points[k]; r.first[k] = b.first[k]; r.count[k] = b.count[k]; }
+		const uint64_t per_row = ((uint64_t)r.count[0] + 63u) / 64u, frame_waves = per_row * r.count[1] * r.count[2];
+		/* (a frame of the ring has far fewer voxels than this: a bound that keeps the kernels' 32-bit wave numbers honest) */
+		if (frame_waves > 4ull * BF_PEAKS_MAX_BLOCKS - 3u) return set_error(BeamformerLibErrorKind_InvalidAccess);
+		r.waves_per_row = (uint32_t)per_row;
+		r.waves = (uint32_t)frame_waves;
+		r.blocks = (uint32_t)((frame_waves + 3u) / 4u);
+		r.wave_first = waves; r.block_first = blocks;
+		const float t = thresholds[threshold_count == 1 ? 0 : n];
+		r.threshold = b.cplx ? t * t : t;
+		r.cap = max_per_frame;
+		waves += r.waves; blocks += r.blocks;
+		if (r.blocks > max_blocks) max_blocks = r.blocks;
+	}
+
+	/* device: rows | results | firsts | masks | counts | offsets; pinned: rows | results | firsts */
+	const size_t rows_bytes = round_up(sizeof(BfPeaksRow) * count, 64), results_bytes = round_up(sizeof(BfPeaksResult) * count, 64),
+	             firsts_bytes = round_up(sizeof(uint32_t) * count, 64), masks_bytes = round_up(sizeof(uint64_t) * waves, 64),
+	             counts_bytes = round_up(sizeof(uint32_t) * blocks, 64);
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && ensure_metrics_memory(d, rows_bytes + results_bytes + firsts_bytes, rows_bytes + results_bytes + firsts_bytes + masks_bytes + 2 * counts_bytes);
+	if (ok && !d.peaks_begin) ok = HIP_OK(hipEventCreate(&d.peaks_begin));
+	if (ok && !d.peaks_end)   ok = HIP_OK(hipEventCreate(&d.peaks_end));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
+	const BfPeaksRow *device_rows    = (const BfPeaksRow *)device;
+	BfPeaksResult    *device_results = (BfPeaksResult *)(device + rows_bytes);
+	uint32_t         *device_firsts  = (uint32_t *)(device + rows_bytes + results_bytes);
+	uint64_t         *device_masks   = (uint64_t *)(device + rows_bytes + results_bytes + firsts_bytes);
+	uint32_t         *device_counts  = (uint32_t *)((char *)device_masks + masks_bytes);
+	uint32_t         *device_offsets = (uint32_t *)((char *)device_counts + counts_bytes);
+	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + rows_bytes);
+	uint32_t            *firsts  = (uint32_t *)(pinned + rows_bytes + results_bytes);
+	std::memcpy(pinned, rows.data(), sizeof(BfPeaksRow) * count);
+	hipStream_t s = d.stream;
+	ok &= HIP_OK(hipMemcpyAsync(device, pinned, sizeof(BfPeaksRow) * count, hipMemcpyHostToDevice, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
+	if (ok) ok &= HIP_OK(bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, max_blocks, device_masks, device_counts, device_offsets, device_results, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
+	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + rows_bytes, device_results, sizeof(BfPeaksResult) * count, hipMemcpyDeviceToHost, s));
+	/* the first synchronise runs whatever failed above: it is what frees the pinned memory */
+	ok &= HIP_OK(hipStreamSynchronize(s));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	uint32_t total = 0;                  /* (at most 1024 frames x 65536 records) */
+	std::vector<uint32_t> stored(count);
+	for (uint32_t n = 0; n < count; n++) {
+		stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
+		firsts[n] = total;
+		total += stored[n];
+	}
+	float ms = 0, emit_ms = 0;
+	const bool timed = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end));
+	if (total) {
+		ok = d.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak));
+		if (ok) {
+			ok &= HIP_OK(hipMemcpyAsync(device_firsts, firsts, sizeof(uint32_t) * count, hipMemcpyHostToDevice, s));
+			ok &= HIP_OK(hipEventRecord(d.peaks_begin, s));
+			if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, max_blocks, device_masks, device_counts, device_offsets,
+			                                                device_firsts, d.peaks_list.ptr, s));
+			ok &= HIP_OK(hipEventRecord(d.peaks_end, s));
+			if (ok) ok &= HIP_OK(hipMemcpyAsync(peaks, d.peaks_list.ptr, (size_t)total * sizeof(BeamformerHipFramePeak), hipMemcpyDeviceToHost, s));
+			ok &= HIP_OK(hipStreamSynchronize(s));
+		}
+		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+		if (!HIP_OK(hipEventElapsedTime(&emit_ms, d.peaks_begin, d.peaks_end))) emit_ms = 0;
+	}
+	if (device_ms) *device_ms = timed ? ms + emit_ms : 0.0f;
+
+	for (uint32_t n = 0; n < count; n++) {
+		const FrameRecord &f = *boxed[n].record;
+		BeamformerHipFramePeaks &m = frames[n];
+		std::memset(&m, 0, sizeof(m));
+		m.frame_id = f.id; m.parameter_block = f.block; m.data_kind = (uint32_t)f.data_kind; m.image_plane_tag = f.tag;
+		for (int k = 0; k < 3; k++) { m.points[k] = f.points[k]; m.region_first[k] = rows[n].first[k]; m.region_count[k] = rows[n].count[k]; }
+		m.threshold = thresholds[threshold_count == 1 ? 0 : n];
+		m.first = firsts[n]; m.stored = stored[n];
+		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
+	}
+	*peak_count = total;
 	return true;
 }
 

@@ -968,6 +968,49 @@ uint32_t beamformer_hip_score_last_frames(uint32_t count, const BeamformerHipFra
 	return score_last_frames(count, region, out, device_ms);
 }
 
+uint32_t beamformer_hip_find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                                               uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks,
+                                               uint32_t *peak_count, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(thresholds != nullptr && frames != nullptr && peaks != nullptr && peak_count != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (uint32_t k = 0; k < threshold_count; k++)
+		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return find_peaks_last_frames(count, region, thresholds, threshold_count, max_per_frame, frames, peaks, peak_count, device_ms);
+}
+
+/* host only: one view a peak, a patch around it (include/ogl_beamformer_hip.h has the algebra) */
+uint32_t beamformer_hip_peaks_to_views(const float source_voxel_transform[16], const uint32_t source_points[3], const BeamformerHipFramePeak *peaks,
+                                       uint32_t peak_count, const uint32_t patch_points[3], const float patch_extent_voxels[3], uint32_t use_offsets,
+                                       uint32_t image_plane_tag, BeamformerHipView *out)
+{
+	if (!check(source_voxel_transform && source_points && peaks && patch_points && patch_extent_voxels && out, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (int a = 0; a < 3; a++)
+		if (!check(patch_points[a] != 0 && std::isfinite(patch_extent_voxels[a]) && patch_extent_voxels[a] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	const float *m = source_voxel_transform;          /* column major: m[4 * column + row] */
+	for (uint32_t n = 0; n < peak_count; n++) {
+		const BeamformerHipFramePeak &p = peaks[n];
+		BeamformerHipView &v = out[n];
+		double origin[3], scale[3];
+		for (int a = 0; a < 3; a++) {
+			const double last = source_points[a] > 1 ? (double)source_points[a] - 1.0 : 1.0;
+			const double c = ((double)p.index[a] + (use_offsets ? (double)p.offset[a] : 0.0)) / last, s = (double)patch_extent_voxels[a] / last;
+			const bool spans = patch_points[a] > 1;
+			origin[a] = spans ? c - 0.5 * s : c;
+			scale[a]  = spans ? s : 1.0;
+		}
+		for (int row = 0; row < 4; row++) {
+			for (int a = 0; a < 3; a++) v.das_voxel_transform[4 * a + row] = (float)((double)m[4 * a + row] * scale[a]);
+			v.das_voxel_transform[12 + row] = (float)((double)m[row] * origin[0] + (double)m[4 + row] * origin[1] + (double)m[8 + row] * origin[2] + (double)m[12 + row]);
+		}
+		for (int a = 0; a < 3; a++) v.output_points[a] = patch_points[a];
+		v.image_plane_tag = image_plane_tag;
+	}
+	return 1;
+}
+
 uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

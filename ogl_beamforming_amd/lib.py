@@ -130,6 +130,10 @@ def _load():
         "beamformer_hip_copy_frame": (u32, [u32, vp, u64]),
         "beamformer_hip_get_frame_info": (u32, [u32, C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_rank_frames": (u32, [C.POINTER(P.HipFrameMetrics), u32, u32, C.POINTER(C.c_double), C.POINTER(u32)]),
+        "beamformer_hip_find_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, u32, C.POINTER(P.HipFramePeaks),
+                                                        C.POINTER(P.HipFramePeak), C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_peaks_to_views": (u32, [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(P.HipFramePeak), u32, C.POINTER(u32),
+                                                C.POINTER(C.c_float), u32, u32, C.POINTER(P.HipView)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -516,6 +520,37 @@ def rank_frames(rows, criterion):
     best = C.c_uint32(0)
     _check(library().beamformer_hip_rank_frames(array, len(rows), int(criterion), scores.ctypes.data_as(C.POINTER(C.c_double)), C.byref(best)))
     return scores[:len(rows)], int(best.value)
+
+
+def find_peaks_last_frames(count, thresholds, max_per_frame, region=None):
+    """beamformer_hip_find_peaks_last_frames: the local maxima of the `count` newest frames, found on the device.  thresholds: one number
+    for all frames, or `count` of them, oldest first (on the magnitude, in the frame's units); region None: every frame whole.  Returns
+    (frames, peaks, device_ms): a ctypes array of `count` HipFramePeaks rows, a ctypes array of the packed HipFramePeak records (frame
+    n's are peaks[frames[n].first : frames[n].first + frames[n].stored]) and the device time of the launches."""
+    count, max_per_frame = int(count), int(max_per_frame)
+    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
+    levels = (C.c_float * max(1, len(values)))(*values)
+    rows = (P.HipFramePeaks * max(1, count))()
+    room = count * max_per_frame if 0 < count <= P.HIP_MAX_SCORED_FRAMES and 0 < max_per_frame <= P.HIP_MAX_PEAKS_PER_FRAME else 0
+    records = np.zeros(max(1, room), np.dtype(P.HipFramePeak))
+    total, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_find_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values), max_per_frame,
+                                                           rows, records.ctypes.data_as(C.POINTER(P.HipFramePeak)), C.byref(total), C.byref(ms)))
+    peaks = (P.HipFramePeak * int(total.value)).from_buffer_copy(records[: int(total.value)].tobytes())
+    return rows, peaks, float(ms.value)
+
+
+def peaks_to_views(source_transform, source_points, peaks, patch_points, patch_extent_voxels, use_offsets=True, tag=0):
+    """beamformer_hip_peaks_to_views (host only): one HipView a peak -- a patch of patch_points voxels spanning patch_extent_voxels voxels
+    of the source grid (its das_voxel_transform and points) around the peak, at its sub-voxel offsets when use_offsets.  A list."""
+    peaks = list(peaks)
+    array = (P.HipFramePeak * max(1, len(peaks)))(*peaks)
+    out = (P.HipView * max(1, len(peaks)))()
+    _check(library().beamformer_hip_peaks_to_views((C.c_float * 16)(*[float(v) for v in source_transform]),
+                                                   (C.c_uint32 * 3)(*[int(v) for v in source_points]), array, len(peaks),
+                                                   (C.c_uint32 * 3)(*[int(v) for v in patch_points]),
+                                                   (C.c_float * 3)(*[float(v) for v in patch_extent_voxels]), 1 if use_offsets else 0, int(tag), out))
+    return list(out[: len(peaks)])
 
 
 def frame_info(frame_id):

@@ -313,6 +313,21 @@ class HipFrameMetrics(C.Structure):
                 ("max_abs", C.c_float), ("reserved", C.c_uint32)]
 
 
+HIP_MAX_PEAKS_PER_FRAME = 65536
+
+
+class HipFramePeak(C.Structure):
+    """BeamformerHipFramePeak: one local maximum of beamformer_hip_find_peaks_last_frames (32 bytes, no padding)"""
+    _fields_ = [("index", C.c_uint32 * 3), ("magnitude", C.c_float), ("offset", C.c_float * 3), ("fitted", C.c_uint32)]
+
+
+class HipFramePeaks(C.Structure):
+    """BeamformerHipFramePeaks: one frame's row of beamformer_hip_find_peaks_last_frames (80 bytes, no padding)"""
+    _fields_ = [("frame_id", C.c_uint32), ("parameter_block", C.c_uint32), ("data_kind", C.c_uint32), ("image_plane_tag", C.c_uint32),
+                ("points", C.c_uint32 * 3), ("region_first", C.c_uint32 * 3), ("region_count", C.c_uint32 * 3),
+                ("threshold", C.c_float), ("first", C.c_uint32), ("stored", C.c_uint32), ("found", C.c_uint64), ("above_threshold", C.c_uint64)]
+
+
 class FrameScore(enum.IntEnum):
     """BeamformerHipFrameScore: the criteria of beamformer_hip_rank_frames"""
     Energy = 0
