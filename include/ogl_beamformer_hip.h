@@ -602,6 +602,77 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_peaks_to_views(const float source_
                                                              const uint32_t patch_points[3], const float patch_extent_voxels[3],
                                                              uint32_t use_offsets, uint32_t image_plane_tag, BeamformerHipView *out);
 
+/* ---- ensemble filter: a linear slow-time operator on the frames of the frame ring (the clutter filter between "ensemble" and "peaks"
+ * of the ULM loop: tissue lies 30 - 60 dB above the microbubbles, so the peaks of an unfiltered ensemble are tissue speckle).  Two
+ * device primitives and one host helper: the K x K slow-time Gram matrix of the K newest frames, reduced where they lie; a projector
+ * made from it on the host; and a mix that writes M linear combinations of the K frames back INTO THE RING as ordinary frames, so that
+ * beamformer_hip_find_peaks_last_frames, beamformer_hip_score_last_frames, beamformer_hip_copy_frame, beamformer_hip_get_frame_info and
+ * beamformer_get_last_frames work on them unchanged.  The weights are the caller's: SVD clutter filtering (the projector below),
+ * polynomial-regression and FIR wall filters, weighted compounding and frame differencing are all one mix ----
+ * DEFINITIONS (tests/ensemble_ref.py restates them in numpy).
+ * GRAM.  The K frames have one grid and one data kind.  G[j][k] = sum over v of conj(f_j[v]) * f_k[v], over the voxels v of the box
+ * that are finite in EVERY one of the K frames (a voxel is finite when both its floats are); a voxel that is not finite in some frame
+ * counts in non_finite and in no entry, so G stays a Gram matrix: Hermitian, positive semidefinite.  Each float is widened to double;
+ * the real part of a term is rj * rk + ij * ik and the imaginary part rj * ik - ij * rk -- the products are exact in double, each part
+ * is one double addition --; the voxel sum is a double sum in an order the box and K alone fix (no atomics): the bytes of `gram` depend
+ * on the K frames and the box only and repeat bit for bit.  Only j <= k is computed; G[k][j] is stored as the exact conjugate of G[j][k];
+ * the imaginary part of a diagonal entry is exactly 0, and real frames give imaginary parts of exactly 0 everywhere.  Index 0 is the
+ * oldest frame, the order of beamformer_get_last_frames.
+ * MIX.  The K frames, of one grid and one kind, give out_count new frames of that grid and kind.  Frames and weights are interleaved
+ * floats.  For output j and voxel v each of the two output floats is ONE float32 fmaf chain from +0 in ascending k --
+ *     real:       acc = fmaf(Wre[j][k], re_k, acc), then acc = fmaf(-Wim[j][k], im_k, acc)
+ *     imaginary:  acc = fmaf(Wim[j][k], re_k, acc), then acc = fmaf( Wre[j][k], im_k, acc)
+ * -- no weight is skipped for being zero, so a voxel that is not finite in some frame is not finite in every output (plain IEEE).  Real
+ * frames use the real parts only: acc = fmaf(Wre[j][k], f_k, acc). */
+#define BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES 256u
+typedef struct {
+	uint32_t count;                           /* K */
+	uint32_t data_kind;                       /* of the frames */
+	uint32_t points[3];                       /* the frames' common grid */
+	uint32_t region_first[3], region_count[3];/* the box that was reduced (the whole frame when region == NULL) */
+	uint32_t first_frame_id;                  /* the frames have ids first_frame_id .. first_frame_id + K - 1 */
+	uint64_t voxels;                          /* voxels of the box finite in ALL K frames: what every entry sums over */
+	uint64_t non_finite;                      /* voxels of the box not finite in at least one frame */
+} BeamformerHipEnsembleInfo;                  /* 64 bytes, no padding */
+/* gram[count][count][2] doubles (re, im), row j column k as above.  Three launches (csrc/ensemble.hip: the all-finite mask, the
+ * partial pass, the fold) are enqueued on the library's current stream behind the frames they read; the matrix and the counts come
+ * back through one device-to-host copy and one stream synchronise.  info may be NULL.  device_ms, when not NULL: the time between two
+ * events around the launches.
+ * Refusals, all decided before anything is enqueued and leaving every output unwritten: count == 0 or
+ * > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES: BufferOverflow; gram == NULL: InvalidAccess; frames that differ in grid or in data kind:
+ * DataSizeMismatch; and everything beamformer_hip_score_last_frames refuses (InvalidAccess) -- no device in use yet, fewer than count
+ * frames queued, a tombstone, an overwritten record, reused storage, a region that does not fit inside the frames, several devices --
+ * and a box of 2^32 voxels or more. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                               double *gram, BeamformerHipEnsembleInfo *info, float *device_ms);
+/* Host only: touches no device and no library state but the last error.  A cyclic Jacobi eigendecomposition, in double, of the
+ * Hermitian matrix whose UPPER triangle gram[count][count][2] holds (the imaginary parts of the diagonal are not read).  With the
+ * eigenpairs (lambda_i, u_i) in descending order of lambda, weights = sum over i from remove_high to count - remove_low - 1 of
+ * u_i u_i^H, rounded once to float32: the projector that removes the remove_high strongest slow-time components (tissue) and the
+ * remove_low weakest (noise).  It does not depend on the phases of the u_i; within a cluster of equal eigenvalues it is defined only
+ * when the cut does not split the cluster.  remove_high + remove_low == count gives zeros, 0 and 0 the identity up to rounding.
+ * weights[count][count][2] floats; eigenvalues[count], descending, may be NULL.  InvalidAccess: gram or weights NULL, remove_high +
+ * remove_low > count, an entry of the upper triangle that is not finite; count == 0 or > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES:
+ * BufferOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_clutter_projector(const double *gram, uint32_t count, uint32_t remove_high, uint32_t remove_low,
+                                                                float *weights, double *eigenvalues);
+/* weights[out_count][count][2] floats; index 0 of the second dimension is the oldest source frame.  The out_count outputs are placed
+ * in the frame ring as ONE contiguous run by the rule every push follows (a run that would straddle the end starts again at offset 0;
+ * the records whose storage it reuses stop being exportable), with consecutive ids from the counters a push advances; their records
+ * carry the newest source frame's parameter block and the call's image_plane_tag; their rows of the timing table report no stages and 0 DAS
+ * voxels.  *first_frame_id (may be NULL): the oldest output's id.  The record of the newest multi-frame push is left alone --
+ * beamformer_hip_get_last_burst_info and its kin go on describing that push behind the outputs -- until an output takes the timing
+ * slot (one of 32, by id) that holds the push's events; from then on those calls fail as they do after any other push.
+ * One launch (csrc/ensemble.hip), enqueued on the current stream behind the frames it reads; the weights travel through pinned memory
+ * of the call's own.  The call does not synchronise unless device_ms is not NULL (then: the time between two events around the launch).
+ * Refusals, all decided BEFORE ANYTHING CHANGES -- the counters, the records, the ring's next offset -- and leaving every output
+ * unwritten: count or out_count 0 or > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES: BufferOverflow; weights == NULL, a weight that is not
+ * finite, a nonzero imaginary weight on real frames: InvalidAccess; frames that differ in grid or kind: DataSizeMismatch; a run of
+ * out_count frames that does not fit the ring, or that -- placed by the rule above -- would reuse storage of one of its own count
+ * source frames: FrameSizeOverflow; and everything beamformer_hip_score_last_frames refuses (InvalidAccess). */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_mix_last_frames(uint32_t count, const float *weights, uint32_t out_count,
+                                                              uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

@@ -394,6 +394,43 @@ typedef struct {
 } BfPeaksRow;
 typedef struct { uint64_t found, above_threshold; } BfPeaksResult;   /* a frame's box */
 
+/* ---- ensemble filter (ensemble.hip: beamformer_hip_gram_last_frames, beamformer_hip_mix_last_frames) ---- */
+#define BF_ENSEMBLE_MAX_FRAMES 256u          /* = BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES */
+#define BF_GRAM_TILE           32u           /* frames a side of a tile of (j, k) pairs: a block of 256 threads, four pairs a thread */
+#define BF_GRAM_WORD           64u           /* voxels a word of the all-finite mask, and a staged tile of voxels */
+#define BF_GRAM_MAX_CHUNKS     1024u         /* chunks x tile pairs x 16 KiB of partials: at most 16 MiB up to 64 frames, 36 MiB at 256 */
+#define BF_GRAM_MIN_CHUNKS     64u
+#define BF_MIX_TILE            16u           /* output frames a block of the mix kernel produces: 32 accumulator VGPRs */
+static inline uint32_t bf_gram_tiles(uint32_t frames) { return (frames + BF_GRAM_TILE - 1u) / BF_GRAM_TILE; }
+static inline uint32_t bf_gram_tile_pairs(uint32_t frames) { const uint32_t t = bf_gram_tiles(frames); return t * (t + 1u) / 2u; }
+/* The partition of a box of `volume` voxels (flat box order, x fastest) into chunks of whole mask words: a function of the box and the
+ * frame count alone, so the bits of a Gram matrix depend on nothing else.  The cap: 1024 / tile pairs chunks, at least 64 -- 1024 chunks
+ * up to 32 frames, 341 at 64, 64 from 160 frames on. */
+static inline uint32_t bf_gram_chunk_words(uint32_t volume, uint32_t frames)
+{
+	const uint32_t words = (uint32_t)(((uint64_t)volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
+	uint32_t cap = BF_GRAM_MAX_CHUNKS / bf_gram_tile_pairs(frames);
+	if (cap < BF_GRAM_MIN_CHUNKS) cap = BF_GRAM_MIN_CHUNKS;
+	/* four words (256 voxels) a chunk until the cap is reached */
+	const uint32_t each = (words + cap - 1u) / cap;
+	return each < 4u ? 4u : each;
+}
+typedef struct {
+	uint32_t frames, cplx;       /* K; 1: Float32Complex, 0: Float32 */
+	uint32_t points[3];          /* the frames' common grid */
+	uint32_t first[3], count[3]; /* the box, inside the grid, every count >= 1 */
+	uint32_t volume, words;      /* voxels of the box (below 2^32), ceil(volume / 64) */
+	uint32_t chunk_words, chunks;/* bf_gram_chunk_words; ceil(words / chunk_words) */
+	uint32_t tiles, tile_pairs;  /* bf_gram_tiles, bf_gram_tile_pairs */
+} BfGramArgs;
+typedef struct {
+	uint32_t frames, outputs;    /* K, M */
+	uint32_t cplx;
+	uint32_t padded_outputs;     /* M rounded up to BF_MIX_TILE: the rows of the weight table, zero past M */
+	uint64_t elements;           /* a frame's complex voxels (cplx) or floats */
+	uint64_t out_offset, out_stride;   /* the first output frame in the ring, bytes; from one output to the next */
+} BfMixArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -445,6 +482,15 @@ hipError_t bf_launch_frame_peaks_mark(const void *ring, const BfPeaksRow *rows, 
 hipError_t bf_launch_frame_peaks_emit(const void *ring, const BfPeaksRow *rows, uint32_t frame_count, uint32_t max_blocks,
                                       const uint64_t *masks, const uint32_t *counts, const uint32_t *offsets, const uint32_t *firsts,
                                       void *list, hipStream_t s);
+/* ensemble.hip, the Gram matrix: three launches, no atomics -- the all-finite mask (a wave a word of 64 box voxels, every frame read
+ * once), the partial pass (grid x the chunk, grid y the tile pair: BF_GRAM_TILE x BF_GRAM_TILE pairs of double2 a block) and the fold
+ * (a thread a pair j <= k sums its chunks' partials in chunk order and stores both triangles; one more block counts the mask's bits).
+ * offsets[frames]: where each frame lies in the ring, bytes, oldest first.  result: {uint64 voxels, uint64 non_finite, double
+ * gram[frames][frames][2]}.  All tables are device memory; the box lies inside every frame (the caller checks) */
+hipError_t bf_launch_gram(const void *ring, const uint64_t *offsets, const BfGramArgs *a, uint64_t *mask, double *partials, void *result, hipStream_t s);
+/* ensemble.hip, the mix: one launch.  weights[padded_outputs][frames][2] floats (real frames: the imaginary ones are not read) and
+ * offsets[frames] are device memory; output j is written at ring + out_offset + j * out_stride */
+hipError_t bf_launch_mix(void *ring, const uint64_t *offsets, const float *weights, const BfMixArgs *a, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

@@ -188,6 +188,10 @@ static void release_one_device(Device &d)
 	if (d.peaks_begin) (void)hipEventDestroy(d.peaks_begin);
 	if (d.peaks_end)   (void)hipEventDestroy(d.peaks_end);
 	d.peaks_begin = d.peaks_end = nullptr;
+	d.mix_table.release();
+	if (d.mix_pinned) (void)hipHostFree(d.mix_pinned);
+	for (hipEvent_t *e : {&d.mix_copied, &d.mix_begin, &d.mix_end}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+	d.mix_pinned = nullptr; d.mix_copy_pending = false;
 	if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
 	if (d.metrics_begin) (void)hipEventDestroy(d.metrics_begin);
 	if (d.metrics_end)   (void)hipEventDestroy(d.metrics_end);
@@ -351,28 +355,39 @@ struct DasJob {
 	uint32_t        path;           /* the kernel that ran its main part */
 };
 
+/* What the ring's placement rule needs of a frame: its grid and the tag its record carries.  A push's frames are DasJobs; the frames
+ * mix_last_frames writes are no jobs.  shape_of(k): frame k of the run. */
+struct FrameShape { const uint32_t *points; uint32_t tag; };
+
 /* The bytes of a run of frames, contiguous in the frame ring, each rounded to 64 bytes (frame_run_bytes per frame: saturating).  False:
  * the run does not fit `ring` bytes. */
-static bool job_run_bytes(const DasJob *jobs, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total)
+template <class ShapeOf>
+static bool run_bytes_of(ShapeOf shape_of, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total)
 {
 	total = 0;
 	for (uint32_t k = 0; k < count; k++) {
 		uint64_t frame;
-		if (!frame_run_bytes(jobs[k].points, nullptr, 1, voxel_bytes, ring, frame) || frame > ring - total) return false;
+		if (!frame_run_bytes(shape_of(k).points, nullptr, 1, voxel_bytes, ring, frame) || frame > ring - total) return false;
 		total += frame;
 	}
 	return true;
 }
 
+static bool job_run_bytes(const DasJob *jobs, uint32_t count, uint64_t voxel_bytes, uint64_t ring, uint64_t &total)
+{
+	return run_bytes_of([jobs](uint32_t k) { return FrameShape{jobs[k].points, jobs[k].tag}; }, count, voxel_bytes, ring, total);
+}
+
 /* beamformer_frame_next (beamformer_core.c:440-466), for a run of `count` frames, contiguous in the ring, each rounded to 64 bytes: frame
- * k has jobs[k]'s points and tag.  A run that would straddle the end starts again at offset 0; the records it overwrites stop being
+ * k has shape_of(k)'s points and tag.  A run that would straddle the end starts again at offset 0; the records it overwrites stop being
  * exportable.  Consecutive ids, each frame's timing slot named in its record.  Returns the first, or null when the run does not fit the
  * ring; total: the bytes of the whole run. */
-static FrameRecord *next_frames(const DasJob *jobs, uint32_t count, bool complex_frame, uint32_t block, uint64_t &total)
+template <class ShapeOf>
+static FrameRecord *place_frames(ShapeOf shape_of, uint32_t count, bool complex_frame, uint32_t block, uint64_t &total)
 {
 	Device &d = *g_context.cur;
 	const int kind = complex_frame ? BeamformerDataKind_Float32Complex : BeamformerDataKind_Float32;
-	if (count == 0 || !job_run_bytes(jobs, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total)) return nullptr;
+	if (count == 0 || !run_bytes_of(shape_of, count, (uint64_t)bf_kind_byte_size[kind], d.ring.size, total)) return nullptr;
 	if (d.ring_next_offset > d.ring.size - total) d.ring_next_offset = 0;
 	/* records whose storage the run reuses stop being exportable: one pass for the run's whole byte range (the run's own records are
 	 * written below, after it) */
@@ -380,19 +395,26 @@ static FrameRecord *next_frames(const DasJob *jobs, uint32_t count, bool complex
 		if (old.bytes && old.offset < d.ring_next_offset + total && d.ring_next_offset < old.offset + old.bytes) old.bytes = 0;
 	FrameRecord *first = nullptr;
 	for (uint32_t k = 0; k < count; k++) {
-		const uint32_t *n = jobs[k].points;
+		const FrameShape shape = shape_of(k);
+		const uint32_t *n = shape.points;
 		const uint64_t bytes = round_up((uint64_t)n[0] * n[1] * n[2] * (uint64_t)bf_kind_byte_size[kind], 64);
 		uint64_t id = d.frame_counter++;
 		FrameRecord *f = &d.frames[id % d.frames.size()];
 		f->offset = d.ring_next_offset; f->bytes = bytes;
 		f->points[0] = n[0]; f->points[1] = n[1]; f->points[2] = n[2];
 		f->data_kind = kind; f->id = (uint32_t)id; f->block = block; f->failed = false;
-		f->tag = jobs[k].tag;
+		f->tag = shape.tag;
 		f->timing_slot = (int)(id % kTimingSlots);
 		d.ring_next_offset += bytes;
 		if (k == 0) first = f;
 	}
 	return first;
+}
+
+/* the frames of a push: job k's points and tag */
+static FrameRecord *next_frames(const DasJob *jobs, uint32_t count, bool complex_frame, uint32_t block, uint64_t &total)
+{
+	return place_frames([jobs](uint32_t k) { return FrameShape{jobs[k].points, jobs[k].tag}; }, count, complex_frame, block, total);
 }
 
 /* A timed HIP event costs ~4 us of stream time on this runtime (measured: a 0.26 MB / 256 x 256
@@ -1567,7 +1589,7 @@ static bool push_frames(uint32_t block, const PushGround &g, const void *data, b
 	share_timing_rows(d, first, F, owner);
 	PushRecord &r = d.multi;
 	r.kind = m.kind; r.first_id = first; r.count = F; r.events_slot = owner; r.decide_us = m.decide_us;
-	r.rf_frames = N;
+	r.rf_frames = N; r.mixed = 0;
 	lockstep.complete = true;
 	return true;
 }
@@ -1649,7 +1671,7 @@ static const PushRecord *newest_push(PushRecord::Kind kind, uint32_t &first_id, 
 	Context &c = g_context;
 	Device &d = c.devices[0];
 	const PushRecord &r = d.multi;
-	if (!c.device_ready || r.kind != kind || d.frame_counter != r.first_id + r.count || !newest_record(d) ||
+	if (!c.device_ready || r.kind != kind || d.frame_counter != r.first_id + r.count + r.mixed || !newest_record(d) ||
 	    !HIP_OK(hipSetDevice(d.device)) || !HIP_OK(hipStreamSynchronize(d.stream))) {
 		set_error(BeamformerLibErrorKind_InvalidAccess);
 		return nullptr;
@@ -2543,6 +2565,172 @@ bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
 	}
 	*peak_count = total;
+	return true;
+}
+
+namespace {
+
+/* the `count` newest frames as the ensemble calls take them: of one grid and one kind (else DataSizeMismatch), boxed */
+bool newest_ensemble_frames(uint32_t count, const BeamformerHipFrameRegion *region, std::vector<BoxedFrame> &boxed)
+{
+	if (!newest_boxed_frames(count, region, boxed)) return false;
+	const FrameRecord &f0 = *boxed[0].record;
+	for (uint32_t n = 1; n < count; n++) {
+		const FrameRecord &f = *boxed[n].record;
+		if (f.data_kind != f0.data_kind || f.points[0] != f0.points[0] || f.points[1] != f0.points[1] || f.points[2] != f0.points[2])
+			return set_error(BeamformerLibErrorKind_DataSizeMismatch);
+	}
+	return true;
+}
+
+} // namespace
+
+/* beamformer_hip_gram_last_frames: the slow-time Gram matrix of the `count` newest frames, reduced where they lie (ensemble.hip).
+ * Everything that can refuse is decided before anything is enqueued. */
+bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipEnsembleInfo) == 64, "a record without padding");
+	static_assert(BF_ENSEMBLE_MAX_FRAMES == BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, "one limit");
+	std::vector<BoxedFrame> boxed;
+	if (!newest_ensemble_frames(count, region, boxed)) return false;
+	Device &d = g_context.devices[0];
+	const BoxedFrame &b0 = boxed[0];
+	if (b0.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);     /* the kernels count a box's voxels in 32 bits */
+
+	BfGramArgs a{};
+	a.frames = count; a.cplx = b0.cplx;
+	for (int k = 0; k < 3; k++) { a.points[k] = b0.record->points[k]; a.first[k] = b0.first[k]; a.count[k] = b0.count[k]; }
+	a.volume = (uint32_t)b0.volume;
+	a.words = (uint32_t)((b0.volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
+	a.chunk_words = bf_gram_chunk_words(a.volume, count);
+	a.chunks = (a.words + a.chunk_words - 1u) / a.chunk_words;
+	a.tiles = bf_gram_tiles(count); a.tile_pairs = bf_gram_tile_pairs(count);
+
+	/* device: offsets | result {voxels, non_finite, gram} | mask | partials; pinned: offsets | result */
+	const size_t offsets_bytes = round_up(sizeof(uint64_t) * count, 64), gram_bytes = sizeof(double) * 2 * count * count,
+	             result_bytes = round_up(16 + gram_bytes, 64), mask_bytes = round_up(sizeof(uint64_t) * a.words, 64),
+	             partials_bytes = sizeof(double) * 2 * BF_GRAM_TILE * BF_GRAM_TILE * a.tile_pairs * a.chunks;
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && ensure_metrics_memory(d, offsets_bytes + result_bytes, offsets_bytes + result_bytes + mask_bytes + partials_bytes);
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
+	uint64_t *offsets = (uint64_t *)pinned;
+	for (uint32_t n = 0; n < count; n++) offsets[n] = boxed[n].record->offset;
+	const char *result = pinned + offsets_bytes;
+	hipStream_t s = d.stream;
+	ok &= HIP_OK(hipMemcpyAsync(device, pinned, sizeof(uint64_t) * count, hipMemcpyHostToDevice, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
+	if (ok) ok &= HIP_OK(bf_launch_gram(d.ring.ptr, (const uint64_t *)device, &a, (uint64_t *)(device + offsets_bytes + result_bytes),
+	                                    (double *)(device + offsets_bytes + result_bytes + mask_bytes), device + offsets_bytes, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
+	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + offsets_bytes, device + offsets_bytes, 16 + gram_bytes, hipMemcpyDeviceToHost, s));
+	/* the synchronise runs whatever failed above: it is what frees the pinned memory */
+	ok &= HIP_OK(hipStreamSynchronize(s));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (device_ms) {
+		float ms = 0;
+		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
+	}
+	std::memcpy(gram, result + 16, gram_bytes);
+	if (info) {
+		std::memset(info, 0, sizeof(*info));
+		info->count = count; info->data_kind = (uint32_t)b0.record->data_kind;
+		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->region_first[k] = a.first[k]; info->region_count[k] = a.count[k]; }
+		info->first_frame_id = b0.record->id;
+		std::memcpy(&info->voxels, result, 8); std::memcpy(&info->non_finite, result + 8, 8);
+	}
+	return true;
+}
+
+/* beamformer_hip_mix_last_frames: out_count linear combinations of the `count` newest frames, queued as frames of their own
+ * (ensemble.hip).  Everything that can refuse is decided, and every buffer grown, before the ids are taken; nothing synchronises unless
+ * device_ms is asked for. */
+bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
+{
+	Context &c = g_context;
+	std::vector<BoxedFrame> boxed;
+	if (!newest_ensemble_frames(count, nullptr, boxed)) return false;
+	Device &d = c.devices[0];
+	const FrameRecord newest = *boxed[count - 1].record;      /* (a copy: the run's records may take its place) */
+	const bool cplx = boxed[0].cplx;
+	if (!cplx)
+		for (size_t n = 0; n < (size_t)out_count * count; n++)
+			if (weights[2 * n + 1] != 0.0f) return set_error(BeamformerLibErrorKind_InvalidAccess);
+
+	/* where the ring's placement rule will put the run, and whether that reuses storage of a source frame */
+	const uint32_t K = count, M = out_count;
+	const auto shape_of = [&newest, image_plane_tag](uint32_t) { return FrameShape{newest.points, image_plane_tag}; };
+	uint64_t run_bytes = 0;
+	if (!run_bytes_of(shape_of, M, cplx ? 8u : 4u, d.ring.size, run_bytes)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+	const uint64_t run_first = d.ring_next_offset > d.ring.size - run_bytes ? 0 : d.ring_next_offset;
+	for (const BoxedFrame &b : boxed)
+		if (b.record->offset < run_first + run_bytes && run_first < b.record->offset + b.record->bytes) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
+
+	/* the table: offsets[K] | weights[tile][k][BF_MIX_TILE][2], rows past M zero */
+	const uint32_t padded = (M + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
+	const size_t offsets_bytes = round_up(sizeof(uint64_t) * K, 64), weights_bytes = sizeof(float) * 2 * padded * K;
+	const size_t table_max = round_up(sizeof(uint64_t) * BF_ENSEMBLE_MAX_FRAMES, 64) + sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES;
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && d.mix_table.ensure(table_max);
+	if (ok && !d.mix_pinned && !HIP_OK(hipHostMalloc(&d.mix_pinned, table_max, hipHostMallocDefault))) { d.mix_pinned = nullptr; ok = false; }
+	if (ok && !d.mix_copied) ok = HIP_OK(hipEventCreateWithFlags(&d.mix_copied, hipEventDisableTiming));
+	if (ok && !d.mix_begin)  ok = HIP_OK(hipEventCreate(&d.mix_begin));
+	if (ok && !d.mix_end)    ok = HIP_OK(hipEventCreate(&d.mix_end));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (d.mix_copy_pending) { (void)hipEventSynchronize(d.mix_copied); d.mix_copy_pending = false; }   /* (the previous call's copy: long done) */
+	char *pinned = (char *)d.mix_pinned;
+	uint64_t *offsets = (uint64_t *)pinned;
+	for (uint32_t n = 0; n < K; n++) offsets[n] = boxed[n].record->offset;
+	float *table = (float *)(pinned + offsets_bytes);
+	std::memset(table, 0, weights_bytes);
+	for (uint32_t j = 0; j < M; j++)
+		for (uint32_t k = 0; k < K; k++) {
+			float *w = table + (((size_t)(j / BF_MIX_TILE) * K + k) * BF_MIX_TILE + j % BF_MIX_TILE) * 2;
+			w[0] = weights[((size_t)j * K + k) * 2]; w[1] = weights[((size_t)j * K + k) * 2 + 1];
+		}
+
+	/* ---- from here on the call owns ids first .. first + M - 1, taken from the counters a push advances ---- */
+	hipStream_t s = d.stream;
+	const uint64_t first = c.push_sequence;
+	c.push_sequence += M;
+	d.frame_counter = first;
+	Tombstones lockstep{c, first, M, 1, false};
+	/* the newest push stays the newest push behind the run -- unless the run takes the timing slot that holds its events */
+	PushRecord &push = d.multi;
+	if (push.kind != PushRecord::None && first == push.first_id + push.count + push.mixed) {
+		bool slot_taken = M >= kTimingSlots;
+		for (uint32_t j = 0; j < M && !slot_taken; j++) slot_taken = (first + j) % kTimingSlots == push.events_slot;
+		if (slot_taken) push.kind = PushRecord::None; else push.mixed += M;
+	}
+	FrameRecord *frame0 = place_frames(shape_of, M, cplx, newest.block, run_bytes);
+	if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);      /* (checked above: not reached) */
+	for (uint32_t j = 0; j < M; j++) {
+		TimingSlot &t = d.timing[(first + j) % kTimingSlots];
+		t.count = 0; t.counted = false; t.sampled = false; t.events_slot = (uint32_t)((first + j) % kTimingSlots); t.share = 1;
+		t.das_voxels = 0; t.das_taps = t.das_sample_bytes = t.das_path = 0; t.das_row_end_planes = 0;
+		t.violations_slot = ~0ull; t.frame_id = first + j; t.failed = false;
+	}
+	d.have_sample = false;              /* the slots of older sampled frames may be gone: a single frame that follows records its own events */
+
+	BfMixArgs a{};
+	a.frames = K; a.outputs = M; a.cplx = cplx; a.padded_outputs = padded;
+	a.elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
+	a.out_offset = frame0->offset; a.out_stride = frame0->bytes;
+	ok &= HIP_OK(hipMemcpyAsync(d.mix_table.ptr, pinned, offsets_bytes + weights_bytes, hipMemcpyHostToDevice, s));
+	d.mix_copy_pending = HIP_OK(hipEventRecord(d.mix_copied, s));
+	ok &= d.mix_copy_pending;
+	if (device_ms) ok &= HIP_OK(hipEventRecord(d.mix_begin, s));
+	if (ok) ok &= HIP_OK(bf_launch_mix(d.ring.ptr, (const uint64_t *)d.mix_table.ptr, (const float *)((const char *)d.mix_table.ptr + offsets_bytes), &a, s));
+	if (device_ms) {
+		ok &= HIP_OK(hipEventRecord(d.mix_end, s));
+		ok &= HIP_OK(hipStreamSynchronize(s));
+		float ms = 0;
+		if (ok) *device_ms = HIP_OK(hipEventElapsedTime(&ms, d.mix_begin, d.mix_end)) ? ms : 0.0f;
+	}
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (first_frame_id) *first_frame_id = (uint32_t)first;
+	lockstep.complete = true;
 	return true;
 }
 

@@ -5,7 +5,9 @@
  * chirps, moments) against the compiled reference by tests/test_host_math.py through the
  * bf_host_* debug exports at the bottom of lib_api.cpp. */
 #include "host_math.h"
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 namespace bf {
@@ -249,6 +251,100 @@ void das_transform(const float mn[3], const float mx[3], int32_t points[3], floa
 		out[0] = mx[0] - mn[0]; out[5] = mx[1] - mn[1]; out[10] = mx[2] - mn[2];
 		out[12] = mn[0]; out[13] = mn[1]; out[14] = mn[2]; out[15] = 1.0f;
 	}
+}
+
+/* Cyclic Jacobi eigendecomposition of the n x n Hermitian matrix whose upper triangle upper[n][n][2] (re, im) holds, in double; the
+ * imaginary parts of the diagonal are not read.  The pair (p, q) with a = A[p][q] = |a| e^{i phi} is rotated by J = P R: P the
+ * phase that makes the entry real (P[q][q] = e^{-i phi}), R the real Jacobi rotation (c, s) that annihilates it -- t = tan of the
+ * angle, the smaller root, A'[p][p] = A[p][p] - t |a|, A'[q][q] = A[q][q] + t |a|.  Rows p and q of J^H A J are formed as whole rows,
+ * the columns mirrored from them, V J kept transposed: every loop runs along contiguous arrays of real and of imaginary parts.  A pair
+ * is skipped when |a| <= 2^-60 ||A||_F; the sweeps end with the first that rotates nothing.  values: descending; vectors_re / _im:
+ * row i the eigenvector of values[i].  False: an entry that is not finite. */
+static bool hermitian_eigen(const double *upper, uint32_t n, std::vector<double> &values, std::vector<double> &vectors_re, std::vector<double> &vectors_im)
+{
+	std::vector<double> ar((size_t)n * n), ai((size_t)n * n), vr((size_t)n * n, 0.0), vi((size_t)n * n, 0.0);
+	double norm2 = 0;
+	for (uint32_t j = 0; j < n; j++) {
+		for (uint32_t k = j; k < n; k++) {
+			const double re = upper[((size_t)j * n + k) * 2], im = j == k ? 0.0 : upper[((size_t)j * n + k) * 2 + 1];
+			if (!std::isfinite(re) || !std::isfinite(im)) return false;
+			ar[(size_t)j * n + k] = re; ai[(size_t)j * n + k] = im;
+			ar[(size_t)k * n + j] = re; ai[(size_t)k * n + j] = 0.0 - im;
+			norm2 += (j == k ? 1.0 : 2.0) * (re * re + im * im);
+		}
+		vr[(size_t)j * n + j] = 1.0;
+	}
+	const double skip = std::ldexp(std::sqrt(norm2), -60);
+	for (int sweep = 0; sweep < 64; sweep++) {
+		bool rotated = false;
+		for (uint32_t p = 0; p + 1 < n; p++) {
+			for (uint32_t q = p + 1; q < n; q++) {
+				const double are = ar[(size_t)p * n + q], aim = ai[(size_t)p * n + q], mag = std::hypot(are, aim);
+				if (!(mag > skip)) continue;
+				rotated = true;
+				const double er = are / mag, ei = aim / mag;              /* e^{i phi} */
+				const double app = ar[(size_t)p * n + p], aqq = ar[(size_t)q * n + q];
+				const double theta = (aqq - app) / (2.0 * mag);
+				const double t = (theta < 0 ? -1.0 : 1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+				const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+				const double sr = s * er, si = s * ei, cr = c * er, ci = c * ei;   /* s e^{i phi}, c e^{i phi} */
+				double *pr = &ar[(size_t)p * n], *pi = &ai[(size_t)p * n], *qr = &ar[(size_t)q * n], *qi = &ai[(size_t)q * n];
+				/* rows p and q of J^H A:  p' = c p - s e^{i phi} q,  q' = s p + c e^{i phi} q */
+				for (uint32_t r = 0; r < n; r++) {
+					const double xr = pr[r], xi = pi[r], yr = qr[r], yi = qi[r];
+					pr[r] = c * xr - (sr * yr - si * yi); pi[r] = c * xi - (sr * yi + si * yr);
+					qr[r] = s * xr + (cr * yr - ci * yi); qi[r] = s * xi + (cr * yi + ci * yr);
+				}
+				/* the columns are their conjugates; the 2 x 2 block in closed form */
+				for (uint32_t r = 0; r < n; r++) {
+					ar[(size_t)r * n + p] = pr[r]; ai[(size_t)r * n + p] = 0.0 - pi[r];
+					ar[(size_t)r * n + q] = qr[r]; ai[(size_t)r * n + q] = 0.0 - qi[r];
+				}
+				pr[p] = app - t * mag; pi[p] = 0.0; qr[q] = aqq + t * mag; qi[q] = 0.0;
+				pr[q] = pi[q] = qr[p] = qi[p] = 0.0;
+				/* columns p and q of V J, V kept transposed:  p' = c p - s e^{-i phi} q,  q' = s p + c e^{-i phi} q */
+				double *upr = &vr[(size_t)p * n], *upi = &vi[(size_t)p * n], *uqr = &vr[(size_t)q * n], *uqi = &vi[(size_t)q * n];
+				for (uint32_t r = 0; r < n; r++) {
+					const double xr = upr[r], xi = upi[r], yr = uqr[r], yi = uqi[r];
+					upr[r] = c * xr - (sr * yr + si * yi); upi[r] = c * xi - (sr * yi - si * yr);
+					uqr[r] = s * xr + (cr * yr + ci * yi); uqi[r] = s * xi + (cr * yi - ci * yr);
+				}
+			}
+		}
+		if (!rotated) break;
+	}
+	std::vector<uint32_t> order(n);
+	for (uint32_t i = 0; i < n; i++) order[i] = i;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ar[(size_t)a * n + a] > ar[(size_t)b * n + b]; });
+	values.resize(n); vectors_re.resize((size_t)n * n); vectors_im.resize((size_t)n * n);
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t from = order[i];
+		values[i] = ar[(size_t)from * n + from];
+		std::copy(&vr[(size_t)from * n], &vr[(size_t)from * n] + n, &vectors_re[(size_t)i * n]);
+		std::copy(&vi[(size_t)from * n], &vi[(size_t)from * n] + n, &vectors_im[(size_t)i * n]);
+	}
+	return true;
+}
+
+/* beamformer_hip_clutter_projector (include/ogl_beamformer_hip.h): weights = sum over the eigenvectors u_i, i from remove_high to
+ * n - remove_low - 1 in descending order of eigenvalue, of u_i u_i^H, rounded once to float32.  The arguments arrive checked. */
+bool clutter_projector(const double *gram, uint32_t n, uint32_t remove_high, uint32_t remove_low, float *weights, double *eigenvalues)
+{
+	std::vector<double> values, ur, ui;
+	if (!hermitian_eigen(gram, n, values, ur, ui)) return false;
+	std::vector<double> wr((size_t)n * n, 0.0), wi((size_t)n * n, 0.0);
+	for (uint32_t i = remove_high; i < n - remove_low; i++) {
+		const double *xr = &ur[(size_t)i * n], *xi = &ui[(size_t)i * n];
+		for (uint32_t j = 0; j < n; j++) {
+			const double jr = xr[j], ji = xi[j];
+			double *rowr = &wr[(size_t)j * n], *rowi = &wi[(size_t)j * n];
+			/* u[j] conj(u[k]) */
+			for (uint32_t k = 0; k < n; k++) { rowr[k] += jr * xr[k] + ji * xi[k]; rowi[k] += ji * xr[k] - jr * xi[k]; }
+		}
+	}
+	for (size_t e = 0; e < (size_t)n * n; e++) { weights[2 * e] = (float)wr[e]; weights[2 * e + 1] = (float)wi[e]; }
+	if (eigenvalues) std::copy(values.begin(), values.end(), eigenvalues);
+	return true;
 }
 
 } // namespace bf

@@ -24,6 +24,7 @@ bool               filter_create(const BeamformerFilterParameters &fp, Filter &o
 constexpr int      kHilbertLength = 63;
 std::vector<float> hilbert_fir();                                     /* 2*63 floats (re, im), correlation order */
 void               m4_mul(const float *a, const float *b, float *out);
+bool               clutter_projector(const double *gram, uint32_t n, uint32_t remove_high, uint32_t remove_low, float *weights, double *eigenvalues);   /* false: a non-finite entry */
 void               das_transform(const float mn[3], const float mx[3], int32_t points[3], float out16[16]);
 
 } // namespace bf

@@ -1011,6 +1011,35 @@ uint32_t beamformer_hip_peaks_to_views(const float source_voxel_transform[16], c
 	return 1;
 }
 
+uint32_t beamformer_hip_gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info,
+                                         float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(gram != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return gram_last_frames(count, region, gram, info, device_ms);
+}
+
+/* host only: the Jacobi eigendecomposition and the projector are host_math.cpp's */
+uint32_t beamformer_hip_clutter_projector(const double *gram, uint32_t count, uint32_t remove_high, uint32_t remove_low, float *weights,
+                                          double *eigenvalues)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(gram != nullptr && weights != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check((uint64_t)remove_high + remove_low <= count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return check(clutter_projector(gram, count, remove_high, remove_low, weights, eigenvalues), BeamformerLibErrorKind_InvalidAccess) ? 1 : 0;
+}
+
+uint32_t beamformer_hip_mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id,
+                                        float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES && out_count >= 1 && out_count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES,
+	           BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(weights != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (size_t n = 0; n < (size_t)2 * count * out_count; n++)
+		if (!check(std::isfinite(weights[n]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return mix_last_frames(count, weights, out_count, image_plane_tag, first_frame_id, device_ms);
+}
+
 uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

@@ -134,6 +134,9 @@ def _load():
                                                         C.POINTER(P.HipFramePeak), C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_peaks_to_views": (u32, [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(P.HipFramePeak), u32, C.POINTER(u32),
                                                 C.POINTER(C.c_float), u32, u32, C.POINTER(P.HipView)]),
+        "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
+        "beamformer_hip_clutter_projector": (u32, [C.POINTER(C.c_double), u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+        "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -551,6 +554,48 @@ def peaks_to_views(source_transform, source_points, peaks, patch_points, patch_e
                                                    (C.c_uint32 * 3)(*[int(v) for v in patch_points]),
                                                    (C.c_float * 3)(*[float(v) for v in patch_extent_voxels]), 1 if use_offsets else 0, int(tag), out))
     return list(out[: len(peaks)])
+
+
+def gram_last_frames(count, region=None):
+    """beamformer_hip_gram_last_frames: the slow-time Gram matrix of the `count` newest frames (one grid, one kind), reduced on the
+    device over the voxels of the box that are finite in every frame; region None: the frames whole.  Returns (gram, info, device_ms):
+    a complex128 (count, count) array -- gram[j, k] = sum of conj(f_j) f_k, index 0 the oldest frame --, the HipEnsembleInfo and the
+    device time of the launches."""
+    count = int(count)
+    room = count if 0 < count <= P.HIP_MAX_ENSEMBLE_FRAMES else 1
+    gram = np.zeros((room, room), np.complex128)
+    info, ms = P.HipEnsembleInfo(), C.c_float(0)
+    _check(library().beamformer_hip_gram_last_frames(count, None if region is None else C.byref(region), gram.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     C.byref(info), C.byref(ms)))
+    return gram, info, float(ms.value)
+
+
+def clutter_projector(gram, remove_high, remove_low=0):
+    """beamformer_hip_clutter_projector (host only): the projector that drops the remove_high strongest and the remove_low weakest
+    slow-time components of the Hermitian `gram` (its upper triangle is read).  Returns (weights, eigenvalues): a complex64 (K, K)
+    array for mix_last_frames and the K eigenvalues in descending order."""
+    gram = np.ascontiguousarray(gram, np.complex128)
+    count = int(gram.shape[0]) if gram.ndim == 2 and gram.shape[0] == gram.shape[1] else 0
+    room = max(1, count)
+    weights, values = np.zeros((room, room), np.complex64), np.zeros(room, np.float64)
+    _check(library().beamformer_hip_clutter_projector(gram.ctypes.data_as(C.POINTER(C.c_double)), count, int(remove_high), int(remove_low),
+                                                      weights.ctypes.data_as(C.POINTER(C.c_float)), values.ctypes.data_as(C.POINTER(C.c_double))))
+    return weights, values
+
+
+def mix_last_frames(count, weights, tag=0, timed=True):
+    """beamformer_hip_mix_last_frames: weights.shape[0] new frames of the frame ring, frame j = sum over k of weights[j, k] times the
+    k-th oldest of the `count` newest frames; weights: (out_count, count), complex (real frames: real, or complex with zero imaginary
+    parts).  Returns (first_frame_id, device_ms); timed False: the call does not synchronise and device_ms is 0."""
+    count = int(count)
+    weights = np.ascontiguousarray(np.atleast_2d(np.asarray(weights)), np.complex64)
+    out_count = int(weights.shape[0])
+    if weights.shape[1] != count:
+        raise ValueError(f"weights {weights.shape}: the second dimension is not count = {count}")
+    first, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_mix_last_frames(count, weights.ctypes.data_as(C.POINTER(C.c_float)), out_count, int(tag), C.byref(first),
+                                                    C.byref(ms) if timed else None))
+    return int(first.value), float(ms.value)
 
 
 def frame_info(frame_id):

@@ -328,6 +328,15 @@ class HipFramePeaks(C.Structure):
                 ("threshold", C.c_float), ("first", C.c_uint32), ("stored", C.c_uint32), ("found", C.c_uint64), ("above_threshold", C.c_uint64)]
 
 
+HIP_MAX_ENSEMBLE_FRAMES = 256
+
+
+class HipEnsembleInfo(C.Structure):
+    """BeamformerHipEnsembleInfo: what beamformer_hip_gram_last_frames reduced (64 bytes, no padding)"""
+    _fields_ = [("count", C.c_uint32), ("data_kind", C.c_uint32), ("points", C.c_uint32 * 3), ("region_first", C.c_uint32 * 3),
+                ("region_count", C.c_uint32 * 3), ("first_frame_id", C.c_uint32), ("voxels", C.c_uint64), ("non_finite", C.c_uint64)]
+
+
 class FrameScore(enum.IntEnum):
     """BeamformerHipFrameScore: the criteria of beamformer_hip_rank_frames"""
     Energy = 0
