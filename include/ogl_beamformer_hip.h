@@ -864,6 +864,8 @@ typedef struct {
 	uint32_t das_samples, iq_pipeline;
 	float    das_sampling_frequency, das_time_offset;
 	float    das_voxel_transform[16];
+	uint64_t intermediate_bytes;      /* what the executor allocates (+ 64) for each of its two inter-stage buffers, and a burst's
+	                                   * frame stride there: the largest write extent of the plan's stages (csrc/planner.cpp) */
 } BeamformerHipPlan;
 /* The stage list the library would run for a parameter block (plan_compute_pipeline,
  * beamformer_core.c:553-1013, with the whole channel count as the chunk). */

@@ -258,6 +258,7 @@ typedef struct {
 	uint32_t size[3];
 	int64_t  in_stride[3], out_stride[3];
 	int32_t  in_kind, out_kind, interleave;
+	int64_t  in_elements;             /* elements of in_kind readable at `left` (per frame); an element past them reads as zero */
 	uint32_t frames;                  /* a burst (executor.cpp push_burst): frames of the launch, 0 or 1 = one; frame f reads and writes f * the strides below further on */
 	uint64_t in_frame_bytes, out_frame_bytes;
 } BfReshapeArgs;

@@ -472,6 +472,7 @@ static bool launch_stage(PlanState *ps, const BeamformerParameters &bp, size_t i
 		for (int k = 0; k < 3; k++) { a.in_stride[k] = st.in_stride[k]; a.out_stride[k] = st.out_stride[k]; }
 		a.in_kind = st.in_kind; a.out_kind = st.out_kind;
 		a.interleave = !bf_kind_complex[st.in_kind] && bf_kind_complex[st.out_kind];
+		a.in_elements = cur_elements_bytes / bf_kind_byte_size[st.in_kind];
 		a.left  = cur;
 		a.right = (const char *)cur + (size_t)Sd * C * A * (size_t)bf_kind_byte_size[st.in_kind];   /* :1384-1385 */
 		a.out = out;
@@ -964,8 +965,23 @@ static bool walk_plan(uint32_t block, PlanState *ps, const Push &w)
 		case BeamformerShaderKind_Filter:
 		case BeamformerShaderKind_Demodulate:{
 			DeviceBuffer &out = w.stage[toggle];
+			/* What the next stage may read of this one's output is what the plan's stages can write of a buffer, plan.intermediate_bytes --
+			 * not the allocation, which a larger plan may have grown and filled.  Filter and Demodulate read windows of consecutive
+			 * elements wherever their row starts put them (filter.glsl:81-87 halves a row start): below that bound they reach elements this
+			 * stage does not write -- the second half of every row of a root-layout buffer after demodulation, the bytes behind a
+			 * narrower kind's extent.  The reference never clears its ping-pong buffer (beamformer_core.c:1229-1237) and finds there what
+			 * the stage two hops back, or an earlier frame, left in the slot.  This build defines such elements as zero: the buffer is
+			 * cleared first wherever the stage does not write all of it (the oracle clears its slots the same way, oracle_plan.c). */
+			const Stage *next = i + 1 < plan.stages.size() ? &plan.stages[i + 1] : nullptr;
+			if (next && (next->kind == BeamformerShaderKind_Filter || next->kind == BeamformerShaderKind_Demodulate)) {
+				uint64_t dense = (uint64_t)plan.das_samples * plan.channels * plan.acquisitions * (uint64_t)bf_kind_byte_size[st.out_kind];
+				if (bf_kind_complex[st.in_kind] && !bf_kind_complex[st.out_kind] &&
+				    (st.kind == BeamformerShaderKind_Filter || st.kind == BeamformerShaderKind_Demodulate)) dense *= 2;
+				if (dense != plan.intermediate_bytes)
+					ok &= HIP_OK(hipMemsetAsync(out.ptr, 0, w.stage_stride ? w.stage_stride * N : plan.intermediate_bytes, s));
+			}
 			ok &= launch_stage(ps, pb.parameters, i, cur, cur_bound, out.ptr, s, N, cur_stride, w.stage_stride);
-			cur = (const char *)out.ptr; cur_stride = w.stage_stride; cur_bound = (int64_t)(w.stage_stride ? w.stage_stride : out.size); toggle ^= 1;
+			cur = (const char *)out.ptr; cur_stride = w.stage_stride; cur_bound = (int64_t)plan.intermediate_bytes; toggle ^= 1;
 		}break;
 		case BeamformerShaderKind_DAS:{
 			uint64_t run_bytes = 0;
@@ -1146,7 +1162,7 @@ static bool run_peers(uint32_t block, const void *src, uint64_t rf_size, uint32_
 		ok &= HIP_OK(hipStreamWaitEvent(p.stream, p.rf_landed[slot], 0));
 		TimingSlot &t = p.timing[p.frame_counter % kTimingSlots];
 		t.sampled = true; t.failed = false; t.events_slot = (uint32_t)(p.frame_counter % kTimingSlots);
-		ok = ok && run_frame(block, p.rf[slot].ptr, (int64_t)p.rf[slot].size, false);
+		ok = ok && run_frame(block, p.rf[slot].ptr, (int64_t)rf_size, false);
 		p.consumed_pending[slot] = ok && HIP_OK(hipEventRecord(p.rf_consumed[slot], p.stream));
 	}
 	if (!select_device(0)) ok = false;
@@ -1411,9 +1427,10 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 	if (multi && borrowed && d.pair_counter.ensure(sizeof(unsigned long long) * (kTimingSlots + 2)))
 		d.last_rf_sum_ready = HIP_OK(bf_launch_rf_checksum(data, rf_size, (unsigned long long *)d.pair_counter.ptr + kTimingSlots + 1, s));
 	if (multi && !run_peers(block, borrowed ? data : d.rf[slot].ptr, rf_size, slot)) return false;
-	/* what the first stage may read: a borrowed buffer's RF, else the whole RF slot */
-	bool done = borrowed ? run_frame(block, data, (int64_t)rf_size, true)
-	                     : run_frame(block, d.rf[slot].ptr, (int64_t)d.rf[slot].size, true);
+	/* what the first stage may read: this frame's RF -- not the whole RF slot, which behind it holds what a larger frame of three pushes
+	 * ago left there (a first stage that indexes past its RF -- the Reshape of a Decode-first pipeline that also demodulates -- reads
+	 * zeros, the same in every slot of the ring) */
+	bool done = run_frame(block, borrowed ? data : d.rf[slot].ptr, (int64_t)rf_size, true);
 	finish_upload(u, overlap, s);
 	/* a caller's device buffer read in place: the contract lets the caller overwrite it from work enqueued
 	 * later on the library's stream, so that stream also waits for the peer copies out of it */
@@ -1578,9 +1595,9 @@ static bool push_frames(uint32_t block, const PushGround &g, const void *data, b
 	note_push_time();
 	d.last_rf = (char *)d.rf[slot].ptr + (N - 1) * rf_stride; d.last_rf_bytes = l.rf_size; d.last_rf_slot = slot; d.last_rf_sum_ready = false;
 
-	/* ---- stages, one after the other over all RF frames.  What the first stage may read: of several frames each frame's RF itself (a
-	 * later stage: a stage buffer's frame with its slack), of one the whole RF slot ---- */
-	m.in = d.rf[slot].ptr; m.in_stride = rf_step; m.in_bound = (int64_t)(N > 1 ? l.rf_size : d.rf[slot].size);
+	/* ---- stages, one after the other over all RF frames.  What the first stage may read: each frame's RF itself (a later stage: what
+	 * the plan's stages can have written of a stage buffer's frame, plan.intermediate_bytes) ---- */
+	m.in = d.rf[slot].ptr; m.in_stride = rf_step; m.in_bound = (int64_t)l.rf_size;
 	m.t = &t;
 	const bool done = walk_plan(block, ps, m);
 	finish_upload(u, overlap, s);

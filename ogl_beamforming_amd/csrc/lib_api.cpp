@@ -1136,6 +1136,7 @@ uint32_t beamformer_hip_describe_plan(uint32_t parameter_slot, BeamformerHipPlan
 	out->das_samples = plan.das_samples; out->iq_pipeline = plan.iq_pipeline;
 	out->das_sampling_frequency = plan.das_sampling_frequency; out->das_time_offset = plan.das_time_offset;
 	std::memcpy(out->das_voxel_transform, plan.das_voxel_transform, sizeof(out->das_voxel_transform));
+	out->intermediate_bytes = plan.intermediate_bytes;
 	return 1;
 }
 

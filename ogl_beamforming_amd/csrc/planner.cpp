@@ -183,7 +183,7 @@ bool build_plan(const ParameterBlock &pb, Plan &plan, std::string &error, bool a
 	if (order.size() - 1 > BeamformerMaxComputeShaderStages) { error = "planned pipeline exceeds 16 stages"; return false; }
 
 	float time_offset = bp.time_offset;
-	size_t widest = 0;
+	uint64_t widest = 0;
 	for (size_t i = 1; i < order.size(); i++) {
 		const Node &n = order[i];
 		if (n.stand_in) continue;
@@ -265,10 +265,21 @@ bool build_plan(const ParameterBlock &pb, Plan &plan, std::string &error, bool a
 		default: break;
 		}
 		if (n.kind != BeamformerShaderKind_DAS && n.kind != BeamformerShaderKind_CoherencyWeighting) {
-			/* every pre-image buffer holds channels x transmits x das_samples elements; a
-			 * deinterleaving filter writes two real planes of that many elements */
-			size_t bytes = (size_t)C * A * samples * 8;
-			if (bytes > widest) widest = bytes;
+			/* The buffer a stage writes is as large as what it writes: (sum_k out_stride[k] (n[k] - 1) + 1) elements of
+			 * its output kind over n = (das_samples, channels, transmits); a deinterleaving filter writes a second real
+			 * plane channels x das_samples x transmits scalars further on (stages.hip: batch_sample_count).  channels x
+			 * transmits x das_samples x 8 bytes is NOT a bound: a stage between two don't-care neighbours inherits the
+			 * root's strides [1, S A, S], in elements of its own kind, and with them writes up to channels x transmits
+			 * x S x 8 bytes, S = 2 D das_samples after demodulation.  The kernels bound their reads (in_elements) and
+			 * nothing bounds their writes, so this is the bound.  tests/plan_fuzz.cpp and tests/pipeline_cases.py
+			 * restate the formula and hold every plan to it. */
+			typedef unsigned __int128 u128;      /* a stage behind DAS inherits the frame's strides: products of three 31-bit counts */
+			u128 last = (u128)st.out_stride[0] * (samples - 1) + (u128)st.out_stride[1] * (C - 1) + (u128)st.out_stride[2] * (A - 1);
+			const bool filter = n.kind == BeamformerShaderKind_Filter || n.kind == BeamformerShaderKind_Demodulate;
+			if (filter && bf_kind_complex[st.in_kind] && !bf_kind_complex[st.out_kind]) last += (u128)C * samples * A;
+			u128 bytes = (last + 1) * (u128)bf_kind_byte_size[st.out_kind];
+			if (bytes >= ((u128)1 << 32)) { error = "an inter-stage buffer exceeds 4 GiB"; return false; }
+			if ((uint64_t)bytes > widest) widest = (uint64_t)bytes;
 		}
 		plan.stages.push_back(std::move(st));
 	}

@@ -131,11 +131,16 @@ __global__ __launch_bounds__(256) void reshape_kernel(const BfReshapeArgs a, con
 		c[order.axis[2]] = (uint32_t)(id / ((uint64_t)n0 * n1));
 		int64_t in_index  = a.in_stride[0]  * c[0] + a.in_stride[1]  * c[1] + a.in_stride[2]  * c[2];
 		int64_t out_index = a.out_stride[0] * c[0] + a.out_stride[1] * c[1] + a.out_stride[2] * c[2];
-		f32x2 v;
+		/* A pipeline that starts with Decode and also demodulates walks the RF with the root's strides [1, S A, S] counted in complex
+		 * elements: twice the RF's length.  What lies past the input reads as zero, as in the filters (the reference reads whatever
+		 * its RF ring holds there). */
+		f32x2 v = {0.f, 0.f};
 		if (a.interleave) {
-			v.x = load_element(a.in_kind, left,  in_index).x;
-			v.y = load_element(a.in_kind, right, in_index).x;
-		} else {
+			if (in_index < a.in_elements - (int64_t)total) {
+				v.x = load_element(a.in_kind, left,  in_index).x;
+				v.y = load_element(a.in_kind, right, in_index).x;
+			}
+		} else if (in_index < a.in_elements) {
 			v = load_element(a.in_kind, left, in_index);
 		}
 		store_element(a.out_kind, out, out_index, v);

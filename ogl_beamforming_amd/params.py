@@ -379,7 +379,7 @@ class HipPlan(C.Structure):
     _fields_ = [("stage_count", C.c_uint32), ("stages", HipPlanStage * MAX_STAGES),
                 ("das_samples", C.c_uint32), ("iq_pipeline", C.c_uint32),
                 ("das_sampling_frequency", C.c_float), ("das_time_offset", C.c_float),
-                ("das_voxel_transform", C.c_float * 16)]
+                ("das_voxel_transform", C.c_float * 16), ("intermediate_bytes", C.c_uint64)]
 
 
 class HipZbpPayload(C.Structure):

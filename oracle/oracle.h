@@ -76,6 +76,7 @@ typedef struct {
 	int   in_stride[3], out_stride[3];
 	int   in_kind, out_kind;  /* BeamformerDataKind */
 	int   interleave;         /* reshape.glsl:71-75 */
+	int64_t in_elements;      /* elements of in_kind readable from `left` (reads beyond give 0; 0: unbounded) */
 } OracleReshape;
 void oracle_reshape(const OracleReshape *r, const void *left, const void *right, void *out);
 

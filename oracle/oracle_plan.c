@@ -258,6 +258,14 @@ static void run_stage(Exec *e, int slot, int channel_offset, const uint8_t *rf_p
 	uint8_t *pp_out = e->ping_pong + e->slot_bytes * (size_t)output_index;
 	uint8_t *pp_das = e->ping_pong + e->slot_bytes * (size_t)das_output_index;
 
+	/* Filter and Demodulate read windows of consecutive elements wherever their row starts put them, also elements their
+	 * predecessor does not write (the second half of every row of a root-layout buffer after demodulation, a decimated row's
+	 * tail).  The reference finds there what an earlier stage of this or the last frame left in the slot; the library defines such
+	 * elements as zero (csrc/executor.cpp walk_plan), and so does the checker: a stage's output slot is cleared before it writes. */
+	if (st->kind == BeamformerShaderKind_Decode || st->kind == BeamformerShaderKind_Filter || st->kind == BeamformerShaderKind_Demodulate ||
+	    st->kind == BeamformerShaderKind_Hilbert || st->kind == BeamformerShaderKind_Reshape)
+		memset((slot + 1) == das_index ? pp_das : pp_out, 0, e->slot_bytes);
+
 	switch (st->kind) {
 	case BeamformerShaderKind_Decode:{
 		OracleDecode d = {0};
@@ -319,6 +327,7 @@ static void run_stage(Exec *e, int slot, int channel_offset, const uint8_t *rf_p
 		r.in_kind = st->in_kind; r.out_kind = st->out_kind;
 		r.interleave = !kind_complex[st->in_kind] && kind_complex[st->out_kind];        /* :961-965 */
 		const uint8_t *left  = slot == 0 ? rf_pointer : pp_in;                          /* :1381-1386 */
+		r.in_elements = slot == 0 ? rf_elements_left : (int64_t)(e->slot_bytes / (size_t)kind_byte_size[st->in_kind]);
 		const uint8_t *right = left + (size_t)r.size[0] * Cc * r.size[2] * (size_t)kind_byte_size[st->in_kind];
 		oracle_reshape(&r, left, right, (slot + 1) == das_index ? pp_das : pp_out);
 		e->input_index = !e->input_index;

@@ -95,6 +95,13 @@ void oracle_reshape(const OracleReshape *r, const void *left, const void *right,
 				int64_t in_index  = (int64_t)r->in_stride[0]  * x + (int64_t)r->in_stride[1]  * y + (int64_t)r->in_stride[2]  * z;
 				int64_t out_index = (int64_t)r->out_stride[0] * x + (int64_t)r->out_stride[1] * y + (int64_t)r->out_stride[2] * z;
 				float v[2] = {0, 0}, t[2];
+				int64_t planes = r->interleave ? (int64_t)r->size[0] * r->size[1] * r->size[2] : 0;
+				if (r->in_elements && in_index >= r->in_elements - planes) {
+					/* past the input: zero (a Decode-first pipeline that also demodulates walks the RF with the root's
+					 * strides in complex elements -- twice its length; the reference reads what its RF ring holds there) */
+					store_element(r->out_kind, out, out_index, v);
+					continue;
+				}
 				if (r->interleave) {
 					load_element(r->in_kind, left,  in_index, t); v[0] = t[0];
 					load_element(r->in_kind, right, in_index, t); v[1] = t[0];

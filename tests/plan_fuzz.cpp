@@ -22,6 +22,23 @@ static float fpick()
 	return rng() % 3 ? v[rng() % (sizeof v / sizeof *v)] : (float)((double)(rng() % 2000000) / 1000.0 - 1000.0);
 }
 
+/* One past the last byte a stage that the executor launches into an inter-stage buffer writes there: its output strides over
+ * n = (das_samples, channels, transmits) elements of its output kind; a filter that takes complex samples and stores real ones writes a
+ * second plane channels x das_samples x transmits scalars further on (stages.hip: batch_sample_count).  The executor allocates
+ * plan.intermediate_bytes (+ 64) per buffer and nothing bounds a kernel's writes: the plan has to.  tests/pipeline_cases.py restates
+ * this for the plans of the C ABI. */
+static uint64_t write_extent(const bf::Plan &plan, const bf::Stage &st)
+{
+	static const uint64_t kind_bytes[6] = {2, 4, 4, 8, 2, 4};
+	static const bool     kind_complex[6] = {false, true, false, true, false, true};
+	uint64_t last = (uint64_t)st.out_stride[0] * (plan.das_samples - 1) + (uint64_t)st.out_stride[1] * (plan.channels - 1)
+	              + (uint64_t)st.out_stride[2] * (plan.acquisitions - 1);
+	bool filter = st.kind == BeamformerShaderKind_Filter || st.kind == BeamformerShaderKind_Demodulate;
+	if (filter && kind_complex[st.in_kind] && !kind_complex[st.out_kind])
+		last += (uint64_t)plan.channels * plan.das_samples * plan.acquisitions;
+	return (last + 1) * kind_bytes[st.out_kind];
+}
+
 int main(int argc, char **argv)
 {
 	long rounds = argc > 1 ? std::atol(argv[1]) : 20000;
@@ -85,8 +102,19 @@ int main(int argc, char **argv)
 		bool ok = plan.channels >= 1 && plan.channels <= 256 && plan.acquisitions >= 1 && plan.acquisitions <= 256 && plan.das_samples >= 1;
 		ok = ok && plan.stages.size() <= 2 * BeamformerMaxComputeShaderStages + 2;
 		ok = ok && (uint64_t)plan.channels * plan.acquisitions * plan.das_samples * (plan.iq_pipeline ? 8 : 4) < (1ull << 32);   /* 32-bit byte offsets in the DAS kernels */
+		ok = ok && (uint64_t)plan.intermediate_bytes < (1ull << 32);
 		for (const bf::Stage &st : plan.stages) {
 			ok = ok && st.in_kind >= 0 && st.in_kind <= 5 && st.out_kind >= 0 && st.out_kind <= 5;
+			if (ok && st.kind != BeamformerShaderKind_DAS && st.kind != BeamformerShaderKind_CoherencyWeighting) {
+				/* no stage writes past the buffer the executor allocates for it */
+				uint64_t extent = write_extent(plan, st);
+				if (extent > plan.intermediate_bytes) {
+					std::fprintf(stderr, "stage %d (kinds %d->%d, out strides %lld %lld %lld) writes %llu bytes into a buffer of %zu\n", st.kind, st.in_kind,
+					             st.out_kind, (long long)st.out_stride[0], (long long)st.out_stride[1], (long long)st.out_stride[2],
+					             (unsigned long long)extent, plan.intermediate_bytes);
+					ok = false;
+				}
+			}
 			if (st.kind == BeamformerShaderKind_DAS) {
 				uint32_t support = bp.interpolation_mode == 2 ? 4u : bp.interpolation_mode == 1 ? 2u : 1u;
 				ok = ok && plan.das_samples >= support;

@@ -8,7 +8,9 @@ Bars:
   * bit-identical (uint32 view) wherever the arithmetic is exact: ingest, channel map, A1S2, Reshape, int/f16 -> f32
     conversion, and Int16 RF decoded before any filter (integer partial sums below 2^24, one identical division);
   * elsewhere |gpu - oracle| <= bar, a forward-error bound propagated stage by stage in float64 from the stage's input
-    magnitudes (stage_bounds below).  Each case prints its largest err / bar."""
+    magnitudes (stage_bounds below).  Each case prints its largest err / bar.  Every Filter / Demodulate stage takes its taps from
+    its own filter slot (the oracle's plan names it); an Int16 store adds 1 in the stored unit (I16_STORE).
+tests/pipeline_cases.py and tests/test_gpu_pipelines.py carry the same bars to the pipelines these cases never plan."""
 import ctypes as C
 import math
 
@@ -32,6 +34,14 @@ U16 = 2.0 ** -11          # ... of binary16
 K_SAMPLE = 6
 # Binary16 store of a stage output: one rounding of values already within the propagated bound of each other.
 K_STORE = 2
+# Int16 / Int16Complex store of a stage output: a truncation toward zero (stages.hip store_scalar, GLSL's int16_t(v)).  Two
+# evaluations within e of each other store integers within e + 1 -- |trunc(a) - trunc(b)| < |a - b| + 1 -- so the store adds 1, in the
+# stored unit, to the bar.  Derived, not measured.  Where the value stored is an exactly computed integer (a Reshape's copy, a Decode
+# of exact integers: partial sums below 2^24, one identical division) both builds truncate the same number and nothing is added.
+I16_STORE = 1.0
+# ... and a float outside the int16 range converts differently on host and device: every Int16-stored stage's magnitude bound
+# stays below half the range (the cases divide their Int16 RF by 8 for it)
+I16_RANGE = 16384.0
 
 
 def k_sum(n):
@@ -41,16 +51,19 @@ def k_sum(n):
 
 # ------------------------------------------------------------------------------------------------ running a case
 
-def filter_taps(oracle, fp):
+def filter_taps(oracle, fp, real_samples=False):
     """(magnitude per tap |hr| + |hi| or |h|, length, complex_filter) exactly as both builds read the taps (Q7: complex taps only
-    for a matched chirp)"""
+    for a matched chirp).  real_samples: the stage filters real samples without demodulating them -- of complex taps only the real
+    parts enter (filter.glsl's real SAMPLE_TYPE reads coefficients[2 j]), so the magnitude per tap is |hr|."""
     from oracle.binding import library
     buf = np.zeros(8192, np.float32)
     delay = C.c_float(0)
     L = library().oracle_filter_create(C.byref(fp), buf.ctypes.data_as(C.POINTER(C.c_float)), 8192, C.byref(delay))
     assert L > 0
     complex_filter = bool(fp.complex) and fp.kind == int(P.FilterKind.MatchedChirp)
-    if complex_filter:
+    if complex_filter and real_samples:
+        h = np.abs(buf[0:2 * L:2].astype(np.float64))
+    elif complex_filter:
         h = np.abs(buf[0:2 * L:2].astype(np.float64)) + np.abs(buf[1:2 * L:2].astype(np.float64))
     else:
         h = np.abs(buf[:L].astype(np.float64))
@@ -90,7 +103,7 @@ def mapped_rf_magnitudes(acq):
     return rows[:, :row].reshape(-1)
 
 
-def stage_bounds(bflib, oracle, acq, plan):
+def stage_bounds(bflib, oracle, acq, plan, trace=None):
     """Walks the library's plan over scalar buffers and returns (exact, magnitude, bar) of the DAS input, both (C, A, Sd)
     arrays: `magnitude` bounds |value| (|re| + |im| for complex), `bar` the distance two faithful evaluations can have.
     exact: every stage on the way is exact arithmetic (then the comparison is bit-identical)."""
@@ -108,28 +121,49 @@ def stage_bounds(bflib, oracle, acq, plan):
         return buf[0::2] + buf[1::2] if kind & 1 else buf
 
     def scatter(size_elements, kind, index, values_mag, values_err):
+        # A complex element's magnitude and error are bounds on |re| + |im| and on |d re| + |d im|: with taps h = hr + i hi,
+        # |out re| + |out im| <= sum (|hr| + |hi|) (|x re| + |x im|), and a real operation (Decode, real taps) keeps the two parts apart.
+        # Each of the element's two scalars holds half of the bound, so that `elements` returns it -- not twice it -- to the next
+        # stage; one scalar alone is bounded by the element's whole bound, which is what the DAS input is judged by below.
         n = 2 if kind & 1 else 1
         m = np.zeros(size_elements * n)
         e = np.zeros(size_elements * n)
         for k in range(n):
-            m[n * index + k] = values_mag
-            e[n * index + k] = values_err
+            m[n * index + k] = values_mag / n
+            e[n * index + k] = values_err / n
         return m, e
 
-    das_index = [int(plan.stages[i].kind) for i in range(plan.stage_count)].index(int(S.DAS))
+    kinds = [int(plan.stages[i].kind) for i in range(plan.stage_count)]
+    das_index = kinds.index(int(S.DAS))
+    # the filter slot of every stage comes from the oracle's plan (the library's describe call does not carry it): first the two plans
+    # must list the same stages, as tests/test_host_logic.py's test_planner_agrees_with_oracle asks of the named cases
+    ref_plan = oracle.plan(bp, acq.filters)
+    assert ref_plan is not None, "the oracle cannot plan this pipeline"
+    assert [int(ref_plan.stages[i].kind) for i in range(ref_plan.stage_count)] == kinds, "the library's and the oracle's plans list different stages"
     for i in range(das_index):
         st = plan.stages[i]
         kind = int(st.kind)
+        assert (int(ref_plan.stages[i].in_kind), int(ref_plan.stages[i].out_kind)) == (int(st.in_kind), int(st.out_kind)), (i, kind)
         ist, ost = [int(v) for v in st.in_stride], [int(v) for v in st.out_stride]
         in_m, in_e = elements(mag, st.in_kind), elements(err, st.in_kind)
         out_f16 = (st.out_kind >> 1) == 2
+        out_i16, in_i16 = (st.out_kind >> 1) == 0, (st.in_kind >> 1) == 0
         if kind == int(S.Reshape):
             assert not (not (st.in_kind & 1) and (st.out_kind & 1)), "interleaving Reshape: not modelled"
             src = ist[0] * n_s + ist[1] * n_ch + ist[2] * n_tx
             dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
             if out_f16 and not integer:
                 exact = False
-            mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, in_m[src], in_e[src] + (K_STORE * U16 * in_m[src] if out_f16 else 0))
+            # past the end of its input a Reshape reads zeros, as the filters do (in_elements; a Decode-first pipeline that also
+            # demodulates walks the RF with the root's strides in complex elements, twice the RF's length)
+            inside = src < len(in_m)
+            src_m = np.where(inside, in_m[np.minimum(src, len(in_m) - 1)], 0.0)
+            src_e = np.where(inside, in_e[np.minimum(src, len(in_m) - 1)], 0.0)
+            store = K_STORE * U16 * src_m if out_f16 else 0
+            if out_i16 and not in_i16:                                      # a converting Reshape truncates; Int16 -> Int16 copies
+                assert src_m.max() < I16_RANGE, f"stage {i}: Int16 store of magnitudes up to {src_m.max():.0f}"
+                exact, store = False, I16_STORE * (2 if st.out_kind & 1 else 1)
+            mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, src_m, src_e + store)
         elif kind == int(S.Decode):
             T = A
             src = ((n_s * Cn + n_ch) * T)[:, 0, :]                          # (C, Sd): element j at + j (decode kernel layout)
@@ -138,14 +172,20 @@ def stage_bounds(bflib, oracle, acq, plan):
             if not integer:                                                 # integer partial sums: exact, one identical division
                 exact = False
                 E = E + k_sum(T) * (U16 if out_f16 else U32) * M
-            integer = False
+                if out_i16:
+                    E = E + I16_STORE * (2 if st.out_kind & 1 else 1)
+            if out_i16:
+                assert M.max() < I16_RANGE, f"stage {i}: Int16 store of magnitudes up to {M.max():.0f}"
+            # an exact Decode stored as Int16 holds exactly computed integers again (both builds truncate the one quotient)
+            integer = integer and out_i16
             dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
             mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, np.broadcast_to(M[:, None, :], dst.shape),
                                np.broadcast_to(E[:, None, :], dst.shape))
         elif kind in (int(S.Filter), int(S.Demodulate)):
             demod = kind == int(S.Demodulate)
-            assert len(acq.filters) == 1
-            h, L, complex_filter = filter_taps(oracle, acq.filters[0])
+            slot = int(ref_plan.stages[i].filter_slot) % P.FILTER_SLOTS
+            assert slot < len(acq.filters) and acq.filters[slot] is not None, f"stage {i} reads filter slot {slot}: the case sets none"
+            h, L, complex_filter = filter_taps(oracle, acq.filters[slot], real_samples=not demod and not st.in_kind & 1)
             D = max(1, int(bp.decimation_rate)) if demod else 1
             f16 = (st.in_kind >> 1) != 1
             scale = 1.0
@@ -172,10 +212,23 @@ def stage_bounds(bflib, oracle, acq, plan):
                     seg_e = np.where(ok, in_e[np.clip(idx, 0, n_el - 1)], 0.0)
                     M[c, t, :keep] = scale * np.correlate(seg_m, h, "valid")[::D][:keep]
                     E[c, t, :keep] = scale * np.correlate(seg_e, h, "valid")[::D][:keep]
+                    # filter.glsl:79: a 64-output group whose window would start before its row (D x group x 64 < L - 1) reads zeros
+                    # for the window's first L - 1 entries -- not what lies in front of the row start.  The bound follows: a row that
+                    # starts inside the buffer (decode layout, a halved row start) takes nothing from the elements before it there
+                    for wg in range((keep + 63) // 64):
+                        if D * wg * 64 >= L - 1:
+                            break
+                        front = idx < row_start + D * wg * 64
+                        group = slice(wg * 64, min(keep, wg * 64 + 64))
+                        M[c, t, group] = scale * np.correlate(np.where(front, 0.0, seg_m), h, "valid")[::D][group]
+                        E[c, t, group] = scale * np.correlate(np.where(front, 0.0, seg_e), h, "valid")[::D][group]
             u_in = U16 if f16 else U32
             E = E + ((K_SAMPLE * u_in if demod else 0.0) + k_sum(terms) * U32) * M
             if out_f16:
                 E = E + K_STORE * U16 * M
+            if out_i16:
+                assert M.max() < I16_RANGE, f"stage {i}: Int16 store of magnitudes up to {M.max():.0f}"
+                E = E + I16_STORE * (2 if st.out_kind & 1 else 1)      # both scalars of a complex element truncate
             exact = integer = False
             dst = ost[0] * n_s + ost[1] * n_ch + ost[2] * n_tx
             if st.in_kind & 1 and not (st.out_kind & 1):                    # deinterleaving store: re, then im a batch later
@@ -208,11 +261,13 @@ def stage_bounds(bflib, oracle, acq, plan):
             mag, err = scatter(int(dst.max()) + 1, st.out_kind, dst, M, E)
         else:
             raise AssertionError(f"stage kind {kind} not modelled")
+        if trace is not None:                                               # (stage, out kind, median magnitude bound, median bar) of what it wrote
+            live = mag > 0
+            trace.append((kind, int(st.out_kind), float(np.median(mag[live])) if live.any() else 0.0, float(np.median(err[live])) if live.any() else 0.0))
     das = plan.stages[das_index]
     ist = [int(v) for v in das.in_stride]
     src = ist[0] * n_s + ist[1] * n_ch + ist[2] * n_tx
-    per_scalar = (lambda b: np.maximum(b[0::2], b[1::2])) if das.in_kind & 1 else (lambda b: b)
-    return exact, elements(mag, das.in_kind)[src], per_scalar(err)[src]
+    return exact, elements(mag, das.in_kind)[src], elements(err, das.in_kind)[src]
 
 
 def oracle_run(oracle, acq):
