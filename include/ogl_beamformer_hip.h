@@ -673,6 +673,41 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_clutter_projector(const double *gr
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_mix_last_frames(uint32_t count, const float *weights, uint32_t out_count,
                                                               uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms);
 
+/* ---- slow-time autocorrelation of an ensemble: the per-voxel reduction ACROSS the frames, behind the filter above.  Lag 0 is the power
+ * Doppler image of the filtered ensemble, lag 1 the Kasai estimate (its angle is the axial velocity: v = angle(R_1) c PRF / (4 pi f0),
+ * the angle is the caller's), lags 0 and 1 together the variance.  The filter is whatever weight table the caller would hand to
+ * beamformer_hip_mix_last_frames, under the same definition; the filtered frames are never stored ----
+ * DEFINITION (tests/autocorr_ref.py restates it in numpy).
+ * SOURCES.  The `count` = K newest frames of the ring, of one grid and one kind: beamformer_hip_mix_last_frames' rules.  Index 0 is the
+ * oldest frame.
+ * FILTERED SAMPLES.  weights[rows][count][2] floats.  y_n[v] = sum over k of W[n][k] f_k[v], n = 0 .. rows - 1: each float is exactly the
+ * float32 fmaf chain of MIX above -- the same order, the same signs, no weight skipped --, so y_n is bit for bit what
+ * beamformer_hip_mix_last_frames would have stored.  weights == NULL is the identity: y_n = f_n, and rows must equal count (an ensemble
+ * that is filtered already, or no filter at all).
+ * LAG PRODUCTS.  For L = 0 .. lag_count - 1: R_L[v] = sum over n = 0 .. rows - 1 - L of conj(y_n[v]) y_{n+L}[v].  Each output float is
+ * ONE float32 fmaf chain from +0 in ascending n --
+ *     real:       acc = fmaf(yr_n, yr_{n+L}, acc), then acc = fmaf( yi_n, yi_{n+L}, acc)
+ *     imaginary:  acc = fmaf(yr_n, yi_{n+L}, acc), then acc = fmaf(-yi_n, yr_{n+L}, acc)
+ * -- but the imaginary part of lag 0, which is no chain (it would leave rounding residue): it is stored as 0 * re(R_0), exactly +0
+ * where that real part is finite and NaN where it is not.  Real frames run acc = fmaf(y_n, y_{n+L}, acc) only.  Plain IEEE otherwise:
+ * a voxel that is not finite in some source frame is not finite in every output float.
+ * OUTPUTS.  lag_count new frames of the sources' grid and kind, lag 0 first, placed in the ring as ONE contiguous run exactly as
+ * beamformer_hip_mix_last_frames places its run: the same ids from the counters a push advances, the newest source's parameter block,
+ * the call's image_plane_tag, rows of the timing table that report no stages and 0 DAS voxels, the same treatment of the record of the
+ * newest multi-frame push.  beamformer_hip_find_peaks_last_frames, beamformer_hip_score_last_frames, beamformer_hip_copy_frame,
+ * beamformer_hip_get_frame_info and beamformer_get_last_frames work on them unchanged.  *first_frame_id (may be NULL): the id of lag 0.
+ * One launch (csrc/autocorr.hip), enqueued on the current stream behind the frames it reads; the call does not synchronise unless
+ * device_ms is not NULL (then: the time between two events around the launch).
+ * Refusals, all decided BEFORE ANYTHING CHANGES and leaving every output unwritten: count or rows 0 or
+ * > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES: BufferOverflow; lag_count 0, > BEAMFORMER_HIP_MAX_LAGS or > rows, weights == NULL with
+ * rows != count, a weight that is not finite, a nonzero imaginary weight on real frames: InvalidAccess; frames that differ in grid or
+ * kind: DataSizeMismatch; a run of lag_count frames that does not fit the ring, or that would reuse storage of one of its own count
+ * source frames: FrameSizeOverflow; and everything beamformer_hip_score_last_frames refuses (InvalidAccess). */
+#define BEAMFORMER_HIP_MAX_LAGS 4u
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows,
+                                                                        uint32_t lag_count, uint32_t image_plane_tag,
+                                                                        uint32_t *first_frame_id, float *device_ms);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

@@ -432,6 +432,15 @@ typedef struct {
 	uint64_t out_offset, out_stride;   /* the first output frame in the ring, bytes; from one output to the next */
 } BfMixArgs;
 
+/* ---- slow-time autocorrelation (autocorr.hip: beamformer_hip_autocorrelate_last_frames) ---- */
+#define BF_AUTOCORR_MAX_LAGS   4u            /* = BEAMFORMER_HIP_MAX_LAGS: a chain reaches 3 rows back, carried across a tile boundary */
+typedef struct {
+	uint32_t frames, rows;       /* K source frames, the rows of the weight table (the identity form: rows == frames) */
+	uint32_t lags, cplx;         /* output frames, lag 0 first; 1: Float32Complex, 0: Float32 */
+	uint64_t elements;           /* a frame's complex voxels (cplx) or floats */
+	uint64_t out_offset, out_stride;   /* the lag 0 frame in the ring, bytes; from one lag to the next */
+} BfAutocorrArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -492,6 +501,10 @@ hipError_t bf_launch_gram(const void *ring, const uint64_t *offsets, const BfGra
 /* ensemble.hip, the mix: one launch.  weights[padded_outputs][frames][2] floats (real frames: the imaginary ones are not read) and
  * offsets[frames] are device memory; output j is written at ring + out_offset + j * out_stride */
 hipError_t bf_launch_mix(void *ring, const uint64_t *offsets, const float *weights, const BfMixArgs *a, hipStream_t s);
+/* autocorr.hip: one launch.  weights: the mix's table of `rows` rows, [ceil(rows / BF_MIX_TILE)][frames][BF_MIX_TILE][2] floats, rows past
+ * `rows` zero -- or NULL, the identity form (rows == frames: row n is source frame n).  Lag l is written at ring + out_offset +
+ * l * out_stride */
+hipError_t bf_launch_autocorr(void *ring, const uint64_t *offsets, const float *weights, const BfAutocorrArgs *a, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

@@ -78,7 +78,7 @@ struct PushRecord {
 	BeamformerHipVariantsDescription variants{};        /* Variants: its route */
 	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
-	uint32_t      mixed = 0;                  /* frames that mix_last_frames has queued behind the push: the push stays "the newest push" behind them */
+	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames have queued behind the push: the push stays "the newest push" behind them */
 };
 
 struct PlanState {
@@ -174,7 +174,7 @@ struct Device {
 	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
 	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
 	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
-	DeviceBuffer mix_table;                                    /* mix_last_frames: the source frames' ring offsets and the weight table of a call (ensemble.hip) */
+	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames: the source frames' ring offsets and the weight table of a call (ensemble.hip, autocorr.hip) */
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
 	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
 	bool         mix_copy_pending = false;
@@ -287,6 +287,8 @@ bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms);
 bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id,
                      float *device_ms);                            /* arguments checked by the caller (lib_api.cpp), but for what needs the frames' kind */
+bool autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows, uint32_t lag_count, uint32_t image_plane_tag,
+                               uint32_t *first_frame_id, float *device_ms);   /* likewise; weights null: the identity form, rows == count */
 const FrameRecord *record_of(const Device &d, uint32_t frame_id);   /* null: no such frame, a tombstone, or storage that a newer frame reused */
 bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
 bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);

@@ -31,8 +31,7 @@
  * output rows past M (zero rows of the weight table) are not stored. */
 #include <hip/hip_runtime.h>
 #include "bf_kernels.h"
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "mix_term.h"
 
 namespace {
 
@@ -171,19 +170,10 @@ __global__ __launch_bounds__(256) void mix_kernel(char *ring, const uint64_t *__
 	for (uint32_t j = 0; j < BF_MIX_TILE; j++) { re[j] = 0.0f; im[j] = 0.0f; }
 	for (uint32_t k = 0; k < a.frames; k++, w += 2u * BF_MIX_TILE) {
 		const char *frame = ring + offsets[k];
-		if (CPLX) {
-			const f32x2 c = ((const f32x2 *)frame)[e];
-			#pragma unroll
-			for (uint32_t j = 0; j < BF_MIX_TILE; j++) {
-				const float wr = w[2u * j], wi = w[2u * j + 1u];
-				re[j] = __builtin_fmaf(wr, c.x, re[j]); re[j] = __builtin_fmaf(-wi, c.y, re[j]);
-				im[j] = __builtin_fmaf(wi, c.x, im[j]); im[j] = __builtin_fmaf(wr, c.y, im[j]);
-			}
-		} else {
-			const float c = ((const float *)frame)[e];
-			#pragma unroll
-			for (uint32_t j = 0; j < BF_MIX_TILE; j++) re[j] = __builtin_fmaf(w[2u * j], c, re[j]);
-		}
+		f32x2 c;
+		if (CPLX) c = ((const f32x2 *)frame)[e];
+		else      { c.x = ((const float *)frame)[e]; c.y = 0.0f; }
+		mix_term<CPLX>(re, im, c, w);
 	}
 	char *out = ring + a.out_offset + (uint64_t)tile * BF_MIX_TILE * a.out_stride;
 	#pragma unroll

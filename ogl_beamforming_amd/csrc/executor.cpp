@@ -2660,10 +2660,17 @@ bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, do
 	return true;
 }
 
-/* beamformer_hip_mix_last_frames: out_count linear combinations of the `count` newest frames, queued as frames of their own
- * (ensemble.hip).  Everything that can refuse is decided, and every buffer grown, before the ids are taken; nothing synchronises unless
- * device_ms is asked for. */
-bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
+namespace {
+
+/* What beamformer_hip_mix_last_frames and beamformer_hip_autocorrelate_last_frames share: `out_count` frames computed from the `count`
+ * newest ones under a weight table of `rows` rows (null: no table -- the caller's launch reads the sources as they are) and queued as
+ * frames of their own behind them.  Everything that can refuse is decided, and every buffer grown, before the ids are taken; nothing
+ * synchronises unless device_ms is asked for.  launch(ring, offsets, table, K, cplx, elements, out_offset, out_stride, stream): the call's
+ * one kernel launch -- the sources' ring offsets and the table [tile][k][BF_MIX_TILE][2] (rows past `rows` zero; null without weights) in
+ * device memory, output j at ring + out_offset + j * out_stride. */
+template <class Launch>
+bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows, uint32_t out_count, uint32_t image_plane_tag,
+                            uint32_t *first_frame_id, float *device_ms, Launch launch)
 {
 	Context &c = g_context;
 	std::vector<BoxedFrame> boxed;
@@ -2671,8 +2678,8 @@ bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, u
 	Device &d = c.devices[0];
 	const FrameRecord newest = *boxed[count - 1].record;      /* (a copy: the run's records may take its place) */
 	const bool cplx = boxed[0].cplx;
-	if (!cplx)
-		for (size_t n = 0; n < (size_t)out_count * count; n++)
+	if (!cplx && weights)
+		for (size_t n = 0; n < (size_t)rows * count; n++)
 			if (weights[2 * n + 1] != 0.0f) return set_error(BeamformerLibErrorKind_InvalidAccess);
 
 	/* where the ring's placement rule will put the run, and whether that reuses storage of a source frame */
@@ -2684,8 +2691,8 @@ bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, u
 	for (const BoxedFrame &b : boxed)
 		if (b.record->offset < run_first + run_bytes && run_first < b.record->offset + b.record->bytes) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 
-	/* the table: offsets[K] | weights[tile][k][BF_MIX_TILE][2], rows past M zero */
-	const uint32_t padded = (M + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
+	/* the table: offsets[K] | weights[tile][k][BF_MIX_TILE][2], rows past `rows` zero */
+	const uint32_t padded = weights ? (rows + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE : 0u;
 	const size_t offsets_bytes = round_up(sizeof(uint64_t) * K, 64), weights_bytes = sizeof(float) * 2 * padded * K;
 	const size_t table_max = round_up(sizeof(uint64_t) * BF_ENSEMBLE_MAX_FRAMES, 64) + sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES;
 	bool ok = HIP_OK(hipSetDevice(d.device));
@@ -2701,7 +2708,7 @@ bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, u
 	for (uint32_t n = 0; n < K; n++) offsets[n] = boxed[n].record->offset;
 	float *table = (float *)(pinned + offsets_bytes);
 	std::memset(table, 0, weights_bytes);
-	for (uint32_t j = 0; j < M; j++)
+	for (uint32_t j = 0; j < rows && weights; j++)
 		for (uint32_t k = 0; k < K; k++) {
 			float *w = table + (((size_t)(j / BF_MIX_TILE) * K + k) * BF_MIX_TILE + j % BF_MIX_TILE) * 2;
 			w[0] = weights[((size_t)j * K + k) * 2]; w[1] = weights[((size_t)j * K + k) * 2 + 1];
@@ -2730,15 +2737,13 @@ bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, u
 	}
 	d.have_sample = false;              /* the slots of older sampled frames may be gone: a single frame that follows records its own events */
 
-	BfMixArgs a{};
-	a.frames = K; a.outputs = M; a.cplx = cplx; a.padded_outputs = padded;
-	a.elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
-	a.out_offset = frame0->offset; a.out_stride = frame0->bytes;
+	const uint64_t elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
 	ok &= HIP_OK(hipMemcpyAsync(d.mix_table.ptr, pinned, offsets_bytes + weights_bytes, hipMemcpyHostToDevice, s));
 	d.mix_copy_pending = HIP_OK(hipEventRecord(d.mix_copied, s));
 	ok &= d.mix_copy_pending;
 	if (device_ms) ok &= HIP_OK(hipEventRecord(d.mix_begin, s));
-	if (ok) ok &= HIP_OK(bf_launch_mix(d.ring.ptr, (const uint64_t *)d.mix_table.ptr, (const float *)((const char *)d.mix_table.ptr + offsets_bytes), &a, s));
+	if (ok) ok &= HIP_OK(launch(d.ring.ptr, (const uint64_t *)d.mix_table.ptr, weights ? (const float *)((const char *)d.mix_table.ptr + offsets_bytes) : nullptr, K, cplx,
+	                            elements, frame0->offset, frame0->bytes, s));
 	if (device_ms) {
 		ok &= HIP_OK(hipEventRecord(d.mix_end, s));
 		ok &= HIP_OK(hipStreamSynchronize(s));
@@ -2749,6 +2754,36 @@ bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, u
 	if (first_frame_id) *first_frame_id = (uint32_t)first;
 	lockstep.complete = true;
 	return true;
+}
+
+} // namespace
+
+/* beamformer_hip_mix_last_frames: out_count linear combinations of the `count` newest frames, queued as frames of their own
+ * (ensemble.hip) */
+bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
+{
+	return queue_frames_of_newest(count, weights, out_count, out_count, image_plane_tag, first_frame_id, device_ms,
+		[=](void *ring, const uint64_t *offsets, const float *table, uint32_t K, bool cplx, uint64_t elements, uint64_t out_offset, uint64_t out_stride, hipStream_t s) {
+			BfMixArgs a{};
+			a.frames = K; a.outputs = out_count; a.cplx = cplx; a.padded_outputs = (out_count + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
+			a.elements = elements; a.out_offset = out_offset; a.out_stride = out_stride;
+			return bf_launch_mix(ring, offsets, table, &a, s);
+		});
+}
+
+/* beamformer_hip_autocorrelate_last_frames: lags 0 .. lag_count - 1 of the slow-time autocorrelation of `rows` mixes of the `count`
+ * newest frames (weights null: of those frames themselves), queued as lag_count frames of their own (autocorr.hip) */
+bool autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows, uint32_t lag_count, uint32_t image_plane_tag,
+                               uint32_t *first_frame_id, float *device_ms)
+{
+	static_assert(BF_AUTOCORR_MAX_LAGS == BEAMFORMER_HIP_MAX_LAGS, "one limit");
+	return queue_frames_of_newest(count, weights, rows, lag_count, image_plane_tag, first_frame_id, device_ms,
+		[=](void *ring, const uint64_t *offsets, const float *table, uint32_t K, bool cplx, uint64_t elements, uint64_t out_offset, uint64_t out_stride, hipStream_t s) {
+			BfAutocorrArgs a{};
+			a.frames = K; a.rows = rows; a.lags = lag_count; a.cplx = cplx;
+			a.elements = elements; a.out_offset = out_offset; a.out_stride = out_stride;
+			return bf_launch_autocorr(ring, offsets, table, &a, s);
+		});
 }
 
 /* The record of the frame with this id, while the frame is still there: its record not yet overwritten (the newest frames.size() ids),

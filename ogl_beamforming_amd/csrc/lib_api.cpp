@@ -1040,6 +1040,18 @@ uint32_t beamformer_hip_mix_last_frames(uint32_t count, const float *weights, ui
 	return mix_last_frames(count, weights, out_count, image_plane_tag, first_frame_id, device_ms);
 }
 
+uint32_t beamformer_hip_autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows, uint32_t lag_count, uint32_t image_plane_tag,
+                                                  uint32_t *first_frame_id, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES && rows >= 1 && rows <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES,
+	           BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(lag_count >= 1 && lag_count <= BEAMFORMER_HIP_MAX_LAGS && lag_count <= rows, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(weights != nullptr || rows == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (size_t n = 0; weights && n < (size_t)2 * count * rows; n++)
+		if (!check(std::isfinite(weights[n]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return autocorrelate_last_frames(count, weights, rows, lag_count, image_plane_tag, first_frame_id, device_ms);
+}
+
 uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

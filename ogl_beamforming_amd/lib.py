@@ -137,6 +137,7 @@ def _load():
         "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
         "beamformer_hip_clutter_projector": (u32, [C.POINTER(C.c_double), u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
         "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_autocorrelate_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -595,6 +596,24 @@ def mix_last_frames(count, weights, tag=0, timed=True):
     first, ms = C.c_uint32(0), C.c_float(0)
     _check(library().beamformer_hip_mix_last_frames(count, weights.ctypes.data_as(C.POINTER(C.c_float)), out_count, int(tag), C.byref(first),
                                                     C.byref(ms) if timed else None))
+    return int(first.value), float(ms.value)
+
+
+def autocorrelate_last_frames(count, weights=None, lags=2, tag=0, timed=True):
+    """beamformer_hip_autocorrelate_last_frames: `lags` new frames of the frame ring, frame L = sum over n of conj(y_n) y_(n+L) per
+    voxel, y_n = sum over k of weights[n, k] times the k-th oldest of the `count` newest frames -- bit for bit the frames
+    mix_last_frames would store, which are never written; weights: (rows, count) as for mix_last_frames, or None: y_n is the n-th
+    frame itself.  Returns (first_frame_id, device_ms): the id of lag 0; timed False: the call does not synchronise and device_ms is 0."""
+    count = int(count)
+    pointer, rows = None, count
+    if weights is not None:
+        weights = np.ascontiguousarray(np.atleast_2d(np.asarray(weights)), np.complex64)
+        if weights.shape[1] != count:
+            raise ValueError(f"weights {weights.shape}: the second dimension is not count = {count}")
+        pointer, rows = weights.ctypes.data_as(C.POINTER(C.c_float)), int(weights.shape[0])
+    first, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_autocorrelate_last_frames(count, pointer, rows, int(lags), int(tag), C.byref(first),
+                                                              C.byref(ms) if timed else None))
     return int(first.value), float(ms.value)
 
 

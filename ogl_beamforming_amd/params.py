@@ -329,6 +329,7 @@ class HipFramePeaks(C.Structure):
 
 
 HIP_MAX_ENSEMBLE_FRAMES = 256
+HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
 
 
 class HipEnsembleInfo(C.Structure):

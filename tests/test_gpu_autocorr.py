@@ -1,0 +1,329 @@
+"""The slow-time autocorrelation on the device (beamformer_hip_autocorrelate_last_frames; csrc/autocorr.hip) and the loop burst -> gram ->
+projector -> autocorrelate -> peaks.  The ensembles, grids and weights are those of tests/test_gpu_ensemble.py; the expected values are
+the numpy reference (tests/autocorr_ref.py) applied to the downloaded source frames.
+
+The bar is derived, not measured: tests/autocorr_ref.py returns it with the values and its docstring has the derivation -- the rounding
+of a float32 fmaf chain of 2N terms over products of the filtered samples, plus what mix's own bound on those samples carries into the
+sum.  Ids, grids, kinds, tags, the zeros the definition promises and the finite masks are asked exactly.  Every test prints what it
+measured -- the worst error as a share of its bound -- before it asserts."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from ogl_beamforming_amd import lib as bf
+from ogl_beamforming_amd import params as P
+from tests import autocorr_ref as ref
+from tests import frame_peaks_ref
+from tests import variants_cases as vc
+from tests.test_gpu_ensemble import block, ensemble, loop_case, newest_id, rf_frames, weights
+from tests.test_gpu_frame_metrics import newest_info
+from tests.test_gpu_frame_peaks import check_call
+
+pytestmark = pytest.mark.gpu
+E = P.LibError
+D = P.DataKind
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(autouse=True)
+def automatic_path(bflib):
+    L = bflib.library()
+    L.beamformer_set_global_timeout(0xFFFFFFFF)
+    L.beamformer_hip_set_das_path(0)
+    yield
+    L.beamformer_hip_set_das_path(0)
+
+
+def parts(a):
+    """the floats of an array of frames as (real parts, imaginary parts or None)"""
+    return (a.real, a.imag) if np.iscomplexobj(a) else (a, None)
+
+
+def share_of_bound(got, expected, bound, finite):
+    """the worst |got - expected| / bound over the finite voxels of every lag, real and imaginary parts (lag 0's imaginary part, exact
+    by definition, is left out): (worst share, every float within its bound)"""
+    worst, inside = 0.0, True
+    for lag in range(len(got)):
+        for which, (g, x) in enumerate(zip(parts(got[lag]), parts(expected[lag]))):
+            if g is None or (which == 1 and lag == 0):
+                continue
+            f = finite[lag]
+            over = np.abs(g[f].astype(np.float64) - x[f])
+            if over.size:
+                worst = max(worst, float((over / np.maximum(bound[lag][f], 1e-300)).max()))
+                inside = inside and bool((over <= bound[lag][f]).all())
+    return worst, inside
+
+
+def burst_info_unchanged(after, before):
+    """the newest burst's info behind the outputs: what the library keeps -- the route, the ids, the stage kinds -- equal byte for byte.
+    The stage times are not kept: every call asks the runtime again for the time between the same two events, and the runtime converts
+    device ticks to nanoseconds with a calibration it renews as it runs, so two answers may differ by nanoseconds; they are asked to
+    within a microsecond."""
+    times = P.HipBurstInfo.stage_ms.offset
+    a, b = bytes(after), bytes(before)
+    moved = max(abs(x - y) for x, y in zip(list(after.stage_ms) + [after.burst_ms], list(before.stage_ms) + [before.burst_ms]))
+    print(f"  burst info behind the outputs: stage times moved by {moved * 1e6:.1f} ns at the most")
+    assert a[:times] == b[:times] and len(a) == len(b) == P.HipBurstInfo.burst_ms.offset + 4
+    assert moved <= 1e-3
+
+
+def finite_of(a):
+    return np.isfinite(a.real) & np.isfinite(a.imag) if np.iscomplexobj(a) else np.isfinite(a)
+
+
+def check_autocorr(which, frames, ids, W, lags, tag=0, what="", factor=1.0, expected=None):
+    """autocorrelate the len(frames) newest frames under W (None: the identity form) and check the outputs and their records; returns
+    (outputs, first id).  expected: (values, bound) other than the reference's on `frames`; factor: the multiple of the bound asked."""
+    acq = block(which)
+    K = len(frames)
+    real = not np.iscomplexobj(frames)
+    source_block = int(bf.frame_info(ids[-1]).parameter_block)
+    first, ms = bf.autocorrelate_last_frames(K, W, lags, tag=tag)
+    out = bf.get_last_frames(acq.bp, lags).copy()
+    values, bound = expected if expected is not None else ref.autocorrelate(list(frames), W, lags)
+    finite = finite_of(values)
+    worst, inside = share_of_bound(out, values, factor * bound, finite)
+    rows = K if W is None else W.shape[0]
+    print(f"  {what}: K {K}, rows {rows}{' (identity)' if W is None else ''}, lags {lags}, {'real' if real else 'complex'} {frames.shape[1:]}: "
+          f"worst error {worst:.4f} of its bound, {int((~finite).sum())} non-finite, {ms * 1e3:.1f} us")
+    assert out.shape == (lags,) + frames.shape[1:] and out.dtype == frames.dtype and ms > 0
+    assert inside
+    # a voxel that is not finite in some source is not finite in every output, lag 0's imaginary part included
+    assert np.array_equal(finite_of(out), finite)
+    if not real:
+        assert np.array_equal(np.isfinite(out[0].imag), finite[0])
+        assert not out[0].imag.view(np.uint32)[finite[0]].any()                      # exactly +0: no bit set
+    assert (out[0].real[finite[0]] >= 0).all()
+    # the records: consecutive ids behind the sources, the grid, the kind, the tag, the newest source's block
+    assert first == ids[-1] + 1 and int(newest_info(bf.library()).frame_id) == first + lags - 1
+    scores, _ = bf.score_last_frames(lags)
+    pz, py, px = frames.shape[1:]
+    for j in range(lags):
+        info = bf.frame_info(first + j)
+        assert (int(info.frame_id), tuple(info.points), int(info.parameter_block)) == (first + j, (px, py, pz), source_block)
+        assert int(info.data_kind) == int(D.Float32 if real else D.Float32Complex)
+        assert (int(scores[j].frame_id), int(scores[j].image_plane_tag), int(scores[j].parameter_block)) == (first + j, tag, source_block)
+    # their rows of the timing table: no stages, no DAS voxels
+    t = P.HipFrameTimings()
+    assert bf.library().beamformer_hip_get_last_frame_timings(C.byref(t)) and t.stage_count == 0 and t.das_voxels == 0
+    # a source frame is still served by its id
+    assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))
+    return out, first
+
+
+# (K, rows, lags): one row; a ragged tile of three; a tile boundary at row 16 with all three carried rows in use; one full tile; two
+# full tiles and one row; more than 64 frames and a ragged fifth tile
+CASES = [(1, 1, 1), (3, 3, 3), (5, 17, 4), (17, 16, 4), (17, 33, 2), (65, 65, 4)]
+
+
+@pytest.mark.parametrize("K,rows,lags", CASES)
+@pytest.mark.parametrize("which", ["plane", "volume"])
+def test_autocorrelation_of_a_filtered_burst(which, K, rows, lags, bflib):
+    frames, ids = ensemble(which, K)
+    before = bflib.last_burst_info() if K > 1 else None
+    out, _ = check_autocorr(which, frames, ids, weights(rows, K, 8100 + 100 * K + rows), lags, tag=5, what=which)
+    if K > 1:
+        burst_info_unchanged(bflib.last_burst_info(), before)      # fewer than 32 outputs: the newest burst's info is unchanged
+    if lags > 1:
+        # the lags are far more than any tolerance apart: a kernel that stored one chain for every lag fails above
+        assert np.abs(out[1] - out[0]).max() > 0.1 * np.abs(out[0]).max()
+
+
+@pytest.mark.parametrize("which", ["plane", "volume"])
+def test_the_identity_form(which, bflib):
+    frames, ids = ensemble(which, 17)
+    before = bflib.last_burst_info()
+    check_autocorr(which, frames, ids, None, 4, tag=6, what=which + " identity")
+    burst_info_unchanged(bflib.last_burst_info(), before)
+
+
+def test_the_time_reversed_rows_give_the_conjugate_of_lag_one(bflib):
+    W = weights(17, 5, 8200)
+    frames, ids = ensemble("plane", 5)
+    forward, _ = check_autocorr("plane", frames, ids, W, 2, what="forward")
+    frames, ids = ensemble("plane", 5)
+    # the reversed rows are the same floats y_n in the other order: only the order of the chain differs, so twice the bound
+    values, bound = ref.autocorrelate(list(frames), W, 2)
+    backward, _ = check_autocorr("plane", frames, ids, W[::-1].copy(), 2, what="reversed, against conj", factor=2.0,
+                                 expected=(np.conj(values), bound))
+    over = np.maximum(np.abs(backward[1].real - forward[1].real), np.abs(backward[1].imag + forward[1].imag))
+    print(f"  R_1 reversed against conj(R_1): worst {float((over / (2 * bound[1])).max()):.4f} of twice the bound")
+    assert (over <= 2 * bound[1]).all() and np.abs(forward[1].imag).max() > 100 * bound[1].max()
+
+
+def test_composition_with_mix_is_bit_for_bit(bflib):
+    K = 17
+    W = weights(K, K, 8300)
+    frames, ids = ensemble("volume", K)
+    fused, _ = check_autocorr("volume", frames, ids, W, 4, what="fused")
+    frames2, _ = ensemble("volume", K)
+    assert np.array_equal(frames2.view(np.uint32), frames.view(np.uint32))
+    first, _ = bflib.mix_last_frames(K, W)
+    mixed = bflib.get_last_frames(block("volume").bp, K).copy()
+    split, _ = check_autocorr("volume", mixed, list(range(first, first + K)), None, 4, what="mix, then the identity form")
+    differing = int((fused.view(np.uint32) != split.view(np.uint32)).sum())
+    print(f"  fused against mix + identity: {differing} of {fused.view(np.uint32).size} words differ")
+    assert fused.tobytes() == split.tobytes()
+
+
+def test_the_same_call_twice_gives_equal_bytes(bflib):
+    W = weights(33, 17, 8400)
+    frames, ids = ensemble("plane", 17)
+    out, _ = check_autocorr("plane", frames, ids, W, 4, tag=3, what="plane")
+    frames2, ids2 = ensemble("plane", 17)
+    assert np.array_equal(frames2.view(np.uint32), frames.view(np.uint32))
+    again, _ = check_autocorr("plane", frames2, ids2, W, 4, tag=3, what="plane again")
+    assert out.tobytes() == again.tobytes()
+
+
+def test_real_frames(bflib):
+    frames, ids = ensemble("real", 5)
+    assert frames.dtype == np.float32
+    out, _ = check_autocorr("real", frames, ids, weights(17, 5, 8500, real=True), 4, what="real")
+    assert out.dtype == np.float32
+    frames, ids = ensemble("real", 5)
+    check_autocorr("real", frames, ids, None, 3, what="real identity")
+    # a nonzero imaginary weight on real frames is refused, and nothing changes
+    frames, ids = ensemble("real", 5)
+    W = weights(3, 5, 8501, real=True)
+    W[2, 4] += 1e-30j
+    first, ms = C.c_uint32(77), C.c_float(-1.0)
+    assert not bflib.library().beamformer_hip_autocorrelate_last_frames(5, W.ctypes.data_as(C.POINTER(C.c_float)), 3, 2, 0, C.byref(first), C.byref(ms))
+    assert bflib.last_error()[0] == E.InvalidAccess and first.value == 77 and ms.value == -1.0
+    assert int(newest_info(bflib.library()).frame_id) == ids[-1]
+
+
+def test_nan_voxels_and_zero_weights(bflib):
+    frames, ids = ensemble("nan", 5)
+    nan = np.isnan(frames).any(axis=0)
+    print(f"  {int(nan.sum())} of {nan.size} voxels NaN in some frame")
+    assert nan.sum() >= 64 and 4 * (~nan).sum() >= nan.size
+    out, _ = check_autocorr("nan", frames, ids, weights(17, 5, 8600), 4, what="nan")
+    assert np.isnan(out.real[:, nan]).all() and np.isnan(out.imag[:, nan]).all() and np.isfinite(out.real[:, ~nan]).all()
+    frames, ids = ensemble("nan", 5)
+    out, _ = check_autocorr("nan", frames, ids, None, 2, what="nan identity")
+    assert np.isnan(out.real[:, nan]).all() and np.isnan(out.imag[:, nan]).all()
+    frames, ids = ensemble("nan", 5)
+    out, _ = check_autocorr("nan", frames, ids, np.zeros((3, 5), np.complex64), 2, what="zero weights")
+    assert not out[:, ~nan].any() and np.isnan(out.real[:, nan]).all() and np.isnan(out.imag[:, nan]).all()   # no weight is skipped: 0 * NaN
+
+
+# ---- the loop: burst -> gram -> projector -> autocorrelate -> peaks ----
+
+def test_the_power_doppler_loop(bflib):
+    acq, rf = loop_case()
+    burst = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
+    G, info, _ = bflib.gram_last_frames(8)
+    W, values = bflib.clutter_projector(G, 1)
+    assert values[0] > 1e3 * values[1] > 0
+    first, ms = bflib.autocorrelate_last_frames(8, W, 2)
+    assert first == int(info.first_frame_id) + 8
+    lag = bflib.get_last_frames(acq.bp, 2).copy()
+    expected, bound = ref.autocorrelate(list(burst), W, 2)
+    worst, inside = share_of_bound(lag, expected, bound, finite_of(expected))
+    print(f"  lags 0 and 1 of the filtered burst: worst error {worst:.4f} of its bound, {ms * 1e3:.1f} us")
+    assert inside and not lag[0].imag.any()
+    # the peaks of the power image, found where it lies: lag 0 is the older of the two newest frames
+    thresholds = [0.25 * float(np.abs(f).max()) for f in lag]
+    _, _, found = check_call(list(lag), thresholds, cap=64, what="lags")
+    assert found[0]["found"] >= 1
+    # the same burst again, mixed: the power image is the sum of |mix outputs|^2 -- of the very floats the mix stores, so within the bound
+    # of the identity form --, and its peaks are that sum's
+    bflib.beamform_burst(acq.bp, rf, acq.filters)
+    bflib.mix_last_frames(8, W)
+    mixed = bflib.get_last_frames(acq.bp, 8).copy()
+    power = (mixed.real.astype(np.float64) ** 2 + mixed.imag.astype(np.float64) ** 2).sum(axis=0)
+    _, identity_bound = ref.autocorrelate(list(mixed), None, 1)
+    over = np.abs(lag[0].real - power)
+    print(f"  lag 0 against the sum of |mix outputs|^2: worst {float((over / identity_bound[0]).max()):.4f} of the identity form's bound")
+    assert (over <= identity_bound[0]).all()
+    of_the_sum = frame_peaks_ref.peaks(power.astype(np.float32).astype(np.complex64), thresholds[0], None, None, cap=64)
+    assert of_the_sum["found"] == found[0]["found"] and np.array_equal(of_the_sum["index"], found[0]["index"])
+
+
+# ---- refusals that need a device ----
+
+def refused(L, K, W, rows, lags, kind):
+    """the call refuses with this error kind, writes nothing and queues nothing: the newest id stays, and the frame pushed next lies
+    where it would have lain (the ring's next offset is unchanged)"""
+    first, ms = C.c_uint32(77), C.c_float(-1.0)
+    newest = newest_id(L)
+    before = bytes(newest_info(L)) if newest is not None and L.beamformer_hip_get_device_count() == 1 else None
+    pointer = None if W is None else W.ctypes.data_as(C.POINTER(C.c_float))
+    assert not L.beamformer_hip_autocorrelate_last_frames(K, pointer, rows, lags, 0, C.byref(first), C.byref(ms))
+    assert bf.last_error()[0] == kind and first.value == 77 and ms.value == -1.0
+    assert newest_id(L) == newest
+    if before is not None:
+        assert bytes(newest_info(L)) == before
+        old = newest_info(L)
+        acq = block("plane")
+        bf.beamform(acq.bp, rf_frames("plane", 1)[0], acq.filters)
+        new = newest_info(L)
+        assert int(new.frame_id) == int(old.frame_id) + 1
+        assert int(new.device_pointer) == int(old.device_pointer) + (int(old.size_bytes) + 63) // 64 * 64
+
+
+def test_refusals(bflib):
+    L = bflib.library()
+    a, v, r = block("plane"), block("volume"), block("real")
+    eye = np.eye(2, dtype=np.complex64)
+    # frames of two grids
+    ensemble("plane", 2)
+    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
+    refused(L, 2, eye, 2, 2, E.DataSizeMismatch)
+    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
+    refused(L, 2, None, 2, 1, E.DataSizeMismatch)
+    # frames of two kinds on one grid (the push inside refused() left a complex plane behind)
+    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
+    refused(L, 2, eye, 2, 1, E.DataSizeMismatch)
+    # more lags than rows, more than BEAMFORMER_HIP_MAX_LAGS, none
+    frames, ids = ensemble("plane", 3)
+    refused(L, 3, weights(2, 3, 8700), 2, 3, E.InvalidAccess)
+    frames, ids = ensemble("plane", 3)
+    refused(L, 3, None, 3, 4, E.InvalidAccess)
+    frames, ids = ensemble("plane", 5)
+    refused(L, 5, None, 5, P.HIP_MAX_LAGS + 1, E.InvalidAccess)
+    frames, ids = ensemble("plane", 3)
+    refused(L, 3, None, 3, 0, E.InvalidAccess)
+    # the identity form with rows != count
+    frames, ids = ensemble("plane", 3)
+    refused(L, 3, None, 2, 1, E.InvalidAccess)
+    # more frames than are there: a fresh context with two
+    L.beamformer_hip_shutdown()
+    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
+    frames, ids = ensemble("plane", 2)
+    assert ids == [0, 1]
+    refused(L, 3, None, 3, 1, E.InvalidAccess)
+    frames, ids = ensemble("plane", 2)
+    check_autocorr("plane", frames, ids, None, 2, what="two frames")
+
+
+def test_several_devices_are_refused(bflib):
+    L = bflib.library()
+    acq = vc.separable_volume()
+    try:
+        L.beamformer_hip_shutdown()
+        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
+        bflib.beamform(acq.bp, acq.rf, acq.filters)
+        assert L.beamformer_hip_get_device_count() == 2
+        refused(L, 1, None, 1, 1, E.InvalidAccess)
+        refused(L, 1, np.ones((1, 1), np.complex64), 1, 1, E.InvalidAccess)
+    finally:
+        L.beamformer_hip_shutdown()
+        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
+    frames, ids = ensemble("plane", 2)
+    check_autocorr("plane", frames, ids, None, 2, what="one device again")
+
+
+def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
+    """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/autocorr_wrap_worker.py"""
+    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "autocorr_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
+    print(run.stdout)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "refused" in run.stdout and "wrapped" in run.stdout, run.stdout
