@@ -708,6 +708,55 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_autocorrelate_last_frames(uint32_t
                                                                         uint32_t lag_count, uint32_t image_plane_tag,
                                                                         uint32_t *first_frame_id, float *device_ms);
 
+/* ---- spatial filter: a separable convolution of ring frames, written back into the ring.  The operators above work across the
+ * ensemble, voxel by voxel, or reduce a frame to numbers; this one takes frames and gives spatially filtered frames: the PSF-sized
+ * Gaussian in front of beamformer_hip_find_peaks_last_frames (without it the maxima are those of the speckle), the box average of the
+ * lag frames of beamformer_hip_autocorrelate_last_frames in front of the Kasai angle, and -- normalised -- a smoothing that neither
+ * darkens a frame at its edges nor spreads the NaN of a coherency-weighted frame, and fills the holes ----
+ * DEFINITION (tests/spatial_ref.py restates it in numpy).
+ * SOURCES.  The `count` newest frames of the ring, of one grid and one kind: beamformer_hip_mix_last_frames' rules.
+ * TAPS.  Axis a (0 = x, the fastest; 1 = y; 2 = z) has n = tap_counts[a] real taps h = taps[a][0 .. n - 1]; n is odd and
+ * <= BEAMFORMER_HIP_MAX_SPATIAL_TAPS, its radius r = (n - 1) / 2.  n == 0 (taps[a] is then not read and may be NULL) leaves the axis
+ * alone: no pass, no rounding.  Real taps act on the real and the imaginary float of a complex voxel independently.
+ * A PASS along axis a turns a field f into g; each float of g is ONE float32 fmaf chain from +0 in ascending t,
+ *     acc = fmaf(h[t], f[i + r - t], acc),   t = 0 .. n - 1,
+ * i the voxel's index along the axis -- a true convolution: taps {0, 0, 1} move the frame by +1 voxel --, and a term whose source index
+ * i + r - t lies outside the frame is skipped.  The passes run in the order x, y, z over the axes with n > 0; each reads the float32
+ * result of the one before it.
+ * mode BeamformerHipSpatialMode_Zero: plain IEEE otherwise.  No tap is skipped for being zero: a voxel that is not finite makes every
+ * output whose support covers it not finite, as the mix does.
+ * mode BeamformerHipSpatialMode_Normalised: m[v] = 1 where the source voxel is finite (both floats of a complex one), else 0.  The
+ * numerator N is the passes above with the terms of the non-finite source voxels SKIPPED in the first pass as out-of-frame terms are;
+ * the denominator D is the same passes applied to m, acc = fmaf(h[t], m[i + r - t], acc), the same terms skipped.  Each output float is
+ * the IEEE float32 quotient N / D; where no finite voxel lies under a positive tap that is +0 / +0 = NaN.  A voxel that is not finite
+ * but has finite neighbours under the taps gets a finite output: the hole is filled; a constant frame stays constant up to its edges.
+ * Taps must be >= 0 in this mode.
+ * The bytes of an output depend on its source frame, the taps and the mode only -- not on count, on the other frames of the call, or on
+ * the call being repeated.
+ * OUTPUTS.  `count` new frames of the sources' grid and kind, output n source n filtered, oldest first, placed in the ring as ONE
+ * contiguous run exactly as beamformer_hip_mix_last_frames places its run: the same ids from the counters a push advances, the newest
+ * source's parameter block, the call's image_plane_tag, rows of the timing table that report no stages and 0 DAS voxels, the same
+ * treatment of the record of the newest multi-frame push.  Everything that reads frames works on them unchanged.  *first_frame_id (may
+ * be NULL): the id of the oldest output.  One launch a live axis (csrc/spatial.hip), enqueued on the current stream behind the frames
+ * they read; what lies between two passes is memory of the library's own and the output run itself, never another frame of the ring.
+ * The call does not synchronise unless device_ms is not NULL (then: the time between two events around the launches).
+ * Refusals, all decided BEFORE ANYTHING CHANGES and leaving every output unwritten: count 0 or > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, a
+ * tap count > BEAMFORMER_HIP_MAX_SPATIAL_TAPS: BufferOverflow; taps or tap_counts NULL, an even tap count, taps[a] NULL with a nonzero
+ * count, all three counts 0, a tap that is not finite, a tap < 0 in Normalised mode, an unknown mode: InvalidAccess;
+ * frames that differ in grid or kind: DataSizeMismatch; a run of `count` frames that does not fit the ring, or that would reuse storage
+ * of one of its own source frames: FrameSizeOverflow; and everything beamformer_hip_score_last_frames refuses, several devices
+ * included (InvalidAccess).  A tap count larger than an axis's extent is legal, also on an axis of 1 point: the skipped terms handle
+ * it. */
+#define BEAMFORMER_HIP_MAX_SPATIAL_TAPS 33u
+typedef enum {
+	BeamformerHipSpatialMode_Zero       = 0,
+	BeamformerHipSpatialMode_Normalised = 1,
+	BeamformerHipSpatialMode_Count
+} BeamformerHipSpatialMode;
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_convolve_last_frames(uint32_t count, const float *const taps[3], const uint32_t tap_counts[3],
+                                                                   uint32_t mode, uint32_t image_plane_tag,
+                                                                   uint32_t *first_frame_id, float *device_ms);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

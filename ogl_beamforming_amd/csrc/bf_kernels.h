@@ -441,6 +441,22 @@ typedef struct {
 	uint64_t out_offset, out_stride;   /* the lag 0 frame in the ring, bytes; from one lag to the next */
 } BfAutocorrArgs;
 
+/* ---- separable spatial filter (spatial.hip: beamformer_hip_convolve_last_frames) ---- */
+#define BF_SPATIAL_MAX_TAPS    33u           /* = BEAMFORMER_HIP_MAX_SPATIAL_TAPS: a halo of 16 voxels either side */
+#define BF_SPATIAL_TAP_STRIDE  96u           /* floats of an axis's row of the device tap table: BF_SPATIAL_TAP_FRONT zeros, the taps, zeros */
+#define BF_SPATIAL_TAP_FRONT   16u
+typedef struct {
+	uint32_t frames, cplx;       /* K frames in, K out; 1: Float32Complex, 0: Float32 */
+	uint32_t stage, last;        /* 0: Zero mode; 1: Normalised, the first pass (the mask is made from the source); 2: Normalised, a later pass
+	                                (D is read); last: Normalised stores N / D and no D */
+	uint32_t inner, extent, outer;   /* the axis: `extent` points at a stride of `inner` voxels, `outer` slices of inner * extent voxels */
+	uint32_t taps;               /* odd, <= BF_SPATIAL_MAX_TAPS */
+	uint64_t in_stride, out_stride;  /* bytes from one frame to the next (in_stride: without an offsets table) */
+	uint64_t d_stride;           /* floats from one frame's D field to the next */
+	uint32_t row_log2, row_rows, row_segments, row_groups;   /* launch geometry, filled in by bf_launch_spatial */
+	uint32_t run_blocks, run_chunks;
+} BfSpatialArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -505,6 +521,12 @@ hipError_t bf_launch_mix(void *ring, const uint64_t *offsets, const float *weigh
  * `rows` zero -- or NULL, the identity form (rows == frames: row n is source frame n).  Lag l is written at ring + out_offset +
  * l * out_stride */
 hipError_t bf_launch_autocorr(void *ring, const uint64_t *offsets, const float *weights, const BfAutocorrArgs *a, hipStream_t s);
+/* spatial.hip: one pass along one axis, one launch.  Frame k is read at in + offsets[k] (offsets: device memory) or, offsets NULL, at
+ * in + k * in_stride, and written at out + k * out_stride; taps: the axis's taps inside their row of the device table, readable from
+ * taps[-BF_SPATIAL_TAP_FRONT] to the row's end; d_in / d_out: the D fields of a Normalised
+ * pass, frame k at k * d_stride floats (d_in: stage 2; d_out: stages 1 and 2 unless `last`) */
+hipError_t bf_launch_spatial(const void *in, const uint64_t *offsets, void *out, const float *d_in, float *d_out, const float *taps,
+                             const BfSpatialArgs *a, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

@@ -189,6 +189,7 @@ static void release_one_device(Device &d)
 	if (d.peaks_end)   (void)hipEventDestroy(d.peaks_end);
 	d.peaks_begin = d.peaks_end = nullptr;
 	d.mix_table.release();
+	d.spatial_scratch.release();
 	if (d.mix_pinned) (void)hipHostFree(d.mix_pinned);
 	for (hipEvent_t *e : {&d.mix_copied, &d.mix_begin, &d.mix_end}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
 	d.mix_pinned = nullptr; d.mix_copy_pending = false;
@@ -2662,16 +2663,39 @@ bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, do
 
 namespace {
 
-/* What beamformer_hip_mix_last_frames and beamformer_hip_autocorrelate_last_frames share: `out_count` frames computed from the `count`
- * newest ones under a weight table of `rows` rows (null: no table -- the caller's launch reads the sources as they are) and queued as
- * frames of their own behind them.  Everything that can refuse is decided, and every buffer grown, before the ids are taken; nothing
- * synchronises unless device_ms is asked for.  launch(ring, offsets, table, K, cplx, elements, out_offset, out_stride, stream): the call's
- * one kernel launch -- the sources' ring offsets and the table [tile][k][BF_MIX_TILE][2] (rows past `rows` zero; null without weights) in
- * device memory, output j at ring + out_offset + j * out_stride. */
-template <class Launch>
-bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows, uint32_t out_count, uint32_t image_plane_tag,
-                            uint32_t *first_frame_id, float *device_ms, Launch launch)
+/* What beamformer_hip_mix_last_frames, beamformer_hip_autocorrelate_last_frames and beamformer_hip_convolve_last_frames share:
+ * `out_count` frames computed from the `count` newest ones and queued as frames of their own behind them.  Everything that can refuse
+ * is decided, and every buffer grown, before the ids are taken; nothing synchronises unless device_ms is asked for.
+ * The call's table travels with the sources' ring offsets: a weight table of `rows` rows, laid out [tile][k][BF_MIX_TILE][2] (rows past
+ * `rows` zero), or `flat_floats` floats as they are (the taps of a convolution), or neither (weights and flat null: the launch reads the
+ * sources as they are).
+ * prepare(device, newest source's record, cplx, out_count): what the call's launches need besides -- memory of their own --, grown
+ * while the call can still refuse; false refuses it (InvalidAccess) with nothing changed.
+ * launch(run): the call's kernel launches, one or several, on run.s -- the sources' offsets and the table in device memory (table null
+ * without one), output j at ring + out_offset + j * out_stride. */
+struct RunTable {
+	const float *weights = nullptr; uint32_t rows = 0;
+	const float *flat = nullptr;    uint32_t flat_floats = 0;
+};
+struct QueuedRun {
+	Device *d;
+	void *ring;
+	const uint64_t *offsets;
+	const float *table;
+	uint32_t K;
+	bool cplx;
+	uint32_t points[3];
+	uint64_t elements, out_offset, out_stride;
+	hipStream_t s;
+};
+const auto nothing_to_prepare = [](Device &, const FrameRecord &, bool, uint32_t) { return true; };
+
+template <class Prepare, class Launch>
+bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_count, uint32_t image_plane_tag,
+                            uint32_t *first_frame_id, float *device_ms, Prepare prepare, Launch launch)
 {
+	const float *weights = t.weights;
+	const uint32_t rows = t.rows;
 	Context &c = g_context;
 	std::vector<BoxedFrame> boxed;
 	if (!newest_ensemble_frames(count, nullptr, boxed)) return false;
@@ -2693,7 +2717,7 @@ bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows,
 
 	/* the table: offsets[K] | weights[tile][k][BF_MIX_TILE][2], rows past `rows` zero */
 	const uint32_t padded = weights ? (rows + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE : 0u;
-	const size_t offsets_bytes = round_up(sizeof(uint64_t) * K, 64), weights_bytes = sizeof(float) * 2 * padded * K;
+	const size_t offsets_bytes = round_up(sizeof(uint64_t) * K, 64), weights_bytes = t.flat ? sizeof(float) * t.flat_floats : sizeof(float) * 2 * padded * K;
 	const size_t table_max = round_up(sizeof(uint64_t) * BF_ENSEMBLE_MAX_FRAMES, 64) + sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES;
 	bool ok = HIP_OK(hipSetDevice(d.device));
 	ok = ok && d.mix_table.ensure(table_max);
@@ -2701,6 +2725,7 @@ bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows,
 	if (ok && !d.mix_copied) ok = HIP_OK(hipEventCreateWithFlags(&d.mix_copied, hipEventDisableTiming));
 	if (ok && !d.mix_begin)  ok = HIP_OK(hipEventCreate(&d.mix_begin));
 	if (ok && !d.mix_end)    ok = HIP_OK(hipEventCreate(&d.mix_end));
+	ok = ok && weights_bytes <= table_max - offsets_bytes && prepare(d, newest, cplx, M);
 	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
 	if (d.mix_copy_pending) { (void)hipEventSynchronize(d.mix_copied); d.mix_copy_pending = false; }   /* (the previous call's copy: long done) */
 	char *pinned = (char *)d.mix_pinned;
@@ -2708,6 +2733,7 @@ bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows,
 	for (uint32_t n = 0; n < K; n++) offsets[n] = boxed[n].record->offset;
 	float *table = (float *)(pinned + offsets_bytes);
 	std::memset(table, 0, weights_bytes);
+	if (t.flat) std::memcpy(table, t.flat, weights_bytes);
 	for (uint32_t j = 0; j < rows && weights; j++)
 		for (uint32_t k = 0; k < K; k++) {
 			float *w = table + (((size_t)(j / BF_MIX_TILE) * K + k) * BF_MIX_TILE + j % BF_MIX_TILE) * 2;
@@ -2737,13 +2763,18 @@ bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows,
 	}
 	d.have_sample = false;              /* the slots of older sampled frames may be gone: a single frame that follows records its own events */
 
-	const uint64_t elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
+	QueuedRun run{};
+	run.d = &d; run.ring = d.ring.ptr; run.offsets = (const uint64_t *)d.mix_table.ptr;
+	run.table = weights || t.flat ? (const float *)((const char *)d.mix_table.ptr + offsets_bytes) : nullptr;
+	run.K = K; run.cplx = cplx;
+	for (int k = 0; k < 3; k++) run.points[k] = newest.points[k];
+	run.elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
+	run.out_offset = frame0->offset; run.out_stride = frame0->bytes; run.s = s;
 	ok &= HIP_OK(hipMemcpyAsync(d.mix_table.ptr, pinned, offsets_bytes + weights_bytes, hipMemcpyHostToDevice, s));
 	d.mix_copy_pending = HIP_OK(hipEventRecord(d.mix_copied, s));
 	ok &= d.mix_copy_pending;
 	if (device_ms) ok &= HIP_OK(hipEventRecord(d.mix_begin, s));
-	if (ok) ok &= HIP_OK(launch(d.ring.ptr, (const uint64_t *)d.mix_table.ptr, weights ? (const float *)((const char *)d.mix_table.ptr + offsets_bytes) : nullptr, K, cplx,
-	                            elements, frame0->offset, frame0->bytes, s));
+	if (ok) ok &= HIP_OK(launch(run));
 	if (device_ms) {
 		ok &= HIP_OK(hipEventRecord(d.mix_end, s));
 		ok &= HIP_OK(hipStreamSynchronize(s));
@@ -2762,12 +2793,13 @@ bool queue_frames_of_newest(uint32_t count, const float *weights, uint32_t rows,
  * (ensemble.hip) */
 bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
 {
-	return queue_frames_of_newest(count, weights, out_count, out_count, image_plane_tag, first_frame_id, device_ms,
-		[=](void *ring, const uint64_t *offsets, const float *table, uint32_t K, bool cplx, uint64_t elements, uint64_t out_offset, uint64_t out_stride, hipStream_t s) {
+	RunTable t; t.weights = weights; t.rows = out_count;
+	return queue_frames_of_newest(count, t, out_count, image_plane_tag, first_frame_id, device_ms, nothing_to_prepare,
+		[=](const QueuedRun &r) {
 			BfMixArgs a{};
-			a.frames = K; a.outputs = out_count; a.cplx = cplx; a.padded_outputs = (out_count + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
-			a.elements = elements; a.out_offset = out_offset; a.out_stride = out_stride;
-			return bf_launch_mix(ring, offsets, table, &a, s);
+			a.frames = r.K; a.outputs = out_count; a.cplx = r.cplx; a.padded_outputs = (out_count + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
+			a.elements = r.elements; a.out_offset = r.out_offset; a.out_stride = r.out_stride;
+			return bf_launch_mix(r.ring, r.offsets, r.table, &a, r.s);
 		});
 }
 
@@ -2777,12 +2809,72 @@ bool autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t ro
                                uint32_t *first_frame_id, float *device_ms)
 {
 	static_assert(BF_AUTOCORR_MAX_LAGS == BEAMFORMER_HIP_MAX_LAGS, "one limit");
-	return queue_frames_of_newest(count, weights, rows, lag_count, image_plane_tag, first_frame_id, device_ms,
-		[=](void *ring, const uint64_t *offsets, const float *table, uint32_t K, bool cplx, uint64_t elements, uint64_t out_offset, uint64_t out_stride, hipStream_t s) {
+	RunTable t; t.weights = weights; t.rows = rows;
+	return queue_frames_of_newest(count, t, lag_count, image_plane_tag, first_frame_id, device_ms, nothing_to_prepare,
+		[=](const QueuedRun &r) {
 			BfAutocorrArgs a{};
-			a.frames = K; a.rows = rows; a.lags = lag_count; a.cplx = cplx;
-			a.elements = elements; a.out_offset = out_offset; a.out_stride = out_stride;
-			return bf_launch_autocorr(ring, offsets, table, &a, s);
+			a.frames = r.K; a.rows = rows; a.lags = lag_count; a.cplx = r.cplx;
+			a.elements = r.elements; a.out_offset = r.out_offset; a.out_stride = r.out_stride;
+			return bf_launch_autocorr(r.ring, r.offsets, r.table, &a, r.s);
+		});
+}
+
+/* beamformer_hip_convolve_last_frames: the `count` newest frames filtered along x, y, z, queued as `count` frames of their own
+ * (spatial.hip).  One launch a live axis.  P passes write, from the last one back, the output run, the scratch run, the output run: the
+ * last pass writes the ring, and what lies between two passes is the library's own buffer or the run being made -- never a frame that
+ * exists.  Scratch: one run's bytes when there are two passes or more, and in Normalised mode a D field (one float a voxel a frame) per
+ * pass but the last, two at the most. */
+bool convolve_last_frames(uint32_t count, const float *const taps[3], const uint32_t tap_counts[3], uint32_t mode, uint32_t image_plane_tag,
+                          uint32_t *first_frame_id, float *device_ms)
+{
+	static_assert(BF_SPATIAL_MAX_TAPS == BEAMFORMER_HIP_MAX_SPATIAL_TAPS, "one limit");
+	float table[3 * BF_SPATIAL_TAP_STRIDE] = {};                  /* an axis's row: zeros, the taps from BF_SPATIAL_TAP_FRONT on, zeros */
+	uint32_t axes[3], passes = 0;
+	for (uint32_t a = 0; a < 3; a++) {
+		if (tap_counts[a] == 0) continue;
+		axes[passes++] = a;
+		std::memcpy(table + a * BF_SPATIAL_TAP_STRIDE + BF_SPATIAL_TAP_FRONT, taps[a], sizeof(float) * tap_counts[a]);
+	}
+	const uint32_t n[3] = {tap_counts[0], tap_counts[1], tap_counts[2]};
+	const bool normalised = mode == BeamformerHipSpatialMode_Normalised;
+	const uint32_t d_fields = normalised ? (passes - 1u < 2u ? passes - 1u : 2u) : 0u;
+	const auto bytes_of = [](const FrameRecord &f, bool cplx, uint32_t frames, uint64_t &run, uint64_t &field) {
+		const uint64_t voxels = (uint64_t)f.points[0] * f.points[1] * f.points[2];
+		run = round_up(voxels * (cplx ? 8u : 4u), 64) * frames;
+		field = round_up(voxels * 4u, 64) * frames;
+	};
+	RunTable t; t.flat = table; t.flat_floats = 3 * BF_SPATIAL_TAP_STRIDE;
+	return queue_frames_of_newest(count, t, count, image_plane_tag, first_frame_id, device_ms,
+		[=](Device &d, const FrameRecord &newest, bool cplx, uint32_t frames) {
+			uint64_t run, field;
+			bytes_of(newest, cplx, frames, run, field);
+			if ((uint64_t)newest.points[0] * newest.points[1] * newest.points[2] > 0x7FFFFFFFull) return false;   /* the launches count a slice's voxels in 32 bits */
+			const uint64_t need = (passes > 1u ? run : 0u) + d_fields * field;
+			return need == 0 || d.spatial_scratch.ensure(need);
+		},
+		[=](const QueuedRun &r) {
+			FrameRecord shape; uint64_t run, field;
+			for (int k = 0; k < 3; k++) shape.points[k] = r.points[k];
+			bytes_of(shape, r.cplx, r.K, run, field);
+			char *scratch = (char *)r.d->spatial_scratch.ptr, *ring_out = (char *)r.ring + r.out_offset;
+			float *d_field[2] = {(float *)(scratch + (passes > 1u ? run : 0u)), (float *)(scratch + (passes > 1u ? run : 0u) + field)};
+			const uint32_t inner[3] = {1u, r.points[0], r.points[0] * r.points[1]}, outer[3] = {r.points[1] * r.points[2], r.points[2], 1u};
+			const void *in = r.ring;
+			for (uint32_t p = 0; p < passes; p++) {
+				const uint32_t axis = axes[p];
+				const bool to_ring = (passes - 1u - p) % 2u == 0;
+				BfSpatialArgs a{};
+				a.frames = r.K; a.cplx = r.cplx; a.stage = normalised ? (p == 0 ? 1u : 2u) : 0u; a.last = p + 1u == passes;
+				a.inner = inner[axis]; a.extent = r.points[axis]; a.outer = outer[axis]; a.taps = n[axis];
+				a.in_stride = r.out_stride; a.out_stride = r.out_stride; a.d_stride = field / r.K / sizeof(float);
+				void *out = to_ring ? ring_out : scratch;
+				const hipError_t e = bf_launch_spatial(in, p == 0 ? r.offsets : nullptr, out, p ? d_field[(p - 1u) % 2u] : nullptr,
+				                                       normalised && !a.last ? d_field[p % 2u] : nullptr,
+				                                       r.table + axis * BF_SPATIAL_TAP_STRIDE + BF_SPATIAL_TAP_FRONT, &a, r.s);
+				if (e != hipSuccess) return e;
+				in = out;
+			}
+			return hipSuccess;
 		});
 }
 

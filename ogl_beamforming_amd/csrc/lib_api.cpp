@@ -1052,6 +1052,25 @@ uint32_t beamformer_hip_autocorrelate_last_frames(uint32_t count, const float *w
 	return autocorrelate_last_frames(count, weights, rows, lag_count, image_plane_tag, first_frame_id, device_ms);
 }
 
+uint32_t beamformer_hip_convolve_last_frames(uint32_t count, const float *const taps[3], const uint32_t tap_counts[3], uint32_t mode,
+                                             uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(taps != nullptr && tap_counts != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (int a = 0; a < 3; a++)
+		if (!check(tap_counts[a] <= BEAMFORMER_HIP_MAX_SPATIAL_TAPS, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(mode < BeamformerHipSpatialMode_Count && (tap_counts[0] | tap_counts[1] | tap_counts[2]) != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (int a = 0; a < 3; a++) {
+		if (tap_counts[a] == 0) continue;
+		if (!check(tap_counts[a] % 2u == 1u && taps[a] != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+		for (uint32_t t = 0; t < tap_counts[a]; t++) {
+			const float h = taps[a][t];
+			if (!check(std::isfinite(h) && !(mode == BeamformerHipSpatialMode_Normalised && h < 0.0f), BeamformerLibErrorKind_InvalidAccess)) return 0;
+		}
+	}
+	return convolve_last_frames(count, taps, tap_counts, mode, image_plane_tag, first_frame_id, device_ms);
+}
+
 uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

@@ -138,6 +138,7 @@ def _load():
         "beamformer_hip_clutter_projector": (u32, [C.POINTER(C.c_double), u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
         "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_autocorrelate_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_convolve_last_frames": (u32, [u32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(u32), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -614,6 +615,24 @@ def autocorrelate_last_frames(count, weights=None, lags=2, tag=0, timed=True):
     first, ms = C.c_uint32(0), C.c_float(0)
     _check(library().beamformer_hip_autocorrelate_last_frames(count, pointer, rows, int(lags), int(tag), C.byref(first),
                                                               C.byref(ms) if timed else None))
+    return int(first.value), float(ms.value)
+
+
+def convolve_last_frames(count, taps, mode=0, tag=0, timed=True):
+    """beamformer_hip_convolve_last_frames: `count` new frames of the frame ring, the `count` newest ones filtered along x, y and z in
+    that order -- taps: three sequences of an odd number of real taps, (x, y, z), or None for an axis that is left alone; a true
+    convolution (taps (0, 0, 1) move the frame by +1 voxel), terms outside the frame skipped.  mode: P.HipSpatialMode -- Zero: plain
+    IEEE; Normalised: the weights renormalised over the finite in-frame voxels under the taps (taps >= 0): no darkening at the edges, NaN
+    holes filled.  Returns (first_frame_id, device_ms): the id of the oldest output; timed False: the call does not synchronise and
+    device_ms is 0."""
+    if len(taps) != 3:
+        raise ValueError("taps: one sequence (or None) per axis, x, y, z")
+    arrays = [None if h is None else np.ascontiguousarray(np.asarray(h, np.float32).reshape(-1)) for h in taps]
+    pointers = (C.POINTER(C.c_float) * 3)(*[None if h is None or not h.size else h.ctypes.data_as(C.POINTER(C.c_float)) for h in arrays])
+    counts = (C.c_uint32 * 3)(*[0 if h is None else int(h.size) for h in arrays])
+    first, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_convolve_last_frames(int(count), pointers, counts, int(mode), int(tag), C.byref(first),
+                                                         C.byref(ms) if timed else None))
     return int(first.value), float(ms.value)
 
 

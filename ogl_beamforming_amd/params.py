@@ -330,6 +330,13 @@ class HipFramePeaks(C.Structure):
 
 HIP_MAX_ENSEMBLE_FRAMES = 256
 HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
+HIP_MAX_SPATIAL_TAPS = 33       # BEAMFORMER_HIP_MAX_SPATIAL_TAPS
+
+
+class HipSpatialMode(enum.IntEnum):
+    """BeamformerHipSpatialMode (beamformer_hip_convolve_last_frames)"""
+    Zero = 0
+    Normalised = 1
 
 
 class HipEnsembleInfo(C.Structure):
