@@ -757,6 +757,77 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_convolve_last_frames(uint32_t coun
                                                                    uint32_t mode, uint32_t image_plane_tag,
                                                                    uint32_t *first_frame_id, float *device_ms);
 
+/* ---- shift correlation: frame-to-frame motion estimated on the device.  Every operator above assumes that voxel v of frame k and
+ * voxel v of frame j show the same tissue; over an ensemble they do not.  This call correlates each of the K newest frames with one of
+ * them at every integer shift of a window, over one box (rigid motion) or many small ones (block matching: a displacement field), and
+ * a host helper turns the tables into displacements.  An integer correction is then one beamformer_hip_convolve_last_frames with a
+ * shifted delta; a sub-voxel one is an addition to localisations on the host ----
+ * DEFINITION (tests/motion_ref.py restates it in numpy).
+ * SOURCES.  The `count` = K newest frames of the ring, of one grid and one kind: beamformer_hip_gram_last_frames' rules and refusals.
+ * Index 0 is the oldest frame; ref is frame `reference` (< K).
+ * SHIFTS.  S_a = max_shift[a] (a: 0 = x, the fastest; 1 = y; 2 = z), a shift s = (sx, sy, sz) with |s_a| <= S_a, T = the product of
+ * the (2 S_a + 1); the flat shift index is ((sz + Sz)(2 Sy + 1) + (sy + Sy))(2 Sx + 1) + (sx + Sx).
+ * BOXES.  regions NULL: one box, the frame whole (region_count is not read and reported as 1); else region_count boxes, which may
+ * overlap and differ in size.
+ * TERMS.  For box b, frame k and shift s: the voxels v inside the box with v + s inside the FRAME (not the box: a shifted read leaves
+ * the box freely, as the peaks' neighbourhoods do), ref[v] finite and f_k[v + s] finite (a complex voxel: both floats).
+ * SUMS over the terms: re + i im = sum conj(ref[v]) f_k[v + s]; energy_reference = sum |ref[v]|^2; energy_frame = sum |f_k[v + s]|^2;
+ * terms = their number.  The arithmetic is the Gram matrix's: every float widened to double, the products exact; the real part
+ * rj rk + ij ik, the imaginary part rj ik - ij rk and a squared magnitude r r + i i are ONE rounding each (written as an fma), adding
+ * one to its running sum is one more.  Real frames take i = 0: every im is exactly 0.  An entry without terms is 40 zero bytes.
+ * SIGN.  If frame k is the reference moved by d voxels, f_k[v + d] = ref[v], then |C| peaks at s = d.
+ * OUTPUT.  table[region][frame][shift]: K tables a region, the reference's own -- its spatial autocorrelation -- included; that one's
+ * entry at s = 0 has im == 0 and re == energy_reference == energy_frame.
+ * ORDER.  Every sum is a double sum in an order that the box and the window alone fix, no atomics: the 40 bytes of an entry depend on
+ * the reference frame, frame k, the box and max_shift only -- not on K, on the other frames, on the other regions or their order, or
+ * on the call being repeated.
+ * Two launches (csrc/correlate.hip), enqueued on the current stream behind the frames they read; the table comes back through one
+ * device-to-host copy and one synchronise.  info and device_ms may be NULL; device_ms: the time between two events around the launches.
+ * Refusals, all decided BEFORE ANYTHING IS ENQUEUED and leaving every output unwritten: count 0 or > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES,
+ * region_count 0 (regions given) or > BEAMFORMER_HIP_MAX_CORRELATION_REGIONS, a max_shift entry > BEAMFORMER_HIP_MAX_SHIFT,
+ * T > BEAMFORMER_HIP_MAX_SHIFTS, regions x K x T > BEAMFORMER_HIP_MAX_CORRELATION_ENTRIES: BufferOverflow; table or max_shift NULL,
+ * reference >= count, a region with a zero count or one that does not fit inside the frames, a box of 2^32 voxels or more, and
+ * everything beamformer_hip_score_last_frames refuses, several devices included: InvalidAccess; frames that differ in grid or kind:
+ * DataSizeMismatch.  A window wider than an axis is legal, also on an axis of 1 point: its out-of-frame shifts have no terms. */
+#define BEAMFORMER_HIP_MAX_SHIFT                16u          /* per axis */
+#define BEAMFORMER_HIP_MAX_SHIFTS               1089u        /* product of (2 S_a + 1): 33 x 33 on a plane, 9 x 9 x 9 in a volume */
+#define BEAMFORMER_HIP_MAX_CORRELATION_REGIONS  256u
+#define BEAMFORMER_HIP_MAX_CORRELATION_ENTRIES  (1u << 20)   /* regions x frames x shifts */
+typedef struct {
+	double   re, im, energy_reference, energy_frame;
+	uint64_t terms;
+} BeamformerHipShiftCorrelation;              /* 40 bytes, no padding */
+typedef struct {
+	uint32_t count, reference, data_kind, region_count;
+	uint32_t points[3], max_shift[3];
+	uint32_t shifts;                          /* T */
+	uint32_t first_frame_id, reference_frame_id;
+	uint32_t reserved;
+} BeamformerHipCorrelationInfo;               /* 56 bytes, no padding */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions,
+                                                                    uint32_t region_count, const uint32_t max_shift[3],
+                                                                    BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info,
+                                                                    float *device_ms);
+/* Host only (no device, no library state but the last error): one displacement a table of T entries, in double.
+ * CANDIDATES: the entries with terms > 0, all four doubles finite and -- when `normalised` -- both energies > 0.
+ * SCORE q = re^2 + im^2, divided by energy_reference * energy_frame when `normalised`.  PEAK: the largest q, the lowest flat shift
+ * index among equals; m = sqrt(q).  FIT: axis a is fitted when S_a > 0, both neighbours at -1 and +1 along it lie in the window and
+ * are candidates, and den = (m- + m+) - (m0 + m0) < 0; then offset = 0.5 (m- - m+) / den, clamped to [-0.5, 0.5] (the peaks'
+ * parabola, in double).  A table without a candidate gives a row of zero bytes.  Returns 1 when at least one table had a candidate;
+ * 0 with InvalidAccess for a NULL argument, or when no table had one (out is filled all the same); 0 with BufferOverflow for
+ * table_count 0, a max_shift entry > BEAMFORMER_HIP_MAX_SHIFT or T > BEAMFORMER_HIP_MAX_SHIFTS. */
+typedef struct {
+	float    displacement[3];                 /* voxels: integer peak + sub-voxel offset */
+	int32_t  shift[3];                        /* the integer peak */
+	float    coefficient;                     /* |C| / sqrt(energy_reference * energy_frame) at the peak, 0 where an energy is 0 */
+	float    phase;                           /* atan2(im, re) at the peak: sub-wavelength axial motion of IQ frames */
+	uint32_t fitted;                          /* bit a: axis a was fitted */
+	uint32_t at_window_edge;                  /* bit a: S_a > 0 and |shift[a]| == S_a -- the true shift may lie outside the window */
+} BeamformerHipDisplacement;                  /* 40 bytes, no padding */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_displacements_from_correlation(const BeamformerHipShiftCorrelation *tables, uint32_t table_count,
+                                                                             const uint32_t max_shift[3], uint32_t normalised,
+                                                                             BeamformerHipDisplacement *out);
+
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
  * times with the voxel and pair counts of the whole frame and the slowest device's frame time.) */

@@ -457,6 +457,64 @@ typedef struct {
 	uint32_t run_blocks, run_chunks;
 } BfSpatialArgs;
 
+/* ---- shift correlation (correlate.hip: beamformer_hip_correlate_last_frames) ---- */
+#define BF_CORRELATE_MAX_SHIFT    16u        /* = BEAMFORMER_HIP_MAX_SHIFT */
+#define BF_CORRELATE_MAX_SHIFTS   1089u      /* = BEAMFORMER_HIP_MAX_SHIFTS */
+#define BF_CORRELATE_THREADS      256u
+#define BF_CORRELATE_MAX_BATCHES  5u         /* ceil(1089 / 256): the shifts a thread owns when the window has more shifts than the block threads */
+#define BF_CORRELATE_TILE_VOXELS  1024u      /* reference voxels a staged tile holds at most: 16 KiB of LDS */
+#define BF_CORRELATE_HALO_VOXELS  4096u      /* voxels of the tile plus its halo at most: 32 KiB of LDS and 4 KiB of validity bytes */
+/* The tile of a box under a window: from 32 voxels an axis (no more than the box has), the longest side halved -- z before y before x
+ * among equals, so that rows stay long -- until the tile holds at most 1024 voxels and the tile plus its halo of S voxels either side at
+ * most 4096.  It ends: a tile of one voxel has a halo of T <= 1089.  A function of the box and the window alone. */
+static inline void bf_correlate_tile(const uint32_t count[3], const uint32_t max_shift[3], uint32_t tile[3])
+{
+	for (int a = 0; a < 3; a++) tile[a] = count[a] < 32u ? count[a] : 32u;
+	for (;;) {
+		const uint32_t voxels = tile[0] * tile[1] * tile[2];
+		const uint32_t halo = (tile[0] + 2u * max_shift[0]) * (tile[1] + 2u * max_shift[1]) * (tile[2] + 2u * max_shift[2]);
+		if (voxels <= BF_CORRELATE_TILE_VOXELS && halo <= BF_CORRELATE_HALO_VOXELS) return;
+		int longest = 2;
+		if (tile[1] > tile[longest]) longest = 1;
+		if (tile[0] > tile[longest]) longest = 0;
+		tile[longest] = (tile[longest] + 1u) / 2u;
+	}
+}
+/* tiles (in flat order, x fastest) a block of the partial pass walks: at most max(16, min(64, 16384 / T)) chunks a box -- 64 up to 256
+ * shifts, 16 at 1089, where an entry's partials are large and a block's work long; a box of one tile is one chunk.  A function of the
+ * box and the window alone: NOT of the frame count. */
+static inline uint32_t bf_correlate_chunk_tiles(uint32_t tiles, uint32_t shifts)
+{
+	uint32_t cap = 16384u / shifts;
+	cap = cap < 16u ? 16u : cap > 64u ? 64u : cap;
+	return (tiles + cap - 1u) / cap;
+}
+/* voxel groups of a block: floor(256 / T) groups of T threads share a tile's voxels (group g takes the voxels n = g, g + G, ...); one
+ * group from 129 shifts on */
+static inline uint32_t bf_correlate_groups(uint32_t shifts) { return shifts < BF_CORRELATE_THREADS ? BF_CORRELATE_THREADS / shifts : 1u; }
+typedef struct {                 /* one box of a call */
+	uint32_t first[3], count[3]; /* inside the frames' grid, every count >= 1 */
+	uint32_t tile[3];            /* bf_correlate_tile */
+	uint32_t tiles[3];           /* ceil(count / tile) an axis */
+	uint32_t halo[3];            /* tile + 2 S */
+	uint32_t tile_voxels, halo_voxels;
+	uint32_t chunk_tiles, chunks;/* bf_correlate_chunk_tiles; ceil(tiles / chunk_tiles) */
+	uint32_t reserved;
+	uint64_t partial_first;      /* its first BfCorrelateEntry among the partials: [chunk][frame][shift] from there */
+} BfCorrelateRow;
+typedef struct { double re, im, energy_reference, energy_frame; uint64_t terms; } BfCorrelateEntry;   /* = BeamformerHipShiftCorrelation */
+typedef struct {
+	uint32_t frames, reference;  /* K; the reference's index among them */
+	uint32_t cplx, regions;      /* 1: Float32Complex, 0: Float32; R */
+	uint32_t points[3];          /* the frames' common grid */
+	uint32_t max_shift[3];       /* S */
+	uint32_t window[3];          /* 2 S + 1 */
+	uint32_t shifts;             /* T */
+	uint32_t groups, batches;    /* bf_correlate_groups; ceil(T / 256) */
+	uint32_t max_chunks;         /* the most chunks any row has: grid x */
+	uint32_t reserved;
+} BfCorrelateArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -527,6 +585,12 @@ hipError_t bf_launch_autocorr(void *ring, const uint64_t *offsets, const float *
  * pass, frame k at k * d_stride floats (d_in: stage 2; d_out: stages 1 and 2 unless `last`) */
 hipError_t bf_launch_spatial(const void *in, const uint64_t *offsets, void *out, const float *d_in, float *d_out, const float *taps,
                              const BfSpatialArgs *a, hipStream_t s);
+/* correlate.hip: two launches, no atomics -- the partial pass (grid x the chunk of a box's tiles, y the frame, z the region: one
+ * BfCorrelateEntry a shift a block) and the fold (a thread an entry of the table sums its chunks' partials in chunk order).
+ * offsets[frames]: where each frame lies in the ring, bytes, oldest first; rows[regions]; table[regions][frames][shifts].  All tables are
+ * device memory; every row's box lies inside the frames and its geometry is what the functions above give (the caller's business) */
+hipError_t bf_launch_correlate(const void *ring, const uint64_t *offsets, const BfCorrelateRow *rows, const BfCorrelateArgs *a,
+                               BfCorrelateEntry *partials, BfCorrelateEntry *table, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

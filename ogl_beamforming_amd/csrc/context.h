@@ -286,6 +286,8 @@ bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
                             uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
                             float *device_ms);                     /* arguments checked by the caller (lib_api.cpp) */
 bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms);
+bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions, uint32_t region_count,
+                           const uint32_t max_shift[3], BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info, float *device_ms);
 bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id,
                      float *device_ms);                            /* arguments checked by the caller (lib_api.cpp), but for what needs the frames' kind */
 bool autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows, uint32_t lag_count, uint32_t image_plane_tag,

@@ -2661,6 +2661,94 @@ bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, do
 	return true;
 }
 
+/* beamformer_hip_correlate_last_frames: the `count` newest frames correlated with one of them at every shift of the window, over every
+ * box, where they lie (correlate.hip).  The arguments arrive checked (lib_api.cpp: the counts, the window, the entry cap); everything
+ * else that can refuse is decided before anything is enqueued. */
+bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions, uint32_t region_count,
+                           const uint32_t max_shift[3], BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info, float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipShiftCorrelation) == 40 && sizeof(BfCorrelateEntry) == 40, "one record, without padding");
+	static_assert(sizeof(BeamformerHipCorrelationInfo) == 56, "a record without padding");
+	static_assert(BF_CORRELATE_MAX_SHIFT == BEAMFORMER_HIP_MAX_SHIFT && BF_CORRELATE_MAX_SHIFTS == BEAMFORMER_HIP_MAX_SHIFTS, "one limit");
+	const uint32_t boxes = regions ? region_count : 1u;
+
+	BfCorrelateArgs a{};
+	a.frames = count; a.reference = reference; a.regions = boxes;
+	a.shifts = 1;
+	for (int k = 0; k < 3; k++) { a.max_shift[k] = max_shift[k]; a.window[k] = 2u * max_shift[k] + 1u; a.shifts *= a.window[k]; }
+	a.groups = bf_correlate_groups(a.shifts);
+	a.batches = (a.shifts + BF_CORRELATE_THREADS - 1u) / BF_CORRELATE_THREADS;
+
+	/* the frames once a box: the same K records each time, and the box of each region judged against every one of them */
+	std::vector<BoxedFrame> boxed, frames;
+	std::vector<BfCorrelateRow> rows(boxes);
+	uint64_t partials = 0;
+	for (uint32_t r = 0; r < boxes; r++) {
+		if (!newest_ensemble_frames(count, regions ? regions + r : nullptr, boxed)) return false;
+		const BoxedFrame &b = boxed[0];
+		if (b.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);      /* the kernels count a box's voxels in 32 bits */
+		if (r == 0) frames = boxed;
+		BfCorrelateRow &row = rows[r];
+		row = BfCorrelateRow{};
+		for (int k = 0; k < 3; k++) { row.first[k] = b.first[k]; row.count[k] = b.count[k]; }
+		bf_correlate_tile(row.count, a.max_shift, row.tile);
+		uint32_t tiles = 1;                                   /* (at most the box's voxels) */
+		row.tile_voxels = 1; row.halo_voxels = 1;
+		for (int k = 0; k < 3; k++) {
+			row.tiles[k] = (row.count[k] + row.tile[k] - 1u) / row.tile[k];
+			row.halo[k] = row.tile[k] + 2u * a.max_shift[k];
+			tiles *= row.tiles[k]; row.tile_voxels *= row.tile[k]; row.halo_voxels *= row.halo[k];
+		}
+		row.chunk_tiles = bf_correlate_chunk_tiles(tiles, a.shifts);
+		row.chunks = (tiles + row.chunk_tiles - 1u) / row.chunk_tiles;
+		row.partial_first = partials;
+		partials += (uint64_t)row.chunks * count * a.shifts;
+		if (row.chunks > a.max_chunks) a.max_chunks = row.chunks;
+	}
+	Device &d = g_context.devices[0];
+	const BoxedFrame &b0 = frames[0];
+	a.cplx = b0.cplx;
+	for (int k = 0; k < 3; k++) a.points[k] = b0.record->points[k];
+
+	/* device: offsets | rows | table | partials; pinned: offsets | rows | table */
+	const size_t entries = (size_t)boxes * count * a.shifts;
+	const size_t offsets_bytes = round_up(sizeof(uint64_t) * count, 64), rows_bytes = round_up(sizeof(BfCorrelateRow) * boxes, 64),
+	             table_bytes = round_up(sizeof(BfCorrelateEntry) * entries, 64), partials_bytes = sizeof(BfCorrelateEntry) * (size_t)partials;
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && ensure_metrics_memory(d, offsets_bytes + rows_bytes + table_bytes, offsets_bytes + rows_bytes + table_bytes + partials_bytes);
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
+	uint64_t *offsets = (uint64_t *)pinned;
+	for (uint32_t n = 0; n < count; n++) offsets[n] = frames[n].record->offset;
+	std::memcpy(pinned + offsets_bytes, rows.data(), sizeof(BfCorrelateRow) * boxes);
+	hipStream_t s = d.stream;
+	ok &= HIP_OK(hipMemcpyAsync(device, pinned, offsets_bytes + sizeof(BfCorrelateRow) * boxes, hipMemcpyHostToDevice, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
+	if (ok) ok &= HIP_OK(bf_launch_correlate(d.ring.ptr, (const uint64_t *)device, (const BfCorrelateRow *)(device + offsets_bytes), &a,
+	                                         (BfCorrelateEntry *)(device + offsets_bytes + rows_bytes + table_bytes),
+	                                         (BfCorrelateEntry *)(device + offsets_bytes + rows_bytes), s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
+	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + offsets_bytes + rows_bytes, device + offsets_bytes + rows_bytes, sizeof(BfCorrelateEntry) * entries,
+	                                    hipMemcpyDeviceToHost, s));
+	/* the synchronise runs whatever failed above: it is what frees the pinned memory */
+	ok &= HIP_OK(hipStreamSynchronize(s));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (device_ms) {
+		float ms = 0;
+		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
+	}
+	std::memcpy(table, pinned + offsets_bytes + rows_bytes, sizeof(BfCorrelateEntry) * entries);
+	if (info) {
+		std::memset(info, 0, sizeof(*info));
+		info->count = count; info->reference = reference; info->data_kind = (uint32_t)b0.record->data_kind; info->region_count = boxes;
+		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->max_shift[k] = a.max_shift[k]; }
+		info->shifts = a.shifts;
+		info->first_frame_id = b0.record->id; info->reference_frame_id = frames[reference].record->id;
+	}
+	return true;
+}
+
 namespace {
 
 /* What beamformer_hip_mix_last_frames, beamformer_hip_autocorrelate_last_frames and beamformer_hip_convolve_last_frames share:

@@ -1071,6 +1071,88 @@ uint32_t beamformer_hip_convolve_last_frames(uint32_t count, const float *const 
 	return convolve_last_frames(count, taps, tap_counts, mode, image_plane_tag, first_frame_id, device_ms);
 }
 
+uint32_t beamformer_hip_correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions, uint32_t region_count,
+                                              const uint32_t max_shift[3], BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info,
+                                              float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(!regions || (region_count >= 1 && region_count <= BEAMFORMER_HIP_MAX_CORRELATION_REGIONS), BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(table != nullptr && max_shift != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	uint64_t shifts = 1;
+	for (int a = 0; a < 3; a++) {
+		if (!check(max_shift[a] <= BEAMFORMER_HIP_MAX_SHIFT, BeamformerLibErrorKind_BufferOverflow)) return 0;
+		shifts *= 2u * max_shift[a] + 1u;
+	}
+	if (!check(shifts <= BEAMFORMER_HIP_MAX_SHIFTS, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check((uint64_t)(regions ? region_count : 1u) * count * shifts <= BEAMFORMER_HIP_MAX_CORRELATION_ENTRIES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(reference < count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return correlate_last_frames(count, reference, regions, region_count, max_shift, table, info, device_ms);
+}
+
+/* host only: the peak of every table and a parabola through its neighbours along each axis (include/ogl_beamformer_hip.h has the rules) */
+uint32_t beamformer_hip_displacements_from_correlation(const BeamformerHipShiftCorrelation *tables, uint32_t table_count, const uint32_t max_shift[3],
+                                                       uint32_t normalised, BeamformerHipDisplacement *out)
+{
+	static_assert(sizeof(BeamformerHipDisplacement) == 40 && sizeof(BeamformerHipShiftCorrelation) == 40, "records without padding");
+	if (!check(tables != nullptr && max_shift != nullptr && out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(table_count >= 1, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	uint32_t window[3], shifts = 1;
+	for (int a = 0; a < 3; a++) {
+		if (!check(max_shift[a] <= BEAMFORMER_HIP_MAX_SHIFT, BeamformerLibErrorKind_BufferOverflow)) return 0;
+		window[a] = 2u * max_shift[a] + 1u;
+		shifts *= window[a];
+	}
+	if (!check(shifts <= BEAMFORMER_HIP_MAX_SHIFTS, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	const uint32_t stride[3] = {1u, window[0], window[0] * window[1]};
+	/* an entry's score; negative: no candidate */
+	auto score = [normalised](const BeamformerHipShiftCorrelation &e) -> double {
+		if (!e.terms || !std::isfinite(e.re) || !std::isfinite(e.im) || !std::isfinite(e.energy_reference) || !std::isfinite(e.energy_frame)) return -1.0;
+		const double q = e.re * e.re + e.im * e.im;
+		if (!normalised) return q;
+		if (!(e.energy_reference > 0.0) || !(e.energy_frame > 0.0)) return -1.0;
+		return q / (e.energy_reference * e.energy_frame);
+	};
+	bool any = false;
+	for (uint32_t n = 0; n < table_count; n++) {
+		const BeamformerHipShiftCorrelation *t = tables + (size_t)n * shifts;
+		BeamformerHipDisplacement &d = out[n];
+		std::memset(&d, 0, sizeof(d));
+		double   best = -1.0;
+		uint32_t best_at = 0;
+		for (uint32_t s = 0; s < shifts; s++) {
+			const double q = score(t[s]);
+			if (q >= 0.0 && q > best) { best = q; best_at = s; }
+		}
+		if (best < 0.0) continue;
+		any = true;
+		const BeamformerHipShiftCorrelation &peak = t[best_at];
+		const uint32_t index[3] = {best_at % window[0], best_at / window[0] % window[1], best_at / (window[0] * window[1])};
+		const double m0 = std::sqrt(best);
+		for (int a = 0; a < 3; a++) {
+			const int32_t shift = (int32_t)index[a] - (int32_t)max_shift[a];
+			double offset = 0.0;
+			if (max_shift[a] > 0 && index[a] > 0 && index[a] + 1u < window[a]) {
+				const double below = score(t[best_at - stride[a]]), above = score(t[best_at + stride[a]]);
+				if (below >= 0.0 && above >= 0.0) {
+					const double lo = std::sqrt(below), hi = std::sqrt(above), den = (lo + hi) - (m0 + m0);
+					if (den < 0.0) {
+						offset = 0.5 * (lo - hi) / den;
+						offset = offset < -0.5 ? -0.5 : offset > 0.5 ? 0.5 : offset;
+						d.fitted |= 1u << a;
+					}
+				}
+			}
+			if (max_shift[a] > 0 && (uint32_t)(shift < 0 ? -shift : shift) == max_shift[a]) d.at_window_edge |= 1u << a;
+			d.shift[a] = shift;
+			d.displacement[a] = (float)((double)shift + offset);
+		}
+		const double energy = peak.energy_reference * peak.energy_frame;
+		d.coefficient = energy > 0.0 ? (float)(std::sqrt(peak.re * peak.re + peak.im * peak.im) / std::sqrt(energy)) : 0.0f;
+		d.phase = (float)std::atan2(peak.im, peak.re);
+	}
+	return check(any, BeamformerLibErrorKind_InvalidAccess) ? 1 : 0;
+}
+
 uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

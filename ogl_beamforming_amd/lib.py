@@ -139,6 +139,9 @@ def _load():
         "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_autocorrelate_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_convolve_last_frames": (u32, [u32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(u32), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_correlate_last_frames": (u32, [u32, u32, C.POINTER(P.HipFrameRegion), u32, C.POINTER(u32), C.POINTER(P.HipShiftCorrelation),
+                                                       C.POINTER(P.HipCorrelationInfo), C.POINTER(C.c_float)]),
+        "beamformer_hip_displacements_from_correlation": (u32, [C.POINTER(P.HipShiftCorrelation), u32, C.POINTER(u32), u32, C.POINTER(P.HipDisplacement)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -634,6 +637,48 @@ def convolve_last_frames(count, taps, mode=0, tag=0, timed=True):
     _check(library().beamformer_hip_convolve_last_frames(int(count), pointers, counts, int(mode), int(tag), C.byref(first),
                                                          C.byref(ms) if timed else None))
     return int(first.value), float(ms.value)
+
+
+def correlate_last_frames(count, reference, max_shift, regions=None):
+    """beamformer_hip_correlate_last_frames: each of the `count` newest frames (one grid, one kind) correlated on the device with frame
+    `reference` of them (0: the oldest) at every integer shift |s_a| <= max_shift[a] (x, y, z), over each box of `regions` (a sequence
+    of HipFrameRegion: see frame_region()); regions None: one box, the frames whole.  Returns (table, info, device_ms): a structured
+    array (P.HipShiftCorrelation's fields) of shape (R, count, 2 Sz + 1, 2 Sy + 1, 2 Sx + 1) -- table[r, k, sz + Sz, sy + Sy, sx + Sx];
+    if frame k is the reference moved by d voxels, |re + i im| peaks at s = d --, the HipCorrelationInfo and the device time of the
+    launches."""
+    count, reference = int(count), int(reference)
+    S = [int(v) for v in max_shift]
+    if len(S) != 3:
+        raise ValueError("max_shift: one number per axis, x, y, z")
+    boxes = None if regions is None else list(regions)
+    R = 1 if boxes is None else len(boxes)
+    window = [2 * v + 1 if 0 <= v <= P.HIP_MAX_SHIFT else 1 for v in S]
+    shape = (max(1, R), max(1, count), window[2], window[1], window[0])
+    if int(np.prod(shape)) > P.HIP_MAX_CORRELATION_ENTRIES:
+        shape = (1, 1, 1, 1, 1)         # the call refuses before it writes: room for nothing
+    table = np.zeros(shape, np.dtype(P.HipShiftCorrelation))
+    array = None if boxes is None else (P.HipFrameRegion * max(1, R))(*boxes)
+    info, ms = P.HipCorrelationInfo(), C.c_float(0)
+    _check(library().beamformer_hip_correlate_last_frames(count, reference, array, R, (C.c_uint32 * 3)(*[v & 0xFFFFFFFF for v in S]),
+                                                          table.ctypes.data_as(C.POINTER(P.HipShiftCorrelation)), C.byref(info), C.byref(ms)))
+    return table, info, float(ms.value)
+
+
+def displacements_from_correlation(tables, max_shift, normalised=True):
+    """beamformer_hip_displacements_from_correlation (host only): one displacement a table.  tables: what correlate_last_frames returns,
+    or any array of P.HipShiftCorrelation entries whose last axes hold whole tables of T = prod(2 max_shift + 1) entries.  Returns a
+    structured array (P.HipDisplacement's fields) with the leading shape of `tables` -- (R, K) for correlate_last_frames' table; an
+    empty table's row is zero.  Raises when no table has a candidate."""
+    tables = np.ascontiguousarray(tables, np.dtype(P.HipShiftCorrelation))
+    S = [int(v) for v in max_shift]
+    T = int(np.prod([2 * v + 1 for v in S]))
+    n = tables.size // T if T > 0 and tables.size % T == 0 else 0
+    lead = tables.shape[:-3] if tables.ndim >= 3 and tables.shape[-3:] == (2 * S[2] + 1, 2 * S[1] + 1, 2 * S[0] + 1) else (n,)
+    out = np.zeros(max(1, n), np.dtype(P.HipDisplacement))
+    _check(library().beamformer_hip_displacements_from_correlation(tables.ctypes.data_as(C.POINTER(P.HipShiftCorrelation)), n,
+                                                                   (C.c_uint32 * 3)(*[v & 0xFFFFFFFF for v in S]), 1 if normalised else 0,
+                                                                   out.ctypes.data_as(C.POINTER(P.HipDisplacement))))
+    return out[:n].reshape(lead)
 
 
 def frame_info(frame_id):

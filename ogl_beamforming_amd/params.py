@@ -345,6 +345,30 @@ class HipEnsembleInfo(C.Structure):
                 ("region_count", C.c_uint32 * 3), ("first_frame_id", C.c_uint32), ("voxels", C.c_uint64), ("non_finite", C.c_uint64)]
 
 
+HIP_MAX_SHIFT = 16                      # BEAMFORMER_HIP_MAX_SHIFT
+HIP_MAX_SHIFTS = 1089                   # BEAMFORMER_HIP_MAX_SHIFTS
+HIP_MAX_CORRELATION_REGIONS = 256       # BEAMFORMER_HIP_MAX_CORRELATION_REGIONS
+HIP_MAX_CORRELATION_ENTRIES = 1 << 20   # BEAMFORMER_HIP_MAX_CORRELATION_ENTRIES
+
+
+class HipShiftCorrelation(C.Structure):
+    """BeamformerHipShiftCorrelation: one entry (region, frame, shift) of beamformer_hip_correlate_last_frames (40 bytes, no padding)"""
+    _fields_ = [("re", C.c_double), ("im", C.c_double), ("energy_reference", C.c_double), ("energy_frame", C.c_double), ("terms", C.c_uint64)]
+
+
+class HipCorrelationInfo(C.Structure):
+    """BeamformerHipCorrelationInfo: what beamformer_hip_correlate_last_frames reduced (56 bytes, no padding)"""
+    _fields_ = [("count", C.c_uint32), ("reference", C.c_uint32), ("data_kind", C.c_uint32), ("region_count", C.c_uint32),
+                ("points", C.c_uint32 * 3), ("max_shift", C.c_uint32 * 3), ("shifts", C.c_uint32),
+                ("first_frame_id", C.c_uint32), ("reference_frame_id", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HipDisplacement(C.Structure):
+    """BeamformerHipDisplacement: one table's row of beamformer_hip_displacements_from_correlation (40 bytes, no padding)"""
+    _fields_ = [("displacement", C.c_float * 3), ("shift", C.c_int32 * 3), ("coefficient", C.c_float), ("phase", C.c_float),
+                ("fitted", C.c_uint32), ("at_window_edge", C.c_uint32)]
+
+
 class FrameScore(enum.IntEnum):
     """BeamformerHipFrameScore: the criteria of beamformer_hip_rank_frames"""
     Energy = 0
