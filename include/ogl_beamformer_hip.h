@@ -760,8 +760,8 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_convolve_last_frames(uint32_t coun
 /* ---- shift correlation: frame-to-frame motion estimated on the device.  Every operator above assumes that voxel v of frame k and
  * voxel v of frame j show the same tissue; over an ensemble they do not.  This call correlates each of the K newest frames with one of
  * them at every integer shift of a window, over one box (rigid motion) or many small ones (block matching: a displacement field), and
- * a host helper turns the tables into displacements.  An integer correction is then one beamformer_hip_convolve_last_frames with a
- * shifted delta; a sub-voxel one is an addition to localisations on the host ----
+ * a host helper turns the tables into displacements.  beamformer_hip_warp_last_frames (below) applies them: it resamples the frames
+ * at the displaced positions, per frame or as a field ----
  * DEFINITION (tests/motion_ref.py restates it in numpy).
  * SOURCES.  The `count` = K newest frames of the ring, of one grid and one kind: beamformer_hip_gram_last_frames' rules and refusals.
  * Index 0 is the oldest frame; ref is frame `reference` (< K).
@@ -827,6 +827,76 @@ typedef struct {
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_displacements_from_correlation(const BeamformerHipShiftCorrelation *tables, uint32_t table_count,
                                                                              const uint32_t max_shift[3], uint32_t normalised,
                                                                              BeamformerHipDisplacement *out);
+
+/* ---- warp: ring frames resampled at displaced positions, written back into the ring: motion compensation.  The shift correlation
+ * above estimates how the frames of an ensemble moved; this call applies the estimate -- a rigid shift per frame or a displacement
+ * field on a lattice of nodes (the block-matching result) --, so that the slow-time operators behind it (Gram matrix, mix,
+ * autocorrelation, peaks) see voxel v of every frame on the same tissue ----
+ * DEFINITION (tests/warp_ref.py restates it in numpy).  Every operation named below is ONE float32 operation, fmaf one rounding.
+ * SOURCES.  The `count` = K newest frames of the ring, of one grid (nx, ny, nz) and one kind: beamformer_hip_mix_last_frames' rules
+ * and refusals.  Index 0 is the oldest frame.  Axis a: 0 = x, the fastest; 1 = y; 2 = z.
+ * FIELD.  field[frame][jz][jy][jx][3] floats: the displacement in voxels (x, y, z) at the nodes of a lattice of N_a = nodes[a] >= 1
+ * nodes an axis; node j of axis a sits at voxel coordinate node_first[a] + j * node_step[a].  One lattice for all frames, values per
+ * frame; nodes = {1, 1, 1}: a rigid shift per frame.  The displacement d(v) at voxel v = (vx, vy, vz) is the trilinear interpolation
+ * of the nodes, constant outside the lattice: per axis with N_a > 1
+ *     c_a = ((float)v_a - node_first[a]) * inv_step_a,   inv_step_a = 1.0f / node_step[a] (one float32 division, on the host),
+ *     c_a clamped to [0, N_a - 1] (fmaxf, then fminf),   j_a = min((int)floorf(c_a), N_a - 2),   s_a = c_a - (float)j_a,
+ * and per component the lerps  fmaf(s, b - a, a)  (a: the value at the lower index) along x between nodes j_x and j_x + 1 -- for each
+ * of the four (j_y + 0 | 1, j_z + 0 | 1) --, then along y over those results, then along z.  An axis with N_a == 1 is not interpolated:
+ * its node index is 0, its lerp is left out, node_first[a] and node_step[a] are not read.
+ * SIGN.  Output n at voxel v is source n sampled at p = v + d_n(v): the correlation's sign -- if f_k[v + d] = ref[v], warping f_k by d
+ * gives ref --, so a BeamformerHipDisplacement.displacement goes into the field as it is.
+ * POSITION AND WEIGHTS.  Per axis with more than one point: p_a = (float)v_a + d_a, i_a = floorf(p_a), t = p_a - i_a.
+ * BeamformerHipWarpInterpolation_Linear: taps at i_a, i_a + 1 with weights  1.0f - t,  t.
+ * BeamformerHipWarpInterpolation_Cubic: Catmull-Rom, taps at i_a - 1 .. i_a + 2 with weights
+ *     w0 = fmaf(fmaf(-0.5f, t, 1.0f), t, -0.5f) * t,          w1 = fmaf(fmaf(1.5f, t, -2.5f) * t, t, 1.0f),
+ *     w2 = fmaf(fmaf(-1.5f, t, 2.0f), t, 0.5f) * t,           w3 = (fmaf(0.5f, t, -0.5f) * t) * t.
+ * An axis of ONE point is not interpolated: that component of the field is not read, and the axis has one tap, at index 0, of weight
+ * exactly 1.0f -- a view plane costs 4 taps (Linear) or 16 (Cubic), not 8 or 64.  There is no nearest mode.
+ * SUM.  Separable: along x for every (y, z) row of the support, then along y over those results, then along z; each of these is ONE
+ * float32 fmaf chain from +0 in ascending tap index, acc = fmaf(w, value, acc); the real and the imaginary float of a complex voxel
+ * are independent chains under the same weights.
+ * EDGE.  BeamformerHipWarpEdge_Zero: a term whose source index (along the chain's axis) lies outside the frame is skipped, as the
+ * convolution skips it; a chain without terms is +0.  BeamformerHipWarpEdge_Clamp: the index is clamped to 0 .. extent - 1 -- the
+ * edge voxel repeats, and a compensated frame does not darken at its rim.  Both make the output a continuous function of p.
+ * Otherwise plain IEEE: a source voxel under the support that is not finite makes the output not finite, no weight is skipped for
+ * being zero.
+ * ROTATIONS.  rotations[frame][2] = (re, im), may be NULL (then nothing is multiplied).  After the sum a complex output (x, y) becomes
+ *     re' = fmaf(-im, y, fmaf(re, x, +0)),   im' = fmaf(re, y, fmaf(im, x, +0))
+ * -- the mix's two chains for a one-term product: exp(-i phase) of a displacement's `phase` is the phase correction an IQ ensemble
+ * needs after axial motion.  A real output x becomes fmaf(re, x, +0); a nonzero imaginary part on real frames is refused.
+ * The bytes of output n depend on source n, its own rows of the field and of the rotations, the lattice and the two modes only -- not
+ * on count, on the other frames, on the call being repeated, or on which of the kernel's two paths a tile took.
+ * OUTPUTS.  `count` new frames of the sources' grid and kind, output n source n warped, oldest first, placed, numbered, recorded and
+ * timed exactly as beamformer_hip_convolve_last_frames' run is, the record of the newest multi-frame push and *first_frame_id (may be
+ * NULL) included.  One launch (csrc/warp.hip) on the current stream behind the frames it reads; the call does not synchronise unless
+ * device_ms is not NULL (then: the time between two events around the launch).
+ * Refusals, all decided BEFORE ANYTHING CHANGES and leaving every output unwritten: count 0 or > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, a
+ * nodes entry 0, the product of nodes > BEAMFORMER_HIP_MAX_WARP_NODES, count x that product > BEAMFORMER_HIP_MAX_WARP_ENTRIES:
+ * BufferOverflow (count first, then -- once nodes is known not to be NULL -- the lattice); field, nodes, node_first or node_step
+ * NULL, a field value, a rotation or a node_first that is not finite, a field value of magnitude > BEAMFORMER_HIP_MAX_WARP_DISPLACEMENT,
+ * a node_step that is not finite or <= 0 on an axis with more than one node (with one node it is not read), an unknown interpolation
+ * or edge, a nonzero imaginary rotation on real frames, a frame of more than 2^31 - 1 voxels, and everything
+ * beamformer_hip_score_last_frames refuses, several devices included: InvalidAccess; frames that differ in grid or kind:
+ * DataSizeMismatch; a run of `count` frames that does not fit the ring, or that would reuse storage of one of its own source frames:
+ * FrameSizeOverflow. */
+#define BEAMFORMER_HIP_MAX_WARP_NODES        4096u        /* product of nodes */
+#define BEAMFORMER_HIP_MAX_WARP_ENTRIES      32768u       /* count x product of nodes */
+#define BEAMFORMER_HIP_MAX_WARP_DISPLACEMENT 65536.0f     /* |component| of a field value, voxels */
+typedef enum {
+	BeamformerHipWarpInterpolation_Linear = 0,
+	BeamformerHipWarpInterpolation_Cubic  = 1,
+	BeamformerHipWarpInterpolation_Count
+} BeamformerHipWarpInterpolation;
+typedef enum {
+	BeamformerHipWarpEdge_Zero  = 0,
+	BeamformerHipWarpEdge_Clamp = 1,
+	BeamformerHipWarpEdge_Count
+} BeamformerHipWarpEdge;
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3],
+                                                               const float node_first[3], const float node_step[3],
+                                                               const float *rotations, uint32_t interpolation, uint32_t edge,
+                                                               uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms);
 
 /* The newest frame as ONE of the devices of beamformer_hip_set_devices saw it: its slab's voxels and
  * pairs, its own event times.  (beamformer_hip_get_last_frame_timings reports the ingest device's stage
@@ -948,6 +1018,10 @@ typedef enum {
 	                                                  push is affected) */
 	BeamformerHipDasPath_NoVariantsKernel = 0x4000,/* flag: a variants push runs every variant's single-frame DAS kernel also where das_variants.hip would take it */
 	BeamformerHipDasPath_PreferVariantsKernel = 0x8000,/* flag: das_variants.hip takes the eligible variants however few their tiles (for tests) */
+	BeamformerHipDasPath_WarpDirect       = 0x10000,/* flag: every tile of beamformer_hip_warp_last_frames takes the direct path, also where its source box fits
+	                                                   the LDS budget (for tests and measurements: the bytes are the same).  A knob of that one call that merely
+	                                                   lives in this mode word: setting or clearing it changes no DAS kernel, but, like every change of the
+	                                                   mode, it makes the next push decide its cached DAS routes afresh */
 } BeamformerHipDasPath;
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_das_path(uint32_t mode);
 /* Environment variables the library reads (none is needed in production):

@@ -515,6 +515,37 @@ typedef struct {
 	uint32_t reserved;
 } BfCorrelateArgs;
 
+/* ---- warp (warp.hip: beamformer_hip_warp_last_frames) ---- */
+#define BF_WARP_THREADS     256u             /* lanes, and output voxels, of a block: a tile of 2^tile_log2[a] voxels an axis */
+#define BF_WARP_BOX_VOXELS  4096u            /* the staged path's LDS budget: source voxels a block stages (32 KiB complex, 16 KiB real) */
+#define BF_WARP_MAX_NODES   4096u            /* = BEAMFORMER_HIP_MAX_WARP_NODES */
+#define BF_WARP_MAX_ENTRIES 32768u           /* = BEAMFORMER_HIP_MAX_WARP_ENTRIES */
+typedef struct {
+	uint32_t frames, cplx;       /* K frames in, K out; 1: Float32Complex, 0: Float32 */
+	uint32_t cubic, clamp;       /* BeamformerHipWarpInterpolation, BeamformerHipWarpEdge */
+	uint32_t rotate;             /* 1: the table's rotations are applied */
+	uint32_t direct;             /* 1: every tile takes the direct path (measurements and tests; the bytes are the same) */
+	uint32_t points[3];          /* the frames' common grid */
+	uint32_t nodes[3];           /* N_a */
+	float    node_first[3], inv_step[3];   /* (not read where N_a == 1) */
+	uint64_t out_offset, out_stride;       /* output n at ring + out_offset + n * out_stride */
+	uint32_t tile_log2[3], tiles[3];       /* launch geometry, filled in by bf_launch_warp */
+} BfWarpArgs;
+/* the call's flat table: rotations[frames][2] | field[frames][nodes z][nodes y][nodes x][3] */
+static inline uint32_t bf_warp_table_floats(uint32_t frames, uint32_t node_product) { return frames * 2u + frames * node_product * 3u; }
+/* the tile of a grid: at most 256 voxels, the eight bits dealt round-robin, x first, over the axes whose tile does not yet cover the
+ * axis (8 x 8 x 4 in a volume, 16 x 16 on a plane, 256 along a line; 2 x 1 x N: 2 x 1 x 128; 1 x 1 x 1: one voxel).  Bits that no axis
+ * can take stay undealt: the lanes beyond the tile's voxels idle */
+static inline void bf_warp_tile(const uint32_t points[3], uint32_t tile_log2[3])
+{
+	uint32_t bits = 8, idle = 0, a = 0;
+	for (uint32_t k = 0; k < 3; k++) tile_log2[k] = 0;
+	while (bits && idle < 3u) {
+		if ((1u << tile_log2[a]) < points[a]) { tile_log2[a]++; bits--; idle = 0; } else idle++;
+		a = (a + 1u) % 3u;
+	}
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -591,6 +622,10 @@ hipError_t bf_launch_spatial(const void *in, const uint64_t *offsets, void *out,
  * device memory; every row's box lies inside the frames and its geometry is what the functions above give (the caller's business) */
 hipError_t bf_launch_correlate(const void *ring, const uint64_t *offsets, const BfCorrelateRow *rows, const BfCorrelateArgs *a,
                                BfCorrelateEntry *partials, BfCorrelateEntry *table, hipStream_t s);
+/* warp.hip: one launch.  Source n is read at ring + offsets[n] (offsets: device memory), output n written at ring + out_offset +
+ * n * out_stride; table: bf_warp_table_floats floats of device memory.  The frames hold at most 2^31 - 1 voxels, every field value
+ * is finite and of magnitude <= BEAMFORMER_HIP_MAX_WARP_DISPLACEMENT (the caller checks: the kernel converts positions to indices) */
+hipError_t bf_launch_warp(void *ring, const uint64_t *offsets, const float *table, const BfWarpArgs *a, hipStream_t s);
 /* out (device) = sum over the 8-byte words w[i] of the buffer of w[i] * (i + 1) mod 2^64 */
 hipError_t bf_launch_rf_checksum(const void *data, uint64_t bytes, unsigned long long *out, hipStream_t s);
 #ifdef __cplusplus

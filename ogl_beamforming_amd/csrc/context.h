@@ -78,7 +78,7 @@ struct PushRecord {
 	BeamformerHipVariantsDescription variants{};        /* Variants: its route */
 	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
-	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames / convolve_last_frames have queued behind the push: the push stays "the newest push" behind them */
+	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames / convolve_last_frames / warp_last_frames have queued behind the push: the push stays "the newest push" behind them */
 };
 
 struct PlanState {
@@ -174,7 +174,7 @@ struct Device {
 	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
 	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
 	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
-	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames: the source frames' ring offsets and the weight table (the tap table) of a call (ensemble.hip, autocorr.hip, spatial.hip) */
+	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
 	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
 	bool         mix_copy_pending = false;
@@ -294,6 +294,9 @@ bool autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t ro
                                uint32_t *first_frame_id, float *device_ms);   /* likewise; weights null: the identity form, rows == count */
 bool convolve_last_frames(uint32_t count, const float *const taps[3], const uint32_t tap_counts[3], uint32_t mode, uint32_t image_plane_tag,
                           uint32_t *first_frame_id, float *device_ms);        /* likewise: the taps and the mode are checked by the caller */
+bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3], const float node_first[3], const float node_step[3],
+                      const float *rotations, uint32_t interpolation, uint32_t edge, uint32_t image_plane_tag,
+                      uint32_t *first_frame_id, float *device_ms);            /* likewise: the field, the lattice and the modes are checked by the caller */
 const FrameRecord *record_of(const Device &d, uint32_t frame_id);   /* null: no such frame, a tombstone, or storage that a newer frame reused */
 bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
 bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);

@@ -2751,7 +2751,8 @@ bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerH
 
 namespace {
 
-/* What beamformer_hip_mix_last_frames, beamformer_hip_autocorrelate_last_frames and beamformer_hip_convolve_last_frames share:
+/* What beamformer_hip_mix_last_frames, beamformer_hip_autocorrelate_last_frames, beamformer_hip_convolve_last_frames and
+ * beamformer_hip_warp_last_frames share:
  * `out_count` frames computed from the `count` newest ones and queued as frames of their own behind them.  Everything that can refuse
  * is decided, and every buffer grown, before the ids are taken; nothing synchronises unless device_ms is asked for.
  * The call's table travels with the sources' ring offsets: a weight table of `rows` rows, laid out [tile][k][BF_MIX_TILE][2] (rows past
@@ -2963,6 +2964,48 @@ bool convolve_last_frames(uint32_t count, const float *const taps[3], const uint
 				in = out;
 			}
 			return hipSuccess;
+		});
+}
+
+/* beamformer_hip_warp_last_frames: the `count` newest frames resampled at v + d(v), queued as `count` frames of their own (warp.hip).
+ * One launch; the rotations and the field travel as the call's flat table (bf_warp_table_floats: within the table of a mix by the
+ * limits lib_api.cpp has checked), the lattice's constants as kernel arguments.  No memory of its own. */
+bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3], const float node_first[3], const float node_step[3],
+                      const float *rotations, uint32_t interpolation, uint32_t edge, uint32_t image_plane_tag,
+                      uint32_t *first_frame_id, float *device_ms)
+{
+	static_assert(BF_WARP_MAX_NODES == BEAMFORMER_HIP_MAX_WARP_NODES && BF_WARP_MAX_ENTRIES == BEAMFORMER_HIP_MAX_WARP_ENTRIES, "one limit");
+	static_assert(sizeof(float) * (2u * BF_ENSEMBLE_MAX_FRAMES + 3u * BF_WARP_MAX_ENTRIES) <= sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES,
+	              "the table of a warp fits the table of a mix");
+	const uint32_t node_product = nodes[0] * nodes[1] * nodes[2];
+	std::vector<float> table(bf_warp_table_floats(count, node_product));
+	for (uint32_t n = 0; n < count; n++) {
+		table[2u * n] = rotations ? rotations[2u * n] : 1.0f;
+		table[2u * n + 1u] = rotations ? rotations[2u * n + 1u] : 0.0f;
+	}
+	std::memcpy(table.data() + 2u * count, field, sizeof(float) * 3u * count * node_product);
+	BfWarpArgs a{};
+	a.cubic = interpolation == BeamformerHipWarpInterpolation_Cubic; a.clamp = edge == BeamformerHipWarpEdge_Clamp;
+	a.rotate = rotations != nullptr;
+	a.direct = (g_context.das_path_mode & BeamformerHipDasPath_WarpDirect) != 0;
+	for (int k = 0; k < 3; k++) {
+		a.nodes[k] = nodes[k];
+		if (nodes[k] > 1u) { a.node_first[k] = node_first[k]; a.inv_step[k] = 1.0f / node_step[k]; }
+	}
+	RunTable t; t.flat = table.data(); t.flat_floats = (uint32_t)table.size();
+	return queue_frames_of_newest(count, t, count, image_plane_tag, first_frame_id, device_ms,
+		[=](Device &, const FrameRecord &newest, bool cplx, uint32_t) {
+			if ((uint64_t)newest.points[0] * newest.points[1] * newest.points[2] > 0x7FFFFFFFull) return false;   /* the kernel indexes a frame's voxels in 32 bits */
+			for (uint32_t n = 0; n < count && rotations && !cplx; n++)
+				if (rotations[2u * n + 1u] != 0.0f) return false;
+			return true;
+		},
+		[=](const QueuedRun &r) {
+			BfWarpArgs args = a;
+			args.frames = r.K; args.cplx = r.cplx;
+			for (int k = 0; k < 3; k++) args.points[k] = r.points[k];
+			args.out_offset = r.out_offset; args.out_stride = r.out_stride;
+			return bf_launch_warp(r.ring, r.offsets, r.table, &args, r.s);
 		});
 }
 

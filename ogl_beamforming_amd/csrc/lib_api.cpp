@@ -1153,6 +1153,31 @@ uint32_t beamformer_hip_displacements_from_correlation(const BeamformerHipShiftC
 	return check(any, BeamformerLibErrorKind_InvalidAccess) ? 1 : 0;
 }
 
+uint32_t beamformer_hip_warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3], const float node_first[3],
+                                         const float node_step[3], const float *rotations, uint32_t interpolation, uint32_t edge,
+                                         uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(field != nullptr && nodes != nullptr && node_first != nullptr && node_step != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	uint64_t node_product = 1;
+	for (int a = 0; a < 3; a++) {
+		if (!check(nodes[a] >= 1, BeamformerLibErrorKind_BufferOverflow)) return 0;
+		node_product *= nodes[a];                             /* (at most 4096 x 2^32 - 1: no overflow) */
+		if (!check(node_product <= BEAMFORMER_HIP_MAX_WARP_NODES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	}
+	if (!check(count * node_product <= BEAMFORMER_HIP_MAX_WARP_ENTRIES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(interpolation < BeamformerHipWarpInterpolation_Count && edge < BeamformerHipWarpEdge_Count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (int a = 0; a < 3; a++) {
+		if (!check(std::isfinite(node_first[a]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+		if (nodes[a] > 1 && !check(std::isfinite(node_step[a]) && node_step[a] > 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	}
+	for (uint64_t n = 0; n < 3 * count * node_product; n++)
+		if (!check(std::isfinite(field[n]) && std::fabs(field[n]) <= BEAMFORMER_HIP_MAX_WARP_DISPLACEMENT, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (uint32_t n = 0; rotations && n < 2 * count; n++)
+		if (!check(std::isfinite(rotations[n]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return warp_last_frames(count, field, nodes, node_first, node_step, rotations, interpolation, edge, image_plane_tag, first_frame_id, device_ms);
+}
+
 uint32_t beamformer_hip_copy_frame(uint32_t frame_id, void *out, uint64_t out_size)
 {
 	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

@@ -142,6 +142,8 @@ def _load():
         "beamformer_hip_correlate_last_frames": (u32, [u32, u32, C.POINTER(P.HipFrameRegion), u32, C.POINTER(u32), C.POINTER(P.HipShiftCorrelation),
                                                        C.POINTER(P.HipCorrelationInfo), C.POINTER(C.c_float)]),
         "beamformer_hip_displacements_from_correlation": (u32, [C.POINTER(P.HipShiftCorrelation), u32, C.POINTER(u32), u32, C.POINTER(P.HipDisplacement)]),
+        "beamformer_hip_warp_last_frames": (u32, [u32, C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                  C.POINTER(C.c_float), u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_synchronize": (u32, []),
         "beamformer_hip_get_last_frame_info": (u32, [C.POINTER(P.HipFrameInfo)]),
         "beamformer_hip_get_last_frame_timings": (u32, [C.POINTER(P.HipFrameTimings)]),
@@ -679,6 +681,38 @@ def displacements_from_correlation(tables, max_shift, normalised=True):
                                                                    (C.c_uint32 * 3)(*[v & 0xFFFFFFFF for v in S]), 1 if normalised else 0,
                                                                    out.ctypes.data_as(C.POINTER(P.HipDisplacement))))
     return out[:n].reshape(lead)
+
+
+def warp_last_frames(count, displacements, nodes=(1, 1, 1), node_first=(0, 0, 0), node_step=(1, 1, 1), rotations=None,
+                     interpolation=P.HipWarpInterpolation.Linear, edge=P.HipWarpEdge.Zero, tag=0, timed=True):
+    """beamformer_hip_warp_last_frames: `count` new frames of the frame ring, output n the n-th of the `count` newest ones sampled at
+    v + d_n(v).  displacements: count x nodes z x nodes y x nodes x x 3 floats (any shape of that size), voxels (x, y, z) at the nodes
+    of a lattice of nodes = (x, y, z) nodes an axis, node j of axis a at voxel coordinate node_first[a] + j * node_step[a]; nodes
+    (1, 1, 1): one rigid shift a frame, a HipDisplacement's `displacement` as it is.  The field is trilinear between the nodes and
+    constant outside them.  rotations: None, or `count` complex factors applied to the outputs (exp(-1j * phase) of a displacement).
+    interpolation: P.HipWarpInterpolation (Linear, Cubic: Catmull-Rom); edge: P.HipWarpEdge (Zero: terms outside the frame are
+    skipped; Clamp: the edge voxel repeats).  Returns (first_frame_id, device_ms): the id of the oldest output; timed False: the
+    call does not synchronise and device_ms is 0."""
+    count = int(count)
+    N = [int(v) for v in nodes]
+    if len(N) != 3 or len(node_first) != 3 or len(node_step) != 3:
+        raise ValueError("nodes, node_first, node_step: one number per axis, x, y, z")
+    field = np.ascontiguousarray(np.asarray(displacements, np.float32).reshape(-1))
+    product = N[0] * N[1] * N[2]
+    if 0 < product <= P.HIP_MAX_WARP_NODES and 0 < count <= P.HIP_MAX_ENSEMBLE_FRAMES and field.size != 3 * count * product:
+        raise ValueError("displacements: count x nodes z x nodes y x nodes x x 3 floats")
+    rot = None
+    if rotations is not None:
+        rot = np.ascontiguousarray(np.asarray(rotations, np.complex64).reshape(-1))
+        if rot.size != count:
+            raise ValueError("rotations: one complex factor a frame")
+    floats = C.POINTER(C.c_float)
+    first, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_warp_last_frames(count, field.ctypes.data_as(floats), (C.c_uint32 * 3)(*[v & 0xFFFFFFFF for v in N]),
+                                                     (C.c_float * 3)(*[float(v) for v in node_first]), (C.c_float * 3)(*[float(v) for v in node_step]),
+                                                     None if rot is None else rot.ctypes.data_as(floats), int(interpolation), int(edge), int(tag),
+                                                     C.byref(first), C.byref(ms) if timed else None))
+    return int(first.value), float(ms.value)
 
 
 def frame_info(frame_id):

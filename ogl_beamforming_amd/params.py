@@ -277,6 +277,7 @@ class HipBurstViewsInfo(C.Structure):
 HIP_MAX_VARIANTS = 64
 HIP_DAS_PATH_NO_VARIANTS_KERNEL = 0x4000      # beamformer_hip_set_das_path flag: a variants push runs every variant's single-frame DAS kernel
 HIP_DAS_PATH_PREFER_VARIANTS_KERNEL = 0x8000  # ... flag: the variants kernel takes the eligible variants however few their tiles
+HIP_DAS_PATH_WARP_DIRECT = 0x10000            # ... flag: every tile of beamformer_hip_warp_last_frames takes the direct path (same bytes)
 
 
 class HipDasVariant(C.Structure):
@@ -367,6 +368,23 @@ class HipDisplacement(C.Structure):
     """BeamformerHipDisplacement: one table's row of beamformer_hip_displacements_from_correlation (40 bytes, no padding)"""
     _fields_ = [("displacement", C.c_float * 3), ("shift", C.c_int32 * 3), ("coefficient", C.c_float), ("phase", C.c_float),
                 ("fitted", C.c_uint32), ("at_window_edge", C.c_uint32)]
+
+
+HIP_MAX_WARP_NODES = 4096               # BEAMFORMER_HIP_MAX_WARP_NODES
+HIP_MAX_WARP_ENTRIES = 32768            # BEAMFORMER_HIP_MAX_WARP_ENTRIES
+HIP_MAX_WARP_DISPLACEMENT = 65536.0     # BEAMFORMER_HIP_MAX_WARP_DISPLACEMENT
+
+
+class HipWarpInterpolation(enum.IntEnum):
+    """BeamformerHipWarpInterpolation (beamformer_hip_warp_last_frames)"""
+    Linear = 0
+    Cubic = 1
+
+
+class HipWarpEdge(enum.IntEnum):
+    """BeamformerHipWarpEdge (beamformer_hip_warp_last_frames)"""
+    Zero = 0
+    Clamp = 1
 
 
 class FrameScore(enum.IntEnum):
