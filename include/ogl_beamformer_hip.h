@@ -602,6 +602,93 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_peaks_to_views(const float source_
                                                              const uint32_t patch_points[3], const float patch_extent_voxels[3],
                                                              uint32_t use_offsets, uint32_t image_plane_tag, BeamformerHipView *out);
 
+/* ---- localisation map: the peaks of the frames of the frame ring accumulated ON THE DEVICE into one grid of counts (ULM's product: the
+ * sub-voxel positions of the peaks of thousands of frames binned on a grid several times finer than the beamforming grid -- no peak list
+ * leaves the device, and the map can be queued into the frame ring as an ordinary Float32 frame, so that
+ * beamformer_hip_convolve_last_frames (the Gaussian that renders it), beamformer_hip_display_last_frame,
+ * beamformer_hip_score_last_frames, beamformer_hip_find_peaks_last_frames and beamformer_hip_copy_frame work on it) ----
+ * The library holds ONE map: points[0] x points[1] x points[2] uint32 counts, x fastest, on the one device.
+ * DEFINITION (tests/localisation_ref.py restates it in numpy).
+ * PEAKS.  A voxel of a frame is a peak exactly when beamformer_hip_find_peaks_last_frames says so: the same decision value, thresholds,
+ * box and frame-clipped neighbourhood (the same mark pass runs).  There is no cap: every found peak takes part.
+ * POSITION.  A peak's position is its record, bit for bit what beamformer_hip_find_peaks_last_frames would have stored (one text
+ * computes both): p_a = (double)index[a] + (double)offset[a] per axis, the offset dropped when use_offsets == 0.
+ * PLACEMENT.  placements[n] is frame n's row-major 3 x 4 matrix A of doubles (placement_count == 1: one for all frames); the peak's
+ * map coordinate is, per row r, in double, every product and every sum one operation of its own (no fused multiply-add), in this order:
+ *     m_r = ((A[r][3] + A[r][0] * p_x) + A[r][1] * p_y) + A[r][2] * p_z
+ * -- numpy float64 reproduces every bit.  Map voxel j of an axis has its centre at map coordinate j.
+ * BIN.  b_r = floor(m_r + 0.5).  The peak is DEPOSITED when 0 <= b_r < points[r] on all three axes: the count at flat index
+ * (b_z * points[1] + b_y) * points[0] + b_x goes up by 1.  Otherwise (a coordinate that is not a number included) it counts in `outside`
+ * and nothing is written.
+ * COUNTS are uint32 and WRAP at 2^32 (4 x 10^9 peaks in one bin: reset or read the map before).  Integer additions commute, so the
+ * bytes of the map depend on the multiset of deposits since the reset only -- not on count, on the order of the calls or of the frames,
+ * or on a call being split in two: the device adds with integer atomics, and no floating-point atomic exists in the library. */
+#define BEAMFORMER_HIP_MAX_MAP_VOXELS (1u << 28)
+/* points[3] (x fastest), each >= 1, product <= BEAMFORMER_HIP_MAX_MAP_VOXELS: (re)allocates the library's one map and zeroes it on the
+ * current stream; its totals (BeamformerHipMapInfo) start again.  points == NULL releases it (always succeeds).
+ * beamformer_hip_shutdown releases it too.  Starts the device when none is in use yet.  A zero extent: InvalidAccess; a product above
+ * the limit: BufferOverflow; memory that cannot be allocated: RFDataSizeOverflow (then there is no map); several devices: InvalidAccess. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_localisation_map_reset(const uint32_t points[3]);
+typedef struct {
+	uint32_t frame_id, parameter_block, data_kind, image_plane_tag;   /* from the frame's record */
+	uint32_t points[3];                       /* the frame's own grid */
+	uint32_t region_first[3], region_count[3];/* the box that was searched (the whole frame when region == NULL) */
+	float    threshold;                       /* the threshold used for this frame */
+	uint32_t reserved[2];                     /* 0 (the second word stands where a compiler would pad: rows compare byte for byte) */
+	uint64_t found, above_threshold;          /* exactly beamformer_hip_find_peaks_last_frames' numbers */
+	uint64_t deposited, outside;              /* found == deposited + outside */
+} BeamformerHipMapDeposits;                   /* 96 bytes, no padding */
+/* The peaks of the `count` newest frames (count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES), oldest first, deposited into the map.  region,
+ * thresholds and threshold_count are beamformer_hip_find_peaks_last_frames'; the frames may differ in grid and in data kind, which is
+ * why every frame may have its own placement (beamformer_hip_map_placement makes one from two voxel transforms).  frames[count] (may
+ * be NULL): a row a frame.  The call runs on the library's current stream behind the frames it reads: the rows and the placements go up
+ * in one copy, the mark pass and the scan run, then the deposit -- the mark pass's grid again: a block without a peak leaves after one
+ * load, a lane that holds a peak forms its record, places it and adds 1 with one integer atomic -- and the scan again over the blocks'
+ * tallies (csrc/frame_peaks.hip); the per-frame numbers come back in one copy behind ONE stream synchronise.  device_ms, when not NULL:
+ * the time between two events around the four launches.
+ * Refusals, all decided before anything is enqueued or changed and leaving every output unwritten: count == 0 or >
+ * BEAMFORMER_HIP_MAX_SCORED_FRAMES: BufferOverflow; InvalidAccess: thresholds or placements NULL; threshold_count or placement_count
+ * neither 1 nor count; a threshold that is negative or not finite; a placement entry that is not finite; no map (never reset, or
+ * released); and everything beamformer_hip_score_last_frames refuses -- no device in use yet, fewer than count frames queued, a
+ * tombstone, an overwritten record, reused storage, a region that does not fit inside every frame, several devices. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                           const float *thresholds, uint32_t threshold_count,
+                                                                           const double *placements /* [placement_count][12] */,
+                                                                           uint32_t placement_count /* 1 or count */, uint32_t use_offsets,
+                                                                           BeamformerHipMapDeposits *frames /* [count], may be NULL */,
+                                                                           float *device_ms);
+typedef struct {
+	uint32_t points[3];
+	uint32_t calls;                           /* successful beamformer_hip_accumulate_peaks_last_frames calls since the reset */
+	uint64_t deposited, outside;              /* their totals */
+} BeamformerHipMapInfo;                       /* 32 bytes, no padding */
+/* The map's counts as they are, copied to out[out_count] behind everything enqueued on the current stream (one synchronise); *info
+ * (may be NULL): the grid and the totals since the reset.  out NULL, no map, no device, several devices: InvalidAccess; out_count below
+ * the map's voxel count: ExportSpaceOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info);
+/* Queues ONE Float32 frame of the map's grid into the frame ring: each value (float)count * scale -- one unsigned-to-float conversion
+ * rounded to nearest, then one float32 multiply.  The map itself is left unchanged.  The frame is placed, numbered, recorded and timed
+ * exactly as a run of one frame of beamformer_hip_mix_last_frames is, the record of the newest multi-frame push (it stays "the newest
+ * push" behind the frame) and *frame_id (may be NULL) included; its record carries image_plane_tag and the parameter block of the
+ * newest frame of the most recent successful beamformer_hip_accumulate_peaks_last_frames call.  One launch (csrc/frame_peaks.hip) on
+ * the current stream; the call does not synchronise unless device_ms is not NULL (then: the time between two events around the launch).
+ * Refusals, all decided before anything changes: a scale that is not finite, no map, no device, several devices, no successful
+ * accumulate call since the reset: InvalidAccess; a frame of the map's size that does not fit the ring: FrameSizeOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);
+/* Host only: touches no device and no library state but the last error.  out[12]: the row-major 3 x 4 placement that takes a voxel
+ * position of a frame (index + offset) to the map coordinate of the same point in space.  The kernels map voxel i of an axis with P
+ * points to i / max(1, P - 1) and then through the column-major voxel transform M (see beamformer_hip_peaks_to_views); of M the upper
+ * three rows are used (an affine map: linear part L, translation t).  With S = diag(1 / max(1, P_a - 1)):
+ *     out = S_map^-1 L_map^-1 [ L_frame S_frame | t_frame - t_map ]      in double.
+ * A planar map (an axis of one point) still needs a regular L_map: give that axis a non-zero extent -- its only voxel is index 0, and
+ * a frame point at the axis's origin lands on it.  A rigid correction of a frame (beamformer_hip_displacements_from_correlation: frame
+ * k shown at v + d is the reference at v) is a translation the caller adds to that frame's placement: out[4 r + 3] -= sum over a of
+ * out[4 r + a] * d_a.
+ * InvalidAccess: a NULL argument; a points entry 0; a singular map transform -- det L_map not finite, or |det| <= 10^-12 times the
+ * product of the lengths of L_map's columns (a zero extent is the common case) --; a result that is not finite. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_map_placement(const float frame_voxel_transform[16], const uint32_t frame_points[3],
+                                                            const float map_voxel_transform[16], const uint32_t map_points[3], double out[12]);
+
 /* ---- ensemble filter: a linear slow-time operator on the frames of the frame ring (the clutter filter between "ensemble" and "peaks"
  * of the ULM loop: tissue lies 30 - 60 dB above the microbubbles, so the peaks of an unfiltered ensemble are tissue speckle).  Two
  * device primitives and one host helper: the K x K slow-time Gram matrix of the K newest frames, reduced where they lie; a projector

@@ -394,6 +394,12 @@ typedef struct {
 	uint32_t reserved;
 } BfPeaksRow;
 typedef struct { uint64_t found, above_threshold; } BfPeaksResult;   /* a frame's box */
+/* the localisation map (frame_peaks.hip: beamformer_hip_accumulate_peaks_last_frames, beamformer_hip_queue_localisation_map) */
+#define BF_MAP_MAX_VOXELS (1ull << 28)       /* = BEAMFORMER_HIP_MAX_MAP_VOXELS */
+typedef struct {
+	uint32_t points[3];          /* the map's grid, x fastest */
+	uint32_t use_offsets;        /* 0: a peak's position is its index */
+} BfMapArgs;
 
 /* ---- ensemble filter (ensemble.hip: beamformer_hip_gram_last_frames, beamformer_hip_mix_last_frames) ---- */
 #define BF_ENSEMBLE_MAX_FRAMES 256u          /* = BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES */
@@ -597,6 +603,15 @@ hipError_t bf_launch_frame_peaks_mark(const void *ring, const BfPeaksRow *rows, 
 hipError_t bf_launch_frame_peaks_emit(const void *ring, const BfPeaksRow *rows, uint32_t frame_count, uint32_t max_blocks,
                                       const uint64_t *masks, const uint32_t *counts, const uint32_t *offsets, const uint32_t *firsts,
                                       void *list, hipStream_t s);
+/* frame_peaks.hip, the localisation map.  _deposit: two launches behind _mark's, on its tables -- the mark pass's grid again, every peak
+ * placed through placements[frame][12] (row-major 3 x 4, double) and added to its bin of `map` (uint32, a->points voxels) by one integer
+ * atomic, a word a block (deposited | outside << 16) into `words`; then the scan kernel over those words: tallies[frame].found the
+ * frame's deposited peaks, .above_threshold the ones outside the map (`offsets` is rewritten).  bf_launch_localisation_convert: one launch,
+ * out[i] = (float)map[i] * scale */
+hipError_t bf_launch_localisation_deposit(const void *ring, const BfPeaksRow *rows, const double *placements, uint32_t frame_count,
+                                         uint32_t max_blocks, const uint64_t *masks, const uint32_t *counts, uint32_t *offsets,
+                                         const BfMapArgs *a, uint32_t *map, uint32_t *words, BfPeaksResult *tallies, hipStream_t s);
+hipError_t bf_launch_localisation_convert(const uint32_t *map, float *out, uint64_t voxels, float scale, hipStream_t s);
 /* ensemble.hip, the Gram matrix: three launches, no atomics -- the all-finite mask (a wave a word of 64 box voxels, every frame read
  * once), the partial pass (grid x the chunk, grid y the tile pair: BF_GRAM_TILE x BF_GRAM_TILE pairs of double2 a block) and the fold
  * (a thread a pair j <= k sums its chunks' partials in chunk order and stores both triangles; one more block counts the mask's bits).

@@ -78,7 +78,7 @@ struct PushRecord {
 	BeamformerHipVariantsDescription variants{};        /* Variants: its route */
 	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
-	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames / convolve_last_frames / warp_last_frames have queued behind the push: the push stays "the newest push" behind them */
+	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames / convolve_last_frames / warp_last_frames / queue_localisation_map have queued behind the push: the push stays "the newest push" behind them */
 };
 
 struct PlanState {
@@ -174,6 +174,10 @@ struct Device {
 	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
 	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
 	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
+	DeviceBuffer map;                                          /* the localisation map: map_points voxels of uint32 counts (beamformer_hip_localisation_map_reset; frame_peaks.hip deposits into it); map_points[0] == 0: none */
+	uint32_t     map_points[3]{};
+	uint32_t     map_calls = 0, map_block = 0;                 /* ... successful accumulate calls since the reset, and the parameter block of the newest frame of the last one */
+	uint64_t     map_deposited = 0, map_outside = 0;           /* ... and their totals */
 	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
 	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
@@ -285,6 +289,12 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
                             uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
                             float *device_ms);                     /* arguments checked by the caller (lib_api.cpp) */
+bool localisation_map_reset(const uint32_t points[3]);             /* null: release; else checked by the caller */
+bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                                  const double *placements, uint32_t placement_count, uint32_t use_offsets, BeamformerHipMapDeposits *frames,
+                                  float *device_ms);               /* arguments checked by the caller (lib_api.cpp) */
+bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info);
+bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);
 bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms);
 bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions, uint32_t region_count,
                            const uint32_t max_shift[3], BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info, float *device_ms);

@@ -188,6 +188,8 @@ static void release_one_device(Device &d)
 	if (d.peaks_begin) (void)hipEventDestroy(d.peaks_begin);
 	if (d.peaks_end)   (void)hipEventDestroy(d.peaks_end);
 	d.peaks_begin = d.peaks_end = nullptr;
+	d.map.release();
+	d.map_points[0] = d.map_points[1] = d.map_points[2] = 0; d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
 	d.mix_table.release();
 	d.spatial_scratch.release();
 	if (d.mix_pinned) (void)hipHostFree(d.mix_pinned);
@@ -2404,6 +2406,40 @@ bool ensure_metrics_memory(Device &d, size_t pinned_bytes, size_t device_bytes)
 	return ok;
 }
 
+/* the mark pass's rows of the boxed frames (frame_peaks.hip), as find_peaks_last_frames and accumulate_peaks_last_frames launch it: the
+ * waves and blocks of all frames, the most blocks of one.  False, with InvalidAccess set: a box of more waves than the kernels number */
+struct PeaksRows {
+	std::vector<BfPeaksRow> rows;
+	uint64_t waves = 0, blocks = 0;
+	uint32_t max_blocks = 0;
+};
+bool peaks_rows_of(const std::vector<BoxedFrame> &boxed, const float *thresholds, uint32_t threshold_count, uint32_t cap, PeaksRows &out)
+{
+	const uint32_t count = (uint32_t)boxed.size();
+	out.rows.resize(count);
+	for (uint32_t n = 0; n < count; n++) {
+		const BoxedFrame &b = boxed[n];
+		BfPeaksRow &r = out.rows[n];
+		r = BfPeaksRow{};
+		r.offset = b.record->offset;
+		r.cplx = b.cplx;
+		for (int k = 0; k < 3; k++) { r.points[k] = b.record->points[k]; r.first[k] = b.first[k]; r.count[k] = b.count[k]; }
+		const uint64_t per_row = ((uint64_t)r.count[0] + 63u) / 64u, frame_waves = per_row * r.count[1] * r.count[2];
+		/* (a frame of the ring has far fewer voxels than this: a bound that keeps the kernels' 32-bit wave numbers honest) */
+		if (frame_waves > 4ull * BF_PEAKS_MAX_BLOCKS - 3u) return set_error(BeamformerLibErrorKind_InvalidAccess);
+		r.waves_per_row = (uint32_t)per_row;
+		r.waves = (uint32_t)frame_waves;
+		r.blocks = (uint32_t)((frame_waves + 3u) / 4u);
+		r.wave_first = out.waves; r.block_first = out.blocks;
+		const float t = thresholds[threshold_count == 1 ? 0 : n];
+		r.threshold = b.cplx ? t * t : t;
+		r.cap = cap;
+		out.waves += r.waves; out.blocks += r.blocks;
+		if (r.blocks > out.max_blocks) out.max_blocks = r.blocks;
+	}
+	return true;
+}
+
 } // namespace
 
 /* beamformer_hip_score_last_frames: focus metrics of the `count` newest frames, reduced where they lie (frame_metrics.hip).  Everything
@@ -2493,29 +2529,11 @@ bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 	if (!newest_boxed_frames(count, region, boxed)) return false;
 	Device &d = g_context.devices[0];
 
-	std::vector<BfPeaksRow> rows(count);
-	uint64_t waves = 0, blocks = 0;
-	uint32_t max_blocks = 0;
-	for (uint32_t n = 0; n < count; n++) {
-		const BoxedFrame &b = boxed[n];
-		BfPeaksRow &r = rows[n];
-		r = BfPeaksRow{};
-		r.offset = b.record->offset;
-		r.cplx = b.cplx;
-		for (int k = 0; k < 3; k++) { r.points[k] = b.record->points[k]; r.first[k] = b.first[k]; r.count[k] = b.count[k]; }
-		const uint64_t per_row = ((uint64_t)r.count[0] + 63u) / 64u, frame_waves = per_row * r.count[1] * r.count[2];
-		/* (a frame of the ring has far fewer voxels than this: a bound that keeps the kernels' 32-bit wave numbers honest) */
-		if (frame_waves > 4ull * BF_PEAKS_MAX_BLOCKS - 3u) return set_error(BeamformerLibErrorKind_InvalidAccess);
-		r.waves_per_row = (uint32_t)per_row;
-		r.waves = (uint32_t)frame_waves;
-		r.blocks = (uint32_t)((frame_waves + 3u) / 4u);
-		r.wave_first = waves; r.block_first = blocks;
-		const float t = thresholds[threshold_count == 1 ? 0 : n];
-		r.threshold = b.cplx ? t * t : t;
-		r.cap = max_per_frame;
-		waves += r.waves; blocks += r.blocks;
-		if (r.blocks > max_blocks) max_blocks = r.blocks;
-	}
+	PeaksRows table;
+	if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
+	const std::vector<BfPeaksRow> &rows = table.rows;
+	const uint64_t waves = table.waves, blocks = table.blocks;
+	const uint32_t max_blocks = table.max_blocks;
 
 	/* device: rows | results | firsts | masks | counts | offsets; pinned: rows | results | firsts */
 	const size_t rows_bytes = round_up(sizeof(BfPeaksRow) * count, 64), results_bytes = round_up(sizeof(BfPeaksResult) * count, 64),
@@ -2583,6 +2601,133 @@ bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
 	}
 	*peak_count = total;
+	return true;
+}
+
+/* beamformer_hip_localisation_map_reset: the one map of the one device, (re)allocated and zeroed on the current stream; points null:
+ * released.  The extents arrive checked (lib_api.cpp). */
+bool localisation_map_reset(const uint32_t points[3])
+{
+	Context &c = g_context;
+	Device &d = c.devices[0];
+	if (!points) {
+		if (c.device_ready && d.map.ptr) {
+			bool ok = HIP_OK(hipSetDevice(d.device));
+			ok = ok && HIP_OK(hipStreamSynchronize(d.stream));          /* a deposit or a conversion may still be reading it */
+			if (!ok) (void)hipGetLastError();
+			d.map.release();
+		}
+		d.map_points[0] = d.map_points[1] = d.map_points[2] = 0; d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
+		return true;
+	}
+	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	const size_t bytes = sizeof(uint32_t) * (size_t)points[0] * points[1] * points[2];
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	/* (a buffer that has to grow is freed first: what is enqueued on it must have run) */
+	if (ok && d.map.ptr && d.map.size < bytes) ok = HIP_OK(hipStreamSynchronize(d.stream));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (!d.map.ensure(bytes)) {
+		(void)hipGetLastError();
+		d.map_points[0] = d.map_points[1] = d.map_points[2] = 0; d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
+		return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
+	}
+	for (int k = 0; k < 3; k++) d.map_points[k] = points[k];
+	d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
+	if (!HIP_OK(hipMemsetAsync(d.map.ptr, 0, bytes, d.stream))) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	return true;
+}
+
+/* beamformer_hip_accumulate_peaks_last_frames: the peaks of the `count` newest frames binned into the localisation map where they lie
+ * (frame_peaks.hip: the mark pass and the scan of find_peaks_last_frames, then the deposit and the scan again over its words).  The
+ * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  One synchronise:
+ * no buffer is sized by what was found. */
+bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                                  const double *placements, uint32_t placement_count, uint32_t use_offsets, BeamformerHipMapDeposits *frames,
+                                  float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipMapDeposits) == 96 && sizeof(BeamformerHipMapInfo) == 32, "records without padding");
+	static_assert(BF_MAP_MAX_VOXELS == BEAMFORMER_HIP_MAX_MAP_VOXELS, "one limit");
+	std::vector<BoxedFrame> boxed;
+	if (!newest_boxed_frames(count, region, boxed)) return false;
+	Device &d = g_context.devices[0];
+	if (!d.map.ptr || !d.map_points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	PeaksRows table;
+	if (!peaks_rows_of(boxed, thresholds, threshold_count, 0, table)) return false;      /* (the cap is the emit pass's: not read) */
+
+	/* device: rows | placements | results | tallies | masks | counts | offsets | words; pinned: the first four */
+	const size_t rows_bytes = round_up(sizeof(BfPeaksRow) * count, 64), placements_bytes = round_up(sizeof(double) * 12 * count, 64),
+	             results_bytes = round_up(sizeof(BfPeaksResult) * count, 64), masks_bytes = round_up(sizeof(uint64_t) * table.waves, 64),
+	             counts_bytes = round_up(sizeof(uint32_t) * table.blocks, 64), up_bytes = rows_bytes + placements_bytes;
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && ensure_metrics_memory(d, up_bytes + 2 * results_bytes, up_bytes + 2 * results_bytes + masks_bytes + 3 * counts_bytes);
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
+	const BfPeaksRow *device_rows       = (const BfPeaksRow *)device;
+	const double     *device_placements = (const double *)(device + rows_bytes);
+	BfPeaksResult    *device_results    = (BfPeaksResult *)(device + up_bytes);
+	BfPeaksResult    *device_tallies    = (BfPeaksResult *)(device + up_bytes + results_bytes);
+	uint64_t         *device_masks      = (uint64_t *)(device + up_bytes + 2 * results_bytes);
+	uint32_t         *device_counts     = (uint32_t *)((char *)device_masks + masks_bytes);
+	uint32_t         *device_offsets    = (uint32_t *)((char *)device_counts + counts_bytes);
+	uint32_t         *device_words      = (uint32_t *)((char *)device_offsets + counts_bytes);
+	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + up_bytes), *tallies = (const BfPeaksResult *)(pinned + up_bytes + results_bytes);
+	std::memcpy(pinned, table.rows.data(), sizeof(BfPeaksRow) * count);
+	for (uint32_t n = 0; n < count; n++)
+		std::memcpy(pinned + rows_bytes + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
+	BfMapArgs a{};
+	for (int k = 0; k < 3; k++) a.points[k] = d.map_points[k];
+	a.use_offsets = use_offsets != 0;
+	hipStream_t s = d.stream;
+	ok &= HIP_OK(hipMemcpyAsync(device, pinned, rows_bytes + sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
+	if (ok) ok &= HIP_OK(bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s));
+	if (ok) ok &= HIP_OK(bf_launch_localisation_deposit(d.ring.ptr, device_rows, device_placements, count, table.max_blocks, device_masks, device_counts,
+	                                                   device_offsets, &a, (uint32_t *)d.map.ptr, device_words, device_tallies, s));
+	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
+	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + up_bytes, device_results, results_bytes + sizeof(BfPeaksResult) * count, hipMemcpyDeviceToHost, s));
+	/* the one synchronise: also what frees the pinned memory for the next call, so it runs whatever failed above */
+	ok &= HIP_OK(hipStreamSynchronize(s));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (device_ms) {
+		float ms = 0;
+		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
+	}
+
+	for (uint32_t n = 0; n < count; n++) {
+		const FrameRecord &f = *boxed[n].record;
+		d.map_deposited += tallies[n].found; d.map_outside += tallies[n].above_threshold;
+		if (!frames) continue;
+		BeamformerHipMapDeposits &m = frames[n];
+		std::memset(&m, 0, sizeof(m));
+		m.frame_id = f.id; m.parameter_block = f.block; m.data_kind = (uint32_t)f.data_kind; m.image_plane_tag = f.tag;
+		for (int k = 0; k < 3; k++) { m.points[k] = f.points[k]; m.region_first[k] = table.rows[n].first[k]; m.region_count[k] = table.rows[n].count[k]; }
+		m.threshold = thresholds[threshold_count == 1 ? 0 : n];
+		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
+		m.deposited = tallies[n].found; m.outside = tallies[n].above_threshold;
+	}
+	d.map_calls++;
+	d.map_block = boxed[count - 1].record->block;
+	return true;
+}
+
+/* beamformer_hip_localisation_map_copy: the counts as they are, behind everything enqueued on the current stream */
+bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info)
+{
+	Context &c = g_context;
+	Device &d = c.devices[0];
+	if (!c.device_ready || c.device_count != 1 || !d.map.ptr || !d.map_points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	const uint64_t voxels = (uint64_t)d.map_points[0] * d.map_points[1] * d.map_points[2];
+	if (out_count < voxels) return set_error(BeamformerLibErrorKind_ExportSpaceOverflow);
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && HIP_OK(hipMemcpyAsync(out, d.map.ptr, sizeof(uint32_t) * voxels, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (info) {
+		std::memset(info, 0, sizeof(*info));
+		for (int k = 0; k < 3; k++) info->points[k] = d.map_points[k];
+		info->calls = d.map_calls; info->deposited = d.map_deposited; info->outside = d.map_outside;
+	}
 	return true;
 }
 
@@ -2753,7 +2898,8 @@ namespace {
 
 /* What beamformer_hip_mix_last_frames, beamformer_hip_autocorrelate_last_frames, beamformer_hip_convolve_last_frames and
  * beamformer_hip_warp_last_frames share:
- * `out_count` frames computed from the `count` newest ones and queued as frames of their own behind them.  Everything that can refuse
+ * `out_count` frames computed from the `count` newest ones and queued as frames of their own behind them (and what
+ * beamformer_hip_queue_localisation_map takes of it: a run without sources, RunTable::shape).  Everything that can refuse
  * is decided, and every buffer grown, before the ids are taken; nothing synchronises unless device_ms is asked for.
  * The call's table travels with the sources' ring offsets: a weight table of `rows` rows, laid out [tile][k][BF_MIX_TILE][2] (rows past
  * `rows` zero), or `flat_floats` floats as they are (the taps of a convolution), or neither (weights and flat null: the launch reads the
@@ -2765,6 +2911,9 @@ namespace {
 struct RunTable {
 	const float *weights = nullptr; uint32_t rows = 0;
 	const float *flat = nullptr;    uint32_t flat_floats = 0;
+	/* not null: a run that has no source frames (count 0: beamformer_hip_queue_localisation_map) -- Float32 frames of this record's grid,
+	 * carrying its block, stand where the newest source's record does */
+	const FrameRecord *shape = nullptr;
 };
 struct QueuedRun {
 	Device *d;
@@ -2787,10 +2936,12 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 	const uint32_t rows = t.rows;
 	Context &c = g_context;
 	std::vector<BoxedFrame> boxed;
-	if (!newest_ensemble_frames(count, nullptr, boxed)) return false;
+	if (t.shape) {
+		if (!c.device_ready || c.device_count != 1 || count != 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	} else if (!newest_ensemble_frames(count, nullptr, boxed)) return false;
 	Device &d = c.devices[0];
-	const FrameRecord newest = *boxed[count - 1].record;      /* (a copy: the run's records may take its place) */
-	const bool cplx = boxed[0].cplx;
+	const FrameRecord newest = t.shape ? *t.shape : *boxed[count - 1].record;      /* (a copy: the run's records may take its place) */
+	const bool cplx = t.shape ? false : boxed[0].cplx;
 	if (!cplx && weights)
 		for (size_t n = 0; n < (size_t)rows * count; n++)
 			if (weights[2 * n + 1] != 0.0f) return set_error(BeamformerLibErrorKind_InvalidAccess);
@@ -2859,7 +3010,7 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 	for (int k = 0; k < 3; k++) run.points[k] = newest.points[k];
 	run.elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
 	run.out_offset = frame0->offset; run.out_stride = frame0->bytes; run.s = s;
-	ok &= HIP_OK(hipMemcpyAsync(d.mix_table.ptr, pinned, offsets_bytes + weights_bytes, hipMemcpyHostToDevice, s));
+	if (offsets_bytes + weights_bytes) ok &= HIP_OK(hipMemcpyAsync(d.mix_table.ptr, pinned, offsets_bytes + weights_bytes, hipMemcpyHostToDevice, s));
 	d.mix_copy_pending = HIP_OK(hipEventRecord(d.mix_copied, s));
 	ok &= d.mix_copy_pending;
 	if (device_ms) ok &= HIP_OK(hipEventRecord(d.mix_begin, s));
@@ -3007,6 +3158,23 @@ bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3
 			args.out_offset = r.out_offset; args.out_stride = r.out_stride;
 			return bf_launch_warp(r.ring, r.offsets, r.table, &args, r.s);
 		});
+}
+
+/* beamformer_hip_queue_localisation_map: the map's counts times `scale`, queued as ONE Float32 frame of the map's grid (frame_peaks.hip:
+ * the conversion) -- a run of one frame that has no source in the ring: the map is the library's own buffer, so no placement can lie on
+ * what the launch reads.  The record carries the block of the newest frame of the last accumulate call. */
+bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+{
+	Context &c = g_context;
+	Device &d = c.devices[0];
+	if (!c.device_ready || c.device_count != 1 || !d.map.ptr || !d.map_points[0] || d.map_calls == 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	FrameRecord shape;
+	for (int k = 0; k < 3; k++) shape.points[k] = d.map_points[k];
+	shape.block = d.map_block;
+	RunTable t; t.shape = &shape;
+	const uint32_t *map = (const uint32_t *)d.map.ptr;
+	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
+		[=](const QueuedRun &r) { return bf_launch_localisation_convert(map, (float *)((char *)r.ring + r.out_offset), r.elements, scale, r.s); });
 }
 
 /* The record of the frame with this id, while the frame is still there: its record not yet overwritten (the newest frames.size() ids),

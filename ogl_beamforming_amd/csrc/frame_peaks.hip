@@ -19,7 +19,17 @@
  * the frame's found and above_threshold -- integer sums, any order gives the same.
  * Emit: the mark pass's grid.  A block without a peak leaves after one load; a lane whose bit is set has rank offset + the peaks of the
  * block's earlier waves + popcount(mask & lower lanes), and below the cap stores its record at list[first + rank] with two 16-byte
- * stores.  No atomics anywhere: a peak's position in the list is a function of its index. */
+ * stores.  No atomics anywhere: a peak's position in the list is a function of its index.
+ *
+ * DEPOSIT (beamformer_hip_accumulate_peaks_last_frames: the peaks binned into the localisation map, no list made).  Behind the same mark
+ * pass, on its grid: a block without a peak stores a zero word and leaves after one load; a lane whose bit is set forms its record with
+ * the emit pass's own functions (magnitude_at and fit_axis: one text for both), places p = index + offset through its frame's 3 x 4 double
+ * matrix -- ((A[r][3] + A[r][0] p_x) + A[r][1] p_y) + A[r][2] p_z, contraction off --, bins b_r = floor(m_r + 0.5) and, inside the map,
+ * adds 1 to its uint32 count with one returnless integer atomic.  Integer additions commute: the map's bytes are a function of the
+ * multiset of deposits -- the one place this file uses an atomic, and no floating-point one.  The ballots of the lanes inside and
+ * outside give a block's word (deposited | outside << 16, both at most 256): the scan kernel sums such words as it sums the mark
+ * pass's, so a second launch of it makes the per-frame tallies.
+ * CONVERT (beamformer_hip_queue_localisation_map): one coalesced pass, count -> (float)count * scale, four voxels a lane. */
 #include <hip/hip_runtime.h>
 #include "bf_kernels.h"
 
@@ -224,5 +234,107 @@ extern "C" hipError_t bf_launch_frame_peaks_emit(const void *ring, const BfPeaks
 	    max_blocks == 0 || max_blocks > BF_PEAKS_MAX_BLOCKS) return hipErrorInvalidValue;
 	hipLaunchKernelGGL(frame_peaks_emit_kernel, dim3(max_blocks, frame_count), dim3(256), 0, s, (const char *)ring, rows, masks, counts, offsets,
 	                   firsts, (uint4 *)list);
+	return hipGetLastError();
+}
+
+/* Deposit: the mark pass's grid.  placements[frame][12]: row-major 3 x 4, double; map: a.points voxels of uint32, x fastest; words: one
+ * a block, deposited | outside << 16. */
+__global__ __launch_bounds__(256) void localisation_deposit_kernel(const char *__restrict__ ring, const BfPeaksRow *__restrict__ rows,
+                                                                  const double *__restrict__ placements, const uint64_t *__restrict__ masks,
+                                                                  const uint32_t *__restrict__ counts, BfMapArgs a, uint32_t *__restrict__ map,
+                                                                  uint32_t *__restrict__ words)
+{
+	#pragma clang fp contract(off)
+	const BfPeaksRow &row = rows[blockIdx.y];
+	if (blockIdx.x >= row.blocks) return;
+	if ((counts[row.block_first + blockIdx.x] & 0xFFFFu) == 0) {
+		if (threadIdx.x == 0) words[row.block_first + blockIdx.x] = 0u;
+		return;
+	}
+	const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), w = blockIdx.x * 4u + wave;
+	__shared__ uint32_t tallies[4];
+	uint32_t tally = 0;
+	if (w < row.waves) {
+		const uint64_t mask = masks[row.wave_first + w];
+		const bool mine = mask >> lane & 1ull;
+		bool inside = false;
+		if (mine) {
+			/* the emit pass's record of this voxel, by the emit pass's functions; without offsets no neighbour is read */
+			const float *frame = (const float *)(ring + row.offset);
+			const uint32_t cplx = row.cplx, nx = row.points[0], ny = row.points[1], nz = row.points[2];
+			const uint64_t plane = (uint64_t)nx * ny;
+			uint32_t x0, y, z;
+			wave_at(row, w, x0, y, z);
+			const uint64_t x = (uint64_t)row.first[0] + x0 + lane, i = z * plane + (uint64_t)y * nx + x;
+			float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+			if (a.use_offsets) {
+				const float m0 = magnitude_at(frame, i, cplx);
+				(void)fit_axis(frame, cplx, i, 1, x, nx, m0, ox);
+				(void)fit_axis(frame, cplx, i, nx, y, ny, m0, oy);
+				(void)fit_axis(frame, cplx, i, plane, z, nz, m0, oz);
+			}
+			const double px = (double)(uint32_t)x + (double)ox, py = (double)y + (double)oy, pz = (double)z + (double)oz;
+			const double *A = placements + 12u * blockIdx.y;
+			uint32_t bin[3];
+			inside = true;
+			#pragma unroll
+			for (int r = 0; r < 3; r++) {
+				const double m = ((A[4 * r + 3] + A[4 * r] * px) + A[4 * r + 1] * py) + A[4 * r + 2] * pz;
+				const double b = __builtin_floor(m + 0.5);
+				const bool in = b >= 0.0 && b < (double)a.points[r];        /* (NaN: neither) */
+				bin[r] = in ? (uint32_t)b : 0u;
+				inside &= in;
+			}
+			/* the one atomic of the file: an integer add whose result nobody reads */
+			if (inside) atomicAdd(map + (((uint64_t)bin[2] * a.points[1] + bin[1]) * a.points[0] + bin[0]), 1u);
+		}
+		const uint64_t deposited = __ballot(inside), outside = __ballot(mine && !inside);
+		tally = (uint32_t)__popcll(deposited) | (uint32_t)__popcll(outside) << 16;
+	}
+	if (lane == 0) tallies[wave] = tally;
+	__syncthreads();
+	if (threadIdx.x == 0) words[row.block_first + blockIdx.x] = tallies[0] + tallies[1] + tallies[2] + tallies[3];
+}
+
+/* Convert: out[i] = (float)map[i] * scale -- one conversion rounded to nearest, one float32 multiply.  The first `quads` groups of four
+ * voxels go as 16 bytes a lane, the voxels behind them one a lane. */
+__global__ __launch_bounds__(256) void localisation_convert_kernel(const uint32_t *__restrict__ map, float *__restrict__ out, uint64_t voxels,
+                                                           uint64_t quads, float scale)
+{
+	#pragma clang fp contract(off)
+	const uint64_t stride = (uint64_t)gridDim.x * 256u, t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	for (uint64_t k = t; k < quads; k += stride) {
+		const uint4 c = ((const uint4 *)map)[k];
+		((float4 *)out)[k] = make_float4((float)c.x * scale, (float)c.y * scale, (float)c.z * scale, (float)c.w * scale);
+	}
+	for (uint64_t i = 4u * quads + t; i < voxels; i += stride) out[i] = (float)map[i] * scale;
+}
+
+/* Behind bf_launch_frame_peaks_mark on the same stream and tables.  placements: frame_count x 12 doubles; map: the product of a->points
+ * uint32 (at most 2^28); words: a uint32 a block, as counts; tallies[frame]: found = deposited, above_threshold = outside -- the scan
+ * kernel over `words`, which rewrites `offsets` (nothing reads them behind the deposit).  All device memory. */
+extern "C" hipError_t bf_launch_localisation_deposit(const void *ring, const BfPeaksRow *rows, const double *placements, uint32_t frame_count,
+                                                    uint32_t max_blocks, const uint64_t *masks, const uint32_t *counts, uint32_t *offsets,
+                                                    const BfMapArgs *a, uint32_t *map, uint32_t *words, BfPeaksResult *tallies, hipStream_t s)
+{
+	if (!ring || !rows || !placements || !masks || !counts || !offsets || !a || !map || !words || !tallies || frame_count == 0 ||
+	    frame_count > 65535u || max_blocks == 0 || max_blocks > BF_PEAKS_MAX_BLOCKS) return hipErrorInvalidValue;
+	if (!a->points[0] || !a->points[1] || !a->points[2] || (uint64_t)a->points[0] * a->points[1] > BF_MAP_MAX_VOXELS ||
+	    (uint64_t)a->points[0] * a->points[1] * a->points[2] > BF_MAP_MAX_VOXELS) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(localisation_deposit_kernel, dim3(max_blocks, frame_count), dim3(256), 0, s, (const char *)ring, rows, placements, masks,
+	                   counts, *a, map, words);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(frame_peaks_scan_kernel, dim3(frame_count), dim3(1024), 0, s, rows, (const uint32_t *)words, offsets, tallies);
+	return hipGetLastError();
+}
+
+/* map: `voxels` uint32; out: `voxels` floats (a frame of the ring); both device memory */
+extern "C" hipError_t bf_launch_localisation_convert(const uint32_t *map, float *out, uint64_t voxels, float scale, hipStream_t s)
+{
+	if (!map || !out || voxels == 0 || voxels > BF_MAP_MAX_VOXELS) return hipErrorInvalidValue;
+	const uint64_t quads = (((uintptr_t)map | (uintptr_t)out) & 15u) ? 0u : voxels / 4u;
+	const uint64_t lanes = quads ? quads : voxels, blocks = (lanes + 255u) / 256u;
+	hipLaunchKernelGGL(localisation_convert_kernel, dim3((uint32_t)(blocks < 4096u ? blocks : 4096u)), dim3(256), 0, s, map, out, voxels, quads, scale);
 	return hipGetLastError();
 }

@@ -1011,6 +1011,85 @@ uint32_t beamformer_hip_peaks_to_views(const float source_voxel_transform[16], c
 	return 1;
 }
 
+uint32_t beamformer_hip_localisation_map_reset(const uint32_t points[3])
+{
+	if (!points) return localisation_map_reset(nullptr);
+	if (!check(points[0] && points[1] && points[2], BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check((uint64_t)points[0] * points[1] <= BEAMFORMER_HIP_MAX_MAP_VOXELS &&
+	           (uint64_t)points[0] * points[1] * points[2] <= BEAMFORMER_HIP_MAX_MAP_VOXELS, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!ensure_device()) return 0;
+	return localisation_map_reset(points);
+}
+
+/* (serves frames that exist, as the calls above: it starts no device) */
+uint32_t beamformer_hip_accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds,
+                                                     uint32_t threshold_count, const double *placements, uint32_t placement_count,
+                                                     uint32_t use_offsets, BeamformerHipMapDeposits *frames, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(thresholds != nullptr && placements != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (uint32_t k = 0; k < threshold_count; k++)
+		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
+		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return accumulate_peaks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, frames, device_ms);
+}
+
+uint32_t beamformer_hip_localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info)
+{
+	if (!check(out != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return localisation_map_copy(out, out_count, info);
+}
+
+uint32_t beamformer_hip_queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+{
+	if (!check(std::isfinite(scale), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return queue_localisation_map(scale, image_plane_tag, frame_id, device_ms);
+}
+
+/* host only: S_map^-1 M_map^-1 M_frame S_frame in double (include/ogl_beamformer_hip.h has the algebra) */
+uint32_t beamformer_hip_map_placement(const float frame_voxel_transform[16], const uint32_t frame_points[3], const float map_voxel_transform[16],
+                                      const uint32_t map_points[3], double out[12])
+{
+	if (!check(frame_voxel_transform && frame_points && map_voxel_transform && map_points && out, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (int a = 0; a < 3; a++)
+		if (!check(frame_points[a] != 0 && map_points[a] != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	const float *f = frame_voxel_transform, *g = map_voxel_transform;      /* column major: m[4 * column + row] */
+	/* the map's linear part L (rows r, columns c) and its cofactor inverse */
+	double L[3][3], norms = 1.0;
+	for (int col = 0; col < 3; col++) {
+		double n2 = 0.0;
+		for (int r = 0; r < 3; r++) { L[r][col] = (double)g[4 * col + r]; n2 += L[r][col] * L[r][col]; }
+		norms *= std::sqrt(n2);
+	}
+	const double c00 = L[1][1] * L[2][2] - L[1][2] * L[2][1], c01 = L[1][2] * L[2][0] - L[1][0] * L[2][2], c02 = L[1][0] * L[2][1] - L[1][1] * L[2][0];
+	const double det = L[0][0] * c00 + L[0][1] * c01 + L[0][2] * c02;
+	/* singular: a determinant that is not finite, or not above 10^-12 of the product of the columns' lengths (float32 columns closer to
+	 * a common plane than that span no volume their own precision could tell from none) */
+	if (!check(std::isfinite(det) && std::fabs(det) > 1e-12 * norms, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	const double inv[3][3] = {
+		{c00 / det, (L[0][2] * L[2][1] - L[0][1] * L[2][2]) / det, (L[0][1] * L[1][2] - L[0][2] * L[1][1]) / det},
+		{c01 / det, (L[0][0] * L[2][2] - L[0][2] * L[2][0]) / det, (L[0][2] * L[1][0] - L[0][0] * L[1][2]) / det},
+		{c02 / det, (L[0][1] * L[2][0] - L[0][0] * L[2][1]) / det, (L[0][0] * L[1][1] - L[0][1] * L[1][0]) / det}};
+	double result[12];
+	for (int r = 0; r < 3; r++) {
+		const double map_last = map_points[r] > 1 ? (double)map_points[r] - 1.0 : 1.0;        /* S_map^-1 */
+		for (int col = 0; col < 4; col++) {
+			/* column col of M_frame S_frame; the last one: the frames' origin seen from the map's */
+			const double frame_last = col < 3 && frame_points[col] > 1 ? (double)frame_points[col] - 1.0 : 1.0;
+			double v[3];
+			for (int k = 0; k < 3; k++) v[k] = col < 3 ? (double)f[4 * col + k] / frame_last : (double)f[12 + k] - (double)g[12 + k];
+			result[4 * r + col] = (inv[r][0] * v[0] + inv[r][1] * v[1] + inv[r][2] * v[2]) * map_last;
+		}
+	}
+	for (int k = 0; k < 12; k++)
+		if (!check(std::isfinite(result[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	std::memcpy(out, result, sizeof(result));
+	return 1;
+}
+
 uint32_t beamformer_hip_gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info,
                                          float *device_ms)
 {

@@ -134,6 +134,12 @@ def _load():
                                                         C.POINTER(P.HipFramePeak), C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_peaks_to_views": (u32, [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(P.HipFramePeak), u32, C.POINTER(u32),
                                                 C.POINTER(C.c_float), u32, u32, C.POINTER(P.HipView)]),
+        "beamformer_hip_localisation_map_reset": (u32, [C.POINTER(u32)]),
+        "beamformer_hip_accumulate_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
+                                                              C.POINTER(P.HipMapDeposits), C.POINTER(C.c_float)]),
+        "beamformer_hip_localisation_map_copy": (u32, [C.POINTER(u32), u64, C.POINTER(P.HipMapInfo)]),
+        "beamformer_hip_queue_localisation_map": (u32, [C.c_float, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_map_placement": (u32, [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_double)]),
         "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
         "beamformer_hip_clutter_projector": (u32, [C.POINTER(C.c_double), u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
         "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
@@ -561,6 +567,71 @@ def peaks_to_views(source_transform, source_points, peaks, patch_points, patch_e
                                                    (C.c_uint32 * 3)(*[int(v) for v in patch_points]),
                                                    (C.c_float * 3)(*[float(v) for v in patch_extent_voxels]), 1 if use_offsets else 0, int(tag), out))
     return list(out[: len(peaks)])
+
+
+_map_points = None      # the grid of the newest localisation_map_reset(): what localisation_map_copy() sizes its array by
+
+
+def localisation_map_reset(points):
+    """beamformer_hip_localisation_map_reset: (re)allocates the library's one localisation map of points = (x, y, z) uint32 counts and
+    zeroes it; points None releases it."""
+    global _map_points
+    _check(library().beamformer_hip_localisation_map_reset(None if points is None else (C.c_uint32 * 3)(*[int(v) & 0xFFFFFFFF for v in points])))
+    _map_points = None if points is None else tuple(int(v) for v in points)
+
+
+def accumulate_peaks_last_frames(count, thresholds, placements, use_offsets=True, region=None):
+    """beamformer_hip_accumulate_peaks_last_frames: the peaks of the `count` newest frames (find_peaks_last_frames' peaks, no cap)
+    deposited on the device into the localisation map.  thresholds and region as find_peaks_last_frames takes them; placements: one
+    3 x 4 float64 matrix for all frames, or `count` of them, oldest first (any shape of 12 or count x 12 numbers; map_placement makes
+    one): a peak at index + offset lands on map coordinate A[:, :3] @ p + A[:, 3] and in the bin floor(. + 0.5).  Returns
+    (frames, device_ms): a ctypes array of `count` HipMapDeposits rows and the device time of the launches."""
+    count = int(count)
+    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
+    levels = (C.c_float * max(1, len(values)))(*values)
+    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
+    if matrices.size % 12:
+        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    rows = (P.HipMapDeposits * max(1, count))()
+    ms = C.c_float(0)
+    _check(library().beamformer_hip_accumulate_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
+                                                                 matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
+                                                                 1 if use_offsets else 0, rows, C.byref(ms)))
+    return rows, float(ms.value)
+
+
+def localisation_map_copy(points=None):
+    """beamformer_hip_localisation_map_copy: (counts, info) -- the map as a uint32 array (Z, Y, X) and its HipMapInfo (the grid, and the
+    calls and deposits since the reset).  points: the map's grid (x, y, z), which sizes the array; None: the grid the newest
+    localisation_map_reset() of this module asked for."""
+    points = _map_points if points is None else tuple(int(v) for v in points)
+    if points is None:
+        raise ValueError("points: no localisation_map_reset() through this module yet")
+    out = np.zeros(max(1, int(np.prod(points))), np.uint32)
+    info = P.HipMapInfo()
+    _check(library().beamformer_hip_localisation_map_copy(out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(info)))
+    shape = (int(info.points[2]), int(info.points[1]), int(info.points[0]))
+    return out[: int(np.prod(shape))].reshape(shape), info
+
+
+def queue_localisation_map(scale=1.0, tag=0, timed=True):
+    """beamformer_hip_queue_localisation_map: the map's counts times `scale` queued into the frame ring as one Float32 frame of the
+    map's grid; the map itself is left as it is.  Returns (frame_id, device_ms); timed False: the call does not synchronise and
+    device_ms is 0."""
+    frame, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_queue_localisation_map(float(scale), int(tag), C.byref(frame), C.byref(ms) if timed else None))
+    return int(frame.value), float(ms.value)
+
+
+def map_placement(frame_transform, frame_points, map_transform, map_points):
+    """beamformer_hip_map_placement (host only): the float64 (3, 4) placement that takes a voxel position of the frame's grid (its
+    das_voxel_transform and points) to the map coordinate of the same point in space, for accumulate_peaks_last_frames."""
+    out = np.zeros(12, np.float64)
+    _check(library().beamformer_hip_map_placement((C.c_float * 16)(*[float(v) for v in frame_transform]),
+                                                  (C.c_uint32 * 3)(*[int(v) for v in frame_points]),
+                                                  (C.c_float * 16)(*[float(v) for v in map_transform]),
+                                                  (C.c_uint32 * 3)(*[int(v) for v in map_points]), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.reshape(3, 4)
 
 
 def gram_last_frames(count, region=None):

@@ -329,6 +329,22 @@ class HipFramePeaks(C.Structure):
                 ("threshold", C.c_float), ("first", C.c_uint32), ("stored", C.c_uint32), ("found", C.c_uint64), ("above_threshold", C.c_uint64)]
 
 
+HIP_MAX_MAP_VOXELS = 1 << 28    # BEAMFORMER_HIP_MAX_MAP_VOXELS
+
+
+class HipMapDeposits(C.Structure):
+    """BeamformerHipMapDeposits: one frame's row of beamformer_hip_accumulate_peaks_last_frames (96 bytes, no padding)"""
+    _fields_ = [("frame_id", C.c_uint32), ("parameter_block", C.c_uint32), ("data_kind", C.c_uint32), ("image_plane_tag", C.c_uint32),
+                ("points", C.c_uint32 * 3), ("region_first", C.c_uint32 * 3), ("region_count", C.c_uint32 * 3),
+                ("threshold", C.c_float), ("reserved", C.c_uint32 * 2), ("found", C.c_uint64), ("above_threshold", C.c_uint64),
+                ("deposited", C.c_uint64), ("outside", C.c_uint64)]
+
+
+class HipMapInfo(C.Structure):
+    """BeamformerHipMapInfo: the localisation map's grid and its totals since the reset (32 bytes, no padding)"""
+    _fields_ = [("points", C.c_uint32 * 3), ("calls", C.c_uint32), ("deposited", C.c_uint64), ("outside", C.c_uint64)]
+
+
 HIP_MAX_ENSEMBLE_FRAMES = 256
 HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
 HIP_MAX_SPATIAL_TAPS = 33       # BEAMFORMER_HIP_MAX_SPATIAL_TAPS
