@@ -139,7 +139,7 @@ hipError_t launch(void *ring, const uint64_t *offsets, const float *weights, con
 } // namespace
 
 /* Every table is device memory.  Every frame and the output run lie inside the ring, and the output run clear of the source frames:
- * the caller's business (executor.cpp: autocorrelate_last_frames), nothing here re-checks it. */
+ * the caller's business (frame_ops.cpp: autocorrelate_last_frames), nothing here re-checks it. */
 extern "C" hipError_t bf_launch_autocorr(void *ring, const uint64_t *offsets, const float *weights, const BfAutocorrArgs *a, hipStream_t s)
 {
 	if (!ring || !offsets || !a || a->frames == 0 || a->frames > BF_ENSEMBLE_MAX_FRAMES || a->rows == 0 || a->rows > BF_ENSEMBLE_MAX_FRAMES ||

@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <list>
 #include <vector>
@@ -19,6 +20,9 @@
 #include "../../include/ogl_beamformer_hip.h"
 
 namespace bf {
+
+#define HIP_OK(expr) ((expr) == hipSuccess)
+inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
 struct DeviceBuffer {
 	void  *ptr  = nullptr;
@@ -144,6 +148,29 @@ inline bool frame_run_bytes(const uint32_t points[3], const BeamformerHipView *v
 	return true;
 }
 
+/* The device state of the calls that work on frames already in the ring (frame_ops.cpp); all of it is created on first use. */
+struct FrameOps {
+	DeviceBuffer metrics_scratch;                              /* score_last_frames: the frames' BfMetricsRows, their results, the blocks' partials (frame_metrics.hip); find_peaks, accumulate_peaks, gram and correlate carve their tables from it too */
+	void        *metrics_pinned = nullptr;                     /* ... the pinned memory the rows are sent from and the results land in (free again when the call returns: it ends in a synchronise) */
+	size_t       metrics_pinned_size = 0;
+	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
+	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
+	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
+	struct LocalisationMap {
+		DeviceBuffer buffer;                                   /* the localisation map: `points` voxels of uint32 counts (beamformer_hip_localisation_map_reset; frame_peaks.hip deposits into it); points[0] == 0: none */
+		uint32_t     points[3]{};
+		uint32_t     calls = 0, block = 0;                     /* ... successful accumulate calls since the reset, and the parameter block of the newest frame of the last one */
+		uint64_t     deposited = 0, outside = 0;               /* ... and their totals */
+		void forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
+	} map;
+	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
+	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
+	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
+	bool         mix_copy_pending = false;
+	DeviceBuffer spatial_scratch;                              /* convolve_last_frames: what lies between two passes -- one run of frames, and the D fields of Normalised mode (spatial.hip) */
+	void release();                                            /* everything above freed and as constructed; the caller has synchronised the device */
+};
+
 /* Everything that lives on one HIP device.  A process normally owns one (devices[0]); after
  * beamformer_hip_set_devices it owns several, each beamforming one z-slab of every frame. */
 struct Device {
@@ -168,21 +195,7 @@ struct Device {
 	bool         have_sample = false;
 	uint64_t     replan_frame = 0;                             /* first frame of the current plan */
 	DeviceBuffer pair_counter, minmax_scratch, sum_scratch;
-	DeviceBuffer metrics_scratch;                              /* score_last_frames: the frames' BfMetricsRows, their results, the blocks' partials (frame_metrics.hip) */
-	void        *metrics_pinned = nullptr;                     /* ... the pinned memory the rows are sent from and the results land in (free again when the call returns: it ends in a synchronise) */
-	size_t       metrics_pinned_size = 0;
-	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
-	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
-	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
-	DeviceBuffer map;                                          /* the localisation map: map_points voxels of uint32 counts (beamformer_hip_localisation_map_reset; frame_peaks.hip deposits into it); map_points[0] == 0: none */
-	uint32_t     map_points[3]{};
-	uint32_t     map_calls = 0, map_block = 0;                 /* ... successful accumulate calls since the reset, and the parameter block of the newest frame of the last one */
-	uint64_t     map_deposited = 0, map_outside = 0;           /* ... and their totals */
-	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
-	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
-	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
-	bool         mix_copy_pending = false;
-	DeviceBuffer spatial_scratch;                              /* convolve_last_frames: what lies between two passes -- one run of frames, and the D fields of Normalised mode (spatial.hip) */
+	FrameOps     ops;                                          /* the calls on frames already in the ring (frame_ops.cpp) */
 	DeviceBuffer burst_stage[2];                               /* a burst: the pre-DAS stages' outputs of every frame of a burst, stage by stage */
 	PushRecord   multi;
 	DeviceBuffer readi_decoded;                                /* a READI image push: the DAS input decoded across its acquisitions (readi_decode.hip), 64 spare bytes behind it */
@@ -285,6 +298,17 @@ bool copy_das_input(void *out, uint64_t out_size);
 bool copy_das_input_frame(uint32_t frame, void *out, uint64_t out_size);
 bool sum_last_frames(uint32_t count, void *out, uint64_t out_size);
 bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float *out, uint64_t out_floats);
+const FrameRecord *record_of(const Device &d, uint32_t frame_id);   /* null: no such frame, a tombstone, or storage that a newer frame reused */
+bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
+bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);
+void shutdown_device();
+/* ... and for frame_ops.cpp: the ring side of a run of `count` frames of `points` voxels queued behind the newest frames -- where
+ * the placement rule will put it, and the run itself: its ids taken and its frames placed, then enqueue(first id, first frame's record) */
+bool queued_run_landing(const Device &d, const uint32_t points[3], uint32_t count, bool cplx, uint64_t &run_first, uint64_t &run_bytes);
+bool claim_queued_run(Device &d, const uint32_t points[3], uint32_t tag, uint32_t count, bool cplx, uint32_t block,
+                      const std::function<bool(uint64_t first, const FrameRecord &frame0)> &enqueue);
+
+/* frame_ops.cpp */
 bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms);
 bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
                             uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
@@ -307,10 +331,6 @@ bool convolve_last_frames(uint32_t count, const float *const taps[3], const uint
 bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3], const float node_first[3], const float node_step[3],
                       const float *rotations, uint32_t interpolation, uint32_t edge, uint32_t image_plane_tag,
                       uint32_t *first_frame_id, float *device_ms);            /* likewise: the field, the lattice and the modes are checked by the caller */
-const FrameRecord *record_of(const Device &d, uint32_t frame_id);   /* null: no such frame, a tombstone, or storage that a newer frame reused */
-bool copy_frame(uint32_t frame_id, void *out, uint64_t out_size);
-bool frame_info(uint32_t frame_id, BeamformerHipFrameInfo *out);
-void shutdown_device();
 
 } // namespace bf
 #endif

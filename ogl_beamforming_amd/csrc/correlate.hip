@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void correlate_fold_kernel(const BfCorrelateRo
 	table[entry] = total;
 }
 
-/* Every table is device memory.  Every box lies inside the frames and every frame inside the ring: the caller's business (executor.cpp:
+/* Every table is device memory.  Every box lies inside the frames and every frame inside the ring: the caller's business (frame_ops.cpp:
  * correlate_last_frames); what is checked here is that the rows' geometry fits the kernel's LDS arrays -- the caller reads the rows
  * back from where it made them, the launcher cannot. */
 extern "C" hipError_t bf_launch_correlate(const void *ring, const uint64_t *offsets, const BfCorrelateRow *rows, const BfCorrelateArgs *a,

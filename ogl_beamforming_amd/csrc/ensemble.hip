@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void mix_kernel(char *ring, const uint64_t *__
 }
 
 /* Every table is device memory.  The box lies inside every frame, every frame and the output run inside the ring, and the output run
- * clear of the source frames: the caller's business (executor.cpp: gram_last_frames, mix_last_frames), nothing here re-checks it. */
+ * clear of the source frames: the caller's business (frame_ops.cpp: gram_last_frames, mix_last_frames), nothing here re-checks it. */
 extern "C" hipError_t bf_launch_gram(const void *ring, const uint64_t *offsets, const BfGramArgs *a, uint64_t *mask, double *partials, void *result,
                                      hipStream_t s)
 {

@@ -35,8 +35,6 @@ bool set_error(BeamformerLibErrorKind kind)
 	return false;
 }
 
-#define HIP_OK(expr) ((expr) == hipSuccess)
-
 bool DeviceBuffer::ensure(size_t bytes)
 {
 	if (bytes <= size && ptr) return true;
@@ -52,8 +50,6 @@ void DeviceBuffer::release()
 	if (ptr) (void)hipFree(ptr);
 	ptr = nullptr; size = 0;
 }
-
-static uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
 /* beamformer.c:196-228 picks the first of {4, 2, 1.5, 1} GiB that fits half the device heap;
  * on a 288 GB MI355X that is always 4 GiB, so the default needs no device query.
@@ -183,22 +179,7 @@ static void release_one_device(Device &d)
 	for (auto &vp : d.variant_plans) vp.clear();
 	for (auto &ip : d.image_plans) { ip.ps.transmits.release(); ip.ps.sparse.release(); ip.ps.valid = false; ip.ps.das_parts.clear(); }
 	d.readi_decoded.release(); d.das_decoded_bytes = 0;
-	d.metrics_scratch.release();
-	d.peaks_list.release();
-	if (d.peaks_begin) (void)hipEventDestroy(d.peaks_begin);
-	if (d.peaks_end)   (void)hipEventDestroy(d.peaks_end);
-	d.peaks_begin = d.peaks_end = nullptr;
-	d.map.release();
-	d.map_points[0] = d.map_points[1] = d.map_points[2] = 0; d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
-	d.mix_table.release();
-	d.spatial_scratch.release();
-	if (d.mix_pinned) (void)hipHostFree(d.mix_pinned);
-	for (hipEvent_t *e : {&d.mix_copied, &d.mix_begin, &d.mix_end}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-	d.mix_pinned = nullptr; d.mix_copy_pending = false;
-	if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
-	if (d.metrics_begin) (void)hipEventDestroy(d.metrics_begin);
-	if (d.metrics_end)   (void)hipEventDestroy(d.metrics_end);
-	d.metrics_pinned = nullptr; d.metrics_pinned_size = 0; d.metrics_begin = d.metrics_end = nullptr;
+	d.ops.release();
 	d.views_table.release();
 	if (d.views_pinned) (void)hipHostFree(d.views_pinned);
 	if (d.views_copied) (void)hipEventDestroy(d.views_copied);
@@ -2345,647 +2326,24 @@ bool display_last_frame(float threshold_db, float gamma, float db_cutoff, float 
 	return ok || set_error(BeamformerLibErrorKind_InvalidAccess);
 }
 
-namespace {
-
-/* one of the `count` newest frames as score_last_frames and find_peaks_last_frames take it: its record, and the box inside it */
-struct BoxedFrame {
-	const FrameRecord *record;
-	uint32_t first[3], count[3], cplx;
-	uint64_t volume;                 /* voxels of the box */
-};
-
-/* The `count` newest frames of the one device, oldest first, each with the box of `region` (NULL: the frame whole).  The records are
- * judged the way export_last_frames and sum_last_frames judge theirs -- but ANY frame missing refuses: something per frame is promised.
- * False, with InvalidAccess set: no device or several, fewer frames queued, a tombstone, an overwritten record, reused storage, a box
- * that does not fit inside every frame, a frame that does not lie inside the ring. */
-bool newest_boxed_frames(uint32_t count, const BeamformerHipFrameRegion *region, std::vector<BoxedFrame> &out)
+/* The ring side of a run that frame_ops.cpp queues behind the newest frames (queue_frames_of_newest): `count` frames of `points`
+ * voxels.  Where the ring's placement rule (place_frames) will put it; false: it does not fit the ring. */
+bool queued_run_landing(const Device &d, const uint32_t points[3], uint32_t count, bool cplx, uint64_t &run_first, uint64_t &run_bytes)
 {
-	Context &c = g_context;
-	/* several devices: a frame is a set of z-slabs there, and a z neighbour would lie across them */
-	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	Device &d = c.devices[0];
-	if (count > d.frame_counter || count > d.frames.size()) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	if (region) for (int k = 0; k < 3; k++) if (!region->count[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	out.resize(count);
-	const uint64_t first_id = d.frame_counter - count;
-	for (uint32_t n = 0; n < count; n++) {
-		const FrameRecord &f = d.frames[(first_id + n) % d.frames.size()];
-		if (f.id != (uint32_t)(first_id + n) || f.failed || !f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
-		BoxedFrame &b = out[n];
-		b.record = &f;
-		b.cplx = f.data_kind == BeamformerDataKind_Float32Complex;
-		b.volume = 1;
-		for (int k = 0; k < 3; k++) {
-			b.first[k] = region ? region->first[k] : 0u;
-			b.count[k] = region ? region->count[k] : f.points[k];
-			/* the box inside the frame (a frame of no voxels -- a pipeline without DAS on a peer -- holds no box) */
-			if (!b.count[k] || (uint64_t)b.first[k] + b.count[k] > f.points[k]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-			b.volume *= b.count[k];     /* (at most the frame's voxels, which fit its record's 64-bit byte count) */
-		}
-		/* and the frame inside the ring: what the kernels index with is what the record says */
-		if (f.offset > d.ring.size || f.bytes > d.ring.size - f.offset ||
-		    (uint64_t)f.points[0] * f.points[1] * f.points[2] * (b.cplx ? 8u : 4u) > f.bytes) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	}
+	if (!run_bytes_of([points](uint32_t) { return FrameShape{points, 0}; }, count, cplx ? 8u : 4u, d.ring.size, run_bytes)) return false;
+	run_first = d.ring_next_offset > d.ring.size - run_bytes ? 0 : d.ring_next_offset;
 	return true;
 }
 
-/* the pinned memory, the device scratch and the first event pair that score_last_frames and find_peaks_last_frames share: both calls
- * end in a synchronise, so all of it is free again when either returns */
-bool ensure_metrics_memory(Device &d, size_t pinned_bytes, size_t device_bytes)
+/* ... and the run itself: ids first .. first + M - 1, taken from the counters a push advances, its frames placed, their timing slots
+ * reset; then enqueue(first, the first frame's record), whose result is the call's: false leaves tombstones under the ids, as a push does */
+bool claim_queued_run(Device &d, const uint32_t points[3], uint32_t tag, uint32_t M, bool cplx, uint32_t block,
+                      const std::function<bool(uint64_t first, const FrameRecord &frame0)> &enqueue)
 {
-	bool ok = true;
-	if (d.metrics_pinned_size < pinned_bytes) {
-		if (d.metrics_pinned) (void)hipHostFree(d.metrics_pinned);
-		d.metrics_pinned = nullptr; d.metrics_pinned_size = 0;
-		ok = HIP_OK(hipHostMalloc(&d.metrics_pinned, pinned_bytes, hipHostMallocDefault));
-		if (ok) d.metrics_pinned_size = pinned_bytes; else d.metrics_pinned = nullptr;
-	}
-	ok = ok && d.metrics_scratch.ensure(device_bytes);
-	if (ok && !d.metrics_begin) ok = HIP_OK(hipEventCreate(&d.metrics_begin));
-	if (ok && !d.metrics_end)   ok = HIP_OK(hipEventCreate(&d.metrics_end));
-	return ok;
-}
-
-/* the mark pass's rows of the boxed frames (frame_peaks.hip), as find_peaks_last_frames and accumulate_peaks_last_frames launch it: the
- * waves and blocks of all frames, the most blocks of one.  False, with InvalidAccess set: a box of more waves than the kernels number */
-struct PeaksRows {
-	std::vector<BfPeaksRow> rows;
-	uint64_t waves = 0, blocks = 0;
-	uint32_t max_blocks = 0;
-};
-bool peaks_rows_of(const std::vector<BoxedFrame> &boxed, const float *thresholds, uint32_t threshold_count, uint32_t cap, PeaksRows &out)
-{
-	const uint32_t count = (uint32_t)boxed.size();
-	out.rows.resize(count);
-	for (uint32_t n = 0; n < count; n++) {
-		const BoxedFrame &b = boxed[n];
-		BfPeaksRow &r = out.rows[n];
-		r = BfPeaksRow{};
-		r.offset = b.record->offset;
-		r.cplx = b.cplx;
-		for (int k = 0; k < 3; k++) { r.points[k] = b.record->points[k]; r.first[k] = b.first[k]; r.count[k] = b.count[k]; }
-		const uint64_t per_row = ((uint64_t)r.count[0] + 63u) / 64u, frame_waves = per_row * r.count[1] * r.count[2];
-		/* (a frame of the ring has far fewer voxels than this: a bound that keeps the kernels' 32-bit wave numbers honest) */
-		if (frame_waves > 4ull * BF_PEAKS_MAX_BLOCKS - 3u) return set_error(BeamformerLibErrorKind_InvalidAccess);
-		r.waves_per_row = (uint32_t)per_row;
-		r.waves = (uint32_t)frame_waves;
-		r.blocks = (uint32_t)((frame_waves + 3u) / 4u);
-		r.wave_first = out.waves; r.block_first = out.blocks;
-		const float t = thresholds[threshold_count == 1 ? 0 : n];
-		r.threshold = b.cplx ? t * t : t;
-		r.cap = cap;
-		out.waves += r.waves; out.blocks += r.blocks;
-		if (r.blocks > out.max_blocks) out.max_blocks = r.blocks;
-	}
-	return true;
-}
-
-} // namespace
-
-/* beamformer_hip_score_last_frames: focus metrics of the `count` newest frames, reduced where they lie (frame_metrics.hip).  Everything
- * that can refuse is decided before anything is enqueued. */
-bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms)
-{
-	std::vector<BoxedFrame> boxed;
-	if (!newest_boxed_frames(count, region, boxed)) return false;
-	Device &d = g_context.devices[0];
-
-	const size_t rows_bytes = round_up(sizeof(BfMetricsRow) * count, 64), results_bytes = round_up(sizeof(BfMetricsResult) * count, 64);
-	std::vector<BfMetricsRow> rows(count);
-	uint32_t partials = 0, max_blocks = 0;
-	for (uint32_t n = 0; n < count; n++) {
-		const BoxedFrame &b = boxed[n];
-		BfMetricsRow &r = rows[n];
-		r = BfMetricsRow{};
-		r.offset = b.record->offset;
-		r.cplx = b.cplx;
-		for (int k = 0; k < 3; k++) { r.points[k] = b.record->points[k]; r.first[k] = b.first[k]; r.count[k] = b.count[k]; }
-		r.blocks = bf_metrics_blocks(b.volume);
-		r.partial_first = partials;
-		const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
-		r.step[0] = (uint32_t)(stride % r.count[0]);
-		r.step[1] = (uint32_t)(stride / r.count[0] % r.count[1]);
-		r.step[2] = (uint32_t)(stride / plane);
-		partials += r.blocks;
-		if (r.blocks > max_blocks) max_blocks = r.blocks;
-	}
-
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	const size_t partials_bytes = sizeof(BfMetricsPartial) * partials, pinned_bytes = rows_bytes + results_bytes;
-	ok = ok && ensure_metrics_memory(d, pinned_bytes, rows_bytes + results_bytes + partials_bytes);
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
-	const BfMetricsRow *device_rows    = (const BfMetricsRow *)device;
-	BfMetricsResult    *device_results = (BfMetricsResult *)(device + rows_bytes);
-	BfMetricsPartial   *device_partials = (BfMetricsPartial *)(device + rows_bytes + results_bytes);
-	const BfMetricsResult *results = (const BfMetricsResult *)(pinned + rows_bytes);
-	std::memcpy(pinned, rows.data(), sizeof(BfMetricsRow) * count);
-	hipStream_t s = d.stream;
-	ok &= HIP_OK(hipMemcpyAsync(device, pinned, sizeof(BfMetricsRow) * count, hipMemcpyHostToDevice, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
-	if (ok) ok &= HIP_OK(bf_launch_frame_metrics(d.ring.ptr, device_rows, count, max_blocks, device_partials, device_results, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
-	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + rows_bytes, device_results, sizeof(BfMetricsResult) * count, hipMemcpyDeviceToHost, s));
-	/* the one synchronise: also what frees the pinned memory for the next call, so it runs whatever failed above */
-	ok &= HIP_OK(hipStreamSynchronize(s));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (device_ms) {
-		float ms = 0;
-		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
-	}
-
-	for (uint32_t n = 0; n < count; n++) {
-		const FrameRecord &f = *boxed[n].record;
-		const BfMetricsRow &r = rows[n];
-		const BfMetricsResult &v = results[n];
-		BeamformerHipFrameMetrics &m = out[n];
-		std::memset(&m, 0, sizeof(m));
-		m.frame_id = f.id; m.parameter_block = f.block; m.data_kind = (uint32_t)f.data_kind; m.image_plane_tag = f.tag;
-		const uint64_t plane = (uint64_t)f.points[0] * f.points[1];
-		for (int k = 0; k < 3; k++) {
-			m.points[k] = f.points[k]; m.region_first[k] = r.first[k]; m.region_count[k] = r.count[k];
-			m.gradient_pairs[k] = v.pairs[k]; m.gradient2[k] = v.g[k];
-		}
-		m.max_index[0] = (uint32_t)(v.max_index % f.points[0]);
-		m.max_index[1] = (uint32_t)(v.max_index / f.points[0] % f.points[1]);
-		m.max_index[2] = (uint32_t)(v.max_index / plane);
-		m.voxels = v.voxels; m.non_finite = v.bad;
-		m.sum_abs = v.s1; m.sum_abs2 = v.s2; m.sum_abs4 = v.s4;
-		m.max_abs = v.max_abs;
-	}
-	return true;
-}
-
-/* beamformer_hip_find_peaks_last_frames: the local maxima of the `count` newest frames, found where they lie (frame_peaks.hip).  The
- * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Two synchronises:
- * the list buffer is sized by what the scan found. */
-bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                            uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
-                            float *device_ms)
-{
-	static_assert(sizeof(BeamformerHipFramePeak) == 32 && sizeof(BeamformerHipFramePeaks) == 80, "records without padding");
-	std::vector<BoxedFrame> boxed;
-	if (!newest_boxed_frames(count, region, boxed)) return false;
-	Device &d = g_context.devices[0];
-
-	PeaksRows table;
-	if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
-	const std::vector<BfPeaksRow> &rows = table.rows;
-	const uint64_t waves = table.waves, blocks = table.blocks;
-	const uint32_t max_blocks = table.max_blocks;
-
-	/* device: rows | results | firsts | masks | counts | offsets; pinned: rows | results | firsts */
-	const size_t rows_bytes = round_up(sizeof(BfPeaksRow) * count, 64), results_bytes = round_up(sizeof(BfPeaksResult) * count, 64),
-	             firsts_bytes = round_up(sizeof(uint32_t) * count, 64), masks_bytes = round_up(sizeof(uint64_t) * waves, 64),
-	             counts_bytes = round_up(sizeof(uint32_t) * blocks, 64);
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && ensure_metrics_memory(d, rows_bytes + results_bytes + firsts_bytes, rows_bytes + results_bytes + firsts_bytes + masks_bytes + 2 * counts_bytes);
-	if (ok && !d.peaks_begin) ok = HIP_OK(hipEventCreate(&d.peaks_begin));
-	if (ok && !d.peaks_end)   ok = HIP_OK(hipEventCreate(&d.peaks_end));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
-	const BfPeaksRow *device_rows    = (const BfPeaksRow *)device;
-	BfPeaksResult    *device_results = (BfPeaksResult *)(device + rows_bytes);
-	uint32_t         *device_firsts  = (uint32_t *)(device + rows_bytes + results_bytes);
-	uint64_t         *device_masks   = (uint64_t *)(device + rows_bytes + results_bytes + firsts_bytes);
-	uint32_t         *device_counts  = (uint32_t *)((char *)device_masks + masks_bytes);
-	uint32_t         *device_offsets = (uint32_t *)((char *)device_counts + counts_bytes);
-	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + rows_bytes);
-	uint32_t            *firsts  = (uint32_t *)(pinned + rows_bytes + results_bytes);
-	std::memcpy(pinned, rows.data(), sizeof(BfPeaksRow) * count);
-	hipStream_t s = d.stream;
-	ok &= HIP_OK(hipMemcpyAsync(device, pinned, sizeof(BfPeaksRow) * count, hipMemcpyHostToDevice, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
-	if (ok) ok &= HIP_OK(bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, max_blocks, device_masks, device_counts, device_offsets, device_results, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
-	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + rows_bytes, device_results, sizeof(BfPeaksResult) * count, hipMemcpyDeviceToHost, s));
-	/* the first synchronise runs whatever failed above: it is what frees the pinned memory */
-	ok &= HIP_OK(hipStreamSynchronize(s));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	uint32_t total = 0;                  /* (at most 1024 frames x 65536 records) */
-	std::vector<uint32_t> stored(count);
-	for (uint32_t n = 0; n < count; n++) {
-		stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
-		firsts[n] = total;
-		total += stored[n];
-	}
-	float ms = 0, emit_ms = 0;
-	const bool timed = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end));
-	if (total) {
-		ok = d.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak));
-		if (ok) {
-			ok &= HIP_OK(hipMemcpyAsync(device_firsts, firsts, sizeof(uint32_t) * count, hipMemcpyHostToDevice, s));
-			ok &= HIP_OK(hipEventRecord(d.peaks_begin, s));
-			if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, max_blocks, device_masks, device_counts, device_offsets,
-			                                                device_firsts, d.peaks_list.ptr, s));
-			ok &= HIP_OK(hipEventRecord(d.peaks_end, s));
-			if (ok) ok &= HIP_OK(hipMemcpyAsync(peaks, d.peaks_list.ptr, (size_t)total * sizeof(BeamformerHipFramePeak), hipMemcpyDeviceToHost, s));
-			ok &= HIP_OK(hipStreamSynchronize(s));
-		}
-		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-		if (!HIP_OK(hipEventElapsedTime(&emit_ms, d.peaks_begin, d.peaks_end))) emit_ms = 0;
-	}
-	if (device_ms) *device_ms = timed ? ms + emit_ms : 0.0f;
-
-	for (uint32_t n = 0; n < count; n++) {
-		const FrameRecord &f = *boxed[n].record;
-		BeamformerHipFramePeaks &m = frames[n];
-		std::memset(&m, 0, sizeof(m));
-		m.frame_id = f.id; m.parameter_block = f.block; m.data_kind = (uint32_t)f.data_kind; m.image_plane_tag = f.tag;
-		for (int k = 0; k < 3; k++) { m.points[k] = f.points[k]; m.region_first[k] = rows[n].first[k]; m.region_count[k] = rows[n].count[k]; }
-		m.threshold = thresholds[threshold_count == 1 ? 0 : n];
-		m.first = firsts[n]; m.stored = stored[n];
-		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
-	}
-	*peak_count = total;
-	return true;
-}
-
-/* beamformer_hip_localisation_map_reset: the one map of the one device, (re)allocated and zeroed on the current stream; points null:
- * released.  The extents arrive checked (lib_api.cpp). */
-bool localisation_map_reset(const uint32_t points[3])
-{
-	Context &c = g_context;
-	Device &d = c.devices[0];
-	if (!points) {
-		if (c.device_ready && d.map.ptr) {
-			bool ok = HIP_OK(hipSetDevice(d.device));
-			ok = ok && HIP_OK(hipStreamSynchronize(d.stream));          /* a deposit or a conversion may still be reading it */
-			if (!ok) (void)hipGetLastError();
-			d.map.release();
-		}
-		d.map_points[0] = d.map_points[1] = d.map_points[2] = 0; d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
-		return true;
-	}
-	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	const size_t bytes = sizeof(uint32_t) * (size_t)points[0] * points[1] * points[2];
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	/* (a buffer that has to grow is freed first: what is enqueued on it must have run) */
-	if (ok && d.map.ptr && d.map.size < bytes) ok = HIP_OK(hipStreamSynchronize(d.stream));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (!d.map.ensure(bytes)) {
-		(void)hipGetLastError();
-		d.map_points[0] = d.map_points[1] = d.map_points[2] = 0; d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
-		return set_error(BeamformerLibErrorKind_RFDataSizeOverflow);
-	}
-	for (int k = 0; k < 3; k++) d.map_points[k] = points[k];
-	d.map_calls = d.map_block = 0; d.map_deposited = d.map_outside = 0;
-	if (!HIP_OK(hipMemsetAsync(d.map.ptr, 0, bytes, d.stream))) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	return true;
-}
-
-/* beamformer_hip_accumulate_peaks_last_frames: the peaks of the `count` newest frames binned into the localisation map where they lie
- * (frame_peaks.hip: the mark pass and the scan of find_peaks_last_frames, then the deposit and the scan again over its words).  The
- * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  One synchronise:
- * no buffer is sized by what was found. */
-bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                                  const double *placements, uint32_t placement_count, uint32_t use_offsets, BeamformerHipMapDeposits *frames,
-                                  float *device_ms)
-{
-	static_assert(sizeof(BeamformerHipMapDeposits) == 96 && sizeof(BeamformerHipMapInfo) == 32, "records without padding");
-	static_assert(BF_MAP_MAX_VOXELS == BEAMFORMER_HIP_MAX_MAP_VOXELS, "one limit");
-	std::vector<BoxedFrame> boxed;
-	if (!newest_boxed_frames(count, region, boxed)) return false;
-	Device &d = g_context.devices[0];
-	if (!d.map.ptr || !d.map_points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	PeaksRows table;
-	if (!peaks_rows_of(boxed, thresholds, threshold_count, 0, table)) return false;      /* (the cap is the emit pass's: not read) */
-
-	/* device: rows | placements | results | tallies | masks | counts | offsets | words; pinned: the first four */
-	const size_t rows_bytes = round_up(sizeof(BfPeaksRow) * count, 64), placements_bytes = round_up(sizeof(double) * 12 * count, 64),
-	             results_bytes = round_up(sizeof(BfPeaksResult) * count, 64), masks_bytes = round_up(sizeof(uint64_t) * table.waves, 64),
-	             counts_bytes = round_up(sizeof(uint32_t) * table.blocks, 64), up_bytes = rows_bytes + placements_bytes;
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && ensure_metrics_memory(d, up_bytes + 2 * results_bytes, up_bytes + 2 * results_bytes + masks_bytes + 3 * counts_bytes);
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
-	const BfPeaksRow *device_rows       = (const BfPeaksRow *)device;
-	const double     *device_placements = (const double *)(device + rows_bytes);
-	BfPeaksResult    *device_results    = (BfPeaksResult *)(device + up_bytes);
-	BfPeaksResult    *device_tallies    = (BfPeaksResult *)(device + up_bytes + results_bytes);
-	uint64_t         *device_masks      = (uint64_t *)(device + up_bytes + 2 * results_bytes);
-	uint32_t         *device_counts     = (uint32_t *)((char *)device_masks + masks_bytes);
-	uint32_t         *device_offsets    = (uint32_t *)((char *)device_counts + counts_bytes);
-	uint32_t         *device_words      = (uint32_t *)((char *)device_offsets + counts_bytes);
-	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + up_bytes), *tallies = (const BfPeaksResult *)(pinned + up_bytes + results_bytes);
-	std::memcpy(pinned, table.rows.data(), sizeof(BfPeaksRow) * count);
-	for (uint32_t n = 0; n < count; n++)
-		std::memcpy(pinned + rows_bytes + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
-	BfMapArgs a{};
-	for (int k = 0; k < 3; k++) a.points[k] = d.map_points[k];
-	a.use_offsets = use_offsets != 0;
-	hipStream_t s = d.stream;
-	ok &= HIP_OK(hipMemcpyAsync(device, pinned, rows_bytes + sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
-	if (ok) ok &= HIP_OK(bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s));
-	if (ok) ok &= HIP_OK(bf_launch_localisation_deposit(d.ring.ptr, device_rows, device_placements, count, table.max_blocks, device_masks, device_counts,
-	                                                   device_offsets, &a, (uint32_t *)d.map.ptr, device_words, device_tallies, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
-	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + up_bytes, device_results, results_bytes + sizeof(BfPeaksResult) * count, hipMemcpyDeviceToHost, s));
-	/* the one synchronise: also what frees the pinned memory for the next call, so it runs whatever failed above */
-	ok &= HIP_OK(hipStreamSynchronize(s));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (device_ms) {
-		float ms = 0;
-		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
-	}
-
-	for (uint32_t n = 0; n < count; n++) {
-		const FrameRecord &f = *boxed[n].record;
-		d.map_deposited += tallies[n].found; d.map_outside += tallies[n].above_threshold;
-		if (!frames) continue;
-		BeamformerHipMapDeposits &m = frames[n];
-		std::memset(&m, 0, sizeof(m));
-		m.frame_id = f.id; m.parameter_block = f.block; m.data_kind = (uint32_t)f.data_kind; m.image_plane_tag = f.tag;
-		for (int k = 0; k < 3; k++) { m.points[k] = f.points[k]; m.region_first[k] = table.rows[n].first[k]; m.region_count[k] = table.rows[n].count[k]; }
-		m.threshold = thresholds[threshold_count == 1 ? 0 : n];
-		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
-		m.deposited = tallies[n].found; m.outside = tallies[n].above_threshold;
-	}
-	d.map_calls++;
-	d.map_block = boxed[count - 1].record->block;
-	return true;
-}
-
-/* beamformer_hip_localisation_map_copy: the counts as they are, behind everything enqueued on the current stream */
-bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info)
-{
-	Context &c = g_context;
-	Device &d = c.devices[0];
-	if (!c.device_ready || c.device_count != 1 || !d.map.ptr || !d.map_points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	const uint64_t voxels = (uint64_t)d.map_points[0] * d.map_points[1] * d.map_points[2];
-	if (out_count < voxels) return set_error(BeamformerLibErrorKind_ExportSpaceOverflow);
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && HIP_OK(hipMemcpyAsync(out, d.map.ptr, sizeof(uint32_t) * voxels, hipMemcpyDeviceToHost, d.stream));
-	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (info) {
-		std::memset(info, 0, sizeof(*info));
-		for (int k = 0; k < 3; k++) info->points[k] = d.map_points[k];
-		info->calls = d.map_calls; info->deposited = d.map_deposited; info->outside = d.map_outside;
-	}
-	return true;
-}
-
-namespace {
-
-/* the `count` newest frames as the ensemble calls take them: of one grid and one kind (else DataSizeMismatch), boxed */
-bool newest_ensemble_frames(uint32_t count, const BeamformerHipFrameRegion *region, std::vector<BoxedFrame> &boxed)
-{
-	if (!newest_boxed_frames(count, region, boxed)) return false;
-	const FrameRecord &f0 = *boxed[0].record;
-	for (uint32_t n = 1; n < count; n++) {
-		const FrameRecord &f = *boxed[n].record;
-		if (f.data_kind != f0.data_kind || f.points[0] != f0.points[0] || f.points[1] != f0.points[1] || f.points[2] != f0.points[2])
-			return set_error(BeamformerLibErrorKind_DataSizeMismatch);
-	}
-	return true;
-}
-
-} // namespace
-
-/* beamformer_hip_gram_last_frames: the slow-time Gram matrix of the `count` newest frames, reduced where they lie (ensemble.hip).
- * Everything that can refuse is decided before anything is enqueued. */
-bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms)
-{
-	static_assert(sizeof(BeamformerHipEnsembleInfo) == 64, "a record without padding");
-	static_assert(BF_ENSEMBLE_MAX_FRAMES == BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, "one limit");
-	std::vector<BoxedFrame> boxed;
-	if (!newest_ensemble_frames(count, region, boxed)) return false;
-	Device &d = g_context.devices[0];
-	const BoxedFrame &b0 = boxed[0];
-	if (b0.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);     /* the kernels count a box's voxels in 32 bits */
-
-	BfGramArgs a{};
-	a.frames = count; a.cplx = b0.cplx;
-	for (int k = 0; k < 3; k++) { a.points[k] = b0.record->points[k]; a.first[k] = b0.first[k]; a.count[k] = b0.count[k]; }
-	a.volume = (uint32_t)b0.volume;
-	a.words = (uint32_t)((b0.volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
-	a.chunk_words = bf_gram_chunk_words(a.volume, count);
-	a.chunks = (a.words + a.chunk_words - 1u) / a.chunk_words;
-	a.tiles = bf_gram_tiles(count); a.tile_pairs = bf_gram_tile_pairs(count);
-
-	/* device: offsets | result {voxels, non_finite, gram} | mask | partials; pinned: offsets | result */
-	const size_t offsets_bytes = round_up(sizeof(uint64_t) * count, 64), gram_bytes = sizeof(double) * 2 * count * count,
-	             result_bytes = round_up(16 + gram_bytes, 64), mask_bytes = round_up(sizeof(uint64_t) * a.words, 64),
-	             partials_bytes = sizeof(double) * 2 * BF_GRAM_TILE * BF_GRAM_TILE * a.tile_pairs * a.chunks;
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && ensure_metrics_memory(d, offsets_bytes + result_bytes, offsets_bytes + result_bytes + mask_bytes + partials_bytes);
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
-	uint64_t *offsets = (uint64_t *)pinned;
-	for (uint32_t n = 0; n < count; n++) offsets[n] = boxed[n].record->offset;
-	const char *result = pinned + offsets_bytes;
-	hipStream_t s = d.stream;
-	ok &= HIP_OK(hipMemcpyAsync(device, pinned, sizeof(uint64_t) * count, hipMemcpyHostToDevice, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
-	if (ok) ok &= HIP_OK(bf_launch_gram(d.ring.ptr, (const uint64_t *)device, &a, (uint64_t *)(device + offsets_bytes + result_bytes),
-	                                    (double *)(device + offsets_bytes + result_bytes + mask_bytes), device + offsets_bytes, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
-	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + offsets_bytes, device + offsets_bytes, 16 + gram_bytes, hipMemcpyDeviceToHost, s));
-	/* the synchronise runs whatever failed above: it is what frees the pinned memory */
-	ok &= HIP_OK(hipStreamSynchronize(s));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (device_ms) {
-		float ms = 0;
-		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
-	}
-	std::memcpy(gram, result + 16, gram_bytes);
-	if (info) {
-		std::memset(info, 0, sizeof(*info));
-		info->count = count; info->data_kind = (uint32_t)b0.record->data_kind;
-		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->region_first[k] = a.first[k]; info->region_count[k] = a.count[k]; }
-		info->first_frame_id = b0.record->id;
-		std::memcpy(&info->voxels, result, 8); std::memcpy(&info->non_finite, result + 8, 8);
-	}
-	return true;
-}
-
-/* beamformer_hip_correlate_last_frames: the `count` newest frames correlated with one of them at every shift of the window, over every
- * box, where they lie (correlate.hip).  The arguments arrive checked (lib_api.cpp: the counts, the window, the entry cap); everything
- * else that can refuse is decided before anything is enqueued. */
-bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions, uint32_t region_count,
-                           const uint32_t max_shift[3], BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info, float *device_ms)
-{
-	static_assert(sizeof(BeamformerHipShiftCorrelation) == 40 && sizeof(BfCorrelateEntry) == 40, "one record, without padding");
-	static_assert(sizeof(BeamformerHipCorrelationInfo) == 56, "a record without padding");
-	static_assert(BF_CORRELATE_MAX_SHIFT == BEAMFORMER_HIP_MAX_SHIFT && BF_CORRELATE_MAX_SHIFTS == BEAMFORMER_HIP_MAX_SHIFTS, "one limit");
-	const uint32_t boxes = regions ? region_count : 1u;
-
-	BfCorrelateArgs a{};
-	a.frames = count; a.reference = reference; a.regions = boxes;
-	a.shifts = 1;
-	for (int k = 0; k < 3; k++) { a.max_shift[k] = max_shift[k]; a.window[k] = 2u * max_shift[k] + 1u; a.shifts *= a.window[k]; }
-	a.groups = bf_correlate_groups(a.shifts);
-	a.batches = (a.shifts + BF_CORRELATE_THREADS - 1u) / BF_CORRELATE_THREADS;
-
-	/* the frames once a box: the same K records each time, and the box of each region judged against every one of them */
-	std::vector<BoxedFrame> boxed, frames;
-	std::vector<BfCorrelateRow> rows(boxes);
-	uint64_t partials = 0;
-	for (uint32_t r = 0; r < boxes; r++) {
-		if (!newest_ensemble_frames(count, regions ? regions + r : nullptr, boxed)) return false;
-		const BoxedFrame &b = boxed[0];
-		if (b.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);      /* the kernels count a box's voxels in 32 bits */
-		if (r == 0) frames = boxed;
-		BfCorrelateRow &row = rows[r];
-		row = BfCorrelateRow{};
-		for (int k = 0; k < 3; k++) { row.first[k] = b.first[k]; row.count[k] = b.count[k]; }
-		bf_correlate_tile(row.count, a.max_shift, row.tile);
-		uint32_t tiles = 1;                                   /* (at most the box's voxels) */
-		row.tile_voxels = 1; row.halo_voxels = 1;
-		for (int k = 0; k < 3; k++) {
-			row.tiles[k] = (row.count[k] + row.tile[k] - 1u) / row.tile[k];
-			row.halo[k] = row.tile[k] + 2u * a.max_shift[k];
-			tiles *= row.tiles[k]; row.tile_voxels *= row.tile[k]; row.halo_voxels *= row.halo[k];
-		}
-		row.chunk_tiles = bf_correlate_chunk_tiles(tiles, a.shifts);
-		row.chunks = (tiles + row.chunk_tiles - 1u) / row.chunk_tiles;
-		row.partial_first = partials;
-		partials += (uint64_t)row.chunks * count * a.shifts;
-		if (row.chunks > a.max_chunks) a.max_chunks = row.chunks;
-	}
-	Device &d = g_context.devices[0];
-	const BoxedFrame &b0 = frames[0];
-	a.cplx = b0.cplx;
-	for (int k = 0; k < 3; k++) a.points[k] = b0.record->points[k];
-
-	/* device: offsets | rows | table | partials; pinned: offsets | rows | table */
-	const size_t entries = (size_t)boxes * count * a.shifts;
-	const size_t offsets_bytes = round_up(sizeof(uint64_t) * count, 64), rows_bytes = round_up(sizeof(BfCorrelateRow) * boxes, 64),
-	             table_bytes = round_up(sizeof(BfCorrelateEntry) * entries, 64), partials_bytes = sizeof(BfCorrelateEntry) * (size_t)partials;
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && ensure_metrics_memory(d, offsets_bytes + rows_bytes + table_bytes, offsets_bytes + rows_bytes + table_bytes + partials_bytes);
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.metrics_scratch.ptr, *pinned = (char *)d.metrics_pinned;
-	uint64_t *offsets = (uint64_t *)pinned;
-	for (uint32_t n = 0; n < count; n++) offsets[n] = frames[n].record->offset;
-	std::memcpy(pinned + offsets_bytes, rows.data(), sizeof(BfCorrelateRow) * boxes);
-	hipStream_t s = d.stream;
-	ok &= HIP_OK(hipMemcpyAsync(device, pinned, offsets_bytes + sizeof(BfCorrelateRow) * boxes, hipMemcpyHostToDevice, s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_begin, s));
-	if (ok) ok &= HIP_OK(bf_launch_correlate(d.ring.ptr, (const uint64_t *)device, (const BfCorrelateRow *)(device + offsets_bytes), &a,
-	                                         (BfCorrelateEntry *)(device + offsets_bytes + rows_bytes + table_bytes),
-	                                         (BfCorrelateEntry *)(device + offsets_bytes + rows_bytes), s));
-	ok &= HIP_OK(hipEventRecord(d.metrics_end, s));
-	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + offsets_bytes + rows_bytes, device + offsets_bytes + rows_bytes, sizeof(BfCorrelateEntry) * entries,
-	                                    hipMemcpyDeviceToHost, s));
-	/* the synchronise runs whatever failed above: it is what frees the pinned memory */
-	ok &= HIP_OK(hipStreamSynchronize(s));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (device_ms) {
-		float ms = 0;
-		*device_ms = HIP_OK(hipEventElapsedTime(&ms, d.metrics_begin, d.metrics_end)) ? ms : 0.0f;
-	}
-	std::memcpy(table, pinned + offsets_bytes + rows_bytes, sizeof(BfCorrelateEntry) * entries);
-	if (info) {
-		std::memset(info, 0, sizeof(*info));
-		info->count = count; info->reference = reference; info->data_kind = (uint32_t)b0.record->data_kind; info->region_count = boxes;
-		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->max_shift[k] = a.max_shift[k]; }
-		info->shifts = a.shifts;
-		info->first_frame_id = b0.record->id; info->reference_frame_id = frames[reference].record->id;
-	}
-	return true;
-}
-
-namespace {
-
-/* What beamformer_hip_mix_last_frames, beamformer_hip_autocorrelate_last_frames, beamformer_hip_convolve_last_frames and
- * beamformer_hip_warp_last_frames share:
- * `out_count` frames computed from the `count` newest ones and queued as frames of their own behind them (and what
- * beamformer_hip_queue_localisation_map takes of it: a run without sources, RunTable::shape).  Everything that can refuse
- * is decided, and every buffer grown, before the ids are taken; nothing synchronises unless device_ms is asked for.
- * The call's table travels with the sources' ring offsets: a weight table of `rows` rows, laid out [tile][k][BF_MIX_TILE][2] (rows past
- * `rows` zero), or `flat_floats` floats as they are (the taps of a convolution), or neither (weights and flat null: the launch reads the
- * sources as they are).
- * prepare(device, newest source's record, cplx, out_count): what the call's launches need besides -- memory of their own --, grown
- * while the call can still refuse; false refuses it (InvalidAccess) with nothing changed.
- * launch(run): the call's kernel launches, one or several, on run.s -- the sources' offsets and the table in device memory (table null
- * without one), output j at ring + out_offset + j * out_stride. */
-struct RunTable {
-	const float *weights = nullptr; uint32_t rows = 0;
-	const float *flat = nullptr;    uint32_t flat_floats = 0;
-	/* not null: a run that has no source frames (count 0: beamformer_hip_queue_localisation_map) -- Float32 frames of this record's grid,
-	 * carrying its block, stand where the newest source's record does */
-	const FrameRecord *shape = nullptr;
-};
-struct QueuedRun {
-	Device *d;
-	void *ring;
-	const uint64_t *offsets;
-	const float *table;
-	uint32_t K;
-	bool cplx;
-	uint32_t points[3];
-	uint64_t elements, out_offset, out_stride;
-	hipStream_t s;
-};
-const auto nothing_to_prepare = [](Device &, const FrameRecord &, bool, uint32_t) { return true; };
-
-template <class Prepare, class Launch>
-bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_count, uint32_t image_plane_tag,
-                            uint32_t *first_frame_id, float *device_ms, Prepare prepare, Launch launch)
-{
-	const float *weights = t.weights;
-	const uint32_t rows = t.rows;
-	Context &c = g_context;
-	std::vector<BoxedFrame> boxed;
-	if (t.shape) {
-		if (!c.device_ready || c.device_count != 1 || count != 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	} else if (!newest_ensemble_frames(count, nullptr, boxed)) return false;
-	Device &d = c.devices[0];
-	const FrameRecord newest = t.shape ? *t.shape : *boxed[count - 1].record;      /* (a copy: the run's records may take its place) */
-	const bool cplx = t.shape ? false : boxed[0].cplx;
-	if (!cplx && weights)
-		for (size_t n = 0; n < (size_t)rows * count; n++)
-			if (weights[2 * n + 1] != 0.0f) return set_error(BeamformerLibErrorKind_InvalidAccess);
-
-	/* where the ring's placement rule will put the run, and whether that reuses storage of a source frame */
-	const uint32_t K = count, M = out_count;
-	const auto shape_of = [&newest, image_plane_tag](uint32_t) { return FrameShape{newest.points, image_plane_tag}; };
-	uint64_t run_bytes = 0;
-	if (!run_bytes_of(shape_of, M, cplx ? 8u : 4u, d.ring.size, run_bytes)) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-	const uint64_t run_first = d.ring_next_offset > d.ring.size - run_bytes ? 0 : d.ring_next_offset;
-	for (const BoxedFrame &b : boxed)
-		if (b.record->offset < run_first + run_bytes && run_first < b.record->offset + b.record->bytes) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
-
-	/* the table: offsets[K] | weights[tile][k][BF_MIX_TILE][2], rows past `rows` zero */
-	const uint32_t padded = weights ? (rows + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE : 0u;
-	const size_t offsets_bytes = round_up(sizeof(uint64_t) * K, 64), weights_bytes = t.flat ? sizeof(float) * t.flat_floats : sizeof(float) * 2 * padded * K;
-	const size_t table_max = round_up(sizeof(uint64_t) * BF_ENSEMBLE_MAX_FRAMES, 64) + sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES;
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && d.mix_table.ensure(table_max);
-	if (ok && !d.mix_pinned && !HIP_OK(hipHostMalloc(&d.mix_pinned, table_max, hipHostMallocDefault))) { d.mix_pinned = nullptr; ok = false; }
-	if (ok && !d.mix_copied) ok = HIP_OK(hipEventCreateWithFlags(&d.mix_copied, hipEventDisableTiming));
-	if (ok && !d.mix_begin)  ok = HIP_OK(hipEventCreate(&d.mix_begin));
-	if (ok && !d.mix_end)    ok = HIP_OK(hipEventCreate(&d.mix_end));
-	ok = ok && weights_bytes <= table_max - offsets_bytes && prepare(d, newest, cplx, M);
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (d.mix_copy_pending) { (void)hipEventSynchronize(d.mix_copied); d.mix_copy_pending = false; }   /* (the previous call's copy: long done) */
-	char *pinned = (char *)d.mix_pinned;
-	uint64_t *offsets = (uint64_t *)pinned;
-	for (uint32_t n = 0; n < K; n++) offsets[n] = boxed[n].record->offset;
-	float *table = (float *)(pinned + offsets_bytes);
-	std::memset(table, 0, weights_bytes);
-	if (t.flat) std::memcpy(table, t.flat, weights_bytes);
-	for (uint32_t j = 0; j < rows && weights; j++)
-		for (uint32_t k = 0; k < K; k++) {
-			float *w = table + (((size_t)(j / BF_MIX_TILE) * K + k) * BF_MIX_TILE + j % BF_MIX_TILE) * 2;
-			w[0] = weights[((size_t)j * K + k) * 2]; w[1] = weights[((size_t)j * K + k) * 2 + 1];
-		}
-
-	/* ---- from here on the call owns ids first .. first + M - 1, taken from the counters a push advances ---- */
-	hipStream_t s = d.stream;
-	const uint64_t first = c.push_sequence;
-	c.push_sequence += M;
+	const uint64_t first = g_context.push_sequence;
+	g_context.push_sequence += M;
 	d.frame_counter = first;
-	Tombstones lockstep{c, first, M, 1, false};
+	Tombstones lockstep{g_context, first, M, 1, false};
 	/* the newest push stays the newest push behind the run -- unless the run takes the timing slot that holds its events */
 	PushRecord &push = d.multi;
 	if (push.kind != PushRecord::None && first == push.first_id + push.count + push.mixed) {
@@ -2993,8 +2351,9 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 		for (uint32_t j = 0; j < M && !slot_taken; j++) slot_taken = (first + j) % kTimingSlots == push.events_slot;
 		if (slot_taken) push.kind = PushRecord::None; else push.mixed += M;
 	}
-	FrameRecord *frame0 = place_frames(shape_of, M, cplx, newest.block, run_bytes);
-	if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);      /* (checked above: not reached) */
+	uint64_t run_bytes = 0;
+	FrameRecord *frame0 = place_frames([points, tag](uint32_t) { return FrameShape{points, tag}; }, M, cplx, block, run_bytes);
+	if (!frame0) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);      /* (queued_run_landing has checked it: not reached) */
 	for (uint32_t j = 0; j < M; j++) {
 		TimingSlot &t = d.timing[(first + j) % kTimingSlots];
 		t.count = 0; t.counted = false; t.sampled = false; t.events_slot = (uint32_t)((first + j) % kTimingSlots); t.share = 1;
@@ -3002,179 +2361,7 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 		t.violations_slot = ~0ull; t.frame_id = first + j; t.failed = false;
 	}
 	d.have_sample = false;              /* the slots of older sampled frames may be gone: a single frame that follows records its own events */
-
-	QueuedRun run{};
-	run.d = &d; run.ring = d.ring.ptr; run.offsets = (const uint64_t *)d.mix_table.ptr;
-	run.table = weights || t.flat ? (const float *)((const char *)d.mix_table.ptr + offsets_bytes) : nullptr;
-	run.K = K; run.cplx = cplx;
-	for (int k = 0; k < 3; k++) run.points[k] = newest.points[k];
-	run.elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
-	run.out_offset = frame0->offset; run.out_stride = frame0->bytes; run.s = s;
-	if (offsets_bytes + weights_bytes) ok &= HIP_OK(hipMemcpyAsync(d.mix_table.ptr, pinned, offsets_bytes + weights_bytes, hipMemcpyHostToDevice, s));
-	d.mix_copy_pending = HIP_OK(hipEventRecord(d.mix_copied, s));
-	ok &= d.mix_copy_pending;
-	if (device_ms) ok &= HIP_OK(hipEventRecord(d.mix_begin, s));
-	if (ok) ok &= HIP_OK(launch(run));
-	if (device_ms) {
-		ok &= HIP_OK(hipEventRecord(d.mix_end, s));
-		ok &= HIP_OK(hipStreamSynchronize(s));
-		float ms = 0;
-		if (ok) *device_ms = HIP_OK(hipEventElapsedTime(&ms, d.mix_begin, d.mix_end)) ? ms : 0.0f;
-	}
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (first_frame_id) *first_frame_id = (uint32_t)first;
-	lockstep.complete = true;
-	return true;
-}
-
-} // namespace
-
-/* beamformer_hip_mix_last_frames: out_count linear combinations of the `count` newest frames, queued as frames of their own
- * (ensemble.hip) */
-bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
-{
-	RunTable t; t.weights = weights; t.rows = out_count;
-	return queue_frames_of_newest(count, t, out_count, image_plane_tag, first_frame_id, device_ms, nothing_to_prepare,
-		[=](const QueuedRun &r) {
-			BfMixArgs a{};
-			a.frames = r.K; a.outputs = out_count; a.cplx = r.cplx; a.padded_outputs = (out_count + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
-			a.elements = r.elements; a.out_offset = r.out_offset; a.out_stride = r.out_stride;
-			return bf_launch_mix(r.ring, r.offsets, r.table, &a, r.s);
-		});
-}
-
-/* beamformer_hip_autocorrelate_last_frames: lags 0 .. lag_count - 1 of the slow-time autocorrelation of `rows` mixes of the `count`
- * newest frames (weights null: of those frames themselves), queued as lag_count frames of their own (autocorr.hip) */
-bool autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows, uint32_t lag_count, uint32_t image_plane_tag,
-                               uint32_t *first_frame_id, float *device_ms)
-{
-	static_assert(BF_AUTOCORR_MAX_LAGS == BEAMFORMER_HIP_MAX_LAGS, "one limit");
-	RunTable t; t.weights = weights; t.rows = rows;
-	return queue_frames_of_newest(count, t, lag_count, image_plane_tag, first_frame_id, device_ms, nothing_to_prepare,
-		[=](const QueuedRun &r) {
-			BfAutocorrArgs a{};
-			a.frames = r.K; a.rows = rows; a.lags = lag_count; a.cplx = r.cplx;
-			a.elements = r.elements; a.out_offset = r.out_offset; a.out_stride = r.out_stride;
-			return bf_launch_autocorr(r.ring, r.offsets, r.table, &a, r.s);
-		});
-}
-
-/* beamformer_hip_convolve_last_frames: the `count` newest frames filtered along x, y, z, queued as `count` frames of their own
- * (spatial.hip).  One launch a live axis.  P passes write, from the last one back, the output run, the scratch run, the output run: the
- * last pass writes the ring, and what lies between two passes is the library's own buffer or the run being made -- never a frame that
- * exists.  Scratch: one run's bytes when there are two passes or more, and in Normalised mode a D field (one float a voxel a frame) per
- * pass but the last, two at the most. */
-bool convolve_last_frames(uint32_t count, const float *const taps[3], const uint32_t tap_counts[3], uint32_t mode, uint32_t image_plane_tag,
-                          uint32_t *first_frame_id, float *device_ms)
-{
-	static_assert(BF_SPATIAL_MAX_TAPS == BEAMFORMER_HIP_MAX_SPATIAL_TAPS, "one limit");
-	float table[3 * BF_SPATIAL_TAP_STRIDE] = {};                  /* an axis's row: zeros, the taps from BF_SPATIAL_TAP_FRONT on, zeros */
-	uint32_t axes[3], passes = 0;
-	for (uint32_t a = 0; a < 3; a++) {
-		if (tap_counts[a] == 0) continue;
-		axes[passes++] = a;
-		std::memcpy(table + a * BF_SPATIAL_TAP_STRIDE + BF_SPATIAL_TAP_FRONT, taps[a], sizeof(float) * tap_counts[a]);
-	}
-	const uint32_t n[3] = {tap_counts[0], tap_counts[1], tap_counts[2]};
-	const bool normalised = mode == BeamformerHipSpatialMode_Normalised;
-	const uint32_t d_fields = normalised ? (passes - 1u < 2u ? passes - 1u : 2u) : 0u;
-	const auto bytes_of = [](const FrameRecord &f, bool cplx, uint32_t frames, uint64_t &run, uint64_t &field) {
-		const uint64_t voxels = (uint64_t)f.points[0] * f.points[1] * f.points[2];
-		run = round_up(voxels * (cplx ? 8u : 4u), 64) * frames;
-		field = round_up(voxels * 4u, 64) * frames;
-	};
-	RunTable t; t.flat = table; t.flat_floats = 3 * BF_SPATIAL_TAP_STRIDE;
-	return queue_frames_of_newest(count, t, count, image_plane_tag, first_frame_id, device_ms,
-		[=](Device &d, const FrameRecord &newest, bool cplx, uint32_t frames) {
-			uint64_t run, field;
-			bytes_of(newest, cplx, frames, run, field);
-			if ((uint64_t)newest.points[0] * newest.points[1] * newest.points[2] > 0x7FFFFFFFull) return false;   /* the launches count a slice's voxels in 32 bits */
-			const uint64_t need = (passes > 1u ? run : 0u) + d_fields * field;
-			return need == 0 || d.spatial_scratch.ensure(need);
-		},
-		[=](const QueuedRun &r) {
-			FrameRecord shape; uint64_t run, field;
-			for (int k = 0; k < 3; k++) shape.points[k] = r.points[k];
-			bytes_of(shape, r.cplx, r.K, run, field);
-			char *scratch = (char *)r.d->spatial_scratch.ptr, *ring_out = (char *)r.ring + r.out_offset;
-			float *d_field[2] = {(float *)(scratch + (passes > 1u ? run : 0u)), (float *)(scratch + (passes > 1u ? run : 0u) + field)};
-			const uint32_t inner[3] = {1u, r.points[0], r.points[0] * r.points[1]}, outer[3] = {r.points[1] * r.points[2], r.points[2], 1u};
-			const void *in = r.ring;
-			for (uint32_t p = 0; p < passes; p++) {
-				const uint32_t axis = axes[p];
-				const bool to_ring = (passes - 1u - p) % 2u == 0;
-				BfSpatialArgs a{};
-				a.frames = r.K; a.cplx = r.cplx; a.stage = normalised ? (p == 0 ? 1u : 2u) : 0u; a.last = p + 1u == passes;
-				a.inner = inner[axis]; a.extent = r.points[axis]; a.outer = outer[axis]; a.taps = n[axis];
-				a.in_stride = r.out_stride; a.out_stride = r.out_stride; a.d_stride = field / r.K / sizeof(float);
-				void *out = to_ring ? ring_out : scratch;
-				const hipError_t e = bf_launch_spatial(in, p == 0 ? r.offsets : nullptr, out, p ? d_field[(p - 1u) % 2u] : nullptr,
-				                                       normalised && !a.last ? d_field[p % 2u] : nullptr,
-				                                       r.table + axis * BF_SPATIAL_TAP_STRIDE + BF_SPATIAL_TAP_FRONT, &a, r.s);
-				if (e != hipSuccess) return e;
-				in = out;
-			}
-			return hipSuccess;
-		});
-}
-
-/* beamformer_hip_warp_last_frames: the `count` newest frames resampled at v + d(v), queued as `count` frames of their own (warp.hip).
- * One launch; the rotations and the field travel as the call's flat table (bf_warp_table_floats: within the table of a mix by the
- * limits lib_api.cpp has checked), the lattice's constants as kernel arguments.  No memory of its own. */
-bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3], const float node_first[3], const float node_step[3],
-                      const float *rotations, uint32_t interpolation, uint32_t edge, uint32_t image_plane_tag,
-                      uint32_t *first_frame_id, float *device_ms)
-{
-	static_assert(BF_WARP_MAX_NODES == BEAMFORMER_HIP_MAX_WARP_NODES && BF_WARP_MAX_ENTRIES == BEAMFORMER_HIP_MAX_WARP_ENTRIES, "one limit");
-	static_assert(sizeof(float) * (2u * BF_ENSEMBLE_MAX_FRAMES + 3u * BF_WARP_MAX_ENTRIES) <= sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES,
-	              "the table of a warp fits the table of a mix");
-	const uint32_t node_product = nodes[0] * nodes[1] * nodes[2];
-	std::vector<float> table(bf_warp_table_floats(count, node_product));
-	for (uint32_t n = 0; n < count; n++) {
-		table[2u * n] = rotations ? rotations[2u * n] : 1.0f;
-		table[2u * n + 1u] = rotations ? rotations[2u * n + 1u] : 0.0f;
-	}
-	std::memcpy(table.data() + 2u * count, field, sizeof(float) * 3u * count * node_product);
-	BfWarpArgs a{};
-	a.cubic = interpolation == BeamformerHipWarpInterpolation_Cubic; a.clamp = edge == BeamformerHipWarpEdge_Clamp;
-	a.rotate = rotations != nullptr;
-	a.direct = (g_context.das_path_mode & BeamformerHipDasPath_WarpDirect) != 0;
-	for (int k = 0; k < 3; k++) {
-		a.nodes[k] = nodes[k];
-		if (nodes[k] > 1u) { a.node_first[k] = node_first[k]; a.inv_step[k] = 1.0f / node_step[k]; }
-	}
-	RunTable t; t.flat = table.data(); t.flat_floats = (uint32_t)table.size();
-	return queue_frames_of_newest(count, t, count, image_plane_tag, first_frame_id, device_ms,
-		[=](Device &, const FrameRecord &newest, bool cplx, uint32_t) {
-			if ((uint64_t)newest.points[0] * newest.points[1] * newest.points[2] > 0x7FFFFFFFull) return false;   /* the kernel indexes a frame's voxels in 32 bits */
-			for (uint32_t n = 0; n < count && rotations && !cplx; n++)
-				if (rotations[2u * n + 1u] != 0.0f) return false;
-			return true;
-		},
-		[=](const QueuedRun &r) {
-			BfWarpArgs args = a;
-			args.frames = r.K; args.cplx = r.cplx;
-			for (int k = 0; k < 3; k++) args.points[k] = r.points[k];
-			args.out_offset = r.out_offset; args.out_stride = r.out_stride;
-			return bf_launch_warp(r.ring, r.offsets, r.table, &args, r.s);
-		});
-}
-
-/* beamformer_hip_queue_localisation_map: the map's counts times `scale`, queued as ONE Float32 frame of the map's grid (frame_peaks.hip:
- * the conversion) -- a run of one frame that has no source in the ring: the map is the library's own buffer, so no placement can lie on
- * what the launch reads.  The record carries the block of the newest frame of the last accumulate call. */
-bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
-{
-	Context &c = g_context;
-	Device &d = c.devices[0];
-	if (!c.device_ready || c.device_count != 1 || !d.map.ptr || !d.map_points[0] || d.map_calls == 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	FrameRecord shape;
-	for (int k = 0; k < 3; k++) shape.points[k] = d.map_points[k];
-	shape.block = d.map_block;
-	RunTable t; t.shape = &shape;
-	const uint32_t *map = (const uint32_t *)d.map.ptr;
-	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
-		[=](const QueuedRun &r) { return bf_launch_localisation_convert(map, (float *)((char *)r.ring + r.out_offset), r.elements, scale, r.s); });
+	return lockstep.complete = enqueue(first, *frame0);
 }
 
 /* The record of the frame with this id, while the frame is still there: its record not yet overwritten (the newest frames.size() ids),

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64) void frame_metrics_final_kernel(const BfMetrics
 }
 
 /* rows, partials, results: device memory; rows[k].partial_first + rows[k].blocks partials, frame_count results.  Every row's box lies
- * inside its frame and its frame inside the ring: the caller's business (executor.cpp: score_last_frames), nothing here re-checks it. */
+ * inside its frame and its frame inside the ring: the caller's business (frame_ops.cpp: score_last_frames), nothing here re-checks it. */
 extern "C" hipError_t bf_launch_frame_metrics(const void *ring, const BfMetricsRow *rows, uint32_t frame_count, uint32_t max_blocks,
                                               BfMetricsPartial *partials, BfMetricsResult *results, hipStream_t s)
 {

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void frame_peaks_emit_kernel(const char *__res
 
 /* ring, rows, masks, counts, offsets, results: device memory; rows[k].wave_first + rows[k].waves masks, rows[k].block_first +
  * rows[k].blocks counts and offsets, frame_count results.  Every row's box lies inside its frame and its frame inside the ring: the
- * caller's business (executor.cpp: find_peaks_last_frames), nothing here re-checks it. */
+ * caller's business (frame_ops.cpp: find_peaks_last_frames), nothing here re-checks it. */
 extern "C" hipError_t bf_launch_frame_peaks_mark(const void *ring, const BfPeaksRow *rows, uint32_t frame_count, uint32_t max_blocks,
                                                  uint64_t *masks, uint32_t *counts, uint32_t *offsets, BfPeaksResult *results, hipStream_t s)
 {

@@ -235,7 +235,7 @@ hipError_t launch(const void *in, const uint64_t *offsets, void *out, const floa
 
 /* One pass.  Every table and field is device memory; the input frames (offsets: inside `in`; else frame k at in + k * in_stride), the
  * output run and the D fields hold frames * inner * extent * outer voxels each and do not overlap: the caller's business
- * (executor.cpp: convolve_last_frames), nothing here re-checks it.  The launch geometry in `args` is filled in here. */
+ * (frame_ops.cpp: convolve_last_frames), nothing here re-checks it.  The launch geometry in `args` is filled in here. */
 extern "C" hipError_t bf_launch_spatial(const void *in, const uint64_t *offsets, void *out, const float *d_in, float *d_out, const float *taps,
                                         const BfSpatialArgs *args, hipStream_t s)
 {

@@ -258,7 +258,7 @@ hipError_t launch(void *ring, const uint64_t *offsets, const float *table, const
 
 } // namespace
 
-/* One launch.  The sources, the output run and the table are device memory and do not overlap: the caller's business (executor.cpp:
+/* One launch.  The sources, the output run and the table are device memory and do not overlap: the caller's business (frame_ops.cpp:
  * warp_last_frames), nothing here re-checks it.  The launch geometry in `args` is filled in here. */
 extern "C" hipError_t bf_launch_warp(void *ring, const uint64_t *offsets, const float *table, const BfWarpArgs *args, hipStream_t s)
 {

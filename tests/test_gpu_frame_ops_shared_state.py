@@ -1,0 +1,176 @@
+"""The calls on frames already in the ring, one after the other in one process: what they share on the device -- the scratch and the
+pinned block that score, find_peaks, gram, correlate and accumulate_peaks carve their tables from, the table of the queued runs, the
+localisation map -- has to grow from one call to the next and come back after a shutdown, which no test of one operation notices.
+
+Every result is judged by the test of its own operation: its reference, its comparator and its bars are imported from there, and
+nothing here restates them."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from ogl_beamforming_amd import lib as bf
+from ogl_beamforming_amd import params as P
+from tests import localisation_ref
+from tests import test_gpu_ensemble as ensemble_tests
+from tests import test_gpu_frame_metrics as metrics_tests
+from tests import test_gpu_frame_peaks as peaks_tests
+from tests import test_gpu_localisation as map_tests
+from tests import test_gpu_motion as motion_tests
+from tests import variants_cases as vc
+from tests.test_gpu_frame_metrics import newest_info, region_of
+
+pytestmark = pytest.mark.gpu
+E = P.LibError
+K = 4
+# two complex planes through the ensemble tests' own block and burst (their GRIDS, by names of this file's): the tables of the second
+# are larger than everything the first left allocated
+ensemble_tests.GRIDS.update(frame_ops_small=((16, 1, 8), vc.LO, vc.HI, True), frame_ops_large=((64, 1, 32), vc.LO, vc.HI, True))
+MAP_POINTS = (8, 1, 8)
+REGIONS = [((1, 0, 1), (13, 1, 5)), ((3, 0, 3), (13, 1, 5))]        # two boxes for correlate, the second against the small frame's far corner
+SCORE_BOX = ((5, 0, 3), (3, 1, 2))
+
+
+@pytest.fixture(autouse=True)
+def automatic_path(bflib):
+    L = bflib.library()
+    L.beamformer_set_global_timeout(0xFFFFFFFF)
+    L.beamformer_hip_set_das_path(0)
+    yield
+    L.beamformer_hip_set_das_path(0)
+    bflib.localisation_map_reset(None)
+
+
+def map_of(which):
+    """the 8 x 1 x 8 map over the frames' own box, and the placement of the frames of `which` onto it"""
+    acq = ensemble_tests.block(which)
+    grid = map_tests.map_view(MAP_POINTS, vc.LO, vc.HI)
+    return grid, map_tests.placement_onto(grid, acq.bp.das_voxel_transform, ensemble_tests.GRIDS[which][0])
+
+
+def the_order(which):
+    """the seven calls on the K newest frames, each judged as its own test judges it; returns what a later run can be compared with"""
+    frames, ids = ensemble_tests.ensemble(which, K)
+    assert frames.shape[1:] == ensemble_tests.GRIDS[which][0][::-1] and np.iscomplexobj(frames)
+    thresholds = peaks_tests.fraction_of_max(frames, 0.25)
+    grid, A = map_of(which)
+    # 1. score, whole frames
+    scored, _ = bf.score_last_frames(K)
+    for k in range(K):
+        metrics_tests.check_row(scored[k], frames[k], what=f"{which} {k}")
+    # 2. find_peaks
+    peak_rows, peaks, found = peaks_tests.check_call(list(frames), thresholds, what=which)
+    assert all(r["found"] >= 2 for r in found)
+    # 3. gram
+    G, _ = ensemble_tests.check_gram(frames, ids, what=which)
+    # 4. correlate, two regions, window (1, 0, 1)
+    table, _, _ = motion_tests.check_call(frames, ids, K // 2, (1, 0, 1), REGIONS, what=which)
+    # 5. accumulate_peaks into the map
+    counts, deposits, info = map_tests.run(grid, frames, thresholds, A)
+    expected, numbers = localisation_ref.accumulate(grid.output_points, frames, thresholds, A)
+    map_tests.same(counts, expected)
+    assert (info.calls, int(info.deposited)) == (1, sum(n["found"] for n in numbers)) and int(counts.sum()) == int(info.deposited) >= K
+    # 6. score again, a 3 x 1 x 2 region
+    boxed, _ = bf.score_last_frames(K, region_of(SCORE_BOX))
+    for k in range(K):
+        metrics_tests.check_row(boxed[k], frames[k], SCORE_BOX, what=f"{which} {k} box")
+        assert (boxed[k].frame_id, boxed[k].parameter_block, boxed[k].data_kind, tuple(boxed[k].points)) == \
+               (scored[k].frame_id, scored[k].parameter_block, scored[k].data_kind, tuple(scored[k].points))
+    # 7. find_peaks again: the bytes of 2.
+    again_rows, again_peaks, _ = peaks_tests.check_call(list(frames), thresholds, what=which + " again")
+    assert bytes(again_rows) == bytes(peak_rows) and bytes(again_peaks) == bytes(peaks)
+    # (the deposit rows last: their check asks find_peaks once more)
+    map_tests.check_rows(deposits, numbers, frames, thresholds)
+    return dict(frames=frames, scored=scored, peak_rows=peak_rows, peaks=peaks, gram=G, table=table, counts=counts)
+
+
+def numbers_of(row):
+    """a HipFrameMetrics row without the frame's id: what depends on the frame's voxels and the box alone"""
+    raw = bytearray(bytes(row))
+    offset = P.HipFrameMetrics.frame_id.offset
+    raw[offset:offset + 4] = b"\0\0\0\0"
+    return bytes(raw)
+
+
+def test_the_scratch_grows_from_small_frames_to_large_ones_and_every_call_finds_its_tables(bflib):
+    small = the_order("frame_ops_small")
+    large = the_order("frame_ops_large")
+    assert large["frames"].nbytes == 16 * small["frames"].nbytes
+    # ... and back: the small frames again, in memory the large ones left behind -- every byte as the first time
+    again = the_order("frame_ops_small")
+    assert np.array_equal(again["frames"].view(np.uint32), small["frames"].view(np.uint32))
+    assert [numbers_of(r) for r in again["scored"]] == [numbers_of(r) for r in small["scored"]]
+    assert bytes(again["peaks"]) == bytes(small["peaks"]) and again["gram"].tobytes() == small["gram"].tobytes()
+    assert again["table"].tobytes() == small["table"].tobytes() and again["counts"].tobytes() == small["counts"].tobytes()
+
+
+def mix_and_score(which, frames, ids):
+    """two mixes of the K newest frames queued behind them (the ensemble tests' check), then their metrics rows"""
+    out, first = ensemble_tests.check_mix(which, frames, ids, ensemble_tests.weights(2, K, 7901), tag=3, what=which)
+    rows, _ = bf.score_last_frames(2)
+    for j in range(2):
+        metrics_tests.check_row(rows[j], out[j], what=f"{which} mix {j}")
+        assert (int(rows[j].frame_id), int(rows[j].image_plane_tag)) == (first + j, 3)
+    return out, first, rows
+
+
+def test_queued_runs_behind_reduce_calls(bflib):
+    which = "frame_ops_small"
+    acq = ensemble_tests.block(which)
+    frames, ids = ensemble_tests.ensemble(which, K)
+    before = bytes(bf.last_burst_info())
+    grid, A = map_of(which)
+    counts, _, _ = map_tests.run(grid, frames, peaks_tests.fraction_of_max(frames, 0.25), A)
+    assert len(np.unique(counts)) >= 2
+    out, first, _ = mix_and_score(which, frames, ids)
+    scale = 0.37
+    frame_id, ms = bf.queue_localisation_map(scale, tag=5)
+    assert ms > 0
+    # get_last_frames serves the map frame: a block of the map's grid says its shape
+    bp = type(acq.bp).from_buffer_copy(acq.bp)
+    bp.output_points[:3] = list(MAP_POINTS)
+    queued = bf.get_last_frames(bp, 1)[0]
+    expected = localisation_ref.queued_frame(counts, scale)
+    assert queued.dtype == np.float32 and np.array_equal(queued.view(np.uint32), expected.view(np.uint32))
+    # consecutive ids: the burst's, the two mixes, the map
+    assert [first, first + 1, frame_id] == [ids[-1] + 1, ids[-1] + 2, ids[-1] + 3] and int(newest_info(bf.library()).frame_id) == frame_id
+    info = bf.frame_info(frame_id)
+    assert tuple(info.points) == MAP_POINTS and info.data_kind == int(P.DataKind.Float32)
+    # the mixes are still served by their ids, and the burst is still the newest multi-frame push, its info as it was
+    assert np.array_equal(bf.copy_frame(first + 1).view(np.uint32), out[1].view(np.uint32))
+    assert bytes(bf.last_burst_info()) == before
+    map_tests.same(bf.localisation_map_copy()[0], counts)
+
+
+def test_a_shutdown_releases_everything_and_the_calls_start_again(bflib):
+    L = bflib.library()
+    which = "frame_ops_small"
+    frames, ids = ensemble_tests.ensemble(which, K)
+    grid, A = map_of(which)
+    map_tests.run(grid, frames, peaks_tests.fraction_of_max(frames, 0.25), A)
+    scored, _ = bf.score_last_frames(K)
+    out, _, mixed_rows = mix_and_score(which, frames, ids)
+
+    L.beamformer_hip_shutdown()
+    counts, info = np.full(int(np.prod(MAP_POINTS)), 0xA5A5A5A5, np.uint32), P.HipMapInfo()
+
+    def no_map():
+        assert not L.beamformer_hip_localisation_map_copy(counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size, C.byref(info))
+        assert bf.last_error()[0] == E.InvalidAccess and (counts == 0xA5A5A5A5).all() and not bytes(info).strip(b"\0")
+
+    no_map()
+    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
+    frames2, ids2 = ensemble_tests.ensemble(which, K)
+    assert ids2 == list(range(K)) and np.array_equal(frames2.view(np.uint32), frames.view(np.uint32))
+    no_map()                                            # a device again, but the map went with the old one
+    scored2, _ = bf.score_last_frames(K)
+    for k in range(K):
+        metrics_tests.check_row(scored2[k], frames2[k], what=f"after the shutdown {k}")
+    assert [numbers_of(r) for r in scored2] == [numbers_of(r) for r in scored]
+    out2, first2, mixed_rows2 = mix_and_score(which, frames2, ids2)
+    assert first2 == K and out2.tobytes() == out.tobytes() and [numbers_of(r) for r in mixed_rows2] == [numbers_of(r) for r in mixed_rows]
+    no_map()
+    # until a reset: an empty map, nothing counted
+    bf.localisation_map_reset(MAP_POINTS)
+    empty, info = bf.localisation_map_copy(MAP_POINTS)
+    assert not empty.any() and (info.calls, int(info.deposited), int(info.outside)) == (0, 0, 0)

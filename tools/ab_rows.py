@@ -51,9 +51,19 @@ def real_row(env):
 FIGURE_KEYS = ("_us", "_us_per_frame", "_us_per_push", "_ms")
 
 
+def medians(value, path, out):
+    """the timings a row keeps as {median_us, min_us, max_us} summaries, however deep: one figure each, its median, named by its path"""
+    if isinstance(value, dict):
+        if isinstance(value.get("median_us"), (int, float)):
+            out[path + ".median_us"] = float(value["median_us"])
+        for k, v in value.items():
+            medians(v, f"{path}.{k}" if path else k, out)
+
+
 def tool_rows(command):
     """every row a rate tool prints (tools/*_rate.py: one JSON object a row), as one figure per timing of the row -- its keys that end
-    in _us, _us_per_frame, _us_per_push or _ms, spreads left out --, named by the row's first four plain fields (the case and its counts)"""
+    in _us, _us_per_frame, _us_per_push or _ms, spreads left out, and the medians of its timing summaries --, named by the row's first
+    four plain fields (the case and its counts)"""
     def run(env):
         out = subprocess.run([sys.executable] + command, env=env, capture_output=True, text=True, check=True, timeout=900).stdout
         figures = {}
@@ -62,6 +72,7 @@ def tool_rows(command):
                 continue
             row = json.loads(line)
             timings = {k: float(v) for k, v in row.items() if k.endswith(FIGURE_KEYS) and "spread" not in k and isinstance(v, (int, float))}
+            medians(row, "", timings)
             plain = [f"{k}={v}" for k, v in row.items() if k not in timings and isinstance(v, (str, int)) and not isinstance(v, bool)][:4]
             for k, v in timings.items():
                 figures[" ".join(plain + [k])] = v
@@ -95,6 +106,17 @@ ROWS = {
     "readi_image_rate": ("tools/readi_image_rate.py --groups 4,16", tool_rows(["tools/readi_image_rate.py", "--groups", "4,16"])),
     "burst_views_rate": ("tools/burst_views_rate.py --frames 2,256", tool_rows(["tools/burst_views_rate.py", "--frames", "2,256"])),
     "variants_rate": ("tools/variants_rate.py --counts 1,64", tool_rows(["tools/variants_rate.py", "--counts", "1,64"])),
+    # time per call of the operations on frames already in the ring (csrc/frame_ops.cpp): each rate tool at its smallest and its default counts
+    "frame_metrics_rate": ("tools/frame_metrics_rate.py --counts 1,64 --host-repeats 1", tool_rows(["tools/frame_metrics_rate.py", "--counts", "1,64", "--host-repeats", "1"])),
+    "frame_peaks_rate": ("tools/frame_peaks_rate.py --counts 1,64 --fractions 0.5,0 --host-repeats 1",
+                         tool_rows(["tools/frame_peaks_rate.py", "--counts", "1,64", "--fractions", "0.5,0", "--host-repeats", "1"])),
+    "ensemble_filter_rate": ("tools/ensemble_filter_rate.py --plane-counts 8,64 --volume-counts 8,64",
+                             tool_rows(["tools/ensemble_filter_rate.py", "--plane-counts", "8,64", "--volume-counts", "8,64"])),
+    "autocorr_rate": ("tools/autocorr_rate.py", tool_rows(["tools/autocorr_rate.py"])),
+    "spatial_rate": ("tools/spatial_rate.py", tool_rows(["tools/spatial_rate.py"])),
+    "motion_rate": ("tools/motion_rate.py", tool_rows(["tools/motion_rate.py"])),
+    "warp_rate": ("tools/warp_rate.py", tool_rows(["tools/warp_rate.py"])),
+    "localisation_rate": ("tools/localisation_rate.py", tool_rows(["tools/localisation_rate.py"])),
 }
 
 
