@@ -321,6 +321,18 @@ static inline uint32_t bf_plane_walk_blocks(uint32_t blocks_x, uint32_t blocks_y
 	uint32_t slots = 2u * ((bands + 15u) / 16u);              /* bands per XCD */
 	return 8u * slots * band_rows * blocks_x;
 }
+/* Blocks to launch for a tile walk that deals the block ids to the 8 XCDs (general_tile, das_general.h): the bands of a view plane, or
+ * the tile count rounded up to a multiple of 8 -- the ids of the ragged tail have no tile. */
+static inline uint32_t bf_walk_grid_blocks(uint32_t depth_major, const uint32_t blocks[3], uint32_t band_rows)
+{
+	const uint32_t total = blocks[0] * blocks[1] * blocks[2];
+	return depth_major == 3u ? bf_plane_walk_blocks(blocks[0], blocks[1], band_rows) : ((total + 7u) / 8u) * 8u;
+}
+static inline uint32_t bf_general_grid_blocks(const BfDasArgs *a) { return bf_walk_grid_blocks(a->depth_major, a->blocks, a->band_rows); }
+/* A channel split (BfDasArgs::split_shift, das.hip and das_factored.hip): K = 1 << split_shift waves share 64 voxels and combine
+ * through [K-1][3][64] floats of LDS; without one a block is 256 threads and has no LDS. */
+static inline uint32_t bf_split_threads(const BfDasArgs *a) { return a->split_shift ? 64u << a->split_shift : 256u; }
+static inline uint32_t bf_split_lds_bytes(const BfDasArgs *a) { return a->split_shift ? ((1u << a->split_shift) - 1u) * 192u * (uint32_t)sizeof(float) : 0u; }
 #ifdef __HIPCC__
 template <bool DEEPEST_FIRST = false>
 static __device__ __forceinline__ bool bf_plane_walk(uint32_t block_id, uint32_t blocks_x, uint32_t blocks_y, uint32_t band_rows,

@@ -145,6 +145,7 @@ __global__ __launch_bounds__(BF_DAS_MAX_THREADS) void das_kernel(const BfDasArgs
 	if (!tile.valid) return;
 	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
 
+	/* (tile_voxel's text, das_general.h, restated: tried behind general_tile with this compiler, the call gave every kernel here other registers) */
 	uint32_t tid = threadIdx.x;
 	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
 	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
@@ -159,12 +160,8 @@ __global__ __launch_bounds__(BF_DAS_MAX_THREADS) void das_kernel(const BfDasArgs
 	acc.init();
 	if (inside) {
 		uint32_t z = p.z_first + zl;
-		/* das.glsl:374-376 */
-		float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
-		float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-		float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
 		float wx, wy, wz;
-		m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+		voxel_point(p, x, y, z, wx, wy, wz);
 		const char *rf = (const char *)p.rf;
 		const int C   = p.channel_count;
 		const int per = (C + (1 << p.split_shift) - 1) >> p.split_shift;
@@ -205,57 +202,33 @@ __global__ __launch_bounds__(BF_DAS_MAX_THREADS) void das_kernel(const BfDasArgs
 		if ((tid & 63u) == 0 && n) atomicAdd(p.pair_counter, n);
 	} else if (inside) {
 		uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-		sample_t<CPLX> v = acc.coherent;
-		/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949):
-		 * c *= c / incoherent, component-wise; incoherent == 0 gives NaN as in the reference */
-		if constexpr (CW) v = v * (v / acc.incoherent);
-		reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = v;
+		reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = coherency_weighted<CW>(acc.coherent, acc.incoherent);
 	}
 }
 
 template <int FAMILY, int INTERP, bool CPLX, bool CW, bool COUNT>
 static hipError_t launch_one(const BfDasArgs *a, hipStream_t s)
 {
-	uint32_t total = a->blocks[0] * a->blocks[1] * a->blocks[2];
-	uint32_t grid  = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
-	uint32_t threads = a->split_shift ? 64u << a->split_shift : 256u;
-	uint32_t lds     = a->split_shift ? ((1u << a->split_shift) - 1u) * 192u * (uint32_t)sizeof(float) : 0u;
-	hipLaunchKernelGGL((das_kernel<FAMILY, INTERP, CPLX, CW, COUNT>), dim3(grid), dim3(threads), lds, s, *a);
+	hipLaunchKernelGGL((das_kernel<FAMILY, INTERP, CPLX, CW, COUNT>), dim3(bf_general_grid_blocks(a)), dim3(bf_split_threads(a)), bf_split_lds_bytes(a), s, *a);
 	return hipGetLastError();
 }
 
-template <int FAMILY, int INTERP, bool COUNT>
+/* COUNT: the pair counters exist for nearest interpolation of real samples without coherency weighting only */
+template <int FAMILY, bool COUNT>
 static hipError_t launch_kind(const BfDasArgs *a, hipStream_t s)
 {
-	if constexpr (COUNT) return launch_one<FAMILY, INTERP, false, false, true>(a, s);
-	else {
-		if (a->complex_data) return a->coherency_weighting ? launch_one<FAMILY, INTERP, true,  true,  false>(a, s)
-		                                                   : launch_one<FAMILY, INTERP, true,  false, false>(a, s);
-		else                 return a->coherency_weighting ? launch_one<FAMILY, INTERP, false, true,  false>(a, s)
-		                                                   : launch_one<FAMILY, INTERP, false, false, false>(a, s);
-	}
-}
-
-template <int FAMILY, bool COUNT>
-static hipError_t launch_interp(const BfDasArgs *a, hipStream_t s)
-{
-	if constexpr (COUNT) return launch_kind<FAMILY, BF_INTERP_NEAREST, true>(a, s);
-	else switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_kind<FAMILY, BF_INTERP_NEAREST, false>(a, s);
-	case BF_INTERP_LINEAR:  return launch_kind<FAMILY, BF_INTERP_LINEAR,  false>(a, s);
-	case BF_INTERP_CUBIC:   return launch_kind<FAMILY, BF_INTERP_CUBIC,   false>(a, s);
-	}
-	return hipErrorInvalidValue;
+	if constexpr (COUNT) return launch_one<FAMILY, BF_INTERP_NEAREST, false, false, true>(a, s);
+	else return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) { return launch_one<FAMILY, interp, cplx, cw, false>(a, s); });
 }
 
 template <bool COUNT>
 static hipError_t launch_family(const BfDasArgs *a, hipStream_t s)
 {
 	switch (a->family) {
-	case BF_DAS_RCA:      return launch_interp<BF_DAS_RCA,      COUNT>(a, s);
-	case BF_DAS_HERCULES: return launch_interp<BF_DAS_HERCULES, COUNT>(a, s);
-	case BF_DAS_FORCES:   return launch_interp<BF_DAS_FORCES,   COUNT>(a, s);
-	case BF_DAS_READI:    return launch_interp<BF_DAS_READI,    COUNT>(a, s);
+	case BF_DAS_RCA:      return launch_kind<BF_DAS_RCA,      COUNT>(a, s);
+	case BF_DAS_HERCULES: return launch_kind<BF_DAS_HERCULES, COUNT>(a, s);
+	case BF_DAS_FORCES:   return launch_kind<BF_DAS_FORCES,   COUNT>(a, s);
+	case BF_DAS_READI:    return launch_kind<BF_DAS_READI,    COUNT>(a, s);
 	}
 	return hipErrorInvalidValue;
 }

@@ -38,6 +38,8 @@ __global__ __launch_bounds__(256) void das_burst_kernel(const BfDasArgs p, const
 	if (!tile.valid) return;
 	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
 
+	/* (tile_voxel's text, das_general.h, restated: tried behind general_tile with this compiler, the call turned a branch of the range
+	 * test below into a select and gave every kernel here other registers) */
 	uint32_t tid = threadIdx.x;
 	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
 	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
@@ -48,8 +50,8 @@ __global__ __launch_bounds__(256) void das_burst_kernel(const BfDasArgs p, const
 	if (!(x < p.size[0] && y < p.size[1] && zl < p.z_count)) return;
 
 	/* this block's frames: first .. first + count - 1; the spare slots of a short last group alias its last frame */
-	const uint32_t first = blockIdx.y * (uint32_t)FB;
-	const uint32_t count = q.frame_count - first < (uint32_t)FB ? q.frame_count - first : (uint32_t)FB;
+	uint32_t first, count;
+	burst_frames(q.frame_count, first, count);
 	const char *rf[FB];
 	for (int f = 0; f < FB; f++) {
 		const uint32_t frame = first + ((uint32_t)f < count ? (uint32_t)f : count - 1u);
@@ -59,12 +61,8 @@ __global__ __launch_bounds__(256) void das_burst_kernel(const BfDasArgs p, const
 	for (int f = 0; f < FB; f++) acc[f].init();
 
 	uint32_t z = p.z_first + zl;
-	/* das.glsl:374-376 */
-	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
-	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
 	float wx, wy, wz;
-	m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+	voxel_point(p, x, y, z, wx, wy, wz);
 
 	/* das.glsl:204-231 */
 	float xx, xy, xz;
@@ -97,10 +95,7 @@ __global__ __launch_bounds__(256) void das_burst_kernel(const BfDasArgs p, const
 	const uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
 	for (int f = 0; f < FB; f++) {
 		if ((uint32_t)f < count) {
-			sample_t<CPLX> v = acc[f].coherent;
-			/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949), as das.hip's epilogue */
-			if constexpr (CW) v = v * (v / acc[f].incoherent);
-			reinterpret_cast<sample_t<CPLX> *>((char *)p.out + (uint64_t)(first + (uint32_t)f) * q.out_stride)[out_index] = v;
+			reinterpret_cast<sample_t<CPLX> *>((char *)p.out + (uint64_t)(first + (uint32_t)f) * q.out_stride)[out_index] = coherency_weighted<CW>(acc[f].coherent, acc[f].incoherent);
 		}
 	}
 }
@@ -119,6 +114,7 @@ __global__ __launch_bounds__(256) void das_readi_burst_kernel(const BfDasArgs p,
 	if (!tile.valid) return;
 	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
 
+	/* (tile_voxel's text restated, as in das_burst_kernel) */
 	uint32_t tid = threadIdx.x;
 	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
 	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
@@ -129,8 +125,8 @@ __global__ __launch_bounds__(256) void das_readi_burst_kernel(const BfDasArgs p,
 	if (!(x < p.size[0] && y < p.size[1] && zl < p.z_count)) return;
 
 	/* this block's frames, as in das_burst_kernel; row[f]: where frame f's signs begin in the Hadamard matrix */
-	const uint32_t first = blockIdx.y * (uint32_t)FB;
-	const uint32_t count = q.frame_count - first < (uint32_t)FB ? q.frame_count - first : (uint32_t)FB;
+	uint32_t first, count;
+	burst_frames(q.frame_count, first, count);
 	const uint32_t G = p.readi_group_count;
 	const char *rf[FB];
 	uint32_t row[FB];
@@ -145,11 +141,8 @@ __global__ __launch_bounds__(256) void das_readi_burst_kernel(const BfDasArgs p,
 
 	uint32_t z = p.z_first + zl;
 	/* das.glsl:374-376; the host pre-multiplied the voxel transform: (xx, xy, xz) is in transducer space (das.hip das_forces) */
-	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
-	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
 	float xx, xy, xz;
-	m4_point(p.voxel_transform, px, py, pz, xx, xy, xz);
+	voxel_point(p, x, y, z, xx, xy, xz);
 
 	/* das.glsl:323-366 */
 	const int S = p.sample_count, A = p.acquisition_count, C = p.channel_count;
@@ -190,29 +183,9 @@ __global__ __launch_bounds__(256) void das_readi_burst_kernel(const BfDasArgs p,
 	const uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
 	for (int f = 0; f < FB; f++) {
 		if ((uint32_t)f < count) {
-			sample_t<CPLX> v = acc[f].coherent;
-			/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949), as das.hip's epilogue */
-			if constexpr (CW) v = v * (v / acc[f].incoherent);
-			reinterpret_cast<sample_t<CPLX> *>((char *)p.out + (uint64_t)(first + (uint32_t)f) * q.out_stride)[out_index] = v;
+			reinterpret_cast<sample_t<CPLX> *>((char *)p.out + (uint64_t)(first + (uint32_t)f) * q.out_stride)[out_index] = coherency_weighted<CW>(acc[f].coherent, acc[f].incoherent);
 		}
 	}
-}
-
-template <int INTERP, bool CPLX, bool CW>
-static hipError_t launch_one(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s)
-{
-	uint32_t total = a->blocks[0] * a->blocks[1] * a->blocks[2];
-	uint32_t grid  = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
-	uint32_t groups = (b->frame_count + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
-	hipLaunchKernelGGL((das_burst_kernel<INTERP, CPLX, CW>), dim3(grid, groups), dim3(256), 0, s, *a, *b);
-	return hipGetLastError();
-}
-
-template <int INTERP>
-static hipError_t launch_kind(const BfDasArgs *a, const BfBurstArgs *b, hipStream_t s)
-{
-	if (a->complex_data) return a->coherency_weighting ? launch_one<INTERP, true,  true>(a, b, s) : launch_one<INTERP, true,  false>(a, b, s);
-	else                 return a->coherency_weighting ? launch_one<INTERP, false, true>(a, b, s) : launch_one<INTERP, false, false>(a, b, s);
 }
 
 /* `a`: the general kernel's arguments without a channel split (DasDecision::general), rf / out those of the burst's first frame. */
@@ -220,29 +193,10 @@ extern "C" hipError_t bf_launch_das_burst(const BfDasArgs *a, const BfBurstArgs 
 {
 	const uint32_t groups = (b->frame_count + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
 	if (a->family != BF_DAS_RCA || a->split_shift || b->frame_count == 0 || groups > 65535u) return hipErrorInvalidValue;
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_kind<BF_INTERP_NEAREST>(a, b, s);
-	case BF_INTERP_LINEAR:  return launch_kind<BF_INTERP_LINEAR>(a, b, s);
-	case BF_INTERP_CUBIC:   return launch_kind<BF_INTERP_CUBIC>(a, b, s);
-	}
-	return hipErrorInvalidValue;
-}
-
-template <int INTERP, bool CPLX, bool CW>
-static hipError_t launch_sweep_one(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s)
-{
-	uint32_t total = a->blocks[0] * a->blocks[1] * a->blocks[2];
-	uint32_t grid  = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
-	uint32_t groups = (b->burst.frame_count + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
-	hipLaunchKernelGGL((das_readi_burst_kernel<INTERP, CPLX, CW>), dim3(grid, groups), dim3(256), 0, s, *a, *b);
-	return hipGetLastError();
-}
-
-template <int INTERP>
-static hipError_t launch_sweep_kind(const BfDasArgs *a, const BfReadiSweepArgs *b, hipStream_t s)
-{
-	if (a->complex_data) return a->coherency_weighting ? launch_sweep_one<INTERP, true,  true>(a, b, s) : launch_sweep_one<INTERP, true,  false>(a, b, s);
-	else                 return a->coherency_weighting ? launch_sweep_one<INTERP, false, true>(a, b, s) : launch_sweep_one<INTERP, false, false>(a, b, s);
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		hipLaunchKernelGGL((das_burst_kernel<interp, cplx, cw>), dim3(bf_general_grid_blocks(a), groups), dim3(256), 0, s, *a, *b);
+		return hipGetLastError();
+	});
 }
 
 /* `a` as for bf_launch_das_burst, family READI; b->groups: frame_count validated group ids on the device. */
@@ -252,10 +206,8 @@ extern "C" hipError_t bf_launch_das_readi_sweep(const BfDasArgs *a, const BfRead
 	const uint32_t groups = (frames + BF_BURST_FRAMES_PER_THREAD - 1u) / BF_BURST_FRAMES_PER_THREAD;
 	if (a->family != BF_DAS_READI || a->split_shift || a->readi_group_count < 2u || !a->readi_hadamard || !b->groups || frames == 0 || groups > 65535u)
 		return hipErrorInvalidValue;
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_sweep_kind<BF_INTERP_NEAREST>(a, b, s);
-	case BF_INTERP_LINEAR:  return launch_sweep_kind<BF_INTERP_LINEAR>(a, b, s);
-	case BF_INTERP_CUBIC:   return launch_sweep_kind<BF_INTERP_CUBIC>(a, b, s);
-	}
-	return hipErrorInvalidValue;
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		hipLaunchKernelGGL((das_readi_burst_kernel<interp, cplx, cw>), dim3(bf_general_grid_blocks(a), groups), dim3(256), 0, s, *a, *b);
+		return hipGetLastError();
+	});
 }

@@ -1,4 +1,6 @@
-/* das_burst_term.h -- one term of BF_BURST_FRAMES_PER_THREAD frames: what the kernels of das_burst.hip and das_burst_views.hip share. */
+/* das_burst_term.h -- what the three kernels of das_burst.hip and das_burst_views.hip share beyond das_general.h: the frames of a block
+ * (burst_frames) and one term of BF_BURST_FRAMES_PER_THREAD frames (burst_term).  The RCA loop around the term is restated in
+ * das_burst_kernel and das_burst_views_kernel: shared as a function it compiled to other code in both (das_burst_views.hip). */
 #ifndef BF_DAS_BURST_TERM_H
 #define BF_DAS_BURST_TERM_H
 
@@ -10,6 +12,13 @@ constexpr int FB = (int)BF_BURST_FRAMES_PER_THREAD;
 struct SlotWeights { float w[FB]; };
 __device__ __forceinline__ float slot_weight(float w, int) { return w; }
 __device__ __forceinline__ float slot_weight(const SlotWeights &w, int f) { return w.w[f]; }
+
+/* The frames of this block (grid y: groups of FB frames): first .. first + count - 1; the last group may hold fewer than FB. */
+__device__ __forceinline__ void burst_frames(uint32_t frame_count, uint32_t &first, uint32_t &count)
+{
+	first = blockIdx.y * (uint32_t)FB;
+	count = frame_count - first < (uint32_t)FB ? frame_count - first : (uint32_t)FB;
+}
 
 /* One in-aperture term of FB frames: sample_rf (das_common.h, das.glsl:99-124 + cubic :67-97) with everything that depends on the
  * index alone -- range test, tap, weights, phasor -- taken once.  A term outside the valid range adds nothing (sample_rf gives +0).

@@ -9,6 +9,10 @@
  * weights, so the compiler can issue the gathers of several (channel, transmit) terms
  * back to back and wait once.  The result is bit-identical to the branchy form: a valid
  * sample is multiplied by 1.0f, an invalid one contributes +0.
+ *
+ * Also what every DAS kernel file shares at its two ends: the voxel's point (voxel_point: das.hip and its burst, views and variants forms,
+ * das_factored.hip, das_tile.hip, das_hercules.hip), the epilogue's value (coherency_weighted: those and the staged kernels) and, on the
+ * host, the launchers' template dispatch (bf_dispatch_kind).
  */
 #ifndef BF_DAS_COMMON_H
 #define BF_DAS_COMMON_H
@@ -154,6 +158,15 @@ __device__ __forceinline__ void m4_point(M m, float x, float y, float z, float &
 	ox = m[0] * x + m[4] * y + m[8]  * z + m[12];
 	oy = m[1] * x + m[5] * y + m[9]  * z + m[13];
 	oz = m[2] * x + m[6] * y + m[10] * z + m[14];
+}
+
+/* das.glsl:374-376: voxel (x, y, z) of the whole grid -> the point the voxel transform gives it */
+__device__ __forceinline__ void voxel_point(const BfDasArgs &p, uint32_t x, uint32_t y, uint32_t z, float &wx, float &wy, float &wz)
+{
+	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
+	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
+	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
+	m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
 }
 
 /* The interpolation of sample_rf split in three steps so that a caller can issue the
@@ -329,6 +342,38 @@ __device__ __forceinline__ sample_t<CPLX> sample_rf(const char *rf, int rf_offse
 		}
 	}
 	return result;
+}
+
+/* The epilogue's value: coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949) -- c *= c / incoherent, component-wise;
+ * incoherent == 0 gives NaN as in the reference.  (The value and not the store: `out[i] = coherency_weighted<CW>(..)` forms the address
+ * after the division, as every kernel's own text did; a helper that took the address compiled the burst kernels to other code.) */
+template <bool CW, typename V>
+__device__ __forceinline__ V coherency_weighted(V v, float incoherent)
+{
+	if constexpr (CW) v = v * (v / incoherent);
+	return v;
+}
+
+/* ---- host: the template dispatch of every launcher whose kernels are instantiated per interpolation mode, sample kind and coherency
+ * weighting.  f(interp, cplx, cw) is called with std::integral_constant<int, BF_INTERP_*>, std::bool_constant<complex_data> and
+ * std::bool_constant<coherency_weighting> BY VALUE, so that a generic lambda can name them as template arguments
+ * (`kernel<interp, cplx, cw>`); an unknown interpolation mode is hipErrorInvalidValue. */
+template <int INTERP, typename F>
+static hipError_t bf_dispatch_sample_kind(const BfDasArgs *a, F &f)
+{
+	constexpr std::integral_constant<int, INTERP> interp{};
+	if (a->complex_data) return a->coherency_weighting ? f(interp, std::true_type{},  std::true_type{}) : f(interp, std::true_type{},  std::false_type{});
+	else                 return a->coherency_weighting ? f(interp, std::false_type{}, std::true_type{}) : f(interp, std::false_type{}, std::false_type{});
+}
+template <typename F>
+static hipError_t bf_dispatch_kind(const BfDasArgs *a, F &&f)
+{
+	switch (a->interpolation) {
+	case BF_INTERP_NEAREST: return bf_dispatch_sample_kind<BF_INTERP_NEAREST>(a, f);
+	case BF_INTERP_LINEAR:  return bf_dispatch_sample_kind<BF_INTERP_LINEAR>(a, f);
+	case BF_INTERP_CUBIC:   return bf_dispatch_sample_kind<BF_INTERP_CUBIC>(a, f);
+	}
+	return hipErrorInvalidValue;
 }
 
 #endif

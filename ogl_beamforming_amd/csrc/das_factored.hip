@@ -26,7 +26,7 @@
  * over transmits, then over channels): results agree to float rounding, tests state the
  * tolerance.  Channel split for small frames as in das.hip.
  */
-#include "das_exact.h"
+#include "das_general.h"      /* transmit_distance */
 
 /* channels per register-resident chunk.  Measured on MI355X (config 4 geometry, 64 planes):
  * 2 -> 172 ms, 4 -> 160, 6 -> 154, 8 -> 154 with spills; cubic holds twice the gather data
@@ -48,22 +48,6 @@ struct ChannelFactor {
 	float apod;            /* for the incoherent sum */
 };
 
-/* das.glsl:187-202 with the per-transmit constants precomputed (same as das.hip) */
-__device__ __forceinline__ float transmit_distance(const BfTransmit &t, float wx, float wy, float wz)
-{
-	float result = 0.f;
-	if (!(t.flags & BF_TX_NONE)) {
-		float px = (t.flags & BF_TX_ROWS) ? wy : wx;
-		if (t.flags & BF_TX_PLANE) {
-			result = px * t.sin_a + wz * t.cos_a;
-		} else {
-			float dx = px - t.focus_x, dz = wz - t.focus_z;
-			result = hw_sqrt(dx * dx + dz * dz);
-		}
-	}
-	return result;
-}
-
 /* ROW_ENDS: the instantiation for launches in which a term can come within reach of an end of its RF row (BfDasArgs::row_ends, a host
  * bound: das_select.cpp); the other one carries none of that code -- its loops and its register allocation are round 3's. */
 template <int FAMILY, int INTERP, bool CPLX, bool CW, bool ROW_ENDS>
@@ -73,7 +57,9 @@ __global__ __launch_bounds__(1024) void das_factored_kernel(const BfDasArgs p)
 	constexpr uint32_t ES = CPLX ? 8 : 4;
 	extern __shared__ __attribute__((aligned(16))) unsigned char factored_lds[];
 
-	/* blockIdx -> tile and thread -> voxel exactly as das.hip */
+	/* blockIdx -> tile and thread -> voxel exactly as das.hip: this file's own text, not general_tile / tile_voxel (das_general.h).  Tried
+	 * with this compiler -- general_tile alone, tile_voxel alone on the walk below, and both --: each changed all 48 kernels here (the
+	 * linear IQ instances run at their register limit: voxel_of below). */
 	uint32_t total = p.blocks[0] * p.blocks[1] * p.blocks[2];
 	uint32_t bid   = blockIdx.x;
 	uint32_t per   = (total + 7u) / 8u;
@@ -130,11 +116,8 @@ __global__ __launch_bounds__(1024) void das_factored_kernel(const BfDasArgs p)
 
 	{
 		uint32_t z = p.z_first + zl;
-		float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);       /* das.glsl:374-376 */
-		float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-		float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
 		float wx, wy, wz;
-		m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+		voxel_point(p, x, y, z, wx, wy, wz);
 
 		const char *rf = (const char *)p.rf;
 		const int   S = p.sample_count, A = p.acquisition_count, C = p.channel_count;
@@ -457,42 +440,20 @@ __global__ __launch_bounds__(1024) void das_factored_kernel(const BfDasArgs p)
 		asm volatile("" : "+v"(thread));
 		voxel_of(thread, sx, sy, szl);
 		uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * szl + (uint64_t)p.size[0] * sy + sx;
-		sample_t<CPLX> v = coherent;
-		if constexpr (CW) v = v * (v / incoherent);                      /* coherency_weighting.glsl:36 */
-		reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = v;
+		reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = coherency_weighted<CW>(coherent, incoherent);
 	}
 }
 
-template <int FAMILY, int INTERP, bool CPLX, bool CW>
-hipError_t launch_one(const BfDasArgs *a, hipStream_t s)
-{
-	uint32_t total   = a->blocks[0] * a->blocks[1] * a->blocks[2];
-	uint32_t grid    = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
-	uint32_t threads = a->split_shift ? 64u << a->split_shift : 256u;
-	uint32_t lds     = a->split_shift ? ((1u << a->split_shift) - 1u) * 192u * (uint32_t)sizeof(float) : 0u;
-	if (a->row_ends && INTERP != BF_INTERP_NEAREST) hipLaunchKernelGGL((das_factored_kernel<FAMILY, INTERP, CPLX, CW, true>), dim3(grid), dim3(threads), lds, s, *a);
-	else                                            hipLaunchKernelGGL((das_factored_kernel<FAMILY, INTERP, CPLX, CW, false>), dim3(grid), dim3(threads), lds, s, *a);
-	return hipGetLastError();
-}
-
-template <int FAMILY, int INTERP>
-hipError_t launch_kind(const BfDasArgs *a, hipStream_t s)
-{
-	if (a->complex_data) return a->coherency_weighting ? launch_one<FAMILY, INTERP, true,  true >(a, s)
-	                                                   : launch_one<FAMILY, INTERP, true,  false>(a, s);
-	else                 return a->coherency_weighting ? launch_one<FAMILY, INTERP, false, true >(a, s)
-	                                                   : launch_one<FAMILY, INTERP, false, false>(a, s);
-}
-
+/* (ROW_ENDS exists for nearest interpolation too, where the kernel has no row-end code: such a launch takes the instance without) */
 template <int FAMILY>
-hipError_t launch_interp(const BfDasArgs *a, hipStream_t s)
+hipError_t launch_family(const BfDasArgs *a, hipStream_t s)
 {
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_kind<FAMILY, BF_INTERP_NEAREST>(a, s);
-	case BF_INTERP_LINEAR:  return launch_kind<FAMILY, BF_INTERP_LINEAR >(a, s);
-	case BF_INTERP_CUBIC:   return launch_kind<FAMILY, BF_INTERP_CUBIC  >(a, s);
-	}
-	return hipErrorInvalidValue;
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		const dim3 grid(bf_general_grid_blocks(a)), threads(bf_split_threads(a));
+		if (a->row_ends && interp != BF_INTERP_NEAREST) hipLaunchKernelGGL((das_factored_kernel<FAMILY, interp, cplx, cw, true>), grid, threads, bf_split_lds_bytes(a), s, *a);
+		else                                            hipLaunchKernelGGL((das_factored_kernel<FAMILY, interp, cplx, cw, false>), grid, threads, bf_split_lds_bytes(a), s, *a);
+		return hipGetLastError();
+	});
 }
 
 } // namespace
@@ -502,8 +463,8 @@ hipError_t launch_interp(const BfDasArgs *a, hipStream_t s)
 extern "C" hipError_t bf_launch_das_factored(const BfDasArgs *a, hipStream_t s)
 {
 	switch (a->family) {
-	case BF_DAS_RCA:    return launch_interp<BF_DAS_RCA>(a, s);
-	case BF_DAS_FORCES: return launch_interp<BF_DAS_FORCES>(a, s);
+	case BF_DAS_RCA:    return launch_family<BF_DAS_RCA>(a, s);
+	case BF_DAS_FORCES: return launch_family<BF_DAS_FORCES>(a, s);
 	}
 	return hipErrorInvalidValue;
 }

@@ -1,6 +1,15 @@
-/* das_general.h -- what the general kernel (das.hip), its ensemble form (das_burst.hip) and its views form (das_views.hip) share: the
- * transmit distance, the sample index, the row-end settlement of an index, the RCA family's loop (das_rca) and the walk from a block id
- * to a voxel tile.  One text, so that a frame of a burst and a view of a views push are the same arithmetic as a single frame. */
+/* das_general.h -- what the general kernel (das.hip) and its forms for an ensemble (das_burst.hip), for several grids (das_views.hip),
+ * for an ensemble on several grids (das_burst_views.hip) and for several scalar sets (das_variants.hip) share.  One text, so that a frame
+ * of a burst, a view and a variant are the same arithmetic as a single frame:
+ *   Accumulator, transmit_distance, sample_index, settle_index   all five (transmit_distance: das_factored.hip too)
+ *   das_rca (the RCA family's loop)                               das.hip, das_views.hip, das_variants.hip
+ *   general_tile (block id -> tile, dealt to the XCDs)            das.hip, das_burst.hip (both kernels)
+ *   general_tile_at (tile number -> tile)                         das_views.hip, das_burst_views.hip, das_variants.hip
+ *   tile_voxel (thread -> voxel)                                  das_views.hip, das_burst_views.hip, das_variants.hip, das_tile.hip;
+ *                                                                 das.hip, das_burst.hip and das_factored.hip restate it (the call
+ *                                                                 compiled to other code there: see those files)
+ * The voxel's point (voxel_point), the epilogue's value (coherency_weighted) and the launchers' template dispatch (bf_dispatch_kind) are
+ * das_common.h's, the grid size (bf_general_grid_blocks) is bf_kernels.h's: the fast kernels use them too. */
 #ifndef BF_DAS_GENERAL_H
 #define BF_DAS_GENERAL_H
 
@@ -154,6 +163,19 @@ __device__ __forceinline__ GeneralTile general_tile_at(const BfDasArgs &p, uint3
 		bz = tile / (p.blocks[0] * p.blocks[1]);
 	}
 	return GeneralTile{bx, by, bz, true};
+}
+
+/* Thread `tid` of the block on `tile` -> its voxel (x, y, z): z counts inside the shard.  The range test stays with the caller.
+ * (Out-parameters, the tile copied to locals first: returned as a struct the same text compiled to other code.) */
+__device__ __forceinline__ void tile_voxel(const BfDasArgs &p, const GeneralTile &tile, uint32_t tid, uint32_t &x, uint32_t &y, uint32_t &z)
+{
+	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
+	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
+	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
+	uint32_t lz  = (tid >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u);
+	x = (bx << p.tile_shift[0]) + lx;
+	y = (by << p.tile_shift[1]) + ly;
+	z = (bz << p.tile_shift[2]) + lz;
 }
 
 #endif

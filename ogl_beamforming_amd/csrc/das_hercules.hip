@@ -81,10 +81,7 @@ __device__ __forceinline__ float transmit_distance(const BfTransmit &t, float wx
 __device__ __forceinline__ void voxel_to_xdc(const BfDasArgs &p, uint32_t x, uint32_t y, uint32_t z,
                                              float &wx, float &wy, float &wz, float &xx, float &xy, float &xz)
 {
-	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);       /* das.glsl:374-376 */
-	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
-	m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+	voxel_point(p, x, y, z, wx, wy, wz);
 	m4_point(p.xdc_transform, wx, wy, wz, xx, xy, xz);
 }
 
@@ -476,8 +473,7 @@ __global__ __launch_bounds__(1024) void das_hercules_kernel(const BfDasArgs p, c
 	if (!inside) return;
 
 	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<VT *>(p.out)[out_index] = coherent;
+	reinterpret_cast<VT *>(p.out)[out_index] = coherency_weighted<CW>(coherent, incoherent);
 }
 
 template <int INTERP, bool CPLX, bool CW, bool PL, bool PD>
@@ -493,35 +489,22 @@ static hipError_t launch_herc(const BfDasArgs *a, const BfHerculesArgs *q, hipSt
 			hipLaunchKernelGGL(hercules_pair_kernel, dim3((total + 2u + 255u) / 256u), dim3(256), 0, s,
 			                   (const f32x2 *)a->rf, (f32x4 *)q->pairs, total, (uint32_t)a->sample_count);
 	}
-	uint32_t total = q->tiles[0] * q->tiles[1] * q->tiles[2];
-	uint32_t grid  = q->depth_major == 3u ? bf_plane_walk_blocks(q->tiles[0], q->tiles[1], q->band_rows) : ((total + 7u) / 8u) * 8u;
+	const uint32_t grid = bf_walk_grid_blocks(q->depth_major, q->tiles, q->band_rows);
 	if (a->row_ends && INTERP != BF_INTERP_NEAREST) hipLaunchKernelGGL((das_hercules_kernel<INTERP, CPLX, CW, PL, PD, true>), dim3(grid), dim3(64u * q->rows), 0, s, *a, *q);
 	else                                            hipLaunchKernelGGL((das_hercules_kernel<INTERP, CPLX, CW, PL, PD, false>), dim3(grid), dim3(64u * q->rows), 0, s, *a, *q);
 	return hipGetLastError();
 }
 
-template <int INTERP, bool CW>
-static hipError_t launch_herc_iq(const BfDasArgs *a, const BfHerculesArgs *q, hipStream_t s)
-{
-	if constexpr (INTERP != BF_INTERP_NEAREST) {
-		if (q->pairs) return q->phase_local ? launch_herc<INTERP, true, CW, true, true>(a, q, s) : launch_herc<INTERP, true, CW, false, true>(a, q, s);
-	}
-	return q->phase_local ? launch_herc<INTERP, true, CW, true, false>(a, q, s) : launch_herc<INTERP, true, CW, false, false>(a, q, s);
-}
-
-template <int INTERP>
-static hipError_t launch_herc_kind(const BfDasArgs *a, const BfHerculesArgs *q, hipStream_t s)
-{
-	if (a->complex_data) return a->coherency_weighting ? launch_herc_iq<INTERP, true>(a, q, s) : launch_herc_iq<INTERP, false>(a, q, s);
-	return a->coherency_weighting ? launch_herc<INTERP, false, true, false, false>(a, q, s) : launch_herc<INTERP, false, false, false, false>(a, q, s);
-}
-
+/* IQ samples: a window-local phase or not (PL), and -- linear and cubic interpolation -- the prepared copy of the input or not (PD) */
 extern "C" hipError_t bf_launch_das_hercules(const BfDasArgs *a, const BfHerculesArgs *q, hipStream_t s)
 {
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_herc_kind<BF_INTERP_NEAREST>(a, q, s);
-	case BF_INTERP_LINEAR:  return launch_herc_kind<BF_INTERP_LINEAR>(a, q, s);
-	case BF_INTERP_CUBIC:   return launch_herc_kind<BF_INTERP_CUBIC>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		if constexpr (!cplx) return launch_herc<interp, false, cw, false, false>(a, q, s);
+		else {
+			if constexpr (interp != BF_INTERP_NEAREST) {
+				if (q->pairs) return q->phase_local ? launch_herc<interp, true, cw, true, true>(a, q, s) : launch_herc<interp, true, cw, false, true>(a, q, s);
+			}
+			return q->phase_local ? launch_herc<interp, true, cw, true, false>(a, q, s) : launch_herc<interp, true, cw, false, false>(a, q, s);
+		}
+	});
 }

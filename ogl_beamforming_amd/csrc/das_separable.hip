@@ -316,33 +316,17 @@ static hipError_t launch_sep(const BfDasArgs *a, const BfSeparableArgs *q, hipSt
 	return rca_launch_tiles(das_rca_separable_kernel<INTERP, CPLX, CW, VS>, q->tiles[0] * q->tiles[1] * q->tiles[2], q->threads, a, q, s);
 }
 
-template <int INTERP>
-static hipError_t launch_sep_kind(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
-{
-	if (a->complex_data) {
-		if constexpr (INTERP == BF_INTERP_LINEAR) {
-			/* compile-time tile extents for the headline case */
-			if (a->coherency_weighting) switch (q->v_shift) {
-			case 4: return launch_sep<INTERP, true, true, 4>(a, q, s);
-			case 5: return launch_sep<INTERP, true, true, 5>(a, q, s);
-			case 6: return launch_sep<INTERP, true, true, 6>(a, q, s);
-			} else switch (q->v_shift) {
-			case 4: return launch_sep<INTERP, true, false, 4>(a, q, s);
-			case 5: return launch_sep<INTERP, true, false, 5>(a, q, s);
-			case 6: return launch_sep<INTERP, true, false, 6>(a, q, s);
-			}
-		}
-		return a->coherency_weighting ? launch_sep<INTERP, true, true, 0>(a, q, s) : launch_sep<INTERP, true, false, 0>(a, q, s);
-	}
-	return a->coherency_weighting ? launch_sep<INTERP, false, true, 0>(a, q, s) : launch_sep<INTERP, false, false, 0>(a, q, s);
-}
-
 extern "C" hipError_t bf_launch_das_separable(const BfDasArgs *a, const BfSeparableArgs *q, hipStream_t s)
 {
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_sep_kind<BF_INTERP_NEAREST>(a, q, s);
-	case BF_INTERP_LINEAR:  return launch_sep_kind<BF_INTERP_LINEAR>(a, q, s);
-	case BF_INTERP_CUBIC:   return launch_sep_kind<BF_INTERP_CUBIC>(a, q, s);
-	}
-	return hipErrorInvalidValue;
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		if constexpr (cplx && interp == BF_INTERP_LINEAR) {
+			/* compile-time tile extents for the headline case */
+			switch (q->v_shift) {
+			case 4: return launch_sep<interp, cplx, cw, 4>(a, q, s);
+			case 5: return launch_sep<interp, cplx, cw, 5>(a, q, s);
+			case 6: return launch_sep<interp, cplx, cw, 6>(a, q, s);
+			}
+		}
+		return launch_sep<interp, cplx, cw, 0>(a, q, s);
+	});
 }

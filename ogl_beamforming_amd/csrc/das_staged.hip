@@ -661,8 +661,7 @@ __device__ __forceinline__ void staged_paired_body(const BfDasArgs &p, const BfS
 	if (!(gu < p.size[u_axis] && gv < p.size[v_axis])) return;
 	const uint32_t x = u_axis == 0 ? gu : gv, y = u_axis == 0 ? gv : gu;
 	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<f32x2 *>(p.out)[out_index] = coherent;
+	reinterpret_cast<f32x2 *>(p.out)[out_index] = coherency_weighted<CW>(coherent, incoherent);
 }
 
 template <bool CW, int VS, int WS, int NL, bool UNI, bool PAIRED>

@@ -285,8 +285,7 @@ template <bool CW, typename Value>
 __device__ __forceinline__ void rca_store_voxel(const BfDasArgs &p, uint32_t zl, uint32_t x, uint32_t y, Value coherent, float incoherent)
 {
 	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * zl + (uint64_t)p.size[0] * y + x;
-	if constexpr (CW) coherent = coherent * (coherent / incoherent);   /* coherency_weighting.glsl:36 */
-	reinterpret_cast<Value *>(p.out)[out_index] = coherent;
+	reinterpret_cast<Value *>(p.out)[out_index] = coherency_weighted<CW>(coherent, incoherent);
 }
 
 /* ---- host: grid from the tile count (a multiple of 8: one run of tiles per XCD), the dynamic LDS limit, the launch */

@@ -29,7 +29,7 @@
  *     others test every term and read a zero element instead.
  * One block per CU (131 KB of windows, <= 128 VGPRs).  No MFMA: gather-accumulate.
  */
-#include "das_common.h"
+#include "das_general.h"
 
 namespace {
 
@@ -118,7 +118,8 @@ __global__ __launch_bounds__(1024, 4) void das_tile_kernel(const BfDasArgs p)
 	constexpr uint32_t ES = 8;
 	extern __shared__ __attribute__((aligned(16))) unsigned char tile_lds[];
 
-	/* blockIdx -> tile, thread -> voxel: das_factored.hip */
+	/* blockIdx -> tile: das_factored.hip's text, thread -> voxel: tile_voxel (das_general.h).  (general_tile in place of the walk below
+	 * changed all eight kernels with this compiler, and so did tile_voxel at the store at the end of the kernel: both stay restated.) */
 	const uint32_t total = p.blocks[0] * p.blocks[1] * p.blocks[2];
 	const uint32_t bid   = blockIdx.x;
 	const uint32_t per   = (total + 7u) / 8u;
@@ -143,10 +144,8 @@ __global__ __launch_bounds__(1024, 4) void das_tile_kernel(const BfDasArgs p)
 	}
 	const uint32_t tid = threadIdx.x;
 	const uint32_t lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-	const uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
-	const uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
-	const uint32_t lz  = (tid >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u);
-	uint32_t x = (bx << p.tile_shift[0]) + lx, y = (by << p.tile_shift[1]) + ly, zl = (bz << p.tile_shift[2]) + lz;
+	uint32_t x, y, zl;
+	tile_voxel(p, GeneralTile{bx, by, bz, true}, tid, x, y, zl);
 	/* every thread takes part in the staging and the reductions: threads outside the grid repeat its last voxel (and store nothing) */
 	x = x < p.size[0] ? x : p.size[0] - 1u;
 	y = y < p.size[1] ? y : p.size[1] - 1u;
@@ -155,13 +154,7 @@ __global__ __launch_bounds__(1024, 4) void das_tile_kernel(const BfDasArgs p)
 	const int   S = p.sample_count, A = p.acquisition_count, C = p.channel_count;
 	const float turns_per_sample = p.demodulation_frequency * p.inv_sampling_frequency;
 	float wx, wy, wz, xx, xy, xz;
-	{
-		const uint32_t z = p.z_first + zl;
-		const float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);       /* das.glsl:374-376 */
-		const float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-		const float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
-		m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
-	}
+	voxel_point(p, x, y, p.z_first + zl, wx, wy, wz);
 	if constexpr (FAMILY == BF_DAS_RCA) m4_point(p.xdc_transform, wx, wy, wz, xx, xy, xz);
 	else { xx = wx; xy = wy; xz = wz; }
 	const float zz = xz * xz;
@@ -548,9 +541,7 @@ __global__ __launch_bounds__(1024, 4) void das_tile_kernel(const BfDasArgs p)
 		const uint32_t sz = (bz << p.tile_shift[2]) + ((t >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u));
 		if (sx < p.size[0] && sy < p.size[1] && sz < p.z_count) {
 			const uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * sz + (uint64_t)p.size[0] * sy + sx;
-			sample_t<true> v = coherent;
-			if constexpr (CW) v = v * (v / incoherent);                      /* coherency_weighting.glsl:36 */
-			reinterpret_cast<sample_t<true> *>(p.out)[out_index] = v;
+			reinterpret_cast<sample_t<true> *>(p.out)[out_index] = coherency_weighted<CW>(coherent, incoherent);
 		}
 	}
 }
@@ -558,8 +549,7 @@ __global__ __launch_bounds__(1024, 4) void das_tile_kernel(const BfDasArgs p)
 template <int FAMILY, bool CW, int WS>
 hipError_t launch_tile(const BfDasArgs *a, hipStream_t s)
 {
-	const uint32_t total = a->blocks[0] * a->blocks[1] * a->blocks[2];
-	const uint32_t grid  = a->depth_major == 3u ? bf_plane_walk_blocks(a->blocks[0], a->blocks[1], a->band_rows) : ((total + 7u) / 8u) * 8u;
+	const uint32_t grid  = bf_general_grid_blocks(a);
 	const uint32_t A_pad = ((uint32_t)a->acquisition_count + 15u) & ~15u;
 	uint32_t lds = 64u + 2u * kTileElems * 32u + 32u + 4u * A_pad + 4u * 2u * kTileCH * 16u + 64u;
 	/* the transmit pass borrows the staging area for its [transmit][wave] minima and maxima: they must end before the zero element and the

@@ -6,8 +6,9 @@
  * split: a split or a dealing chosen from the total would make a variant's bits depend on its company.  Grid y: the taken variant.  A
  * block reads what differs from variant to variant from its BfVariantRow (32 bytes, the same for every lane: scalar loads, the fields
  * live in SGPRs for the whole loop), copies the launch's BfDasArgs, overrides those five fields and the frame, and then IS a block of the
- * general kernel: the prologue (das.glsl:374-376), das_rca over all channels -- settle_index reads the overridden arguments, so the row
- * ends follow each variant's own speed and margin -- and the epilogue with coherency weighting are das.hip's text.  No LDS, no barrier.
+ * general kernel: the prologue (tile_voxel, voxel_point), das_rca over all channels -- settle_index reads the overridden arguments, so the row
+ * ends follow each variant's own speed and margin -- and the epilogue's value (coherency_weighted) are the functions das.hip calls.  No
+ * LDS, no barrier.
  *
  * A variant's bits depend on the DAS input, the parameter block and its own triple: not on how many variants the launch holds, nor on
  * their order.  RCA family only (RCA_TPW, RCA_VLS, Flash): 3 interpolation modes x real / IQ x with / without coherency weighting = 12
@@ -26,47 +27,19 @@ __global__ __launch_bounds__(256) void das_variants_kernel(const BfDasArgs base,
 	p.out = (char *)base.out + row.out_offset;
 
 	const GeneralTile tile = general_tile_at(p, blockIdx.x);
-	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
-
-	uint32_t tid = threadIdx.x;
-	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
-	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
-	uint32_t lz  = (tid >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u);
-	uint32_t x = (bx << p.tile_shift[0]) + lx;
-	uint32_t y = (by << p.tile_shift[1]) + ly;
-	uint32_t z = (bz << p.tile_shift[2]) + lz;
+	uint32_t x, y, z;
+	tile_voxel(p, tile, threadIdx.x, x, y, z);
 	/* (the shifts of a tile sum to 8: a grid of fewer than 256 voxels gives the spare ones to x, and those lanes fall outside) */
 	if (!(x < p.size[0] && y < p.size[1] && z < p.size[2])) return;
 
 	Accumulator<CPLX, CW, false> acc;
 	acc.init();
-	/* das.glsl:374-376 */
-	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
-	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
 	float wx, wy, wz;
-	m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+	voxel_point(p, x, y, z, wx, wy, wz);
 	das_rca<INTERP, CPLX, CW, false>(p, (const char *)p.rf, wx, wy, wz, x, y, z, 0, p.channel_count, acc);
 
 	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * z + (uint64_t)p.size[0] * y + x;
-	sample_t<CPLX> v = acc.coherent;
-	/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949), as das.hip's epilogue */
-	if constexpr (CW) v = v * (v / acc.incoherent);
-	reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = v;
-}
-
-template <int INTERP, bool CPLX, bool CW>
-static hipError_t launch_one(const BfDasArgs *a, const BfVariantRow *rows, uint32_t variant_count, uint32_t tiles, hipStream_t s)
-{
-	hipLaunchKernelGGL((das_variants_kernel<INTERP, CPLX, CW>), dim3(tiles, variant_count), dim3(256), 0, s, *a, rows);
-	return hipGetLastError();
-}
-
-template <int INTERP>
-static hipError_t launch_kind(const BfDasArgs *a, const BfVariantRow *rows, uint32_t variant_count, uint32_t tiles, hipStream_t s)
-{
-	if (a->complex_data) return a->coherency_weighting ? launch_one<INTERP, true,  true>(a, rows, variant_count, tiles, s) : launch_one<INTERP, true,  false>(a, rows, variant_count, tiles, s);
-	else                 return a->coherency_weighting ? launch_one<INTERP, false, true>(a, rows, variant_count, tiles, s) : launch_one<INTERP, false, false>(a, rows, variant_count, tiles, s);
+	reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = coherency_weighted<CW>(acc.coherent, acc.incoherent);
 }
 
 /* `a`: the block's general-kernel arguments with 256-voxel tiles and no channel split, rf the DAS input, out the first taken variant's
@@ -76,10 +49,8 @@ extern "C" hipError_t bf_launch_das_variants(const BfDasArgs *a, const BfVariant
 	const uint64_t tiles = (uint64_t)a->blocks[0] * a->blocks[1] * a->blocks[2];
 	if (a->family != BF_DAS_RCA || a->split_shift || a->depth_major > 2u || a->z_first != 0 || a->z_count != a->size[2] || !rows ||
 	    variant_count == 0 || variant_count > 65535u || tiles == 0 || tiles > 0x7FFFFFFFu) return hipErrorInvalidValue;
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_kind<BF_INTERP_NEAREST>(a, rows, variant_count, (uint32_t)tiles, s);
-	case BF_INTERP_LINEAR:  return launch_kind<BF_INTERP_LINEAR>(a, rows, variant_count, (uint32_t)tiles, s);
-	case BF_INTERP_CUBIC:   return launch_kind<BF_INTERP_CUBIC>(a, rows, variant_count, (uint32_t)tiles, s);
-	}
-	return hipErrorInvalidValue;
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		hipLaunchKernelGGL((das_variants_kernel<interp, cplx, cw>), dim3((uint32_t)tiles, variant_count), dim3(256), 0, s, *a, rows);
+		return hipGetLastError();
+	});
 }

@@ -8,8 +8,9 @@
  * a patch is 1-4 blocks.  A block finds its view by a binary search over first_block[] -- K + 1 words in global memory, the same for
  * every lane, so the loads are scalar loads -- and reads what differs from view to view from that view's BfViewRow (128 bytes, scalar
  * loads again: the fields live in SGPRs for the whole loop).  It then IS a block of the general kernel on that grid: the prologue
- * (das.glsl:374-376), das_rca over all channels (das_general.h: the general kernel's own loop, row-end settlement included) and the
- * epilogue with coherency weighting are das.hip's text.  No channel split -- the views fill the chip as frames do in das_burst.hip, and
+ * (tile_voxel, das_general.h; voxel_point, das_common.h), das_rca over all channels (das_general.h: the general kernel's own loop,
+ * row-end settlement included) and the epilogue's value (coherency_weighted, das_common.h) are the functions das.hip calls.  (The view
+ * search and the override below are restated in das_burst_views.hip: see there.)  No channel split -- the views fill the chip as frames do in das_burst.hip, and
  * a split chosen from the total would make a view's bits depend on its company --, no LDS, no barrier.
  *
  * A view's bits depend on the DAS input, the parameter block and its own grid: not on how many views the launch holds, nor on their
@@ -39,33 +40,19 @@ __global__ __launch_bounds__(256) void das_views_kernel(const BfDasArgs base, co
 	p.out = (char *)base.out + row.out_offset;
 
 	const GeneralTile tile = general_tile_at(p, bid - first_block[lo]);
-	const uint32_t bx = tile.bx, by = tile.by, bz = tile.bz;
-
-	uint32_t tid = threadIdx.x;
-	uint32_t lx  = tid & ((1u << p.tile_shift[0]) - 1u);
-	uint32_t ly  = (tid >> p.tile_shift[0]) & ((1u << p.tile_shift[1]) - 1u);
-	uint32_t lz  = (tid >> (p.tile_shift[0] + p.tile_shift[1])) & ((1u << p.tile_shift[2]) - 1u);
-	uint32_t x = (bx << p.tile_shift[0]) + lx;
-	uint32_t y = (by << p.tile_shift[1]) + ly;
-	uint32_t z = (bz << p.tile_shift[2]) + lz;
+	uint32_t x, y, z;
+	tile_voxel(p, tile, threadIdx.x, x, y, z);
 	/* (the shifts of a tile sum to 8: a grid of fewer than 256 voxels gives the spare ones to x, and those lanes fall outside) */
 	if (!(x < p.size[0] && y < p.size[1] && z < p.size[2])) return;
 
 	Accumulator<CPLX, CW, false> acc;
 	acc.init();
-	/* das.glsl:374-376 */
-	float px = (float)x / fmaxf(1.0f, (float)p.size[0] - 1.0f);
-	float py = (float)y / fmaxf(1.0f, (float)p.size[1] - 1.0f);
-	float pz = (float)z / fmaxf(1.0f, (float)p.size[2] - 1.0f);
 	float wx, wy, wz;
-	m4_point(p.voxel_transform, px, py, pz, wx, wy, wz);
+	voxel_point(p, x, y, z, wx, wy, wz);
 	das_rca<INTERP, CPLX, CW, false>(p, (const char *)p.rf, wx, wy, wz, x, y, z, 0, p.channel_count, acc);
 
 	uint64_t out_index = (uint64_t)p.size[0] * p.size[1] * z + (uint64_t)p.size[0] * y + x;
-	sample_t<CPLX> v = acc.coherent;
-	/* coherency_weighting.glsl:36 with Scale = 1 (beamformer_core.c:949), as das.hip's epilogue */
-	if constexpr (CW) v = v * (v / acc.incoherent);
-	reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = v;
+	reinterpret_cast<sample_t<CPLX> *>(p.out)[out_index] = coherency_weighted<CW>(acc.coherent, acc.incoherent);
 }
 
 /* The rows and the prefix table of a push, from the pinned memory the host wrote them to (`src`: its device-side address) into the
@@ -84,29 +71,13 @@ extern "C" hipError_t bf_launch_views_table(void *dst, const void *src, uint32_t
 	return hipGetLastError();
 }
 
-template <int INTERP, bool CPLX, bool CW>
-static hipError_t launch_one(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s)
-{
-	hipLaunchKernelGGL((das_views_kernel<INTERP, CPLX, CW>), dim3(total_blocks), dim3(256), 0, s, *a, v->rows, v->first_block, v->view_count);
-	return hipGetLastError();
-}
-
-template <int INTERP>
-static hipError_t launch_kind(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s)
-{
-	if (a->complex_data) return a->coherency_weighting ? launch_one<INTERP, true,  true>(a, v, total_blocks, s) : launch_one<INTERP, true,  false>(a, v, total_blocks, s);
-	else                 return a->coherency_weighting ? launch_one<INTERP, false, true>(a, v, total_blocks, s) : launch_one<INTERP, false, false>(a, v, total_blocks, s);
-}
-
 /* `a`: the block's general-kernel arguments (everything but the grid), rf the DAS input, out the first view's frame; `v`: the rows and
  * the prefix table, total_blocks = first_block[view_count] */
 extern "C" hipError_t bf_launch_das_views(const BfDasArgs *a, const BfViewsArgs *v, uint32_t total_blocks, hipStream_t s)
 {
 	if (a->family != BF_DAS_RCA || v->view_count == 0 || total_blocks == 0 || !v->rows || !v->first_block) return hipErrorInvalidValue;
-	switch (a->interpolation) {
-	case BF_INTERP_NEAREST: return launch_kind<BF_INTERP_NEAREST>(a, v, total_blocks, s);
-	case BF_INTERP_LINEAR:  return launch_kind<BF_INTERP_LINEAR>(a, v, total_blocks, s);
-	case BF_INTERP_CUBIC:   return launch_kind<BF_INTERP_CUBIC>(a, v, total_blocks, s);
-	}
-	return hipErrorInvalidValue;
+	return bf_dispatch_kind(a, [&](auto interp, auto cplx, auto cw) {
+		hipLaunchKernelGGL((das_views_kernel<interp, cplx, cw>), dim3(total_blocks), dim3(256), 0, s, *a, v->rows, v->first_block, v->view_count);
+		return hipGetLastError();
+	});
 }

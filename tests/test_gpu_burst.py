@@ -139,6 +139,19 @@ def test_burst_kernel_parity(name, n, bflib, oracle):
     check_burst(bflib, oracle, acq, n, seed=4000 + n, expect_kernel=True)
 
 
+@pytest.mark.parametrize("interp", [I.Nearest, I.Linear, I.Cubic], ids=["nearest", "linear", "cubic"])
+def test_burst_kernel_parity_of_real_samples_under_coherency_weighting(interp, bflib, oracle):
+    """the three instances of the burst kernel no case above dispatches: real samples with coherency weighting, one per interpolation
+    mode, on the file's two small real cases with the mode and the weighting set in the parameter block; the bars are check_burst's"""
+    name = "rca_nearest_real" if interp == I.Nearest else "rca_cubic_real"
+    acq = cases.make(name)
+    acq.bp.interpolation_mode = int(interp)
+    acq.bp.coherency_weighting = 1
+    if name in GENERAL_PATH_FOR:
+        bflib.library().beamformer_hip_set_das_path(1)
+    check_burst(bflib, oracle, acq, 5, seed=4300, expect_kernel=True)
+
+
 def test_three_transmit_nearest_case_on_its_automatic_route(bflib, oracle):
     """rca_nearest_real as the selection gives it: single frames on the factored kernel, so the burst runs that kernel once per frame"""
     check_burst(bflib, oracle, cases.make("rca_nearest_real"), 5, seed=4100, expect_kernel=False)

@@ -22,7 +22,7 @@ from ogl_beamforming_amd import params as P
 from tests import cases
 from tests.test_gpu_burst import close_to_single_push, noise_frames, row_end_case, same_bits, single_push
 from tests.test_gpu_parity import compare, reference
-from tests.test_gpu_views import KERNEL_CASES, box, inner, kernel_views, mode_for, on_grid, per_view_views
+from tests.test_gpu_views import DISPATCH_CASES, KERNEL_CASES, box, case_of, inner, kernel_views, mode_for, on_grid, per_view_views
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
@@ -60,7 +60,7 @@ def prepared(name, which="kernel"):
         views = [bf.view_of(acq.bp), bf.view((96, 1, 12), *inner(lo, hi, (0, 0, (r - 8) / 95), (1, 1, (r + 3) / 95))),
                  bf.view((96, 1, 12), *inner(lo, hi, (0, 0, 84 / 95), (1, 1, 1)))]
     else:
-        acq = cases.make(name)
+        acq = case_of(name)
         rf = noise_frames(acq, N, 6000)
         views = four_views(acq) if which == "kernel" else per_view_views(acq)
     refs = []
@@ -91,7 +91,7 @@ def check_parity(name, frames, refs, what):
     print(f"{name}: {len(refs)} views x {len(refs[0])} RF frames on the {what}: worst max_rel_err {worst:.3e}")
 
 
-@pytest.mark.parametrize("name", KERNEL_CASES)
+@pytest.mark.parametrize("name", KERNEL_CASES + DISPATCH_CASES)
 def test_fused_kernel_parity(name, bflib):
     """every one of the K x 5 frames against the oracle on (block with view v's grid, RF k)"""
     acq, rf, views, refs = prepared(name)

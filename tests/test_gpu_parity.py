@@ -309,6 +309,36 @@ def test_factored_kernel(name, split, bflib, oracle):
     compare(gpu, ref, acq, flags)
 
 
+_I = P.InterpolationMode
+# (case, interpolation mode, coherency weighting, das path mode, the DAS path the frame must report): the instantiations of the general,
+# HERCULES, separable-gather and factored kernels that no case of cases.CASES dispatches as it stands -- real samples with coherency
+# weighting, or another interpolation mode of the FORCES cases -- on the smallest case of the family, with the two fields set in its
+# parameter block.  Reference and bars are every other test's here: the oracle on the same block, compare().
+DISPATCH = [("hercules_real", _I.Nearest, 1, 6, 4), ("hercules_real", _I.Cubic, 1, 6, 4),            # das_hercules.hip
+            ("hercules_real", _I.Nearest, 1, 0x11, 0), ("hercules_real", _I.Cubic, 1, 0x11, 0),      # das.hip, HERCULES
+            ("forces", _I.Nearest, 0, 0x11, 0), ("forces", _I.Cubic, 0, 0x11, 0),                    # das.hip, FORCES
+            ("rca_sep_real_nearest", _I.Nearest, 1, 3, 1), ("rca_sep_real_nearest", _I.Cubic, 1, 3, 1),   # das_separable.hip
+            ("rca_cubic_real", _I.Cubic, 1, 0x04, 3), ("rca_staged_real", _I.Cubic, 1, 0x04, 3),     # das_factored.hip, RCA: rows that end, and not
+            ("forces", _I.Linear, 1, 0x04, 3), ("forces", _I.Cubic, 0, 0x04, 3)]                     # das_factored.hip, FORCES
+
+
+@pytest.mark.parametrize("name,interp,cw,mode,want", DISPATCH,
+                         ids=[f"{n}-{i.name.lower()}-{'cw' if c else 'plain'}-{m:#x}" for n, i, c, m, _ in DISPATCH])
+def test_kernel_instances_no_case_dispatches_as_it_stands(name, interp, cw, mode, want, bflib, oracle):
+    acq = cases.make(name)
+    acq.bp.interpolation_mode = int(interp)
+    acq.bp.coherency_weighting = cw
+    ref, pairs, flags = reference(oracle, acq)
+    lib = bflib.library()
+    lib.beamformer_hip_set_das_path(mode)
+    try:
+        gpu = bflib.beamform(acq.bp, acq.rf, acq.filters)
+        assert last_das_path(bflib) == want
+    finally:
+        lib.beamformer_hip_set_das_path(0)
+    compare(gpu, ref, acq, flags)
+
+
 DECODING = sorted(n for n in cases.CASES
                   if cases.make(n).bp.decode_mode and int(P.ShaderKind.Decode) in list(cases.make(n).bp.compute_stages[:cases.make(n).bp.compute_stages_count]))
 

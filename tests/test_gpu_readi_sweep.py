@@ -170,7 +170,7 @@ def test_bits_do_not_depend_on_the_slot(geometry, interp, iq, cw, bflib):
         assert same_bits(five[i], nine[4 + i]), i
 
 
-@pytest.mark.parametrize("geometry,interp,iq,cw", [VARIANTS[0], VARIANTS[7], VARIANTS[9]], ids=[VARIANT_IDS[0], VARIANT_IDS[7], VARIANT_IDS[9]])
+@pytest.mark.parametrize("geometry,interp,iq,cw", VARIANTS, ids=VARIANT_IDS)      # (all twelve: the single pushes are the general kernel's READI instances)
 def test_the_per_frame_route_is_the_single_push(geometry, interp, iq, cw, bflib, oracle):
     """under das path flag 0x400 every frame is the single push's, bit for bit; the kernel's frames of the same sweep are within
     close_to_single_push's slack of them"""

@@ -27,6 +27,11 @@ I = P.InterpolationMode
 
 KERNEL_CASES = ["config1_small", "rca_cubic_real", "rca_f32_complex_in", "rca_a1s2", "rca_nearest_real"]
 GENERAL_PATH_FOR = {"rca_nearest_real"}            # see the module docstring
+# The instantiations of the views kernels no case above dispatches (every one with coherency weighting, and nearest x IQ): the file's
+# small real and IQ cases with the interpolation mode and the weighting set in the parameter block ("case+mode+cw", case_of()), run
+# under das path 1 like rca_nearest_real so that the views kernel takes them whatever their single frames would run.
+DISPATCH_CASES = ["rca_nearest_real+cw", "rca_f32_complex_in+nearest", "rca_f32_complex_in+nearest+cw", "rca_cubic_real+linear+cw",
+                  "rca_f32_complex_in+linear+cw", "rca_cubic_real+cw", "rca_f32_complex_in+cw"]
 PER_VIEW_CASES = ["forces", "hercules_wide_cw", "rca_staged_auto", "config5_literal_order"]
 PREFER, NO_KERNEL = P.HIP_DAS_PATH_PREFER_VIEWS_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL
 # the part of the case's depth range its RF rows reach (256-sample rows end a tenth of the way down the 6 .. 18 mm image): the views are
@@ -46,6 +51,18 @@ def box(bp):
 def inner(lo, hi, a, b):
     """the part a .. b (fractions of the extent, per axis) of the box lo .. hi"""
     return (tuple(l + (h - l) * f for l, h, f in zip(lo, hi, a)), tuple(l + (h - l) * f for l, h, f in zip(lo, hi, b)))
+
+
+def case_of(name):
+    """cases.make() of the name before the first '+', then 'nearest' / 'linear' / 'cubic' and 'cw' set in its parameter block"""
+    base, *changes = name.split("+")
+    acq = cases.make(base)
+    for change in changes:
+        if change == "cw":
+            acq.bp.coherency_weighting = 1
+        else:
+            acq.bp.interpolation_mode = int({"nearest": I.Nearest, "linear": I.Linear, "cubic": I.Cubic}[change])
+    return acq
 
 
 def kernel_views(acq):
@@ -87,7 +104,7 @@ def prepared(name, which="kernel"):
     """(acquisition, noise RF, views, per view: its acquisition and the oracle's reference) -- computed once, shared, left unchanged"""
     from oracle import binding
     binding.library()
-    acq = row_end_case({"row_ends_linear": I.Linear, "row_ends_cubic": I.Cubic}[name]) if name.startswith("row_ends") else cases.make(name)
+    acq = row_end_case({"row_ends_linear": I.Linear, "row_ends_cubic": I.Cubic}[name]) if name.startswith("row_ends") else case_of(name)
     rf = noise_frames(acq, 1, 4200 if name.startswith("row_ends") else 5000)[0]
     if name.startswith("row_ends"):
         # the whole plane; the deepest 96 x 1 x 12 strip -- which lies wholly past the ends of the 256-sample rows: an image of zeros,
@@ -109,7 +126,7 @@ def prepared(name, which="kernel"):
 
 
 def mode_for(name, flag):
-    return flag | (1 if name in GENERAL_PATH_FOR else 0)
+    return flag | (1 if name in GENERAL_PATH_FOR or name in DISPATCH_CASES else 0)
 
 
 @pytest.fixture(autouse=True)
@@ -175,6 +192,19 @@ def test_views_kernel(name, bflib):
         assert (err <= slack).all(), f"view {k}: views kernel and single push differ by {err.max() / scale:.3e} of the frame maximum"
         identical += same_bits(one, frames[k])
     print(f"{name}: {identical} of {len(views)} views of the views kernel equal their single push bit for bit")
+
+
+@pytest.mark.parametrize("name", DISPATCH_CASES)
+def test_views_kernel_instances_no_other_case_dispatches(name, bflib):
+    """parity of every view on the views kernel, as test_views_kernel's first step: the same views, reference and bars"""
+    acq, rf, views, refs = prepared(name)
+    bflib.library().beamformer_hip_set_das_path(mode_for(name, PREFER))
+    described = bflib.describe_views(acq.bp, views, acq.filters)
+    assert described.kernel_views == len(views) and described.das_launches == 1, described.reason
+    frames = bflib.beamform_views(acq.bp, rf, views, acq.filters)
+    info = bflib.last_views_info()
+    assert info.view_count == len(views) and info.route.kernel_views == len(views) and info.route.das_launches == 1, info.route.reason
+    check_parity(name, frames, refs, "views kernel")
 
 
 def check_per_view(bflib, name, which, mode):
