@@ -602,6 +602,70 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_peaks_to_views(const float source_
                                                              const uint32_t patch_points[3], const float patch_extent_voxels[3],
                                                              uint32_t use_offsets, uint32_t image_plane_tag, BeamformerHipView *out);
 
+/* ---- frame quantiles: exact order statistics of the `count` newest frames, selected ON THE DEVICE where the frames lie, in the units the
+ * peak calls decide in (a threshold from "the brightest 0.1 % of voxels are candidates" or "6 x the median" instead of a fraction of
+ * max_abs, the single brightest voxel and the likeliest outlier; the range of a display between two percentiles; a scale for
+ * beamformer_hip_queue_localisation_map) -- instead of downloading every frame to sort it ----
+ * DEFINITION (tests/frame_quantiles_ref.py restates it in numpy).
+ * DECISION VALUE.  The decision value q of a voxel is the one beamformer_hip_find_peaks_last_frames decides on: re * re + im * im for
+ * Float32Complex frames, every operation rounded to float32 on its own (no fused multiply-add), fabsf(v) for Float32 frames.  No
+ * square root takes part.  A voxel is finite when q is; a voxel that is not counts in non_finite and in nothing else.  q is never
+ * negative and never -0, so the order of the values is the order of their bit patterns as uint32.
+ * ORDER STATISTICS.  Let n be the finite voxels of the box and q_(0) <= ... <= q_(n-1) their decision values in ascending order.  A
+ * fraction f is a double with 0 <= f <= 1.  Its rank is r = (uint64)floor(f * (double)(n - 1) + 0.5): one double multiply, one add,
+ * one floor, no fused multiply-add -- numpy float64 reproduces it.  The quantile's `value` is q_(r), an actual voxel's value: nothing
+ * is interpolated, so it is exact.  below = #{q < value} and equal = #{q == value}, so below <= r < below + equal.  When n == 0:
+ * rank = below = equal = 0 and value = magnitude = threshold = 0.
+ * MAGNITUDE AND THRESHOLD are formed on the host from `value`, so they are IEEE-exact.  magnitude is sqrtf(value) for complex frames
+ * and value for real ones.  threshold is the number to hand to the peak calls: value for real frames; for complex frames the LARGEST
+ * float32 T >= 0 with fl(T * T) <= value (what stepping from sqrtf(value) with nextafterf arrives at: the condition holds for T and
+ * fails for the next float up).  With it the eligible set of beamformer_hip_find_peaks_last_frames (q >= fl(T * T)) contains every
+ * voxel with q >= value; it contains nothing else unless a voxel's q lies in [fl(T * T), value).  Not every float is the rounded
+ * square of a float, so equality with `value` cannot be promised.
+ * COARSE HISTOGRAM (optional): BEAMFORMER_HIP_QUANTILE_BINS uint32 counts a frame; bin b counts the finite voxels of the box whose q
+ * has bits >> 20 == b: 8 bins an octave of q, about 0.75 dB a bin for real frames and 0.38 dB for complex ones.  Bins from 2040 up are
+ * the non-finite patterns and stay 0.  It is the first selection pass's table, handed out as it is.
+ * Every count is an integer sum (the device adds with integer atomics, and no floating-point atomic exists in the library): the bytes
+ * of a frame's rows and of its histogram depend on that frame, the region and the fractions only -- not on count, not on the other
+ * frames of the call, not on the call being repeated. */
+#define BEAMFORMER_HIP_MAX_QUANTILES  16u
+#define BEAMFORMER_HIP_QUANTILE_BINS  2048u
+typedef struct {
+	double   fraction;                        /* as given */
+	uint64_t rank, below, equal;
+	float    value, magnitude, threshold;
+	uint32_t reserved;                        /* 0 */
+} BeamformerHipFrameQuantile;                 /* 48 bytes, no padding */
+typedef struct {
+	uint32_t frame_id, parameter_block, data_kind, image_plane_tag;   /* from the frame's record */
+	uint32_t points[3];                       /* the frame's own grid */
+	uint32_t region_first[3], region_count[3];/* the box that was ranked (the whole frame when region == NULL) */
+	uint32_t first, stored, reserved;         /* this frame's records: quantiles[first .. first + stored), stored == fraction_count; reserved 0 */
+	uint64_t voxels, non_finite;              /* finite / not finite voxels of the box */
+} BeamformerHipFrameQuantiles;                /* 80 bytes, no padding */
+/* frames[count], oldest first; the frames may differ in grid and in data kind, as for beamformer_hip_score_last_frames.  fractions
+ * [fraction_count] need not be sorted and may repeat; quantiles[count * fraction_count] is frame-major, in the order of `fractions`.
+ * histograms: NULL, or room for count * BEAMFORMER_HIP_QUANTILE_BINS counts, frame-major.  The call runs on the library's current stream
+ * behind the frames it reads: the rows and the fractions go up in one copy, one memset zeroes the count tables, three count passes
+ * each followed by a pick run (csrc/frame_quantiles.hip: a radix select on bits 30..20, 19..10 and 9..0 of q, so the frames are read
+ * three times), the results come back in one copy -- the histograms in one more -- behind ONE stream synchronise.  device_ms, when not
+ * NULL: the time between two events around the memset and the six launches.
+ * Refusals, all decided before anything is enqueued and leaving every output unwritten: count == 0 or > BEAMFORMER_HIP_MAX_SCORED_FRAMES,
+ * fraction_count == 0 or > BEAMFORMER_HIP_MAX_QUANTILES: BufferOverflow; InvalidAccess: fractions, frames or quantiles NULL; a
+ * fraction that is NaN or outside [0, 1]; a box of more than 2^32 - 1 voxels; and everything beamformer_hip_score_last_frames refuses --
+ * no device in use yet, fewer than count frames queued, a tombstone, an overwritten record, reused storage, a region that does not fit
+ * inside every frame, several devices. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                    const double *fractions, uint32_t fraction_count,
+                                                                    BeamformerHipFrameQuantiles *frames /* [count] */,
+                                                                    BeamformerHipFrameQuantile *quantiles /* [count * fraction_count] */,
+                                                                    uint32_t *histograms /* [count][2048], may be NULL */, float *device_ms);
+/* Host only: touches no device and no library state but the last error.  *threshold: the `threshold` of a quantile whose `value` is
+ * decision_value, as defined above -- decision_value itself for BeamformerDataKind_Float32, the largest float32 T >= 0 with
+ * fl(T * T) <= decision_value for BeamformerDataKind_Float32Complex.  InvalidAccess: threshold NULL, a decision value that is negative
+ * or not finite, any other data kind. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_peak_threshold_of(float decision_value, uint32_t data_kind, float *threshold);
+
 /* ---- localisation map: the peaks of the frames of the frame ring accumulated ON THE DEVICE into one grid of counts (ULM's product: the
  * sub-voxel positions of the peaks of thousands of frames binned on a grid several times finer than the beamforming grid -- no peak list
  * leaves the device, and the map can be queued into the frame ring as an ordinary Float32 frame, so that

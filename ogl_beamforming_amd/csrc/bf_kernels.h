@@ -413,6 +413,39 @@ typedef struct {
 	uint32_t use_offsets;        /* 0: a peak's position is its index */
 } BfMapArgs;
 
+/* ---- frame quantiles (frame_quantiles.hip: beamformer_hip_quantiles_last_frames) ---- */
+#define BF_QUANTILES_MAX       16u           /* = BEAMFORMER_HIP_MAX_QUANTILES: ranks a frame, and so distinct prefixes a digit pass */
+#define BF_QUANTILES_BINS1     2048u         /* = BEAMFORMER_HIP_QUANTILE_BINS: bits 30..20 of a decision value */
+#define BF_QUANTILES_BINS      1024u         /* bits 19..10, then bits 9..0 */
+typedef struct {
+	uint64_t offset;             /* of the frame in the frame ring, bytes */
+	uint32_t points[3], cplx;    /* the frame's grid; 1: Float32Complex, 0: Float32 */
+	uint32_t first[3], count[3]; /* the box, inside the grid, every count >= 1, at most 2^32 - 1 voxels */
+	uint32_t blocks;             /* bf_metrics_blocks of the box */
+	uint32_t step[3];            /* blocks * 256 voxels of the box as steps in x, y, z: (n % cx, n / cx % cy, n / (cx * cy)) */
+} BfQuantilesRow;                /* 64 bytes */
+typedef struct { uint64_t voxels, non_finite; } BfQuantilesTally;   /* a frame's box */
+typedef struct {                 /* one rank of one frame: what the pick kernels carry from pass to pass, and the answer */
+	uint64_t rank, below, equal; /* below: the finite voxels under the prefix so far, at the end under the value */
+	uint32_t value_bits;         /* the bit pattern of q_(rank), after the third pick */
+	uint32_t prefix;             /* the leading bits selected so far: 11 after the first pick, 21 after the second */
+	uint32_t residual;           /* the rank inside the prefix */
+	uint32_t slot;               /* which of the frame's distinct prefixes: the table the next count pass adds to for it */
+} BfQuantileState;               /* 40 bytes */
+typedef struct {                 /* a frame's distinct prefixes, for the count pass that follows */
+	uint64_t mask;               /* bit (prefix & 63) set for every one of them: the test most voxels fail */
+	uint32_t tables, reserved;   /* how many; 0: no finite voxel */
+	uint32_t prefix[BF_QUANTILES_MAX];   /* unused ones 0xFFFFFFFF, no voxel's key */
+} BfQuantilesPrefixes;           /* 80 bytes */
+/* the count tables of a call, uint32 words zeroed by one memset: non_finite[frames] (rounded up to 16 words) | pass 1 [frames][2048] |
+ * pass 2 [frames][fractions][1024] | pass 3 likewise */
+static inline size_t bf_quantiles_pass1_at(uint32_t frames) { return ((size_t)frames + 15u) / 16u * 16u; }
+static inline size_t bf_quantiles_pass_words(uint32_t frames, uint32_t fractions) { return (size_t)frames * fractions * BF_QUANTILES_BINS; }
+static inline size_t bf_quantiles_table_words(uint32_t frames, uint32_t fractions)
+{
+	return bf_quantiles_pass1_at(frames) + (size_t)frames * BF_QUANTILES_BINS1 + 2u * bf_quantiles_pass_words(frames, fractions);
+}
+
 /* ---- ensemble filter (ensemble.hip: beamformer_hip_gram_last_frames, beamformer_hip_mix_last_frames) ---- */
 #define BF_ENSEMBLE_MAX_FRAMES 256u          /* = BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES */
 #define BF_GRAM_TILE           32u           /* frames a side of a tile of (j, k) pairs: a block of 256 threads, four pairs a thread */
@@ -606,6 +639,14 @@ hipError_t bf_launch_min_max(const void *frame, uint64_t voxels, int complex_dat
  * inside its frame (the caller checks: the kernels index with what the rows say) */
 hipError_t bf_launch_frame_metrics(const void *ring, const BfMetricsRow *rows, uint32_t frame_count, uint32_t max_blocks,
                                    BfMetricsPartial *partials, BfMetricsResult *results, hipStream_t s);
+/* frame_quantiles.hip: one memset and six launches -- three count passes (grid x max_blocks, the most blocks any row asks for; grid y the
+ * frame), each followed by a pick, one block a frame.  `tables`: bf_quantiles_table_words(frame_count, fraction_count) words, zeroed
+ * here; fractions[fraction_count]; prefixes[frame_count]; tallies[frame_count]; states[frame_count][fraction_count].  Integer atomics
+ * only.  All tables are device memory; every row's box lies inside its frame and holds at most 2^32 - 1 voxels (the caller checks: the
+ * kernels index with what the rows say) */
+hipError_t bf_launch_frame_quantiles(const void *ring, const BfQuantilesRow *rows, const double *fractions, uint32_t frame_count,
+                                     uint32_t fraction_count, uint32_t max_blocks, uint32_t *tables, BfQuantilesPrefixes *prefixes,
+                                     BfQuantilesTally *tallies, BfQuantileState *states, hipStream_t s);
 /* frame_peaks.hip: three launches, no atomics.  _mark: the mark pass (grid x max_blocks, the most blocks any row asks for; grid y the
  * frame) and the scan, one block a frame; _emit: the mark pass's grid again, storing 32-byte records (BeamformerHipFramePeak's layout) at
  * list[firsts[frame] + rank].  The host reads `results` between the two to size `list` and to fill `firsts`.  All tables are device

@@ -313,6 +313,10 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
                             uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
                             float *device_ms);                     /* arguments checked by the caller (lib_api.cpp) */
+bool quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const double *fractions, uint32_t fraction_count,
+                           BeamformerHipFrameQuantiles *frames, BeamformerHipFrameQuantile *quantiles, uint32_t *histograms,
+                           float *device_ms);                      /* arguments checked by the caller (lib_api.cpp) */
+float peak_threshold_of(float value, bool cplx);                   /* host only; value finite and >= 0 (the caller checks) */
 bool localisation_map_reset(const uint32_t points[3]);             /* null: release; else checked by the caller */
 bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
                                   const double *placements, uint32_t placement_count, uint32_t use_offsets, BeamformerHipMapDeposits *frames,

@@ -4,6 +4,7 @@
  * device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is executor.cpp's. */
 #include "context.h"
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstring>
 
 namespace bf {
@@ -14,6 +15,28 @@ void FrameOps::release()
 	for (void *p : {metrics_pinned, mix_pinned}) if (p) (void)hipHostFree(p);
 	for (hipEvent_t e : {metrics_begin, metrics_end, peaks_begin, peaks_end, mix_copied, mix_begin, mix_end}) if (e) (void)hipEventDestroy(e);
 	*this = FrameOps{};
+}
+
+/* beamformer_hip_peak_threshold_of: the number to hand to the peak calls for a decision value -- the value itself for real frames; for
+ * complex ones the largest float32 T >= 0 with fl(T * T) <= value.  The product is formed in float32 on its own, as the mark pass forms
+ * it, and rounding is monotone: the condition holds up to one T and fails from the next, so the T is found by bisection over the bit
+ * patterns of the non-negative floats -- what stepping from sqrtf(value) with nextafterf arrives at, without the 10^8 steps that takes
+ * where the products underflow (value 0: every T up to 2^-75). */
+float peak_threshold_of(float value, bool cplx)
+{
+	if (!cplx) return value;
+	const auto holds = [value](uint32_t bits) {
+		float t; std::memcpy(&t, &bits, sizeof(t));
+		volatile float p = t * t;                          /* (one rounding to float32, whatever the host evaluates in) */
+		return p <= value;
+	};
+	uint32_t lo = 0, hi = 0x7F7FFFFFu;                     /* holds(lo): 0 <= value; the largest finite float may hold too */
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+		if (holds(mid)) lo = mid; else hi = mid - 1u;
+	}
+	float t; std::memcpy(&t, &lo, sizeof(t));
+	return t;
 }
 
 namespace {
@@ -112,8 +135,9 @@ bool ensure_metrics_memory(Device &d, size_t pinned_bytes, size_t device_bytes)
 
 /* What a reduce call enqueues and waits for: the first up_bytes of the pinned block sent to the scratch, launch(stream) between the
  * metrics event pair, [down_at, down_at + down_bytes) of the scratch brought back to the same place in the pinned block.  The one
- * synchronise is also what frees the pinned memory for the next call, so it runs whatever failed before it.  False: InvalidAccess set. */
-template <class Launch> bool timed_reduce(Device &d, size_t up_bytes, size_t down_at, size_t down_bytes, float *device_ms, Launch launch)
+ * synchronise is also what frees the pinned memory for the next call, so it runs whatever failed before it.  False: InvalidAccess set.
+ * also(stream): copies of the call's own to the caller's memory, enqueued behind the events and in front of the synchronise. */
+template <class Launch, class Also> bool timed_reduce(Device &d, size_t up_bytes, size_t down_at, size_t down_bytes, float *device_ms, Launch launch, Also also)
 {
 	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
 	hipStream_t s = d.stream;
@@ -122,11 +146,16 @@ template <class Launch> bool timed_reduce(Device &d, size_t up_bytes, size_t dow
 	if (ok) ok &= HIP_OK(launch(s));
 	ok &= HIP_OK(hipEventRecord(d.ops.metrics_end, s));
 	if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + down_at, device + down_at, down_bytes, hipMemcpyDeviceToHost, s));
+	if (ok) ok &= HIP_OK(also(s));
 	ok &= HIP_OK(hipStreamSynchronize(s));
 	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
 	float ms = 0;
 	if (device_ms) *device_ms = HIP_OK(hipEventElapsedTime(&ms, d.ops.metrics_begin, d.ops.metrics_end)) ? ms : 0.0f;
 	return true;
+}
+template <class Launch> bool timed_reduce(Device &d, size_t up_bytes, size_t down_at, size_t down_bytes, float *device_ms, Launch launch)
+{
+	return timed_reduce(d, up_bytes, down_at, down_bytes, device_ms, launch, [](hipStream_t) { return hipSuccess; });
 }
 
 /* the mark pass's rows of the boxed frames (frame_peaks.hip), as find_peaks_last_frames and accumulate_peaks_last_frames launch it: the
@@ -289,6 +318,78 @@ bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
 	}
 	*peak_count = total;
+	return true;
+}
+
+/* beamformer_hip_quantiles_last_frames: exact order statistics of the `count` newest frames, selected where they lie
+ * (frame_quantiles.hip: three count passes, a pick behind each).  The arguments arrive checked (lib_api.cpp); everything else that can
+ * refuse is decided before anything is enqueued.  One synchronise: no buffer is sized by what was counted. */
+bool quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const double *fractions, uint32_t fraction_count,
+                           BeamformerHipFrameQuantiles *frames, BeamformerHipFrameQuantile *quantiles, uint32_t *histograms, float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipFrameQuantile) == 48 && sizeof(BeamformerHipFrameQuantiles) == 80, "records without padding");
+	static_assert(BF_QUANTILES_MAX == BEAMFORMER_HIP_MAX_QUANTILES && BF_QUANTILES_BINS1 == BEAMFORMER_HIP_QUANTILE_BINS, "one limit");
+	std::vector<BoxedFrame> boxed;
+	if (!newest_boxed_frames(count, region, boxed)) return false;
+	Device &d = ctx().devices[0];
+
+	std::vector<BfQuantilesRow> rows(count);
+	uint32_t max_blocks = 0;
+	for (uint32_t n = 0; n < count; n++) {
+		if (boxed[n].volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);     /* the kernels count a box's voxels in 32 bits */
+		BfQuantilesRow &r = rows[n];
+		box_into(r, boxed[n]);
+		r.blocks = bf_metrics_blocks(boxed[n].volume);
+		const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
+		r.step[0] = (uint32_t)(stride % r.count[0]);
+		r.step[1] = (uint32_t)(stride / r.count[0] % r.count[1]);
+		r.step[2] = (uint32_t)(stride / plane);
+		if (r.blocks > max_blocks) max_blocks = r.blocks;
+	}
+
+	/* device: rows | fractions | tallies | states | count tables | prefixes; pinned: the first four
+	 * (rows and fractions go up in one copy, tallies and states come back in one: each pair stays adjacent) */
+	const size_t ranks = (size_t)count * fraction_count;
+	Carve dev;
+	const size_t rows_at = dev.take(sizeof(BfQuantilesRow) * count), fractions_at = dev.take(sizeof(double) * fraction_count),
+	             tallies_at = dev.take(sizeof(BfQuantilesTally) * count), states_at = dev.take(sizeof(BfQuantileState) * ranks), pinned_bytes = dev.total,
+	             tables_at = dev.take(sizeof(uint32_t) * bf_quantiles_table_words(count, fraction_count)),
+	             prefixes_at = dev.take(sizeof(BfQuantilesPrefixes) * count);
+	if (!ensure_metrics_memory(d, pinned_bytes, dev.total)) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
+	uint32_t *device_tables = (uint32_t *)(device + tables_at);
+	const BfQuantilesTally *tallies = (const BfQuantilesTally *)(pinned + tallies_at);
+	const BfQuantileState  *states  = (const BfQuantileState *)(pinned + states_at);
+	std::memcpy(pinned + rows_at, rows.data(), sizeof(BfQuantilesRow) * count);
+	std::memcpy(pinned + fractions_at, fractions, sizeof(double) * fraction_count);
+	if (!timed_reduce(d, fractions_at + sizeof(double) * fraction_count, tallies_at, states_at - tallies_at + sizeof(BfQuantileState) * ranks, device_ms,
+	                  [&](hipStream_t s) {
+		return bf_launch_frame_quantiles(d.ring.ptr, (const BfQuantilesRow *)(device + rows_at), (const double *)(device + fractions_at), count, fraction_count,
+		                                 max_blocks, device_tables, (BfQuantilesPrefixes *)(device + prefixes_at), (BfQuantilesTally *)(device + tallies_at),
+		                                 (BfQuantileState *)(device + states_at), s);
+	}, [&](hipStream_t s) {
+		/* the first pass's tables as they are: [count][2048], straight to the caller's memory */
+		return histograms ? hipMemcpyAsync(histograms, device_tables + bf_quantiles_pass1_at(count), sizeof(uint32_t) * BF_QUANTILES_BINS1 * count,
+		                                   hipMemcpyDeviceToHost, s) : hipSuccess;
+	})) return false;
+
+	for (uint32_t n = 0; n < count; n++) {
+		BeamformerHipFrameQuantiles &m = frames[n];
+		describe_frame(m, boxed[n]);
+		m.first = n * fraction_count; m.stored = fraction_count;
+		m.voxels = tallies[n].voxels; m.non_finite = tallies[n].non_finite;
+		for (uint32_t k = 0; k < fraction_count; k++) {
+			const BfQuantileState &st = states[(size_t)n * fraction_count + k];
+			BeamformerHipFrameQuantile &q = quantiles[(size_t)n * fraction_count + k];
+			std::memset(&q, 0, sizeof(q));
+			q.fraction = fractions[k];
+			q.rank = st.rank; q.below = st.below; q.equal = st.equal;
+			std::memcpy(&q.value, &st.value_bits, sizeof(float));
+			q.magnitude = boxed[n].cplx ? sqrtf(q.value) : q.value;
+			q.threshold = m.voxels ? peak_threshold_of(q.value, boxed[n].cplx != 0) : 0.0f;      /* (no finite voxel: every number 0) */
+		}
+	}
 	return true;
 }
 

@@ -981,6 +981,27 @@ uint32_t beamformer_hip_find_peaks_last_frames(uint32_t count, const BeamformerH
 	return find_peaks_last_frames(count, region, thresholds, threshold_count, max_per_frame, frames, peaks, peak_count, device_ms);
 }
 
+uint32_t beamformer_hip_quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const double *fractions, uint32_t fraction_count,
+                                              BeamformerHipFrameQuantiles *frames, BeamformerHipFrameQuantile *quantiles, uint32_t *histograms,
+                                              float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(fraction_count >= 1 && fraction_count <= BEAMFORMER_HIP_MAX_QUANTILES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(fractions != nullptr && frames != nullptr && quantiles != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (uint32_t k = 0; k < fraction_count; k++)
+		if (!check(fractions[k] >= 0.0 && fractions[k] <= 1.0, BeamformerLibErrorKind_InvalidAccess)) return 0;      /* (a NaN fails both) */
+	return quantiles_last_frames(count, region, fractions, fraction_count, frames, quantiles, histograms, device_ms);
+}
+
+/* host only: the threshold of the peak calls that goes with a decision value (include/ogl_beamformer_hip.h has the rule) */
+uint32_t beamformer_hip_peak_threshold_of(float decision_value, uint32_t data_kind, float *threshold)
+{
+	if (!check(threshold != nullptr && std::isfinite(decision_value) && decision_value >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(data_kind == BeamformerDataKind_Float32 || data_kind == BeamformerDataKind_Float32Complex, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	*threshold = peak_threshold_of(decision_value, data_kind == BeamformerDataKind_Float32Complex);
+	return 1;
+}
+
 /* host only: one view a peak, a patch around it (include/ogl_beamformer_hip.h has the algebra) */
 uint32_t beamformer_hip_peaks_to_views(const float source_voxel_transform[16], const uint32_t source_points[3], const BeamformerHipFramePeak *peaks,
                                        uint32_t peak_count, const uint32_t patch_points[3], const float patch_extent_voxels[3], uint32_t use_offsets,

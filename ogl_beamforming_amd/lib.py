@@ -134,6 +134,9 @@ def _load():
                                                         C.POINTER(P.HipFramePeak), C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_peaks_to_views": (u32, [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(P.HipFramePeak), u32, C.POINTER(u32),
                                                 C.POINTER(C.c_float), u32, u32, C.POINTER(P.HipView)]),
+        "beamformer_hip_quantiles_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), u32, C.POINTER(P.HipFrameQuantiles),
+                                                       C.POINTER(P.HipFrameQuantile), C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_peak_threshold_of": (u32, [C.c_float, u32, C.POINTER(C.c_float)]),
         "beamformer_hip_localisation_map_reset": (u32, [C.POINTER(u32)]),
         "beamformer_hip_accumulate_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
                                                               C.POINTER(P.HipMapDeposits), C.POINTER(C.c_float)]),
@@ -567,6 +570,32 @@ def peaks_to_views(source_transform, source_points, peaks, patch_points, patch_e
                                                    (C.c_uint32 * 3)(*[int(v) for v in patch_points]),
                                                    (C.c_float * 3)(*[float(v) for v in patch_extent_voxels]), 1 if use_offsets else 0, int(tag), out))
     return list(out[: len(peaks)])
+
+
+def quantiles_last_frames(count, fractions, region=None, histograms=False):
+    """beamformer_hip_quantiles_last_frames: exact order statistics of the `count` newest frames, selected on the device.  fractions: up
+    to HIP_MAX_QUANTILES numbers in [0, 1], in any order; region None: every frame whole.  Returns (frames, quantiles, histograms,
+    device_ms): a ctypes array of `count` HipFrameQuantiles rows, a ctypes array of count * len(fractions) HipFrameQuantile records
+    (frame n's are quantiles[frames[n].first : frames[n].first + frames[n].stored], in the order of `fractions`), the coarse histograms
+    as a uint32 array (count, HIP_QUANTILE_BINS) -- None unless asked for -- and the device time of the launches."""
+    count = int(count)
+    values = np.ascontiguousarray(np.atleast_1d(np.asarray(fractions, np.float64)))
+    rows = (P.HipFrameQuantiles * max(1, count))()
+    records = (P.HipFrameQuantile * max(1, count * len(values)))()
+    tables = np.zeros((max(1, count), P.HIP_QUANTILE_BINS), np.uint32) if histograms else None
+    ms = C.c_float(0)
+    _check(library().beamformer_hip_quantiles_last_frames(count, None if region is None else C.byref(region),
+                                                          values.ctypes.data_as(C.POINTER(C.c_double)), len(values), rows, records,
+                                                          None if tables is None else tables.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(ms)))
+    return rows, records, tables, float(ms.value)
+
+
+def peak_threshold_of(decision_value, data_kind):
+    """beamformer_hip_peak_threshold_of (host only): the threshold of the peak calls for a quantile's `value` -- the value itself for
+    P.DataKind.Float32, the largest float32 T with fl(T * T) <= value for P.DataKind.Float32Complex."""
+    out = C.c_float(0)
+    _check(library().beamformer_hip_peak_threshold_of(float(decision_value), int(data_kind), C.byref(out)))
+    return float(out.value)
 
 
 _map_points = None      # the grid of the newest localisation_map_reset(): what localisation_map_copy() sizes its array by

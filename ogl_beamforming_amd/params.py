@@ -329,6 +329,23 @@ class HipFramePeaks(C.Structure):
                 ("threshold", C.c_float), ("first", C.c_uint32), ("stored", C.c_uint32), ("found", C.c_uint64), ("above_threshold", C.c_uint64)]
 
 
+HIP_MAX_QUANTILES = 16          # BEAMFORMER_HIP_MAX_QUANTILES
+HIP_QUANTILE_BINS = 2048        # BEAMFORMER_HIP_QUANTILE_BINS
+
+
+class HipFrameQuantile(C.Structure):
+    """BeamformerHipFrameQuantile: one order statistic of beamformer_hip_quantiles_last_frames (48 bytes, no padding)"""
+    _fields_ = [("fraction", C.c_double), ("rank", C.c_uint64), ("below", C.c_uint64), ("equal", C.c_uint64),
+                ("value", C.c_float), ("magnitude", C.c_float), ("threshold", C.c_float), ("reserved", C.c_uint32)]
+
+
+class HipFrameQuantiles(C.Structure):
+    """BeamformerHipFrameQuantiles: one frame's row of beamformer_hip_quantiles_last_frames (80 bytes, no padding)"""
+    _fields_ = [("frame_id", C.c_uint32), ("parameter_block", C.c_uint32), ("data_kind", C.c_uint32), ("image_plane_tag", C.c_uint32),
+                ("points", C.c_uint32 * 3), ("region_first", C.c_uint32 * 3), ("region_count", C.c_uint32 * 3),
+                ("first", C.c_uint32), ("stored", C.c_uint32), ("reserved", C.c_uint32), ("voxels", C.c_uint64), ("non_finite", C.c_uint64)]
+
+
 HIP_MAX_MAP_VOXELS = 1 << 28    # BEAMFORMER_HIP_MAX_MAP_VOXELS
 
 
