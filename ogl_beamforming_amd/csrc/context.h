@@ -275,6 +275,7 @@ bool push_readi_image(uint32_t block, const void *data, uint32_t frame_size, uin
 bool last_readi_image_info(BeamformerHipReadiImageInfo *out);
 void describe_readi_image_decision(const ReadiImageDecision &route, BeamformerHipReadiImageDescription *out);
 bool last_burst_info(BeamformerHipBurstInfo *out);
+void describe_burst_decision(const BurstDecision &route, BeamformerHipBurstDescription *out);
 bool push_views(uint32_t block, const void *data, uint32_t size, const BeamformerHipView *views, uint32_t view_count, bool data_on_device);
 bool last_views_info(BeamformerHipViewsInfo *out);
 bool push_burst_views(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const BeamformerHipView *views, uint32_t view_count,

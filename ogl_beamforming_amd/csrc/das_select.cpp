@@ -1,11 +1,17 @@
 /* das_select.cpp -- which DAS kernel a frame runs, and why (das_select.h).  Host arithmetic only.
  *
- * The rules, in the order they are tried (decide_das):
- *   general     das.hip            every family; forced by path 1; the fallback
- *   gather      das_separable.hip  row-column frames whose receive and transmit delays separate over the tile axes (plan_separable)
- *   staged      das_staged*.hip    ... and whose delay spread provably fits an LDS window (plan_staged), from kStagedMinTransmits
- *   hercules    das_hercules.hip   HERCULES family on array-aligned grids, volumes and view planes (plan_hercules)
- *   factored    das_factored.hip   any frame whose index is a receive term plus a transmit term (factored_applies)
+ * The rules, in the order decide_das tries them -- one function each; the first that takes the frame ends the ladder:
+ *   rule_zero       (no kernel)        a family or interpolation mode the shader leaves at zero: the frame is cleared
+ *   rule_separable  das_separable.hip  gather: row-column frames whose receive and transmit delays separate over the tile axes (plan_separable)
+ *                   das_staged*.hip    staged: ... and whose delay spread provably fits an LDS window (plan_staged), from kStagedMinTransmits;
+ *                                      its transmit tables global under the table cap, else in LDS, else back to the gather kernel
+ *   rule_hercules   das_hercules.hip   HERCULES family on array-aligned grids, volumes and view planes (plan_hercules)
+ *   rule_tile       das_tile.hip       cubic IQ frames the factored kernel would run, on grids fine enough that a 64 x 16 tile fits a staged window
+ *   rule_factored   das_factored.hip   any frame whose index is a receive term plus a transmit term (factored_applies)
+ *   rule_general    das.hip            every family; asked for by path 1; the fallback
+ * fill_das_args fills the arguments in front of them and chooses nothing.  A rule that declines writes why[] of its own path and of no
+ * other; a rule that takes the frame also speaks for the rules behind it, which are not tried.  A new kernel is a new rule_* at its
+ * place in the ladder: one line in decide_das and one here (tests/select_digest.cpp shows which decisions it moves).
  */
 #include "das_select.h"
 #include "host_math.h"
@@ -68,6 +74,8 @@ bool set_hook(const char *name, const char *value)
 /* ---------------------------------------------------------------- geometry rules */
 
 static uint32_t ceil_log2(uint32_t v) { uint32_t s = 0; while ((1u << s) < v) s++; return s; }
+/* blocks of 2^shift voxels (tiles, columns) that cover `extent` voxels of an axis */
+static uint32_t blocks_at(uint32_t extent, uint32_t shift) { return (extent + (1u << shift) - 1) >> shift; }
 
 /* Shape of the 2^tile_log2-voxel block of the DAS launch.  The axis along which the transducer-space
  * depth changes fastest gets extent 1: sample indices move ~2 samples per voxel along depth
@@ -182,7 +190,7 @@ static float tile_spread_sampled(const BfDasArgs &a, const std::vector<BfTransmi
 	};
 	uint32_t tiles[3][3], tile_count[3];
 	for (int k = 0; k < 3; k++) {
-		const uint32_t n = (ext[k] + (1u << shift[k]) - 1) >> shift[k];
+		const uint32_t n = blocks_at(ext[k], shift[k]);
 		tiles[k][0] = 0; tiles[k][1] = n / 2; tiles[k][2] = n - 1;
 		tile_count[k] = n >= 3 ? 3 : n == 2 ? 2 : 1;
 		if (n == 2) tiles[k][1] = 1;
@@ -305,10 +313,8 @@ static bool plan_separable(const BfDasArgs &a, const std::vector<BfTransmit> &tx
 	if (!best_waves) return false;
 	q.u_axis = (uint32_t)u_axis;
 	q.depth_major = 1u;
-	const uint32_t best_u = q.u_shift, best_v = q.v_shift;
-	uint32_t nu = a.size[u_axis], nv = a.size[1 - u_axis];
-	q.tiles[0] = (nu + (1u << best_u) - 1) >> best_u;
-	q.tiles[1] = (nv + (1u << best_v) - 1) >> best_v;
+	q.tiles[0] = blocks_at(a.size[u_axis], q.u_shift);
+	q.tiles[1] = blocks_at(a.size[1 - u_axis], q.v_shift);
 	q.tiles[2] = zcount;
 	q.walk_columns = 1u;          /* the gather kernel: one column (four together doubled its HBM-side bytes at config 4, 280 -> 520 GB, time equal) */
 	return true;
@@ -427,9 +433,8 @@ static bool plan_staged(const BfDasArgs &a, const std::vector<BfTransmit> &tx, c
 		             step_u, step_v, best_waves, best.u_shift, best.v_shift, best.window_samples, best.channel_chunk, best.lds_bytes, best.uniform);
 	if (!best_waves) return false;
 	q = best;
-	uint32_t nu = a.size[u_axis], nv = a.size[v_axis];
-	q.tiles[0] = (nu + (1u << q.u_shift) - 1) >> q.u_shift;
-	q.tiles[1] = (nv + (1u << q.v_shift) - 1) >> q.v_shift;
+	q.tiles[0] = blocks_at(a.size[u_axis], q.u_shift);
+	q.tiles[1] = blocks_at(a.size[v_axis], q.v_shift);
 	q.tiles[2] = zcount;
 	q.walk_columns = bf_walk_columns(q.tiles[0]);
 	return true;
@@ -530,18 +535,17 @@ static bool plan_hercules(const BfDasArgs &a, const std::vector<BfTransmit> &tx,
  * index to be a receive term plus a transmit term: RCA-family frames whose transmits all share
  * one receive orientation, and FORCES/UFORCES.  With fewer than three transmits per channel
  * chunk the receive factors are not amortised and the general kernel is as fast. */
-static bool factored_applies(const BfDasArgs &a, const std::vector<BfTransmit> &tx, uint32_t mode)
+static bool factored_applies(const BfDasArgs &a, const std::vector<BfTransmit> &tx, uint32_t request)
 {
-	if (mode == 1) return false;
+	if (request == BeamformerHipDasPath_General) return false;
 	int transmits = a.acquisition_count - (a.family == BF_DAS_FORCES && a.sparse ? 1 : 0);
-	if (transmits < 3 && mode != 4) return false;
+	if (transmits < 3 && request != BeamformerHipDasPath_PreferFactored) return false;
 	if (a.family == BF_DAS_FORCES) return true;
 	if (a.family != BF_DAS_RCA || tx.empty()) return false;
 	for (const BfTransmit &t : tx)
 		if ((t.flags & BF_RX_ROWS) != (tx[0].flags & BF_RX_ROWS)) return false;
 	return true;
 }
-
 
 /* ---------------------------------------------------------------- the decision */
 
@@ -569,12 +573,30 @@ std::vector<BfTransmit> build_transmit_table(const ParameterBlock &pb)
 	return table;
 }
 
-void decide_das(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx,
-                uint32_t zfirst, uint32_t zcount, uint32_t mode, DasDecision &out)
+/* voxel (unit cube) -> transducer coordinates of a family's frames: FORCES and READI plans carry the product already (plan_on_view) */
+static void voxel_to_xdc(int family, const ParameterBlock &pb, const Plan &plan, float *m)
 {
+	if (family == BF_DAS_FORCES || family == BF_DAS_READI) std::memcpy(m, plan.das_voxel_transform, sizeof(plan.das_voxel_transform));
+	else m4_mul(pb.parameters.xdc_transform, plan.das_voxel_transform, m);
+}
+
+/* What the rules of decide_das share: the frame they judge, the decision they fill, and what fill_das_args found on its way */
+struct Frame {
+	const ParameterBlock &pb; const Plan &plan; const std::vector<BfTransmit> &tx;
+	uint32_t mode, request;              /* the das path mode word; its kernel request (das_path_request) */
+	DasDecision &out;                    /* out.z_first, out.z_count: the planes of this launch */
+	float    to_xdc[16];                 /* voxel_to_xdc of the frame's family */
+	uint32_t ext[3];                     /* voxels of this launch per axis */
+	bool     factored;                   /* factored_applies */
+};
+
+/* out.a, out.general, out.das_input_bytes and out.depth_axis from block, plan and mode: every argument of the general kernel, its tile
+ * and channel split included.  It chooses no kernel: the rules behind it do, and change what their kernels read otherwise. */
+static void fill_das_args(Frame &f)
+{
+	const ParameterBlock &pb = f.pb; const Plan &plan = f.plan; DasDecision &out = f.out;
 	const BeamformerParameters &bp = pb.parameters;
-	out = DasDecision{};
-	out.z_first = zfirst; out.z_count = zcount; out.mode = mode; out.hooks_version = hooks().version;
+	const uint32_t zfirst = out.z_first, zcount = out.z_count, mode = f.mode;
 	const uint32_t C = plan.channels, A = plan.acquisitions, Sd = plan.das_samples;
 
 	BfDasArgs &a = out.a;
@@ -623,10 +645,10 @@ void decide_das(const ParameterBlock &pb, const Plan &plan, const std::vector<Bf
 	a.readi_group_count = bp.readi_group_count; a.readi_group = bp.readi_group;
 	out.das_input_bytes = (uint64_t)C * A * Sd * (plan.iq_pipeline ? 8u : 4u);
 
-	float to_xdc[16];
-	if (a.family == BF_DAS_FORCES || a.family == BF_DAS_READI) std::memcpy(to_xdc, plan.das_voxel_transform, sizeof(to_xdc));
-	else m4_mul(bp.xdc_transform, plan.das_voxel_transform, to_xdc);
-	const uint32_t ext[3] = {a.size[0], a.size[1], zcount};
+	float (&to_xdc)[16] = f.to_xdc;
+	uint32_t (&ext)[3] = f.ext;
+	voxel_to_xdc(a.family, pb, plan, to_xdc);
+	ext[0] = a.size[0]; ext[1] = a.size[1]; ext[2] = zcount;
 	/* Small frames (real-time 2-D imaging) do not fill 256 CUs with one thread per voxel:
 	 * split the channel loop over K waves of a block (wave-level partial sums, combined
 	 * through LDS in split order) until the launch has ~16 waves per CU (config 1, us per
@@ -634,166 +656,227 @@ void decide_das(const ParameterBlock &pb, const Plan &plan, const std::vector<Bf
 	const uint64_t voxel_waves = ((uint64_t)ext[0] * ext[1] * ext[2] + 63) / 64;
 	a.split_shift = 0;
 	const uint64_t split_target = 4096;
-	while (!(mode & 0x10) && a.split_shift < 4 && (voxel_waves << a.split_shift) < split_target && (C >> (a.split_shift + 1)) >= 4) a.split_shift++;
+	while (!(mode & BeamformerHipDasPath_NoChannelSplit) && a.split_shift < 4 && (voxel_waves << a.split_shift) < split_target && (C >> (a.split_shift + 1)) >= 4) a.split_shift++;
 	out.depth_axis = choose_tile(to_xdc, a.size, zcount, a.tile_shift, a.split_shift ? 6 : 8);
-	for (int k = 0; k < 3; k++) a.blocks[k] = (ext[k] + (1u << a.tile_shift[k]) - 1) >> a.tile_shift[k];
+	for (int k = 0; k < 3; k++) a.blocks[k] = blocks_at(ext[k], a.tile_shift[k]);
 	a.depth_major = tile_walk(out.depth_axis, zcount, a.blocks[1], a.band_rows);
 	out.general = a;
+}
 
-	if (a.family < 0 || a.interpolation < 0 || a.interpolation > 2) {
-		out.path = DasPath_Zero;
-		for (auto &w : out.why) w = "acquisition kind or interpolation mode the shader leaves at zero";
-		out.valid = true;
-		return;
-	}
-	const uint32_t das_mode = mode & 0xF;
-	const bool factored = factored_applies(a, tx, das_mode);
+/* ---- the rules.  Each returns whether it took the frame.  The reason a path declines with has ONE writer: its rule, or the *_declines
+ * function its rule shares with a rule in front that took the frame and speaks for it. */
+
+static const char *const kGeneralAsked = "das path 1: the general kernel was asked for";
+
+static bool take(Frame &f, int path)      /* a specialised kernel runs the frame */
+{
+	f.out.path = path;
+	f.out.why[DasPath_General] = "a specialised kernel applies";
+	return true;
+}
+
+static bool rule_zero(Frame &f)
+{
+	const BfDasArgs &a = f.out.a;
+	if (a.family >= 0 && a.interpolation >= 0 && a.interpolation <= 2) return false;
+	for (auto &w : f.out.why) w = "acquisition kind or interpolation mode the shader leaves at zero";
+	f.out.path = DasPath_Zero;
+	return true;
+}
+
+static void hercules_declines(Frame &f)
+{
+	f.out.why[DasPath_Hercules] = f.request == BeamformerHipDasPath_General ? kGeneralAsked
+	                            : f.out.a.family != BF_DAS_HERCULES ? "not a HERCULES-family acquisition"
+	                            : f.out.a.split_shift ? "a small frame: the general kernel's channel split fills the chip better"
+	                            : "grid narrower than 32 voxels along x / more than 25 % idle lanes, or no transducer axis is a function of the output row alone";
+}
+
+static void factored_declines(Frame &f)
+{
+	const int family = f.out.a.family;
+	f.out.why[DasPath_Factored] = f.request == BeamformerHipDasPath_General ? kGeneralAsked
+	                            : family == BF_DAS_HERCULES || family == BF_DAS_READI ? "the sample index is not a receive term plus a transmit term (HERCULES / READI)"
+	                            : "fewer than 3 transmits per channel chunk, or transmits with different receive orientations";
+}
+
+/* das_separable.hip (gather) and das_staged*.hip (staged): why[Gather] and why[Staged] */
+static bool rule_separable(Frame &f)
+{
+	DasDecision &out = f.out;
+	const BfDasArgs &a = out.a;
+	const Plan &plan = f.plan;
+	const float *xdc = f.pb.parameters.xdc_transform, *vox = plan.das_voxel_transform;
 	auto &why = out.why;
-	why[DasPath_Tile] = "only where the factored kernel would run (its block-staged form)";
-	if (das_mode == 1) {
-		why[DasPath_Gather] = why[DasPath_Staged] = why[DasPath_Hercules] = why[DasPath_Factored] = "das path 1: the general kernel was asked for";
+	if (f.request == BeamformerHipDasPath_General || f.request == BeamformerHipDasPath_PreferFactored) {
+		why[DasPath_Gather] = why[DasPath_Staged] = f.request == BeamformerHipDasPath_General ? kGeneralAsked : "das path 4: the factored kernel was asked for";
+		return false;
 	}
-	if (!factored && why[DasPath_Factored].empty())
-		why[DasPath_Factored] = a.family == BF_DAS_HERCULES || a.family == BF_DAS_READI ? "the sample index is not a receive term plus a transmit term (HERCULES / READI)"
-		                      : "fewer than 3 transmits per channel chunk, or transmits with different receive orientations";
-
+	BfSeparableArgs sep{};
+	if (!plan_separable(a, f.tx, xdc, vox, out.z_count, sep)) {
+		why[DasPath_Gather] = why[DasPath_Staged] = "not a row-column frame whose receive and transmit delays separate over the voxel x / y axes with depth on z";
+		return false;
+	}
 	/* The LDS-table kernels' hand-scheduled loop exists for linear interpolation; for cubic and nearest the gather kernel's
 	 * generic loop loses to the factored kernel (200 ch x 33 tx -> 129 x 333 x 21, cubic: 7.6 ms against 4.8 ms; nearest 2.6
 	 * against 2.1), which then goes first -- except for cubic IQ frames with enough transmits, which try the staged cubic kernel
 	 * (it declines, and the factored kernel runs, when the geometry is not separable or the spread does not fit a window). */
-	const bool want_staged  = das_mode == 3 || (das_mode == 0 && A >= kStagedMinTransmits);
-	const bool staged_cubic = a.interpolation == 2 && plan.iq_pipeline && want_staged;
-	bool tables_first = a.interpolation == 1 || das_mode == 3 || staged_cubic || !factored;
-	BfSeparableArgs sep{};
-	bool separable = false, staged = false;
-	if (das_mode != 1 && das_mode != 4) {
-		separable = plan_separable(a, tx, bp.xdc_transform, plan.das_voxel_transform, zcount, sep);
-		if (!separable) why[DasPath_Gather] = why[DasPath_Staged] = "not a row-column frame whose receive and transmit delays separate over the voxel x / y axes with depth on z";
-	} else if (das_mode == 4) {
-		why[DasPath_Gather] = why[DasPath_Staged] = "das path 4: the factored kernel was asked for";
-	}
-	BfSeparableArgs gather = sep;
-	if (separable) {
-		sep.zero_offset = gather.zero_offset = (uint32_t)out.das_input_bytes;       /* 64 zero bytes right behind the DAS input */
-		if (!want_staged) {
-			why[DasPath_Staged] = das_mode == 2 ? "das path 2: no LDS staging" : "fewer than 6 transmits per channel: two barriers and a window copy per channel are not amortised";
-		} else {
-			staged = plan_staged(a, tx, bp.xdc_transform, plan.das_voxel_transform, zcount, sep);
-			if (!staged) {
-				sep = gather;
-				why[DasPath_Staged] = a.interpolation == 0 ? "nearest interpolation" : (a.interpolation == 2 && !plan.iq_pipeline) ? "cubic interpolation of real samples"
-				                    : out.das_input_bytes >= (1ull << 31) ? "DAS input of 2 GiB or more (32-bit staging offsets)"
-				                    : "the delay spread of no tile shape fits a 32- / 64-sample window (or the windows do not fit the LDS)";
-			}
+	const bool prefer_staged = f.request == BeamformerHipDasPath_PreferLdsStaged;
+	const bool want_staged   = prefer_staged || (f.request == BeamformerHipDasPath_Automatic && plan.acquisitions >= kStagedMinTransmits);
+	const bool staged_cubic  = a.interpolation == 2 && plan.iq_pipeline && want_staged;
+	bool tables_first = a.interpolation == 1 || prefer_staged || staged_cubic || !f.factored;
+	sep.zero_offset = (uint32_t)out.das_input_bytes;                                /* 64 zero bytes right behind the DAS input */
+	const BfSeparableArgs gather = sep;
+	bool staged = false;
+	if (!want_staged) {
+		why[DasPath_Staged] = f.request == BeamformerHipDasPath_NoLdsStaging ? "das path 2: no LDS staging"
+		                    : "fewer than 6 transmits per channel: two barriers and a window copy per channel are not amortised";
+	} else {
+		staged = plan_staged(a, f.tx, xdc, vox, out.z_count, sep);
+		if (!staged) {
+			sep = gather;
+			why[DasPath_Staged] = a.interpolation == 0 ? "nearest interpolation" : (a.interpolation == 2 && !plan.iq_pipeline) ? "cubic interpolation of real samples"
+			                    : out.das_input_bytes >= (1ull << 31) ? "DAS input of 2 GiB or more (32-bit staging offsets)"
+			                    : "the delay spread of no tile shape fits a 32- / 64-sample window (or the windows do not fit the LDS)";
 		}
-		if (!staged && staged_cubic && das_mode != 3 && factored) tables_first = false;          /* cubic: the factored kernel, not the gather kernel's generic loop */
-		if (!staged && !tables_first) why[DasPath_Gather] = "cubic / nearest interpolation: its generic loop loses to the factored kernel";
 	}
-	if (separable && tables_first) {
-		out.sep = sep; out.sep_gather = gather;
-		out.path = staged ? DasPath_Staged : DasPath_Gather;
-		if (staged && sep.uniform) {
-			/* the wave-uniform transmit tables live in global memory (a few MB to 244 MB at 512^3 with 75 transmits); too big or no
-			 * memory at launch: the shape with the tables in LDS, planned here */
-			BfSeparableArgs again = gather;
-			out.has_lds_tables = plan_staged(a, tx, bp.xdc_transform, plan.das_voxel_transform, zcount, again, false);
-			if (out.has_lds_tables) out.sep_lds_tables = again;
-			const uint64_t table_bytes = (uint64_t)sep.table_stride * sep.tiles[1] * sep.tiles[2];
-			if (table_bytes > hooks().staged_table_cap) {
-				if (out.has_lds_tables) out.sep = again;
-				else { out.sep = gather; out.path = DasPath_Gather; why[DasPath_Staged] = "global transmit table too large and no LDS-table shape fits"; }
-			}
+	if (!staged && staged_cubic && !prefer_staged && f.factored) tables_first = false;      /* cubic: the factored kernel, not the gather kernel's generic loop */
+	if (!staged && !tables_first) {
+		why[DasPath_Gather] = "cubic / nearest interpolation: its generic loop loses to the factored kernel";
+		return false;
+	}
+	out.sep = sep; out.sep_gather = gather;
+	take(f, staged ? DasPath_Staged : DasPath_Gather);
+	if (staged && sep.uniform) {
+		/* the wave-uniform transmit tables live in global memory (a few MB to 244 MB at 512^3 with 75 transmits); too big or no
+		 * memory at launch: the shape with the tables in LDS, planned here */
+		BfSeparableArgs again = gather;
+		out.has_lds_tables = plan_staged(a, f.tx, xdc, vox, out.z_count, again, false);
+		if (out.has_lds_tables) out.sep_lds_tables = again;
+		const uint64_t table_bytes = (uint64_t)sep.table_stride * sep.tiles[1] * sep.tiles[2];
+		if (table_bytes > hooks().staged_table_cap) {
+			if (out.has_lds_tables) out.sep = again;
+			else { out.sep = gather; out.path = DasPath_Gather; why[DasPath_Staged] = "global transmit table too large and no LDS-table shape fits"; }
 		}
-		if (out.path == DasPath_Staged) why[DasPath_Gather] = "superseded by the LDS-staged kernel";
-		why[DasPath_Hercules] = "not a HERCULES-family acquisition";
-		if (why[DasPath_Factored].empty()) why[DasPath_Factored] = "superseded by the separable-delay kernels";
-		why[DasPath_General] = "a specialised kernel applies";
-		out.valid = true;
-		return;
 	}
-	if (das_mode != 1) {
-		BfHerculesArgs hq{};
-		if (plan_hercules(a, tx, bp.xdc_transform, plan.das_voxel_transform, zcount, das_mode == 6, hq)) {
-			hq.zero_offset = (uint32_t)out.das_input_bytes;
-			/* linear / cubic interpolation of IQ samples may read a prepared copy of the input ({sample, difference}, 16 bytes; cubic: the
-			 * four polynomial coefficients of every segment, 32 bytes; 32-bit byte offsets: under 4 GiB).  Not on coarse grids: the copy
-			 * is 2-4 x the RF, and where every lane reads its own cache line the memory system pays for the bytes -- the harness's view
-			 * plane with cubic polynomials: 28.1 ms, 158 GB from beyond L2 per frame; with the taps gathered from the RF itself 25.2 ms */
-			const uint64_t prepared = out.das_input_bytes * (a.interpolation == 2 ? 4u : 2u);
-			out.hercules_prepared = plan.iq_pipeline && (a.interpolation == 1 || a.interpolation == 2) && prepared + 64 < (1ull << 32) &&
-			                        lane_step_samples(to_xdc, a) < 1.0f;
-			out.herc = hq;
-			out.path = DasPath_Hercules;
-			why[DasPath_General] = "a specialised kernel applies";
-			if (why[DasPath_Factored].empty()) why[DasPath_Factored] = "the sample index is not a receive term plus a transmit term (HERCULES)";
-			out.valid = true;
-			return;
-		}
-		why[DasPath_Hercules] = a.family != BF_DAS_HERCULES ? "not a HERCULES-family acquisition"
-		                      : a.split_shift ? "a small frame: the general kernel's channel split fills the chip better"
-		                      : "grid narrower than 32 voxels along x / more than 25 % idle lanes, or no transducer axis is a function of the output row alone";
-	}
-	if (factored) {
-		a.zero_offset = (uint32_t)out.das_input_bytes;
-		/* das_tile.hip: cubic IQ frames on FINE grids -- there the four taps of a term are two gather instructions through L1 (32.6 clk
-		 * per CU per term: what config 2 waits for) and a 64 x 16-voxel block touches a window of a few dozen samples of every RF row, which
-		 * the block stages as cubic polynomials.  Tried when the estimated spread of such a tile fits a 64-sample window (the kernel measures
-		 * the real spread per block and chunk and falls back to the gather loop itself, so the estimate only decides whether it is worth
-		 * trying); flag 0x100 forces it wherever it is supported, 0x200 forbids it. */
-		{
-			bool tile_ok = plan.iq_pipeline && a.interpolation == 2 && Sd >= 8 && out.das_input_bytes < (1ull << 31) &&
-			               A - (a.family == BF_DAS_FORCES && a.sparse ? 1u : 0u) >= 4u;
-			/* tile: 64 voxels along x (a wave), the other 16 along the next axis that has voxels */
-			uint32_t shift[3] = {0, 0, 0}, left = 10;
-			for (int k = 0; k < 3 && left; k++) {
-				uint32_t room = ceil_log2(ext[k]), want = k == 0 ? 6u : left;
-				uint32_t give = room < want ? room : want;
-				give = give < left ? give : left;
-				shift[k] = give; left -= give;
-			}
-			for (int k = 0; k < 3 && left; k++) { uint32_t room = ceil_log2(ext[k]) - shift[k]; uint32_t give = room < left ? room : left; shift[k] += give; left -= give; }
-			/* (left > 0: a frame -- or a device's slab of it -- that does not even span one 1024-voxel tile) */
-			/* the derivative bound first (cheap, a true upper bound); where it does not already say "32 samples", what the kernel would measure
-			 * on the image's extreme tiles */
-			float spread = tile_spread_estimate(a, tx, to_xdc, plan.das_voxel_transform, shift);
-			if (left == 0 && spread == spread && spread > 26.f && spread < 400.f) {
-				const float sampled = tile_spread_sampled(a, tx, pb, plan.das_voxel_transform, ext, shift, zfirst);
-				if (sampled == sampled && sampled < spread) spread = sampled;
-			}
-			out.tile_spread = left == 0 ? spread : 0.f;
-			for (int k = 0; k < 3; k++) out.tile_estimate_shift[k] = shift[k];
-			/* frames small enough for the channel split (under 4096 voxel waves): one block per CU, so the block-staged kernel is
-			 * only worth it from about three quarters of the CUs (config 2 onto 448 x 448: 196 blocks, 0.66 ms against the split
-			 * kernel's 0.82; onto 384 x 384 the split kernel wins: profiles/r03_tile_threshold.json) */
-			uint64_t tile_blocks = 1;
-			for (int k = 0; k < 3; k++) tile_blocks *= (ext[k] + (1u << shift[k]) - 1) >> shift[k];
-			tile_ok = tile_ok && (!a.split_shift || tile_blocks >= 192u);
-			const bool forced = (mode & 0x100) != 0;
-			if (tile_ok && left == 0 && !(mode & 0x200) && (forced || (spread == spread && spread <= 58.f && lane_step_samples(to_xdc, a) < 1.0f))) {
-				a.split_shift = 0;
-				for (int k = 0; k < 3; k++) a.tile_shift[k] = shift[k];
-				for (int k = 0; k < 3; k++) a.blocks[k] = (ext[k] + (1u << a.tile_shift[k]) - 1) >> a.tile_shift[k];
-				a.depth_major = tile_walk(out.depth_axis, zcount, a.blocks[1], a.band_rows);
-				a.tile_window_shift = spread <= 26.f ? 5u : 6u;
-				out.path = DasPath_Tile;
-				why[DasPath_Factored] = "superseded by its block-staged form (das_tile.hip)";
-				why[DasPath_General] = "a specialised kernel applies";
-				out.valid = true;
-				return;
-			}
-			why[DasPath_Tile] = !plan.iq_pipeline || a.interpolation != 2 ? "cubic interpolation of IQ samples only"
-			                  : !tile_ok ? "small frame (channel split: fewer than 192 blocks), fewer than 4 transmits, or a DAS input of 2 GiB or more"
-			                  : (mode & 0x200) ? "das path flag 0x200: no block staging"
-			                  : "coarse grid or steep delays: a 64 x 16-voxel tile's estimated spread exceeds a 64-sample window";
-		}
-		out.path = DasPath_Factored;
-		why[DasPath_General] = "a specialised kernel applies";
-		out.valid = true;
-		return;
-	}
-	out.path = DasPath_General;
-	out.valid = true;
+	if (out.path == DasPath_Staged) why[DasPath_Gather] = "superseded by the LDS-staged kernel";
+	/* the rules behind it: a row-column frame is no HERCULES frame; the factored kernel would have run it, or says why not */
+	hercules_declines(f);
+	if (f.factored) why[DasPath_Factored] = "superseded by the separable-delay kernels";
+	return true;
 }
+
+/* das_hercules.hip: why[Hercules] */
+static bool rule_hercules(Frame &f)
+{
+	DasDecision &out = f.out;
+	const BfDasArgs &a = out.a;
+	BfHerculesArgs hq{};
+	if (f.request == BeamformerHipDasPath_General ||
+	    !plan_hercules(a, f.tx, f.pb.parameters.xdc_transform, f.plan.das_voxel_transform, out.z_count, f.request == BeamformerHipDasPath_HerculesAnyWidth, hq)) {
+		hercules_declines(f);
+		return false;
+	}
+	hq.zero_offset = (uint32_t)out.das_input_bytes;
+	/* linear / cubic interpolation of IQ samples may read a prepared copy of the input ({sample, difference}, 16 bytes; cubic: the
+	 * four polynomial coefficients of every segment, 32 bytes; 32-bit byte offsets: under 4 GiB).  Not on coarse grids: the copy
+	 * is 2-4 x the RF, and where every lane reads its own cache line the memory system pays for the bytes -- the harness's view
+	 * plane with cubic polynomials: 28.1 ms, 158 GB from beyond L2 per frame; with the taps gathered from the RF itself 25.2 ms */
+	const uint64_t prepared = out.das_input_bytes * (a.interpolation == 2 ? 4u : 2u);
+	out.hercules_prepared = f.plan.iq_pipeline && (a.interpolation == 1 || a.interpolation == 2) && prepared + 64 < (1ull << 32) &&
+	                        lane_step_samples(f.to_xdc, a) < 1.0f;
+	out.herc = hq;
+	/* (the factored rule behind it has said why not: f.factored is false for this family) */
+	return take(f, DasPath_Hercules);
+}
+
+/* das_tile.hip: why[Tile].  Cubic IQ frames on FINE grids -- there the four taps of a term are two gather instructions through L1 (32.6 clk
+ * per CU per term: what config 2 waits for) and a 64 x 16-voxel block touches a window of a few dozen samples of every RF row, which
+ * the block stages as cubic polynomials.  Tried when the estimated spread of such a tile fits a 64-sample window (the kernel measures
+ * the real spread per block and chunk and falls back to the gather loop itself, so the estimate only decides whether it is worth
+ * trying); flag 0x100 forces it wherever it is supported, 0x200 forbids it. */
+static bool rule_tile(Frame &f)
+{
+	if (!f.factored) return false;          /* (why[Tile] keeps what decide_das gave it) */
+	DasDecision &out = f.out;
+	BfDasArgs &a = out.a;
+	const Plan &plan = f.plan;
+	const uint32_t (&ext)[3] = f.ext;
+	bool tile_ok = plan.iq_pipeline && a.interpolation == 2 && plan.das_samples >= 8 && out.das_input_bytes < (1ull << 31) &&
+	               plan.acquisitions - (a.family == BF_DAS_FORCES && a.sparse ? 1u : 0u) >= 4u;
+	/* tile: 64 voxels along x (a wave), the other 16 along the next axis that has voxels */
+	uint32_t shift[3] = {0, 0, 0}, left = 10;
+	for (int k = 0; k < 3 && left; k++) {
+		uint32_t room = ceil_log2(ext[k]), want = k == 0 ? 6u : left;
+		uint32_t give = room < want ? room : want;
+		give = give < left ? give : left;
+		shift[k] = give; left -= give;
+	}
+	for (int k = 0; k < 3 && left; k++) { uint32_t room = ceil_log2(ext[k]) - shift[k]; uint32_t give = room < left ? room : left; shift[k] += give; left -= give; }
+	/* (left > 0: a frame -- or a device's slab of it -- that does not even span one 1024-voxel tile) */
+	/* the derivative bound first (cheap, a true upper bound); where it does not already say "32 samples", what the kernel would measure
+	 * on the image's extreme tiles */
+	float spread = tile_spread_estimate(a, f.tx, f.to_xdc, plan.das_voxel_transform, shift);
+	if (left == 0 && spread == spread && spread > 26.f && spread < 400.f) {
+		const float sampled = tile_spread_sampled(a, f.tx, f.pb, plan.das_voxel_transform, ext, shift, out.z_first);
+		if (sampled == sampled && sampled < spread) spread = sampled;
+	}
+	out.tile_spread = left == 0 ? spread : 0.f;
+	for (int k = 0; k < 3; k++) out.tile_estimate_shift[k] = shift[k];
+	/* frames small enough for the channel split (under 4096 voxel waves): one block per CU, so the block-staged kernel is
+	 * only worth it from about three quarters of the CUs (config 2 onto 448 x 448: 196 blocks, 0.66 ms against the split
+	 * kernel's 0.82; onto 384 x 384 the split kernel wins: profiles/r03_tile_threshold.json) */
+	uint64_t tile_blocks = 1;
+	for (int k = 0; k < 3; k++) tile_blocks *= blocks_at(ext[k], shift[k]);
+	tile_ok = tile_ok && (!a.split_shift || tile_blocks >= 192u);
+	const bool forced = (f.mode & BeamformerHipDasPath_TileStaging) != 0, forbidden = (f.mode & BeamformerHipDasPath_NoTileStaging) != 0;
+	if (!(tile_ok && left == 0 && !forbidden && (forced || (spread == spread && spread <= 58.f && lane_step_samples(f.to_xdc, a) < 1.0f)))) {
+		out.why[DasPath_Tile] = !plan.iq_pipeline || a.interpolation != 2 ? "cubic interpolation of IQ samples only"
+		                      : !tile_ok ? "small frame (channel split: fewer than 192 blocks), fewer than 4 transmits, or a DAS input of 2 GiB or more"
+		                      : forbidden ? "das path flag 0x200: no block staging"
+		                      : "coarse grid or steep delays: a 64 x 16-voxel tile's estimated spread exceeds a 64-sample window";
+		return false;
+	}
+	a.zero_offset = (uint32_t)out.das_input_bytes;
+	a.split_shift = 0;
+	for (int k = 0; k < 3; k++) a.tile_shift[k] = shift[k];
+	for (int k = 0; k < 3; k++) a.blocks[k] = blocks_at(ext[k], a.tile_shift[k]);
+	a.depth_major = tile_walk(out.depth_axis, out.z_count, a.blocks[1], a.band_rows);
+	a.tile_window_shift = spread <= 26.f ? 5u : 6u;
+	out.why[DasPath_Factored] = "superseded by its block-staged form (das_tile.hip)";      /* the rule behind it */
+	return take(f, DasPath_Tile);
+}
+
+/* das_factored.hip: why[Factored] (factored_declines: decide_das, before the ladder -- the separable rule orders itself by f.factored) */
+static bool rule_factored(Frame &f)
+{
+	if (!f.factored) return false;
+	f.out.a.zero_offset = (uint32_t)f.out.das_input_bytes;
+	return take(f, DasPath_Factored);
+}
+
+/* das.hip: the fallback declines nothing (why[General]: take) */
+static bool rule_general(Frame &f) { f.out.path = DasPath_General; return true; }
+
+void decide_das(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx,
+                uint32_t zfirst, uint32_t zcount, uint32_t mode, DasDecision &out)
+{
+	out = DasDecision{};
+	out.z_first = zfirst; out.z_count = zcount; out.mode = mode; out.hooks_version = hooks().version;
+	Frame f{pb, plan, tx, mode, das_path_request(mode), out, {}, {}, false};
+	fill_das_args(f);
+	out.valid = true;
+	if (rule_zero(f)) return;
+	out.why[DasPath_Tile] = "only where the factored kernel would run (its block-staged form)";      /* (a frame das_tile.hip takes keeps it) */
+	f.factored = factored_applies(out.a, tx, f.request);
+	if (!f.factored) factored_declines(f);
+	if (rule_separable(f)) return;
+	if (rule_hercules(f)) return;
+	if (rule_tile(f)) return;
+	if (rule_factored(f)) return;
+	rule_general(f);
+}
+
 
 /* ---------------------------------------------------------------- row ends (das_exact.h), host side */
 
@@ -915,6 +998,12 @@ Range plane_index_bounds(const BfDasArgs &a, const std::vector<BfTransmit> &tx, 
 
 } // namespace
 
+/* the mode the planes of a row-end fallback part are decided under: the caller's flags, block staging off, kernel request `request` */
+static uint32_t row_end_fallback_mode(uint32_t mode, uint32_t request)
+{
+	return (mode & ~kDasPathRequestMask & ~(uint32_t)BeamformerHipDasPath_TileStaging) | BeamformerHipDasPath_NoTileStaging | request;
+}
+
 void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx,
                       uint32_t zfirst, uint32_t zcount, uint32_t mode, std::vector<DasDecision> &parts)
 {
@@ -929,8 +1018,7 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 	 * READI keeps row_ends = 1, and so does nearest interpolation (which has no row-end evaluation: its flips are everywhere) */
 	if (a.family == BF_DAS_READI || a.family < 0 || a.interpolation == 0) return;
 	float to_xdc[16];
-	if (a.family == BF_DAS_FORCES) std::memcpy(to_xdc, plan.das_voxel_transform, sizeof(to_xdc));
-	else m4_mul(pb.parameters.xdc_transform, plan.das_voxel_transform, to_xdc);
+	voxel_to_xdc(a.family, pb, plan, to_xdc);
 	const bool   cubic = a.interpolation == 2;
 	const double reach = 2.0 * (double)a.edge_margin;        /* the kernels' indices and these bounds differ by far less than the margin */
 	const double lo = (cubic ? 1.0 : 0.0) + reach, hi = (double)(a.sample_count - (cubic ? 2 : 1)) - reach;
@@ -947,8 +1035,9 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 	if (whole.path != DasPath_Staged && whole.path != DasPath_Tile) return;    /* every other kernel evaluates such terms itself */
 	/* the kernel behind the staged one, with block staging off: the one asked for where it evaluates row ends itself (1: general,
 	 * 4: factored), else "automatic, never staged" (a request for the LDS-staged kernel, 3, included) */
-	const uint32_t asked = mode & 0xFu;
-	const uint32_t fallback_mode = (mode & ~0xFu & ~0x100u) | 0x200u | (asked == 1u || asked == 4u ? asked : 2u);
+	const uint32_t asked = das_path_request(mode);
+	const bool exact_asked = asked == BeamformerHipDasPath_General || asked == BeamformerHipDasPath_PreferFactored;
+	const uint32_t fallback_mode = row_end_fallback_mode(mode, exact_asked ? asked : (uint32_t)BeamformerHipDasPath_NoLdsStaging);
 	std::vector<DasDecision> cut;
 	uint32_t runs = 1;
 	for (uint32_t k = 1; k < zcount; k++) runs += clear[k] != clear[k - 1];
@@ -960,7 +1049,7 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 		decide_das(pb, plan, tx, zfirst + begin, k - begin, clear[begin] ? mode : fallback_mode, d);
 		if (!clear[begin] && (d.path == DasPath_Staged || d.path == DasPath_Tile)) {
 			d = DasDecision{};                                                        /* (cannot happen: the general kernel) */
-			decide_das(pb, plan, tx, zfirst + begin, k - begin, (mode & ~0xFu & ~0x100u) | 0x200u | 1u, d);
+			decide_das(pb, plan, tx, zfirst + begin, k - begin, row_end_fallback_mode(mode, BeamformerHipDasPath_General), d);
 		}
 		d.row_end_fallback = !clear[begin];
 		d.a.row_ends = d.general.row_ends = clear[begin] ? 0u : 1u;
@@ -969,29 +1058,64 @@ void decide_das_parts(const ParameterBlock &pb, const Plan &plan, const std::vec
 	parts.swap(cut);
 }
 
+/* ---------------------------------------------------------------- the multi-frame routes, on single-frame decisions */
+
+/* launches of the ingest and of every pre-DAS stage for frame_count RF frames of a plan: one, but the filters share a grid axis with
+ * the channels and take the frames in chunks of bf_stage_frame_chunk (stages.hip) */
+static uint32_t stage_launches(const Plan &plan, uint32_t frame_count)
+{
+	return (frame_count + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels);
+}
+
+/* single-frame DAS launches of a part list: one a part, none where the frame is only cleared */
+static uint32_t single_launches(const std::vector<DasDecision> &parts)
+{
+	uint32_t n = 0;
+	for (const DasDecision &d : parts) n += d.path != DasPath_Zero;
+	return n;
+}
+
+/* One item (a view, a variant) of a push whose fused kernel takes items that run the general kernel in one part.  True: a candidate
+ * for it; else the tally says what the item is instead -- cleared, cut by the row-end rule, on a faster kernel -- or nothing: another
+ * family, or `no_kernel` (the push's flag against its fused kernel). */
+struct ItemTally {
+	uint32_t zero = 0, cut = 0, faster = 0;
+	int      family = BF_DAS_RCA, faster_path = DasPath_General;      /* of the last item seen; of the last faster one */
+};
+static bool fused_candidate(const std::vector<DasDecision> &parts, bool no_kernel, ItemTally &t)
+{
+	const DasDecision &head = main_part(parts);
+	t.family = head.a.family;
+	if (head.path == DasPath_Zero) { t.zero++; return false; }
+	if (parts.size() != 1) { t.cut++; return false; }
+	if (head.path != DasPath_General) { t.faster++; t.faster_path = head.path; return false; }
+	return head.a.family == BF_DAS_RCA && !no_kernel;
+}
+
 void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const std::vector<DasDecision> &parts,
                   uint32_t zfirst, uint32_t zcount, uint32_t mode, uint32_t frame_count, BurstDecision &out, bool readi_sweep)
 {
 	out = BurstDecision{};
 	out.readi_sweep = readi_sweep;
-	const bool sweep = readi_sweep && main_part(parts).a.family == BF_DAS_READI;      /* the family the sweep kernel exists for */
+	out.stage_launches = stage_launches(plan, frame_count);
+	if (parts.empty()) {                                 /* no DAS stage in the plan, or no planes: nothing was decided */
+		out.min_frames = readi_sweep ? kReadiSweepMinFrames : kBurstMinFrames;
+		out.single_path = -1;
+		out.reason = "no DAS stage runs: the frames are cleared";
+		return;
+	}
+	const DasDecision &head = main_part(parts);
+	const bool sweep = readi_sweep && head.a.family == BF_DAS_READI;                  /* the family the sweep kernel exists for */
 	const uint32_t min_frames = sweep ? kReadiSweepMinFrames : kBurstMinFrames;
 	out.min_frames = min_frames;
-	const DasDecision &head = main_part(parts);
 	out.single_path = head.path;
-	/* the ingest and every pre-DAS stage take the burst in one launch; the filters share a grid axis with the channels and take it in
-	 * chunks of bf_stage_frame_chunk frames (stages.hip) */
-	const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
-	out.stage_launches = (frame_count + chunk - 1) / chunk;
-	uint32_t launches = 0;
-	for (const DasDecision &d : parts) launches += d.path != DasPath_Zero;
-	out.das_launches = launches * frame_count;
+	out.das_launches = single_launches(parts) * frame_count;
 	char text[160];
 	if (plan.das_index < 0 || zcount == 0) {
 		out.reason = "no DAS stage runs: the frames are cleared";
 	} else if (head.path == DasPath_Zero) {
 		out.reason = "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared";
-	} else if (mode & 0x400u) {
+	} else if (mode & BeamformerHipDasPath_NoBurstKernel) {
 		out.reason = "das path flag 0x400: the single-frame kernel once per frame was asked for";
 	} else if (head.a.family != BF_DAS_RCA && !sweep) {
 		out.reason = "the burst kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per frame";
@@ -1006,7 +1130,7 @@ void decide_burst(const ParameterBlock &pb, const Plan &plan, const std::vector<
 	} else {
 		/* the general kernel's tiles at one thread per voxel: the frames fill the chip, not a channel split */
 		DasDecision whole;
-		decide_das(pb, plan, tx, zfirst, zcount, mode | 0x10u, whole);
+		decide_das(pb, plan, tx, zfirst, zcount, mode | BeamformerHipDasPath_NoChannelSplit, whole);
 		out.a = whole.general;
 		out.a.row_ends = head.general.row_ends;
 		out.burst_kernel = true;
@@ -1035,12 +1159,11 @@ void decide_readi_image(const Plan &derived_plan, const std::vector<DasDecision>
 {
 	out = ReadiImageDecision{};
 	out.transmit_count = derived_plan.acquisitions;
-	const uint32_t chunk = bf_stage_frame_chunk(derived_plan.channels);
-	out.stage_launches = (frame_count + chunk - 1) / chunk;
+	out.stage_launches = stage_launches(derived_plan, frame_count);
 	if (parts.empty()) { out.reason = "no DAS stage runs: the frame is cleared"; return; }
 	const DasDecision &head = main_part(parts);
 	out.path = head.path;
-	for (const DasDecision &d : parts) out.das_launches += d.path != DasPath_Zero;
+	out.das_launches = single_launches(parts);
 	char text[160];
 	if (head.path == DasPath_Zero) {
 		out.reason = "interpolation mode the shader leaves at zero: the frame is cleared";
@@ -1073,31 +1196,28 @@ static void decide_views_for(const ParameterBlock &pb, const Plan &plan, const s
 	Plan on_view = plan;                         /* one copy; per view only the grid changes */
 	std::vector<BfViewRow> rows(view_count);
 	std::vector<uint8_t> eligible(view_count, 0);
-	uint32_t tiles = 0, candidates = 0, zero = 0, cut = 0, faster = 0;
-	int family = BF_DAS_RCA, faster_path = DasPath_General;
+	uint32_t tiles = 0, candidates = 0;
+	const bool no_kernel = (mode & BeamformerHipDasPath_NoViewsKernel) != 0;
+	ItemTally t;
 	for (uint32_t v = 0; v < view_count; v++) {
 		plan_on_view(pb, views[v], on_view);
 		const uint32_t zcount = on_view.output_points[2];
 		std::vector<DasDecision> &parts = out.parts[v];
 		decide_das_parts(pb, on_view, tx, 0, zcount, mode, parts);
-		const DasDecision &head = main_part(parts);
-		family = head.a.family;
-		for (const DasDecision &d : parts) out.das_launches += d.path != DasPath_Zero;
-		if (head.path == DasPath_Zero) { zero++; continue; }
-		if (parts.size() != 1) { cut++; continue; }
-		if (head.path != DasPath_General) { faster++; faster_path = head.path; continue; }
-		if (head.a.family != BF_DAS_RCA || (mode & 0x800u)) continue;
+		out.das_launches += single_launches(parts);
+		if (!fused_candidate(parts, no_kernel, t)) continue;
+		const DasDecision &head = parts[0];
 		/* the general kernel's tiles at one thread per voxel (decide_das under flag 0x10): the views fill the chip, not a channel split */
 		BfViewRow &r = rows[v];
 		r = BfViewRow{};
 		BfDasArgs g = head.general;
 		float to_xdc[16];
-		m4_mul(pb.parameters.xdc_transform, on_view.das_voxel_transform, to_xdc);
+		voxel_to_xdc(g.family, pb, on_view, to_xdc);
 		const int depth_axis = choose_tile(to_xdc, g.size, zcount, g.tile_shift, 8);
 		uint32_t view_tiles = 1;
 		for (int k = 0; k < 3; k++) {
 			r.size[k] = g.size[k]; r.tile_shift[k] = g.tile_shift[k];
-			r.blocks[k] = (g.size[k] + (1u << g.tile_shift[k]) - 1) >> g.tile_shift[k];
+			r.blocks[k] = blocks_at(g.size[k], g.tile_shift[k]);
 			view_tiles *= r.blocks[k];
 		}
 		r.depth_major = tile_walk(depth_axis, zcount, r.blocks[1], r.band_rows);
@@ -1125,15 +1245,15 @@ static void decide_views_for(const ParameterBlock &pb, const Plan &plan, const s
 		out.kernel_views = candidates; out.kernel_tiles = tiles; out.das_launches++;
 		out.a.split_shift = 0; out.a.row_ends = row_ends;
 		std::snprintf(text, sizeof(text), "RCA family on the general kernel: %u of %u views, %u tiles, in one launch of the views kernel", candidates, view_count, tiles);
-	} else if (zero == view_count) {
+	} else if (t.zero == view_count) {
 		std::snprintf(text, sizeof(text), "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared");
-	} else if (mode & 0x800u) {
+	} else if (no_kernel) {
 		std::snprintf(text, sizeof(text), "das path flag 0x800: each view's single-frame kernel on the shared DAS input was asked for");
-	} else if (family != BF_DAS_RCA) {
+	} else if (t.family != BF_DAS_RCA) {
 		std::snprintf(text, sizeof(text), "the views kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per view");
 	} else if (!candidates) {
-		if (faster) std::snprintf(text, sizeof(text), "single frames on these grids run the %s: it runs once per view on the shared DAS input", das_path_name(faster_path));
-		else if (cut) std::snprintf(text, sizeof(text), "the row-end rule cuts the views into parts run by different kernels: the single-frame launches once per view");
+		if (t.faster) std::snprintf(text, sizeof(text), "single frames on these grids run the %s: it runs once per view on the shared DAS input", das_path_name(t.faster_path));
+		else if (t.cut) std::snprintf(text, sizeof(text), "the row-end rule cuts the views into parts run by different kernels: the single-frame launches once per view");
 		else          std::snprintf(text, sizeof(text), "no view the views kernel can take: each runs its own launch");
 	} else {
 		std::snprintf(text, sizeof(text), "fewer than %u tiles in the eligible views: the single-frame general kernel once per view", kViewsMinTiles);
@@ -1144,7 +1264,7 @@ static void decide_views_for(const ParameterBlock &pb, const Plan &plan, const s
 void decide_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
                   uint32_t mode, ViewsDecision &out)
 {
-	decide_views_for(pb, plan, tx, views, view_count, mode, (mode & 0x1000u) != 0, out);
+	decide_views_for(pb, plan, tx, views, view_count, mode, (mode & BeamformerHipDasPath_PreferViewsKernel) != 0, out);
 }
 
 void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::vector<BfTransmit> &tx, const ViewGrid *views, uint32_t view_count,
@@ -1152,9 +1272,9 @@ void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::v
 {
 	out = BurstViewsDecision{};
 	const uint32_t N = frame_count;
-	const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
-	out.stage_launches = (N + chunk - 1) / chunk;
-	const bool fused_asked = N >= kBurstViewsMinFrames && !(mode & 0x400u) && !(mode & 0x800u);
+	out.stage_launches = stage_launches(plan, N);
+	const bool per_frame_asked = (mode & BeamformerHipDasPath_NoBurstKernel) != 0;
+	const bool fused_asked = N >= kBurstViewsMinFrames && !per_frame_asked && !(mode & BeamformerHipDasPath_NoViewsKernel);
 	/* rung 1: the views the views kernel is eligible for, whatever their tile count; rungs 2 and 3: decide_views' own rules (under 0x800 it
 	 * takes no view) */
 	if (fused_asked) decide_views_for(pb, plan, tx, views, view_count, mode, true, out.views);
@@ -1162,7 +1282,7 @@ void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::v
 	const ViewsDecision &v = out.views;
 	uint32_t own = 0;                        /* single-frame launches of the views no kernel takes, for one RF frame */
 	for (uint32_t k = 0; k < view_count; k++)
-		if (!v.taken[k]) for (const DasDecision &d : v.parts[k]) own += d.path != DasPath_Zero;
+		if (!v.taken[k]) own += single_launches(v.parts[k]);
 	char text[160];
 	if (fused_asked && v.kernel_views) {
 		out.rung = 1;
@@ -1179,7 +1299,7 @@ void decide_burst_views(const ParameterBlock &pb, const Plan &plan, const std::v
 		out.rung = 2;
 		out.frame_kernel_views = v.kernel_views;
 		out.das_launches = N * v.das_launches;
-		if (mode & 0x400u) std::snprintf(text, sizeof(text), "das path flag 0x400: the views kernel once per RF frame (%u of %u views) was asked for", v.kernel_views, view_count);
+		if (per_frame_asked) std::snprintf(text, sizeof(text), "das path flag 0x400: the views kernel once per RF frame (%u of %u views) was asked for", v.kernel_views, view_count);
 		else               std::snprintf(text, sizeof(text), "fewer than %u frames: the views kernel once per RF frame (%u of %u views)", kBurstViewsMinFrames, v.kernel_views, view_count);
 		out.reason = text;
 	} else {
@@ -1224,8 +1344,9 @@ void decide_variants(const ParameterBlock &pb, const Plan &plan, const std::vect
 	if (plan.das_index < 0) { out.reason = "no DAS stage runs: the frames are cleared"; return; }
 	const uint32_t zcount = plan.output_points[2];
 	std::vector<uint8_t> eligible(variant_count, 0);
-	uint32_t candidates = 0, zero = 0, cut = 0, faster = 0;
-	int family = BF_DAS_RCA, faster_path = DasPath_General;
+	uint32_t candidates = 0;
+	const bool no_kernel = (mode & BeamformerHipDasPath_NoVariantsKernel) != 0;
+	ItemTally t;
 	ParameterBlock derived_pb;
 	Plan derived_plan;
 	for (uint32_t v = 0; v < variant_count; v++) {
@@ -1236,27 +1357,22 @@ void decide_variants(const ParameterBlock &pb, const Plan &plan, const std::vect
 			derive_variant(pb, plan, variants[v], derived_pb, derived_plan);
 			decide_das_parts(derived_pb, derived_plan, tx, 0, zcount, mode, parts);
 		}
-		const DasDecision &head = main_part(parts);
-		family = head.a.family;
-		for (const DasDecision &d : parts) out.das_launches += d.path != DasPath_Zero;
-		if (head.path == DasPath_Zero) { zero++; continue; }
-		if (parts.size() != 1) { cut++; continue; }
-		if (head.path != DasPath_General) { faster++; faster_path = head.path; continue; }
-		if (head.a.family != BF_DAS_RCA || (mode & 0x4000u)) continue;
+		out.das_launches += single_launches(parts);
+		if (!fused_candidate(parts, no_kernel, t)) continue;
 		eligible[v] = 1; candidates++;
 	}
 	/* the general kernel's tiles at one thread per voxel (decide_das under flag 0x10), the same for every variant: the grid is the block's */
 	uint64_t tiles = 0;
 	if (candidates) {
 		DasDecision whole;
-		decide_das(pb, plan, tx, 0, zcount, mode | 0x10u, whole);
+		decide_das(pb, plan, tx, 0, zcount, mode | BeamformerHipDasPath_NoChannelSplit, whole);
 		out.a = whole.general;
 		if (out.a.depth_major == 3u) { out.a.depth_major = 2u; out.a.band_rows = 1; }      /* a view plane's balanced bands deal padded ids to the XCDs: here y fastest */
 		tiles = (uint64_t)out.a.blocks[0] * out.a.blocks[1] * out.a.blocks[2];
 		if (tiles == 0 || tiles > 0x7FFFFFFFu) candidates = 0;                            /* (grid x: such a grid runs its own launches) */
 	}
 	char text[160];
-	const bool take = candidates && (tiles * candidates >= kVariantsMinTiles || candidates >= kVariantsMinVariants || (mode & 0x8000u));
+	const bool take = candidates && (tiles * candidates >= kVariantsMinTiles || candidates >= kVariantsMinVariants || (mode & BeamformerHipDasPath_PreferVariantsKernel));
 	if (take) {
 		uint32_t row_ends = 0;
 		for (uint32_t v = 0; v < variant_count; v++) {
@@ -1279,15 +1395,15 @@ void decide_variants(const ParameterBlock &pb, const Plan &plan, const std::vect
 		out.a.split_shift = 0; out.a.row_ends = row_ends;
 		out.a.z_first = 0; out.a.z_count = out.a.size[2];
 		std::snprintf(text, sizeof(text), "RCA family on the general kernel: %u of %u variants x %u tiles in one launch of the variants kernel", candidates, variant_count, (uint32_t)tiles);
-	} else if (zero == variant_count) {
+	} else if (t.zero == variant_count) {
 		std::snprintf(text, sizeof(text), "acquisition kind or interpolation mode the shader leaves at zero: the frames are cleared");
-	} else if (mode & 0x4000u) {
+	} else if (no_kernel) {
 		std::snprintf(text, sizeof(text), "das path flag 0x4000: each variant's single-frame kernel on the shared DAS input was asked for");
-	} else if (family != BF_DAS_RCA) {
+	} else if (t.family != BF_DAS_RCA) {
 		std::snprintf(text, sizeof(text), "the variants kernel exists for the RCA family (Flash, RCA_TPW, RCA_VLS) only: this family runs its single-frame kernel once per variant");
 	} else if (!candidates) {
-		if (faster) std::snprintf(text, sizeof(text), "single frames on this grid run the %s: it runs once per variant on the shared DAS input", das_path_name(faster_path));
-		else if (cut) std::snprintf(text, sizeof(text), "the row-end rule cuts the frames into parts run by different kernels: the single-frame launches once per variant");
+		if (t.faster) std::snprintf(text, sizeof(text), "single frames on this grid run the %s: it runs once per variant on the shared DAS input", das_path_name(t.faster_path));
+		else if (t.cut) std::snprintf(text, sizeof(text), "the row-end rule cuts the frames into parts run by different kernels: the single-frame launches once per variant");
 		else          std::snprintf(text, sizeof(text), "no variant the variants kernel can take: each runs its own launch");
 	} else {
 		std::snprintf(text, sizeof(text), "fewer than %u eligible variants and fewer than %u variants x tiles: the single-frame general kernel once per variant",

@@ -1,11 +1,14 @@
-/* das_select.h -- which DAS kernel a frame runs, and why: ONE table of rules, host only (no HIP call), shared by the executor
- * (which launches what it says), beamformer_hip_describe_das (which reports it, also without a device) and the tests (which ask
- * instead of restating the rules).  Also the library's six diagnostic switches (beamformer_hip_set_hook). */
+/* das_select.h -- which DAS kernel a frame runs, and why: one ladder of rules, each a function, tried in the order decide_das lists them
+ * (das_select.cpp); host only (no HIP call), shared by the executor (which launches what it says), beamformer_hip_describe_das (which
+ * reports it, also without a device) and the tests (which ask instead of restating the rules).  On the single-frame decision stand the
+ * routes of the multi-frame pushes (decide_burst, decide_views, decide_burst_views, decide_variants, decide_readi_image).  Also the
+ * library's six diagnostic switches (beamformer_hip_set_hook). */
 #ifndef BF_DAS_SELECT_H
 #define BF_DAS_SELECT_H
 
 #include "planner.h"
 #include "bf_kernels.h"
+#include "../../include/ogl_beamformer_hip.h"
 #include <string>
 #include <vector>
 
@@ -20,6 +23,11 @@ enum DasPath {
 };
 const char *das_path_name(int path);      /* "LDS-staged kernel", ... */
 const char *das_kernel_name(int path);    /* "das_rca_staged_kernel", ... */
+
+/* The das path mode word (beamformer_hip_set_das_path): a kernel request in the low nibble (BeamformerHipDasPath_Automatic ..
+ * _HerculesAnyWidth), flags above it (BeamformerHipDasPath_NoChannelSplit ...). */
+constexpr uint32_t kDasPathRequestMask = 0xF;
+inline uint32_t das_path_request(uint32_t mode) { return mode & kDasPathRequestMask; }
 
 constexpr uint32_t kStagedMinTransmits = 6;      /* das_staged.hip by default from this many transmits per channel (tools/staged_threshold.py,
                                                     profiles/r03_staged_threshold.json: 1.29 of the gather kernel's time at 4 transmits, 1.01 at 6,

@@ -467,7 +467,7 @@ static bool launch_stage(PlanState *ps, const BeamformerParameters &bp, size_t i
 		BfDecodeArgs a{};
 		a.in = cur; a.out = out;
 		a.hadamard_t = (const float *)ps->hadamard_t.ptr;
-		a.hadamard_base_order = (c.das_path_mode & 0x20) ? 0 : plan.hadamard_base_order;
+		a.hadamard_base_order = (c.das_path_mode & BeamformerHipDasPath_DenseDecode) ? 0 : plan.hadamard_base_order;
 		a.hadamard_base = a.hadamard_base_order ? (const float *)ps->hadamard_base.ptr : nullptr;
 		a.transmit_count = A; a.channel_count = C; a.sample_count = Sd;
 		for (int k = 0; k < 3; k++) a.out_stride[k] = st.out_stride[k];
@@ -978,10 +978,10 @@ static bool walk_plan(uint32_t block, PlanState *ps, const Push &w)
 			d.das_input_stride = N > 1 ? cur_stride : 0; d.das_input_frames = N;
 			/* (Flag 0x2000: the step fails here, as a refused launch would -- the only way to such a push's tombstones that needs no
 			 * device fault: everything a caller can get wrong is refused before the ids are taken) */
-			if (w.fails_on_flag && (c.das_path_mode & 0x2000u)) return set_error(BeamformerLibErrorKind_InvalidAccess);
+			if (w.fails_on_flag && (c.das_path_mode & BeamformerHipDasPath_FailViewsDas)) return set_error(BeamformerLibErrorKind_InvalidAccess);
 			if (!jobs[0].parts) break;   /* more devices than planes: this device holds an empty slab of the frame */
 
-			/* ---- the jobs.  Which kernel, with which geometry: one table of rules (das_select.cpp), in each job's parts.  Usually ONE
+			/* ---- the jobs.  Which kernel, with which geometry: the ladder of rules of decide_das (das_select.cpp), in each job's parts.  Usually ONE
 			 * launch per job; where a term of the frame can reach an end of its RF row the z range is cut and the planes concerned go to
 			 * the kernel behind the staged one (decide_das_parts, das_exact.h). */
 			if (w.decode_groups && main_part(*jobs[0].parts).path != DasPath_Zero) {
@@ -1085,8 +1085,8 @@ static bool run_frame_stages(uint32_t block, const void *rf, int64_t rf_bytes, b
 	if (ingest_timed) segment(t, kStageIngest, d.stream);
 	else              record(t, 0, d.stream);
 
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	uint32_t zfirst, zcount;
+	shard_planes(pb, plan, zfirst, zcount);
 	if (c.device_count > 1) { zfirst = d.slab_first; zcount = d.slab_count; }   /* this device's z-slab (run_peers) */
 	/* no DAS in the pipeline: a single push's frame is the block's whole grid whatever its shard -- with several devices on the ingest
 	 * device, the others holding an empty slab of it (a burst's frames are the shard's planes) */
@@ -1462,8 +1462,7 @@ static bool begin_push(uint32_t block, bool whole_grid, PushGround &g)
 	g.ps = commit_block(block);
 	if (!g.ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
 	const Plan &plan = g.ps->plan;
-	g.z_first = 0; g.z_count = plan.output_points[2];
-	if (pb.shard_z_count) { g.z_first = pb.shard_z_first; g.z_count = pb.shard_z_count; }
+	shard_planes(pb, plan, g.z_first, g.z_count);
 	g.points[0] = plan.output_points[0]; g.points[1] = plan.output_points[1]; g.points[2] = g.z_count;
 	return true;
 }
@@ -1611,15 +1610,9 @@ bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t 
 	if (!begin_push(block, false, g)) return false;
 	const Plan &plan = g.ps->plan;
 
-	const std::vector<DasDecision> *parts = frame_das_parts(g.ps, pb, g.z_first, g.z_count);
+	const std::vector<DasDecision> no_parts, *parts = frame_das_parts(g.ps, pb, g.z_first, g.z_count);
 	BurstDecision route;
-	if (parts) decide_burst(pb, plan, g.ps->transmit_table, *parts, g.z_first, g.z_count, c.das_path_mode, N, route, groups != nullptr);
-	else {
-		const uint32_t chunk = bf_stage_frame_chunk(plan.channels);
-		route.readi_sweep = groups != nullptr;
-		if (groups) route.min_frames = kReadiSweepMinFrames;
-		route.stage_launches = (N + chunk - 1) / chunk; route.single_path = -1; route.reason = "no DAS stage runs: the frames are cleared";
-	}
+	decide_burst(pb, plan, g.ps->transmit_table, parts ? *parts : no_parts, g.z_first, g.z_count, c.das_path_mode, N, route, groups != nullptr);
 
 	std::vector<DasJob> jobs(N);
 	for (uint32_t k = 0; k < N; k++) {
@@ -1694,17 +1687,23 @@ static const PushRecord *newest_push(PushRecord::Kind kind, uint32_t &first_id, 
 static int abi_path(int path) { return path == DasPath_Zero ? -2 : path; }
 static int abi_path(const std::vector<DasDecision> &parts) { return parts.empty() ? -1 : abi_path(main_part(parts).path); }
 
+/* beamformer_hip_describe_burst, _describe_readi_sweep / _get_last_burst_info: a decision in the words of the C ABI */
+void describe_burst_decision(const BurstDecision &route, BeamformerHipBurstDescription *out)
+{
+	std::memset(out, 0, sizeof(*out));
+	out->burst_kernel = route.burst_kernel; out->single_path = abi_path(route.single_path);
+	out->frames_per_thread = route.frames_per_thread; out->das_launches = route.das_launches;
+	out->stage_launches = route.stage_launches; out->min_frames = route.min_frames;
+	std::snprintf(out->reason, sizeof(out->reason), "%s", route.reason.c_str());
+}
+
 /* beamformer_hip_get_last_burst_info */
 bool last_burst_info(BeamformerHipBurstInfo *out)
 {
 	std::memset(out, 0, sizeof(*out));
 	const PushRecord *r = newest_push(PushRecord::Burst, out->first_frame_id, out->frame_count, out->stage_count, out->stage_kind, out->stage_ms, out->burst_ms);
 	if (!r) return false;
-	const BurstDecision &b = r->burst;
-	out->route.burst_kernel = b.burst_kernel; out->route.single_path = abi_path(b.single_path);
-	out->route.frames_per_thread = b.frames_per_thread; out->route.das_launches = b.das_launches;
-	out->route.stage_launches = b.stage_launches; out->route.min_frames = b.min_frames;
-	std::snprintf(out->route.reason, sizeof(out->route.reason), "%s", b.reason.c_str());
+	describe_burst_decision(r->burst, &out->route);
 	return true;
 }
 

@@ -122,12 +122,18 @@ bool on_one_device(const char *what)
 	return set_error(BeamformerLibErrorKind_InvalidAccess);
 }
 
+/* the block's resolved plan, or InvalidComputeStage */
+bool resolved_plan(const ParameterBlock &pb, Plan &plan)
+{
+	std::string error;
+	return check(build_plan(pb, plan, error, ctx().hilbert_enabled), BeamformerLibErrorKind_InvalidComputeStage);
+}
+
 /* a multi-frame push's whole run of frames in the frame ring (context.h: frame_run_bytes; needs the block's plan, no device) */
 bool run_fits_the_ring(const ParameterBlock &pb, const BeamformerHipView *views, uint32_t count, uint32_t per_view = 1)
 {
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, ctx().hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(pb, plan)) return false;
 	const uint32_t points[3] = {plan.output_points[0], plan.output_points[1], pb.shard_z_count ? pb.shard_z_count : plan.output_points[2]};
 	uint64_t total;
 	return check(frame_run_bytes(points, views, count, plan.iq_pipeline ? 8u : 4u, frame_ring_bytes(), total, per_view), BeamformerLibErrorKind_FrameSizeOverflow);
@@ -231,8 +237,7 @@ bool resolve_readi_image(uint32_t slot, const uint32_t *groups, uint32_t frame_c
 		return set_error(BeamformerLibErrorKind_InvalidAccess);
 	}
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(pb, plan)) return false;
 	derive_readi_image(pb, plan, derived, derived_plan);
 	const uint64_t decoded = (uint64_t)plan.channels * transmits * plan.das_samples * (plan.iq_pipeline ? 8u : 4u);
 	return check(decoded < (1ull << 32), BeamformerLibErrorKind_RFDataSizeOverflow);
@@ -695,27 +700,15 @@ static uint32_t describe_burst_route(uint32_t parameter_slot, uint32_t frame_cou
 	Context &c = ctx();
 	const ParameterBlock &pb = c.blocks[parameter_slot];
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
-	std::memset(out, 0, sizeof(*out));
-	out->min_frames = readi_sweep ? kReadiSweepMinFrames : kBurstMinFrames;
-	out->frames_per_thread = 1; out->stage_launches = (frame_count + bf_stage_frame_chunk(plan.channels) - 1) / bf_stage_frame_chunk(plan.channels);
-	if (plan.das_index < 0) {
-		out->single_path = -1;
-		std::snprintf(out->reason, sizeof(out->reason), "no DAS stage runs: the frames are cleared");
-		return 1;
-	}
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	if (!resolved_plan(pb, plan)) return 0;
+	uint32_t zfirst, zcount;
+	shard_planes(pb, plan, zfirst, zcount);
 	const std::vector<BfTransmit> transmits = build_transmit_table(pb);
 	std::vector<DasDecision> parts;
-	decide_das_parts(pb, plan, transmits, zfirst, zcount, c.das_path_mode, parts);
-	BurstDecision b;
-	decide_burst(pb, plan, transmits, parts, zfirst, zcount, c.das_path_mode, frame_count, b, readi_sweep);
-	out->min_frames = b.min_frames;
-	out->burst_kernel = b.burst_kernel; out->single_path = b.single_path == DasPath_Zero ? -2 : b.single_path;
-	out->frames_per_thread = b.frames_per_thread; out->das_launches = b.das_launches; out->stage_launches = b.stage_launches;
-	std::snprintf(out->reason, sizeof(out->reason), "%s", b.reason.c_str());
+	if (plan.das_index >= 0) decide_das_parts(pb, plan, transmits, zfirst, zcount, c.das_path_mode, parts);
+	BurstDecision route;
+	decide_burst(pb, plan, transmits, parts, zfirst, zcount, c.das_path_mode, frame_count, route, readi_sweep);
+	describe_burst_decision(route, out);
 	return 1;
 }
 
@@ -777,8 +770,8 @@ uint32_t beamformer_hip_describe_readi_image(uint32_t parameter_slot, const uint
 	Plan derived_plan;
 	if (!resolve_readi_image(parameter_slot, readi_groups, frame_count, ids, derived, derived_plan)) return 0;
 	const ParameterBlock &pb = c.blocks[parameter_slot];
-	uint32_t zfirst = 0, zcount = derived_plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	uint32_t zfirst, zcount;
+	shard_planes(pb, derived_plan, zfirst, zcount);
 	std::vector<DasDecision> parts;
 	if (derived_plan.das_index >= 0 && zcount) decide_das_parts(derived, derived_plan, build_transmit_table(derived), zfirst, zcount, c.das_path_mode, parts);
 	ReadiImageDecision route;
@@ -817,8 +810,7 @@ uint32_t beamformer_hip_describe_views(uint32_t parameter_slot, const Beamformer
 	Context &c = ctx();
 	const ParameterBlock &pb = c.blocks[parameter_slot];
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(pb, plan)) return 0;
 	ViewsDecision route;
 	decide_views(pb, plan, build_transmit_table(pb), view_grids(views, view_count).data(), view_count, c.das_path_mode, route);
 	describe_views_decision(route, view_count, out);
@@ -850,8 +842,7 @@ uint32_t beamformer_hip_describe_burst_views(uint32_t parameter_slot, uint32_t f
 	Context &c = ctx();
 	const ParameterBlock &pb = c.blocks[parameter_slot];
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(pb, plan)) return 0;
 	BurstViewsDecision route;
 	decide_burst_views(pb, plan, build_transmit_table(pb), view_grids(views, view_count).data(), view_count, c.das_path_mode, frame_count, route);
 	describe_burst_views_decision(route, view_count, out);
@@ -883,8 +874,7 @@ uint32_t beamformer_hip_describe_variants(uint32_t parameter_slot, const Beamfor
 	Context &c = ctx();
 	const ParameterBlock &pb = c.blocks[parameter_slot];
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(pb, plan)) return 0;
 	VariantsDecision route;
 	decide_variants(pb, plan, build_transmit_table(pb), das_variants(variants, variant_count).data(), variant_count, c.das_path_mode, route);
 	describe_variants_decision(route, variant_count, out);
@@ -1362,8 +1352,7 @@ uint32_t beamformer_hip_describe_plan(uint32_t parameter_slot, BeamformerHipPlan
 {
 	if (!valid_parameter_block(parameter_slot)) return 0;
 	Plan plan;
-	std::string error;
-	if (!build_plan(ctx().blocks[parameter_slot], plan, error, ctx().hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(ctx().blocks[parameter_slot], plan)) return 0;
 	std::memset(out, 0, sizeof(*out));
 	out->stage_count = (uint32_t)plan.stages.size();
 	for (size_t i = 0; i < plan.stages.size() && i < BeamformerMaxComputeShaderStages; i++) {
@@ -1389,12 +1378,11 @@ uint32_t beamformer_hip_describe_das(uint32_t parameter_slot, BeamformerHipDasDe
 	Context &c = ctx();
 	const ParameterBlock &pb = c.blocks[parameter_slot];
 	Plan plan;
-	std::string error;
-	if (!build_plan(pb, plan, error, c.hilbert_enabled)) return check(false, BeamformerLibErrorKind_InvalidComputeStage);
+	if (!resolved_plan(pb, plan)) return 0;
 	std::memset(out, 0, sizeof(*out));
 	if (plan.das_index < 0) { out->path = -1; return 1; }
-	uint32_t zfirst = 0, zcount = plan.output_points[2];
-	if (pb.shard_z_count) { zfirst = pb.shard_z_first; zcount = pb.shard_z_count; }
+	uint32_t zfirst, zcount;
+	shard_planes(pb, plan, zfirst, zcount);
 	/* the decision for the planes that keep the first choice; where the row-end rule cuts the range (das_select.h: decide_das_parts) the
 	 * planes handed to the kernel behind it are counted in row_end_planes */
 	std::vector<DasDecision> parts;

@@ -65,6 +65,13 @@ struct Plan {
 	size_t   intermediate_bytes = 0;     /* largest inter-stage buffer */
 };
 
+/* The planes of the plan's grid a frame of the block covers: its output shard (beamformer_hip_set_output_shard), else all of them */
+inline void shard_planes(const ParameterBlock &pb, const Plan &plan, uint32_t &z_first, uint32_t &z_count)
+{
+	z_first = pb.shard_z_count ? pb.shard_z_first : 0u;
+	z_count = pb.shard_z_count ? pb.shard_z_count : plan.output_points[2];
+}
+
 /* Restates plan_compute_pipeline (beamformer_core.c:553-1013) for a backend that runs every
  * receive channel in one pass: the reference's 16-channel chunk becomes channel_count.
  * Returns false with `error` set when the pipeline cannot run. */
