@@ -753,6 +753,113 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_queue_localisation_map(float scale
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_map_placement(const float frame_voxel_transform[16], const uint32_t frame_points[3],
                                                             const float map_voxel_transform[16], const uint32_t map_points[3], double out[12]);
 
+/* ---- peak pairs: the peaks of consecutive frames of the frame ring linked ON THE DEVICE, and the track map (what ULM publishes besides
+ * the density of detections: the velocity map, and the rejection of detections that do not persist from one frame to the next --
+ * instead of downloading every peak list through beamformer_hip_find_peaks_last_frames and pairing on the host, every ensemble) ----
+ * The library holds ONE track map next to the localisation map, on the one device: points[0] x points[1] x points[2] uint32 counts and
+ * three int64 displacement sums a voxel, x fastest.
+ * DEFINITION (tests/tracks_ref.py restates it in numpy).  Every decision is integer or double arithmetic in a fixed operation order
+ * without fused multiply-add: numpy float64 and int64 reproduce every bit.
+ * PEAKS.  A frame's peaks are exactly the records of beamformer_hip_find_peaks_last_frames for the same frame, box, threshold and
+ * max_per_frame (the same mark, scan and emit passes run: one text computes both).  A peak's RANK is its place in that list, in
+ * ascending flat index; when found > max_per_frame the peaks kept are the first in flat order, as there.
+ * POSITION.  p_a = (double)index[a] + (double)offset[a], the offset dropped when use_offsets == 0; the map coordinate, per row r of the
+ * frame's row-major 3 x 4 double placement A (placement_count == 1: one for all frames), is
+ *     m_r = ((A[r][3] + A[r][0] * p_x) + A[r][1] * p_y) + A[r][2] * p_z
+ * -- the localisation map's formula, byte for byte.  A peak with any m_r not finite is UNPLACED: neither a query nor a candidate.
+ * DISTANCE.  For a in frame n (the older) and b in frame n + 1: d_r = m_r(b) - m_r(a) and d2 = ((d_x * d_x) + (d_y * d_y)) + (d_z * d_z);
+ * both directions use this one expression, so their bits agree.  b is WITHIN REACH of a when d2 <= R2, with
+ * R2 = (double)max_distance * (double)max_distance formed once on the host; max_distance is in map coordinates.
+ * CHOICE.  f(a) is the b within reach that minimises (d2, rank of b) lexicographically, g(b) the a within reach that minimises
+ * (d2, rank of a); either is "none" when nothing is within reach.  The minimum is lexicographic, so it does not depend on the order in
+ * which candidates are visited.
+ * PAIR.  (a, b) is a pair of frame pair n when f(a) = b and g(b) = a: a peak is in at most one pair per neighbouring frame.  The pairs
+ * of frame pair n are listed in ascending rank of a.  The lists depend on those two frames, the box, the thresholds, the placements and
+ * max_distance only: not on count, not on the other frames of the call, not on the call being repeated (the device emits them without
+ * atomics: a pair's place is a function of a).
+ * DEPOSIT (deposit != 0).  The midpoint c_r = 0.5 * (m_r(a) + m_r(b)), its bin b_r = floor(c_r + 0.5).  Inside the track map on all
+ * three axes: the bin's uint32 count goes up by 1 and its three int64 sums by q_r = (int64)floor(d_r * 1048576.0 + 0.5) (2^-20 of a map
+ * voxel; |d_r| <= 2^20, so q_r fits by far); both WRAP.  Otherwise the pair counts in `outside` and nothing is written.  The device
+ * adds with integer atomics, 32-bit for the count and 64-bit for the sums; integer additions commute, so the map's bytes are a function
+ * of the multiset of deposits since the reset.  There is still no floating-point atomic in the library.
+ * COST.  P_n x P_{n+1} distance evaluations a direction a frame pair, P the stored peaks of a frame: every peak of one frame is compared
+ * with every peak of the other.  There is no search window and no spatial structure: bound P with the threshold and max_per_frame. */
+#define BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS  (1u << 26)
+#define BEAMFORMER_HIP_MAX_PAIR_DISTANCE     1048576.0f
+#define BEAMFORMER_HIP_TRACK_MAP_COMPONENTS  5u
+/* points[3] (x fastest), each >= 1, product <= BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS: (re)allocates the library's one track map (28 bytes
+ * a voxel) and zeroes it on the current stream; its totals (BeamformerHipTrackMapInfo) start again.  points == NULL releases it (always
+ * succeeds).  beamformer_hip_shutdown releases it too.  Starts the device when none is in use yet.  The error kinds are those of
+ * beamformer_hip_localisation_map_reset: a zero extent: InvalidAccess; a product above the limit: BufferOverflow; memory that cannot be
+ * allocated: RFDataSizeOverflow (then there is no map); several devices: InvalidAccess. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_track_map_reset(const uint32_t points[3]);
+typedef struct {
+	uint32_t frame;                           /* n: the frame pair, a in frame n of the call, b in frame n + 1 */
+	uint32_t a, b;                            /* ranks: indices into the two frames' find_peaks lists */
+	uint32_t deposited;                       /* 1: added to the track map; 0: outside it, or deposit == 0 */
+	double   displacement[3];                 /* d_r, in map voxels per frame interval */
+	double   distance2;                       /* d2 */
+} BeamformerHipPeakPair;                      /* 48 bytes, no padding */
+typedef struct {
+	uint32_t frame_id[2];                     /* of frame n and frame n + 1, from their records */
+	float    threshold[2];                    /* the thresholds used for them */
+	uint32_t peaks[2];                        /* their stored peaks: min(found, max_per_frame) */
+	uint32_t unplaced[2];                     /* stored peaks with a map coordinate that is not finite */
+	uint32_t unpaired[2];                     /* placed peaks that are not in a pair of THIS frame pair */
+	uint32_t first, pairs;                    /* this frame pair's records: pairs[first .. first + pairs) */
+	uint32_t deposited, outside;              /* deposited + outside == pairs; both 0 when deposit == 0 */
+	uint64_t found[2];                        /* exactly beamformer_hip_find_peaks_last_frames' numbers */
+} BeamformerHipPeakPairs;                     /* 72 bytes, no padding */
+/* The peaks of the `count` newest frames (2 <= count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES), oldest first, linked frame to frame: count - 1
+ * frame pairs.  region, thresholds, threshold_count and max_per_frame are beamformer_hip_find_peaks_last_frames'; the frames may differ
+ * in grid and in data kind, which is why every frame may have its own placement (beamformer_hip_map_placement makes one).  rows
+ * [count - 1]: a row a frame pair.  pairs (may be NULL: no record comes back, the rows and the deposits are the same) has room for
+ * (count - 1) * max_per_frame records and comes back PACKED: frame pair n's records start at rows[n].first, *pair_count is their total.
+ * The call runs on the library's current stream behind the frames it reads, in THREE synchronises at the most: the rows and the
+ * placements go up, the mark pass and the scan run (csrc/frame_peaks.hip) and the per-frame counts come back (first synchronise); the
+ * buffers are grown to what was found; the emit pass, then csrc/frame_tracks.hip: place, nearest -- the hot kernel --, match, scan and
+ * emit, and the per-frame-pair numbers come back (second); exactly the pair records come back (third; skipped when pairs is NULL or
+ * there is no pair; frames without a peak skip the second too).  device_ms, when not NULL: the time between events around the launches,
+ * both parts added.
+ * Refusals, all decided before anything is enqueued or changed and leaving every output unwritten: count < 2 or >
+ * BEAMFORMER_HIP_MAX_SCORED_FRAMES, max_per_frame == 0 or > BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME: BufferOverflow; InvalidAccess: rows,
+ * pair_count, thresholds or placements NULL; threshold_count or placement_count neither 1 nor count; a threshold that is negative or not
+ * finite; a placement entry that is not finite; max_distance not finite, negative or above BEAMFORMER_HIP_MAX_PAIR_DISTANCE;
+ * deposit != 0 without a track map; and everything beamformer_hip_score_last_frames refuses -- no device in use yet, fewer than count
+ * frames queued, a tombstone, an overwritten record, reused storage, a region that does not fit inside every frame, several devices. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                     const float *thresholds, uint32_t threshold_count,
+                                                                     const double *placements /* [placement_count][12] */,
+                                                                     uint32_t placement_count /* 1 or count */, uint32_t use_offsets,
+                                                                     float max_distance, uint32_t max_per_frame, uint32_t deposit,
+                                                                     BeamformerHipPeakPairs *rows /* [count - 1] */,
+                                                                     BeamformerHipPeakPair *pairs /* may be NULL; room for (count - 1) * max_per_frame */,
+                                                                     uint32_t *pair_count, float *device_ms);
+typedef struct {
+	uint32_t points[3];
+	uint32_t calls;                           /* successful beamformer_hip_pair_peaks_last_frames calls with deposit != 0 since the reset */
+	uint64_t pairs, deposited, outside;       /* their totals: pairs == deposited + outside */
+} BeamformerHipTrackMapInfo;                  /* 40 bytes, no padding */
+/* The track map as it is, behind everything enqueued on the current stream (one synchronise): counts[out_count] and sums[3 * voxels]
+ * -- component r of voxel i at sums[r * voxels + i], voxels the map's own number, NOT out_count --; *info (may be NULL): the grid and
+ * the totals since the reset.  Errors as beamformer_hip_localisation_map_copy: counts or sums NULL, no map, no device, several devices:
+ * InvalidAccess; out_count below the map's voxel count: ExportSpaceOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info);
+/* Queues ONE Float32 frame of the track map's grid into the frame ring; the map itself is left unchanged.  With n a voxel's count and
+ * k = max(1, min_pairs): a voxel with n < k is 0.  Otherwise components 0..2 are the mean displacement along map axis r per frame
+ * interval, (float)(((double)sum_r / 1048576.0) / (double)n) * scale -- a double division, a double division, one conversion rounded to
+ * nearest, one float32 multiply --; component 3 is (float)n * scale; component 4 is the squared mean speed,
+ * (float)((mx * mx + my * my) + mz * mz) * scale with the three means in double: no square root takes part, so the frame is
+ * reproducible bit for bit.  The frame is placed, numbered, recorded and timed exactly as beamformer_hip_queue_localisation_map does
+ * its frame, the record of the newest multi-frame push and *frame_id (may be NULL) included; its record carries image_plane_tag and the
+ * parameter block of the newest frame of the most recent successful pair call with deposit.  One launch (csrc/frame_tracks.hip) on the
+ * current stream; the call does not synchronise unless device_ms is not NULL.
+ * Refusals, all decided before anything changes: component >= BEAMFORMER_HIP_TRACK_MAP_COMPONENTS, a scale that is not finite, no map,
+ * no device, several devices, no successful pair call with deposit since the reset: InvalidAccess; a frame of the map's size that does
+ * not fit the ring: FrameSizeOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag,
+                                                              uint32_t *frame_id, float *device_ms);
+
 /* ---- ensemble filter: a linear slow-time operator on the frames of the frame ring (the clutter filter between "ensemble" and "peaks"
  * of the ULM loop: tissue lies 30 - 60 dB above the microbubbles, so the peaks of an unfiltered ensemble are tissue speckle).  Two
  * device primitives and one host helper: the K x K slow-time Gram matrix of the K newest frames, reduced where they lie; a projector

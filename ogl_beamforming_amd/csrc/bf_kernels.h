@@ -412,6 +412,17 @@ typedef struct {
 	uint32_t points[3];          /* the map's grid, x fastest */
 	uint32_t use_offsets;        /* 0: a peak's position is its index */
 } BfMapArgs;
+/* peak pairs and the track map (frame_tracks.hip: beamformer_hip_pair_peaks_last_frames, beamformer_hip_queue_track_map) */
+#define BF_TRACK_MAX_VOXELS (1ull << 26)     /* = BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS */
+#define BF_TRACK_MAX_PEAKS  65536u           /* = BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME: records a frame */
+#define BF_TRACK_NONE       0xFFFFFFFFu      /* f(a) or g(b): nothing within reach */
+#define BF_TRACK_FIXED      1048576.0        /* the sums' fixed point: 2^20 a map voxel */
+#define BF_TRACK_COMPONENTS 5u               /* = BEAMFORMER_HIP_TRACK_MAP_COMPONENTS */
+typedef struct { uint32_t pairs, deposited, outside, reserved; } BfTrackTally;   /* a frame pair */
+typedef struct {
+	uint32_t points[3];          /* the track map's grid, x fastest (read with deposit only) */
+	uint32_t deposit;            /* 0: nothing is added to the map */
+} BfTrackArgs;
 
 /* ---- frame quantiles (frame_quantiles.hip: beamformer_hip_quantiles_last_frames) ---- */
 #define BF_QUANTILES_MAX       16u           /* = BEAMFORMER_HIP_MAX_QUANTILES: ranks a frame, and so distinct prefixes a digit pass */
@@ -665,6 +676,26 @@ hipError_t bf_launch_localisation_deposit(const void *ring, const BfPeaksRow *ro
                                          uint32_t max_blocks, const uint64_t *masks, const uint32_t *counts, uint32_t *offsets,
                                          const BfMapArgs *a, uint32_t *map, uint32_t *words, BfPeaksResult *tallies, hipStream_t s);
 hipError_t bf_launch_localisation_convert(const uint32_t *map, float *out, uint64_t voxels, float scale, hipStream_t s);
+/* frame_tracks.hip, behind bf_launch_frame_peaks_emit on the same stream: frame n's stored[n] records lie at list[firsts[n]] (firsts,
+ * stored: device memory, `frames` entries; max_stored, the most records of one frame, sizes the grids).  _place: one launch, three
+ * doubles a record into `positions` (NaN: unplaced) and the frames' unplaced counts (zeroed by the caller, integer atomics).  _nearest,
+ * the hot kernel: one launch, grid (blocks of 256 queries, frame pair, direction); forward[firsts[n] + a] = f(a) and
+ * backward[firsts[n + 1] + b] = g(b) of frame pair n, BF_TRACK_NONE for none; stored[n] x stored[n + 1] distance evaluations a
+ * direction.  _pair: three launches (match, scan, emit); block_firsts[frames - 1]: frame pair n's first block of ceil(stored[n] / 256),
+ * `blocks` in all; masks: four words a block; words, offsets: one a block; tallies[frames - 1], zeroed by the caller; pairs: NULL, or
+ * 48-byte records (BeamformerHipPeakPair's layout) PACKED, frame pair after frame pair, at most the sum of min(stored[n], stored[n + 1]);
+ * with t->deposit the track map: map_counts, the grid's voxels of uint32, map_sums, three times as many int64 (integer atomics).
+ * bf_launch_track_convert: one launch, a frame of the map's grid from counts and sums (min_pairs 0 counts as 1) */
+hipError_t bf_launch_tracks_place(const void *list, const double *placements, const uint32_t *firsts, const uint32_t *stored,
+                                  uint32_t frames, uint32_t max_stored, uint32_t use_offsets, double *positions, uint32_t *unplaced, hipStream_t s);
+hipError_t bf_launch_tracks_nearest(const double *positions, const uint32_t *firsts, const uint32_t *stored, uint32_t frames,
+                                    uint32_t max_stored, double r2, uint32_t *forward, uint32_t *backward, hipStream_t s);
+hipError_t bf_launch_tracks_pair(const double *positions, const uint32_t *firsts, const uint32_t *stored, const uint32_t *block_firsts,
+                                 uint32_t frames, uint32_t max_stored, uint32_t blocks, const uint32_t *forward, const uint32_t *backward,
+                                 uint64_t *masks, uint32_t *words, uint32_t *offsets, const BfTrackArgs *t, uint32_t *map_counts,
+                                 void *map_sums, void *pairs, BfTrackTally *tallies, hipStream_t s);
+hipError_t bf_launch_track_convert(const uint32_t *counts, const void *sums, float *out, uint64_t voxels, uint32_t component,
+                                   uint32_t min_pairs, float scale, hipStream_t s);
 /* ensemble.hip, the Gram matrix: three launches, no atomics -- the all-finite mask (a wave a word of 64 box voxels, every frame read
  * once), the partial pass (grid x the chunk, grid y the tile pair: BF_GRAM_TILE x BF_GRAM_TILE pairs of double2 a block) and the fold
  * (a thread a pair j <= k sums its chunks' partials in chunk order and stores both triangles; one more block counts the mask's bits).

@@ -82,7 +82,7 @@ struct PushRecord {
 	BeamformerHipVariantsDescription variants{};        /* Variants: its route */
 	uint32_t      rf_frames = 0;
 	float         decide_us = 0;
-	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames / convolve_last_frames / warp_last_frames / queue_localisation_map have queued behind the push: the push stays "the newest push" behind them */
+	uint32_t      mixed = 0;                  /* frames that mix_last_frames / autocorrelate_last_frames / convolve_last_frames / warp_last_frames / queue_localisation_map / queue_track_map have queued behind the push: the push stays "the newest push" behind them */
 };
 
 struct PlanState {
@@ -163,6 +163,16 @@ struct FrameOps {
 		uint64_t     deposited = 0, outside = 0;               /* ... and their totals */
 		void forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
 	} map;
+	struct TrackMap {
+		DeviceBuffer buffer;                                   /* the track map: `points` voxels of uint32 counts, then -- from sums_at() on -- three times as many int64 displacement sums (beamformer_hip_track_map_reset; frame_tracks.hip deposits into it); points[0] == 0: none */
+		uint32_t     points[3]{};
+		uint32_t     calls = 0, block = 0;                     /* ... successful pair calls with deposit since the reset, and the parameter block of the newest frame of the last one */
+		uint64_t     pairs = 0, deposited = 0, outside = 0;    /* ... and their totals */
+		uint64_t voxels() const { return (uint64_t)points[0] * points[1] * points[2]; }
+		size_t   sums_at() const { return round_up(sizeof(uint32_t) * voxels(), 64); }
+		void forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; pairs = deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
+	} tracks;
+	DeviceBuffer tracks_scratch;                               /* pair_peaks_last_frames: what is sized by the peaks the scan found -- positions, choices, the match pass's tables, the pair records (frame_tracks.hip); its small tables live in metrics_scratch and metrics_pinned, its peak records in peaks_list */
 	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
 	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
@@ -324,6 +334,13 @@ bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion
                                   float *device_ms);               /* arguments checked by the caller (lib_api.cpp) */
 bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info);
 bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);
+bool track_map_reset(const uint32_t points[3]);                    /* null: release; else checked by the caller */
+bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                            const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
+                            uint32_t max_per_frame, uint32_t deposit, BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs,
+                            uint32_t *pair_count, float *device_ms);   /* arguments checked by the caller (lib_api.cpp) */
+bool track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info);
+bool queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);
 bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms);
 bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerHipFrameRegion *regions, uint32_t region_count,
                            const uint32_t max_shift[3], BeamformerHipShiftCorrelation *table, BeamformerHipCorrelationInfo *info, float *device_ms);

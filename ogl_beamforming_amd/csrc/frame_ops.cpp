@@ -1,6 +1,7 @@
-/* frame_ops.cpp -- the calls that work on frames already in the ring: the reduce calls (score, find_peaks, accumulate_peaks, gram,
- * correlate), which read the newest frames where they lie and end in a synchronise, the localisation map, and the queued runs (mix,
- * autocorrelate, convolve, warp, queue_localisation_map), which write frames of their own behind the newest ones and do not.  Their
+/* frame_ops.cpp -- the calls that work on frames already in the ring: the reduce calls (score, find_peaks, accumulate_peaks, pair_peaks,
+ * gram, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
+ * the queued runs (mix, autocorrelate, convolve, warp, queue_localisation_map, queue_track_map), which write frames of their own behind
+ * the newest ones and do not.  Their
  * device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is executor.cpp's. */
 #include "context.h"
 #include <hip/hip_runtime.h>
@@ -11,7 +12,7 @@ namespace bf {
 
 void FrameOps::release()
 {
-	for (DeviceBuffer *b : {&metrics_scratch, &peaks_list, &map.buffer, &mix_table, &spatial_scratch}) b->release();
+	for (DeviceBuffer *b : {&metrics_scratch, &peaks_list, &map.buffer, &tracks.buffer, &tracks_scratch, &mix_table, &spatial_scratch}) b->release();
 	for (void *p : {metrics_pinned, mix_pinned}) if (p) (void)hipHostFree(p);
 	for (hipEvent_t e : {metrics_begin, metrics_end, peaks_begin, peaks_end, mix_copied, mix_begin, mix_end}) if (e) (void)hipEventDestroy(e);
 	*this = FrameOps{};
@@ -507,6 +508,201 @@ bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapIn
 	return true;
 }
 
+/* beamformer_hip_track_map_reset: the one track map of the one device -- counts, and the three displacement sums behind them --,
+ * (re)allocated and zeroed on the current stream; points null: released.  The extents arrive checked (lib_api.cpp). */
+bool track_map_reset(const uint32_t points[3])
+{
+	Context &c = ctx();
+	Device &d = c.devices[0];
+	FrameOps::TrackMap &map = d.ops.tracks;
+	if (!points) {
+		if (c.device_ready && map.buffer.ptr) {
+			bool ok = HIP_OK(hipSetDevice(d.device));
+			ok = ok && HIP_OK(hipStreamSynchronize(d.stream));          /* a deposit or a conversion may still be reading it */
+			if (!ok) (void)hipGetLastError();
+			map.buffer.release();
+		}
+		map.forget();
+		return true;
+	}
+	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	FrameOps::TrackMap shape;
+	for (int k = 0; k < 3; k++) shape.points[k] = points[k];
+	const size_t bytes = shape.sums_at() + 3 * sizeof(int64_t) * (size_t)shape.voxels();
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	/* (a buffer that has to grow is freed first: what is enqueued on it must have run) */
+	if (ok && map.buffer.ptr && map.buffer.size < bytes) ok = HIP_OK(hipStreamSynchronize(d.stream));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	map.forget();                       /* (also when the buffer cannot be had: no map then) */
+	if (!map.buffer.ensure(bytes)) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
+	for (int k = 0; k < 3; k++) map.points[k] = points[k];
+	if (!HIP_OK(hipMemsetAsync(map.buffer.ptr, 0, bytes, d.stream))) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	return true;
+}
+
+/* beamformer_hip_pair_peaks_last_frames: the peaks of the `count` newest frames linked frame to frame where they lie (frame_peaks.hip:
+ * the mark pass, the scan and the emit pass of find_peaks_last_frames; frame_tracks.hip: place, nearest, match, scan, emit).  The
+ * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Three synchronises
+ * at the most: the buffers are sized by what the scan found, and the copy of the records by the pairs that were made. */
+bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                            const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
+                            uint32_t max_per_frame, uint32_t deposit, BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs,
+                            uint32_t *pair_count, float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipPeakPair) == 48 && sizeof(BeamformerHipPeakPairs) == 72 && sizeof(BeamformerHipTrackMapInfo) == 40, "records without padding");
+	static_assert(BF_TRACK_MAX_VOXELS == BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS && BF_TRACK_MAX_PEAKS == BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME &&
+	              BF_TRACK_COMPONENTS == BEAMFORMER_HIP_TRACK_MAP_COMPONENTS, "one limit");
+	std::vector<BoxedFrame> boxed;
+	if (!newest_boxed_frames(count, region, boxed)) return false;
+	Device &d = ctx().devices[0];
+	FrameOps::TrackMap &map = d.ops.tracks;
+	if (deposit && (!map.buffer.ptr || !map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	PeaksRows table;
+	if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
+	const uint32_t links = count - 1u;
+
+	/* device: rows | placements | results | firsts | stored | block_firsts | unplaced | tallies | masks | counts | offsets; pinned: the
+	 * first eight (rows and placements go up in one copy, firsts, stored and block_firsts in a second, unplaced and tallies come back
+	 * in one: each group stays adjacent) */
+	Carve dev;
+	const size_t rows_at = dev.take(sizeof(BfPeaksRow) * count), placements_at = dev.take(sizeof(double) * 12 * count),
+	             results_at = dev.take(sizeof(BfPeaksResult) * count), firsts_at = dev.take(sizeof(uint32_t) * count),
+	             stored_at = dev.take(sizeof(uint32_t) * count), block_firsts_at = dev.take(sizeof(uint32_t) * links),
+	             unplaced_at = dev.take(sizeof(uint32_t) * count), tallies_at = dev.take(sizeof(BfTrackTally) * links), pinned_bytes = dev.total,
+	             masks_at = dev.take(sizeof(uint64_t) * table.waves), counts_at = dev.take(sizeof(uint32_t) * table.blocks),
+	             offsets_at = dev.take(sizeof(uint32_t) * table.blocks);
+	bool ok = ensure_metrics_memory(d, pinned_bytes, dev.total);
+	if (ok && !d.ops.peaks_begin) ok = HIP_OK(hipEventCreate(&d.ops.peaks_begin));
+	if (ok && !d.ops.peaks_end)   ok = HIP_OK(hipEventCreate(&d.ops.peaks_end));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
+	const BfPeaksRow *device_rows       = (const BfPeaksRow *)(device + rows_at);
+	const double     *device_placements = (const double *)(device + placements_at);
+	BfPeaksResult    *device_results    = (BfPeaksResult *)(device + results_at);
+	const uint32_t   *device_firsts     = (const uint32_t *)(device + firsts_at), *device_stored = (const uint32_t *)(device + stored_at),
+	                 *device_block_firsts = (const uint32_t *)(device + block_firsts_at);
+	uint32_t         *device_unplaced   = (uint32_t *)(device + unplaced_at);
+	BfTrackTally     *device_tallies    = (BfTrackTally *)(device + tallies_at);
+	uint64_t         *device_masks      = (uint64_t *)(device + masks_at);
+	uint32_t         *device_counts     = (uint32_t *)(device + counts_at);
+	uint32_t         *device_offsets    = (uint32_t *)(device + offsets_at);
+	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + results_at);
+	uint32_t *firsts = (uint32_t *)(pinned + firsts_at), *stored = (uint32_t *)(pinned + stored_at), *block_firsts = (uint32_t *)(pinned + block_firsts_at);
+	const uint32_t     *unplaced = (const uint32_t *)(pinned + unplaced_at);
+	const BfTrackTally *tallies  = (const BfTrackTally *)(pinned + tallies_at);
+	std::memcpy(pinned + rows_at, table.rows.data(), sizeof(BfPeaksRow) * count);
+	for (uint32_t n = 0; n < count; n++)
+		std::memcpy(pinned + placements_at + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
+	if (!timed_reduce(d, placements_at + sizeof(double) * 12 * count, results_at, sizeof(BfPeaksResult) * count, nullptr, [&](hipStream_t s) {   /* (its time: read below, with the rest's) */
+		return bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s);
+	})) return false;
+
+	/* what the scan found sizes everything from here on: the records, the positions, the choices, the match pass's blocks, the pairs */
+	uint32_t total = 0, max_stored = 0, blocks = 0;      /* (at most 1024 frames x 65536 records, 256 blocks a frame) */
+	uint64_t capacity = 0;
+	for (uint32_t n = 0; n < count; n++) {
+		stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
+		firsts[n] = total;
+		total += stored[n];
+		if (stored[n] > max_stored) max_stored = stored[n];
+		if (n) capacity += stored[n - 1] < stored[n] ? stored[n - 1] : stored[n];
+		if (n < links) { block_firsts[n] = blocks; blocks += (stored[n] + 255u) / 256u; }
+	}
+	std::memset(pinned + unplaced_at, 0, tallies_at - unplaced_at + sizeof(BfTrackTally) * links);
+	float ms = 0, rest_ms = 0;
+	const bool timed = HIP_OK(hipEventElapsedTime(&ms, d.ops.metrics_begin, d.ops.metrics_end));
+	const double reach = (double)max_distance, r2 = reach * reach;
+	uint64_t total_pairs = 0;
+	if (total) {
+		/* tracks_scratch: positions | forward | backward | masks | words | offsets | pairs */
+		Carve big;
+		const size_t positions_at = big.take(sizeof(double) * 3 * total), forward_at = big.take(sizeof(uint32_t) * total),
+		             backward_at = big.take(sizeof(uint32_t) * total), pair_masks_at = big.take(sizeof(uint64_t) * 4 * blocks),
+		             words_at = big.take(sizeof(uint32_t) * blocks), pair_offsets_at = big.take(sizeof(uint32_t) * blocks),
+		             pairs_at = big.take(pairs ? sizeof(BeamformerHipPeakPair) * (size_t)capacity : 0);
+		hipStream_t s = d.stream;
+		ok = d.ops.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak)) && d.ops.tracks_scratch.ensure(big.total);
+		if (ok) {
+			char *scratch = (char *)d.ops.tracks_scratch.ptr;
+			double   *positions = (double *)(scratch + positions_at);
+			uint32_t *forward = (uint32_t *)(scratch + forward_at), *backward = (uint32_t *)(scratch + backward_at);
+			void     *device_pairs = pairs && capacity ? scratch + pairs_at : nullptr;
+			BfTrackArgs a{};
+			for (int k = 0; k < 3; k++) a.points[k] = deposit ? map.points[k] : 0u;
+			a.deposit = deposit != 0;
+			ok &= HIP_OK(hipMemcpyAsync(device + firsts_at, firsts, unplaced_at - firsts_at, hipMemcpyHostToDevice, s));
+			ok &= HIP_OK(hipMemsetAsync(device_unplaced, 0, tallies_at - unplaced_at + sizeof(BfTrackTally) * links, s));
+			ok &= HIP_OK(hipEventRecord(d.ops.peaks_begin, s));
+			if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets,
+			                                                device_firsts, d.ops.peaks_list.ptr, s));
+			if (ok) ok &= HIP_OK(bf_launch_tracks_place(d.ops.peaks_list.ptr, device_placements, device_firsts, device_stored, count, max_stored,
+			                                            use_offsets != 0, positions, device_unplaced, s));
+			/* (no frame pair with peaks on both sides: nothing to choose from, every tally stays 0) */
+			if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_nearest(positions, device_firsts, device_stored, count, max_stored, r2, forward, backward, s));
+			if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_pair(positions, device_firsts, device_stored, device_block_firsts, count, max_stored, blocks,
+			                                                       forward, backward, (uint64_t *)(scratch + pair_masks_at), (uint32_t *)(scratch + words_at),
+			                                                       (uint32_t *)(scratch + pair_offsets_at), &a, (uint32_t *)map.buffer.ptr,
+			                                                       deposit ? (char *)map.buffer.ptr + map.sums_at() : nullptr, device_pairs, device_tallies, s));
+			ok &= HIP_OK(hipEventRecord(d.ops.peaks_end, s));
+			if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + unplaced_at, device_unplaced, tallies_at - unplaced_at + sizeof(BfTrackTally) * links,
+			                                    hipMemcpyDeviceToHost, s));
+			ok &= HIP_OK(hipStreamSynchronize(s));
+			for (uint32_t n = 0; n < links && ok; n++) total_pairs += tallies[n].pairs;
+			if (ok && pairs && total_pairs) {
+				ok = total_pairs <= capacity;                             /* (what the kernels promise: the copy below relies on it) */
+				ok = ok && HIP_OK(hipMemcpyAsync(pairs, device_pairs, (size_t)total_pairs * sizeof(BeamformerHipPeakPair), hipMemcpyDeviceToHost, s));
+				ok &= HIP_OK(hipStreamSynchronize(s));
+			}
+		}
+		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+		if (!HIP_OK(hipEventElapsedTime(&rest_ms, d.ops.peaks_begin, d.ops.peaks_end))) rest_ms = 0;
+	}
+	if (device_ms) *device_ms = timed ? ms + rest_ms : 0.0f;
+
+	uint32_t first = 0;
+	for (uint32_t n = 0; n < links; n++) {
+		BeamformerHipPeakPairs &m = rows[n];
+		const BfTrackTally &t = tallies[n];
+		std::memset(&m, 0, sizeof(m));
+		for (uint32_t k = 0; k < 2; k++) {
+			m.frame_id[k] = boxed[n + k].record->id;
+			m.threshold[k] = thresholds[threshold_count == 1 ? 0 : n + k];
+			m.peaks[k] = stored[n + k]; m.found[k] = results[n + k].found;
+			m.unplaced[k] = unplaced[n + k];
+			m.unpaired[k] = stored[n + k] - unplaced[n + k] - t.pairs;
+		}
+		m.first = first; m.pairs = t.pairs; m.deposited = t.deposited; m.outside = t.outside;
+		first += t.pairs;
+		if (deposit) { map.pairs += t.pairs; map.deposited += t.deposited; map.outside += t.outside; }
+	}
+	if (deposit) { map.calls++; map.block = boxed[count - 1].record->block; }
+	*pair_count = first;
+	return true;
+}
+
+/* beamformer_hip_track_map_copy: the counts and the sums as they are, behind everything enqueued on the current stream */
+bool track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info)
+{
+	Context &c = ctx();
+	Device &d = c.devices[0];
+	const FrameOps::TrackMap &map = d.ops.tracks;
+	if (!c.device_ready || c.device_count != 1 || !map.buffer.ptr || !map.points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	const uint64_t voxels = map.voxels();
+	if (out_count < voxels) return set_error(BeamformerLibErrorKind_ExportSpaceOverflow);
+	bool ok = HIP_OK(hipSetDevice(d.device));
+	ok = ok && HIP_OK(hipMemcpyAsync(counts, map.buffer.ptr, sizeof(uint32_t) * voxels, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipMemcpyAsync(sums, (const char *)map.buffer.ptr + map.sums_at(), 3 * sizeof(int64_t) * voxels, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
+	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	if (info) {
+		std::memset(info, 0, sizeof(*info));
+		for (int k = 0; k < 3; k++) info->points[k] = map.points[k];
+		info->calls = map.calls; info->pairs = map.pairs; info->deposited = map.deposited; info->outside = map.outside;
+	}
+	return true;
+}
+
 /* beamformer_hip_gram_last_frames: the slow-time Gram matrix of the `count` newest frames, reduced where they lie (ensemble.hip).
  * Everything that can refuse is decided before anything is enqueued. */
 bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms)
@@ -888,6 +1084,25 @@ bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *fra
 	const uint32_t *map = (const uint32_t *)d.ops.map.buffer.ptr;
 	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
 		[=](const QueuedRun &r) { return bf_launch_localisation_convert(map, (float *)((char *)r.ring + r.out_offset), r.elements, scale, r.s); });
+}
+
+/* beamformer_hip_queue_track_map: one component of the track map -- a mean displacement, the count, the squared mean speed --, queued
+ * as ONE Float32 frame of the map's grid (frame_tracks.hip: the conversion), through the skeleton of queue_localisation_map: a run of one
+ * frame without a source in the ring.  The record carries the block of the newest frame of the last pair call that deposited. */
+bool queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+{
+	Context &c = ctx();
+	Device &d = c.devices[0];
+	const FrameOps::TrackMap &map = d.ops.tracks;
+	if (!c.device_ready || c.device_count != 1 || !map.buffer.ptr || !map.points[0] || map.calls == 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	FrameRecord shape;
+	for (int k = 0; k < 3; k++) shape.points[k] = map.points[k];
+	shape.block = map.block;
+	RunTable t; t.shape = &shape;
+	const uint32_t *counts = (const uint32_t *)map.buffer.ptr;
+	const void *sums = (const char *)map.buffer.ptr + map.sums_at();
+	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
+		[=](const QueuedRun &r) { return bf_launch_track_convert(counts, sums, (float *)((char *)r.ring + r.out_offset), r.elements, component, min_pairs, scale, r.s); });
 }
 
 } // namespace bf

@@ -1,0 +1,327 @@
+/* frame_tracks.hip -- the peaks of consecutive frames of the frame ring linked into pairs (beamformer_hip_pair_peaks_last_frames: the
+ * velocity map of ULM and the rejection of detections that do not persist, without a peak list leaving the device), and the track map's
+ * frame (beamformer_hip_queue_track_map).
+ *
+ * DEFINITION (include/ogl_beamformer_hip.h has it for callers; tests/tracks_ref.py is its numpy restatement).  A frame's peaks are the
+ * records frame_peaks.hip emits (the caller runs its mark, scan and emit passes in front of these launches); a peak's rank is its place
+ * in that list.  Its position is p = index + offset (the offset dropped without offsets), its map coordinate
+ * m_r = ((A[r][3] + A[r][0] p_x) + A[r][1] p_y) + A[r][2] p_z under its frame's 3 x 4 double placement -- the localisation map's
+ * formula --; a peak with an m_r that is not finite is unplaced.  For a in frame n and b in frame n + 1: d_r = m_r(b) - m_r(a),
+ * d2 = ((d_x d_x) + (d_y d_y)) + (d_z d_z), b within reach of a when d2 <= R2.  f(a): the b within reach of the least (d2, rank of b);
+ * g(b): the a within reach of the least (d2, rank of a); (a, b) is a pair when f(a) = b and g(b) = a.  Everything is double arithmetic
+ * with contraction off, one expression for both directions.
+ *
+ * Place: grid y the frame, grid x blocks of 256 records; a lane reads its record's index and offset (32 bytes) and stores three doubles,
+ * NaN all three for an unplaced peak; a wave adds the count of its unplaced lanes to the frame's tally with one integer atomic.
+ * Nearest, the hot kernel: grid x blocks of 256 queries, grid y the frame pair, grid z the direction (0: f, the queries are frame n's;
+ * 1: g, they are frame n + 1's).  A lane owns one query.  The other frame's positions pass through LDS in tiles of 256, stored as three
+ * rows of doubles: in the inner loop every lane reads the same address, which LDS serves as a broadcast, without bank conflicts.  A
+ * candidate costs three subtractions, three products and two sums in double; the best (d2, rank) is kept with a strict < while the
+ * ranks ascend, which is the lexicographic minimum.  A NaN coordinate on either side makes d2 NaN, and every comparison with it false:
+ * an unplaced peak neither chooses nor is chosen.  Blocks past their frame's peak count leave at once.  The cost is P_n x P_{n+1}
+ * distance evaluations a direction a frame pair: there is no search window.
+ * Match, scan, emit: the pair list WITHOUT atomics.  Match: grid x blocks of 256 a, grid y the frame pair; the ballot of the lanes with
+ * f(a) = b and g(b) = a is the wave's 64-bit mask, their number a block's word, and a wave adds it to the frame pair's tally (an
+ * integer atomic on a counter: the count, not a place).  Scan: one block turns the words of all frame pairs, in frame-pair order,
+ * into exclusive offsets -- the lists are packed one behind the other, so one running offset serves them all.  Emit: the match pass's
+ * grid; a lane whose bit is set has the place offset + the pairs of the block's earlier waves + popcount(mask & lower lanes): a pair's
+ * place is a function of a.  It forms d_r and d2 again (the same expression: the same bits), and with `deposit` the midpoint
+ * c_r = 0.5 * (m_r(a) + m_r(b)), its bin floor(c_r + 0.5) and, inside the track map, adds 1 to the bin's uint32 count and
+ * q_r = (int64)floor(d_r * 2^20 + 0.5) to its three int64 sums: returnless integer atomics, which commute -- the map's bytes are a
+ * function of the multiset of deposits, and there is still no floating-point atomic in the library.  The ballots of the lanes inside and
+ * outside go to the frame pair's tally.
+ * Convert (beamformer_hip_queue_track_map): one coalesced pass, a voxel a lane. */
+#include <hip/hip_runtime.h>
+#include "bf_kernels.h"
+
+namespace {
+
+__device__ __forceinline__ bool is_finite(double a) { return (__double_as_longlong(a) & 0x7FF0000000000000ll) != 0x7FF0000000000000ll; }
+
+} // namespace
+
+__global__ __launch_bounds__(256) void tracks_place_kernel(const uint4 *__restrict__ list, const double *__restrict__ placements,
+                                                           const uint32_t *__restrict__ firsts, const uint32_t *__restrict__ stored,
+                                                           uint32_t use_offsets, double *__restrict__ positions, uint32_t *__restrict__ unplaced)
+{
+	#pragma clang fp contract(off)
+	const uint32_t frame = blockIdx.y, n = stored[frame], k = blockIdx.x * 256u + threadIdx.x;
+	if (blockIdx.x * 256u >= n) return;
+	bool lost = false;
+	if (k < n) {
+		const uint64_t at = (uint64_t)firsts[frame] + k;
+		const uint4 where = list[2u * at], fit = list[2u * at + 1u];
+		const double ox = use_offsets ? (double)__uint_as_float(fit.x) : 0.0, oy = use_offsets ? (double)__uint_as_float(fit.y) : 0.0,
+		             oz = use_offsets ? (double)__uint_as_float(fit.z) : 0.0;
+		const double px = (double)where.x + ox, py = (double)where.y + oy, pz = (double)where.z + oz;
+		const double *A = placements + 12u * frame;
+		double m[3];
+		bool placed = true;
+		#pragma unroll
+		for (int r = 0; r < 3; r++) {
+			m[r] = ((A[4 * r + 3] + A[4 * r] * px) + A[4 * r + 1] * py) + A[4 * r + 2] * pz;
+			placed &= is_finite(m[r]);
+		}
+		lost = !placed;
+		const double nan = __builtin_nan("");
+		#pragma unroll
+		for (int r = 0; r < 3; r++) positions[3u * at + r] = placed ? m[r] : nan;
+	}
+	const uint64_t lost_lanes = __ballot(lost);
+	if ((threadIdx.x & 63u) == 0 && lost_lanes) atomicAdd(unplaced + frame, (unsigned int)__popcll(lost_lanes));
+}
+
+__global__ __launch_bounds__(256) void tracks_nearest_kernel(const double *__restrict__ positions, const uint32_t *__restrict__ firsts,
+                                                             const uint32_t *__restrict__ stored, double r2, uint32_t *__restrict__ forward,
+                                                             uint32_t *__restrict__ backward)
+{
+	#pragma clang fp contract(off)
+	const uint32_t pair = blockIdx.y, back = blockIdx.z;
+	const uint32_t mine = pair + back, other = pair + 1u - back;             /* the queries' frame, the candidates' */
+	const uint32_t queries = stored[mine], candidates = stored[other];
+	if (blockIdx.x * 256u >= queries) return;
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	const bool live = k < queries;
+	const double *q = positions + 3ull * ((uint64_t)firsts[mine] + (live ? k : 0u));
+	const double qx = q[0], qy = q[1], qz = q[2];
+	const double *from = positions + 3ull * firsts[other];
+	__shared__ double tile[3][256];
+	double best = __builtin_inf();
+	uint32_t best_rank = BF_TRACK_NONE;
+	for (uint32_t base = 0; base < candidates; base += 256u) {
+		const uint32_t c = base + threadIdx.x, here = candidates - base < 256u ? candidates - base : 256u;
+		if (c < candidates) {
+			tile[0][threadIdx.x] = from[3ull * c];
+			tile[1][threadIdx.x] = from[3ull * c + 1u];
+			tile[2][threadIdx.x] = from[3ull * c + 2u];
+		}
+		__syncthreads();
+		#pragma unroll 4
+		for (uint32_t j = 0; j < here; j++) {
+			/* d = m(b) - m(a) on the way forward and its negative on the way back: a difference and its negative round alike, and a
+			 * product does not see the sign, so d2 has the bits of the one expression in both directions */
+			const double dx = tile[0][j] - qx, dy = tile[1][j] - qy, dz = tile[2][j] - qz;
+			const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+			if (d2 <= r2 && d2 < best) { best = d2; best_rank = base + j; }
+		}
+		__syncthreads();
+	}
+	if (live) (back ? backward : forward)[(uint64_t)firsts[mine] + k] = best_rank;
+}
+
+namespace {
+
+/* is lane a's peak half of a pair, and with which b */
+__device__ __forceinline__ bool mutual(const uint32_t *forward, const uint32_t *backward, uint32_t first_a, uint32_t first_b, uint32_t a, uint32_t &b)
+{
+	b = forward[(uint64_t)first_a + a];
+	return b != BF_TRACK_NONE && backward[(uint64_t)first_b + b] == a;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(256) void tracks_match_kernel(const uint32_t *__restrict__ firsts, const uint32_t *__restrict__ stored,
+                                                           const uint32_t *__restrict__ block_firsts, const uint32_t *__restrict__ forward,
+                                                           const uint32_t *__restrict__ backward, uint64_t *__restrict__ masks,
+                                                           uint32_t *__restrict__ words, BfTrackTally *__restrict__ tallies)
+{
+	const uint32_t pair = blockIdx.y, n = stored[pair], a = blockIdx.x * 256u + threadIdx.x;
+	if (blockIdx.x * 256u >= n) return;
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, block = block_firsts[pair] + blockIdx.x;
+	__shared__ uint32_t counts[4];
+	uint32_t b = 0;
+	const uint64_t mask = __ballot(a < n && mutual(forward, backward, firsts[pair], firsts[pair + 1u], a, b));
+	if (lane == 0) {
+		masks[4ull * block + wave] = mask;
+		counts[wave] = (uint32_t)__popcll(mask);
+		if (mask) atomicAdd(&tallies[pair].pairs, (unsigned int)__popcll(mask));
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) words[block] = counts[0] + counts[1] + counts[2] + counts[3];
+}
+
+/* one block: words[blocks] (each at most 256, at most 2^26 in all) -> their exclusive offsets */
+__global__ __launch_bounds__(1024) void tracks_scan_kernel(const uint32_t *__restrict__ words, uint32_t blocks, uint32_t *__restrict__ offsets)
+{
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	__shared__ uint32_t wave_sums[16];
+	uint32_t running = 0;
+	for (uint32_t base = 0; base < blocks; base += 1024u) {
+		const uint32_t k = base + threadIdx.x, mine = k < blocks ? words[k] : 0u;
+		uint32_t upto = mine;
+		for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(upto, off, 64); if (lane >= (uint32_t)off) upto += v; }
+		if (lane == 63) wave_sums[wave] = upto;
+		__syncthreads();
+		uint32_t before = 0, all = 0;
+		for (uint32_t j = 0; j < 16; j++) {
+			const uint32_t v = wave_sums[j];
+			if (j < wave) before += v;
+			all += v;
+		}
+		if (k < blocks) offsets[k] = running + before + (upto - mine);
+		running += all;
+		__syncthreads();
+	}
+}
+
+__global__ __launch_bounds__(256) void tracks_emit_kernel(const double *__restrict__ positions, const uint32_t *__restrict__ firsts,
+                                                          const uint32_t *__restrict__ stored, const uint32_t *__restrict__ block_firsts,
+                                                          const uint32_t *__restrict__ forward, const uint64_t *__restrict__ masks,
+                                                          const uint32_t *__restrict__ words, const uint32_t *__restrict__ offsets, BfTrackArgs t,
+                                                          uint32_t *__restrict__ map_counts, unsigned long long *__restrict__ map_sums,
+                                                          uint4 *__restrict__ pairs, BfTrackTally *__restrict__ tallies)
+{
+	#pragma clang fp contract(off)
+	const uint32_t pair = blockIdx.y, n = stored[pair];
+	if (blockIdx.x * 256u >= n) return;
+	const uint32_t block = block_firsts[pair] + blockIdx.x;
+	if (words[block] == 0) return;
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, a = blockIdx.x * 256u + threadIdx.x;
+	uint32_t place = offsets[block];
+	for (uint32_t k = 0; k < wave; k++) place += (uint32_t)__popcll(masks[4ull * block + k]);
+	const uint64_t mask = masks[4ull * block + wave];
+	if (!mask) return;                                                   /* (the whole wave: the ballots below are the wave's own) */
+	const bool mine = mask >> lane & 1ull;
+	bool inside = false;
+	if (mine) {
+		place += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+		const uint32_t b = forward[(uint64_t)firsts[pair] + a];
+		const double *ma = positions + 3ull * ((uint64_t)firsts[pair] + a), *mb = positions + 3ull * ((uint64_t)firsts[pair + 1u] + b);
+		double d[3], c[3];
+		#pragma unroll
+		for (int r = 0; r < 3; r++) { const double u = ma[r], v = mb[r]; d[r] = v - u; c[r] = 0.5 * (u + v); }
+		const double d2 = ((d[0] * d[0]) + (d[1] * d[1])) + (d[2] * d[2]);
+		if (t.deposit) {
+			uint32_t bin[3];
+			inside = true;
+			#pragma unroll
+			for (int r = 0; r < 3; r++) {
+				const double at = __builtin_floor(c[r] + 0.5);
+				const bool in = at >= 0.0 && at < (double)t.points[r];
+				bin[r] = in ? (uint32_t)at : 0u;
+				inside &= in;
+			}
+			if (inside) {
+				/* integer adds whose results nobody reads; |d_r| <= 2^20 (d2 <= R2 <= 2^40): q_r fits easily */
+				const uint64_t voxels = (uint64_t)t.points[0] * t.points[1] * t.points[2];
+				const uint64_t at = ((uint64_t)bin[2] * t.points[1] + bin[1]) * t.points[0] + bin[0];
+				atomicAdd(map_counts + at, 1u);
+				#pragma unroll
+				for (int r = 0; r < 3; r++) {
+					const long long q = (long long)__builtin_floor(d[r] * BF_TRACK_FIXED + 0.5);
+					atomicAdd(map_sums + r * voxels + at, (unsigned long long)q);
+				}
+			}
+		}
+		if (pairs) {
+			uint4 *record = pairs + 3ull * place;
+			const uint64_t dx = (uint64_t)__double_as_longlong(d[0]), dy = (uint64_t)__double_as_longlong(d[1]),
+			               dz = (uint64_t)__double_as_longlong(d[2]), dd = (uint64_t)__double_as_longlong(d2);
+			record[0] = make_uint4(pair, a, b, inside ? 1u : 0u);
+			record[1] = make_uint4((uint32_t)dx, (uint32_t)(dx >> 32), (uint32_t)dy, (uint32_t)(dy >> 32));
+			record[2] = make_uint4((uint32_t)dz, (uint32_t)(dz >> 32), (uint32_t)dd, (uint32_t)(dd >> 32));
+		}
+	}
+	if (t.deposit) {
+		const uint64_t in = __ballot(inside), out = __ballot(mine && !inside);
+		if (lane == 0) {
+			if (in)  atomicAdd(&tallies[pair].deposited, (unsigned int)__popcll(in));
+			if (out) atomicAdd(&tallies[pair].outside, (unsigned int)__popcll(out));
+		}
+	}
+}
+
+/* Convert: n = counts[i]; below max(1, min_pairs): 0.  Components 0..2: (float)(((double)sum_r / 2^20) / (double)n) * scale -- two double
+ * divisions, one conversion rounded to nearest, one float32 multiply; 3: (float)n * scale; 4: (float)((mx mx + my my) + mz mz) * scale
+ * with the three means in double. */
+__global__ __launch_bounds__(256) void tracks_convert_kernel(const uint32_t *__restrict__ counts, const long long *__restrict__ sums,
+                                                             float *__restrict__ out, uint64_t voxels, uint32_t component, uint32_t least, float scale)
+{
+	#pragma clang fp contract(off)
+	const uint64_t stride = (uint64_t)gridDim.x * 256u;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < voxels; i += stride) {
+		const uint32_t n = counts[i];
+		float v = 0.0f;
+		if (n >= least) {
+			if (component == 3u) v = (float)n * scale;
+			else if (component < 3u) v = (float)(((double)sums[component * voxels + i] / BF_TRACK_FIXED) / (double)n) * scale;
+			else {
+				const double mx = ((double)sums[i] / BF_TRACK_FIXED) / (double)n, my = ((double)sums[voxels + i] / BF_TRACK_FIXED) / (double)n,
+				             mz = ((double)sums[2u * voxels + i] / BF_TRACK_FIXED) / (double)n;
+				v = (float)((mx * mx + my * my) + mz * mz) * scale;
+			}
+		}
+		out[i] = v;
+	}
+}
+
+namespace {
+
+bool grid_fits(uint32_t frames, uint32_t max_stored)
+{
+	return frames >= 2 && frames <= 65535u && max_stored >= 1 && max_stored <= BF_TRACK_MAX_PEAKS;
+}
+
+} // namespace
+
+/* list: the emit pass's records, frame n's stored[n] at firsts[n]; placements: frames x 12 doubles; positions: three doubles a record;
+ * unplaced[frames]: zeroed by the caller.  All device memory; max_stored: the most records of one frame (host). */
+extern "C" hipError_t bf_launch_tracks_place(const void *list, const double *placements, const uint32_t *firsts, const uint32_t *stored,
+                                             uint32_t frames, uint32_t max_stored, uint32_t use_offsets, double *positions, uint32_t *unplaced,
+                                             hipStream_t s)
+{
+	if (!list || ((uintptr_t)list & 15u) || !placements || !firsts || !stored || !positions || !unplaced || !grid_fits(frames, max_stored))
+		return hipErrorInvalidValue;
+	hipLaunchKernelGGL(tracks_place_kernel, dim3((max_stored + 255u) / 256u, frames), dim3(256), 0, s, (const uint4 *)list, placements, firsts, stored,
+	                   use_offsets, positions, unplaced);
+	return hipGetLastError();
+}
+
+/* forward, backward: a uint32 a record, at the record's own index: forward[firsts[n] + a] = f(a) of frame pair n, backward[firsts[n + 1]
+ * + b] = g(b) of frame pair n (BF_TRACK_NONE: none).  The oldest frame's backward and the newest frame's forward entries stay unwritten
+ * and unread. */
+extern "C" hipError_t bf_launch_tracks_nearest(const double *positions, const uint32_t *firsts, const uint32_t *stored, uint32_t frames,
+                                               uint32_t max_stored, double r2, uint32_t *forward, uint32_t *backward, hipStream_t s)
+{
+	if (!positions || !firsts || !stored || !forward || !backward || !grid_fits(frames, max_stored) || !(r2 >= 0.0)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(tracks_nearest_kernel, dim3((max_stored + 255u) / 256u, frames - 1u, 2), dim3(256), 0, s, positions, firsts, stored, r2,
+	                   forward, backward);
+	return hipGetLastError();
+}
+
+/* Three launches: match, scan, emit.  block_firsts[frames - 1]: frame pair n's first block, the pairs before it holding
+ * ceil(stored / 256) each, `blocks` in all (host); masks: four words a block; words, offsets: one a block; tallies[frames - 1]: zeroed
+ * by the caller.  pairs: NULL, or room for the sum over n of min(stored[n], stored[n + 1]) 48-byte records, 16-byte aligned.  With
+ * t->deposit: map_counts, t->points voxels of uint32, and map_sums, three times as many int64 behind one another. */
+extern "C" hipError_t bf_launch_tracks_pair(const double *positions, const uint32_t *firsts, const uint32_t *stored, const uint32_t *block_firsts,
+                                            uint32_t frames, uint32_t max_stored, uint32_t blocks, const uint32_t *forward, const uint32_t *backward,
+                                            uint64_t *masks, uint32_t *words, uint32_t *offsets, const BfTrackArgs *t, uint32_t *map_counts,
+                                            void *map_sums, void *pairs, BfTrackTally *tallies, hipStream_t s)
+{
+	if (!positions || !firsts || !stored || !block_firsts || !forward || !backward || !masks || !words || !offsets || !t || !tallies ||
+	    ((uintptr_t)pairs & 15u) || !grid_fits(frames, max_stored) || blocks == 0) return hipErrorInvalidValue;
+	if (t->deposit && (!map_counts || !map_sums || !t->points[0] || !t->points[1] || !t->points[2] ||
+	                   (uint64_t)t->points[0] * t->points[1] > BF_TRACK_MAX_VOXELS ||
+	                   (uint64_t)t->points[0] * t->points[1] * t->points[2] > BF_TRACK_MAX_VOXELS)) return hipErrorInvalidValue;
+	const dim3 grid((max_stored + 255u) / 256u, frames - 1u);
+	hipLaunchKernelGGL(tracks_match_kernel, grid, dim3(256), 0, s, firsts, stored, block_firsts, forward, backward, masks, words, tallies);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(tracks_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)words, blocks, offsets);
+	e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(tracks_emit_kernel, grid, dim3(256), 0, s, positions, firsts, stored, block_firsts, forward, (const uint64_t *)masks,
+	                   (const uint32_t *)words, (const uint32_t *)offsets, *t, map_counts, (unsigned long long *)map_sums, (uint4 *)pairs, tallies);
+	return hipGetLastError();
+}
+
+/* counts: `voxels` uint32; sums: 3 x `voxels` int64; out: `voxels` floats (a frame of the ring); all device memory */
+extern "C" hipError_t bf_launch_track_convert(const uint32_t *counts, const void *sums, float *out, uint64_t voxels, uint32_t component,
+                                              uint32_t min_pairs, float scale, hipStream_t s)
+{
+	if (!counts || !sums || !out || voxels == 0 || voxels > BF_TRACK_MAX_VOXELS || component >= BF_TRACK_COMPONENTS) return hipErrorInvalidValue;
+	const uint64_t blocks = (voxels + 255u) / 256u;
+	hipLaunchKernelGGL(tracks_convert_kernel, dim3((uint32_t)(blocks < 4096u ? blocks : 4096u)), dim3(256), 0, s, counts, (const long long *)sums, out,
+	                   voxels, component, min_pairs ? min_pairs : 1u, scale);
+	return hipGetLastError();
+}

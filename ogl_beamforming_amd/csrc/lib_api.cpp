@@ -1060,6 +1060,48 @@ uint32_t beamformer_hip_queue_localisation_map(float scale, uint32_t image_plane
 	return queue_localisation_map(scale, image_plane_tag, frame_id, device_ms);
 }
 
+uint32_t beamformer_hip_track_map_reset(const uint32_t points[3])
+{
+	if (!points) return track_map_reset(nullptr);
+	if (!check(points[0] && points[1] && points[2], BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check((uint64_t)points[0] * points[1] <= BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS &&
+	           (uint64_t)points[0] * points[1] * points[2] <= BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!ensure_device()) return 0;
+	return track_map_reset(points);
+}
+
+/* (serves frames that exist, as the calls above: it starts no device) */
+uint32_t beamformer_hip_pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds,
+                                               uint32_t threshold_count, const double *placements, uint32_t placement_count,
+                                               uint32_t use_offsets, float max_distance, uint32_t max_per_frame, uint32_t deposit,
+                                               BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs, uint32_t *pair_count, float *device_ms)
+{
+	if (!check(count >= 2 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(rows != nullptr && pair_count != nullptr && thresholds != nullptr && placements != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (uint32_t k = 0; k < threshold_count; k++)
+		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
+		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(max_distance >= 0.0f && max_distance <= BEAMFORMER_HIP_MAX_PAIR_DISTANCE, BeamformerLibErrorKind_InvalidAccess)) return 0;   /* (a NaN fails both) */
+	return pair_peaks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame,
+	                              deposit, rows, pairs, pair_count, device_ms);
+}
+
+uint32_t beamformer_hip_track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info)
+{
+	if (!check(counts != nullptr && sums != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return track_map_copy(counts, sums, out_count, info);
+}
+
+uint32_t beamformer_hip_queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+{
+	if (!check(component < BEAMFORMER_HIP_TRACK_MAP_COMPONENTS && std::isfinite(scale), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return queue_track_map(component, scale, min_pairs, image_plane_tag, frame_id, device_ms);
+}
+
 /* host only: S_map^-1 M_map^-1 M_frame S_frame in double (include/ogl_beamformer_hip.h has the algebra) */
 uint32_t beamformer_hip_map_placement(const float frame_voxel_transform[16], const uint32_t frame_points[3], const float map_voxel_transform[16],
                                       const uint32_t map_points[3], double out[12])

@@ -143,6 +143,12 @@ def _load():
         "beamformer_hip_localisation_map_copy": (u32, [C.POINTER(u32), u64, C.POINTER(P.HipMapInfo)]),
         "beamformer_hip_queue_localisation_map": (u32, [C.c_float, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_map_placement": (u32, [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_double)]),
+        "beamformer_hip_track_map_reset": (u32, [C.POINTER(u32)]),
+        "beamformer_hip_pair_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
+                                                        C.c_float, u32, u32, C.POINTER(P.HipPeakPairs), C.POINTER(P.HipPeakPair), C.POINTER(u32),
+                                                        C.POINTER(C.c_float)]),
+        "beamformer_hip_track_map_copy": (u32, [C.POINTER(u32), C.POINTER(C.c_int64), u64, C.POINTER(P.HipTrackMapInfo)]),
+        "beamformer_hip_queue_track_map": (u32, [u32, C.c_float, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
         "beamformer_hip_clutter_projector": (u32, [C.POINTER(C.c_double), u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
         "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
@@ -661,6 +667,74 @@ def map_placement(frame_transform, frame_points, map_transform, map_points):
                                                   (C.c_float * 16)(*[float(v) for v in map_transform]),
                                                   (C.c_uint32 * 3)(*[int(v) for v in map_points]), out.ctypes.data_as(C.POINTER(C.c_double))))
     return out.reshape(3, 4)
+
+
+_track_points = None    # the grid of the newest track_map_reset(): what track_map_copy() sizes its arrays by
+
+
+def track_map_reset(points):
+    """beamformer_hip_track_map_reset: (re)allocates the library's one track map of points = (x, y, z) voxels -- a uint32 count and three
+    int64 displacement sums each -- and zeroes it; points None releases it."""
+    global _track_points
+    _check(library().beamformer_hip_track_map_reset(None if points is None else (C.c_uint32 * 3)(*[int(v) & 0xFFFFFFFF for v in points])))
+    _track_points = None if points is None else tuple(int(v) for v in points)
+
+
+def pair_peaks_last_frames(count, thresholds, placements, max_distance, max_per_frame, use_offsets=True, deposit=False, region=None,
+                           records=True):
+    """beamformer_hip_pair_peaks_last_frames: the peaks of the `count` newest frames (find_peaks_last_frames' records at the same
+    thresholds, region and max_per_frame) linked frame to frame on the device: a peak a of frame n and a peak b of frame n + 1 are a
+    pair when each is the other's nearest within max_distance (in map coordinates, under the frames' placements: one 3 x 4 float64
+    matrix for all frames or `count` of them, as accumulate_peaks_last_frames takes them).  deposit: the pairs' midpoints and
+    displacements go into the track map (track_map_reset).  Returns (rows, pairs, device_ms): a ctypes array of count - 1 HipPeakPairs
+    rows, a ctypes array of the packed HipPeakPair records (frame pair n's are pairs[rows[n].first : rows[n].first + rows[n].pairs];
+    empty with records False: the call makes none) and the device time of the launches."""
+    count, max_per_frame = int(count), int(max_per_frame)
+    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
+    levels = (C.c_float * max(1, len(values)))(*values)
+    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
+    if matrices.size % 12:
+        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    rows = (P.HipPeakPairs * max(1, count - 1))()
+    room = (count - 1) * max_per_frame if records and 2 <= count <= P.HIP_MAX_SCORED_FRAMES and 0 < max_per_frame <= P.HIP_MAX_PEAKS_PER_FRAME else 0
+    out = np.zeros(max(1, room), np.dtype(P.HipPeakPair))
+    total, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_pair_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
+                                                           matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
+                                                           1 if use_offsets else 0, float(max_distance), max_per_frame, 1 if deposit else 0, rows,
+                                                           out.ctypes.data_as(C.POINTER(P.HipPeakPair)) if records else None, C.byref(total),
+                                                           C.byref(ms)))
+    kept = int(total.value) if records else 0
+    pairs = (P.HipPeakPair * kept).from_buffer_copy(out[:kept].tobytes())
+    return rows, pairs, float(ms.value)
+
+
+def track_map_copy(points=None):
+    """beamformer_hip_track_map_copy: (counts, sums, info) -- the track map's counts as a uint32 array (Z, Y, X), its displacement sums
+    as an int64 array (3, Z, Y, X) in units of 2^-20 map voxels (component r along map axis r) and its HipTrackMapInfo.  points: the
+    map's grid (x, y, z), which sizes the arrays; None: the grid the newest track_map_reset() of this module asked for."""
+    points = _track_points if points is None else tuple(int(v) for v in points)
+    if points is None:
+        raise ValueError("points: no track_map_reset() through this module yet")
+    voxels = max(1, int(np.prod(points)))
+    counts, sums = np.zeros(voxels, np.uint32), np.zeros(3 * voxels, np.int64)
+    info = P.HipTrackMapInfo()
+    _check(library().beamformer_hip_track_map_copy(counts.ctypes.data_as(C.POINTER(C.c_uint32)), sums.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   counts.size, C.byref(info)))
+    shape = (int(info.points[2]), int(info.points[1]), int(info.points[0]))
+    n = int(np.prod(shape))
+    return counts[:n].reshape(shape), sums[:3 * n].reshape((3,) + shape), info
+
+
+def queue_track_map(component, scale=1.0, min_pairs=1, tag=0, timed=True):
+    """beamformer_hip_queue_track_map: one component of the track map queued into the frame ring as one Float32 frame of the map's grid
+    -- 0..2: the mean displacement along map axis x, y, z per frame interval; 3: the pair count; 4: the squared mean speed --, times
+    `scale`, 0 where fewer than max(1, min_pairs) pairs were deposited.  Returns (frame_id, device_ms); timed False: the call does not
+    synchronise and device_ms is 0."""
+    frame, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_queue_track_map(int(component), float(scale), int(min_pairs), int(tag), C.byref(frame),
+                                                    C.byref(ms) if timed else None))
+    return int(frame.value), float(ms.value)
 
 
 def gram_last_frames(count, region=None):

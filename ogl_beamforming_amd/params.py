@@ -362,6 +362,29 @@ class HipMapInfo(C.Structure):
     _fields_ = [("points", C.c_uint32 * 3), ("calls", C.c_uint32), ("deposited", C.c_uint64), ("outside", C.c_uint64)]
 
 
+HIP_MAX_TRACK_MAP_VOXELS = 1 << 26     # BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS
+HIP_MAX_PAIR_DISTANCE = 1048576.0      # BEAMFORMER_HIP_MAX_PAIR_DISTANCE
+HIP_TRACK_MAP_COMPONENTS = 5           # BEAMFORMER_HIP_TRACK_MAP_COMPONENTS
+
+
+class HipPeakPair(C.Structure):
+    """BeamformerHipPeakPair: one link of beamformer_hip_pair_peaks_last_frames (48 bytes, no padding)"""
+    _fields_ = [("frame", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("deposited", C.c_uint32),
+                ("displacement", C.c_double * 3), ("distance2", C.c_double)]
+
+
+class HipPeakPairs(C.Structure):
+    """BeamformerHipPeakPairs: one frame pair's row of beamformer_hip_pair_peaks_last_frames (72 bytes, no padding)"""
+    _fields_ = [("frame_id", C.c_uint32 * 2), ("threshold", C.c_float * 2), ("peaks", C.c_uint32 * 2), ("unplaced", C.c_uint32 * 2),
+                ("unpaired", C.c_uint32 * 2), ("first", C.c_uint32), ("pairs", C.c_uint32), ("deposited", C.c_uint32), ("outside", C.c_uint32),
+                ("found", C.c_uint64 * 2)]
+
+
+class HipTrackMapInfo(C.Structure):
+    """BeamformerHipTrackMapInfo: the track map's grid and its totals since the reset (40 bytes, no padding)"""
+    _fields_ = [("points", C.c_uint32 * 3), ("calls", C.c_uint32), ("pairs", C.c_uint64), ("deposited", C.c_uint64), ("outside", C.c_uint64)]
+
+
 HIP_MAX_ENSEMBLE_FRAMES = 256
 HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
 HIP_MAX_SPATIAL_TAPS = 33       # BEAMFORMER_HIP_MAX_SPATIAL_TAPS
