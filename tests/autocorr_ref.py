@@ -7,6 +7,7 @@ import numpy as np
 from tests import ensemble_ref
 
 U = 2.0 ** -24                     # the unit roundoff of float32
+TINY = 2.0 ** -150                 # half the spacing of the float32 subnormals: what one rounding below 2^-126 can be off by
 
 
 def filtered(frames, W):
@@ -44,6 +45,18 @@ def lag_products(y, lags, conj_second=False, shift=0):
     return out
 
 
+def float32_range(out, y, lags):
+    """`out` with the floats that leave the float32 range made what the float32 chain makes of them: the header's chains are float32
+    chains under plain IEEE, so a product or a sum beyond FLT_MAX is an infinity (or, met by its opposite, a NaN) in the device's
+    frame although its exact value is a finite double.  The narrow chain rounds the product and the sum apart, which moves no
+    overflow but one within an ulp of FLT_MAX."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        narrow = lag_products(y.astype(np.complex64 if np.iscomplexobj(y) else np.float32), lags)
+    if not np.iscomplexobj(out):
+        return np.where(np.isfinite(narrow), out, narrow.astype(out.dtype))
+    return np.where(np.isfinite(narrow.real), out.real, narrow.real) + 1j * np.where(np.isfinite(narrow.imag), out.imag, narrow.imag)
+
+
 def autocorrelate(frames, W, lags):
     """(out, bound): out[L] = R_L in complex128 (float64 for real frames), bound[L] on each float of the device's R_L, both of shape
     (lags,) + the frames'.
@@ -63,16 +76,20 @@ def autocorrelate(frames, W, lags):
     (The form first proposed for this bound had e_n e_m once in (ii) and not at all in (i): each part of a term is a sum of TWO
     products, each of which carries its own e_n e_m.  The difference is of second order.)  Real frames run N terms, not 2N, with
     a_n = |y_n|: the same expression bounds them.  This reference's own float64 rounding is 2^-29 of (i) and inside its "+ 2".
-    Lag 0's imaginary part is exact (0, or NaN where the real part is not finite): the bound is not asked there."""
+    Lag 0's imaginary part is exact (0, or NaN where the real part is not finite): the bound is not asked there.
+    UNDERFLOW.  The relative bound of (i) holds for roundings of normal results; a chain link whose result lies below 2^-126 rounds to
+    a multiple of 2^-149 and is off by up to 2^-150 whatever its size (the product of two subnormal voxels is 0 on the device): 2N links,
+    2N x 2^-150 more.
+    A float whose float32 chain leaves the float32 range is not finite in `out` (float32_range): the bound is not asked there either."""
     stack = np.stack([np.asarray(f) for f in frames])
     y, e = filtered(frames, W)
     rows = y.shape[0]
-    out = lag_products(y, lags)
+    out = float32_range(lag_products(y, lags), y, lags)
     a = np.abs(np.real(y)) + np.abs(np.imag(y))
     bound = np.zeros((lags,) + y.shape[1:], np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
         for L in range(lags):
             N = rows - L
             an, am, en, em = a[:N], a[L:], e[:N], e[L:]
-            bound[L] = (2 * N + 2) * U * ((an + en) * (am + em) + en * em).sum(axis=0) + (an * em + am * en + 2 * en * em).sum(axis=0)
+            bound[L] = (2 * N + 2) * U * ((an + en) * (am + em) + en * em).sum(axis=0) + (an * em + am * en + 2 * en * em).sum(axis=0) + 2 * N * TINY
     return out.reshape((lags,) + stack.shape[1:]), bound.reshape((lags,) + stack.shape[1:])

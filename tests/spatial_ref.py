@@ -89,11 +89,13 @@ def convolve(frame, taps, mode=ZERO, flip=False, centre=0, plain_sum=False):
         [B_N + rho |N| + u (|N| + B_N)] / (D (1 - rho))  <=  [B_N + (rho + u)(|N| + B_N)] / (D (1 - rho)):
     the form proposed is the right-hand side -- it holds, with rho B_N to spare, a term of second order -- and is what is returned,
     where D > 0 (elsewhere the quotient is 0 / 0 and the bound NaN).  D^ > 0 exactly where D > 0: a sum of non-negative terms rounds to
-    0 only if it is 0 (underflow aside)."""
+    0 only if it is 0 (underflow aside).
+    A float whose float32 chain leaves the float32 range is not finite in `values` (float32_range): no bound is asked there."""
     f = floats_of(frame)
+    definition = not (flip or centre or plain_sum)
     if mode == ZERO:
         values = passes(f, taps, flip=flip, centre=centre)
-        return frame_of(values), frame_of(pass_bound(f, taps))
+        return frame_of(float32_range(values, frame, taps, mode) if definition else values), frame_of(pass_bound(f, taps))
     finite = np.isfinite(f).all(axis=-1, keepdims=True)
     f0 = np.where(finite, f, 0.0)
     m = np.broadcast_to(finite.astype(np.float64), f.shape)
@@ -105,7 +107,17 @@ def convolve(frame, taps, mode=ZERO, flip=False, centre=0, plain_sum=False):
     with np.errstate(invalid="ignore", divide="ignore"):
         values = np.where(D > 0, N / divisor, np.nan)
         bound = np.where(D > 0, (B_N + (rho + U) * (np.abs(N) + B_N)) / (D * (1.0 - rho)), np.nan)
-    return frame_of(values), frame_of(bound)
+    return frame_of(float32_range(values, frame, taps, mode) if definition else values), frame_of(bound)
+
+
+def float32_range(values, frame, taps, mode):
+    """`values` (z, y, x, parts) with the floats that leave the float32 range made what the float32 chain makes of them: the header's
+    chains are float32 chains under plain IEEE, so a sum beyond FLT_MAX is an infinity (or, met by its opposite, a NaN) in the device's
+    frame although its exact value is a finite double.  convolve_float32 rounds the product and the sum apart, which moves no overflow
+    but one within an ulp of FLT_MAX."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        narrow = floats_of(convolve_float32(frame, taps, mode))
+    return np.where(np.isfinite(narrow), values, narrow)
 
 
 def convolve_float32(frame, taps, mode=ZERO):

@@ -194,7 +194,8 @@ def warp(frame, field, nodes=(1, 1, 1), node_first=(0, 0, 0), node_step=(1, 1, 1
     growth = np.prod([1.0 + (n_taps + 2) * U for a in range(3) if live[a]])
     plain = [(first, [np.abs(w) for w in ws]) for first, ws in taps]
     padded = [(first, [np.abs(w) + (c_w * U if live[a] else 0.0) for w in ws]) for a, (first, ws) in enumerate(taps)]
-    bound = growth * separable(absolute, padded, edge, fma64, np.float64) - separable(absolute, plain, edge, fma64, np.float64)
+    with np.errstate(invalid="ignore"):             # (inf - inf under an infinite voxel: no bound where the value is not finite)
+        bound = growth * separable(absolute, padded, edge, fma64, np.float64) - separable(absolute, plain, edge, fma64, np.float64)
 
     # the position part.  A voxel that is not finite and lies under the WIDENED support only adds nothing: the value is finite there,
     # and so must the device's be -- if the device's floor brought that voxel under its own support, its output would not be finite
