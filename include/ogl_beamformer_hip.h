@@ -723,7 +723,7 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_accumulate_peaks_last_frames(uint3
                                                                            float *device_ms);
 typedef struct {
 	uint32_t points[3];
-	uint32_t calls;                           /* successful beamformer_hip_accumulate_peaks_last_frames calls since the reset */
+	uint32_t calls;                           /* successful beamformer_hip_accumulate_peaks_last_frames calls, and beamformer_hip_track_peaks_last_frames calls with BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS, since the reset */
 	uint64_t deposited, outside;              /* their totals */
 } BeamformerHipMapInfo;                       /* 32 bytes, no padding */
 /* The map's counts as they are, copied to out[out_count] behind everything enqueued on the current stream (one synchronise); *info
@@ -837,7 +837,7 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_pair_peaks_last_frames(uint32_t co
                                                                      uint32_t *pair_count, float *device_ms);
 typedef struct {
 	uint32_t points[3];
-	uint32_t calls;                           /* successful beamformer_hip_pair_peaks_last_frames calls with deposit != 0 since the reset */
+	uint32_t calls;                           /* successful beamformer_hip_pair_peaks_last_frames calls with deposit != 0, and beamformer_hip_track_peaks_last_frames calls with BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS, since the reset */
 	uint64_t pairs, deposited, outside;       /* their totals: pairs == deposited + outside */
 } BeamformerHipTrackMapInfo;                  /* 40 bytes, no padding */
 /* The track map as it is, behind everything enqueued on the current stream (one synchronise): counts[out_count] and sums[3 * voxels]
@@ -859,6 +859,81 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_track_map_copy(uint32_t *counts, i
  * not fit the ring: FrameSizeOverflow. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag,
                                                               uint32_t *frame_id, float *device_ms);
+
+/* ---- peak tracks: the pairs of a call's frames chained ON THE DEVICE, and kept by length (what decides the quality of a published ULM
+ * image: a detection counts only when it persists over L consecutive frames, L about 10 to 15 -- the pair call alone is L = 2 --;
+ * instead of downloading every packed pair list and chaining on the host, every ensemble) ----
+ * DEFINITION (tests/track_chains_ref.py restates it in numpy, on top of tests/tracks_ref.py).  All of it beyond the pairs is integer.
+ * PEAKS, RANK, POSITION, DISTANCE, CHOICE and PAIR are beamformer_hip_pair_peaks_last_frames', byte for byte: the same mark, scan, emit,
+ * place and nearest launches run.
+ * LINK.  A pair (a, b) of frame pair n links peak a of frame n to peak b of frame n + 1: a peak has at most one link to the older frame
+ * and at most one to the newer.  An UNPLACED peak has no links and belongs to no track: it counts in `unplaced` only.
+ * TRACK.  A HEAD is a placed peak with no link to the older frame (every placed peak of frame 0 is one).  A track is a head followed by
+ * its links toward newer frames until a peak has no link to the newer frame, the TAIL: every placed peak lies in exactly one track, of
+ * L = 1 .. count peaks, one a frame, in consecutive frames.  There is NO GAP CLOSING: a frame without a partner ends the track, and what
+ * follows it is another track.
+ * KEPT when L >= min_length.
+ * ORDER.  The kept tracks are listed in ascending (start frame, rank of the head); a track's points follow one another, oldest first,
+ * and the tracks' point runs are packed in track order.  Both lists depend on the frames, the box, the thresholds, the placements,
+ * max_distance, max_per_frame and min_length only: not on the call being repeated (no atomic decides a place).
+ * DEPOSIT.  BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS: every point of every kept track goes to the bin floor(m_r + 0.5) of the LOCALISATION
+ * map -- its BIN rule --: inside the map the bin's count goes up by 1, otherwise the point counts in points_outside.
+ * BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS: every link of every kept track goes into the TRACK map by the pair call's DEPOSIT rule,
+ * expression for expression (the midpoint, the fixed-point displacement).  Integer atomics only.
+ * EQUALITIES.  (i) min_length <= 2 with LINKS leaves the track map's bytes as the pair call with deposit leaves them on the same frames
+ * (every pair lies in a track of at least two peaks).  (ii) min_length == 1 with POINTS, no frame with found > max_per_frame and no
+ * unplaced peak: the localisation map's bytes are beamformer_hip_accumulate_peaks_last_frames'.  (iii) The links of all tracks at
+ * min_length == 1 are exactly the pair call's records. */
+#define BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS 1u   /* kept tracks' peaks -> the localisation map */
+#define BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS  2u   /* kept tracks' pairs -> the track map        */
+typedef struct {
+	uint32_t frame;                           /* s: the frame of the call (0 = oldest) the track begins in */
+	uint32_t rank;                            /* the head's rank in frame s's find_peaks list */
+	uint32_t length;                          /* L: its peaks, one a frame, in frames s .. s + L - 1 */
+	uint32_t first;                           /* its points: points[first .. first + L) */
+	uint32_t flags;                           /* bit 0: begins in the call's oldest frame; bit 1: ends in its newest (either may be cut by the call's window) */
+	uint32_t reserved;                        /* 0 */
+	double   displacement[3];                 /* m(tail) - m(head), one subtraction a row */
+} BeamformerHipPeakTrack;                     /* 48 bytes, no padding */
+typedef struct {
+	uint32_t track;                           /* index into `tracks` */
+	uint32_t frame, rank;                     /* the peak: frame of the call, rank in that frame's list */
+	uint32_t deposited;                       /* bit 0: this point went into the localisation map; bit 1: its link to the next point went into the track map */
+	double   position[3];                     /* m_r, the map coordinate */
+} BeamformerHipTrackPoint;                    /* 40 bytes, no padding */
+typedef struct {                              /* a row a FRAME */
+	uint32_t frame_id; float threshold;       /* from the frame's record; the threshold used for it */
+	uint32_t peaks, unplaced;                 /* stored records; those whose coordinate is not finite */
+	uint32_t heads, kept_heads;               /* tracks that begin here: all of them, and those kept */
+	uint32_t kept_points, kept_links;         /* this frame's peaks in kept tracks; of them, those with a link to the next frame */
+	uint32_t points_deposited, points_outside, links_deposited, links_outside;   /* all 0 without the deposit bit; else the two of a kind add up to kept_points, kept_links */
+	uint64_t found;                           /* exactly beamformer_hip_find_peaks_last_frames' number */
+} BeamformerHipTrackedFrame;                  /* 56 bytes, no padding */
+/* The peaks of the `count` newest frames (2 <= count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES), oldest first, chained into tracks; every
+ * argument up to max_per_frame is beamformer_hip_pair_peaks_last_frames'.  min_length: 1 .. BEAMFORMER_HIP_MAX_SCORED_FRAMES
+ * (min_length > count is legal and keeps nothing).  deposit: 0 or any of the two bits.  rows[count]: a row a frame.  tracks and points
+ * (either may be NULL: those records do not come back, everything else is the same) each have room for count * max_per_frame records
+ * -- the convention of find_peaks' `peaks` -- and come back packed in ORDER; *track_count and *point_count are the totals (also with
+ * NULL lists).  The call runs on the current stream in THREE synchronises at the most, as the pair call and for its reasons: the counts
+ * (the buffers are sized by them), the per-frame tallies (the two downloads are sized by them), the records (skipped when both lists
+ * are NULL or empty).  Behind the nearest kernel (csrc/frame_tracks.hip): link, ceil(log2(count)) pointer-jumping rounds, keep, the
+ * scan twice, finish.  device_ms, when not NULL: the time between events around the launches, both parts added.
+ * A successful call with POINTS is a depositing call of the localisation map (its calls, deposited and outside go up, the parameter
+ * block of the call's newest frame is remembered for beamformer_hip_queue_localisation_map); one with LINKS is one of the track map
+ * (calls, pairs -- by the kept links --, deposited, outside; beamformer_hip_queue_track_map).
+ * Refusals, all decided before anything is enqueued or changed and leaving every output unwritten: everything
+ * beamformer_hip_pair_peaks_last_frames refuses, with its error kinds (count < 2 among them); min_length == 0 or >
+ * BEAMFORMER_HIP_MAX_SCORED_FRAMES: BufferOverflow; InvalidAccess: a deposit bit other than the two; POINTS without a localisation map,
+ * LINKS without a track map; rows, track_count or point_count NULL. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                      const float *thresholds, uint32_t threshold_count,
+                                                                      const double *placements /* [placement_count][12] */,
+                                                                      uint32_t placement_count /* 1 or count */, uint32_t use_offsets,
+                                                                      float max_distance, uint32_t max_per_frame, uint32_t min_length, uint32_t deposit,
+                                                                      BeamformerHipTrackedFrame *rows /* [count] */,
+                                                                      BeamformerHipPeakTrack *tracks /* may be NULL; room for count * max_per_frame */,
+                                                                      BeamformerHipTrackPoint *points /* may be NULL; room for count * max_per_frame */,
+                                                                      uint32_t *track_count, uint32_t *point_count, float *device_ms);
 
 /* ---- ensemble filter: a linear slow-time operator on the frames of the frame ring (the clutter filter between "ensemble" and "peaks"
  * of the ULM loop: tissue lies 30 - 60 dB above the microbubbles, so the peaks of an unfiltered ensemble are tissue speckle).  Two

@@ -423,6 +423,18 @@ typedef struct {
 	uint32_t points[3];          /* the track map's grid, x fastest (read with deposit only) */
 	uint32_t deposit;            /* 0: nothing is added to the map */
 } BfTrackArgs;
+/* peak tracks (frame_tracks.hip: beamformer_hip_track_peaks_last_frames) */
+#define BF_CHAIN_POINTS 1u                   /* = BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS */
+#define BF_CHAIN_LINKS  2u                   /* = BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS */
+typedef struct {                             /* a frame: BeamformerHipTrackedFrame's eight counters, in its order */
+	uint32_t heads, kept_heads, kept_points, kept_links, points_deposited, points_outside, links_deposited, links_outside;
+} BfChainTally;
+typedef struct {
+	uint32_t point_map[3];       /* the localisation map's grid, x fastest (read with BF_CHAIN_POINTS only) */
+	uint32_t track_map[3];       /* the track map's (read with BF_CHAIN_LINKS only) */
+	uint32_t deposit;            /* BF_CHAIN_POINTS | BF_CHAIN_LINKS */
+	uint32_t min_length;         /* a track is kept with at least so many peaks */
+} BfChainArgs;
 
 /* ---- frame quantiles (frame_quantiles.hip: beamformer_hip_quantiles_last_frames) ---- */
 #define BF_QUANTILES_MAX       16u           /* = BEAMFORMER_HIP_MAX_QUANTILES: ranks a frame, and so distinct prefixes a digit pass */
@@ -696,6 +708,19 @@ hipError_t bf_launch_tracks_pair(const double *positions, const uint32_t *firsts
                                  void *map_sums, void *pairs, BfTrackTally *tallies, hipStream_t s);
 hipError_t bf_launch_track_convert(const uint32_t *counts, const void *sums, float *out, uint64_t voxels, uint32_t component,
                                    uint32_t min_pairs, float scale, hipStream_t s);
+/* frame_tracks.hip, behind _nearest on the same stream: the pairs chained into tracks, ceil(log2(frames)) + 5 launches (link, the
+ * pointer-jumping rounds, keep, the scan twice, finish), integer work but for the displacements.  total: the records of all frames,
+ * at most 2^26.  forward, backward: _nearest's, or both NULL when it did not run (no frame pair with peaks on both sides: no links).
+ * Tables of the caller's, unread before they are written here: next, lengths, tails, track_of, first_of: `total` uint32 each; links:
+ * 2 x total pairs of uint32 (8-byte aligned); words, offsets: 2 x ceil(total / 256) uint32 each.  tracks, points: NULL, or room for
+ * `total` records of BeamformerHipPeakTrack's and BeamformerHipTrackPoint's layout (8-byte aligned), written PACKED in the order of the
+ * definition.  With a->deposit & BF_CHAIN_POINTS: point_map, a->point_map voxels of uint32; with BF_CHAIN_LINKS: track_counts and
+ * track_sums as _pair takes them, a->track_map voxels.  tallies[frames]: zeroed by the caller (integer atomics, a wave a counter) */
+hipError_t bf_launch_tracks_chain(const double *positions, const uint32_t *firsts, const uint32_t *stored, uint32_t frames, uint32_t max_stored,
+                                  uint32_t total, const uint32_t *forward, const uint32_t *backward, uint32_t *next, void *links, uint32_t *lengths,
+                                  uint32_t *tails, uint32_t *track_of, uint32_t *first_of, uint32_t *words, uint32_t *offsets, const BfChainArgs *a,
+                                  uint32_t *point_map, uint32_t *track_counts, void *track_sums, void *tracks, void *points, BfChainTally *tallies,
+                                  hipStream_t s);
 /* ensemble.hip, the Gram matrix: three launches, no atomics -- the all-finite mask (a wave a word of 64 box voxels, every frame read
  * once), the partial pass (grid x the chunk, grid y the tile pair: BF_GRAM_TILE x BF_GRAM_TILE pairs of double2 a block) and the fold
  * (a thread a pair j <= k sums its chunks' partials in chunk order and stores both triangles; one more block counts the mask's bits).

@@ -1,5 +1,5 @@
 /* frame_ops.cpp -- the calls that work on frames already in the ring: the reduce calls (score, find_peaks, accumulate_peaks, pair_peaks,
- * gram, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
+ * track_peaks, gram, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
  * the queued runs (mix, autocorrelate, convolve, warp, queue_localisation_map, queue_track_map), which write frames of their own behind
  * the newest ones and do not.  Their
  * device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is executor.cpp's. */
@@ -189,6 +189,137 @@ bool peaks_rows_of(const std::vector<BoxedFrame> &boxed, const float *thresholds
 	}
 	return true;
 }
+
+/* What pair_peaks_last_frames and track_peaks_last_frames share: the peaks of the boxed frames found, placed and offered to one another
+ * (frame_peaks.hip: mark, scan, emit; frame_tracks.hip: place, nearest).  The caller fills `boxed` (newest_boxed_frames), decides its
+ * own refusals, and then calls find() -- the first synchronise --, takes its own tables from `big`, ensure(), enqueue(), its own
+ * launches, collect() -- the second.
+ * device: rows | placements | results | firsts | stored | block_firsts | unplaced | tallies | extra | masks | counts | offsets; pinned:
+ * the first nine (rows and placements go up in one copy, firsts, stored and block_firsts in a second, unplaced, tallies and the
+ * caller's `extra` come back in one: each group stays adjacent).  tracks_scratch: positions | forward | backward | the caller's. */
+struct PeakChoices {
+	std::vector<BoxedFrame> boxed;
+	PeaksRows table;
+	uint32_t count = 0, links = 0;
+	size_t firsts_at = 0, unplaced_at = 0, tally_bytes = 0;          /* (tally_bytes: from unplaced_at to the end of `extra`) */
+	char *device = nullptr, *pinned = nullptr;
+	const BfPeaksRow *device_rows = nullptr;
+	const double *device_placements = nullptr;
+	const uint32_t *device_firsts = nullptr, *device_stored = nullptr, *device_block_firsts = nullptr;
+	uint32_t *device_unplaced = nullptr, *device_counts = nullptr, *device_offsets = nullptr;
+	BfTrackTally *device_tallies = nullptr;
+	void *device_extra = nullptr;
+	uint64_t *device_masks = nullptr;
+	const BfPeaksResult *results = nullptr;
+	uint32_t *firsts = nullptr, *stored = nullptr, *block_firsts = nullptr;
+	const uint32_t *unplaced = nullptr;
+	const BfTrackTally *tallies = nullptr;
+	const void *extra = nullptr;
+	/* what the scan found: it sizes everything behind find() -- the records, the positions, the choices, the match pass's blocks, the pairs */
+	uint32_t total = 0, max_stored = 0, blocks = 0;                  /* (at most 1024 frames x 65536 records, 256 blocks a frame) */
+	uint64_t capacity = 0;                                           /* the sum over the frame pairs of min(stored[n], stored[n + 1]) */
+	float mark_ms = 0;
+	bool timed = false;
+	Carve big;
+	size_t positions_at = 0, forward_at = 0, backward_at = 0;
+
+	bool find(Device &d, const float *thresholds, uint32_t threshold_count, const double *placements, uint32_t placement_count,
+	          uint32_t max_per_frame, size_t extra_bytes)
+	{
+		count = (uint32_t)boxed.size(); links = count - 1u;
+		if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
+		Carve dev;
+		const size_t rows_at = dev.take(sizeof(BfPeaksRow) * count), placements_at = dev.take(sizeof(double) * 12 * count),
+		             results_at = dev.take(sizeof(BfPeaksResult) * count);
+		firsts_at = dev.take(sizeof(uint32_t) * count);
+		const size_t stored_at = dev.take(sizeof(uint32_t) * count), block_firsts_at = dev.take(sizeof(uint32_t) * links);
+		unplaced_at = dev.take(sizeof(uint32_t) * count);
+		const size_t tallies_at = dev.take(sizeof(BfTrackTally) * links), extra_at = dev.take(extra_bytes), pinned_bytes = dev.total,
+		             masks_at = dev.take(sizeof(uint64_t) * table.waves), counts_at = dev.take(sizeof(uint32_t) * table.blocks),
+		             offsets_at = dev.take(sizeof(uint32_t) * table.blocks);
+		tally_bytes = (extra_bytes ? extra_at + extra_bytes : tallies_at + sizeof(BfTrackTally) * links) - unplaced_at;
+		bool ok = ensure_metrics_memory(d, pinned_bytes, dev.total);
+		if (ok && !d.ops.peaks_begin) ok = HIP_OK(hipEventCreate(&d.ops.peaks_begin));
+		if (ok && !d.ops.peaks_end)   ok = HIP_OK(hipEventCreate(&d.ops.peaks_end));
+		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+		device = (char *)d.ops.metrics_scratch.ptr; pinned = (char *)d.ops.metrics_pinned;
+		device_rows       = (const BfPeaksRow *)(device + rows_at);
+		device_placements = (const double *)(device + placements_at);
+		BfPeaksResult *device_results = (BfPeaksResult *)(device + results_at);
+		device_firsts = (const uint32_t *)(device + firsts_at); device_stored = (const uint32_t *)(device + stored_at);
+		device_block_firsts = (const uint32_t *)(device + block_firsts_at);
+		device_unplaced = (uint32_t *)(device + unplaced_at);
+		device_tallies  = (BfTrackTally *)(device + tallies_at);
+		device_extra    = device + extra_at;
+		device_masks    = (uint64_t *)(device + masks_at);
+		device_counts   = (uint32_t *)(device + counts_at);
+		device_offsets  = (uint32_t *)(device + offsets_at);
+		results = (const BfPeaksResult *)(pinned + results_at);
+		firsts = (uint32_t *)(pinned + firsts_at); stored = (uint32_t *)(pinned + stored_at); block_firsts = (uint32_t *)(pinned + block_firsts_at);
+		unplaced = (const uint32_t *)(pinned + unplaced_at);
+		tallies  = (const BfTrackTally *)(pinned + tallies_at);
+		extra    = pinned + extra_at;
+		std::memcpy(pinned + rows_at, table.rows.data(), sizeof(BfPeaksRow) * count);
+		for (uint32_t n = 0; n < count; n++)
+			std::memcpy(pinned + placements_at + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
+		if (!timed_reduce(d, placements_at + sizeof(double) * 12 * count, results_at, sizeof(BfPeaksResult) * count, nullptr, [&](hipStream_t s) {   /* (its time: read below, with the rest's) */
+			return bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s);
+		})) return false;
+
+		for (uint32_t n = 0; n < count; n++) {
+			stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
+			firsts[n] = total;
+			total += stored[n];
+			if (stored[n] > max_stored) max_stored = stored[n];
+			if (n) capacity += stored[n - 1] < stored[n] ? stored[n - 1] : stored[n];
+			if (n < links) { block_firsts[n] = blocks; blocks += (stored[n] + 255u) / 256u; }
+		}
+		std::memset(pinned + unplaced_at, 0, tally_bytes);
+		timed = HIP_OK(hipEventElapsedTime(&mark_ms, d.ops.metrics_begin, d.ops.metrics_end));
+		positions_at = big.take(sizeof(double) * 3 * total); forward_at = big.take(sizeof(uint32_t) * total); backward_at = big.take(sizeof(uint32_t) * total);
+		return true;
+	}
+
+	bool ensure(Device &d) const { return d.ops.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak)) && d.ops.tracks_scratch.ensure(big.total); }
+	double   *positions(Device &d) const { return (double *)((char *)d.ops.tracks_scratch.ptr + positions_at); }
+	uint32_t *forward(Device &d) const { return (uint32_t *)((char *)d.ops.tracks_scratch.ptr + forward_at); }
+	uint32_t *backward(Device &d) const { return (uint32_t *)((char *)d.ops.tracks_scratch.ptr + backward_at); }
+
+	/* behind ensure(), total != 0: the tables up, the tallies zeroed, the first event, then emit, place and -- with a frame pair that has
+	 * peaks on both sides: else nothing is there to choose from -- nearest */
+	bool enqueue(Device &d, bool use_offsets, double r2)
+	{
+		hipStream_t s = d.stream;
+		bool ok = HIP_OK(hipMemcpyAsync(device + firsts_at, firsts, unplaced_at - firsts_at, hipMemcpyHostToDevice, s));
+		ok &= HIP_OK(hipMemsetAsync(device_unplaced, 0, tally_bytes, s));
+		ok &= HIP_OK(hipEventRecord(d.ops.peaks_begin, s));
+		if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets,
+		                                                device_firsts, d.ops.peaks_list.ptr, s));
+		if (ok) ok &= HIP_OK(bf_launch_tracks_place(d.ops.peaks_list.ptr, device_placements, device_firsts, device_stored, count, max_stored,
+		                                            use_offsets, positions(d), device_unplaced, s));
+		if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_nearest(positions(d), device_firsts, device_stored, count, max_stored, r2, forward(d), backward(d), s));
+		return ok;
+	}
+
+	/* the second event, the tallies back, the second synchronise -- which runs whatever failed before it */
+	bool collect(Device &d, bool ok)
+	{
+		hipStream_t s = d.stream;
+		ok &= HIP_OK(hipEventRecord(d.ops.peaks_end, s));
+		if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + unplaced_at, device_unplaced, tally_bytes, hipMemcpyDeviceToHost, s));
+		ok &= HIP_OK(hipStreamSynchronize(s));
+		return ok;
+	}
+
+	/* the call's device time: mark and scan, and -- `rest`: something was enqueued behind them -- the rest */
+	float device_ms(Device &d, bool rest) const
+	{
+		float rest_ms = 0;
+		if (rest && !HIP_OK(hipEventElapsedTime(&rest_ms, d.ops.peaks_begin, d.ops.peaks_end))) rest_ms = 0;
+		return timed ? mark_ms + rest_ms : 0.0f;
+	}
+};
 
 } // namespace
 
@@ -552,132 +683,150 @@ bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 	static_assert(sizeof(BeamformerHipPeakPair) == 48 && sizeof(BeamformerHipPeakPairs) == 72 && sizeof(BeamformerHipTrackMapInfo) == 40, "records without padding");
 	static_assert(BF_TRACK_MAX_VOXELS == BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS && BF_TRACK_MAX_PEAKS == BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME &&
 	              BF_TRACK_COMPONENTS == BEAMFORMER_HIP_TRACK_MAP_COMPONENTS, "one limit");
-	std::vector<BoxedFrame> boxed;
-	if (!newest_boxed_frames(count, region, boxed)) return false;
+	PeakChoices c;
+	if (!newest_boxed_frames(count, region, c.boxed)) return false;
 	Device &d = ctx().devices[0];
 	FrameOps::TrackMap &map = d.ops.tracks;
 	if (deposit && (!map.buffer.ptr || !map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	PeaksRows table;
-	if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
-	const uint32_t links = count - 1u;
-
-	/* device: rows | placements | results | firsts | stored | block_firsts | unplaced | tallies | masks | counts | offsets; pinned: the
-	 * first eight (rows and placements go up in one copy, firsts, stored and block_firsts in a second, unplaced and tallies come back
-	 * in one: each group stays adjacent) */
-	Carve dev;
-	const size_t rows_at = dev.take(sizeof(BfPeaksRow) * count), placements_at = dev.take(sizeof(double) * 12 * count),
-	             results_at = dev.take(sizeof(BfPeaksResult) * count), firsts_at = dev.take(sizeof(uint32_t) * count),
-	             stored_at = dev.take(sizeof(uint32_t) * count), block_firsts_at = dev.take(sizeof(uint32_t) * links),
-	             unplaced_at = dev.take(sizeof(uint32_t) * count), tallies_at = dev.take(sizeof(BfTrackTally) * links), pinned_bytes = dev.total,
-	             masks_at = dev.take(sizeof(uint64_t) * table.waves), counts_at = dev.take(sizeof(uint32_t) * table.blocks),
-	             offsets_at = dev.take(sizeof(uint32_t) * table.blocks);
-	bool ok = ensure_metrics_memory(d, pinned_bytes, dev.total);
-	if (ok && !d.ops.peaks_begin) ok = HIP_OK(hipEventCreate(&d.ops.peaks_begin));
-	if (ok && !d.ops.peaks_end)   ok = HIP_OK(hipEventCreate(&d.ops.peaks_end));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
-	const BfPeaksRow *device_rows       = (const BfPeaksRow *)(device + rows_at);
-	const double     *device_placements = (const double *)(device + placements_at);
-	BfPeaksResult    *device_results    = (BfPeaksResult *)(device + results_at);
-	const uint32_t   *device_firsts     = (const uint32_t *)(device + firsts_at), *device_stored = (const uint32_t *)(device + stored_at),
-	                 *device_block_firsts = (const uint32_t *)(device + block_firsts_at);
-	uint32_t         *device_unplaced   = (uint32_t *)(device + unplaced_at);
-	BfTrackTally     *device_tallies    = (BfTrackTally *)(device + tallies_at);
-	uint64_t         *device_masks      = (uint64_t *)(device + masks_at);
-	uint32_t         *device_counts     = (uint32_t *)(device + counts_at);
-	uint32_t         *device_offsets    = (uint32_t *)(device + offsets_at);
-	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + results_at);
-	uint32_t *firsts = (uint32_t *)(pinned + firsts_at), *stored = (uint32_t *)(pinned + stored_at), *block_firsts = (uint32_t *)(pinned + block_firsts_at);
-	const uint32_t     *unplaced = (const uint32_t *)(pinned + unplaced_at);
-	const BfTrackTally *tallies  = (const BfTrackTally *)(pinned + tallies_at);
-	std::memcpy(pinned + rows_at, table.rows.data(), sizeof(BfPeaksRow) * count);
-	for (uint32_t n = 0; n < count; n++)
-		std::memcpy(pinned + placements_at + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
-	if (!timed_reduce(d, placements_at + sizeof(double) * 12 * count, results_at, sizeof(BfPeaksResult) * count, nullptr, [&](hipStream_t s) {   /* (its time: read below, with the rest's) */
-		return bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s);
-	})) return false;
-
-	/* what the scan found sizes everything from here on: the records, the positions, the choices, the match pass's blocks, the pairs */
-	uint32_t total = 0, max_stored = 0, blocks = 0;      /* (at most 1024 frames x 65536 records, 256 blocks a frame) */
-	uint64_t capacity = 0;
-	for (uint32_t n = 0; n < count; n++) {
-		stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
-		firsts[n] = total;
-		total += stored[n];
-		if (stored[n] > max_stored) max_stored = stored[n];
-		if (n) capacity += stored[n - 1] < stored[n] ? stored[n - 1] : stored[n];
-		if (n < links) { block_firsts[n] = blocks; blocks += (stored[n] + 255u) / 256u; }
-	}
-	std::memset(pinned + unplaced_at, 0, tallies_at - unplaced_at + sizeof(BfTrackTally) * links);
-	float ms = 0, rest_ms = 0;
-	const bool timed = HIP_OK(hipEventElapsedTime(&ms, d.ops.metrics_begin, d.ops.metrics_end));
+	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, 0)) return false;
+	const uint32_t links = c.links;
 	const double reach = (double)max_distance, r2 = reach * reach;
 	uint64_t total_pairs = 0;
-	if (total) {
-		/* tracks_scratch: positions | forward | backward | masks | words | offsets | pairs */
-		Carve big;
-		const size_t positions_at = big.take(sizeof(double) * 3 * total), forward_at = big.take(sizeof(uint32_t) * total),
-		             backward_at = big.take(sizeof(uint32_t) * total), pair_masks_at = big.take(sizeof(uint64_t) * 4 * blocks),
-		             words_at = big.take(sizeof(uint32_t) * blocks), pair_offsets_at = big.take(sizeof(uint32_t) * blocks),
-		             pairs_at = big.take(pairs ? sizeof(BeamformerHipPeakPair) * (size_t)capacity : 0);
+	if (c.total) {
+		/* tracks_scratch, behind the choices: masks | words | offsets | pairs */
+		const size_t pair_masks_at = c.big.take(sizeof(uint64_t) * 4 * c.blocks), words_at = c.big.take(sizeof(uint32_t) * c.blocks),
+		             pair_offsets_at = c.big.take(sizeof(uint32_t) * c.blocks),
+		             pairs_at = c.big.take(pairs ? sizeof(BeamformerHipPeakPair) * (size_t)c.capacity : 0);
 		hipStream_t s = d.stream;
-		ok = d.ops.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak)) && d.ops.tracks_scratch.ensure(big.total);
+		bool ok = c.ensure(d);
 		if (ok) {
 			char *scratch = (char *)d.ops.tracks_scratch.ptr;
-			double   *positions = (double *)(scratch + positions_at);
-			uint32_t *forward = (uint32_t *)(scratch + forward_at), *backward = (uint32_t *)(scratch + backward_at);
-			void     *device_pairs = pairs && capacity ? scratch + pairs_at : nullptr;
+			void *device_pairs = pairs && c.capacity ? scratch + pairs_at : nullptr;
 			BfTrackArgs a{};
 			for (int k = 0; k < 3; k++) a.points[k] = deposit ? map.points[k] : 0u;
 			a.deposit = deposit != 0;
-			ok &= HIP_OK(hipMemcpyAsync(device + firsts_at, firsts, unplaced_at - firsts_at, hipMemcpyHostToDevice, s));
-			ok &= HIP_OK(hipMemsetAsync(device_unplaced, 0, tallies_at - unplaced_at + sizeof(BfTrackTally) * links, s));
-			ok &= HIP_OK(hipEventRecord(d.ops.peaks_begin, s));
-			if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets,
-			                                                device_firsts, d.ops.peaks_list.ptr, s));
-			if (ok) ok &= HIP_OK(bf_launch_tracks_place(d.ops.peaks_list.ptr, device_placements, device_firsts, device_stored, count, max_stored,
-			                                            use_offsets != 0, positions, device_unplaced, s));
-			/* (no frame pair with peaks on both sides: nothing to choose from, every tally stays 0) */
-			if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_nearest(positions, device_firsts, device_stored, count, max_stored, r2, forward, backward, s));
-			if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_pair(positions, device_firsts, device_stored, device_block_firsts, count, max_stored, blocks,
-			                                                       forward, backward, (uint64_t *)(scratch + pair_masks_at), (uint32_t *)(scratch + words_at),
-			                                                       (uint32_t *)(scratch + pair_offsets_at), &a, (uint32_t *)map.buffer.ptr,
-			                                                       deposit ? (char *)map.buffer.ptr + map.sums_at() : nullptr, device_pairs, device_tallies, s));
-			ok &= HIP_OK(hipEventRecord(d.ops.peaks_end, s));
-			if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + unplaced_at, device_unplaced, tallies_at - unplaced_at + sizeof(BfTrackTally) * links,
-			                                    hipMemcpyDeviceToHost, s));
-			ok &= HIP_OK(hipStreamSynchronize(s));
-			for (uint32_t n = 0; n < links && ok; n++) total_pairs += tallies[n].pairs;
+			ok = c.enqueue(d, use_offsets != 0, r2);
+			/* (no frame pair with peaks on both sides: every tally stays 0) */
+			if (ok && c.capacity) ok &= HIP_OK(bf_launch_tracks_pair(c.positions(d), c.device_firsts, c.device_stored, c.device_block_firsts, count, c.max_stored,
+			                                                         c.blocks, c.forward(d), c.backward(d), (uint64_t *)(scratch + pair_masks_at),
+			                                                         (uint32_t *)(scratch + words_at), (uint32_t *)(scratch + pair_offsets_at), &a,
+			                                                         (uint32_t *)map.buffer.ptr, deposit ? (char *)map.buffer.ptr + map.sums_at() : nullptr,
+			                                                         device_pairs, c.device_tallies, s));
+			ok = c.collect(d, ok);
+			for (uint32_t n = 0; n < links && ok; n++) total_pairs += c.tallies[n].pairs;
 			if (ok && pairs && total_pairs) {
-				ok = total_pairs <= capacity;                             /* (what the kernels promise: the copy below relies on it) */
+				ok = total_pairs <= c.capacity;                           /* (what the kernels promise: the copy below relies on it) */
 				ok = ok && HIP_OK(hipMemcpyAsync(pairs, device_pairs, (size_t)total_pairs * sizeof(BeamformerHipPeakPair), hipMemcpyDeviceToHost, s));
 				ok &= HIP_OK(hipStreamSynchronize(s));
 			}
 		}
 		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-		if (!HIP_OK(hipEventElapsedTime(&rest_ms, d.ops.peaks_begin, d.ops.peaks_end))) rest_ms = 0;
 	}
-	if (device_ms) *device_ms = timed ? ms + rest_ms : 0.0f;
+	if (device_ms) *device_ms = c.device_ms(d, c.total != 0);
 
 	uint32_t first = 0;
 	for (uint32_t n = 0; n < links; n++) {
 		BeamformerHipPeakPairs &m = rows[n];
-		const BfTrackTally &t = tallies[n];
+		const BfTrackTally &t = c.tallies[n];
 		std::memset(&m, 0, sizeof(m));
 		for (uint32_t k = 0; k < 2; k++) {
-			m.frame_id[k] = boxed[n + k].record->id;
+			m.frame_id[k] = c.boxed[n + k].record->id;
 			m.threshold[k] = thresholds[threshold_count == 1 ? 0 : n + k];
-			m.peaks[k] = stored[n + k]; m.found[k] = results[n + k].found;
-			m.unplaced[k] = unplaced[n + k];
-			m.unpaired[k] = stored[n + k] - unplaced[n + k] - t.pairs;
+			m.peaks[k] = c.stored[n + k]; m.found[k] = c.results[n + k].found;
+			m.unplaced[k] = c.unplaced[n + k];
+			m.unpaired[k] = c.stored[n + k] - c.unplaced[n + k] - t.pairs;
 		}
 		m.first = first; m.pairs = t.pairs; m.deposited = t.deposited; m.outside = t.outside;
 		first += t.pairs;
 		if (deposit) { map.pairs += t.pairs; map.deposited += t.deposited; map.outside += t.outside; }
 	}
-	if (deposit) { map.calls++; map.block = boxed[count - 1].record->block; }
+	if (deposit) { map.calls++; map.block = c.boxed[count - 1].record->block; }
 	*pair_count = first;
+	return true;
+}
+
+/* beamformer_hip_track_peaks_last_frames: the pairs of the `count` newest frames chained into tracks, the tracks of at least min_length
+ * peaks listed and deposited (frame_tracks.hip: link, jump, keep, scan, finish, behind the launches pair_peaks_last_frames shares with
+ * this call -- its own match, scan and emit are not needed: the chains are read off the choices).  The arguments arrive checked
+ * (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Three synchronises at the most, for the pair
+ * call's reasons: the buffers are sized by what the scan found -- the two record lists by ALL stored records, an upper bound --, and
+ * the two downloads by the tallies. */
+bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
+                             uint32_t max_per_frame, uint32_t min_length, uint32_t deposit, BeamformerHipTrackedFrame *rows,
+                             BeamformerHipPeakTrack *tracks, BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count,
+                             float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipPeakTrack) == 48 && sizeof(BeamformerHipTrackPoint) == 40 && sizeof(BeamformerHipTrackedFrame) == 56, "records without padding");
+	static_assert(BF_CHAIN_POINTS == BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS && BF_CHAIN_LINKS == BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS, "one pair of bits");
+	PeakChoices c;
+	if (!newest_boxed_frames(count, region, c.boxed)) return false;
+	Device &d = ctx().devices[0];
+	FrameOps::LocalisationMap &point_map = d.ops.map;
+	FrameOps::TrackMap &link_map = d.ops.tracks;
+	const bool with_points = deposit & BF_CHAIN_POINTS, with_links = deposit & BF_CHAIN_LINKS;
+	if (with_points && (!point_map.buffer.ptr || !point_map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (with_links && (!link_map.buffer.ptr || !link_map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, sizeof(BfChainTally) * count)) return false;
+	const BfChainTally *tallies = (const BfChainTally *)c.extra;
+	const double reach = (double)max_distance, r2 = reach * reach;
+	uint64_t total_tracks = 0, total_points = 0;
+	if (c.total) {
+		/* tracks_scratch, behind the choices: next | links, twice | lengths | tails | track_of | first_of | words | offsets | tracks | points */
+		const size_t each = sizeof(uint32_t) * c.total, chain_blocks = ((size_t)c.total + 255u) / 256u;
+		const size_t next_at = c.big.take(each), links_at = c.big.take(4 * each), lengths_at = c.big.take(each), tails_at = c.big.take(each),
+		             track_of_at = c.big.take(each), first_of_at = c.big.take(each), words_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks),
+		             offsets_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks),
+		             tracks_at = c.big.take(tracks ? sizeof(BeamformerHipPeakTrack) * (size_t)c.total : 0),
+		             points_at = c.big.take(points ? sizeof(BeamformerHipTrackPoint) * (size_t)c.total : 0);
+		hipStream_t s = d.stream;
+		bool ok = c.ensure(d);
+		if (ok) {
+			char *scratch = (char *)d.ops.tracks_scratch.ptr;
+			void *device_tracks = tracks ? scratch + tracks_at : nullptr, *device_points = points ? scratch + points_at : nullptr;
+			BfChainArgs a{};
+			for (int k = 0; k < 3; k++) { a.point_map[k] = with_points ? point_map.points[k] : 0u; a.track_map[k] = with_links ? link_map.points[k] : 0u; }
+			a.deposit = deposit; a.min_length = min_length;
+			ok = c.enqueue(d, use_offsets != 0, r2);
+			if (ok) ok &= HIP_OK(bf_launch_tracks_chain(c.positions(d), c.device_firsts, c.device_stored, count, c.max_stored, c.total,
+			                                            c.capacity ? c.forward(d) : nullptr, c.capacity ? c.backward(d) : nullptr,
+			                                            (uint32_t *)(scratch + next_at), scratch + links_at, (uint32_t *)(scratch + lengths_at),
+			                                            (uint32_t *)(scratch + tails_at), (uint32_t *)(scratch + track_of_at),
+			                                            (uint32_t *)(scratch + first_of_at), (uint32_t *)(scratch + words_at),
+			                                            (uint32_t *)(scratch + offsets_at), &a, with_points ? (uint32_t *)point_map.buffer.ptr : nullptr,
+			                                            with_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
+			                                            with_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr, device_tracks,
+			                                            device_points, (BfChainTally *)c.device_extra, s));
+			ok = c.collect(d, ok);
+			for (uint32_t n = 0; n < count && ok; n++) { total_tracks += tallies[n].kept_heads; total_points += tallies[n].kept_points; }
+			ok = ok && total_tracks <= c.total && total_points <= c.total;      /* (what the kernels promise: the copies below rely on it) */
+			const bool tracks_back = tracks && total_tracks, points_back = points && total_points;
+			if (ok && tracks_back)
+				ok = HIP_OK(hipMemcpyAsync(tracks, device_tracks, (size_t)total_tracks * sizeof(BeamformerHipPeakTrack), hipMemcpyDeviceToHost, s));
+			if (ok && points_back)
+				ok = HIP_OK(hipMemcpyAsync(points, device_points, (size_t)total_points * sizeof(BeamformerHipTrackPoint), hipMemcpyDeviceToHost, s));
+			if (tracks_back || points_back) ok &= HIP_OK(hipStreamSynchronize(s));
+		}
+		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	}
+	if (device_ms) *device_ms = c.device_ms(d, c.total != 0);
+
+	for (uint32_t n = 0; n < count; n++) {
+		BeamformerHipTrackedFrame &m = rows[n];
+		const BfChainTally &t = tallies[n];
+		std::memset(&m, 0, sizeof(m));
+		m.frame_id = c.boxed[n].record->id; m.threshold = thresholds[threshold_count == 1 ? 0 : n];
+		m.peaks = c.stored[n]; m.unplaced = c.unplaced[n];
+		m.heads = t.heads; m.kept_heads = t.kept_heads; m.kept_points = t.kept_points; m.kept_links = t.kept_links;
+		m.points_deposited = t.points_deposited; m.points_outside = t.points_outside;
+		m.links_deposited = t.links_deposited; m.links_outside = t.links_outside;
+		m.found = c.results[n].found;
+		if (with_points) { point_map.deposited += t.points_deposited; point_map.outside += t.points_outside; }
+		if (with_links) { link_map.pairs += t.kept_links; link_map.deposited += t.links_deposited; link_map.outside += t.links_outside; }
+	}
+	if (with_points) { point_map.calls++; point_map.block = c.boxed[count - 1].record->block; }
+	if (with_links) { link_map.calls++; link_map.block = c.boxed[count - 1].record->block; }
+	*track_count = (uint32_t)total_tracks; *point_count = (uint32_t)total_points;
 	return true;
 }
 

@@ -1,6 +1,7 @@
 /* frame_tracks.hip -- the peaks of consecutive frames of the frame ring linked into pairs (beamformer_hip_pair_peaks_last_frames: the
- * velocity map of ULM and the rejection of detections that do not persist, without a peak list leaving the device), and the track map's
- * frame (beamformer_hip_queue_track_map).
+ * velocity map of ULM and the rejection of detections that do not persist, without a peak list leaving the device), the pairs chained
+ * into tracks and kept by length (beamformer_hip_track_peaks_last_frames: the chain kernels have their own comment further down), and
+ * the track map's frame (beamformer_hip_queue_track_map).
  *
  * DEFINITION (include/ogl_beamformer_hip.h has it for callers; tests/tracks_ref.py is its numpy restatement).  A frame's peaks are the
  * records frame_peaks.hip emits (the caller runs its mark, scan and emit passes in front of these launches); a peak's rank is its place
@@ -255,6 +256,190 @@ __global__ __launch_bounds__(256) void tracks_convert_kernel(const uint32_t *__r
 	}
 }
 
+/* ---- the pairs chained into tracks (beamformer_hip_track_peaks_last_frames).  A record's GLOBAL index is i = firsts[frame] + rank: the
+ * lists are packed frame after frame, so ascending i is ascending (frame, rank), the ORDER of the definition.
+ * Link: a lane a record; from forward[] and backward[] it forms next[i] -- the mutual partner in the newer frame, or NONE -- and the
+ * pair (anc, pos): the mutual partner in the older frame and 1, or i itself and 0 for a head; an unplaced peak (a NaN coordinate)
+ * carries anc = NONE and takes part in nothing.
+ * Jump: pointer jumping, R = ceil(log2(frames)) launches over all records, from one buffer into the other and never in place:
+ * (anc, pos)'[i] = (anc[anc[i]], pos[i] + pos[anc[i]]), one 8-byte gather a record a round.  A chain is at most frames - 1 < 2^R links
+ * deep, so after R rounds anc is the head and pos the place in the track -- instead of walking a chain head by head, up to 1023
+ * dependent loads on one lane.  The LAST round also lets the tails (next == NONE) store length[head] = pos + 1 and tail_of[head] = i:
+ * one writer a head, no atomic; a launch of its own would read (anc, pos) once more for nothing.
+ * Keep: blocks of 256 records in global order.  A kept head (anc == i, length >= min_length) gets its number among the block's kept
+ * heads (a ballot) and the sum of their lengths before it (a scan), every other record NONE for a number; the block's two totals -- at most 256, and at most 2^18 -- go
+ * through tracks_scan_kernel, launched twice.
+ * Finish: grid y the frame, so that a wave's ballots are one frame's.  Every record whose head has a number: its track is that number
+ * plus its block's offset, its place first_of[head] + pos -- both functions of the records alone, no atomic decides a place --; it
+ * stores its 40-byte record, deposits its point by the localisation map's BIN rule and its link by tracks_emit_kernel's expressions
+ * (contraction off), and a head stores the 48-byte track record as well.  One kernel instead of a heads pass and a points pass: a head
+ * is a point, both read the same tables, and the heads pass would only have stored two words for the points pass to load again.
+ * The per-frame tallies: ballots, one integer atomic a wave a counter -- counts, never places. */
+namespace {
+
+struct ChainTrack { uint32_t frame, rank, length, first, flags, reserved; double displacement[3]; };
+struct ChainPoint { uint32_t track, frame, rank, deposited; double position[3]; };
+static_assert(sizeof(ChainTrack) == 48 && sizeof(ChainPoint) == 40, "BeamformerHipPeakTrack's and BeamformerHipTrackPoint's layout");
+
+} // namespace
+
+__global__ __launch_bounds__(256) void tracks_link_kernel(const double *__restrict__ positions, const uint32_t *__restrict__ firsts,
+                                                          const uint32_t *__restrict__ stored, uint32_t frames,
+                                                          const uint32_t *__restrict__ forward, const uint32_t *__restrict__ backward,
+                                                          uint32_t *__restrict__ next, uint2 *__restrict__ links, uint32_t *__restrict__ lengths)
+{
+	const uint32_t frame = blockIdx.y, n = stored[frame], k = blockIdx.x * 256u + threadIdx.x;
+	if (k >= n) return;
+	const uint32_t i = firsts[frame] + k;
+	uint32_t newer = BF_TRACK_NONE, anc = BF_TRACK_NONE, pos = 0;
+	if (is_finite(positions[3ull * i])) {                                /* (an unplaced peak: NaN all three) */
+		anc = i;
+		if (forward && frame + 1u < frames) {
+			const uint32_t first_b = firsts[frame + 1u], b = forward[i];
+			if (b != BF_TRACK_NONE && backward[(uint64_t)first_b + b] == k) newer = first_b + b;
+		}
+		if (forward && frame) {
+			const uint32_t first_a = firsts[frame - 1u], a = backward[i];
+			if (a != BF_TRACK_NONE && forward[(uint64_t)first_a + a] == k) { anc = first_a + a; pos = 1u; }
+		}
+	}
+	next[i] = newer;
+	links[i] = make_uint2(anc, pos);
+	lengths[i] = 0;                                                      /* (a head's is stored by its tail, behind the last jump) */
+}
+
+__global__ __launch_bounds__(256) void tracks_jump_kernel(const uint2 *__restrict__ in, uint2 *__restrict__ out, uint32_t total,
+                                                          const uint32_t *__restrict__ next, uint32_t last, uint32_t *__restrict__ lengths,
+                                                          uint32_t *__restrict__ tails)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= total) return;
+	uint2 me = in[i];
+	if (me.x != BF_TRACK_NONE && me.x != i) {
+		const uint2 up = in[me.x];
+		me = make_uint2(up.x, me.y + up.y);
+	}
+	out[i] = me;
+	if (last && me.x != BF_TRACK_NONE && next[i] == BF_TRACK_NONE) { lengths[me.x] = me.y + 1u; tails[me.x] = i; }
+}
+
+__global__ __launch_bounds__(256) void tracks_keep_kernel(const uint2 *__restrict__ links, const uint32_t *__restrict__ lengths, uint32_t total,
+                                                          uint32_t min_length, uint32_t *__restrict__ track_of, uint32_t *__restrict__ first_of,
+                                                          uint32_t *__restrict__ track_words, uint32_t *__restrict__ point_words)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint32_t length = 0;
+	if (i < total && links[i].x == i) length = lengths[i];
+	const bool kept = length && length >= min_length;
+	if (!kept) length = 0;
+	const uint64_t mask = __ballot(kept);
+	uint32_t upto = length;
+	for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(upto, off, 64); if (lane >= (uint32_t)off) upto += v; }
+	__shared__ uint32_t wave_tracks[4], wave_points[4];
+	if (lane == 63) { wave_tracks[wave] = (uint32_t)__popcll(mask); wave_points[wave] = upto; }
+	__syncthreads();
+	uint32_t tracks_before = 0, points_before = 0, all_tracks = 0, all_points = 0;
+	for (uint32_t j = 0; j < 4; j++) {
+		const uint32_t t = wave_tracks[j], p = wave_points[j];
+		if (j < wave) { tracks_before += t; points_before += p; }
+		all_tracks += t; all_points += p;
+	}
+	/* track_of says for EVERY record whether it is a kept head: the one place where a length meets min_length */
+	if (i < total) track_of[i] = kept ? tracks_before + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)) : BF_TRACK_NONE;
+	if (kept) first_of[i] = points_before + (upto - length);
+	if (threadIdx.x == 0) { track_words[blockIdx.x] = all_tracks; point_words[blockIdx.x] = all_points; }
+}
+
+__global__ __launch_bounds__(256) void tracks_finish_kernel(const double *__restrict__ positions, const uint32_t *__restrict__ firsts,
+                                                            const uint32_t *__restrict__ stored, uint32_t frames, const uint2 *__restrict__ links,
+                                                            const uint32_t *__restrict__ next, const uint32_t *__restrict__ lengths,
+                                                            const uint32_t *__restrict__ tails, const uint32_t *__restrict__ track_of,
+                                                            const uint32_t *__restrict__ first_of, const uint32_t *__restrict__ track_offsets,
+                                                            const uint32_t *__restrict__ point_offsets, BfChainArgs t, uint32_t *__restrict__ point_map,
+                                                            uint32_t *__restrict__ map_counts, unsigned long long *__restrict__ map_sums,
+                                                            ChainTrack *__restrict__ tracks, ChainPoint *__restrict__ points,
+                                                            BfChainTally *__restrict__ tallies)
+{
+	#pragma clang fp contract(off)
+	const uint32_t frame = blockIdx.y, n = stored[frame], k = blockIdx.x * 256u + threadIdx.x;
+	if (blockIdx.x * 256u >= n) return;
+	bool head = false, kept = false, linked = false, point_in = false, link_in = false;
+	if (k < n) {
+		const uint32_t i = firsts[frame] + k;
+		const uint2 me = links[i];
+		if (me.x != BF_TRACK_NONE) {
+			const uint32_t h = me.x, number = track_of[h];
+			head = h == i;
+			kept = number != BF_TRACK_NONE;
+			if (kept) {
+				const uint32_t length = lengths[h], track = track_offsets[h >> 8] + number, place = point_offsets[h >> 8] + first_of[h] + me.y, newer = next[i];
+				linked = newer != BF_TRACK_NONE;
+				const double *m = positions + 3ull * i;
+				const double u[3] = {m[0], m[1], m[2]};
+				if (t.deposit & BF_CHAIN_POINTS) {
+					/* the localisation map's BIN rule (frame_peaks.hip), on the coordinate the place pass formed by its formula */
+					uint32_t bin[3];
+					point_in = true;
+					#pragma unroll
+					for (int r = 0; r < 3; r++) {
+						const double b = __builtin_floor(u[r] + 0.5);
+						const bool in = b >= 0.0 && b < (double)t.point_map[r];
+						bin[r] = in ? (uint32_t)b : 0u;
+						point_in &= in;
+					}
+					if (point_in) atomicAdd(point_map + (((uint64_t)bin[2] * t.point_map[1] + bin[1]) * t.point_map[0] + bin[0]), 1u);
+				}
+				if (linked && (t.deposit & BF_CHAIN_LINKS)) {
+					/* tracks_emit_kernel's deposit, expression for expression */
+					const double *mb = positions + 3ull * newer;
+					double d[3], c[3];
+					#pragma unroll
+					for (int r = 0; r < 3; r++) { const double v = mb[r]; d[r] = v - u[r]; c[r] = 0.5 * (u[r] + v); }
+					uint32_t bin[3];
+					link_in = true;
+					#pragma unroll
+					for (int r = 0; r < 3; r++) {
+						const double at = __builtin_floor(c[r] + 0.5);
+						const bool in = at >= 0.0 && at < (double)t.track_map[r];
+						bin[r] = in ? (uint32_t)at : 0u;
+						link_in &= in;
+					}
+					if (link_in) {
+						const uint64_t voxels = (uint64_t)t.track_map[0] * t.track_map[1] * t.track_map[2];
+						const uint64_t at = ((uint64_t)bin[2] * t.track_map[1] + bin[1]) * t.track_map[0] + bin[0];
+						atomicAdd(map_counts + at, 1u);
+						#pragma unroll
+						for (int r = 0; r < 3; r++) {
+							const long long q = (long long)__builtin_floor(d[r] * BF_TRACK_FIXED + 0.5);
+							atomicAdd(map_sums + r * voxels + at, (unsigned long long)q);
+						}
+					}
+				}
+				if (points) {
+					ChainPoint &p = points[place];
+					p.track = track; p.frame = frame; p.rank = k; p.deposited = (point_in ? 1u : 0u) | (link_in ? 2u : 0u);
+					p.position[0] = u[0]; p.position[1] = u[1]; p.position[2] = u[2];
+				}
+				if (head && tracks) {
+					const double *mt = positions + 3ull * tails[h];
+					ChainTrack &r = tracks[track];
+					r.frame = frame; r.rank = k; r.length = length; r.first = place;
+					r.flags = (frame == 0 ? 1u : 0u) | (frame + length == frames ? 2u : 0u); r.reserved = 0;
+					r.displacement[0] = mt[0] - u[0]; r.displacement[1] = mt[1] - u[1]; r.displacement[2] = mt[2] - u[2];
+				}
+			}
+		}
+	}
+	const bool with_points = kept && (t.deposit & BF_CHAIN_POINTS), with_links = kept && linked && (t.deposit & BF_CHAIN_LINKS);
+	const uint64_t lanes[8] = {__ballot(head), __ballot(head && kept), __ballot(kept), __ballot(kept && linked), __ballot(point_in),
+	                           __ballot(with_points && !point_in), __ballot(link_in), __ballot(with_links && !link_in)};
+	if ((threadIdx.x & 63u) == 0) {
+		uint32_t *tally = (uint32_t *)(tallies + frame);                 /* (eight counters, in the ballots' order) */
+		#pragma unroll
+		for (int c = 0; c < 8; c++) if (lanes[c]) atomicAdd(tally + c, (unsigned int)__popcll(lanes[c]));
+	}
+}
+
 namespace {
 
 bool grid_fits(uint32_t frames, uint32_t max_stored)
@@ -323,5 +508,52 @@ extern "C" hipError_t bf_launch_track_convert(const uint32_t *counts, const void
 	const uint64_t blocks = (voxels + 255u) / 256u;
 	hipLaunchKernelGGL(tracks_convert_kernel, dim3((uint32_t)(blocks < 4096u ? blocks : 4096u)), dim3(256), 0, s, counts, (const long long *)sums, out,
 	                   voxels, component, min_pairs ? min_pairs : 1u, scale);
+	return hipGetLastError();
+}
+
+/* (bf_kernels.h says what every table is) */
+extern "C" hipError_t bf_launch_tracks_chain(const double *positions, const uint32_t *firsts, const uint32_t *stored, uint32_t frames,
+                                             uint32_t max_stored, uint32_t total, const uint32_t *forward, const uint32_t *backward, uint32_t *next,
+                                             void *links, uint32_t *lengths, uint32_t *tails, uint32_t *track_of, uint32_t *first_of, uint32_t *words,
+                                             uint32_t *offsets, const BfChainArgs *a, uint32_t *point_map, uint32_t *track_counts, void *track_sums,
+                                             void *tracks, void *points, BfChainTally *tallies, hipStream_t s)
+{
+	static_assert(sizeof(BfChainTally) == 32, "eight counters");
+	if (!positions || !firsts || !stored || !next || !links || ((uintptr_t)links & 7u) || !lengths || !tails || !track_of || !first_of || !words ||
+	    !offsets || !a || !tallies || ((uintptr_t)tracks & 7u) || ((uintptr_t)points & 7u) || !grid_fits(frames, max_stored) || total == 0 ||
+	    total > (1u << 26) || (forward == nullptr) != (backward == nullptr) || a->min_length == 0 || (a->deposit & ~(BF_CHAIN_POINTS | BF_CHAIN_LINKS)))
+		return hipErrorInvalidValue;
+	if ((a->deposit & BF_CHAIN_POINTS) && (!point_map || !a->point_map[0] || !a->point_map[1] || !a->point_map[2] ||
+	                                       (uint64_t)a->point_map[0] * a->point_map[1] > BF_MAP_MAX_VOXELS ||
+	                                       (uint64_t)a->point_map[0] * a->point_map[1] * a->point_map[2] > BF_MAP_MAX_VOXELS)) return hipErrorInvalidValue;
+	if ((a->deposit & BF_CHAIN_LINKS) && (!track_counts || !track_sums || !a->track_map[0] || !a->track_map[1] || !a->track_map[2] ||
+	                                      (uint64_t)a->track_map[0] * a->track_map[1] > BF_TRACK_MAX_VOXELS ||
+	                                      (uint64_t)a->track_map[0] * a->track_map[1] * a->track_map[2] > BF_TRACK_MAX_VOXELS)) return hipErrorInvalidValue;
+	const dim3 by_frame((max_stored + 255u) / 256u, frames);
+	const uint32_t blocks = (total + 255u) / 256u;
+	uint2 *ping = (uint2 *)links, *pong = ping + total;
+	hipLaunchKernelGGL(tracks_link_kernel, by_frame, dim3(256), 0, s, positions, firsts, stored, frames, forward, backward, next, ping, lengths);
+	hipError_t e = hipGetLastError();
+	uint32_t rounds = 0;
+	while ((1u << rounds) < frames) rounds++;                            /* frames >= 2: at least one, which is also the tails' */
+	for (uint32_t r = 0; r < rounds && e == hipSuccess; r++) {
+		hipLaunchKernelGGL(tracks_jump_kernel, dim3(blocks), dim3(256), 0, s, (const uint2 *)ping, pong, total, (const uint32_t *)next,
+		                   r + 1u == rounds ? 1u : 0u, lengths, tails);
+		e = hipGetLastError();
+		uint2 *swap = ping; ping = pong; pong = swap;                    /* ping: what the next launch reads */
+	}
+	if (e != hipSuccess) return e;
+	uint32_t *track_words = words, *point_words = words + blocks, *track_offsets = offsets, *point_offsets = offsets + blocks;
+	hipLaunchKernelGGL(tracks_keep_kernel, dim3(blocks), dim3(256), 0, s, (const uint2 *)ping, (const uint32_t *)lengths, total, a->min_length, track_of,
+	                   first_of, track_words, point_words);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL(tracks_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)track_words, blocks, track_offsets);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL(tracks_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)point_words, blocks, point_offsets);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL(tracks_finish_kernel, by_frame, dim3(256), 0, s, positions, firsts, stored, frames, (const uint2 *)ping, (const uint32_t *)next,
+	                   (const uint32_t *)lengths, (const uint32_t *)tails, (const uint32_t *)track_of, (const uint32_t *)first_of,
+	                   (const uint32_t *)track_offsets, (const uint32_t *)point_offsets, *a, point_map, track_counts, (unsigned long long *)track_sums,
+	                   (ChainTrack *)tracks, (ChainPoint *)points, tallies);
 	return hipGetLastError();
 }

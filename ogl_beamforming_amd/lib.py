@@ -147,6 +147,9 @@ def _load():
         "beamformer_hip_pair_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
                                                         C.c_float, u32, u32, C.POINTER(P.HipPeakPairs), C.POINTER(P.HipPeakPair), C.POINTER(u32),
                                                         C.POINTER(C.c_float)]),
+        "beamformer_hip_track_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
+                                                         C.c_float, u32, u32, u32, C.POINTER(P.HipTrackedFrame), C.POINTER(P.HipPeakTrack),
+                                                         C.POINTER(P.HipTrackPoint), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_track_map_copy": (u32, [C.POINTER(u32), C.POINTER(C.c_int64), u64, C.POINTER(P.HipTrackMapInfo)]),
         "beamformer_hip_queue_track_map": (u32, [u32, C.c_float, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
@@ -707,6 +710,38 @@ def pair_peaks_last_frames(count, thresholds, placements, max_distance, max_per_
     kept = int(total.value) if records else 0
     pairs = (P.HipPeakPair * kept).from_buffer_copy(out[:kept].tobytes())
     return rows, pairs, float(ms.value)
+
+
+def track_peaks_last_frames(count, thresholds, placements, max_distance, max_per_frame, min_length, use_offsets=True, deposit=0, region=None,
+                            records=True):
+    """beamformer_hip_track_peaks_last_frames: the pairs of pair_peaks_last_frames (same arguments up to max_per_frame) chained over the
+    `count` newest frames into tracks -- a head, its links toward newer frames, no gap closing --, of which those of at least
+    min_length peaks are kept, listed in ascending (start frame, head's rank) and deposited: deposit is 0 or any of
+    P.HIP_TRACK_DEPOSIT_POINTS (the kept tracks' peaks into the localisation map) and P.HIP_TRACK_DEPOSIT_LINKS (their pairs into the
+    track map).  Returns (rows, tracks, points, device_ms): a ctypes array of `count` HipTrackedFrame rows, ctypes arrays of the
+    HipPeakTrack and the HipTrackPoint records (track t's points are points[tracks[t].first : tracks[t].first + tracks[t].length];
+    both empty with records False: the call downloads none) and the device time of the launches."""
+    count, max_per_frame = int(count), int(max_per_frame)
+    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
+    levels = (C.c_float * max(1, len(values)))(*values)
+    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
+    if matrices.size % 12:
+        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    rows = (P.HipTrackedFrame * max(1, count))()
+    room = count * max_per_frame if records and 2 <= count <= P.HIP_MAX_SCORED_FRAMES and 0 < max_per_frame <= P.HIP_MAX_PEAKS_PER_FRAME else 0
+    out_tracks, out_points = np.zeros(max(1, room), np.dtype(P.HipPeakTrack)), np.zeros(max(1, room), np.dtype(P.HipTrackPoint))
+    track_total, point_total, ms = C.c_uint32(0), C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_track_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
+                                                            matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
+                                                            1 if use_offsets else 0, float(max_distance), max_per_frame, int(min_length),
+                                                            int(deposit), rows,
+                                                            out_tracks.ctypes.data_as(C.POINTER(P.HipPeakTrack)) if records else None,
+                                                            out_points.ctypes.data_as(C.POINTER(P.HipTrackPoint)) if records else None,
+                                                            C.byref(track_total), C.byref(point_total), C.byref(ms)))
+    kept_tracks, kept_points = (int(track_total.value), int(point_total.value)) if records else (0, 0)
+    tracks = (P.HipPeakTrack * kept_tracks).from_buffer_copy(out_tracks[:kept_tracks].tobytes())
+    points = (P.HipTrackPoint * kept_points).from_buffer_copy(out_points[:kept_points].tobytes())
+    return rows, tracks, points, float(ms.value)
 
 
 def track_map_copy(points=None):

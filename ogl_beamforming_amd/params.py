@@ -385,6 +385,30 @@ class HipTrackMapInfo(C.Structure):
     _fields_ = [("points", C.c_uint32 * 3), ("calls", C.c_uint32), ("pairs", C.c_uint64), ("deposited", C.c_uint64), ("outside", C.c_uint64)]
 
 
+HIP_TRACK_DEPOSIT_POINTS = 1           # BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS
+HIP_TRACK_DEPOSIT_LINKS = 2            # BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS
+
+
+class HipPeakTrack(C.Structure):
+    """BeamformerHipPeakTrack: one kept track of beamformer_hip_track_peaks_last_frames (48 bytes, no padding)"""
+    _fields_ = [("frame", C.c_uint32), ("rank", C.c_uint32), ("length", C.c_uint32), ("first", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("displacement", C.c_double * 3)]
+
+
+class HipTrackPoint(C.Structure):
+    """BeamformerHipTrackPoint: one peak of a kept track of beamformer_hip_track_peaks_last_frames (40 bytes, no padding)"""
+    _fields_ = [("track", C.c_uint32), ("frame", C.c_uint32), ("rank", C.c_uint32), ("deposited", C.c_uint32), ("position", C.c_double * 3)]
+
+
+class HipTrackedFrame(C.Structure):
+    """BeamformerHipTrackedFrame: one frame's row of beamformer_hip_track_peaks_last_frames (56 bytes, no padding)"""
+    _fields_ = [("frame_id", C.c_uint32), ("threshold", C.c_float), ("peaks", C.c_uint32), ("unplaced", C.c_uint32), ("heads", C.c_uint32),
+                ("kept_heads", C.c_uint32), ("kept_points", C.c_uint32), ("kept_links", C.c_uint32), ("points_deposited", C.c_uint32),
+                ("points_outside", C.c_uint32), ("links_deposited", C.c_uint32), ("links_outside", C.c_uint32), ("found", C.c_uint64)]
+
+
+assert C.sizeof(HipPeakTrack) == 48 and C.sizeof(HipTrackPoint) == 40 and C.sizeof(HipTrackedFrame) == 56
+
 HIP_MAX_ENSEMBLE_FRAMES = 256
 HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
 HIP_MAX_SPATIAL_TAPS = 33       # BEAMFORMER_HIP_MAX_SPATIAL_TAPS
