@@ -723,7 +723,7 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_accumulate_peaks_last_frames(uint3
                                                                            float *device_ms);
 typedef struct {
 	uint32_t points[3];
-	uint32_t calls;                           /* successful beamformer_hip_accumulate_peaks_last_frames calls, and beamformer_hip_track_peaks_last_frames calls with BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS, since the reset */
+	uint32_t calls;                           /* successful beamformer_hip_accumulate_peaks_last_frames calls, and beamformer_hip_track_peaks_last_frames or beamformer_hip_draw_tracks_last_frames calls with BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS, since the reset */
 	uint64_t deposited, outside;              /* their totals */
 } BeamformerHipMapInfo;                       /* 32 bytes, no padding */
 /* The map's counts as they are, copied to out[out_count] behind everything enqueued on the current stream (one synchronise); *info
@@ -837,7 +837,7 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_pair_peaks_last_frames(uint32_t co
                                                                      uint32_t *pair_count, float *device_ms);
 typedef struct {
 	uint32_t points[3];
-	uint32_t calls;                           /* successful beamformer_hip_pair_peaks_last_frames calls with deposit != 0, and beamformer_hip_track_peaks_last_frames calls with BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS, since the reset */
+	uint32_t calls;                           /* successful beamformer_hip_pair_peaks_last_frames calls with deposit != 0, and beamformer_hip_track_peaks_last_frames or beamformer_hip_draw_tracks_last_frames calls with BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS, since the reset */
 	uint64_t pairs, deposited, outside;       /* their totals: pairs == deposited + outside */
 } BeamformerHipTrackMapInfo;                  /* 40 bytes, no padding */
 /* The track map as it is, behind everything enqueued on the current stream (one synchronise): counts[out_count] and sums[3 * voxels]
@@ -934,6 +934,71 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_track_peaks_last_frames(uint32_t c
                                                                       BeamformerHipPeakTrack *tracks /* may be NULL; room for count * max_per_frame */,
                                                                       BeamformerHipTrackPoint *points /* may be NULL; room for count * max_per_frame */,
                                                                       uint32_t *track_count, uint32_t *point_count, float *device_ms);
+
+/* ---- drawn tracks: the kept tracks RASTERISED into both maps on the device.  Both maps are several times finer than the frames: a
+ * bubble that moves one frame voxel a frame leaves, through the track call's DEPOSIT, one bin every 5 to 10 map cells -- a dotted
+ * vessel, a velocity map with holes.  Every published ULM pipeline interpolates a kept track at map resolution before it accumulates
+ * it, usually behind a short moving average along the track; this call does both where the kept tracks' points already lie, instead
+ * of both record lists being downloaded and drawn on the host, every ensemble ----
+ * DEFINITION (tests/track_draw_ref.py restates it in numpy, on top of tests/track_chains_ref.py).  Everything is double or integer
+ * arithmetic in a fixed order, no fused multiply-add.
+ * TRACKS, KEPT, ORDER are beamformer_hip_track_peaks_last_frames', byte for byte: the same launches run.  A kept track of ONE point has
+ * no link and draws nothing: it counts in `lone`.
+ * SMOOTH, half-width w.  Point i of a kept track with the points m_0 .. m_{L-1} (map coordinates) has the window j0 = max(0, i - w) ..
+ * j1 = min(L - 1, i + w) -- clipped at the TRACK's own ends -- and s_i = (((m_j0 + m_{j0+1}) + ...) + m_j1) / (double)(j1 - j0 + 1) a
+ * row: the sum in ascending j, one addition at a time, then one division.  w = 0: s_i = m_i, bit for bit.
+ * LINK, EXTENT.  Link i joins s_i to s_{i+1}: d_r = s_{i+1,r} - s_{i,r}, e = max_r |d_r|.  A link with !(e <= 4096.0)
+ * (BEAMFORMER_HIP_MAX_LINK_SAMPLES; a sum that overflowed to something not finite is such a link) is SKIPPED: it draws nothing, counts
+ * in links_skipped, and is no predecessor.  Otherwise S = max(1, (uint32)ceil(e)).
+ * SAMPLE k of 0 .. S - 1: t = ((double)k + 0.5) / (double)S, c_r = s_{i,r} + d_r * t (one multiply, then one add), B_r = floor(c_r +
+ * 0.5), kept as a double.  c steps by |d_r| / S <= 1 a sample, so successive samples step by at most one cell an axis -- except on the
+ * axis of a WHOLE-NUMBERED extent, where the step is 1 exactly, every c_r lies on a cell border and the rounding of t decides its side:
+ * there a step may be 0 or 2.  B is monotone an axis within a link: a link never returns to a bin it has left.
+ * REPEAT.  A sample's predecessor is the sample before it on the same track: sample k - 1 of its link for k > 0; for k = 0 and i > 0
+ * the LAST sample of link i - 1, unless that link was skipped; otherwise it has none.  A sample whose B equals its predecessor's on all
+ * three axes (compared as doubles, inside a map or not) is a REPEAT and is dropped; every other sample is DRAWN.
+ * DEPOSIT.  BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS: a drawn sample whose B lies inside the localisation map adds 1 there, otherwise it
+ * counts in points_outside.  BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS: inside the track map it adds 1 to the count and q_r = (int64)floor(d_r *
+ * 1048576.0 + 0.5) to the three sums -- the pair call's fixed point, of the smoothed link; every sample of a link carries the link's own
+ * d --, otherwise it counts in links_outside.  Integer atomics only: the maps' bytes stay a function of the multiset of deposits.
+ * EQUALITY.  use_offsets 0, an integer placement, smooth 0 and LINKS, on frames whose links all have e <= 1 and whose rows report no
+ * repeat: S = 1 and t = 0.5, the one sample is the midpoint exactly, and the track map's bytes are the track call's with LINKS. */
+#define BEAMFORMER_HIP_MAX_TRACK_SMOOTH 8u          /* w, the moving average's half-width */
+#define BEAMFORMER_HIP_MAX_LINK_SAMPLES 4096.0      /* a link's extent in map cells, and so its samples */
+typedef struct {                              /* a row a FRAME; a link belongs to the frame of its OLDER point */
+	uint32_t frame_id; float threshold;       /* from the frame's record; the threshold used for it */
+	uint32_t peaks, unplaced;                 /* stored records; those whose coordinate is not finite */
+	uint32_t kept_points, kept_links;         /* the track call's: this frame's peaks in kept tracks; of them, those with a link to the next frame */
+	uint32_t lone;                            /* kept tracks of one point that begin (and end) here */
+	uint32_t links_skipped;                   /* of kept_links, those whose extent is above the limit or not a number */
+	uint32_t samples, repeats;                /* the sum of S over the other links; of them, the samples dropped as repeats */
+	uint32_t points_deposited, points_outside, links_deposited, links_outside;   /* all 0 without the deposit bit; else the two of a kind add up to samples - repeats */
+	uint64_t found;                           /* exactly beamformer_hip_find_peaks_last_frames' number */
+} BeamformerHipDrawnFrame;                    /* 64 bytes, no padding */
+#ifdef __cplusplus
+static_assert(sizeof(BeamformerHipDrawnFrame) == 64, "BeamformerHipDrawnFrame: 14 words and found, no padding");
+#else
+_Static_assert(sizeof(BeamformerHipDrawnFrame) == 64, "BeamformerHipDrawnFrame: 14 words and found, no padding");
+#endif
+/* The kept tracks of the `count` newest frames drawn into the maps `deposit` names; every argument up to min_length is
+ * beamformer_hip_track_peaks_last_frames'.  smooth: 0 .. BEAMFORMER_HIP_MAX_TRACK_SMOOTH.  deposit: 0 (everything is counted, nothing
+ * deposited) or any of the two bits.  rows[count]: a row a frame.  No record list comes back: both live on the device for this call.
+ * The call runs on the current stream in TWO synchronises: the counts (the buffers are sized by them) and the tallies.  Behind the
+ * track call's launches, which deposit nothing here (csrc/frame_tracks.hip): smooth (not for smooth == 0), draw.  device_ms, when not
+ * NULL: the time between events around the launches, both parts added.
+ * A successful call with POINTS is a depositing call of the localisation map (calls, deposited, outside, the remembered parameter
+ * block); one with LINKS is one of the track map, whose `pairs` goes up by the drawn samples, so that pairs == deposited + outside
+ * still holds.  beamformer_hip_queue_localisation_map and beamformer_hip_queue_track_map work on the drawn maps unchanged.
+ * Refusals, all decided before anything is enqueued or changed and leaving every output unwritten: everything
+ * beamformer_hip_track_peaks_last_frames refuses, with its error kinds; smooth > BEAMFORMER_HIP_MAX_TRACK_SMOOTH: BufferOverflow;
+ * InvalidAccess: a deposit bit other than the two, a bit without its map, rows NULL. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region,
+                                                                      const float *thresholds, uint32_t threshold_count,
+                                                                      const double *placements /* [placement_count][12] */,
+                                                                      uint32_t placement_count /* 1 or count */, uint32_t use_offsets,
+                                                                      float max_distance, uint32_t max_per_frame, uint32_t min_length,
+                                                                      uint32_t smooth, uint32_t deposit,
+                                                                      BeamformerHipDrawnFrame *rows /* [count] */, float *device_ms);
 
 /* ---- ensemble filter: a linear slow-time operator on the frames of the frame ring (the clutter filter between "ensemble" and "peaks"
  * of the ULM loop: tissue lies 30 - 60 dB above the microbubbles, so the peaks of an unfiltered ensemble are tissue speckle).  Two

@@ -435,6 +435,18 @@ typedef struct {
 	uint32_t deposit;            /* BF_CHAIN_POINTS | BF_CHAIN_LINKS */
 	uint32_t min_length;         /* a track is kept with at least so many peaks */
 } BfChainArgs;
+/* drawn tracks (frame_tracks.hip: beamformer_hip_draw_tracks_last_frames) */
+#define BF_DRAW_MAX_SMOOTH  8u               /* = BEAMFORMER_HIP_MAX_TRACK_SMOOTH */
+#define BF_DRAW_MAX_SAMPLES 4096.0           /* = BEAMFORMER_HIP_MAX_LINK_SAMPLES: a link of a larger extent is skipped */
+typedef struct {                             /* a frame: BeamformerHipDrawnFrame's eight counters behind kept_links, in its order */
+	uint32_t lone, links_skipped, samples, repeats, points_deposited, points_outside, links_deposited, links_outside;
+} BfDrawTally;
+typedef struct {
+	uint32_t point_map[3];       /* the localisation map's grid, x fastest (read with BF_CHAIN_POINTS only) */
+	uint32_t track_map[3];       /* the track map's (read with BF_CHAIN_LINKS only) */
+	uint32_t deposit;            /* BF_CHAIN_POINTS | BF_CHAIN_LINKS */
+	uint32_t smooth;             /* w, the moving average's half-width; 0: none, the points are drawn as they are */
+} BfDrawArgs;
 
 /* ---- frame quantiles (frame_quantiles.hip: beamformer_hip_quantiles_last_frames) ---- */
 #define BF_QUANTILES_MAX       16u           /* = BEAMFORMER_HIP_MAX_QUANTILES: ranks a frame, and so distinct prefixes a digit pass */
@@ -721,6 +733,15 @@ hipError_t bf_launch_tracks_chain(const double *positions, const uint32_t *first
                                   uint32_t *tails, uint32_t *track_of, uint32_t *first_of, uint32_t *words, uint32_t *offsets, const BfChainArgs *a,
                                   uint32_t *point_map, uint32_t *track_counts, void *track_sums, void *tracks, void *points, BfChainTally *tallies,
                                   hipStream_t s);
+/* frame_tracks.hip, behind _chain on the same stream and on ITS tables (links, lengths, track_of, first_of, words, offsets: as they
+ * were passed to it; tracks, points: not NULL here): the kept tracks drawn into the maps, one launch (draw), two with a->smooth (smooth,
+ * draw).  smoothed: room for 3 x total doubles (not read or written with a->smooth == 0).  The maps as _chain takes them.
+ * tallies[frames]: zeroed by the caller (integer atomics, a wave a counter) */
+hipError_t bf_launch_tracks_draw(const uint32_t *firsts, const uint32_t *stored, uint32_t frames, uint32_t max_stored, uint32_t total,
+                                 const void *links, const uint32_t *lengths, const uint32_t *track_of, const uint32_t *first_of,
+                                 const uint32_t *words, const uint32_t *offsets, const void *tracks, const void *points, double *smoothed,
+                                 const BfDrawArgs *a, uint32_t *point_map, uint32_t *track_counts, void *track_sums, BfDrawTally *tallies,
+                                 hipStream_t s);
 /* ensemble.hip, the Gram matrix: three launches, no atomics -- the all-finite mask (a wave a word of 64 box voxels, every frame read
  * once), the partial pass (grid x the chunk, grid y the tile pair: BF_GRAM_TILE x BF_GRAM_TILE pairs of double2 a block) and the fold
  * (a thread a pair j <= k sums its chunks' partials in chunk order and stores both triangles; one more block counts the mask's bits).

@@ -172,7 +172,7 @@ struct FrameOps {
 		size_t   sums_at() const { return round_up(sizeof(uint32_t) * voxels(), 64); }
 		void forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; pairs = deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
 	} tracks;
-	DeviceBuffer tracks_scratch;                               /* pair_peaks_last_frames, track_peaks_last_frames: what is sized by the peaks the scan found -- positions, choices, the match pass's tables and the pair records, or the chain tables and the track and point records (frame_tracks.hip); its small tables live in metrics_scratch and metrics_pinned, its peak records in peaks_list */
+	DeviceBuffer tracks_scratch;                               /* pair_peaks_last_frames, track_peaks_last_frames, draw_tracks_last_frames: what is sized by the peaks the scan found -- positions, choices, the match pass's tables and the pair records, or the chain tables and the track and point records, and the smoothed points (frame_tracks.hip); its small tables live in metrics_scratch and metrics_pinned, its peak records in peaks_list */
 	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
 	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
@@ -343,6 +343,10 @@ bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *reg
                              const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
                              uint32_t max_per_frame, uint32_t min_length, uint32_t deposit, BeamformerHipTrackedFrame *rows,
                              BeamformerHipPeakTrack *tracks, BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count,
+                             float *device_ms);
+bool draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
+                             uint32_t max_per_frame, uint32_t min_length, uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows,
                              float *device_ms);
 bool track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info);
 bool queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);

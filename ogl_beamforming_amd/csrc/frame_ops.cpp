@@ -1,5 +1,5 @@
 /* frame_ops.cpp -- the calls that work on frames already in the ring: the reduce calls (score, find_peaks, accumulate_peaks, pair_peaks,
- * track_peaks, gram, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
+ * track_peaks, draw_tracks, gram, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
  * the queued runs (mix, autocorrelate, convolve, warp, queue_localisation_map, queue_track_map), which write frames of their own behind
  * the newest ones and do not.  Their
  * device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is executor.cpp's. */
@@ -320,6 +320,50 @@ struct PeakChoices {
 		return timed ? mark_ms + rest_ms : 0.0f;
 	}
 };
+
+/* What track_peaks_last_frames and draw_tracks_last_frames share behind PeakChoices::find(), total != 0: the chain's tables carved from
+ * tracks_scratch behind the choices -- next | links, twice | lengths | tails | track_of | first_of | words | offsets | tracks | points,
+ * the two record lists sized by ALL stored records, an upper bound, or left out -- and the chain's launches behind enqueue(). */
+struct ChainTables {
+	size_t next_at = 0, links_at = 0, lengths_at = 0, tails_at = 0, track_of_at = 0, first_of_at = 0, words_at = 0, offsets_at = 0, tracks_at = 0,
+	       points_at = 0;
+	bool with_tracks = false, with_points = false;
+	void carve(PeakChoices &c, bool tracks, bool points)
+	{
+		const size_t each = sizeof(uint32_t) * c.total, chain_blocks = ((size_t)c.total + 255u) / 256u;
+		next_at = c.big.take(each); links_at = c.big.take(4 * each); lengths_at = c.big.take(each); tails_at = c.big.take(each);
+		track_of_at = c.big.take(each); first_of_at = c.big.take(each); words_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks);
+		offsets_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks);
+		tracks_at = c.big.take(tracks ? sizeof(BeamformerHipPeakTrack) * (size_t)c.total : 0);
+		points_at = c.big.take(points ? sizeof(BeamformerHipTrackPoint) * (size_t)c.total : 0);
+		with_tracks = tracks; with_points = points;
+	}
+	template <class T = char> T *at(Device &d, size_t where) const { return (T *)((char *)d.ops.tracks_scratch.ptr + where); }
+	void *tracks(Device &d) const { return with_tracks ? at(d, tracks_at) : nullptr; }
+	void *points(Device &d) const { return with_points ? at(d, points_at) : nullptr; }
+	/* a: the maps' grids are filled in here, from the maps a->deposit names (the caller has checked that they exist) */
+	hipError_t launch(Device &d, PeakChoices &c, BfChainArgs a, BfChainTally *tallies, hipStream_t s) const
+	{
+		const FrameOps::LocalisationMap &point_map = d.ops.map;
+		const FrameOps::TrackMap &link_map = d.ops.tracks;
+		const bool to_points = a.deposit & BF_CHAIN_POINTS, to_links = a.deposit & BF_CHAIN_LINKS;
+		for (int k = 0; k < 3; k++) { a.point_map[k] = to_points ? point_map.points[k] : 0u; a.track_map[k] = to_links ? link_map.points[k] : 0u; }
+		return bf_launch_tracks_chain(c.positions(d), c.device_firsts, c.device_stored, c.count, c.max_stored, c.total,
+		                              c.capacity ? c.forward(d) : nullptr, c.capacity ? c.backward(d) : nullptr, at<uint32_t>(d, next_at),
+		                              at(d, links_at), at<uint32_t>(d, lengths_at), at<uint32_t>(d, tails_at), at<uint32_t>(d, track_of_at),
+		                              at<uint32_t>(d, first_of_at), at<uint32_t>(d, words_at), at<uint32_t>(d, offsets_at), &a,
+		                              to_points ? (uint32_t *)point_map.buffer.ptr : nullptr, to_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
+		                              to_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr, tracks(d), points(d), tallies, s);
+	}
+};
+
+/* the deposit bits of the two calls against the maps that exist */
+bool maps_for(Device &d, uint32_t deposit)
+{
+	if ((deposit & BF_CHAIN_POINTS) && (!d.ops.map.buffer.ptr || !d.ops.map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if ((deposit & BF_CHAIN_LINKS) && (!d.ops.tracks.buffer.ptr || !d.ops.tracks.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	return true;
+}
 
 } // namespace
 
@@ -765,38 +809,22 @@ bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *reg
 	FrameOps::LocalisationMap &point_map = d.ops.map;
 	FrameOps::TrackMap &link_map = d.ops.tracks;
 	const bool with_points = deposit & BF_CHAIN_POINTS, with_links = deposit & BF_CHAIN_LINKS;
-	if (with_points && (!point_map.buffer.ptr || !point_map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	if (with_links && (!link_map.buffer.ptr || !link_map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!maps_for(d, deposit)) return false;
 	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, sizeof(BfChainTally) * count)) return false;
 	const BfChainTally *tallies = (const BfChainTally *)c.extra;
 	const double reach = (double)max_distance, r2 = reach * reach;
 	uint64_t total_tracks = 0, total_points = 0;
 	if (c.total) {
-		/* tracks_scratch, behind the choices: next | links, twice | lengths | tails | track_of | first_of | words | offsets | tracks | points */
-		const size_t each = sizeof(uint32_t) * c.total, chain_blocks = ((size_t)c.total + 255u) / 256u;
-		const size_t next_at = c.big.take(each), links_at = c.big.take(4 * each), lengths_at = c.big.take(each), tails_at = c.big.take(each),
-		             track_of_at = c.big.take(each), first_of_at = c.big.take(each), words_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks),
-		             offsets_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks),
-		             tracks_at = c.big.take(tracks ? sizeof(BeamformerHipPeakTrack) * (size_t)c.total : 0),
-		             points_at = c.big.take(points ? sizeof(BeamformerHipTrackPoint) * (size_t)c.total : 0);
+		ChainTables t;
+		t.carve(c, tracks != nullptr, points != nullptr);
 		hipStream_t s = d.stream;
 		bool ok = c.ensure(d);
 		if (ok) {
-			char *scratch = (char *)d.ops.tracks_scratch.ptr;
-			void *device_tracks = tracks ? scratch + tracks_at : nullptr, *device_points = points ? scratch + points_at : nullptr;
+			void *device_tracks = t.tracks(d), *device_points = t.points(d);
 			BfChainArgs a{};
-			for (int k = 0; k < 3; k++) { a.point_map[k] = with_points ? point_map.points[k] : 0u; a.track_map[k] = with_links ? link_map.points[k] : 0u; }
 			a.deposit = deposit; a.min_length = min_length;
 			ok = c.enqueue(d, use_offsets != 0, r2);
-			if (ok) ok &= HIP_OK(bf_launch_tracks_chain(c.positions(d), c.device_firsts, c.device_stored, count, c.max_stored, c.total,
-			                                            c.capacity ? c.forward(d) : nullptr, c.capacity ? c.backward(d) : nullptr,
-			                                            (uint32_t *)(scratch + next_at), scratch + links_at, (uint32_t *)(scratch + lengths_at),
-			                                            (uint32_t *)(scratch + tails_at), (uint32_t *)(scratch + track_of_at),
-			                                            (uint32_t *)(scratch + first_of_at), (uint32_t *)(scratch + words_at),
-			                                            (uint32_t *)(scratch + offsets_at), &a, with_points ? (uint32_t *)point_map.buffer.ptr : nullptr,
-			                                            with_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
-			                                            with_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr, device_tracks,
-			                                            device_points, (BfChainTally *)c.device_extra, s));
+			if (ok) ok &= HIP_OK(t.launch(d, c, a, (BfChainTally *)c.device_extra, s));
 			ok = c.collect(d, ok);
 			for (uint32_t n = 0; n < count && ok; n++) { total_tracks += tallies[n].kept_heads; total_points += tallies[n].kept_points; }
 			ok = ok && total_tracks <= c.total && total_points <= c.total;      /* (what the kernels promise: the copies below rely on it) */
@@ -827,6 +855,77 @@ bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *reg
 	if (with_points) { point_map.calls++; point_map.block = c.boxed[count - 1].record->block; }
 	if (with_links) { link_map.calls++; link_map.block = c.boxed[count - 1].record->block; }
 	*track_count = (uint32_t)total_tracks; *point_count = (uint32_t)total_points;
+	return true;
+}
+
+/* beamformer_hip_draw_tracks_last_frames: the track call's kept tracks, smoothed along the track and drawn into both maps at map
+ * resolution (frame_tracks.hip: smooth, draw, behind the chain's launches, which run without a deposit of their own).  The two record
+ * lists stay on the device, where the draw pass reads them; nothing is sized by what was kept, so there are TWO synchronises: the
+ * counts and the tallies.  The arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is
+ * enqueued. */
+bool draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
+                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
+                             uint32_t max_per_frame, uint32_t min_length, uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows,
+                             float *device_ms)
+{
+	static_assert(sizeof(BeamformerHipDrawnFrame) == 64, "a record without padding");
+	static_assert(BF_DRAW_MAX_SMOOTH == BEAMFORMER_HIP_MAX_TRACK_SMOOTH && BF_DRAW_MAX_SAMPLES == BEAMFORMER_HIP_MAX_LINK_SAMPLES, "one limit");
+	PeakChoices c;
+	if (!newest_boxed_frames(count, region, c.boxed)) return false;
+	Device &d = ctx().devices[0];
+	FrameOps::LocalisationMap &point_map = d.ops.map;
+	FrameOps::TrackMap &link_map = d.ops.tracks;
+	const bool with_points = deposit & BF_CHAIN_POINTS, with_links = deposit & BF_CHAIN_LINKS;
+	if (!maps_for(d, deposit)) return false;
+	/* extra: the chain's tallies, then the draw pass's */
+	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, (sizeof(BfChainTally) + sizeof(BfDrawTally)) * count)) return false;
+	const BfChainTally *chained = (const BfChainTally *)c.extra;
+	const BfDrawTally *drawn = (const BfDrawTally *)(chained + count);
+	const double reach = (double)max_distance, r2 = reach * reach;
+	if (c.total) {
+		ChainTables t;
+		t.carve(c, true, true);
+		const size_t smoothed_at = c.big.take(smooth ? sizeof(double) * 3 * (size_t)c.total : 0);
+		hipStream_t s = d.stream;
+		bool ok = c.ensure(d);
+		if (ok) {
+			BfChainArgs a{};
+			a.min_length = min_length;                                      /* (deposit 0: the finish pass lists, the draw pass deposits) */
+			BfDrawArgs w{};
+			for (int k = 0; k < 3; k++) { w.point_map[k] = with_points ? point_map.points[k] : 0u; w.track_map[k] = with_links ? link_map.points[k] : 0u; }
+			w.deposit = deposit; w.smooth = smooth;
+			ok = c.enqueue(d, use_offsets != 0, r2);
+			if (ok) ok &= HIP_OK(t.launch(d, c, a, (BfChainTally *)c.device_extra, s));
+			if (ok) ok &= HIP_OK(bf_launch_tracks_draw(c.device_firsts, c.device_stored, count, c.max_stored, c.total, t.at(d, t.links_at),
+			                                           t.at<uint32_t>(d, t.lengths_at), t.at<uint32_t>(d, t.track_of_at), t.at<uint32_t>(d, t.first_of_at),
+			                                           t.at<uint32_t>(d, t.words_at), t.at<uint32_t>(d, t.offsets_at), t.tracks(d), t.points(d),
+			                                           smooth ? t.at<double>(d, smoothed_at) : nullptr, &w,
+			                                           with_points ? (uint32_t *)point_map.buffer.ptr : nullptr,
+			                                           with_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
+			                                           with_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr,
+			                                           (BfDrawTally *)((BfChainTally *)c.device_extra + count), s));
+			ok = c.collect(d, ok);
+		}
+		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	}
+	if (device_ms) *device_ms = c.device_ms(d, c.total != 0);
+
+	for (uint32_t n = 0; n < count; n++) {
+		BeamformerHipDrawnFrame &m = rows[n];
+		const BfDrawTally &t = drawn[n];
+		std::memset(&m, 0, sizeof(m));
+		m.frame_id = c.boxed[n].record->id; m.threshold = thresholds[threshold_count == 1 ? 0 : n];
+		m.peaks = c.stored[n]; m.unplaced = c.unplaced[n];
+		m.kept_points = chained[n].kept_points; m.kept_links = chained[n].kept_links;
+		m.lone = t.lone; m.links_skipped = t.links_skipped; m.samples = t.samples; m.repeats = t.repeats;
+		m.points_deposited = t.points_deposited; m.points_outside = t.points_outside;
+		m.links_deposited = t.links_deposited; m.links_outside = t.links_outside;
+		m.found = c.results[n].found;
+		if (with_points) { point_map.deposited += t.points_deposited; point_map.outside += t.points_outside; }
+		if (with_links) { link_map.pairs += t.samples - t.repeats; link_map.deposited += t.links_deposited; link_map.outside += t.links_outside; }
+	}
+	if (with_points) { point_map.calls++; point_map.block = c.boxed[count - 1].record->block; }
+	if (with_links) { link_map.calls++; link_map.block = c.boxed[count - 1].record->block; }
 	return true;
 }
 

@@ -1,7 +1,8 @@
 /* frame_tracks.hip -- the peaks of consecutive frames of the frame ring linked into pairs (beamformer_hip_pair_peaks_last_frames: the
  * velocity map of ULM and the rejection of detections that do not persist, without a peak list leaving the device), the pairs chained
- * into tracks and kept by length (beamformer_hip_track_peaks_last_frames: the chain kernels have their own comment further down), and
- * the track map's frame (beamformer_hip_queue_track_map).
+ * into tracks and kept by length (beamformer_hip_track_peaks_last_frames: the chain kernels have their own comment further down), the
+ * kept tracks smoothed and drawn into both maps (beamformer_hip_draw_tracks_last_frames: likewise), and the track map's frame
+ * (beamformer_hip_queue_track_map).
  *
  * DEFINITION (include/ogl_beamformer_hip.h has it for callers; tests/tracks_ref.py is its numpy restatement).  A frame's peaks are the
  * records frame_peaks.hip emits (the caller runs its mark, scan and emit passes in front of these launches); a peak's rank is its place
@@ -440,11 +441,166 @@ __global__ __launch_bounds__(256) void tracks_finish_kernel(const double *__rest
 	}
 }
 
+/* ---- the kept tracks drawn into both maps at map resolution (beamformer_hip_draw_tracks_last_frames; the header has the DEFINITION,
+ * tests/track_draw_ref.py its numpy restatement).  Both kernels read the finish pass's packed point list where it lies.
+ * Smooth: a lane a packed point slot p below the kept total, which it reads from the keep pass's last block (offset + word).  Its
+ * track's `first` and `length` bound the window: the sum runs over the track's own run, oldest first, one addition at a time, then one
+ * division; three doubles go to smoothed[3 p].  Not launched for w = 0: the draw pass then reads the positions in the point records.
+ * Draw: the finish pass's grid -- grid y the frame, so that a wave's tallies are one frame's, grid x blocks of 256 records --, a lane a
+ * record.  A record that is a kept point with a successor owns link i = its place in the track: the lane forms d and S, then walks the
+ * samples k = 0 .. S - 1 in a loop and carries the B of the sample before in registers; only for k = 0 does it form the predecessor
+ * itself, the last sample of link i - 1 from that link's own s, d and S -- eleven double operations a link instead of a scan over
+ * samples whose number only the device knows.  A drawn sample costs one integer atomic (POINTS) and four (LINKS), all returnless.  A
+ * group of 16 lanes a link striding k was measured against this and was slower where it matters: sixteen times the waves,
+ * each with its own tally atomics, for links of 8 samples.  Tallies: every lane counts its own, six shuffle rounds add a wave's, one
+ * integer atomic a wave a counter that is not zero. */
+namespace {
+
+/* link `slot` -> `slot` + 1 of the packed list: a = s_i, d = s_{i+1} - s_i, S; false: SKIPPED (!(e <= 4096), a NaN included) */
+__device__ __forceinline__ bool draw_link(const double *src, uint32_t stride, uint32_t slot, double a[3], double d[3], uint32_t &S)
+{
+	#pragma clang fp contract(off)
+	bool ok = true;
+	double e = 0.0;
+	#pragma unroll
+	for (int r = 0; r < 3; r++) {
+		const double u = src[(uint64_t)slot * stride + r], v = src[((uint64_t)slot + 1u) * stride + r];
+		a[r] = u; d[r] = v - u;
+		const double m = __builtin_fabs(d[r]);
+		ok &= m <= BF_DRAW_MAX_SAMPLES;
+		e = m > e ? m : e;
+	}
+	const uint32_t up = ok ? (uint32_t)__builtin_ceil(e) : 0u;
+	S = up ? up : 1u;
+	return ok;
+}
+
+/* B of sample k of a link: floor(c_r + 0.5), c_r = s_r + d_r * t, t = (k + 0.5) / S */
+__device__ __forceinline__ void draw_bin(const double a[3], const double d[3], uint32_t S, uint32_t k, double B[3])
+{
+	#pragma clang fp contract(off)
+	const double t = ((double)k + 0.5) / (double)S;
+	#pragma unroll
+	for (int r = 0; r < 3; r++) {
+		const double step = d[r] * t, c = a[r] + step;
+		B[r] = __builtin_floor(c + 0.5);
+	}
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+	for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
+	return v;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(256) void tracks_smooth_kernel(const ChainTrack *__restrict__ tracks, const ChainPoint *__restrict__ points,
+                                                            const uint32_t *__restrict__ point_words, const uint32_t *__restrict__ point_offsets,
+                                                            uint32_t blocks, uint32_t w, double *__restrict__ smoothed)
+{
+	#pragma clang fp contract(off)
+	const uint32_t kept = point_offsets[blocks - 1u] + point_words[blocks - 1u], p = blockIdx.x * 256u + threadIdx.x;
+	if (p >= kept) return;
+	const ChainTrack &t = tracks[points[p].track];
+	const uint32_t first = t.first, i = p - first, lo = i > w ? i - w : 0u, hi = i + w < t.length ? i + w : t.length - 1u;
+	const ChainPoint *run = points + first;
+	double sum[3] = {run[lo].position[0], run[lo].position[1], run[lo].position[2]};
+	for (uint32_t j = lo + 1u; j <= hi; j++) {
+		#pragma unroll
+		for (int r = 0; r < 3; r++) sum[r] = sum[r] + run[j].position[r];
+	}
+	const double n = (double)(hi - lo + 1u);
+	#pragma unroll
+	for (int r = 0; r < 3; r++) smoothed[3ull * p + r] = sum[r] / n;
+}
+
+/* src, stride: point slot p's three doubles lie at src[p * stride] -- the smoothed list (3), or the positions inside the point records (5) */
+__global__ __launch_bounds__(256) void tracks_draw_kernel(const double *__restrict__ src, uint32_t stride, const uint32_t *__restrict__ firsts,
+                                                          const uint32_t *__restrict__ stored, const uint2 *__restrict__ links,
+                                                          const uint32_t *__restrict__ lengths, const uint32_t *__restrict__ track_of,
+                                                          const uint32_t *__restrict__ first_of, const uint32_t *__restrict__ point_offsets,
+                                                          BfDrawArgs t, uint32_t *__restrict__ point_map, uint32_t *__restrict__ map_counts,
+                                                          unsigned long long *__restrict__ map_sums, BfDrawTally *__restrict__ tallies)
+{
+	#pragma clang fp contract(off)
+	const uint32_t frame = blockIdx.y, n = stored[frame], k = blockIdx.x * 256u + threadIdx.x;
+	if (blockIdx.x * 256u >= n) return;
+	uint32_t counted[8] = {0, 0, 0, 0, 0, 0, 0, 0};                      /* (BfDrawTally's counters, in its order) */
+	if (k < n) {
+		const uint32_t i = firsts[frame] + k;
+		const uint2 me = links[i];
+		const uint32_t h = me.x;
+		if (h != BF_TRACK_NONE && track_of[h] != BF_TRACK_NONE) {
+			const uint32_t length = lengths[h], slot = point_offsets[h >> 8] + first_of[h] + me.y;
+			if (length == 1u) counted[0] = 1u;
+			if (me.y + 1u < length) {
+				double a[3], d[3], before[3] = {0.0, 0.0, 0.0};
+				uint32_t S;
+				if (!draw_link(src, stride, slot, a, d, S)) counted[1] = 1u;
+				else {
+					counted[2] = S;
+					/* the sample before the first: the last one of link i - 1, by that link's own numbers; a skipped link is no predecessor */
+					bool follows = false;
+					if (me.y) {
+						double pa[3], pd[3];
+						uint32_t pS;
+						if (draw_link(src, stride, slot - 1u, pa, pd, pS)) { draw_bin(pa, pd, pS, pS - 1u, before); follows = true; }
+					}
+					/* the pair call's fixed point, of the smoothed link; |d_r| <= 4096: q_r fits easily */
+					const long long q[3] = {(long long)__builtin_floor(d[0] * BF_TRACK_FIXED + 0.5), (long long)__builtin_floor(d[1] * BF_TRACK_FIXED + 0.5),
+					                        (long long)__builtin_floor(d[2] * BF_TRACK_FIXED + 0.5)};
+					const uint64_t voxels = (uint64_t)t.track_map[0] * t.track_map[1] * t.track_map[2];
+					for (uint32_t s = 0; s < S; s++) {
+						double B[3];
+						draw_bin(a, d, S, s, B);
+						const bool repeat = follows && B[0] == before[0] && B[1] == before[1] && B[2] == before[2];
+						before[0] = B[0]; before[1] = B[1]; before[2] = B[2];
+						follows = true;
+						if (repeat) { counted[3]++; continue; }
+						if (t.deposit & BF_CHAIN_POINTS) {
+							const bool in = B[0] >= 0.0 && B[0] < (double)t.point_map[0] && B[1] >= 0.0 && B[1] < (double)t.point_map[1] &&
+							                B[2] >= 0.0 && B[2] < (double)t.point_map[2];
+							if (in) atomicAdd(point_map + (((uint64_t)(uint32_t)B[2] * t.point_map[1] + (uint32_t)B[1]) * t.point_map[0] + (uint32_t)B[0]), 1u);
+							if (in) counted[4]++; else counted[5]++;
+						}
+						if (t.deposit & BF_CHAIN_LINKS) {
+							const bool in = B[0] >= 0.0 && B[0] < (double)t.track_map[0] && B[1] >= 0.0 && B[1] < (double)t.track_map[1] &&
+							                B[2] >= 0.0 && B[2] < (double)t.track_map[2];
+							if (in) {
+								const uint64_t at = ((uint64_t)(uint32_t)B[2] * t.track_map[1] + (uint32_t)B[1]) * t.track_map[0] + (uint32_t)B[0];
+								atomicAdd(map_counts + at, 1u);
+								#pragma unroll
+								for (int r = 0; r < 3; r++) atomicAdd(map_sums + r * voxels + at, (unsigned long long)q[r]);
+							}
+							if (in) counted[6]++; else counted[7]++;
+						}
+					}
+				}
+			}
+		}
+	}
+	uint32_t *tally = (uint32_t *)(tallies + frame);
+	#pragma unroll
+	for (int c = 0; c < 8; c++) {
+		const uint32_t all = wave_sum(counted[c]);
+		if ((threadIdx.x & 63u) == 0 && all) atomicAdd(tally + c, all);
+	}
+}
+
 namespace {
 
 bool grid_fits(uint32_t frames, uint32_t max_stored)
 {
 	return frames >= 2 && frames <= 65535u && max_stored >= 1 && max_stored <= BF_TRACK_MAX_PEAKS;
+}
+
+/* the chain's pointer-jumping rounds; the links table it leaves is the first half of `links` after an even number, the second after an odd one */
+uint32_t jump_rounds(uint32_t frames)
+{
+	uint32_t rounds = 0;
+	while ((1u << rounds) < frames) rounds++;                            /* frames >= 2: at least one, which is also the tails' */
+	return rounds;
 }
 
 } // namespace
@@ -534,8 +690,7 @@ extern "C" hipError_t bf_launch_tracks_chain(const double *positions, const uint
 	uint2 *ping = (uint2 *)links, *pong = ping + total;
 	hipLaunchKernelGGL(tracks_link_kernel, by_frame, dim3(256), 0, s, positions, firsts, stored, frames, forward, backward, next, ping, lengths);
 	hipError_t e = hipGetLastError();
-	uint32_t rounds = 0;
-	while ((1u << rounds) < frames) rounds++;                            /* frames >= 2: at least one, which is also the tails' */
+	const uint32_t rounds = jump_rounds(frames);
 	for (uint32_t r = 0; r < rounds && e == hipSuccess; r++) {
 		hipLaunchKernelGGL(tracks_jump_kernel, dim3(blocks), dim3(256), 0, s, (const uint2 *)ping, pong, total, (const uint32_t *)next,
 		                   r + 1u == rounds ? 1u : 0u, lengths, tails);
@@ -555,5 +710,41 @@ extern "C" hipError_t bf_launch_tracks_chain(const double *positions, const uint
 	                   (const uint32_t *)lengths, (const uint32_t *)tails, (const uint32_t *)track_of, (const uint32_t *)first_of,
 	                   (const uint32_t *)track_offsets, (const uint32_t *)point_offsets, *a, point_map, track_counts, (unsigned long long *)track_sums,
 	                   (ChainTrack *)tracks, (ChainPoint *)points, tallies);
+	return hipGetLastError();
+}
+
+/* (bf_kernels.h says what every table is) */
+extern "C" hipError_t bf_launch_tracks_draw(const uint32_t *firsts, const uint32_t *stored, uint32_t frames, uint32_t max_stored, uint32_t total,
+                                            const void *links, const uint32_t *lengths, const uint32_t *track_of, const uint32_t *first_of,
+                                            const uint32_t *words, const uint32_t *offsets, const void *tracks, const void *points, double *smoothed,
+                                            const BfDrawArgs *a, uint32_t *point_map, uint32_t *track_counts, void *track_sums, BfDrawTally *tallies,
+                                            hipStream_t s)
+{
+	static_assert(sizeof(BfDrawTally) == 32 && sizeof(ChainPoint) == 5 * sizeof(double) && offsetof(ChainPoint, position) == 2 * sizeof(double),
+	              "eight counters; a point record is five doubles wide, its position the last three");
+	if (!firsts || !stored || !links || ((uintptr_t)links & 7u) || !lengths || !track_of || !first_of || !words || !offsets || !tracks ||
+	    ((uintptr_t)tracks & 7u) || !points || ((uintptr_t)points & 7u) || !a || !tallies || !grid_fits(frames, max_stored) || total == 0 ||
+	    total > (1u << 26) || a->smooth > BF_DRAW_MAX_SMOOTH || (a->smooth && !smoothed) || (a->deposit & ~(BF_CHAIN_POINTS | BF_CHAIN_LINKS)))
+		return hipErrorInvalidValue;
+	if ((a->deposit & BF_CHAIN_POINTS) && (!point_map || !a->point_map[0] || !a->point_map[1] || !a->point_map[2] ||
+	                                       (uint64_t)a->point_map[0] * a->point_map[1] > BF_MAP_MAX_VOXELS ||
+	                                       (uint64_t)a->point_map[0] * a->point_map[1] * a->point_map[2] > BF_MAP_MAX_VOXELS)) return hipErrorInvalidValue;
+	if ((a->deposit & BF_CHAIN_LINKS) && (!track_counts || !track_sums || !a->track_map[0] || !a->track_map[1] || !a->track_map[2] ||
+	                                      (uint64_t)a->track_map[0] * a->track_map[1] > BF_TRACK_MAX_VOXELS ||
+	                                      (uint64_t)a->track_map[0] * a->track_map[1] * a->track_map[2] > BF_TRACK_MAX_VOXELS)) return hipErrorInvalidValue;
+	const uint32_t blocks = (total + 255u) / 256u;
+	const uint2 *final_links = (const uint2 *)links + (jump_rounds(frames) & 1u ? total : 0u);
+	const uint32_t *point_offsets = offsets + blocks;
+	const double *src = (const double *)points + 2;
+	uint32_t stride = 5;
+	if (a->smooth) {
+		hipLaunchKernelGGL(tracks_smooth_kernel, dim3(blocks), dim3(256), 0, s, (const ChainTrack *)tracks, (const ChainPoint *)points, words + blocks,
+		                   point_offsets, blocks, a->smooth, smoothed);
+		const hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+		src = smoothed; stride = 3;
+	}
+	hipLaunchKernelGGL(tracks_draw_kernel, dim3((max_stored + 255u) / 256u, frames), dim3(256), 0, s, src, stride, firsts, stored, final_links, lengths, track_of, first_of, point_offsets, *a, point_map, track_counts,
+	                   (unsigned long long *)track_sums, tallies);
 	return hipGetLastError();
 }

@@ -1114,6 +1114,29 @@ uint32_t beamformer_hip_track_peaks_last_frames(uint32_t count, const Beamformer
 	                               min_length, deposit, rows, tracks, points, track_count, point_count, device_ms);
 }
 
+/* (the track call's checks, in its order and with its error kinds, then the call's own) */
+uint32_t beamformer_hip_draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds,
+                                                uint32_t threshold_count, const double *placements, uint32_t placement_count,
+                                                uint32_t use_offsets, float max_distance, uint32_t max_per_frame, uint32_t min_length,
+                                                uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows, float *device_ms)
+{
+	if (!check(count >= 2 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(min_length >= 1 && min_length <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(rows != nullptr && thresholds != nullptr && placements != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (uint32_t k = 0; k < threshold_count; k++)
+		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
+		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(max_distance >= 0.0f && max_distance <= BEAMFORMER_HIP_MAX_PAIR_DISTANCE, BeamformerLibErrorKind_InvalidAccess)) return 0;   /* (a NaN fails both) */
+	if (!check((deposit & ~(BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS | BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS)) == 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check(smooth <= BEAMFORMER_HIP_MAX_TRACK_SMOOTH, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	return draw_tracks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame,
+	                               min_length, smooth, deposit, rows, device_ms);
+}
+
 uint32_t beamformer_hip_track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info)
 {
 	if (!check(counts != nullptr && sums != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;

@@ -150,6 +150,8 @@ def _load():
         "beamformer_hip_track_peaks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
                                                          C.c_float, u32, u32, u32, C.POINTER(P.HipTrackedFrame), C.POINTER(P.HipPeakTrack),
                                                          C.POINTER(P.HipTrackPoint), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_draw_tracks_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_float), u32, C.POINTER(C.c_double), u32, u32,
+                                                         C.c_float, u32, u32, u32, u32, C.POINTER(P.HipDrawnFrame), C.POINTER(C.c_float)]),
         "beamformer_hip_track_map_copy": (u32, [C.POINTER(u32), C.POINTER(C.c_int64), u64, C.POINTER(P.HipTrackMapInfo)]),
         "beamformer_hip_queue_track_map": (u32, [u32, C.c_float, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
@@ -742,6 +744,28 @@ def track_peaks_last_frames(count, thresholds, placements, max_distance, max_per
     tracks = (P.HipPeakTrack * kept_tracks).from_buffer_copy(out_tracks[:kept_tracks].tobytes())
     points = (P.HipTrackPoint * kept_points).from_buffer_copy(out_points[:kept_points].tobytes())
     return rows, tracks, points, float(ms.value)
+
+
+def draw_tracks_last_frames(count, thresholds, placements, max_distance, max_per_frame, min_length, smooth=0, use_offsets=True, deposit=0,
+                            region=None):
+    """beamformer_hip_draw_tracks_last_frames: the kept tracks of track_peaks_last_frames (same arguments up to min_length) smoothed by
+    a moving average of half-width `smooth` (0 .. P.HIP_MAX_TRACK_SMOOTH, clipped at each track's ends) and drawn at map resolution:
+    every link is sampled once a map cell of its extent, and each drawn sample goes into the localisation map
+    (P.HIP_TRACK_DEPOSIT_POINTS) and, with the link's displacement, into the track map (P.HIP_TRACK_DEPOSIT_LINKS).  No record list
+    comes back.  Returns (rows, device_ms): a ctypes array of `count` HipDrawnFrame rows and the device time of the launches."""
+    count, max_per_frame = int(count), int(max_per_frame)
+    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
+    levels = (C.c_float * max(1, len(values)))(*values)
+    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
+    if matrices.size % 12:
+        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    rows = (P.HipDrawnFrame * max(1, count))()
+    ms = C.c_float(0)
+    _check(library().beamformer_hip_draw_tracks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
+                                                            matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
+                                                            1 if use_offsets else 0, float(max_distance), max_per_frame, int(min_length),
+                                                            int(smooth), int(deposit), rows, C.byref(ms)))
+    return rows, float(ms.value)
 
 
 def track_map_copy(points=None):

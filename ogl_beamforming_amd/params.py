@@ -409,6 +409,20 @@ class HipTrackedFrame(C.Structure):
 
 assert C.sizeof(HipPeakTrack) == 48 and C.sizeof(HipTrackPoint) == 40 and C.sizeof(HipTrackedFrame) == 56
 
+HIP_MAX_TRACK_SMOOTH = 8               # BEAMFORMER_HIP_MAX_TRACK_SMOOTH
+HIP_MAX_LINK_SAMPLES = 4096.0          # BEAMFORMER_HIP_MAX_LINK_SAMPLES
+
+
+class HipDrawnFrame(C.Structure):
+    """BeamformerHipDrawnFrame: one frame's row of beamformer_hip_draw_tracks_last_frames (64 bytes, no padding)"""
+    _fields_ = [("frame_id", C.c_uint32), ("threshold", C.c_float), ("peaks", C.c_uint32), ("unplaced", C.c_uint32), ("kept_points", C.c_uint32),
+                ("kept_links", C.c_uint32), ("lone", C.c_uint32), ("links_skipped", C.c_uint32), ("samples", C.c_uint32), ("repeats", C.c_uint32),
+                ("points_deposited", C.c_uint32), ("points_outside", C.c_uint32), ("links_deposited", C.c_uint32), ("links_outside", C.c_uint32),
+                ("found", C.c_uint64)]
+
+
+assert C.sizeof(HipDrawnFrame) == 64
+
 HIP_MAX_ENSEMBLE_FRAMES = 256
 HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
 HIP_MAX_SPATIAL_TAPS = 33       # BEAMFORMER_HIP_MAX_SPATIAL_TAPS
