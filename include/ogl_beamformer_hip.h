@@ -1071,6 +1071,83 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_clutter_projector(const double *gr
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_mix_last_frames(uint32_t count, const float *weights, uint32_t out_count,
                                                               uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms);
 
+/* ---- block-wise ensemble filter: the filter above made local.  Over a real field of view the slow-time statistics are not uniform --
+ * tissue moves differently from region to region, the noise floor rises with depth --, and one SVD cut for the whole frame leaves tissue
+ * in one part of the image and eats bubbles in another.  The block-wise filter takes a Gram matrix and a projector for each of many
+ * overlapping boxes and blends the filtered blocks by a window: here the Gram matrices of all boxes in ONE call, a host helper that lays
+ * the boxes on a lattice of nodes, and a mix whose weight table is given at those nodes and interpolated between them, as
+ * beamformer_hip_warp_last_frames interpolates its displacement field -- the pair that beamformer_hip_correlate_last_frames and the warp
+ * are for motion.  Out of scope: an autocorrelation that takes a weight field, any rule that picks the rank of a box ----
+ * Axis a: 0 = x (the fastest), 1 = y, 2 = z.  Index 0 is the oldest frame.  tests/block_filter_ref.py restates the definitions in numpy.
+ *
+ * beamformer_hip_gram_boxes_last_frames.
+ * DEFINITION.  The matrix and the info of box b are byte for byte what beamformer_hip_gram_last_frames(count, &regions[b], ...) returns on
+ * the same frames, `voxels` and `non_finite` included: the partition of a box into chunks is that call's, a function of the box and
+ * count alone.  The result of a box does not depend on the other boxes, their order, their overlap, or on the call being repeated; boxes
+ * may overlap, repeat and differ in size.
+ * OUTPUTS.  grams[region][count][count][2] doubles; infos[region], may be NULL.  device_ms, when not NULL: the time between two events
+ * around the launches.
+ * The boxes are walked in batches whose partial sums (16 KiB a chunk and tile pair) fit a budget of 64 MiB; a batch is three launches
+ * (csrc/ensemble_blocks.hip: the passes of the single-box call, each over all boxes of the batch), the batches lie behind one another on
+ * the library's current stream behind the frames they read.  A call costs ONE upload, ONE device-to-host copy and ONE stream
+ * synchronise, however many boxes.
+ * Refusals, all decided before anything is enqueued and leaving every output unwritten: count == 0 or
+ * > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, region_count == 0 or > BEAMFORMER_HIP_MAX_GRAM_BOXES, region_count x count x count >
+ * BEAMFORMER_HIP_MAX_GRAM_BOX_ENTRIES: BufferOverflow (decided first); grams or regions NULL, a box with a zero count or one that does
+ * not fit inside the frames, a box of 2^32 voxels or more, and everything beamformer_hip_gram_last_frames refuses, several devices
+ * included: InvalidAccess; frames that differ in grid or in data kind: DataSizeMismatch. */
+#define BEAMFORMER_HIP_MAX_GRAM_BOXES        1024u
+#define BEAMFORMER_HIP_MAX_GRAM_BOX_ENTRIES  (1u << 22)   /* region_count x count x count: a result of at most 64 MiB */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regions, uint32_t region_count,
+                                                                     double *grams /* [region][count][count][2] */,
+                                                                     BeamformerHipEnsembleInfo *infos /* [region], may be NULL */,
+                                                                     float *device_ms);
+/* Host only: touches no device and no library state but the last error.  The boxes of a lattice of N_a = nodes[a] nodes an axis on a
+ * grid of `points`.  Node j of axis a sits at voxel P_j = node_first[a] + j * node_step[a], computed in 64 bits: a node may lie beyond
+ * the frame.  Its box along that axis is [max(0, P_j - half[a]), min(points[a], P_j + half[a] + 1)); the box of node (jx, jy, jz) is the
+ * product of its three, written to regions[(jz * Ny + jy) * Nx + jx] -- the flat node order of the weight table of
+ * beamformer_hip_mix_field_last_frames.  node_step[a] is not read where N_a == 1.
+ * Refusals, leaving regions unwritten: a NULL pointer, a points or nodes entry of 0, node_step[a] == 0 with N_a > 1, a box that misses
+ * the frame (no voxel along some axis): InvalidAccess; the product of nodes > BEAMFORMER_HIP_MAX_MIX_NODES: BufferOverflow. */
+#define BEAMFORMER_HIP_MAX_MIX_NODES         1024u        /* product of nodes */
+#define BEAMFORMER_HIP_MAX_MIX_FIELD_ENTRIES (1u << 22)   /* product of nodes x out_count x count */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_lattice_boxes(const uint32_t points[3], const uint32_t nodes[3], const uint32_t node_first[3],
+                                                            const uint32_t node_step[3], const uint32_t half[3],
+                                                            BeamformerHipFrameRegion *regions /* [product of nodes], node order */);
+/* beamformer_hip_mix_field_last_frames: a mix whose weight table varies over the frame.
+ * DEFINITION.
+ * SOURCES.  The `count` = K newest frames of the ring, of one grid and one kind: beamformer_hip_mix_last_frames' rules.
+ * CORNER VALUES.  weights[node][out_count][count][2] floats, the nodes in the flat order above.  For node c, output j and voxel v,
+ * y_c[j][v] is the MIX chain above under W[c][j][.] -- the same order, the same signs, no weight skipped --: bit for bit what
+ * beamformer_hip_mix_last_frames would store for that table.
+ * SEGMENTS.  Along axis a with N = nodes[a], for a voxel of index i: N == 1: node 0, no interpolation (node_first[a] and node_step[a]
+ * are not read); i < P_0: node 0 alone; i >= P_(N-1): node N - 1 alone; otherwise j = (i - node_first[a]) / node_step[a],
+ * r = (i - node_first[a]) - j * node_step[a] and t = (float)r * inv, inv = 1.0f / (float)node_step[a] (one float32 division, on the
+ * host): nodes j and j + 1 are blended.
+ * BLEND.  Each output float is blended by lerps fmaf(t, b - a, a), a the value at the lower node: along x -- for each of the up to four
+ * (y, z) corner choices --, then along y over those results, then along z.  An axis on which the voxel has a single node contributes
+ * that node's value and no lerp.  Plain IEEE otherwise: a source voxel that is not finite makes every output at it not finite (NaN
+ * payloads are not promised).
+ * So nodes = {1, 1, 1} gives beamformer_hip_mix_last_frames' bytes; equal tables at all nodes give them wherever the outputs are
+ * finite; a voxel outside the lattice on every interpolated axis has the plain mix's bytes under that corner node.  The bytes of output
+ * j depend on the sources, the rows W[.][j][.] and the lattice only -- not on out_count, on the other rows, or on repetition.
+ * OUTPUTS.  out_count new frames of the sources' grid and kind in ONE contiguous run, placed, numbered, recorded and timed exactly as
+ * beamformer_hip_mix_last_frames' run is, the record of the newest multi-frame push and *first_frame_id (may be NULL) included.
+ * One launch (csrc/ensemble_blocks.hip), enqueued on the current stream behind the frames it reads; the weights travel through pinned
+ * memory of the call's own.  The call does not synchronise unless device_ms is not NULL (then: the time between two events around the
+ * launch).
+ * Refusals, all decided BEFORE ANYTHING CHANGES and leaving every output unwritten: count or out_count 0 or
+ * > BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES: BufferOverflow (decided first); weights, nodes, node_first or node_step NULL: InvalidAccess;
+ * a nodes entry of 0, the product of nodes > BEAMFORMER_HIP_MAX_MIX_NODES, that product x out_count x count >
+ * BEAMFORMER_HIP_MAX_MIX_FIELD_ENTRIES: BufferOverflow; node_step[a] == 0 with N_a > 1, a weight that is not finite, a nonzero imaginary
+ * weight on real frames, a frame of more than 2^31 - 1 voxels, and everything beamformer_hip_score_last_frames refuses, several devices
+ * included: InvalidAccess; frames that differ in grid or kind: DataSizeMismatch; a run of out_count frames that does not fit the ring,
+ * or that would reuse storage of one of its own count source frames: FrameSizeOverflow. */
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_mix_field_last_frames(uint32_t count, const float *weights /* [node][out_count][count][2] */,
+                                                                    const uint32_t nodes[3], const uint32_t node_first[3],
+                                                                    const uint32_t node_step[3], uint32_t out_count, uint32_t image_plane_tag,
+                                                                    uint32_t *first_frame_id, float *device_ms);
+
 /* ---- slow-time autocorrelation of an ensemble: the per-voxel reduction ACROSS the frames, behind the filter above.  Lag 0 is the power
  * Doppler image of the filtered ensemble, lag 1 the Kasai estimate (its angle is the axial velocity: v = angle(R_1) c PRF / (4 pi f0),
  * the angle is the caller's), lags 0 and 1 together the variance.  The filter is whatever weight table the caller would hand to
@@ -1433,7 +1510,13 @@ BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_das_path(uint32_t mode);
  *   STAGED_TABLE_CAP=bytes  largest global transmit table taken (default 2 GiB; 0: always the LDS-table fallback)
  *   DEBUG                   one line per staged plan on stderr
  *   SCRATCH_POISON          both intermediate buffers and the frame's ring slot filled with 0xFF bytes (NaN in binary16 and f32)
- *                           at the start of every frame: an element a stage reads without the frame having written it turns into NaN */
+ *                           at the start of every frame: an element a stage reads without the frame having written it turns into NaN
+ * and two of the frame operations:
+ *   GRAM_BOXES_BUDGET=bytes the partials a batch of boxes of beamformer_hip_gram_boxes_last_frames may hold (default 64 MiB): a small
+ *                           value makes a handful of small boxes cross a batch boundary (the bytes are the same)
+ *   BLEND_SHAPE=0|1         the kernel of beamformer_hip_mix_field_last_frames: 0 the corner nodes outermost, 1 each source loaded once
+ *                           for all corners (only where the lattice has one node along y; elsewhere 0 runs); unset: the measured
+ *                           default (the bytes are the same) */
 
 /* ---- ZBP acquisition files (external/zemp_bp.h; loader tests/throughput.c:135-374) ----
  * Host only, no device needed.  The reference keeps this loader in its throughput harness;

@@ -632,6 +632,43 @@ static inline void bf_warp_tile(const uint32_t points[3], uint32_t tile_log2[3])
 	}
 }
 
+/* ---- block-wise ensemble filter (ensemble_blocks.hip: beamformer_hip_gram_boxes_last_frames, beamformer_hip_mix_field_last_frames) ---- */
+#define BF_BLOCKS_MAX_BOXES    1024u         /* = BEAMFORMER_HIP_MAX_GRAM_BOXES */
+#define BF_BLOCKS_BUDGET       (64ull << 20) /* bytes of partials a batch of boxes may hold (hook GRAM_BOXES_BUDGET sets another) */
+#define BF_BLEND_MAX_NODES     1024u         /* = BEAMFORMER_HIP_MAX_MIX_NODES */
+#define BF_BLEND_MAX_ENTRIES   (1u << 22)    /* = BEAMFORMER_HIP_MAX_MIX_FIELD_ENTRIES */
+/* one box of a batch: the arguments the single-box kernels take -- the chunking is the box's own bf_gram_chunk_words --, and where the
+ * box's blocks, mask words, partials and result lie in the batch */
+typedef struct {
+	BfGramArgs a;
+	uint32_t mask_block_first;   /* the box's first block of the mask pass (ceil(words / 4) blocks a box), a prefix over the batch */
+	uint32_t partial_block_first;/* ... of the partial pass (chunks x tile pairs blocks a box, the tile pair fastest) */
+	uint64_t mask_first;         /* the box's first word in the batch's mask */
+	uint64_t partial_first;      /* its first (chunk, tile pair) in the batch's partials */
+	uint64_t result_first;       /* its result {voxels, non_finite, gram[frames][frames][2]} in the call's results, bytes */
+} BfBlocksBox;
+/* one segment cell of the field mix: a box of the frame whose voxels share their (up to) 8 corner nodes */
+typedef struct {
+	uint32_t first[3], count[3]; /* the box, inside the frame, every count >= 1; a voxel's r along axis a is its index inside the box */
+	uint32_t node[3];            /* the lower node along each axis */
+	uint32_t corners[3];         /* 2: nodes node[a] and node[a] + 1 are blended along axis a; 1: node[a] alone */
+	uint32_t volume;             /* voxels of the box */
+	uint32_t block_first;        /* the cell's first block (ceil(volume / 256) x output tiles blocks a cell, the tile fastest), a prefix */
+	uint32_t reserved[2];
+} BfBlendCell;
+typedef struct {
+	uint32_t frames, outputs;    /* K, M */
+	uint32_t cplx;
+	uint32_t padded_outputs;     /* M rounded up to BF_MIX_TILE: the rows of a node's weight table, zero past M */
+	uint32_t points[3];          /* the frames' common grid */
+	uint32_t nodes[3];           /* N_a */
+	float    inv_step[3];        /* 1.0f / node_step[a] (not read where N_a == 1) */
+	uint32_t cells, blocks;      /* cells of the table, blocks of the launch */
+	uint32_t once;               /* 1: blend_once_kernel, each source loaded once a k for all corners (nodes[1] == 1 only; the bytes are the same) */
+	uint32_t reserved;
+	uint64_t out_offset, out_stride;   /* the first output frame in the ring, bytes; from one output to the next */
+} BfBlendArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -751,6 +788,16 @@ hipError_t bf_launch_gram(const void *ring, const uint64_t *offsets, const BfGra
 /* ensemble.hip, the mix: one launch.  weights[padded_outputs][frames][2] floats (real frames: the imaginary ones are not read) and
  * offsets[frames] are device memory; output j is written at ring + out_offset + j * out_stride */
 hipError_t bf_launch_mix(void *ring, const uint64_t *offsets, const float *weights, const BfMixArgs *a, hipStream_t s);
+/* ensemble_blocks.hip, the Gram matrices of one batch of boxes: the three passes of bf_launch_gram, each ONE launch over all boxes of
+ * the batch.  host_boxes: the batch's rows as the caller filled them (read here for the launch shapes and checked as bf_launch_gram
+ * checks its arguments), boxes: the same rows in device memory; mask_blocks, partial_blocks: the batch's totals.  mask, partials: the
+ * batch's own (a box's rows say where in them it lies); results: the call's.  The boxes lie inside every frame (the caller checks) */
+hipError_t bf_launch_gram_boxes(const void *ring, const uint64_t *offsets, const BfBlocksBox *host_boxes, const BfBlocksBox *boxes, uint32_t box_count,
+                                uint32_t mask_blocks, uint32_t partial_blocks, uint64_t *mask, double *partials, void *results, hipStream_t s);
+/* ensemble_blocks.hip, the field mix: one launch.  weights[node][padded_outputs / BF_MIX_TILE][frames][BF_MIX_TILE][2] floats -- a mix's
+ * table a node, in the lattice's flat node order --, cells[a->cells] and offsets[frames] are device memory; the cells tile the frame, and
+ * a->blocks is the sum their block_first prefix ends in (the caller builds both: frame_ops.cpp) */
+hipError_t bf_launch_blend(void *ring, const uint64_t *offsets, const float *weights, const BfBlendCell *cells, const BfBlendArgs *a, hipStream_t s);
 /* autocorr.hip: one launch.  weights: the mix's table of `rows` rows, [ceil(rows / BF_MIX_TILE)][frames][BF_MIX_TILE][2] floats, rows past
  * `rows` zero -- or NULL, the identity form (rows == frames: row n is source frame n).  Lag l is written at ring + out_offset +
  * l * out_stride */

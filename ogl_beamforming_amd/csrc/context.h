@@ -177,6 +177,11 @@ struct FrameOps {
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
 	hipEvent_t   mix_copied = nullptr, mix_begin = nullptr, mix_end = nullptr;   /* ... and the event pair around its launch */
 	bool         mix_copy_pending = false;
+	DeviceBuffer blend_table;                                  /* mix_field_last_frames: the nodes' weight tables and the cell table of a call (ensemble_blocks.hip); the sources' ring offsets travel in mix_table */
+	void        *blend_pinned = nullptr;                       /* ... the pinned memory they are sent from, grown on demand, free again once blend_copied has passed (the call does not synchronise) */
+	size_t       blend_pinned_size = 0;
+	hipEvent_t   blend_copied = nullptr;
+	bool         blend_copy_pending = false;
 	DeviceBuffer spatial_scratch;                              /* convolve_last_frames: what lies between two passes -- one run of frames, and the D fields of Normalised mode (spatial.hip) */
 	void release();                                            /* everything above freed and as constructed; the caller has synchronised the device */
 };
@@ -362,6 +367,13 @@ bool convolve_last_frames(uint32_t count, const float *const taps[3], const uint
 bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3], const float node_first[3], const float node_step[3],
                       const float *rotations, uint32_t interpolation, uint32_t edge, uint32_t image_plane_tag,
                       uint32_t *first_frame_id, float *device_ms);            /* likewise: the field, the lattice and the modes are checked by the caller */
+bool gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regions, uint32_t region_count, double *grams,
+                            BeamformerHipEnsembleInfo *infos, float *device_ms);   /* likewise: the counts and the entry cap are checked by the caller */
+void set_gram_boxes_budget(uint64_t bytes);                       /* hook GRAM_BOXES_BUDGET: the partials a batch of boxes may hold; 0: the default, BF_BLOCKS_BUDGET */
+void set_blend_shape(int shape);                                 /* hook BLEND_SHAPE: 0 corners outermost, 1 sources once (where the lattice has no nodes along y), -1: the measured default */
+bool mix_field_last_frames(uint32_t count, const float *weights, const uint32_t nodes[3], const uint32_t node_first[3],
+                           const uint32_t node_step[3], uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id,
+                           float *device_ms);                      /* likewise: the counts, the lattice and the weights' finiteness are checked by the caller */
 
 } // namespace bf
 #endif

@@ -1,6 +1,6 @@
 /* frame_ops.cpp -- the calls that work on frames already in the ring: the reduce calls (score, find_peaks, accumulate_peaks, pair_peaks,
- * track_peaks, draw_tracks, gram, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
- * the queued runs (mix, autocorrelate, convolve, warp, queue_localisation_map, queue_track_map), which write frames of their own behind
+ * track_peaks, draw_tracks, gram, gram_boxes, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
+ * the queued runs (mix, mix_field, autocorrelate, convolve, warp, queue_localisation_map, queue_track_map), which write frames of their own behind
  * the newest ones and do not.  Their
  * device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is executor.cpp's. */
 #include "context.h"
@@ -12,9 +12,9 @@ namespace bf {
 
 void FrameOps::release()
 {
-	for (DeviceBuffer *b : {&metrics_scratch, &peaks_list, &map.buffer, &tracks.buffer, &tracks_scratch, &mix_table, &spatial_scratch}) b->release();
-	for (void *p : {metrics_pinned, mix_pinned}) if (p) (void)hipHostFree(p);
-	for (hipEvent_t e : {metrics_begin, metrics_end, peaks_begin, peaks_end, mix_copied, mix_begin, mix_end}) if (e) (void)hipEventDestroy(e);
+	for (DeviceBuffer *b : {&metrics_scratch, &peaks_list, &map.buffer, &tracks.buffer, &tracks_scratch, &mix_table, &blend_table, &spatial_scratch}) b->release();
+	for (void *p : {metrics_pinned, mix_pinned, blend_pinned}) if (p) (void)hipHostFree(p);
+	for (hipEvent_t e : {metrics_begin, metrics_end, peaks_begin, peaks_end, mix_copied, mix_begin, mix_end, blend_copied}) if (e) (void)hipEventDestroy(e);
 	*this = FrameOps{};
 }
 
@@ -998,6 +998,96 @@ bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, do
 	return true;
 }
 
+namespace { uint64_t g_gram_boxes_budget = BF_BLOCKS_BUDGET; }
+void set_gram_boxes_budget(uint64_t bytes) { g_gram_boxes_budget = bytes ? bytes : BF_BLOCKS_BUDGET; }
+
+/* beamformer_hip_gram_boxes_last_frames: the Gram matrix of every box of a list, each what gram_last_frames gives for that box
+ * (ensemble_blocks.hip).  The boxes are walked in BATCHES whose partials fit the budget (a box that does not fit one on its own is a batch
+ * of one); a batch is one triple of launches, the batches sit behind one another on the stream and share one mask and one partials
+ * buffer.  One upload (the frames' offsets and every box's row), one copy back (every box's result), one synchronise.  The counts arrive
+ * checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued. */
+bool gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regions, uint32_t region_count, double *grams,
+                            BeamformerHipEnsembleInfo *infos, float *device_ms)
+{
+	static_assert(BF_BLOCKS_MAX_BOXES == BEAMFORMER_HIP_MAX_GRAM_BOXES, "one limit");
+	struct Batch { uint32_t first, boxes, mask_blocks, partial_blocks; uint64_t mask_words, partial_tiles; };
+	const uint64_t tile_bytes = sizeof(double) * 2 * BF_GRAM_TILE * BF_GRAM_TILE;
+	const size_t gram_bytes = sizeof(double) * 2 * count * count, result_bytes = 16 + gram_bytes;
+
+	/* the frames once a box: the same K records each time, and each box judged against every one of them */
+	std::vector<BoxedFrame> boxed, frames;
+	std::vector<BfBlocksBox> rows(region_count);
+	std::vector<Batch> batches;
+	for (uint32_t r = 0; r < region_count; r++) {
+		if (!newest_ensemble_frames(count, regions + r, boxed)) return false;
+		const BoxedFrame &b = boxed[0];
+		if (b.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);      /* the kernels count a box's voxels in 32 bits */
+		if (r == 0) frames = boxed;
+		BfBlocksBox &row = rows[r];
+		row = BfBlocksBox{};
+		BfGramArgs &a = row.a;
+		a.frames = count; a.cplx = b.cplx;
+		for (int k = 0; k < 3; k++) { a.points[k] = b.record->points[k]; a.first[k] = b.first[k]; a.count[k] = b.count[k]; }
+		a.volume = (uint32_t)b.volume;
+		a.words = (uint32_t)((b.volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
+		a.chunk_words = bf_gram_chunk_words(a.volume, count);
+		a.chunks = (a.words + a.chunk_words - 1u) / a.chunk_words;
+		a.tiles = bf_gram_tiles(count); a.tile_pairs = bf_gram_tile_pairs(count);
+		const uint64_t mask_blocks = (a.words + 3u) / 4u, partial_tiles = (uint64_t)a.chunks * a.tile_pairs;
+		if (batches.empty() || (batches.back().partial_tiles + partial_tiles) * tile_bytes > g_gram_boxes_budget ||
+		    batches.back().mask_blocks + mask_blocks > 0x7FFFFFFFull || batches.back().partial_blocks + partial_tiles > 0x7FFFFFFFull)
+			batches.push_back(Batch{r, 0, 0, 0, 0, 0});
+		Batch &batch = batches.back();
+		row.mask_block_first = batch.mask_blocks; row.partial_block_first = batch.partial_blocks;
+		row.mask_first = batch.mask_words; row.partial_first = batch.partial_tiles;
+		row.result_first = (uint64_t)r * result_bytes;
+		batch.boxes++; batch.mask_blocks += (uint32_t)mask_blocks; batch.partial_blocks += (uint32_t)partial_tiles;
+		batch.mask_words += a.words; batch.partial_tiles += partial_tiles;
+	}
+	Device &d = ctx().devices[0];
+	uint64_t mask_words = 0, partial_tiles = 0;
+	for (const Batch &batch : batches) {
+		if (batch.mask_words > mask_words) mask_words = batch.mask_words;
+		if (batch.partial_tiles > partial_tiles) partial_tiles = batch.partial_tiles;
+	}
+
+	/* device: offsets | rows | results | mask | partials; pinned: offsets | rows | results */
+	Carve dev;
+	const size_t offsets_at = dev.take(sizeof(uint64_t) * count), rows_at = dev.take(sizeof(BfBlocksBox) * region_count),
+	             results_at = dev.take(result_bytes * region_count), pinned_bytes = dev.total,
+	             mask_at = dev.take(sizeof(uint64_t) * mask_words), partials_at = dev.take(tile_bytes * partial_tiles);
+	if (!ensure_metrics_memory(d, pinned_bytes, dev.total)) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+
+	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
+	uint64_t *offsets = (uint64_t *)(pinned + offsets_at);
+	for (uint32_t n = 0; n < count; n++) offsets[n] = frames[n].record->offset;
+	std::memcpy(pinned + rows_at, rows.data(), sizeof(BfBlocksBox) * region_count);
+	if (!timed_reduce(d, rows_at + sizeof(BfBlocksBox) * region_count, results_at, result_bytes * region_count, device_ms, [&](hipStream_t s) {
+		for (const Batch &batch : batches) {
+			const hipError_t e = bf_launch_gram_boxes(d.ring.ptr, (const uint64_t *)(device + offsets_at), rows.data() + batch.first,
+			                                          (const BfBlocksBox *)(device + rows_at) + batch.first, batch.boxes, batch.mask_blocks,
+			                                          batch.partial_blocks, (uint64_t *)(device + mask_at), (double *)(device + partials_at),
+			                                          device + results_at, s);
+			if (e != hipSuccess) return e;
+		}
+		return hipSuccess;
+	})) return false;
+	const BoxedFrame &b0 = frames[0];
+	for (uint32_t r = 0; r < region_count; r++) {
+		const char *result = pinned + results_at + (size_t)r * result_bytes;
+		std::memcpy((char *)grams + (size_t)r * gram_bytes, result + 16, gram_bytes);
+		if (!infos) continue;
+		BeamformerHipEnsembleInfo *info = infos + r;
+		const BfGramArgs &a = rows[r].a;
+		std::memset(info, 0, sizeof(*info));
+		info->count = count; info->data_kind = (uint32_t)b0.record->data_kind;
+		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->region_first[k] = a.first[k]; info->region_count[k] = a.count[k]; }
+		info->first_frame_id = b0.record->id;
+		std::memcpy(&info->voxels, result, 8); std::memcpy(&info->non_finite, result + 8, 8);
+	}
+	return true;
+}
+
 /* beamformer_hip_correlate_last_frames: the `count` newest frames correlated with one of them at every shift of the window, over every
  * box, where they lie (correlate.hip).  The arguments arrive checked (lib_api.cpp: the counts, the window, the entry cap); everything
  * else that can refuse is decided before anything is enqueued. */
@@ -1090,6 +1180,9 @@ namespace {
 struct RunTable {
 	const float *weights = nullptr; uint32_t rows = 0;
 	const float *flat = nullptr;    uint32_t flat_floats = 0;
+	/* true: `weights` holds `rows` rows that are judged as a mix's are (no imaginary part on real frames) but travel in a table of the
+	 * call's own, which prepare() fills and launch() sends (beamformer_hip_mix_field_last_frames: a table a node) */
+	bool own_table = false;
 	/* not null: a run that has no source frames (count 0: beamformer_hip_queue_localisation_map) -- Float32 frames of this record's grid,
 	 * carrying its block, stand where the newest source's record does */
 	const FrameRecord *shape = nullptr;
@@ -1133,7 +1226,7 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 		if (b.record->offset < run_first + run_bytes && run_first < b.record->offset + b.record->bytes) return set_error(BeamformerLibErrorKind_FrameSizeOverflow);
 
 	/* the table: offsets[K] | weights[tile][k][BF_MIX_TILE][2], rows past `rows` zero */
-	const uint32_t padded = weights ? (rows + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE : 0u;
+	const uint32_t padded = weights && !t.own_table ? (rows + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE : 0u;
 	const size_t offsets_bytes = round_up(sizeof(uint64_t) * K, 64), weights_bytes = t.flat ? sizeof(float) * t.flat_floats : sizeof(float) * 2 * padded * K;
 	const size_t table_max = round_up(sizeof(uint64_t) * BF_ENSEMBLE_MAX_FRAMES, 64) + sizeof(float) * 2 * BF_ENSEMBLE_MAX_FRAMES * BF_ENSEMBLE_MAX_FRAMES;
 	bool ok = HIP_OK(hipSetDevice(d.device));
@@ -1151,7 +1244,7 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 	float *table = (float *)(pinned + offsets_bytes);
 	std::memset(table, 0, weights_bytes);
 	if (t.flat) std::memcpy(table, t.flat, weights_bytes);
-	for (uint32_t j = 0; j < rows && weights; j++)
+	for (uint32_t j = 0; j < rows && weights && !t.own_table; j++)
 		for (uint32_t k = 0; k < K; k++) {
 			float *w = table + (((size_t)(j / BF_MIX_TILE) * K + k) * BF_MIX_TILE + j % BF_MIX_TILE) * 2;
 			w[0] = weights[((size_t)j * K + k) * 2]; w[1] = weights[((size_t)j * K + k) * 2 + 1];
@@ -1162,7 +1255,7 @@ bool queue_frames_of_newest(uint32_t count, const RunTable &t, uint32_t out_coun
 		hipStream_t s = d.stream;
 		QueuedRun run{};
 		run.d = &d; run.ring = d.ring.ptr; run.offsets = (const uint64_t *)d.ops.mix_table.ptr;
-		run.table = weights || t.flat ? (const float *)((const char *)d.ops.mix_table.ptr + offsets_bytes) : nullptr;
+		run.table = (weights && !t.own_table) || t.flat ? (const float *)((const char *)d.ops.mix_table.ptr + offsets_bytes) : nullptr;
 		run.K = K; run.cplx = cplx;
 		for (int k = 0; k < 3; k++) run.points[k] = newest.points[k];
 		run.elements = (uint64_t)newest.points[0] * newest.points[1] * newest.points[2];
@@ -1197,6 +1290,106 @@ bool mix_last_frames(uint32_t count, const float *weights, uint32_t out_count, u
 			a.frames = r.K; a.outputs = out_count; a.cplx = r.cplx; a.padded_outputs = (out_count + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE;
 			a.elements = r.elements; a.out_offset = r.out_offset; a.out_stride = r.out_stride;
 			return bf_launch_mix(r.ring, r.offsets, r.table, &a, r.s);
+		});
+}
+
+/* which shape of the field mix runs where both apply -- a lattice without nodes along y --, by measurement (tools/block_filter_rate.py,
+ * profiles/block_filter_rate.json) */
+constexpr bool kBlendSourcesOnce = false;
+namespace { int g_blend_shape = -1; }
+void set_blend_shape(int shape) { g_blend_shape = shape; }
+
+/* beamformer_hip_mix_field_last_frames: out_count combinations of the `count` newest frames under a weight table that varies over the
+ * frame -- given at the nodes of a lattice, blended between them --, queued as frames of their own (ensemble_blocks.hip).  One launch.
+ * The frame is cut into segment cells here: along axis a the segments [0, P_0), [P_j, P_j+1) and [P_N-1, points), each clipped to the
+ * frame and left out when empty (one segment, the whole axis, where N_a == 1); a cell is the product of one segment an axis, and carries
+ * its lower nodes, whether it blends along each axis, and the prefix of block counts the kernel finds its cell by.  The nodes' tables
+ * -- each laid out as a mix's, [tile][k][BF_MIX_TILE][2], rows past out_count zero -- and the cells travel through pinned memory of the
+ * call's own (FrameOps::blend_pinned), the sources' offsets through the skeleton's table. */
+bool mix_field_last_frames(uint32_t count, const float *weights, const uint32_t nodes[3], const uint32_t node_first[3],
+                           const uint32_t node_step[3], uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id, float *device_ms)
+{
+	static_assert(BF_BLEND_MAX_NODES == BEAMFORMER_HIP_MAX_MIX_NODES && BF_BLEND_MAX_ENTRIES == BEAMFORMER_HIP_MAX_MIX_FIELD_ENTRIES, "one limit");
+	const uint32_t node_product = nodes[0] * nodes[1] * nodes[2];
+	const uint32_t K = count, M = out_count, padded = (M + BF_MIX_TILE - 1u) / BF_MIX_TILE * BF_MIX_TILE, tiles = padded / BF_MIX_TILE;
+	const size_t node_floats = (size_t)2 * padded * K, weights_bytes = round_up(sizeof(float) * node_floats * node_product, 64);
+	BfBlendArgs a{};
+	a.frames = K; a.outputs = M; a.padded_outputs = padded;
+	for (int k = 0; k < 3; k++) {
+		a.nodes[k] = nodes[k];
+		if (nodes[k] > 1u) a.inv_step[k] = 1.0f / (float)node_step[k];
+	}
+	/* the kernel's shape (ensemble_blocks.hip; the bytes are the same): hook BLEND_SHAPE, else kBlendSourcesOnce; sources-once has no lerp along y */
+	a.once = (g_blend_shape < 0 ? kBlendSourcesOnce : g_blend_shape == 1) && nodes[1] == 1u;
+	std::vector<BfBlendCell> cells;
+	RunTable t; t.weights = weights; t.rows = node_product * M; t.own_table = true;
+	return queue_frames_of_newest(count, t, out_count, image_plane_tag, first_frame_id, device_ms,
+		[&](Device &d, const FrameRecord &newest, bool, uint32_t) {
+			if ((uint64_t)newest.points[0] * newest.points[1] * newest.points[2] > 0x7FFFFFFFull) return false;   /* the kernel counts a cell's voxels in 32 bits */
+			/* the segments of every axis: {first voxel, voxels, lower node, corners} */
+			struct Segment { uint32_t first, count, node, corners; };
+			std::vector<Segment> segments[3];
+			for (int k = 0; k < 3; k++) {
+				const uint64_t points = newest.points[k];
+				if (nodes[k] == 1u) { segments[k].push_back(Segment{0u, (uint32_t)points, 0u, 1u}); continue; }
+				const auto node_at = [&](uint32_t j) { const uint64_t at = (uint64_t)node_first[k] + (uint64_t)j * node_step[k]; return at < points ? at : points; };
+				if (node_at(0) > 0) segments[k].push_back(Segment{0u, (uint32_t)node_at(0), 0u, 1u});
+				for (uint32_t j = 0; j + 1u < nodes[k]; j++)
+					if (node_at(j + 1u) > node_at(j)) segments[k].push_back(Segment{(uint32_t)node_at(j), (uint32_t)(node_at(j + 1u) - node_at(j)), j, 2u});
+				if (node_at(nodes[k] - 1u) < points)
+					segments[k].push_back(Segment{(uint32_t)node_at(nodes[k] - 1u), (uint32_t)(points - node_at(nodes[k] - 1u)), nodes[k] - 1u, 1u});
+			}
+			cells.clear();
+			uint64_t blocks = 0;
+			for (const Segment &sz : segments[2]) for (const Segment &sy : segments[1]) for (const Segment &sx : segments[0]) {
+				const Segment *of[3] = {&sx, &sy, &sz};
+				BfBlendCell cell{};
+				cell.volume = 1;
+				for (int k = 0; k < 3; k++) {
+					cell.first[k] = of[k]->first; cell.count[k] = of[k]->count; cell.node[k] = of[k]->node; cell.corners[k] = of[k]->corners;
+					cell.volume *= of[k]->count;
+				}
+				cell.block_first = (uint32_t)blocks;
+				blocks += (uint64_t)((cell.volume + 255u) / 256u) * tiles;      /* (at most the frame's voxels x 16 tiles: below 2^35) */
+				cells.push_back(cell);
+			}
+			if (blocks > 0x7FFFFFFFull) return false;
+			a.cells = (uint32_t)cells.size(); a.blocks = (uint32_t)blocks;
+			for (int k = 0; k < 3; k++) a.points[k] = newest.points[k];
+
+			/* the call's own table: weights[node][tile][k][BF_MIX_TILE][2] | cells */
+			FrameOps &o = d.ops;
+			const size_t bytes = weights_bytes + sizeof(BfBlendCell) * cells.size();
+			if (!o.blend_table.ensure(bytes)) return false;
+			if (o.blend_copy_pending) { (void)hipEventSynchronize(o.blend_copied); o.blend_copy_pending = false; }   /* (the previous call's copy: long done) */
+			if (o.blend_pinned_size < bytes) {
+				if (o.blend_pinned) (void)hipHostFree(o.blend_pinned);
+				o.blend_pinned = nullptr; o.blend_pinned_size = 0;
+				if (!HIP_OK(hipHostMalloc(&o.blend_pinned, bytes, hipHostMallocDefault))) { o.blend_pinned = nullptr; return false; }
+				o.blend_pinned_size = bytes;
+			}
+			if (!o.blend_copied && !HIP_OK(hipEventCreateWithFlags(&o.blend_copied, hipEventDisableTiming))) { o.blend_copied = nullptr; return false; }
+			float *table = (float *)o.blend_pinned;
+			std::memset(table, 0, weights_bytes);
+			for (uint32_t c = 0; c < node_product; c++)
+				for (uint32_t j = 0; j < M; j++)
+					for (uint32_t k = 0; k < K; k++) {
+						const float *from = weights + (((size_t)c * M + j) * K + k) * 2;
+						float *w = table + (size_t)c * node_floats + (((size_t)(j / BF_MIX_TILE) * K + k) * BF_MIX_TILE + j % BF_MIX_TILE) * 2;
+						w[0] = from[0]; w[1] = from[1];
+					}
+			std::memcpy((char *)o.blend_pinned + weights_bytes, cells.data(), sizeof(BfBlendCell) * cells.size());
+			/* sent from here, in front of the event pair: nothing refuses the call any more, and the table is read by this call's launch alone */
+			if (!HIP_OK(hipMemcpyAsync(o.blend_table.ptr, o.blend_pinned, bytes, hipMemcpyHostToDevice, d.stream))) return false;
+			o.blend_copy_pending = HIP_OK(hipEventRecord(o.blend_copied, d.stream));
+			return o.blend_copy_pending;
+		},
+		[&](const QueuedRun &r) {
+			FrameOps &o = r.d->ops;
+			BfBlendArgs args = a;
+			args.cplx = r.cplx; args.out_offset = r.out_offset; args.out_stride = r.out_stride;
+			return bf_launch_blend(r.ring, r.offsets, (const float *)o.blend_table.ptr, (const BfBlendCell *)((const char *)o.blend_table.ptr + weights_bytes),
+			                       &args, r.s);
 		});
 }
 

@@ -1219,6 +1219,69 @@ uint32_t beamformer_hip_mix_last_frames(uint32_t count, const float *weights, ui
 	return mix_last_frames(count, weights, out_count, image_plane_tag, first_frame_id, device_ms);
 }
 
+uint32_t beamformer_hip_gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regions, uint32_t region_count, double *grams,
+                                               BeamformerHipEnsembleInfo *infos, float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(region_count >= 1 && region_count <= BEAMFORMER_HIP_MAX_GRAM_BOXES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check((uint64_t)region_count * count * count <= BEAMFORMER_HIP_MAX_GRAM_BOX_ENTRIES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(grams != nullptr && regions != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return gram_boxes_last_frames(count, regions, region_count, grams, infos, device_ms);
+}
+
+/* host only: the boxes of a lattice's nodes, clipped to the frame (include/ogl_beamformer_hip.h has the rule) */
+uint32_t beamformer_hip_lattice_boxes(const uint32_t points[3], const uint32_t nodes[3], const uint32_t node_first[3], const uint32_t node_step[3],
+                                      const uint32_t half[3], BeamformerHipFrameRegion *regions)
+{
+	if (!check(points && nodes && node_first && node_step && half && regions, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	uint64_t node_product = 1;
+	for (int a = 0; a < 3; a++) {
+		if (!check(points[a] != 0 && nodes[a] != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+		node_product *= nodes[a];                             /* (at most 1024 x 2^32 - 1: no overflow) */
+		if (!check(node_product <= BEAMFORMER_HIP_MAX_MIX_NODES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	}
+	/* an axis's boxes: [max(0, P - half), min(points, P + half + 1)), P in 64 bits */
+	std::vector<uint32_t> first[3], count[3];
+	for (int a = 0; a < 3; a++) {
+		if (!check(nodes[a] == 1 || node_step[a] != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+		for (uint32_t j = 0; j < nodes[a]; j++) {
+			const uint64_t at = (uint64_t)node_first[a] + (uint64_t)j * (nodes[a] > 1 ? node_step[a] : 0u);
+			const uint64_t lo = at > half[a] ? at - half[a] : 0, hi = at + half[a] + 1u < points[a] ? at + half[a] + 1u : points[a];
+			if (!check(lo < hi, BeamformerLibErrorKind_InvalidAccess)) return 0;      /* the box misses the frame */
+			first[a].push_back((uint32_t)lo); count[a].push_back((uint32_t)(hi - lo));
+		}
+	}
+	for (uint32_t jz = 0; jz < nodes[2]; jz++)
+		for (uint32_t jy = 0; jy < nodes[1]; jy++)
+			for (uint32_t jx = 0; jx < nodes[0]; jx++) {
+				BeamformerHipFrameRegion &r = regions[((size_t)jz * nodes[1] + jy) * nodes[0] + jx];
+				const uint32_t j[3] = {jx, jy, jz};
+				for (int a = 0; a < 3; a++) { r.first[a] = first[a][j[a]]; r.count[a] = count[a][j[a]]; }
+			}
+	return 1;
+}
+
+uint32_t beamformer_hip_mix_field_last_frames(uint32_t count, const float *weights, const uint32_t nodes[3], const uint32_t node_first[3],
+                                              const uint32_t node_step[3], uint32_t out_count, uint32_t image_plane_tag, uint32_t *first_frame_id,
+                                              float *device_ms)
+{
+	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES && out_count >= 1 && out_count <= BEAMFORMER_HIP_MAX_ENSEMBLE_FRAMES,
+	           BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!check(weights != nullptr && nodes != nullptr && node_first != nullptr && node_step != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	uint64_t node_product = 1;
+	for (int a = 0; a < 3; a++) {
+		if (!check(nodes[a] >= 1, BeamformerLibErrorKind_BufferOverflow)) return 0;
+		node_product *= nodes[a];                             /* (at most 1024 x 2^32 - 1: no overflow) */
+		if (!check(node_product <= BEAMFORMER_HIP_MAX_MIX_NODES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	}
+	if (!check(node_product * out_count * count <= BEAMFORMER_HIP_MAX_MIX_FIELD_ENTRIES, BeamformerLibErrorKind_BufferOverflow)) return 0;
+	for (int a = 0; a < 3; a++)
+		if (!check(nodes[a] == 1 || node_step[a] != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	for (size_t n = 0; n < (size_t)2 * node_product * out_count * count; n++)
+		if (!check(std::isfinite(weights[n]), BeamformerLibErrorKind_InvalidAccess)) return 0;
+	return mix_field_last_frames(count, weights, nodes, node_first, node_step, out_count, image_plane_tag, first_frame_id, device_ms);
+}
+
 uint32_t beamformer_hip_autocorrelate_last_frames(uint32_t count, const float *weights, uint32_t rows, uint32_t lag_count, uint32_t image_plane_tag,
                                                   uint32_t *first_frame_id, float *device_ms)
 {
@@ -1458,6 +1521,16 @@ uint32_t beamformer_hip_describe_plan(uint32_t parameter_slot, BeamformerHipPlan
 
 uint32_t beamformer_hip_set_hook(const char *name, const char *value)
 {
+	/* the two switches that are no das_select.cpp switches: how the boxes of beamformer_hip_gram_boxes_last_frames are batched, and which
+	 * of its two kernels beamformer_hip_mix_field_last_frames runs (frame_ops.cpp) */
+	if (name && !std::strcmp(name, "GRAM_BOXES_BUDGET")) {
+		set_gram_boxes_budget(value && value[0] ? std::strtoull(value, nullptr, 0) : 0);
+		return 1;
+	}
+	if (name && !std::strcmp(name, "BLEND_SHAPE")) {
+		set_blend_shape(value && value[0] ? (std::strtoul(value, nullptr, 0) ? 1 : 0) : -1);
+		return 1;
+	}
 	return check(set_hook(name, value), BeamformerLibErrorKind_InvalidAccess);
 }
 

@@ -157,6 +157,11 @@ def _load():
         "beamformer_hip_gram_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo), C.POINTER(C.c_float)]),
         "beamformer_hip_clutter_projector": (u32, [C.POINTER(C.c_double), u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
         "beamformer_hip_mix_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
+        "beamformer_hip_gram_boxes_last_frames": (u32, [u32, C.POINTER(P.HipFrameRegion), u32, C.POINTER(C.c_double), C.POINTER(P.HipEnsembleInfo),
+                                                        C.POINTER(C.c_float)]),
+        "beamformer_hip_lattice_boxes": (u32, [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(P.HipFrameRegion)]),
+        "beamformer_hip_mix_field_last_frames": (u32, [u32, C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, u32,
+                                                       C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_autocorrelate_last_frames": (u32, [u32, C.POINTER(C.c_float), u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_convolve_last_frames": (u32, [u32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(u32), u32, u32, C.POINTER(u32), C.POINTER(C.c_float)]),
         "beamformer_hip_correlate_last_frames": (u32, [u32, u32, C.POINTER(P.HipFrameRegion), u32, C.POINTER(u32), C.POINTER(P.HipShiftCorrelation),
@@ -835,6 +840,61 @@ def mix_last_frames(count, weights, tag=0, timed=True):
     first, ms = C.c_uint32(0), C.c_float(0)
     _check(library().beamformer_hip_mix_last_frames(count, weights.ctypes.data_as(C.POINTER(C.c_float)), out_count, int(tag), C.byref(first),
                                                     C.byref(ms) if timed else None))
+    return int(first.value), float(ms.value)
+
+
+def gram_boxes_last_frames(count, regions):
+    """beamformer_hip_gram_boxes_last_frames: the slow-time Gram matrix of the `count` newest frames over each box of `regions` (a
+    sequence of HipFrameRegion: see frame_region() and lattice_boxes()), each byte for byte what gram_last_frames gives for that box, in
+    one call that synchronises once.  Returns (grams, infos, device_ms): a complex128 (B, count, count) array, the B HipEnsembleInfo
+    and the device time of the launches."""
+    count = int(count)
+    boxes = list(regions)
+    B = len(boxes)
+    room = (B, count, count) if 0 < B <= P.HIP_MAX_GRAM_BOXES and 0 < count <= P.HIP_MAX_ENSEMBLE_FRAMES and \
+        B * count * count <= P.HIP_MAX_GRAM_BOX_ENTRIES else (1, 1, 1)       # the call refuses before it writes: room for nothing
+    grams = np.zeros(room, np.complex128)
+    array = (P.HipFrameRegion * max(1, B))(*boxes)
+    infos, ms = (P.HipEnsembleInfo * room[0])(), C.c_float(0)
+    _check(library().beamformer_hip_gram_boxes_last_frames(count, array, B, grams.ctypes.data_as(C.POINTER(C.c_double)), infos, C.byref(ms)))
+    return grams, list(infos), float(ms.value)
+
+
+def _three(values, what):
+    values = [int(v) for v in values]
+    if len(values) != 3:
+        raise ValueError(what + ": one number per axis, x, y, z")
+    return (C.c_uint32 * 3)(*[v & 0xFFFFFFFF for v in values]), values
+
+
+def lattice_boxes(points, nodes, node_first, node_step, half):
+    """beamformer_hip_lattice_boxes (host only): the boxes of a lattice of nodes = (x, y, z) nodes an axis on a grid of `points`, node j
+    of axis a at voxel node_first[a] + j * node_step[a], each box reaching `half[a]` voxels to either side of its node and clipped to the
+    frame.  Returns a list of HipFrameRegion in flat node order, (jz * Ny + jy) * Nx + jx: what gram_boxes_last_frames takes, and the
+    order of the nodes of mix_field_last_frames' weights."""
+    arrays = [_three(v, what) for v, what in ((points, "points"), (nodes, "nodes"), (node_first, "node_first"), (node_step, "node_step"), (half, "half"))]
+    N = arrays[1][1]
+    product = N[0] * N[1] * N[2]
+    regions = (P.HipFrameRegion * (product if 0 < product <= P.HIP_MAX_MIX_NODES else 1))()
+    _check(library().beamformer_hip_lattice_boxes(*[a for a, _ in arrays], regions))
+    return list(regions)
+
+
+def mix_field_last_frames(count, weights, node_first, node_step, tag=0, timed=True):
+    """beamformer_hip_mix_field_last_frames: weights.shape[3] new frames of the frame ring, a mix of the `count` newest frames whose
+    weight table varies over the frame.  weights: complex (Nz, Ny, Nx, M, count) -- the table mix_last_frames would take, one at each
+    node of a lattice, node j of axis a at voxel node_first[a] + j * node_step[a] (x, y, z).  Between two nodes the nodes' outputs are
+    blended linearly, outside the lattice the nearest node's table holds; a lattice of one node is mix_last_frames.  Returns
+    (first_frame_id, device_ms); timed False: the call does not synchronise and device_ms is 0."""
+    count = int(count)
+    weights = np.ascontiguousarray(np.asarray(weights), np.complex64)
+    if weights.ndim != 5 or weights.shape[4] != count:
+        raise ValueError(f"weights {weights.shape}: not (Nz, Ny, Nx, M, count = {count})")
+    nodes, _ = _three(weights.shape[2::-1], "nodes")
+    first, ms = C.c_uint32(0), C.c_float(0)
+    _check(library().beamformer_hip_mix_field_last_frames(count, weights.ctypes.data_as(C.POINTER(C.c_float)), nodes, _three(node_first, "node_first")[0],
+                                                          _three(node_step, "node_step")[0], int(weights.shape[3]), int(tag), C.byref(first),
+                                                          C.byref(ms) if timed else None))
     return int(first.value), float(ms.value)
 
 

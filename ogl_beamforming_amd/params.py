@@ -424,6 +424,10 @@ class HipDrawnFrame(C.Structure):
 assert C.sizeof(HipDrawnFrame) == 64
 
 HIP_MAX_ENSEMBLE_FRAMES = 256
+HIP_MAX_GRAM_BOXES = 1024               # BEAMFORMER_HIP_MAX_GRAM_BOXES
+HIP_MAX_GRAM_BOX_ENTRIES = 1 << 22      # BEAMFORMER_HIP_MAX_GRAM_BOX_ENTRIES: boxes x count x count
+HIP_MAX_MIX_NODES = 1024                # BEAMFORMER_HIP_MAX_MIX_NODES: product of nodes
+HIP_MAX_MIX_FIELD_ENTRIES = 1 << 22     # BEAMFORMER_HIP_MAX_MIX_FIELD_ENTRIES: product of nodes x out_count x count
 HIP_MAX_LAGS = 4                # BEAMFORMER_HIP_MAX_LAGS
 HIP_MAX_SPATIAL_TAPS = 33       # BEAMFORMER_HIP_MAX_SPATIAL_TAPS
 
