@@ -156,22 +156,28 @@ struct FrameOps {
 	hipEvent_t   metrics_begin = nullptr, metrics_end = nullptr;   /* ... and the event pair around its launches, created once */
 	DeviceBuffer peaks_list;                                   /* find_peaks_last_frames: the packed records of a call (frame_peaks.hip); its tables live in metrics_scratch and metrics_pinned */
 	hipEvent_t   peaks_begin = nullptr, peaks_end = nullptr;   /* ... and the event pair around its emit launch (metrics_begin / metrics_end: around mark and scan) */
-	struct LocalisationMap {
-		DeviceBuffer buffer;                                   /* the localisation map: `points` voxels of uint32 counts (beamformer_hip_localisation_map_reset; frame_peaks.hip deposits into it); points[0] == 0: none */
+	/* A map the peak calls deposit into: `points` voxels of uint32 counts and, behind them from sums_at() on, `sum_components` times as
+	 * many int64 sums (frame_peaks.hip, frame_tracks.hip deposit into it); points[0] == 0: none.  Beside it what the deposits since its
+	 * reset add up to. */
+	struct DepositMap {
+		explicit DepositMap(uint32_t sums) : sum_components(sums) {}
+		DeviceBuffer buffer;
 		uint32_t     points[3]{};
-		uint32_t     calls = 0, block = 0;                     /* ... successful accumulate calls since the reset, and the parameter block of the newest frame of the last one */
-		uint64_t     deposited = 0, outside = 0;               /* ... and their totals */
-		void forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
-	} map;
-	struct TrackMap {
-		DeviceBuffer buffer;                                   /* the track map: `points` voxels of uint32 counts, then -- from sums_at() on -- three times as many int64 displacement sums (beamformer_hip_track_map_reset; frame_tracks.hip deposits into it); points[0] == 0: none */
-		uint32_t     points[3]{};
-		uint32_t     calls = 0, block = 0;                     /* ... successful pair calls with deposit since the reset, and the parameter block of the newest frame of the last one */
+		uint32_t     sum_components;                           /* 0 or 3 */
+		uint32_t     calls = 0, block = 0;                     /* the successful calls that deposited since the reset, and the parameter block of the newest frame of the last one */
 		uint64_t     pairs = 0, deposited = 0, outside = 0;    /* ... and their totals */
 		uint64_t voxels() const { return (uint64_t)points[0] * points[1] * points[2]; }
 		size_t   sums_at() const { return round_up(sizeof(uint32_t) * voxels(), 64); }
-		void forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; pairs = deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
-	} tracks;
+		size_t   bytes() const { return sum_components ? sums_at() + sum_components * sizeof(int64_t) * (size_t)voxels() : sizeof(uint32_t) * (size_t)voxels(); }
+		bool     exists() const { return buffer.ptr && points[0]; }
+		void     forget() { points[0] = points[1] = points[2] = 0; calls = block = 0; pairs = deposited = outside = 0; }   /* no map, nothing counted; the buffer stays */
+		void     credit(uint32_t newest_block, uint64_t more_pairs, uint64_t more_deposited, uint64_t more_outside)      /* one successful call's deposits */
+		{
+			calls++; block = newest_block; pairs += more_pairs; deposited += more_deposited; outside += more_outside;
+		}
+	};
+	DepositMap   map{0};                                       /* the localisation map: counts alone (beamformer_hip_localisation_map_reset) */
+	DepositMap   tracks{3};                                    /* the track map: counts and three displacement sums (beamformer_hip_track_map_reset) */
 	DeviceBuffer tracks_scratch;                               /* pair_peaks_last_frames, track_peaks_last_frames, draw_tracks_last_frames: what is sized by the peaks the scan found -- positions, choices, the match pass's tables and the pair records, or the chain tables and the track and point records, and the smoothed points (frame_tracks.hip); its small tables live in metrics_scratch and metrics_pinned, its peak records in peaks_list */
 	DeviceBuffer mix_table;                                    /* mix_last_frames, autocorrelate_last_frames, convolve_last_frames, warp_last_frames: the source frames' ring offsets and the weight table (the tap table; the rotations and the field) of a call (ensemble.hip, autocorr.hip, spatial.hip, warp.hip) */
 	void        *mix_pinned = nullptr;                         /* ... the pinned memory they are sent from, free again once mix_copied has passed (the call does not synchronise) */
@@ -325,34 +331,35 @@ bool claim_queued_run(Device &d, const uint32_t points[3], uint32_t tag, uint32_
                       const std::function<bool(uint64_t first, const FrameRecord &frame0)> &enqueue);
 
 /* frame_ops.cpp */
+/* What the five peak calls are asked in common (include/ogl_beamformer_hip.h has each member's meaning); the arguments arrive checked
+ * (lib_api.cpp).  A call that takes no placements, reach or cap leaves them 0. */
+struct PeakQuery {
+	uint32_t count;
+	const BeamformerHipFrameRegion *region;
+	const float  *thresholds;  uint32_t threshold_count;               /* one for all frames, or one a frame */
+	const double *placements;  uint32_t placement_count;               /* likewise: 12 numbers each */
+	uint32_t use_offsets;
+	float    max_distance;
+	uint32_t max_per_frame;
+	float threshold_of(uint32_t frame) const { return thresholds[threshold_count == 1 ? 0 : frame]; }
+	const double *placement_of(uint32_t frame) const { return placements + (placement_count == 1 ? 0 : 12 * (size_t)frame); }
+};
 bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, BeamformerHipFrameMetrics *out, float *device_ms);
-bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                            uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
-                            float *device_ms);                     /* arguments checked by the caller (lib_api.cpp) */
+bool find_peaks_last_frames(const PeakQuery &q, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
+                            float *device_ms);                     /* (no placements) */
 bool quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const double *fractions, uint32_t fraction_count,
                            BeamformerHipFrameQuantiles *frames, BeamformerHipFrameQuantile *quantiles, uint32_t *histograms,
                            float *device_ms);                      /* arguments checked by the caller (lib_api.cpp) */
 float peak_threshold_of(float value, bool cplx);                   /* host only; value finite and >= 0 (the caller checks) */
-bool localisation_map_reset(const uint32_t points[3]);             /* null: release; else checked by the caller */
-bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                                  const double *placements, uint32_t placement_count, uint32_t use_offsets, BeamformerHipMapDeposits *frames,
-                                  float *device_ms);               /* arguments checked by the caller (lib_api.cpp) */
+bool deposit_map_reset(FrameOps::DepositMap &map, const uint32_t points[3]);   /* ctx().devices[0].ops.map or .tracks; null: release; else checked by the caller */
+bool accumulate_peaks_last_frames(const PeakQuery &q, BeamformerHipMapDeposits *frames, float *device_ms);
 bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info);
 bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);
-bool track_map_reset(const uint32_t points[3]);                    /* null: release; else checked by the caller */
-bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                            const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
-                            uint32_t max_per_frame, uint32_t deposit, BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs,
-                            uint32_t *pair_count, float *device_ms);   /* arguments checked by the caller (lib_api.cpp) */
-bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
-                             uint32_t max_per_frame, uint32_t min_length, uint32_t deposit, BeamformerHipTrackedFrame *rows,
-                             BeamformerHipPeakTrack *tracks, BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count,
-                             float *device_ms);
-bool draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
-                             uint32_t max_per_frame, uint32_t min_length, uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows,
-                             float *device_ms);
+bool pair_peaks_last_frames(const PeakQuery &q, uint32_t deposit, BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs, uint32_t *pair_count,
+                            float *device_ms);
+bool track_peaks_last_frames(const PeakQuery &q, uint32_t min_length, uint32_t deposit, BeamformerHipTrackedFrame *rows, BeamformerHipPeakTrack *tracks,
+                             BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count, float *device_ms);
+bool draw_tracks_last_frames(const PeakQuery &q, uint32_t min_length, uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows, float *device_ms);
 bool track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info);
 bool queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms);
 bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, double *gram, BeamformerHipEnsembleInfo *info, float *device_ms);

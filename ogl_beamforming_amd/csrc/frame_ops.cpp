@@ -1,8 +1,9 @@
-/* frame_ops.cpp -- the calls that work on frames already in the ring: the reduce calls (score, find_peaks, accumulate_peaks, pair_peaks,
- * track_peaks, draw_tracks, gram, gram_boxes, correlate), which read the newest frames where they lie and end in a synchronise, the localisation map and the track map, and
- * the queued runs (mix, mix_field, autocorrelate, convolve, warp, queue_localisation_map, queue_track_map), which write frames of their own behind
- * the newest ones and do not.  Their
- * device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is executor.cpp's. */
+/* frame_ops.cpp -- the calls that work on frames already in the ring.  The reduce calls (score, quantiles, find_peaks, accumulate_peaks,
+ * pair_peaks, track_peaks, draw_tracks, gram, gram_boxes, correlate) read the newest frames where they lie and end in a synchronise.
+ * The two deposit maps -- the localisation map and the track map -- are what the peak calls add to.  The queued runs (mix, mix_field,
+ * autocorrelate, convolve, warp, queue_localisation_map, queue_track_map) write frames of their own behind the newest ones and do not
+ * synchronise.  Their device state is Device::ops (context.h: FrameOps); the ring -- ids, placement, records, timing slots -- is
+ * executor.cpp's. */
 #include "context.h"
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -116,6 +117,12 @@ template <class Row> void box_into(Row &r, const BoxedFrame &b)
 /* The tables of a reduce call, one behind the other, each from a 64-byte boundary: take() is a table's offset in the device scratch --
  * and in the pinned block, which holds the leading tables at the same offsets (its bytes: `total` once they are taken). */
 struct Carve { size_t total = 0; size_t take(size_t bytes) { const size_t at = total; total += round_up(bytes, 64); return at; } };
+/* ... and a table of `n` T taken from one: in(base) is the table in the block that starts at `base` -- the scratch, or the pinned block */
+template <class T> struct Table {
+	size_t at = 0;
+	void take(Carve &c, size_t n) { at = c.take(sizeof(T) * n); }
+	T *in(void *base) const { return (T *)((char *)base + at); }
+};
 
 /* the pinned memory, the device scratch and the first event pair the reduce calls share: each ends in a synchronise, so all is free again when it returns */
 bool ensure_metrics_memory(Device &d, size_t pinned_bytes, size_t device_bytes)
@@ -159,14 +166,14 @@ template <class Launch> bool timed_reduce(Device &d, size_t up_bytes, size_t dow
 	return timed_reduce(d, up_bytes, down_at, down_bytes, device_ms, launch, [](hipStream_t) { return hipSuccess; });
 }
 
-/* the mark pass's rows of the boxed frames (frame_peaks.hip), as find_peaks_last_frames and accumulate_peaks_last_frames launch it: the
- * waves and blocks of all frames, the most blocks of one.  False, with InvalidAccess set: a box of more waves than the kernels number */
+/* the mark pass's rows of the boxed frames (frame_peaks.hip): the waves and blocks of all frames, the most blocks of one.  False, with
+ * InvalidAccess set: a box of more waves than the kernels number */
 struct PeaksRows {
 	std::vector<BfPeaksRow> rows;
 	uint64_t waves = 0, blocks = 0;
 	uint32_t max_blocks = 0;
 };
-bool peaks_rows_of(const std::vector<BoxedFrame> &boxed, const float *thresholds, uint32_t threshold_count, uint32_t cap, PeaksRows &out)
+bool peaks_rows_of(const std::vector<BoxedFrame> &boxed, const PeakQuery &q, PeaksRows &out)
 {
 	const uint32_t count = (uint32_t)boxed.size();
 	out.rows.resize(count);
@@ -181,138 +188,85 @@ bool peaks_rows_of(const std::vector<BoxedFrame> &boxed, const float *thresholds
 		r.waves = (uint32_t)frame_waves;
 		r.blocks = (uint32_t)((frame_waves + 3u) / 4u);
 		r.wave_first = out.waves; r.block_first = out.blocks;
-		const float t = thresholds[threshold_count == 1 ? 0 : n];
+		const float t = q.threshold_of(n);
 		r.threshold = b.cplx ? t * t : t;
-		r.cap = cap;
+		r.cap = q.max_per_frame;                           /* (the emit pass's: a call without one leaves it 0) */
 		out.waves += r.waves; out.blocks += r.blocks;
 		if (r.blocks > out.max_blocks) out.max_blocks = r.blocks;
 	}
 	return true;
 }
 
-/* What pair_peaks_last_frames and track_peaks_last_frames share: the peaks of the boxed frames found, placed and offered to one another
- * (frame_peaks.hip: mark, scan, emit; frame_tracks.hip: place, nearest).  The caller fills `boxed` (newest_boxed_frames), decides its
- * own refusals, and then calls find() -- the first synchronise --, takes its own tables from `big`, ensure(), enqueue(), its own
- * launches, collect() -- the second.
- * device: rows | placements | results | firsts | stored | block_firsts | unplaced | tallies | extra | masks | counts | offsets; pinned:
- * the first nine (rows and placements go up in one copy, firsts, stored and block_firsts in a second, unplaced, tallies and the
- * caller's `extra` come back in one: each group stays adjacent).  tracks_scratch: positions | forward | backward | the caller's. */
-struct PeakChoices {
+/* What the five peak calls do first (frame_peaks.hip: mark, scan): the rows of the boxed frames, the mark pass's tables carved from the
+ * reduce calls' scratch, the rows -- and the placements, of a call that has them -- in pinned memory, the mark launch, and what the
+ * scan found turned into the numbers that size everything behind it.  The caller fills `boxed` (newest_boxed_frames), decides its own
+ * refusals, then prepare(); then run() -- the first synchronise --, or mark() inside a timed_reduce of its own.
+ * device: rows | placements | results | lead | masks | counts | offsets | tail; pinned: up to the end of `lead` -- the tables of the
+ * call's own that travel: rows and placements go up in one copy, what comes back starts at results. */
+struct MarkFront {
 	std::vector<BoxedFrame> boxed;
 	PeaksRows table;
-	uint32_t count = 0, links = 0;
-	size_t firsts_at = 0, unplaced_at = 0, tally_bytes = 0;          /* (tally_bytes: from unplaced_at to the end of `extra`) */
+	uint32_t count = 0, cap = 0;
+	Carve dev;
+	size_t up_bytes = 0;
+	Table<BfPeaksRow> rows; Table<double> placements; Table<BfPeaksResult> results; Table<uint64_t> masks; Table<uint32_t> counts, offsets;
 	char *device = nullptr, *pinned = nullptr;
-	const BfPeaksRow *device_rows = nullptr;
-	const double *device_placements = nullptr;
-	const uint32_t *device_firsts = nullptr, *device_stored = nullptr, *device_block_firsts = nullptr;
-	uint32_t *device_unplaced = nullptr, *device_counts = nullptr, *device_offsets = nullptr;
-	BfTrackTally *device_tallies = nullptr;
-	void *device_extra = nullptr;
-	uint64_t *device_masks = nullptr;
-	const BfPeaksResult *results = nullptr;
-	uint32_t *firsts = nullptr, *stored = nullptr, *block_firsts = nullptr;
-	const uint32_t *unplaced = nullptr;
-	const BfTrackTally *tallies = nullptr;
-	const void *extra = nullptr;
-	/* what the scan found: it sizes everything behind find() -- the records, the positions, the choices, the match pass's blocks, the pairs */
+	/* what the scan found, from run() on: each frame's stored records and the first of them in the packed list, their number, and for the
+	 * calls that link frames the most of one frame, the sum over the frame pairs of min(stored[n], stored[n + 1]) and the match pass's blocks */
+	std::vector<uint32_t> stored, firsts, block_firsts;
 	uint32_t total = 0, max_stored = 0, blocks = 0;                  /* (at most 1024 frames x 65536 records, 256 blocks a frame) */
-	uint64_t capacity = 0;                                           /* the sum over the frame pairs of min(stored[n], stored[n + 1]) */
+	uint64_t capacity = 0;
 	float mark_ms = 0;
 	bool timed = false;
-	Carve big;
-	size_t positions_at = 0, forward_at = 0, backward_at = 0;
 
-	bool find(Device &d, const float *thresholds, uint32_t threshold_count, const double *placements, uint32_t placement_count,
-	          uint32_t max_per_frame, size_t extra_bytes)
+	/* lead(carve), tail(carve): the call takes its own tables there */
+	template <class Lead, class Tail> bool prepare(Device &d, const PeakQuery &q, Lead lead, Tail tail)
 	{
-		count = (uint32_t)boxed.size(); links = count - 1u;
-		if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
-		Carve dev;
-		const size_t rows_at = dev.take(sizeof(BfPeaksRow) * count), placements_at = dev.take(sizeof(double) * 12 * count),
-		             results_at = dev.take(sizeof(BfPeaksResult) * count);
-		firsts_at = dev.take(sizeof(uint32_t) * count);
-		const size_t stored_at = dev.take(sizeof(uint32_t) * count), block_firsts_at = dev.take(sizeof(uint32_t) * links);
-		unplaced_at = dev.take(sizeof(uint32_t) * count);
-		const size_t tallies_at = dev.take(sizeof(BfTrackTally) * links), extra_at = dev.take(extra_bytes), pinned_bytes = dev.total,
-		             masks_at = dev.take(sizeof(uint64_t) * table.waves), counts_at = dev.take(sizeof(uint32_t) * table.blocks),
-		             offsets_at = dev.take(sizeof(uint32_t) * table.blocks);
-		tally_bytes = (extra_bytes ? extra_at + extra_bytes : tallies_at + sizeof(BfTrackTally) * links) - unplaced_at;
-		bool ok = ensure_metrics_memory(d, pinned_bytes, dev.total);
-		if (ok && !d.ops.peaks_begin) ok = HIP_OK(hipEventCreate(&d.ops.peaks_begin));
-		if (ok && !d.ops.peaks_end)   ok = HIP_OK(hipEventCreate(&d.ops.peaks_end));
-		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
+		count = (uint32_t)boxed.size(); cap = q.max_per_frame;
+		if (!peaks_rows_of(boxed, q, table)) return false;
+		const uint32_t placed = q.placements ? count : 0u;
+		rows.take(dev, count); placements.take(dev, 12 * (size_t)placed); results.take(dev, count);
+		up_bytes = placements.at + sizeof(double) * 12 * placed;
+		lead(dev);
+		const size_t pinned_bytes = dev.total;
+		masks.take(dev, table.waves); counts.take(dev, table.blocks); offsets.take(dev, table.blocks);
+		tail(dev);
+		if (!ensure_metrics_memory(d, pinned_bytes, dev.total)) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
 		device = (char *)d.ops.metrics_scratch.ptr; pinned = (char *)d.ops.metrics_pinned;
-		device_rows       = (const BfPeaksRow *)(device + rows_at);
-		device_placements = (const double *)(device + placements_at);
-		BfPeaksResult *device_results = (BfPeaksResult *)(device + results_at);
-		device_firsts = (const uint32_t *)(device + firsts_at); device_stored = (const uint32_t *)(device + stored_at);
-		device_block_firsts = (const uint32_t *)(device + block_firsts_at);
-		device_unplaced = (uint32_t *)(device + unplaced_at);
-		device_tallies  = (BfTrackTally *)(device + tallies_at);
-		device_extra    = device + extra_at;
-		device_masks    = (uint64_t *)(device + masks_at);
-		device_counts   = (uint32_t *)(device + counts_at);
-		device_offsets  = (uint32_t *)(device + offsets_at);
-		results = (const BfPeaksResult *)(pinned + results_at);
-		firsts = (uint32_t *)(pinned + firsts_at); stored = (uint32_t *)(pinned + stored_at); block_firsts = (uint32_t *)(pinned + block_firsts_at);
-		unplaced = (const uint32_t *)(pinned + unplaced_at);
-		tallies  = (const BfTrackTally *)(pinned + tallies_at);
-		extra    = pinned + extra_at;
-		std::memcpy(pinned + rows_at, table.rows.data(), sizeof(BfPeaksRow) * count);
-		for (uint32_t n = 0; n < count; n++)
-			std::memcpy(pinned + placements_at + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
-		if (!timed_reduce(d, placements_at + sizeof(double) * 12 * count, results_at, sizeof(BfPeaksResult) * count, nullptr, [&](hipStream_t s) {   /* (its time: read below, with the rest's) */
-			return bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s);
-		})) return false;
+		std::memcpy(rows.in(pinned), table.rows.data(), sizeof(BfPeaksRow) * count);
+		for (uint32_t n = 0; n < placed; n++) std::memcpy(placements.in(pinned) + 12 * (size_t)n, q.placement_of(n), sizeof(double) * 12);
+		return true;
+	}
+	template <class Lead> bool prepare(Device &d, const PeakQuery &q, Lead lead) { return prepare(d, q, lead, [](Carve &) {}); }
 
+	hipError_t mark(Device &d, hipStream_t s) const
+	{
+		return bf_launch_frame_peaks_mark(d.ring.ptr, rows.in(device), count, table.max_blocks, masks.in(device), counts.in(device), offsets.in(device),
+		                                  results.in(device), s);
+	}
+
+	/* the mark pass on its own, for the calls whose buffers are sized by what it finds; its time is read here, with the rest's in device_ms() */
+	bool run(Device &d)
+	{
+		bool ok = d.ops.peaks_begin || HIP_OK(hipEventCreate(&d.ops.peaks_begin));
+		ok = ok && (d.ops.peaks_end || HIP_OK(hipEventCreate(&d.ops.peaks_end)));
+		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+		if (!timed_reduce(d, up_bytes, results.at, sizeof(BfPeaksResult) * count, nullptr, [&](hipStream_t s) { return mark(d, s); })) return false;
+		const BfPeaksResult *found = results.in(pinned);
+		stored.resize(count); firsts.resize(count); block_firsts.resize(count - 1u);
 		for (uint32_t n = 0; n < count; n++) {
-			stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
+			stored[n] = found[n].found < cap ? (uint32_t)found[n].found : cap;
 			firsts[n] = total;
 			total += stored[n];
 			if (stored[n] > max_stored) max_stored = stored[n];
 			if (n) capacity += stored[n - 1] < stored[n] ? stored[n - 1] : stored[n];
-			if (n < links) { block_firsts[n] = blocks; blocks += (stored[n] + 255u) / 256u; }
+			if (n + 1u < count) { block_firsts[n] = blocks; blocks += (stored[n] + 255u) / 256u; }
 		}
-		std::memset(pinned + unplaced_at, 0, tally_bytes);
 		timed = HIP_OK(hipEventElapsedTime(&mark_ms, d.ops.metrics_begin, d.ops.metrics_end));
-		positions_at = big.take(sizeof(double) * 3 * total); forward_at = big.take(sizeof(uint32_t) * total); backward_at = big.take(sizeof(uint32_t) * total);
 		return true;
 	}
 
-	bool ensure(Device &d) const { return d.ops.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak)) && d.ops.tracks_scratch.ensure(big.total); }
-	double   *positions(Device &d) const { return (double *)((char *)d.ops.tracks_scratch.ptr + positions_at); }
-	uint32_t *forward(Device &d) const { return (uint32_t *)((char *)d.ops.tracks_scratch.ptr + forward_at); }
-	uint32_t *backward(Device &d) const { return (uint32_t *)((char *)d.ops.tracks_scratch.ptr + backward_at); }
-
-	/* behind ensure(), total != 0: the tables up, the tallies zeroed, the first event, then emit, place and -- with a frame pair that has
-	 * peaks on both sides: else nothing is there to choose from -- nearest */
-	bool enqueue(Device &d, bool use_offsets, double r2)
-	{
-		hipStream_t s = d.stream;
-		bool ok = HIP_OK(hipMemcpyAsync(device + firsts_at, firsts, unplaced_at - firsts_at, hipMemcpyHostToDevice, s));
-		ok &= HIP_OK(hipMemsetAsync(device_unplaced, 0, tally_bytes, s));
-		ok &= HIP_OK(hipEventRecord(d.ops.peaks_begin, s));
-		if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets,
-		                                                device_firsts, d.ops.peaks_list.ptr, s));
-		if (ok) ok &= HIP_OK(bf_launch_tracks_place(d.ops.peaks_list.ptr, device_placements, device_firsts, device_stored, count, max_stored,
-		                                            use_offsets, positions(d), device_unplaced, s));
-		if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_nearest(positions(d), device_firsts, device_stored, count, max_stored, r2, forward(d), backward(d), s));
-		return ok;
-	}
-
-	/* the second event, the tallies back, the second synchronise -- which runs whatever failed before it */
-	bool collect(Device &d, bool ok)
-	{
-		hipStream_t s = d.stream;
-		ok &= HIP_OK(hipEventRecord(d.ops.peaks_end, s));
-		if (ok) ok &= HIP_OK(hipMemcpyAsync(pinned + unplaced_at, device_unplaced, tally_bytes, hipMemcpyDeviceToHost, s));
-		ok &= HIP_OK(hipStreamSynchronize(s));
-		return ok;
-	}
-
-	/* the call's device time: mark and scan, and -- `rest`: something was enqueued behind them -- the rest */
+	/* the call's device time: mark and scan, and -- `rest`: something was enqueued behind them, between the peaks event pair -- the rest */
 	float device_ms(Device &d, bool rest) const
 	{
 		float rest_ms = 0;
@@ -321,47 +275,173 @@ struct PeakChoices {
 	}
 };
 
+/* What pair_peaks_last_frames, track_peaks_last_frames and draw_tracks_last_frames share behind the mark front: the peaks placed and
+ * offered to one another (frame_peaks.hip: emit; frame_tracks.hip: place, nearest).  find() -- the first synchronise --, then the
+ * caller takes its own tables from `big`, ensure(), enqueue(), its own launches, collect() -- the second.
+ * lead: firsts | stored | block_firsts | unplaced | tallies | extra (the first three go up in one copy, unplaced, tallies and the
+ * caller's `extra` come back in one: each group stays adjacent).  tracks_scratch: positions | forward | backward | the caller's. */
+struct PeakChoices : MarkFront {
+	uint32_t links = 0;
+	Table<uint32_t> up_firsts, up_stored, up_block_firsts, unplaced;
+	Table<BfTrackTally> tallies;
+	Table<char> extra;
+	size_t tally_bytes = 0;                                          /* from unplaced to the end of `extra` */
+	Carve big;
+	Table<double> positions;
+	Table<uint32_t> forward, backward;
+	char *scratch = nullptr;                                         /* tracks_scratch, from ensure() on */
+
+	bool find(Device &d, const PeakQuery &q, size_t extra_bytes)
+	{
+		links = q.count - 1u;
+		if (!prepare(d, q, [&](Carve &c) {
+			up_firsts.take(c, q.count); up_stored.take(c, q.count); up_block_firsts.take(c, links); unplaced.take(c, q.count);
+			tallies.take(c, links); extra.take(c, extra_bytes);
+		}) || !run(d)) return false;
+		tally_bytes = (extra_bytes ? extra.at + extra_bytes : tallies.at + sizeof(BfTrackTally) * links) - unplaced.at;
+		std::memcpy(up_firsts.in(pinned), firsts.data(), sizeof(uint32_t) * count);
+		std::memcpy(up_stored.in(pinned), stored.data(), sizeof(uint32_t) * count);
+		std::memcpy(up_block_firsts.in(pinned), block_firsts.data(), sizeof(uint32_t) * links);
+		std::memset(unplaced.in(pinned), 0, tally_bytes);
+		positions.take(big, 3 * (size_t)total); forward.take(big, total); backward.take(big, total);
+		return true;
+	}
+
+	bool ensure(Device &d)
+	{
+		const bool ok = d.ops.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak)) && d.ops.tracks_scratch.ensure(big.total);
+		scratch = (char *)d.ops.tracks_scratch.ptr;
+		return ok;
+	}
+
+	/* behind ensure(), total != 0: the tables up, the tallies zeroed, the first event, then emit, place and -- with a frame pair that has
+	 * peaks on both sides: else nothing is there to choose from -- nearest */
+	bool enqueue(Device &d, const PeakQuery &q)
+	{
+		hipStream_t s = d.stream;
+		const double reach = (double)q.max_distance;
+		bool ok = HIP_OK(hipMemcpyAsync(up_firsts.in(device), up_firsts.in(pinned), unplaced.at - up_firsts.at, hipMemcpyHostToDevice, s));
+		ok &= HIP_OK(hipMemsetAsync(unplaced.in(device), 0, tally_bytes, s));
+		ok &= HIP_OK(hipEventRecord(d.ops.peaks_begin, s));
+		if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, rows.in(device), count, table.max_blocks, masks.in(device), counts.in(device),
+		                                                offsets.in(device), up_firsts.in(device), d.ops.peaks_list.ptr, s));
+		if (ok) ok &= HIP_OK(bf_launch_tracks_place(d.ops.peaks_list.ptr, placements.in(device), up_firsts.in(device), up_stored.in(device), count,
+		                                            max_stored, q.use_offsets != 0, positions.in(scratch), unplaced.in(device), s));
+		if (ok && capacity) ok &= HIP_OK(bf_launch_tracks_nearest(positions.in(scratch), up_firsts.in(device), up_stored.in(device), count, max_stored,
+		                                                          reach * reach, forward.in(scratch), backward.in(scratch), s));
+		return ok;
+	}
+
+	/* the second event, the tallies back, the second synchronise -- which runs whatever failed before it */
+	bool collect(Device &d, bool ok)
+	{
+		hipStream_t s = d.stream;
+		ok &= HIP_OK(hipEventRecord(d.ops.peaks_end, s));
+		if (ok) ok &= HIP_OK(hipMemcpyAsync(unplaced.in(pinned), unplaced.in(device), tally_bytes, hipMemcpyDeviceToHost, s));
+		ok &= HIP_OK(hipStreamSynchronize(s));
+		return ok;
+	}
+};
+
+/* what a track or a draw call deposited, summed over its frames, and the maps its deposit bits name credited with it */
+struct ChainDeposits {
+	uint64_t points_deposited = 0, points_outside = 0, links = 0, links_deposited = 0, links_outside = 0;
+	void credit(Device &d, uint32_t deposit, uint32_t block) const
+	{
+		if (deposit & BF_CHAIN_POINTS) d.ops.map.credit(block, 0, points_deposited, points_outside);
+		if (deposit & BF_CHAIN_LINKS) d.ops.tracks.credit(block, links, links_deposited, links_outside);
+	}
+};
+
 /* What track_peaks_last_frames and draw_tracks_last_frames share behind PeakChoices::find(), total != 0: the chain's tables carved from
  * tracks_scratch behind the choices -- next | links, twice | lengths | tails | track_of | first_of | words | offsets | tracks | points,
  * the two record lists sized by ALL stored records, an upper bound, or left out -- and the chain's launches behind enqueue(). */
 struct ChainTables {
-	size_t next_at = 0, links_at = 0, lengths_at = 0, tails_at = 0, track_of_at = 0, first_of_at = 0, words_at = 0, offsets_at = 0, tracks_at = 0,
-	       points_at = 0;
+	Table<uint32_t> next, lengths, tails, track_of, first_of, words, offsets;
+	Table<char> links, tracks, points;
 	bool with_tracks = false, with_points = false;
-	void carve(PeakChoices &c, bool tracks, bool points)
+	void carve(PeakChoices &c, bool keep_tracks, bool keep_points)
 	{
-		const size_t each = sizeof(uint32_t) * c.total, chain_blocks = ((size_t)c.total + 255u) / 256u;
-		next_at = c.big.take(each); links_at = c.big.take(4 * each); lengths_at = c.big.take(each); tails_at = c.big.take(each);
-		track_of_at = c.big.take(each); first_of_at = c.big.take(each); words_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks);
-		offsets_at = c.big.take(2 * sizeof(uint32_t) * chain_blocks);
-		tracks_at = c.big.take(tracks ? sizeof(BeamformerHipPeakTrack) * (size_t)c.total : 0);
-		points_at = c.big.take(points ? sizeof(BeamformerHipTrackPoint) * (size_t)c.total : 0);
-		with_tracks = tracks; with_points = points;
+		const size_t chain_blocks = ((size_t)c.total + 255u) / 256u;
+		next.take(c.big, c.total); links.take(c.big, 4 * sizeof(uint32_t) * c.total); lengths.take(c.big, c.total); tails.take(c.big, c.total);
+		track_of.take(c.big, c.total); first_of.take(c.big, c.total); words.take(c.big, 2 * chain_blocks); offsets.take(c.big, 2 * chain_blocks);
+		tracks.take(c.big, keep_tracks ? sizeof(BeamformerHipPeakTrack) * (size_t)c.total : 0);
+		points.take(c.big, keep_points ? sizeof(BeamformerHipTrackPoint) * (size_t)c.total : 0);
+		with_tracks = keep_tracks; with_points = keep_points;
 	}
-	template <class T = char> T *at(Device &d, size_t where) const { return (T *)((char *)d.ops.tracks_scratch.ptr + where); }
-	void *tracks(Device &d) const { return with_tracks ? at(d, tracks_at) : nullptr; }
-	void *points(Device &d) const { return with_points ? at(d, points_at) : nullptr; }
-	/* a: the maps' grids are filled in here, from the maps a->deposit names (the caller has checked that they exist) */
+	void *tracks_in(char *scratch) const { return with_tracks ? tracks.in(scratch) : nullptr; }
+	void *points_in(char *scratch) const { return with_points ? points.in(scratch) : nullptr; }
+	/* a: the maps' grids are filled in here, from the maps a.deposit names (the caller has checked that they exist) */
 	hipError_t launch(Device &d, PeakChoices &c, BfChainArgs a, BfChainTally *tallies, hipStream_t s) const
 	{
-		const FrameOps::LocalisationMap &point_map = d.ops.map;
-		const FrameOps::TrackMap &link_map = d.ops.tracks;
+		const FrameOps::DepositMap &point_map = d.ops.map, &link_map = d.ops.tracks;
 		const bool to_points = a.deposit & BF_CHAIN_POINTS, to_links = a.deposit & BF_CHAIN_LINKS;
 		for (int k = 0; k < 3; k++) { a.point_map[k] = to_points ? point_map.points[k] : 0u; a.track_map[k] = to_links ? link_map.points[k] : 0u; }
-		return bf_launch_tracks_chain(c.positions(d), c.device_firsts, c.device_stored, c.count, c.max_stored, c.total,
-		                              c.capacity ? c.forward(d) : nullptr, c.capacity ? c.backward(d) : nullptr, at<uint32_t>(d, next_at),
-		                              at(d, links_at), at<uint32_t>(d, lengths_at), at<uint32_t>(d, tails_at), at<uint32_t>(d, track_of_at),
-		                              at<uint32_t>(d, first_of_at), at<uint32_t>(d, words_at), at<uint32_t>(d, offsets_at), &a,
-		                              to_points ? (uint32_t *)point_map.buffer.ptr : nullptr, to_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
-		                              to_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr, tracks(d), points(d), tallies, s);
+		return bf_launch_tracks_chain(c.positions.in(c.scratch), c.up_firsts.in(c.device), c.up_stored.in(c.device), c.count, c.max_stored, c.total,
+		                              c.capacity ? c.forward.in(c.scratch) : nullptr, c.capacity ? c.backward.in(c.scratch) : nullptr, next.in(c.scratch),
+		                              links.in(c.scratch), lengths.in(c.scratch), tails.in(c.scratch), track_of.in(c.scratch), first_of.in(c.scratch),
+		                              words.in(c.scratch), offsets.in(c.scratch), &a, to_points ? (uint32_t *)point_map.buffer.ptr : nullptr,
+		                              to_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
+		                              to_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr, tracks_in(c.scratch), points_in(c.scratch),
+		                              tallies, s);
 	}
 };
 
-/* the deposit bits of the two calls against the maps that exist */
+/* the deposit bits of the track and the draw call against the maps that exist */
 bool maps_for(Device &d, uint32_t deposit)
 {
-	if ((deposit & BF_CHAIN_POINTS) && (!d.ops.map.buffer.ptr || !d.ops.map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	if ((deposit & BF_CHAIN_LINKS) && (!d.ops.tracks.buffer.ptr || !d.ops.tracks.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (((deposit & BF_CHAIN_POINTS) && !d.ops.map.exists()) || ((deposit & BF_CHAIN_LINKS) && !d.ops.tracks.exists()))
+		return set_error(BeamformerLibErrorKind_InvalidAccess);
+	return true;
+}
+
+/* the blocks of a strided reduce over a boxed frame (frame_metrics.hip, frame_quantiles.hip) and what a thread's stride of all their
+ * threads is in the box's coordinates */
+template <class Row> void stride_into(Row &r, const BoxedFrame &b)
+{
+	r.blocks = bf_metrics_blocks(b.volume);
+	const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
+	r.step[0] = (uint32_t)(stride % r.count[0]);
+	r.step[1] = (uint32_t)(stride / r.count[0] % r.count[1]);
+	r.step[2] = (uint32_t)(stride / plane);
+}
+
+/* the Gram kernels' arguments for `count` frames of box `b` (ensemble.hip, ensemble_blocks.hip) */
+BfGramArgs gram_args_of(const BoxedFrame &b, uint32_t count)
+{
+	BfGramArgs a{};
+	a.frames = count; a.cplx = b.cplx;
+	for (int k = 0; k < 3; k++) { a.points[k] = b.record->points[k]; a.first[k] = b.first[k]; a.count[k] = b.count[k]; }
+	a.volume = (uint32_t)b.volume;
+	a.words = (uint32_t)((b.volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
+	a.chunk_words = bf_gram_chunk_words(a.volume, count);
+	a.chunks = (a.words + a.chunk_words - 1u) / a.chunk_words;
+	a.tiles = bf_gram_tiles(count); a.tile_pairs = bf_gram_tile_pairs(count);
+	return a;
+}
+
+/* ... and the ABI record of one Gram matrix: the frames, the box, and the two counts its result {voxels, non_finite, gram} begins with */
+void ensemble_info_of(BeamformerHipEnsembleInfo &info, const BfGramArgs &a, const FrameRecord &oldest, const char *result)
+{
+	std::memset(&info, 0, sizeof(info));
+	info.count = a.frames; info.data_kind = (uint32_t)oldest.data_kind;
+	for (int k = 0; k < 3; k++) { info.points[k] = a.points[k]; info.region_first[k] = a.first[k]; info.region_count[k] = a.count[k]; }
+	info.first_frame_id = oldest.id;
+	std::memcpy(&info.voxels, result, 8); std::memcpy(&info.non_finite, result + 8, 8);
+}
+
+/* The same `count` newest frames judged against each of `boxes` regions (regions null: one box, the frame whole), as the calls that
+ * take a list of boxes need them: `frames` are the records, boxed by the first region, and row(r, box) hears of every box -- its oldest
+ * frame stands for all: they are of one grid.  False, with the error set: what newest_ensemble_frames refuses, or a box of 2^32 voxels. */
+template <class Each> bool frames_once_a_box(uint32_t count, const BeamformerHipFrameRegion *regions, uint32_t boxes, std::vector<BoxedFrame> &frames, Each row)
+{
+	std::vector<BoxedFrame> boxed;
+	for (uint32_t r = 0; r < boxes; r++) {
+		if (!newest_ensemble_frames(count, regions ? regions + r : nullptr, boxed)) return false;
+		if (boxed[0].volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);      /* the kernels count a box's voxels in 32 bits */
+		if (r == 0) frames = boxed;
+		row(r, boxed[0]);
+	}
 	return true;
 }
 
@@ -380,12 +460,8 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 	for (uint32_t n = 0; n < count; n++) {
 		BfMetricsRow &r = rows[n];
 		box_into(r, boxed[n]);
-		r.blocks = bf_metrics_blocks(boxed[n].volume);
+		stride_into(r, boxed[n]);
 		r.partial_first = partials;
-		const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
-		r.step[0] = (uint32_t)(stride % r.count[0]);
-		r.step[1] = (uint32_t)(stride / r.count[0] % r.count[1]);
-		r.step[2] = (uint32_t)(stride / plane);
 		partials += r.blocks;
 		if (r.blocks > max_blocks) max_blocks = r.blocks;
 	}
@@ -424,76 +500,41 @@ bool score_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, B
 /* beamformer_hip_find_peaks_last_frames: the local maxima of the `count` newest frames, found where they lie (frame_peaks.hip).  The
  * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Two synchronises:
  * the list buffer is sized by what the scan found. */
-bool find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                            uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count,
-                            float *device_ms)
+bool find_peaks_last_frames(const PeakQuery &q, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks, uint32_t *peak_count, float *device_ms)
 {
 	static_assert(sizeof(BeamformerHipFramePeak) == 32 && sizeof(BeamformerHipFramePeaks) == 80, "records without padding");
-	std::vector<BoxedFrame> boxed;
-	if (!newest_boxed_frames(count, region, boxed)) return false;
+	MarkFront f;
+	if (!newest_boxed_frames(q.count, q.region, f.boxed)) return false;
 	Device &d = ctx().devices[0];
+	Table<uint32_t> up_firsts;                       /* lead: firsts */
+	if (!f.prepare(d, q, [&](Carve &c) { up_firsts.take(c, q.count); }) || !f.run(d)) return false;
 
-	PeaksRows table;
-	if (!peaks_rows_of(boxed, thresholds, threshold_count, max_per_frame, table)) return false;
-
-	/* device: rows | results | firsts | masks | counts | offsets; pinned: rows | results | firsts */
-	Carve dev;
-	const size_t rows_at = dev.take(sizeof(BfPeaksRow) * count), results_at = dev.take(sizeof(BfPeaksResult) * count),
-	             firsts_at = dev.take(sizeof(uint32_t) * count), pinned_bytes = dev.total, masks_at = dev.take(sizeof(uint64_t) * table.waves),
-	             counts_at = dev.take(sizeof(uint32_t) * table.blocks), offsets_at = dev.take(sizeof(uint32_t) * table.blocks);
-	bool ok = ensure_metrics_memory(d, pinned_bytes, dev.total);
-	if (ok && !d.ops.peaks_begin) ok = HIP_OK(hipEventCreate(&d.ops.peaks_begin));
-	if (ok && !d.ops.peaks_end)   ok = HIP_OK(hipEventCreate(&d.ops.peaks_end));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
-	const BfPeaksRow *device_rows    = (const BfPeaksRow *)(device + rows_at);
-	BfPeaksResult    *device_results = (BfPeaksResult *)(device + results_at);
-	uint32_t         *device_firsts  = (uint32_t *)(device + firsts_at);
-	uint64_t         *device_masks   = (uint64_t *)(device + masks_at);
-	uint32_t         *device_counts  = (uint32_t *)(device + counts_at);
-	uint32_t         *device_offsets = (uint32_t *)(device + offsets_at);
-	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + results_at);
-	uint32_t            *firsts  = (uint32_t *)(pinned + firsts_at);
-	std::memcpy(pinned + rows_at, table.rows.data(), sizeof(BfPeaksRow) * count);
-	if (!timed_reduce(d, sizeof(BfPeaksRow) * count, results_at, sizeof(BfPeaksResult) * count, nullptr, [&](hipStream_t s) {   /* (its time: read below, with the emit pass's) */
-		return bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s);
-	})) return false;
-
-	uint32_t total = 0;                  /* (at most 1024 frames x 65536 records) */
-	std::vector<uint32_t> stored(count);
-	for (uint32_t n = 0; n < count; n++) {
-		stored[n] = results[n].found < max_per_frame ? (uint32_t)results[n].found : max_per_frame;
-		firsts[n] = total;
-		total += stored[n];
-	}
-	float ms = 0, emit_ms = 0;
-	const bool timed = HIP_OK(hipEventElapsedTime(&ms, d.ops.metrics_begin, d.ops.metrics_end));
-	if (total) {
+	if (f.total) {
 		hipStream_t s = d.stream;
-		ok = d.ops.peaks_list.ensure((size_t)total * sizeof(BeamformerHipFramePeak));
+		std::memcpy(up_firsts.in(f.pinned), f.firsts.data(), sizeof(uint32_t) * q.count);
+		bool ok = d.ops.peaks_list.ensure((size_t)f.total * sizeof(BeamformerHipFramePeak));
 		if (ok) {
-			ok &= HIP_OK(hipMemcpyAsync(device_firsts, firsts, sizeof(uint32_t) * count, hipMemcpyHostToDevice, s));
+			ok &= HIP_OK(hipMemcpyAsync(up_firsts.in(f.device), up_firsts.in(f.pinned), sizeof(uint32_t) * q.count, hipMemcpyHostToDevice, s));
 			ok &= HIP_OK(hipEventRecord(d.ops.peaks_begin, s));
-			if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets,
-			                                                device_firsts, d.ops.peaks_list.ptr, s));
+			if (ok) ok &= HIP_OK(bf_launch_frame_peaks_emit(d.ring.ptr, f.rows.in(f.device), q.count, f.table.max_blocks, f.masks.in(f.device),
+			                                                f.counts.in(f.device), f.offsets.in(f.device), up_firsts.in(f.device), d.ops.peaks_list.ptr, s));
 			ok &= HIP_OK(hipEventRecord(d.ops.peaks_end, s));
-			if (ok) ok &= HIP_OK(hipMemcpyAsync(peaks, d.ops.peaks_list.ptr, (size_t)total * sizeof(BeamformerHipFramePeak), hipMemcpyDeviceToHost, s));
+			if (ok) ok &= HIP_OK(hipMemcpyAsync(peaks, d.ops.peaks_list.ptr, (size_t)f.total * sizeof(BeamformerHipFramePeak), hipMemcpyDeviceToHost, s));
 			ok &= HIP_OK(hipStreamSynchronize(s));
 		}
 		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-		if (!HIP_OK(hipEventElapsedTime(&emit_ms, d.ops.peaks_begin, d.ops.peaks_end))) emit_ms = 0;
 	}
-	if (device_ms) *device_ms = timed ? ms + emit_ms : 0.0f;
+	if (device_ms) *device_ms = f.device_ms(d, f.total != 0);
 
-	for (uint32_t n = 0; n < count; n++) {
+	const BfPeaksResult *results = f.results.in(f.pinned);
+	for (uint32_t n = 0; n < q.count; n++) {
 		BeamformerHipFramePeaks &m = frames[n];
-		describe_frame(m, boxed[n]);
-		m.threshold = thresholds[threshold_count == 1 ? 0 : n];
-		m.first = firsts[n]; m.stored = stored[n];
+		describe_frame(m, f.boxed[n]);
+		m.threshold = q.threshold_of(n);
+		m.first = f.firsts[n]; m.stored = f.stored[n];
 		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
 	}
-	*peak_count = total;
+	*peak_count = f.total;
 	return true;
 }
 
@@ -515,11 +556,7 @@ bool quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *regio
 		if (boxed[n].volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);     /* the kernels count a box's voxels in 32 bits */
 		BfQuantilesRow &r = rows[n];
 		box_into(r, boxed[n]);
-		r.blocks = bf_metrics_blocks(boxed[n].volume);
-		const uint64_t stride = (uint64_t)r.blocks * 256u, plane = (uint64_t)r.count[0] * r.count[1];
-		r.step[0] = (uint32_t)(stride % r.count[0]);
-		r.step[1] = (uint32_t)(stride / r.count[0] % r.count[1]);
-		r.step[2] = (uint32_t)(stride / plane);
+		stride_into(r, boxed[n]);
 		if (r.blocks > max_blocks) max_blocks = r.blocks;
 	}
 
@@ -569,13 +606,12 @@ bool quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *regio
 	return true;
 }
 
-/* beamformer_hip_localisation_map_reset: the one map of the one device, (re)allocated and zeroed on the current stream; points null:
- * released.  The extents arrive checked (lib_api.cpp). */
-bool localisation_map_reset(const uint32_t points[3])
+/* beamformer_hip_localisation_map_reset, beamformer_hip_track_map_reset: one of the two maps of the one device, (re)allocated and zeroed
+ * on the current stream; points null: released.  The extents arrive checked (lib_api.cpp). */
+bool deposit_map_reset(FrameOps::DepositMap &map, const uint32_t points[3])
 {
 	Context &c = ctx();
 	Device &d = c.devices[0];
-	FrameOps::LocalisationMap &map = d.ops.map;
 	if (!points) {
 		if (c.device_ready && map.buffer.ptr) {
 			bool ok = HIP_OK(hipSetDevice(d.device));
@@ -587,7 +623,9 @@ bool localisation_map_reset(const uint32_t points[3])
 		return true;
 	}
 	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	const size_t bytes = sizeof(uint32_t) * (size_t)points[0] * points[1] * points[2];
+	FrameOps::DepositMap shape(map.sum_components);
+	for (int k = 0; k < 3; k++) shape.points[k] = points[k];
+	const size_t bytes = shape.bytes();
 	bool ok = HIP_OK(hipSetDevice(d.device));
 	/* (a buffer that has to grow is freed first: what is enqueued on it must have run) */
 	if (ok && map.buffer.ptr && map.buffer.size < bytes) ok = HIP_OK(hipStreamSynchronize(d.stream));
@@ -603,115 +641,78 @@ bool localisation_map_reset(const uint32_t points[3])
  * (frame_peaks.hip: the mark pass and the scan of find_peaks_last_frames, then the deposit and the scan again over its words).  The
  * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  One synchronise:
  * no buffer is sized by what was found. */
-bool accumulate_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                                  const double *placements, uint32_t placement_count, uint32_t use_offsets, BeamformerHipMapDeposits *frames,
-                                  float *device_ms)
+bool accumulate_peaks_last_frames(const PeakQuery &q, BeamformerHipMapDeposits *frames, float *device_ms)
 {
 	static_assert(sizeof(BeamformerHipMapDeposits) == 96 && sizeof(BeamformerHipMapInfo) == 32, "records without padding");
 	static_assert(BF_MAP_MAX_VOXELS == BEAMFORMER_HIP_MAX_MAP_VOXELS, "one limit");
-	std::vector<BoxedFrame> boxed;
-	if (!newest_boxed_frames(count, region, boxed)) return false;
+	MarkFront f;
+	if (!newest_boxed_frames(q.count, q.region, f.boxed)) return false;
 	Device &d = ctx().devices[0];
-	if (!d.ops.map.buffer.ptr || !d.ops.map.points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	PeaksRows table;
-	if (!peaks_rows_of(boxed, thresholds, threshold_count, 0, table)) return false;      /* (the cap is the emit pass's: not read) */
-
-	/* device: rows | placements | results | tallies | masks | counts | offsets | words; pinned: the first four
-	 * (rows and placements go up in one copy, results and tallies come back in one: each pair stays adjacent) */
-	Carve dev;
-	const size_t rows_at = dev.take(sizeof(BfPeaksRow) * count), placements_at = dev.take(sizeof(double) * 12 * count),
-	             results_at = dev.take(sizeof(BfPeaksResult) * count), tallies_at = dev.take(sizeof(BfPeaksResult) * count), pinned_bytes = dev.total,
-	             masks_at = dev.take(sizeof(uint64_t) * table.waves), counts_at = dev.take(sizeof(uint32_t) * table.blocks),
-	             offsets_at = dev.take(sizeof(uint32_t) * table.blocks), words_at = dev.take(sizeof(uint32_t) * table.blocks);
-	if (!ensure_metrics_memory(d, pinned_bytes, dev.total)) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-
-	char *device = (char *)d.ops.metrics_scratch.ptr, *pinned = (char *)d.ops.metrics_pinned;
-	const BfPeaksRow *device_rows       = (const BfPeaksRow *)(device + rows_at);
-	const double     *device_placements = (const double *)(device + placements_at);
-	BfPeaksResult    *device_results    = (BfPeaksResult *)(device + results_at);
-	BfPeaksResult    *device_tallies    = (BfPeaksResult *)(device + tallies_at);
-	uint64_t         *device_masks      = (uint64_t *)(device + masks_at);
-	uint32_t         *device_counts     = (uint32_t *)(device + counts_at);
-	uint32_t         *device_offsets    = (uint32_t *)(device + offsets_at);
-	uint32_t         *device_words      = (uint32_t *)(device + words_at);
-	const BfPeaksResult *results = (const BfPeaksResult *)(pinned + results_at), *tallies = (const BfPeaksResult *)(pinned + tallies_at);
-	std::memcpy(pinned + rows_at, table.rows.data(), sizeof(BfPeaksRow) * count);
-	for (uint32_t n = 0; n < count; n++)
-		std::memcpy(pinned + placements_at + sizeof(double) * 12 * n, placements + (placement_count == 1 ? 0 : 12 * (size_t)n), sizeof(double) * 12);
+	FrameOps::DepositMap &map = d.ops.map;
+	if (!map.exists()) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	/* lead: the deposit's tallies, which come back with the results in one copy; tail: its words */
+	Table<BfPeaksResult> tallies;
+	Table<uint32_t> words;
+	if (!f.prepare(d, q, [&](Carve &c) { tallies.take(c, q.count); }, [&](Carve &c) { words.take(c, f.table.blocks); })) return false;
 	BfMapArgs a{};
-	for (int k = 0; k < 3; k++) a.points[k] = d.ops.map.points[k];
-	a.use_offsets = use_offsets != 0;
-	if (!timed_reduce(d, placements_at + sizeof(double) * 12 * count, results_at, tallies_at - results_at + sizeof(BfPeaksResult) * count, device_ms,
-	                  [&](hipStream_t s) {
-		const hipError_t e = bf_launch_frame_peaks_mark(d.ring.ptr, device_rows, count, table.max_blocks, device_masks, device_counts, device_offsets, device_results, s);
+	for (int k = 0; k < 3; k++) a.points[k] = map.points[k];
+	a.use_offsets = q.use_offsets != 0;
+	if (!timed_reduce(d, f.up_bytes, f.results.at, tallies.at - f.results.at + sizeof(BfPeaksResult) * q.count, device_ms, [&](hipStream_t s) {
+		const hipError_t e = f.mark(d, s);
 		if (e != hipSuccess) return e;
-		return bf_launch_localisation_deposit(d.ring.ptr, device_rows, device_placements, count, table.max_blocks, device_masks, device_counts,
-		                                      device_offsets, &a, (uint32_t *)d.ops.map.buffer.ptr, device_words, device_tallies, s);
+		return bf_launch_localisation_deposit(d.ring.ptr, f.rows.in(f.device), f.placements.in(f.device), q.count, f.table.max_blocks, f.masks.in(f.device),
+		                                      f.counts.in(f.device), f.offsets.in(f.device), &a, (uint32_t *)map.buffer.ptr, words.in(f.device),
+		                                      tallies.in(f.device), s);
 	})) return false;
 
-	for (uint32_t n = 0; n < count; n++) {
-		d.ops.map.deposited += tallies[n].found; d.ops.map.outside += tallies[n].above_threshold;
+	const BfPeaksResult *results = f.results.in(f.pinned), *deposits = tallies.in(f.pinned);
+	uint64_t deposited = 0, outside = 0;
+	for (uint32_t n = 0; n < q.count; n++) {
+		deposited += deposits[n].found; outside += deposits[n].above_threshold;
 		if (!frames) continue;
 		BeamformerHipMapDeposits &m = frames[n];
-		describe_frame(m, boxed[n]);
-		m.threshold = thresholds[threshold_count == 1 ? 0 : n];
+		describe_frame(m, f.boxed[n]);
+		m.threshold = q.threshold_of(n);
 		m.found = results[n].found; m.above_threshold = results[n].above_threshold;
-		m.deposited = tallies[n].found; m.outside = tallies[n].above_threshold;
+		m.deposited = deposits[n].found; m.outside = deposits[n].above_threshold;
 	}
-	d.ops.map.calls++;
-	d.ops.map.block = boxed[count - 1].record->block;
+	map.credit(f.boxed[q.count - 1].record->block, 0, deposited, outside);
 	return true;
 }
 
-/* beamformer_hip_localisation_map_copy: the counts as they are, behind everything enqueued on the current stream */
-bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info)
+/* the counts of a map that exists, `voxels` of them, -- and `sums`, where it has any -- as they are, behind everything enqueued on the
+ * current stream.  False, with the error set: no such map (InvalidAccess), less room than voxels (ExportSpaceOverflow) */
+static bool deposit_map_copy(const FrameOps::DepositMap &map, uint32_t *counts, int64_t *sums, uint64_t out_count)
 {
 	Context &c = ctx();
 	Device &d = c.devices[0];
-	if (!c.device_ready || c.device_count != 1 || !d.ops.map.buffer.ptr || !d.ops.map.points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	const uint64_t voxels = (uint64_t)d.ops.map.points[0] * d.ops.map.points[1] * d.ops.map.points[2];
+	if (!c.device_ready || c.device_count != 1 || !map.exists()) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	const uint64_t voxels = map.voxels();
 	if (out_count < voxels) return set_error(BeamformerLibErrorKind_ExportSpaceOverflow);
 	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && HIP_OK(hipMemcpyAsync(out, d.ops.map.buffer.ptr, sizeof(uint32_t) * voxels, hipMemcpyDeviceToHost, d.stream));
+	ok = ok && HIP_OK(hipMemcpyAsync(counts, map.buffer.ptr, sizeof(uint32_t) * voxels, hipMemcpyDeviceToHost, d.stream));
+	if (sums)
+		ok = ok && HIP_OK(hipMemcpyAsync(sums, (const char *)map.buffer.ptr + map.sums_at(), map.sum_components * sizeof(int64_t) * voxels,
+		                                 hipMemcpyDeviceToHost, d.stream));
 	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
 	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (info) {
-		std::memset(info, 0, sizeof(*info));
-		for (int k = 0; k < 3; k++) info->points[k] = d.ops.map.points[k];
-		info->calls = d.ops.map.calls; info->deposited = d.ops.map.deposited; info->outside = d.ops.map.outside;
-	}
 	return true;
 }
 
-/* beamformer_hip_track_map_reset: the one track map of the one device -- counts, and the three displacement sums behind them --,
- * (re)allocated and zeroed on the current stream; points null: released.  The extents arrive checked (lib_api.cpp). */
-bool track_map_reset(const uint32_t points[3])
+/* ... and what both ABI info records hold of it: the grid and the totals (pairs: the track map's alone) */
+template <class Info> static void deposit_map_info(const FrameOps::DepositMap &map, Info *info)
 {
-	Context &c = ctx();
-	Device &d = c.devices[0];
-	FrameOps::TrackMap &map = d.ops.tracks;
-	if (!points) {
-		if (c.device_ready && map.buffer.ptr) {
-			bool ok = HIP_OK(hipSetDevice(d.device));
-			ok = ok && HIP_OK(hipStreamSynchronize(d.stream));          /* a deposit or a conversion may still be reading it */
-			if (!ok) (void)hipGetLastError();
-			map.buffer.release();
-		}
-		map.forget();
-		return true;
-	}
-	if (!c.device_ready || c.device_count != 1) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	FrameOps::TrackMap shape;
-	for (int k = 0; k < 3; k++) shape.points[k] = points[k];
-	const size_t bytes = shape.sums_at() + 3 * sizeof(int64_t) * (size_t)shape.voxels();
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	/* (a buffer that has to grow is freed first: what is enqueued on it must have run) */
-	if (ok && map.buffer.ptr && map.buffer.size < bytes) ok = HIP_OK(hipStreamSynchronize(d.stream));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	map.forget();                       /* (also when the buffer cannot be had: no map then) */
-	if (!map.buffer.ensure(bytes)) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_RFDataSizeOverflow); }
-	for (int k = 0; k < 3; k++) map.points[k] = points[k];
-	if (!HIP_OK(hipMemsetAsync(map.buffer.ptr, 0, bytes, d.stream))) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
+	std::memset(info, 0, sizeof(*info));
+	for (int k = 0; k < 3; k++) info->points[k] = map.points[k];
+	info->calls = map.calls; info->deposited = map.deposited; info->outside = map.outside;
+}
+
+/* beamformer_hip_localisation_map_copy */
+bool localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info)
+{
+	const FrameOps::DepositMap &map = ctx().devices[0].ops.map;
+	if (!deposit_map_copy(map, out, nullptr, out_count)) return false;
+	if (info) deposit_map_info(map, info);
 	return true;
 }
 
@@ -719,45 +720,44 @@ bool track_map_reset(const uint32_t points[3])
  * the mark pass, the scan and the emit pass of find_peaks_last_frames; frame_tracks.hip: place, nearest, match, scan, emit).  The
  * arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Three synchronises
  * at the most: the buffers are sized by what the scan found, and the copy of the records by the pairs that were made. */
-bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                            const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
-                            uint32_t max_per_frame, uint32_t deposit, BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs,
-                            uint32_t *pair_count, float *device_ms)
+bool pair_peaks_last_frames(const PeakQuery &q, uint32_t deposit, BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs, uint32_t *pair_count,
+                            float *device_ms)
 {
 	static_assert(sizeof(BeamformerHipPeakPair) == 48 && sizeof(BeamformerHipPeakPairs) == 72 && sizeof(BeamformerHipTrackMapInfo) == 40, "records without padding");
 	static_assert(BF_TRACK_MAX_VOXELS == BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS && BF_TRACK_MAX_PEAKS == BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME &&
 	              BF_TRACK_COMPONENTS == BEAMFORMER_HIP_TRACK_MAP_COMPONENTS, "one limit");
 	PeakChoices c;
-	if (!newest_boxed_frames(count, region, c.boxed)) return false;
+	if (!newest_boxed_frames(q.count, q.region, c.boxed)) return false;
 	Device &d = ctx().devices[0];
-	FrameOps::TrackMap &map = d.ops.tracks;
-	if (deposit && (!map.buffer.ptr || !map.points[0])) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, 0)) return false;
-	const uint32_t links = c.links;
-	const double reach = (double)max_distance, r2 = reach * reach;
+	FrameOps::DepositMap &map = d.ops.tracks;
+	if (deposit && !map.exists()) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!c.find(d, q, 0)) return false;
+	const BfTrackTally *tallies = c.tallies.in(c.pinned);
 	uint64_t total_pairs = 0;
 	if (c.total) {
 		/* tracks_scratch, behind the choices: masks | words | offsets | pairs */
-		const size_t pair_masks_at = c.big.take(sizeof(uint64_t) * 4 * c.blocks), words_at = c.big.take(sizeof(uint32_t) * c.blocks),
-		             pair_offsets_at = c.big.take(sizeof(uint32_t) * c.blocks),
-		             pairs_at = c.big.take(pairs ? sizeof(BeamformerHipPeakPair) * (size_t)c.capacity : 0);
+		Table<uint64_t> pair_masks;
+		Table<uint32_t> words, pair_offsets;
+		Table<BeamformerHipPeakPair> made;
+		pair_masks.take(c.big, 4 * (size_t)c.blocks); words.take(c.big, c.blocks); pair_offsets.take(c.big, c.blocks);
+		made.take(c.big, pairs ? (size_t)c.capacity : 0);
 		hipStream_t s = d.stream;
 		bool ok = c.ensure(d);
 		if (ok) {
-			char *scratch = (char *)d.ops.tracks_scratch.ptr;
-			void *device_pairs = pairs && c.capacity ? scratch + pairs_at : nullptr;
+			void *device_pairs = pairs && c.capacity ? made.in(c.scratch) : nullptr;
 			BfTrackArgs a{};
 			for (int k = 0; k < 3; k++) a.points[k] = deposit ? map.points[k] : 0u;
 			a.deposit = deposit != 0;
-			ok = c.enqueue(d, use_offsets != 0, r2);
+			ok = c.enqueue(d, q);
 			/* (no frame pair with peaks on both sides: every tally stays 0) */
-			if (ok && c.capacity) ok &= HIP_OK(bf_launch_tracks_pair(c.positions(d), c.device_firsts, c.device_stored, c.device_block_firsts, count, c.max_stored,
-			                                                         c.blocks, c.forward(d), c.backward(d), (uint64_t *)(scratch + pair_masks_at),
-			                                                         (uint32_t *)(scratch + words_at), (uint32_t *)(scratch + pair_offsets_at), &a,
-			                                                         (uint32_t *)map.buffer.ptr, deposit ? (char *)map.buffer.ptr + map.sums_at() : nullptr,
-			                                                         device_pairs, c.device_tallies, s));
+			if (ok && c.capacity) ok &= HIP_OK(bf_launch_tracks_pair(c.positions.in(c.scratch), c.up_firsts.in(c.device), c.up_stored.in(c.device),
+			                                                         c.up_block_firsts.in(c.device), q.count, c.max_stored, c.blocks, c.forward.in(c.scratch),
+			                                                         c.backward.in(c.scratch), pair_masks.in(c.scratch), words.in(c.scratch),
+			                                                         pair_offsets.in(c.scratch), &a, (uint32_t *)map.buffer.ptr,
+			                                                         deposit ? (char *)map.buffer.ptr + map.sums_at() : nullptr, device_pairs,
+			                                                         c.tallies.in(c.device), s));
 			ok = c.collect(d, ok);
-			for (uint32_t n = 0; n < links && ok; n++) total_pairs += c.tallies[n].pairs;
+			for (uint32_t n = 0; n < c.links && ok; n++) total_pairs += tallies[n].pairs;
 			if (ok && pairs && total_pairs) {
 				ok = total_pairs <= c.capacity;                           /* (what the kernels promise: the copy below relies on it) */
 				ok = ok && HIP_OK(hipMemcpyAsync(pairs, device_pairs, (size_t)total_pairs * sizeof(BeamformerHipPeakPair), hipMemcpyDeviceToHost, s));
@@ -768,23 +768,26 @@ bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 	}
 	if (device_ms) *device_ms = c.device_ms(d, c.total != 0);
 
+	const BfPeaksResult *results = c.results.in(c.pinned);
+	const uint32_t *unplaced = c.unplaced.in(c.pinned);
 	uint32_t first = 0;
-	for (uint32_t n = 0; n < links; n++) {
+	uint64_t deposited = 0, outside = 0;
+	for (uint32_t n = 0; n < c.links; n++) {
 		BeamformerHipPeakPairs &m = rows[n];
-		const BfTrackTally &t = c.tallies[n];
+		const BfTrackTally &t = tallies[n];
 		std::memset(&m, 0, sizeof(m));
 		for (uint32_t k = 0; k < 2; k++) {
 			m.frame_id[k] = c.boxed[n + k].record->id;
-			m.threshold[k] = thresholds[threshold_count == 1 ? 0 : n + k];
-			m.peaks[k] = c.stored[n + k]; m.found[k] = c.results[n + k].found;
-			m.unplaced[k] = c.unplaced[n + k];
-			m.unpaired[k] = c.stored[n + k] - c.unplaced[n + k] - t.pairs;
+			m.threshold[k] = q.threshold_of(n + k);
+			m.peaks[k] = c.stored[n + k]; m.found[k] = results[n + k].found;
+			m.unplaced[k] = unplaced[n + k];
+			m.unpaired[k] = c.stored[n + k] - unplaced[n + k] - t.pairs;
 		}
 		m.first = first; m.pairs = t.pairs; m.deposited = t.deposited; m.outside = t.outside;
 		first += t.pairs;
-		if (deposit) { map.pairs += t.pairs; map.deposited += t.deposited; map.outside += t.outside; }
+		deposited += t.deposited; outside += t.outside;
 	}
-	if (deposit) { map.calls++; map.block = c.boxed[count - 1].record->block; }
+	if (deposit) map.credit(c.boxed[q.count - 1].record->block, first, deposited, outside);
 	*pair_count = first;
 	return true;
 }
@@ -795,24 +798,18 @@ bool pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
  * (lib_api.cpp); everything else that can refuse is decided before anything is enqueued.  Three synchronises at the most, for the pair
  * call's reasons: the buffers are sized by what the scan found -- the two record lists by ALL stored records, an upper bound --, and
  * the two downloads by the tallies. */
-bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
-                             uint32_t max_per_frame, uint32_t min_length, uint32_t deposit, BeamformerHipTrackedFrame *rows,
-                             BeamformerHipPeakTrack *tracks, BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count,
-                             float *device_ms)
+bool track_peaks_last_frames(const PeakQuery &q, uint32_t min_length, uint32_t deposit, BeamformerHipTrackedFrame *rows, BeamformerHipPeakTrack *tracks,
+                             BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count, float *device_ms)
 {
 	static_assert(sizeof(BeamformerHipPeakTrack) == 48 && sizeof(BeamformerHipTrackPoint) == 40 && sizeof(BeamformerHipTrackedFrame) == 56, "records without padding");
 	static_assert(BF_CHAIN_POINTS == BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS && BF_CHAIN_LINKS == BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS, "one pair of bits");
+	const uint32_t count = q.count;
 	PeakChoices c;
-	if (!newest_boxed_frames(count, region, c.boxed)) return false;
+	if (!newest_boxed_frames(count, q.region, c.boxed)) return false;
 	Device &d = ctx().devices[0];
-	FrameOps::LocalisationMap &point_map = d.ops.map;
-	FrameOps::TrackMap &link_map = d.ops.tracks;
-	const bool with_points = deposit & BF_CHAIN_POINTS, with_links = deposit & BF_CHAIN_LINKS;
 	if (!maps_for(d, deposit)) return false;
-	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, sizeof(BfChainTally) * count)) return false;
-	const BfChainTally *tallies = (const BfChainTally *)c.extra;
-	const double reach = (double)max_distance, r2 = reach * reach;
+	if (!c.find(d, q, sizeof(BfChainTally) * count)) return false;               /* extra: the chain's tallies */
+	const BfChainTally *tallies = (const BfChainTally *)c.extra.in(c.pinned);
 	uint64_t total_tracks = 0, total_points = 0;
 	if (c.total) {
 		ChainTables t;
@@ -820,40 +817,41 @@ bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *reg
 		hipStream_t s = d.stream;
 		bool ok = c.ensure(d);
 		if (ok) {
-			void *device_tracks = t.tracks(d), *device_points = t.points(d);
 			BfChainArgs a{};
 			a.deposit = deposit; a.min_length = min_length;
-			ok = c.enqueue(d, use_offsets != 0, r2);
-			if (ok) ok &= HIP_OK(t.launch(d, c, a, (BfChainTally *)c.device_extra, s));
+			ok = c.enqueue(d, q);
+			if (ok) ok &= HIP_OK(t.launch(d, c, a, (BfChainTally *)c.extra.in(c.device), s));
 			ok = c.collect(d, ok);
 			for (uint32_t n = 0; n < count && ok; n++) { total_tracks += tallies[n].kept_heads; total_points += tallies[n].kept_points; }
 			ok = ok && total_tracks <= c.total && total_points <= c.total;      /* (what the kernels promise: the copies below rely on it) */
 			const bool tracks_back = tracks && total_tracks, points_back = points && total_points;
 			if (ok && tracks_back)
-				ok = HIP_OK(hipMemcpyAsync(tracks, device_tracks, (size_t)total_tracks * sizeof(BeamformerHipPeakTrack), hipMemcpyDeviceToHost, s));
+				ok = HIP_OK(hipMemcpyAsync(tracks, t.tracks_in(c.scratch), (size_t)total_tracks * sizeof(BeamformerHipPeakTrack), hipMemcpyDeviceToHost, s));
 			if (ok && points_back)
-				ok = HIP_OK(hipMemcpyAsync(points, device_points, (size_t)total_points * sizeof(BeamformerHipTrackPoint), hipMemcpyDeviceToHost, s));
+				ok = HIP_OK(hipMemcpyAsync(points, t.points_in(c.scratch), (size_t)total_points * sizeof(BeamformerHipTrackPoint), hipMemcpyDeviceToHost, s));
 			if (tracks_back || points_back) ok &= HIP_OK(hipStreamSynchronize(s));
 		}
 		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
 	}
 	if (device_ms) *device_ms = c.device_ms(d, c.total != 0);
 
+	const BfPeaksResult *results = c.results.in(c.pinned);
+	const uint32_t *unplaced = c.unplaced.in(c.pinned);
+	ChainDeposits sum;
 	for (uint32_t n = 0; n < count; n++) {
 		BeamformerHipTrackedFrame &m = rows[n];
 		const BfChainTally &t = tallies[n];
 		std::memset(&m, 0, sizeof(m));
-		m.frame_id = c.boxed[n].record->id; m.threshold = thresholds[threshold_count == 1 ? 0 : n];
-		m.peaks = c.stored[n]; m.unplaced = c.unplaced[n];
+		m.frame_id = c.boxed[n].record->id; m.threshold = q.threshold_of(n);
+		m.peaks = c.stored[n]; m.unplaced = unplaced[n];
 		m.heads = t.heads; m.kept_heads = t.kept_heads; m.kept_points = t.kept_points; m.kept_links = t.kept_links;
 		m.points_deposited = t.points_deposited; m.points_outside = t.points_outside;
 		m.links_deposited = t.links_deposited; m.links_outside = t.links_outside;
-		m.found = c.results[n].found;
-		if (with_points) { point_map.deposited += t.points_deposited; point_map.outside += t.points_outside; }
-		if (with_links) { link_map.pairs += t.kept_links; link_map.deposited += t.links_deposited; link_map.outside += t.links_outside; }
+		m.found = results[n].found;
+		sum.points_deposited += t.points_deposited; sum.points_outside += t.points_outside;
+		sum.links += t.kept_links; sum.links_deposited += t.links_deposited; sum.links_outside += t.links_outside;
 	}
-	if (with_points) { point_map.calls++; point_map.block = c.boxed[count - 1].record->block; }
-	if (with_links) { link_map.calls++; link_map.block = c.boxed[count - 1].record->block; }
+	sum.credit(d, deposit, c.boxed[count - 1].record->block);
 	*track_count = (uint32_t)total_tracks; *point_count = (uint32_t)total_points;
 	return true;
 }
@@ -863,91 +861,78 @@ bool track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *reg
  * lists stay on the device, where the draw pass reads them; nothing is sized by what was kept, so there are TWO synchronises: the
  * counts and the tallies.  The arguments arrive checked (lib_api.cpp); everything else that can refuse is decided before anything is
  * enqueued. */
-bool draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
-                             const double *placements, uint32_t placement_count, uint32_t use_offsets, float max_distance,
-                             uint32_t max_per_frame, uint32_t min_length, uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows,
-                             float *device_ms)
+bool draw_tracks_last_frames(const PeakQuery &q, uint32_t min_length, uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows, float *device_ms)
 {
 	static_assert(sizeof(BeamformerHipDrawnFrame) == 64, "a record without padding");
 	static_assert(BF_DRAW_MAX_SMOOTH == BEAMFORMER_HIP_MAX_TRACK_SMOOTH && BF_DRAW_MAX_SAMPLES == BEAMFORMER_HIP_MAX_LINK_SAMPLES, "one limit");
+	const uint32_t count = q.count;
 	PeakChoices c;
-	if (!newest_boxed_frames(count, region, c.boxed)) return false;
+	if (!newest_boxed_frames(count, q.region, c.boxed)) return false;
 	Device &d = ctx().devices[0];
-	FrameOps::LocalisationMap &point_map = d.ops.map;
-	FrameOps::TrackMap &link_map = d.ops.tracks;
+	const FrameOps::DepositMap &point_map = d.ops.map, &link_map = d.ops.tracks;
 	const bool with_points = deposit & BF_CHAIN_POINTS, with_links = deposit & BF_CHAIN_LINKS;
 	if (!maps_for(d, deposit)) return false;
 	/* extra: the chain's tallies, then the draw pass's */
-	if (!c.find(d, thresholds, threshold_count, placements, placement_count, max_per_frame, (sizeof(BfChainTally) + sizeof(BfDrawTally)) * count)) return false;
-	const BfChainTally *chained = (const BfChainTally *)c.extra;
+	if (!c.find(d, q, (sizeof(BfChainTally) + sizeof(BfDrawTally)) * count)) return false;
+	const BfChainTally *chained = (const BfChainTally *)c.extra.in(c.pinned);
 	const BfDrawTally *drawn = (const BfDrawTally *)(chained + count);
-	const double reach = (double)max_distance, r2 = reach * reach;
 	if (c.total) {
 		ChainTables t;
 		t.carve(c, true, true);
-		const size_t smoothed_at = c.big.take(smooth ? sizeof(double) * 3 * (size_t)c.total : 0);
+		Table<double> smoothed;
+		smoothed.take(c.big, smooth ? 3 * (size_t)c.total : 0);
 		hipStream_t s = d.stream;
 		bool ok = c.ensure(d);
 		if (ok) {
+			BfChainTally *device_chained = (BfChainTally *)c.extra.in(c.device);
 			BfChainArgs a{};
 			a.min_length = min_length;                                      /* (deposit 0: the finish pass lists, the draw pass deposits) */
 			BfDrawArgs w{};
 			for (int k = 0; k < 3; k++) { w.point_map[k] = with_points ? point_map.points[k] : 0u; w.track_map[k] = with_links ? link_map.points[k] : 0u; }
 			w.deposit = deposit; w.smooth = smooth;
-			ok = c.enqueue(d, use_offsets != 0, r2);
-			if (ok) ok &= HIP_OK(t.launch(d, c, a, (BfChainTally *)c.device_extra, s));
-			if (ok) ok &= HIP_OK(bf_launch_tracks_draw(c.device_firsts, c.device_stored, count, c.max_stored, c.total, t.at(d, t.links_at),
-			                                           t.at<uint32_t>(d, t.lengths_at), t.at<uint32_t>(d, t.track_of_at), t.at<uint32_t>(d, t.first_of_at),
-			                                           t.at<uint32_t>(d, t.words_at), t.at<uint32_t>(d, t.offsets_at), t.tracks(d), t.points(d),
-			                                           smooth ? t.at<double>(d, smoothed_at) : nullptr, &w,
+			ok = c.enqueue(d, q);
+			if (ok) ok &= HIP_OK(t.launch(d, c, a, device_chained, s));
+			if (ok) ok &= HIP_OK(bf_launch_tracks_draw(c.up_firsts.in(c.device), c.up_stored.in(c.device), count, c.max_stored, c.total, t.links.in(c.scratch),
+			                                           t.lengths.in(c.scratch), t.track_of.in(c.scratch), t.first_of.in(c.scratch), t.words.in(c.scratch),
+			                                           t.offsets.in(c.scratch), t.tracks_in(c.scratch), t.points_in(c.scratch),
+			                                           smooth ? smoothed.in(c.scratch) : nullptr, &w,
 			                                           with_points ? (uint32_t *)point_map.buffer.ptr : nullptr,
 			                                           with_links ? (uint32_t *)link_map.buffer.ptr : nullptr,
 			                                           with_links ? (char *)link_map.buffer.ptr + link_map.sums_at() : nullptr,
-			                                           (BfDrawTally *)((BfChainTally *)c.device_extra + count), s));
+			                                           (BfDrawTally *)(device_chained + count), s));
 			ok = c.collect(d, ok);
 		}
 		if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
 	}
 	if (device_ms) *device_ms = c.device_ms(d, c.total != 0);
 
+	const BfPeaksResult *results = c.results.in(c.pinned);
+	const uint32_t *unplaced = c.unplaced.in(c.pinned);
+	ChainDeposits sum;
 	for (uint32_t n = 0; n < count; n++) {
 		BeamformerHipDrawnFrame &m = rows[n];
 		const BfDrawTally &t = drawn[n];
 		std::memset(&m, 0, sizeof(m));
-		m.frame_id = c.boxed[n].record->id; m.threshold = thresholds[threshold_count == 1 ? 0 : n];
-		m.peaks = c.stored[n]; m.unplaced = c.unplaced[n];
+		m.frame_id = c.boxed[n].record->id; m.threshold = q.threshold_of(n);
+		m.peaks = c.stored[n]; m.unplaced = unplaced[n];
 		m.kept_points = chained[n].kept_points; m.kept_links = chained[n].kept_links;
 		m.lone = t.lone; m.links_skipped = t.links_skipped; m.samples = t.samples; m.repeats = t.repeats;
 		m.points_deposited = t.points_deposited; m.points_outside = t.points_outside;
 		m.links_deposited = t.links_deposited; m.links_outside = t.links_outside;
-		m.found = c.results[n].found;
-		if (with_points) { point_map.deposited += t.points_deposited; point_map.outside += t.points_outside; }
-		if (with_links) { link_map.pairs += t.samples - t.repeats; link_map.deposited += t.links_deposited; link_map.outside += t.links_outside; }
+		m.found = results[n].found;
+		sum.points_deposited += t.points_deposited; sum.points_outside += t.points_outside;
+		sum.links += t.samples - t.repeats; sum.links_deposited += t.links_deposited; sum.links_outside += t.links_outside;
 	}
-	if (with_points) { point_map.calls++; point_map.block = c.boxed[count - 1].record->block; }
-	if (with_links) { link_map.calls++; link_map.block = c.boxed[count - 1].record->block; }
+	sum.credit(d, deposit, c.boxed[count - 1].record->block);
 	return true;
 }
 
-/* beamformer_hip_track_map_copy: the counts and the sums as they are, behind everything enqueued on the current stream */
+/* beamformer_hip_track_map_copy */
 bool track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info)
 {
-	Context &c = ctx();
-	Device &d = c.devices[0];
-	const FrameOps::TrackMap &map = d.ops.tracks;
-	if (!c.device_ready || c.device_count != 1 || !map.buffer.ptr || !map.points[0]) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	const uint64_t voxels = map.voxels();
-	if (out_count < voxels) return set_error(BeamformerLibErrorKind_ExportSpaceOverflow);
-	bool ok = HIP_OK(hipSetDevice(d.device));
-	ok = ok && HIP_OK(hipMemcpyAsync(counts, map.buffer.ptr, sizeof(uint32_t) * voxels, hipMemcpyDeviceToHost, d.stream));
-	ok = ok && HIP_OK(hipMemcpyAsync(sums, (const char *)map.buffer.ptr + map.sums_at(), 3 * sizeof(int64_t) * voxels, hipMemcpyDeviceToHost, d.stream));
-	ok = ok && HIP_OK(hipStreamSynchronize(d.stream));
-	if (!ok) { (void)hipGetLastError(); return set_error(BeamformerLibErrorKind_InvalidAccess); }
-	if (info) {
-		std::memset(info, 0, sizeof(*info));
-		for (int k = 0; k < 3; k++) info->points[k] = map.points[k];
-		info->calls = map.calls; info->pairs = map.pairs; info->deposited = map.deposited; info->outside = map.outside;
-	}
+	const FrameOps::DepositMap &map = ctx().devices[0].ops.tracks;
+	if (!deposit_map_copy(map, counts, sums, out_count)) return false;
+	if (info) { deposit_map_info(map, info); info->pairs = map.pairs; }
 	return true;
 }
 
@@ -963,14 +948,7 @@ bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, do
 	const BoxedFrame &b0 = boxed[0];
 	if (b0.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);     /* the kernels count a box's voxels in 32 bits */
 
-	BfGramArgs a{};
-	a.frames = count; a.cplx = b0.cplx;
-	for (int k = 0; k < 3; k++) { a.points[k] = b0.record->points[k]; a.first[k] = b0.first[k]; a.count[k] = b0.count[k]; }
-	a.volume = (uint32_t)b0.volume;
-	a.words = (uint32_t)((b0.volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
-	a.chunk_words = bf_gram_chunk_words(a.volume, count);
-	a.chunks = (a.words + a.chunk_words - 1u) / a.chunk_words;
-	a.tiles = bf_gram_tiles(count); a.tile_pairs = bf_gram_tile_pairs(count);
+	const BfGramArgs a = gram_args_of(b0, count);
 
 	/* device: offsets | result {voxels, non_finite, gram} | mask | partials; pinned: offsets | result */
 	const size_t gram_bytes = sizeof(double) * 2 * count * count;
@@ -988,13 +966,7 @@ bool gram_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, do
 		                      device + result_at, s);
 	})) return false;
 	std::memcpy(gram, result + 16, gram_bytes);
-	if (info) {
-		std::memset(info, 0, sizeof(*info));
-		info->count = count; info->data_kind = (uint32_t)b0.record->data_kind;
-		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->region_first[k] = a.first[k]; info->region_count[k] = a.count[k]; }
-		info->first_frame_id = b0.record->id;
-		std::memcpy(&info->voxels, result, 8); std::memcpy(&info->non_finite, result + 8, 8);
-	}
+	if (info) ensemble_info_of(*info, a, *b0.record, result);
 	return true;
 }
 
@@ -1014,25 +986,13 @@ bool gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 	const uint64_t tile_bytes = sizeof(double) * 2 * BF_GRAM_TILE * BF_GRAM_TILE;
 	const size_t gram_bytes = sizeof(double) * 2 * count * count, result_bytes = 16 + gram_bytes;
 
-	/* the frames once a box: the same K records each time, and each box judged against every one of them */
-	std::vector<BoxedFrame> boxed, frames;
+	std::vector<BoxedFrame> frames;
 	std::vector<BfBlocksBox> rows(region_count);
 	std::vector<Batch> batches;
-	for (uint32_t r = 0; r < region_count; r++) {
-		if (!newest_ensemble_frames(count, regions + r, boxed)) return false;
-		const BoxedFrame &b = boxed[0];
-		if (b.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);      /* the kernels count a box's voxels in 32 bits */
-		if (r == 0) frames = boxed;
+	if (!frames_once_a_box(count, regions, region_count, frames, [&](uint32_t r, const BoxedFrame &b) {
 		BfBlocksBox &row = rows[r];
 		row = BfBlocksBox{};
-		BfGramArgs &a = row.a;
-		a.frames = count; a.cplx = b.cplx;
-		for (int k = 0; k < 3; k++) { a.points[k] = b.record->points[k]; a.first[k] = b.first[k]; a.count[k] = b.count[k]; }
-		a.volume = (uint32_t)b.volume;
-		a.words = (uint32_t)((b.volume + BF_GRAM_WORD - 1u) / BF_GRAM_WORD);
-		a.chunk_words = bf_gram_chunk_words(a.volume, count);
-		a.chunks = (a.words + a.chunk_words - 1u) / a.chunk_words;
-		a.tiles = bf_gram_tiles(count); a.tile_pairs = bf_gram_tile_pairs(count);
+		const BfGramArgs &a = row.a = gram_args_of(b, count);
 		const uint64_t mask_blocks = (a.words + 3u) / 4u, partial_tiles = (uint64_t)a.chunks * a.tile_pairs;
 		if (batches.empty() || (batches.back().partial_tiles + partial_tiles) * tile_bytes > g_gram_boxes_budget ||
 		    batches.back().mask_blocks + mask_blocks > 0x7FFFFFFFull || batches.back().partial_blocks + partial_tiles > 0x7FFFFFFFull)
@@ -1043,7 +1003,7 @@ bool gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 		row.result_first = (uint64_t)r * result_bytes;
 		batch.boxes++; batch.mask_blocks += (uint32_t)mask_blocks; batch.partial_blocks += (uint32_t)partial_tiles;
 		batch.mask_words += a.words; batch.partial_tiles += partial_tiles;
-	}
+	})) return false;
 	Device &d = ctx().devices[0];
 	uint64_t mask_words = 0, partial_tiles = 0;
 	for (const Batch &batch : batches) {
@@ -1072,18 +1032,10 @@ bool gram_boxes_last_frames(uint32_t count, const BeamformerHipFrameRegion *regi
 		}
 		return hipSuccess;
 	})) return false;
-	const BoxedFrame &b0 = frames[0];
 	for (uint32_t r = 0; r < region_count; r++) {
 		const char *result = pinned + results_at + (size_t)r * result_bytes;
 		std::memcpy((char *)grams + (size_t)r * gram_bytes, result + 16, gram_bytes);
-		if (!infos) continue;
-		BeamformerHipEnsembleInfo *info = infos + r;
-		const BfGramArgs &a = rows[r].a;
-		std::memset(info, 0, sizeof(*info));
-		info->count = count; info->data_kind = (uint32_t)b0.record->data_kind;
-		for (int k = 0; k < 3; k++) { info->points[k] = a.points[k]; info->region_first[k] = a.first[k]; info->region_count[k] = a.count[k]; }
-		info->first_frame_id = b0.record->id;
-		std::memcpy(&info->voxels, result, 8); std::memcpy(&info->non_finite, result + 8, 8);
+		if (infos) ensemble_info_of(infos[r], rows[r].a, *frames[0].record, result);
 	}
 	return true;
 }
@@ -1106,15 +1058,10 @@ bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerH
 	a.groups = bf_correlate_groups(a.shifts);
 	a.batches = (a.shifts + BF_CORRELATE_THREADS - 1u) / BF_CORRELATE_THREADS;
 
-	/* the frames once a box: the same K records each time, and the box of each region judged against every one of them */
-	std::vector<BoxedFrame> boxed, frames;
+	std::vector<BoxedFrame> frames;
 	std::vector<BfCorrelateRow> rows(boxes);
 	uint64_t partials = 0;
-	for (uint32_t r = 0; r < boxes; r++) {
-		if (!newest_ensemble_frames(count, regions ? regions + r : nullptr, boxed)) return false;
-		const BoxedFrame &b = boxed[0];
-		if (b.volume > 0xFFFFFFFFull) return set_error(BeamformerLibErrorKind_InvalidAccess);      /* the kernels count a box's voxels in 32 bits */
-		if (r == 0) frames = boxed;
+	if (!frames_once_a_box(count, regions, boxes, frames, [&](uint32_t r, const BoxedFrame &b) {
 		BfCorrelateRow &row = rows[r];
 		row = BfCorrelateRow{};
 		for (int k = 0; k < 3; k++) { row.first[k] = b.first[k]; row.count[k] = b.count[k]; }
@@ -1131,7 +1078,7 @@ bool correlate_last_frames(uint32_t count, uint32_t reference, const BeamformerH
 		row.partial_first = partials;
 		partials += (uint64_t)row.chunks * count * a.shifts;
 		if (row.chunks > a.max_chunks) a.max_chunks = row.chunks;
-	}
+	})) return false;
 	Device &d = ctx().devices[0];
 	const BoxedFrame &b0 = frames[0];
 	a.cplx = b0.cplx;
@@ -1510,40 +1457,43 @@ bool warp_last_frames(uint32_t count, const float *field, const uint32_t nodes[3
 		});
 }
 
-/* beamformer_hip_queue_localisation_map: the map's counts times `scale`, queued as ONE Float32 frame of the map's grid (frame_peaks.hip:
- * the conversion) -- a run of one frame that has no source in the ring: the map is the library's own buffer, so no placement can lie on
- * what the launch reads.  The record carries the block of the newest frame of the last accumulate call. */
-bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+/* What beamformer_hip_queue_localisation_map and beamformer_hip_queue_track_map share: something made of a map that has been deposited
+ * into, queued as ONE Float32 frame of the map's grid -- a run of one frame that has no source in the ring: the map is the library's own
+ * buffer, so no placement can lie on what the launch reads.  The record carries the block of the newest frame of the last call that
+ * deposited.  convert(run, out): the one launch. */
+template <class Convert>
+static bool queue_deposit_map(const FrameOps::DepositMap &map, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms, Convert convert)
 {
 	Context &c = ctx();
-	Device &d = c.devices[0];
-	if (!c.device_ready || c.device_count != 1 || !d.ops.map.buffer.ptr || !d.ops.map.points[0] || d.ops.map.calls == 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
-	FrameRecord shape;
-	for (int k = 0; k < 3; k++) shape.points[k] = d.ops.map.points[k];
-	shape.block = d.ops.map.block;
-	RunTable t; t.shape = &shape;
-	const uint32_t *map = (const uint32_t *)d.ops.map.buffer.ptr;
-	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
-		[=](const QueuedRun &r) { return bf_launch_localisation_convert(map, (float *)((char *)r.ring + r.out_offset), r.elements, scale, r.s); });
-}
-
-/* beamformer_hip_queue_track_map: one component of the track map -- a mean displacement, the count, the squared mean speed --, queued
- * as ONE Float32 frame of the map's grid (frame_tracks.hip: the conversion), through the skeleton of queue_localisation_map: a run of one
- * frame without a source in the ring.  The record carries the block of the newest frame of the last pair call that deposited. */
-bool queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
-{
-	Context &c = ctx();
-	Device &d = c.devices[0];
-	const FrameOps::TrackMap &map = d.ops.tracks;
-	if (!c.device_ready || c.device_count != 1 || !map.buffer.ptr || !map.points[0] || map.calls == 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
+	if (!c.device_ready || c.device_count != 1 || !map.exists() || map.calls == 0) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	FrameRecord shape;
 	for (int k = 0; k < 3; k++) shape.points[k] = map.points[k];
 	shape.block = map.block;
 	RunTable t; t.shape = &shape;
+	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
+		[=](const QueuedRun &r) { return convert(r, (float *)((char *)r.ring + r.out_offset)); });
+}
+
+/* beamformer_hip_queue_localisation_map: the map's counts times `scale` (frame_peaks.hip: the conversion) */
+bool queue_localisation_map(float scale, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+{
+	const FrameOps::DepositMap &map = ctx().devices[0].ops.map;
+	const uint32_t *counts = (const uint32_t *)map.buffer.ptr;
+	return queue_deposit_map(map, image_plane_tag, frame_id, device_ms, [=](const QueuedRun &r, float *out) {
+		return bf_launch_localisation_convert(counts, out, r.elements, scale, r.s);
+	});
+}
+
+/* beamformer_hip_queue_track_map: one component of the track map -- a mean displacement, the count, the squared mean speed
+ * (frame_tracks.hip: the conversion) */
+bool queue_track_map(uint32_t component, float scale, uint32_t min_pairs, uint32_t image_plane_tag, uint32_t *frame_id, float *device_ms)
+{
+	const FrameOps::DepositMap &map = ctx().devices[0].ops.tracks;
 	const uint32_t *counts = (const uint32_t *)map.buffer.ptr;
 	const void *sums = (const char *)map.buffer.ptr + map.sums_at();
-	return queue_frames_of_newest(0, t, 1, image_plane_tag, frame_id, device_ms, nothing_to_prepare,
-		[=](const QueuedRun &r) { return bf_launch_track_convert(counts, sums, (float *)((char *)r.ring + r.out_offset), r.elements, component, min_pairs, scale, r.s); });
+	return queue_deposit_map(map, image_plane_tag, frame_id, device_ms, [=](const QueuedRun &r, float *out) {
+		return bf_launch_track_convert(counts, sums, out, r.elements, component, min_pairs, scale, r.s);
+	});
 }
 
 } // namespace bf

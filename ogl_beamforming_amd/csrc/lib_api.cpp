@@ -958,17 +958,32 @@ uint32_t beamformer_hip_score_last_frames(uint32_t count, const BeamformerHipFra
 	return score_last_frames(count, region, out, device_ms);
 }
 
+/* The arguments the five peak calls share, refused in the one order all five keep -- with several faults at once the order decides which
+ * error kind the caller sees: the ranges (BufferOverflow), then the pointers, the counts and the values (InvalidAccess).  capped,
+ * placed: the call has a max_per_frame, placements; linking: it links frames -- two at the least, within a max_distance; min_length:
+ * null where the call has none; outputs: the call's own output pointers are all there.  A call's further checks come behind these. */
+static bool valid_peak_query(const PeakQuery &q, bool capped, bool placed, bool linking, const uint32_t *min_length, bool outputs)
+{
+	if (!check(q.count >= (linking ? 2u : 1u) && q.count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (capped && !check(q.max_per_frame >= 1 && q.max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (min_length && !check(*min_length >= 1 && *min_length <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return false;
+	if (!check(outputs && q.thresholds != nullptr && (!placed || q.placements != nullptr), BeamformerLibErrorKind_InvalidAccess)) return false;
+	if (!check(q.threshold_count == 1 || q.threshold_count == q.count, BeamformerLibErrorKind_InvalidAccess)) return false;
+	if (placed && !check(q.placement_count == 1 || q.placement_count == q.count, BeamformerLibErrorKind_InvalidAccess)) return false;
+	for (uint32_t k = 0; k < q.threshold_count; k++)
+		if (!check(std::isfinite(q.thresholds[k]) && q.thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return false;
+	for (size_t k = 0; placed && k < (size_t)12 * q.placement_count; k++)
+		if (!check(std::isfinite(q.placements[k]), BeamformerLibErrorKind_InvalidAccess)) return false;
+	return !linking || check(q.max_distance >= 0.0f && q.max_distance <= BEAMFORMER_HIP_MAX_PAIR_DISTANCE, BeamformerLibErrorKind_InvalidAccess);   /* (a NaN fails both) */
+}
+
 uint32_t beamformer_hip_find_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds, uint32_t threshold_count,
                                                uint32_t max_per_frame, BeamformerHipFramePeaks *frames, BeamformerHipFramePeak *peaks,
                                                uint32_t *peak_count, float *device_ms)
 {
-	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(thresholds != nullptr && frames != nullptr && peaks != nullptr && peak_count != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (uint32_t k = 0; k < threshold_count; k++)
-		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	return find_peaks_last_frames(count, region, thresholds, threshold_count, max_per_frame, frames, peaks, peak_count, device_ms);
+	const PeakQuery q{count, region, thresholds, threshold_count, nullptr, 0, 0, 0.0f, max_per_frame};
+	if (!valid_peak_query(q, true, false, false, nullptr, frames != nullptr && peaks != nullptr && peak_count != nullptr)) return 0;
+	return find_peaks_last_frames(q, frames, peaks, peak_count, device_ms);
 }
 
 uint32_t beamformer_hip_quantiles_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const double *fractions, uint32_t fraction_count,
@@ -1022,14 +1037,20 @@ uint32_t beamformer_hip_peaks_to_views(const float source_voxel_transform[16], c
 	return 1;
 }
 
+/* a map's extents against its voxel limit, the device started, the map (re)allocated; points null: released, with no device needed */
+static uint32_t reset_deposit_map(FrameOps::DepositMap &map, const uint32_t points[3], uint64_t max_voxels)
+{
+	if (!points) return deposit_map_reset(map, nullptr);
+	if (!check(points[0] && points[1] && points[2], BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (!check((uint64_t)points[0] * points[1] <= max_voxels && (uint64_t)points[0] * points[1] * points[2] <= max_voxels,
+	           BeamformerLibErrorKind_BufferOverflow)) return 0;
+	if (!ensure_device()) return 0;
+	return deposit_map_reset(map, points);
+}
+
 uint32_t beamformer_hip_localisation_map_reset(const uint32_t points[3])
 {
-	if (!points) return localisation_map_reset(nullptr);
-	if (!check(points[0] && points[1] && points[2], BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check((uint64_t)points[0] * points[1] <= BEAMFORMER_HIP_MAX_MAP_VOXELS &&
-	           (uint64_t)points[0] * points[1] * points[2] <= BEAMFORMER_HIP_MAX_MAP_VOXELS, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!ensure_device()) return 0;
-	return localisation_map_reset(points);
+	return reset_deposit_map(ctx().devices[0].ops.map, points, BEAMFORMER_HIP_MAX_MAP_VOXELS);
 }
 
 /* (serves frames that exist, as the calls above: it starts no device) */
@@ -1037,15 +1058,9 @@ uint32_t beamformer_hip_accumulate_peaks_last_frames(uint32_t count, const Beamf
                                                      uint32_t threshold_count, const double *placements, uint32_t placement_count,
                                                      uint32_t use_offsets, BeamformerHipMapDeposits *frames, float *device_ms)
 {
-	if (!check(count >= 1 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(thresholds != nullptr && placements != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (uint32_t k = 0; k < threshold_count; k++)
-		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
-		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
-	return accumulate_peaks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, frames, device_ms);
+	const PeakQuery q{count, region, thresholds, threshold_count, placements, placement_count, use_offsets, 0.0f, 0};
+	if (!valid_peak_query(q, false, true, false, nullptr, true)) return 0;
+	return accumulate_peaks_last_frames(q, frames, device_ms);
 }
 
 uint32_t beamformer_hip_localisation_map_copy(uint32_t *out, uint64_t out_count, BeamformerHipMapInfo *info)
@@ -1062,79 +1077,47 @@ uint32_t beamformer_hip_queue_localisation_map(float scale, uint32_t image_plane
 
 uint32_t beamformer_hip_track_map_reset(const uint32_t points[3])
 {
-	if (!points) return track_map_reset(nullptr);
-	if (!check(points[0] && points[1] && points[2], BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check((uint64_t)points[0] * points[1] <= BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS &&
-	           (uint64_t)points[0] * points[1] * points[2] <= BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!ensure_device()) return 0;
-	return track_map_reset(points);
+	return reset_deposit_map(ctx().devices[0].ops.tracks, points, BEAMFORMER_HIP_MAX_TRACK_MAP_VOXELS);
 }
 
-/* (serves frames that exist, as the calls above: it starts no device) */
+/* (the three below serve frames that exist, as the calls above: they start no device) */
 uint32_t beamformer_hip_pair_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds,
                                                uint32_t threshold_count, const double *placements, uint32_t placement_count,
                                                uint32_t use_offsets, float max_distance, uint32_t max_per_frame, uint32_t deposit,
                                                BeamformerHipPeakPairs *rows, BeamformerHipPeakPair *pairs, uint32_t *pair_count, float *device_ms)
 {
-	if (!check(count >= 2 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(rows != nullptr && pair_count != nullptr && thresholds != nullptr && placements != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (uint32_t k = 0; k < threshold_count; k++)
-		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
-		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(max_distance >= 0.0f && max_distance <= BEAMFORMER_HIP_MAX_PAIR_DISTANCE, BeamformerLibErrorKind_InvalidAccess)) return 0;   /* (a NaN fails both) */
-	return pair_peaks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame,
-	                              deposit, rows, pairs, pair_count, device_ms);
+	const PeakQuery q{count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame};
+	if (!valid_peak_query(q, true, true, true, nullptr, rows != nullptr && pair_count != nullptr)) return 0;
+	return pair_peaks_last_frames(q, deposit, rows, pairs, pair_count, device_ms);
 }
 
-/* (the pair call's checks, in its order and with its error kinds, then the call's own) */
+static bool valid_track_deposit(uint32_t deposit)
+{
+	return check((deposit & ~(BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS | BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS)) == 0, BeamformerLibErrorKind_InvalidAccess);
+}
+
 uint32_t beamformer_hip_track_peaks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds,
                                                 uint32_t threshold_count, const double *placements, uint32_t placement_count,
                                                 uint32_t use_offsets, float max_distance, uint32_t max_per_frame, uint32_t min_length,
                                                 uint32_t deposit, BeamformerHipTrackedFrame *rows, BeamformerHipPeakTrack *tracks,
                                                 BeamformerHipTrackPoint *points, uint32_t *track_count, uint32_t *point_count, float *device_ms)
 {
-	if (!check(count >= 2 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(min_length >= 1 && min_length <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(rows != nullptr && track_count != nullptr && point_count != nullptr && thresholds != nullptr && placements != nullptr,
-	           BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (uint32_t k = 0; k < threshold_count; k++)
-		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
-		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(max_distance >= 0.0f && max_distance <= BEAMFORMER_HIP_MAX_PAIR_DISTANCE, BeamformerLibErrorKind_InvalidAccess)) return 0;   /* (a NaN fails both) */
-	if (!check((deposit & ~(BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS | BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS)) == 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	return track_peaks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame,
-	                               min_length, deposit, rows, tracks, points, track_count, point_count, device_ms);
+	const PeakQuery q{count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame};
+	if (!valid_peak_query(q, true, true, true, &min_length, rows != nullptr && track_count != nullptr && point_count != nullptr)) return 0;
+	if (!valid_track_deposit(deposit)) return 0;
+	return track_peaks_last_frames(q, min_length, deposit, rows, tracks, points, track_count, point_count, device_ms);
 }
 
-/* (the track call's checks, in its order and with its error kinds, then the call's own) */
 uint32_t beamformer_hip_draw_tracks_last_frames(uint32_t count, const BeamformerHipFrameRegion *region, const float *thresholds,
                                                 uint32_t threshold_count, const double *placements, uint32_t placement_count,
                                                 uint32_t use_offsets, float max_distance, uint32_t max_per_frame, uint32_t min_length,
                                                 uint32_t smooth, uint32_t deposit, BeamformerHipDrawnFrame *rows, float *device_ms)
 {
-	if (!check(count >= 2 && count <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(max_per_frame >= 1 && max_per_frame <= BEAMFORMER_HIP_MAX_PEAKS_PER_FRAME, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(min_length >= 1 && min_length <= BEAMFORMER_HIP_MAX_SCORED_FRAMES, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	if (!check(rows != nullptr && thresholds != nullptr && placements != nullptr, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(threshold_count == 1 || threshold_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(placement_count == 1 || placement_count == count, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (uint32_t k = 0; k < threshold_count; k++)
-		if (!check(std::isfinite(thresholds[k]) && thresholds[k] >= 0.0f, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	for (size_t k = 0; k < (size_t)12 * placement_count; k++)
-		if (!check(std::isfinite(placements[k]), BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(max_distance >= 0.0f && max_distance <= BEAMFORMER_HIP_MAX_PAIR_DISTANCE, BeamformerLibErrorKind_InvalidAccess)) return 0;   /* (a NaN fails both) */
-	if (!check((deposit & ~(BEAMFORMER_HIP_TRACK_DEPOSIT_POINTS | BEAMFORMER_HIP_TRACK_DEPOSIT_LINKS)) == 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
-	if (!check(smooth <= BEAMFORMER_HIP_MAX_TRACK_SMOOTH, BeamformerLibErrorKind_BufferOverflow)) return 0;
-	return draw_tracks_last_frames(count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame,
-	                               min_length, smooth, deposit, rows, device_ms);
+	const PeakQuery q{count, region, thresholds, threshold_count, placements, placement_count, use_offsets, max_distance, max_per_frame};
+	if (!valid_peak_query(q, true, true, true, &min_length, rows != nullptr)) return 0;
+	if (!valid_track_deposit(deposit)) return 0;
+	if (!check(smooth <= BEAMFORMER_HIP_MAX_TRACK_SMOOTH, BeamformerLibErrorKind_BufferOverflow)) return 0;      /* (behind every InvalidAccess) */
+	return draw_tracks_last_frames(q, min_length, smooth, deposit, rows, device_ms);
 }
 
 uint32_t beamformer_hip_track_map_copy(uint32_t *counts, int64_t *sums, uint64_t out_count, BeamformerHipTrackMapInfo *info)

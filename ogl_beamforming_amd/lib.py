@@ -557,22 +557,41 @@ def rank_frames(rows, criterion):
     return scores[:len(rows)], int(best.value)
 
 
+_NO_PLACEMENTS = object()
+
+
+def _peak_arguments(count, thresholds, region, placements=_NO_PLACEMENTS):
+    """What the peak calls take first, as ctypes: [count, region, thresholds, their number] and -- for a call that has placements --
+    [placements, their number], ready to be passed on.  Raises ValueError for placements that are not 12 numbers a matrix."""
+    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
+    head = [int(count), None if region is None else C.byref(region), (C.c_float * max(1, len(values)))(*values), len(values)]
+    if placements is not _NO_PLACEMENTS:
+        matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
+        if matrices.size % 12:
+            raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+        head += [matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12]
+    return head
+
+
+def _first_records(kind, records, total):
+    """the first `total` of the packed records a call wrote into a numpy array of `kind`, as a ctypes array of their own"""
+    return (kind * total).from_buffer_copy(records[:total].tobytes())
+
+
 def find_peaks_last_frames(count, thresholds, max_per_frame, region=None):
     """beamformer_hip_find_peaks_last_frames: the local maxima of the `count` newest frames, found on the device.  thresholds: one number
     for all frames, or `count` of them, oldest first (on the magnitude, in the frame's units); region None: every frame whole.  Returns
     (frames, peaks, device_ms): a ctypes array of `count` HipFramePeaks rows, a ctypes array of the packed HipFramePeak records (frame
     n's are peaks[frames[n].first : frames[n].first + frames[n].stored]) and the device time of the launches."""
     count, max_per_frame = int(count), int(max_per_frame)
-    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
-    levels = (C.c_float * max(1, len(values)))(*values)
+    head = _peak_arguments(count, thresholds, region)
     rows = (P.HipFramePeaks * max(1, count))()
     room = count * max_per_frame if 0 < count <= P.HIP_MAX_SCORED_FRAMES and 0 < max_per_frame <= P.HIP_MAX_PEAKS_PER_FRAME else 0
     records = np.zeros(max(1, room), np.dtype(P.HipFramePeak))
     total, ms = C.c_uint32(0), C.c_float(0)
-    _check(library().beamformer_hip_find_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values), max_per_frame,
-                                                           rows, records.ctypes.data_as(C.POINTER(P.HipFramePeak)), C.byref(total), C.byref(ms)))
-    peaks = (P.HipFramePeak * int(total.value)).from_buffer_copy(records[: int(total.value)].tobytes())
-    return rows, peaks, float(ms.value)
+    _check(library().beamformer_hip_find_peaks_last_frames(*head, max_per_frame, rows, records.ctypes.data_as(C.POINTER(P.HipFramePeak)),
+                                                           C.byref(total), C.byref(ms)))
+    return rows, _first_records(P.HipFramePeak, records, int(total.value)), float(ms.value)
 
 
 def peaks_to_views(source_transform, source_points, peaks, patch_points, patch_extent_voxels, use_offsets=True, tag=0):
@@ -632,16 +651,10 @@ def accumulate_peaks_last_frames(count, thresholds, placements, use_offsets=True
     one): a peak at index + offset lands on map coordinate A[:, :3] @ p + A[:, 3] and in the bin floor(. + 0.5).  Returns
     (frames, device_ms): a ctypes array of `count` HipMapDeposits rows and the device time of the launches."""
     count = int(count)
-    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
-    levels = (C.c_float * max(1, len(values)))(*values)
-    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
-    if matrices.size % 12:
-        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    head = _peak_arguments(count, thresholds, region, placements)
     rows = (P.HipMapDeposits * max(1, count))()
     ms = C.c_float(0)
-    _check(library().beamformer_hip_accumulate_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
-                                                                 matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
-                                                                 1 if use_offsets else 0, rows, C.byref(ms)))
+    _check(library().beamformer_hip_accumulate_peaks_last_frames(*head, 1 if use_offsets else 0, rows, C.byref(ms)))
     return rows, float(ms.value)
 
 
@@ -700,23 +713,15 @@ def pair_peaks_last_frames(count, thresholds, placements, max_distance, max_per_
     rows, a ctypes array of the packed HipPeakPair records (frame pair n's are pairs[rows[n].first : rows[n].first + rows[n].pairs];
     empty with records False: the call makes none) and the device time of the launches."""
     count, max_per_frame = int(count), int(max_per_frame)
-    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
-    levels = (C.c_float * max(1, len(values)))(*values)
-    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
-    if matrices.size % 12:
-        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    head = _peak_arguments(count, thresholds, region, placements)
     rows = (P.HipPeakPairs * max(1, count - 1))()
     room = (count - 1) * max_per_frame if records and 2 <= count <= P.HIP_MAX_SCORED_FRAMES and 0 < max_per_frame <= P.HIP_MAX_PEAKS_PER_FRAME else 0
     out = np.zeros(max(1, room), np.dtype(P.HipPeakPair))
     total, ms = C.c_uint32(0), C.c_float(0)
-    _check(library().beamformer_hip_pair_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
-                                                           matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
-                                                           1 if use_offsets else 0, float(max_distance), max_per_frame, 1 if deposit else 0, rows,
-                                                           out.ctypes.data_as(C.POINTER(P.HipPeakPair)) if records else None, C.byref(total),
+    _check(library().beamformer_hip_pair_peaks_last_frames(*head, 1 if use_offsets else 0, float(max_distance), max_per_frame, 1 if deposit else 0,
+                                                           rows, out.ctypes.data_as(C.POINTER(P.HipPeakPair)) if records else None, C.byref(total),
                                                            C.byref(ms)))
-    kept = int(total.value) if records else 0
-    pairs = (P.HipPeakPair * kept).from_buffer_copy(out[:kept].tobytes())
-    return rows, pairs, float(ms.value)
+    return rows, _first_records(P.HipPeakPair, out, int(total.value) if records else 0), float(ms.value)
 
 
 def track_peaks_last_frames(count, thresholds, placements, max_distance, max_per_frame, min_length, use_offsets=True, deposit=0, region=None,
@@ -729,26 +734,18 @@ def track_peaks_last_frames(count, thresholds, placements, max_distance, max_per
     HipPeakTrack and the HipTrackPoint records (track t's points are points[tracks[t].first : tracks[t].first + tracks[t].length];
     both empty with records False: the call downloads none) and the device time of the launches."""
     count, max_per_frame = int(count), int(max_per_frame)
-    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
-    levels = (C.c_float * max(1, len(values)))(*values)
-    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
-    if matrices.size % 12:
-        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    head = _peak_arguments(count, thresholds, region, placements)
     rows = (P.HipTrackedFrame * max(1, count))()
     room = count * max_per_frame if records and 2 <= count <= P.HIP_MAX_SCORED_FRAMES and 0 < max_per_frame <= P.HIP_MAX_PEAKS_PER_FRAME else 0
     out_tracks, out_points = np.zeros(max(1, room), np.dtype(P.HipPeakTrack)), np.zeros(max(1, room), np.dtype(P.HipTrackPoint))
     track_total, point_total, ms = C.c_uint32(0), C.c_uint32(0), C.c_float(0)
-    _check(library().beamformer_hip_track_peaks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
-                                                            matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
-                                                            1 if use_offsets else 0, float(max_distance), max_per_frame, int(min_length),
+    _check(library().beamformer_hip_track_peaks_last_frames(*head, 1 if use_offsets else 0, float(max_distance), max_per_frame, int(min_length),
                                                             int(deposit), rows,
                                                             out_tracks.ctypes.data_as(C.POINTER(P.HipPeakTrack)) if records else None,
                                                             out_points.ctypes.data_as(C.POINTER(P.HipTrackPoint)) if records else None,
                                                             C.byref(track_total), C.byref(point_total), C.byref(ms)))
     kept_tracks, kept_points = (int(track_total.value), int(point_total.value)) if records else (0, 0)
-    tracks = (P.HipPeakTrack * kept_tracks).from_buffer_copy(out_tracks[:kept_tracks].tobytes())
-    points = (P.HipTrackPoint * kept_points).from_buffer_copy(out_points[:kept_points].tobytes())
-    return rows, tracks, points, float(ms.value)
+    return rows, _first_records(P.HipPeakTrack, out_tracks, kept_tracks), _first_records(P.HipTrackPoint, out_points, kept_points), float(ms.value)
 
 
 def draw_tracks_last_frames(count, thresholds, placements, max_distance, max_per_frame, min_length, smooth=0, use_offsets=True, deposit=0,
@@ -759,16 +756,10 @@ def draw_tracks_last_frames(count, thresholds, placements, max_distance, max_per
     (P.HIP_TRACK_DEPOSIT_POINTS) and, with the link's displacement, into the track map (P.HIP_TRACK_DEPOSIT_LINKS).  No record list
     comes back.  Returns (rows, device_ms): a ctypes array of `count` HipDrawnFrame rows and the device time of the launches."""
     count, max_per_frame = int(count), int(max_per_frame)
-    values = [float(t) for t in np.atleast_1d(np.asarray(thresholds, np.float32))]
-    levels = (C.c_float * max(1, len(values)))(*values)
-    matrices = np.ascontiguousarray(np.asarray(placements, np.float64).reshape(-1))
-    if matrices.size % 12:
-        raise ValueError("placements: 12 numbers (row-major 3 x 4) a matrix")
+    head = _peak_arguments(count, thresholds, region, placements)
     rows = (P.HipDrawnFrame * max(1, count))()
     ms = C.c_float(0)
-    _check(library().beamformer_hip_draw_tracks_last_frames(count, None if region is None else C.byref(region), levels, len(values),
-                                                            matrices.ctypes.data_as(C.POINTER(C.c_double)), matrices.size // 12,
-                                                            1 if use_offsets else 0, float(max_distance), max_per_frame, int(min_length),
+    _check(library().beamformer_hip_draw_tracks_last_frames(*head, 1 if use_offsets else 0, float(max_distance), max_per_frame, int(min_length),
                                                             int(smooth), int(deposit), rows, C.byref(ms)))
     return rows, float(ms.value)
 

@@ -1,6 +1,7 @@
 """The calls on frames already in the ring, one after the other in one process: what they share on the device -- the scratch and the
-pinned block that score, find_peaks, gram, correlate and accumulate_peaks carve their tables from, the table of the queued runs, the
-localisation map -- has to grow from one call to the next and come back after a shutdown, which no test of one operation notices.
+pinned block that score, quantiles, find_peaks, gram, gram_boxes, correlate, accumulate_peaks, pair_peaks, track_peaks and draw_tracks
+carve their tables from, the scratch the last three size by the peaks they find, the table of the queued runs, the two deposit maps --
+has to grow from one call to the next and come back after a shutdown, which no test of one operation notices.
 
 Every result is judged by the test of its own operation: its reference, its comparator and its bars are imported from there, and
 nothing here restates them."""
@@ -12,11 +13,17 @@ import pytest
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import localisation_ref
+from tests import test_gpu_block_filter as boxes_tests
 from tests import test_gpu_ensemble as ensemble_tests
 from tests import test_gpu_frame_metrics as metrics_tests
 from tests import test_gpu_frame_peaks as peaks_tests
+from tests import test_gpu_frame_quantiles as quantiles_tests
 from tests import test_gpu_localisation as map_tests
 from tests import test_gpu_motion as motion_tests
+from tests import test_gpu_track_chains as chains_tests
+from tests import test_gpu_track_draw as draw_tests
+from tests import test_gpu_tracks as tracks_tests
+from tests import track_chains_ref, track_draw_ref, tracks_ref
 from tests import variants_cases as vc
 from tests.test_gpu_frame_metrics import newest_info, region_of
 
@@ -29,6 +36,8 @@ ensemble_tests.GRIDS.update(frame_ops_small=((16, 1, 8), vc.LO, vc.HI, True), fr
 MAP_POINTS = (8, 1, 8)
 REGIONS = [((1, 0, 1), (13, 1, 5)), ((3, 0, 3), (13, 1, 5))]        # two boxes for correlate, the second against the small frame's far corner
 SCORE_BOX = ((5, 0, 3), (3, 1, 2))
+REACH = 3.0                                                         # map voxels: a voxel and a half of the small frames along z
+BOTH = track_chains_ref.POINTS | track_chains_ref.LINKS
 
 
 @pytest.fixture(autouse=True)
@@ -39,6 +48,7 @@ def automatic_path(bflib):
     yield
     L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
+    bflib.track_map_reset(None)
 
 
 def map_of(which):
@@ -48,8 +58,54 @@ def map_of(which):
     return grid, map_tests.placement_onto(grid, acq.bp.das_voxel_transform, ensemble_tests.GRIDS[which][0])
 
 
+def the_newer_calls(which, frames, thresholds, A):
+    """quantiles, gram_boxes, pair_peaks, track_peaks and draw_tracks on the K newest frames, each judged as its own test judges it, the
+    three that deposit on fresh maps of MAP_POINTS; returns every call's bytes, and both maps as the draw call leaves them"""
+    out = {}
+    # quantiles: its own check, then the call's bytes
+    quantiles_tests.ranked(list(frames), quantiles_tests.FRACTIONS)
+    rows, records, tables, _ = bf.quantiles_last_frames(K, quantiles_tests.FRACTIONS, histograms=True)
+    out["quantiles"] = bytes(rows), bytes(records), tables.tobytes()
+    # gram_boxes, two boxes, against gram one box at a time
+    want = boxes_tests.singles(K, REGIONS)
+    grams, infos, _ = bf.gram_boxes_last_frames(K, [region_of(box) for box in REGIONS])
+    boxes_tests.same_as_singles(grams, infos, want, which)
+    out["gram_boxes"] = grams.tobytes(), [bytes(i) for i in infos]
+    # pair_peaks, depositing
+    records = tracks_tests.records_of(K, thresholds)
+    bf.track_map_reset(MAP_POINTS)
+    rows, pairs = tracks_tests.pair(K, thresholds, A, REACH, deposit=True)
+    counts, sums = tracks_ref.empty_map(MAP_POINTS)
+    want, numbers = tracks_ref.pair_records(records, A, REACH, counts=counts, sums=sums)
+    tracks_tests.same_call(rows, pairs, want, numbers, K, thresholds)
+    tracks_tests.same_map(MAP_POINTS, counts, sums)
+    assert sum(w["pairs"] for w in numbers) >= 1
+    out["pairs"] = bytes(rows), pairs.tobytes()
+    # track_peaks, min_length 2, both deposits; then without records: the same rows, the maps once more
+    density, counts, sums = chains_tests.fresh_maps(MAP_POINTS)
+    got = chains_tests.track(K, thresholds, A, REACH, 2, deposit=BOTH)
+    want = track_chains_ref.chain_records(records, A, REACH, 2, True, deposit=BOTH, point_map=density, counts=counts, sums=sums)
+    chains_tests.same_call(got, want, K, thresholds)
+    chains_tests.same_maps(MAP_POINTS, density, counts, sums)
+    assert len(want["tracks"]) >= 1
+    rows, none, nothing, _ = bf.track_peaks_last_frames(K, thresholds, A, REACH, chains_tests.CAP, 2, deposit=BOTH, records=False)
+    assert bytes(rows) == bytes(got[0]) and len(none) == 0 and len(nothing) == 0
+    chains_tests.same_maps(MAP_POINTS, 2 * density, 2 * counts, 2 * sums)
+    out["tracks"] = [bytes(v) for v in got]
+    # draw_tracks, smooth 1, both deposits; track_map_copy beside localisation_map_copy
+    density, counts, sums = draw_tests.fresh_maps(MAP_POINTS, MAP_POINTS)
+    rows = draw_tests.draw(K, thresholds, A, REACH, 2, 1, deposit=BOTH)
+    want = track_draw_ref.draw_records(records, A, REACH, 2, 1, True, deposit=BOTH, point_map=density, counts=counts, sums=sums)
+    draw_tests.same_rows(rows, want, K, thresholds)
+    point_info, link_info = draw_tests.same_maps(MAP_POINTS, MAP_POINTS, density, counts, sums)
+    draw_tests.same_infos(point_info, link_info, 1, want["rows"], BOTH)
+    out["drawn"] = bytes(rows)
+    out["maps"] = bf.localisation_map_copy(MAP_POINTS)[0].tobytes(), *(v.tobytes() for v in bf.track_map_copy(MAP_POINTS)[:2])
+    return out
+
+
 def the_order(which):
-    """the seven calls on the K newest frames, each judged as its own test judges it; returns what a later run can be compared with"""
+    """the calls on the K newest frames, each judged as its own test judges it; returns what a later run can be compared with"""
     frames, ids = ensemble_tests.ensemble(which, K)
     assert frames.shape[1:] == ensemble_tests.GRIDS[which][0][::-1] and np.iscomplexobj(frames)
     thresholds = peaks_tests.fraction_of_max(frames, 0.25)
@@ -81,7 +137,10 @@ def the_order(which):
     assert bytes(again_rows) == bytes(peak_rows) and bytes(again_peaks) == bytes(peaks)
     # (the deposit rows last: their check asks find_peaks once more)
     map_tests.check_rows(deposits, numbers, frames, thresholds)
-    return dict(frames=frames, scored=scored, peak_rows=peak_rows, peaks=peaks, gram=G, table=table, counts=counts)
+    # 8. the newer calls, and at the end of the walk each of them again: the bytes of its first run
+    newer = the_newer_calls(which, frames, thresholds, A)
+    assert the_newer_calls(which, frames, thresholds, A) == newer
+    return dict(frames=frames, scored=scored, peak_rows=peak_rows, peaks=peaks, gram=G, table=table, counts=counts, newer=newer)
 
 
 def numbers_of(row):
@@ -102,7 +161,9 @@ def test_the_scratch_grows_from_small_frames_to_large_ones_and_every_call_finds_
     assert [numbers_of(r) for r in again["scored"]] == [numbers_of(r) for r in small["scored"]]
     assert bytes(again["peaks"]) == bytes(small["peaks"]) and again["gram"].tobytes() == small["gram"].tobytes()
     assert again["table"].tobytes() == small["table"].tobytes() and again["counts"].tobytes() == small["counts"].tobytes()
-
+    # the rows carry the frames' ids; the pair, track and point records and both maps do not: byte for byte
+    first, second = small["newer"], again["newer"]
+    assert second["pairs"][1] == first["pairs"][1] and second["tracks"][1:] == first["tracks"][1:] and second["maps"] == first["maps"]
 
 def mix_and_score(which, frames, ids):
     """two mixes of the K newest frames queued behind them (the ensemble tests' check), then their metrics rows"""
@@ -150,13 +211,19 @@ def test_a_shutdown_releases_everything_and_the_calls_start_again(bflib):
     map_tests.run(grid, frames, peaks_tests.fraction_of_max(frames, 0.25), A)
     scored, _ = bf.score_last_frames(K)
     out, _, mixed_rows = mix_and_score(which, frames, ids)
+    bf.track_map_reset(MAP_POINTS)
+    assert tuple(bf.track_map_copy(MAP_POINTS)[2].points) == MAP_POINTS              # the track map exists
 
     L.beamformer_hip_shutdown()
     counts, info = np.full(int(np.prod(MAP_POINTS)), 0xA5A5A5A5, np.uint32), P.HipMapInfo()
+    sums, track_info = np.full(3 * counts.size, 0x5A, np.int64), P.HipTrackMapInfo()
 
     def no_map():
         assert not L.beamformer_hip_localisation_map_copy(counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size, C.byref(info))
         assert bf.last_error()[0] == E.InvalidAccess and (counts == 0xA5A5A5A5).all() and not bytes(info).strip(b"\0")
+        assert not L.beamformer_hip_track_map_copy(counts.ctypes.data_as(C.POINTER(C.c_uint32)), sums.ctypes.data_as(C.POINTER(C.c_int64)), counts.size,
+                                                   C.byref(track_info))
+        assert bf.last_error()[0] == E.InvalidAccess and (counts == 0xA5A5A5A5).all() and (sums == 0x5A).all() and not bytes(track_info).strip(b"\0")
 
     no_map()
     assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
@@ -174,3 +241,7 @@ def test_a_shutdown_releases_everything_and_the_calls_start_again(bflib):
     bf.localisation_map_reset(MAP_POINTS)
     empty, info = bf.localisation_map_copy(MAP_POINTS)
     assert not empty.any() and (info.calls, int(info.deposited), int(info.outside)) == (0, 0, 0)
+    bf.track_map_reset(MAP_POINTS)
+    empty, no_sums, track_info = bf.track_map_copy(MAP_POINTS)
+    assert not empty.any() and not no_sums.any()
+    assert (track_info.calls, int(track_info.pairs), int(track_info.deposited), int(track_info.outside)) == (0, 0, 0, 0)

@@ -117,6 +117,12 @@ ROWS = {
     "motion_rate": ("tools/motion_rate.py", tool_rows(["tools/motion_rate.py"])),
     "warp_rate": ("tools/warp_rate.py", tool_rows(["tools/warp_rate.py"])),
     "localisation_rate": ("tools/localisation_rate.py", tool_rows(["tools/localisation_rate.py"])),
+    "frame_quantiles_rate": ("tools/frame_quantiles_rate.py --counts 1,64 --host-repeats 1",
+                             tool_rows(["tools/frame_quantiles_rate.py", "--counts", "1,64", "--host-repeats", "1"])),
+    "pairs_rate": ("tools/pairs_rate.py", tool_rows(["tools/pairs_rate.py"])),
+    "tracks_rate": ("tools/tracks_rate.py", tool_rows(["tools/tracks_rate.py"])),
+    "draw_rate": ("tools/draw_rate.py", tool_rows(["tools/draw_rate.py"])),
+    "block_filter_rate": ("tools/block_filter_rate.py", tool_rows(["tools/block_filter_rate.py"])),
 }
 
 
