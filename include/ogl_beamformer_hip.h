@@ -1607,6 +1607,44 @@ typedef struct {
 } BeamformerHipDasDescription;
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_das(uint32_t parameter_slot, BeamformerHipDasDescription *out);
 
+/* How the RF of a push reaches the RF ring: the library's ONE rule (csrc/executor.cpp: decide_upload), which the push functions follow
+ * and this call reports.  Needs no device.  data_size: the bytes of ONE raw frame, as the push calls take it; frame_count: 1 describes
+ * beamformer_push_data_with_compute / beamformer_hip_push_device_data_with_compute, 2 and more a burst of that many frames (every
+ * push of several frames, and the views and variants pushes of one, follow the burst's rule: the ingest kernel always runs, and the
+ * whole upload is measured against the copy-engine threshold); device_pointer: the device address a device-resident push would be
+ * given -- the copy width depends on its alignment -- or NULL for host data.
+ *   route          BeamformerHipUploadRoute:
+ *                  PinnedInPlace     host data under 8 MiB: copied into a pinned slot, which the ingest kernel reads in place;
+ *                  CopyEngineDirect  host data of 8 MiB and more already in the mapped layout (identity channel mapping, no row padding,
+ *                                    no contrast mode): one H2D copy on the copy stream into the RF ring, no kernel;
+ *                  CopyEngineStaged  other host data of 8 MiB and more: H2D into raw staging on the copy stream, then the ingest kernel;
+ *                  DeviceBorrowed    device data already in the mapped layout whose plan does not start with DAS: the first stage
+ *                                    reads the caller's buffer in place;
+ *                  DeviceCopy        ... whose plan starts with DAS: one device-to-device copy into the RF ring;
+ *                  DeviceIngest      other device data: the ingest kernel reads the caller's buffer;
+ *   ingest_kernel  0 none, 1 ingest_copy_kernel, 2 ingest_a1s2_kernel;
+ *   copy_bytes     ingest_copy_kernel: bytes per lane and step, 16, 4 or 2 -- the widest that divides the raw and the mapped row, the
+ *                  frame strides of a burst and device_pointer; otherwise 0;
+ *   a1s2_base      the scalar type of the data kind, which ingest_a1s2_kernel is instantiated for: 0 int16, 1 float32, 2 float16;
+ *   rf_bytes       one frame in the RF ring (what beamformer_hip_get_device_info checksums);
+ *   upload_bytes   data_size x frame_count, what the threshold is applied to. */
+typedef enum {
+	BeamformerHipUploadRoute_PinnedInPlace    = 0,
+	BeamformerHipUploadRoute_CopyEngineDirect = 1,
+	BeamformerHipUploadRoute_CopyEngineStaged = 2,
+	BeamformerHipUploadRoute_DeviceBorrowed   = 3,
+	BeamformerHipUploadRoute_DeviceCopy       = 4,
+	BeamformerHipUploadRoute_DeviceIngest     = 5,
+	BeamformerHipUploadRoute_Count
+} BeamformerHipUploadRoute;
+typedef struct {
+	uint32_t route, ingest_kernel, copy_bytes, a1s2_base;
+	uint64_t rf_bytes, upload_bytes;
+	char     name[32];              /* "pinned-in-place", "copy-engine-direct", "copy-engine-staged", "device-borrowed", "device-copy", "device-ingest" */
+} BeamformerHipUploadDescription;
+BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_describe_upload(uint32_t parameter_slot, uint32_t data_size, uint32_t frame_count,
+                                                             const void *device_pointer, BeamformerHipUploadDescription *out);
+
 /* Diagnostic switches (none is needed in production; listed above, csrc/das_select.h says what each does): set and cleared
  * (value NULL or "") through this call only -- the library reads no environment variable for them.  Returns 0 for an unknown name. */
 BEAMFORMER_LIB_EXPORT uint32_t beamformer_hip_set_hook(const char *name, const char *value);

@@ -253,6 +253,16 @@ typedef struct {
 	uint64_t in_frame_bytes, out_frame_bytes;
 } BfIngestArgs;
 
+/* Bytes a lane of ingest_copy_kernel moves per step: the widest of 16, 4 and 2 that divides both row strides, both frame strides and
+ * both addresses.  stages.hip launches by it and executor.cpp's decide_upload reports it (a buffer of the library's own counts as 0:
+ * device allocations and pinned slots are aligned far beyond 16 bytes). */
+static inline uint32_t bf_ingest_copy_bytes(uint64_t in_row_bytes, uint64_t out_row_bytes, uint64_t raw, uint64_t out,
+                                            uint64_t in_frame_bytes, uint64_t out_frame_bytes)
+{
+	uint64_t align = in_row_bytes | out_row_bytes | raw | out | in_frame_bytes | out_frame_bytes;
+	return (align % 16 == 0) ? 16u : (align % 4 == 0) ? 4u : 2u;
+}
+
 typedef struct {
 	const void *left, *right; void *out;
 	uint32_t size[3];

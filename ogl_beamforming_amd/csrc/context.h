@@ -291,6 +291,9 @@ bool     set_error(BeamformerLibErrorKind kind);   /* records and returns false 
 bool ensure_device();                               /* SharedMemory error when no HIP device */
 uint64_t default_frame_ring_bytes();
 bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool data_on_device);
+/* beamformer_hip_describe_upload: decide_upload's decision for `frames` raw frames of frame_size bytes each (one: the single push) */
+bool describe_upload(const ParameterBlock &pb, const Plan &plan, uint64_t frame_size, uint32_t frames, const void *device_pointer,
+                     BeamformerHipUploadDescription *out);
 bool push_burst(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);   /* groups: a READI sweep */
 bool push_readi_image(uint32_t block, const void *data, uint32_t frame_size, uint32_t frame_count, const uint32_t *groups, bool data_on_device);
 bool last_readi_image_info(BeamformerHipReadiImageInfo *out);

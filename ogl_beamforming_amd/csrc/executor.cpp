@@ -1211,6 +1211,58 @@ static bool rf_layout(const ParameterBlock &pb, RfLayout &l)
 	return true;
 }
 
+/* How a push's RF reaches the RF ring: the ONE rule, followed by push_rf_and_compute and push_frames and reported by
+ * beamformer_hip_describe_upload (include/ogl_beamformer_hip.h names the routes).  Host arithmetic only.
+ *   direct     the mapped layout is the raw layout, so one copy (H2D or D2D) lands the RF in its slot and no ingest kernel runs --
+ *              unless the upload is small, when the ingest kernel IS the copy out of the pinned slot.  A single push only: a push of
+ *              several frames (and the views and variants pushes of one) always runs the ingest kernel;
+ *   overlap    host data of kOverlapBytes and more, all frames together: H2D on the copy stream;
+ *   zero_copy  other host data: the ingest kernel reads the pinned slot in place;
+ *   borrowed   device-resident RF already in the mapped layout is read in place by the first stage (no copy into the RF ring): the
+ *              caller keeps it unchanged until the frame has run, which stream order gives for free when its producer is on the
+ *              library's stream.  Plans that start with DAS still copy: the DAS input needs the library's zero block behind it. */
+struct UploadDecision {
+	uint32_t route;                         /* BeamformerHipUploadRoute */
+	bool     direct, overlap, zero_copy, borrowed, ingest;
+	uint32_t ingest_kernel, copy_bytes;     /* 0 none, 1 copy (copy_bytes per lane and step, for buffers of the library's own), 2 A1S2 */
+	uint64_t in_step, rf_step;              /* several frames: frame k of the raw data and of the RF slot at k times these */
+};
+
+static UploadDecision decide_upload(const RfLayout &l, const Plan &plan, uint64_t frame_size, uint32_t frames, bool multi_frame_push,
+                                    const void *device_pointer)
+{
+	UploadDecision u{};
+	const bool on_device = device_pointer != nullptr;
+	u.direct    = !multi_frame_push && l.identity && !l.a1s2 && l.in_row == l.out_row;
+	u.overlap   = !on_device && frame_size * frames >= kOverlapBytes;
+	u.zero_copy = !on_device && !u.overlap;
+	u.borrowed  = on_device && u.direct && !plan.stages.empty() && plan.stages[0].kind != BeamformerShaderKind_DAS;
+	u.ingest    = !u.direct || u.zero_copy;
+	if (on_device) u.route = u.borrowed ? BeamformerHipUploadRoute_DeviceBorrowed : u.ingest ? BeamformerHipUploadRoute_DeviceIngest : BeamformerHipUploadRoute_DeviceCopy;
+	else           u.route = u.zero_copy ? BeamformerHipUploadRoute_PinnedInPlace : u.ingest ? BeamformerHipUploadRoute_CopyEngineStaged : BeamformerHipUploadRoute_CopyEngineDirect;
+	u.in_step = frames > 1 ? frame_size : 0;
+	u.rf_step = frames > 1 ? round_up(l.rf_size, 64) + 64 : 0;
+	u.ingest_kernel = !u.ingest ? 0u : l.a1s2 ? 2u : 1u;
+	u.copy_bytes = u.ingest_kernel == 1 ? bf_ingest_copy_bytes(l.in_row, l.out_row, (uint64_t)(uintptr_t)device_pointer, 0, u.in_step, u.rf_step) : 0u;
+	return u;
+}
+
+bool describe_upload(const ParameterBlock &pb, const Plan &plan, uint64_t frame_size, uint32_t frames, const void *device_pointer,
+                     BeamformerHipUploadDescription *out)
+{
+	static const char *const names[BeamformerHipUploadRoute_Count] = {"pinned-in-place", "copy-engine-direct", "copy-engine-staged",
+	                                                                  "device-borrowed", "device-copy", "device-ingest"};
+	RfLayout l;
+	if (!rf_layout(pb, l)) return false;
+	const UploadDecision u = decide_upload(l, plan, frame_size, frames, frames > 1, device_pointer);
+	std::memset(out, 0, sizeof(*out));
+	out->route = u.route; out->ingest_kernel = u.ingest_kernel; out->copy_bytes = u.copy_bytes;
+	out->a1s2_base = (uint32_t)bf_kind_base[pb.data_kind];
+	out->rf_bytes = l.rf_size; out->upload_bytes = frame_size * frames;
+	std::snprintf(out->name, sizeof(out->name), "%s", names[u.route]);
+	return true;
+}
+
 /* The ingest kernel: `frames` raw frames at `raw` into the mapped layout at `out`, frame k at k * the frame strides (one frame: 0). */
 static bool launch_ingest(PlanState *ps, const ParameterBlock &pb, const RfLayout &l, const void *raw, void *out, uint32_t frames,
                           uint64_t in_frame_bytes, uint64_t out_frame_bytes, hipStream_t s)
@@ -1362,44 +1414,32 @@ bool push_rf_and_compute(uint32_t block, const void *data, uint32_t size, bool d
 		t.events_slot = (uint32_t)(d.last_sampled_frame % kTimingSlots);
 	}
 
-	/* the copy shortcuts of a single push.  direct: the mapped layout is the raw layout, so one copy (H2D or D2D) lands the RF in its slot
-	 * and no ingest kernel runs -- unless the upload is small, when the ingest kernel IS the copy out of the pinned slot */
+	/* the route of a single push: decide_upload */
 	UploadSlot &u = d.upload[slot];
 	if (!claim_upload(u, size, !data_on_device)) return false;
-	const bool direct  = l.identity && !l.a1s2 && l.in_row == l.out_row;
-	const bool overlap = !data_on_device && size >= kOverlapBytes;
+	PlanState *ps = commit_block(block);
+	if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	const UploadDecision route = decide_upload(l, ps->plan, size, 1, false, data_on_device ? data : nullptr);
+	const bool overlap = route.overlap, borrowed = route.borrowed;
 	const void *raw = data;
 	if (!data_on_device) {
 		void *dst = nullptr;
 		if (overlap) {
 			dst = d.rf[slot].ptr;
-			if (!direct) {
+			if (route.ingest) {
 				if (!d.raw_staging[slot].ensure(round_up(size, 64) + 64)) return set_error(BeamformerLibErrorKind_BufferOverflow);
 				dst = d.raw_staging[slot].ptr;
 			}
 		}
-		raw = enqueue_upload(d, u, data, size, dst, direct ? rf_size : (uint64_t)size);
+		raw = enqueue_upload(d, u, data, size, dst, route.ingest ? (uint64_t)size : rf_size);
 		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	}
-	const bool zero_copy = !data_on_device && !overlap;
-	/* borrowed: device-resident RF already in the mapped layout is read in place by the first stage (no
-	 * copy into the RF ring): the caller keeps it unchanged until the frame has run, which stream
-	 * order gives for free when its producer is on the library's stream.  Plans that start with
-	 * DAS still copy: the DAS input needs the library's zero block behind it. */
-	bool borrowed = false;
-	if (data_on_device && direct) {
-		PlanState *ps = commit_block(block);
-		if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
-		borrowed = !ps->plan.stages.empty() && ps->plan.stages[0].kind != BeamformerShaderKind_DAS;
-	}
 	bool ok = true;
-	if (direct && !zero_copy) {
-		if (data_on_device && !borrowed) ok &= HIP_OK(hipMemcpyAsync(d.rf[slot].ptr, data, rf_size, hipMemcpyDeviceToDevice, s));
-	} else {
-		PlanState *ps = commit_block(block);
-		if (!ps) return set_error(BeamformerLibErrorKind_InvalidComputeStage);
+	if (route.ingest) {
 		ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, 1, 0, 0, s);
-		if (zero_copy) ok &= pinned_read_by(u, s);
+		if (route.zero_copy) ok &= pinned_read_by(u, s);
+	} else if (route.route == BeamformerHipUploadRoute_DeviceCopy) {
+		ok &= HIP_OK(hipMemcpyAsync(d.rf[slot].ptr, data, rf_size, hipMemcpyDeviceToDevice, s));
 	}
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	note_push_time();
@@ -1521,7 +1561,9 @@ static bool push_frames(uint32_t block, const PushGround &g, const void *data, b
 	const uint64_t rf_stride = round_up(l.rf_size, 64) + 64;
 	const uint64_t total     = (uint64_t)m.rf_frame_size * N;
 	const uint32_t slot = (uint32_t)(d.rf_index % BeamformerMaxRawDataFramesInFlight);
-	const bool overlap = !data_on_device && total >= kOverlapBytes;
+	/* the route: decide_upload, as a push of several frames (the ingest kernel always runs) */
+	const UploadDecision route = decide_upload(l, plan, m.rf_frame_size, N, true, data_on_device ? data : nullptr);
+	const bool overlap = route.overlap;
 	bool fits = d.rf[slot].ensure(rf_stride * N);
 	m.stage = N > 1 ? d.burst_stage : d.scratch;
 	m.stage_stride = N > 1 ? round_up(plan.intermediate_bytes, 64) + 64 : 0;
@@ -1565,14 +1607,14 @@ static bool push_frames(uint32_t block, const PushGround &g, const void *data, b
 	bool ok = HIP_OK(hipEventRecord(t.events[0], s));
 
 	/* ---- upload and ingest: a multi-frame push always runs the ingest kernel.  One RF frame: strides 0, as in a single push ---- */
-	const uint64_t in_step = N > 1 ? m.rf_frame_size : 0, rf_step = N > 1 ? rf_stride : 0;
+	const uint64_t in_step = route.in_step, rf_step = route.rf_step;
 	const void *raw = data;
 	if (!data_on_device) {
 		raw = enqueue_upload(d, u, data, total, overlap ? d.raw_staging[slot].ptr : nullptr, total);
 		if (!raw) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	}
 	ok &= launch_ingest(ps, pb, l, raw, d.rf[slot].ptr, N, in_step, rf_step, s);
-	if (!data_on_device && !overlap) ok &= pinned_read_by(u, s);
+	if (route.zero_copy) ok &= pinned_read_by(u, s);
 	segment(t, kStageIngest, s);
 	if (!ok) return set_error(BeamformerLibErrorKind_InvalidAccess);
 	note_push_time();

@@ -1502,6 +1502,19 @@ uint32_t beamformer_hip_describe_plan(uint32_t parameter_slot, BeamformerHipPlan
 	return 1;
 }
 
+uint32_t beamformer_hip_describe_upload(uint32_t parameter_slot, uint32_t data_size, uint32_t frame_count, const void *device_pointer,
+                                        BeamformerHipUploadDescription *out)
+{
+	if (!valid_parameter_block(parameter_slot) || !check(out != nullptr && frame_count != 0, BeamformerLibErrorKind_InvalidAccess)) return 0;
+	if (frame_count > 1 && !valid_burst_count(frame_count)) return 0;
+	const ParameterBlock &pb = ctx().blocks[parameter_slot];
+	/* the frame against the block, as the push judges it (there is no data to look at: any non-null address passes for it) */
+	if (!valid_rf_frame(pb, out, data_size)) return 0;
+	Plan plan;
+	if (!resolved_plan(pb, plan)) return 0;
+	return describe_upload(pb, plan, data_size, frame_count, device_pointer, out) ? 1 : 0;
+}
+
 uint32_t beamformer_hip_set_hook(const char *name, const char *value)
 {
 	/* the two switches that are no das_select.cpp switches: how the boxes of beamformer_hip_gram_boxes_last_frames are batched, and which

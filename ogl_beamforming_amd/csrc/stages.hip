@@ -97,8 +97,7 @@ extern "C" hipError_t bf_launch_ingest(const BfIngestArgs *a, hipStream_t s)
 		}
 		return hipGetLastError();
 	}
-	uint64_t align = a->in_row_bytes | a->out_row_bytes | (uint64_t)(uintptr_t)a->raw | (uint64_t)(uintptr_t)a->out | a->in_frame_bytes | a->out_frame_bytes;
-	uint32_t v = (align % 16 == 0) ? 16 : (align % 4 == 0) ? 4 : 2;
+	uint32_t v = bf_ingest_copy_bytes(a->in_row_bytes, a->out_row_bytes, (uint64_t)(uintptr_t)a->raw, (uint64_t)(uintptr_t)a->out, a->in_frame_bytes, a->out_frame_bytes);
 	uint64_t n = a->out_row_bytes / v;
 	dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256), a->channels, a->frames ? a->frames : 1u);
 	switch (v) {

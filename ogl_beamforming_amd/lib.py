@@ -192,6 +192,7 @@ def _load():
                                         C.POINTER(C.c_float), C.POINTER(u32)]),
         "beamformer_hip_describe_plan": (u32, [u32, C.POINTER(P.HipPlan)]),
         "beamformer_hip_describe_das": (u32, [u32, C.POINTER(P.HipDasDescription)]),
+        "beamformer_hip_describe_upload": (u32, [u32, u32, u32, vp, C.POINTER(P.HipUploadDescription)]),
         "beamformer_hip_set_hook": (u32, [C.c_char_p, C.c_char_p]),
         "beamformer_hip_shutdown": (None, []),
     }
@@ -1123,3 +1124,16 @@ def describe_das(bp, filters=(), slot=0):
     assert L.beamformer_hip_describe_das(slot, C.byref(d)), last_error()
     reasons = {k: bytes(d.declined[k]).split(b"\0")[0].decode() for k in range(8)}
     return int(d.path), d.kernel.decode(), d.name.decode(), reasons, d
+
+
+def describe_upload(bp, data_size, frame_count=1, device_pointer=None, filters=(), slot=0):
+    """How the RF of a push of these parameters would reach the RF ring (beamformer_hip_describe_upload): the description struct;
+    .route is a P.UploadRoute, .name says it in words.  data_size: the bytes of one raw frame; device_pointer: the address a
+    device-resident push would be given, None for host data.  Needs no device."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    d = P.HipUploadDescription()
+    _check(L.beamformer_hip_describe_upload(slot, data_size, frame_count, C.c_void_p(device_pointer), C.byref(d)))
+    return d

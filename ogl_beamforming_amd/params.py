@@ -530,6 +530,20 @@ class HipPlan(C.Structure):
                 ("das_voxel_transform", C.c_float * 16), ("intermediate_bytes", C.c_uint64)]
 
 
+class UploadRoute(enum.IntEnum):
+    PinnedInPlace = 0
+    CopyEngineDirect = 1
+    CopyEngineStaged = 2
+    DeviceBorrowed = 3
+    DeviceCopy = 4
+    DeviceIngest = 5
+
+
+class HipUploadDescription(C.Structure):
+    _fields_ = [("route", C.c_uint32), ("ingest_kernel", C.c_uint32), ("copy_bytes", C.c_uint32), ("a1s2_base", C.c_uint32),
+                ("rf_bytes", C.c_uint64), ("upload_bytes", C.c_uint64), ("name", C.c_char * 32)]
+
+
 class HipZbpPayload(C.Structure):
     _fields_ = [("major", C.c_uint32), ("data_kind", C.c_uint32), ("compression_kind", C.c_uint32),
                 ("reserved", C.c_uint32), ("offset", C.c_uint64), ("size", C.c_uint64)]

@@ -140,6 +140,20 @@ def plan(bp, filters=()):
     return out if ok else None
 
 
+def channel_map(bp, rf):
+    """oracle_channel_map: the RF as the client's copy loop lays it out (channel mapping, raw padding dropped, A1S2 contrast), as
+    (channels, transmits x samples x scalars) of rf's scalar type"""
+    lib = library()
+    lib.oracle_channel_map.restype = None
+    lib.oracle_channel_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(P.Parameters), C.c_int, C.POINTER(C.c_int16)]
+    pb = parameter_block(bp)
+    rf = np.ascontiguousarray(rf)
+    scalars = 2 if P.DATA_KIND_COMPLEX[int(bp.data_kind)] else 1
+    out = np.full((int(bp.channel_count), int(bp.acquisition_count) * int(bp.sample_count) * scalars), 0x55, rf.dtype)
+    lib.oracle_channel_map(rf.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.byref(pb.parameters), int(bp.data_kind), pb.channel_mapping)
+    return out
+
+
 def beamform(bp, rf, filters=(), threads=0, z=(0, 0), y=(0, 0), timing=None, stride=(1, 1), flags=None, truth=None, das_input=None):
     """Whole frame on the CPU, 16-channel chunks as the reference runs it.  z / y = (first,
     count) restrict the computed planes / rows (count 0 = whole axis); stride = (z, y) steps

@@ -172,9 +172,10 @@ def test_sum_of_last_frames_matches_the_sum_stage(bflib, oracle):
 
 
 def test_pipelined_host_pushes_keep_their_own_data(bflib):
-    """Host pushes go through three pinned slots and a copy stream; nine back-to-back pushes
-    of alternating RF (x1, x2: exact in every stage) must come out as F, 2F, F, ... with no
-    slot read before its upload landed or overwritten before its frame finished."""
+    """Host pushes under the copy-engine threshold go through three pinned slots, each read in place by the ingest kernel on the
+    compute stream (the pinned-in-place route of beamformer_hip_describe_upload: neither case reaches the copy stream, which
+    tests/test_gpu_ingest.py covers); nine back-to-back pushes of alternating RF (x1, x2: exact in every stage) must come out as
+    F, 2F, F, ... with no slot overwritten before the kernel that reads it has run."""
     L = bflib.library()
     L.beamformer_set_global_timeout(0xFFFFFFFF)
     for name in ("config1_small", "rca_shuffled_padded"):      # direct copy / ingest-kernel path
