@@ -59,7 +59,7 @@ __global__ __launch_bounds__(1024) void das_factored_kernel(const BfDasArgs p)
 
 	/* blockIdx -> tile and thread -> voxel exactly as das.hip: this file's own text, not general_tile / tile_voxel (das_general.h).  Tried
 	 * with this compiler -- general_tile alone, tile_voxel alone on the walk below, and both --: each changed all 48 kernels here (the
-	 * linear IQ instances run at their register limit: voxel_of below). */
+	 * linear IQ instances run at their register limit: voxel_of below).  Checked at its regime edges by the entries of tests/walk_cases.py. */
 	uint32_t total = p.blocks[0] * p.blocks[1] * p.blocks[2];
 	uint32_t bid   = blockIdx.x;
 	uint32_t per   = (total + 7u) / 8u;

@@ -104,7 +104,8 @@ __device__ __forceinline__ void das_rca(const BfDasArgs &p, const char *rf, floa
 	}
 }
 
-/* Block id -> tile (bx, by, bz) of the general kernel's grid; valid false: a block of the ragged tail, which has no tile. */
+/* Block id -> tile (bx, by, bz) of the general kernel's grid; valid false: a block of the ragged tail, which has no tile.
+ * (One of six copies of this walk; tests/walk_cases.py pins each at the tile counts and band counts where its branches differ.) */
 struct GeneralTile { uint32_t bx, by, bz; bool valid; };
 __device__ __forceinline__ GeneralTile general_tile(const BfDasArgs &p, uint32_t bid)
 {

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(1024) void das_hercules_kernel(const BfDasArgs p, c
 	constexpr bool RAWC = !PD && CPLX && INTERP == BF_INTERP_CUBIC;
 	using VT = sample_t<CPLX>;
 
-	/* blockIdx -> tile with each XCD walking a contiguous run of tiles (das.hip) */
+	/* blockIdx -> tile with each XCD walking a contiguous run of tiles (das.hip); checked at its regime edges by the entries of tests/walk_cases.py */
 	const uint32_t total = q.tiles[0] * q.tiles[1] * q.tiles[2];
 	const uint32_t per   = (total + 7u) / 8u;
 	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);

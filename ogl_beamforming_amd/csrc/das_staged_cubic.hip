@@ -53,7 +53,7 @@ __global__ __launch_bounds__(1024, 4) void das_rca_staged_cubic_kernel(const BfD
 	const uint32_t per   = (total + 7u) / 8u;
 	const uint32_t tile  = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
 	if (tile >= total) return;                               /* whole block */
-	uint32_t tu, tv, zl;                                     /* walk order: staged_tile_of */
+	uint32_t tu, tv, zl;                                     /* walk order: staged_tile_of; checked by the entries of tests/walk_cases.py */
 	if (q.depth_major & 1u) {
 		bf_column_walk(tile, q.tiles[0], q.tiles[2], q.walk_columns, tu, tv, zl);
 	} else {

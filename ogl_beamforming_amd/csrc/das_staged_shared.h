@@ -25,7 +25,8 @@ typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
  * sequence -- the two a CU holds (dispatch is breadth first over an XCD's 32 CUs) -- are NEIGHBOURS ALONG u in one plane: they read
  * the same rows of the global transmit table (14.6 KB at 76 transmits: the scalar cache holds 16 KB) and adjacent RF windows.
  * tu, tv, zl: along the receive axis, along the transmit axis, plane inside the shard.
- * False: no tile (the grid's rounding, the last chunk's padding) -- a whole block: no barrier is skipped. */
+ * False: no tile (the grid's rounding, the last chunk's padding) -- a whole block: no barrier is skipped.
+ * (One of six copies of the walk; tests/walk_cases.py pins each at the tile, column and z-chunk counts where its branches differ.) */
 template <uint32_t DEPTH_MASK = 1u>
 __device__ __forceinline__ bool staged_tile_of(const BfSeparableArgs &q, bool global_tables, uint32_t &tu, uint32_t &tv, uint32_t &zl)
 {

@@ -119,7 +119,8 @@ __global__ __launch_bounds__(1024, 4) void das_tile_kernel(const BfDasArgs p)
 	extern __shared__ __attribute__((aligned(16))) unsigned char tile_lds[];
 
 	/* blockIdx -> tile: das_factored.hip's text, thread -> voxel: tile_voxel (das_general.h).  (general_tile in place of the walk below
-	 * changed all eight kernels with this compiler, and so did tile_voxel at the store at the end of the kernel: both stay restated.) */
+	 * changed all eight kernels with this compiler, and so did tile_voxel at the store at the end of the kernel: both stay restated.)
+	 * Checked at its regime edges by the entries of tests/walk_cases.py. */
 	const uint32_t total = p.blocks[0] * p.blocks[1] * p.blocks[2];
 	const uint32_t bid   = blockIdx.x;
 	const uint32_t per   = (total + 7u) / 8u;
