@@ -3,25 +3,17 @@ BEAMFORMER_HIP_FRAME_RING_BYTES = 1 MiB (the ring is sized once per process): 32
 at most four frames, so it meets its own sources only by wrapping: a burst of 16 and a mix 16 -> 15 leave 32 KiB at the end of the ring,
 and the two lags of those 15 wrap to offset 0, clear of their sources; another burst of 16 and a mix 16 -> 14 then fill the ring to its
 last byte, and one lag of the 32 newest frames -- the two lag frames at offset 0 among them -- would wrap onto the oldest of its own
-sources: FrameSizeOverflow, and nothing has changed."""
+sources: FrameSizeOverflow, and nothing has changed.
+Started as python -m tests.autocorr_wrap_worker from the repository root (tests/scaffold.py run_ring_worker)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from ogl_beamforming_amd import configs as cfg, lib, params as P  # noqa: E402
-from tests import autocorr_ref as ref  # noqa: E402
-from tests import variants_cases as vc  # noqa: E402
-
-
-def newest(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
+from ogl_beamforming_amd import configs as cfg, lib, params as P
+from tests import autocorr_ref as ref
+from tests import variants_cases as vc
+from tests.frame_info import newest_info as newest
 
 
 def share_of_bound(out, frames, W, lags):

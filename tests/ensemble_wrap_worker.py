@@ -1,25 +1,17 @@
 """Child process of tests/test_gpu_ensemble.py: beamformer_hip_mix_last_frames in a frame ring of BEAMFORMER_HIP_FRAME_RING_BYTES =
 1 MiB (the ring is sized once per process).  A burst of 16 complex 64 x 1 x 64 frames takes 512 KiB.  A mix 16 -> 16 fills the ring
 exactly; the next one wraps to offset 0 and the burst's records stop being exportable; a mix 16 -> 17 would wrap onto its own sources:
-FrameSizeOverflow, and nothing has changed."""
+FrameSizeOverflow, and nothing has changed.
+Started as python -m tests.ensemble_wrap_worker from the repository root (tests/scaffold.py run_ring_worker)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from ogl_beamforming_amd import configs as cfg, lib, params as P  # noqa: E402
-from tests import ensemble_ref as ref  # noqa: E402
-from tests import variants_cases as vc  # noqa: E402
-
-
-def newest(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
+from ogl_beamforming_amd import configs as cfg, lib, params as P
+from tests import ensemble_ref as ref
+from tests import variants_cases as vc
+from tests.frame_info import newest_info as newest
 
 
 def within_bound(out, frames, W):

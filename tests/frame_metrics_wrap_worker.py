@@ -1,18 +1,15 @@
 """Child process of tests/test_gpu_frame_metrics.py: frame metrics in a frame ring of BEAMFORMER_HIP_FRAME_RING_BYTES (the ring is sized
 once per process), small enough that a few variants pushes wrap it.  A frame whose ring storage a newer frame has reused is no longer
-scored, copied or described -- InvalidAccess, as for a tombstone --, while every frame that is still there is."""
+scored, copied or described -- InvalidAccess, as for a tombstone --, while every frame that is still there is.
+Started as python -m tests.frame_metrics_wrap_worker from the repository root (tests/scaffold.py run_ring_worker)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from ogl_beamforming_amd import lib, params as P  # noqa: E402
-from tests import frame_metrics_ref as ref  # noqa: E402
-from tests import variants_cases as vc  # noqa: E402
+from ogl_beamforming_amd import lib, params as P
+from tests import frame_metrics_ref as ref
+from tests import variants_cases as vc
 
 E = P.LibError
 

@@ -175,7 +175,7 @@ SIGNAL_SHARE = 0.5
 def signal_share(bflib, oracle, acq, ref_in):
     """the share of the live DAS-input elements whose oracle value (the larger of |re|, |im|) exceeds the element's bar; 1.0 where
     every stage is exact (the check is bit-identity there)"""
-    from tests import test_gpu_stages as stages
+    from tests import stage_checks as stages
     bflib.library().beamformer_reserve_parameter_blocks(1)
     exact, mag, bar = stages.stage_bounds(bflib, oracle, acq, stages.plan_of(bflib, acq))
     if exact:

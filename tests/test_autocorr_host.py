@@ -14,8 +14,7 @@ import pytest
 from ogl_beamforming_amd import lib
 from ogl_beamforming_amd import params as P
 from tests import autocorr_ref as ref
-from tests.test_gpu_autocorr import CASES
-from tests.test_gpu_ensemble import GRIDS, weights
+from tests.ring_frames import AUTOCORR_CASES as CASES, GRIDS, weights
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E = P.LibError

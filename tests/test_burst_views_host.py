@@ -12,7 +12,7 @@ import pytest
 from ogl_beamforming_amd import lib
 from ogl_beamforming_amd import params as P
 from tests import cases
-from tests.test_views_host import mixed_views, patches, push_parameters
+from tests.das_push import mixed_views, patches, push_parameters
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E = P.LibError

@@ -289,7 +289,7 @@ def test_a_push_that_fails_leaves_no_stale_last_frame(bflib):
     Every reader of "the newest frame" -- get_last_frames, the frame info, the timings, min/max, the rolling sum, the display reduction --
     then FAILS instead of serving the record that sat in the same ring slot BeamformerMaxBacklogFrames pushes ago (or returning
     success with the caller's buffer unwritten); the next good push is served normally and older good frames stay exportable."""
-    from tests.test_hilbert import acquisitions
+    from tests.stage_checks import acquisitions
     L = bflib.library()
     L.beamformer_set_global_timeout(0xFFFFFFFF)
     good = cases.make("rca_cubic_real")

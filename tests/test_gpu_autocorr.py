@@ -7,9 +7,6 @@ of a float32 fmaf chain of 2N terms over products of the filtered samples, plus 
 sum.  Ids, grids, kinds, tags, the zeros the definition promises and the finite masks are asked exactly.  Every test prints what it
 measured -- the worst error as a share of its bound -- before it asserts."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,106 +16,13 @@ from ogl_beamforming_amd import params as P
 from tests import autocorr_ref as ref
 from tests import frame_peaks_ref
 from tests import variants_cases as vc
-from tests.test_gpu_ensemble import block, ensemble, loop_case, newest_id, rf_frames, weights
-from tests.test_gpu_frame_metrics import newest_info
-from tests.test_gpu_frame_peaks import check_call
+from tests.frame_info import newest_id, newest_info
+from tests.ring_frames import (block, burst_info_unchanged, AUTOCORR_CASES as CASES, check_autocorr, check_peaks as check_call, ensemble, finite_of,
+                               loop_case, rf_frames, share_of_bound, weights)
+from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-D = P.DataKind
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
-
-
-def parts(a):
-    """the floats of an array of frames as (real parts, imaginary parts or None)"""
-    return (a.real, a.imag) if np.iscomplexobj(a) else (a, None)
-
-
-def share_of_bound(got, expected, bound, finite):
-    """the worst |got - expected| / bound over the finite voxels of every lag, real and imaginary parts (lag 0's imaginary part, exact
-    by definition, is left out): (worst share, every float within its bound)"""
-    worst, inside = 0.0, True
-    for lag in range(len(got)):
-        for which, (g, x) in enumerate(zip(parts(got[lag]), parts(expected[lag]))):
-            if g is None or (which == 1 and lag == 0):
-                continue
-            f = finite[lag]
-            over = np.abs(g[f].astype(np.float64) - x[f])
-            if over.size:
-                worst = max(worst, float((over / np.maximum(bound[lag][f], 1e-300)).max()))
-                inside = inside and bool((over <= bound[lag][f]).all())
-    return worst, inside
-
-
-def burst_info_unchanged(after, before):
-    """the newest burst's info behind the outputs: what the library keeps -- the route, the ids, the stage kinds -- equal byte for byte.
-    The stage times are not kept: every call asks the runtime again for the time between the same two events, and the runtime converts
-    device ticks to nanoseconds with a calibration it renews as it runs, so two answers may differ by nanoseconds; they are asked to
-    within a microsecond."""
-    times = P.HipBurstInfo.stage_ms.offset
-    a, b = bytes(after), bytes(before)
-    moved = max(abs(x - y) for x, y in zip(list(after.stage_ms) + [after.burst_ms], list(before.stage_ms) + [before.burst_ms]))
-    print(f"  burst info behind the outputs: stage times moved by {moved * 1e6:.1f} ns at the most")
-    assert a[:times] == b[:times] and len(a) == len(b) == P.HipBurstInfo.burst_ms.offset + 4
-    assert moved <= 1e-3
-
-
-def finite_of(a):
-    return np.isfinite(a.real) & np.isfinite(a.imag) if np.iscomplexobj(a) else np.isfinite(a)
-
-
-def check_autocorr(which, frames, ids, W, lags, tag=0, what="", factor=1.0, expected=None):
-    """autocorrelate the len(frames) newest frames under W (None: the identity form) and check the outputs and their records; returns
-    (outputs, first id).  expected: (values, bound) other than the reference's on `frames`; factor: the multiple of the bound asked."""
-    acq = block(which)
-    K = len(frames)
-    real = not np.iscomplexobj(frames)
-    source_block = int(bf.frame_info(ids[-1]).parameter_block)
-    first, ms = bf.autocorrelate_last_frames(K, W, lags, tag=tag)
-    out = bf.get_last_frames(acq.bp, lags).copy()
-    values, bound = expected if expected is not None else ref.autocorrelate(list(frames), W, lags)
-    finite = finite_of(values)
-    worst, inside = share_of_bound(out, values, factor * bound, finite)
-    rows = K if W is None else W.shape[0]
-    print(f"  {what}: K {K}, rows {rows}{' (identity)' if W is None else ''}, lags {lags}, {'real' if real else 'complex'} {frames.shape[1:]}: "
-          f"worst error {worst:.4f} of its bound, {int((~finite).sum())} non-finite, {ms * 1e3:.1f} us")
-    assert out.shape == (lags,) + frames.shape[1:] and out.dtype == frames.dtype and ms > 0
-    assert inside
-    # a voxel that is not finite in some source is not finite in every output, lag 0's imaginary part included
-    assert np.array_equal(finite_of(out), finite)
-    if not real:
-        assert np.array_equal(np.isfinite(out[0].imag), finite[0])
-        assert not out[0].imag.view(np.uint32)[finite[0]].any()                      # exactly +0: no bit set
-    assert (out[0].real[finite[0]] >= 0).all()
-    # the records: consecutive ids behind the sources, the grid, the kind, the tag, the newest source's block
-    assert first == ids[-1] + 1 and int(newest_info(bf.library()).frame_id) == first + lags - 1
-    scores, _ = bf.score_last_frames(lags)
-    pz, py, px = frames.shape[1:]
-    for j in range(lags):
-        info = bf.frame_info(first + j)
-        assert (int(info.frame_id), tuple(info.points), int(info.parameter_block)) == (first + j, (px, py, pz), source_block)
-        assert int(info.data_kind) == int(D.Float32 if real else D.Float32Complex)
-        assert (int(scores[j].frame_id), int(scores[j].image_plane_tag), int(scores[j].parameter_block)) == (first + j, tag, source_block)
-    # their rows of the timing table: no stages, no DAS voxels
-    t = P.HipFrameTimings()
-    assert bf.library().beamformer_hip_get_last_frame_timings(C.byref(t)) and t.stage_count == 0 and t.das_voxels == 0
-    # a source frame is still served by its id
-    assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))
-    return out, first
-
-
-# (K, rows, lags): one row; a ragged tile of three; a tile boundary at row 16 with all three carried rows in use; one full tile; two
-# full tiles and one row; more than 64 frames and a ragged fifth tile
-CASES = [(1, 1, 1), (3, 3, 3), (5, 17, 4), (17, 16, 4), (17, 33, 2), (65, 65, 4)]
 
 
 @pytest.mark.parametrize("K,rows,lags", CASES)
@@ -306,24 +210,13 @@ def test_refusals(bflib):
 def test_several_devices_are_refused(bflib):
     L = bflib.library()
     acq = vc.separable_volume()
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq):
         refused(L, 1, None, 1, 1, E.InvalidAccess)
         refused(L, 1, np.ones((1, 1), np.complex64), 1, 1, E.InvalidAccess)
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     frames, ids = ensemble("plane", 2)
     check_autocorr("plane", frames, ids, None, 2, what="one device again")
 
 
 def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/autocorr_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "autocorr_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "refused" in run.stdout and "wrapped" in run.stdout, run.stdout
+    run_ring_worker("autocorr_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

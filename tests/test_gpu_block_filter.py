@@ -1,6 +1,6 @@
 """The block-wise ensemble filter on the device (beamformer_hip_gram_boxes_last_frames, beamformer_hip_mix_field_last_frames;
 csrc/ensemble_blocks.hip) and the loop burst -> lattice_boxes -> gram_boxes -> projector a box -> mix_field.  The grids and the pushes
-are tests/test_gpu_ensemble.py's.
+are the ensemble tests' (tests/ring_frames.py).
 
 Gram boxes: every matrix and every info is compared BIT FOR BIT with beamformer_hip_gram_last_frames on the same frames and the same
 box -- that call's own parity is tests/test_gpu_ensemble.py's business.  Field mix: every voxel of every output is compared BIT FOR BIT
@@ -19,9 +19,9 @@ from tests import block_filter_ref as ref
 from tests import ensemble_ref
 from tests import planted
 from tests import variants_cases as vc
-from tests.test_gpu_ensemble import BOXES, GRIDS, block, ensemble, newest_id, rf_frames, weights
-from tests.test_gpu_frame_metrics import newest_info, region_of
-from tests.test_gpu_frame_peaks import check_call
+from tests.frame_info import newest_id, newest_info
+from tests.ring_frames import block, BOXES, check_peaks as check_call, ensemble, GRIDS, region_of, rf_frames, same_as_singles, singles, weights
+from tests.scaffold import automatic_path, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
@@ -30,12 +30,8 @@ U3 = C.c_uint32 * 3
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def hooks_cleared(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.set_hook("GRAM_BOXES_BUDGET", None)
     bflib.set_hook("BLEND_SHAPE", None)
 
@@ -73,16 +69,6 @@ def batches_under(boxes, K, budget):
             count, held = count + 1, 0
         held += need
     return count
-
-
-def singles(K, boxes):
-    return [bf.gram_last_frames(K, region_of(box))[:2] for box in boxes]
-
-
-def same_as_singles(got, infos, want, what):
-    for n, (G, info) in enumerate(want):
-        assert got[n].tobytes() == G.tobytes(), f"{what}: the matrix of box {n}"
-        assert bytes(infos[n]) == bytes(info), f"{what}: the info of box {n}"
 
 
 @pytest.mark.parametrize("K", [1, 2, 17, 33, 65])
@@ -385,16 +371,9 @@ def test_several_devices_are_refused(bflib):
     L = bflib.library()
     acq = vc.separable_volume()
     lattice = LATTICES["one"]
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq):
         mix_field_refused(L, 1, np.ones((1, 1, 1, 1, 1), np.complex64), lattice, E.InvalidAccess)
         gram_boxes_refused(L, 1, [bflib.frame_region((0, 0, 0), (1, 1, 1))], E.InvalidAccess)
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     out, _, _, _ = field_mix("plane", 2, node_weights(lattice, 1, 2, 8700), lattice)
     assert np.isfinite(out.view(np.float32)).all()
 

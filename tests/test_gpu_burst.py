@@ -8,10 +8,7 @@ general kernel for every frame), where the burst kernel takes it -- the nearest 
 where the per-frame route must meet the same checks."""
 import ctypes as C
 import dataclasses
-import os
 import statistics
-import subprocess
-import sys
 import time
 
 import numpy as np
@@ -20,12 +17,12 @@ import pytest
 from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import params as P
 from tests import cases, draws
-from tests.test_gpu_parity import compare, reference
+from tests.das_push import check_burst, compare, I, noise_frames, row_end_case, same_bits, single_push
+from tests.parity import reference
+from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-I = P.InterpolationMode
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BURST_KERNEL_CASES = ["config1_small", "rca_flash_none_tx", "rca_nearest_real", "rca_cubic_real", "rca_f32_complex_in", "rca_i16_complex_in",
                       "rca_f32_demod", "rca_shuffled_padded", "rca_a1s2"]
@@ -34,100 +31,6 @@ FALLBACK_CASES = ["forces", "hercules_wide_cw", "rca_staged_auto", "config5_lite
 # tests/draws.py draw(): the first 30 seeds whose draw is of the RCA family with at most two transmits and a non-empty image
 # (checked again in the test)
 RCA_SEEDS = [0, 6, 8, 16, 27, 36, 39, 43, 44, 54, 56, 57, 58, 59, 61, 75, 80, 81, 82, 87, 90, 91, 96, 105, 107, 115, 124, 127, 129, 134]
-
-
-def row_end_case(interp):
-    """A two-transmit RCA plane of real f32 samples whose 256-sample rows end inside the image (the deepest voxels ask for sample
-    290): it takes the burst kernel, and -- found by a scan of the depth range on the CPU -- the float oracle and its double twin
-    keep or drop a row-end term differently at one or two of its voxels (parity.py's flip set)."""
-    j = {I.Linear: 29, I.Cubic: 68}[interp]
-    return cfg.rca(f"burst_row_ends_{interp.name.lower()}", 24, 2, 256, (96, 1, 96), (-3e-3, 0, 5e-3), (3e-3, 0, 9.0e-3 + j * 37e-6),
-                   seed=900 + j, interp=interp, demodulate=False, data_kind=P.DataKind.Float32, f_number=1.0, angles=np.array([-6.0, 6.0]))
-
-
-def noise_frames(acq, n, seed):
-    rng = np.random.default_rng(seed)
-    shape = (n,) + acq.rf.shape
-    if acq.rf.dtype.kind == "i":
-        return np.clip(np.rint(rng.normal(0, 1000.0, shape)), -32000, 32000).astype(acq.rf.dtype)
-    return rng.normal(0, 1.0, shape).astype(acq.rf.dtype)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def single_push(bflib, acq, rf):
-    rf = np.ascontiguousarray(rf)
-    assert bflib.library().beamformer_push_data_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, 0, 0), bflib.last_error()
-    return bflib.get_last_frame(acq.bp).copy()
-
-
-def close_to_single_push(oracle, acq, rf, one, frame, k):
-    """a burst's frame `frame` against the single push `one` of the same RF, where another DAS kernel computed it (the burst kernel):
-    within the case's tolerance of the frame maximum"""
-    assert np.array_equal(np.isnan(one), np.isnan(frame))
-    ok = ~np.isnan(one)
-    scale = np.abs(one[ok]).max()
-    slack = cases.tolerance(acq) * scale
-    if acq.bp.interpolation_mode == int(I.Nearest):
-        # a tap within float rounding of k + 1/2 may fall either way in either kernel: the oracle's per-voxel budget, once each
-        flags = {}
-        oracle.beamform(acq.bp, rf, acq.filters, flags=flags)
-        slack = slack + 2.02 * flags["budget"][ok]
-    err = np.abs(one[ok] - frame[ok])
-    assert (err <= slack).all(), f"frame {k}: burst and single push differ by {err.max() / scale:.3e} of the frame maximum"
-
-
-def check_burst(bflib, oracle, acq, n, seed, expect_kernel, against_single=True):
-    """one burst of n noise frames: parity of every frame, pairwise different frames, frame k belongs to RF k, the route the library
-    reports, and every frame against the single push of the same RF.  Returns (frames, RF)."""
-    L = bflib.library()
-    rf = noise_frames(acq, n, seed)
-    described = bflib.describe_burst(acq.bp, n, acq.filters)
-    assert bool(described.burst_kernel) == expect_kernel, described.reason
-    gpu = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
-    info = bflib.last_burst_info()
-    assert info.frame_count == n and bool(info.route.burst_kernel) == expect_kernel, info.route.reason
-    assert info.route.das_launches == described.das_launches and info.route.single_path == described.single_path
-    if expect_kernel:
-        assert info.route.das_launches == 1 and info.route.frames_per_thread == 4
-    frame_info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(frame_info)) and frame_info.frame_id == info.first_frame_id + n - 1
-    assert gpu.shape[0] == n
-    worst = 0.0
-    for k in range(n):
-        acq_k = dataclasses.replace(acq, rf=rf[k])
-        ref, pairs, flags = reference(oracle, acq_k)
-        v = compare(gpu[k], ref, acq_k, flags, label=f"{acq.name}/burst{n}/{k}")
-        worst = max(worst, v.max_rel_err)
-    print(f"{acq.name}: burst of {n} on the {'burst kernel' if expect_kernel else 'per-frame route'}: worst max_rel_err {worst:.3e}")
-    for a in range(n):
-        for b in range(a + 1, n):
-            assert not np.array_equal(gpu[a], gpu[b], equal_nan=True), (a, b)
-    # the order: the same frames permuted come back permuted, bit for bit (a frame's bits do not depend on its slot in the burst)
-    perm = np.random.default_rng(seed + 1).permutation(n)
-    again = bflib.beamform_burst(acq.bp, rf[perm], acq.filters)
-    for i in range(n):
-        assert same_bits(again[i], gpu[perm[i]]), f"frame {i} of the permuted burst is not the frame of RF {perm[i]}"
-    if against_single:
-        identical = 0
-        for k in range(n):
-            one = single_push(bflib, acq, rf[k])
-            close_to_single_push(oracle, acq, rf[k], one, gpu[k], k)
-            identical += same_bits(one, gpu[k])
-        if expect_kernel:
-            print(f"{acq.name}: {identical} of {n} frames of the burst equal their single push bit for bit")
-    return gpu, rf
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
 
 
 @pytest.mark.parametrize("n", [5, 9])
@@ -228,10 +131,7 @@ def test_device_resident_bursts_equal_host_bursts(name, bflib):
 
 def test_a_burst_that_wraps_the_ring_stays_exportable():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/burst_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "burst_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "wrapped" in run.stdout, run.stdout
+    run_ring_worker("burst_wrap_worker", 1 << 20, expect=("wrapped",), timeout=600)
 
 
 def test_timings_of_a_burst_are_per_frame_shares(bflib):

@@ -10,9 +10,6 @@ frame must be the single push of RF k on the block with that grid, bit for bit. 
 tests/test_gpu_views.py."""
 import ctypes as C
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,27 +17,16 @@ import pytest
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import cases
-from tests.test_gpu_burst import close_to_single_push, noise_frames, row_end_case, same_bits, single_push
-from tests.test_gpu_parity import compare, reference
-from tests.test_gpu_views import DISPATCH_CASES, KERNEL_CASES, box, case_of, inner, kernel_views, mode_for, on_grid, per_view_views
+from tests.das_push import (box, case_of, close_to_single_push, compare, DISPATCH_CASES, four_views, I, inner, KERNEL_CASES, mode_for, noise_frames,
+                            on_grid, per_view_views, row_end_case, same_bits, single_push)
+from tests.parity import reference
+from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-I = P.InterpolationMode
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NO_BURST, NO_VIEWS, FAIL_DAS = P.HIP_DAS_PATH_NO_BURST_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL, P.HIP_DAS_PATH_FAIL_VIEWS_DAS
 PER_VIEW_CASES = ["forces", "hercules_wide_cw", "rca_staged_auto"]
 N = 5
-
-
-def four_views(acq):
-    """of tests/test_gpu_views.py's kernel_views: less than a tile (5 x 1 x 7), ragged tiles (33 x 1 x 17), a small volume (9 x 6 x 5)
-    and the case's own grid.  Nearest interpolation keeps that helper's own filter (views of at least the case's voxel count), so that
-    compare()'s outlier share is met by the reference alone."""
-    views = kernel_views(acq)
-    if acq.bp.interpolation_mode == int(I.Nearest):
-        return views[:4]
-    return [views[1], views[2], views[3], views[5]]
 
 
 @functools.lru_cache(maxsize=None)
@@ -71,15 +57,6 @@ def prepared(name, which="kernel"):
             row.append((acq_vk,) + tuple(reference(binding, acq_vk)))
         refs.append(row)
     return acq, rf, views, refs
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
 
 
 def check_parity(name, frames, refs, what):
@@ -216,7 +193,7 @@ def test_blocks_no_views_kernel_takes_run_every_frame_as_its_single_push(name, b
 
 def test_a_mixed_push(bflib):
     """views the fused kernel takes and views it does not: the others are their single push bit for bit, per RF frame"""
-    from tests.test_views_host import mixed_views
+    from tests.das_push import mixed_views
     acq = cases.make("rca_flash_none_tx")
     rf = noise_frames(acq, N, 6200)
     views = mixed_views(acq)
@@ -370,10 +347,7 @@ def test_device_resident_rf_equals_host_rf(bflib):
 
 def test_a_run_that_wraps_the_ring_starts_again_at_0():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/burst_views_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "burst_views_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "wrapped" in run.stdout, run.stdout
+    run_ring_worker("burst_views_wrap_worker", 1 << 20, expect=("wrapped",), timeout=600)
 
 
 @pytest.mark.parametrize("flag", [0, NO_BURST, NO_VIEWS], ids=["rung1", "rung2", "rung3"])

@@ -13,7 +13,8 @@ import pytest
 
 from ogl_beamforming_amd import params as P
 from tests import cases, draws, parity, twins
-from tests.test_gpu_parity import FACTORED, HERCULES, SEPARABLE, STAGED, TILE, last_timings
+from tests.das_kernel_cases import FACTORED, HERCULES, SEPARABLE, STAGED, TILE
+from tests.das_push import last_timings
 
 pytestmark = pytest.mark.gpu
 

@@ -9,92 +9,21 @@ parts of an entry.  Mix: an output float is a float32 fmaf chain of 2K terms: (2
 Counts, ids, grids, the Hermitian mirror and every zero the definition promises are asked exactly.  Every test prints what it measured
 before it asserts."""
 import ctypes as C
-import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import ensemble_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import block as metrics_block, newest_info, region_of
-from tests.test_gpu_frame_peaks import check_call
+from tests.frame_info import newest_id, newest_info
+from tests.ring_frames import (block, BOXES, check_peaks as check_call, check_gram, check_mix, ensemble, GRIDS, loop_case, LOOP_POINTS, metrics_block,
+                               region_of, rf_frames, weights)
+from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-D = P.DataKind
-GRIDS = {"plane": ((33, 1, 7), vc.LO, vc.HI, True), "square": ((64, 1, 64), vc.LO, vc.HI, True),
-         "volume": ((9, 5, 6), vc.LO3, vc.HI3, True), "real": ((33, 1, 7), vc.LO, vc.HI, False)}
-# boxes with odd offsets and odd extents: no multiple of a mask word, rows that are no whole lines
-BOXES = {"plane": ((1, 0, 1), (29, 1, 5)), "square": ((3, 0, 5), (57, 1, 51)), "volume": ((1, 1, 1), (7, 3, 5)), "real": ((5, 0, 3), (27, 1, 3))}
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
-
-
-@functools.lru_cache(maxsize=None)
-def block(which):
-    """16 channels x 2 plane waves of float32 RF straight into DAS on the grid `which` names; "nan": the coherency-weighted plane of the
-    frame metrics tests, which leaves NaN where no term passed"""
-    if which == "nan":
-        return metrics_block("D")
-    points, lo, hi, iq = GRIDS[which]
-    return cfg.rca("ensemble_" + which, 16, 2, 256, points, lo, hi, seed=7500, interp=P.InterpolationMode.Linear, demodulate=False,
-                   data_kind=D.Float32Complex if iq else D.Float32, angles=np.array([-6.0, 6.0]), kind=P.AcquisitionKind.RCA_TPW)
-
-
-@functools.lru_cache(maxsize=None)
-def rf_frames(which, K):
-    acq = block(which)
-    rng = np.random.default_rng(7600 + K)
-    return rng.normal(0.0, 1.0, (K,) + acq.rf.shape).astype(acq.rf.dtype)
-
-
-def ensemble(which, K):
-    """K frames of the grid by one burst push (one: a single push): (frames (K, Z, Y, X), their ids)"""
-    acq, rf = block(which), rf_frames(which, K)
-    if K == 1:
-        frames = bf.beamform(acq.bp, rf[0], acq.filters).copy()[None]
-    else:
-        frames = bf.beamform_burst(acq.bp, rf, acq.filters).copy()
-    newest = int(newest_info(bf.library()).frame_id)
-    return frames, list(range(newest - K + 1, newest + 1))
-
-
-def check_gram(frames, ids, box=None, what=""):
-    K = len(frames)
-    real = not np.iscomplexobj(frames)
-    G, info, ms = bf.gram_last_frames(K, region_of(box))
-    expected, voxels, non_finite, bound = ref.gram(list(frames), box)
-    pz, py, px = frames[0].shape
-    over = np.maximum(np.abs(G.real - expected.real), np.abs(G.imag - expected.imag))
-    worst = float((over / np.maximum(bound, 1e-300)).max()) if voxels else 0.0
-    print(f"  {what}: K {K} {(px, py, pz)} {'real' if real else 'complex'} box {box}: voxels {int(info.voxels)} ({voxels}), non-finite "
-          f"{int(info.non_finite)} ({non_finite}), worst error {over.max():.3e} = {worst:.3f} of its bound, {ms * 1e3:.1f} us")
-    assert G.shape == (K, K) and G.dtype == np.complex128 and ms > 0
-    assert (int(info.count), int(info.data_kind)) == (K, int(D.Float32 if real else D.Float32Complex))
-    assert tuple(info.points) == (px, py, pz) and int(info.first_frame_id) == ids[0]
-    assert tuple(info.region_first) == (tuple(box[0]) if box else (0, 0, 0)) and tuple(info.region_count) == (tuple(box[1]) if box else (px, py, pz))
-    assert (int(info.voxels), int(info.non_finite)) == (voxels, non_finite)
-    # the mirror: equal real parts bit for bit, opposite imaginary parts, a real diagonal
-    assert np.array_equal(G.real.view(np.uint64), G.real.T.copy().view(np.uint64))
-    assert np.array_equal(G.imag, -G.imag.T) and not np.diagonal(G).imag.any()
-    if real:
-        assert not G.imag.any()
-    assert (over <= bound).all()
-    return G, bound
 
 
 @pytest.mark.parametrize("K", [1, 2, 3, 17, 65])
@@ -143,51 +72,6 @@ def test_gram_of_the_octants_sums_to_the_whole(bflib):
 
 # ---- mix ----
 
-def weights(M, K, seed, real=False):
-    rng = np.random.default_rng(seed)
-    if real:
-        return rng.standard_normal((M, K)).astype(np.float32).astype(np.complex64)
-    return (rng.standard_normal((M, K)) + 1j * rng.standard_normal((M, K))).astype(np.complex64)
-
-
-def check_mix(which, frames, ids, W, tag=0, what=""):
-    """mix the len(frames) newest frames under W and check the outputs and their records; returns (outputs, first id)"""
-    acq = block(which)
-    K, M = len(frames), W.shape[0]
-    real = not np.iscomplexobj(frames)
-    source_block = int(bf.frame_info(ids[-1]).parameter_block)
-    first, ms = bf.mix_last_frames(K, W, tag=tag)
-    out = bf.get_last_frames(acq.bp, M).copy()
-    expected, bound = ref.mix(list(frames), W)
-    finite = np.isfinite(expected.real) & np.isfinite(expected.imag) if not real else np.isfinite(expected)
-    if real:
-        over = np.abs(out.astype(np.float64) - expected)
-    else:
-        over = np.maximum(np.abs(out.real.astype(np.float64) - expected.real), np.abs(out.imag.astype(np.float64) - expected.imag))
-    ratio = np.where(finite, over / np.maximum(bound, 1e-300), 0.0)
-    print(f"  {what}: K {K} -> M {M} {'real' if real else 'complex'}: worst error {np.where(finite, over, 0).max():.3e} = {ratio.max():.3f} of its bound, "
-          f"{int((~finite).sum())} non-finite, {ms * 1e3:.1f} us")
-    assert out.shape == (M,) + frames.shape[1:] and out.dtype == frames.dtype and ms > 0
-    assert (over[finite] <= bound[finite]).all()
-    # a voxel that is not finite in some input is not finite in every output
-    got_finite = np.isfinite(out.real) & np.isfinite(out.imag) if not real else np.isfinite(out)
-    assert np.array_equal(got_finite, finite)
-    # the records: consecutive ids behind the sources, the grid, the kind, the tag, the newest source's block
-    assert first == ids[-1] + 1 and int(newest_info(bf.library()).frame_id) == first + M - 1
-    rows, _ = bf.score_last_frames(M)
-    pz, py, px = frames.shape[1:]
-    for j in range(M):
-        info = bf.frame_info(first + j)
-        assert (int(info.frame_id), tuple(info.points), int(info.parameter_block)) == (first + j, (px, py, pz), source_block)
-        assert int(info.data_kind) == int(D.Float32 if real else D.Float32Complex)
-        assert (int(rows[j].frame_id), int(rows[j].image_plane_tag), int(rows[j].parameter_block)) == (first + j, tag, source_block)
-    # their rows of the timing table: no stages, no DAS voxels
-    t = P.HipFrameTimings()
-    assert bf.library().beamformer_hip_get_last_frame_timings(C.byref(t)) and t.stage_count == 0 and t.das_voxels == 0
-    # a source frame is still served by its id
-    assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))
-    return out, first
-
 
 @pytest.mark.parametrize("K,M", [(1, 1), (3, 3), (17, 5), (5, 17), (65, 65)])
 def test_mix_of_a_burst(K, M, bflib):
@@ -234,21 +118,6 @@ def test_mix_by_a_permutation_by_zero_and_over_nan_voxels(bflib):
 
 # ---- the loop: burst -> gram -> projector -> mix -> peaks -> views ----
 
-LOOP_POINTS = (32, 1, 48)
-
-
-@functools.lru_cache(maxsize=None)
-def loop_case():
-    """8 RF frames a_k R0 + b_k R1 of two seeded float32 RF frames, |a| 100 times |b|: a strong common component (tissue) and a weak one"""
-    acq = cfg.rca("ensemble_loop", 16, 2, 256, LOOP_POINTS, vc.LO, vc.HI, seed=7900, interp=P.InterpolationMode.Linear, demodulate=False,
-                  data_kind=D.Float32Complex, angles=np.array([-6.0, 6.0]), kind=P.AcquisitionKind.RCA_TPW)
-    rng = np.random.default_rng(7901)
-    r0, r1 = (rng.normal(0.0, 1.0, acq.rf.shape).astype(np.float32) for _ in range(2))
-    a = 10.0 * (1.0 + 0.05 * np.cos(np.arange(8)))
-    b = 0.1 * np.array([1, -1, 1, 1, -1, -1, 1, -1], np.float64)
-    rf = np.stack([(a[k] * r0 + b[k] * r1).astype(np.float32) for k in range(8)])
-    return acq, rf
-
 
 def test_the_clutter_filter_loop(bflib):
     acq, rf = loop_case()
@@ -281,11 +150,6 @@ def test_the_clutter_filter_loop(bflib):
 
 
 # ---- refusals that need a device ----
-
-def newest_id(L):
-    """the newest frame's id; None while the newest push is a tombstone"""
-    info = P.HipFrameInfo()
-    return int(info.frame_id) if L.beamformer_hip_get_last_frame_info(C.byref(info)) else None
 
 
 def refused_both(L, K, kind, region=None):
@@ -342,22 +206,12 @@ def test_refusals(bflib):
 def test_several_devices_are_refused(bflib):
     L = bflib.library()
     acq = vc.separable_volume()
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq):
         refused_both(L, 1, E.InvalidAccess)
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     frames, ids = ensemble("plane", 2)
     check_gram(frames, ids, what="one device again")
 
 
 def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/ensemble_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ensemble_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "refused" in run.stdout, run.stdout
+    run_ring_worker("ensemble_wrap_worker", 1 << 20, expect=("refused",))

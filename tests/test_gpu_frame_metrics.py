@@ -10,108 +10,20 @@ accumulation adding about n x 2^-53.  The perturbation of a sum G of (a - b)^2 u
 1e-6 sqrt(G S2): the bar is twice that, plus 1e-12 S2.  On real frames fabsf is exact and only the order of the double additions differs:
 1e-12 relative.  Every test prints what it measured before it asserts."""
 import ctypes as C
-import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import configs as cfg
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import frame_metrics_ref as ref
 from tests import variants_cases as vc
+from tests.frame_info import newest_info
+from tests.ring_frames import BOX, metrics_block as block, check_row, region_of, variants_push
+from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
 S = P.FrameScore
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BOX = ((3, 2, 1), (10, 13, 30))            # 3900 voxels of 16 x 16 x 32: no multiple of a wave or a block, all three gradients cut
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
-
-
-@functools.lru_cache(maxsize=None)
-def block(which):
-    """the acquisitions of the blocks A .. D, built once"""
-    if which == "A":
-        return vc.block("linear", iq=True, cw=False)
-    if which == "B":
-        return vc.block("linear", iq=False, cw=False)
-    if which == "C":
-        return vc.separable_volume()
-    if which == "forces":
-        return vc.forces_block()
-    points, lo, hi = {"D": ((24, 1, 40), (-6e-3, 0, 0.2e-3), (6e-3, 0, 5.5e-3)),
-                      "D3": ((16, 16, 32), (-12e-3, -12e-3, 0.5e-3), (12e-3, 12e-3, 5.5e-3))}[which]
-    return cfg.rca("frame_metrics_nan_" + which, 16, 2, 256, points, lo, hi, seed=7300, interp=P.InterpolationMode.Linear, cw=True,
-                   demodulate=False, data_kind=P.DataKind.Float32Complex, angles=np.array([-6.0, 6.0]), kind=P.AcquisitionKind.RCA_TPW)
-
-
-def newest_info(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
-
-
-def variants_push(which):
-    """a variants push of the block under variants_cases.candidates: (frames (3, Z, Y, X), their ids)"""
-    acq = block(which)
-    frames = bf.beamform_variants(acq.bp, acq.rf, vc.candidates(acq.bp), acq.filters).copy()
-    newest = int(newest_info(bf.library()).frame_id)
-    return frames, [newest - 2, newest - 1, newest]
-
-
-def region_of(box):
-    return None if box is None else bf.frame_region(*box)
-
-
-def within(got, expected, bar, what):
-    print(f"    {what}: {got!r} against {expected!r}, off by {abs(got - expected):.3e} (bar {bar:.3e})")
-    assert abs(got - expected) <= bar, what
-
-
-def check_row(row, frame, box=None, what=""):
-    """one row against the reference applied to the downloaded frame"""
-    real = not np.iscomplexobj(frame)
-    r = ref.metrics(frame, *(box if box else (None, None)))
-    print(f"  {what}: frame {int(row.frame_id)} {tuple(row.points)} {'real' if real else 'complex'} box {r['region_first']} + {r['region_count']}")
-    # identity: the record's
-    info = bf.frame_info(int(row.frame_id))
-    assert tuple(row.points) == tuple(info.points) == r["points"] and row.data_kind == info.data_kind
-    assert row.data_kind == int(P.DataKind.Float32 if real else P.DataKind.Float32Complex) and row.parameter_block == info.parameter_block
-    assert tuple(row.region_first) == r["region_first"] and tuple(row.region_count) == r["region_count"] and row.reserved == 0
-    # counts: exact
-    assert (int(row.voxels), int(row.non_finite), [int(n) for n in row.gradient_pairs]) == (r["voxels"], r["non_finite"], r["gradient_pairs"])
-    assert row.voxels + row.non_finite == int(np.prod(r["region_count"]))
-    # sums
-    s2 = r["sum_abs2"]
-    for name, bar in (("sum_abs", 1e-6), ("sum_abs2", 2e-6), ("sum_abs4", 4e-6)):
-        within(getattr(row, name), r[name], (1e-12 if real else bar) * r[name], name)
-    for axis in range(3):
-        bar = 1e-12 * r["gradient2"][axis] if real else 2e-6 * np.sqrt(r["gradient2"][axis] * s2) + 1e-12 * s2
-        within(row.gradient2[axis], r["gradient2"][axis], bar, f"gradient2[{axis}]")
-    # the maximum
-    within(float(row.max_abs), r["max_abs"], 3e-7 * r["max_abs"], "max_abs")
-    index = tuple(int(v) for v in row.max_index)
-    if real or not r["voxels"]:
-        assert index == r["max_index"], (index, r["max_index"])
-    else:
-        local = tuple(i - f for i, f in zip(index, r["region_first"]))
-        assert all(0 <= i < c for i, c in zip(local, r["region_count"])), index
-        at = float(r["magnitude"][local[2], local[1], local[0]])
-        print(f"    max_index {index} (reference {r['max_index']}): reference magnitude there {at!r}")
-        assert at >= r["max_abs"] * (1 - 3e-7)
-    return r
 
 
 def test_block_a_three_variants_of_a_complex_plane(bflib):
@@ -289,11 +201,8 @@ def test_several_devices_are_refused(bflib):
     z-slabs: the single push is served, scoring and the by-id calls are InvalidAccess"""
     L = bflib.library()
     acq = block("C")
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        frame = bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert frame.shape == (32, 16, 16) and L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq) as frame:
+        assert frame.shape == (32, 16, 16)
         out = (P.HipFrameMetrics * 1)()
         untouched = bytes(out)
         assert not L.beamformer_hip_score_last_frames(1, None, out, None) and bflib.last_error()[0] == E.InvalidAccess and bytes(out) == untouched
@@ -302,9 +211,6 @@ def test_several_devices_are_refused(bflib):
         assert not L.beamformer_hip_copy_frame(newest, raw.ctypes.data_as(C.c_void_p), raw.nbytes) and bflib.last_error()[0] == E.InvalidAccess
         assert not L.beamformer_hip_get_frame_info(newest, C.byref(P.HipFrameInfo())) and bflib.last_error()[0] == E.InvalidAccess
         assert not raw.any()
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     # and one device again scores
     single = bflib.beamform(acq.bp, acq.rf, acq.filters).copy()
     rows, _ = bflib.score_last_frames(1)
@@ -358,7 +264,4 @@ def test_the_autofocus_loop(bflib):
 
 def test_storage_that_a_newer_frame_reused():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/frame_metrics_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "frame_metrics_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "reused" in run.stdout, run.stdout
+    run_ring_worker("frame_metrics_wrap_worker", 1 << 20, expect=("reused",))

@@ -13,26 +13,19 @@ import pytest
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import localisation_ref
-from tests import test_gpu_block_filter as boxes_tests
-from tests import test_gpu_ensemble as ensemble_tests
-from tests import test_gpu_frame_metrics as metrics_tests
-from tests import test_gpu_frame_peaks as peaks_tests
-from tests import test_gpu_frame_quantiles as quantiles_tests
-from tests import test_gpu_localisation as map_tests
-from tests import test_gpu_motion as motion_tests
-from tests import test_gpu_track_chains as chains_tests
-from tests import test_gpu_track_draw as draw_tests
-from tests import test_gpu_tracks as tracks_tests
+from tests import ring_frames
 from tests import track_chains_ref, track_draw_ref, tracks_ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import newest_info, region_of
+from tests.frame_info import newest_info
+from tests.ring_frames import region_of
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
 K = 4
 # two complex planes through the ensemble tests' own block and burst (their GRIDS, by names of this file's): the tables of the second
 # are larger than everything the first left allocated
-ensemble_tests.GRIDS.update(frame_ops_small=((16, 1, 8), vc.LO, vc.HI, True), frame_ops_large=((64, 1, 32), vc.LO, vc.HI, True))
+ring_frames.GRIDS.update(frame_ops_small=((16, 1, 8), vc.LO, vc.HI, True), frame_ops_large=((64, 1, 32), vc.LO, vc.HI, True))
 MAP_POINTS = (8, 1, 8)
 REGIONS = [((1, 0, 1), (13, 1, 5)), ((3, 0, 3), (13, 1, 5))]        # two boxes for correlate, the second against the small frame's far corner
 SCORE_BOX = ((5, 0, 3), (3, 1, 2))
@@ -41,21 +34,17 @@ BOTH = track_chains_ref.POINTS | track_chains_ref.LINKS
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def maps_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
     bflib.track_map_reset(None)
 
 
 def map_of(which):
     """the 8 x 1 x 8 map over the frames' own box, and the placement of the frames of `which` onto it"""
-    acq = ensemble_tests.block(which)
-    grid = map_tests.map_view(MAP_POINTS, vc.LO, vc.HI)
-    return grid, map_tests.placement_onto(grid, acq.bp.das_voxel_transform, ensemble_tests.GRIDS[which][0])
+    acq = ring_frames.block(which)
+    grid = ring_frames.map_view(MAP_POINTS, vc.LO, vc.HI)
+    return grid, ring_frames.placement_onto(grid, acq.bp.das_voxel_transform, ring_frames.GRIDS[which][0])
 
 
 def the_newer_calls(which, frames, thresholds, A):
@@ -63,42 +52,42 @@ def the_newer_calls(which, frames, thresholds, A):
     three that deposit on fresh maps of MAP_POINTS; returns every call's bytes, and both maps as the draw call leaves them"""
     out = {}
     # quantiles: its own check, then the call's bytes
-    quantiles_tests.ranked(list(frames), quantiles_tests.FRACTIONS)
-    rows, records, tables, _ = bf.quantiles_last_frames(K, quantiles_tests.FRACTIONS, histograms=True)
+    ring_frames.ranked(list(frames), ring_frames.FRACTIONS)
+    rows, records, tables, _ = bf.quantiles_last_frames(K, ring_frames.FRACTIONS, histograms=True)
     out["quantiles"] = bytes(rows), bytes(records), tables.tobytes()
     # gram_boxes, two boxes, against gram one box at a time
-    want = boxes_tests.singles(K, REGIONS)
+    want = ring_frames.singles(K, REGIONS)
     grams, infos, _ = bf.gram_boxes_last_frames(K, [region_of(box) for box in REGIONS])
-    boxes_tests.same_as_singles(grams, infos, want, which)
+    ring_frames.same_as_singles(grams, infos, want, which)
     out["gram_boxes"] = grams.tobytes(), [bytes(i) for i in infos]
     # pair_peaks, depositing
-    records = tracks_tests.records_of(K, thresholds)
+    records = ring_frames.peak_lists(K, thresholds)
     bf.track_map_reset(MAP_POINTS)
-    rows, pairs = tracks_tests.pair(K, thresholds, A, REACH, deposit=True)
+    rows, pairs = ring_frames.pair(K, thresholds, A, REACH, deposit=True)
     counts, sums = tracks_ref.empty_map(MAP_POINTS)
     want, numbers = tracks_ref.pair_records(records, A, REACH, counts=counts, sums=sums)
-    tracks_tests.same_call(rows, pairs, want, numbers, K, thresholds)
-    tracks_tests.same_map(MAP_POINTS, counts, sums)
+    ring_frames.same_pairs_call(rows, pairs, want, numbers, K, thresholds)
+    ring_frames.same_map(MAP_POINTS, counts, sums)
     assert sum(w["pairs"] for w in numbers) >= 1
     out["pairs"] = bytes(rows), pairs.tobytes()
     # track_peaks, min_length 2, both deposits; then without records: the same rows, the maps once more
-    density, counts, sums = chains_tests.fresh_maps(MAP_POINTS)
-    got = chains_tests.track(K, thresholds, A, REACH, 2, deposit=BOTH)
+    density, counts, sums = ring_frames.fresh_maps(MAP_POINTS)
+    got = ring_frames.track(K, thresholds, A, REACH, 2, deposit=BOTH)
     want = track_chains_ref.chain_records(records, A, REACH, 2, True, deposit=BOTH, point_map=density, counts=counts, sums=sums)
-    chains_tests.same_call(got, want, K, thresholds)
-    chains_tests.same_maps(MAP_POINTS, density, counts, sums)
+    ring_frames.same_tracks_call(got, want, K, thresholds)
+    ring_frames.same_maps(MAP_POINTS, density, counts, sums)
     assert len(want["tracks"]) >= 1
-    rows, none, nothing, _ = bf.track_peaks_last_frames(K, thresholds, A, REACH, chains_tests.CAP, 2, deposit=BOTH, records=False)
+    rows, none, nothing, _ = bf.track_peaks_last_frames(K, thresholds, A, REACH, ring_frames.CAP, 2, deposit=BOTH, records=False)
     assert bytes(rows) == bytes(got[0]) and len(none) == 0 and len(nothing) == 0
-    chains_tests.same_maps(MAP_POINTS, 2 * density, 2 * counts, 2 * sums)
+    ring_frames.same_maps(MAP_POINTS, 2 * density, 2 * counts, 2 * sums)
     out["tracks"] = [bytes(v) for v in got]
     # draw_tracks, smooth 1, both deposits; track_map_copy beside localisation_map_copy
-    density, counts, sums = draw_tests.fresh_maps(MAP_POINTS, MAP_POINTS)
-    rows = draw_tests.draw(K, thresholds, A, REACH, 2, 1, deposit=BOTH)
+    density, counts, sums = ring_frames.fresh_point_and_track_maps(MAP_POINTS, MAP_POINTS)
+    rows = ring_frames.draw(K, thresholds, A, REACH, 2, 1, deposit=BOTH)
     want = track_draw_ref.draw_records(records, A, REACH, 2, 1, True, deposit=BOTH, point_map=density, counts=counts, sums=sums)
-    draw_tests.same_rows(rows, want, K, thresholds)
-    point_info, link_info = draw_tests.same_maps(MAP_POINTS, MAP_POINTS, density, counts, sums)
-    draw_tests.same_infos(point_info, link_info, 1, want["rows"], BOTH)
+    ring_frames.same_rows(rows, want, K, thresholds)
+    point_info, link_info = ring_frames.same_point_and_track_maps(MAP_POINTS, MAP_POINTS, density, counts, sums)
+    ring_frames.same_infos(point_info, link_info, 1, want["rows"], BOTH)
     out["drawn"] = bytes(rows)
     out["maps"] = bf.localisation_map_copy(MAP_POINTS)[0].tobytes(), *(v.tobytes() for v in bf.track_map_copy(MAP_POINTS)[:2])
     return out
@@ -106,37 +95,37 @@ def the_newer_calls(which, frames, thresholds, A):
 
 def the_order(which):
     """the calls on the K newest frames, each judged as its own test judges it; returns what a later run can be compared with"""
-    frames, ids = ensemble_tests.ensemble(which, K)
-    assert frames.shape[1:] == ensemble_tests.GRIDS[which][0][::-1] and np.iscomplexobj(frames)
-    thresholds = peaks_tests.fraction_of_max(frames, 0.25)
+    frames, ids = ring_frames.ensemble(which, K)
+    assert frames.shape[1:] == ring_frames.GRIDS[which][0][::-1] and np.iscomplexobj(frames)
+    thresholds = ring_frames.fraction_of_max(frames, 0.25)
     grid, A = map_of(which)
     # 1. score, whole frames
     scored, _ = bf.score_last_frames(K)
     for k in range(K):
-        metrics_tests.check_row(scored[k], frames[k], what=f"{which} {k}")
+        ring_frames.check_row(scored[k], frames[k], what=f"{which} {k}")
     # 2. find_peaks
-    peak_rows, peaks, found = peaks_tests.check_call(list(frames), thresholds, what=which)
+    peak_rows, peaks, found = ring_frames.check_peaks(list(frames), thresholds, what=which)
     assert all(r["found"] >= 2 for r in found)
     # 3. gram
-    G, _ = ensemble_tests.check_gram(frames, ids, what=which)
+    G, _ = ring_frames.check_gram(frames, ids, what=which)
     # 4. correlate, two regions, window (1, 0, 1)
-    table, _, _ = motion_tests.check_call(frames, ids, K // 2, (1, 0, 1), REGIONS, what=which)
+    table, _, _ = ring_frames.check_correlate(frames, ids, K // 2, (1, 0, 1), REGIONS, what=which)
     # 5. accumulate_peaks into the map
-    counts, deposits, info = map_tests.run(grid, frames, thresholds, A)
+    counts, deposits, info = ring_frames.run_localise(grid, frames, thresholds, A)
     expected, numbers = localisation_ref.accumulate(grid.output_points, frames, thresholds, A)
-    map_tests.same(counts, expected)
+    ring_frames.same_localise(counts, expected)
     assert (info.calls, int(info.deposited)) == (1, sum(n["found"] for n in numbers)) and int(counts.sum()) == int(info.deposited) >= K
     # 6. score again, a 3 x 1 x 2 region
     boxed, _ = bf.score_last_frames(K, region_of(SCORE_BOX))
     for k in range(K):
-        metrics_tests.check_row(boxed[k], frames[k], SCORE_BOX, what=f"{which} {k} box")
+        ring_frames.check_row(boxed[k], frames[k], SCORE_BOX, what=f"{which} {k} box")
         assert (boxed[k].frame_id, boxed[k].parameter_block, boxed[k].data_kind, tuple(boxed[k].points)) == \
                (scored[k].frame_id, scored[k].parameter_block, scored[k].data_kind, tuple(scored[k].points))
     # 7. find_peaks again: the bytes of 2.
-    again_rows, again_peaks, _ = peaks_tests.check_call(list(frames), thresholds, what=which + " again")
+    again_rows, again_peaks, _ = ring_frames.check_peaks(list(frames), thresholds, what=which + " again")
     assert bytes(again_rows) == bytes(peak_rows) and bytes(again_peaks) == bytes(peaks)
     # (the deposit rows last: their check asks find_peaks once more)
-    map_tests.check_rows(deposits, numbers, frames, thresholds)
+    ring_frames.check_rows(deposits, numbers, frames, thresholds)
     # 8. the newer calls, and at the end of the walk each of them again: the bytes of its first run
     newer = the_newer_calls(which, frames, thresholds, A)
     assert the_newer_calls(which, frames, thresholds, A) == newer
@@ -167,21 +156,21 @@ def test_the_scratch_grows_from_small_frames_to_large_ones_and_every_call_finds_
 
 def mix_and_score(which, frames, ids):
     """two mixes of the K newest frames queued behind them (the ensemble tests' check), then their metrics rows"""
-    out, first = ensemble_tests.check_mix(which, frames, ids, ensemble_tests.weights(2, K, 7901), tag=3, what=which)
+    out, first = ring_frames.check_mix(which, frames, ids, ring_frames.weights(2, K, 7901), tag=3, what=which)
     rows, _ = bf.score_last_frames(2)
     for j in range(2):
-        metrics_tests.check_row(rows[j], out[j], what=f"{which} mix {j}")
+        ring_frames.check_row(rows[j], out[j], what=f"{which} mix {j}")
         assert (int(rows[j].frame_id), int(rows[j].image_plane_tag)) == (first + j, 3)
     return out, first, rows
 
 
 def test_queued_runs_behind_reduce_calls(bflib):
     which = "frame_ops_small"
-    acq = ensemble_tests.block(which)
-    frames, ids = ensemble_tests.ensemble(which, K)
+    acq = ring_frames.block(which)
+    frames, ids = ring_frames.ensemble(which, K)
     before = bytes(bf.last_burst_info())
     grid, A = map_of(which)
-    counts, _, _ = map_tests.run(grid, frames, peaks_tests.fraction_of_max(frames, 0.25), A)
+    counts, _, _ = ring_frames.run_localise(grid, frames, ring_frames.fraction_of_max(frames, 0.25), A)
     assert len(np.unique(counts)) >= 2
     out, first, _ = mix_and_score(which, frames, ids)
     scale = 0.37
@@ -200,15 +189,15 @@ def test_queued_runs_behind_reduce_calls(bflib):
     # the mixes are still served by their ids, and the burst is still the newest multi-frame push, its info as it was
     assert np.array_equal(bf.copy_frame(first + 1).view(np.uint32), out[1].view(np.uint32))
     assert bytes(bf.last_burst_info()) == before
-    map_tests.same(bf.localisation_map_copy()[0], counts)
+    ring_frames.same_localise(bf.localisation_map_copy()[0], counts)
 
 
 def test_a_shutdown_releases_everything_and_the_calls_start_again(bflib):
     L = bflib.library()
     which = "frame_ops_small"
-    frames, ids = ensemble_tests.ensemble(which, K)
+    frames, ids = ring_frames.ensemble(which, K)
     grid, A = map_of(which)
-    map_tests.run(grid, frames, peaks_tests.fraction_of_max(frames, 0.25), A)
+    ring_frames.run_localise(grid, frames, ring_frames.fraction_of_max(frames, 0.25), A)
     scored, _ = bf.score_last_frames(K)
     out, _, mixed_rows = mix_and_score(which, frames, ids)
     bf.track_map_reset(MAP_POINTS)
@@ -227,12 +216,12 @@ def test_a_shutdown_releases_everything_and_the_calls_start_again(bflib):
 
     no_map()
     assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames2, ids2 = ensemble_tests.ensemble(which, K)
+    frames2, ids2 = ring_frames.ensemble(which, K)
     assert ids2 == list(range(K)) and np.array_equal(frames2.view(np.uint32), frames.view(np.uint32))
     no_map()                                            # a device again, but the map went with the old one
     scored2, _ = bf.score_last_frames(K)
     for k in range(K):
-        metrics_tests.check_row(scored2[k], frames2[k], what=f"after the shutdown {k}")
+        ring_frames.check_row(scored2[k], frames2[k], what=f"after the shutdown {k}")
     assert [numbers_of(r) for r in scored2] == [numbers_of(r) for r in scored]
     out2, first2, mixed_rows2 = mix_and_score(which, frames2, ids2)
     assert first2 == K and out2.tobytes() == out.tobytes() and [numbers_of(r) for r in mixed_rows2] == [numbers_of(r) for r in mixed_rows]

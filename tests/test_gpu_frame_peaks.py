@@ -18,100 +18,19 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import configs as cfg
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import cases
-from tests import frame_metrics_ref
 from tests import frame_peaks_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import BOX, block, newest_info, region_of, variants_push
-from tests.test_gpu_parity import compare, reference
+from tests.das_push import compare
+from tests.parity import reference
+from tests.frame_info import newest_info
+from tests.ring_frames import (metrics_block as block, BOX, CAP, check_peaks as check_call, fraction_of_max, peak_records as records_of, region_of,
+                               variants_push)
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-CAP = 4096
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
-
-
-def fraction_of_max(frames, fraction):
-    """per frame: `fraction` of its largest finite magnitude, as the float32 the call is given"""
-    out = []
-    for f in frames:
-        m = frame_metrics_ref.magnitude(f)
-        out.append(float(np.float32(fraction) * m[np.isfinite(m)].max()))
-    return out
-
-
-def ulps(a, b):
-    """distance in units in the last place of two arrays of finite non-negative float32"""
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
-
-
-def records_of(row, peaks):
-    return np.frombuffer(bytes(peaks), np.dtype(P.HipFramePeak))[int(row.first):int(row.first) + int(row.stored)]
-
-
-def check_frame(row, peaks, frame, threshold, box=None, cap=CAP, first=None, what=""):
-    """one frame's row and records against the reference applied to the downloaded frame"""
-    real = not np.iscomplexobj(frame)
-    r = ref.peaks(frame, threshold, *(box if box else (None, None)), cap=cap)
-    pz, py, px = frame.shape
-    print(f"  {what}: frame {int(row.frame_id)} {(px, py, pz)} {'real' if real else 'complex'} threshold {threshold!r} box {box}: "
-          f"found {int(row.found)} ({r['found']}), above {int(row.above_threshold)} ({r['above_threshold']}), stored {int(row.stored)} ({r['stored']})")
-    info = bf.frame_info(int(row.frame_id))
-    assert tuple(row.points) == tuple(info.points) == (px, py, pz) and row.data_kind == info.data_kind and row.parameter_block == info.parameter_block
-    assert row.data_kind == int(P.DataKind.Float32 if real else P.DataKind.Float32Complex)
-    assert tuple(row.region_first) == (tuple(box[0]) if box else (0, 0, 0)) and tuple(row.region_count) == (tuple(box[1]) if box else (px, py, pz))
-    assert row.threshold == np.float32(threshold)
-    assert (int(row.found), int(row.above_threshold), int(row.stored)) == (r["found"], r["above_threshold"], r["stored"])
-    if first is not None:
-        assert int(row.first) == first
-    got = records_of(row, peaks)
-    assert np.array_equal(got["index"], r["index"]), (got["index"][:8], r["index"][:8])
-    assert np.array_equal(got["fitted"], r["fitted"])
-    if real:
-        assert np.array_equal(got["magnitude"].view(np.uint32), r["magnitude"].view(np.uint32))
-        assert np.array_equal(got["offset"].view(np.uint32), r["offset"].view(np.uint32))
-    elif len(got):
-        away = ulps(got["magnitude"], r["magnitude"])
-        print(f"    magnitude: {int((away == 0).sum())} of {len(away)} bit-equal, worst {int(away.max())} ulp")
-        assert away.max() <= 1
-        # den per axis from the reference's magnitudes, for the bar
-        m = np.pad(frame_metrics_ref.magnitude(frame), 1, constant_values=np.float32(np.nan)).astype(np.float64)
-        x, y, z = (r["index"][:, a].astype(np.int64) + 1 for a in range(3))
-        m0 = m[z, y, x]
-        for axis, (dz, dy, dx) in enumerate(((0, 0, 1), (0, 1, 0), (1, 0, 0))):
-            on = (r["fitted"] >> axis & 1).astype(bool)
-            den = (m[z - dz, y - dy, x - dx] + m[z + dz, y + dy, x + dx]) - 2 * m0
-            bar = 8 * 2.0 ** -23 * m0[on] / np.abs(den[on]) + 2.0 ** -20
-            off = np.abs(got["offset"][on, axis].astype(np.float64) - r["offset"][on, axis].astype(np.float64))
-            if on.any():
-                print(f"    offset[{axis}]: {int(on.sum())} fitted, worst {off.max():.3e} (its bar {bar[np.argmax(off)]:.3e}), "
-                      f"{int((got['offset'][on, axis] == r['offset'][on, axis]).sum())} bit-equal")
-            assert (off <= bar).all(), axis
-            assert not got["offset"][~on, axis].any()
-        assert (np.abs(got["offset"]) <= 0.5).all()
-    return r
-
-
-def check_call(frames, thresholds, box=None, cap=CAP, what=""):
-    """find the peaks of the len(frames) newest frames and check every frame; thresholds: one number or one a frame"""
-    rows, peaks, ms = bf.find_peaks_last_frames(len(frames), thresholds, cap, region_of(box))
-    each = [thresholds] * len(frames) if np.ndim(thresholds) == 0 else list(thresholds)
-    first, out = 0, []
-    for k, frame in enumerate(frames):
-        out.append(check_frame(rows[k], peaks, frame, each[k], box, cap, first, what=f"{what} {k}"))
-        first += int(rows[k].stored)
-    assert len(peaks) == first and ms > 0
-    return rows, peaks, out
 
 
 def test_block_a_three_variants_of_a_complex_plane(bflib):

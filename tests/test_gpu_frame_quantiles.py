@@ -10,68 +10,21 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import frame_peaks_ref
 from tests import frame_quantiles_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import BOX, block, region_of, variants_push
-from tests.test_gpu_localisation import finer, map_view, placement_onto
+from tests.ring_frames import bits, metrics_block as block, BOX, finer, FRACTIONS, map_view, placement_onto, ranked, region_of, variants_push
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-FRACTIONS = [0.5, 1.0, 0.05, 0.999, 0.0, 0.5]       # unsorted, with a repeat
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def map_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
-
-
-def bits(value):
-    return int(np.asarray(value, np.float32).view(np.uint32))
-
-
-def ranked(frames, fractions, box=None, histograms=True):
-    """one call over the len(frames) newest frames, every field against the reference applied to the downloaded frames: the
-    reference's results, frame by frame"""
-    rows, records, tables, ms = bf.quantiles_last_frames(len(frames), fractions, region_of(box), histograms=histograms)
-    fractions = [float(f) for f in np.atleast_1d(fractions)]
-    K = len(fractions)
-    volume = sum(int(np.prod(box[1] if box else f.shape)) * f.itemsize for f in frames)
-    print(f"  quantiles of {len(frames)} frames, {K} fractions, box {box}: {volume} bytes of boxes, device {ms:.4f} ms")
-    assert ms > 0 and len(records) == len(frames) * K and (tables is not None) == histograms
-    expected = []
-    for n, frame in enumerate(frames):
-        want = ref.quantiles(frame, fractions, *(box if box else (None, None)))
-        row, real = rows[n], not np.iscomplexobj(frame)
-        info = bf.frame_info(int(row.frame_id))
-        assert tuple(row.points) == tuple(info.points) == want["points"] and row.data_kind == info.data_kind
-        assert row.data_kind == int(P.DataKind.Float32 if real else P.DataKind.Float32Complex)
-        assert row.parameter_block == info.parameter_block
-        assert tuple(row.region_first) == want["region_first"] and tuple(row.region_count) == want["region_count"]
-        assert (int(row.first), int(row.stored), int(row.reserved)) == (n * K, K, 0)
-        assert (int(row.voxels), int(row.non_finite)) == (want["voxels"], want["non_finite"]), (n, int(row.voxels), int(row.non_finite))
-        assert row.voxels + row.non_finite == int(np.prod(want["region_count"]))
-        for k, q in enumerate(want["rows"]):
-            got = records[n * K + k]
-            print(f"    frame {int(row.frame_id)} f {q['fraction']!r}: rank {int(got.rank)} value {float(got.value)!r} below {int(got.below)} "
-                  f"equal {int(got.equal)} threshold {float(got.threshold)!r}  (reference rank {q['rank']} value {float(q['value'])!r})")
-            assert got.fraction == q["fraction"] and got.reserved == 0
-            assert (int(got.rank), int(got.below), int(got.equal)) == (q["rank"], q["below"], q["equal"]), (n, k)
-            assert bits(got.value) == q["value_bits"], (n, k)
-            assert bits(got.magnitude) == bits(q["magnitude"]) and bits(got.threshold) == bits(q["threshold"]), (n, k)
-            assert got.below <= got.rank < got.below + got.equal or want["voxels"] == 0
-        if histograms:
-            assert tables.shape == (len(frames), P.HIP_QUANTILE_BINS) and tables[n].tobytes() == want["histogram"].tobytes(), n
-            assert int(tables[n].sum(dtype=np.uint64)) == int(row.voxels) and not tables[n, 2040:].any()
-        expected.append(want)
-    return expected
 
 
 def test_block_a_three_variants_of_a_complex_plane(bflib):

@@ -369,7 +369,7 @@ def test_config1_at_full_size_against_the_whole_oracle_frame(bflib, oracle):
     """BASELINE configs[0] at its own (small) size: 64 channels x 2048 samples x 1 plane wave -> 256 x 256, every voxel against
     the oracle on the automatic path (general kernel with the channel split) and without the split"""
     from tests import cases
-    from tests.test_gpu_parity import compare
+    from tests.das_push import compare
     acq = cfg.config(1)
     ref, _ = oracle.beamform(acq.bp, acq.rf, acq.filters, threads=16)
     for mode in (0, 0x11):

@@ -15,8 +15,8 @@ import pytest
 
 from ogl_beamforming_amd import params as P
 from tests import ingest_cases as IC
-from tests.test_gpu_parity import compare, last_timings
-from tests.test_gpu_stages import as_bits, check_das_input, oracle_run, push
+from tests.das_push import compare, last_timings
+from tests.stage_checks import as_bits, check_das_input, oracle_run, push
 
 pytestmark = pytest.mark.gpu
 

@@ -8,9 +8,6 @@ in numpy, and the placement is float64 arithmetic in a fixed order: the map is t
 byte.  On complex frames a magnitude may differ from numpy's by 1 ulp (tests/test_gpu_frame_peaks.py), so there the reference bins the
 records beamformer_hip_find_peaks_last_frames returns for the same frames: the call promises those positions bit for bit."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,71 +17,19 @@ from ogl_beamforming_amd import params as P
 from tests import frame_peaks_ref
 from tests import localisation_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import BOX, block, newest_info, region_of, variants_push
-from tests.test_gpu_frame_peaks import fraction_of_max
+from tests.frame_info import newest_info
+from tests.ring_frames import (binned_records, metrics_block as block, BOX, check_rows, finer, fraction_of_max, map_view, placement_onto, points_of,
+                               run_localise as run, same_localise as same, variants_push)
+from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def map_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
-
-
-def finer(points, factor=4):
-    """the grid `factor` times finer an axis over the same box: voxel i lands on map voxel factor * i"""
-    return tuple(factor * (n - 1) + 1 if n > 1 else 1 for n in points)
-
-
-def map_view(points, lo, hi):
-    """the map's grid as a view; an axis without extent (a plane's y) gets one: the map's transform has to be regular"""
-    return bf.view(points, lo, tuple(h if h != l else l + 1e-3 for l, h in zip(lo, hi)))
-
-
-def placement_onto(grid, transform, points):
-    return bf.map_placement(list(transform), points, list(grid.das_voxel_transform), list(grid.output_points))
-
-
-def points_of(frame):
-    return frame.shape[::-1]
-
-
-def run(grid, frames, thresholds, placements, use_offsets=True, box=None, reset=True):
-    """reset the map (unless told not to), deposit the len(frames) newest frames, download: (counts, rows, info)"""
-    if reset:
-        bf.localisation_map_reset(grid.output_points)
-    rows, ms = bf.accumulate_peaks_last_frames(len(frames), thresholds, placements, use_offsets, region_of(box))
-    assert ms > 0
-    counts, info = bf.localisation_map_copy(grid.output_points)
-    assert tuple(info.points) == tuple(grid.output_points)
-    return counts, rows, info
-
-
-def check_rows(rows, expected, frames, thresholds, box=None):
-    """the rows against the reference's numbers and against find_peaks' rows of the same call"""
-    found, _, _ = bf.find_peaks_last_frames(len(frames), thresholds, 16, region_of(box))
-    each = [thresholds] * len(frames) if np.ndim(thresholds) == 0 else list(thresholds)
-    for k, (row, want, peaks) in enumerate(zip(rows, expected, found)):
-        print(f"  frame {int(row.frame_id)} {tuple(row.points)}: found {int(row.found)}, above {int(row.above_threshold)}, "
-              f"deposited {int(row.deposited)}, outside {int(row.outside)}")
-        assert (int(row.found), int(row.above_threshold)) == (int(peaks.found), int(peaks.above_threshold)) == (want["found"], want["above_threshold"])
-        assert (int(row.deposited), int(row.outside)) == (want["deposited"], want["outside"]) and row.deposited + row.outside == row.found
-        assert (row.frame_id, row.parameter_block, row.data_kind, row.image_plane_tag) == (peaks.frame_id, peaks.parameter_block, peaks.data_kind, peaks.image_plane_tag)
-        assert tuple(row.points) == tuple(peaks.points) == points_of(frames[k]) and tuple(row.reserved) == (0, 0)
-        assert tuple(row.region_first) == tuple(peaks.region_first) and tuple(row.region_count) == tuple(peaks.region_count)
-        assert row.threshold == np.float32(each[k])
-
-
-def same(counts, expected):
-    assert counts.dtype == expected.dtype == np.uint32 and counts.shape == expected.shape
-    assert counts.tobytes() == expected.tobytes(), f"{int((counts != expected).sum())} bins differ"
 
 
 def test_real_frames_a_plane_and_a_volume(bflib):
@@ -123,21 +68,6 @@ def test_real_frames_a_plane_and_a_volume(bflib):
     expected, numbers = ref.accumulate(grid.output_points, [frame], threshold, A, first=BOX[0], count=BOX[1])
     same(counts, expected)
     check_rows(rows, numbers, [frame], threshold, box=BOX)
-
-
-def binned_records(points, frames_count, thresholds, placements, use_offsets=True, box=None):
-    """the reference map of the records find_peaks returns for the newest frames, at the cap of 65536"""
-    rows, peaks, _ = bf.find_peaks_last_frames(frames_count, thresholds, P.HIP_MAX_PEAKS_PER_FRAME, region_of(box))
-    records = np.frombuffer(bytes(peaks), np.dtype(P.HipFramePeak))
-    counts = np.zeros((points[2], points[1], points[0]), np.uint32)
-    A = np.asarray(placements, np.float64).reshape(-1, 3, 4)
-    numbers = []
-    for k, row in enumerate(rows):
-        assert row.stored == row.found
-        mine = records[int(row.first):int(row.first) + int(row.stored)]
-        deposited, outside = ref.deposit_records(counts, mine["index"], mine["offset"], A[0 if len(A) == 1 else k], use_offsets)
-        numbers.append({"found": int(row.found), "above_threshold": int(row.above_threshold), "deposited": deposited, "outside": outside})
-    return counts, numbers
 
 
 def test_complex_frames_land_where_their_find_peaks_records_say(bflib):
@@ -400,8 +330,4 @@ def test_refusals_on_the_device_change_nothing(bflib):
 
 def test_the_ring_a_queued_map_that_wraps_and_one_that_does_not_fit():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/localisation_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "localisation_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "refused" in run.stdout and "wrapped" in run.stdout, run.stdout
+    run_ring_worker("localisation_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

@@ -15,25 +15,14 @@ from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import motion_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_ensemble import BOXES, GRIDS, block, ensemble, rf_frames
-from tests.test_gpu_frame_metrics import newest_info
+from tests.frame_info import newest_info
+from tests.ring_frames import block, BOXES, check_correlate as check_call, DOUBLES, ensemble, GRIDS, regions_of, rf_frames
+from tests.scaffold import automatic_path, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-D = P.DataKind
-ENTRY = np.dtype(P.HipShiftCorrelation)
 NAN_POINTS = (24, 1, 40)
 INTERIOR = dict(BOXES, nan=((1, 0, 3), (21, 1, 35)))
-DOUBLES = ("re", "im", "energy_reference", "energy_frame")
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
 
 
 def points_of(which):
@@ -45,54 +34,6 @@ def corner_box(which):
     px, py, pz = points_of(which)
     count = (min(px, 13), min(py, 3), min(pz, 5))
     return (px - count[0], py - count[1], pz - count[2]), count
-
-
-def regions_of(boxes):
-    return None if boxes is None else [bf.frame_region(*b) for b in boxes]
-
-
-SEEN = []           # the worst share of its bar of every call checked in this run, for the figure the commit message quotes
-
-
-def worst_of(table, expected, bars):
-    """the largest error of the four doubles as a fraction of its bar (0 where the bar and the error are both 0, inf where the bar alone is)"""
-    worst = 0.0
-    for name, bar in zip(DOUBLES, (0, 0, 1, 2)):
-        over = np.abs(table[name] - expected[name])
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ratio = np.where(over > 0, over / bars[..., bar], 0.0)
-        worst = max(worst, float(ratio.max()))
-    return worst
-
-
-def check_call(frames, ids, reference, window, boxes=None, what=""):
-    """one call against the reference applied to the downloaded frames; returns (table, expected, bars)"""
-    K = len(frames)
-    real = not np.iscomplexobj(frames)
-    pz, py, px = frames[0].shape
-    table, info, ms = bf.correlate_last_frames(K, reference, window, regions_of(boxes))
-    expected, bars = ref.correlate(list(frames), reference, window, boxes)
-    R, T = (1 if boxes is None else len(boxes)), int(np.prod([2 * s + 1 for s in window]))
-    assert table.shape == expected.shape == (R, K, 2 * window[2] + 1, 2 * window[1] + 1, 2 * window[0] + 1) and table.dtype == ENTRY
-    same_terms = np.array_equal(table["terms"], expected["terms"])
-    finite = all(np.isfinite(table[name]).all() for name in DOUBLES)
-    worst = worst_of(table, expected, bars) if same_terms and finite else float("nan")
-    SEEN.append(worst)
-    print(f"  {what}: K {K} ref {reference} {(px, py, pz)} {'real' if real else 'complex'} window {window} boxes {boxes}: terms "
-          f"{int(table['terms'].sum())} ({int(expected['terms'].sum())}), worst error {worst:.3f} of its bar (the largest of this run so far "
-          f"{max(SEEN):.3f}), {ms * 1e3:.1f} us")
-    assert same_terms and finite and ms > 0
-    assert worst <= 1.0
-    # info, field by field
-    assert (int(info.count), int(info.reference), int(info.data_kind), int(info.region_count)) == (K, reference, int(D.Float32 if real else D.Float32Complex), R)
-    assert tuple(info.points) == (px, py, pz) and tuple(info.max_shift) == tuple(window) and int(info.shifts) == T
-    assert (int(info.first_frame_id), int(info.reference_frame_id), int(info.reserved)) == (ids[0], ids[reference], 0)
-    # an entry without terms is 40 zero bytes; real frames have no imaginary part
-    empty = table["terms"] == 0
-    assert not table[empty].tobytes().strip(b"\0")
-    if real:
-        assert not table["im"].any()
-    return table, expected, bars
 
 
 def windows_of(which):
@@ -292,14 +233,7 @@ def test_refusals(bflib):
 def test_several_devices_are_refused(bflib):
     L = bflib.library()
     acq = vc.separable_volume()
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq):
         refused(L, E.InvalidAccess, 1, 0, (1, 1, 1))
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     frames, ids = ensemble("plane", 2)
     check_call(frames, ids, 1, (1, 0, 1), None, what="one device again")

@@ -10,15 +10,9 @@ import pytest
 
 from ogl_beamforming_amd import params as P
 from tests import cases
+from tests.das_push import same_bits, use_devices
 
 pytestmark = pytest.mark.gpu
-
-
-def use_devices(lib, ordinals):
-    lib.beamformer_hip_shutdown()
-    arr = (C.c_int32 * len(ordinals))(*ordinals)
-    assert lib.beamformer_hip_set_devices(arr, len(ordinals))
-    assert lib.beamformer_hip_get_device_count() == len(ordinals)
 
 
 @pytest.fixture()
@@ -26,10 +20,6 @@ def devices(bflib):
     lib = bflib.library()
     yield lambda ordinals: use_devices(lib, ordinals)
     use_devices(lib, [0])                      # leave the process-wide library as the other tests expect it
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 @pytest.mark.parametrize("name, count", [("config4_small", 2), ("config4_small", 3), ("config5_small", 4),

@@ -6,62 +6,12 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import params as P
-from tests import cases, parity
-# the comparison lives in tests/parity.py (a plain module: its CPU tests, tests/test_compare.py, and the tools use it); reference and
-# truth_frame are re-exported from there, and compare with the DAS path of the library's newest frame in its log entry
-from tests.parity import reference, truth_frame  # noqa: F401
+from tests import cases
+from tests.das_kernel_cases import FACTORED, HERCULES, SEPARABLE, STAGED, TILE
+from tests.das_push import compare, last_das_path, last_timings
+from tests.parity import reference
 
 pytestmark = pytest.mark.gpu
-
-
-def compare(gpu, ref, acq, flags=None, *, path=None, label=None):
-    """tests/parity.py compare(); the log entry names the DAS path of the library's newest frame unless `path` is given"""
-    if path is None:
-        from ogl_beamforming_amd import lib
-        path = last_das_path(lib)
-    return parity.compare(gpu, ref, acq, flags, path=path, label=label)
-
-
-def last_timings(bflib):
-    import ctypes as C
-    t = P.HipFrameTimings()
-    assert bflib.library().beamformer_hip_get_last_frame_timings(C.byref(t))
-    return t
-
-
-def last_das_path(bflib):
-    return int(last_timings(bflib).das_path)
-
-
-# geometries whose receive and transmit axes differ: the separable-delay fast path must pick
-# them up on its own (das_separable.hip)
-SEPARABLE = {"config4_small", "rca_vls_cw", "rca_sep_ragged_cubic", "rca_sep_real_nearest",
-             "rca_staged_w64", "rca_staged_too_wide", "rca_staged_ragged", "rca_staged_auto", "rca_vls_staged", "rca_vls_staged_short_rows", "rca_staged_real", "rca_staged_real_short_rows", "rca_staged_real_narrow_cw", "rca_staged_cubic", "rca_staged_cubic_short_rows",
-             "rca_staged_fine", "rca_staged_fine_vls_short_rows"}
-# ... and of those, the ones with linear interpolation (complex or real samples) or cubic interpolation of complex samples whose
-# delay spread fits an LDS window
-# can run the LDS-staged kernel (das_staged.hip): automatically from STAGED_MIN_TRANSMITS transmits per
-# channel (executor.cpp kStagedMinTransmits), on request (path 3) below that
-STAGED = {"config4_small", "rca_staged_w64", "rca_staged_ragged", "rca_staged_auto", "rca_vls_staged", "rca_vls_staged_short_rows", "rca_staged_real", "rca_staged_real_short_rows", "rca_staged_real_narrow_cw", "rca_staged_cubic", "rca_staged_cubic_short_rows",
-          "rca_sep_ragged_cubic", "rca_staged_fine", "rca_staged_fine_vls_short_rows"}
-STAGED_MIN_TRANSMITS = 6
-
-
-def factored_applies(acq):
-    """whether das_factored.hip takes the frame when asked for (das path 4): the library says (beamformer_hip_describe_das)"""
-    from ogl_beamforming_amd import lib
-    L = lib.library()
-    L.beamformer_hip_set_das_path(0x14)
-    try:
-        return lib.describe_das(acq.bp, acq.filters)[0] == 3
-    finally:
-        L.beamformer_hip_set_das_path(0)
-
-
-def hercules_family(bp):
-    return P.AcquisitionKind(bp.acquisition_kind) in (P.AcquisitionKind.HERCULES, P.AcquisitionKind.UHERCULES,
-                                                      P.AcquisitionKind.HERO_PA)
-
 
 EXPECTED_AUTOMATIC = cases.EXPECTED_AUTOMATIC
 
@@ -226,9 +176,6 @@ def test_general_kernel_without_channel_split(name, bflib, oracle):
     compare(gpu, ref, acq, flags)
 
 
-HERCULES = sorted(n for n in cases.CASES if hercules_family(cases.make(n).bp))
-
-
 @pytest.mark.parametrize("name", HERCULES)
 def test_hercules_aligned_kernel(name, bflib, oracle):
     """das_hercules.hip on every HERCULES-family case (mode 6 also takes the grids too narrow for the
@@ -286,9 +233,6 @@ def test_hercules_coherent_peak_at_long_delays(bflib, oracle):
             lib.beamformer_hip_set_das_path(0)
         err = np.abs(gpu - ref).max() / peak
         assert err <= 1e-4, (mode, err)
-
-
-FACTORED = sorted(n for n in cases.CASES if factored_applies(cases.make(n)))
 
 
 @pytest.mark.parametrize("split", [True, False])
@@ -381,23 +325,6 @@ def test_pair_count_matches_oracle(bflib, oracle):
             lib.beamformer_hip_enable_pair_counting(0)
         assert abs(int(t.das_pairs) - pairs) <= max(4, 2e-4 * pairs), (name, int(t.das_pairs), pairs)
 
-
-def tile_candidates():
-    from ogl_beamforming_amd import lib as bflib_mod
-    out = []
-    lib = bflib_mod.library()
-    lib.beamformer_hip_set_das_path(0x14 | 0x100)
-    try:
-        for n in sorted(cases.CASES):
-            acq = cases.make(n)
-            if bflib_mod.describe_das(acq.bp, acq.filters)[0] == 5:
-                out.append(n)
-    finally:
-        lib.beamformer_hip_set_das_path(0)
-    return sorted(out)
-
-
-TILE = tile_candidates()
 
 # what the block does with its (block, chunk of four channels) pairs -- staged windows, or the kernel's own gather loop where the
 # spread of the chunk does not fit the window (BeamformerHipFrameTimings::tile_staged_chunks / tile_gather_chunks)

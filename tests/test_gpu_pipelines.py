@@ -17,10 +17,8 @@ from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import params as P
 from tests import cases
 from tests import pipeline_cases as pc
-from tests import test_gpu_stages as stages
-from tests import test_gpu_stages_burst as burst
-from tests.test_gpu_burst import noise_frames
-from tests.test_gpu_parity import compare
+from tests import stage_checks as stages
+from tests.das_push import compare, noise_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -124,12 +122,12 @@ def test_long_chain_in_a_burst(name, bflib, hooks):
     rf = noise_frames(acq, 3, 9900 + pc.LONG_CHAINS.index(name))
     if rf.dtype.kind == "i":
         rf = (rf // 8).astype(rf.dtype)
-    _, inputs, _ = burst.push_burst(bflib, hooks, acq, rf, 0)
+    _, inputs, _ = stages.push_burst(bflib, hooks, acq, rf, 0)
     for k in range(3):
-        burst.nan_free(acq, inputs[k], f"{name} burst frame {k}")
+        stages.nan_free(acq, inputs[k], f"{name} burst frame {k}")
         _, one_in = stages.push(bflib, dataclasses.replace(acq, rf=rf[k]), hooks, poison=True)
         assert np.array_equal(as_bits(inputs[k]), as_bits(one_in)), \
-            f"{name}: burst frame {k}'s DAS input is not its single push's: {burst.first_difference(inputs[k], one_in)}"
+            f"{name}: burst frame {k}'s DAS input is not its single push's: {stages.first_difference(inputs[k], one_in)}"
 
 
 # ------------------------------------------------------------------------------------------------ frame graphs

@@ -9,22 +9,13 @@ counts, planned indices, planned offsets, the int64 results of the integer frame
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import lib as bf
 from tests import frame_peaks_ref, frame_quantiles_ref, localisation_ref, tracks_ref
 from tests import planted
-from tests import test_gpu_autocorr as autocorr_tests
-from tests import test_gpu_ensemble as ensemble_tests
-from tests import test_gpu_frame_metrics as metrics_tests
-from tests import test_gpu_frame_peaks as peaks_tests
-from tests import test_gpu_frame_quantiles as quantiles_tests
-from tests import test_gpu_localisation as map_tests
-from tests import test_gpu_motion as motion_tests
-from tests import test_gpu_spatial as spatial_tests
-from tests import test_gpu_tracks as tracks_tests
-from tests import test_gpu_warp as warp_tests
-from tests import test_planted_host as host
+from tests import ring_frames
+from tests import planted_ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import newest_info, region_of
+from tests.ring_frames import planted_burst as burst, planted_push as push, region_of
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 PLANE, WAVE, VOLUME = planted.PLANE, planted.WAVE, planted.VOLUME
@@ -40,39 +31,14 @@ def grid_name(points, cplx):
 # ask their module's block for the shape and the kind of the frames they download, and for nothing else
 for _points in (PLANE, WAVE, VOLUME):
     for _cplx in (False, True):
-        ensemble_tests.GRIDS[grid_name(_points, _cplx)] = (_points, vc.LO if _points[1] == 1 else vc.LO3, vc.HI if _points[1] == 1 else vc.HI3, _cplx)
+        ring_frames.GRIDS[grid_name(_points, _cplx)] = (_points, vc.LO if _points[1] == 1 else vc.LO3, vc.HI if _points[1] == 1 else vc.HI3, _cplx)
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def maps_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
     bflib.track_map_reset(None)
-
-
-def push(values):
-    """one planted frame by a single push: (the downloaded frame, its id) -- and it IS what was planted"""
-    acq = planted.block(values)
-    frame = bf.beamform(acq.bp, acq.rf, acq.filters).copy()
-    assert planted.same(frame, planted.expected(values)), "the DAS kernel changed a planted value"
-    return frame, int(newest_info(bf.library()).frame_id)
-
-
-def burst(stack):
-    """K planted frames by one burst push (one: a single push): (frames (K, Z, Y, X), ids); frame k is planted array k"""
-    if len(stack) == 1:
-        frame, frame_id = push(stack[0])
-        return frame[None], [frame_id]
-    blocks = [planted.block(values) for values in stack]
-    frames = bf.beamform_burst(blocks[0].bp, np.stack([acq.rf for acq in blocks]), blocks[0].filters).copy()
-    for k, values in enumerate(stack):
-        assert planted.same(frames[k], planted.expected(values)), f"frame {k} of the burst is not planted array {k}"
-    newest = int(newest_info(bf.library()).frame_id)
-    return frames, list(range(newest - len(stack) + 1, newest + 1))
 
 
 def at(array, position):
@@ -123,9 +89,9 @@ def make(name, points, cplx, seed=0):
 
 # ----------------------------------------------------------------------------- planting on the device
 
-@pytest.mark.parametrize("name,points,cplx", host.HAZARDS, ids=lambda v: str(v).replace(" ", ""))
+@pytest.mark.parametrize("name,points,cplx", planted_ref.HAZARDS, ids=lambda v: str(v).replace(" ", ""))
 def test_every_hazard_frame_comes_back_as_planted(name, points, cplx, bflib):
-    values = host.hazard(name, points, cplx)
+    values = planted_ref.hazard(name, points, cplx)
     frame, _ = push(values)
     parts = frame.view(np.float32)
     assert frame.shape == points[::-1] and not (np.signbit(parts) & (parts == 0)).any()
@@ -169,7 +135,7 @@ def test_score(name, points, cplx, bflib):
         boxes.append((first, tuple(n - f for n, f in zip(points, first))))
     for box in boxes:
         rows, _ = bflib.score_last_frames(1, region_of(box))
-        metrics_tests.check_row(rows[0], frame, box, what=f"{name} {points} box {box}")
+        ring_frames.check_row(rows[0], frame, box, what=f"{name} {points} box {box}")
         owed = planted.box_numbers(plan, box)
         assert (int(rows[0].non_finite), [int(n) for n in rows[0].gradient_pairs]) == (owed["non_finite"], owed["gradient_pairs"])
         if owed["max_index"] is not None:
@@ -182,7 +148,7 @@ def test_score(name, points, cplx, bflib):
 # ----------------------------------------------------------------------------- find_peaks
 
 def indices(row, peaks):
-    return [tuple(int(v) for v in i) for i in peaks_tests.records_of(row, peaks)["index"]]
+    return [tuple(int(v) for v in i) for i in ring_frames.peak_records(row, peaks)["index"]]
 
 
 @pytest.mark.parametrize("name,points,cplx", HAZARDS, ids=IDS)
@@ -192,7 +158,7 @@ def test_find_peaks(name, points, cplx, bflib):
     present(frame, plan)
     q = frame_peaks_ref.decision(frame)
     for threshold in (0.0, HEIGHT if name == "plateaus" else 1.0):
-        rows, peaks, found = peaks_tests.check_call([frame], threshold, what=f"{name} {points} at {threshold}")
+        rows, peaks, found = ring_frames.check_peaks([frame], threshold, what=f"{name} {points} at {threshold}")
         whole = indices(rows[0], peaks)
         assert found[0]["found"] == len(whole) >= 2
         if name == "plateaus" and threshold:
@@ -200,7 +166,7 @@ def test_find_peaks(name, points, cplx, bflib):
             level = frame_peaks_ref.level(frame, threshold)
             assert int((q == level).sum()) >= sum(len(v) for k, v in plan["plateaus"].items() if k not in ("rounding", "collision")) - 1
             assert whole == plan["peaks"]
-            records = peaks_tests.records_of(rows[0], peaks)
+            records = ring_frames.peak_records(rows[0], peaks)
             for (position, axis), (offset, fitted) in plan["offsets"].items():
                 record = records[whole.index(position)]
                 assert bool(record["fitted"] >> axis & 1) == fitted, (position, axis)
@@ -208,7 +174,7 @@ def test_find_peaks(name, points, cplx, bflib):
         # tiled into boxes: the tiles' lists concatenate to the whole frame's -- no peak invented at a face, none doubled
         tiled = []
         for box in halves(points):
-            rows, peaks, _ = peaks_tests.check_call([frame], threshold, box=box, what=f"{name} {points} at {threshold}, tile {box}")
+            rows, peaks, _ = ring_frames.check_peaks([frame], threshold, box=box, what=f"{name} {points} at {threshold}, tile {box}")
             tiled += indices(rows[0], peaks)
         assert sorted(tiled, key=lambda p: planted._flat(points, p)) == whole
 
@@ -222,13 +188,13 @@ def test_quantiles_of_the_radix_frame(bflib):
     assert non_finite == 0 and np.array_equal(np.sort(bits), plan["keys"])             # every planted key is in the downloaded frame
     keys = []
     for fractions in plan["fractions"]:
-        want = quantiles_tests.ranked([frame], fractions, histograms=True)[0]
+        want = ring_frames.ranked([frame], fractions, histograms=True)[0]
         keys += [q["value_bits"] for q in want["rows"]]
         assert [q["rank"] for q in want["rows"]] == plan["ranks"][len(keys) - len(fractions):len(keys)]
-        quantiles_tests.ranked([frame], fractions, histograms=False)
-        for box in (metrics_tests.BOX, cut(VOLUME)):
-            quantiles_tests.ranked([frame], fractions, box, histograms=True)
-            quantiles_tests.ranked([frame], fractions, box, histograms=False)
+        ring_frames.ranked([frame], fractions, histograms=False)
+        for box in (ring_frames.BOX, cut(VOLUME)):
+            ring_frames.ranked([frame], fractions, box, histograms=True)
+            ring_frames.ranked([frame], fractions, box, histograms=False)
     assert keys == [int(plan["keys"][r]) for r in plan["ranks"]]
     first, last = plan["tie"]
     assert keys[plan["ranks"].index(first)] == keys[plan["ranks"].index(last)] == planted.RADIX_TIE
@@ -244,11 +210,11 @@ def test_quantiles_leave_out_the_non_finite_voxels_and_the_zeros_are_the_lowest_
     fractions = [0.0, 1.0, 0.5, (zeros - 1) / (frame.size - len(plan["non_finite"]) - 1), zeros / (frame.size - len(plan["non_finite"]) - 1)]
     for box in (None, cut(points)):
         for histograms in (True, False):
-            want = quantiles_tests.ranked([frame], fractions, box, histograms=histograms)[0]
+            want = ring_frames.ranked([frame], fractions, box, histograms=histograms)[0]
         assert want["non_finite"] == planted.box_numbers(plan, box)["non_finite"]
         assert np.isfinite([q["value"] for q in want["rows"]]).all()
     # (the whole frame) rank 0 and the last rank of the plateau of zeros hold 0, the rank behind it the smallest q above 0
-    rows = quantiles_tests.ranked([frame], fractions)[0]["rows"]
+    rows = ring_frames.ranked([frame], fractions)[0]["rows"]
     assert [(r["rank"], r["value_bits"], r["below"], r["equal"]) for r in (rows[0], rows[3])] == [(0, 0, 0, zeros), (zeros - 1, 0, 0, zeros)]
     assert rows[4]["rank"] == rows[4]["below"] == zeros and 0 < rows[4]["value"] < planted.FLT_MIN
 
@@ -265,16 +231,16 @@ def test_plateaus_moved_by_a_known_shift_deposit_and_pair(points, cplx, bflib):
     acq = planted.block(values)
     lo, hi = planted.extent(points)
     # deposits: the frames' own grid (an offset of +-0.5 is a bin boundary there) and a grid four times finer
-    for grid in (map_tests.map_view(points, lo, hi), map_tests.map_view(map_tests.finer(points), lo, hi)):
-        A = map_tests.placement_onto(grid, acq.bp.das_voxel_transform, points)
+    for grid in (ring_frames.map_view(points, lo, hi), ring_frames.map_view(ring_frames.finer(points), lo, hi)):
+        A = ring_frames.placement_onto(grid, acq.bp.das_voxel_transform, points)
         for use_offsets in (True, False):
-            counts, rows, info = map_tests.run(grid, frames, HEIGHT, A, use_offsets)
+            counts, rows, info = ring_frames.run_localise(grid, frames, HEIGHT, A, use_offsets)
             if cplx:
-                expected, numbers = map_tests.binned_records(grid.output_points, 2, HEIGHT, A, use_offsets)
+                expected, numbers = ring_frames.binned_records(grid.output_points, 2, HEIGHT, A, use_offsets)
             else:
                 expected, numbers = localisation_ref.accumulate(grid.output_points, frames, HEIGHT, A, use_offsets)
-            map_tests.same(counts, expected)
-            map_tests.check_rows(rows, numbers, frames, HEIGHT)
+            ring_frames.same_localise(counts, expected)
+            ring_frames.check_rows(rows, numbers, frames, HEIGHT)
             assert [n["found"] for n in numbers] == [len(plan["peaks"]), len(plan["peaks"]) - 1] and int(counts.sum()) == int(info.deposited)
 
     # pairs: x stretched by 3 and z by 2, so that the shift (1, 0, 2) is the displacement (3, 0, 4) of length 5 exactly
@@ -283,15 +249,15 @@ def test_plateaus_moved_by_a_known_shift_deposit_and_pair(points, cplx, bflib):
 
     def reference(reach, use_offsets, counts=None, sums=None):
         if cplx:
-            return tracks_ref.pair_records(tracks_tests.records_of(2, HEIGHT), S, reach, use_offsets, counts, sums)
-        return tracks_ref.pair_frames(frames, HEIGHT, S, reach, tracks_tests.CAP, use_offsets, counts=counts, sums=sums)
+            return tracks_ref.pair_records(ring_frames.peak_lists(2, HEIGHT), S, reach, use_offsets, counts, sums)
+        return tracks_ref.pair_frames(frames, HEIGHT, S, reach, ring_frames.CAP, use_offsets, counts=counts, sums=sums)
     for use_offsets in (False, True):
         bflib.track_map_reset(field)
-        rows, got = tracks_tests.pair(2, HEIGHT, S, 5.0, use_offsets=use_offsets, deposit=True)
+        rows, got = ring_frames.pair(2, HEIGHT, S, 5.0, use_offsets=use_offsets, deposit=True)
         counts, sums = tracks_ref.empty_map(field)
         want, numbers = reference(5.0, use_offsets, counts, sums)
-        tracks_tests.same_call(rows, got, want, numbers, 2, HEIGHT)
-        tracks_tests.same_map(field, counts, sums)
+        ring_frames.same_pairs_call(rows, got, want, numbers, 2, HEIGHT)
+        ring_frames.same_map(field, counts, sums)
         if not use_offsets:
             # every pair is a peak and its image: the displacement is exactly the shift, its distance^2 == reach^2 -- and pairs
             # with every peak of the second frame; the peak of the plateau that left the frame is the one without a partner
@@ -299,9 +265,9 @@ def test_plateaus_moved_by_a_known_shift_deposit_and_pair(points, cplx, bflib):
             assert numbers[0]["unpaired"] == [1, 0] and numbers[0]["pairs"] == len(plan["peaks"]) - 1
     # one ulp below the distance: nothing is within reach
     below = float(np.nextafter(np.float32(5.0), np.float32(0.0)))
-    rows, got = tracks_tests.pair(2, HEIGHT, S, below, use_offsets=False)
+    rows, got = ring_frames.pair(2, HEIGHT, S, below, use_offsets=False)
     want, numbers = reference(below, False)
-    tracks_tests.same_call(rows, got, want, numbers, 2, HEIGHT)
+    ring_frames.same_pairs_call(rows, got, want, numbers, 2, HEIGHT)
     assert len(got) == 0 and numbers[0]["pairs"] == 0
 
 
@@ -321,35 +287,35 @@ def test_integer_frames_give_the_int64_results(points, K, cplx, bflib):
     frames, ids = burst(stack)
     assert np.abs(frames.view(np.float32)).max() == 64 and (frames.view(np.float32) == np.rint(frames.view(np.float32))).all()
     # gram: the whole frame, and a box
-    G, _ = ensemble_tests.check_gram(frames, ids, what=which)
-    assert np.array_equal(G, host.gram_int64(frames).astype(np.complex128))
+    G, _ = ring_frames.check_gram(frames, ids, what=which)
+    assert np.array_equal(G, planted_ref.gram_int64(frames).astype(np.complex128))
     box = cut(points)
-    G, _ = ensemble_tests.check_gram(frames, ids, box, what=which + " box")
+    G, _ = ring_frames.check_gram(frames, ids, box, what=which + " box")
     (x0, y0, z0), (nx, ny, nz) = box
-    assert np.array_equal(G, host.gram_int64(frames[:, z0:z0 + nz, y0:y0 + ny, x0:x0 + nx]).astype(np.complex128))
+    assert np.array_equal(G, planted_ref.gram_int64(frames[:, z0:z0 + nz, y0:y0 + ny, x0:x0 + nx]).astype(np.complex128))
     # mix: K -> 3
-    W = host.integer_weights(3, K, cplx)
-    out, _ = ensemble_tests.check_mix(which, frames, ids, W, what=which)
-    mixed = host.mix_int64(frames, W)
-    assert same_values(out, host.to_kind(*mixed, cplx, frames.dtype))
+    W = planted_ref.integer_weights(3, K, cplx)
+    out, _ = ring_frames.check_mix(which, frames, ids, W, what=which)
+    mixed = planted_ref.mix_int64(frames, W)
+    assert same_values(out, planted_ref.to_kind(*mixed, cplx, frames.dtype))
     # autocorrelate: the identity form, and -- K == 3 -- behind the mix's weights
     for weights in ([None, W] if K == 3 else [None]):
         frames, ids = burst(stack)
-        out, _ = autocorr_tests.check_autocorr(which, frames, ids, weights, 3, what=which)
-        re, im = host.autocorr_int64(*(host.exact(frames) if weights is None else mixed), 3)
+        out, _ = ring_frames.check_autocorr(which, frames, ids, weights, 3, what=which)
+        re, im = planted_ref.autocorr_int64(*(planted_ref.exact(frames) if weights is None else mixed), 3)
         im[0] = 0
-        assert same_values(out, host.to_kind(re, im, cplx, frames.dtype))
+        assert same_values(out, planted_ref.to_kind(re, im, cplx, frames.dtype))
     # convolve: integer taps, ZERO mode
-    taps = (host.TAPS[0], None if points[1] == 1 else host.TAPS[1], host.TAPS[2])
+    taps = (planted_ref.TAPS[0], None if points[1] == 1 else planted_ref.TAPS[1], planted_ref.TAPS[2])
     frames, ids = burst(stack)
-    out, _ = spatial_tests.check_convolve(which, frames, ids, taps, what=which)
+    out, _ = ring_frames.check_convolve(which, frames, ids, taps, what=which)
     for k in range(K):
-        assert same_values(out[k], host.to_kind(*host.convolve_int64(frames[k], taps), cplx, frames.dtype)), k
+        assert same_values(out[k], planted_ref.to_kind(*planted_ref.convolve_int64(frames[k], taps), cplx, frames.dtype)), k
     # correlate: the three newest frames against the middle one
     frames, ids = burst(stack)
     window = (1, 0 if points[1] == 1 else 1, 2)
-    table, _, _ = motion_tests.check_call(frames[K - 3:], ids[K - 3:], 1, window, what=which)
-    want = host.correlate_int64(frames[K - 3:], 1, window)
+    table, _, _ = ring_frames.check_correlate(frames[K - 3:], ids[K - 3:], 1, window, what=which)
+    want = planted_ref.correlate_int64(frames[K - 3:], 1, window)
     for n, name in enumerate(("re", "im", "energy_reference", "energy_frame", "terms")):
         assert np.array_equal(table[0][name], want[n].astype(table[name].dtype)), name
 
@@ -372,35 +338,35 @@ def test_the_same_calls_on_frames_that_hold_the_special_voxels(points, bflib):
     # GRAM: "a voxel that is not finite in some frame counts in non_finite and in no entry"; the squares of FLT_MAX and of the
     # subnormals are doubles ("Each float is widened to double")
     for box in (None, cut(points)):
-        G, _ = ensemble_tests.check_gram(frames, ids, box, what=which)
+        G, _ = ring_frames.check_gram(frames, ids, box, what=which)
         assert np.isfinite(G.real).all() and G.real.max() >= float(planted.FLT_MAX) ** 2
     _, info, _ = bflib.gram_last_frames(3)
     assert (int(info.non_finite), int(info.voxels)) == (holes, frames[0].size - holes)
     # MIX: "no weight is skipped for being zero, so a voxel that is not finite in some frame is not finite in every output (plain
     # IEEE)": row 1 copies frame 1 but for 0 * inf and 0 * NaN; FLT_MAX - FLT_MAX + FLT_MAX stays FLT_MAX, the subnormals stay exact
-    out, _ = ensemble_tests.check_mix(which, frames, ids, SPECIAL_WEIGHTS, what=which)
+    out, _ = ring_frames.check_mix(which, frames, ids, SPECIAL_WEIGHTS, what=which)
     finite = np.isfinite(frames).all(axis=0)
     assert np.array_equal(out[1][finite].view(np.uint32), frames[1][finite].view(np.uint32)) and np.isnan(out[1][~finite]).all()
     assert int((~finite).sum()) == holes and (np.abs(out[0][finite]) == planted.FLT_MAX).any() and (np.abs(out[0]) == planted.SUB_MIN).any()
     # AUTOCORRELATE: "ONE float32 fmaf chain ... Plain IEEE otherwise": FLT_MAX * FLT_MAX is +inf although every source is finite
     # there, and the product of two subnormals is 0
     frames, ids = burst(stack)
-    out, _ = autocorr_tests.check_autocorr(which, frames, ids, None, 2, what=which)
+    out, _ = ring_frames.check_autocorr(which, frames, ids, None, 2, what=which)
     big = [p for p in plan["largest"]]
     assert all(np.isposinf(at(out[0], p)) for p in big) and all(at(out[0], p) == 0 for p in plan["subnormal"])
     # CONVOLVE, Zero mode: "a voxel that is not finite makes every output whose support covers it not finite, as the mix does"
     taps = (SPECIAL_TAPS[0], None if points[1] == 1 else SPECIAL_TAPS[1], SPECIAL_TAPS[2])
     frames, ids = burst(stack)
-    out, _ = spatial_tests.check_convolve(which, frames, ids, taps, what=which)
+    out, _ = ring_frames.check_convolve(which, frames, ids, taps, what=which)
     assert all(not np.isfinite(at(out[0], p)) for p in plan["non_finite"]) and np.isfinite(out[0]).sum() > out[0].size // 2
     # ... Normalised mode: "the terms of the non-finite source voxels SKIPPED": the holes are filled
     frames, ids = burst(stack)
     positive = tuple(None if h is None else np.abs(h) for h in taps)
-    out, _ = spatial_tests.check_convolve(which, frames, ids, positive, mode=spatial_tests.NORMALISED, what=which + " normalised")
+    out, _ = ring_frames.check_convolve(which, frames, ids, positive, mode=ring_frames.NORMALISED, what=which + " normalised")
     # CORRELATE: "ref[v] finite and f_k[v + s] finite": the terms leave the holes out, the sums are the Gram matrix's doubles
     frames, ids = burst(stack)
     window = (1, 0 if points[1] == 1 else 1, 1)
-    table, expected, _ = motion_tests.check_call(frames, ids, 1, window, [((0, 0, 0), points), cut(points)], what=which)
+    table, expected, _ = ring_frames.check_correlate(frames, ids, 1, window, [((0, 0, 0), points), cut(points)], what=which)
     centre = (0, 1, window[2], window[1], window[0])
     assert int(table["terms"][centre]) == frames[0].size - holes and table["re"][centre] == table["energy_reference"][centre] > float(planted.FLT_MAX) ** 2
 
@@ -431,12 +397,12 @@ def test_warp_by_a_zero_field_and_by_an_integer_shift(name, points, cplx, bflib)
     stack = [make(name, points, cplx, seed)[0] for seed in (0, 1)]
     plan = make(name, points, cplx)[1]
     for shift in ((0, 0, 0), (2, 0 if points[1] == 1 else -1, -3)):
-        for interpolation in (warp_tests.LINEAR, warp_tests.CUBIC):
+        for interpolation in (ring_frames.LINEAR, ring_frames.CUBIC):
             frames, ids = burst(stack)
             present(frames[0], plan)
             case = dict(field=np.array([shift, [-s for s in shift]], np.float32).reshape(2, 1, 1, 1, 3), nodes=(1, 1, 1), node_first=(0, 0, 0), node_step=(1, 1, 1))
-            out, _, _, _ = warp_tests.check_warp(which, frames, ids, case, None, interpolation, warp_tests.ZERO, what=f"{name} {points} moved by {shift}", same_masks=True)
-            reach = (0, 1) if interpolation == warp_tests.LINEAR else (1, 2)
+            out, _, _, _ = ring_frames.check_warp(which, frames, ids, case, None, interpolation, ring_frames.WARP_ZERO, what=f"{name} {points} moved by {shift}", same_masks=True)
+            reach = (0, 1) if interpolation == ring_frames.LINEAR else (1, 2)
             for n, sign in ((0, 1), (1, -1)):
                 d = tuple(sign * s for s in shift)
                 clean = support_is_finite(frames[n], d, reach)

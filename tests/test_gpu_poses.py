@@ -18,9 +18,10 @@ from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import cases, draws, poses
 from tests import variants_cases as vc
-from tests.test_gpu_burst import check_burst, noise_frames
-from tests.test_gpu_parity import FACTORED, HERCULES, STAGED, TILE, compare, last_timings, reference
-from tests.test_gpu_views import REACHED_DEPTH, box, inner, on_grid
+from tests.das_kernel_cases import FACTORED, HERCULES, STAGED, TILE
+from tests.das_push import box, check_burst, compare, inner, last_timings, noise_frames, on_grid, REACHED_DEPTH
+from tests.parity import reference
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 I = P.InterpolationMode
@@ -42,13 +43,9 @@ def posed_reference(name, pose):
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def pair_counting_off(automatic_path, bflib):
     yield
-    L.beamformer_hip_enable_pair_counting(0)
-    L.beamformer_hip_set_das_path(0)
+    bflib.library().beamformer_hip_enable_pair_counting(0)
 
 
 def check(bflib, name, pose, mode, want=None, label=None):
@@ -182,7 +179,7 @@ def test_pair_count_matches_oracle(pose, name, bflib):
 # ---- the fused multi-frame kernels restate voxel-to-point: one posed acquisition each
 
 FUSED_POSES = ("tilt_both", "combo")
-FUSED_CASE = "rca_cubic_real"          # of BURST_KERNEL_CASES and of test_gpu_views.py's KERNEL_CASES: single frames run the general kernel
+FUSED_CASE = "rca_cubic_real"          # of BURST_KERNEL_CASES and of tests/das_push.py's KERNEL_CASES: single frames run the general kernel
 PREFER_VIEWS, NO_VIEWS = P.HIP_DAS_PATH_PREFER_VIEWS_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL
 
 

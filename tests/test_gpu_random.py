@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import params as P
+from tests.das_push import compare, last_das_path, last_timings
 from tests.draws import K, draw, draw_plane, draw_separable, draw_tile  # noqa: F401  (the generators live in tests/draws.py)
-from tests.test_gpu_parity import compare, last_das_path, last_timings, reference
+from tests.parity import reference
 
 pytestmark = pytest.mark.gpu
 

@@ -14,8 +14,9 @@ import pytest
 from ogl_beamforming_amd import params as P
 from tests import cases
 from tests import readi_image_cases as R
-from tests.test_gpu_burst import noise_frames, same_bits
-from tests.test_gpu_parity import compare, last_timings, reference
+from tests.das_push import compare, last_timings, noise_frames, same_bits
+from tests.parity import reference
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
@@ -64,13 +65,10 @@ def image(bflib, acq, rf, groups, device_pointer=None):
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
+def two_parameter_blocks(automatic_path, bflib):
     L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
     L.beamformer_reserve_parameter_blocks(2)
     yield
-    L.beamformer_hip_set_das_path(0)
     L.beamformer_reserve_parameter_blocks(1)
 
 

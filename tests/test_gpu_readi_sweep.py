@@ -15,30 +15,15 @@ import pytest
 from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import params as P
 from tests import cases
-from tests.test_gpu_burst import close_to_single_push, noise_frames, same_bits
-from tests.test_gpu_parity import compare, reference
+from tests.das_push import close_to_single_push, compare, GEOMETRIES, GROUPS5, groups_for, noise_frames, S, same_bits, sweep_case
+from tests.parity import reference
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
 I = P.InterpolationMode
-S = P.ShaderKind
-LO, HI = (-1e-3, 0, 5e-3), (1e-3, 0, 9e-3)          # the `readi` case's extent (tests/cases.py LO3 / HI3)
 
-# (readi_group_count, acquisition_count, voxels): G x A = 16 transmit elements on 16 channels
-GEOMETRIES = {"g4a4": (4, 4, (16, 1, 16)), "g2a8": (2, 8, (24, 1, 20)), "g8a2": (8, 2, (32, 1, 32))}
-GROUPS5 = [2, 0, 3, 3, 1]                            # not monotone, with a repeat; taken modulo G
 GROUPS9 = [1, 3, 0, 0, 2, 3, 1, 2, 0]
-
-
-def sweep_case(geometry, interp, iq, cw):
-    G, A, points = GEOMETRIES[geometry]
-    name = f"readi_sweep_{geometry}_{interp.name.lower()}_{'iq' if iq else 'real'}{'_cw' if cw else ''}"
-    seed = 3300 + 16 * list(GEOMETRIES).index(geometry) + 4 * int(interp) + 2 * iq + cw
-    if iq:       # Int16 through Demodulate: IQ samples
-        return cfg.forces(name, 16, A, 512, points, LO, HI, seed=seed, interp=interp, cw=cw, decode=0, readi_groups=G, readi_group=1,
-                          stages=(S.Demodulate, S.DAS))
-    return cfg.forces(name, 16, A, 512, points, LO, HI, seed=seed, interp=interp, cw=cw, decode=0, readi_groups=G, readi_group=1,
-                      data_kind=P.DataKind.Float32)
 
 
 # every interpolation x kind x cw once, the geometries dealt round
@@ -65,10 +50,6 @@ def with_group(acq, group, rf=None):
     bp = type(acq.bp).from_buffer_copy(acq.bp)
     bp.readi_group = int(group)
     return dataclasses.replace(acq, bp=bp, rf=acq.rf if rf is None else rf)
-
-
-def groups_for(acq, groups):
-    return [g % int(acq.bp.readi_group_count) for g in groups]
 
 
 _REFERENCES = {}
@@ -119,15 +100,6 @@ def single_push(bflib, acq, rf, group):
     """a parameter push with the group, then a single push of the RF"""
     one = with_group(acq, group)
     return bflib.beamform(one.bp, np.ascontiguousarray(rf), acq.filters).copy()
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
 
 
 @pytest.mark.parametrize("n", [5, 9])

@@ -9,53 +9,26 @@ The bar is derived, not measured: tests/spatial_ref.py returns it with the value
 kinds, tags, finite masks and every case the definition makes exact are asked exactly.  Every test prints what it measured -- the worst
 error as a share of its bound -- before it asserts."""
 import ctypes as C
-import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import frame_peaks_ref
 from tests import spatial_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_autocorr import burst_info_unchanged
-from tests.test_gpu_ensemble import block, ensemble, loop_case, newest_id, rf_frames
-from tests.test_gpu_frame_metrics import block as metrics_block, newest_info
-from tests.test_gpu_frame_peaks import check_call
+from tests.frame_info import newest_id, newest_info
+from tests.ring_frames import (block, spatial_block_of as block_of, burst_info_unchanged, check_peaks as check_call, check_convolve, ensemble,
+                               loop_case, metrics_block, NORMALISED, rf_frames, SPATIAL_ZERO as ZERO)
+from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-D = P.DataKind
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ZERO, NORMALISED = int(P.HipSpatialMode.Zero), int(P.HipSpatialMode.Normalised)
-ROWS = (273, 3, 5)
-COLUMN = (1, 5, 9)                 # one x point: the y axis is the contiguous one, and spatial_row_kernel runs it
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
-
-
-@functools.lru_cache(maxsize=None)
-def block_of(which):
-    if which not in ("rows", "column"):
-        return block(which)
-    return cfg.rca("spatial_" + which, 16, 2, 256, ROWS if which == "rows" else COLUMN, vc.LO3, vc.HI3, seed=7500, interp=P.InterpolationMode.Linear, demodulate=False,
-                   data_kind=D.Float32Complex, angles=np.array([-6.0, 6.0]), kind=P.AcquisitionKind.RCA_TPW)
 
 
 def frames_of(which, K):
-    """K frames of the grid (tests/test_gpu_ensemble.py's ensemble; "rows", "column": the same by this file's blocks): (frames (K, Z, Y, X), ids)"""
+    """K frames of the grid (tests/ring_frames.py's ensemble; "rows", "column": the same by this file's blocks): (frames (K, Z, Y, X), ids)"""
     if which not in ("rows", "column"):
         return ensemble(which, K)
     acq = block_of(which)
@@ -76,48 +49,6 @@ def taps_of(counts, seed, positive=False):
         h = rng.uniform(0.1, 1.0, n) if positive else rng.standard_normal(n)
         out.append((h * np.linspace(1.0, 2.0, n)).astype(np.float32))
     return out
-
-
-def finite_parts(a):
-    return (np.isfinite(a.real), np.isfinite(a.imag)) if np.iscomplexobj(a) else (np.isfinite(a),)
-
-
-def check_convolve(which, frames, ids, taps, mode=ZERO, tag=0, what=""):
-    """filter the len(frames) newest frames and check the outputs and their records; returns (outputs, first id)"""
-    acq = block_of(which)
-    K = len(frames)
-    real = not np.iscomplexobj(frames)
-    source_block = int(bf.frame_info(ids[-1]).parameter_block)
-    first, ms = bf.convolve_last_frames(K, taps, mode, tag=tag)
-    out = bf.get_last_frames(acq.bp, K).copy()
-    assert out.shape == frames.shape and out.dtype == frames.dtype and ms > 0
-    worst, inside, masks, holes = 0.0, True, True, 0
-    for n in range(K):
-        values, bound = ref.convolve(frames[n], taps, mode)
-        w, i = ref.share_of_bound(out[n], values, bound)
-        worst, inside = max(worst, w), inside and i
-        # finite exactly where the reference is: Zero mode, where no voxel under the taps is not finite; Normalised, where D > 0
-        masks = masks and all(np.array_equal(g, x) for g, x in zip(finite_parts(out[n]), finite_parts(values)))
-        holes += int((~finite_parts(values)[0]).sum())
-    counts = [0 if h is None else len(h) for h in taps]
-    print(f"  {what}: K {K}, taps {counts}, mode {mode}, {'real' if real else 'complex'} {frames.shape[1:]}: worst error {worst:.4f} of its bound, "
-          f"{holes} real parts not finite, {ms * 1e3:.1f} us")
-    assert inside and masks
-    # the records: consecutive ids behind the sources, the grid, the kind, the tag, the newest source's block
-    assert first == ids[-1] + 1 and int(newest_info(bf.library()).frame_id) == first + K - 1
-    scores, _ = bf.score_last_frames(K)
-    pz, py, px = frames.shape[1:]
-    for j in range(K):
-        info = bf.frame_info(first + j)
-        assert (int(info.frame_id), tuple(info.points), int(info.parameter_block)) == (first + j, (px, py, pz), source_block)
-        assert int(info.data_kind) == int(D.Float32 if real else D.Float32Complex)
-        assert (int(scores[j].frame_id), int(scores[j].image_plane_tag), int(scores[j].parameter_block)) == (first + j, tag, source_block)
-    # their rows of the timing table: no stages, no DAS voxels
-    t = P.HipFrameTimings()
-    assert bf.library().beamformer_hip_get_last_frame_timings(C.byref(t)) and t.stage_count == 0 and t.das_voxels == 0
-    # a source frame is still served by its id
-    assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))
-    return out, first
 
 
 # (grid, K, tap counts x / y / z): every count of 1, 3, 9, 33 on every kind of axis, mixed per axis; counts larger than the axis's
@@ -410,24 +341,13 @@ def test_several_devices_are_refused(bflib):
     L = bflib.library()
     acq = vc.separable_volume()
     box = [np.full(3, 1 / 3, np.float32)] * 3
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq):
         refused(L, 1, box, ZERO, E.InvalidAccess)
         refused(L, 1, box, NORMALISED, E.InvalidAccess)
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     frames, ids = ensemble("plane", 2)
     check_convolve("plane", frames, ids, box[:1] + [None, box[2]], what="one device again")
 
 
 def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/spatial_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "spatial_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "refused" in run.stdout and "wrapped" in run.stdout, run.stdout
+    run_ring_worker("spatial_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

@@ -8,8 +8,8 @@ import pytest
 
 from ogl_beamforming_amd import configs as cfg
 from tests import cases, draws
-from tests.test_gpu_multi_device import same_bits, use_devices
-from tests.test_gpu_parity import compare, last_das_path, last_timings, reference
+from tests.das_push import compare, run, same_bits, use_devices
+from tests.parity import reference
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +31,6 @@ NAMED = ["config4_small", "rca_staged_fine"]
 
 def make(name):
     return EXTRA[name]() if name in EXTRA else cases.make(name)
-
-
-def run(bflib, acq):
-    frame = bflib.beamform(acq.bp, acq.rf, acq.filters).copy()
-    return frame, last_das_path(bflib), last_timings(bflib).staged_window_violations
 
 
 @pytest.mark.parametrize("name", NAMED + sorted(EXTRA))

@@ -17,8 +17,8 @@ import pytest
 
 from ogl_beamforming_amd import configs as cfg
 from tests import cases
-from tests.test_gpu_multi_device import same_bits
-from tests.test_gpu_parity import compare, last_das_path, last_timings, reference
+from tests.das_push import compare, last_das_path, last_timings, same_bits
+from tests.parity import reference
 
 pytestmark = pytest.mark.gpu
 

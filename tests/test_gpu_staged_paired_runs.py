@@ -35,10 +35,8 @@ import pytest
 from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
-from tests.test_gpu_multi_device import same_bits
-from tests.test_gpu_parity import compare, last_timings, reference
-from tests.test_gpu_staged_paired import run
-from tests.test_gpu_staged_paired_tail import lds_bytes, plan
+from tests.das_push import compare, last_timings, lds_bytes, plan, run, same_bits
+from tests.parity import reference
 
 PITCH, FS, F_NUMBER = 0.3e-3, 25e6, 0.8
 U_SPAN, V_SPAN = 4e-3, 1.2e-3              # half extents of the grid along the receive and the transmit axis

@@ -23,11 +23,9 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import configs as cfg
-from ogl_beamforming_amd import lib as bf
 from tests import cases
-from tests.test_gpu_multi_device import same_bits
-from tests.test_gpu_parity import compare, reference
-from tests.test_gpu_staged_paired import run
+from tests.das_push import compare, lds_bytes, plan, run, same_bits
+from tests.parity import reference
 
 LO3, HI3 = cases.LO3, cases.HI3
 
@@ -48,23 +46,6 @@ CASES = {
     "a66_second_group_even_short_rows": (lambda: rca("tail_a66", 32, 66, 384, (150, 40, 2), 87, 0x12, True), (48, 20), 18),
     "a75_second_group_odd": (lambda: rca("tail_a75", 33, 75, 512, (45, 150, 2), 88, 0x21, True), (48, 28), 27),
 }
-
-
-def lds_bytes(group, chunk, a4):
-    """bf_staged_paired_lds_bytes (bf_kernels.h), restated"""
-    return (16 * (group * 64 + 3) + 16 * (((chunk + 1) & ~1) << 5) + 4 * (a4 + 2 * (chunk + 2)) + 128 + 15) & ~15
-
-
-def plan(acq):
-    """the plan of the frame with the paired shape asked for (beamformer_hip_describe_das needs no device)"""
-    lib = bf.library()
-    bf.set_hook("STAGED_SHAPE", "5,5,5")
-    lib.beamformer_hip_set_das_path(3)
-    try:
-        return bf.describe_das(acq.bp, acq.filters)[4]
-    finally:
-        lib.beamformer_hip_set_das_path(0)
-        bf.set_hook("STAGED_SHAPE", None)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

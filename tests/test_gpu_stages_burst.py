@@ -12,7 +12,7 @@ One burst of n = 5 independent noise frames with the SCRATCH_POISON hook set; fo
      arithmetic is exact, else inside the propagated forward-error bound -- nothing new);
   4. the frame meets compare() against the oracle; on the per-frame route (the single push's DAS kernel, free of floating-point
      atomics, on the same input bits) it is also bit-identical to the single push's frame, on the burst kernel within the tolerance
-     tests/test_gpu_burst.py's check_burst uses;
+     tests/das_push.py's check_burst uses;
   5. the poisoned burst's frames equal an unpoisoned burst's, bit for bit.
 
 The chunk boundary (tests/burst_chunk_cases.py): three bursts of 257 frames of 256 channels, built from four distinct RF frames, whose
@@ -24,55 +24,16 @@ import pytest
 
 from ogl_beamforming_amd import params as P
 from tests import burst_chunk_cases, cases
-from tests import test_gpu_stages as stages
-from tests import test_hilbert as hilbert_cases
-from tests.test_gpu_burst import close_to_single_push, noise_frames, same_bits
-from tests.test_gpu_parity import compare
-from tests.test_hilbert import hilbert  # noqa: F401  (the fixture that enables the stage in the library and the oracle)
+from tests import stage_checks as stages
+from tests.das_push import close_to_single_push, compare, noise_frames, same_bits
+from tests.stage_checks import hilbert  # noqa: F401  (the fixture that enables the stage in the library and the oracle)
+from tests.stage_checks import first_difference, nan_free, push_burst
 
 pytestmark = pytest.mark.gpu
 
 DK = P.DataKind
 N = 5
 as_bits = stages.as_bits
-
-
-def nan_free(acq, das_in, label):
-    """bar 1, with check_das_input's message"""
-    nan = np.isnan(das_in)
-    if nan.any():
-        c, t, s = np.argwhere(nan)[0]
-        raise AssertionError(f"{label}: {int(nan.sum())} DAS-input elements are NaN (read without having been written this frame), "
-                             f"first at channel {c} transmit {t} sample {s} of {das_in.shape[2]} "
-                             f"(decimation {acq.bp.decimation_rate}: samples [{das_in.shape[2] // max(1, acq.bp.decimation_rate)}, "
-                             f"{das_in.shape[2]}) are the filter's tail)")
-
-
-def first_difference(a, b):
-    diff = as_bits(a) != as_bits(b)
-    return f"{int(diff.sum())} scalars differ, first at {np.argwhere(diff)[0]} of {diff.shape}"
-
-
-def push_burst(bflib, hooks, acq, rf, mode, poison=True):
-    """(frames, [DAS input of frame k], route) of one burst of the RF frames `rf`"""
-    L = bflib.library()
-    if poison:
-        hooks.set("SCRATCH_POISON")
-    else:
-        hooks.clear("SCRATCH_POISON")
-    L.beamformer_hip_set_das_path(mode)
-    try:
-        frames = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
-        route = bflib.last_burst_info().route
-        inputs = [bflib.das_input(acq.bp, k) for k in range(len(rf))]
-        newest = bflib.das_input(acq.bp)
-        with pytest.raises(bflib.BeamformerError) as refused:
-            bflib.das_input(acq.bp, len(rf))
-    finally:
-        L.beamformer_hip_set_das_path(0)
-    assert refused.value.kind == P.LibError.InvalidAccess, "a frame index past the burst's frames is InvalidAccess"
-    assert np.array_equal(as_bits(newest), as_bits(inputs[-1])), "beamformer_hip_copy_das_input after a burst: not the last frame's"
-    return frames, inputs, route
 
 
 def burst_case(bflib, oracle, hooks, acq, modes=(0,), seed=0, each_reference=None):
@@ -178,9 +139,9 @@ def test_float16_complex_rf(pipeline, bflib, oracle, hooks):
 
 # ------------------------------------------------------------------------------------------------ Hilbert
 
-@pytest.mark.parametrize("name", sorted(hilbert_cases.acquisitions()) + [f"ragged_{n}" for n in hilbert_cases.RAGGED_SAMPLES])
+@pytest.mark.parametrize("name", sorted(stages.acquisitions()) + [f"ragged_{n}" for n in stages.RAGGED_SAMPLES])
 def test_hilbert_stage(name, bflib, oracle, hooks, hilbert):  # noqa: F811
-    acq = hilbert_cases.ragged_acquisition(int(name[7:])) if name.startswith("ragged_") else hilbert_cases.acquisitions()[name]
+    acq = stages.ragged_acquisition(int(name[7:])) if name.startswith("ragged_") else stages.acquisitions()[name]
     burst_case(bflib, oracle, hooks, acq, seed=400 + len(name))
 
 

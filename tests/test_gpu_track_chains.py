@@ -1,7 +1,7 @@
 """Peak tracks on the device (beamformer_hip_track_peaks_last_frames; csrc/frame_tracks.hip: link, jump, keep, scan, finish).  Frames are
-PLANTED (tests/planted.py) by one burst push, as tests/test_gpu_planted.py does it: a frame then is the array, and the numpy reference
-(tests/track_chains_ref.py) runs on the downloaded frames; the plans are tests/test_track_chains_host.py's, which checks without a
-device that they hold what they claim.  On complex frames the reference chains the records beamformer_hip_find_peaks_last_frames
+PLANTED (tests/planted.py) by one burst push (tests/ring_frames.py planted_burst): a frame then is the array, and the numpy reference
+(tests/track_chains_ref.py) runs on the downloaded frames; the plans are tests/track_plans.py's, and tests/test_track_chains_host.py checks
+without a device that they hold what they claim.  On complex frames the reference chains the records beamformer_hip_find_peaks_last_frames
 returns (tests/test_gpu_tracks.py says why: a magnitude may differ from numpy's by 1 ulp).
 
 Everything compared is an integer or a bit pattern and is asked exactly: there is no tolerance in this file."""
@@ -13,29 +13,25 @@ import pytest
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import localisation_ref, planted, tracks_ref
-from tests import test_gpu_tracks as tracks_tests
-from tests import test_track_chains_host as host
+from tests import ring_frames
+from tests import track_plans
 from tests import track_chains_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import block, newest_info, region_of, variants_push
-from tests.test_gpu_frame_peaks import fraction_of_max
-from tests.test_gpu_localisation import finer, map_view, placement_onto
-from tests.test_gpu_planted import burst
+from tests.frame_info import newest_info
+from tests.ring_frames import (metrics_block as block, planted_burst as burst, finer, fraction_of_max, fresh_maps, map_view, placement_onto,
+                               same_tracks_call as same_call, same_maps, track, variants_push)
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-IDENTITY, LEVEL, REACH, CAP = host.IDENTITY, host.LEVEL, host.REACH, tracks_tests.CAP
+IDENTITY, LEVEL, REACH, CAP = track_plans.IDENTITY, track_plans.LEVEL, track_plans.REACH, ring_frames.CAP
 POINTS, LINKS = P.HIP_TRACK_DEPOSIT_POINTS, P.HIP_TRACK_DEPOSIT_LINKS
 FIELD = (20, 1, 40)                                        # both maps over the plane plan: its spots at x = 20, 21 and 22 lie outside
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def maps_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
     bflib.track_map_reset(None)
 
@@ -43,50 +39,9 @@ def automatic_path(bflib):
 @pytest.fixture
 def plane(bflib):
     """the plane plan on the device: the 11 downloaded frames"""
-    stack, _ = host.plane_plan()
+    stack, _ = track_plans.plane_plan()
     frames, _ = burst(stack)
     return list(frames)
-
-
-def track(count, thresholds, placements, reach, min_length, cap=CAP, use_offsets=True, deposit=0, box=None):
-    rows, tracks, points, ms = bf.track_peaks_last_frames(count, thresholds, placements, reach, cap, min_length, use_offsets, deposit, region_of(box))
-    assert ms > 0
-    return rows, np.frombuffer(bytes(tracks), ref.TRACK), np.frombuffer(bytes(points), ref.POINT)
-
-
-def expected_rows(numbers, count, thresholds, cap, box=None):
-    """the rows the call owes: the reference's numbers, and find_peaks' ids and counts of the same frames"""
-    found, _, _ = bf.find_peaks_last_frames(count, thresholds, cap, region_of(box))
-    levels = tracks_ref.each(np.asarray(thresholds, np.float32), count)
-    rows = (P.HipTrackedFrame * count)()
-    for row, want, peaks, level in zip(rows, numbers, found, levels):
-        row.frame_id, row.threshold, row.peaks, row.found, row.unplaced = peaks.frame_id, float(level), peaks.stored, peaks.found, want["unplaced"]
-        assert int(peaks.stored) == want["peaks"] and ("found" not in want or int(peaks.found) == want["found"])
-        for name in ref.COUNTERS:
-            setattr(row, name, want[name])
-    return rows
-
-
-def same_call(got, want, count, thresholds, cap=CAP, box=None):
-    """the tracks, the points and the rows, byte for byte"""
-    rows, tracks, points = got
-    print(f"  {len(want['tracks'])} of {len(want['lengths'])} tracks kept, {len(want['points'])} points; lengths {sorted(want['lengths'])[-12:]}")
-    assert tracks.tobytes() == want["tracks"].tobytes(), f"{len(tracks)} tracks against {len(want['tracks'])}"
-    assert points.tobytes() == want["points"].tobytes(), f"{len(points)} points against {len(want['points'])}"
-    assert bytes(rows) == bytes(expected_rows(want["rows"], count, thresholds, cap, box))
-
-
-def fresh_maps(field):
-    """both maps of the device reset to `field`, and the reference's: (density, counts, sums)"""
-    bf.localisation_map_reset(field)
-    bf.track_map_reset(field)
-    return (np.zeros(field[::-1], np.uint32),) + tracks_ref.empty_map(field)
-
-
-def same_maps(field, density, counts, sums):
-    got, info = bf.localisation_map_copy(field)
-    assert got.tobytes() == density.tobytes(), f"{int((got != density).sum())} bins of the localisation map differ"
-    return info, tracks_tests.same_map(field, counts, sums)
 
 
 # ----------------------------------------------------------------------------- 1: the plane plan
@@ -110,7 +65,7 @@ def test_the_plane_plan_at_four_lengths_with_every_deposit(min_length, plane, bf
             ((1, sum(r["kept_links"] for r in rows), sum(r["links_deposited"] for r in rows), sum(r["links_outside"] for r in rows)) if deposit & LINKS else (0, 0, 0, 0))
         assert int(density.sum()) == int(point_info.deposited) and int(counts.sum()) == int(link_info.deposited)
     if min_length in (3, 9):
-        host.teeth(want, min_length, K)
+        track_plans.teeth(want, min_length, K)
         assert int(point_info.outside) + int(link_info.outside) >= (1 if min_length == 3 else 0)
     elif min_length == 1:
         assert len(want["tracks"]) == 9 and int(point_info.outside) == 4 and int(link_info.outside) == 2
@@ -121,7 +76,7 @@ def test_the_plane_plan_at_four_lengths_with_every_deposit(min_length, plane, bf
 # ----------------------------------------------------------------------------- 2: more than 512 peaks a frame
 
 def test_a_lattice_of_more_than_512_peaks_a_frame(bflib):
-    stack, placements = host.volume_plan()
+    stack, placements = track_plans.volume_plan()
     frames, _ = burst(stack)
     K, field = len(frames), (12, 16, 32)                       # both maps end at x = 12: the lattice's last columns lie outside
     density, counts, sums = fresh_maps(field)
@@ -145,7 +100,7 @@ def test_the_three_equalities_with_the_pair_call_and_the_accumulate_call(plane, 
     K = len(plane)
     # (i) min_length <= 2 with LINKS: the track map's bytes are the pair call's
     bf.track_map_reset(FIELD)
-    pair_rows, pairs = tracks_tests.pair(K, LEVEL, IDENTITY, REACH, deposit=True)
+    pair_rows, pairs = ring_frames.pair(K, LEVEL, IDENTITY, REACH, deposit=True)
     of_the_pairs = bf.track_map_copy(FIELD)
     assert int(of_the_pairs[2].pairs) == len(pairs) == 37 and int(of_the_pairs[2].outside) == 2
     for min_length in (1, 2):
@@ -187,7 +142,7 @@ def test_complex_frames_chain_as_their_find_peaks_records_say(bflib):
     for min_length, use_offsets in ((1, True), (2, True), (3, True), (2, False)):
         density, counts, sums = fresh_maps(field)
         got = track(3, thresholds, A, 6.0, min_length, use_offsets=use_offsets, deposit=POINTS | LINKS)
-        want = ref.chain_records(tracks_tests.records_of(3, thresholds), A, 6.0, min_length, use_offsets, deposit=POINTS | LINKS,
+        want = ref.chain_records(ring_frames.peak_lists(3, thresholds), A, 6.0, min_length, use_offsets, deposit=POINTS | LINKS,
                                  point_map=density, counts=counts, sums=sums)
         same_call(got, want, 3, thresholds)
         same_maps(field, density, counts, sums)
@@ -225,7 +180,7 @@ def test_an_unplaced_frame_a_cap_a_box_and_no_offsets(plane, bflib):
         assert sorted(want["lengths"]) == [1, 2, 5, 6, 8, 9]
     # per-frame thresholds: frame 6 asks for more than the spots' height, and has no peak
     levels = np.full(K, LEVEL, np.float32)
-    levels[6] = 2 * host.HEIGHT
+    levels[6] = 2 * track_plans.HEIGHT
     got = track(K, levels, IDENTITY, REACH, 1)
     want = ref.chain_frames(plane, levels, IDENTITY, REACH, CAP, 1)
     same_call(got, want, K, levels)

@@ -1,7 +1,7 @@
 """Drawn tracks on the device (beamformer_hip_draw_tracks_last_frames; csrc/frame_tracks.hip: smooth, draw, behind the chain's
 launches).  Frames are PLANTED (tests/planted.py) by one burst push, as tests/test_gpu_track_chains.py does it, and the numpy reference
-(tests/track_draw_ref.py) runs on the downloaded frames; the plans are tests/test_track_chains_host.py's and
-tests/test_track_draw_host.py's, which checks without a device that they hold what they claim.  On complex frames the reference draws
+(tests/track_draw_ref.py) runs on the downloaded frames; the plans are tests/track_plans.py's, and tests/test_track_chains_host.py and
+tests/test_track_draw_host.py check without a device that they hold what they claim.  On complex frames the reference draws
 the records beamformer_hip_find_peaks_last_frames returns.
 
 Everything compared is an integer or a bit pattern and is asked exactly: there is no tolerance in this file."""
@@ -13,32 +13,25 @@ import pytest
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import localisation_ref, tracks_ref
-from tests import test_gpu_track_chains as chain_tests
-from tests import test_gpu_tracks as tracks_tests
-from tests import test_track_chains_host as chain_host
-from tests import test_track_draw_host as host
+from tests import ring_frames
+from tests import track_plans
 from tests import track_draw_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import block, newest_info, region_of, variants_push
-from tests.test_gpu_frame_peaks import fraction_of_max
-from tests.test_gpu_localisation import finer, map_view, placement_onto
-from tests.test_gpu_planted import burst
+from tests.frame_info import newest_info
+from tests.ring_frames import (metrics_block as block, planted_burst as burst, draw, finer, fraction_of_max, fresh_point_and_track_maps as fresh_maps,
+                               LINKS, map_view, placement_onto, POINTS, same_infos, same_point_and_track_maps as same_maps, same_rows, variants_push)
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-IDENTITY, LEVEL, REACH, CAP = host.IDENTITY, host.LEVEL, host.REACH, tracks_tests.CAP
-POINTS, LINKS = P.HIP_TRACK_DEPOSIT_POINTS, P.HIP_TRACK_DEPOSIT_LINKS
-FOUR = host.scaled(4)
-FIELD4 = host.times(host.PLANE_FIELD, 4)                    # both maps over the plane plan, 4 x finer: its spots beyond x = 20 draw partly outside
+IDENTITY, LEVEL, REACH, CAP = track_plans.IDENTITY, track_plans.LEVEL, track_plans.REACH, ring_frames.CAP
+FOUR = track_plans.scaled(4)
+FIELD4 = track_plans.times(track_plans.PLANE_FIELD, 4)                    # both maps over the plane plan, 4 x finer: its spots beyond x = 20 draw partly outside
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def maps_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
     bflib.track_map_reset(None)
 
@@ -46,7 +39,7 @@ def automatic_path(bflib):
 @pytest.fixture
 def plane(bflib):
     """the plane plan on the device: the 11 downloaded frames"""
-    stack, _ = chain_host.plane_plan()
+    stack, _ = track_plans.plane_plan()
     frames, _ = burst(stack)
     return list(frames)
 
@@ -54,60 +47,9 @@ def plane(bflib):
 @pytest.fixture
 def own(bflib):
     """the draw plan on the device: the 6 downloaded frames"""
-    stack, _ = host.draw_plan()
+    stack, _ = track_plans.draw_plan()
     frames, _ = burst(stack)
     return list(frames)
-
-
-def draw(count, thresholds, placements, reach, min_length, smooth, cap=CAP, use_offsets=True, deposit=0, box=None):
-    rows, ms = bf.draw_tracks_last_frames(count, thresholds, placements, reach, cap, min_length, smooth, use_offsets, deposit, region_of(box))
-    assert ms > 0
-    return rows
-
-
-def expected_rows(numbers, count, thresholds, cap, box=None):
-    """the rows the call owes: the reference's numbers, and find_peaks' ids and counts of the same frames"""
-    found, _, _ = bf.find_peaks_last_frames(count, thresholds, cap, region_of(box))
-    levels = tracks_ref.each(np.asarray(thresholds, np.float32), count)
-    rows = (P.HipDrawnFrame * count)()
-    for row, want, peaks, level in zip(rows, numbers, found, levels):
-        row.frame_id, row.threshold, row.peaks, row.found, row.unplaced = peaks.frame_id, float(level), peaks.stored, peaks.found, want["unplaced"]
-        assert int(peaks.stored) == want["peaks"] and ("found" not in want or int(peaks.found) == want["found"])
-        for name in ref.COUNTERS:
-            setattr(row, name, want[name])
-    return rows
-
-
-def same_rows(rows, want, count, thresholds, cap=CAP, box=None):
-    owed = expected_rows(want["rows"], count, thresholds, cap, box)
-    if bytes(rows) != bytes(owed):
-        for n, (a, b) in enumerate(zip(rows, owed)):
-            print(n, [(name, getattr(a, name), getattr(b, name)) for name, _ in P.HipDrawnFrame._fields_ if getattr(a, name) != getattr(b, name)])
-    assert bytes(rows) == bytes(owed)
-
-
-def fresh_maps(point_field, track_field):
-    """both maps of the device reset, and the reference's: (density, counts, sums)"""
-    bf.localisation_map_reset(point_field)
-    bf.track_map_reset(track_field)
-    return (np.zeros(point_field[::-1], np.uint32),) + tracks_ref.empty_map(track_field)
-
-
-def same_maps(point_field, track_field, density, counts, sums):
-    got, info = bf.localisation_map_copy(point_field)
-    assert got.tobytes() == density.tobytes(), f"{int((got != density).sum())} bins of the localisation map differ"
-    return info, tracks_tests.same_map(track_field, counts, sums)
-
-
-def same_infos(point_info, link_info, calls, rows, deposit):
-    """the maps' totals after `calls` equal calls on fresh maps"""
-    total = ref.totals(rows)
-    drawn = total["samples"] - total["repeats"]
-    assert (point_info.calls, int(point_info.deposited), int(point_info.outside)) == \
-        ((calls, calls * total["points_deposited"], calls * total["points_outside"]) if deposit & POINTS else (0, 0, 0))
-    assert (link_info.calls, int(link_info.pairs), int(link_info.deposited), int(link_info.outside)) == \
-        ((calls, calls * drawn, calls * total["links_deposited"], calls * total["links_outside"]) if deposit & LINKS else (0, 0, 0, 0))
-    assert int(link_info.pairs) == int(link_info.deposited) + int(link_info.outside)
 
 
 def one_call(frames, placements, reach, min_length, smooth, deposit, point_field, track_field, thresholds=LEVEL, cap=CAP, use_offsets=True, box=None):
@@ -155,7 +97,7 @@ def test_a_sample_inside_one_map_and_outside_the_other(plane, bflib):
 
 # ----------------------------------------------------------------------------- 3, 4, 5: the draw plan
 
-@pytest.mark.parametrize("case", host.DRAW_CALLS, ids=lambda case: case[0])
+@pytest.mark.parametrize("case", track_plans.DRAW_CALLS, ids=lambda case: case[0])
 def test_the_draw_plan_wide_far_and_at_negative_coordinates(case, own, bflib):
     name, A, reach, point_field, track_field = case
     for min_length, smooth in ((1, 0), (2, 1), (1, 8)):
@@ -165,11 +107,11 @@ def test_the_draw_plan_wide_far_and_at_negative_coordinates(case, own, bflib):
         if smooth:
             continue
         sizes = [len(B) for track in want["links"] for skipped, d, B, drawn in track if not skipped]
-        if case is host.WIDE:                                             # a link's samples cross any lane group and a whole wave
+        if case is track_plans.WIDE:                                             # a link's samples cross any lane group and a whole wave
             assert max(sizes) == 72 and total["links_skipped"] == 0 and total["points_deposited"] >= 100 and total["links_outside"] >= 100
-        elif case is host.FAR_AWAY:                                       # the skipped links would have crossed the maps: they stay zero
+        elif case is track_plans.FAR_AWAY:                                       # the skipped links would have crossed the maps: they stay zero
             assert total["links_skipped"] == 2 and total["points_deposited"] == 0 and total["links_deposited"] == 0 and max(sizes) == 4096
-        elif case is host.FAR_EDGE:                                       # e = 4096 exactly still draws
+        elif case is track_plans.FAR_EDGE:                                       # e = 4096 exactly still draws
             assert total["links_skipped"] == 2 and max(sizes) == 4096 and total["links_deposited"] >= 4096
         else:
             assert total["repeats"] >= 5 and 1 in sizes and total["points_outside"] >= 10 and total["lone"] == 1
@@ -178,7 +120,7 @@ def test_the_draw_plan_wide_far_and_at_negative_coordinates(case, own, bflib):
 # ----------------------------------------------------------------------------- 6: the lattice
 
 def test_a_lattice_of_more_than_512_peaks_a_frame(bflib):
-    stack, placements = chain_host.volume_plan()
+    stack, placements = track_plans.volume_plan()
     frames, _ = burst(stack)
     field = (36, 48, 96)                                                  # the chain tests' field, 3 x finer: the lattice's last columns lie outside
     for smooth in (0, 2):
@@ -191,9 +133,9 @@ def test_a_lattice_of_more_than_512_peaks_a_frame(bflib):
 # ----------------------------------------------------------------------------- 7: equality with the track call
 
 def test_one_sample_a_link_leaves_the_track_calls_track_map(own, bflib):
-    K, box, field = len(own), host.EQUALITY_BOX, (24, 1, 40)
+    K, box, field = len(own), track_plans.EQUALITY_BOX, (24, 1, 40)
     bf.track_map_reset(field)
-    chain_tests.track(K, LEVEL, IDENTITY, REACH, 1, use_offsets=False, deposit=LINKS, box=box)
+    ring_frames.track(K, LEVEL, IDENTITY, REACH, 1, use_offsets=False, deposit=LINKS, box=box)
     of_the_tracks = bf.track_map_copy(field)
     bf.track_map_reset(field)
     rows = draw(K, LEVEL, IDENTITY, REACH, 1, 0, use_offsets=False, deposit=LINKS, box=box)
@@ -248,7 +190,7 @@ def test_complex_frames_draw_as_their_find_peaks_records_say(bflib):
     for min_length, smooth, use_offsets in ((1, 0, True), (2, 1, True), (3, 2, True), (2, 0, False)):
         density, counts, sums = fresh_maps(field, field)
         rows = draw(3, thresholds, A, 6.0, min_length, smooth, use_offsets=use_offsets, deposit=POINTS | LINKS)
-        want = ref.draw_records(tracks_tests.records_of(3, thresholds), A, 6.0, min_length, smooth, use_offsets, deposit=POINTS | LINKS,
+        want = ref.draw_records(ring_frames.peak_lists(3, thresholds), A, 6.0, min_length, smooth, use_offsets, deposit=POINTS | LINKS,
                                 point_map=density, counts=counts, sums=sums)
         same_rows(rows, want, 3, thresholds)
         same_maps(field, field, density, counts, sums)
@@ -276,7 +218,7 @@ def test_an_unplaced_frame_a_cap_a_box_and_thresholds_a_frame(plane, bflib):
         assert sorted(want["lengths"]) == [1, 2, 5, 6, 8, 9]
     # per-frame thresholds: frame 6 asks for more than the spots' height, and has no peak
     levels = np.full(K, LEVEL, np.float32)
-    levels[6] = 2 * host.HEIGHT
+    levels[6] = 2 * track_plans.HEIGHT
     want = one_call(plane, FOUR, 6.0, 1, 3, POINTS | LINKS, FIELD4, FIELD4, thresholds=levels)
     assert want["rows"][6]["peaks"] == 0 and max(want["lengths"]) == 6
     # the newest frames of a longer ring: a call over the 4 newest frames sees only them

@@ -9,9 +9,6 @@ it), so there the reference pairs the records beamformer_hip_find_peaks_last_fra
 positions bit for bit.  The queued frames' double divisions are IEEE divisions on the device as in numpy: components 0..4 are compared
 bit for bit."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,66 +17,22 @@ from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import tracks_ref as ref
 from tests import variants_cases as vc
-from tests.test_gpu_frame_metrics import BOX, block, newest_info, region_of, variants_push
-from tests.test_gpu_frame_peaks import fraction_of_max
-from tests.test_gpu_localisation import finer, map_view, placement_onto, points_of
+from tests.frame_info import newest_info
+from tests.ring_frames import (metrics_block as block, BOX, CAP, finer, fraction_of_max, map_view, pair, placement_onto, peak_lists as records_of,
+                               same_pairs_call as same_call, same_map, variants_push)
+from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDENTITY = np.eye(3, 4)
 FAR = np.array([[0.0, 0.0, 0.0, -1e6]] * 3)            # a placement that puts every peak outside any map
-CAP = 4096
 
 
 @pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
+def maps_reset(automatic_path, bflib):
     yield
-    L.beamformer_hip_set_das_path(0)
     bflib.localisation_map_reset(None)
     bflib.track_map_reset(None)
-
-
-def pair(count, thresholds, placements, reach, cap=CAP, use_offsets=True, deposit=False, box=None):
-    rows, pairs, ms = bf.pair_peaks_last_frames(count, thresholds, placements, reach, cap, use_offsets, deposit, region_of(box))
-    assert ms > 0
-    return rows, np.frombuffer(bytes(pairs), ref.PAIR)
-
-
-def expected_rows(numbers, count, thresholds, cap, box=None):
-    """the rows the call owes: the reference's numbers, and find_peaks' ids and counts of the same frames"""
-    found, _, _ = bf.find_peaks_last_frames(count, thresholds, cap, region_of(box))
-    levels = ref.each(np.asarray(thresholds, np.float32), count)
-    rows = (P.HipPeakPairs * len(numbers))()
-    for n, (row, want) in enumerate(zip(rows, numbers)):
-        for k in range(2):
-            peaks = found[n + k]
-            row.frame_id[k], row.threshold[k], row.peaks[k], row.found[k] = peaks.frame_id, float(levels[n + k]), peaks.stored, peaks.found
-            assert int(peaks.stored) == want["peaks"][k] and ("found" not in want or int(peaks.found) == want["found"][k])
-            row.unplaced[k], row.unpaired[k] = want["unplaced"][k], want["unpaired"][k]
-        row.first, row.pairs, row.deposited, row.outside = want["first"], want["pairs"], want["deposited"], want["outside"]
-    return rows
-
-
-def same_call(rows, got, want, numbers, count, thresholds, cap=CAP, box=None):
-    """the packed records and the rows, byte for byte"""
-    print("  " + ", ".join(f"pair {n}: {w['peaks']} peaks, {w['pairs']} pairs, unpaired {w['unpaired']}, unplaced {w['unplaced']}, "
-                           f"deposited {w['deposited']}, outside {w['outside']}" for n, w in enumerate(numbers)))
-    assert got.tobytes() == want.tobytes(), f"{len(got)} records against {len(want)}"
-    assert bytes(rows) == bytes(expected_rows(numbers, count, thresholds, cap, box))
-    for row in rows:
-        assert row.deposited + row.outside in (0, row.pairs) and row.peaks[0] - row.unplaced[0] - row.pairs == row.unpaired[0]
-
-
-def same_map(points, counts, sums):
-    got_counts, got_sums, info = bf.track_map_copy(points)
-    assert tuple(info.points) == tuple(points) and got_counts.dtype == np.uint32 and got_sums.dtype == np.int64
-    assert got_counts.tobytes() == counts.tobytes(), f"{int((got_counts != counts).sum())} counts differ"
-    assert got_sums.tobytes() == sums.tobytes(), f"{int((got_sums != sums).sum())} sums differ"
-    return info
 
 
 def teeth(numbers):
@@ -89,13 +42,6 @@ def teeth(numbers):
     one_sided = sum(int((w["forward"] != ref.NONE).sum()) - w["pairs"] for w in numbers)
     print(f"  teeth: {pairs} pairs, {alone} unpaired, {one_sided} forward choices not mutual")
     assert pairs >= 8 and alone >= 1 and one_sided >= 1
-
-
-def records_of(count, thresholds, cap=CAP, box=None):
-    """the find_peaks records of the `count` newest frames: [(index, offset)] for the reference (complex frames)"""
-    rows, peaks, _ = bf.find_peaks_last_frames(count, thresholds, cap, region_of(box))
-    records = np.frombuffer(bytes(peaks), np.dtype(P.HipFramePeak))
-    return [(records[int(r.first):int(r.first) + int(r.stored)]["index"], records[int(r.first):int(r.first) + int(r.stored)]["offset"]) for r in rows]
 
 
 def shifted_views(points, count, step=0.04e-3):
@@ -504,8 +450,4 @@ def test_refusals_on_the_device_change_nothing(bflib):
 
 def test_the_ring_a_queued_track_map_that_wraps_and_one_that_does_not_fit():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/tracks_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tracks_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "refused" in run.stdout and "wrapped" in run.stdout, run.stdout
+    run_ring_worker("tracks_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

@@ -10,9 +10,6 @@ derived plan state and must be the single push of the block carrying its values,
 import ctypes as C
 import dataclasses
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,12 +18,12 @@ from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import cases
 from tests import variants_cases as vc
-from tests.test_gpu_burst import same_bits, single_push
-from tests.test_gpu_parity import compare, reference
+from tests.das_push import compare, same_bits, single_push
+from tests.parity import reference
+from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PREFER, NO_KERNEL = vc.PREFER, vc.NO_KERNEL
 FLOAT32_BLOCKS = [(interp, iq, cw) for interp in ("cubic", "linear", "nearest") for iq in (True, False) for cw in (False, True)]
 
@@ -46,15 +43,6 @@ def prepared(interp="linear", iq=True, cw=False, demodulate=False, which="block"
     variants = vc.candidates(acq.bp)
     refs = [(carrying(acq, v),) + tuple(reference(binding, carrying(acq, v))) for v in variants]
     return acq, variants, refs
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
 
 
 def frame_id(L):
@@ -338,10 +326,7 @@ def test_pair_counting_runs_per_variant(bflib):
 
 def test_a_run_that_would_straddle_the_end_of_the_ring_starts_again_at_offset_0():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/variants_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "variants_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "wrapped" in run.stdout, run.stdout
+    run_ring_worker("variants_wrap_worker", 1 << 20, expect=("wrapped",), timeout=600)
 
 
 @pytest.mark.parametrize("route", ["variants kernel", "per-variant route"])

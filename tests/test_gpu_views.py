@@ -9,133 +9,21 @@ factored kernel: it is run under das path 1 (the general kernel for every frame)
 real instantiation.  Under flag 0x800, and for blocks the views kernel does not take, every view runs its single-frame kernel on the
 shared DAS input and must be the single push of the block with that grid, bit for bit."""
 import ctypes as C
-import dataclasses
-import functools
 
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import cases
-from tests.test_gpu_burst import noise_frames, row_end_case, same_bits, single_push
-from tests.test_gpu_parity import compare, reference
+from tests.das_push import compare, DISPATCH_CASES, KERNEL_CASES, kernel_views, mode_for, noise_frames, on_grid, prepared, same_bits, single_push
+from tests.parity import reference
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-I = P.InterpolationMode
 
-KERNEL_CASES = ["config1_small", "rca_cubic_real", "rca_f32_complex_in", "rca_a1s2", "rca_nearest_real"]
-GENERAL_PATH_FOR = {"rca_nearest_real"}            # see the module docstring
-# The instantiations of the views kernels no case above dispatches (every one with coherency weighting, and nearest x IQ): the file's
-# small real and IQ cases with the interpolation mode and the weighting set in the parameter block ("case+mode+cw", case_of()), run
-# under das path 1 like rca_nearest_real so that the views kernel takes them whatever their single frames would run.
-DISPATCH_CASES = ["rca_nearest_real+cw", "rca_f32_complex_in+nearest", "rca_f32_complex_in+nearest+cw", "rca_cubic_real+linear+cw",
-                  "rca_f32_complex_in+linear+cw", "rca_cubic_real+cw", "rca_f32_complex_in+cw"]
 PER_VIEW_CASES = ["forces", "hercules_wide_cw", "rca_staged_auto", "config5_literal_order"]
 PREFER, NO_KERNEL = P.HIP_DAS_PATH_PREFER_VIEWS_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL
-# the part of the case's depth range its RF rows reach (256-sample rows end a tenth of the way down the 6 .. 18 mm image): the views are
-# laid inside it, so that none of them is an empty image -- and their deepest voxels lie at the ends of the rows
-REACHED_DEPTH = {"rca_f32_complex_in": 0.1, "rca_a1s2": 0.1, "rca_cubic_real": 0.8, "rca_nearest_real": 0.8}
-
-
-def box(bp):
-    """(lo, hi) of the case's own grid in world coordinates, read off its voxel transform: a volume's three extents, or a view
-    plane's x and depth with the lateral extent repeated along y"""
-    m = list(bp.das_voxel_transform)
-    if m[10] != 0.0:                       # das_transform_3d
-        return (m[12], m[13], m[14]), (m[12] + m[0], m[13] + m[5], m[14] + m[10])
-    return (m[12], m[12], m[14]), (m[12] + m[0], m[12] + m[0], m[14] + m[6])      # das_transform_2d_xz
-
-
-def inner(lo, hi, a, b):
-    """the part a .. b (fractions of the extent, per axis) of the box lo .. hi"""
-    return (tuple(l + (h - l) * f for l, h, f in zip(lo, hi, a)), tuple(l + (h - l) * f for l, h, f in zip(lo, hi, b)))
-
-
-def case_of(name):
-    """cases.make() of the name before the first '+', then 'nearest' / 'linear' / 'cubic' and 'cw' set in its parameter block"""
-    base, *changes = name.split("+")
-    acq = cases.make(base)
-    for change in changes:
-        if change == "cw":
-            acq.bp.coherency_weighting = 1
-        else:
-            acq.bp.interpolation_mode = int({"nearest": I.Nearest, "linear": I.Linear, "cubic": I.Cubic}[change])
-    return acq
-
-
-def kernel_views(acq):
-    """the view set of the kernel tests: the max(1, n - 1) division, less than a tile, ragged tiles, a volume, a YZ plane, the case's
-    own grid, and the second view once more.  Nearest interpolation keeps the views of at least the case's own voxel count (on
-    fewer voxels compare()'s share rule for nearest taps allows no outlier at all) and repeats its own grid."""
-    lo, hi = box(acq.bp)
-    d = REACHED_DEPTH.get(acq.name, 1.0)
-    views = [bf.view((1, 1, 1), *inner(lo, hi, (0.5, 0.5, 0.5 * d), (1, 1, d))),
-             bf.view((5, 1, 7), *inner(lo, hi, (0.3, 0.5, 0.2 * d), (0.6, 0.5, 0.7 * d))),
-             bf.view((33, 1, 17), *inner(lo, hi, (0.1, 0.5, 0.1 * d), (0.9, 0.5, 0.9 * d))),
-             bf.view((9, 6, 5), *inner(lo, hi, (0.2, 0.3, 0.3 * d), (0.8, 0.7, 0.8 * d))),
-             bf.view((1, 40, 24), *inner(lo, hi, (0.5, 0.1, 0.2 * d), (0.5, 0.9, 1.1 * d))),
-             bf.view_of(acq.bp)]
-    views.append(views[1])
-    if acq.bp.interpolation_mode == int(I.Nearest):
-        views = [v for v in views if int(np.prod(list(v.output_points))) >= acq.voxels]
-        views.append(bf.view_of(acq.bp))
-    return views
-
-
-def per_view_views(acq):
-    lo, hi = box(acq.bp)
-    own = [int(n) for n in acq.bp.output_points[:3]]
-    part = tuple(max(1, n // 2 + (n > 2)) for n in own)
-    return [bf.view_of(acq.bp), bf.view(part, *inner(lo, hi, (0.2, 0.2, 0.3), (0.7, 0.7, 0.8))), bf.view_of(acq.bp)]
-
-
-def on_grid(acq, view, rf):
-    """the acquisition with the view's grid in its parameter block, and `rf`"""
-    bp = type(acq.bp).from_buffer_copy(acq.bp)
-    bp.das_voxel_transform[:] = list(view.das_voxel_transform)
-    bp.output_points[:3] = [int(n) for n in view.output_points]
-    return dataclasses.replace(acq, bp=bp, rf=rf)
-
-
-@functools.lru_cache(maxsize=None)
-def prepared(name, which="kernel"):
-    """(acquisition, noise RF, views, per view: its acquisition and the oracle's reference) -- computed once, shared, left unchanged"""
-    from oracle import binding
-    binding.library()
-    acq = row_end_case({"row_ends_linear": I.Linear, "row_ends_cubic": I.Cubic}[name]) if name.startswith("row_ends") else case_of(name)
-    rf = noise_frames(acq, 1, 4200 if name.startswith("row_ends") else 5000)[0]
-    if name.startswith("row_ends"):
-        # the whole plane; the deepest 96 x 1 x 12 strip -- which lies wholly past the ends of the 256-sample rows: an image of zeros,
-        # compared exactly --; and the 12 rows around the depth at which the rows end (rows r - 8 .. r + 3 of the plane, r its last
-        # row with signal), which compare() judges as it judges the plane
-        lo, hi = box(acq.bp)
-        whole = reference(binding, on_grid(acq, bf.view_of(acq.bp), rf))[0]
-        r = int(np.flatnonzero((whole != 0).any(axis=(1, 2)))[-1])
-        assert 8 <= r <= 80
-        views = [bf.view_of(acq.bp), bf.view((96, 1, 12), *inner(lo, hi, (0, 0, (r - 8) / 95), (1, 1, (r + 3) / 95))),
-                 bf.view((96, 1, 12), *inner(lo, hi, (0, 0, 84 / 95), (1, 1, 1)))]
-    else:
-        views = kernel_views(acq) if which == "kernel" else per_view_views(acq)
-    refs = []
-    for v in views:
-        acq_v = on_grid(acq, v, rf)
-        refs.append((acq_v,) + tuple(reference(binding, acq_v)))
-    return acq, rf, views, refs
-
-
-def mode_for(name, flag):
-    return flag | (1 if name in GENERAL_PATH_FOR or name in DISPATCH_CASES else 0)
-
-
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
 
 
 def check_parity(name, frames, refs, what):
@@ -236,7 +124,7 @@ def test_blocks_the_views_kernel_does_not_take(name, bflib):
 
 def test_a_mixed_push(bflib):
     """views the views kernel takes and views it does not, in one push: parity of all, the others their single push bit for bit"""
-    from tests.test_views_host import mixed_views
+    from tests.das_push import mixed_views
     from oracle import binding
     acq = cases.make("rca_flash_none_tx")
     rf = noise_frames(acq, 1, 5300)[0]

@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from tests import walk_cases as W
-from tests.test_gpu_parity import compare, last_timings, reference
+from tests.das_push import compare, last_timings, same_bits
+from tests.parity import reference
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +23,6 @@ NAMES = [e.name for e in W.ENTRIES]
 SLABS = [e.name for e in W.ENTRIES if e.slab]
 BURSTS = [e.name for e in W.ENTRIES if e.burst]
 CHECKED = [e.name for e in W.ENTRIES if e.checked]
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 # one module-scoped parameter per entry: pytest then runs an entry's checks one after the other, and they share its frames

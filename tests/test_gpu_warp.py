@@ -14,54 +14,26 @@ share of its bound -- before it asserts.
 
 WORST SHARE of the bound over this file on an MI355X: see DESIGN.md 3.7g."""
 import ctypes as C
-import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import variants_cases as vc
 from tests import warp_ref as ref
-from tests.test_gpu_ensemble import block, ensemble, newest_id, rf_frames
-from tests.test_gpu_frame_metrics import newest_info
+from tests.frame_info import newest_id, newest_info
+from tests.ring_frames import block, warp_block_of as block_of, check_warp, CLAMP, CUBIC, ensemble, LINEAR, OWN, rf_frames, WARP_ZERO as ZERO
+from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
-D = P.DataKind
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LINEAR, CUBIC = int(P.HipWarpInterpolation.Linear), int(P.HipWarpInterpolation.Cubic)
-ZERO, CLAMP = int(P.HipWarpEdge.Zero), int(P.HipWarpEdge.Clamp)
 MODES = [(LINEAR, ZERO), (LINEAR, CLAMP), (CUBIC, ZERO), (CUBIC, CLAMP)]
-DEEP, WIDE = (37, 19, 11), (96, 1, 96)
-OWN = {"deep": (DEEP, vc.LO3, vc.HI3), "wide": (WIDE, vc.LO, vc.HI)}
 GRIDS = ["plane", "square", "volume", "real", "nan", "deep", "wide"]
 
 
-@pytest.fixture(autouse=True)
-def automatic_path(bflib):
-    L = bflib.library()
-    L.beamformer_set_global_timeout(0xFFFFFFFF)
-    L.beamformer_hip_set_das_path(0)
-    yield
-    L.beamformer_hip_set_das_path(0)
-
-
-@functools.lru_cache(maxsize=None)
-def block_of(which):
-    if which not in OWN:
-        return block(which)
-    points, lo, hi = OWN[which]
-    return cfg.rca("warp_" + which, 16, 2, 256, points, lo, hi, seed=7500, interp=P.InterpolationMode.Linear, demodulate=False,
-                   data_kind=D.Float32Complex, angles=np.array([-6.0, 6.0]), kind=P.AcquisitionKind.RCA_TPW)
-
-
 def frames_of(which, K):
-    """K frames of the grid (tests/test_gpu_ensemble.py's ensemble; "deep", "wide": the same by this file's blocks): (frames (K, Z, Y, X), ids)"""
+    """K frames of the grid (tests/ring_frames.py's ensemble; "deep", "wide": the same by this file's blocks): (frames (K, Z, Y, X), ids)"""
     if which not in OWN:
         return ensemble(which, K)
     acq = block_of(which)
@@ -149,51 +121,6 @@ def rotations_of(K, seed):
     rng = np.random.default_rng(seed)
     r = np.exp(-1j * rng.uniform(-np.pi, np.pi, K)) * rng.uniform(0.5, 1.5, K)
     return r.astype(np.complex64)
-
-
-def call(K, case, rotations=None, interpolation=LINEAR, edge=ZERO, tag=0):
-    return bf.warp_last_frames(K, case["field"], case["nodes"], case["node_first"], case["node_step"], rotations, interpolation, edge, tag=tag)
-
-
-def reference(frames, case, rotations, interpolation, edge):
-    return [ref.warp(frames[n], case["field"][n], case["nodes"], case["node_first"], case["node_step"],
-                     None if rotations is None else rotations[n], interpolation, edge) for n in range(len(frames))]
-
-
-def check_warp(which, frames, ids, case, rotations=None, interpolation=LINEAR, edge=ZERO, tag=0, what="", same_masks=False):
-    """warp the len(frames) newest frames and check the outputs and their records; returns (outputs, first id, worst share, compared share)"""
-    acq = block_of(which)
-    K = len(frames)
-    real = not np.iscomplexobj(frames)
-    source_block = int(bf.frame_info(ids[-1]).parameter_block)
-    first, ms = call(K, case, rotations, interpolation, edge, tag)
-    out = bf.get_last_frames(acq.bp, K).copy()
-    assert out.shape == frames.shape and out.dtype == frames.dtype and ms > 0
-    worst, inside, compared, total = 0.0, True, 0, 0
-    for n, (values, bound) in enumerate(reference(frames, case, rotations, interpolation, edge)):
-        w, i = ref.share_of_bound(out[n], values, bound)
-        worst, inside = max(worst, w), inside and i
-        for got, x in zip(*[(a.real, a.imag) if np.iscomplexobj(values) else (a,) for a in (out[n], values)]):
-            compared, total = compared + int(np.isfinite(x).sum()), total + x.size
-            if same_masks:                # the positions are float32 numbers: the device's support is the reference's, voxel for voxel
-                assert np.array_equal(np.isfinite(got), np.isfinite(x))
-    share = compared / total
-    print(f"  {what}: K {K}, nodes {case['nodes']}, interpolation {interpolation}, edge {edge}, {'real' if real else 'complex'} {frames.shape[1:]}: "
-          f"worst error {worst:.4f} of its bound, {share:.4f} of the floats compared, {ms * 1e3:.1f} us")
-    assert inside
-    # the records: consecutive ids behind the sources, the grid, the kind, the tag, the newest source's block
-    assert first == ids[-1] + 1 and int(newest_info(bf.library()).frame_id) == first + K - 1
-    scores, _ = bf.score_last_frames(K)
-    pz, py, px = frames.shape[1:]
-    for j in range(K):
-        info = bf.frame_info(first + j)
-        assert (int(info.frame_id), tuple(info.points), int(info.parameter_block)) == (first + j, (px, py, pz), source_block)
-        assert int(info.data_kind) == int(D.Float32 if real else D.Float32Complex)
-        assert (int(scores[j].frame_id), int(scores[j].image_plane_tag), int(scores[j].parameter_block)) == (first + j, tag, source_block)
-    t = P.HipFrameTimings()
-    assert bf.library().beamformer_hip_get_last_frame_timings(C.byref(t)) and t.stage_count == 0 and t.das_voxels == 0
-    assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))       # a source is still served by its id
-    return out, first, worst, share
 
 
 # ---- parity: every grid x both interpolations x both edges at K = 1, 3, 17 ----
@@ -455,23 +382,12 @@ def test_several_devices_are_refused(bflib):
     L = bflib.library()
     acq = vc.separable_volume()
     still = dict(field=np.zeros((1, 1, 1, 1, 3), np.float32), nodes=(1, 1, 1), node_first=(0, 0, 0), node_step=(1, 1, 1))
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        bflib.beamform(acq.bp, acq.rf, acq.filters)
-        assert L.beamformer_hip_get_device_count() == 2
+    with two_contexts_on_device_0(bflib, acq):
         refused(L, 1, still, E.InvalidAccess)
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
     frames, ids = ensemble("plane", 2)
     check_warp("plane", frames, ids, dict(still, field=np.zeros((2, 1, 1, 1, 3), np.float32)), what="one device again")
 
 
 def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/warp_wrap_worker.py"""
-    env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(1 << 20))
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "warp_wrap_worker.py")], env=env, capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "refused" in run.stdout and "wrapped" in run.stdout, run.stdout
+    run_ring_worker("warp_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

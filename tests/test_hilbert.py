@@ -8,52 +8,11 @@ import numpy as np
 import pytest
 
 from ogl_beamforming_amd import configs as cfg, params as P
-from tests.test_gpu_parity import compare, reference
+from tests.das_push import compare
+from tests.parity import reference
+from tests.stage_checks import RAGGED_SAMPLES, acquisitions, hilbert, ragged_acquisition
 
 S, D, I, K = P.ShaderKind, P.DataKind, P.InterpolationMode, P.AcquisitionKind
-LO3, HI3 = (-2e-3, -2e-3, 3e-3), (2e-3, 2e-3, 9e-3)
-
-
-def acquisitions():
-    out = {}
-    out["rca_i16"] = cfg.rca("rca_hilbert", 16, 3, 512, (16, 16, 1), (-2e-3, 0, 3e-3), (2e-3, 0, 9e-3), seed=71, demodulate=False)
-    out["rca_f32_cubic_cw"] = cfg.rca("rca_hilbert_f32", 16, 4, 512, (12, 10, 3), LO3, HI3, seed=72, demodulate=False,
-                                      data_kind=D.Float32, interp=I.Cubic, cw=True, orientation=0x12)
-    out["hercules_decode"] = cfg.hercules("hercules_hilbert", 16, 8, 512, (8, 8, 6), LO3, HI3, seed=73, data_kind=D.Float16)
-    out["forces_decode"] = cfg.forces("forces_hilbert", 16, 8, 512, (16, 1, 12), LO3, HI3, seed=74)
-    for acq in out.values():
-        with_hilbert(acq)
-    return out
-
-
-def with_hilbert(acq):
-    """{Decode, DAS} -> {Decode, Hilbert, DAS}"""
-    bp = acq.bp
-    assert list(bp.compute_stages[:2]) == [int(S.Decode), int(S.DAS)]
-    bp.compute_stages[1], bp.compute_stages[2] = int(S.Hilbert), int(S.DAS)
-    bp.compute_stages_count = 3
-    return acq
-
-
-RAGGED_SAMPLES = (130, 1001)
-
-
-def ragged_acquisition(samples):
-    """tests/test_gpu_stages.py's decoded ragged rows with the stage behind the Decode: a wave's window is 64 + 62 samples, so 130
-    leaves a last group of two outputs whose window ends 62 samples past the row, and 1001 an odd row"""
-    from tests.test_gpu_stages import ragged_case
-    acq = with_hilbert(ragged_case(samples, False, seed=800 + samples))
-    acq.name = f"ragged_{samples}_hilbert"
-    return acq
-
-
-@pytest.fixture
-def hilbert(bflib, oracle):
-    assert bflib.library().beamformer_hip_enable_hilbert(1)
-    oracle.enable_hilbert(True)
-    yield
-    bflib.library().beamformer_hip_enable_hilbert(0)
-    oracle.enable_hilbert(False)
 
 
 def test_stage_is_refused_by_default_as_in_the_reference(bflib, oracle):
@@ -134,7 +93,7 @@ def test_frame_parity_with_the_stage(name, bflib, oracle, hilbert):
 def test_das_input_with_the_stage(name, bflib, oracle, hooks, hilbert):
     """the element-wise bar of tests/test_gpu_stages.py in a single push with SCRATCH_POISON: what the DAS stage read against the
     oracle's capture of it, inside the forward-error bound stage_bounds propagates through the 63 taps; then the frame"""
-    from tests.test_gpu_stages import run_case
+    from tests.stage_checks import run_case
     acq = ragged_acquisition(int(name[7:])) if name.startswith("ragged_") else acquisitions()[name]
     _, _, results = run_case(bflib, oracle, hooks, acq)
     assert results[0][2][0] == "bound"

@@ -8,7 +8,7 @@ import pytest
 
 from ogl_beamforming_amd import params as P
 from tests import pipeline_cases as pc
-from tests import test_gpu_stages as stages
+from tests import stage_checks as stages
 
 S = P.ShaderKind
 DK = P.DataKind

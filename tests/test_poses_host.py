@@ -76,13 +76,13 @@ def test_forced_selection_under_a_pose(group, pose, name):
 def test_the_forced_expectations_cover_their_families():
     """the case lists of poses.EXPECTED_FORCED are written down; this keeps them complete: every tile_* case the block-staged kernel
     takes unposed, every HERCULES-family case, every case of the staged parity tests"""
-    from tests import test_gpu_parity as T
+    from tests import das_kernel_cases
     E = poses.EXPECTED_FORCED
     assert set(E["tile"]["cases"]) == {n for n in cases.CASES if n.startswith("tile_") and described(n, None, 0x114)[0] == 5}
-    assert set(E["hercules_planes"]["cases"]) | set(E["hercules_volumes"]["cases"]) == set(T.HERCULES)
+    assert set(E["hercules_planes"]["cases"]) | set(E["hercules_volumes"]["cases"]) == set(das_kernel_cases.HERCULES)
     assert all(int(cases.make(n).bp.output_points[2]) == 1 for n in E["hercules_planes"]["cases"])
     assert all(int(cases.make(n).bp.output_points[2]) > 1 for n in E["hercules_volumes"]["cases"])
-    assert set(E["staged"]["cases"]) | set(E["staged_every_plane_rerouted"]["cases"]) == set(T.STAGED)
+    assert set(E["staged"]["cases"]) | set(E["staged_every_plane_rerouted"]["cases"]) == set(das_kernel_cases.STAGED)
     assert set(E["staged_every_plane_rerouted"]["cases"]) == set(cases.ROW_END_EVERY_PLANE)
 
 

@@ -11,7 +11,7 @@ import pytest
 from ogl_beamforming_amd import params as P
 from tests import cases
 from tests import readi_image_cases as R
-from tests.test_gpu_burst import noise_frames
+from tests.das_push import noise_frames
 
 E = P.LibError
 I = P.InterpolationMode

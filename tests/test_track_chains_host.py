@@ -11,82 +11,14 @@ import numpy as np
 
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
-from tests import frame_peaks_ref, planted, tracks_ref
+from tests import frame_peaks_ref, tracks_ref
 from tests import track_chains_ref as ref
+from tests.track_plans import HEIGHT, IDENTITY, LEVEL, REACH, ROOT, coordinates_of, plane_plan, teeth, volume_plan
 
 E = P.LibError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-IDENTITY = np.eye(3, 4)
-HEIGHT, LEVEL, REACH = 8.0, 4.0, 1.5
 
 
 # ----------------------------------------------------------------------------- the planted plans
-
-def plane_plan():
-    """K = 11 frames of planted.PLANE, zero but for isolated voxels of HEIGHT, each at least 2 voxels from any other of its frame; under
-    the identity placement and reach 1.5: tracks of the lengths [1, 1, 2, 3, 5, 6, 8, 9, 11], 37 pairs and one forward choice that is
-    not mutual.  Returns (stack (K, Z, 1, X), the spots: {frame: [(x, z)]})"""
-    K, (X, _, Z) = 11, planted.PLANE
-    spots = {k: [] for k in range(K)}
-    for k in range(K):
-        spots[k].append((2, 2 + k))                                  # moves one voxel a frame, all 11 frames
-        if 2 <= k <= 9:
-            spots[k].append((6, 20))                                 # length 8: neither begins in frame 0 nor ends in frame 10
-        if 1 <= k <= 9:
-            spots[k].append((10, 20))                                # length 9
-        if k in (4, 5):
-            spots[k].append((14, 5 + k))                             # length 2
-        spots[k].append((18, 2 + k + (3 if k >= 5 else 0)))          # jumps 4 voxels between frames 4 and 5: tracks of 5 and 6
-    spots[7].append((14, 30))                                        # alone
-    spots[3] += [(20, 20), (22, 20)]                                 # both choose (21, 20) of frame 4, which returns the lower rank:
-    spots[4].append((21, 20))                                        # a tie that leaves one choice unreturned, and a track of 3
-    spots[5].append((21, 21))
-    stack = np.zeros((K, Z, 1, X), np.float32)
-    for k, where in spots.items():
-        for x, z in where:
-            stack[k, z, 0, x] = HEIGHT
-    return stack, spots
-
-
-VOLUME_SHIFT = (1, 0, 0)
-
-
-def volume_plan():
-    """K = 5 frames of planted.VOLUME: a lattice of every second voxel (1024 peaks), frame k moved by k voxels along x (planted.moved),
-    frame 2 without the lattice rows of y = 0 mod 8 and frame 3 without those of z = 0 mod 8.  A lattice of step 2 moved by 1 leaves
-    every peak EQUALLY far from its own successor and from its left neighbour's, and the tie goes to the lower rank -- almost nothing
-    would pair --, so frame k's placement takes half of the motion back: the successor lies at 0.5, the other at 1.5, and the reach
-    is 1.  Returns (stack (K, Z, Y, X), placements (K, 3, 4))"""
-    K, (X, Y, Z) = 5, planted.VOLUME
-    lattice = np.zeros((Z, Y, X), np.float32)
-    lattice[::2, ::2, ::2] = HEIGHT
-    stack = []
-    for k in range(K):
-        values = lattice.copy()
-        if k == 2:
-            values[:, ::8, :] = 0
-        if k == 3:
-            values[::8, :, :] = 0
-        stack.append(planted.moved(values, tuple(k * s for s in VOLUME_SHIFT)))
-    placements = np.stack([IDENTITY] * K)
-    placements[:, 0, 3] = [-0.5 * k for k in range(K)]
-    return np.stack(stack), placements
-
-
-def coordinates_of(stack, placements, cap=65536):
-    """the frames' map coordinates by the references of the peaks and of the positions"""
-    A = np.asarray(placements, np.float64).reshape(-1, 3, 4)
-    found = [frame_peaks_ref.peaks(f, LEVEL, cap=cap) for f in stack]
-    return [tracks_ref.positions(r["index"], r["offset"], A[0 if len(A) == 1 else n]) for n, r in enumerate(found)]
-
-
-def teeth(out, min_length, count):
-    """the case decides something: a track kept, one dropped for its length, a kept one cut by neither end of the call's window, and
-    the lengths on both sides of the bar"""
-    lengths, tracks = out["lengths"], out["tracks"]
-    assert len(tracks) >= 1 and len(tracks) < len(lengths)
-    assert any(t["frame"] > 0 and t["frame"] + t["length"] < count and t["flags"] == 0 for t in tracks)
-    assert min_length - 1 in lengths and min_length in lengths
 
 
 def test_the_plane_plan_is_what_it_claims():

@@ -14,59 +14,18 @@ import numpy as np
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import planted, tracks_ref
-from tests import test_track_chains_host as chain_host
+from tests import track_plans
 from tests import track_chains_ref as chains
 from tests import track_draw_ref as ref
+from tests.track_plans import EQUALITY_BOX, FAR_AWAY, FAR_EDGE, OWN, PLANE_FIELD, WIDE, draw_plan, scaled, times
 
 E = P.LibError
-ROOT = chain_host.ROOT
-IDENTITY, HEIGHT, LEVEL, REACH = chain_host.IDENTITY, chain_host.HEIGHT, chain_host.LEVEL, chain_host.REACH
+ROOT = track_plans.ROOT
+IDENTITY, HEIGHT, LEVEL, REACH = track_plans.IDENTITY, track_plans.HEIGHT, track_plans.LEVEL, track_plans.REACH
 POINTS, LINKS = ref.POINTS, ref.LINKS
-PLANE_FIELD = (20, 1, 40)                                             # the chain tests' field over the plane plan
-
-
-def scaled(factor, shift=(0.0, 0.0, 0.0)):
-    """the placement m = factor * p + shift"""
-    A = IDENTITY * float(factor)
-    A[:, 3] = shift
-    return A
-
-
-def times(field, factor):
-    return tuple(int(v) * factor for v in field)
 
 
 # ----------------------------------------------------------------------------- the planted plans
-
-def draw_plan():
-    """K = 6 frames of planted.PLANE, isolated spots of HEIGHT as the plane plan's.  Under the identity and reach 1.5 -- A (x = 3): forth
-    and back along z, 5 6 7 6 5 4, so the first sample of a link that turns repeats the last of the link before it; B (7, 20): stationary,
-    d = 0, S = 1, every link after the first a repeat; C (x = 11): z = 10, then a line of TWO voxels at z = 11 and 12 -- one peak at 11
-    with the offset +0.5 --, then 13, then 14: two links of 1.5 voxels and one of 1; D (x = 0): z = k, along the frame's edge; E
-    (16, 30) in frame 2 alone; F (20, 5 + k) in frames 3 and 4; G (14 + k, 36 - k): diagonal, both axes move.
-    Returns (stack (K, Z, 1, X), the voxels: {frame: [(x, z)]})"""
-    K, (X, _, Z) = 6, planted.PLANE
-    voxels = {k: [] for k in range(K)}
-    for k in range(K):
-        voxels[k] += [(3, [5, 6, 7, 6, 5, 4][k]), (7, 20), (0, k), (14 + k, 36 - k)]
-    voxels[0].append((11, 10))
-    voxels[1] += [(11, 11), (11, 12)]
-    voxels[2] += [(11, 13), (16, 30)]
-    voxels[3] += [(11, 14), (20, 8)]
-    voxels[4].append((20, 9))
-    stack = np.zeros((K, Z, 1, X), np.float32)
-    for k, where in voxels.items():
-        for x, z in where:
-            stack[k, z, 0, x] = HEIGHT
-    return stack, voxels
-
-
-# the GPU file's calls on the draw plan: (name, placement, reach, point field, track field)
-WIDE = ("48 x", scaled(48), 72.0, (600, 1, 700), (400, 1, 1000))       # S reaches 72; each map holds a corner of it
-FAR_AWAY = ("4096 x, the maps under the skipped links", scaled(4096, (2 - 4096 * 11, 0, -4096 * 10)), 6144.0, (8, 1, 8192), (8, 1, 8192))
-FAR_EDGE = ("4096 x, the maps along the frame's edge", scaled(4096), 6144.0, (4, 1, 9000), (2, 1, 20000))
-OWN = ("4 x, moved to negative coordinates", scaled(4, (-20.0, 0.0, -30.0)), 6.0, (60, 1, 120), (40, 1, 140))
-DRAW_CALLS = (WIDE, FAR_AWAY, FAR_EDGE, OWN)
 
 
 def every_link(out):
@@ -79,7 +38,7 @@ def deposited(out_rows, kind):
 
 def drawn_on(stack, placement, reach, min_length, w, point_field=None, track_field=None):
     """the reference on a planted stack with fresh maps: (out, density, counts, sums)"""
-    coordinates = chain_host.coordinates_of(stack, placement)
+    coordinates = track_plans.coordinates_of(stack, placement)
     density = np.zeros(point_field[::-1], np.uint32) if point_field else None
     counts, sums = tracks_ref.empty_map(track_field) if track_field else (None, None)
     deposit = (POINTS if point_field else 0) | (LINKS if track_field else 0)
@@ -91,7 +50,7 @@ def test_the_draw_plan_is_what_it_claims():
     stack, voxels = draw_plan()
     for k, where in voxels.items():
         assert frame_peaks(stack[k]) == len(where) - (1 if k == 1 else 0)               # the line of two voxels is one peak
-    coordinates = chain_host.coordinates_of(stack, IDENTITY)
+    coordinates = track_plans.coordinates_of(stack, IDENTITY)
     everything = chains.chain_positions(coordinates, REACH, 1)
     assert sorted(everything["lengths"]) == [1, 2, 4, 6, 6, 6, 6]
     runs = [everything["points"]["position"][int(t["first"]):int(t["first"]) + int(t["length"])] for t in everything["tracks"]]
@@ -147,7 +106,7 @@ def frame_peaks(frame):
 
 
 def test_the_plane_plan_under_the_draw_calls_of_the_gpu_file():
-    stack, _ = chain_host.plane_plan()
+    stack, _ = track_plans.plane_plan()
     field = times(PLANE_FIELD, 4)
     seen = set()
     for min_length in (1, 3, 12):
@@ -183,9 +142,6 @@ def test_the_equality_frames_have_no_repeat_and_no_link_beyond_one_cell():
     mine = tracks_ref.empty_map(planted.PLANE)
     ref.draw_positions(coordinates, REACH, 1, 0, deposit=LINKS, counts=mine[0], sums=mine[1])
     assert mine[0].tobytes() == counts.tobytes() and mine[1].tobytes() == sums.tobytes() and int(counts.sum()) == len(links)
-
-
-EQUALITY_BOX = ((9, 0, 0), (15, 1, 40))
 
 
 def frame_peaks_boxed(frame):

@@ -12,6 +12,7 @@ import pytest
 from ogl_beamforming_amd import lib
 from ogl_beamforming_amd import params as P
 from tests import cases
+from tests.das_push import mixed_views, patches, push_parameters
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E = P.LibError
@@ -25,11 +26,6 @@ def automatic_path():
     lib.library().beamformer_hip_set_das_path(0)
     yield
     lib.library().beamformer_hip_set_das_path(0)
-
-
-def patches(n, points=(16, 1, 16)):
-    """n small patches inside config 1's image (x -19 .. 19 mm of a 64-element array at 0.3 mm pitch; 5 .. 40 mm deep)"""
-    return [lib.view(points, (-4e-3 + 0.4e-3 * k, 0, 10e-3 + 0.5e-3 * k), (-3e-3 + 0.4e-3 * k, 0, 11e-3 + 0.5e-3 * k)) for k in range(n)]
 
 
 def test_the_four_views_symbols_are_declared_exported_and_bound():
@@ -106,26 +102,12 @@ def test_other_families_and_faster_kernels_run_per_view_and_say_why():
     assert d.kernel_views == 0 and d.path[0] == single[0] == int(P.DasPath.Staged) and d.das_launches == 2, d.reason
 
 
-def mixed_views(acq):
-    """rca_flash_none_tx's block: its own plane runs the general kernel (the views kernel takes it), volumes the gather kernel"""
-    volume = lib.view((12, 10, 3), (-2e-3, -2e-3, 8e-3), (2e-3, 2e-3, 9e-3))
-    return [lib.view_of(acq.bp), volume, lib.view((5, 1, 7), (-1e-3, 0, 8e-3), (1e-3, 0, 10e-3)), volume]
-
-
 def test_a_mixed_list_is_one_launch_plus_the_others():
     acq = cases.make("rca_flash_none_tx")
     lib.library().beamformer_hip_set_das_path(PREFER)
     d = lib.describe_views(acq.bp, mixed_views(acq), acq.filters)
     assert list(d.path[:4]) == [int(P.DasPath.General), int(P.DasPath.Gather), int(P.DasPath.General), int(P.DasPath.Gather)]
     assert d.kernel_views == 2 and d.das_launches == 1 + 2, d.reason
-
-
-def push_parameters(acq):
-    L = lib.library()
-    for s, fp in enumerate(acq.filters):
-        assert L.beamformer_create_filter(C.byref(fp), s, 0)
-    assert L.beamformer_push_simple_parameters(C.byref(acq.bp)), lib.last_error()
-    return L
 
 
 def test_malformed_pushes_are_refused_before_a_device_is_touched():

@@ -2,25 +2,17 @@
 (the ring is sized once per process): 32 complex 64 x 1 x 64 frames of 32 KiB.  A burst of 16 and a mix 16 -> 15 leave 32 KiB at the end
 of the ring; the peaks of the two newest frames are paired into a track map of 128 x 1 x 100 voxels, whose Float32 frame (51200 bytes)
 does not fit behind them: it wraps to offset 0, over the burst's two oldest frames.  A track map of 512 x 1 x 513 voxels is a frame
-larger than the whole ring: FrameSizeOverflow, and nothing has changed."""
+larger than the whole ring: FrameSizeOverflow, and nothing has changed.
+Started as python -m tests.tracks_wrap_worker from the repository root (tests/scaffold.py run_ring_worker)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from ogl_beamforming_amd import configs as cfg, lib, params as P  # noqa: E402
-from tests import tracks_ref as ref  # noqa: E402
-from tests import variants_cases as vc  # noqa: E402
-
-
-def newest(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
+from ogl_beamforming_amd import configs as cfg, lib, params as P
+from tests import tracks_ref as ref
+from tests import variants_cases as vc
+from tests.frame_info import newest_info as newest
 
 
 def paired(points, count, A, reach):

@@ -1,23 +1,15 @@
 """Child process of tests/test_gpu_variants.py: variants pushes in a frame ring of BEAMFORMER_HIP_FRAME_RING_BYTES (the ring is sized
 once per process).  A run of frames that would straddle the end of the ring starts again at offset 0, contiguous, and stays exportable;
-a run the ring cannot hold is refused and takes no frame id."""
+a run the ring cannot hold is refused and takes no frame id.
+Started as python -m tests.variants_wrap_worker from the repository root (tests/scaffold.py run_ring_worker)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from ogl_beamforming_amd import lib, params as P  # noqa: E402
-from tests import variants_cases as vc  # noqa: E402
-
-
-def newest(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
+from ogl_beamforming_amd import lib, params as P
+from tests import variants_cases as vc
+from tests.frame_info import newest_info as newest
 
 
 def main():

@@ -2,25 +2,17 @@
 (the ring is sized once per process): 32 complex 64 x 1 x 64 frames of 32 KiB.  A burst of 16 and a mix 16 -> 15 leave 32 KiB at the
 end of the ring, and the warped copies of the 2 newest frames wrap to offset 0, clear of their sources; another burst of 16 and a mix
 16 -> 14 then fill the ring to its last byte, and the 32 newest frames warped -- a run of the whole ring -- would lie on every one of
-its own sources: FrameSizeOverflow, and nothing has changed; the 14 newest then wrap to offset 0 under a lattice field."""
+its own sources: FrameSizeOverflow, and nothing has changed; the 14 newest then wrap to offset 0 under a lattice field.
+Started as python -m tests.warp_wrap_worker from the repository root (tests/scaffold.py run_ring_worker)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from ogl_beamforming_amd import configs as cfg, lib, params as P  # noqa: E402
-from tests import variants_cases as vc  # noqa: E402
-from tests import warp_ref as ref  # noqa: E402
-
-
-def newest(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
+from ogl_beamforming_amd import configs as cfg, lib, params as P
+from tests import variants_cases as vc
+from tests import warp_ref as ref
+from tests.frame_info import newest_info as newest
 
 
 def share_of_bound(out, frames, field, **k):

@@ -23,8 +23,8 @@ import numpy as np
 from ogl_beamforming_amd import lib as bflib
 from oracle import binding as oracle
 from tests import draws as R, parity
+from tests.das_push import last_timings
 from tests.parity import reference
-from tests.test_gpu_parity import last_timings
 
 ap = argparse.ArgumentParser()
 ap.add_argument("first", type=int)

@@ -17,9 +17,7 @@ import torch
 
 from ogl_beamforming_amd import lib, params as P
 from tests import cases
-from tests.test_gpu_burst import noise_frames, row_end_case
-from tests.test_gpu_views import kernel_views, per_view_views, prepared
-from tests.test_views_host import mixed_views
+from tests.das_push import kernel_views, mixed_views, noise_frames, per_view_views, prepared, row_end_case
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--json", default="")
@@ -294,8 +292,7 @@ finally:
 # from host and from device-resident RF, with pair counting on and under the SCRATCH_POISON hook
 from tests import readi_image_cases as R                                  # noqa: E402
 from tests import variants_cases as vc                                    # noqa: E402
-from tests.test_gpu_burst_views import four_views                         # noqa: E402
-from tests.test_gpu_readi_sweep import GROUPS5, groups_for, sweep_case    # noqa: E402
+from tests.das_push import GROUPS5, four_views, groups_for, sweep_case    # noqa: E402
 
 NO_BURST = P.HIP_DAS_PATH_NO_BURST_KERNEL
 
@@ -478,7 +475,7 @@ for section in ("readi_sweep", "readi_image", "burst_views", "variants", "varian
 
 # ---- the row-column DAS family (das_staged*.hip, das_separable.hip): every named case the gather or a staged kernel takes, under
 # the das path modes and staged-kernel hooks of tests/test_gpu_parity.py -- the frame's digest and the path that produced it
-from tests.test_gpu_parity import SEPARABLE, STAGED                      # noqa: E402
+from tests.das_kernel_cases import SEPARABLE, STAGED                    # noqa: E402
 
 STAGED_SHAPES = ["5,4,5", "4,5,5", "6,4,5", "5,5,5", "4,6,5", "5,4,6", "4,5,6", "6,4,6", "5,5,6", "4,6,6"]
 FAMILY_MODES = [("path0", 0, ()), ("path2", 2, ()), ("path3", 3, ()), ("path3_checked", 3, (("STAGED_CHECKED", "1"),)),

@@ -8,7 +8,7 @@ import json
 import numpy as np
 
 from ogl_beamforming_amd import configs, lib as bflib
-from tests.test_gpu_parity import last_timings
+from tests.das_push import last_timings
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--json", default="")
