@@ -252,6 +252,26 @@ def _prepared(bp, filters, timeout_ms):
     return lib
 
 
+def _described(bp, filters, slot):
+    """The library with the filters and the parameters (block `slot`) of a describe_*() call in place."""
+    L = library()
+    for i, fp in enumerate(filters):
+        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
+    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    return L
+
+
+def _push(kind, rf, on_device_pointer, frame_size, *arguments):
+    """beamformer_hip_push_data_<kind>_with_compute on the host array `rf`, or -- `on_device_pointer` given -- its device-resident twin
+    on that address; `arguments`: what both take after the frame size."""
+    lib = library()
+    if on_device_pointer is not None:
+        call, data = getattr(lib, f"beamformer_hip_push_device_data_{kind}_with_compute"), C.c_void_p(on_device_pointer)
+    else:
+        call, data = getattr(lib, f"beamformer_hip_push_data_{kind}_with_compute"), rf.ctypes.data_as(C.c_void_p)
+    _check(call(data, frame_size, *arguments))
+
+
 def beamform(bp, rf, filters=(), timeout_ms=-1):
     """One frame through the C ABI exactly as tests/throughput.c drives the reference:
     create_filter* -> push_simple_parameters -> push_data_with_compute -> get_last_frames.
@@ -285,24 +305,18 @@ def get_last_frames(bp, count, shard_planes=None):
 def beamform_burst(bp, rf_frames, filters=(), timeout_ms=-1, on_device_pointer=None):
     """N frames of one geometry in one call (beamformer_hip_push_data_burst_with_compute): `rf_frames` is a C-contiguous array
     whose first axis runs over the frames, each frame laid out as beamform() takes it.  Returns (N, Z, Y, X), oldest first."""
-    lib = _prepared(bp, filters, timeout_ms)
+    _prepared(bp, filters, timeout_ms)
     rf_frames = np.ascontiguousarray(rf_frames)
     count = rf_frames.shape[0]
     frame_size = rf_frames.nbytes // count
-    if on_device_pointer is not None:
-        _check(lib.beamformer_hip_push_device_data_burst_with_compute(C.c_void_p(on_device_pointer), frame_size, count, 0, 0))
-    else:
-        _check(lib.beamformer_hip_push_data_burst_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, count, 0, 0))
+    _push("burst", rf_frames, on_device_pointer, frame_size, count, 0, 0)
     return get_last_frames(bp, count)
 
 
 def describe_burst(bp, n, filters=(), slot=0):
     """What a burst of n frames of these parameters would run (beamformer_hip_describe_burst): the description struct; .reason
     says why.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     d = P.HipBurstDescription()
     _check(L.beamformer_hip_describe_burst(slot, n, C.byref(d)))
     return d
@@ -327,25 +341,19 @@ def beamform_readi_sweep(bp, rf_frames, groups=None, filters=(), timeout_ms=-1, 
     """The group acquisitions of a READI sequence in one call (beamformer_hip_push_data_readi_sweep_with_compute): `rf_frames` as
     beamform_burst() takes it, frame k beamformed with readi_group = groups[k]; groups None: (bp.readi_group + k) % readi_group_count.
     Returns (N, Z, Y, X), oldest first."""
-    lib = _prepared(bp, filters, timeout_ms)
+    _prepared(bp, filters, timeout_ms)
     rf_frames = np.ascontiguousarray(rf_frames)
     count = rf_frames.shape[0]
     assert groups is None or len(groups) == count
     frame_size = rf_frames.nbytes // count
-    if on_device_pointer is not None:
-        _check(lib.beamformer_hip_push_device_data_readi_sweep_with_compute(C.c_void_p(on_device_pointer), frame_size, count, _group_array(groups), 0, 0))
-    else:
-        _check(lib.beamformer_hip_push_data_readi_sweep_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, count, _group_array(groups), 0, 0))
+    _push("readi_sweep", rf_frames, on_device_pointer, frame_size, count, _group_array(groups), 0, 0)
     return get_last_frames(bp, count)
 
 
 def describe_readi_sweep(bp, n, groups=None, filters=(), slot=0):
     """What a READI sweep of n frames of these parameters would run (beamformer_hip_describe_readi_sweep): the description struct;
     .reason says why.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     d = P.HipBurstDescription()
     _check(L.beamformer_hip_describe_readi_sweep(slot, _group_array(groups), n, C.byref(d)))
     return d
@@ -364,25 +372,19 @@ def beamform_readi_image(bp, rf_frames, groups=None, filters=(), timeout_ms=-1, 
     """The group acquisitions of a READI sequence compounded into ONE frame (beamformer_hip_push_data_readi_image_with_compute):
     `rf_frames` and `groups` as beamform_readi_sweep() takes them.  Returns the image, (Z, Y, X): the derived FORCES block's frame of
     the DAS input decoded across the acquisitions -- without coherency weighting the sum of the sweep's frames."""
-    lib = _prepared(bp, filters, timeout_ms)
+    _prepared(bp, filters, timeout_ms)
     rf_frames = np.ascontiguousarray(rf_frames)
     count = rf_frames.shape[0]
     assert groups is None or len(groups) == count
     frame_size = rf_frames.nbytes // count
-    if on_device_pointer is not None:
-        _check(lib.beamformer_hip_push_device_data_readi_image_with_compute(C.c_void_p(on_device_pointer), frame_size, count, _group_array(groups), 0, 0))
-    else:
-        _check(lib.beamformer_hip_push_data_readi_image_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, count, _group_array(groups), 0, 0))
+    _push("readi_image", rf_frames, on_device_pointer, frame_size, count, _group_array(groups), 0, 0)
     return get_last_frame(bp)
 
 
 def describe_readi_image(bp, n, groups=None, filters=(), slot=0):
     """What a READI image push of n RF frames of these parameters would run (beamformer_hip_describe_readi_image): the description
     struct; .reason says what.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     d = P.HipReadiImageDescription()
     _check(L.beamformer_hip_describe_readi_image(slot, _group_array(groups), n, C.byref(d)))
     return d
@@ -444,23 +446,17 @@ def get_last_views(views):
 def beamform_views(bp, rf, views, filters=(), timeout_ms=-1, on_device_pointer=None):
     """ONE RF frame on K grids in one call (beamformer_hip_push_data_views_with_compute): everything but the grid from `bp`, view k on
     views[k] (HipView: see view()).  `rf` as beamform() takes it.  Returns a list of K arrays (Z, Y, X), in view order."""
-    lib = _prepared(bp, filters, timeout_ms)
+    _prepared(bp, filters, timeout_ms)
     rf = np.ascontiguousarray(rf)
     array, count = _view_array(views)
-    if on_device_pointer is not None:
-        _check(lib.beamformer_hip_push_device_data_views_with_compute(C.c_void_p(on_device_pointer), rf.nbytes, array, count, 0))
-    else:
-        _check(lib.beamformer_hip_push_data_views_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, array, count, 0))
+    _push("views", rf, on_device_pointer, rf.nbytes, array, count, 0)
     return get_last_views(views)
 
 
 def describe_views(bp, views, filters=(), slot=0):
     """What a views push of these grids would run (beamformer_hip_describe_views): the description struct; .path[k] is view k's own
     single-frame decision, .reason says why this route.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     array, count = _view_array(views)
     d = P.HipViewsDescription()
     _check(L.beamformer_hip_describe_views(slot, array, count, C.byref(d)))
@@ -502,23 +498,17 @@ def beamform_variants(bp, rf, variants, filters=(), timeout_ms=-1, on_device_poi
     """ONE RF frame under K sets of DAS scalars in one call (beamformer_hip_push_data_variants_with_compute): everything but speed of
     sound, time offset and f-number from `bp`, frame k under variants[k] (HipDasVariant: see variant()).  `rf` as beamform() takes it.
     Returns (K, Z, Y, X), variant 0 first."""
-    lib = _prepared(bp, filters, timeout_ms)
+    _prepared(bp, filters, timeout_ms)
     rf = np.ascontiguousarray(rf)
     array, count = _variant_array(variants)
-    if on_device_pointer is not None:
-        _check(lib.beamformer_hip_push_device_data_variants_with_compute(C.c_void_p(on_device_pointer), rf.nbytes, array, count, 0, 0))
-    else:
-        _check(lib.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, array, count, 0, 0))
+    _push("variants", rf, on_device_pointer, rf.nbytes, array, count, 0, 0)
     return get_last_frames(bp, count)
 
 
 def describe_variants(bp, variants, filters=(), slot=0):
     """What a variants push of these candidates would run (beamformer_hip_describe_variants): the description struct; .path[k] is
     variant k's own single-frame decision, .taken[k] whether the fused launch takes it, .reason says why this route.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     array, count = _variant_array(variants)
     d = P.HipVariantsDescription()
     _check(L.beamformer_hip_describe_variants(slot, array, count, C.byref(d)))
@@ -1023,16 +1013,13 @@ def beamform_burst_views(bp, rf_frames, views, filters=(), timeout_ms=-1, on_dev
     """N RF frames on K grids in one call (beamformer_hip_push_data_burst_views_with_compute): `rf_frames` as beamform_burst() takes it,
     `views` as beamform_views() does.  Returns a list of K lists of N arrays (Z, Y, X): [v][k] is (view v, RF frame k) -- the order the
     frames are queued in, view-major."""
-    lib = _prepared(bp, filters, timeout_ms)
+    _prepared(bp, filters, timeout_ms)
     rf_frames = np.ascontiguousarray(rf_frames)
     n = rf_frames.shape[0]
     frame_size = rf_frames.nbytes // n
     views = list(views)
     array, count = _view_array(views)
-    if on_device_pointer is not None:
-        _check(lib.beamformer_hip_push_device_data_burst_views_with_compute(C.c_void_p(on_device_pointer), frame_size, n, array, count, 0))
-    else:
-        _check(lib.beamformer_hip_push_data_burst_views_with_compute(rf_frames.ctypes.data_as(C.c_void_p), frame_size, n, array, count, 0))
+    _push("burst_views", rf_frames, on_device_pointer, frame_size, n, array, count, 0)
     flat = get_last_views([v for v in views for _ in range(n)])
     return [flat[v * n:(v + 1) * n] for v in range(count)]
 
@@ -1040,10 +1027,7 @@ def beamform_burst_views(bp, rf_frames, views, filters=(), timeout_ms=-1, on_dev
 def describe_burst_views(bp, n, views, filters=(), slot=0):
     """What a burst views push of n RF frames on these grids would run (beamformer_hip_describe_burst_views): the description struct;
     .rung is the ladder's rung, .path[k] view k's own single-frame decision, .reason says why.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     array, count = _view_array(views)
     d = P.HipBurstViewsDescription()
     _check(L.beamformer_hip_describe_burst_views(slot, n, array, count, C.byref(d)))
@@ -1116,10 +1100,7 @@ def set_hook(name, value=None):
 def describe_das(bp, filters=(), slot=0):
     """The DAS kernel the library would run for these parameters under the current das path mode, and why the others
     were declined (beamformer_hip_describe_das): (path, kernel, name, {path number: reason}, description struct).  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     d = P.HipDasDescription()
     assert L.beamformer_hip_describe_das(slot, C.byref(d)), last_error()
     reasons = {k: bytes(d.declined[k]).split(b"\0")[0].decode() for k in range(8)}
@@ -1130,10 +1111,7 @@ def describe_upload(bp, data_size, frame_count=1, device_pointer=None, filters=(
     """How the RF of a push of these parameters would reach the RF ring (beamformer_hip_describe_upload): the description struct;
     .route is a P.UploadRoute, .name says it in words.  data_size: the bytes of one raw frame; device_pointer: the address a
     device-resident push would be given, None for host data.  Needs no device."""
-    L = library()
-    for i, fp in enumerate(filters):
-        assert L.beamformer_create_filter(C.byref(fp), i, slot), last_error()
-    assert L.beamformer_push_simple_parameters_at(C.byref(bp), slot), last_error()
+    L = _described(bp, filters, slot)
     d = P.HipUploadDescription()
     _check(L.beamformer_hip_describe_upload(slot, data_size, frame_count, C.c_void_p(device_pointer), C.byref(d)))
     return d

@@ -1,5 +1,6 @@
-"""The scaffolding GPU test modules share: the fixture that leaves the automatic DAS path behind, the two-contexts-on-one-device dance of the
-test_several_devices_are_refused tests, and the launcher of the *_wrap_worker.py processes.  Imports nothing of tests/."""
+"""The scaffolding test modules share: the fixtures that leave the automatic DAS path behind (on the device, and on the host), the
+two-contexts-on-one-device dance of the test_several_devices_are_refused tests, and the launcher of the *_wrap_worker.py processes.
+Imports nothing of tests/."""
 import contextlib
 import ctypes as C
 import os
@@ -19,6 +20,15 @@ def automatic_path(bflib):
     L.beamformer_hip_set_das_path(0)
     yield
     L.beamformer_hip_set_das_path(0)
+
+
+@pytest.fixture(autouse=True)
+def automatic_path_on_the_host():
+    """automatic_path for the modules that need no device: no bflib, no timeout; autouse in every module that imports it by name"""
+    from ogl_beamforming_amd import lib
+    lib.library().beamformer_hip_set_das_path(0)
+    yield
+    lib.library().beamformer_hip_set_das_path(0)
 
 
 @contextlib.contextmanager

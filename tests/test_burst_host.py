@@ -1,10 +1,7 @@
-"""Bursts (beamformer_hip_push_data_burst_with_compute) on the CPU: the four entry points exist and are bound, the burst kernel is
-in the library with its twelve instantiations, beamformer_hip_describe_burst (no device needed) names the route the rules of
-csrc/das_select.cpp give, and a malformed burst is refused before any device is touched."""
+"""Bursts (beamformer_hip_push_data_burst_with_compute) on the CPU: beamformer_hip_describe_burst (no device needed) names the route the
+rules of csrc/das_select.cpp give.  What a burst shares with every other multi-frame push -- its symbols, its kernel's instantiations,
+its refusals -- is asked of all kinds in tests/test_push_contract_host.py."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,35 +10,7 @@ from ogl_beamforming_amd import lib
 from ogl_beamforming_amd import params as P
 from tests import burst_chunk_cases, cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E = P.LibError
-BURST_SYMBOLS = ("beamformer_hip_push_data_burst_with_compute", "beamformer_hip_push_device_data_burst_with_compute",
-                 "beamformer_hip_describe_burst", "beamformer_hip_get_last_burst_info")
-
-
-def test_the_four_burst_symbols_are_declared_exported_and_bound():
-    header = open(os.path.join(ROOT, "include", "ogl_beamformer_hip.h")).read()
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIBRARY_PATH], capture_output=True, text=True, check=True)
-    exported = {line.split()[-1] for line in nm.stdout.splitlines() if " T " in line}
-    for name in BURST_SYMBOLS:
-        assert f"{name}(" in header, name
-        assert name in exported, name
-        assert name in lib.exported_symbols(), name
-    assert "#define BEAMFORMER_HIP_MAX_BURST_FRAMES" in header and P.HIP_MAX_BURST_FRAMES >= 256
-    # the structs the binding mirrors: 6 words + the reason; the description + 3 words + 24 kinds + 24 times + the total
-    assert C.sizeof(P.HipBurstDescription) == 24 + 160
-    assert C.sizeof(P.HipBurstInfo) == 184 + 12 + 4 * 24 + 4 * 24 + 4
-
-
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
-def test_the_burst_kernel_has_twelve_instantiations_without_spills():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    kernels = [k for k in kernel_resources.kernels_of(lib.LIBRARY_PATH) if "das_burst_kernel" in k["demangled"]]
-    assert len({k["demangled"] for k in kernels}) == 12, sorted(k["demangled"] for k in kernels)
-    for k in kernels:
-        assert not k["vgpr_spill_count"] and not k["private_segment_fixed_size"], k["demangled"]
-        assert k["vgpr_count"] <= 128, (k["demangled"], k["vgpr_count"])        # 256-thread blocks: 4 waves per SIMD at least
 
 
 @pytest.mark.parametrize("name", ["config1_small", "rca_flash_none_tx", "rca_cubic_real"])
@@ -129,38 +98,3 @@ def test_the_chunk_boundary_cases_cross_a_chunk(name):
     a = bc.assignment(9400)
     assert len(a) == bc.FRAMES and len({a[254], a[255], a[256]}) == 3 and a[255] != a[0] and a[256] != a[1]
     assert np.array_equal(a, bc.assignment(9400)) and len(set(a)) == bc.SOURCES
-
-
-def push_parameters(acq):
-    L = lib.library()
-    for s, fp in enumerate(acq.filters):
-        assert L.beamformer_create_filter(C.byref(fp), s, 0)
-    assert L.beamformer_push_simple_parameters(C.byref(acq.bp)), lib.last_error()
-    return L
-
-
-def test_malformed_bursts_are_refused_before_a_device_is_touched():
-    acq = cases.make("config1_small")
-    L = push_parameters(acq)
-    rf = np.ascontiguousarray(np.stack([acq.rf] * 3))
-    ptr, size = rf.ctypes.data_as(C.c_void_p), acq.rf.nbytes
-    burst = L.beamformer_hip_push_data_burst_with_compute
-    assert not burst(ptr, size, 0, 0, 0) and lib.last_error()[0] == E.BufferOverflow
-    assert not burst(ptr, size, P.HIP_MAX_BURST_FRAMES + 1, 0, 0) and lib.last_error()[0] == E.BufferOverflow
-    # the single push's checks, with its error kinds (lib/ogl_beamformer_lib.c:503-511)
-    assert not burst(ptr, size - 2, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
-    assert not burst(ptr, size + 2, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
-    assert not burst(ptr, size, 3, 7, 0) and lib.last_error()[0] == E.InvalidImagePlane
-    assert not burst(ptr, size, 3, 0, 5) and lib.last_error()[0] == E.ParameterBlockUnallocated
-    assert not burst(None, size, 3, 0, 0) and lib.last_error()[0] == E.BufferOverflow
-    assert not L.beamformer_hip_push_device_data_burst_with_compute(ptr, size - 2, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
-
-
-def test_a_burst_larger_than_the_frame_ring_is_refused_whole():
-    """1024 x 1024 complex voxels are 8 MiB a frame: 1024 of them are twice the default 4 GiB ring (one of them fits)"""
-    acq = cases.make("config1_small")
-    acq.bp.output_points[:] = [1024, 1024, 1, 1]
-    L = push_parameters(acq)
-    rf = np.zeros((1024,) + acq.rf.shape, acq.rf.dtype)
-    assert not L.beamformer_hip_push_data_burst_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 1024, 0, 0)
-    assert lib.last_error()[0] == E.FrameSizeOverflow

@@ -116,19 +116,6 @@ def test_bursts_and_single_pushes_interleaved_come_back_oldest_first(bflib, orac
     assert not L.beamformer_hip_get_last_burst_info(C.byref(P.HipBurstInfo())) and bflib.last_error()[0] == E.InvalidAccess
 
 
-@pytest.mark.parametrize("name", ["config1_small", "rca_shuffled_padded", "forces"])
-def test_device_resident_bursts_equal_host_bursts(name, bflib):
-    import torch
-    acq = cases.make(name)
-    rf = noise_frames(acq, 5, 4500)
-    host = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
-    dev = torch.from_numpy(rf.view(np.uint8).reshape(-1)).cuda()
-    torch.cuda.synchronize()
-    device = bflib.beamform_burst(acq.bp, rf, acq.filters, on_device_pointer=dev.data_ptr())
-    for k in range(5):
-        assert same_bits(host[k], device[k]), k
-
-
 def test_a_burst_that_wraps_the_ring_stays_exportable():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/burst_wrap_worker.py"""
     run_ring_worker("burst_wrap_worker", 1 << 20, expect=("wrapped",), timeout=600)
@@ -166,50 +153,6 @@ def test_timings_of_a_burst_are_per_frame_shares(bflib):
         assert burst_pairs == int(t.das_pairs) > 0
     finally:
         L.beamformer_hip_enable_pair_counting(0)
-
-
-def test_an_output_shard_is_honoured(bflib):
-    L = bflib.library()
-    acq = cases.make("rca_vls_cw")                       # 12 x 10 x 14
-    rf = noise_frames(acq, 3, 4650)
-    whole = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
-    try:
-        assert L.beamformer_hip_set_output_shard(0, 4, 6)
-        assert L.beamformer_hip_push_data_burst_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 3, 0, 0), bflib.last_error()
-        part = bflib.get_last_frames(acq.bp, 3, shard_planes=6)
-    finally:
-        assert L.beamformer_hip_set_output_shard(0, 0, 0)
-    for k in range(3):
-        assert same_bits(part[k], np.ascontiguousarray(whole[k][4:10])), k
-
-
-def test_several_devices_refuse_a_burst_and_frame_graphs_change_nothing(bflib, capfd):
-    L = bflib.library()
-    acq = cases.make("config1_small")
-    rf = noise_frames(acq, 5, 4700)
-    plain = bflib.beamform_burst(acq.bp, rf, acq.filters).copy()
-    try:
-        L.beamformer_hip_enable_frame_graphs(1)
-        for _ in range(2):            # (a plan's first frame never runs from a graph)
-            graphs = bflib.beamform_burst(acq.bp, rf, acq.filters)
-        for k in range(5):
-            assert same_bits(plain[k], graphs[k]), k
-    finally:
-        L.beamformer_hip_enable_frame_graphs(0)
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        assert L.beamformer_push_simple_parameters(C.byref(acq.bp))
-        capfd.readouterr()
-        assert not L.beamformer_hip_push_data_burst_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 5, 0, 0)
-        assert bflib.last_error()[0] == E.InvalidAccess
-        assert "one device" in capfd.readouterr().err
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    again = bflib.beamform_burst(acq.bp, rf, acq.filters)
-    for k in range(5):
-        assert same_bits(plain[k], again[k]), k
 
 
 @pytest.mark.parametrize("seed", RCA_SEEDS)

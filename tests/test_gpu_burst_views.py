@@ -18,13 +18,13 @@ from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import cases
 from tests.das_push import (box, case_of, close_to_single_push, compare, DISPATCH_CASES, four_views, I, inner, KERNEL_CASES, mode_for, noise_frames,
-                            on_grid, per_view_views, row_end_case, same_bits, single_push)
+                            on_grid, per_view_views, row_end_case, same_bits)
 from tests.parity import reference
+from tests.push_kinds import frame_id
 from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
-NO_BURST, NO_VIEWS, FAIL_DAS = P.HIP_DAS_PATH_NO_BURST_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL, P.HIP_DAS_PATH_FAIL_VIEWS_DAS
+NO_BURST, NO_VIEWS = P.HIP_DAS_PATH_NO_BURST_KERNEL, P.HIP_DAS_PATH_NO_VIEWS_KERNEL
 PER_VIEW_CASES = ["forces", "hercules_wide_cw", "rca_staged_auto"]
 N = 5
 
@@ -229,12 +229,6 @@ def test_rows_that_end_inside_the_views(interp, bflib):
         assert not refs[2][k][1].any() and np.array_equal(frames[2][k], refs[2][k][1])
 
 
-def frame_id(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
-
-
 @pytest.mark.parametrize("flag", [0, NO_BURST, NO_VIEWS], ids=["rung1", "rung2", "rung3"])
 def test_ids_layout_timings_and_info(flag, bflib):
     L = bflib.library()
@@ -292,31 +286,6 @@ def test_ids_layout_timings_and_info(flag, bflib):
     assert not L.beamformer_hip_copy_das_input_frame(N, burst_input[0].ctypes.data_as(C.c_void_p), burst_input[0].nbytes)
 
 
-def test_only_the_newest_multi_frame_push_serves_its_info(bflib):
-    L = bflib.library()
-    acq, rf, views, _ = prepared("config1_small")
-
-    def served():
-        out = []
-        for call, info in ((L.beamformer_hip_get_last_burst_views_info, P.HipBurstViewsInfo()), (L.beamformer_hip_get_last_views_info, P.HipViewsInfo()),
-                           (L.beamformer_hip_get_last_burst_info, P.HipBurstInfo()), (L.beamformer_hip_get_last_readi_image_info, P.HipReadiImageInfo())):
-            out.append(True if call(C.byref(info)) else bflib.last_error()[0])
-        return out
-
-    no = E.InvalidAccess
-    bflib.beamform_burst_views(acq.bp, rf, views, acq.filters)
-    assert served() == [True, no, no, no]
-    bflib.beamform_views(acq.bp, rf[0], views, acq.filters)
-    assert served() == [no, True, no, no]
-    bflib.beamform_burst_views(acq.bp, rf[:1], views, acq.filters)          # one RF frame: the same code
-    assert served() == [True, no, no, no]
-    bflib.beamform_burst(acq.bp, rf, acq.filters)
-    assert served() == [no, no, True, no]
-    bflib.beamform_burst_views(acq.bp, rf[:2], views, acq.filters)
-    bflib.beamform(acq.bp, rf[0], acq.filters)
-    assert served() == [no, no, no, no]
-
-
 def test_pair_counting_runs_once_per_view(bflib):
     L = bflib.library()
     acq, rf, views, refs = prepared("rca_cubic_real")
@@ -333,68 +302,9 @@ def test_pair_counting_runs_once_per_view(bflib):
         L.beamformer_hip_enable_pair_counting(0)
 
 
-def test_device_resident_rf_equals_host_rf(bflib):
-    import torch
-    acq, rf, views, _ = prepared("config1_small")
-    host = bflib.beamform_burst_views(acq.bp, rf, views, acq.filters)
-    dev = torch.from_numpy(np.ascontiguousarray(rf).view(np.uint8).reshape(-1)).cuda()
-    torch.cuda.synchronize()
-    device = bflib.beamform_burst_views(acq.bp, rf, views, acq.filters, on_device_pointer=dev.data_ptr())
-    for v in range(len(views)):
-        for k in range(N):
-            assert same_bits(host[v][k], device[v][k]), (v, k)
-
-
 def test_a_run_that_wraps_the_ring_starts_again_at_0():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/burst_views_wrap_worker.py"""
     run_ring_worker("burst_views_wrap_worker", 1 << 20, expect=("wrapped",), timeout=600)
-
-
-@pytest.mark.parametrize("flag", [0, NO_BURST, NO_VIEWS], ids=["rung1", "rung2", "rung3"])
-def test_a_push_that_fails_leaves_a_tombstone_under_every_one_of_its_ids(flag, bflib):
-    """das path flag 0x2000 fails the push at its DAS stage as it fails a views push: its ids are taken, its frames placed, nothing
-    launched there.  Every reader of "the newest frame" then fails; older good frames stay exportable; the next push is served."""
-    L = bflib.library()
-    acq, rf, views, _ = prepared("rca_cubic_real")
-    K = len(views)
-    F = N * K
-    array = (P.HipView * K)(*views)
-    ptr = rf.ctypes.data_as(C.c_void_p)
-    L.beamformer_hip_set_das_path(flag)
-    good = bflib.beamform_burst_views(acq.bp, rf, views, acq.filters)
-    L.beamformer_hip_set_das_path(flag | FAIL_DAS)
-    assert same_bits(single_push(bflib, acq, rf[0]), bflib.beamform(acq.bp, rf[0], acq.filters))      # the flag fails no single push
-    older = bflib.get_last_frame(acq.bp).copy()
-    newest = frame_id(L).frame_id
-    assert not L.beamformer_hip_push_data_burst_views_with_compute(ptr, rf[0].nbytes, N, array, K, 0)
-    assert bflib.last_error()[0] == E.InvalidAccess
-    sentinel = np.full(sum((f.nbytes + 63) // 64 * 64 for row in good for f in row) // 4 + older.size + 64, -7.0, np.float32)
-    sptr = sentinel.ctypes.data_as(C.c_void_p)
-    for count in (1, N, F):              # the newest frame is missing: an error, and nothing of the failed push is served
-        assert not L.beamformer_get_last_frames(sptr, sentinel.nbytes, count)
-        assert bflib.last_error()[0] == E.InvalidAccess and (sentinel == -7.0).all()
-    assert not L.beamformer_hip_get_last_frame_info(C.byref(P.HipFrameInfo()))
-    assert not L.beamformer_hip_get_last_burst_views_info(C.byref(P.HipBurstViewsInfo())) and bflib.last_error()[0] == E.InvalidAccess
-    assert not L.beamformer_hip_get_last_frame_timings(C.byref(P.HipFrameTimings()))
-    assert not L.beamformer_hip_frame_min_max((C.c_float * 2)())
-    assert (sentinel == -7.0).all()
-    # the last F + 1 frames: F tombstones are skipped, the older good frame is still exported; the call reports the missing newest one
-    assert not L.beamformer_get_last_frames(sptr, sentinel.nbytes, F + 1)
-    assert np.array_equal(sentinel[: older.size].view(np.uint32), older.reshape(-1).view(np.uint32))
-    assert (sentinel[(older.nbytes + 63) // 64 * 16:] == -7.0).all()
-    # every row of the failed push in the 32-frame table stays zero
-    table = P.ComputeStatsTable()
-    assert L.beamformer_compute_timings(C.byref(table), -1)
-    for j in range(F):
-        assert not any(table.times[(newest + 1 + j) % 32][col] for col in range(int(table.shader_count)))
-    # the library is not wedged: the failed push consumed its F ids, the next good one takes the next F and is served whole
-    L.beamformer_hip_set_das_path(flag)
-    again = bflib.beamform_burst_views(acq.bp, rf, views, acq.filters)
-    info = bflib.last_burst_views_info()
-    assert info.first_frame_id == newest + 1 + F and (info.frame_count, info.view_count) == (N, K)
-    for v in range(K):
-        for k in range(N):
-            assert same_bits(again[v][k], good[v][k]), (v, k)
 
 
 @pytest.mark.parametrize("flag", [0, NO_BURST], ids=["rung1", "rung2"])

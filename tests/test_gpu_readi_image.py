@@ -16,10 +16,10 @@ from tests import cases
 from tests import readi_image_cases as R
 from tests.das_push import compare, last_timings, noise_frames, same_bits
 from tests.parity import reference
+from tests.push_kinds import group_list, image, last_frame_id
 from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
 I = P.InterpolationMode
 S = P.ShaderKind
 
@@ -30,38 +30,6 @@ VARIANTS += [("g12a1", I.Linear, "real", False, "partial"), ("g12a1", I.Cubic, "
              ("g4a4", I.Cubic, "real", False, "no-list"), ("g8a2", I.Linear, "iq", True, "no-list"),
              ("g4a4", I.Linear, "iq", False, "one"), ("g2a8", I.Cubic, "real", True, "one")]
 VARIANT_IDS = [f"{g}-{interp.name.lower()}-{kind}{'-cw' if cw else ''}-{listed}" for g, interp, kind, cw, listed in VARIANTS]
-
-
-def group_list(geometry, listed):
-    """(group list as the push takes it, frame count)"""
-    G = R.GEOMETRIES[geometry][0]
-    if listed == "partial":
-        return R.PARTIAL12, len(R.PARTIAL12)
-    if listed == "no-list":
-        return None, G                               # (block.readi_group + k) % G, readi_group 1
-    if listed == "one":
-        return [G - 1], 1
-    return R.PERMUTATIONS[geometry], G
-
-
-def last_frame_id(bflib):
-    info = P.HipFrameInfo()
-    assert bflib.library().beamformer_hip_get_last_frame_info(C.byref(info)), bflib.last_error()
-    return int(info.frame_id)
-
-
-def image(bflib, acq, rf, groups, device_pointer=None):
-    """one image push; the route the library reports is the one described.  Returns (frame, info)."""
-    n = len(rf)
-    G, A = int(acq.bp.readi_group_count), int(acq.bp.acquisition_count)
-    described = bflib.describe_readi_image(acq.bp, n, groups, acq.filters)
-    frame = bflib.beamform_readi_image(acq.bp, rf, groups, acq.filters, on_device_pointer=device_pointer).copy()
-    info = bflib.last_readi_image_info()
-    assert info.rf_frame_count == n and info.frame_id == last_frame_id(bflib)
-    assert bytes(info.route) == bytes(described), (info.route.reason, described.reason)
-    assert info.route.transmit_count == G * A and info.route.decode_launches == 1 and info.route.das_launches == 1
-    assert int(last_timings(bflib).das_path) == info.route.das_path
-    return frame, info
 
 
 @pytest.fixture(autouse=True)
@@ -178,55 +146,6 @@ def test_one_id_one_frame_and_the_stage_list(bflib):
     assert same_bits(again, frame) and info2.frame_id == before + 2
 
 
-def test_the_push_infos_refuse_each_others_pushes(bflib):
-    acq = R.image_case("g4a4", I.Linear, "real")
-    rf = noise_frames(acq, 4, 6700)
-    image(bflib, acq, rf, None)
-    for other in (bflib.last_burst_info, bflib.last_views_info):
-        with pytest.raises(bflib.BeamformerError) as e:
-            other()
-        assert e.value.kind == E.InvalidAccess
-    bflib.beamform_burst(acq.bp, rf, acq.filters)
-    with pytest.raises(bflib.BeamformerError) as e:
-        bflib.last_readi_image_info()
-    assert e.value.kind == E.InvalidAccess
-    bflib.beamform_readi_sweep(acq.bp, rf, None, acq.filters)
-    with pytest.raises(bflib.BeamformerError):
-        bflib.last_readi_image_info()
-    bflib.beamform(acq.bp, rf[0], acq.filters)
-    with pytest.raises(bflib.BeamformerError):
-        bflib.last_readi_image_info()
-
-
-def test_an_output_shard_is_honoured(bflib):
-    L = bflib.library()
-    acq = R.image_case("g8a2", I.Linear, "iq")              # 32 x 1 x 32
-    groups = R.PERMUTATIONS["g8a2"]
-    rf = noise_frames(acq, 8, 6800)
-    whole, _ = image(bflib, acq, rf, groups)
-    array = (C.c_uint32 * 8)(*groups)
-    try:
-        assert L.beamformer_hip_set_output_shard(0, 9, 13)
-        assert L.beamformer_hip_push_data_readi_image_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 8, array, 0, 0), bflib.last_error()
-        assert bflib.last_readi_image_info().route.das_launches == 1
-        part = bflib.get_last_frame(acq.bp, shard_planes=13).copy()
-    finally:
-        assert L.beamformer_hip_set_output_shard(0, 0, 0)
-    assert same_bits(part, np.ascontiguousarray(whole[9:22]))
-
-
-def test_the_device_resident_variant_equals_the_host_variant(bflib):
-    import torch
-    acq = R.image_case("g8a2", I.Cubic, "iq", True)
-    groups = R.PERMUTATIONS["g8a2"]
-    rf = noise_frames(acq, 8, 6900)
-    host, _ = image(bflib, acq, rf, groups)
-    dev = torch.from_numpy(rf.view(np.uint8).reshape(-1)).cuda()
-    torch.cuda.synchronize()
-    device, _ = image(bflib, acq, rf, groups, device_pointer=dev.data_ptr())
-    assert same_bits(host, device)
-
-
 def test_pair_counting_counts_on_the_derived_block(bflib):
     L = bflib.library()
     acq = R.image_case("g4a4", I.Linear, "real")
@@ -246,54 +165,3 @@ def test_pair_counting_counts_on_the_derived_block(bflib):
     finally:
         L.beamformer_hip_enable_pair_counting(0)
     assert same_bits(plain, counted)
-
-
-def test_several_devices_refuse_an_image_push_and_frame_graphs_change_nothing(bflib, capfd):
-    L = bflib.library()
-    acq = R.image_case("g4a4", I.Cubic, "real")
-    groups = R.PERMUTATIONS["g4a4"]
-    rf = noise_frames(acq, 4, 7100)
-    array = (C.c_uint32 * 4)(*groups)
-    plain, _ = image(bflib, acq, rf, groups)
-    try:
-        L.beamformer_hip_enable_frame_graphs(1)
-        for _ in range(2):
-            graphs, _ = image(bflib, acq, rf, groups)
-        assert same_bits(plain, graphs)
-    finally:
-        L.beamformer_hip_enable_frame_graphs(0)
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        assert L.beamformer_push_simple_parameters(C.byref(acq.bp))
-        capfd.readouterr()
-        assert not L.beamformer_hip_push_data_readi_image_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 4, array, 0, 0)
-        assert bflib.last_error()[0] == E.InvalidAccess
-        assert "one device" in capfd.readouterr().err
-        info = P.HipFrameInfo()
-        assert not L.beamformer_hip_get_last_frame_info(C.byref(info))                # nothing was queued
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    again, _ = image(bflib, acq, rf, groups)
-    assert same_bits(plain, again)
-
-
-def test_refusals_on_the_device_consume_no_id(bflib, capfd):
-    """the refusals of tests/test_readi_image_host.py with a device up: the newest frame stays the newest"""
-    L = bflib.library()
-    acq = R.image_case("g4a4", I.Linear, "real")
-    rf = noise_frames(acq, 5, 7200)
-    frame, info = image(bflib, acq, rf[:4], None)
-    data, size = rf.ctypes.data_as(C.c_void_p), rf[0].nbytes
-    for count, groups, kind in ((0, None, E.BufferOverflow), (1025, None, E.BufferOverflow), (5, [0, 1, 2, 3, 4], E.InvalidComputeStage)):
-        array = None if groups is None else (C.c_uint32 * len(groups))(*groups)
-        assert not L.beamformer_hip_push_data_readi_image_with_compute(data, size, count, array, 0, 0)
-        assert bflib.last_error()[0] == kind
-    flash = cases.make("config1_small")
-    assert L.beamformer_push_simple_parameters_at(C.byref(flash.bp), 1)
-    assert not L.beamformer_hip_push_data_readi_image_with_compute(flash.rf.ctypes.data_as(C.c_void_p), flash.rf.nbytes, 1, None, 0, 1)
-    assert bflib.last_error()[0] == E.InvalidAccess
-    assert last_frame_id(bflib) == info.frame_id
-    assert same_bits(bflib.get_last_frame(acq.bp).copy(), frame)
-    assert bflib.last_readi_image_info().frame_id == info.frame_id

@@ -17,10 +17,10 @@ from ogl_beamforming_amd import params as P
 from tests import cases
 from tests.das_push import close_to_single_push, compare, GEOMETRIES, GROUPS5, groups_for, noise_frames, S, same_bits, sweep_case
 from tests.parity import reference
+from tests.push_kinds import sweep
 from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
 I = P.InterpolationMode
 
 GROUPS9 = [1, 3, 0, 0, 2, 3, 1, 2, 0]
@@ -74,26 +74,6 @@ def judge(oracle, acq, rf_seed, rf, ks, groups, frames, label):
         v = compare(frames[i], ref, acq_k, flags, label=f"{acq.name}/{label}/{i}")
         worst = max(worst, v.max_rel_err)
     return worst
-
-
-def sweep(bflib, acq, rf, groups, expect_kernel=True, device_pointer=None):
-    """one sweep; the route the library reports is the one described, and -- on the kernel -- one DAS launch of four frames a thread"""
-    n = len(rf)
-    described = bflib.describe_readi_sweep(acq.bp, n, groups, acq.filters)
-    assert bool(described.burst_kernel) == expect_kernel, described.reason
-    frames = bflib.beamform_readi_sweep(acq.bp, rf, groups, acq.filters, on_device_pointer=device_pointer).copy()
-    info = bflib.last_burst_info()
-    assert info.frame_count == n and bool(info.route.burst_kernel) == expect_kernel, info.route.reason
-    assert info.route.das_launches == described.das_launches and info.route.single_path == described.single_path
-    assert info.route.min_frames == described.min_frames
-    if expect_kernel:
-        assert info.route.das_launches == 1 and info.route.frames_per_thread == 4
-    else:
-        assert info.route.das_launches == n and info.route.frames_per_thread == 1
-    frame_info = P.HipFrameInfo()
-    assert bflib.library().beamformer_hip_get_last_frame_info(C.byref(frame_info)) and frame_info.frame_id == info.first_frame_id + n - 1
-    assert frames.shape[0] == n
-    return frames
 
 
 def single_push(bflib, acq, rf, group):
@@ -223,19 +203,6 @@ def test_sweeps_single_pushes_and_bursts_interleaved_come_back_oldest_first(bfli
         assert same_bits(got[k], frame), k
 
 
-def test_the_device_resident_variant_equals_the_host_variant(bflib):
-    import torch
-    acq = sweep_case("g8a2", I.Cubic, True, True)
-    rf = noise_frames(acq, 5, 5500)
-    groups = groups_for(acq, [5, 0, 7, 7, 2])
-    host = sweep(bflib, acq, rf, groups)
-    dev = torch.from_numpy(rf.view(np.uint8).reshape(-1)).cuda()
-    torch.cuda.synchronize()
-    device = sweep(bflib, acq, rf, groups, device_pointer=dev.data_ptr())
-    for k in range(5):
-        assert same_bits(host[k], device[k]), k
-
-
 def test_timing_rows_are_shares_and_pair_counts_are_the_single_frames(bflib):
     L = bflib.library()
     acq = sweep_case("g4a4", I.Linear, False, False)
@@ -275,55 +242,6 @@ def test_timing_rows_are_shares_and_pair_counts_are_the_single_frames(bflib):
     finally:
         L.beamformer_hip_set_das_path(0)
         L.beamformer_hip_enable_pair_counting(0)
-
-
-def test_an_output_shard_is_honoured(bflib):
-    L = bflib.library()
-    acq = sweep_case("g8a2", I.Linear, True, False)          # 32 x 1 x 32
-    rf = noise_frames(acq, 5, 5700)
-    groups = groups_for(acq, [6, 1, 1, 4, 3])
-    whole = sweep(bflib, acq, rf, groups)
-    array = (C.c_uint32 * 5)(*groups)
-    try:
-        assert L.beamformer_hip_set_output_shard(0, 9, 13)
-        assert L.beamformer_hip_push_data_readi_sweep_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 5, array, 0, 0), bflib.last_error()
-        assert bflib.last_burst_info().route.burst_kernel == 1
-        part = bflib.get_last_frames(acq.bp, 5, shard_planes=13)
-    finally:
-        assert L.beamformer_hip_set_output_shard(0, 0, 0)
-    for k in range(5):
-        assert same_bits(part[k], np.ascontiguousarray(whole[k][9:22])), k
-
-
-def test_several_devices_refuse_a_sweep_and_frame_graphs_change_nothing(bflib, capfd):
-    L = bflib.library()
-    acq = sweep_case("g4a4", I.Cubic, False, False)
-    rf = noise_frames(acq, 5, 5800)
-    groups = [2, 0, 3, 3, 1]
-    array = (C.c_uint32 * 5)(*groups)
-    plain = sweep(bflib, acq, rf, groups)
-    try:
-        L.beamformer_hip_enable_frame_graphs(1)
-        for _ in range(2):
-            graphs = sweep(bflib, acq, rf, groups)
-        for k in range(5):
-            assert same_bits(plain[k], graphs[k]), k
-    finally:
-        L.beamformer_hip_enable_frame_graphs(0)
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        assert L.beamformer_push_simple_parameters(C.byref(acq.bp))
-        capfd.readouterr()
-        assert not L.beamformer_hip_push_data_readi_sweep_with_compute(rf.ctypes.data_as(C.c_void_p), rf[0].nbytes, 5, array, 0, 0)
-        assert bflib.last_error()[0] == E.InvalidAccess
-        assert "one device" in capfd.readouterr().err
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    again = sweep(bflib, acq, rf, groups)
-    for k in range(5):
-        assert same_bits(plain[k], again[k]), k
 
 
 def test_a_plain_burst_of_the_readi_block_is_what_it_was(bflib, oracle):

@@ -20,6 +20,7 @@ from tests import cases
 from tests import variants_cases as vc
 from tests.das_push import compare, same_bits, single_push
 from tests.parity import reference
+from tests.push_kinds import frame_id, single_push_of
 from tests.scaffold import automatic_path, run_ring_worker  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -43,12 +44,6 @@ def prepared(interp="linear", iq=True, cw=False, demodulate=False, which="block"
     variants = vc.candidates(acq.bp)
     refs = [(carrying(acq, v),) + tuple(reference(binding, carrying(acq, v))) for v in variants]
     return acq, variants, refs
-
-
-def frame_id(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
 
 
 def oracle_frames_differ(acq, refs):
@@ -290,21 +285,6 @@ def test_ids_layout_info_and_the_block_left_alone(bflib):
     assert not L.beamformer_hip_get_last_variants_info(C.byref(P.HipVariantsInfo())) and bflib.last_error()[0] == E.InvalidAccess
 
 
-def single_push_of(bflib, acq):
-    return bflib.beamform(acq.bp, acq.rf, acq.filters).copy()
-
-
-def test_device_resident_rf_equals_host_rf(bflib):
-    import torch
-    acq, variants, _ = prepared("linear", True, True)
-    host = bflib.beamform_variants(acq.bp, acq.rf, variants, acq.filters).copy()
-    dev = torch.from_numpy(np.ascontiguousarray(acq.rf).view(np.uint8).reshape(-1)).cuda()
-    torch.cuda.synchronize()
-    device = bflib.beamform_variants(acq.bp, acq.rf, variants, acq.filters, on_device_pointer=dev.data_ptr())
-    for k in range(3):
-        assert same_bits(host[k], device[k]), k
-
-
 def test_pair_counting_runs_per_variant(bflib):
     """f_number changes the count: the last variant's (half the f-number) is its single push's, and more than the first's"""
     L = bflib.library()
@@ -327,67 +307,3 @@ def test_pair_counting_runs_per_variant(bflib):
 def test_a_run_that_would_straddle_the_end_of_the_ring_starts_again_at_offset_0():
     """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/variants_wrap_worker.py"""
     run_ring_worker("variants_wrap_worker", 1 << 20, expect=("wrapped",), timeout=600)
-
-
-@pytest.mark.parametrize("route", ["variants kernel", "per-variant route"])
-def test_a_push_that_fails_leaves_a_tombstone_under_every_one_of_its_ids(route, bflib):
-    """das path flag 0x2000 fails a variants push at its DAS stage as it fails a views push: its ids are taken, its frames placed,
-    nothing launched there.  Every reader of "the newest frame" then fails; older good frames stay exportable; the next good push takes
-    the next ids and is served whole."""
-    L = bflib.library()
-    acq, variants, _ = prepared("cubic", False, False)
-    array = (P.HipDasVariant * 3)(*variants)
-    rf = np.ascontiguousarray(acq.rf)
-    ptr = rf.ctypes.data_as(C.c_void_p)
-    flag = PREFER if route == "variants kernel" else NO_KERNEL
-    L.beamformer_hip_set_das_path(flag)
-    good = bflib.beamform_variants(acq.bp, rf, variants, acq.filters).copy()
-    L.beamformer_hip_set_das_path(flag | P.HIP_DAS_PATH_FAIL_VIEWS_DAS)
-    older = single_push_of(bflib, acq)                    # the flag fails no single push
-    newest = frame_id(L).frame_id
-    assert not L.beamformer_hip_push_data_variants_with_compute(ptr, rf.nbytes, array, 3, 0, 0)
-    assert bflib.last_error()[0] == E.InvalidAccess
-    sentinel = np.full(4 * good[0].size * (2 if good.dtype == np.complex64 else 1) + 64, -7.0, np.float32)
-    sptr = sentinel.ctypes.data_as(C.c_void_p)
-    for count in (1, 3):                 # the newest frame is missing: an error, and nothing of the failed push is served
-        assert not L.beamformer_get_last_frames(sptr, sentinel.nbytes, count)
-        assert bflib.last_error()[0] == E.InvalidAccess and (sentinel == -7.0).all()
-    assert not L.beamformer_hip_get_last_frame_info(C.byref(P.HipFrameInfo()))
-    assert not L.beamformer_hip_get_last_variants_info(C.byref(P.HipVariantsInfo())) and bflib.last_error()[0] == E.InvalidAccess
-    assert not L.beamformer_hip_get_last_frame_timings(C.byref(P.HipFrameTimings()))
-    # the last K + 1 frames: the tombstones are skipped, the older good frame is still exported; the call reports the missing newest one
-    assert not L.beamformer_get_last_frames(sptr, sentinel.nbytes, 4)
-    assert np.array_equal(sentinel[: older.size].view(np.uint32), older.reshape(-1).view(np.uint32))
-    table = P.ComputeStatsTable()
-    assert L.beamformer_compute_timings(C.byref(table), -1)
-    for k in range(3):
-        assert not any(table.times[(newest + 1 + k) % 32][col] for col in range(int(table.shader_count)))
-    # the library is not wedged: the failed push consumed its ids, the next good one takes the next three and is served whole
-    L.beamformer_hip_set_das_path(flag)
-    again = bflib.beamform_variants(acq.bp, rf, variants, acq.filters)
-    info = bflib.last_variants_info()
-    assert info.first_frame_id == newest + 1 + 3 and info.variant_count == 3
-    assert info.route.kernel_variants == (3 if route == "variants kernel" else 0)
-    for k in range(3):
-        assert same_bits(again[k], good[k]), k
-
-
-def test_a_refused_push_queues_nothing(bflib, capfd):
-    L = bflib.library()
-    acq, variants, _ = prepared("linear", True, False)
-    good = bflib.beamform_variants(acq.bp, acq.rf, variants, acq.filters).copy()
-    newest = frame_id(L).frame_id
-    rf = np.ascontiguousarray(acq.rf)
-    bad = (P.HipDasVariant * 3)(*variants)
-    bad[1].speed_of_sound = float("nan")
-    assert not L.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, bad, 3, 0, 0)
-    assert bflib.last_error()[0] == E.InvalidAccess and "variant 1" in capfd.readouterr().err
-    try:
-        assert L.beamformer_hip_set_output_shard(0, 4, 6)
-        array = (P.HipDasVariant * 3)(*variants)
-        assert not L.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, array, 3, 0, 0)
-        assert bflib.last_error()[0] == E.InvalidAccess and "not sharded" in capfd.readouterr().err
-    finally:
-        assert L.beamformer_hip_set_output_shard(0, 0, 0)
-    assert frame_id(L).frame_id == newest and bflib.last_variants_info().first_frame_id == newest - 2
-    assert same_bits(bflib.get_last_frames(acq.bp, 3)[2], good[2])

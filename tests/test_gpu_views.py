@@ -15,8 +15,9 @@ import pytest
 
 from ogl_beamforming_amd import params as P
 from tests import cases
-from tests.das_push import compare, DISPATCH_CASES, KERNEL_CASES, kernel_views, mode_for, noise_frames, on_grid, prepared, same_bits, single_push
+from tests.das_push import compare, DISPATCH_CASES, KERNEL_CASES, mode_for, noise_frames, on_grid, prepared, same_bits, single_push
 from tests.parity import reference
+from tests.push_kinds import frame_id
 from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -157,12 +158,6 @@ def test_rows_that_end_inside_the_views(interp, bflib):
     assert not refs[2][1].any() and np.array_equal(frames[2], refs[2][1])          # past the ends of the rows: zeros, exactly
 
 
-def frame_id(L):
-    info = P.HipFrameInfo()
-    assert L.beamformer_hip_get_last_frame_info(C.byref(info))
-    return info
-
-
 def test_ids_layout_and_info(bflib):
     L = bflib.library()
     acq, rf, views, _ = prepared("rca_cubic_real")
@@ -231,19 +226,6 @@ def test_views_pushes_interleaved_with_single_pushes_and_a_burst_come_back_oldes
         at += size
 
 
-@pytest.mark.parametrize("name", ["config1_small", "forces"])
-def test_device_resident_rf_equals_host_rf(name, bflib):
-    import torch
-    acq, rf, views, _ = prepared(name, "kernel" if name == "config1_small" else "per_view")
-    bflib.library().beamformer_hip_set_das_path(PREFER)
-    host = bflib.beamform_views(acq.bp, rf, views, acq.filters)
-    dev = torch.from_numpy(np.ascontiguousarray(rf).view(np.uint8).reshape(-1)).cuda()
-    torch.cuda.synchronize()
-    device = bflib.beamform_views(acq.bp, rf, views, acq.filters, on_device_pointer=dev.data_ptr())
-    for k in range(len(views)):
-        assert same_bits(host[k], device[k]), k
-
-
 def test_pair_counting_runs_per_view(bflib):
     L = bflib.library()
     acq, rf, views, refs = prepared("rca_cubic_real")
@@ -260,116 +242,3 @@ def test_pair_counting_runs_per_view(bflib):
         assert pairs == int(t.das_pairs) > 0
     finally:
         L.beamformer_hip_enable_pair_counting(0)
-
-
-def test_several_devices_and_a_sharded_block_are_refused_and_a_refused_push_queues_nothing(bflib, capfd):
-    L = bflib.library()
-    acq, rf, views, _ = prepared("rca_vls_cw", "per_view")
-    array = (P.HipView * len(views))(*views)
-    ptr = rf.ctypes.data_as(C.c_void_p)
-    plain = bflib.beamform_views(acq.bp, rf, views, acq.filters)
-    newest = frame_id(L).frame_id
-    try:
-        assert L.beamformer_hip_set_output_shard(0, 4, 6)
-        assert not L.beamformer_hip_push_data_views_with_compute(ptr, rf.nbytes, array, len(views), 0)
-        assert bflib.last_error()[0] == E.InvalidAccess and "not sharded" in capfd.readouterr().err
-    finally:
-        assert L.beamformer_hip_set_output_shard(0, 0, 0)
-    # refused: no id consumed, the newest frame is still the last view of the good push
-    assert frame_id(L).frame_id == newest and same_bits(bflib.get_last_views(views)[-1], plain[-1])
-    try:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        assert L.beamformer_push_simple_parameters(C.byref(acq.bp))
-        capfd.readouterr()
-        assert not L.beamformer_hip_push_data_views_with_compute(ptr, rf.nbytes, array, len(views), 0)
-        assert bflib.last_error()[0] == E.InvalidAccess and "one device" in capfd.readouterr().err
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    again = bflib.beamform_views(acq.bp, rf, views, acq.filters)
-    for k in range(len(views)):
-        assert same_bits(plain[k], again[k]), k
-
-
-@pytest.mark.parametrize("route", ["views kernel", "per-view route"])
-def test_a_push_that_fails_leaves_a_tombstone_under_every_one_of_its_ids(route, bflib):
-    """das path flag 0x2000 fails a views push at its DAS stage: its ids are taken, its frames placed, nothing launched there -- what a
-    refused launch leaves.  Every reader of "the newest frame" then FAILS instead of serving an older record (or reporting success
-    with the caller's buffer unwritten); older good frames stay exportable; the flag touches no other push; the next good views push
-    takes the next ids and is served whole."""
-    L = bflib.library()
-    acq, rf, views, _ = prepared("rca_cubic_real")
-    K = len(views)
-    array = (P.HipView * K)(*views)
-    ptr = rf.ctypes.data_as(C.c_void_p)
-    flag = PREFER if route == "views kernel" else NO_KERNEL
-    L.beamformer_hip_set_das_path(flag)
-    good = bflib.beamform_views(acq.bp, rf, views, acq.filters)
-    before = bflib.last_views_info()
-    newest = frame_id(L).frame_id
-    assert newest == before.first_frame_id + K - 1
-    L.beamformer_hip_set_das_path(flag | P.HIP_DAS_PATH_FAIL_VIEWS_DAS)
-    # the flag fails views pushes only
-    assert same_bits(single_push(bflib, acq, rf), bflib.beamform(acq.bp, rf, acq.filters))
-    older = bflib.get_last_frame(acq.bp).copy()
-    newest = frame_id(L).frame_id
-    assert not L.beamformer_hip_push_data_views_with_compute(ptr, rf.nbytes, array, K, 0)
-    assert bflib.last_error()[0] == E.InvalidAccess
-    sentinel = np.full(sum((f.nbytes + 63) // 64 * 64 for f in good) // 4 + older.size + 64, -7.0, np.float32)
-    sptr = sentinel.ctypes.data_as(C.c_void_p)
-    for count in (1, K):                 # the newest frame is missing: an error, and nothing of the failed push is served
-        assert not L.beamformer_get_last_frames(sptr, sentinel.nbytes, count)
-        assert bflib.last_error()[0] == E.InvalidAccess and (sentinel == -7.0).all()
-    assert not L.beamformer_hip_get_last_frame_info(C.byref(P.HipFrameInfo()))
-    assert not L.beamformer_hip_get_last_views_info(C.byref(P.HipViewsInfo())) and bflib.last_error()[0] == E.InvalidAccess
-    assert not L.beamformer_hip_get_last_frame_timings(C.byref(P.HipFrameTimings()))
-    assert not L.beamformer_hip_frame_min_max((C.c_float * 2)())
-    assert (sentinel == -7.0).all()
-    # the last K + 1 frames: K tombstones are skipped, the older good frame is still exported; the call reports the missing newest one
-    assert not L.beamformer_get_last_frames(sptr, sentinel.nbytes, K + 1)
-    assert np.array_equal(sentinel[: older.size].view(np.uint32), older.reshape(-1).view(np.uint32))
-    assert (sentinel[(older.nbytes + 63) // 64 * 16:] == -7.0).all()
-    # every row of the failed push in the 32-frame table stays zero
-    table = P.ComputeStatsTable()
-    assert L.beamformer_compute_timings(C.byref(table), -1)
-    for k in range(K):
-        assert not any(table.times[(newest + 1 + k) % 32][col] for col in range(int(table.shader_count)))
-    # the library is not wedged: the failed push consumed its K ids, the next good one takes the next K and is served whole
-    L.beamformer_hip_set_das_path(flag)
-    again = bflib.beamform_views(acq.bp, rf, views, acq.filters)
-    info = bflib.last_views_info()
-    assert info.first_frame_id == newest + 1 + K and info.view_count == K
-    assert info.route.kernel_views == (K if route == "views kernel" else 0)
-    for k in range(K):
-        assert same_bits(again[k], good[k]), k
-
-
-def test_only_the_newest_multi_frame_push_serves_its_info(bflib):
-    """beamformer_hip_get_last_views_info serves a views push and beamformer_hip_get_last_burst_info a burst only while that push is the
-    newest one, complete: the other call, both calls after a single push, and both after a views push that failed are InvalidAccess"""
-    L = bflib.library()
-    acq = cases.make("config1_small")
-    rf = noise_frames(acq, 5, 5400)
-    views = kernel_views(acq)[:3]          # 1 x 1 x 1, 5 x 1 x 7, 33 x 1 x 17
-    assert all(int(np.prod(list(v.output_points))) <= 33 * 17 for v in views)
-
-    def served():
-        out = []
-        for call, info in ((L.beamformer_hip_get_last_views_info, P.HipViewsInfo()), (L.beamformer_hip_get_last_burst_info, P.HipBurstInfo())):
-            out.append(True if call(C.byref(info)) else bflib.last_error()[0])
-        return out
-
-    bflib.beamform_views(acq.bp, rf[0], views, acq.filters)
-    assert served() == [True, E.InvalidAccess]
-    bflib.beamform_burst(acq.bp, rf, acq.filters)
-    assert served() == [E.InvalidAccess, True]
-    bflib.beamform(acq.bp, rf[0], acq.filters)
-    assert served() == [E.InvalidAccess, E.InvalidAccess]
-    bflib.beamform_views(acq.bp, rf[1], views, acq.filters)
-    assert served() == [True, E.InvalidAccess]
-    L.beamformer_hip_set_das_path(P.HIP_DAS_PATH_FAIL_VIEWS_DAS)
-    array = (P.HipView * len(views))(*views)
-    assert not L.beamformer_hip_push_data_views_with_compute(rf[2].ctypes.data_as(C.c_void_p), rf[2].nbytes, array, len(views), 0)
-    assert bflib.last_error()[0] == E.InvalidAccess
-    assert served() == [E.InvalidAccess, E.InvalidAccess]

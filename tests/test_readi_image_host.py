@@ -1,4 +1,4 @@
-"""READI image pushes (beamformer_hip_push_data_readi_image_with_compute), everything that needs no device: the symbols, what
+"""READI image pushes (beamformer_hip_push_data_readi_image_with_compute), everything that needs no device: what
 beamformer_hip_describe_readi_image reports against beamformer_hip_describe_das of the derived FORCES block, the refusals -- which
 the push makes before it touches a device and before it takes an id, so they are asked of the push itself as well -- and the
 identity the push rests on, checked on the CPU oracle alone: the sum of the oracle's READI frames is the oracle's FORCES frame of the
@@ -15,8 +15,6 @@ from tests.das_push import noise_frames
 
 E = P.LibError
 I = P.InterpolationMode
-SYMBOLS = ["beamformer_hip_push_data_readi_image_with_compute", "beamformer_hip_push_device_data_readi_image_with_compute",
-           "beamformer_hip_describe_readi_image", "beamformer_hip_get_last_readi_image_info"]
 
 # (geometry, interpolation, kind, acquisition kind, sparse elements, group list -- None: a permutation of 0 .. G - 1)
 DESCRIBED = [("g4a4", I.Linear, "real", R.K.FORCES, None, None), ("g2a8", I.Cubic, "iq", R.K.FORCES, None, None),
@@ -56,14 +54,6 @@ def push(bflib, acq, n, groups=None):
     rf = np.ascontiguousarray(np.broadcast_to(acq.rf, (max(n, 1),) + acq.rf.shape))
     array = None if groups is None else (C.c_uint32 * len(groups))(*groups)
     bflib._check(lib.beamformer_hip_push_data_readi_image_with_compute(rf.ctypes.data_as(C.c_void_p), acq.rf.nbytes, n, array, 0, 0))
-
-
-def test_the_symbols_and_the_structs(L, bflib):
-    for name in SYMBOLS:
-        assert hasattr(L, name), name
-        assert name in bflib.exported_symbols()
-    assert C.sizeof(P.HipReadiImageDescription) == 20 + 160
-    assert C.sizeof(P.HipReadiImageInfo) == 180 + 12 + 4 * 24 + 4 * 24 + 4
 
 
 @pytest.mark.parametrize("geometry,interp,kind,acquisition_kind,sparse,groups", DESCRIBED, ids=DESCRIBED_IDS)
@@ -147,21 +137,6 @@ def test_more_transmits_than_the_emission_limit(L, bflib, capfd):
     # at the limit it is taken: G = 16, A = 16
     ok = R._forces("readi_image_g16a16", 16, 16, (16, 1, 16), "real", I.Linear, False, 3998)
     assert bflib.describe_readi_image(ok.bp, 4).transmit_count == 256
-
-
-def test_a_frame_larger_than_the_ring_and_a_wrong_size(L, bflib):
-    acq = R.image_case("g4a4", I.Linear, "real")
-    before = frames_taken(bflib)
-    lib = bflib.library()
-    assert lib.beamformer_push_simple_parameters(C.byref(acq.bp))
-    rf = np.ascontiguousarray(np.broadcast_to(acq.rf, (2,) + acq.rf.shape))
-    assert not lib.beamformer_hip_push_data_readi_image_with_compute(rf.ctypes.data_as(C.c_void_p), acq.rf.nbytes - 4, 2, None, 0, 0)
-    assert bflib.last_error()[0] == E.DataSizeMismatch
-    assert not lib.beamformer_hip_push_data_readi_image_with_compute(None, acq.rf.nbytes, 2, None, 0, 0)
-    assert bflib.last_error()[0] == E.BufferOverflow
-    assert not lib.beamformer_hip_push_data_readi_image_with_compute(rf.ctypes.data_as(C.c_void_p), acq.rf.nbytes, 2, None, 99, 0)
-    assert bflib.last_error()[0] == E.InvalidImagePlane
-    assert frames_taken(bflib) == before
 
 
 # ---- the identity, on the oracle alone

@@ -1,4 +1,4 @@
-"""READI sweeps (beamformer_hip_push_data_readi_sweep_with_compute), everything that needs no device: the symbols, the route
+"""READI sweeps (beamformer_hip_push_data_readi_sweep_with_compute), everything that needs no device: the route
 beamformer_hip_describe_readi_sweep reports and its reason, how the group list is resolved, and the refusals -- which the push makes
 before it touches a device, so they are asked of the push itself as well."""
 import ctypes as C
@@ -37,12 +37,6 @@ def push(bflib, acq, n, groups=None):
     rf = np.ascontiguousarray(np.broadcast_to(acq.rf, (max(n, 1),) + acq.rf.shape))
     array = None if groups is None else (C.c_uint32 * len(groups))(*groups)
     bflib._check(lib.beamformer_hip_push_data_readi_sweep_with_compute(rf.ctypes.data_as(C.c_void_p), acq.rf.nbytes, n, array, 0, 0))
-
-
-def test_the_symbols_exist(L, bflib):
-    for name in SYMBOLS:
-        assert hasattr(L, name), name
-        assert name in bflib.exported_symbols()
 
 
 def test_the_kernel_takes_sweeps_from_the_threshold_on(L, bflib):

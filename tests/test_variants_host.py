@@ -1,63 +1,18 @@
-"""Variants pushes (beamformer_hip_push_data_variants_with_compute) on the CPU: the four entry points exist and are bound, the variants
-kernel is in the library with its twelve instantiations, beamformer_hip_describe_variants (no device needed) names the route the rules
-of csrc/das_select.cpp give -- per variant the decision of a block pushed with those values --, and a malformed push is refused before
-any device is touched."""
+"""Variants pushes (beamformer_hip_push_data_variants_with_compute) on the CPU: beamformer_hip_describe_variants (no device needed)
+names the route the rules of csrc/das_select.cpp give -- per variant the decision of a block pushed with those values.  What a variants
+push shares with every other multi-frame push -- its symbols, its kernel's instantiations, its refusals -- is asked of all kinds in
+tests/test_push_contract_host.py."""
 import ctypes as C
-import math
-import os
-import subprocess
-import sys
 
-import numpy as np
 import pytest
 
 from ogl_beamforming_amd import lib
 from ogl_beamforming_amd import params as P
 from tests import cases
 from tests import variants_cases as vc
+from tests.scaffold import automatic_path_on_the_host  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E = P.LibError
-SYMBOLS = ("beamformer_hip_push_data_variants_with_compute", "beamformer_hip_push_device_data_variants_with_compute",
-           "beamformer_hip_describe_variants", "beamformer_hip_get_last_variants_info")
 PREFER, NO_KERNEL = vc.PREFER, vc.NO_KERNEL
-
-
-@pytest.fixture(autouse=True)
-def automatic_path():
-    lib.library().beamformer_hip_set_das_path(0)
-    yield
-    lib.library().beamformer_hip_set_das_path(0)
-
-
-def test_the_four_variants_symbols_are_declared_exported_and_bound():
-    header = open(os.path.join(ROOT, "include", "ogl_beamformer_hip.h")).read()
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIBRARY_PATH], capture_output=True, text=True, check=True)
-    exported = {line.split()[-1] for line in nm.stdout.splitlines() if " T " in line}
-    for name in SYMBOLS:
-        assert f"{name}(" in header, name
-        assert name in exported, name
-        assert name in lib.exported_symbols(), name
-    assert "#define BEAMFORMER_HIP_MAX_VARIANTS 64u" in header and P.HIP_MAX_VARIANTS == 64
-    assert "BeamformerHipDasPath_NoVariantsKernel = 0x4000" in header and NO_KERNEL == 0x4000
-    assert "BeamformerHipDasPath_PreferVariantsKernel = 0x8000" in header and PREFER == 0x8000
-    # the structs the binding mirrors: three floats; 6 words + 64 paths + 64 flags + the reason; the description + 3 words + 24 kinds
-    # + 24 times + the total + the host time
-    assert C.sizeof(P.HipDasVariant) == 12
-    assert C.sizeof(P.HipVariantsDescription) == 24 + 64 + 64 + 160
-    assert C.sizeof(P.HipVariantsInfo) == 312 + 12 + 4 * 24 + 4 * 24 + 4 + 4
-
-
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
-def test_the_variants_kernel_has_twelve_instantiations_without_spills():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    kernels = [k for k in kernel_resources.kernels_of(lib.LIBRARY_PATH) if "das_variants_kernel" in k["demangled"]]
-    assert len({k["demangled"] for k in kernels}) == 12, sorted(k["demangled"] for k in kernels)
-    for k in kernels:
-        assert not k["vgpr_spill_count"] and not k["private_segment_fixed_size"], k["demangled"]      # 0 vector spills, 0 scratch
-        assert k["vgpr_count"] <= 128, (k["demangled"], k["vgpr_count"])
-        assert not k["group_segment_fixed_size"], k["demangled"]                 # no LDS
 
 
 def test_an_rca_small_frame_takes_the_variants_kernel_in_one_launch():
@@ -181,82 +136,3 @@ def test_the_derived_time_offset_is_the_planners():
         assert L.beamformer_hip_describe_plan(0, C.byref(plan))
         resolved.append(float(plan.das_time_offset))
     assert resolved[0] != float(acq.bp.time_offset) and abs((resolved[1] - resolved[0]) - 0.3e-6) < 1e-9
-
-
-def push_parameters(acq):
-    L = lib.library()
-    for s, fp in enumerate(acq.filters):
-        assert L.beamformer_create_filter(C.byref(fp), s, 0)
-    assert L.beamformer_push_simple_parameters(C.byref(acq.bp)), lib.last_error()
-    return L
-
-
-def test_malformed_pushes_are_refused_before_a_device_is_touched(capfd):
-    acq = vc.block("linear", iq=True)
-    L = push_parameters(acq)
-    rf = np.ascontiguousarray(acq.rf)
-    ptr, size = rf.ctypes.data_as(C.c_void_p), rf.nbytes
-    good = vc.candidates(acq.bp)
-    variants = (P.HipDasVariant * 3)(*good)
-    push = L.beamformer_hip_push_data_variants_with_compute
-    description = P.HipVariantsDescription()
-    assert not push(ptr, size, variants, 0, 0, 0) and lib.last_error()[0] == E.BufferOverflow
-    many = (P.HipDasVariant * (P.HIP_MAX_VARIANTS + 1))(*([good[0]] * (P.HIP_MAX_VARIANTS + 1)))
-    assert not push(ptr, size, many, P.HIP_MAX_VARIANTS + 1, 0, 0) and lib.last_error()[0] == E.BufferOverflow
-    assert not L.beamformer_hip_describe_variants(0, many, P.HIP_MAX_VARIANTS + 1, C.byref(description)) and lib.last_error()[0] == E.BufferOverflow
-    assert not L.beamformer_hip_describe_variants(0, variants, 0, C.byref(description)) and lib.last_error()[0] == E.BufferOverflow
-    assert not push(ptr, size, None, 3, 0, 0) and lib.last_error()[0] == E.InvalidAccess
-    # the single push's checks, with its error kinds (lib/ogl_beamformer_lib.c:503-511)
-    assert not push(ptr, size - 2, variants, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
-    assert not push(ptr, size + 2, variants, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
-    assert not push(ptr, size, variants, 3, 7, 0) and lib.last_error()[0] == E.InvalidImagePlane
-    assert not push(ptr, size, variants, 3, 0, 5) and lib.last_error()[0] == E.ParameterBlockUnallocated
-    assert not push(None, size, variants, 3, 0, 0) and lib.last_error()[0] == E.BufferOverflow
-    assert not L.beamformer_hip_push_device_data_variants_with_compute(ptr, size - 2, variants, 3, 0, 0) and lib.last_error()[0] == E.DataSizeMismatch
-    # a field that is not finite, a speed of sound that is not above zero: InvalidAccess, with a line on stderr
-    capfd.readouterr()
-    for field, value in (("speed_of_sound", math.nan), ("speed_of_sound", math.inf), ("speed_of_sound", 0.0), ("speed_of_sound", -1540.0),
-                         ("time_offset", math.nan), ("time_offset", -math.inf), ("f_number", math.nan), ("f_number", math.inf)):
-        bad = (P.HipDasVariant * 3)(*good)
-        setattr(bad[2], field, value)
-        assert not push(ptr, size, bad, 3, 0, 0) and lib.last_error()[0] == E.InvalidAccess, (field, value)
-        assert "variant 2" in capfd.readouterr().err, (field, value)
-        assert not L.beamformer_hip_describe_variants(0, bad, 3, C.byref(description)) and lib.last_error()[0] == E.InvalidAccess
-        capfd.readouterr()
-    # an output shard on the block
-    try:
-        assert L.beamformer_hip_set_output_shard(0, 0, 1)
-        assert not push(ptr, size, variants, 3, 0, 0) and lib.last_error()[0] == E.InvalidAccess
-        assert "not sharded" in capfd.readouterr().err
-    finally:
-        assert L.beamformer_hip_set_output_shard(0, 0, 0)
-
-
-def test_several_devices_are_refused_before_a_device_is_touched(capfd):
-    acq = vc.block("linear", iq=True)
-    L = push_parameters(acq)
-    rf = np.ascontiguousarray(acq.rf)
-    variants = (P.HipDasVariant * 3)(*vc.candidates(acq.bp))
-    try:
-        L.beamformer_hip_shutdown()          # (where a device is in use, the set of devices is fixed until the library lets go of it)
-        assert L.beamformer_hip_set_devices((C.c_int32 * 2)(0, 0), 2)
-        capfd.readouterr()
-        assert not L.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, variants, 3, 0, 0)
-        assert lib.last_error()[0] == E.InvalidAccess and "one device" in capfd.readouterr().err
-    finally:
-        L.beamformer_hip_shutdown()
-        assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-
-
-def test_frames_larger_than_the_frame_ring_are_refused_whole():
-    """4096 x 4096 complex voxels are 128 MiB a frame: one fits the default 4 GiB ring, 64 of them are twice its size"""
-    acq = vc.block("linear", iq=True)
-    bp = type(acq.bp).from_buffer_copy(acq.bp)
-    bp.output_points[:3] = [4096, 1, 4096]
-    L = lib.library()
-    assert L.beamformer_push_simple_parameters(C.byref(bp)), lib.last_error()
-    rf = np.ascontiguousarray(acq.rf)
-    one = lib.variant_of(bp)
-    variants = (P.HipDasVariant * 64)(*([one] * 64))
-    assert not L.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, variants, 64, 0, 0)
-    assert lib.last_error()[0] == E.FrameSizeOverflow
