@@ -10,6 +10,7 @@ from ogl_beamforming_amd import configs as cfg
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import autocorr_ref
+from tests import block_filter_ref
 from tests import ensemble_ref
 from tests import frame_metrics_ref
 from tests import frame_peaks_ref
@@ -276,6 +277,23 @@ def check_mix(which, frames, ids, W, tag=0, what=""):
     assert bf.library().beamformer_hip_get_last_frame_timings(C.byref(t)) and t.stage_count == 0 and t.das_voxels == 0
     # a source frame is still served by its id
     assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))
+    return out, first
+
+
+def check_mix_field(which, frames, ids, W, lattice, tag=0, what=""):
+    """mix the len(frames) newest frames under the field W (Nz, Ny, Nx, M, K) on `lattice` (nodes, first, step) and check the outputs
+    against the float64 reference within its bound, and their ids; returns (outputs, first id)"""
+    M = W.shape[3]
+    first, ms = bf.mix_field_last_frames(len(frames), W, lattice["first"], lattice["step"], tag=tag)
+    out = bf.get_last_frames(block(which).bp, M).copy()
+    expected, bound = block_filter_ref.mix_field(list(frames), W, lattice["first"], lattice["step"])
+    over = np.abs(out.astype(np.float64) - expected) if not np.iscomplexobj(frames) else \
+        np.maximum(np.abs(out.real - expected.real), np.abs(out.imag - expected.imag))
+    print(f"  {what}: K {len(frames)} -> M {M}, nodes {lattice['nodes']}: worst error {float((over / np.maximum(bound, 1e-300)).max()):.3f} of its bound, {ms * 1e3:.1f} us")
+    assert out.shape == (M,) + frames.shape[1:] and out.dtype == frames.dtype and ms > 0
+    assert (over <= bound).all()
+    assert first == ids[-1] + 1 and int(newest_info(bf.library()).frame_id) == first + M - 1
+    assert np.array_equal(bf.copy_frame(ids[0]).view(np.uint32), frames[0].view(np.uint32))       # a source is still served by its id
     return out, first
 
 

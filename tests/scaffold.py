@@ -47,11 +47,11 @@ def two_contexts_on_device_0(bflib, acq):
         assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
 
 
-def run_ring_worker(module, ring_bytes, expect, timeout=300):
-    """python -m tests.<module> in a process of its own with a frame ring of `ring_bytes` (the ring is sized once per process): it has to
-    end well and say every word of `expect`"""
+def run_ring_worker(module, ring_bytes, expect, timeout=300, args=()):
+    """python -m tests.<module> <args> in a process of its own with a frame ring of `ring_bytes` (the ring is sized once per process): it
+    has to end well and say every word of `expect`"""
     env = dict(os.environ, BEAMFORMER_HIP_FRAME_RING_BYTES=str(ring_bytes))
-    run = subprocess.run([sys.executable, "-m", "tests." + module], cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+    run = subprocess.run([sys.executable, "-m", "tests." + module, *args], cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     print(run.stdout)
     assert run.returncode == 0, run.stdout + run.stderr
     assert all(word in run.stdout for word in expect), run.stdout

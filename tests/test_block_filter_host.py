@@ -222,16 +222,11 @@ def test_every_refusal_of_the_device_calls_that_needs_no_device():
         assert lib.last_error()[0] == kind
         assert (bytes(grams), bytes(infos)) == untouched and ms.value == -1.0
 
-    for count in (0, MAX + 1):
-        gram_refused(E.BufferOverflow, count=count)
-    for region_count in (0, P.HIP_MAX_GRAM_BOXES + 1):
-        gram_refused(E.BufferOverflow, region_count=region_count)
+    # (the count, the number of boxes, the outputs and the good call without a device, of both calls: tests/test_frame_ops_contract_host.py)
     gram_refused(E.BufferOverflow, count=65, region_count=1024)          # 1024 x 65 x 65 entries: more than 2^22 (64 x 64 is exactly the cap)
-    gram_refused(E.BufferOverflow, count=0, out=None)                    # BufferOverflow is decided first, whatever else is wrong
     gram_refused(E.BufferOverflow, region_count=0, regions=None)
     gram_refused(E.InvalidAccess, out=None)
     gram_refused(E.InvalidAccess, regions=None)
-    gram_refused(E.InvalidAccess)                                        # every argument good: no device yet, so there is no frame
     gram_refused(E.InvalidAccess, count=64, region_count=1024, regions=(P.HipFrameRegion * 1024)())     # at the cap: past the limits, no device
     assert not L.beamformer_hip_gram_boxes_last_frames(2, boxes, 2, grams, None, None) and lib.last_error()[0] == E.InvalidAccess
     assert bytes(grams) == untouched[0]
@@ -246,7 +241,6 @@ def test_every_refusal_of_the_device_calls_that_needs_no_device():
         assert first.value == 77 and ms.value == -1.0
 
     for n in (0, MAX + 1):
-        mix_refused(E.BufferOverflow, count=n)
         mix_refused(E.BufferOverflow, out_count=n)
     mix_refused(E.BufferOverflow, count=0, weights=None)
     mix_refused(E.BufferOverflow, out_count=0, nodes=None)
@@ -269,14 +263,7 @@ def test_every_refusal_of_the_device_calls_that_needs_no_device():
             w = (C.c_float * 16)(*good)
             w[at] = bad
             mix_refused(E.InvalidAccess, weights=w)
-    mix_refused(E.InvalidAccess)                                # every argument good: no device yet
     mix_refused(E.InvalidAccess, nodes=U3(1, 1, 1), node_step=U3(0, 0, 0), weights=(C.c_float * 8)(*good[:8]))   # one node: the step is not read
-    assert not L.beamformer_hip_mix_field_last_frames(2, good, lattice["nodes"], lattice["node_first"], lattice["node_step"], 2, 0, None, None)
-    assert lib.last_error()[0] == E.InvalidAccess
-    with pytest.raises(lib.BeamformerError):
-        lib.gram_boxes_last_frames(2, [boxes[0], boxes[1]])
-    with pytest.raises(lib.BeamformerError):
-        lib.mix_field_last_frames(2, np.eye(2).reshape(1, 1, 1, 2, 2), (0, 0, 0), (1, 1, 1))
     with pytest.raises(ValueError):
         lib.mix_field_last_frames(2, np.eye(2), (0, 0, 0), (1, 1, 1))
     # the two hooks of these calls are the library's, through the one entry point

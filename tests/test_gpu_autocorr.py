@@ -11,15 +11,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import autocorr_ref as ref
 from tests import frame_peaks_ref
-from tests import variants_cases as vc
-from tests.frame_info import newest_id, newest_info
+from tests.frame_info import newest_info
 from tests.ring_frames import (block, burst_info_unchanged, AUTOCORR_CASES as CASES, check_autocorr, check_peaks as check_call, ensemble, finite_of,
-                               loop_case, rf_frames, share_of_bound, weights)
-from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
+                               loop_case, share_of_bound, weights)
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
@@ -148,75 +146,3 @@ def test_the_power_doppler_loop(bflib):
     assert (over <= identity_bound[0]).all()
     of_the_sum = frame_peaks_ref.peaks(power.astype(np.float32).astype(np.complex64), thresholds[0], None, None, cap=64)
     assert of_the_sum["found"] == found[0]["found"] and np.array_equal(of_the_sum["index"], found[0]["index"])
-
-
-# ---- refusals that need a device ----
-
-def refused(L, K, W, rows, lags, kind):
-    """the call refuses with this error kind, writes nothing and queues nothing: the newest id stays, and the frame pushed next lies
-    where it would have lain (the ring's next offset is unchanged)"""
-    first, ms = C.c_uint32(77), C.c_float(-1.0)
-    newest = newest_id(L)
-    before = bytes(newest_info(L)) if newest is not None and L.beamformer_hip_get_device_count() == 1 else None
-    pointer = None if W is None else W.ctypes.data_as(C.POINTER(C.c_float))
-    assert not L.beamformer_hip_autocorrelate_last_frames(K, pointer, rows, lags, 0, C.byref(first), C.byref(ms))
-    assert bf.last_error()[0] == kind and first.value == 77 and ms.value == -1.0
-    assert newest_id(L) == newest
-    if before is not None:
-        assert bytes(newest_info(L)) == before
-        old = newest_info(L)
-        acq = block("plane")
-        bf.beamform(acq.bp, rf_frames("plane", 1)[0], acq.filters)
-        new = newest_info(L)
-        assert int(new.frame_id) == int(old.frame_id) + 1
-        assert int(new.device_pointer) == int(old.device_pointer) + (int(old.size_bytes) + 63) // 64 * 64
-
-
-def test_refusals(bflib):
-    L = bflib.library()
-    a, v, r = block("plane"), block("volume"), block("real")
-    eye = np.eye(2, dtype=np.complex64)
-    # frames of two grids
-    ensemble("plane", 2)
-    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
-    refused(L, 2, eye, 2, 2, E.DataSizeMismatch)
-    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
-    refused(L, 2, None, 2, 1, E.DataSizeMismatch)
-    # frames of two kinds on one grid (the push inside refused() left a complex plane behind)
-    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
-    refused(L, 2, eye, 2, 1, E.DataSizeMismatch)
-    # more lags than rows, more than BEAMFORMER_HIP_MAX_LAGS, none
-    frames, ids = ensemble("plane", 3)
-    refused(L, 3, weights(2, 3, 8700), 2, 3, E.InvalidAccess)
-    frames, ids = ensemble("plane", 3)
-    refused(L, 3, None, 3, 4, E.InvalidAccess)
-    frames, ids = ensemble("plane", 5)
-    refused(L, 5, None, 5, P.HIP_MAX_LAGS + 1, E.InvalidAccess)
-    frames, ids = ensemble("plane", 3)
-    refused(L, 3, None, 3, 0, E.InvalidAccess)
-    # the identity form with rows != count
-    frames, ids = ensemble("plane", 3)
-    refused(L, 3, None, 2, 1, E.InvalidAccess)
-    # more frames than are there: a fresh context with two
-    L.beamformer_hip_shutdown()
-    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames, ids = ensemble("plane", 2)
-    assert ids == [0, 1]
-    refused(L, 3, None, 3, 1, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_autocorr("plane", frames, ids, None, 2, what="two frames")
-
-
-def test_several_devices_are_refused(bflib):
-    L = bflib.library()
-    acq = vc.separable_volume()
-    with two_contexts_on_device_0(bflib, acq):
-        refused(L, 1, None, 1, 1, E.InvalidAccess)
-        refused(L, 1, np.ones((1, 1), np.complex64), 1, 1, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_autocorr("plane", frames, ids, None, 2, what="one device again")
-
-
-def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
-    """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/autocorr_wrap_worker.py"""
-    run_ring_worker("autocorr_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

@@ -18,15 +18,13 @@ from ogl_beamforming_amd import params as P
 from tests import block_filter_ref as ref
 from tests import ensemble_ref
 from tests import planted
-from tests import variants_cases as vc
-from tests.frame_info import newest_id, newest_info
-from tests.ring_frames import block, BOXES, check_peaks as check_call, ensemble, GRIDS, region_of, rf_frames, same_as_singles, singles, weights
-from tests.scaffold import automatic_path, two_contexts_on_device_0  # noqa: F401
+from tests.frame_info import newest_info
+from tests.frame_ops_table import node_weights
+from tests.ring_frames import block, BOXES, check_peaks as check_call, ensemble, GRIDS, region_of, same_as_singles, singles, weights
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
 D = P.DataKind
-U3 = C.c_uint32 * 3
 
 
 @pytest.fixture(autouse=True)
@@ -121,42 +119,6 @@ def test_gram_boxes_over_the_nan_block(bflib):
     same_as_singles(cut, cut_infos, want, "nan, a box a batch")
 
 
-def gram_boxes_refused(L, K, regions, kind):
-    count = len(regions)
-    grams = np.full((max(1, count), K, K), -7.0 - 7.0j, np.complex128)
-    untouched = grams.tobytes()
-    infos = (P.HipEnsembleInfo * max(1, count))()
-    ms = C.c_float(-1.0)
-    newest = newest_id(L)
-    array = (P.HipFrameRegion * max(1, count))(*regions)
-    assert not L.beamformer_hip_gram_boxes_last_frames(K, array, count, grams.ctypes.data_as(C.POINTER(C.c_double)), infos, C.byref(ms))
-    assert bf.last_error()[0] == kind and grams.tobytes() == untouched and not bytes(infos).strip(b"\0") and ms.value == -1.0
-    assert newest_id(L) == newest
-
-
-def test_gram_boxes_refusals_leave_the_outputs_unwritten(bflib):
-    L = bflib.library()
-    frames, ids = ensemble("plane", 2)
-    good = bflib.frame_region((1, 0, 1), (5, 1, 3))
-    # one bad box among good ones: outside the frames, a zero extent, a first that wraps
-    for bad in (((0, 0, 0), (34, 1, 7)), ((1, 0, 0), (33, 1, 7)), ((0, 0, 7), (1, 1, 1)), ((0, 0, 0), (33, 0, 7)), ((0xFFFFFFFF, 0, 0), (2, 1, 1))):
-        gram_boxes_refused(L, 2, [good, bflib.frame_region(*bad), good], E.InvalidAccess)
-        gram_boxes_refused(L, 2, [good, good, bflib.frame_region(*bad)], E.InvalidAccess)
-    gram_boxes_refused(L, 2, [], E.BufferOverflow)
-    gram_boxes_refused(L, 2, [good] * 1025, E.BufferOverflow)
-    # frames of two grids, of two kinds
-    b, r = block("square"), block("real")
-    bflib.beamform(b.bp, rf_frames("square", 1)[0], b.filters)
-    gram_boxes_refused(L, 2, [good, good], E.DataSizeMismatch)
-    ensemble("plane", 1)
-    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
-    gram_boxes_refused(L, 2, [good], E.DataSizeMismatch)
-    # and the call still works
-    frames, ids = ensemble("plane", 2)
-    got, infos, _ = bflib.gram_boxes_last_frames(2, [good])
-    same_as_singles(got, infos, singles(2, [((1, 0, 1), (5, 1, 3))]), "after the refusals")
-
-
 # ---- field mix ----
 
 LATTICES = {
@@ -167,11 +129,6 @@ LATTICES = {
     "flat":    dict(nodes=(2, 2, 1), first=(3, 0, 0), step=(11, 1, 1)),                # two nodes along y on a grid of one point along y
     "nan":     dict(nodes=(2, 1, 2), first=(5, 0, 7), step=(9, 1, 20)),
 }
-
-
-def node_weights(lattice, M, K, seed, real=False):
-    nx, ny, nz = lattice["nodes"]
-    return np.stack([weights(M, K, seed + n, real) for n in range(nx * ny * nz)]).reshape(nz, ny, nx, M, K)
 
 
 def corners_by_the_plain_mix(which, K, W):
@@ -308,74 +265,6 @@ def test_field_mix_over_the_nan_block(bflib):
     frames, _ = ensemble("nan", K)
     bad = np.isnan(frames).any(axis=0)
     assert np.isnan(out.real[:, bad]).all() and np.isnan(out.imag[:, bad]).all() and np.isfinite(out.real[:, ~bad]).all()
-
-
-def mix_field_refused(L, K, W, lattice, kind):
-    """the call refuses with this kind, writes nothing and queues nothing: the newest id stays, and the frame pushed next lies where it
-    would have lain (the ring's next offset is unchanged)"""
-    first, ms = C.c_uint32(77), C.c_float(-1.0)
-    newest = newest_id(L)
-    before = bytes(newest_info(L)) if newest is not None and L.beamformer_hip_get_device_count() == 1 else None
-    W = np.ascontiguousarray(W, np.complex64)
-    assert not L.beamformer_hip_mix_field_last_frames(K, W.ctypes.data_as(C.POINTER(C.c_float)), U3(*lattice["nodes"]), U3(*lattice["first"]),
-                                                      U3(*lattice["step"]), W.shape[3], 0, C.byref(first), C.byref(ms))
-    assert bf.last_error()[0] == kind and first.value == 77 and ms.value == -1.0
-    assert newest_id(L) == newest
-    if before is not None:
-        assert bytes(newest_info(L)) == before
-        old = newest_info(L)
-        acq = block("plane")
-        bf.beamform(acq.bp, rf_frames("plane", 1)[0], acq.filters)
-        new = newest_info(L)
-        assert int(new.frame_id) == int(old.frame_id) + 1
-        assert int(new.device_pointer) == int(old.device_pointer) + (int(old.size_bytes) + 63) // 64 * 64
-
-
-def test_field_mix_refusals_change_nothing(bflib):
-    L = bflib.library()
-    lattice = LATTICES["beyond"]
-    v, r = block("volume"), block("real")
-    W = node_weights(lattice, 2, 2, 8600)
-    # frames of two grids, of two kinds on one grid (the push inside mix_field_refused() left a complex plane behind)
-    ensemble("plane", 2)
-    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
-    mix_field_refused(L, 2, W, lattice, E.DataSizeMismatch)
-    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
-    mix_field_refused(L, 2, W, lattice, E.DataSizeMismatch)
-    # a nonzero imaginary weight on real frames, at the last node's last row; without it the call runs
-    ensemble("real", 3)
-    Wr = node_weights(lattice, 2, 3, 8601, real=True)
-    bad = Wr.copy()
-    bad[-1, -1, -1, -1, -1] += 1e-30j
-    mix_field_refused(L, 3, bad, lattice, E.InvalidAccess)
-    ensemble("real", 3)
-    first, _ = bflib.mix_field_last_frames(3, Wr, lattice["first"], lattice["step"])
-    assert int(newest_info(L).frame_id) == first + 1
-    # what needs no frames is refused with frames present as without: the lattice, the weights
-    ensemble("plane", 2)
-    mix_field_refused(L, 2, W, dict(lattice, step=(0, 1, 9)), E.InvalidAccess)
-    mix_field_refused(L, 2, W, dict(lattice, nodes=(0, 1, 2)), E.BufferOverflow)
-    nan = W.copy()
-    nan[0, 0, 1, 1, 0] = np.nan
-    mix_field_refused(L, 2, nan, lattice, E.InvalidAccess)
-    # more frames than are there: a fresh context with two
-    L.beamformer_hip_shutdown()
-    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames, ids = ensemble("plane", 2)
-    assert ids == [0, 1]
-    mix_field_refused(L, 3, node_weights(lattice, 2, 3, 8602), lattice, E.InvalidAccess)
-    gram_boxes_refused(L, 4, [bflib.frame_region((0, 0, 0), (1, 1, 1))], E.InvalidAccess)
-
-
-def test_several_devices_are_refused(bflib):
-    L = bflib.library()
-    acq = vc.separable_volume()
-    lattice = LATTICES["one"]
-    with two_contexts_on_device_0(bflib, acq):
-        mix_field_refused(L, 1, np.ones((1, 1, 1, 1, 1), np.complex64), lattice, E.InvalidAccess)
-        gram_boxes_refused(L, 1, [bflib.frame_region((0, 0, 0), (1, 1, 1))], E.InvalidAccess)
-    out, _, _, _ = field_mix("plane", 2, node_weights(lattice, 1, 2, 8700), lattice)
-    assert np.isfinite(out.view(np.float32)).all()
 
 
 # ---- the loop on planted frames ----

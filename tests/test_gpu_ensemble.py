@@ -13,14 +13,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import ensemble_ref as ref
-from tests import variants_cases as vc
-from tests.frame_info import newest_id, newest_info
-from tests.ring_frames import (block, BOXES, check_peaks as check_call, check_gram, check_mix, ensemble, GRIDS, loop_case, LOOP_POINTS, metrics_block,
-                               region_of, rf_frames, weights)
-from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
+from tests.frame_info import newest_info
+from tests.ring_frames import BOXES, check_peaks as check_call, check_gram, check_mix, ensemble, GRIDS, loop_case, LOOP_POINTS, region_of, weights
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E = P.LibError
@@ -147,71 +144,3 @@ def test_the_clutter_filter_loop(bflib):
     patches = bflib.beamform_burst_views(acq.bp, rf, views, acq.filters)
     assert len(patches) == len(few) and all(len(p) == 8 and p[0].shape == (17, 1, 17) for p in patches)
     assert int(newest_info(bflib.library()).frame_id) - int(bflib.last_burst_views_info().first_frame_id) + 1 == 8 * len(few)
-
-
-# ---- refusals that need a device ----
-
-
-def refused_both(L, K, kind, region=None):
-    """both device calls refuse `K` frames with this error kind, write nothing and queue nothing (a region: the Gram call alone)"""
-    gram = np.full((K, K), -7.0 - 7.0j, np.complex128)
-    untouched = gram.tobytes()
-    info = P.HipEnsembleInfo()
-    newest = newest_id(L)
-    assert not L.beamformer_hip_gram_last_frames(K, None if region is None else C.byref(region), gram.ctypes.data_as(C.POINTER(C.c_double)), C.byref(info), None)
-    assert bf.last_error()[0] == kind and gram.tobytes() == untouched and not bytes(info).strip(b"\0")
-    if region is None:
-        first = C.c_uint32(77)
-        W = np.eye(K, dtype=np.complex64)
-        assert not L.beamformer_hip_mix_last_frames(K, W.ctypes.data_as(C.POINTER(C.c_float)), K, 0, C.byref(first), None)
-        assert bf.last_error()[0] == kind and first.value == 77
-    assert newest_id(L) == newest
-
-
-def test_refusals(bflib):
-    L = bflib.library()
-    # more frames asked for than were ever queued: a fresh context with two frames
-    L.beamformer_hip_shutdown()
-    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames, ids = ensemble("plane", 2)
-    assert ids == [0, 1]
-    refused_both(L, 3, E.InvalidAccess)
-    check_gram(frames, ids, what="two frames")
-    # a box outside the frames, a zero extent
-    for box in (((0, 0, 0), (34, 1, 7)), ((1, 0, 0), (33, 1, 7)), ((0, 0, 7), (1, 1, 1)), ((0, 0, 0), (33, 0, 7)), ((0xFFFFFFFF, 0, 0), (2, 1, 1))):
-        refused_both(L, 2, E.InvalidAccess, bflib.frame_region(*box))
-    # frames of two grids, frames of two kinds on one grid
-    a, b, r = block("plane"), block("square"), block("real")
-    bflib.beamform(b.bp, rf_frames("square", 1)[0], b.filters)
-    refused_both(L, 2, E.DataSizeMismatch)
-    refused_both(L, 3, E.DataSizeMismatch)
-    bflib.beamform(a.bp, rf_frames("plane", 1)[0], a.filters)
-    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
-    refused_both(L, 2, E.DataSizeMismatch)
-    # a tombstone among the K: a variants push that fails at its DAS stage (das path flag 0x2000) leaves three, without any device fault
-    acq = metrics_block("A")
-    variants = vc.candidates(acq.bp)
-    bflib.beamform_variants(acq.bp, acq.rf, variants, acq.filters)
-    rf = np.ascontiguousarray(acq.rf)
-    L.beamformer_hip_set_das_path(P.HIP_DAS_PATH_FAIL_VIEWS_DAS)
-    assert not L.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, (P.HipDasVariant * 3)(*variants), 3, 0, 0)
-    L.beamformer_hip_set_das_path(0)
-    refused_both(L, 1, E.InvalidAccess)
-    refused_both(L, 4, E.InvalidAccess)
-    single = bflib.beamform(acq.bp, acq.rf, acq.filters).copy()
-    refused_both(L, 2, E.InvalidAccess)
-    check_gram(single[None], [int(newest_info(L).frame_id)], what="behind the tombstones")
-
-
-def test_several_devices_are_refused(bflib):
-    L = bflib.library()
-    acq = vc.separable_volume()
-    with two_contexts_on_device_0(bflib, acq):
-        refused_both(L, 1, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_gram(frames, ids, what="one device again")
-
-
-def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
-    """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/ensemble_wrap_worker.py"""
-    run_ring_worker("ensemble_wrap_worker", 1 << 20, expect=("refused",))

@@ -6,21 +6,15 @@ The bars are derived, not measured (tests/motion_ref.py returns them with the va
 is one rounding and the running sum `terms` more: (terms + 2) 2^-53 sum (|r| + |i|)(|r| + |i|) over the terms, the two factors those of
 the product.  `terms`, ids, grids and every zero the definition promises are asked exactly.  Every test prints what it measured before
 it asserts."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
 from tests import motion_ref as ref
-from tests import variants_cases as vc
-from tests.frame_info import newest_info
-from tests.ring_frames import block, BOXES, check_correlate as check_call, DOUBLES, ensemble, GRIDS, regions_of, rf_frames
-from tests.scaffold import automatic_path, two_contexts_on_device_0  # noqa: F401
+from tests.ring_frames import block, BOXES, check_correlate as check_call, DOUBLES, ensemble, GRIDS, regions_of
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
 NAN_POINTS = (24, 1, 40)
 INTERIOR = dict(BOXES, nan=((1, 0, 3), (21, 1, 35)))
 
@@ -175,65 +169,3 @@ def test_a_known_shift(bflib):
     print(f"  window {narrow}: shift {tuple(r['shift'])}, coefficient {float(r['coefficient'])!r}, at the edge {int(r['at_window_edge']):03b}")
     assert float(r["coefficient"]) < 0.99
     assert tuple(r["shift"]) == tuple(alone["shift"]) and int(r["at_window_edge"]) == int(alone["at_window_edge"])
-
-
-# ---- refusals that need a device ----
-
-def refused(L, kind, count, reference, window, regions=None):
-    """the call refuses with this error kind, writes nothing and queues nothing"""
-    room = max(1, (len(regions) if regions else 1) * count * int(np.prod([2 * s + 1 for s in window])))
-    table = np.full(min(room, 1 << 16) * 5, -7.0, np.float64)
-    untouched = table.tobytes()
-    info = P.HipCorrelationInfo()
-    C.memset(C.byref(info), 0x5A, C.sizeof(info))
-    ms = C.c_float(-1.0)
-    newest = int(newest_info(L).frame_id)
-    array = None if regions is None else (P.HipFrameRegion * len(regions))(*regions)
-    assert not L.beamformer_hip_correlate_last_frames(count, reference, array, 0 if regions is None else len(regions), (C.c_uint32 * 3)(*window),
-                                                      table.ctypes.data_as(C.POINTER(P.HipShiftCorrelation)), C.byref(info), C.byref(ms))
-    assert bf.last_error()[0] == kind, bf.last_error()
-    assert table.tobytes() == untouched and bytes(info) == b"\x5A" * C.sizeof(info) and ms.value == -1.0
-    assert int(newest_info(L).frame_id) == newest
-
-
-def test_refusals(bflib):
-    L = bflib.library()
-    # more frames asked for than were ever queued: a fresh context with two frames
-    L.beamformer_hip_shutdown()
-    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames, ids = ensemble("plane", 2)
-    assert ids == [0, 1]
-    window = (1, 0, 1)
-    refused(L, E.InvalidAccess, 3, 0, window)
-    check_call(frames, ids, 0, window, None, what="two frames")
-    # a region outside the frames, a zero extent, also behind a good region
-    good = bflib.frame_region((0, 0, 0), (33, 1, 7))
-    for box in (((0, 0, 0), (34, 1, 7)), ((1, 0, 0), (33, 1, 7)), ((0, 0, 7), (1, 1, 1)), ((0, 0, 0), (33, 0, 7)), ((0xFFFFFFFF, 0, 0), (2, 1, 1))):
-        refused(L, E.InvalidAccess, 2, 0, window, [bflib.frame_region(*box)])
-        refused(L, E.InvalidAccess, 2, 0, window, [good, bflib.frame_region(*box)])
-    check_call(frames, ids, 1, window, [((0, 0, 0), (33, 1, 7))], what="behind the boxes")
-    # the reference is one of the frames
-    refused(L, E.InvalidAccess, 2, 2, window)
-    check_call(frames, ids, 0, window, None, what="behind the refusals")
-    # frames of two grids
-    b = block("square")
-    bflib.beamform(b.bp, rf_frames("square", 1)[0], b.filters)
-    refused(L, E.DataSizeMismatch, 2, 0, window)
-    # the entry cap with everything else in order: 17 frames x 1089 shifts x 57 regions = 1055241 > 2^20, x 56 = 1036728 is legal
-    frames, ids = ensemble("plane", 17)
-    wide = (16, 0, 16)
-    refused(L, E.BufferOverflow, 17, 0, wide, [good] * 57)
-    refused(L, E.BufferOverflow, 17, 0, wide, [good] * 256)
-    many, info, ms = bflib.correlate_last_frames(17, 0, wide, [good] * 56)
-    single, _, _ = check_call(frames, ids, 0, wide, [((0, 0, 0), (33, 1, 7))], what="behind the cap")
-    print(f"  56 regions x 17 frames x 1089 shifts: {ms * 1e3:.1f} us")
-    assert many.shape[0] == 56 and int(info.region_count) == 56 and all(many[r].tobytes() == single[0].tobytes() for r in (0, 1, 55))
-
-
-def test_several_devices_are_refused(bflib):
-    L = bflib.library()
-    acq = vc.separable_volume()
-    with two_contexts_on_device_0(bflib, acq):
-        refused(L, E.InvalidAccess, 1, 0, (1, 1, 1))
-    frames, ids = ensemble("plane", 2)
-    check_call(frames, ids, 1, (1, 0, 1), None, what="one device again")

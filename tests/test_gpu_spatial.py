@@ -8,23 +8,18 @@ frames.
 The bar is derived, not measured: tests/spatial_ref.py returns it with the values and its docstring has the derivation.  Ids, grids,
 kinds, tags, finite masks and every case the definition makes exact are asked exactly.  Every test prints what it measured -- the worst
 error as a share of its bound -- before it asserts."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ogl_beamforming_amd import lib as bf
-from ogl_beamforming_amd import params as P
 from tests import frame_peaks_ref
 from tests import spatial_ref as ref
-from tests import variants_cases as vc
-from tests.frame_info import newest_id, newest_info
-from tests.ring_frames import (block, spatial_block_of as block_of, burst_info_unchanged, check_peaks as check_call, check_convolve, ensemble,
-                               loop_case, metrics_block, NORMALISED, rf_frames, SPATIAL_ZERO as ZERO)
-from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
+from tests.frame_info import newest_info
+from tests.ring_frames import (spatial_block_of as block_of, burst_info_unchanged, check_peaks as check_call, check_convolve, ensemble,
+                               loop_case, NORMALISED, SPATIAL_ZERO as ZERO)
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
 
 
 def frames_of(which, K):
@@ -275,79 +270,3 @@ def test_the_doppler_loop_with_the_box_average_of_the_lag_frames(bflib):
     # the Kasai angle of the averaged lag 1 is smoother than that of the raw one: what the average is for
     rough, smooth = np.angle(lags[1]), np.angle(averaged[1])
     assert np.abs(np.diff(smooth, axis=2)).mean() < np.abs(np.diff(rough, axis=2)).mean()
-
-
-# ---- refusals that need frames ----
-
-def refused(L, K, taps, mode, kind):
-    """the call refuses with this error kind, writes nothing and queues nothing: the newest id stays, and the frame pushed next lies
-    where it would have lain (the ring's next offset is unchanged)"""
-    first, ms = C.c_uint32(77), C.c_float(-1.0)
-    newest = newest_id(L)
-    before = bytes(newest_info(L)) if newest is not None and L.beamformer_hip_get_device_count() == 1 else None
-    arrays = [None if h is None else np.ascontiguousarray(h, np.float32) for h in taps]
-    pointers = (C.POINTER(C.c_float) * 3)(*[None if h is None else h.ctypes.data_as(C.POINTER(C.c_float)) for h in arrays])
-    counts = (C.c_uint32 * 3)(*[0 if h is None else len(h) for h in arrays])
-    assert not L.beamformer_hip_convolve_last_frames(K, pointers, counts, mode, 0, C.byref(first), C.byref(ms))
-    assert bf.last_error()[0] == kind and first.value == 77 and ms.value == -1.0
-    assert newest_id(L) == newest
-    if before is not None:
-        assert bytes(newest_info(L)) == before
-        old = newest_info(L)
-        acq = block("plane")
-        bf.beamform(acq.bp, rf_frames("plane", 1)[0], acq.filters)
-        new = newest_info(L)
-        assert int(new.frame_id) == int(old.frame_id) + 1
-        assert int(new.device_pointer) == int(old.device_pointer) + (int(old.size_bytes) + 63) // 64 * 64
-
-
-def test_refusals(bflib):
-    L = bflib.library()
-    v, r = block("volume"), block("real")
-    box = [np.full(3, 1 / 3, np.float32), None, np.full(3, 1 / 3, np.float32)]
-    # frames of two grids
-    ensemble("plane", 2)
-    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
-    refused(L, 2, box, ZERO, E.DataSizeMismatch)
-    # frames of two kinds on one grid (the push inside refused() left a complex plane behind)
-    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
-    refused(L, 2, box, NORMALISED, E.DataSizeMismatch)
-    # a negative tap in Normalised mode, with frames that Zero mode takes
-    frames, ids = ensemble("plane", 3)
-    refused(L, 3, [np.array([0.5, -0.25, 0.5], np.float32), None, None], NORMALISED, E.InvalidAccess)
-    frames, ids = ensemble("plane", 3)
-    check_convolve("plane", frames, ids, [np.array([0.5, -0.25, 0.5], np.float32), None, None], ZERO, what="the same taps, zero mode")
-    # a tombstone among the K: a variants push that fails at its DAS stage (das path flag 0x2000) leaves three, without any device fault
-    acq = metrics_block("A")
-    variants = vc.candidates(acq.bp)
-    bflib.beamform_variants(acq.bp, acq.rf, variants, acq.filters)
-    rf = np.ascontiguousarray(acq.rf)
-    L.beamformer_hip_set_das_path(P.HIP_DAS_PATH_FAIL_VIEWS_DAS)
-    assert not L.beamformer_hip_push_data_variants_with_compute(rf.ctypes.data_as(C.c_void_p), rf.nbytes, (P.HipDasVariant * 3)(*variants), 3, 0, 0)
-    L.beamformer_hip_set_das_path(0)
-    refused(L, 1, box, ZERO, E.InvalidAccess)
-    refused(L, 4, box, ZERO, E.InvalidAccess)
-    # more frames than are there: a fresh context with two
-    L.beamformer_hip_shutdown()
-    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames, ids = ensemble("plane", 2)
-    assert ids == [0, 1]
-    refused(L, 3, box, ZERO, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_convolve("plane", frames, ids, box, NORMALISED, what="two frames")
-
-
-def test_several_devices_are_refused(bflib):
-    L = bflib.library()
-    acq = vc.separable_volume()
-    box = [np.full(3, 1 / 3, np.float32)] * 3
-    with two_contexts_on_device_0(bflib, acq):
-        refused(L, 1, box, ZERO, E.InvalidAccess)
-        refused(L, 1, box, NORMALISED, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_convolve("plane", frames, ids, box[:1] + [None, box[2]], what="one device again")
-
-
-def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
-    """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/spatial_wrap_worker.py"""
-    run_ring_worker("spatial_wrap_worker", 1 << 20, expect=("refused", "wrapped"))

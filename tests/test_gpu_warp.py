@@ -13,21 +13,17 @@ kinds, tags and every case the definition makes exact are asked exactly.  Every 
 share of its bound -- before it asserts.
 
 WORST SHARE of the bound over this file on an MI355X: see DESIGN.md 3.7g."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ogl_beamforming_amd import lib as bf
 from ogl_beamforming_amd import params as P
-from tests import variants_cases as vc
 from tests import warp_ref as ref
-from tests.frame_info import newest_id, newest_info
-from tests.ring_frames import block, warp_block_of as block_of, check_warp, CLAMP, CUBIC, ensemble, LINEAR, OWN, rf_frames, WARP_ZERO as ZERO
-from tests.scaffold import automatic_path, run_ring_worker, two_contexts_on_device_0  # noqa: F401
+from tests.frame_info import newest_info
+from tests.ring_frames import warp_block_of as block_of, check_warp, CLAMP, CUBIC, ensemble, LINEAR, OWN, WARP_ZERO as ZERO
+from tests.scaffold import automatic_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E = P.LibError
 MODES = [(LINEAR, ZERO), (LINEAR, CLAMP), (CUBIC, ZERO), (CUBIC, CLAMP)]
 GRIDS = ["plane", "square", "volume", "real", "nan", "deep", "wide"]
 
@@ -326,68 +322,3 @@ def test_the_outputs_are_ordinary_frames(bflib):
     values = [ref.warp(frames[n], case["field"][n]) for n in range(3)]
     got = bflib.get_last_frames(block_of("square").bp, 3)
     assert all(ref.share_of_bound(got[n], *values[n])[1] for n in range(3))
-
-
-def refused(L, K, case, kind, rotations=None):
-    """the call refuses with this error kind, writes nothing and queues nothing: the newest id stays, and the frame pushed next lies
-    where it would have lain (the ring's next offset is unchanged)"""
-    first, ms = C.c_uint32(77), C.c_float(-1.0)
-    newest = newest_id(L)
-    before = bytes(newest_info(L)) if newest is not None and L.beamformer_hip_get_device_count() == 1 else None
-    floats = C.POINTER(C.c_float)
-    field = np.ascontiguousarray(case["field"], np.float32)
-    rot = None if rotations is None else np.ascontiguousarray(rotations, np.complex64)
-    assert not L.beamformer_hip_warp_last_frames(K, field.ctypes.data_as(floats), (C.c_uint32 * 3)(*case["nodes"]), (C.c_float * 3)(*case["node_first"]),
-                                                 (C.c_float * 3)(*case["node_step"]), None if rot is None else rot.ctypes.data_as(floats), 0, 0, 0,
-                                                 C.byref(first), C.byref(ms))
-    assert bf.last_error()[0] == kind and first.value == 77 and ms.value == -1.0
-    assert newest_id(L) == newest
-    if before is not None:
-        assert bytes(newest_info(L)) == before
-        old = newest_info(L)
-        acq = block("plane")
-        bf.beamform(acq.bp, rf_frames("plane", 1)[0], acq.filters)
-        new = newest_info(L)
-        assert int(new.frame_id) == int(old.frame_id) + 1
-        assert int(new.device_pointer) == int(old.device_pointer) + (int(old.size_bytes) + 63) // 64 * 64
-
-
-def test_refusals_with_frames_present(bflib):
-    L = bflib.library()
-    v, r = block("volume"), block("real")
-    still = dict(field=np.zeros((4, 1, 1, 1, 3), np.float32), nodes=(1, 1, 1), node_first=(0, 0, 0), node_step=(1, 1, 1))
-    # frames of two grids
-    ensemble("plane", 2)
-    bflib.beamform(v.bp, rf_frames("volume", 1)[0], v.filters)
-    refused(L, 2, still, E.DataSizeMismatch)
-    # frames of two kinds on one grid (the push inside refused() left a complex plane behind)
-    bflib.beamform(r.bp, rf_frames("real", 1)[0], r.filters)
-    refused(L, 2, still, E.DataSizeMismatch)
-    # an imaginary rotation on real frames; the same call with real factors runs
-    frames, ids = ensemble("real", 3)
-    refused(L, 3, still, E.InvalidAccess, rotations=[1, 1 + 1e-30j, 1])
-    frames, ids = ensemble("real", 3)
-    check_warp("real", frames, ids, dict(still, field=still["field"][:3]), np.array([1, -2, 0.5], np.complex64), what="real factors")
-    # more frames than are there: a fresh context with two
-    L.beamformer_hip_shutdown()
-    assert L.beamformer_hip_set_devices((C.c_int32 * 1)(0), 1)
-    frames, ids = ensemble("plane", 2)
-    assert ids == [0, 1]
-    refused(L, 3, still, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_warp("plane", frames, ids, dict(still, field=still["field"][:2]), what="two frames")
-
-
-def test_several_devices_are_refused(bflib):
-    L = bflib.library()
-    acq = vc.separable_volume()
-    still = dict(field=np.zeros((1, 1, 1, 1, 3), np.float32), nodes=(1, 1, 1), node_first=(0, 0, 0), node_step=(1, 1, 1))
-    with two_contexts_on_device_0(bflib, acq):
-        refused(L, 1, still, E.InvalidAccess)
-    frames, ids = ensemble("plane", 2)
-    check_warp("plane", frames, ids, dict(still, field=np.zeros((2, 1, 1, 1, 3), np.float32)), what="one device again")
-
-
-def test_the_ring_a_run_that_wraps_and_one_that_would_reuse_its_sources():
-    """a 1 MiB frame ring in a process of its own (the ring is sized once per process): tests/warp_wrap_worker.py"""
-    run_ring_worker("warp_wrap_worker", 1 << 20, expect=("refused", "wrapped"))
